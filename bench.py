@@ -28,6 +28,10 @@ direct stores with --transport ipc --, interior rows on the caller's stream); to
 carries the 128-byte ring id, the barriers and the MAX reductions.  `--share-gpu` rehearses the N-rank
 run on ONE device (every rank on GPU 0, peer-mapped transport, gloo control plane): plumbing, not a number.
 
+--dump-outputs DIR (N = 1): the last timed batch restarts from the Taylor-Green state and the populations it leaves are
+written to DIR/f.npy (f64, [9, nodes]; a fixed seeded sample of nodes on large lattices), so that two builds of the
+project can be compared output for output.
+
 N = 1 adds `secondary`: BASELINE configs 3, 4, 5 (KBC 4096^2, two-phase 8192x2048, BGK + immersed
 cylinder 16384x4096) timed after the headline, each with a roofline built the same way.
 
@@ -997,12 +1001,15 @@ def run_secondary(lib, dev, which, a):
     return out
 
 
-def timed_batches(box, steps, repeats, ctl):
+def timed_batches(box, steps, repeats, ctl, before_last=None):
     """`repeats` batches of exactly `steps` steps, each bracketed by barrier + synchronize; returns
-    per-repeat (wall seconds, device ms between HIP events on the launch stream), MAX over ranks."""
+    per-repeat (wall seconds, device ms between HIP events on the launch stream), MAX over ranks.
+    `before_last`, if given, runs ahead of the last batch, outside its bracket."""
     torch = box.torch
     wall, devms, enq = [], [], []
-    for _ in range(repeats):
+    for i in range(repeats):
+        if before_last and i == repeats - 1:
+            before_last()
         torch.cuda.synchronize()
         ctl.barrier()
         torch.cuda.synchronize()
@@ -1067,7 +1074,30 @@ def parse_args(argv):
     ap.add_argument("--no-power", action="store_true", help="skip the rocm-smi clock / power samples beside the workloads")
     ap.add_argument("--secondary-steps", type=int, default=30, help="time steps per timed batch of a secondary workload")
     ap.add_argument("--secondary-only", action="store_true", help="skip the headline (profiling passes)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: write the populations the last timed batch computed to DIR/f.npy (the batch starts from "
+                         "the initial state; a fixed sample of nodes on large lattices)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.gpus != 1 or a.secondary_only):
+        ap.error("--dump-outputs needs the headline on one GPU (--gpus 1, no --secondary-only)")
+    return a
+
+
+DUMP_MAX_NODES = 1 << 19     # x 9 f64 populations = 36 MiB: --dump-outputs stays below 64 MB
+
+
+def dump_outputs(box, out_dir):
+    """f [9, nodes] f64, the box's populations in SoA order after its last launch: every node of a lattice of at most
+    DUMP_MAX_NODES, else the same seeded sample of row-major node indices (sorted) for a given lattice size."""
+    import numpy as np
+    n = box.R * box.C
+    f = box.owned().reshape(9, n)
+    if n > DUMP_MAX_NODES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_NODES, replace=False))
+        f = f.index_select(1, box.torch.from_numpy(idx).to(f.device))
+    np.save(os.path.join(out_dir, "f.npy"), f.contiguous().cpu().numpy())
 
 
 def main(argv=None):
@@ -1083,6 +1113,8 @@ def main(argv=None):
             with open(a.status_file, "a") as fh:
                 fh.write(word + "\n")
     stage("start")
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
     stall = os.environ.get("LBM_BENCH_STALL")      # fault injection (tests): "rank:attempt" never brings its ring up
     if stall and a.worker and stall == f"{os.environ.get('RANK', '0')}:{a.attempt}":
         time.sleep(3600)
@@ -1167,7 +1199,15 @@ def main(argv=None):
     if repeats <= 0:
         w1, _, _ = timed_batches(box, a.steps, 1, ctl)        # pilot batch (also warm-up)
         repeats = max(5, min(25, int(2.5 / max(w1[0], 1e-6))))
-    wall, devms, enq = timed_batches(box, a.steps, repeats, ctl)
+    restart = None
+    if a.dump_outputs:
+        # the warm-up and the repeat count follow the clock: the dumped batch restarts from the initial state, so that
+        # what it computes depends on the arguments alone
+        def restart():
+            box.load(taylor_green(lib, torch, _ptr, R, C, rank * R, world * R, dev))
+    wall, devms, enq = timed_batches(box, a.steps, repeats, ctl, restart)
+    if a.dump_outputs:
+        dump_outputs(box, a.dump_outputs)
     order = sorted(range(repeats), key=lambda i: wall[i])
     mid = order[repeats // 2]
     dt, dev_ms = wall[mid], devms[mid]

@@ -29,13 +29,3 @@ def relerr(a, b):
 def oracle():
     from pyoracle import Oracle
     return Oracle()
-
-
-@pytest.fixture(scope="session")
-def ref():
-    """The unmodified reference on CPU libtorch; only where oracle/_ref has been built."""
-    import torch  # noqa: F401  (loads libtorch for the .so)
-    from pyoracle import Ref
-    if not Ref.available():
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    return Ref()

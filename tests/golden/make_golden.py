@@ -12,6 +12,7 @@ Sources of each fixture
   dsf_128.npz       test/ulbm_double_shear_flow.cpp      main(), unmodified (oracle/_ref/dsf)
   kbc_units.npz     ulbm::d2q9::kbc collide/advect via ref_capi.cpp
   diff5.npz         differential::x / ::y via ref_capi.cpp
+  ref_recheck_29x41.npz  solver::advect, the BGK periodic loop and differential::x on one random state
   upo_units.npz     the loop of test/ulbm_poiseuille.cpp on the reference's own kbc class and
                     solver::incomp_equilibrium, sequenced by ref_capi.cpp (ref_upo_steps)
   ddl_512.npz       test/decompose_domain_loop.cpp main(), unmodified (oracle/_ref/ddl): 50000 steps, ~25 min
@@ -206,6 +207,19 @@ def gen_diff(r):
          lin_dy=r.diff_y(lin))
 
 
+def gen_ref_recheck(r):
+    """test_oracle_golden.py::test_oracle_against_live_reference: odd-sized random state, omega 1.7, 25 steps"""
+    rng = np.random.default_rng(11)
+    R, C = 29, 41
+    rho = 1 + 0.02 * rng.standard_normal((R, C))
+    u = 0.04 * rng.standard_normal((R, C, 2))
+    f = r.equilibrium(u, rho) * (1 + 0.02 * rng.standard_normal((R, C, 9)))
+    psi = rng.standard_normal((R, C))
+    bf, brho, bu = r.bgk_periodic_steps(f, 1.7, 25)
+    save("ref_recheck_29x41.npz", f_in=f, psi=psi, advect=r.advect(f), bgk25_f=bf, bgk25_rho=brho, bgk25_u=bu,
+         diff_x=r.diff_x(psi))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-dsf", action="store_true", help="skip the ~minutes-long shear-flow run")
@@ -225,6 +239,7 @@ if __name__ == "__main__":
     gen_solver_units(r, o)
     gen_kbc(r, o)
     gen_diff(r)
+    gen_ref_recheck(r)
     gen_hpt()
     gen_ddm()
     gen_gt()

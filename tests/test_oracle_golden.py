@@ -115,19 +115,22 @@ def test_differential(oracle):
     assert np.allclose(oracle.diff_y(g["lin"])[2:-2, 2:-2], 1.0, rtol=1e-13)
 
 
-def test_oracle_against_live_reference(oracle, ref):
-    """Where oracle/_ref exists (build container), re-check on fresh random inputs."""
-    rng = np.random.default_rng(11)
-    R, C = 29, 41
-    rho = 1 + 0.02 * rng.standard_normal((R, C))
-    u = 0.04 * rng.standard_normal((R, C, 2))
-    f = ref.equilibrium(u, rho) * (1 + 0.02 * rng.standard_normal((R, C, 9)))
-    assert np.array_equal(oracle.advect(f), ref.advect(f))
+def test_oracle_against_live_reference(oracle):
+    """Random odd-sized inputs (29 x 41, omega 1.7, 25 steps) against what the unmodified reference computed from
+    them: the stored outputs (ref_recheck_29x41.npz) always, and the live reference too where oracle/_ref is built."""
+    from pyoracle import Ref
+    g = golden("ref_recheck_29x41.npz")
+    f, psi = g["f_in"], g["psi"]
+    wants = [(g["advect"], (g["bgk25_f"], g["bgk25_rho"], g["bgk25_u"]), g["diff_x"])]
+    if Ref.available():
+        import torch  # noqa: F401  (loads libtorch for the .so)
+        ref = Ref()
+        wants.append((ref.advect(f), ref.bgk_periodic_steps(f, 1.7, 25), ref.diff_x(psi)))
     a = oracle.bgk_periodic_steps(f, 1.7, 25)
-    b = ref.bgk_periodic_steps(f, 1.7, 25)
-    assert all(relerr(x, y) < 1e-12 for x, y in zip(a, b))
-    psi = rng.standard_normal((R, C))
-    assert relerr(oracle.diff_x(psi), ref.diff_x(psi)) < 1e-14
+    for adv, b, dx in wants:
+        assert np.array_equal(oracle.advect(f), adv)
+        assert all(relerr(x, y) < 1e-12 for x, y in zip(a, b))
+        assert relerr(oracle.diff_x(psi), dx) < 1e-14
 
 
 def sbt_constants(H=51, W=51):
