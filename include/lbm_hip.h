@@ -334,11 +334,16 @@ int lbm_cg_step_fused(double* pn_r, double* pn_b, const double* p_r, const doubl
                       const lbm_geom* g, const lbm_bc* bc, const lbm_cg_params* prm, int row_begin,
                       int row_end, double* rho_r, double* rho_b, double* u, double* psi, double* s_nu,
                       lbm_stream_t s);
-/* the same step as TWO launches for a slab whose neighbours wait for its edge rows: LBM_CG_PART_FRAME = the boundary-gather
- * instantiation on the frame of the lattice widened to the first and last `edge_rows` rows (whole tiles of 16 rows),
- * LBM_CG_PART_INNER = everything else through the plain-offset inner kernel.  The parts write disjoint nodes and may run
- * on two streams at once (lbm_ring_cg_step: frame, pack and exchange on the ring's stream beside the inner launch);
- * together they are lbm_cg_step_fused on [0, R), bit for bit (test/mrtcg_rayleigh_taylor.cpp:431-477 per node). */
+/* the same step as TWO launches for a slab whose neighbours wait for its edge rows.  The nodes each part writes (both
+ * colours, all 9 planes; the field outputs at the same nodes):
+ *   LBM_CG_PART_INNER: one rectangle of whole 16 x 32 tiles through the plain-offset inner kernel, inside rows
+ *     [edge_rows, R - edge_rows) and away from the wall rows and the wall / copy columns -- possibly empty;
+ *   LBM_CG_PART_FRAME: every other node of [0, R) x [0, C) through the boundary-gather instantiation, so ALWAYS every node
+ *     of rows [0, edge_rows) and [R - edge_rows, R) and of columns 0 and C - 1, whatever R % 16 is.
+ * Neither writes a ghost row, the row-pitch padding or the plane padding.  The parts are disjoint and may run on two
+ * streams at once (lbm_ring_cg_step: frame, pack and exchange on the ring's stream beside the inner launch); together
+ * they are lbm_cg_step_fused on [0, R), bit for bit (test/mrtcg_rayleigh_taylor.cpp:431-477 per node).
+ * tests/test_gpu_write_sets.py pins both sets. */
 #define LBM_CG_PART_FRAME 1
 #define LBM_CG_PART_INNER 2
 int lbm_cg_step_fused_part(double* pn_r, double* pn_b, const double* p_r, const double* p_b,

@@ -84,8 +84,8 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
                              const Geom& g, const Bc& bc, const CgFast& cf, double* rho_r,
                              double* rho_b, double* u, double* psi, double* snu, const MacroIdx& mi,
                              int row_begin, int row_end, hipStream_t st, int part = 0, int edge_rows = 0) {
-  // part 0: the whole row range (frame beside the inner launch on a helper stream); 1 / 2: ONLY the frame -- widened to the
-  // first and last `edge_rows` rows of the range, in whole tiles -- / ONLY the inner rectangle, on `st`: a slab runs the
+  // part 0: the whole row range (frame beside the inner launch on a helper stream); 1 / 2: ONLY the frame -- widened to
+  // every node of the first and last `edge_rows` rows of the range -- / ONLY the inner rectangle, on `st`: a slab runs the
   // two on two streams and sends its edge rows while the inner launch is still busy (lbm_cg_step_fused_part)
   const int tiles_r = (row_end - row_begin + TR - 1) / TR, tiles_c = (g.C + TC - 1) / TC;
   const int tiles = tiles_r * tiles_c;
@@ -106,9 +106,12 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
   rc.ic1 = (g.C - 3) / TC;  // last tile column with c_base + TC + 1 <= C - 2
   if (rc.ic1 > tiles_c) rc.ic1 = tiles_c;
   if (part && edge_rows > 0) {
-    const int et = (edge_rows + TR - 1) / TR;
-    rc.ir0 = rc.ir0 > et ? rc.ir0 : et;
-    rc.ir1 = rc.ir1 < tiles_r - et ? rc.ir1 : tiles_r - et;
+    // clamp by rows counted from row_begin, not by tiles counted back from the last one: that tile may be partial, and
+    // tiles_r - ceil(edge_rows / TR) would leave up to TR - 1 of the last edge_rows rows inside the inner rectangle
+    // (R = 130, edge_rows = 3: row 127).  Where TR divides the height the two bounds agree.
+    const int first = (edge_rows + TR - 1) / TR, last = (row_end - row_begin - edge_rows) / TR;
+    rc.ir0 = rc.ir0 > first ? rc.ir0 : first;
+    rc.ir1 = rc.ir1 < last ? rc.ir1 : last;
   }
   bool split = (part || tuning("cg_split", 1) != 0) && rc.ir1 - rc.ir0 >= 1 && rc.ic1 - rc.ic0 >= 1;
   g_last_inner_form = 0;

@@ -359,7 +359,7 @@ def test_cg_strip_kernel_equals_tile_kernel(lib, oracle, R, C):
             assert torch.equal(val[k], ref[k]), (key, k, float((val[k] - ref[k]).abs().max()))
 
 
-@pytest.mark.parametrize("R,C,edge", [(256, 200, 16), (130, 1040, 3), (64, 32, 16), (200, 544, 40)])
+@pytest.mark.parametrize("R,C,edge", [(256, 200, 16), (130, 1040, 3), (64, 32, 16), (200, 544, 40), (130, 64, 16), (2050, 64, 3)])
 def test_cg_step_in_two_parts_equals_one_call(lib, oracle, R, C, edge):
     """lbm_cg_step_fused_part: FRAME (boundary-gather kernel on the lattice's frame widened to the first / last `edge` rows)
     + INNER (plain-offset kernel on the rest) write disjoint nodes and are together lbm_cg_step_fused on [0, R) -- on a

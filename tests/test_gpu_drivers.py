@@ -188,6 +188,19 @@ def test_slab_ring_rt_emulated_chain_of_four_slabs(tmp_path):
     assert line["check"] == "bitwise equal to one block" and line["slabs"] == 4 and line["message_rows_per_colour_and_side"] == 21
 
 
+@pytest.mark.parametrize("rows,edge", [(50, 16), (130, 3)])
+def test_slab_ring_rt_emulated_chain_with_partial_tiles(tmp_path, rows, edge):
+    """slab heights 16 does not divide, with edge rows that reach into the last, partial tile row (50 % 16 = 2 < 16,
+    130 % 16 = 2 < 3): the frame part must still compute every edge row the messages carry; == the single block bit for bit"""
+    import json
+    exe = os.path.join(BIN, "slab_ring_rt")
+    r = subprocess.run([exe, "--emulate", "3", "--rows", str(rows), "--cols", "200", "--steps", "7", "--warmup", "2",
+                        "--edge-rows", str(edge), "--check", "1"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["check"] == "bitwise equal to one block" and line["slabs"] == 3
+
+
 def test_slab_ring_rt_with_row_padded_slabs(tmp_path):
     """1024 columns: slab_geom pads the rows of the slabs' lattices (lbm_default_row_pitch) -- init through
     lbm_lattice_copy_rows, ring pack / unpack, the two-part step and the check all on padded lattices; the emulated chain

@@ -146,8 +146,20 @@ def test_kbc_ring_across_processes_equals_one_block(lib, tmp_path, n, ghost, dep
 def test_cg_ring_across_processes_equals_one_block(lib, oracle, tmp_path, n):
     """lbm_ring_cg_step: the fused two-phase step on a CHAIN of slabs (3 ghost rows, both colours in one message);
     mrtcg_rayleigh_taylor.cpp:413-478 with its walls (:495-533) on the outer slabs"""
+    cg_ring_vs_one_block(lib, oracle, tmp_path, n, 48, 64, 16)
+
+
+@pytest.mark.parametrize("R,edge", [(50, 3), (50, 16), (130, 3), (130, 16)])
+@pytest.mark.parametrize("n", [2, 3])
+def test_cg_ring_with_partial_tile_slabs_equals_one_block(lib, oracle, tmp_path, n, R, edge):
+    """the same on slab heights 16 does not divide (R % 16 = 2), 200 columns: wide enough for an inner rectangle, so the
+    frame part and the inner part really run on two streams, and the frame must hold every edge row the exchange packs"""
+    cg_ring_vs_one_block(lib, oracle, tmp_path, n, R, 200, edge)
+
+
+def cg_ring_vs_one_block(lib, oracle, tmp_path, n, R, C, edge):
     import pyoracle
-    R, C, steps = 48, 64, 9
+    steps = 9
     Rg = R * n
     s0 = oracle.cg_init(pyoracle.cg_params(Rg, C))
     pg = pylbm.cg_params()
@@ -167,7 +179,7 @@ def test_cg_ring_across_processes_equals_one_block(lib, oracle, tmp_path, n):
                           None, None, None, None, None, None)
         a, b = b, a
     torch.cuda.synchronize()
-    outs = run_ranks(lib, tmp_path, "cg", n, dict(R=R, C=C, steps=steps), dict(p0r=p0[0], p0b=p0[1]))
+    outs = run_ranks(lib, tmp_path, "cg", n, dict(R=R, C=C, steps=steps, edge_rows=edge), dict(p0r=p0[0], p0b=p0[1]))
     for k, key in ((0, "Pr"), (1, "Pb")):
         got = np.concatenate([o[key] for o in outs], axis=1)
         assert bits_equal(got, a[k].cpu().numpy()), (key, ulp_diff(got, a[k].cpu().numpy()))
