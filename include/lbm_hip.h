@@ -455,6 +455,54 @@ int lbm_solver_attach_ibm(lbm_solver* sv, lbm_ibm* ib, double guo_a, double guo_
  * that drive lbm_*_stream_collide themselves (benchmarks, multi-GPU slabs) */
 int lbm_solver_lattices(lbm_solver* sv, double** cur, double** other, lbm_geom* geom /* may be NULL */);
 
+/* ---- fluid + transported scalar (advection-diffusion; test/rectangle_sedimentation_test.cpp:88-247) -------
+ * A second D2Q9 distribution g carried with a compressible BGK fluid f: the scalar's equilibrium is
+ * solver::equilibrium(g_equi, u + w, C) with C = calc_rho(g) and u the fluid's velocity (:125), it relaxes with its
+ * own BGK rate (:132) and streams like f (:145-146).  Dye, temperature as a passive scalar, sediment.
+ * One fused pull step per node streams both post-collision lattices, forms rho, u from f and C from g, collides both
+ * and writes both (288 B per node update).  Single block (ghost = 0), C even.  Edges: PERIODIC or BOUNCE_BACK rows,
+ * PERIODIC, BOUNCE_BACK or SPECULAR columns; g takes exactly the fix-up f takes at a wall, on its own post-collision
+ * populations -- a no-flux wall (the driver's bottom wall, :234-236 = :180-182).  Everything else (HALO, ABB_VELOCITY,
+ * WRAP_NOSHIFT, pressure rows, ghost rows) is refused on the host.  The fluid parameters must be the plain
+ * compressible model: incompressible = delta_form = force_mode = 0.  Both halves run in the form of `scalar->form`
+ * (LBM_FORM_DEFAULT resolves through "bgk_fast" as for BGK): REFERENCE_ORDER = solver.cpp's operation order, the fluid
+ * half bitwise equal to lbm_bgk_stream_collide; REASSOCIATED = BgkFastModel for f and its counterpart for g. */
+typedef struct lbm_ade_params {
+  double omega_g;  /* scalar relaxation rate; the driver uses lp.omega / Sc with Sc = 1 (:132) */
+  double w_r, w_c; /* velocity added to u in the scalar's equilibrium; the driver adds w_s to BOTH components (:125) */
+  int form;        /* LBM_FORM_*, both halves */
+} lbm_ade_params;
+/* collide only (the first iteration, like lbm_bgk_collide): post-collision fp, gp from pre-collision f, g_in; in
+ * place allowed.  rho [R][C], u [2][R][C], conc [R][C] (dense; all or none may be NULL) receive the moments. */
+int lbm_ade_collide(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                    const lbm_bgk_params* fluid, const lbm_ade_params* scalar, double* rho, double* u, double* conc,
+                    lbm_stream_t s);
+/* the fused step on rows [row_begin, row_end): (fn, gn) = collide(stream(fo, go)), wall fix-ups included; one launch,
+ * two with wall edges (interior + edge pass).  Lattices distinct and 16-byte aligned, row pitch and plane stride even.
+ * rho, u, conc (all or none may be NULL): the moments of the streamed state. */
+int lbm_ade_stream_collide(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                           const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int row_begin,
+                           int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
+/* driver loop context (single block; g->row_pitch and g->plane_stride 0: the context pads its own lattices).
+ * set_state takes f_adve, g_adve (host AoS [R][C][9]); step(n) runs n driver iterations, enqueueing only (no
+ * allocation, no host synchronisation: a created stream can capture it, lbm_graph_*); get_state returns what the
+ * reference loop holds after them: f_adve, g_adve, rho = calc_rho(f_adve), u = calc_u(f_adve, rho) (AoS [R][C][2]),
+ * C = calc_rho(g_adve) -- any output may be NULL; synchronises. */
+typedef struct lbm_ade_solver lbm_ade_solver;
+int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc /* NULL = periodic */,
+                          const lbm_bgk_params* fluid, const lbm_ade_params* scalar, lbm_stream_t s);
+int lbm_ade_solver_destroy(lbm_ade_solver* sv);
+int lbm_ade_solver_set_state(lbm_ade_solver* sv, const double* f_host, const double* g_host);
+int lbm_ade_solver_step(lbm_ade_solver* sv, int n_steps);
+int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f_host, double* g_host, double* rho_host, double* u_host,
+                             double* conc_host);
+int lbm_ade_solver_sync(lbm_ade_solver* sv);
+/* device pointers of the resident lattices (current post-collision state, scratch) and their padded geometry */
+int lbm_ade_solver_lattices(lbm_ade_solver* sv, double** f_cur, double** g_cur, double** f_other, double** g_other,
+                            lbm_geom* geom /* may be NULL */);
+/* kernel launches lbm_ade_solver_step has enqueued so far; -1 for NULL */
+long long lbm_ade_solver_launches(const lbm_ade_solver* sv);
+
 /* ---- slab ring in C++: one process per GPU, packed halo messages between row slabs ------------------
  * Native counterpart of pylbm/slab.py (same kernels, same halo sets): edge rows + pack + ONE message
  * to and from each neighbour + unpack on the ring's own high-priority stream, interior rows on the

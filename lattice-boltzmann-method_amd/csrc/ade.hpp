@@ -1,0 +1,205 @@
+// Fluid + transported scalar (advection-diffusion) on one block: the sediment concentration g of
+// test/rectangle_sedimentation_test.cpp:88-247 carried with a compressible BGK fluid.  g is a second D2Q9
+// distribution with the equilibrium solver::equilibrium(g_equi, u + w_s, C), C = calc_rho(g), u the fluid's
+// velocity (:125), relaxed with its own BGK rate (:132) and streamed like f (:145).
+//
+// One fused pull step per node: stream both post-collision lattices (edge fix-ups included), form rho and u
+// from f and C from g, collide both, write both -- 18 loads and 18 stores of 8 bytes, 288 B per node update.
+#pragma once
+#include "d2q9.hpp"
+
+namespace lbm {
+
+// The scalar half in the REFERENCE order: solver::equilibrium (solver.cpp:51-62) and solver::collision
+// (:65-74) expression by expression with rho -> C and u -> (u_r + w_r, u_c + w_c); the sum u + w is formed
+// first, as the driver's torch expression `u + w_s` does.  Bitwise equal to the oracle's primitives.
+struct AdeModelRef {
+  double omega, wr, wc;
+  __device__ __forceinline__ void collide(double (&g)[Q], double ux, double uy, double& conc) const {
+    double jx, jy, e[Q];
+    BgkModel::moments(g, conc, jx, jy);  // calc_rho(g); the first moments are dead code
+    (void)jx;
+    (void)jy;
+    BgkModel::feq_comp(e, conc, ux + wr, uy + wc);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) g[q] = (1.0 - omega) * g[q] + omega * e[q];
+  }
+};
+
+// The scalar half REASSOCIATED, in the style of BgkFastModel: pairwise zeroth moment, equilibrium split into
+// its parts even / odd under c -> -c with omega folded into the weights, FMA contraction per expression.  No
+// reciprocal: the scalar equilibrium is linear in C.  Agreement with AdeModelRef to rounding.
+struct AdeFastModel {
+  double keep, ow0, ow1, ow5, wr, wc;
+  __host__ __device__ AdeFastModel(double om, double w_r, double w_c)
+      : keep(1.0 - om), ow0(om * (4.0 / 9.0)), ow1(om * (1.0 / 9.0)), ow5(om * (1.0 / 36.0)), wr(w_r), wc(w_c) {}
+  __device__ __forceinline__ void collide(double (&g)[Q], double ux, double uy, double& conc) const {
+#pragma clang fp contract(on)
+    conc = (g[0] + (g[1] + g[3])) + ((g[2] + g[4]) + ((g[5] + g[7]) + (g[6] + g[8])));
+    const double vx = ux + wr, vy = uy + wc;
+    const double us = vx + vy, ud = vx - vy;
+    const double base = 1.0 - 1.5 * (vx * vx + vy * vy);
+    const double r1 = ow1 * conc, r5 = ow5 * conc;
+    const double E1 = r1 * (base + 4.5 * vx * vx), E2 = r1 * (base + 4.5 * vy * vy);
+    const double E5 = r5 * (base + 4.5 * us * us), E6 = r5 * (base + 4.5 * ud * ud);
+    const double O1 = 3.0 * r1 * vx, O2 = 3.0 * r1 * vy, O5 = 3.0 * r5 * us, O8 = 3.0 * r5 * ud;
+    g[0] = keep * g[0] + (ow0 * conc) * base;
+    g[1] = keep * g[1] + (E1 + O1);
+    g[3] = keep * g[3] + (E1 - O1);
+    g[2] = keep * g[2] + (E2 + O2);
+    g[4] = keep * g[4] + (E2 - O2);
+    g[5] = keep * g[5] + (E5 + O5);
+    g[7] = keep * g[7] + (E5 - O5);
+    g[8] = keep * g[8] + (E6 + O8);
+    g[6] = keep * g[6] + (E6 - O8);
+  }
+};
+
+// the two collisions of one node: fluid first (its u feeds the scalar's equilibrium)
+template <class FM, class SM>
+__device__ __forceinline__ void ade_collide_node(double (&f)[Q], double (&h)[Q], const FM& fm, const SM& sm, double& rho,
+                                                 double& ux, double& uy, double& conc) {
+  fm.collide(f, rho, ux, uy);
+  sm.collide(h, ux, uy, conc);
+}
+
+// The 9 pulled populations of node pair (r, c), (r, c + 1) of one lattice, 16-byte accesses where the pair's
+// sources are column-aligned (q = 0, 1, 3) or lie inside the row (the +-1-column shifted reads, 8-byte aligned
+// 16-byte loads); the first and last pair of a row wrap per node.  k_stream_collide_v2's gather, for any lattice.
+template <bool NT>
+__device__ __forceinline__ void pull_pair(double (&a)[Q], double (&b)[Q], const double* __restrict__ po, const Geom& g,
+                                          long rm, long r0, long rp, int c) {
+  dbl2 v;
+  v = load2a<NT>(po + 0 * g.plane + r0 + c); a[0] = v.x; b[0] = v.y;
+  v = load2a<NT>(po + 1 * g.plane + rm + c); a[1] = v.x; b[1] = v.y;
+  v = load2a<NT>(po + 3 * g.plane + rp + c); a[3] = v.x; b[3] = v.y;
+  if (c > 0 && c + 2 < g.C) {
+    v = load2u<NT>(po + 2 * g.plane + r0 + c - 1); a[2] = v.x; b[2] = v.y;
+    v = load2u<NT>(po + 5 * g.plane + rm + c - 1); a[5] = v.x; b[5] = v.y;
+    v = load2u<NT>(po + 6 * g.plane + rp + c - 1); a[6] = v.x; b[6] = v.y;
+    v = load2u<NT>(po + 4 * g.plane + r0 + c + 1); a[4] = v.x; b[4] = v.y;
+    v = load2u<NT>(po + 7 * g.plane + rp + c + 1); a[7] = v.x; b[7] = v.y;
+    v = load2u<NT>(po + 8 * g.plane + rm + c + 1); a[8] = v.x; b[8] = v.y;
+  } else {
+    const int cm = wrap_col(g, c - 1), cp = wrap_col(g, c + 2);
+    a[2] = po[2 * g.plane + r0 + cm]; b[2] = po[2 * g.plane + r0 + c];
+    a[5] = po[5 * g.plane + rm + cm]; b[5] = po[5 * g.plane + rm + c];
+    a[6] = po[6 * g.plane + rp + cm]; b[6] = po[6 * g.plane + rp + c];
+    a[4] = po[4 * g.plane + r0 + c + 1]; b[4] = po[4 * g.plane + r0 + cp];
+    a[7] = po[7 * g.plane + rp + c + 1]; b[7] = po[7 * g.plane + rp + cp];
+    a[8] = po[8 * g.plane + rm + c + 1]; b[8] = po[8 * g.plane + rm + cp];
+  }
+}
+
+// Fused pull step of the pair, interior path: one thread updates two column-adjacent nodes of BOTH lattices
+// (36 loads of 8 bytes as 18 16-byte accesses, the same stores); rows wrap (single block).  Boundary fix-ups are
+// NOT applied here: k_ade_edge recomputes the wall nodes afterwards.  Requires C % 2 == 0, even row pitch and
+// plane stride, 16-byte aligned lattices.  Moments (optional, dense [R][C] / [2][R][C]) of the streamed state.
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS>
+__global__ __launch_bounds__(256) void k_ade_stream_collide(
+    double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
+    Geom g, FM fm, SM sm, int row_begin, int row_end, int tiles_per_row, double* __restrict__ rho_out,
+    double* __restrict__ u_out, double* __restrict__ c_out) {
+  const long items = (long)(row_end - row_begin) * tiles_per_row;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const int r = row_begin + (int)(it / tiles_per_row);
+    const int c = ((int)(it % tiles_per_row) * 256 + threadIdx.x) * 2;
+    if (c >= g.C) continue;
+    const long rm = g.at(wrap_row(g, r - 1), 0);  // source row of cx = +1 populations
+    const long r0 = g.at(r, 0);
+    const long rp = g.at(wrap_row(g, r + 1), 0);  // source row of cx = -1 populations
+    double fa[Q], fb[Q], ha[Q], hb[Q];            // f and g of node (r, c) and node (r, c + 1)
+    pull_pair<NT_LOAD>(fa, fb, fo, g, rm, r0, rp, c);
+    pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+    double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
+    ade_collide_node(fa, ha, fm, sm, rho_a, ux_a, uy_a, c_a);
+    ade_collide_node(fb, hb, fm, sm, rho_b, ux_b, uy_b, c_b);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    if (WITH_MOMENTS) {
+      const long o = (long)r * g.C + c;  // moment fields are dense
+      const long n = (long)g.R * g.C;
+      store2<false>(rho_out + o, rho_a, rho_b);
+      store2<false>(u_out + o, ux_a, ux_b);
+      store2<false>(u_out + n + o, uy_a, uy_b);
+      store2<false>(c_out + o, c_a, c_b);
+    }
+  }
+}
+
+// Edge pass: the wall nodes of rows [row_begin, row_end) recomputed with the wall gather on both lattices,
+// overwriting what the interior launch stored for them.  g takes exactly the fix-up f takes at that edge,
+// applied to its own post-collision populations (the driver's no-flux bottom wall, :234-236 = :180-182).
+// Edge list: [0, C) row 0 | [C, 2C) row R-1 | [2C, 2C+n) column 0 | [2C+n, 2C+2n) column C-1; an edge is
+// listed only if its mode is a wall (the host passes which).
+template <class FM, class SM, bool WITH_MOMENTS>
+__global__ __launch_bounds__(256) void k_ade_edge(double* __restrict__ fn, double* __restrict__ gn,
+                                                  const double* __restrict__ fo, const double* __restrict__ go, Geom g,
+                                                  Bc bc, FM fm, SM sm, int row_begin, int row_end,
+                                                  double* __restrict__ rho_out, double* __restrict__ u_out,
+                                                  double* __restrict__ c_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, n = row_end - row_begin;
+  int r, c;
+  if (i < g.C) { r = 0; c = i; if (!bc_is_wall(bc.row_lo)) return; }
+  else if (i < 2 * g.C) { r = g.R - 1; c = i - g.C; if (!bc_is_wall(bc.row_hi)) return; }
+  else if (i < 2 * g.C + n) { r = row_begin + i - 2 * g.C; c = 0; if (!bc_is_wall(bc.col_lo)) return; }
+  else if (i < 2 * g.C + 2 * n) { r = row_begin + i - 2 * g.C - n; c = g.C - 1; if (!bc_is_wall(bc.col_hi)) return; }
+  else return;
+  if (r < row_begin || r >= row_end) return;
+  // a corner with a wall row belongs to the row lists
+  if (i >= 2 * g.C && ((r == 0 && bc_is_wall(bc.row_lo)) || (r == g.R - 1 && bc_is_wall(bc.row_hi)))) return;
+  // the same corner node on both column lists (C == 1) is listed once
+  if (i >= 2 * g.C + n && g.C == 1 && bc_is_wall(bc.col_lo)) return;
+  double f[Q], h[Q], rho, ux, uy, conc;
+  gather_walls(f, fo, g, bc, r, c);
+  gather_walls(h, go, g, bc, r, c);
+  ade_collide_node(f, h, fm, sm, rho, ux, uy, conc);
+  const long o = g.at(r, c);
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    fn[q * g.plane + o] = f[q];
+    gn[q * g.plane + o] = h[q];
+  }
+  if (WITH_MOMENTS) {
+    const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
+    rho_out[oo] = rho;
+    u_out[oo] = ux;
+    u_out[nn + oo] = uy;
+    c_out[oo] = conc;
+  }
+}
+
+// Collide only, no streaming: the driver's first iteration on the pre-collision state (one node per thread).
+template <class FM, class SM, bool WITH_MOMENTS>
+__global__ __launch_bounds__(256) void k_ade_collide(double* __restrict__ fp, double* __restrict__ gp,
+                                                     const double* __restrict__ f_in, const double* __restrict__ g_in,
+                                                     Geom g, FM fm, SM sm, double* __restrict__ rho_out,
+                                                     double* __restrict__ u_out, double* __restrict__ c_out) {
+  const long n_nodes = (long)g.R * g.C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes; i += (long)gridDim.x * blockDim.x) {
+    const int r = (int)(i / g.C), c = (int)(i % g.C);
+    const long o = g.at(r, c);
+    double f[Q], h[Q], rho, ux, uy, conc;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      f[q] = f_in[q * g.plane + o];
+      h[q] = g_in[q * g.plane + o];
+    }
+    ade_collide_node(f, h, fm, sm, rho, ux, uy, conc);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      fp[q * g.plane + o] = f[q];
+      gp[q * g.plane + o] = h[q];
+    }
+    if (WITH_MOMENTS) {
+      rho_out[i] = rho;
+      u_out[i] = ux;
+      u_out[n_nodes + i] = uy;
+      c_out[i] = conc;
+    }
+  }
+}
+
+}  // namespace lbm

@@ -158,6 +158,53 @@ class Solver {  // single-phase BGK / KBC block, wraps lbm_solver
   int R_, C_;
 };
 
+// Compressible BGK fluid + transported scalar on one block, wraps lbm_ade_solver: the sediment concentration of
+// test/rectangle_sedimentation_test.cpp:88-247 (equilibrium(g_equi, u + w, C), its own BGK rate, streamed like f;
+// no-flux walls).  Host arrays in the reference layout.
+class AdeSolver {
+ public:
+  AdeSolver(int R, int C, double omega, double omega_g, double w_r, double w_c, const lbm_bc& bc = BoundarySet(),
+            int form = LBM_FORM_DEFAULT)
+      : R_(R), C_(C) {
+    lbm_geom g{R, C, 0, 0, 0};
+    const lbm_bgk_params fluid{omega, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, form};
+    const lbm_ade_params scalar{omega_g, w_r, w_c, form};
+    check(lbm_ade_solver_create(&h_, &g, &bc, &fluid, &scalar, nullptr));
+  }
+  AdeSolver(AdeSolver&& o) noexcept : h_(o.h_), R_(o.R_), C_(o.C_) { o.h_ = nullptr; }
+  AdeSolver(const AdeSolver&) = delete;
+  ~AdeSolver() {
+    if (h_) lbm_ade_solver_destroy(h_);
+  }
+  // f_adve, g_adve [R][C][9]
+  void set_state(const std::vector<double>& f, const std::vector<double>& g) {
+    if (f.size() != (size_t)R_ * C_ * 9 || g.size() != f.size()) throw std::runtime_error("lbm::AdeSolver::set_state: size");
+    check(lbm_ade_solver_set_state(h_, f.data(), g.data()));
+  }
+  void step(int n) { check(lbm_ade_solver_step(h_, n)); }
+  // what the reference loop holds after the iterations run so far
+  struct State {
+    std::vector<double> f, g;  // [R][C][9]
+    std::vector<double> rho;   // [R][C]
+    std::vector<double> u;     // [R][C][2]
+    std::vector<double> C;     // [R][C]
+  };
+  State state() {
+    const size_t n = (size_t)R_ * C_;
+    State s{std::vector<double>(n * 9), std::vector<double>(n * 9), std::vector<double>(n), std::vector<double>(n * 2),
+            std::vector<double>(n)};
+    check(lbm_ade_solver_get_state(h_, s.f.data(), s.g.data(), s.rho.data(), s.u.data(), s.C.data()));
+    return s;
+  }
+  long long launches() const { return lbm_ade_solver_launches(h_); }
+  void sync() { check(lbm_ade_solver_sync(h_)); }
+  lbm_ade_solver* handle() { return h_; }
+
+ private:
+  lbm_ade_solver* h_ = nullptr;
+  int R_, C_;
+};
+
 }  // namespace lbm
 
 // ===============================================================================================

@@ -79,6 +79,15 @@ class CgParams(ct.Structure):
                 ("delta", ct.c_double), ("form", ct.c_int)]
 
 
+class AdeParams(ct.Structure):
+    """lbm_ade_params: the transported scalar's relaxation rate, the velocity w added to the fluid's u in its
+    equilibrium (the sedimentation driver's w_s on both components), and the form of both halves (FORM_*)"""
+    _fields_ = [("omega_g", ct.c_double), ("w_r", ct.c_double), ("w_c", ct.c_double), ("form", ct.c_int)]
+
+    def __init__(self, omega_g=1.0, w=(0.0, 0.0), form=FORM_DEFAULT):
+        super().__init__(omega_g, w[0], w[1], form)
+
+
 class LbmError(RuntimeError):
     pass
 
@@ -102,6 +111,7 @@ def load_library(path=LIB_PATH):
     lib.lbm_slab_ibm_msg_doubles.restype = ct.c_longlong
     lib.lbm_cg_solver_pair_launches.restype = ct.c_longlong
     lib.lbm_slab_pressure_msg_doubles.restype = ct.c_longlong
+    lib.lbm_ade_solver_launches.restype = ct.c_longlong
     return lib
 
 
@@ -220,6 +230,61 @@ class Solver:
         a, b, g = _dp(), _dp(), Geom()
         self.lib.solver_lattices(self.h, ct.byref(a), ct.byref(b), ct.byref(g))
         return ct.cast(a, ct.c_void_p).value, ct.cast(b, ct.c_void_p).value, g
+
+
+class AdeSolver:
+    """Python face of lbm_ade_solver: a compressible BGK fluid f and a transported scalar g on one block
+    (the sediment loop of test/rectangle_sedimentation_test.cpp), numpy AoS in/out, reference layout."""
+
+    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None):
+        self.lib, self.R, self.C, self.fluid, self.scalar = lib, R, C, fluid, scalar
+        self.g = Geom(R, C, 0)
+        self.bc = bc if bc is not None else Bc.periodic()
+        self.h = ct.c_void_p()
+        lib.ade_solver_create(ct.byref(self.h), ct.byref(self.g), ct.byref(self.bc), ct.byref(fluid),
+                              ct.byref(scalar), _stream(stream))
+
+    def close(self):
+        if self.h:
+            self.lib.ade_solver_destroy(self.h)
+            self.h = ct.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_state(self, f, g):
+        """f_adve, g_adve as [R, C, 9]"""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        g = np.ascontiguousarray(g, dtype=np.float64)
+        assert f.shape == (self.R, self.C, 9) and g.shape == (self.R, self.C, 9)
+        self.lib.ade_solver_set_state(self.h, _hptr(f), _hptr(g))
+
+    def step(self, n):
+        self.lib.ade_solver_step(self.h, int(n))
+
+    def get_state(self):
+        """dict f, g [R, C, 9], rho [R, C], u [R, C, 2], C [R, C]: what the reference loop holds"""
+        R, C = self.R, self.C
+        out = dict(f=np.empty((R, C, 9)), g=np.empty((R, C, 9)), rho=np.empty((R, C)), u=np.empty((R, C, 2)),
+                   C=np.empty((R, C)))
+        self.lib.ade_solver_get_state(self.h, *[_hptr(out[k]) for k in ("f", "g", "rho", "u", "C")])
+        return out
+
+    def sync(self):
+        self.lib.ade_solver_sync(self.h)
+
+    def launches(self):
+        return int(self.lib.raw.lbm_ade_solver_launches(self.h))
+
+    def lattices(self):
+        """device addresses (f_cur, g_cur, f_other, g_other) and the padded geometry"""
+        p = [_dp() for _ in range(4)]
+        g = Geom()
+        self.lib.ade_solver_lattices(self.h, *[ct.byref(x) for x in p], ct.byref(g))
+        return tuple(ct.cast(x, ct.c_void_p).value for x in p) + (g,)
 
 
 def cg_params(red=(3.0, 0.7, 0.04, 0.7), blue=(1.0, 0.1, 0.04, -0.7), sigma=0.1, gravity=6.25e-6,

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Fluid + transported scalar (lbm_ade_*): the fused step against the same step composed from the unfused operators
+and against the single-step BGK launch, on one periodic box, in one process, alternated.  Prints one JSON line.
+
+  fused      lbm_ade_solver_step: one launch per step on a periodic box (ade.hpp k_ade_stream_collide)
+  composed   calc_rho, calc_u, calc_rho(g), equilibrium x2, axpb x2 (u + w), collision x2, advect x2 per step (11 launches)
+  bgk        lbm_bgk_stream_collide on two padded lattices (the single-step BGK launch, f only)
+MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
+(18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
+usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast]"""
+import argparse
+import ctypes as ct
+import json
+import math
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "lattice-boltzmann-method_amd"))
+
+import torch  # noqa: E402
+
+import pylbm  # noqa: E402
+from pylbm import _ptr  # noqa: E402
+
+HBM_TBS = 8.0
+W = (3e-3, 3e-3)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=8192)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--form", choices=["default", "ref", "fast"], default="default")
+    ap.add_argument("--skip-composed", action="store_true")
+    a = ap.parse_args()
+    form = {"default": pylbm.FORM_DEFAULT, "ref": pylbm.FORM_REFERENCE_ORDER, "fast": pylbm.FORM_REASSOCIATED}[a.form]
+    lib = pylbm.Lib()
+    if lib.device_count() < 1:
+        raise SystemExit("ade_bench.py: no HIP device visible")
+    R = C = a.size
+    n = R * C
+    dev = torch.device("cuda:0")
+    st = ct.c_void_p()
+    lib.stream_create(ct.byref(st))
+    e0, e1 = ct.c_void_p(), ct.c_void_p()
+    lib.event_create(ct.byref(e0))
+    lib.event_create(ct.byref(e1))
+
+    def timed(fn, steps):
+        lib.event_record(e0, st)
+        fn(steps)
+        lib.event_record(e1, st)
+        ms = ct.c_float()
+        lib.event_elapsed_ms(ct.byref(ms), e0, e1)
+        return ms.value / 1e3
+
+    # initial state built on the device: a shear wave and a scalar band, equilibrium populations (dense SoA)
+    r = torch.arange(R, dtype=torch.float64, device=dev).view(R, 1).expand(R, C)
+    c = torch.arange(C, dtype=torch.float64, device=dev).view(1, C).expand(R, C)
+    rho = torch.ones((R, C), dtype=torch.float64, device=dev)
+    conc = 1e-3 * torch.exp(-((c - C / 2) / (C / 8)) ** 2)
+    u = torch.zeros((2, R, C), dtype=torch.float64, device=dev)
+    u[1] = 0.02 * torch.sin(2 * math.pi * r / R)
+    del r, c
+    f = torch.empty((9, R, C), dtype=torch.float64, device=dev)
+    g = torch.empty_like(f)
+    lib.equilibrium(_ptr(f), _ptr(u), _ptr(rho), R, C, None)
+    lib.equilibrium(_ptr(g), _ptr(u), _ptr(conc), R, C, None)
+    torch.cuda.synchronize()
+
+    # fused: the solver context; its lattices are filled from the dense arrays (pre-collision state)
+    fluid, scalar = pylbm.BgkParams(1.2, 0, form=form), pylbm.AdeParams(1.7, W, form=form)
+    sv = pylbm.AdeSolver(lib, R, C, fluid, scalar, stream=st.value)
+    f_cur, g_cur, _, _, sg = sv.lattices()   # device addresses as Python ints: through _ptr, never bare (a bare int is a C int)
+    dg = pylbm.Geom(R, C, 0)
+    lib.lattice_copy_rows(_ptr(f_cur), ct.byref(sg), 0, _ptr(f), ct.byref(dg), 0, R, st)
+    lib.lattice_copy_rows(_ptr(g_cur), ct.byref(sg), 0, _ptr(g), ct.byref(dg), 0, R, st)
+    lib.stream_sync(st)
+
+    # single-step BGK on two padded lattices (as bench.py's box)
+    plane = n + lib.default_plane_pad(R, C)
+    bgk = [torch.empty(9 * plane, dtype=torch.float64, device=dev) for _ in range(2)]
+    bg = pylbm.Geom(R, C, 0, plane, 0)
+    lib.lattice_copy_rows(_ptr(bgk[0]), ct.byref(bg), 0, _ptr(f), ct.byref(dg), 0, R, st)
+    bprm, bbc = pylbm.BgkParams(1.2, 0, form=form), pylbm.Bc.periodic()
+    lib.bgk_collide(_ptr(bgk[1]), _ptr(bgk[0]), ct.byref(bg), ct.byref(bbc), ct.byref(bprm), None, None, st)
+    cur = [1]
+
+    def run_bgk(k):
+        for _ in range(k):
+            s, d = bgk[cur[0]], bgk[cur[0] ^ 1]
+            lib.bgk_stream_collide(_ptr(d), _ptr(s), ct.byref(bg), ct.byref(bbc), ct.byref(bprm), 0, R, None, None, st)
+            cur[0] ^= 1
+
+    def run_fused(k):
+        sv.step(k)
+
+    # composed: the reference loop from the unfused operators (dense lattices f, g advance in place of the loop)
+    if not a.skip_composed:
+        fe, ge, fc, gc = (torch.empty_like(f) for _ in range(4))
+        uw = torch.empty_like(u)
+
+    def run_composed(k):
+        for _ in range(k):
+            lib.calc_rho(_ptr(rho), _ptr(f), R, C, st)
+            lib.calc_u(_ptr(u), _ptr(f), _ptr(rho), R, C, st)
+            lib.calc_rho(_ptr(conc), _ptr(g), R, C, st)
+            lib.equilibrium(_ptr(fe), _ptr(u), _ptr(rho), R, C, st)
+            lib.axpb(_ptr(uw[0]), _ptr(u[0]), ct.c_double(1.0), ct.c_double(W[0]), ct.c_longlong(n), st)
+            lib.axpb(_ptr(uw[1]), _ptr(u[1]), ct.c_double(1.0), ct.c_double(W[1]), ct.c_longlong(n), st)
+            lib.equilibrium(_ptr(ge), _ptr(uw), _ptr(conc), R, C, st)
+            lib.collision(_ptr(fc), _ptr(f), _ptr(fe), ct.c_double(1.2), R, C, st)
+            lib.collision(_ptr(gc), _ptr(g), _ptr(ge), ct.c_double(1.7), R, C, st)
+            lib.advect(_ptr(f), _ptr(fc), R, C, st)
+            lib.advect(_ptr(g), _ptr(gc), R, C, st)
+
+    runs = {"fused": run_fused, "bgk": run_bgk}
+    if not a.skip_composed:
+        runs["composed"] = run_composed
+    for fn in runs.values():
+        timed(fn, a.warmup)
+    launches0 = sv.launches()
+    times = {k: [] for k in runs}
+    for _ in range(a.repeats):
+        for k, fn in runs.items():
+            times[k].append(timed(fn, a.steps))
+    launches = sv.launches() - launches0
+    mlups = {k: n * a.steps / statistics.median(v) / 1e6 for k, v in times.items()}
+    fused_tbs = 288.0 * n * a.steps / statistics.median(times["fused"]) / 1e12
+    bgk_tbs = 144.0 * n * a.steps / statistics.median(times["bgk"]) / 1e12
+    out = {"metric": "fused fluid + scalar step, D2Q9 f64, periodic box", "size": [R, C], "steps": a.steps,
+           "repeats": a.repeats, "form": a.form,
+           "fused_mlups": round(mlups["fused"], 1),
+           "composed_mlups": round(mlups["composed"], 1) if "composed" in mlups else None,
+           "bgk_single_step_mlups": round(mlups["bgk"], 1),
+           "fused_over_composed": round(mlups["fused"] / mlups["composed"], 3) if "composed" in mlups else None,
+           "fused_over_bgk": round(mlups["fused"] / mlups["bgk"], 3),
+           "fused_algorithmic_tbs": round(fused_tbs, 3), "fused_fraction_of_8tbs": round(fused_tbs / HBM_TBS, 3),
+           "bgk_algorithmic_tbs": round(bgk_tbs, 3),
+           "fused_launches_per_step": launches / (a.steps * a.repeats),
+           "times_s": {k: [round(t, 5) for t in v] for k, v in times.items()}}
+    sv.close()
+    lib.event_destroy(e0)
+    lib.event_destroy(e1)
+    lib.stream_destroy(st)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
