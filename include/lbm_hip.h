@@ -14,7 +14,7 @@
  * lbm_soa_to_aos convert bit-exactly: AoS element ((r*C)+c)*Q+q  <->  SoA q*R*C + r*C + c.
  * Scalar fields: rho[R][C]; vector fields u[2][R][C] (component slowest).
  * A lattice with g ghost rows per side (multi-GPU slabs; g = the steps per launch D, or m x D with one
- * exchange per m launches, or 3 for the two-phase step) stores planes of (R+2g) rows: row index r in
+ * exchange per m launches, 3 for the two-phase step, 1 for the fluid + scalar pair) stores planes of (R+2g) rows: row index r in
  * [-g, R+g) lives at plane offset (r+g)*C; see lbm_geom.
  *
  * All functions return 0 (LBM_OK) or a negative status and never throw; the message of
@@ -460,7 +460,8 @@ int lbm_solver_lattices(lbm_solver* sv, double** cur, double** other, lbm_geom* 
  * solver::equilibrium(g_equi, u + w, C) with C = calc_rho(g) and u the fluid's velocity (:125), it relaxes with its
  * own BGK rate (:132) and streams like f (:145-146).  Dye, temperature as a passive scalar, sediment.
  * One fused pull step per node streams both post-collision lattices, forms rho, u from f and C from g, collides both
- * and writes both (288 B per node update).  Single block (ghost = 0), C even.  Edges: PERIODIC or BOUNCE_BACK rows,
+ * and writes both (288 B per node update).  Single block (ghost = 0; row slabs: lbm_ade_stream_collide_part and
+ * lbm_ring_ade_* below), C even.  Edges: PERIODIC or BOUNCE_BACK rows,
  * PERIODIC, BOUNCE_BACK or SPECULAR columns; g takes exactly the fix-up f takes at a wall, on its own post-collision
  * populations -- a no-flux wall (the driver's bottom wall, :234-236 = :180-182).  Everything else (HALO, ABB_VELOCITY,
  * WRAP_NOSHIFT, pressure rows, ghost rows) is refused on the host.  The fluid parameters must be the plain
@@ -483,6 +484,23 @@ int lbm_ade_collide(double* fp, double* gp, const double* f, const double* g_in,
 int lbm_ade_stream_collide(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                            const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int row_begin,
                            int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
+/* The same step on a PART of a slab, for a slab whose neighbours wait for its edge rows (lbm_ring_ade_step).  One
+ * dispatch per part, the wall fix-ups inline: lanes of wall nodes (every node of a wall row; column 0 / C-1 at a wall
+ * column) gather with the fix-ups on both lattices, all others take the plain pull -- bit for bit the loads and the
+ * arithmetic of lbm_ade_stream_collide.  The nodes each part writes (f and g, all 9 planes; the moments at the same nodes):
+ *   LBM_ADE_PART_FRAME: every node of rows [0, edge_rows) and [R - edge_rows, R), both bands in one dispatch;
+ *   LBM_ADE_PART_INNER: every node of rows [edge_rows, R - edge_rows).
+ * 1 <= edge_rows, 2 x edge_rows < R.  Neither writes a ghost row, the row-pitch padding or the plane padding; the parts are
+ * disjoint and may run on two streams at once; together they are lbm_ade_stream_collide on [0, R), bit for bit, in both
+ * forms.  Geometries: ghost = 0 with PERIODIC (wrapping) or BOUNCE_BACK rows, as lbm_ade_stream_collide; or ghost >= 1
+ * with HALO or BOUNCE_BACK rows (a slab of a chain or ring: a HALO edge reads the ghost row beside it, which the caller
+ * keeps current -- lbm_halo_pack / _unpack at depth 1 on both lattices).  Everything else lbm_ade_stream_collide refuses
+ * is refused here too, and so are HALO without ghost rows and PERIODIC rows with them. */
+#define LBM_ADE_PART_FRAME 1
+#define LBM_ADE_PART_INNER 2
+int lbm_ade_stream_collide_part(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int part,
+                                int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s);
 /* driver loop context (single block; g->row_pitch and g->plane_stride 0: the context pads its own lattices).
  * set_state takes f_adve, g_adve (host AoS [R][C][9]); step(n) runs n driver iterations, enqueueing only (no
  * allocation, no host synchronisation: a created stream can capture it, lbm_graph_*); get_state returns what the
@@ -561,6 +579,21 @@ int lbm_ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm_bc
 /* the same for KBC (n_steps 1, or 2..4 with the reassociated collision) */
 int lbm_ring_kbc_step(lbm_ring* rg, double* dst, const double* src, const lbm_bc* bc,
                       const lbm_kbc_params* prm, int n_steps, int edge_rows, lbm_stream_t main);
+
+/* The fluid + scalar step over row slabs (lbm_ade_stream_collide_part).  The ring's slab geometry must carry ghost = 1;
+ * bc: the physical edges of the GLOBAL domain (NULL = periodic), seams become HALO, and so do both row edges of a closed
+ * ring.  Every message carries the single-step halo of BOTH lattices: 2 x lbm_halo_rows(1) = 6 rows of C doubles per
+ * side.  On return `main` waits for everything.  All arguments are checked on the host before any device call.
+ * lbm_ring_ade_collide: the first driver iteration on a slab -- collide-only on the owned rows of (f, g_in) into
+ * (fp, gp), then one exchange of both. */
+int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in,
+                         const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, lbm_stream_t main);
+/* one overlapped step: FRAME + pack + ONE message per neighbour on the ring's stream, INNER on `main` beside them */
+int lbm_ring_ade_step(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                      const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int edge_rows, lbm_stream_t main);
+/* refresh the single-step ghost rows of two lattices in one message per neighbour (e.g. after restoring a state);
+ * asynchronous, ordered after the work enqueued on `after` (lbm_ring_join makes a stream wait for it) */
+int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after);
 
 /* phase timing for diagnosing a scaling run: on = 1 records timed events around the edge rows, the
  * exchange (pack + send/recv + unpack) and the interior rows of every bgk / kbc launch-step;

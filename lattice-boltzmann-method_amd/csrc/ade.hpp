@@ -171,6 +171,87 @@ __global__ __launch_bounds__(256) void k_ade_edge(double* __restrict__ fn, doubl
   }
 }
 
+// The wall fix-ups of gather_walls (bc_fixups_own: rows first, columns win at the corners) for the pair (r, c), (r, c + 1)
+// of one lattice after pull_pair: each replaced population is loaded from the node's own post-collision populations, as
+// gather_walls loads it -- the same value, so the same bits.  Only the replaced populations are loaded (the own pair of
+// a wall row as 16-byte accesses), which keeps the step's register count at the pull's.  Rows: bounce-back; columns:
+// bounce-back or specular (what the fused step accepts).
+template <bool NT>
+__device__ __forceinline__ void wall_fixups_pair(double (&a)[Q], double (&b)[Q], const double* __restrict__ po,
+                                                 const Geom& g, const Bc& bc, bool row_lo, bool row_hi, long r0, int c) {
+  dbl2 v;
+  if (row_lo) {  // bc_fixups_own: f[1] = own[3]; f[5] = own[7]; f[8] = own[6]
+    v = load2a<NT>(po + 3 * g.plane + r0 + c); a[1] = v.x; b[1] = v.y;
+    v = load2a<NT>(po + 7 * g.plane + r0 + c); a[5] = v.x; b[5] = v.y;
+    v = load2a<NT>(po + 6 * g.plane + r0 + c); a[8] = v.x; b[8] = v.y;
+  }
+  if (row_hi) {  // f[3] = own[1]; f[7] = own[5]; f[6] = own[8]
+    v = load2a<NT>(po + 1 * g.plane + r0 + c); a[3] = v.x; b[3] = v.y;
+    v = load2a<NT>(po + 5 * g.plane + r0 + c); a[7] = v.x; b[7] = v.y;
+    v = load2a<NT>(po + 8 * g.plane + r0 + c); a[6] = v.x; b[6] = v.y;
+  }
+  if (c + 2 == g.C && bc_is_wall(bc.col_hi)) {  // node b; bounce-back: f[4] = own[2], f[7] = own[5], f[8] = own[6]
+    const double* o = po + r0 + c + 1;
+    const bool sp = bc.col_hi == LBM_EDGE_SPECULAR;  // specular: f[7] = own[6], f[8] = own[5]
+    b[4] = o[2 * g.plane];
+    b[7] = o[(sp ? 6 : 5) * g.plane];
+    b[8] = o[(sp ? 5 : 6) * g.plane];
+  }
+  if (c == 0 && bc_is_wall(bc.col_lo)) {  // node a; bounce-back: f[2] = own[4], f[5] = own[7], f[6] = own[8]
+    const double* o = po + r0;
+    const bool sp = bc.col_lo == LBM_EDGE_SPECULAR;  // specular: f[5] = own[8], f[6] = own[7]
+    a[2] = o[4 * g.plane];
+    a[5] = o[(sp ? 8 : 7) * g.plane];
+    a[6] = o[(sp ? 7 : 8) * g.plane];
+  }
+}
+
+// The fused step on a PART of a slab, in ONE dispatch with the wall fix-ups inline: rows [band0, band0 + n0) followed by
+// rows [band1, band1 + nrows - n0) (FRAME: both edge bands; INNER: one band, n0 = nrows).  Every lane takes pull_pair;
+// a lane whose pair holds a wall node -- every node of a wall row, column 0 / C-1 at a wall column -- then replaces the
+// populations the wall gather replaces (wall_fixups_pair), on both lattices.  Each population is the value of the one
+// load gather_walls / pull_pair take for it and the arithmetic is ade_collide_node's, so the results are those of
+// k_ade_stream_collide + k_ade_edge bit for bit.  Rows come from wrap_row: ghost rows once g.ghost > 0 (HALO edges),
+// wrapped on a single block (a wall row's pulled row is replaced).  Writes owned nodes only.
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS>
+__global__ __launch_bounds__(256) void k_ade_stream_collide_part(
+    double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
+    Geom g, Bc bc, FM fm, SM sm, int band0, int n0, int band1, int nrows, int tiles_per_row,
+    double* __restrict__ rho_out, double* __restrict__ u_out, double* __restrict__ c_out) {
+  const long items = (long)nrows * tiles_per_row;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const int v = (int)(it / tiles_per_row);
+    const int r = v < n0 ? band0 + v : band1 + (v - n0);
+    const int c = ((int)(it % tiles_per_row) * 256 + threadIdx.x) * 2;
+    if (c >= g.C) continue;
+    const long rm = g.at(wrap_row(g, r - 1), 0);  // source row of cx = +1 populations
+    const long r0 = g.at(r, 0);
+    const long rp = g.at(wrap_row(g, r + 1), 0);  // source row of cx = -1 populations
+    const bool row_lo = r == 0 && bc.row_lo == LBM_EDGE_BOUNCE_BACK, row_hi = r == g.R - 1 && bc.row_hi == LBM_EDGE_BOUNCE_BACK;
+    const bool wall = row_lo || row_hi || (c == 0 && bc_is_wall(bc.col_lo)) || (c + 2 == g.C && bc_is_wall(bc.col_hi));
+    double fa[Q], fb[Q], ha[Q], hb[Q];            // f and g of node (r, c) and node (r, c + 1)
+    pull_pair<NT_LOAD>(fa, fb, fo, g, rm, r0, rp, c);
+    if (wall) wall_fixups_pair<NT_LOAD>(fa, fb, fo, g, bc, row_lo, row_hi, r0, c);
+    pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+    if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, bc, row_lo, row_hi, r0, c);
+    double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
+    ade_collide_node(fa, ha, fm, sm, rho_a, ux_a, uy_a, c_a);
+    ade_collide_node(fb, hb, fm, sm, rho_b, ux_b, uy_b, c_b);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    if (WITH_MOMENTS) {
+      const long o = (long)r * g.C + c;  // moment fields are dense
+      const long n = (long)g.R * g.C;
+      store2<false>(rho_out + o, rho_a, rho_b);
+      store2<false>(u_out + o, ux_a, ux_b);
+      store2<false>(u_out + n + o, uy_a, uy_b);
+      store2<false>(c_out + o, c_a, c_b);
+    }
+  }
+}
+
 // Collide only, no streaming: the driver's first iteration on the pre-collision state (one node per thread).
 template <class FM, class SM, bool WITH_MOMENTS>
 __global__ __launch_bounds__(256) void k_ade_collide(double* __restrict__ fp, double* __restrict__ gp,

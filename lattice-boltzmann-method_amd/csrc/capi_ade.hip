@@ -23,27 +23,41 @@ static const char* edge_name(int m) {
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-// Everything the fused step accepts, checked on the host before any device call.  Rows: PERIODIC or
-// BOUNCE_BACK; columns: PERIODIC, BOUNCE_BACK or SPECULAR.  The scalar takes the fluid's fix-up at every wall.
+// Everything the fused step accepts, checked on the host before any device call.  Single block (slab = false): ghost
+// 0, rows PERIODIC or BOUNCE_BACK.  Slab (the part launches and the ring): ghost 0 with PERIODIC or BOUNCE_BACK rows, or
+// ghost >= 1 with HALO or BOUNCE_BACK rows -- ghost rows are read where a row edge is HALO and nothing wraps.  Columns:
+// PERIODIC, BOUNCE_BACK or SPECULAR.  The scalar takes the fluid's fix-up at every wall.
 static int ade_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
-                        const lbm_ade_params* scalar) {
+                        const lbm_ade_params* scalar, bool slab = false) {
   LBM_REQUIRE(g, "%s: NULL geometry", fn);
   LBM_REQUIRE(g->R >= 1 && g->C >= 1, "%s: R=%d C=%d must be positive", fn, g->R, g->C);
-  LBM_REQUIRE(g->ghost == 0, "%s: ghost=%d: the fluid + scalar step runs on a single block (ghost = 0)", fn, g->ghost);
+  if (slab) LBM_REQUIRE(g->ghost >= 0 && g->ghost <= 15, "%s: ghost=%d must be 0..15", fn, g->ghost);
+  else LBM_REQUIRE(g->ghost == 0, "%s: ghost=%d: the fluid + scalar step runs on a single block (ghost = 0)", fn, g->ghost);
   LBM_REQUIRE(g->C % 2 == 0, "%s: C=%d must be even (two nodes per lane)", fn, g->C);
   LBM_REQUIRE(g->row_pitch == 0 || (g->row_pitch >= g->C && g->row_pitch % 2 == 0),
               "%s: row_pitch=%d must be even and >= C=%d (0 = dense)", fn, g->row_pitch, g->C);
   const long long pitch = g->row_pitch > 0 ? g->row_pitch : g->C;
-  LBM_REQUIRE(g->plane_stride == 0 || (g->plane_stride >= (long long)g->R * pitch && g->plane_stride % 2 == 0),
+  LBM_REQUIRE(g->plane_stride == 0 || (g->plane_stride >= (long long)(g->R + 2 * g->ghost) * pitch && g->plane_stride % 2 == 0),
               "%s: plane_stride=%lld must be even and at least a plane (0 = dense)", fn, g->plane_stride);
+  if (slab && g->ghost > 0)
+    LBM_REQUIRE(bc && bc->row_lo != LBM_EDGE_PERIODIC && bc->row_hi != LBM_EDGE_PERIODIC,
+                "%s: ghost=%d: a slab's row edges are HALO or BOUNCE_BACK (row edge mode PERIODIC given: nothing wraps "
+                "where there are ghost rows)", fn, g->ghost);
   if (bc) {
     LBM_REQUIRE(bc->pressure_rows == 0, "%s: pressure_rows=%d not supported by the fluid + scalar step", fn,
                 bc->pressure_rows);
     auto row_ok = [](int m) { return m == LBM_EDGE_PERIODIC || m == LBM_EDGE_BOUNCE_BACK; };
     auto col_ok = [](int m) { return m == LBM_EDGE_PERIODIC || m == LBM_EDGE_BOUNCE_BACK || m == LBM_EDGE_SPECULAR; };
-    LBM_REQUIRE(row_ok(bc->row_lo), "%s: row edge mode %s (%d) not supported (PERIODIC or BOUNCE_BACK)", fn,
+    if (slab) {
+      for (int m : {bc->row_lo, bc->row_hi}) {
+        LBM_REQUIRE(m != LBM_EDGE_HALO || g->ghost > 0, "%s: row edge mode HALO needs ghost rows (ghost=0)", fn);
+        LBM_REQUIRE(row_ok(m) || m == LBM_EDGE_HALO,
+                    "%s: row edge mode %s (%d) not supported (PERIODIC, HALO or BOUNCE_BACK)", fn, edge_name(m), m);
+      }
+    }
+    LBM_REQUIRE(slab || row_ok(bc->row_lo), "%s: row edge mode %s (%d) not supported (PERIODIC or BOUNCE_BACK)", fn,
                 edge_name(bc->row_lo), bc->row_lo);
-    LBM_REQUIRE(row_ok(bc->row_hi), "%s: row edge mode %s (%d) not supported (PERIODIC or BOUNCE_BACK)", fn,
+    LBM_REQUIRE(slab || row_ok(bc->row_hi), "%s: row edge mode %s (%d) not supported (PERIODIC or BOUNCE_BACK)", fn,
                 edge_name(bc->row_hi), bc->row_hi);
     LBM_REQUIRE(col_ok(bc->col_lo), "%s: column edge mode %s (%d) not supported (PERIODIC, BOUNCE_BACK or SPECULAR)",
                 fn, edge_name(bc->col_lo), bc->col_lo);
@@ -122,10 +136,39 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
   return LBM_OK;
 }
 
+// one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline
+template <class FM, class SM>
+static int ade_part_launch(double* fn, double* gn, const double* fo, const double* go, const Geom& g, const Bc& bc,
+                           const FM& fm, const SM& sm, int band0, int n0, int band1, int nrows, double* rho, double* u,
+                           double* conc, hipStream_t st) {
+  const bool mom = rho != nullptr;
+  const int nt = tuning("nt", 3);  // as the single-block step
+  const int cap = tuning("grid_cap", 0);
+  const int tiles = (g.C + 511) / 512;
+  const long items = (long)nrows * tiles;
+  const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
+  switch ((nt & 3) | (mom ? 4 : 0)) {
+#define LBM_ADE_P(NL, NS, M)                                                                                            \
+  LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL, NS, M>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, \
+              sm, band0, n0, band1, nrows, tiles, rho, u, conc)
+    case 0: LBM_ADE_P(false, false, false); break;
+    case 1: LBM_ADE_P(true, false, false); break;
+    case 2: LBM_ADE_P(false, true, false); break;
+    case 3: LBM_ADE_P(true, true, false); break;
+    case 4: LBM_ADE_P(false, false, true); break;
+    case 5: LBM_ADE_P(true, false, true); break;
+    case 6: LBM_ADE_P(false, true, true); break;
+    default: LBM_ADE_P(true, true, true); break;
+#undef LBM_ADE_P
+  }
+  LBM_CHECK_LAUNCH();
+  return LBM_OK;
+}
+
 static int ade_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* lg,
                        const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, double* rho,
-                       double* u, double* conc, hipStream_t st) {
-  int rc = ade_validate(fn, lg, bc, fluid, scalar);
+                       double* u, double* conc, hipStream_t st, bool slab = false) {
+  int rc = ade_validate(fn, lg, bc, fluid, scalar, slab);
   if (rc) return rc;
   LBM_REQUIRE(fp && gp && f && h, "%s: NULL lattice", fn);
   LBM_REQUIRE((rho == nullptr) == (u == nullptr) && (rho == nullptr) == (conc == nullptr),
@@ -161,6 +204,33 @@ static int ade_stream_collide(const char* fn, double* fn_, double* gn, const dou
   return ade_step_launch(fn_, gn, fo, go, g, bc, BgkModelT<0, 0>{fluid->omega},
                          AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, row_begin, row_end, rho, u, conc, st,
                          launches);
+}
+
+int ade_part_check(const char* name, const double* fn, const double* gn, const double* fo, const double* go,
+                   const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                   int part, int edge_rows, const double* rho, const double* u, const double* conc) {
+  int rc = ade_validate(name, lg, lbc, fluid, scalar, true);
+  if (rc) return rc;
+  LBM_REQUIRE(fn && gn && fo && go, "%s: NULL lattice", name);
+  LBM_REQUIRE(fn != fo && fn != go && gn != fo && gn != go && fn != gn && fo != go, "%s: aliased lattices", name);
+  LBM_REQUIRE(aligned16(fn) && aligned16(gn) && aligned16(fo) && aligned16(go), "%s: lattices must be 16-byte aligned", name);
+  LBM_REQUIRE((rho == nullptr) == (u == nullptr) && (rho == nullptr) == (conc == nullptr),
+              "%s: rho, u and conc must all be given or all be NULL", name);
+  LBM_REQUIRE(part == LBM_ADE_PART_FRAME || part == LBM_ADE_PART_INNER,
+              "%s: part=%d (LBM_ADE_PART_FRAME or LBM_ADE_PART_INNER)", name, part);
+  LBM_REQUIRE(edge_rows >= 1 && 2 * edge_rows < lg->R, "%s: edge_rows=%d: need 1 <= edge_rows and 2 x edge_rows < R=%d",
+              name, edge_rows, lg->R);
+  return LBM_OK;
+}
+
+int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
+                      const lbm_ade_params* scalar) {
+  return ade_validate(fn, g, bc, fluid, scalar, true);
+}
+
+int ade_collide_slab(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
+                     const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, hipStream_t st) {
+  return ade_collide(fn, fp, gp, f, h, g, bc, fluid, scalar, nullptr, nullptr, nullptr, st, true);
 }
 
 }  // namespace lbm
@@ -200,6 +270,28 @@ int lbm_ade_stream_collide(double* fn, double* gn, const double* fo, const doubl
   long long launches = 0;
   return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, row_begin, row_end, rho, u,
                             conc, as_stream(s), &launches);
+}
+
+int lbm_ade_stream_collide_part(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
+                                const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int part,
+                                int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
+  int rc = ade_part_check("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, fluid, scalar, part, edge_rows, rho, u,
+                          conc);
+  if (rc) return rc;
+  const int R = lg->R;
+  const Geom g = make_geom(*lg);
+  const Bc bc = make_bc(lbc);
+  // FRAME: rows [0, E) then [R - E, R); INNER: rows [E, R - E)
+  const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;
+  const int n0 = part == LBM_ADE_PART_FRAME ? edge_rows : R - 2 * edge_rows;
+  const int band1 = R - edge_rows, nrows = part == LBM_ADE_PART_FRAME ? 2 * edge_rows : n0;
+  if (ade_fast(scalar))
+    return ade_part_launch(fn, gn, fo, go, g, bc, BgkFastModel(fluid->omega),
+                           AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c), band0, n0, band1, nrows, rho, u, conc,
+                           as_stream(s));
+  return ade_part_launch(fn, gn, fo, go, g, bc, BgkModelT<0, 0>{fluid->omega},
+                         AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, band0, n0, band1, nrows, rho, u, conc,
+                         as_stream(s));
 }
 
 int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,

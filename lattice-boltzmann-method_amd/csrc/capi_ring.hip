@@ -279,16 +279,13 @@ static int ring_transfer(lbm_ring* rg, const double* send_prev, size_t n_send_pr
   return LBM_OK;
 }
 
-// Bring the ghost rows of `lattice` (and of `lattice2`, if given: the second colour of the
-// two-phase model travels in the same message) up to date: pack, one send + one recv per neighbour
-// in one RCCL group, unpack -- all enqueued on the ring's edge stream, after the work already
-// enqueued on `after`.
-static int ring_exchange(lbm_ring* rg, double* lattice, double* lattice2, lbm_stream_t after, bool full = false) {
-  // two lattices = the two colours; full = complete ghost rows (multi-step launches with walls)
-  const int G = lattice2 ? LBM_HALO_TWO_PHASE : (full ? LBM_HALO_FULL(rg->g.ghost) : rg->g.ghost);
+// Bring the ghost rows of one or two lattices up to date with halo depth code G (lbm_halo_rows: 1..15,
+// LBM_HALO_FULL(d), LBM_HALO_TWO_PHASE): pack, one send + one recv per neighbour carrying every lattice back to back,
+// unpack -- all enqueued on the ring's edge stream, after the work already enqueued on `after`.
+static int ring_exchange_depth(lbm_ring* rg, double* lattice, double* lattice2, int G, lbm_stream_t after) {
   const size_t msg = (size_t)lbm_halo_rows(G) * rg->g.C;
   LBM_REQUIRE(msg * (lattice2 ? 2 : 1) <= rg->bufsz, "lbm_ring: message of %zu doubles, buffers of %zu", msg * (lattice2 ? 2 : 1), rg->bufsz);
-  rg->valid = lattice2 ? 3 : rg->g.ghost;  // these ghost rows are current again
+  rg->valid = G == LBM_HALO_TWO_PHASE ? 3 : (G >= 100 ? G - 100 : G);  // these ghost rows are current again
   rg->skipped = 0;
   if (as_stream(after) != rg->edge) {
     LBM_CHECK_HIP(hipEventRecord(rg->main_done, as_stream(after)));
@@ -323,6 +320,13 @@ static int ring_exchange(lbm_ring* rg, double* lattice, double* lattice2, lbm_st
     }
   }
   return LBM_OK;
+}
+
+// one lattice at the ring's depth (full = complete ghost rows: multi-step launches with walls), or the two colours of the
+// two-phase model (LBM_HALO_TWO_PHASE)
+static int ring_exchange(lbm_ring* rg, double* lattice, double* lattice2, lbm_stream_t after, bool full = false) {
+  const int G = lattice2 ? LBM_HALO_TWO_PHASE : (full ? LBM_HALO_FULL(rg->g.ghost) : rg->g.ghost);
+  return ring_exchange_depth(rg, lattice, lattice2, G, after);
 }
 
 int lbm_ring_exchange(lbm_ring* rg, double* lattice, lbm_stream_t after) {
@@ -389,6 +393,79 @@ int lbm_ring_cg_step(lbm_ring* rg, double* dst_r, double* dst_b, const double* s
   LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
   LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
   return LBM_OK;
+}
+
+// ---- the fluid + scalar pair (lbm_ade_*) over row slabs: one ghost row per side, both lattices in one message ----------
+// The slab's edges: the GLOBAL domain's (NULL = periodic) with the seams -- both row edges of a closed ring -- as HALO;
+// checked with everything else the part launches check, before any device call.
+static int ring_ade_edges(const char* fn, lbm_ring* rg, const lbm_bc* bc, const lbm_bgk_params* fluid,
+                          const lbm_ade_params* scalar, lbm_bc* b) {
+  LBM_REQUIRE(rg->g.ghost == 1, "%s: ghost=%d: the fluid + scalar step over slabs exchanges one ghost row per side (ring "
+              "slabs need ghost=1)", fn, rg->g.ghost);
+  *b = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
+  if (rg->prev >= 0) b->row_lo = LBM_EDGE_HALO;
+  if (rg->next >= 0) b->row_hi = LBM_EDGE_HALO;
+  return ade_validate_slab(fn, &rg->g, b, fluid, scalar);
+}
+
+// make `main` wait for the ring's stream
+static int ring_join_main(lbm_ring* rg, hipStream_t main) {
+  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
+  LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
+  return LBM_OK;
+}
+
+int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, lbm_stream_t main_s) {
+  const char* fn = "lbm_ring_ade_collide";
+  LBM_REQUIRE(rg && fp && gp && f && g_in && fluid && scalar, "%s: NULL argument", fn);
+  lbm_bc b;
+  int rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
+  if (rc) return rc;
+  hipStream_t main = as_stream(main_s);
+  rc = ade_collide_slab(fn, fp, gp, f, g_in, &rg->g, &b, fluid, scalar, main);
+  if (rc || (rg->prev < 0 && rg->next < 0)) return rc;
+  rc = ring_exchange_depth(rg, fp, gp, 1, main);
+  return rc ? rc : ring_join_main(rg, main);
+}
+
+// FRAME (both edge bands, one dispatch) + pack + one message per neighbour on the ring's stream, INNER on `main` beside
+// them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches
+int lbm_ring_ade_step(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                      const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int edge_rows, lbm_stream_t main_s) {
+  const char* fn = "lbm_ring_ade_step";
+  LBM_REQUIRE(rg && fn_ && gn && fo && go && fluid && scalar, "%s: NULL argument", fn);
+  lbm_bc b;
+  int rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
+  if (rc) return rc;
+  if (edge_rows < 1) edge_rows = 1;
+  rc = ade_part_check(fn, fn_, gn, fo, go, &rg->g, &b, fluid, scalar, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr,
+                      nullptr);
+  if (rc) return rc;
+  hipStream_t main = as_stream(main_s);
+  auto part = [&](int which, hipStream_t st) {
+    return lbm_ade_stream_collide_part(fn_, gn, fo, go, &rg->g, &b, fluid, scalar, which, edge_rows, nullptr, nullptr,
+                                       nullptr, st);
+  };
+  if (rg->prev < 0 && rg->next < 0) {  // a chain of one slab: nothing travels
+    rc = part(LBM_ADE_PART_FRAME, main);
+    return rc ? rc : part(LBM_ADE_PART_INNER, main);
+  }
+  // the ring's stream starts after everything enqueued on main so far (fo, go complete)
+  LBM_CHECK_HIP(hipEventRecord(rg->main_done, main));
+  LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
+  rc = part(LBM_ADE_PART_FRAME, rg->edge);
+  if (!rc) rc = part(LBM_ADE_PART_INNER, main);  // overlaps the exchange
+  if (!rc) rc = ring_exchange_depth(rg, fn_, gn, 1, rg->edge);
+  return rc ? rc : ring_join_main(rg, main);
+}
+
+int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after) {
+  LBM_REQUIRE(rg && lattice_a && lattice_b, "lbm_ring_exchange_pair: NULL argument");
+  LBM_REQUIRE(lattice_a != lattice_b, "lbm_ring_exchange_pair: the two lattices are the same");
+  LBM_REQUIRE(rg->g.ghost == 1, "lbm_ring_exchange_pair: ghost=%d: the pair travels with one ghost row per side (ring "
+              "slabs need ghost=1)", rg->g.ghost);
+  return ring_exchange_depth(rg, lattice_a, lattice_b, 1, after);
 }
 
 }  // extern "C"

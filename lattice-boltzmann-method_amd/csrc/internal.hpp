@@ -47,6 +47,15 @@ int box_copy(double* dst, const lbm_geom& dg, int dst_row, int dst_col, const do
 // (A stream that spares one compute unit for the chain -- hipExtStreamCreateWithCUMask -- was tried and is far slower:
 // profiles/r02_ibm_box_bench.log.)
 int make_background_stream(hipStream_t* out);
+// capi_ade.hip: the host checks of lbm_ade_stream_collide_part (slab geometries: ghost rows, HALO row edges; all of its
+// arguments / the geometry and parameters alone) and the collide-only launch on the owned rows of such a geometry (the first driver iteration of lbm_ring_ade_collide)
+int ade_part_check(const char* fn, const double* f_new, const double* g_new, const double* f_old, const double* g_old,
+                   const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                   int part, int edge_rows, const double* rho, const double* u, const double* conc);
+int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
+                      const lbm_ade_params* scalar);
+int ade_collide_slab(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
+                     const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, hipStream_t st);
 // NumPy .npy (v1.0, little-endian f64, C order) writer shared by the snapshot objects
 int write_npy(const char* path, const double* data, const std::vector<long>& shape);
 

@@ -1,0 +1,464 @@
+// Fluid + transported scalar (lbm_ade_*, the sediment loop of test/rectangle_sedimentation_test.cpp:88-247 without its
+// driver-specific edges) slab-decomposed along r: one ghost row per side, ONE packed message per neighbour per step
+// carrying the single-step halo of both lattices (2 x 3 rows), FRAME + pack + exchange on the ring's stream beside the
+// INNER rows (lbm_ring_ade_step).  C++ host on lbm_ring_* + lbm_ade_stream_collide_part; one process per GPU.
+//
+//   slab_ring_ade --spawn N [...]          fork N ranks on this node (rank i -> GPU i; --one-gpu 1: all on GPU 0,
+//                                          with --transport ipc: N real ranks sharing one device)
+//   RANK=i WORLD_SIZE=N LOCAL_RANK=i slab_ring_ade --id-file /tmp/x [...]   under any launcher
+//   slab_ring_ade --emulate N [...]        ONE process / one GPU playing all N slabs in turn: the same two part launches
+//                                          on the same two streams, the messages by device copies, per-slab time by HIP
+//                                          events, each step alternated with the step of one slab-sized single block
+//
+// Options: --rows R (per slab, weak scaling) --cols C --steps K --warmup W --edge-rows E --omega w --omega-g wg
+//          --walls 1 (bounce-back rows on the chain ends, bounce-back column 0, specular column C-1: a chain; default a
+//          closed, periodic ring)  --form ref|fast (both halves)  --check 1 (bitwise against one block: small sizes)
+//
+// Printed: one JSON line; ms per step of the slowest slab, and the one-block step of a slab-sized lattice beside it.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "common.hpp"
+#include "ring_common.hpp"
+
+namespace {
+
+struct Args {
+  int rows = 512, cols = 1024, steps = 50, warmup = 5, edge_rows = 16, check = 0, emulate = 0, walls = 0;
+  double omega = 1.2, omega_g = 1.7;
+  bool fast = true;
+  std::string id_file;
+};
+
+// shear wave + Taylor-Green vortices on the GLOBAL box, scalar: a Gaussian blob; f = feq(u, rho), g = feq(u + w, C) in
+// the reference's operation order (solver.cpp:51-62) -- the same bits for every decomposition
+const double kW[2] = {3e-3, 3e-3};
+void init_node(double* f9, double* g9, int gr, int c, int Rg, int C) {
+  const double pi = 3.14159265358979323846;
+  const double x = 2 * pi * gr / Rg, y = 2 * pi * c / C;
+  const double u0 = 0.03 * std::sin(x) * std::cos(y), u1 = 0.03 * std::sin(x) - 0.02 * std::cos(x) * std::sin(y);
+  const double rho = 1.0 + 0.01 * std::cos(2 * x);
+  const double dr = gr - 0.45 * Rg, dc = c - 0.55 * C, s = 0.12 * std::min(Rg, C);
+  const double conc = 1e-3 * std::exp(-(dr * dr + dc * dc) / (2 * s * s));
+  static const double w[9] = {4. / 9, 1. / 9, 1. / 9, 1. / 9, 1. / 9, 1. / 36, 1. / 36, 1. / 36, 1. / 36};
+  static const int cx[9] = {0, 1, 0, -1, 0, 1, -1, -1, 1}, cy[9] = {0, 0, 1, 0, -1, 1, 1, -1, -1};
+  auto feq = [&](double* e, double d, double a, double b) {
+    const double uu = a * a + b * b;
+    for (int q = 0; q < 9; ++q) {
+      const double cu = cx[q] * a + cy[q] * b;
+      e[q] = w[q] * d * (1.0 + 3.0 * cu + 4.5 * cu * cu - 1.5 * uu);
+    }
+  };
+  feq(f9, rho, u0, u1);
+  feq(g9, conc, u0 + kW[0], u1 + kW[1]);
+}
+
+// the plain compressible fluid and the scalar, both halves in the form of --form
+lbm_bgk_params fluid_params(const Args& a) {
+  lbm_bgk_params p{};
+  p.omega = a.omega;
+  p.form = a.fast ? LBM_FORM_REASSOCIATED : LBM_FORM_REFERENCE_ORDER;
+  return p;
+}
+lbm_ade_params scalar_params(const Args& a) {
+  return lbm_ade_params{a.omega_g, kW[0], kW[1], a.fast ? LBM_FORM_REASSOCIATED : LBM_FORM_REFERENCE_ORDER};
+}
+
+lbm_bc global_bc(const Args& a) {
+  lbm_bc b{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
+  if (a.walls) {
+    b.row_lo = b.row_hi = LBM_EDGE_BOUNCE_BACK;
+    b.col_lo = LBM_EDGE_BOUNCE_BACK;
+    b.col_hi = LBM_EDGE_SPECULAR;
+  }
+  return b;
+}
+
+// padded like the solver contexts' lattices (rows off a power-of-two stride, planes off a power-of-two size)
+lbm_geom padded_geom(int R, int C, int G) {
+  const int pitch = lbm_default_row_pitch(C);
+  long long plane = (long long)(R + 2 * G) * pitch + lbm_default_plane_pad(R + 2 * G, pitch);
+  plane += plane & 1;  // even: 16-byte accesses
+  return lbm_geom{R, C, G, plane, pitch > C ? pitch : 0};
+}
+
+// doubles per plane of a lattice (plane_stride 0 = dense: (R + 2 ghost) rows of the row pitch)
+size_t plane_doubles(const lbm_geom& g) {
+  if (g.plane_stride > 0) return (size_t)g.plane_stride;
+  return (size_t)(g.R + 2 * g.ghost) * (size_t)(g.row_pitch > 0 ? g.row_pitch : g.C);
+}
+
+double* alloc_lattice(const lbm_geom& g) {
+  const size_t bytes = plane_doubles(g) * 9 * 8;
+  if (bytes == 0) throw std::runtime_error("empty lattice");
+  double* p = nullptr;
+  check(lbm_malloc((void**)&p, bytes), "lbm_malloc");
+  check(lbm_memset(p, 0, bytes, nullptr), "memset");
+  return p;
+}
+
+// pre-collision f, g of global rows [row0, row0 + R) into lattices of geometry g (owned rows; the rest zero)
+void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
+  const int R = g.R, C = g.C;
+  const lbm_geom d{R, C, 0, 0, 0};
+  std::vector<double> hf((size_t)9 * R * C), hg((size_t)9 * R * C);
+  double f9[9], g9[9];
+  for (int r = 0; r < R; ++r)
+    for (int c = 0; c < C; ++c) {
+      init_node(f9, g9, row0 + r, c, Rg, C);
+      for (int q = 0; q < 9; ++q) {
+        hf[(size_t)q * R * C + (size_t)r * C + c] = f9[q];
+        hg[(size_t)q * R * C + (size_t)r * C + c] = g9[q];
+      }
+    }
+  double* stage = nullptr;
+  check(lbm_malloc((void**)&stage, hf.size() * 8), "lbm_malloc");
+  for (auto [dst, src] : {std::pair<double*, std::vector<double>*>{f, &hf}, {h, &hg}}) {
+    check(lbm_memset(dst, 0, plane_doubles(g) * 9 * 8, nullptr), "memset");
+    check(lbm_memcpy_h2d(stage, src->data(), src->size() * 8, nullptr), "h2d");
+    check(lbm_lattice_copy_rows(dst, &g, 0, stage, &d, 0, R, nullptr), "lbm_lattice_copy_rows");
+  }
+  check(lbm_stream_sync(nullptr), "sync");
+  lbm_free(stage);
+}
+
+// owned rows of a lattice as dense [9][R][C] on the host
+void owned_to_host(std::vector<double>& out, const double* lat, const lbm_geom& g) {
+  const lbm_geom d{g.R, g.C, 0, 0, 0};
+  double* dense = nullptr;
+  check(lbm_malloc((void**)&dense, (size_t)9 * g.R * g.C * 8), "lbm_malloc");
+  check(lbm_lattice_copy_rows(dense, &d, 0, lat, &g, 0, g.R, nullptr), "lbm_lattice_copy_rows");
+  out.resize((size_t)9 * g.R * g.C);
+  check(lbm_memcpy_d2h(out.data(), dense, out.size() * 8, nullptr), "d2h");
+  check(lbm_stream_sync(nullptr), "sync");
+  lbm_free(dense);
+}
+
+// One block of Rg x C (ghost 0, dense), collide-only + `steps` fused steps: the yardstick of --check.  Returns f, g of
+// the owned rows as dense [9][Rg][C] on the host.
+void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_params& sc, std::vector<double>& f_out,
+               std::vector<double>& g_out) {
+  const lbm_geom g{Rg, a.cols, 0, 0, 0};
+  const lbm_bc bc = global_bc(a);
+  double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
+  upload_rows(f[0], h[0], g, 0, Rg);
+  check(lbm_ade_collide(f[1], h[1], f[0], h[0], &g, &bc, &fl, &sc, nullptr, nullptr, nullptr, nullptr), "lbm_ade_collide");
+  int cur = 1;
+  for (int t = 0; t < a.warmup + a.steps; ++t, cur ^= 1)
+    check(lbm_ade_stream_collide(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, 0, Rg, nullptr, nullptr, nullptr,
+                                 nullptr), "lbm_ade_stream_collide");
+  owned_to_host(f_out, f[cur], g);
+  owned_to_host(g_out, h[cur], g);
+  for (int k = 0; k < 2; ++k) {
+    lbm_free(f[k]);
+    lbm_free(h[k]);
+  }
+}
+
+// The one-block step of a slab-sized lattice (R x C, ghost 0, periodic, padded as the solver context pads): ms per step
+struct SlabSizedBlock {
+  lbm_geom g;
+  double *f[2], *h[2];
+  int cur = 0;
+  void* ev[2];
+  double ms = 0;
+  SlabSizedBlock(int R, int C) : g(padded_geom(R, C, 0)) {
+    for (int k = 0; k < 2; ++k) {
+      f[k] = alloc_lattice(g);
+      h[k] = alloc_lattice(g);
+      check(lbm_event_create(&ev[k]), "lbm_event_create");
+    }
+    upload_rows(f[0], h[0], g, 0, R);
+  }
+  void step(const lbm_bgk_params& fl, const lbm_ade_params& sc, bool timed) {
+    check(lbm_event_record(ev[0], nullptr), "event");
+    check(lbm_ade_stream_collide(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, nullptr, &fl, &sc, 0, g.R, nullptr, nullptr,
+                                 nullptr, nullptr), "lbm_ade_stream_collide");
+    check(lbm_event_record(ev[1], nullptr), "event");
+    float m = 0;
+    check(lbm_event_elapsed_ms(&m, ev[0], ev[1]), "elapsed");
+    if (timed) ms += m;
+    cur ^= 1;
+  }
+  ~SlabSizedBlock() {
+    for (int k = 0; k < 2; ++k) {
+      lbm_free(f[k]);
+      lbm_free(h[k]);
+      lbm_event_destroy(ev[k]);
+    }
+  }
+};
+
+const char* check_field(const Args& a, int bad) {
+  return !a.check ? "" : (bad ? ", \"check\": \"MISMATCH\"" : ", \"check\": \"bitwise equal to one block\"");
+}
+
+// --emulate N: every slab in turn on ONE GPU.  A slab's step is what lbm_ring_ade_step enqueues -- FRAME on the ring's
+// stream, INNER on the main stream beside it, the pack behind FRAME -- with the messages (both lattices, 2 x 3 rows per
+// side) as device copies between the steps.  Slab k's edges: the global box's, seams HALO (both row edges of a closed
+// ring).  The initial state is the one block's post-collision state, scattered into the slabs with their ghost rows.
+int run_emulated(const Args& a, int N) {
+  check(lbm_set_device(0), "lbm_set_device");
+  const int R = a.rows, C = a.cols, Rg = R * N, E = a.edge_rows;
+  if (E < 1 || 2 * E >= R) throw std::runtime_error("--edge-rows must satisfy 1 <= E and 2 E < rows");
+  const lbm_bgk_params fl = fluid_params(a);
+  const lbm_ade_params sc = scalar_params(a);
+  const lbm_bc gbc = global_bc(a);
+  const bool closed = !a.walls;
+  const lbm_geom g = padded_geom(R, C, 1);
+  const size_t msg = (size_t)lbm_halo_rows(1) * C;  // per lattice
+  struct Slab {
+    lbm_bc bc;
+    double *f[2], *h[2];
+    double* buf[2][2];  // [side][send / recv]: f then g
+    bool prev, next;
+    void* ev[2];
+    double ms = 0;
+  };
+  std::vector<Slab> S(N);
+  {
+    // the one block's post-collision state (lbm_ade_collide on the global lattice), scattered into the slabs
+    const lbm_geom gg{Rg, C, 0, 0, 0};
+    double *f0 = alloc_lattice(gg), *h0 = alloc_lattice(gg), *fp = alloc_lattice(gg), *hp = alloc_lattice(gg);
+    upload_rows(f0, h0, gg, 0, Rg);
+    check(lbm_ade_collide(fp, hp, f0, h0, &gg, &gbc, &fl, &sc, nullptr, nullptr, nullptr, nullptr), "lbm_ade_collide");
+    for (int k = 0; k < N; ++k) {
+      Slab& s = S[k];
+      s.prev = closed || k > 0;
+      s.next = closed || k < N - 1;
+      s.bc = gbc;
+      if (s.prev) s.bc.row_lo = LBM_EDGE_HALO;
+      if (s.next) s.bc.row_hi = LBM_EDGE_HALO;
+      for (int b = 0; b < 2; ++b) {
+        s.f[b] = alloc_lattice(g);
+        s.h[b] = alloc_lattice(g);
+        check(lbm_event_create(&s.ev[b]), "lbm_event_create");
+        for (int x = 0; x < 2; ++x) check(lbm_malloc((void**)&s.buf[b][x], 2 * msg * 8), "lbm_malloc");
+      }
+      // owned rows and the ghost rows beside them (wrapping on a closed ring): the exchange would bring the same bits
+      for (int r = -1; r <= R; ++r) {
+        const int gr = k * R + r;
+        if (gr < 0 && !closed) continue;
+        if (gr >= Rg && !closed) continue;
+        const int src = (gr + Rg) % Rg;
+        check(lbm_lattice_copy_rows(s.f[0], &g, r, fp, &gg, src, 1, nullptr), "lbm_lattice_copy_rows");
+        check(lbm_lattice_copy_rows(s.h[0], &g, r, hp, &gg, src, 1, nullptr), "lbm_lattice_copy_rows");
+      }
+    }
+    check(lbm_stream_sync(nullptr), "sync");
+    for (double* p : {f0, h0, fp, hp}) lbm_free(p);
+  }
+  lbm_stream_t edge = nullptr;
+  check(lbm_stream_create(&edge), "lbm_stream_create");
+  void *ev_fork = nullptr, *ev_join = nullptr;
+  check(lbm_event_create(&ev_fork), "lbm_event_create");
+  check(lbm_event_create(&ev_join), "lbm_event_create");
+  SlabSizedBlock block(R, C);
+  auto part = [&](Slab& s, int cur, int which, lbm_stream_t st) {
+    check(lbm_ade_stream_collide_part(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc, which, E, nullptr,
+                                      nullptr, nullptr, st), "lbm_ade_stream_collide_part");
+  };
+  auto pack = [&](Slab& s, double* f, double* h, lbm_stream_t st) {
+    if (s.prev) {
+      check(lbm_halo_pack(s.buf[0][0], f, &g, 1, 0, st), "lbm_halo_pack");
+      check(lbm_halo_pack(s.buf[0][0] + msg, h, &g, 1, 0, st), "lbm_halo_pack");
+    }
+    if (s.next) {
+      check(lbm_halo_pack(s.buf[1][0], f, &g, 1, 1, st), "lbm_halo_pack");
+      check(lbm_halo_pack(s.buf[1][0] + msg, h, &g, 1, 1, st), "lbm_halo_pack");
+    }
+  };
+  int cur = 0;
+  for (int i = 0; i < a.warmup + a.steps; ++i) {
+    for (int k = 0; k < N; ++k) {
+      Slab& s = S[k];
+      check(lbm_event_record(s.ev[0], nullptr), "event");
+      if (s.prev || s.next) {
+        check(lbm_event_record(ev_fork, nullptr), "event");
+        check(lbm_stream_wait_event(edge, ev_fork), "wait");
+        part(s, cur, LBM_ADE_PART_FRAME, edge);
+        part(s, cur, LBM_ADE_PART_INNER, nullptr);
+        pack(s, s.f[cur ^ 1], s.h[cur ^ 1], edge);
+        check(lbm_event_record(ev_join, edge), "event");
+        check(lbm_stream_wait_event(nullptr, ev_join), "wait");
+      } else {
+        part(s, cur, LBM_ADE_PART_FRAME, nullptr);
+        part(s, cur, LBM_ADE_PART_INNER, nullptr);
+      }
+      check(lbm_event_record(s.ev[1], nullptr), "event");
+    }
+    // deliver: slab k's side-1 message is slab k+1's side-0 input and vice versa
+    for (int k = 0; k < N; ++k) {
+      const int n = (k + 1) % N;
+      if (!S[k].next) continue;
+      check(lbm_memcpy_d2d(S[n].buf[0][1], S[k].buf[1][0], 2 * msg * 8, nullptr), "d2d");
+      check(lbm_memcpy_d2d(S[k].buf[1][1], S[n].buf[0][0], 2 * msg * 8, nullptr), "d2d");
+    }
+    for (int k = 0; k < N; ++k) {
+      Slab& s = S[k];
+      for (int side = 0; side < 2; ++side) {
+        if (!(side ? s.next : s.prev)) continue;
+        check(lbm_halo_unpack(s.f[cur ^ 1], s.buf[side][1], &g, 1, side, nullptr), "lbm_halo_unpack");
+        check(lbm_halo_unpack(s.h[cur ^ 1], s.buf[side][1] + msg, &g, 1, side, nullptr), "lbm_halo_unpack");
+      }
+      float m = 0;
+      check(lbm_event_elapsed_ms(&m, s.ev[0], s.ev[1]), "elapsed");
+      if (i >= a.warmup) s.ms += m;
+    }
+    block.step(fl, sc, i >= a.warmup);  // alternated with the chain's step
+    cur ^= 1;
+  }
+  check(lbm_stream_sync(edge), "sync");
+  lbm_stream_destroy(edge);
+  lbm_event_destroy(ev_fork);
+  lbm_event_destroy(ev_join);
+  int bad = 0;
+  if (a.check) {
+    std::vector<double> wf, wg, got;
+    one_block(a, Rg, fl, sc, wf, wg);
+    for (int k = 0; k < N; ++k)
+      for (int lat = 0; lat < 2; ++lat) {
+        owned_to_host(got, lat ? S[k].h[cur] : S[k].f[cur], g);
+        const std::vector<double>& want = lat ? wg : wf;
+        for (int q = 0; q < 9; ++q)
+          if (std::memcmp(&got[(size_t)q * R * C], &want[(size_t)q * Rg * C + (size_t)k * R * C], (size_t)R * C * 8) != 0) ++bad;
+      }
+  }
+  double slowest = 0;
+  for (auto& s : S) slowest = std::max(slowest, s.ms / a.steps);
+  const double blk = block.ms / a.steps;
+  std::printf("{\"driver\": \"slab_ring_ade\", \"mode\": \"emulated %s on one GPU\", \"slabs\": %d, \"rows_per_slab\": %d, "
+              "\"cols\": %d, \"global_rows\": %d, \"walls\": %d, \"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, "
+              "\"message_rows_per_side\": %d, \"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, "
+              "\"slab_rate_over_one_block\": %.3f, \"per_slab_ms\": [",
+              closed ? "closed ring" : "chain", N, R, C, Rg, a.walls, a.fast ? "fast" : "ref", a.steps, E,
+              2 * lbm_halo_rows(1), slowest, blk, blk / slowest);
+  for (int k = 0; k < N; ++k) std::printf("%s%.4f", k ? ", " : "", S[k].ms / a.steps);
+  std::printf("]%s}\n", check_field(a, bad));
+  std::fflush(stdout);
+  for (auto& s : S)
+    for (int b = 0; b < 2; ++b) {
+      lbm_free(s.f[b]);
+      lbm_free(s.h[b]);
+      lbm_event_destroy(s.ev[b]);
+      for (int x = 0; x < 2; ++x) lbm_free(s.buf[b][x]);
+    }
+  return bad ? 3 : 0;
+}
+
+int run_rank(const Args& a, int rank, int world, int local_rank) {
+  check(lbm_set_device(std::getenv("LBM_ONE_GPU") ? 0 : local_rank), "lbm_set_device");
+  const int R = a.rows, C = a.cols, Rg = R * world;
+  const lbm_bgk_params fl = fluid_params(a);
+  const lbm_ade_params sc = scalar_params(a);
+  const lbm_bc gbc = global_bc(a);
+  const lbm_geom g = padded_geom(R, C, 1);
+  unsigned char id[128];
+  share_unique_id(id, rank, world, a.id_file);
+  lbm_ring* ring = nullptr;
+  check(lbm_ring_create(&ring, id, rank, world, &g, /*periodic=*/a.walls ? 0 : 1), "lbm_ring_create");
+  double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
+  upload_rows(f[1], h[1], g, rank * R, Rg);  // pre-collision, then the first driver iteration: collide + one exchange
+  check(lbm_ring_ade_collide(ring, f[0], h[0], f[1], h[1], &gbc, &fl, &sc, nullptr), "lbm_ring_ade_collide");
+  int cur = 0;
+  auto step = [&]() {
+    check(lbm_ring_ade_step(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, a.edge_rows, nullptr),
+          "lbm_ring_ade_step");
+    cur ^= 1;
+  };
+  for (int i = 0; i < a.warmup; ++i) step();
+  check(lbm_stream_sync(nullptr), "sync");
+  auto t0 = std::chrono::steady_clock::now();
+  for (int i = 0; i < a.steps; ++i) step();
+  check(lbm_stream_sync(nullptr), "sync");
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (const int failed = ring_failed(ring, "slab_ring_ade", rank)) return failed;
+  const double tmax = max_time_over_ranks(sec, rank, world, a.id_file);
+
+  int bad = 0;
+  if (a.check) {
+    std::vector<double> own[2];
+    owned_to_host(own[0], f[cur], g);
+    owned_to_host(own[1], h[cur], g);
+    for (int lat = 0; lat < 2; ++lat)
+      write_file_atomic(a.id_file + (lat ? ".g" : ".f") + std::to_string(rank), own[lat].data(), own[lat].size() * 8);
+    if (rank == 0) {
+      std::vector<double> want[2];
+      one_block(a, Rg, fl, sc, want[0], want[1]);
+      for (int r = 0; r < world; ++r)
+        for (int lat = 0; lat < 2; ++lat) {
+          wait_file(a.id_file + (lat ? ".g" : ".f") + std::to_string(r), own[lat].data(), own[lat].size() * 8);
+          for (int q = 0; q < 9; ++q)
+            if (std::memcmp(&own[lat][(size_t)q * R * C], &want[lat][(size_t)q * Rg * C + (size_t)r * R * C], (size_t)R * C * 8) != 0)
+              ++bad;
+        }
+    }
+  }
+  if (rank == 0) {
+    // the one-block step of a slab-sized lattice on this GPU, after the ring's run
+    SlabSizedBlock block(R, C);
+    for (int i = 0; i < a.warmup + a.steps; ++i) block.step(fl, sc, i >= a.warmup);
+    const double ms = 1e3 * tmax / a.steps, blk = block.ms / a.steps;
+    std::printf("{\"driver\": \"slab_ring_ade\", \"n_gpus\": %d, \"rows_per_gpu\": %d, \"cols\": %d, \"walls\": %d, "
+                "\"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, \"message_rows_per_side\": %d, "
+                "\"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, "
+                "\"mlups\": %.1f%s}\n",
+                world, R, C, a.walls, a.fast ? "fast" : "ref", a.steps, a.edge_rows, 2 * lbm_halo_rows(1), ms, blk, blk / ms,
+                (double)Rg * C / (ms * 1e3), check_field(a, bad));
+    std::fflush(stdout);
+  }
+  lbm_ring_destroy(ring);
+  for (int k = 0; k < 2; ++k) {
+    lbm_free(f[k]);
+    lbm_free(h[k]);
+  }
+  return bad ? 3 : 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  Args a;
+  a.rows = std::atoi(arg_value(argc, argv, "--rows", "512").c_str());
+  a.cols = std::atoi(arg_value(argc, argv, "--cols", "1024").c_str());
+  a.steps = std::max(1, std::atoi(arg_value(argc, argv, "--steps", "50").c_str()));
+  a.warmup = std::max(0, std::atoi(arg_value(argc, argv, "--warmup", "5").c_str()));
+  a.edge_rows = std::atoi(arg_value(argc, argv, "--edge-rows", "16").c_str());
+  a.check = std::atoi(arg_value(argc, argv, "--check", "0").c_str());
+  a.walls = std::atoi(arg_value(argc, argv, "--walls", "0").c_str());
+  a.emulate = std::atoi(arg_value(argc, argv, "--emulate", "0").c_str());
+  a.omega = std::atof(arg_value(argc, argv, "--omega", "1.2").c_str());
+  a.omega_g = std::atof(arg_value(argc, argv, "--omega-g", "1.7").c_str());
+  const std::string form = arg_value(argc, argv, "--form", "fast");
+  if (form != "fast" && form != "ref") {
+    std::fprintf(stderr, "slab_ring_ade: --form ref|fast\n");
+    return 2;
+  }
+  a.fast = form == "fast";
+  const std::string transport = arg_value(argc, argv, "--transport", "");
+  if (!transport.empty()) setenv("LBM_RING_TRANSPORT", transport.c_str(), 1);  // lbm_ring_unique_id / lbm_ring_create follow it
+  if (std::atoi(arg_value(argc, argv, "--one-gpu", "0").c_str())) setenv("LBM_ONE_GPU", "1", 1);
+  a.id_file = arg_value(argc, argv, "--id-file", "/tmp/lbm_ring_id." + std::to_string((long)getpid()));
+  const int spawn = std::atoi(arg_value(argc, argv, "--spawn", "0").c_str());
+  try {
+    if (a.emulate > 0) return run_emulated(a, a.emulate);
+    if (spawn > 0) {
+      cleanup_ring_files(a.id_file, spawn);  // a stale id file of a killed run must not be picked up
+      const int rc = spawn_ranks(spawn, [&](int r) { return run_rank(a, r, spawn, r); });
+      cleanup_ring_files(a.id_file, spawn);
+      return rc;
+    }
+    const char* er = std::getenv("RANK");
+    const char* ew = std::getenv("WORLD_SIZE");
+    const char* el = std::getenv("LOCAL_RANK");
+    const int rank = er ? std::atoi(er) : 0, world = ew ? std::atoi(ew) : 1;
+    return run_rank(a, rank, world, el ? std::atoi(el) : rank);
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "slab_ring_ade: %s\n", e.what());
+    return 1;
+  }
+}

@@ -22,6 +22,7 @@ MODEL_BGK, MODEL_KBC = 0, 1
 FORM_DEFAULT, FORM_REFERENCE_ORDER, FORM_REASSOCIATED = 0, 1, 2   # field `form` of the parameter structs (LBM_FORM_*)
 RING_DEFAULT, RING_RCCL, RING_IPC = -1, 0, 1
 CG_PART_FRAME, CG_PART_INNER = 1, 2   # lbm_cg_step_fused_part (LBM_CG_PART_*)
+ADE_PART_FRAME, ADE_PART_INNER = 1, 2  # lbm_ade_stream_collide_part (LBM_ADE_PART_*)
 
 _dp = ct.POINTER(ct.c_double)
 

@@ -1,0 +1,415 @@
+"""GPU suite, the fluid + scalar step over row slabs: lbm_ade_stream_collide_part (FRAME / INNER, one dispatch each,
+wall fix-ups inline), lbm_ring_ade_collide / lbm_ring_ade_step / lbm_ring_exchange_pair and the slab_ring_ade driver.
+
+The yardstick is one block: lbm_ade_stream_collide on the global lattice (pinned to the reference loop bit for bit in
+tests/test_gpu_ade.py).  Post-collision f and g are compared BITWISE on every owned node:
+  * FRAME + INNER == the full step, on single blocks and on ghost-1 slabs cut from the global lattice;
+  * each part alone writes exactly its rows, nothing of the ghost rows or the padding (NaN-poisoned destinations);
+  * chains / rings of 2..4 slabs, halos moved by lbm_halo_pack / _unpack on both lattices, == one block;
+  * real rank processes over the peer-mapped transport (tests/ade_ring_rank.py) == one block;
+  * the driver's own --check; and the scalar's mass and transport across the seams."""
+import ctypes as ct
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+import pylbm  # noqa: E402
+from gpu_util import dev  # noqa: E402
+from pylbm import _ptr  # noqa: E402
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+BIN = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin")
+REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
+FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
+BB, SP, HALO, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR, pylbm.EDGE_HALO, pylbm.EDGE_PERIODIC
+SENTINEL = 0x7FF8DEADBEEF5A5A  # a quiet NaN no kernel computes: "never written"
+PLANE_PAD = 40                 # doubles behind every plane (even: 16-byte alignment kept)
+W9 = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
+W = (3e-3, 3e-3)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    lib = pylbm.Lib()
+    assert lib.device_count() >= 1, "no HIP device visible"
+    return lib
+
+
+def params(form, w=W, omega=1.2, omega_g=1.7):
+    return pylbm.BgkParams(omega, 0, form=form), pylbm.AdeParams(omega_g, w, form=form)
+
+
+def wall_bc(walls):
+    return pylbm.Bc(row_lo=BB, row_hi=BB, col_lo=BB, col_hi=SP) if walls else pylbm.Bc.periodic()
+
+
+# ---- lattices ------------------------------------------------------------------------------------------------------------
+def geom(R, C, ghost, pitch=0):
+    P = pitch or C
+    return pylbm.Geom(R, C, ghost, (R + 2 * ghost) * P + PLANE_PAD, pitch)
+
+
+def pitch_of(C):
+    return C + 16 if C >= 1024 else 0  # 1040 columns: a padded row pitch
+
+
+def alloc(g):
+    return torch.zeros(9 * g.plane_stride, dtype=torch.float64, device=dev())
+
+
+def rows_view(t, g):
+    """[9, R + 2 ghost, C] view: every stored row (ghost rows included) of a flat lattice"""
+    P = g.row_pitch or g.C
+    return t.view(9, g.plane_stride)[:, :(g.R + 2 * g.ghost) * P].view(9, g.R + 2 * g.ghost, P)[:, :, :g.C]
+
+
+def owned(t, g):
+    return rows_view(t, g)[:, g.ghost:g.ghost + g.R]
+
+
+def random_lattice(g, seed):
+    """a finite post-collision-like lattice: every double of the allocation near w_q"""
+    rng = np.random.default_rng(seed)
+    a = np.repeat(W9, g.plane_stride).reshape(9, g.plane_stride) * (1.0 + 0.05 * rng.random((9, g.plane_stride)))
+    return torch.from_numpy(a.reshape(-1)).to(dev())
+
+
+def bits(t):
+    return t.view(torch.int64)
+
+
+def assert_bits(got, want, what):
+    bad = torch.nonzero(bits(got) != bits(want))
+    assert bad.numel() == 0, f"{what}: {bad.shape[0]} doubles differ; first at {tuple(bad[0].tolist())}"
+
+
+def full_step(lib, g, bc, prm, fo, go):
+    fn, gn = alloc(g), alloc(g)
+    lib.ade_stream_collide(_ptr(fn), _ptr(gn), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
+                           ct.byref(prm[1]), 0, g.R, None, None, None, None)
+    return fn, gn
+
+
+def part(lib, g, bc, prm, dst, src, which, E, stream=None):
+    lib.ade_stream_collide_part(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
+                                ct.byref(prm[0]), ct.byref(prm[1]), which, E, None, None, None, None,
+                                pylbm._stream(stream))
+
+
+def cut_slab(glob, gg, r0, r1, pitch, closed):
+    """ghost-1 slab of global rows [r0, r1): owned rows and the ghost rows beside them (wrapped on a closed domain;
+    left poisoned beyond a wall end -- nothing may read them)"""
+    sg = geom(r1 - r0, gg.C, 1, pitch)
+    t = alloc(sg)
+    bits(t).fill_(SENTINEL)
+    rv, src = rows_view(t, sg), owned(glob, gg)
+    rv[:, 1:1 + sg.R] = src[:, r0:r1]
+    for slab_row, grow in ((0, r0 - 1), (sg.R + 1, r1)):
+        if 0 <= grow < gg.R or closed:
+            rv[:, slab_row] = src[:, grow % gg.R]
+    return sg, t
+
+
+# ---- 1. FRAME + INNER == the full step -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", [REF, FAST])
+@pytest.mark.parametrize("walls", [0, 1])
+def test_frame_plus_inner_is_the_full_step_on_one_block(lib, form, walls):
+    prm, bc = params(form), wall_bc(walls)
+    for R in (64, 130, 257):
+        for C in (96, 200, 1040):
+            g = geom(R, C, 0, pitch_of(C))
+            src = (random_lattice(g, R + C), random_lattice(g, R * C))
+            want = full_step(lib, g, bc, prm, *src)
+            for E in (1, 3, 16, 40):
+                if 2 * E >= R:
+                    continue
+                dst = (alloc(g), alloc(g))
+                part(lib, g, bc, prm, dst, src, FRAME, E)
+                part(lib, g, bc, prm, dst, src, INNER, E)
+                torch.cuda.synchronize()
+                for k in range(2):
+                    assert_bits(owned(dst[k], g), owned(want[k], g), f"R={R} C={C} E={E} walls={walls} lattice {k}")
+
+
+@pytest.mark.parametrize("form", [REF, FAST])
+@pytest.mark.parametrize("walls", [0, 1])
+def test_frame_plus_inner_on_slabs_cut_from_the_global_lattice(lib, form, walls):
+    """ghost-1 slabs (HALO on one or both sides, the global walls on a chain end) == the global step on their rows"""
+    prm, gbc = params(form), wall_bc(walls)
+    for R in (64, 130, 257):
+        for C in (96, 200, 1040):
+            gg = geom(R, C, 0, pitch_of(C))
+            src = (random_lattice(gg, R + 7 * C), random_lattice(gg, 3 * R + C))
+            want = full_step(lib, gg, gbc, prm, *src)
+            h = R // 2
+            for r0, r1 in ((0, h), (h, R), (R // 4, R // 4 + h)):
+                bc = pylbm.Bc(row_lo=gbc.row_lo if (r0 == 0 and walls) else HALO,
+                              row_hi=gbc.row_hi if (r1 == R and walls) else HALO, col_lo=gbc.col_lo, col_hi=gbc.col_hi)
+                slab = [cut_slab(s, gg, r0, r1, pitch_of(C), not walls) for s in src]
+                sg = slab[0][0]
+                for E in (1, 3, 16, 40):
+                    if 2 * E >= sg.R:
+                        continue
+                    dst = (alloc(sg), alloc(sg))
+                    part(lib, sg, bc, prm, dst, (slab[0][1], slab[1][1]), FRAME, E)
+                    part(lib, sg, bc, prm, dst, (slab[0][1], slab[1][1]), INNER, E)
+                    torch.cuda.synchronize()
+                    for k in range(2):
+                        assert_bits(owned(dst[k], sg), owned(want[k], gg)[:, r0:r1],
+                                    f"R={R} C={C} slab [{r0}, {r1}) E={E} walls={walls} lattice {k}")
+
+
+# ---- 2. write sets -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("R,C,E", [(64, 96, 1), (64, 96, 16), (130, 200, 3), (130, 1040, 40), (50, 200, 16),
+                                   (57, 96, 28), (131, 200, 64), (33, 96, 5)])
+@pytest.mark.parametrize("walls", [0, 1])
+def test_each_part_alone_writes_exactly_its_rows(lib, R, C, E, walls):
+    """NaN-poisoned destinations, ghost rows and row / plane padding included: the changed doubles of both lattices in
+    all 9 planes are exactly the part's rows, each bit-equal to the full-range call"""
+    assert 2 * E < R
+    prm = params(FAST)
+    # a chain-end slab with walls (bounce-back row 0, wall columns) or a middle slab (HALO both sides)
+    bc = pylbm.Bc(row_lo=BB if walls else HALO, row_hi=HALO, col_lo=BB if walls else PER, col_hi=SP if walls else PER)
+    g = geom(R, C, 1, pitch_of(C))
+    src = (random_lattice(g, R), random_lattice(g, C))
+    want = [alloc(g), alloc(g)]
+    part(lib, g, bc, prm, want, src, FRAME, E)
+    part(lib, g, bc, prm, want, src, INNER, E)
+    for which, rows in ((FRAME, list(range(E)) + list(range(R - E, R))), (INNER, list(range(E, R - E)))):
+        dst = (alloc(g), alloc(g))
+        for d in dst:
+            bits(d).fill_(SENTINEL)
+        torch.cuda.synchronize()
+        part(lib, g, bc, prm, dst, src, which, E)
+        torch.cuda.synchronize()
+        expect = torch.zeros(9 * g.plane_stride, dtype=torch.bool, device=dev())
+        owned(expect, g)[:, rows] = True
+        for k in range(2):
+            changed = bits(dst[k]) != SENTINEL
+            wrong = torch.nonzero(changed != expect)
+            what = f"{'FRAME' if which == FRAME else 'INNER'} R={R} C={C} E={E} walls={walls} lattice {k}"
+            assert wrong.numel() == 0, f"{what}: {wrong.shape[0]} doubles wrong, first flat index {int(wrong[0, 0])} " \
+                                       f"({'missed' if bool(expect[int(wrong[0, 0])]) else 'over-written'})"
+            diff = torch.nonzero(expect & (bits(dst[k]) != bits(want[k])))
+            assert diff.numel() == 0, f"{what}: {diff.shape[0]} written doubles differ from the full call"
+
+
+# ---- 3. chains and rings of slabs in one process -------------------------------------------------------------------------
+def global_state(lib, oracle, Rg, C, seed=0, w=W, conc_rows=None):
+    """pre-collision f, g of the global box (dense SoA, ghost 0): a shear wave with noise, the scalar a Gaussian blob
+    (or, with conc_rows = (a, b), a blob confined to rows [a, b): exactly zero elsewhere)"""
+    rng = np.random.default_rng(seed)
+    r, c = np.meshgrid(np.arange(Rg, dtype=float), np.arange(C, dtype=float), indexing="ij")
+    u = np.zeros((Rg, C, 2))
+    u[..., 1] = 0.03 * np.sin(2 * np.pi * r / Rg)
+    u += 0.005 * rng.standard_normal((Rg, C, 2))
+    rho = 1 + 0.01 * rng.standard_normal((Rg, C))
+    f = oracle.equilibrium(u, rho) * (1 + 0.005 * rng.standard_normal((Rg, C, 9)))
+    s = 0.15 * min(Rg, C)
+    if conc_rows is None:
+        conc = 1e-3 * np.exp(-((r - 0.4 * Rg) ** 2 + (c - 0.55 * C) ** 2) / (2 * s * s))
+    else:
+        a, b = conc_rows
+        conc = np.where((r >= a) & (r < b), 1e-3 * np.exp(-((r - (a + b) / 2) ** 2 + (c - C / 2) ** 2) / (2 * s * s)), 0.0)
+    g = oracle.equilibrium(u + np.asarray(w), conc)
+    gg = geom(Rg, C, 0)
+    out = []
+    for a in (f, g):
+        t = alloc(gg)
+        owned(t, gg)[:] = torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1))).to(dev())
+        out.append(t)
+    return gg, out
+
+
+class Chain:
+    """slabs of the given heights of one global box, every slab in turn on this GPU: FRAME + INNER, then the single-step
+    halo of BOTH lattices by lbm_halo_pack -> device copy -> lbm_halo_unpack"""
+
+    def __init__(self, lib, gg, post, heights, closed, gbc, prm, C_pitch=0):
+        self.lib, self.prm, self.closed, self.n = lib, prm, closed, len(heights)
+        self.r0 = np.concatenate([[0], np.cumsum(heights)]).tolist()
+        self.slabs = []
+        for k in range(self.n):
+            a, b = self.r0[k], self.r0[k + 1]
+            bc = pylbm.Bc(row_lo=HALO if (closed or k > 0) else gbc.row_lo,
+                          row_hi=HALO if (closed or k < self.n - 1) else gbc.row_hi, col_lo=gbc.col_lo, col_hi=gbc.col_hi)
+            cut = [cut_slab(p, gg, a, b, C_pitch, closed) for p in post]
+            g = cut[0][0]
+            self.slabs.append(dict(g=g, bc=bc, lat=[[cut[0][1], cut[1][1]], [alloc(g), alloc(g)]]))
+        self.msg = lib.raw.lbm_halo_rows(1) * gg.C
+        self.cur = 0
+
+    def step(self, E):
+        lib, cur = self.lib, self.cur
+        for s in self.slabs:
+            e = min(E, (s["g"].R - 1) // 2)
+            part(lib, s["g"], s["bc"], self.prm, s["lat"][cur ^ 1], s["lat"][cur], FRAME, e)
+            part(lib, s["g"], s["bc"], self.prm, s["lat"][cur ^ 1], s["lat"][cur], INNER, e)
+        n = self.n
+        for k in range(n):
+            nx = (k + 1) % n
+            if not self.closed and k == n - 1:
+                continue
+            a, b = self.slabs[k], self.slabs[nx]
+            for j in range(2):
+                down = torch.empty(self.msg, dtype=torch.float64, device=dev())
+                up = torch.empty(self.msg, dtype=torch.float64, device=dev())
+                lib.halo_pack(_ptr(down), _ptr(a["lat"][cur ^ 1][j]), ct.byref(a["g"]), 1, 1, None)
+                lib.halo_pack(_ptr(up), _ptr(b["lat"][cur ^ 1][j]), ct.byref(b["g"]), 1, 0, None)
+                lib.halo_unpack(_ptr(b["lat"][cur ^ 1][j]), _ptr(down), ct.byref(b["g"]), 1, 0, None)
+                lib.halo_unpack(_ptr(a["lat"][cur ^ 1][j]), _ptr(up), ct.byref(a["g"]), 1, 1, None)
+        self.cur ^= 1
+
+    def gather(self, j):
+        return torch.cat([owned(s["lat"][self.cur][j], s["g"]) for s in self.slabs], dim=1)
+
+
+def one_block(lib, gg, pre, gbc, prm, steps):
+    """lbm_ade_collide + `steps` x lbm_ade_stream_collide on the global lattice: (post-collision state, after steps)"""
+    post = [alloc(gg), alloc(gg)]
+    lib.ade_collide(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(gg), ct.byref(gbc),
+                    ct.byref(prm[0]), ct.byref(prm[1]), None, None, None, None)
+    cur = [t.clone() for t in post]
+    for _ in range(steps):
+        cur = list(full_step(lib, gg, gbc, prm, *cur))
+    torch.cuda.synchronize()
+    return post, cur
+
+
+@pytest.mark.parametrize("form", [REF, FAST])
+@pytest.mark.parametrize("closed", [True, False])
+@pytest.mark.parametrize("heights,C", [((64, 64), 96), ((48, 48, 48), 200), ((40, 40, 40, 40), 96), ((50, 130), 200),
+                                       ((130, 50, 130), 200)])
+def test_emulated_chain_equals_one_block(lib, oracle, form, closed, heights, C):
+    prm, gbc = params(form), (pylbm.Bc.periodic() if closed else wall_bc(True))
+    Rg, steps = sum(heights), 53
+    gg, pre = global_state(lib, oracle, Rg, C)
+    post, want = one_block(lib, gg, pre, gbc, prm, steps)
+    ch = Chain(lib, gg, post, heights, closed, gbc, prm)
+    for _ in range(steps):
+        ch.step(16)
+    torch.cuda.synchronize()
+    for j in range(2):
+        assert_bits(ch.gather(j), owned(want[j], gg), f"{len(heights)} slabs {heights} closed={closed} lattice {j}")
+
+
+# ---- 4. real rank processes ----------------------------------------------------------------------------------------------
+def run_ranks(lib, tmp_path, n, cfg, arrays, timeout=240):
+    """n processes of tests/ade_ring_rank.py on this GPU over the peer-mapped transport; a failing rank ends the rest"""
+    work = str(tmp_path)
+    json.dump(cfg, open(os.path.join(work, "cfg.json"), "w"))
+    ident = (ct.c_ubyte * 128)()
+    lib.ring_unique_id_ex(ident, pylbm.RING_IPC)
+    open(os.path.join(work, "id.bin"), "wb").write(bytes(ident))
+    for k, a in arrays.items():
+        np.save(os.path.join(work, k + ".npy"), a)
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    procs = []
+    for r in range(n):
+        log = open(os.path.join(work, f"rank{r}.log"), "w")
+        procs.append((subprocess.Popen([sys.executable, os.path.join(HERE, "ade_ring_rank.py"), str(r), str(n), work],
+                                       stdout=log, stderr=subprocess.STDOUT, env=env), log))
+    t0, failed = time.time(), None
+    while any(p.poll() is None for p, _ in procs):
+        bad = [r for r, (p, _) in enumerate(procs) if p.poll() not in (None, 0)]
+        if bad or time.time() - t0 > timeout:
+            failed = f"rank(s) {bad} failed" if bad else f"timed out after {timeout} s"
+            for p, _ in procs:
+                if p.poll() is None:
+                    p.kill()
+            break
+        time.sleep(0.05)
+    for p, log in procs:
+        p.wait()
+        log.close()
+    bad = [r for r, (p, _) in enumerate(procs) if p.returncode != 0]
+    if failed or bad:
+        logs = "\n".join(f"--- rank {r} (rc {procs[r][0].returncode}) ---\n" + open(os.path.join(work, f"rank{r}.log")).read()[-3000:]
+                         for r in range(n))
+        raise AssertionError(f"{failed or bad}\n{logs}")
+    return [np.load(os.path.join(work, f"out_{r}.npz")) for r in range(n)]
+
+
+@pytest.mark.parametrize("n", [2, 3])
+@pytest.mark.parametrize("closed", [True, False])
+def test_ring_of_rank_processes_equals_one_block(lib, oracle, tmp_path, n, closed):
+    R, C, steps, form = 48, 200, 31, FAST
+    prm, gbc = params(form), (pylbm.Bc.periodic() if closed else wall_bc(True))
+    gg, pre = global_state(lib, oracle, R * n, C, seed=n)
+    _, want = one_block(lib, gg, pre, gbc, prm, steps)
+    cfg = dict(R=R, C=C, steps=steps, edge_rows=16, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W))
+    outs = run_ranks(lib, tmp_path, n, cfg, dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()))
+    for j, key in enumerate(("f", "g")):
+        got = np.concatenate([o[key] for o in outs], axis=1)
+        ref = owned(want[j], gg).cpu().numpy()
+        assert np.array_equal(got.view(np.uint64), ref.view(np.uint64)), f"{n} ranks closed={closed}: {key} differs"
+    # refresh after a restore (lbm_ring_exchange_pair) is checked by the ranks themselves: ghost rows == neighbours' rows
+    assert all(bool(o["pair_ok"]) for o in outs)
+
+
+def test_ring_entry_points_refuse_a_ring_without_one_ghost_row(lib, tmp_path):
+    """ghost != 1 on the ring: every ring entry point of the pair refuses it on the host (one rank, its own process)"""
+    cfg = dict(case="refusals", R=32, C=64)
+    outs = run_ranks(lib, tmp_path, 1, cfg, {})
+    msgs = json.loads(str(outs[0]["msgs"]))
+    assert len(msgs) == 3
+    for m in msgs:
+        assert "ghost=2" in m, m
+
+
+# ---- 5. the driver -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("walls", [0, 1])
+@pytest.mark.parametrize("form", ["fast", "ref"])
+def test_slab_ring_ade_driver_emulated_chain_of_four(walls, form):
+    exe = os.path.join(BIN, "slab_ring_ade")
+    r = subprocess.run([exe, "--emulate", "4", "--rows", "48", "--cols", "200", "--steps", "9", "--warmup", "2",
+                        "--edge-rows", "8", "--walls", str(walls), "--form", form, "--check", "1"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["check"] == "bitwise equal to one block" and line["slabs"] == 4 and line["message_rows_per_side"] == 6
+    assert line["slowest_slab_ms_per_step"] > 0 and line["one_block_slab_sized_ms_per_step"] > 0
+
+
+@pytest.mark.parametrize("walls", [0, 1])
+def test_slab_ring_ade_driver_self_ring(tmp_path, walls):
+    """one forked rank: closed, its neighbours are itself (every step exchanges through the ring); with walls a chain
+    of one slab (nothing travels) -- both == one block bit for bit"""
+    exe = os.path.join(BIN, "slab_ring_ade")
+    r = subprocess.run([exe, "--spawn", "1", "--rows", "96", "--cols", "256", "--steps", "5", "--warmup", "1",
+                        "--edge-rows", "16", "--walls", str(walls), "--check", "1", "--id-file", str(tmp_path / "id")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["check"] == "bitwise equal to one block" and line["n_gpus"] == 1
+
+
+# ---- 6. physics across the seams -----------------------------------------------------------------------------------------
+def test_scalar_mass_and_transport_across_the_seams_of_a_walled_chain(lib, oracle):
+    """walls all round, w across the seams (+r), the scalar on the first slab only: sum C stays to 1e-12 relative over
+    500 steps, and C rises from exactly 0 beyond the seam"""
+    heights, C = (40, 40, 40), 64
+    w = (0.05, 0.0)
+    prm, gbc = params(FAST, w=w), wall_bc(True)
+    gg, pre = global_state(lib, oracle, sum(heights), C, seed=5, w=w, conc_rows=(4, 36))
+    assert float(owned(pre[1], gg)[:, 40:].abs().sum()) == 0.0
+    post, _ = one_block(lib, gg, pre, gbc, prm, 0)
+    ch = Chain(lib, gg, post, heights, False, gbc, prm)
+    m0 = float(ch.gather(1).sum())
+    for _ in range(500):
+        ch.step(8)
+    torch.cuda.synchronize()
+    conc = ch.gather(1).sum(dim=0)
+    m1 = float(conc.sum())
+    assert abs(m1 - m0) <= 1e-12 * abs(m0), (m0, m1)
+    beyond = float(conc[40:80].sum())
+    assert beyond > 1e-3 * m0, f"no scalar crossed the seam: {beyond} of {m0}"
