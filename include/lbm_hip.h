@@ -463,7 +463,8 @@ int lbm_solver_lattices(lbm_solver* sv, double** cur, double** other, lbm_geom* 
  * and writes both (288 B per node update).  Single block (ghost = 0; row slabs: lbm_ade_stream_collide_part and
  * lbm_ring_ade_* below), C even.  Edges: PERIODIC or BOUNCE_BACK rows,
  * PERIODIC, BOUNCE_BACK or SPECULAR columns; g takes exactly the fix-up f takes at a wall, on its own post-collision
- * populations -- a no-flux wall (the driver's bottom wall, :234-236 = :180-182).  Everything else (HALO, ABB_VELOCITY,
+ * populations -- a no-flux wall (the driver's bottom wall, :234-236 = :180-182) -- unless lbm_ade_scalar_bc below makes
+ * the edge a fixed-concentration wall.  Everything else (HALO, ABB_VELOCITY,
  * WRAP_NOSHIFT, pressure rows, ghost rows) is refused on the host.  The fluid parameters must be the plain
  * compressible model: incompressible = delta_form = force_mode = 0.  Both halves run in the form of `scalar->form`
  * (LBM_FORM_DEFAULT resolves through "bgk_fast" as for BGK): REFERENCE_ORDER = solver.cpp's operation order, the fluid
@@ -520,6 +521,40 @@ int lbm_ade_solver_lattices(lbm_ade_solver* sv, double** f_cur, double** g_cur, 
                             lbm_geom* geom /* may be NULL */);
 /* kernel launches lbm_ade_solver_step has enqueued so far; -1 for NULL */
 long long lbm_ade_solver_launches(const lbm_ade_solver* sv);
+
+/* The scalar's walls, per edge in the order row_lo, row_hi, col_lo, col_hi (additive to all of the above; NULL, or every
+ * mode NO_FLUX, is the no-flux wall: the same bits and the same launches).
+ *   LBM_ADE_SCALAR_NO_FLUX  g takes the fix-up f takes (bounce-back or specular on its own populations);
+ *   LBM_ADE_SCALAR_FIXED    a fixed concentration C_w: every population the no-flux wall replaces is replaced by
+ *     anti-bounce-back, g[qbar] = -g*[q] + 2 ((1 + 3 c_q.v + 4.5 (c_q.v)^2 - 1.5 v.v) E_q C_w), v = u + w, u the node's
+ *     fluid velocity after streaming, g* its own post-collision populations -- the inlet of
+ *     test/rectangle_sedimentation_test.cpp:203-218 restricted to the incoming populations; C_w = 0 is its absorbing
+ *     obstacle (:221-232).  On a SPECULAR fluid column g pairs q with its opposite all the same.  Corners: rows first,
+ *     columns win; each population takes the rule and C_w of the edge that wins it.
+ * FIXED needs a wall of the fluid there: a BOUNCE_BACK row, a BOUNCE_BACK or SPECULAR column (never PERIODIC, HALO,
+ * ABB_VELOCITY, WRAP_NOSHIFT).  C_w: conc[e], or, where profile[e] is not NULL, a device array (8-byte aligned) of C
+ * values on a row edge / R values on a column edge, in the rows of the lattice the call sees (a slab passes its own
+ * slice).  The array is read by every step, never copied: rewriting it between graph replays changes the boundary;
+ * the descriptor itself is taken by value at each call (a captured graph keeps the one of its capture). */
+#define LBM_ADE_SCALAR_NO_FLUX 0
+#define LBM_ADE_SCALAR_FIXED 1
+typedef struct lbm_ade_scalar_bc {
+  int mode[4];              /* LBM_ADE_SCALAR_* */
+  double conc[4];           /* C_w of a FIXED edge without a profile; finite */
+  const double* profile[4]; /* NULL or device C_w per node along the edge */
+} lbm_ade_scalar_bc;
+/* lbm_ade_stream_collide / _part with the scalar's walls (sbc may be NULL) */
+int lbm_ade_stream_collide_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                              const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                              const lbm_ade_scalar_bc* sbc, int row_begin, int row_end, double* rho, double* u,
+                              double* conc, lbm_stream_t s);
+int lbm_ade_stream_collide_part_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                   const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                                   const lbm_ade_scalar_bc* sbc, int part, int edge_rows, double* rho, double* u,
+                                   double* conc, lbm_stream_t s);
+/* the context's scalar walls from the next stream on (the lazy one of get_state included); NULL = all NO_FLUX.  Checked
+ * against the context's edges; the descriptor is copied, a profile array is not. */
+int lbm_ade_solver_set_scalar_bc(lbm_ade_solver* sv, const lbm_ade_scalar_bc* sbc);
 
 /* ---- slab ring in C++: one process per GPU, packed halo messages between row slabs ------------------
  * Native counterpart of pylbm/slab.py (same kernels, same halo sets): edge rows + pack + ONE message
@@ -591,6 +626,12 @@ int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, 
 /* one overlapped step: FRAME + pack + ONE message per neighbour on the ring's stream, INNER on `main` beside them */
 int lbm_ring_ade_step(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                       const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int edge_rows, lbm_stream_t main);
+/* the same with the scalar's walls of the GLOBAL domain (lbm_ade_scalar_bc, checked against bc; NULL = all NO_FLUX): a
+ * FIXED row edge acts at the chain end that carries it and is dropped at the seams, as bc's row walls are; a profile of a
+ * column edge holds this slab's R rows */
+int lbm_ring_ade_step_ex(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                         int edge_rows, lbm_stream_t main);
 /* refresh the single-step ghost rows of two lattices in one message per neighbour (e.g. after restoring a state);
  * asynchronous, ordered after the work enqueued on `after` (lbm_ring_join makes a stream wait for it) */
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after);

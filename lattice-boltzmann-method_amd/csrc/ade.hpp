@@ -63,6 +63,53 @@ __device__ __forceinline__ void ade_collide_node(double (&f)[Q], double (&h)[Q],
   sm.collide(h, ux, uy, conc);
 }
 
+// The scalar's fixed-concentration walls (lbm_ade_scalar_bc, device copy).  Edge e: 0 row_lo, 1 row_hi, 2 col_lo,
+// 3 col_hi.  C_w of a node: profile[e][c] on a row edge, profile[e][r] on a column edge (rows of the lattice the launch
+// sees), conc[e] where the edge has no profile.  The host checks that every FIXED edge is a wall of the fluid.
+struct AdeWalls {
+  int fixed;  // bit e: edge e is FIXED
+  double conc[4];
+  const double* profile[4];
+};
+
+// The populations of g that bounce back at a FIXED edge anti-bounce back instead (test/rectangle_sedimentation_test.cpp
+// :203-232): h[qbar] = -h*[q] + 2 G_q(v, C_w), G_q = (1 + 3 c_q.v + 4.5 (c_q.v)^2 - 1.5 v.v) E_q C_w, v = u + w, in the
+// driver's expression order.  On entry the slots a wall replaces hold the bounce-back gather (h[qbar] = h*[q]: a FIXED
+// column gathers as BOUNCE_BACK, also beside a specular fluid column); u is the fluid velocity of the streamed f.  Slot
+// ownership is bc_fixups_own's: rows first, a wall column wins at the corners, and each slot takes the rule and C_w of
+// the edge that wins it (a NO_FLUX column keeps its corner slots bounce-back).
+__device__ __forceinline__ void ade_fixed_walls(double (&h)[Q], const Geom& g, const Bc& bc, const AdeWalls& sw, int r,
+                                                int c, double ux, double uy, double wr, double wc) {
+  const bool rl = r == 0 && bc.row_lo == LBM_EDGE_BOUNCE_BACK, rh = r == g.R - 1 && bc.row_hi == LBM_EDGE_BOUNCE_BACK;
+  const bool cl = c == 0 && bc_is_wall(bc.col_lo), ch = c == g.C - 1 && bc_is_wall(bc.col_hi);
+  // C_w of the node's edges, loaded up front (independent loads; no dynamic indexing into sw)
+  const double w_rl = rl && (sw.fixed & 1) ? (sw.profile[0] ? sw.profile[0][c] : sw.conc[0]) : 0.0;
+  const double w_rh = rh && (sw.fixed & 2) ? (sw.profile[1] ? sw.profile[1][c] : sw.conc[1]) : 0.0;
+  const double w_cl = cl && (sw.fixed & 4) ? (sw.profile[2] ? sw.profile[2][r] : sw.conc[2]) : 0.0;
+  const double w_ch = ch && (sw.fixed & 8) ? (sw.profile[3] ? sw.profile[3][r] : sw.conc[3]) : 0.0;
+  const double vr = ux + wr, vc = uy + wc;
+  const double vv = vr * vr + vc * vc;
+#pragma unroll
+  for (int s = 1; s < Q; ++s) {
+    const int e = (cl && icy(s) == 1) ? 2 : (ch && icy(s) == -1) ? 3 : (rl && icx(s) == 1) ? 0 : (rh && icx(s) == -1) ? 1 : -1;
+    if (e < 0 || !((sw.fixed >> e) & 1)) continue;
+    const double cw = e == 0 ? w_rl : e == 1 ? w_rh : e == 2 ? w_cl : w_ch;
+    const int q = opp(s);  // the outgoing direction
+    // c_q.v as matmul(v, c) forms it (products with 0, +-1 are exact)
+    const double cv = q == 1 ? vr : q == 2 ? vc : q == 3 ? -vr : q == 4 ? -vc : q == 5 ? vr + vc : q == 6 ? -vr + vc
+                    : q == 7 ? -vr - vc : vr - vc;
+    h[s] = -h[s] + 2.0 * (((((1.0 + 3.0 * cv) + 4.5 * (cv * cv)) - 1.5 * vv) * wq(q)) * cw);
+  }
+}
+
+// g's gather modes at the walls: a FIXED column bounces back (its anti-bounce-back pairs q with its opposite, also where
+// the fluid column is specular)
+__host__ __device__ inline Bc ade_scalar_gather_bc(Bc b, int fixed) {
+  if (fixed & 4) b.col_lo = LBM_EDGE_BOUNCE_BACK;
+  if (fixed & 8) b.col_hi = LBM_EDGE_BOUNCE_BACK;
+  return b;
+}
+
 // The 9 pulled populations of node pair (r, c), (r, c + 1) of one lattice, 16-byte accesses where the pair's
 // sources are column-aligned (q = 0, 1, 3) or lie inside the row (the +-1-column shifted reads, 8-byte aligned
 // 16-byte loads); the first and last pair of a row wrap per node.  k_stream_collide_v2's gather, for any lattice.
@@ -134,12 +181,14 @@ __global__ __launch_bounds__(256) void k_ade_stream_collide(
 // applied to its own post-collision populations (the driver's no-flux bottom wall, :234-236 = :180-182).
 // Edge list: [0, C) row 0 | [C, 2C) row R-1 | [2C, 2C+n) column 0 | [2C+n, 2C+2n) column C-1; an edge is
 // listed only if its mode is a wall (the host passes which).
-template <class FM, class SM, bool WITH_MOMENTS>
+// FIXED: the scalar's FIXED edges (sw) anti-bounce back between the two collisions (ade_fixed_walls); without it the
+// kernel is the no-flux pass and sw is not read.
+template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false>
 __global__ __launch_bounds__(256) void k_ade_edge(double* __restrict__ fn, double* __restrict__ gn,
                                                   const double* __restrict__ fo, const double* __restrict__ go, Geom g,
                                                   Bc bc, FM fm, SM sm, int row_begin, int row_end,
                                                   double* __restrict__ rho_out, double* __restrict__ u_out,
-                                                  double* __restrict__ c_out) {
+                                                  double* __restrict__ c_out, AdeWalls sw) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x, n = row_end - row_begin;
   int r, c;
   if (i < g.C) { r = 0; c = i; if (!bc_is_wall(bc.row_lo)) return; }
@@ -154,8 +203,15 @@ __global__ __launch_bounds__(256) void k_ade_edge(double* __restrict__ fn, doubl
   if (i >= 2 * g.C + n && g.C == 1 && bc_is_wall(bc.col_lo)) return;
   double f[Q], h[Q], rho, ux, uy, conc;
   gather_walls(f, fo, g, bc, r, c);
-  gather_walls(h, go, g, bc, r, c);
-  ade_collide_node(f, h, fm, sm, rho, ux, uy, conc);
+  if (FIXED) {
+    gather_walls(h, go, g, ade_scalar_gather_bc(bc, sw.fixed), r, c);
+    fm.collide(f, rho, ux, uy);
+    ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    sm.collide(h, ux, uy, conc);
+  } else {
+    gather_walls(h, go, g, bc, r, c);
+    ade_collide_node(f, h, fm, sm, rho, ux, uy, conc);
+  }
   const long o = g.at(r, c);
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
@@ -213,11 +269,13 @@ __device__ __forceinline__ void wall_fixups_pair(double (&a)[Q], double (&b)[Q],
 // load gather_walls / pull_pair take for it and the arithmetic is ade_collide_node's, so the results are those of
 // k_ade_stream_collide + k_ade_edge bit for bit.  Rows come from wrap_row: ghost rows once g.ghost > 0 (HALO edges),
 // wrapped on a single block (a wall row's pulled row is replaced).  Writes owned nodes only.
-template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS>
+// FIXED: as k_ade_edge -- g gathers with ade_scalar_gather_bc and the wall lanes anti-bounce back at the FIXED edges
+// between the two collisions of each node.
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool FIXED = false>
 __global__ __launch_bounds__(256) void k_ade_stream_collide_part(
     double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
     Geom g, Bc bc, FM fm, SM sm, int band0, int n0, int band1, int nrows, int tiles_per_row,
-    double* __restrict__ rho_out, double* __restrict__ u_out, double* __restrict__ c_out) {
+    double* __restrict__ rho_out, double* __restrict__ u_out, double* __restrict__ c_out, AdeWalls sw) {
   const long items = (long)nrows * tiles_per_row;
   for (long it = blockIdx.x; it < items; it += gridDim.x) {
     const int v = (int)(it / tiles_per_row);
@@ -233,12 +291,26 @@ __global__ __launch_bounds__(256) void k_ade_stream_collide_part(
     pull_pair<NT_LOAD>(fa, fb, fo, g, rm, r0, rp, c);
     if (wall) wall_fixups_pair<NT_LOAD>(fa, fb, fo, g, bc, row_lo, row_hi, r0, c);
     pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
-    if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, bc, row_lo, row_hi, r0, c);
     double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
-    ade_collide_node(fa, ha, fm, sm, rho_a, ux_a, uy_a, c_a);
-    ade_collide_node(fb, hb, fm, sm, rho_b, ux_b, uy_b, c_b);
+    if (FIXED) {  // f is stored before the scalar's walls and collisions: its registers are free for them
+      if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, ade_scalar_gather_bc(bc, sw.fixed), row_lo, row_hi, r0, c);
+      fm.collide(fa, rho_a, ux_a, uy_a);
+      fm.collide(fb, rho_b, ux_b, uy_b);
 #pragma unroll
-    for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+      if (wall) {
+        ade_fixed_walls(ha, g, bc, sw, r, c, ux_a, uy_a, sm.wr, sm.wc);
+        ade_fixed_walls(hb, g, bc, sw, r, c + 1, ux_b, uy_b, sm.wr, sm.wc);
+      }
+      sm.collide(ha, ux_a, uy_a, c_a);
+      sm.collide(hb, ux_b, uy_b, c_b);
+    } else {
+      if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, bc, row_lo, row_hi, r0, c);
+      ade_collide_node(fa, ha, fm, sm, rho_a, ux_a, uy_a, c_a);
+      ade_collide_node(fb, hb, fm, sm, rho_b, ux_b, uy_b, c_b);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+    }
 #pragma unroll
     for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
     if (WITH_MOMENTS) {
@@ -250,6 +322,27 @@ __global__ __launch_bounds__(256) void k_ade_stream_collide_part(
       store2<false>(c_out + o, c_a, c_b);
     }
   }
+}
+
+// The FIXED edges of the lazily streamed scalar (lbm_ade_solver_get_state): hs = stream(post-collision g) with the
+// gather modes of ade_scalar_gather_bc; u = [2][R][C] dense, the reference-order calc_u of the streamed f.  One thread per
+// node of the perimeter (rows 0 and R-1, then columns 0 and C-1 without the corners), each node once.
+__global__ __launch_bounds__(256) void k_ade_fixed_state(double* __restrict__ hs, Geom g, Bc bc, AdeWalls sw,
+                                                         const double* __restrict__ u, double wr, double wc) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, inner = g.R > 2 ? g.R - 2 : 0;
+  int r, c;
+  if (i < g.C) { r = 0; c = i; }
+  else if (i < 2 * g.C) { r = g.R - 1; c = i - g.C; if (g.R == 1) return; }
+  else if (i < 2 * g.C + inner) { r = 1 + i - 2 * g.C; c = 0; }
+  else if (i < 2 * g.C + 2 * inner) { r = 1 + i - 2 * g.C - inner; c = g.C - 1; }
+  else return;
+  const long o = g.at(r, c), n = (long)g.R * g.C, d = (long)r * g.C + c;
+  double h[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) h[q] = hs[q * g.plane + o];
+  ade_fixed_walls(h, g, bc, sw, r, c, u[d], u[n + d], wr, wc);
+#pragma unroll
+  for (int q = 0; q < Q; ++q) hs[q * g.plane + o] = h[q];
 }
 
 // Collide only, no streaming: the driver's first iteration on the pre-collision state (one node per thread).

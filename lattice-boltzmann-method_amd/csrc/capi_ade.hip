@@ -1,6 +1,7 @@
 // C ABI, fluid + transported scalar: the compressible BGK fluid f and the advection-diffusion scalar g of
 // test/rectangle_sedimentation_test.cpp:88-247 in one fused pull step per node (ade.hpp), and the solver
 // context that runs the driver loop on one block.
+#include <cmath>
 #include <cstdint>
 #include <new>
 
@@ -88,6 +89,33 @@ static bool ade_fast(const lbm_ade_params* scalar) {
   return scalar->form == LBM_FORM_DEFAULT ? tuning("bgk_fast", 1) != 0 : scalar->form == LBM_FORM_REASSOCIATED;
 }
 
+static const char* const kEdge[4] = {"row_lo", "row_hi", "col_lo", "col_hi"};
+
+// The scalar's walls (lbm_ade_scalar_bc) against the edges `bc` the launch runs with, on the host: a FIXED edge must be a
+// wall of the fluid there -- a BOUNCE_BACK row, a BOUNCE_BACK or SPECULAR column.  *sw receives the device copy.
+static int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc, AdeWalls* sw) {
+  *sw = AdeWalls{};
+  if (!sbc) return LBM_OK;
+  const int modes[4] = {bc ? bc->row_lo : LBM_EDGE_PERIODIC, bc ? bc->row_hi : LBM_EDGE_PERIODIC,
+                        bc ? bc->col_lo : LBM_EDGE_PERIODIC, bc ? bc->col_hi : LBM_EDGE_PERIODIC};
+  for (int e = 0; e < 4; ++e) {
+    const int m = sbc->mode[e];
+    LBM_REQUIRE(m == LBM_ADE_SCALAR_NO_FLUX || m == LBM_ADE_SCALAR_FIXED,
+                "%s: scalar edge %s: mode=%d (LBM_ADE_SCALAR_NO_FLUX or LBM_ADE_SCALAR_FIXED)", fn, kEdge[e], m);
+    if (m != LBM_ADE_SCALAR_FIXED) continue;
+    const bool wall = modes[e] == LBM_EDGE_BOUNCE_BACK || (e >= 2 && modes[e] == LBM_EDGE_SPECULAR);
+    LBM_REQUIRE(wall, "%s: scalar edge %s: FIXED on a %s (%d) edge (a BOUNCE_BACK row, a BOUNCE_BACK or SPECULAR column)",
+                fn, kEdge[e], edge_name(modes[e]), modes[e]);
+    LBM_REQUIRE(std::isfinite(sbc->conc[e]), "%s: scalar edge %s: conc=%g must be finite", fn, kEdge[e], sbc->conc[e]);
+    LBM_REQUIRE(((uintptr_t)sbc->profile[e] & 7u) == 0, "%s: scalar edge %s: profile %p must be 8-byte aligned", fn,
+                kEdge[e], (const void*)sbc->profile[e]);
+    sw->fixed |= 1 << e;
+    sw->conc[e] = sbc->conc[e];
+    sw->profile[e] = sbc->profile[e];
+  }
+  return LBM_OK;
+}
+
 template <class FM, class SM>
 static int ade_collide_launch(double* fp, double* gp, const double* f, const double* h, const Geom& g, const FM& fm,
                               const SM& sm, double* rho, double* u, double* conc, hipStream_t st) {
@@ -102,8 +130,8 @@ static int ade_collide_launch(double* fp, double* gp, const double* f, const dou
 // interior launch + (walls only) the edge pass; *launches += the kernels enqueued
 template <class FM, class SM>
 static int ade_step_launch(double* fn, double* gn, const double* fo, const double* go, const Geom& g, const Bc& bc,
-                           const FM& fm, const SM& sm, int row_begin, int row_end, double* rho, double* u, double* conc,
-                           hipStream_t st, long long* launches) {
+                           const FM& fm, const SM& sm, const AdeWalls& sw, int row_begin, int row_end, double* rho,
+                           double* u, double* conc, hipStream_t st, long long* launches) {
   const bool mom = rho != nullptr;
   const int nt = tuning("nt", 3);  // bit 0: non-temporal loads, bit 1: non-temporal stores
   const int cap = tuning("grid_cap", 0);
@@ -128,8 +156,16 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
   ++*launches;
   if (bc_needs_edge_pass(bc)) {
     const int n_edge = 2 * g.C + 2 * (row_end - row_begin);
-    if (mom) LBM_KLAUNCH((k_ade_edge<FM, SM, true>), dim3((n_edge + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin, row_end, rho, u, conc);
-    else LBM_KLAUNCH((k_ade_edge<FM, SM, false>), dim3((n_edge + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin, row_end, rho, u, conc);
+    const dim3 grid_e((n_edge + 255) / 256);
+    switch ((sw.fixed ? 2 : 0) | (mom ? 1 : 0)) {
+#define LBM_ADE_E(M, F) \
+  LBM_KLAUNCH((k_ade_edge<FM, SM, M, F>), grid_e, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin, row_end, rho, u, conc, sw)
+      case 0: LBM_ADE_E(false, false); break;
+      case 1: LBM_ADE_E(true, false); break;
+      case 2: LBM_ADE_E(false, true); break;
+      default: LBM_ADE_E(true, true); break;
+#undef LBM_ADE_E
+    }
     LBM_CHECK_LAUNCH();
     ++*launches;
   }
@@ -139,26 +175,34 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
 // one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline
 template <class FM, class SM>
 static int ade_part_launch(double* fn, double* gn, const double* fo, const double* go, const Geom& g, const Bc& bc,
-                           const FM& fm, const SM& sm, int band0, int n0, int band1, int nrows, double* rho, double* u,
-                           double* conc, hipStream_t st) {
+                           const FM& fm, const SM& sm, const AdeWalls& sw, int band0, int n0, int band1, int nrows,
+                           double* rho, double* u, double* conc, hipStream_t st) {
   const bool mom = rho != nullptr;
   const int nt = tuning("nt", 3);  // as the single-block step
   const int cap = tuning("grid_cap", 0);
   const int tiles = (g.C + 511) / 512;
   const long items = (long)nrows * tiles;
   const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
-  switch ((nt & 3) | (mom ? 4 : 0)) {
-#define LBM_ADE_P(NL, NS, M)                                                                                            \
-  LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL, NS, M>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, \
-              sm, band0, n0, band1, nrows, tiles, rho, u, conc)
-    case 0: LBM_ADE_P(false, false, false); break;
-    case 1: LBM_ADE_P(true, false, false); break;
-    case 2: LBM_ADE_P(false, true, false); break;
-    case 3: LBM_ADE_P(true, true, false); break;
-    case 4: LBM_ADE_P(false, false, true); break;
-    case 5: LBM_ADE_P(true, false, true); break;
-    case 6: LBM_ADE_P(false, true, true); break;
-    default: LBM_ADE_P(true, true, true); break;
+  switch ((nt & 3) | (mom ? 4 : 0) | (sw.fixed ? 8 : 0)) {
+#define LBM_ADE_P(NL, NS, M, F)                                                                                            \
+  LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL, NS, M, F>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, \
+              sm, band0, n0, band1, nrows, tiles, rho, u, conc, sw)
+    case 0: LBM_ADE_P(false, false, false, false); break;
+    case 1: LBM_ADE_P(true, false, false, false); break;
+    case 2: LBM_ADE_P(false, true, false, false); break;
+    case 3: LBM_ADE_P(true, true, false, false); break;
+    case 4: LBM_ADE_P(false, false, true, false); break;
+    case 5: LBM_ADE_P(true, false, true, false); break;
+    case 6: LBM_ADE_P(false, true, true, false); break;
+    case 7: LBM_ADE_P(true, true, true, false); break;
+    case 8: LBM_ADE_P(false, false, false, true); break;
+    case 9: LBM_ADE_P(true, false, false, true); break;
+    case 10: LBM_ADE_P(false, true, false, true); break;
+    case 11: LBM_ADE_P(true, true, false, true); break;
+    case 12: LBM_ADE_P(false, false, true, true); break;
+    case 13: LBM_ADE_P(true, false, true, true); break;
+    case 14: LBM_ADE_P(false, true, true, true); break;
+    default: LBM_ADE_P(true, true, true, true); break;
 #undef LBM_ADE_P
   }
   LBM_CHECK_LAUNCH();
@@ -183,9 +227,11 @@ static int ade_collide(const char* fn, double* fp, double* gp, const double* f, 
 
 static int ade_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
                               const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
-                              const lbm_ade_params* scalar, int row_begin, int row_end, double* rho, double* u,
-                              double* conc, hipStream_t st, long long* launches) {
-  int rc = ade_validate(fn, lg, lbc, fluid, scalar);
+                              const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, int row_begin, int row_end,
+                              double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
+  AdeWalls sw;  // the scalar's walls first: a FIXED edge names the edge mode it cannot sit on
+  int rc = ade_scalar_bc_check(fn, sbc, lbc, &sw);
+  if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar);
   if (rc) return rc;
   LBM_REQUIRE(fn_ && gn && fo && go, "%s: NULL lattice", fn);
   LBM_REQUIRE(fn_ != fo && fn_ != go && gn != fo && gn != go && fn_ != gn && fo != go, "%s: aliased lattices", fn);
@@ -199,10 +245,10 @@ static int ade_stream_collide(const char* fn, double* fn_, double* gn, const dou
   const Bc bc = make_bc(lbc);
   if (ade_fast(scalar))
     return ade_step_launch(fn_, gn, fo, go, g, bc, BgkFastModel(fluid->omega),
-                           AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c), row_begin, row_end, rho, u, conc, st,
-                           launches);
+                           AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c), sw, row_begin, row_end, rho, u, conc,
+                           st, launches);
   return ade_step_launch(fn_, gn, fo, go, g, bc, BgkModelT<0, 0>{fluid->omega},
-                         AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, row_begin, row_end, rho, u, conc, st,
+                         AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, sw, row_begin, row_end, rho, u, conc, st,
                          launches);
 }
 
@@ -221,6 +267,36 @@ int ade_part_check(const char* name, const double* fn, const double* gn, const d
   LBM_REQUIRE(edge_rows >= 1 && 2 * edge_rows < lg->R, "%s: edge_rows=%d: need 1 <= edge_rows and 2 x edge_rows < R=%d",
               name, edge_rows, lg->R);
   return LBM_OK;
+}
+
+int ade_scalar_bc_validate(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc) {
+  AdeWalls sw;
+  return ade_scalar_bc_check(fn, sbc, bc, &sw);
+}
+
+// lbm_ade_stream_collide_part(_ex) under the caller's name
+static int ade_part(const char* name, double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
+                    const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                    const lbm_ade_scalar_bc* sbc, int part, int edge_rows, double* rho, double* u, double* conc,
+                    hipStream_t st) {
+  AdeWalls sw;  // the scalar's walls first, as ade_stream_collide
+  int rc = ade_scalar_bc_check(name, sbc, lbc, &sw);
+  if (!rc) rc = ade_part_check(name, fn, gn, fo, go, lg, lbc, fluid, scalar, part, edge_rows, rho, u, conc);
+  if (rc) return rc;
+  const int R = lg->R;
+  const Geom g = make_geom(*lg);
+  const Bc bc = make_bc(lbc);
+  // FRAME: rows [0, E) then [R - E, R); INNER: rows [E, R - E)
+  const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;
+  const int n0 = part == LBM_ADE_PART_FRAME ? edge_rows : R - 2 * edge_rows;
+  const int band1 = R - edge_rows, nrows = part == LBM_ADE_PART_FRAME ? 2 * edge_rows : n0;
+  if (ade_fast(scalar))
+    return ade_part_launch(fn, gn, fo, go, g, bc, BgkFastModel(fluid->omega),
+                           AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c), sw, band0, n0, band1, nrows, rho, u,
+                           conc, st);
+  return ade_part_launch(fn, gn, fo, go, g, bc, BgkModelT<0, 0>{fluid->omega},
+                         AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, sw, band0, n0, band1, nrows, rho, u, conc,
+                         st);
 }
 
 int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
@@ -242,6 +318,8 @@ struct lbm_ade_solver {
   lbm_bc bc;
   lbm_bgk_params fluid;
   lbm_ade_params scalar;
+  lbm_ade_scalar_bc sbc;  // all NO_FLUX unless set
+  bool fixed;             // some edge of sbc is FIXED
   hipStream_t st;
   double* lat[2];
   double* dense;  // [9][R][C] SoA scratch of get_state
@@ -268,30 +346,32 @@ int lbm_ade_stream_collide(double* fn, double* gn, const double* fo, const doubl
                            const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int row_begin,
                            int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
   long long launches = 0;
-  return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, row_begin, row_end, rho, u,
-                            conc, as_stream(s), &launches);
+  return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, nullptr, row_begin, row_end,
+                            rho, u, conc, as_stream(s), &launches);
+}
+
+int lbm_ade_stream_collide_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                              const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                              const lbm_ade_scalar_bc* sbc, int row_begin, int row_end, double* rho, double* u,
+                              double* conc, lbm_stream_t s) {
+  long long launches = 0;
+  return ade_stream_collide("lbm_ade_stream_collide_ex", fn, gn, fo, go, g, bc, fluid, scalar, sbc, row_begin, row_end,
+                            rho, u, conc, as_stream(s), &launches);
 }
 
 int lbm_ade_stream_collide_part(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                                 const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int part,
                                 int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
-  int rc = ade_part_check("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, fluid, scalar, part, edge_rows, rho, u,
-                          conc);
-  if (rc) return rc;
-  const int R = lg->R;
-  const Geom g = make_geom(*lg);
-  const Bc bc = make_bc(lbc);
-  // FRAME: rows [0, E) then [R - E, R); INNER: rows [E, R - E)
-  const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;
-  const int n0 = part == LBM_ADE_PART_FRAME ? edge_rows : R - 2 * edge_rows;
-  const int band1 = R - edge_rows, nrows = part == LBM_ADE_PART_FRAME ? 2 * edge_rows : n0;
-  if (ade_fast(scalar))
-    return ade_part_launch(fn, gn, fo, go, g, bc, BgkFastModel(fluid->omega),
-                           AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c), band0, n0, band1, nrows, rho, u, conc,
-                           as_stream(s));
-  return ade_part_launch(fn, gn, fo, go, g, bc, BgkModelT<0, 0>{fluid->omega},
-                         AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, band0, n0, band1, nrows, rho, u, conc,
-                         as_stream(s));
+  return ade_part("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, fluid, scalar, nullptr, part, edge_rows, rho,
+                  u, conc, as_stream(s));
+}
+
+int lbm_ade_stream_collide_part_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
+                                   const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                                   const lbm_ade_scalar_bc* sbc, int part, int edge_rows, double* rho, double* u,
+                                   double* conc, lbm_stream_t s) {
+  return ade_part("lbm_ade_stream_collide_part_ex", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, part, edge_rows, rho, u,
+                  conc, as_stream(s));
 }
 
 int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
@@ -307,6 +387,8 @@ int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc*
   sv->bc = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
   sv->fluid = *fluid;
   sv->scalar = *scalar;
+  sv->sbc = lbm_ade_scalar_bc{};
+  sv->fixed = false;
   sv->st = as_stream(s);
   sv->cur = 0;
   sv->post = false;
@@ -374,7 +456,8 @@ int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
       if (!rc) ++sv->launches;
     } else {
       rc = ade_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
-                              &sv->fluid, &sv->scalar, 0, sv->g.R, nullptr, nullptr, nullptr, sv->st, &sv->launches);
+                              &sv->fluid, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, 0, sv->g.R, nullptr, nullptr,
+                              nullptr, sv->st, &sv->launches);
     }
     if (rc) return rc;
     sv->cur = o;
@@ -394,27 +477,49 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
   const int R = g.R, C = g.C;
   const size_t n = (size_t)R * C;
   int k = sv->cur;
+  const lbm_geom dg{R, C, 0, 0, 0};
+  const bool fixed = sv->post && sv->fixed;
   if (sv->post) {
     int rc = lbm_stream(sv->f(k ^ 1), sv->f(k), &g, &sv->bc, sv->st);
-    if (!rc) rc = lbm_stream(sv->h(k ^ 1), sv->h(k), &g, &sv->bc, sv->st);
+    if (rc) return rc;
+    AdeWalls sw;
+    rc = ade_scalar_bc_check("lbm_ade_solver_get_state", fixed ? &sv->sbc : nullptr, &sv->bc, &sw);
+    if (rc) return rc;
+    // g gathers as BOUNCE_BACK at a FIXED column (ade_scalar_gather_bc); the FIXED edges then take their rule with
+    // u = the reference-order calc_u of the streamed f
+    lbm_bc gbc = sv->bc;
+    if (sw.fixed & 4) gbc.col_lo = LBM_EDGE_BOUNCE_BACK;
+    if (sw.fixed & 8) gbc.col_hi = LBM_EDGE_BOUNCE_BACK;
+    rc = lbm_stream(sv->h(k ^ 1), sv->h(k), &g, &gbc, sv->st);
     if (rc) return rc;
     k ^= 1;
+    if (fixed) {
+      rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->f(k), &g, 0, R, sv->st);
+      if (!rc) rc = lbm_calc_rho(sv->rho, sv->dense, R, C, sv->st);
+      if (!rc) rc = lbm_calc_u(sv->u, sv->dense, sv->rho, R, C, sv->st);
+      if (rc) return rc;
+      const int n_edge = 2 * C + 2 * R;
+      LBM_KLAUNCH(k_ade_fixed_state, dim3((n_edge + 255) / 256), dim3(256), 0, sv->st, sv->h(k), make_geom(g),
+                  make_bc(&sv->bc), sw, sv->u, sv->scalar.w_r, sv->scalar.w_c);
+      LBM_CHECK_LAUNCH();
+    }
   }
-  const lbm_geom dg{R, C, 0, 0, 0};
   if (f || rho || u) {
     if (f) {
       int rc = lbm_soa_to_aos_pitched(sv->stage, sv->f(k), R, C, 9, g.plane_stride, g.row_pitch, sv->st);
       if (rc) return rc;
       LBM_CHECK_HIP(hipMemcpyAsync(f, sv->stage, n * 9 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
     }
-    if (rho || u) {
+    if ((rho || u) && !fixed) {
       int rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->f(k), &g, 0, R, sv->st);
       if (!rc) rc = lbm_calc_rho(sv->rho, sv->dense, R, C, sv->st);
       if (!rc) rc = lbm_calc_u(sv->u, sv->dense, sv->rho, R, C, sv->st);
       if (rc) return rc;
+    }
+    if (rho || u) {
       if (rho) LBM_CHECK_HIP(hipMemcpyAsync(rho, sv->rho, n * sizeof(double), hipMemcpyDeviceToHost, sv->st));
       if (u) {
-        rc = lbm_soa_to_aos(sv->stage, sv->u, R, C, 2, sv->st);
+        int rc = lbm_soa_to_aos(sv->stage, sv->u, R, C, 2, sv->st);
         if (rc) return rc;
         LBM_CHECK_HIP(hipMemcpyAsync(u, sv->stage, n * 2 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
       }
@@ -453,5 +558,15 @@ int lbm_ade_solver_lattices(lbm_ade_solver* sv, double** f_cur, double** g_cur, 
 }
 
 long long lbm_ade_solver_launches(const lbm_ade_solver* sv) { return sv ? sv->launches : -1; }
+
+int lbm_ade_solver_set_scalar_bc(lbm_ade_solver* sv, const lbm_ade_scalar_bc* sbc) {
+  LBM_REQUIRE(sv, "lbm_ade_solver_set_scalar_bc: NULL solver");
+  AdeWalls sw;
+  int rc = ade_scalar_bc_check("lbm_ade_solver_set_scalar_bc", sbc, &sv->bc, &sw);
+  if (rc) return rc;
+  sv->sbc = sbc ? *sbc : lbm_ade_scalar_bc{};
+  sv->fixed = sw.fixed != 0;
+  return LBM_OK;
+}
 
 }  // extern "C"

@@ -431,21 +431,35 @@ int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, 
 
 // FRAME (both edge bands, one dispatch) + pack + one message per neighbour on the ring's stream, INNER on `main` beside
 // them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches
-int lbm_ring_ade_step(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
-                      const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int edge_rows, lbm_stream_t main_s) {
-  const char* fn = "lbm_ring_ade_step";
+static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go,
+                         const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                         const lbm_ade_scalar_bc* gsbc, int edge_rows, lbm_stream_t main_s) {
   LBM_REQUIRE(rg && fn_ && gn && fo && go && fluid && scalar, "%s: NULL argument", fn);
   lbm_bc b;
   int rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
   if (rc) return rc;
+  // the scalar's walls: checked against the global edges; a FIXED row acts where the slab keeps that edge (a chain end)
+  // and is dropped at a seam, as the fluid's row wall is
+  lbm_ade_scalar_bc sb{};
+  const lbm_ade_scalar_bc* sbc = nullptr;
+  if (gsbc) {
+    const lbm_bc glob = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
+    rc = ade_scalar_bc_validate(fn, gsbc, &glob);
+    if (rc) return rc;
+    sb = *gsbc;
+    if (b.row_lo == LBM_EDGE_HALO) sb.mode[0] = LBM_ADE_SCALAR_NO_FLUX;
+    if (b.row_hi == LBM_EDGE_HALO) sb.mode[1] = LBM_ADE_SCALAR_NO_FLUX;
+    sbc = &sb;
+  }
   if (edge_rows < 1) edge_rows = 1;
   rc = ade_part_check(fn, fn_, gn, fo, go, &rg->g, &b, fluid, scalar, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr,
                       nullptr);
+  if (!rc) rc = ade_scalar_bc_validate(fn, sbc, &b);
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
   auto part = [&](int which, hipStream_t st) {
-    return lbm_ade_stream_collide_part(fn_, gn, fo, go, &rg->g, &b, fluid, scalar, which, edge_rows, nullptr, nullptr,
-                                       nullptr, st);
+    return lbm_ade_stream_collide_part_ex(fn_, gn, fo, go, &rg->g, &b, fluid, scalar, sbc, which, edge_rows, nullptr,
+                                          nullptr, nullptr, st);
   };
   if (rg->prev < 0 && rg->next < 0) {  // a chain of one slab: nothing travels
     rc = part(LBM_ADE_PART_FRAME, main);
@@ -458,6 +472,17 @@ int lbm_ring_ade_step(lbm_ring* rg, double* fn_, double* gn, const double* fo, c
   if (!rc) rc = part(LBM_ADE_PART_INNER, main);  // overlaps the exchange
   if (!rc) rc = ring_exchange_depth(rg, fn_, gn, 1, rg->edge);
   return rc ? rc : ring_join_main(rg, main);
+}
+
+int lbm_ring_ade_step(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                      const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int edge_rows, lbm_stream_t main_s) {
+  return ring_ade_step("lbm_ring_ade_step", rg, fn_, gn, fo, go, bc, fluid, scalar, nullptr, edge_rows, main_s);
+}
+
+int lbm_ring_ade_step_ex(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                         int edge_rows, lbm_stream_t main_s) {
+  return ring_ade_step("lbm_ring_ade_step_ex", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, edge_rows, main_s);
 }
 
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after) {

@@ -52,6 +52,8 @@ int make_background_stream(hipStream_t* out);
 int ade_part_check(const char* fn, const double* f_new, const double* g_new, const double* f_old, const double* g_old,
                    const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                    int part, int edge_rows, const double* rho, const double* u, const double* conc);
+// the scalar's walls (lbm_ade_scalar_bc, NULL allowed) against the edges bc, on the host
+int ade_scalar_bc_validate(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc);
 int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
                       const lbm_ade_params* scalar);
 int ade_collide_slab(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,

@@ -3,10 +3,14 @@
 // streamed like f) on lbm::AdeSolver.  Initial state: rho = 1, u = (0, U0 sin(2 pi r / R)) -- a shear wave --
 // f = equilibrium(u, rho); a Gaussian blob C = C0 exp(-|x - x_c|^2 / (2 sigma^2)) at the centre, g = equilibrium(u, C)
 // (as the driver initialises g_adve, :95).
-//   usage: passive_scalar_box R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1]
-// --dump writes prefix-{f0,g0,f,g,rho,u,C}.f64 (raw f64, reference layout [R][C][Q]); --walls 1: bounce-back columns.
+//   usage: passive_scalar_box R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]
+//          [--fixed edge=C_w[,edge=C_w...]]
+// --dump writes prefix-{f0,g0,f,g,rho,u,C}.f64 (raw f64, reference layout [R][C][Q]); --walls 1: bounce-back columns,
+// 2: bounce-back rows and columns.  --fixed: the named edges (row_lo, row_hi, col_lo, col_hi; walls of the fluid) hold
+// the scalar at the constant C_w (lbm_ade_scalar_bc FIXED), the others stay no-flux.
 #include <cmath>
 #include <iostream>
+#include <sstream>
 #include <string>
 
 #include "../include/lbm/lbm.hpp"
@@ -14,7 +18,8 @@
 
 int main(int argc, char** argv) {
   if (argc < 8) {
-    std::cerr << "usage: " << argv[0] << " R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1]\n";
+    std::cerr << "usage: " << argv[0] << " R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]"
+                 " [--fixed edge=C_w[,edge=C_w...]]\n";
     return 1;
   }
   try {
@@ -23,7 +28,18 @@ int main(int argc, char** argv) {
     const double w_r = std::stod(argv[6]), w_c = std::stod(argv[7]);
     const std::string dump = arg_value(argc, argv, "--dump", "");
     const int form = std::stoi(arg_value(argc, argv, "--form", "0"));
-    const bool walls = arg_value(argc, argv, "--walls", "0") == "1";
+    const int walls = std::stoi(arg_value(argc, argv, "--walls", "0"));
+    lbm_ade_scalar_bc sbc{};
+    std::stringstream fixed(arg_value(argc, argv, "--fixed", ""));
+    for (std::string item; std::getline(fixed, item, ',');) {
+      static const char* const names[4] = {"row_lo", "row_hi", "col_lo", "col_hi"};
+      const size_t eq = item.find('=');
+      int e = 0;
+      while (e < 4 && item.substr(0, eq) != names[e]) ++e;
+      if (eq == std::string::npos || e == 4) throw std::runtime_error("--fixed: '" + item + "' is not edge=C_w");
+      sbc.mode[e] = LBM_ADE_SCALAR_FIXED;
+      sbc.conc[e] = std::stod(item.substr(eq + 1));
+    }
     if (lbm_device_count() < 1) {
       std::cerr << "no HIP device available\n";
       return 2;
@@ -48,7 +64,9 @@ int main(int argc, char** argv) {
 
     lbm::BoundarySet bc;
     if (walls) bc.col_lo = bc.col_hi = LBM_EDGE_BOUNCE_BACK;
+    if (walls == 2) bc.row_lo = bc.row_hi = LBM_EDGE_BOUNCE_BACK;
     lbm::AdeSolver sv(R, C, omega, omega_g, w_r, w_c, bc, form);
+    sv.set_scalar_bc(sbc);
     sv.set_state(f0, g0);
     sv.step(steps);
     const lbm::AdeSolver::State s = sv.state();

@@ -13,6 +13,10 @@
 // Options: --rows R (per slab, weak scaling) --cols C --steps K --warmup W --edge-rows E --omega w --omega-g wg
 //          --walls 1 (bounce-back rows on the chain ends, bounce-back column 0, specular column C-1: a chain; default a
 //          closed, periodic ring)  --form ref|fast (both halves)  --check 1 (bitwise against one block: small sizes)
+//          --scalar-fixed 1 (with --walls 1: fixed-concentration walls of the scalar, lbm_ade_scalar_bc -- row 0 of the
+//          chain at C_w = 1e-3, column 0 at a profile, 1e-3 on the last quarter of the global rows and 0 elsewhere, read
+//          from a device array of which each slab passes its slice, column C-1 absorbing, C_w = 0, beside the specular
+//          fluid column; the last row stays no-flux)
 //
 // Printed: one JSON line; ms per step of the slowest slab, and the one-block step of a slab-sized lattice beside it.
 #include <algorithm>
@@ -29,6 +33,7 @@ namespace {
 
 struct Args {
   int rows = 512, cols = 1024, steps = 50, warmup = 5, edge_rows = 16, check = 0, emulate = 0, walls = 0;
+  int scalar_fixed = 0;
   double omega = 1.2, omega_g = 1.7;
   bool fast = true;
   std::string id_file;
@@ -76,6 +81,30 @@ lbm_bc global_bc(const Args& a) {
     b.col_hi = LBM_EDGE_SPECULAR;
   }
   return b;
+}
+
+// --scalar-fixed: the column-0 profile of the global box on the device (Rg values), NULL without the flag
+double* scalar_profile(const Args& a, int Rg) {
+  if (!a.scalar_fixed) return nullptr;
+  std::vector<double> p(Rg);
+  for (int r = 0; r < Rg; ++r) p[r] = r >= Rg - Rg / 4 ? 1e-3 : 0.0;
+  double* d = nullptr;
+  check(lbm_malloc((void**)&d, (size_t)Rg * 8), "lbm_malloc");
+  check(lbm_memcpy_h2d(d, p.data(), (size_t)Rg * 8, nullptr), "h2d");
+  check(lbm_stream_sync(nullptr), "sync");
+  return d;
+}
+
+// the scalar's walls of the rows [row0, row0 + R) of the global box: the profile's slice; a seam (HALO row edge) carries
+// no FIXED row -- what lbm_ring_ade_step_ex does with the global descriptor
+lbm_ade_scalar_bc scalar_bc(const double* profile, int row0, const lbm_bc& bc) {
+  lbm_ade_scalar_bc s{};
+  s.mode[0] = bc.row_lo == LBM_EDGE_HALO ? LBM_ADE_SCALAR_NO_FLUX : LBM_ADE_SCALAR_FIXED;
+  s.conc[0] = 1e-3;
+  s.mode[2] = s.mode[3] = LBM_ADE_SCALAR_FIXED;
+  s.profile[2] = profile ? profile + row0 : nullptr;
+  s.conc[3] = 0.0;
+  return s;
 }
 
 // padded like the solver contexts' lattices (rows off a power-of-two stride, planes off a power-of-two size)
@@ -145,12 +174,15 @@ void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_pa
   const lbm_geom g{Rg, a.cols, 0, 0, 0};
   const lbm_bc bc = global_bc(a);
   double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
+  double* prof = scalar_profile(a, Rg);
+  const lbm_ade_scalar_bc sbc = scalar_bc(prof, 0, bc);
   upload_rows(f[0], h[0], g, 0, Rg);
   check(lbm_ade_collide(f[1], h[1], f[0], h[0], &g, &bc, &fl, &sc, nullptr, nullptr, nullptr, nullptr), "lbm_ade_collide");
   int cur = 1;
   for (int t = 0; t < a.warmup + a.steps; ++t, cur ^= 1)
-    check(lbm_ade_stream_collide(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, 0, Rg, nullptr, nullptr, nullptr,
-                                 nullptr), "lbm_ade_stream_collide");
+    check(lbm_ade_stream_collide_ex(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr, 0, Rg,
+                                    nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_ex");
+  if (prof) lbm_free(prof);
   owned_to_host(f_out, f[cur], g);
   owned_to_host(g_out, h[cur], g);
   for (int k = 0; k < 2; ++k) {
@@ -211,8 +243,10 @@ int run_emulated(const Args& a, int N) {
   const bool closed = !a.walls;
   const lbm_geom g = padded_geom(R, C, 1);
   const size_t msg = (size_t)lbm_halo_rows(1) * C;  // per lattice
+  double* prof = scalar_profile(a, Rg);
   struct Slab {
     lbm_bc bc;
+    lbm_ade_scalar_bc sbc;
     double *f[2], *h[2];
     double* buf[2][2];  // [side][send / recv]: f then g
     bool prev, next;
@@ -233,6 +267,7 @@ int run_emulated(const Args& a, int N) {
       s.bc = gbc;
       if (s.prev) s.bc.row_lo = LBM_EDGE_HALO;
       if (s.next) s.bc.row_hi = LBM_EDGE_HALO;
+      s.sbc = scalar_bc(prof, k * R, s.bc);
       for (int b = 0; b < 2; ++b) {
         s.f[b] = alloc_lattice(g);
         s.h[b] = alloc_lattice(g);
@@ -259,8 +294,9 @@ int run_emulated(const Args& a, int N) {
   check(lbm_event_create(&ev_join), "lbm_event_create");
   SlabSizedBlock block(R, C);
   auto part = [&](Slab& s, int cur, int which, lbm_stream_t st) {
-    check(lbm_ade_stream_collide_part(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc, which, E, nullptr,
-                                      nullptr, nullptr, st), "lbm_ade_stream_collide_part");
+    check(lbm_ade_stream_collide_part_ex(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
+                                         prof ? &s.sbc : nullptr, which, E, nullptr, nullptr, nullptr, st),
+          "lbm_ade_stream_collide_part_ex");
   };
   auto pack = [&](Slab& s, double* f, double* h, lbm_stream_t st) {
     if (s.prev) {
@@ -313,6 +349,7 @@ int run_emulated(const Args& a, int N) {
     cur ^= 1;
   }
   check(lbm_stream_sync(edge), "sync");
+  if (prof) lbm_free(prof);
   lbm_stream_destroy(edge);
   lbm_event_destroy(ev_fork);
   lbm_event_destroy(ev_join);
@@ -332,10 +369,10 @@ int run_emulated(const Args& a, int N) {
   for (auto& s : S) slowest = std::max(slowest, s.ms / a.steps);
   const double blk = block.ms / a.steps;
   std::printf("{\"driver\": \"slab_ring_ade\", \"mode\": \"emulated %s on one GPU\", \"slabs\": %d, \"rows_per_slab\": %d, "
-              "\"cols\": %d, \"global_rows\": %d, \"walls\": %d, \"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, "
-              "\"message_rows_per_side\": %d, \"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, "
-              "\"slab_rate_over_one_block\": %.3f, \"per_slab_ms\": [",
-              closed ? "closed ring" : "chain", N, R, C, Rg, a.walls, a.fast ? "fast" : "ref", a.steps, E,
+              "\"cols\": %d, \"global_rows\": %d, \"walls\": %d, \"scalar_fixed\": %d, \"form\": \"%s\", \"steps\": %d, "
+              "\"edge_rows\": %d, \"message_rows_per_side\": %d, \"slowest_slab_ms_per_step\": %.4f, "
+              "\"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, \"per_slab_ms\": [",
+              closed ? "closed ring" : "chain", N, R, C, Rg, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, E,
               2 * lbm_halo_rows(1), slowest, blk, blk / slowest);
   for (int k = 0; k < N; ++k) std::printf("%s%.4f", k ? ", " : "", S[k].ms / a.steps);
   std::printf("]%s}\n", check_field(a, bad));
@@ -364,10 +401,12 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
   upload_rows(f[1], h[1], g, rank * R, Rg);  // pre-collision, then the first driver iteration: collide + one exchange
   check(lbm_ring_ade_collide(ring, f[0], h[0], f[1], h[1], &gbc, &fl, &sc, nullptr), "lbm_ring_ade_collide");
+  double* prof = scalar_profile(a, Rg);
+  const lbm_ade_scalar_bc sbc = scalar_bc(prof, rank * R, gbc);  // the global descriptor, this slab's profile rows
   int cur = 0;
   auto step = [&]() {
-    check(lbm_ring_ade_step(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, a.edge_rows, nullptr),
-          "lbm_ring_ade_step");
+    check(lbm_ring_ade_step_ex(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
+                               a.edge_rows, nullptr), "lbm_ring_ade_step_ex");
     cur ^= 1;
   };
   for (int i = 0; i < a.warmup; ++i) step();
@@ -404,14 +443,15 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
     for (int i = 0; i < a.warmup + a.steps; ++i) block.step(fl, sc, i >= a.warmup);
     const double ms = 1e3 * tmax / a.steps, blk = block.ms / a.steps;
     std::printf("{\"driver\": \"slab_ring_ade\", \"n_gpus\": %d, \"rows_per_gpu\": %d, \"cols\": %d, \"walls\": %d, "
-                "\"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, \"message_rows_per_side\": %d, "
+                "\"scalar_fixed\": %d, \"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, \"message_rows_per_side\": %d, "
                 "\"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, "
                 "\"mlups\": %.1f%s}\n",
-                world, R, C, a.walls, a.fast ? "fast" : "ref", a.steps, a.edge_rows, 2 * lbm_halo_rows(1), ms, blk, blk / ms,
+                world, R, C, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, a.edge_rows, 2 * lbm_halo_rows(1), ms, blk, blk / ms,
                 (double)Rg * C / (ms * 1e3), check_field(a, bad));
     std::fflush(stdout);
   }
   lbm_ring_destroy(ring);
+  if (prof) lbm_free(prof);
   for (int k = 0; k < 2; ++k) {
     lbm_free(f[k]);
     lbm_free(h[k]);
@@ -430,6 +470,11 @@ int main(int argc, char** argv) {
   a.edge_rows = std::atoi(arg_value(argc, argv, "--edge-rows", "16").c_str());
   a.check = std::atoi(arg_value(argc, argv, "--check", "0").c_str());
   a.walls = std::atoi(arg_value(argc, argv, "--walls", "0").c_str());
+  a.scalar_fixed = std::atoi(arg_value(argc, argv, "--scalar-fixed", "0").c_str());
+  if (a.scalar_fixed && !a.walls) {
+    std::fprintf(stderr, "--scalar-fixed 1 needs --walls 1 (fixed-concentration walls sit on walls of the fluid)\n");
+    return 1;
+  }
   a.emulate = std::atoi(arg_value(argc, argv, "--emulate", "0").c_str());
   a.omega = std::atof(arg_value(argc, argv, "--omega", "1.2").c_str());
   a.omega_g = std::atof(arg_value(argc, argv, "--omega-g", "1.7").c_str());

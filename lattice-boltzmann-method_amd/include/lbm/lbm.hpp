@@ -160,7 +160,7 @@ class Solver {  // single-phase BGK / KBC block, wraps lbm_solver
 
 // Compressible BGK fluid + transported scalar on one block, wraps lbm_ade_solver: the sediment concentration of
 // test/rectangle_sedimentation_test.cpp:88-247 (equilibrium(g_equi, u + w, C), its own BGK rate, streamed like f;
-// no-flux walls).  Host arrays in the reference layout.
+// no-flux walls, or fixed-concentration ones through set_scalar_bc).  Host arrays in the reference layout.
 class AdeSolver {
  public:
   AdeSolver(int R, int C, double omega, double omega_g, double w_r, double w_c, const lbm_bc& bc = BoundarySet(),
@@ -182,6 +182,9 @@ class AdeSolver {
     check(lbm_ade_solver_set_state(h_, f.data(), g.data()));
   }
   void step(int n) { check(lbm_ade_solver_step(h_, n)); }
+  // the scalar's walls from the next stream on: NO_FLUX or FIXED per edge (lbm_ade_scalar_bc; a profile is a device
+  // array the caller keeps alive and may rewrite between steps)
+  void set_scalar_bc(const lbm_ade_scalar_bc& sbc) { check(lbm_ade_solver_set_scalar_bc(h_, &sbc)); }
   // what the reference loop holds after the iterations run so far
   struct State {
     std::vector<double> f, g;  // [R][C][9]

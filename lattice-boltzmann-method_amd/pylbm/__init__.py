@@ -23,6 +23,7 @@ FORM_DEFAULT, FORM_REFERENCE_ORDER, FORM_REASSOCIATED = 0, 1, 2   # field `form`
 RING_DEFAULT, RING_RCCL, RING_IPC = -1, 0, 1
 CG_PART_FRAME, CG_PART_INNER = 1, 2   # lbm_cg_step_fused_part (LBM_CG_PART_*)
 ADE_PART_FRAME, ADE_PART_INNER = 1, 2  # lbm_ade_stream_collide_part (LBM_ADE_PART_*)
+ADE_SCALAR_NO_FLUX, ADE_SCALAR_FIXED = 0, 1  # lbm_ade_scalar_bc.mode (LBM_ADE_SCALAR_*)
 
 _dp = ct.POINTER(ct.c_double)
 
@@ -87,6 +88,27 @@ class AdeParams(ct.Structure):
 
     def __init__(self, omega_g=1.0, w=(0.0, 0.0), form=FORM_DEFAULT):
         super().__init__(omega_g, w[0], w[1], form)
+
+
+class AdeScalarBC(ct.Structure):
+    """lbm_ade_scalar_bc: the scalar's wall per edge (row_lo, row_hi, col_lo, col_hi), NO_FLUX or FIXED.  A FIXED edge
+    takes fixed=(conc, profile) with profile None (the constant conc) or a device array of C_w along the edge (a float64
+    torch tensor, C values on a row edge / R on a column edge, or a device address), read by every step, never copied."""
+    EDGES = ("row_lo", "row_hi", "col_lo", "col_hi")
+    _fields_ = [("mode", ct.c_int * 4), ("conc", ct.c_double * 4), ("profile", _dp * 4)]
+
+    def __init__(self, **fixed):
+        """AdeScalarBC(col_lo=1e-3, col_hi=(0.0, profile_tensor)): the named edges FIXED, the others NO_FLUX"""
+        super().__init__()
+        self._keep = []  # the profile tensors stay alive with the descriptor
+        for name, v in fixed.items():
+            e = self.EDGES.index(name)
+            conc, prof = (v if isinstance(v, tuple) else (v, None))
+            self.mode[e] = ADE_SCALAR_FIXED
+            self.conc[e] = float(conc)
+            self.profile[e] = _ptr(prof) if prof is not None else ct.cast(None, _dp)
+            if prof is not None and not isinstance(prof, int):
+                self._keep.append(prof)
 
 
 class LbmError(RuntimeError):
@@ -237,13 +259,25 @@ class AdeSolver:
     """Python face of lbm_ade_solver: a compressible BGK fluid f and a transported scalar g on one block
     (the sediment loop of test/rectangle_sedimentation_test.cpp), numpy AoS in/out, reference layout."""
 
-    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None):
+    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None, scalar_bc=None):
         self.lib, self.R, self.C, self.fluid, self.scalar = lib, R, C, fluid, scalar
         self.g = Geom(R, C, 0)
         self.bc = bc if bc is not None else Bc.periodic()
         self.h = ct.c_void_p()
         lib.ade_solver_create(ct.byref(self.h), ct.byref(self.g), ct.byref(self.bc), ct.byref(fluid),
                               ct.byref(scalar), _stream(stream))
+        self.scalar_bc = None
+        if scalar_bc is not None:
+            try:
+                self.set_scalar_bc(scalar_bc)
+            except LbmError:
+                self.close()
+                raise
+
+    def set_scalar_bc(self, scalar_bc):
+        """the scalar's walls from the next stream on (AdeScalarBC, or None: all NO_FLUX)"""
+        self.lib.ade_solver_set_scalar_bc(self.h, ct.byref(scalar_bc) if scalar_bc is not None else None)
+        self.scalar_bc = scalar_bc  # keeps its profile arrays alive
 
     def close(self):
         if self.h:

@@ -5,9 +5,12 @@ and against the single-step BGK launch, on one periodic box, in one process, alt
   fused      lbm_ade_solver_step: one launch per step on a periodic box (ade.hpp k_ade_stream_collide)
   composed   calc_rho, calc_u, calc_rho(g), equilibrium x2, axpb x2 (u + w), collision x2, advect x2 per step (11 launches)
   bgk        lbm_bgk_stream_collide on two padded lattices (the single-step BGK launch, f only)
+  --fixed-walls adds two walled boxes (bounce-back rows and columns, two launches per step): walls_no_flux, the scalar's
+  no-flux walls, and walls_fixed, all four edges FIXED (lbm_ade_scalar_bc; C_w = 1e-3 on row 0, a device profile on
+  column 0, 0 on the others)
 MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
 (18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
-usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast]"""
+usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls]"""
 import argparse
 import ctypes as ct
 import json
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--form", choices=["default", "ref", "fast"], default="default")
     ap.add_argument("--skip-composed", action="store_true")
+    ap.add_argument("--fixed-walls", action="store_true")
     a = ap.parse_args()
     form = {"default": pylbm.FORM_DEFAULT, "ref": pylbm.FORM_REFERENCE_ORDER, "fast": pylbm.FORM_REASSOCIATED}[a.form]
     lib = pylbm.Lib()
@@ -99,6 +103,21 @@ def main():
     def run_fused(k):
         sv.step(k)
 
+    walled = {}
+    if a.fixed_walls:
+        wbc = pylbm.Bc(row_lo=pylbm.EDGE_BOUNCE_BACK, row_hi=pylbm.EDGE_BOUNCE_BACK, col_lo=pylbm.EDGE_BOUNCE_BACK,
+                       col_hi=pylbm.EDGE_BOUNCE_BACK)
+        prof = torch.zeros(R, dtype=torch.float64, device=dev)
+        prof[R - R // 4:] = 1e-3
+        for key, sbc in (("walls_no_flux", None),
+                         ("walls_fixed", pylbm.AdeScalarBC(row_lo=1e-3, row_hi=0.0, col_lo=(0.0, prof), col_hi=0.0))):
+            w = pylbm.AdeSolver(lib, R, C, fluid, scalar, bc=wbc, stream=st.value, scalar_bc=sbc)
+            wf, wg, _, _, wgeo = w.lattices()
+            lib.lattice_copy_rows(_ptr(wf), ct.byref(wgeo), 0, _ptr(f), ct.byref(dg), 0, R, st)
+            lib.lattice_copy_rows(_ptr(wg), ct.byref(wgeo), 0, _ptr(g), ct.byref(dg), 0, R, st)
+            walled[key] = w
+        lib.stream_sync(st)
+
     # composed: the reference loop from the unfused operators (dense lattices f, g advance in place of the loop)
     if not a.skip_composed:
         fe, ge, fc, gc = (torch.empty_like(f) for _ in range(4))
@@ -119,6 +138,8 @@ def main():
             lib.advect(_ptr(g), _ptr(gc), R, C, st)
 
     runs = {"fused": run_fused, "bgk": run_bgk}
+    for key, w in walled.items():
+        runs[key] = w.step
     if not a.skip_composed:
         runs["composed"] = run_composed
     for fn in runs.values():
@@ -143,6 +164,14 @@ def main():
            "bgk_algorithmic_tbs": round(bgk_tbs, 3),
            "fused_launches_per_step": launches / (a.steps * a.repeats),
            "times_s": {k: [round(t, 5) for t in v] for k, v in times.items()}}
+    if walled:
+        out["walls_no_flux_mlups"] = round(mlups["walls_no_flux"], 1)
+        out["walls_fixed_mlups"] = round(mlups["walls_fixed"], 1)
+        out["walls_fixed_over_no_flux"] = round(mlups["walls_fixed"] / mlups["walls_no_flux"], 4)
+        out["walls_fixed_over_no_flux_per_repeat"] = [round(b / a, 4) for a, b in zip(times["walls_fixed"], times["walls_no_flux"])]
+        out["walls_launches_total"] = {k: w.launches() for k, w in walled.items()}
+        for w in walled.values():
+            w.close()
     sv.close()
     lib.event_destroy(e0)
     lib.event_destroy(e1)
