@@ -637,7 +637,8 @@ int lbm_ring_ade_step_ex(lbm_ring* rg, double* fn, double* gn, const double* fo,
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after);
 
 /* phase timing for diagnosing a scaling run: on = 1 records timed events around the edge rows, the
- * exchange (pack + send/recv + unpack) and the interior rows of every bgk / kbc launch-step;
+ * exchange (pack + send/recv + unpack) and the interior rows of every overlapped bgk / kbc / cg / ade
+ * launch-step;
  * lbm_ring_last_timing waits for the last one: out4 = {edge_rows_ms, exchange_ms, interior_ms, span_ms} */
 int lbm_ring_profile(lbm_ring* rg, int on);
 int lbm_ring_last_timing(lbm_ring* rg, double* out4);
@@ -852,7 +853,7 @@ int lbm_solver_checkpoint_load(lbm_solver* sv, const char* path);
  * wall-carrying launch; same bits).  value < 0 restores the default.  Measurements: DESIGN.md "BGK kernel variants". */
 int lbm_set_tuning(const char* key, int value);
 /* 1 when the library was built with EXPERIMENTS=1: the launch forms that were measured and not kept (tuning keys "sw_pair",
- * "sw_pf2", "ibm_chain_kernel", "ring_edges_main", "cg_strip", "cg_strip2" = 1 / 2 / 4, "cg_merge") exist; 0: those keys are
+ * "sw_pf2", "ibm_chain_kernel", "cg_strip", "cg_strip2" = 1 / 2 / 4, "cg_merge") exist; 0: those keys are
  * ignored */
 int lbm_build_has_experiments(void);
 /* an empty one-thread kernel ("k_lbm_marker") to cut a profiler trace at: measurement harnesses bracket the launches

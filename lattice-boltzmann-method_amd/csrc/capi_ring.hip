@@ -100,7 +100,6 @@ struct lbm_ring {
   int skipped;                   // launches without an exchange since the last one (their ghost rows are used up)
   int rank, nranks, next, prev;  // neighbours, -1 = none (chain end)
   lbm_geom g;                    // slab geometry (ghost = halo depth)
-  size_t msg;                    // doubles per packed message
   hipStream_t edge;              // edge rows, pack, send/recv, unpack
   hipStream_t aux;               // immersed-boundary rows + forcing chain (created on first use)
   hipEvent_t main_done, edge_done, aux_done;
@@ -115,13 +114,349 @@ struct lbm_ring {
 
 using namespace lbm;
 
-extern "C" {
+// ---- helpers of the entry points below --------------------------------------------------------------------------------
 
 static int default_transport() {
   const char* e = std::getenv("LBM_RING_TRANSPORT");
   if (e && (!std::strcmp(e, "ipc") || !std::strcmp(e, "peer") || !std::strcmp(e, "1"))) return LBM_RING_IPC;
   return LBM_RING_RCCL;
 }
+
+// One message to and one from each neighbour, enqueued on the ring's edge stream (counts in doubles; 0 = none)
+static int ring_transfer(lbm_ring* rg, const double* send_prev, size_t n_send_prev, double* recv_prev, size_t n_recv_prev,
+                         const double* send_next, size_t n_send_next, double* recv_next, size_t n_recv_next) {
+  if (rg->transport == LBM_RING_IPC)
+    return ipc_sendrecv(rg->ipc, send_prev, n_send_prev, recv_prev, n_recv_prev, send_next, n_send_next, recv_next, n_recv_next, rg->edge);
+  LBM_CHECK_NCCL(g_rccl.GroupStart());
+  // sends (to next, to prev), receives (from prev, from next): with two ranks both neighbours
+  // are the same peer and messages match in issue order
+  if (rg->next >= 0 && n_send_next) LBM_CHECK_NCCL(g_rccl.Send(send_next, n_send_next, kNcclFloat64, rg->next, rg->comm, rg->edge));
+  if (rg->prev >= 0 && n_send_prev) LBM_CHECK_NCCL(g_rccl.Send(send_prev, n_send_prev, kNcclFloat64, rg->prev, rg->comm, rg->edge));
+  if (rg->prev >= 0 && n_recv_prev) LBM_CHECK_NCCL(g_rccl.Recv(recv_prev, n_recv_prev, kNcclFloat64, rg->prev, rg->comm, rg->edge));
+  if (rg->next >= 0 && n_recv_next) LBM_CHECK_NCCL(g_rccl.Recv(recv_next, n_recv_next, kNcclFloat64, rg->next, rg->comm, rg->edge));
+  LBM_CHECK_NCCL(g_rccl.GroupEnd());
+  return LBM_OK;
+}
+
+// the ring's stream starts after everything enqueued on `main` so far
+static int ring_fork(lbm_ring* rg, hipStream_t main) {
+  LBM_CHECK_HIP(hipEventRecord(rg->main_done, main));
+  LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
+  return LBM_OK;
+}
+
+// make `main` wait for the ring's stream.  rc != 0: the caller failed after its fork; the join is enqueued all the same
+// (nothing left on the ring's stream runs unordered against main's next use of the buffers) and rc is what returns
+static int ring_join(lbm_ring* rg, hipStream_t main, int rc = LBM_OK) {
+  if (rc) {
+    if (hipEventRecord(rg->edge_done, rg->edge) == hipSuccess) (void)hipStreamWaitEvent(main, rg->edge_done, 0);
+    return rc;
+  }
+  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
+  LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
+  return LBM_OK;
+}
+
+// Bring the ghost rows of one or two lattices up to date with halo depth code G (lbm_halo_rows: 1..15,
+// LBM_HALO_FULL(d), LBM_HALO_TWO_PHASE): pack, one send + one recv per neighbour carrying every lattice back to back,
+// unpack -- all enqueued on the ring's edge stream, after the work already enqueued on `after`.
+static int ring_exchange_depth(lbm_ring* rg, double* lattice, double* lattice2, int G, lbm_stream_t after) {
+  const size_t msg = (size_t)lbm_halo_rows(G) * rg->g.C;
+  LBM_REQUIRE(msg * (lattice2 ? 2 : 1) <= rg->bufsz, "lbm_ring: message of %zu doubles, buffers of %zu", msg * (lattice2 ? 2 : 1), rg->bufsz);
+  rg->valid = G == LBM_HALO_TWO_PHASE ? 3 : (G >= 100 ? G - 100 : G);  // these ghost rows are current again
+  rg->skipped = 0;
+  if (as_stream(after) != rg->edge) {
+    int rc = ring_fork(rg, as_stream(after));
+    if (rc) return rc;
+  }
+  double* lats[2] = {lattice, lattice2};
+  const int nl = lattice2 ? 2 : 1;
+  const size_t count = msg * nl;
+  for (int k = 0; k < nl; ++k) {
+    if (rg->next >= 0) {
+      int rc = lbm_halo_pack(rg->send_next + k * msg, lats[k], &rg->g, G, 1, rg->edge);
+      if (rc) return rc;
+    }
+    if (rg->prev >= 0) {
+      int rc = lbm_halo_pack(rg->send_prev + k * msg, lats[k], &rg->g, G, 0, rg->edge);
+      if (rc) return rc;
+    }
+  }
+  {
+    const size_t np = rg->prev >= 0 ? count : 0, nn = rg->next >= 0 ? count : 0;
+    int rc = ring_transfer(rg, rg->send_prev, np, rg->recv_prev, np, rg->send_next, nn, rg->recv_next, nn);
+    if (rc) return rc;
+  }
+  for (int k = 0; k < nl; ++k) {
+    if (rg->prev >= 0) {
+      int rc = lbm_halo_unpack(lats[k], rg->recv_prev + k * msg, &rg->g, G, 0, rg->edge);
+      if (rc) return rc;
+    }
+    if (rg->next >= 0) {
+      int rc = lbm_halo_unpack(lats[k], rg->recv_next + k * msg, &rg->g, G, 1, rg->edge);
+      if (rc) return rc;
+    }
+  }
+  return LBM_OK;
+}
+
+// one lattice at the ring's depth (full = complete ghost rows: multi-step launches with walls), or the two colours of the
+// two-phase model (LBM_HALO_TWO_PHASE)
+static int ring_exchange(lbm_ring* rg, double* lattice, double* lattice2, lbm_stream_t after, bool full = false) {
+  const int G = lattice2 ? LBM_HALO_TWO_PHASE : (full ? LBM_HALO_FULL(rg->g.ghost) : rg->g.ghost);
+  return ring_exchange_depth(rg, lattice, lattice2, G, after);
+}
+
+// One send + one recv per neighbour in one RCCL group on the ring's edge stream, ordered after `after`.
+static int ring_sendrecv(lbm_ring* rg, const double* send_prev, size_t n_send_prev, double* recv_prev, size_t n_recv_prev,
+                         const double* send_next, size_t n_send_next, double* recv_next, size_t n_recv_next,
+                         hipStream_t after) {
+  if (int rc = ring_fork(rg, after)) return rc;
+  return ring_join(rg, after,
+                   ring_transfer(rg, send_prev, rg->prev >= 0 ? n_send_prev : 0, recv_prev, rg->prev >= 0 ? n_recv_prev : 0,
+                                 send_next, rg->next >= 0 ? n_send_next : 0, recv_next, rg->next >= 0 ? n_recv_next : 0));
+}
+
+// the global edges every model but the two-phase one assumes when the caller passes none
+static const lbm_bc kPeriodicBc = {0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
+
+// The slab's edges: the GLOBAL domain's (bc; NULL = dflt) with the seams -- the row edges that have a neighbour -- as HALO
+static lbm_bc ring_slab_bc(const lbm_ring* rg, const lbm_bc* bc, const lbm_bc& dflt = kPeriodicBc) {
+  lbm_bc b = bc ? *bc : dflt;
+  if (rg->prev >= 0) b.row_lo = LBM_EDGE_HALO;
+  if (rg->next >= 0) b.row_hi = LBM_EDGE_HALO;
+  return b;
+}
+
+// edge_rows below `least` become `least`; the two edge bands must leave interior rows between them
+static int ring_edge_rows(const char* fn, const lbm_ring* rg, int least, int* edge_rows) {
+  if (*edge_rows < least) *edge_rows = least;
+  LBM_REQUIRE(2 * *edge_rows < rg->g.R, "%s: edge_rows=%d too large for %d rows", fn, *edge_rows, rg->g.R);
+  return LBM_OK;
+}
+
+// One overlapped launch-step of a slab: `edges(stream)` launches the rows at both slab ends (what the neighbours wait for)
+// on the ring's stream, after everything enqueued on `main` so far (src complete); `interior(stream)` launches the rows
+// between them on `main`, concurrently; behind the edges the ring's stream exchanges dst (and dst2 in the same messages)
+// with halo depth code G.  Every exit after the fork makes `main` wait for the ring's stream: the next call may follow at
+// once.  lbm_ring_profile(1): timed events around the three phases.
+template <class Edges, class Interior>
+static int ring_step(lbm_ring* rg, hipStream_t main, Edges&& edges, Interior&& interior, double* dst, double* dst2, int G) {
+  if (int rc = ring_fork(rg, main)) return rc;
+  auto overlapped = [&]() -> int {
+    const bool prof = rg->profile != 0;
+    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_edge0, rg->edge));
+    int rc = edges(rg->edge);
+    if (rc) return rc;
+    if (prof) {
+      LBM_CHECK_HIP(hipEventRecord(rg->t_edge1, rg->edge));
+      LBM_CHECK_HIP(hipEventRecord(rg->t_main0, main));
+    }
+    rc = interior(main);  // overlaps the exchange
+    if (rc) return rc;
+    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_main1, main));
+    rc = ring_exchange_depth(rg, dst, dst2, G, rg->edge);
+    if (rc) return rc;
+    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_xchg1, rg->edge));
+    return LBM_OK;
+  };
+  return ring_join(rg, main, overlapped());
+}
+
+// ghost = m x n_steps on a closed ring: ONE exchange per m launches.  What a launch with an exchange costs over a plain
+// launch is the fork / join of the two streams (0.11 ms, profiles/r02_ring_dissect.txt), not the bytes, so the m - 1
+// launches in between run as ONE plain launch on the caller's stream over the owned rows plus the ghost rows the later
+// launches of the period still read (n_steps fewer per side each time; 2 x 5 extra rows in 1024 at m = 2), and the last
+// one is the overlapped launch-step with all m x n_steps ghost rows in the message.  Every rank takes the same branch: the
+// decision depends on the ring's shape (rg->closed -- not "this rank has both neighbours": the middle ranks of a CHAIN
+// have them too, its end ranks do not) and on the call sequence (rg->valid: ghost rows current after the last exchange
+// minus what launches without one have used up; depths may vary from call to call).
+// true: this launch goes without an exchange, as one plain launch over all g2->R rows of the widened geometry *g2
+static bool ring_period_skip(lbm_ring* rg, int n_steps, lbm_geom* g2) {
+  if (n_steps <= 1 || !rg->closed || tuning("ring_period", 0) == 1 || rg->valid < 2 * n_steps) return false;
+  // enough current ghost rows for this launch AND a later one: no exchange now.  e rows per side stay current
+  const int e = rg->valid - n_steps;
+  *g2 = rg->g;
+  g2->plane_stride = make_geom(rg->g).plane;
+  g2->R = rg->g.R + 2 * e;
+  g2->ghost = rg->g.ghost - e;
+  rg->valid = e;
+  rg->skipped += 1;
+  return true;
+}
+
+// A launch that exchanges still READS n_steps ghost rows of src.  After launches without an exchange only rg->valid of them
+// are current: a deeper launch than the rows left (depths 2,2,2,5 on 10 ghost rows leave 4) refreshes src's ghost rows first.
+static int ring_refresh_if_used_up(lbm_ring* rg, const double* src, int n_steps, bool full, hipStream_t main) {
+  if (!rg->skipped || rg->valid >= n_steps) return LBM_OK;
+  return ring_join(rg, main, ring_exchange(rg, const_cast<double*>(src), nullptr, main, full));
+}
+
+static int ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm_bc* bc,
+                         const lbm_bgk_params* prm, int n_steps, int edge_rows, lbm_stream_t main_s, bool may_skip,
+                         bool force_full = false) {
+  LBM_REQUIRE(rg && dst && src && prm, "lbm_ring_bgk_step: NULL argument");
+  const int R = rg->g.R, G = rg->g.ghost;
+  LBM_REQUIRE(n_steps >= 1 && n_steps <= G, "lbm_ring_bgk_step: %d steps with %d ghost rows", n_steps, G);
+  int rc = ring_edge_rows("lbm_ring_bgk_step", rg, G, &edge_rows);
+  if (rc) return rc;
+  const lbm_bc b = ring_slab_bc(rg, bc);
+  lbm_geom g2;
+  if (may_skip && ring_period_skip(rg, n_steps, &g2)) return lbm_bgk_stream_collide_xn(dst, src, &g2, &b, prm, n_steps, 0, g2.R, main_s);
+  // walls + several steps per launch: the NEXT launch reads complete ghost rows (force_full: a neighbour that owns an
+  // immersed-boundary band always sends and expects complete rows, whatever the columns are)
+  // (G > 1, not n_steps > 1: a single-step launch may be followed by a multi-step one that reads what travels now)
+  const bool full = force_full || (G > 1 && (bc_is_wall(b.row_lo) || bc_is_wall(b.row_hi) || bc_is_wall(b.col_lo) || bc_is_wall(b.col_hi)));
+  hipStream_t main = as_stream(main_s);
+  rc = ring_refresh_if_used_up(rg, src, n_steps, full, main);
+  if (rc) return rc;
+  auto rows = [&](int r0, int r1, hipStream_t st) -> int {
+    if (n_steps == 1) return lbm_bgk_stream_collide(dst, src, &rg->g, &b, prm, r0, r1, nullptr, nullptr, st);
+    return lbm_bgk_stream_collide_xn(dst, src, &rg->g, &b, prm, n_steps, r0, r1, st);
+  };
+  auto edges = [&](hipStream_t st) -> int {  // both ends in ONE dispatch where the window kernel runs them
+    if (n_steps > 1 && edge_rows <= 192) return lbm_bgk_stream_collide_xn2(dst, src, &rg->g, &b, prm, n_steps, 0, edge_rows, R - edge_rows, st);
+    int rc = rows(0, edge_rows, st);
+    return rc ? rc : rows(R - edge_rows, R, st);
+  };
+  auto interior = [&](hipStream_t st) { return rows(edge_rows, R - edge_rows, st); };
+  return ring_step(rg, main, edges, interior, dst, nullptr, full ? LBM_HALO_FULL(G) : G);
+}
+
+// ---- the fluid + scalar pair (lbm_ade_*) over row slabs: one ghost row per side, both lattices in one message ----------
+// The slab's edges (ring_slab_bc, periodic by default), checked with everything else the part launches check, before any
+// device call.
+static int ring_ade_edges(const char* fn, lbm_ring* rg, const lbm_bc* bc, const lbm_bgk_params* fluid,
+                          const lbm_ade_params* scalar, lbm_bc* b) {
+  LBM_REQUIRE(rg->g.ghost == 1, "%s: ghost=%d: the fluid + scalar step over slabs exchanges one ghost row per side (ring "
+              "slabs need ghost=1)", fn, rg->g.ghost);
+  *b = ring_slab_bc(rg, bc);
+  return ade_validate_slab(fn, &rg->g, b, fluid, scalar);
+}
+
+// FRAME (both edge bands, one dispatch) + pack + one message per neighbour on the ring's stream, INNER on `main` beside
+// them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches
+static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go,
+                         const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                         const lbm_ade_scalar_bc* gsbc, int edge_rows, lbm_stream_t main_s) {
+  LBM_REQUIRE(rg && fn_ && gn && fo && go && fluid && scalar, "%s: NULL argument", fn);
+  lbm_bc b;
+  int rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
+  if (rc) return rc;
+  // the scalar's walls: checked against the global edges; a FIXED row acts where the slab keeps that edge (a chain end)
+  // and is dropped at a seam, as the fluid's row wall is
+  lbm_ade_scalar_bc sb{};
+  const lbm_ade_scalar_bc* sbc = nullptr;
+  if (gsbc) {
+    rc = ade_scalar_bc_validate(fn, gsbc, bc ? bc : &kPeriodicBc);
+    if (rc) return rc;
+    sb = *gsbc;
+    if (b.row_lo == LBM_EDGE_HALO) sb.mode[0] = LBM_ADE_SCALAR_NO_FLUX;
+    if (b.row_hi == LBM_EDGE_HALO) sb.mode[1] = LBM_ADE_SCALAR_NO_FLUX;
+    sbc = &sb;
+  }
+  if (edge_rows < 1) edge_rows = 1;
+  rc = ade_part_check(fn, fn_, gn, fo, go, &rg->g, &b, fluid, scalar, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr,
+                      nullptr);
+  if (!rc) rc = ade_scalar_bc_validate(fn, sbc, &b);
+  if (rc) return rc;
+  hipStream_t main = as_stream(main_s);
+  auto part = [&](int which, hipStream_t st) {
+    return lbm_ade_stream_collide_part_ex(fn_, gn, fo, go, &rg->g, &b, fluid, scalar, sbc, which, edge_rows, nullptr,
+                                          nullptr, nullptr, st);
+  };
+  if (rg->prev < 0 && rg->next < 0) {  // a chain of one slab: nothing travels
+    rc = part(LBM_ADE_PART_FRAME, main);
+    return rc ? rc : part(LBM_ADE_PART_INNER, main);
+  }
+  return ring_step(rg, main, [&](hipStream_t st) { return part(LBM_ADE_PART_FRAME, st); },
+                   [&](hipStream_t st) { return part(LBM_ADE_PART_INNER, st); }, fn_, gn, 1);
+}
+
+// the priming exchange of lbm_slab_ibm_prime_* (once per run: its buffers are allocated here and freed
+// again; co-owners swap all their owned band rows, which the ring's block-sized buffers cannot hold)
+static int ring_ibm_prime(lbm_ring* rg, lbm_slab_ibm* sl, double* lattice, double* post, lbm_stream_t main_s) {
+  LBM_REQUIRE(rg && sl && lattice, "lbm_ring_ibm_prime: NULL argument");
+  LBM_REQUIRE((!sl->has_prev || rg->prev >= 0) && (!sl->has_next || rg->next >= 0),
+              "lbm_ring_ibm_prime: the slab has a neighbour the ring does not know");
+  LBM_REQUIRE(rg->g.ghost == sl->D, "lbm_ring_ibm_prime: ring with %d ghost rows, blocks of %d steps", rg->g.ghost, sl->D);
+  hipStream_t main = as_stream(main_s);
+  long long cnt[2][2];  // [side][send / recv]
+  for (int side = 0; side < 2; ++side) {
+    int rc = lbm_slab_ibm_prime_counts(sl, side, &cnt[side][0], &cnt[side][1]);
+    if (rc) return rc;
+  }
+  double* buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  hipError_t e = hipSuccess;
+  for (int side = 0; side < 2; ++side)
+    for (int k = 0; k < 2; ++k)
+      if (cnt[side][k] > 0 && e == hipSuccess) e = hipMalloc(&buf[side][k], (size_t)cnt[side][k] * sizeof(double));
+  int rc = LBM_OK;
+  if (e != hipSuccess) {
+    set_error("lbm_ring_ibm_prime: %s", hipGetErrorString(e));
+    rc = LBM_ERR_HIP;
+  }
+  if (!rc) rc = lbm_slab_ibm_prime_pack(sl, lattice, buf[0][0], buf[1][0], main_s);
+  if (!rc) rc = ring_sendrecv(rg, buf[0][0], (size_t)cnt[0][0], buf[0][1], (size_t)cnt[0][1], buf[1][0], (size_t)cnt[1][0],
+                              buf[1][1], (size_t)cnt[1][1], main);
+  if (!rc) rc = post ? lbm_slab_ibm_start_finish(sl, post, lattice, buf[0][1], buf[1][1], main_s)
+                     : lbm_slab_ibm_prime_finish(sl, lattice, buf[0][1], buf[1][1], main_s);
+  if (!rc && hipStreamSynchronize(main) != hipSuccess) {
+    set_error("lbm_ring_ibm_prime: stream synchronisation failed");
+    rc = LBM_ERR_HIP;
+  }
+  for (int side = 0; side < 2; ++side)
+    for (int k = 0; k < 2; ++k)
+      if (buf[side][k]) (void)hipFree(buf[side][k]);
+  return rc;
+}
+
+// ---- pressure-periodic rows over the (periodic) ring: capi_slab_pressure.hip holds the engine ---------------------
+static int ring_pressure_start(lbm_ring* rg, lbm_slab_pressure* sl, double* post, double* pre, const double* m0, const double* m1,
+                               lbm_stream_t main_s) {
+  LBM_REQUIRE(rg && sl && post && pre, "lbm_ring_pressure_start: NULL argument");
+  LBM_REQUIRE(rg->prev >= 0 && rg->next >= 0 && rg->nranks >= 2, "lbm_ring_pressure_start: needs a periodic ring of at least 2 slabs");
+  {
+    int R = 0, C = 0, ghost = 0, D = 0;
+    int rc = lbm_slab_pressure_info(sl, &R, &C, &ghost, &D);
+    if (rc) return rc;
+    LBM_REQUIRE(rg->g.R == R && rg->g.C == C && rg->g.ghost == ghost && ghost >= D,
+                "lbm_ring_pressure_start: ring (%d x %d, %d ghost rows) and slab (%d x %d, %d ghost rows, blocks of %d) differ",
+                rg->g.R, rg->g.C, rg->g.ghost, R, C, ghost, D);
+  }
+  const size_t n_prev = (size_t)lbm_slab_pressure_msg_doubles(sl, 0, 1), n_next = (size_t)lbm_slab_pressure_msg_doubles(sl, 1, 1);
+  // (the partner of a seam sends what this side receives: the start-up messages across the pressure seam are both 2 D rows)
+  double* buf[4] = {nullptr, nullptr, nullptr, nullptr};
+  const size_t cnt[4] = {n_prev, n_prev, n_next, n_next};  // send_prev, recv_prev, send_next, recv_next
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipMalloc(&buf[k], cnt[k] * sizeof(double));
+  int rc = LBM_OK;
+  if (e != hipSuccess) {
+    set_error("lbm_ring_pressure_start: %s", hipGetErrorString(e));
+    rc = LBM_ERR_HIP;
+  }
+  hipStream_t main = as_stream(main_s);
+  if (!rc) rc = m0 ? lbm_slab_pressure_start_pack_kbc(sl, pre, m0, m1, buf[0], buf[2], main_s) : lbm_slab_pressure_start_pack(sl, pre, buf[0], buf[2], main_s);
+  if (!rc) rc = ring_sendrecv(rg, buf[0], n_prev, buf[1], n_prev, buf[2], n_next, buf[3], n_next, main);
+  if (!rc) rc = m0 ? lbm_slab_pressure_start_finish_kbc(sl, post, pre, m0, m1, buf[1], buf[3], main_s)
+                   : lbm_slab_pressure_start_finish(sl, post, pre, buf[1], buf[3], main_s);
+  if (!rc && m0) {  // KBC: the collision on held moments left the ghost rows of `post` behind: complete halos over every seam
+    rc = ring_exchange(rg, post, nullptr, main, true);
+    if (!rc) rc = ring_join(rg, main);  // (errors become rc: the common tail below still syncs and frees the four start-up buffers)
+  }
+  // the start-up buffers are freed below: nothing enqueued on them may still be running -- on the error paths too
+  hipError_t es = hipStreamSynchronize(main);
+  if (es == hipSuccess && rg->edge) es = hipStreamSynchronize(rg->edge);
+  if (!rc && es != hipSuccess) {
+    set_error("lbm_ring_pressure_start: stream synchronisation failed");
+    rc = LBM_ERR_HIP;
+  }
+  for (double* b : buf)
+    if (b) (void)hipFree(b);
+  return rc;
+}
+
+extern "C" {
 
 int lbm_ring_unique_id_ex(unsigned char* id128, int transport) {
   LBM_REQUIRE(id128, "lbm_ring_unique_id: NULL buffer");
@@ -165,7 +500,6 @@ int lbm_ring_create_ex(lbm_ring** out, const unsigned char* id128, int rank, int
   rg->prev = (periodic || rank > 0) ? (rank + nranks - 1) % nranks : -1;
   rg->closed = periodic ? 1 : 0;
   rg->g = *slab;
-  rg->msg = (size_t)lbm_halo_rows(slab->ghost) * slab->C;
   // room for the two-colour message of the two-phase step when the slab has its 3 ghost rows
   size_t bufsz = (size_t)lbm_halo_rows(LBM_HALO_FULL(slab->ghost)) * slab->C;  // complete ghost rows (walls)
   if (slab->ghost == 3 && bufsz < 2 * (size_t)lbm_halo_rows(LBM_HALO_TWO_PHASE) * slab->C) bufsz = 2 * (size_t)lbm_halo_rows(LBM_HALO_TWO_PHASE) * slab->C;
@@ -263,72 +597,6 @@ int lbm_ring_destroy(lbm_ring* rg) {
   return LBM_OK;
 }
 
-// One message to and one from each neighbour, enqueued on the ring's edge stream (counts in doubles; 0 = none)
-static int ring_transfer(lbm_ring* rg, const double* send_prev, size_t n_send_prev, double* recv_prev, size_t n_recv_prev,
-                         const double* send_next, size_t n_send_next, double* recv_next, size_t n_recv_next) {
-  if (rg->transport == LBM_RING_IPC)
-    return ipc_sendrecv(rg->ipc, send_prev, n_send_prev, recv_prev, n_recv_prev, send_next, n_send_next, recv_next, n_recv_next, rg->edge);
-  LBM_CHECK_NCCL(g_rccl.GroupStart());
-  // sends (to next, to prev), receives (from prev, from next): with two ranks both neighbours
-  // are the same peer and messages match in issue order
-  if (rg->next >= 0 && n_send_next) LBM_CHECK_NCCL(g_rccl.Send(send_next, n_send_next, kNcclFloat64, rg->next, rg->comm, rg->edge));
-  if (rg->prev >= 0 && n_send_prev) LBM_CHECK_NCCL(g_rccl.Send(send_prev, n_send_prev, kNcclFloat64, rg->prev, rg->comm, rg->edge));
-  if (rg->prev >= 0 && n_recv_prev) LBM_CHECK_NCCL(g_rccl.Recv(recv_prev, n_recv_prev, kNcclFloat64, rg->prev, rg->comm, rg->edge));
-  if (rg->next >= 0 && n_recv_next) LBM_CHECK_NCCL(g_rccl.Recv(recv_next, n_recv_next, kNcclFloat64, rg->next, rg->comm, rg->edge));
-  LBM_CHECK_NCCL(g_rccl.GroupEnd());
-  return LBM_OK;
-}
-
-// Bring the ghost rows of one or two lattices up to date with halo depth code G (lbm_halo_rows: 1..15,
-// LBM_HALO_FULL(d), LBM_HALO_TWO_PHASE): pack, one send + one recv per neighbour carrying every lattice back to back,
-// unpack -- all enqueued on the ring's edge stream, after the work already enqueued on `after`.
-static int ring_exchange_depth(lbm_ring* rg, double* lattice, double* lattice2, int G, lbm_stream_t after) {
-  const size_t msg = (size_t)lbm_halo_rows(G) * rg->g.C;
-  LBM_REQUIRE(msg * (lattice2 ? 2 : 1) <= rg->bufsz, "lbm_ring: message of %zu doubles, buffers of %zu", msg * (lattice2 ? 2 : 1), rg->bufsz);
-  rg->valid = G == LBM_HALO_TWO_PHASE ? 3 : (G >= 100 ? G - 100 : G);  // these ghost rows are current again
-  rg->skipped = 0;
-  if (as_stream(after) != rg->edge) {
-    LBM_CHECK_HIP(hipEventRecord(rg->main_done, as_stream(after)));
-    LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
-  }
-  double* lats[2] = {lattice, lattice2};
-  const int nl = lattice2 ? 2 : 1;
-  const size_t count = msg * nl;
-  for (int k = 0; k < nl; ++k) {
-    if (rg->next >= 0) {
-      int rc = lbm_halo_pack(rg->send_next + k * msg, lats[k], &rg->g, G, 1, rg->edge);
-      if (rc) return rc;
-    }
-    if (rg->prev >= 0) {
-      int rc = lbm_halo_pack(rg->send_prev + k * msg, lats[k], &rg->g, G, 0, rg->edge);
-      if (rc) return rc;
-    }
-  }
-  {
-    const size_t np = rg->prev >= 0 ? count : 0, nn = rg->next >= 0 ? count : 0;
-    int rc = ring_transfer(rg, rg->send_prev, np, rg->recv_prev, np, rg->send_next, nn, rg->recv_next, nn);
-    if (rc) return rc;
-  }
-  for (int k = 0; k < nl; ++k) {
-    if (rg->prev >= 0) {
-      int rc = lbm_halo_unpack(lats[k], rg->recv_prev + k * msg, &rg->g, G, 0, rg->edge);
-      if (rc) return rc;
-    }
-    if (rg->next >= 0) {
-      int rc = lbm_halo_unpack(lats[k], rg->recv_next + k * msg, &rg->g, G, 1, rg->edge);
-      if (rc) return rc;
-    }
-  }
-  return LBM_OK;
-}
-
-// one lattice at the ring's depth (full = complete ghost rows: multi-step launches with walls), or the two colours of the
-// two-phase model (LBM_HALO_TWO_PHASE)
-static int ring_exchange(lbm_ring* rg, double* lattice, double* lattice2, lbm_stream_t after, bool full = false) {
-  const int G = lattice2 ? LBM_HALO_TWO_PHASE : (full ? LBM_HALO_FULL(rg->g.ghost) : rg->g.ghost);
-  return ring_exchange_depth(rg, lattice, lattice2, G, after);
-}
-
 int lbm_ring_exchange(lbm_ring* rg, double* lattice, lbm_stream_t after) {
   LBM_REQUIRE(rg && lattice, "lbm_ring_exchange: NULL argument");
   return ring_exchange(rg, lattice, nullptr, after);
@@ -356,63 +624,32 @@ int lbm_ring_cg_step(lbm_ring* rg, double* dst_r, double* dst_b, const double* s
   LBM_REQUIRE(rg && dst_r && dst_b && src_r && src_b && prm, "lbm_ring_cg_step: NULL argument");
   const int R = rg->g.R, G = rg->g.ghost;
   LBM_REQUIRE(G == 3, "lbm_ring_cg_step: the two-phase step needs 3 ghost rows (ring has %d)", G);
-  if (edge_rows < G) edge_rows = G;
-  LBM_REQUIRE(2 * edge_rows < R, "lbm_ring_cg_step: edge_rows=%d too large for %d rows", edge_rows, R);
+  int rc = ring_edge_rows("lbm_ring_cg_step", rg, G, &edge_rows);
+  if (rc) return rc;
   hipStream_t main = as_stream(main_s);
-  lbm_bc b;
-  if (bc) b = *bc;
-  else lbm_cg_default_bc(&b);
-  if (rg->prev >= 0) b.row_lo = LBM_EDGE_HALO;
-  if (rg->next >= 0) b.row_hi = LBM_EDGE_HALO;
+  lbm_bc walls;
+  lbm_cg_default_bc(&walls);
+  const lbm_bc b = ring_slab_bc(rg, bc, walls);
   auto rows = [&](int r0, int r1, hipStream_t st) -> int {
     return lbm_cg_step_fused(dst_r, dst_b, src_r, src_b, &rg->g, &b, prm, r0, r1, nullptr, nullptr,
                              nullptr, nullptr, nullptr, st);
   };
-  LBM_CHECK_HIP(hipEventRecord(rg->main_done, main));
-  LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
-  int rc = LBM_OK;
-  if (rg->prev >= 0 || rg->next >= 0) {
-    if (tuning("ring_cg_parts", 1) && tuning("cg_tile", 4) == 4 && tuning("cg_strip", 0) == 0) {
-      // round 4: TWO compute launches per step instead of three row ranges of two each -- the frame of the slab (its wall /
-      // copy columns AND the first and last edge rows, whose results the neighbours wait for) on the ring's stream with the
-      // exchange behind it, the inner rectangle on the caller's stream beside both
-      rc = lbm_cg_step_fused_part(dst_r, dst_b, src_r, src_b, &rg->g, &b, prm, LBM_CG_PART_FRAME, edge_rows, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, rg->edge);
-      if (!rc) rc = lbm_cg_step_fused_part(dst_r, dst_b, src_r, src_b, &rg->g, &b, prm, LBM_CG_PART_INNER, edge_rows, nullptr, nullptr,
-                                           nullptr, nullptr, nullptr, main);
-    } else {
-      rc = rows(0, edge_rows, rg->edge);
-      if (!rc) rc = rows(R - edge_rows, R, rg->edge);
-      if (!rc) rc = rows(edge_rows, R - edge_rows, main);  // interior overlaps the exchange
-    }
-    if (!rc) rc = ring_exchange(rg, dst_r, dst_b, rg->edge);
-  } else {
-    rc = rows(0, R, main);
-  }
-  if (rc) return rc;
-  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
-  LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
-  return LBM_OK;
-}
-
-// ---- the fluid + scalar pair (lbm_ade_*) over row slabs: one ghost row per side, both lattices in one message ----------
-// The slab's edges: the GLOBAL domain's (NULL = periodic) with the seams -- both row edges of a closed ring -- as HALO;
-// checked with everything else the part launches check, before any device call.
-static int ring_ade_edges(const char* fn, lbm_ring* rg, const lbm_bc* bc, const lbm_bgk_params* fluid,
-                          const lbm_ade_params* scalar, lbm_bc* b) {
-  LBM_REQUIRE(rg->g.ghost == 1, "%s: ghost=%d: the fluid + scalar step over slabs exchanges one ghost row per side (ring "
-              "slabs need ghost=1)", fn, rg->g.ghost);
-  *b = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
-  if (rg->prev >= 0) b->row_lo = LBM_EDGE_HALO;
-  if (rg->next >= 0) b->row_hi = LBM_EDGE_HALO;
-  return ade_validate_slab(fn, &rg->g, b, fluid, scalar);
-}
-
-// make `main` wait for the ring's stream
-static int ring_join_main(lbm_ring* rg, hipStream_t main) {
-  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
-  LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
-  return LBM_OK;
+  if (rg->prev < 0 && rg->next < 0) return rows(0, R, main);  // a chain of one slab: nothing travels
+  // TWO compute launches per step where the default tile kernel runs: the frame of the slab (its wall / copy columns AND
+  // the first and last edge rows, whose results the neighbours wait for) on the ring's stream, the inner rectangle on the
+  // caller's stream; the other tile / strip forms have no part launch and run three row ranges instead
+  const bool parts = tuning("cg_tile", 4) == 4 && tuning("cg_strip", 0) == 0;
+  auto part = [&](int which, hipStream_t st) {
+    return lbm_cg_step_fused_part(dst_r, dst_b, src_r, src_b, &rg->g, &b, prm, which, edge_rows, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, st);
+  };
+  auto edges = [&](hipStream_t st) -> int {
+    if (parts) return part(LBM_CG_PART_FRAME, st);
+    int rc = rows(0, edge_rows, st);
+    return rc ? rc : rows(R - edge_rows, R, st);
+  };
+  auto interior = [&](hipStream_t st) { return parts ? part(LBM_CG_PART_INNER, st) : rows(edge_rows, R - edge_rows, st); };
+  return ring_step(rg, main, edges, interior, dst_r, dst_b, LBM_HALO_TWO_PHASE);
 }
 
 int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
@@ -425,53 +662,7 @@ int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, 
   hipStream_t main = as_stream(main_s);
   rc = ade_collide_slab(fn, fp, gp, f, g_in, &rg->g, &b, fluid, scalar, main);
   if (rc || (rg->prev < 0 && rg->next < 0)) return rc;
-  rc = ring_exchange_depth(rg, fp, gp, 1, main);
-  return rc ? rc : ring_join_main(rg, main);
-}
-
-// FRAME (both edge bands, one dispatch) + pack + one message per neighbour on the ring's stream, INNER on `main` beside
-// them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches
-static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go,
-                         const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                         const lbm_ade_scalar_bc* gsbc, int edge_rows, lbm_stream_t main_s) {
-  LBM_REQUIRE(rg && fn_ && gn && fo && go && fluid && scalar, "%s: NULL argument", fn);
-  lbm_bc b;
-  int rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
-  if (rc) return rc;
-  // the scalar's walls: checked against the global edges; a FIXED row acts where the slab keeps that edge (a chain end)
-  // and is dropped at a seam, as the fluid's row wall is
-  lbm_ade_scalar_bc sb{};
-  const lbm_ade_scalar_bc* sbc = nullptr;
-  if (gsbc) {
-    const lbm_bc glob = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
-    rc = ade_scalar_bc_validate(fn, gsbc, &glob);
-    if (rc) return rc;
-    sb = *gsbc;
-    if (b.row_lo == LBM_EDGE_HALO) sb.mode[0] = LBM_ADE_SCALAR_NO_FLUX;
-    if (b.row_hi == LBM_EDGE_HALO) sb.mode[1] = LBM_ADE_SCALAR_NO_FLUX;
-    sbc = &sb;
-  }
-  if (edge_rows < 1) edge_rows = 1;
-  rc = ade_part_check(fn, fn_, gn, fo, go, &rg->g, &b, fluid, scalar, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr,
-                      nullptr);
-  if (!rc) rc = ade_scalar_bc_validate(fn, sbc, &b);
-  if (rc) return rc;
-  hipStream_t main = as_stream(main_s);
-  auto part = [&](int which, hipStream_t st) {
-    return lbm_ade_stream_collide_part_ex(fn_, gn, fo, go, &rg->g, &b, fluid, scalar, sbc, which, edge_rows, nullptr,
-                                          nullptr, nullptr, st);
-  };
-  if (rg->prev < 0 && rg->next < 0) {  // a chain of one slab: nothing travels
-    rc = part(LBM_ADE_PART_FRAME, main);
-    return rc ? rc : part(LBM_ADE_PART_INNER, main);
-  }
-  // the ring's stream starts after everything enqueued on main so far (fo, go complete)
-  LBM_CHECK_HIP(hipEventRecord(rg->main_done, main));
-  LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
-  rc = part(LBM_ADE_PART_FRAME, rg->edge);
-  if (!rc) rc = part(LBM_ADE_PART_INNER, main);  // overlaps the exchange
-  if (!rc) rc = ring_exchange_depth(rg, fn_, gn, 1, rg->edge);
-  return rc ? rc : ring_join_main(rg, main);
+  return ring_join(rg, main, ring_exchange_depth(rg, fp, gp, 1, main));
 }
 
 int lbm_ring_ade_step(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
@@ -493,126 +684,6 @@ int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, l
   return ring_exchange_depth(rg, lattice_a, lattice_b, 1, after);
 }
 
-}  // extern "C"
-
-// One launch-step of a slab with overlap: edge rows (edge stream), interior rows (main stream,
-// concurrently), halo exchange of dst behind the edge rows.  `rows(r0, r1, stream)` launches the
-// model's kernel on a row range.  On return `main` has been made to wait for everything: the next
-// call may follow immediately.
-template <class Rows, class Edges>
-static int ring_step(lbm_ring* rg, double* dst, int edge_rows, hipStream_t main, Rows&& rows, Edges&& edges, bool full = false) {
-  const int R = rg->g.R;
-#ifdef LBM_EXPERIMENTS
-  if (tuning("ring_edges_main", 0)) {
-    // Variant (opt-in): edge rows on the caller's stream in front of the interior, only the exchange on the ring's
-    // stream.  Measured at N = 1 with self send / recv (profiles/r02_ring_dissect.txt): what a launch-step loses against
-    // one launch over all rows (1.92 ms) is NOT the exchange -- pack, RCCL and unpack together add nothing measurable --
-    // but the fork / join itself: one event record + wait pair each way per step costs 0.11 ms with the default schedule
-    // below and 0.18-0.20 ms with this one (device-scope release events change neither figure).
-    const bool prof = rg->profile != 0;
-    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_edge0, main));
-    int rc = edges(main);
-    if (rc) return rc;
-    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_edge1, main));
-    LBM_CHECK_HIP(hipEventRecord(rg->main_done, main));
-    LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
-    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_main0, main));
-    rc = rows(edge_rows, R - edge_rows, main);
-    if (rc) return rc;
-    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_main1, main));
-    rc = ring_exchange(rg, dst, nullptr, rg->edge, full);
-    if (rc) return rc;
-    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_xchg1, rg->edge));
-    LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
-    LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
-    return LBM_OK;
-  }
-#endif  // LBM_EXPERIMENTS
-  // edge stream starts after everything previously enqueued on main (src complete)
-  LBM_CHECK_HIP(hipEventRecord(rg->main_done, main));
-  LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
-  const bool prof = rg->profile != 0;
-  if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_edge0, rg->edge));
-  int rc = edges(rg->edge);  // rows [0, edge_rows) and [R - edge_rows, R)
-  if (rc) return rc;
-  if (prof) {
-    LBM_CHECK_HIP(hipEventRecord(rg->t_edge1, rg->edge));
-    LBM_CHECK_HIP(hipEventRecord(rg->t_main0, main));
-  }
-  rc = rows(edge_rows, R - edge_rows, main);  // interior overlaps the exchange
-  if (rc) return rc;
-  if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_main1, main));
-  rc = ring_exchange(rg, dst, nullptr, rg->edge, full);
-  if (rc) return rc;
-  if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_xchg1, rg->edge));
-  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
-  LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
-  return LBM_OK;
-}
-
-// A launch that exchanges still READS n_steps ghost rows of src.  After launches without an exchange only rg->valid of them
-// are current: a deeper launch than the rows left (depths 2,2,2,5 on 10 ghost rows leave 4) refreshes src's ghost rows first.
-static int ring_refresh_if_used_up(lbm_ring* rg, const double* src, int n_steps, bool full, hipStream_t main) {
-  if (!rg->skipped || rg->valid >= n_steps) return LBM_OK;
-  int rc = ring_exchange(rg, const_cast<double*>(src), nullptr, main, full);
-  if (rc) return rc;
-  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
-  LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
-  return LBM_OK;
-}
-
-static int ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm_bc* bc,
-                         const lbm_bgk_params* prm, int n_steps, int edge_rows, lbm_stream_t main_s, bool may_skip,
-                         bool force_full = false) {
-  LBM_REQUIRE(rg && dst && src && prm, "lbm_ring_bgk_step: NULL argument");
-  const int R = rg->g.R, G = rg->g.ghost;
-  LBM_REQUIRE(n_steps >= 1 && n_steps <= G, "lbm_ring_bgk_step: %d steps with %d ghost rows", n_steps, G);
-  if (edge_rows < G) edge_rows = G;
-  LBM_REQUIRE(2 * edge_rows < R, "lbm_ring_bgk_step: edge_rows=%d too large for %d rows", edge_rows, R);
-  lbm_bc b = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
-  if (rg->prev >= 0) b.row_lo = LBM_EDGE_HALO;
-  if (rg->next >= 0) b.row_hi = LBM_EDGE_HALO;
-  // ghost = m x n_steps on a closed ring: ONE exchange per m launches.  What a launch with an exchange costs over a
-  // plain launch is the fork / join of the two streams (0.11 ms, profiles/r02_ring_dissect.txt), not the bytes, so the
-  // m - 1 launches in between run as ONE plain launch on the caller's stream over the owned rows plus the ghost rows
-  // the later launches of the period still read (n_steps fewer per side each time; 2 x 5 extra rows in 1024 at m = 2),
-  // and the last one is the overlapped launch-step below with all m x n_steps ghost rows in the message.  Every rank
-  // takes the same branch: the decision depends on the ring's shape (rg->closed -- not "this rank has both neighbours":
-  // the middle ranks of a CHAIN have them too, its end ranks do not) and on the call sequence (rg->valid: ghost rows
-  // current after the last exchange minus what launches without one have used up; depths may vary from call to call).
-  if (may_skip && n_steps > 1 && rg->closed && tuning("ring_period", 0) != 1 && rg->valid >= 2 * n_steps) {
-    // enough current ghost rows for this launch AND a later one: no exchange now.  e rows per side stay current
-    const int e = rg->valid - n_steps;
-    lbm_geom g2 = rg->g;
-    g2.plane_stride = make_geom(rg->g).plane;
-    g2.R = R + 2 * e;
-    g2.ghost = G - e;
-    rg->valid = e;
-    rg->skipped += 1;
-    return lbm_bgk_stream_collide_xn(dst, src, &g2, &b, prm, n_steps, 0, g2.R, main_s);
-  }
-  // walls + several steps per launch: the NEXT launch reads complete ghost rows (force_full: a neighbour that owns an
-  // immersed-boundary band always sends and expects complete rows, whatever the columns are)
-  // (G > 1, not n_steps > 1: a single-step launch may be followed by a multi-step one that reads what travels now)
-  const bool full = force_full || (G > 1 && (bc_is_wall(b.row_lo) || bc_is_wall(b.row_hi) || bc_is_wall(b.col_lo) || bc_is_wall(b.col_hi)));
-  {
-    int rc = ring_refresh_if_used_up(rg, src, n_steps, full, as_stream(main_s));
-    if (rc) return rc;
-  }
-  auto rows = [&](int r0, int r1, hipStream_t st) -> int {
-    if (n_steps == 1) return lbm_bgk_stream_collide(dst, src, &rg->g, &b, prm, r0, r1, nullptr, nullptr, st);
-    return lbm_bgk_stream_collide_xn(dst, src, &rg->g, &b, prm, n_steps, r0, r1, st);
-  };
-  auto edges = [&](hipStream_t st) -> int {  // both ends in ONE dispatch where the window kernel runs them
-    if (n_steps > 1 && edge_rows <= 192) return lbm_bgk_stream_collide_xn2(dst, src, &rg->g, &b, prm, n_steps, 0, edge_rows, R - edge_rows, st);
-    int rc = rows(0, edge_rows, st);
-    return rc ? rc : rows(R - edge_rows, R, st);
-  };
-  return ring_step(rg, dst, edge_rows, as_stream(main_s), rows, edges, full);
-}
-
-extern "C" {
-
 // BGK: n_steps = 1: single-step kernel (ghost >= 1); n_steps >= 2: sliding-window kernel
 // (ghost >= n_steps; ghost = m x n_steps on a closed ring: one exchange per m launches).
 int lbm_ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm_bc* bc,
@@ -627,26 +698,14 @@ int lbm_ring_kbc_step(lbm_ring* rg, double* dst, const double* src, const lbm_bc
   LBM_REQUIRE(rg && dst && src && prm, "lbm_ring_kbc_step: NULL argument");
   const int R = rg->g.R, G = rg->g.ghost;
   LBM_REQUIRE(n_steps >= 1 && n_steps <= G && n_steps <= 4, "lbm_ring_kbc_step: %d steps with %d ghost rows (max 4)", n_steps, G);
-  if (edge_rows < G) edge_rows = G;
-  LBM_REQUIRE(2 * edge_rows < R, "lbm_ring_kbc_step: edge_rows=%d too large for %d rows", edge_rows, R);
-  lbm_bc b = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
-  if (rg->prev >= 0) b.row_lo = LBM_EDGE_HALO;
-  if (rg->next >= 0) b.row_hi = LBM_EDGE_HALO;
-  if (n_steps > 1 && rg->closed && tuning("ring_period", 0) != 1 && rg->valid >= 2 * n_steps) {
-    // ghost = m x n_steps rows on a closed ring: no exchange on this launch (see ring_bgk_step)
-    const int e = rg->valid - n_steps;
-    lbm_geom g2 = rg->g;
-    g2.plane_stride = make_geom(rg->g).plane;
-    g2.R = R + 2 * e;
-    g2.ghost = G - e;
-    rg->valid = e;
-    rg->skipped += 1;
-    return lbm_kbc_stream_collide_xn(dst, src, &g2, &b, prm, n_steps, 0, g2.R, main_s);
-  }
-  {
-    int rc = ring_refresh_if_used_up(rg, src, n_steps, false, as_stream(main_s));
-    if (rc) return rc;
-  }
+  int rc = ring_edge_rows("lbm_ring_kbc_step", rg, G, &edge_rows);
+  if (rc) return rc;
+  const lbm_bc b = ring_slab_bc(rg, bc);
+  lbm_geom g2;
+  if (ring_period_skip(rg, n_steps, &g2)) return lbm_kbc_stream_collide_xn(dst, src, &g2, &b, prm, n_steps, 0, g2.R, main_s);
+  hipStream_t main = as_stream(main_s);
+  rc = ring_refresh_if_used_up(rg, src, n_steps, false, main);
+  if (rc) return rc;
   auto rows = [&](int r0, int r1, hipStream_t st) -> int {
     if (n_steps == 1) return lbm_kbc_stream_collide(dst, src, &rg->g, &b, prm, r0, r1, nullptr, nullptr, st);
     return lbm_kbc_stream_collide_xn(dst, src, &rg->g, &b, prm, n_steps, r0, r1, st);
@@ -655,7 +714,8 @@ int lbm_ring_kbc_step(lbm_ring* rg, double* dst, const double* src, const lbm_bc
     int rc = rows(0, edge_rows, st);
     return rc ? rc : rows(R - edge_rows, R, st);
   };
-  return ring_step(rg, dst, edge_rows, as_stream(main_s), rows, edges);
+  auto interior = [&](hipStream_t st) { return rows(edge_rows, R - edge_rows, st); };
+  return ring_step(rg, main, edges, interior, dst, nullptr, G);
 }
 
 // One overlapped single-step launch of a BGK slab that may own an immersed boundary (config 5:
@@ -676,15 +736,13 @@ int lbm_ring_bgk_step_ibm(lbm_ring* rg, double* dst, const double* src, const lb
   LBM_REQUIRE(!ib || (rho && u), "lbm_ring_bgk_step_ibm: the owning rank needs rho and u buffers");
   const int R = rg->g.R, G = rg->g.ghost;
   LBM_REQUIRE(G >= 1, "lbm_ring_bgk_step_ibm: slab without ghost rows");
-  if (edge_rows < 1) edge_rows = 1;
-  LBM_REQUIRE(2 * edge_rows < R, "lbm_ring_bgk_step_ibm: edge_rows=%d too large for %d rows", edge_rows, R);
+  int rc = ring_edge_rows("lbm_ring_bgk_step_ibm", rg, 1, &edge_rows);
+  if (rc) return rc;
   hipStream_t main = as_stream(main_s);
-  lbm_bc b = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
-  if (rg->prev >= 0) b.row_lo = LBM_EDGE_HALO;
-  if (rg->next >= 0) b.row_hi = LBM_EDGE_HALO;
+  const lbm_bc b = ring_slab_bc(rg, bc);
   int q0 = 0, q1 = 0, c0 = 0, c1 = 0;  // ROI rows [q0, q1)
   if (ib) {
-    int rc = lbm_ibm_roi(ib, &q0, &q1, &c0, &c1);
+    rc = lbm_ibm_roi(ib, &q0, &q1, &c0, &c1);
     if (rc) return rc;
     LBM_REQUIRE(q0 >= 1 && q1 <= R - 1 && q0 < q1, "lbm_ring_bgk_step_ibm: ROI rows [%d, %d) touch the slab edge", q0, q1);
     if (!rg->aux) {
@@ -705,12 +763,12 @@ int lbm_ring_bgk_step_ibm(lbm_ring* rg, double* dst, const double* src, const lb
     if (!rc) rc = rows(q1 > r1 ? r1 : q1, r1, false, st);
     return rc;
   };
-  LBM_CHECK_HIP(hipEventRecord(rg->main_done, main));
-  LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
-  int rc = rows_outside_roi(0, edge_rows, rg->edge);
+  rc = ring_fork(rg, main);
+  if (rc) return rc;
+  rc = rows_outside_roi(0, edge_rows, rg->edge);
   if (!rc) rc = rows_outside_roi(R - edge_rows, R, rg->edge);
   if (!rc) rc = ring_exchange(rg, dst, nullptr, rg->edge);
-  if (rc) return rc;
+  if (rc) return ring_join(rg, main, rc);
   LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
   if (ib) {
     LBM_CHECK_HIP(hipStreamWaitEvent(rg->aux, rg->main_done, 0));
@@ -726,11 +784,11 @@ int lbm_ring_bgk_step_ibm(lbm_ring* rg, double* dst, const double* src, const lb
   return LBM_OK;
 }
 
-// Phase timing of launch-steps (diagnosis of a scaling run): on = 1 makes lbm_ring_bgk_step /
-// lbm_ring_kbc_step record timed events around the edge rows, the exchange (pack + send/recv +
-// unpack) and the interior rows of every launch-step; lbm_ring_last_timing waits for the last one
-// and returns {edge_rows_ms, exchange_ms, interior_ms, span_ms} (span: first edge row -> the later of
-// exchange end / interior end).  Off (default) records nothing.
+// Phase timing of launch-steps (diagnosis of a scaling run): on = 1 makes every overlapped launch-step (ring_step:
+// lbm_ring_bgk_step, lbm_ring_kbc_step, lbm_ring_cg_step, lbm_ring_ade_step*) record timed events around the edge rows,
+// the exchange (pack + send/recv + unpack) and the interior rows; lbm_ring_last_timing waits for the last one and returns
+// {edge_rows_ms, exchange_ms, interior_ms, span_ms} (span: first edge row -> the later of exchange end / interior end).
+// Off (default) records nothing.
 int lbm_ring_profile(lbm_ring* rg, int on) {
   LBM_REQUIRE(rg, "lbm_ring_profile: NULL ring");
   if (on && !rg->t_edge0)
@@ -759,25 +817,6 @@ int lbm_ring_last_timing(lbm_ring* rg, double* out4) {
 }
 
 // ---- config 5 over slabs at multi-step speed (capi_slab_ibm.hip holds the per-rank engine) ----------------
-// One send + one recv per neighbour in one RCCL group on the ring's edge stream, ordered after `after`.
-static int ring_sendrecv(lbm_ring* rg, const double* send_prev, size_t n_send_prev, double* recv_prev, size_t n_recv_prev,
-                         const double* send_next, size_t n_send_next, double* recv_next, size_t n_recv_next,
-                         hipStream_t after) {
-  LBM_CHECK_HIP(hipEventRecord(rg->main_done, after));
-  LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
-  {
-    int rc = ring_transfer(rg, send_prev, rg->prev >= 0 ? n_send_prev : 0, recv_prev, rg->prev >= 0 ? n_recv_prev : 0, send_next,
-                           rg->next >= 0 ? n_send_next : 0, recv_next, rg->next >= 0 ? n_recv_next : 0);
-    if (rc) return rc;
-  }
-  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
-  LBM_CHECK_HIP(hipStreamWaitEvent(after, rg->edge_done, 0));
-  return LBM_OK;
-}
-
-// the priming exchange of lbm_slab_ibm_prime_* (once per run: its buffers are allocated here and freed
-// again; co-owners swap all their owned band rows, which the ring's block-sized buffers cannot hold)
-static int ring_ibm_prime(lbm_ring* rg, lbm_slab_ibm* sl, double* lattice, double* post, lbm_stream_t main_s);
 int lbm_ring_ibm_prime(lbm_ring* rg, lbm_slab_ibm* sl, double* lattice, lbm_stream_t main_s) {
   return ring_ibm_prime(rg, sl, lattice, nullptr, main_s);
 }
@@ -786,41 +825,6 @@ int lbm_ring_ibm_prime(lbm_ring* rg, lbm_slab_ibm* sl, double* lattice, lbm_stre
 int lbm_ring_ibm_start(lbm_ring* rg, lbm_slab_ibm* sl, double* post, double* pre, lbm_stream_t main_s) {
   LBM_REQUIRE(post, "lbm_ring_ibm_start: NULL argument");
   return ring_ibm_prime(rg, sl, pre, post, main_s);
-}
-static int ring_ibm_prime(lbm_ring* rg, lbm_slab_ibm* sl, double* lattice, double* post, lbm_stream_t main_s) {
-  LBM_REQUIRE(rg && sl && lattice, "lbm_ring_ibm_prime: NULL argument");
-  LBM_REQUIRE((!sl->has_prev || rg->prev >= 0) && (!sl->has_next || rg->next >= 0),
-              "lbm_ring_ibm_prime: the slab has a neighbour the ring does not know");
-  LBM_REQUIRE(rg->g.ghost == sl->D, "lbm_ring_ibm_prime: ring with %d ghost rows, blocks of %d steps", rg->g.ghost, sl->D);
-  hipStream_t main = as_stream(main_s);
-  long long cnt[2][2];  // [side][send / recv]
-  for (int side = 0; side < 2; ++side) {
-    int rc = lbm_slab_ibm_prime_counts(sl, side, &cnt[side][0], &cnt[side][1]);
-    if (rc) return rc;
-  }
-  double* buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  hipError_t e = hipSuccess;
-  for (int side = 0; side < 2; ++side)
-    for (int k = 0; k < 2; ++k)
-      if (cnt[side][k] > 0 && e == hipSuccess) e = hipMalloc(&buf[side][k], (size_t)cnt[side][k] * sizeof(double));
-  int rc = LBM_OK;
-  if (e != hipSuccess) {
-    set_error("lbm_ring_ibm_prime: %s", hipGetErrorString(e));
-    rc = LBM_ERR_HIP;
-  }
-  if (!rc) rc = lbm_slab_ibm_prime_pack(sl, lattice, buf[0][0], buf[1][0], main_s);
-  if (!rc) rc = ring_sendrecv(rg, buf[0][0], (size_t)cnt[0][0], buf[0][1], (size_t)cnt[0][1], buf[1][0], (size_t)cnt[1][0],
-                              buf[1][1], (size_t)cnt[1][1], main);
-  if (!rc) rc = post ? lbm_slab_ibm_start_finish(sl, post, lattice, buf[0][1], buf[1][1], main_s)
-                     : lbm_slab_ibm_prime_finish(sl, lattice, buf[0][1], buf[1][1], main_s);
-  if (!rc && hipStreamSynchronize(main) != hipSuccess) {
-    set_error("lbm_ring_ibm_prime: stream synchronisation failed");
-    rc = LBM_ERR_HIP;
-  }
-  for (int side = 0; side < 2; ++side)
-    for (int k = 0; k < 2; ++k)
-      if (buf[side][k]) (void)hipFree(buf[side][k]);
-  return rc;
 }
 
 // One block of sl->D steps of a BGK slab in the ring.  Slabs without valid band rows run the overlapped
@@ -847,9 +851,6 @@ int lbm_ring_bgk_block_ibm(lbm_ring* rg, lbm_slab_ibm* sl, double* dst, const do
   return lbm_slab_ibm_block_finish(sl, dst, rg->recv_prev, rg->recv_next, main_s);
 }
 
-// ---- pressure-periodic rows over the (periodic) ring: capi_slab_pressure.hip holds the engine ---------------------
-static int ring_pressure_start(lbm_ring* rg, lbm_slab_pressure* sl, double* post, double* pre, const double* m0, const double* m1,
-                               lbm_stream_t main_s);
 int lbm_ring_pressure_start(lbm_ring* rg, lbm_slab_pressure* sl, double* post, double* pre, lbm_stream_t main_s) {
   return ring_pressure_start(rg, sl, post, pre, nullptr, nullptr, main_s);
 }
@@ -857,56 +858,6 @@ int lbm_ring_pressure_start_kbc(lbm_ring* rg, lbm_slab_pressure* sl, double* pos
                                 const double* m1, lbm_stream_t main_s) {
   LBM_REQUIRE(m0 && m1, "lbm_ring_pressure_start_kbc: NULL moments");
   return ring_pressure_start(rg, sl, post, pre, m0, m1, main_s);
-}
-static int ring_pressure_start(lbm_ring* rg, lbm_slab_pressure* sl, double* post, double* pre, const double* m0, const double* m1,
-                               lbm_stream_t main_s) {
-  LBM_REQUIRE(rg && sl && post && pre, "lbm_ring_pressure_start: NULL argument");
-  LBM_REQUIRE(rg->prev >= 0 && rg->next >= 0 && rg->nranks >= 2, "lbm_ring_pressure_start: needs a periodic ring of at least 2 slabs");
-  {
-    int R = 0, C = 0, ghost = 0, D = 0;
-    int rc = lbm_slab_pressure_info(sl, &R, &C, &ghost, &D);
-    if (rc) return rc;
-    LBM_REQUIRE(rg->g.R == R && rg->g.C == C && rg->g.ghost == ghost && ghost >= D,
-                "lbm_ring_pressure_start: ring (%d x %d, %d ghost rows) and slab (%d x %d, %d ghost rows, blocks of %d) differ",
-                rg->g.R, rg->g.C, rg->g.ghost, R, C, ghost, D);
-  }
-  const size_t n_prev = (size_t)lbm_slab_pressure_msg_doubles(sl, 0, 1), n_next = (size_t)lbm_slab_pressure_msg_doubles(sl, 1, 1);
-  // (the partner of a seam sends what this side receives: the start-up messages across the pressure seam are both 2 D rows)
-  double* buf[4] = {nullptr, nullptr, nullptr, nullptr};
-  const size_t cnt[4] = {n_prev, n_prev, n_next, n_next};  // send_prev, recv_prev, send_next, recv_next
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipMalloc(&buf[k], cnt[k] * sizeof(double));
-  int rc = LBM_OK;
-  if (e != hipSuccess) {
-    set_error("lbm_ring_pressure_start: %s", hipGetErrorString(e));
-    rc = LBM_ERR_HIP;
-  }
-  hipStream_t main = as_stream(main_s);
-  if (!rc) rc = m0 ? lbm_slab_pressure_start_pack_kbc(sl, pre, m0, m1, buf[0], buf[2], main_s) : lbm_slab_pressure_start_pack(sl, pre, buf[0], buf[2], main_s);
-  if (!rc) rc = ring_sendrecv(rg, buf[0], n_prev, buf[1], n_prev, buf[2], n_next, buf[3], n_next, main);
-  if (!rc) rc = m0 ? lbm_slab_pressure_start_finish_kbc(sl, post, pre, m0, m1, buf[1], buf[3], main_s)
-                   : lbm_slab_pressure_start_finish(sl, post, pre, buf[1], buf[3], main_s);
-  if (!rc && m0) {  // KBC: the collision on held moments left the ghost rows of `post` behind: complete halos over every seam
-    rc = ring_exchange(rg, post, nullptr, main, true);
-    if (!rc) {  // (errors become rc: the common tail below still syncs and frees the four start-up buffers)
-      hipError_t ej = hipEventRecord(rg->edge_done, rg->edge);
-      if (ej == hipSuccess) ej = hipStreamWaitEvent(main, rg->edge_done, 0);
-      if (ej != hipSuccess) {
-        set_error("lbm_ring_pressure_start: %s", hipGetErrorString(ej));
-        rc = LBM_ERR_HIP;
-      }
-    }
-  }
-  // the start-up buffers are freed below: nothing enqueued on them may still be running -- on the error paths too
-  hipError_t es = hipStreamSynchronize(main);
-  if (es == hipSuccess && rg->edge) es = hipStreamSynchronize(rg->edge);
-  if (!rc && es != hipSuccess) {
-    set_error("lbm_ring_pressure_start: stream synchronisation failed");
-    rc = LBM_ERR_HIP;
-  }
-  for (double* b : buf)
-    if (b) (void)hipFree(b);
-  return rc;
 }
 
 int lbm_ring_bgk_block_pressure(lbm_ring* rg, lbm_slab_pressure* sl, double* dst, const double* src, lbm_stream_t main_s) {
@@ -932,9 +883,7 @@ int lbm_ring_bgk_block_pressure(lbm_ring* rg, lbm_slab_pressure* sl, double* dst
 // make `main` wait for an exchange enqueued with lbm_ring_exchange (initial ghost fill)
 int lbm_ring_join(lbm_ring* rg, lbm_stream_t main_s) {
   LBM_REQUIRE(rg, "lbm_ring_join: NULL ring");
-  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
-  LBM_CHECK_HIP(hipStreamWaitEvent(as_stream(main_s), rg->edge_done, 0));
-  return LBM_OK;
+  return ring_join(rg, as_stream(main_s));
 }
 
 }  // extern "C"
