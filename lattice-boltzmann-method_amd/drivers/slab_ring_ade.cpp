@@ -19,24 +19,19 @@
 //          fluid column; the last row stays no-flux)
 //
 // Printed: one JSON line; ms per step of the slowest slab, and the one-block step of a slab-sized lattice beside it.
-#include <algorithm>
-#include <chrono>
+//
+// run_rank / run_emulated hold the model and its lbm_ring_* calls; options, main(), the timed run, --check's comparison
+// and the emulation's links are ring_common.hpp.
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "common.hpp"
 #include "ring_common.hpp"
 
 namespace {
 
-struct Args {
-  int rows = 512, cols = 1024, steps = 50, warmup = 5, edge_rows = 16, check = 0, emulate = 0, walls = 0;
-  int scalar_fixed = 0;
+struct Args : RingOpts {
+  int walls = 0, scalar_fixed = 0;
   double omega = 1.2, omega_g = 1.7;
   bool fast = true;
-  std::string id_file;
 };
 
 // shear wave + Taylor-Green vortices on the GLOBAL box, scalar: a Gaussian blob; f = feq(u, rho), g = feq(u + w, C) in
@@ -49,17 +44,8 @@ void init_node(double* f9, double* g9, int gr, int c, int Rg, int C) {
   const double rho = 1.0 + 0.01 * std::cos(2 * x);
   const double dr = gr - 0.45 * Rg, dc = c - 0.55 * C, s = 0.12 * std::min(Rg, C);
   const double conc = 1e-3 * std::exp(-(dr * dr + dc * dc) / (2 * s * s));
-  static const double w[9] = {4. / 9, 1. / 9, 1. / 9, 1. / 9, 1. / 9, 1. / 36, 1. / 36, 1. / 36, 1. / 36};
-  static const int cx[9] = {0, 1, 0, -1, 0, 1, -1, -1, 1}, cy[9] = {0, 0, 1, 0, -1, 1, 1, -1, -1};
-  auto feq = [&](double* e, double d, double a, double b) {
-    const double uu = a * a + b * b;
-    for (int q = 0; q < 9; ++q) {
-      const double cu = cx[q] * a + cy[q] * b;
-      e[q] = w[q] * d * (1.0 + 3.0 * cu + 4.5 * cu * cu - 1.5 * uu);
-    }
-  };
-  feq(f9, rho, u0, u1);
-  feq(g9, conc, u0 + kW[0], u1 + kW[1]);
+  d2q9_equilibrium(f9, rho, u0, u1);
+  d2q9_equilibrium(g9, conc, u0 + kW[0], u1 + kW[1]);
 }
 
 // the plain compressible fluid and the scalar, both halves in the form of --form
@@ -107,29 +93,6 @@ lbm_ade_scalar_bc scalar_bc(const double* profile, int row0, const lbm_bc& bc) {
   return s;
 }
 
-// padded like the solver contexts' lattices (rows off a power-of-two stride, planes off a power-of-two size)
-lbm_geom padded_geom(int R, int C, int G) {
-  const int pitch = lbm_default_row_pitch(C);
-  long long plane = (long long)(R + 2 * G) * pitch + lbm_default_plane_pad(R + 2 * G, pitch);
-  plane += plane & 1;  // even: 16-byte accesses
-  return lbm_geom{R, C, G, plane, pitch > C ? pitch : 0};
-}
-
-// doubles per plane of a lattice (plane_stride 0 = dense: (R + 2 ghost) rows of the row pitch)
-size_t plane_doubles(const lbm_geom& g) {
-  if (g.plane_stride > 0) return (size_t)g.plane_stride;
-  return (size_t)(g.R + 2 * g.ghost) * (size_t)(g.row_pitch > 0 ? g.row_pitch : g.C);
-}
-
-double* alloc_lattice(const lbm_geom& g) {
-  const size_t bytes = plane_doubles(g) * 9 * 8;
-  if (bytes == 0) throw std::runtime_error("empty lattice");
-  double* p = nullptr;
-  check(lbm_malloc((void**)&p, bytes), "lbm_malloc");
-  check(lbm_memset(p, 0, bytes, nullptr), "memset");
-  return p;
-}
-
 // pre-collision f, g of global rows [row0, row0 + R) into lattices of geometry g (owned rows; the rest zero)
 void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
   const int R = g.R, C = g.C;
@@ -155,18 +118,6 @@ void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
   lbm_free(stage);
 }
 
-// owned rows of a lattice as dense [9][R][C] on the host
-void owned_to_host(std::vector<double>& out, const double* lat, const lbm_geom& g) {
-  const lbm_geom d{g.R, g.C, 0, 0, 0};
-  double* dense = nullptr;
-  check(lbm_malloc((void**)&dense, (size_t)9 * g.R * g.C * 8), "lbm_malloc");
-  check(lbm_lattice_copy_rows(dense, &d, 0, lat, &g, 0, g.R, nullptr), "lbm_lattice_copy_rows");
-  out.resize((size_t)9 * g.R * g.C);
-  check(lbm_memcpy_d2h(out.data(), dense, out.size() * 8, nullptr), "d2h");
-  check(lbm_stream_sync(nullptr), "sync");
-  lbm_free(dense);
-}
-
 // One block of Rg x C (ghost 0, dense), collide-only + `steps` fused steps: the yardstick of --check.  Returns f, g of
 // the owned rows as dense [9][Rg][C] on the host.
 void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_params& sc, std::vector<double>& f_out,
@@ -183,8 +134,8 @@ void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_pa
     check(lbm_ade_stream_collide_ex(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr, 0, Rg,
                                     nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_ex");
   if (prof) lbm_free(prof);
-  owned_to_host(f_out, f[cur], g);
-  owned_to_host(g_out, h[cur], g);
+  f_out = owned_to_host(f[cur], g);
+  g_out = owned_to_host(h[cur], g);
   for (int k = 0; k < 2; ++k) {
     lbm_free(f[k]);
     lbm_free(h[k]);
@@ -225,10 +176,6 @@ struct SlabSizedBlock {
   }
 };
 
-const char* check_field(const Args& a, int bad) {
-  return !a.check ? "" : (bad ? ", \"check\": \"MISMATCH\"" : ", \"check\": \"bitwise equal to one block\"");
-}
-
 // --emulate N: every slab in turn on ONE GPU.  A slab's step is what lbm_ring_ade_step enqueues -- FRAME on the ring's
 // stream, INNER on the main stream beside it, the pack behind FRAME -- with the messages (both lattices, 2 x 3 rows per
 // side) as device copies between the steps.  Slab k's edges: the global box's, seams HALO (both row edges of a closed
@@ -248,12 +195,9 @@ int run_emulated(const Args& a, int N) {
     lbm_bc bc;
     lbm_ade_scalar_bc sbc;
     double *f[2], *h[2];
-    double* buf[2][2];  // [side][send / recv]: f then g
-    bool prev, next;
-    void* ev[2];
-    double ms = 0;
   };
   std::vector<Slab> S(N);
+  EmulatedLinks links(N, closed);  // a message: f then g
   {
     // the one block's post-collision state (lbm_ade_collide on the global lattice), scattered into the slabs
     const lbm_geom gg{Rg, C, 0, 0, 0};
@@ -262,17 +206,14 @@ int run_emulated(const Args& a, int N) {
     check(lbm_ade_collide(fp, hp, f0, h0, &gg, &gbc, &fl, &sc, nullptr, nullptr, nullptr, nullptr), "lbm_ade_collide");
     for (int k = 0; k < N; ++k) {
       Slab& s = S[k];
-      s.prev = closed || k > 0;
-      s.next = closed || k < N - 1;
       s.bc = gbc;
-      if (s.prev) s.bc.row_lo = LBM_EDGE_HALO;
-      if (s.next) s.bc.row_hi = LBM_EDGE_HALO;
+      if (links.prev(k)) s.bc.row_lo = LBM_EDGE_HALO;
+      if (links.next(k)) s.bc.row_hi = LBM_EDGE_HALO;
       s.sbc = scalar_bc(prof, k * R, s.bc);
       for (int b = 0; b < 2; ++b) {
         s.f[b] = alloc_lattice(g);
         s.h[b] = alloc_lattice(g);
-        check(lbm_event_create(&s.ev[b]), "lbm_event_create");
-        for (int x = 0; x < 2; ++x) check(lbm_malloc((void**)&s.buf[b][x], 2 * msg * 8), "lbm_malloc");
+        links.alloc(k, /*side=*/b, 2 * msg, 2 * msg);
       }
       // owned rows and the ghost rows beside them (wrapping on a closed ring): the exchange would bring the same bits
       for (int r = -1; r <= R; ++r) {
@@ -287,108 +228,80 @@ int run_emulated(const Args& a, int N) {
     check(lbm_stream_sync(nullptr), "sync");
     for (double* p : {f0, h0, fp, hp}) lbm_free(p);
   }
-  lbm_stream_t edge = nullptr;
-  check(lbm_stream_create(&edge), "lbm_stream_create");
-  void *ev_fork = nullptr, *ev_join = nullptr;
-  check(lbm_event_create(&ev_fork), "lbm_event_create");
-  check(lbm_event_create(&ev_join), "lbm_event_create");
+  EdgeStream es;
   SlabSizedBlock block(R, C);
   auto part = [&](Slab& s, int cur, int which, lbm_stream_t st) {
     check(lbm_ade_stream_collide_part_ex(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
                                          prof ? &s.sbc : nullptr, which, E, nullptr, nullptr, nullptr, st),
           "lbm_ade_stream_collide_part_ex");
   };
-  auto pack = [&](Slab& s, double* f, double* h, lbm_stream_t st) {
-    if (s.prev) {
-      check(lbm_halo_pack(s.buf[0][0], f, &g, 1, 0, st), "lbm_halo_pack");
-      check(lbm_halo_pack(s.buf[0][0] + msg, h, &g, 1, 0, st), "lbm_halo_pack");
-    }
-    if (s.next) {
-      check(lbm_halo_pack(s.buf[1][0], f, &g, 1, 1, st), "lbm_halo_pack");
-      check(lbm_halo_pack(s.buf[1][0] + msg, h, &g, 1, 1, st), "lbm_halo_pack");
+  auto pack = [&](int k, double* f, double* h, lbm_stream_t st) {
+    for (int side = 0; side < 2; ++side) {
+      if (!links.has(k, side)) continue;
+      check(lbm_halo_pack(links.send(k, side), f, &g, 1, side, st), "lbm_halo_pack");
+      check(lbm_halo_pack(links.send(k, side) + msg, h, &g, 1, side, st), "lbm_halo_pack");
     }
   };
   int cur = 0;
   for (int i = 0; i < a.warmup + a.steps; ++i) {
     for (int k = 0; k < N; ++k) {
       Slab& s = S[k];
-      check(lbm_event_record(s.ev[0], nullptr), "event");
-      if (s.prev || s.next) {
-        check(lbm_event_record(ev_fork, nullptr), "event");
-        check(lbm_stream_wait_event(edge, ev_fork), "wait");
-        part(s, cur, LBM_ADE_PART_FRAME, edge);
+      links.begin(k);
+      if (links.prev(k) || links.next(k)) {
+        es.fork();
+        part(s, cur, LBM_ADE_PART_FRAME, es.edge);
         part(s, cur, LBM_ADE_PART_INNER, nullptr);
-        pack(s, s.f[cur ^ 1], s.h[cur ^ 1], edge);
-        check(lbm_event_record(ev_join, edge), "event");
-        check(lbm_stream_wait_event(nullptr, ev_join), "wait");
+        pack(k, s.f[cur ^ 1], s.h[cur ^ 1], es.edge);
+        es.join();
       } else {
         part(s, cur, LBM_ADE_PART_FRAME, nullptr);
         part(s, cur, LBM_ADE_PART_INNER, nullptr);
       }
-      check(lbm_event_record(s.ev[1], nullptr), "event");
+      links.end(k);
     }
-    // deliver: slab k's side-1 message is slab k+1's side-0 input and vice versa
-    for (int k = 0; k < N; ++k) {
-      const int n = (k + 1) % N;
-      if (!S[k].next) continue;
-      check(lbm_memcpy_d2d(S[n].buf[0][1], S[k].buf[1][0], 2 * msg * 8, nullptr), "d2d");
-      check(lbm_memcpy_d2d(S[k].buf[1][1], S[n].buf[0][0], 2 * msg * 8, nullptr), "d2d");
-    }
+    links.deliver(2 * msg);  // slab k's side-1 message is slab k+1's side-0 input and vice versa
     for (int k = 0; k < N; ++k) {
       Slab& s = S[k];
       for (int side = 0; side < 2; ++side) {
-        if (!(side ? s.next : s.prev)) continue;
-        check(lbm_halo_unpack(s.f[cur ^ 1], s.buf[side][1], &g, 1, side, nullptr), "lbm_halo_unpack");
-        check(lbm_halo_unpack(s.h[cur ^ 1], s.buf[side][1] + msg, &g, 1, side, nullptr), "lbm_halo_unpack");
+        if (!links.has(k, side)) continue;
+        check(lbm_halo_unpack(s.f[cur ^ 1], links.recv(k, side), &g, 1, side, nullptr), "lbm_halo_unpack");
+        check(lbm_halo_unpack(s.h[cur ^ 1], links.recv(k, side) + msg, &g, 1, side, nullptr), "lbm_halo_unpack");
       }
-      float m = 0;
-      check(lbm_event_elapsed_ms(&m, s.ev[0], s.ev[1]), "elapsed");
-      if (i >= a.warmup) s.ms += m;
+      links.add_elapsed(k, i >= a.warmup);
     }
     block.step(fl, sc, i >= a.warmup);  // alternated with the chain's step
     cur ^= 1;
   }
-  check(lbm_stream_sync(edge), "sync");
+  check(lbm_stream_sync(es.edge), "sync");
   if (prof) lbm_free(prof);
-  lbm_stream_destroy(edge);
-  lbm_event_destroy(ev_fork);
-  lbm_event_destroy(ev_join);
   int bad = 0;
   if (a.check) {
-    std::vector<double> wf, wg, got;
-    one_block(a, Rg, fl, sc, wf, wg);
+    std::vector<double> want[2];
+    one_block(a, Rg, fl, sc, want[0], want[1]);
     for (int k = 0; k < N; ++k)
-      for (int lat = 0; lat < 2; ++lat) {
-        owned_to_host(got, lat ? S[k].h[cur] : S[k].f[cur], g);
-        const std::vector<double>& want = lat ? wg : wf;
-        for (int q = 0; q < 9; ++q)
-          if (std::memcmp(&got[(size_t)q * R * C], &want[(size_t)q * Rg * C + (size_t)k * R * C], (size_t)R * C * 8) != 0) ++bad;
-      }
+      for (int lat = 0; lat < 2; ++lat)
+        bad += mismatching_planes(want[lat], Rg, owned_to_host(lat ? S[k].h[cur] : S[k].f[cur], g), R, k * R, C);
   }
-  double slowest = 0;
-  for (auto& s : S) slowest = std::max(slowest, s.ms / a.steps);
-  const double blk = block.ms / a.steps;
+  const double slowest = links.slowest_ms() / a.steps, blk = block.ms / a.steps;
   std::printf("{\"driver\": \"slab_ring_ade\", \"mode\": \"emulated %s on one GPU\", \"slabs\": %d, \"rows_per_slab\": %d, "
               "\"cols\": %d, \"global_rows\": %d, \"walls\": %d, \"scalar_fixed\": %d, \"form\": \"%s\", \"steps\": %d, "
               "\"edge_rows\": %d, \"message_rows_per_side\": %d, \"slowest_slab_ms_per_step\": %.4f, "
               "\"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, \"per_slab_ms\": [",
               closed ? "closed ring" : "chain", N, R, C, Rg, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, E,
               2 * lbm_halo_rows(1), slowest, blk, blk / slowest);
-  for (int k = 0; k < N; ++k) std::printf("%s%.4f", k ? ", " : "", S[k].ms / a.steps);
-  std::printf("]%s}\n", check_field(a, bad));
+  for (int k = 0; k < N; ++k) std::printf("%s%.4f", k ? ", " : "", links.ms(k) / a.steps);
+  std::printf("]%s}\n", check_field(a.check, bad));
   std::fflush(stdout);
   for (auto& s : S)
     for (int b = 0; b < 2; ++b) {
       lbm_free(s.f[b]);
       lbm_free(s.h[b]);
-      lbm_event_destroy(s.ev[b]);
-      for (int x = 0; x < 2; ++x) lbm_free(s.buf[b][x]);
     }
   return bad ? 3 : 0;
 }
 
 int run_rank(const Args& a, int rank, int world, int local_rank) {
-  check(lbm_set_device(std::getenv("LBM_ONE_GPU") ? 0 : local_rank), "lbm_set_device");
+  check(lbm_set_device(ring_device(local_rank)), "lbm_set_device");
   const int R = a.rows, C = a.cols, Rg = R * world;
   const lbm_bgk_params fl = fluid_params(a);
   const lbm_ade_params sc = scalar_params(a);
@@ -409,32 +322,19 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
                                a.edge_rows, nullptr), "lbm_ring_ade_step_ex");
     cur ^= 1;
   };
-  for (int i = 0; i < a.warmup; ++i) step();
-  check(lbm_stream_sync(nullptr), "sync");
-  auto t0 = std::chrono::steady_clock::now();
-  for (int i = 0; i < a.steps; ++i) step();
-  check(lbm_stream_sync(nullptr), "sync");
-  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (const int failed = ring_failed(ring, "slab_ring_ade", rank)) return failed;
-  const double tmax = max_time_over_ranks(sec, rank, world, a.id_file);
+  double tmax = 0;
+  if (const int failed = timed_ring_run(ring, "slab_ring_ade", a, rank, world, a.warmup, a.steps, step, &tmax)) return failed;
 
   int bad = 0;
   if (a.check) {
-    std::vector<double> own[2];
-    owned_to_host(own[0], f[cur], g);
-    owned_to_host(own[1], h[cur], g);
-    for (int lat = 0; lat < 2; ++lat)
-      write_file_atomic(a.id_file + (lat ? ".g" : ".f") + std::to_string(rank), own[lat].data(), own[lat].size() * 8);
+    publish_owned_rows(a, ".f", rank, f[cur], g);
+    publish_owned_rows(a, ".g", rank, h[cur], g);
     if (rank == 0) {
       std::vector<double> want[2];
       one_block(a, Rg, fl, sc, want[0], want[1]);
       for (int r = 0; r < world; ++r)
-        for (int lat = 0; lat < 2; ++lat) {
-          wait_file(a.id_file + (lat ? ".g" : ".f") + std::to_string(r), own[lat].data(), own[lat].size() * 8);
-          for (int q = 0; q < 9; ++q)
-            if (std::memcmp(&own[lat][(size_t)q * R * C], &want[lat][(size_t)q * Rg * C + (size_t)r * R * C], (size_t)R * C * 8) != 0)
-              ++bad;
-        }
+        for (int lat = 0; lat < 2; ++lat)
+          bad += mismatching_planes(want[lat], Rg, read_owned_rows(a, lat ? ".g" : ".f", r, R, C), R, r * R, C);
     }
   }
   if (rank == 0) {
@@ -447,7 +347,7 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
                 "\"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, "
                 "\"mlups\": %.1f%s}\n",
                 world, R, C, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, a.edge_rows, 2 * lbm_halo_rows(1), ms, blk, blk / ms,
-                (double)Rg * C / (ms * 1e3), check_field(a, bad));
+                (double)Rg * C / (ms * 1e3), check_field(a.check, bad));
     std::fflush(stdout);
   }
   lbm_ring_destroy(ring);
@@ -463,19 +363,15 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
 
 int main(int argc, char** argv) {
   Args a;
-  a.rows = std::atoi(arg_value(argc, argv, "--rows", "512").c_str());
-  a.cols = std::atoi(arg_value(argc, argv, "--cols", "1024").c_str());
-  a.steps = std::max(1, std::atoi(arg_value(argc, argv, "--steps", "50").c_str()));
-  a.warmup = std::max(0, std::atoi(arg_value(argc, argv, "--warmup", "5").c_str()));
-  a.edge_rows = std::atoi(arg_value(argc, argv, "--edge-rows", "16").c_str());
-  a.check = std::atoi(arg_value(argc, argv, "--check", "0").c_str());
-  a.walls = std::atoi(arg_value(argc, argv, "--walls", "0").c_str());
-  a.scalar_fixed = std::atoi(arg_value(argc, argv, "--scalar-fixed", "0").c_str());
+  parse_ring_opts(a, argc, argv, /*rows=*/512, /*cols=*/1024, /*steps=*/50, /*warmup=*/5, /*edge_rows=*/16);
+  a.steps = std::max(1, a.steps);
+  a.warmup = std::max(0, a.warmup);
+  a.walls = int_arg(argc, argv, "--walls", 0);
+  a.scalar_fixed = int_arg(argc, argv, "--scalar-fixed", 0);
   if (a.scalar_fixed && !a.walls) {
     std::fprintf(stderr, "--scalar-fixed 1 needs --walls 1 (fixed-concentration walls sit on walls of the fluid)\n");
     return 1;
   }
-  a.emulate = std::atoi(arg_value(argc, argv, "--emulate", "0").c_str());
   a.omega = std::atof(arg_value(argc, argv, "--omega", "1.2").c_str());
   a.omega_g = std::atof(arg_value(argc, argv, "--omega-g", "1.7").c_str());
   const std::string form = arg_value(argc, argv, "--form", "fast");
@@ -484,26 +380,5 @@ int main(int argc, char** argv) {
     return 2;
   }
   a.fast = form == "fast";
-  const std::string transport = arg_value(argc, argv, "--transport", "");
-  if (!transport.empty()) setenv("LBM_RING_TRANSPORT", transport.c_str(), 1);  // lbm_ring_unique_id / lbm_ring_create follow it
-  if (std::atoi(arg_value(argc, argv, "--one-gpu", "0").c_str())) setenv("LBM_ONE_GPU", "1", 1);
-  a.id_file = arg_value(argc, argv, "--id-file", "/tmp/lbm_ring_id." + std::to_string((long)getpid()));
-  const int spawn = std::atoi(arg_value(argc, argv, "--spawn", "0").c_str());
-  try {
-    if (a.emulate > 0) return run_emulated(a, a.emulate);
-    if (spawn > 0) {
-      cleanup_ring_files(a.id_file, spawn);  // a stale id file of a killed run must not be picked up
-      const int rc = spawn_ranks(spawn, [&](int r) { return run_rank(a, r, spawn, r); });
-      cleanup_ring_files(a.id_file, spawn);
-      return rc;
-    }
-    const char* er = std::getenv("RANK");
-    const char* ew = std::getenv("WORLD_SIZE");
-    const char* el = std::getenv("LOCAL_RANK");
-    const int rank = er ? std::atoi(er) : 0, world = ew ? std::atoi(ew) : 1;
-    return run_rank(a, rank, world, el ? std::atoi(el) : rank);
-  } catch (const std::exception& e) {
-    std::fprintf(stderr, "slab_ring_ade: %s\n", e.what());
-    return 1;
-  }
+  return ring_main("slab_ring_ade", a, run_rank, run_emulated);
 }

@@ -14,21 +14,11 @@
 //
 // The block binding this generalises: test/decompose_domain.cpp:181-187 (3 populations per
 // interface row, one row per step); here 9(D-1) rows per side per D-step launch (3 for D = 1).
-#include <sys/wait.h>
-#include <unistd.h>
-
-#include <chrono>
+//
+// The calls that make a host are all in run_rank, in order; what surrounds them (options, main(), the timed run,
+// --check's files and comparison) is ring_common.hpp.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "../../include/lbm_hip.h"
-#include "common.hpp"
 #include "ring_common.hpp"
 
 namespace {
@@ -41,26 +31,19 @@ void init_node(double* f9, int gr, int c, int Rg, int C) {
   const double x = 2 * pi * gr / Rg, y = 2 * pi * c / C;
   const double u0 = 0.04 * std::sin(x) * std::cos(y), u1 = -0.04 * std::cos(x) * std::sin(y);
   const double rho = 1.0 + 0.01 * std::cos(2 * x);
-  static const double w[9] = {4. / 9, 1. / 9, 1. / 9, 1. / 9, 1. / 9, 1. / 36, 1. / 36, 1. / 36, 1. / 36};
-  static const int cx[9] = {0, 1, 0, -1, 0, 1, -1, -1, 1}, cy[9] = {0, 0, 1, 0, -1, 1, 1, -1, -1};
-  const double uu = u0 * u0 + u1 * u1;
-  for (int q = 0; q < 9; ++q) {
-    const double cu = cx[q] * u0 + cy[q] * u1;
-    f9[q] = w[q] * rho * (1.0 + 3.0 * cu + 4.5 * cu * cu - 1.5 * uu);
-  }
+  d2q9_equilibrium(f9, rho, u0, u1);
 }
 
-struct Args {
-  int rows = 8192, cols = 8192, steps = 20, warmup = 5, depth = 5, period = 2, edge_rows = 32, check = 0, desert = -1;
+struct Args : RingOpts {
+  int depth = 5, period = 2, desert = -1;
   double omega = 1.2;
   bool kbc = false;
-  std::string id_file;
 };
 
 // post-collision slab lattice [9][R+2D][C] of rows [row0, row0+R) of an Rg x C box
 double* make_slab(const Args& a, int R, int row0, int Rg, const lbm_geom& g, const lbm_bgk_params& prm) {
   const int C = a.cols, D = g.ghost;
-  const size_t plane = (size_t)(R + 2 * D) * C;
+  const size_t plane = plane_doubles(g);
   std::vector<double> h(9 * plane, 0.0);
   double f9[9];
   for (int r = 0; r < R; ++r)
@@ -68,11 +51,10 @@ double* make_slab(const Args& a, int R, int row0, int Rg, const lbm_geom& g, con
       init_node(f9, row0 + r, c, Rg, C);
       for (int q = 0; q < 9; ++q) h[q * plane + (size_t)(r + D) * C + c] = f9[q];
     }
-  double *pre = nullptr, *post = nullptr;
+  double* pre = nullptr;
   check(lbm_malloc((void**)&pre, 9 * plane * sizeof(double)), "lbm_malloc");
-  check(lbm_malloc((void**)&post, 9 * plane * sizeof(double)), "lbm_malloc");
+  double* post = alloc_lattice(g);
   check(lbm_memcpy_h2d(pre, h.data(), 9 * plane * sizeof(double), nullptr), "h2d");
-  check(lbm_memset(post, 0, 9 * plane * sizeof(double), nullptr), "memset");
   // the collide-only launch that opens the post-collision-resident loop (ghost rows: collide of
   // zeros stays in the ghost rows and is overwritten by the first exchange)
   if (a.kbc) {
@@ -87,7 +69,7 @@ double* make_slab(const Args& a, int R, int row0, int Rg, const lbm_geom& g, con
 }
 
 int run_rank(const Args& a, int rank, int world, int local_rank) {
-  check(lbm_set_device(std::getenv("LBM_ONE_GPU") ? 0 : local_rank), "lbm_set_device");
+  check(lbm_set_device(ring_device(local_rank)), "lbm_set_device");
   const int R = a.rows, C = a.cols, D = a.depth, Rg = R * world;
   // ghost = period x D rows: lbm_ring_bgk_step / _kbc_step exchange once per `period` launches
   const int G = D * (D < 2 ? 1 : a.period);
@@ -97,12 +79,7 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   lbm_kbc_params kprm{a.omega, LBM_FORM_DEFAULT};
 
   unsigned char id[128];
-  if (rank == 0) {
-    check(lbm_ring_unique_id(id), "lbm_ring_unique_id");
-    if (world > 1) write_file_atomic(a.id_file, id, sizeof id);
-  } else {
-    wait_file(a.id_file, id, sizeof id);
-  }
+  share_unique_id(id, rank, world, a.id_file);
   lbm_ring* ring = nullptr;
   check(lbm_ring_create(&ring, id, rank, world, &g, /*periodic=*/1), "lbm_ring_create");
   if (rank == a.desert) {  // joined, mapped, gone
@@ -110,11 +87,9 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
     _exit(0);
   }
 
-  const size_t plane = (size_t)(R + 2 * G) * C;
   double* lat[2];
   lat[0] = make_slab(a, R, rank * R, Rg, g, prm);
-  check(lbm_malloc((void**)&lat[1], 9 * plane * sizeof(double)), "lbm_malloc");
-  check(lbm_memset(lat[1], 0, 9 * plane * sizeof(double), nullptr), "memset");
+  lat[1] = alloc_lattice(g);
   check(lbm_ring_exchange(ring, lat[0], nullptr), "lbm_ring_exchange");
   check(lbm_ring_join(ring, nullptr), "lbm_ring_join");
 
@@ -124,61 +99,28 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
     else check(lbm_ring_bgk_step(ring, lat[cur ^ 1], lat[cur], nullptr, &prm, D, a.edge_rows, nullptr), "lbm_ring_bgk_step");
     cur ^= 1;
   };
-  for (int i = 0; i < a.warmup; ++i) launch();
-  check(lbm_stream_sync(nullptr), "sync");
-  // (each rank starts its clock after its own warm-up; the neighbour exchanges keep ranks in step)
-  auto t0 = std::chrono::steady_clock::now();
-  for (int i = 0; i < a.steps; ++i) launch();
-  check(lbm_stream_sync(nullptr), "sync");
-  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (const int failed = ring_failed(ring, "slab_ring_box", rank)) return failed;
-
-  // gather the per-rank times through files (no MPI here); value = all nodes / slowest rank
-  double tmax = sec;
-  if (world > 1) {
-    write_file_atomic(a.id_file + ".t" + std::to_string(rank), &sec, sizeof sec);
-    if (rank == 0)
-      for (int r = 1; r < world; ++r) {
-        double t;
-        wait_file(a.id_file + ".t" + std::to_string(r), &t, sizeof t);
-        tmax = std::max(tmax, t);
-      }
-  }
+  // the rate: all nodes / the slowest rank's time (gathered through files: no MPI here)
+  double tmax = 0;
+  if (const int failed = timed_ring_run(ring, "slab_ring_box", a, rank, world, a.warmup, a.steps, launch, &tmax)) return failed;
 
   int bad = 0;
   if (a.check) {
     // every rank dumps its owned rows; rank 0 recomputes the whole box on its own GPU (ghost 0,
     // periodic wrap inside the block) and compares bit for bit
-    std::vector<double> h(9 * plane);
-    check(lbm_memcpy_d2h(h.data(), lat[cur], h.size() * sizeof(double), nullptr), "d2h");
-    check(lbm_stream_sync(nullptr), "sync");
-    std::vector<double> own((size_t)9 * R * C);
-    for (int q = 0; q < 9; ++q)
-      std::memcpy(&own[(size_t)q * R * C], &h[q * plane + (size_t)G * C], (size_t)R * C * sizeof(double));
-    write_file_atomic(a.id_file + ".f" + std::to_string(rank), own.data(), own.size() * sizeof(double));
+    publish_owned_rows(a, ".f", rank, lat[cur], g);
     if (rank == 0) {
-      Args whole = a;
       lbm_geom gw{Rg, C, 0, 0, 0};
-      double* p = make_slab(whole, Rg, 0, Rg, gw, prm);
+      double* p = make_slab(a, Rg, 0, Rg, gw, prm);
       double* q2 = nullptr;
-      const size_t n = (size_t)9 * Rg * C;
-      check(lbm_malloc((void**)&q2, n * sizeof(double)), "lbm_malloc");
+      check(lbm_malloc((void**)&q2, plane_doubles(gw) * 9 * sizeof(double)), "lbm_malloc");
       const int total = (a.warmup + a.steps) * D;
       for (int t = 0; t < total; ++t) {
         if (a.kbc) check(lbm_kbc_stream_collide(q2, p, &gw, nullptr, &kprm, 0, Rg, nullptr, nullptr, nullptr), "ref step");
         else check(lbm_bgk_stream_collide(q2, p, &gw, nullptr, &prm, 0, Rg, nullptr, nullptr, nullptr), "ref step");
         std::swap(p, q2);
       }
-      std::vector<double> want(n);
-      check(lbm_memcpy_d2h(want.data(), p, n * sizeof(double), nullptr), "d2h");
-      check(lbm_stream_sync(nullptr), "sync");
-      for (int r = 0; r < world; ++r) {
-        wait_file(a.id_file + ".f" + std::to_string(r), own.data(), own.size() * sizeof(double));
-        for (int q = 0; q < 9; ++q)
-          if (std::memcmp(&own[(size_t)q * R * C], &want[(size_t)q * Rg * C + (size_t)r * R * C],
-                          (size_t)R * C * sizeof(double)) != 0)
-            ++bad;
-      }
+      const std::vector<double> want = owned_to_host(p, gw);
+      for (int r = 0; r < world; ++r) bad += mismatching_planes(want, Rg, read_owned_rows(a, ".f", r, R, C), R, r * R, C);
       lbm_free(p);
       lbm_free(q2);
     }
@@ -190,7 +132,7 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
                 "\"depth\": %d, \"ghost_rows\": %d, \"launches\": %d, \"ms_per_launch\": %.4f, \"mlups\": %.1f, "
                 "\"transport\": \"rccl send/recv (C++ ring)\"%s}\n",
                 a.kbc ? "kbc" : "bgk", world, R, C, D, G, a.steps, 1e3 * tmax / a.steps, lups / 1e6,
-                a.check ? (bad ? ", \"check\": \"MISMATCH\"" : ", \"check\": \"bitwise equal to one block\"") : "");
+                check_field(a.check, bad));
     std::fflush(stdout);
   }
   lbm_ring_destroy(ring);
@@ -203,39 +145,12 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
 
 int main(int argc, char** argv) {
   Args a;
-  a.rows = std::atoi(arg_value(argc, argv, "--rows", "8192").c_str());
-  a.cols = std::atoi(arg_value(argc, argv, "--cols", "8192").c_str());
-  a.steps = std::atoi(arg_value(argc, argv, "--steps", "20").c_str());
-  a.warmup = std::atoi(arg_value(argc, argv, "--warmup", "5").c_str());
-  a.depth = std::atoi(arg_value(argc, argv, "--depth", "5").c_str());
-  a.period = std::max(1, std::min(3, std::atoi(arg_value(argc, argv, "--period", "2").c_str())));
-  a.edge_rows = std::atoi(arg_value(argc, argv, "--edge-rows", "32").c_str());
-  a.check = std::atoi(arg_value(argc, argv, "--check", "0").c_str());
-  a.desert = std::atoi(arg_value(argc, argv, "--desert", "-1").c_str());
+  parse_ring_opts(a, argc, argv, /*rows=*/8192, /*cols=*/8192, /*steps=*/20, /*warmup=*/5, /*edge_rows=*/32);
+  a.depth = int_arg(argc, argv, "--depth", 5);
+  a.period = std::max(1, std::min(3, int_arg(argc, argv, "--period", 2)));
+  a.desert = int_arg(argc, argv, "--desert", -1);
   a.omega = std::atof(arg_value(argc, argv, "--omega", "1.2").c_str());
   a.kbc = arg_value(argc, argv, "--model", "bgk") == "kbc";
   if (a.kbc && a.depth > 4) a.depth = 3;
-  a.id_file = arg_value(argc, argv, "--id-file", "/tmp/lbm_ring_id." + std::to_string((long)getpid()));
-  const int spawn = std::atoi(arg_value(argc, argv, "--spawn", "0").c_str());
-  // --transport rccl|ipc: what carries the ring's messages (lbm_ring_unique_id / lbm_ring_create follow the environment);
-  // --one-gpu 1: every rank on GPU 0 (with ipc: N real ranks on one device, which RCCL refuses)
-  const std::string transport = arg_value(argc, argv, "--transport", "");
-  if (!transport.empty()) setenv("LBM_RING_TRANSPORT", transport.c_str(), 1);
-  if (std::atoi(arg_value(argc, argv, "--one-gpu", "0").c_str())) setenv("LBM_ONE_GPU", "1", 1);
-  try {
-    if (spawn > 0) {
-      cleanup_ring_files(a.id_file, spawn);  // a stale id file of a killed run must not be picked up
-      const int rc = spawn_ranks(spawn, [&](int r) { return run_rank(a, r, spawn, r); });
-      cleanup_ring_files(a.id_file, spawn);
-      return rc;
-    }
-    const char* er = std::getenv("RANK");
-    const char* ew = std::getenv("WORLD_SIZE");
-    const char* el = std::getenv("LOCAL_RANK");
-    const int rank = er ? std::atoi(er) : 0, world = ew ? std::atoi(ew) : 1;
-    return run_rank(a, rank, world, el ? std::atoi(el) : rank);
-  } catch (const std::exception& e) {
-    std::fprintf(stderr, "slab_ring_box: %s\n", e.what());
-    return 1;
-  }
+  return ring_main("slab_ring_box", a, run_rank);  // (no emulation: --emulate is not a flag of this driver)
 }
