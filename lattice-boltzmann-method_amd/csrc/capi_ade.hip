@@ -89,6 +89,27 @@ static bool ade_fast(const lbm_ade_params* scalar) {
   return scalar->form == LBM_FORM_DEFAULT ? tuning("bgk_fast", 1) != 0 : scalar->form == LBM_FORM_REASSOCIATED;
 }
 
+// f(fluid model, scalar model): the reassociated pair or the reference-order pair
+template <class F>
+static int with_ade_models(const lbm_bgk_params* fluid, const lbm_ade_params* scalar, F f) {
+  if (ade_fast(scalar)) return f(BgkFastModel(fluid->omega), AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c));
+  return f(BgkModelT<0, 0>{fluid->omega}, AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c});
+}
+
+// The lattice and field arguments of a launch: four lattices given (distinct: also pairwise different and 16-byte
+// aligned -- the collide-only launch reads and writes node by node and asks for neither); rho, u, conc all or none.
+static int ade_lattice_args(const char* fn, const double* fn_, const double* gn, const double* fo, const double* go,
+                            const double* rho, const double* u, const double* conc, bool distinct) {
+  LBM_REQUIRE(fn_ && gn && fo && go, "%s: NULL lattice", fn);
+  if (distinct) {
+    LBM_REQUIRE(fn_ != fo && fn_ != go && gn != fo && gn != go && fn_ != gn && fo != go, "%s: aliased lattices", fn);
+    LBM_REQUIRE(aligned16(fn_) && aligned16(gn) && aligned16(fo) && aligned16(go), "%s: lattices must be 16-byte aligned", fn);
+  }
+  LBM_REQUIRE((rho == nullptr) == (u == nullptr) && (rho == nullptr) == (conc == nullptr),
+              "%s: rho, u and conc must all be given or all be NULL", fn);
+  return LBM_OK;
+}
+
 static const char* const kEdge[4] = {"row_lo", "row_hi", "col_lo", "col_hi"};
 
 // The scalar's walls (lbm_ade_scalar_bc) against the edges `bc` the launch runs with, on the host: a FIXED edge must be a
@@ -121,8 +142,7 @@ static int ade_collide_launch(double* fp, double* gp, const double* f, const dou
                               const SM& sm, double* rho, double* u, double* conc, hipStream_t st) {
   const long n = (long)g.R * g.C;
   const int grid = capped_grid((n + 255) / 256);
-  if (rho) LBM_KLAUNCH((k_ade_collide<FM, SM, true>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, g, fm, sm, rho, u, conc);
-  else LBM_KLAUNCH((k_ade_collide<FM, SM, false>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, g, fm, sm, rho, u, conc);
+  with_flags([&](auto M) { LBM_KLAUNCH((k_ade_collide<FM, SM, M()>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, g, fm, sm, rho, u, conc); }, rho != nullptr);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
@@ -138,34 +158,19 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
   const int tiles = (g.C + 511) / 512;
   const long items = (long)(row_end - row_begin) * tiles;
   const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
-  switch ((nt & 3) | (mom ? 4 : 0)) {
-#define LBM_ADE_K(NL, NS, M)                                                                                       \
-  LBM_KLAUNCH((k_ade_stream_collide<FM, SM, NL, NS, M>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, fm, sm, \
-              row_begin, row_end, tiles, rho, u, conc)
-    case 0: LBM_ADE_K(false, false, false); break;
-    case 1: LBM_ADE_K(true, false, false); break;
-    case 2: LBM_ADE_K(false, true, false); break;
-    case 3: LBM_ADE_K(true, true, false); break;
-    case 4: LBM_ADE_K(false, false, true); break;
-    case 5: LBM_ADE_K(true, false, true); break;
-    case 6: LBM_ADE_K(false, true, true); break;
-    default: LBM_ADE_K(true, true, true); break;
-#undef LBM_ADE_K
-  }
+  with_flags([&](auto NL, auto NS, auto M) {
+    LBM_KLAUNCH((k_ade_stream_collide<FM, SM, NL(), NS(), M()>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, fm, sm,
+                row_begin, row_end, tiles, rho, u, conc);
+  }, nt & 1, nt & 2, mom);
   LBM_CHECK_LAUNCH();
   ++*launches;
   if (bc_needs_edge_pass(bc)) {
     const int n_edge = 2 * g.C + 2 * (row_end - row_begin);
     const dim3 grid_e((n_edge + 255) / 256);
-    switch ((sw.fixed ? 2 : 0) | (mom ? 1 : 0)) {
-#define LBM_ADE_E(M, F) \
-  LBM_KLAUNCH((k_ade_edge<FM, SM, M, F>), grid_e, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin, row_end, rho, u, conc, sw)
-      case 0: LBM_ADE_E(false, false); break;
-      case 1: LBM_ADE_E(true, false); break;
-      case 2: LBM_ADE_E(false, true); break;
-      default: LBM_ADE_E(true, true); break;
-#undef LBM_ADE_E
-    }
+    with_flags([&](auto M, auto F) {
+      LBM_KLAUNCH((k_ade_edge<FM, SM, M(), F()>), grid_e, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin,
+                  row_end, rho, u, conc, sw);
+    }, mom, sw.fixed);
     LBM_CHECK_LAUNCH();
     ++*launches;
   }
@@ -183,28 +188,10 @@ static int ade_part_launch(double* fn, double* gn, const double* fo, const doubl
   const int tiles = (g.C + 511) / 512;
   const long items = (long)nrows * tiles;
   const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
-  switch ((nt & 3) | (mom ? 4 : 0) | (sw.fixed ? 8 : 0)) {
-#define LBM_ADE_P(NL, NS, M, F)                                                                                            \
-  LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL, NS, M, F>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, \
-              sm, band0, n0, band1, nrows, tiles, rho, u, conc, sw)
-    case 0: LBM_ADE_P(false, false, false, false); break;
-    case 1: LBM_ADE_P(true, false, false, false); break;
-    case 2: LBM_ADE_P(false, true, false, false); break;
-    case 3: LBM_ADE_P(true, true, false, false); break;
-    case 4: LBM_ADE_P(false, false, true, false); break;
-    case 5: LBM_ADE_P(true, false, true, false); break;
-    case 6: LBM_ADE_P(false, true, true, false); break;
-    case 7: LBM_ADE_P(true, true, true, false); break;
-    case 8: LBM_ADE_P(false, false, false, true); break;
-    case 9: LBM_ADE_P(true, false, false, true); break;
-    case 10: LBM_ADE_P(false, true, false, true); break;
-    case 11: LBM_ADE_P(true, true, false, true); break;
-    case 12: LBM_ADE_P(false, false, true, true); break;
-    case 13: LBM_ADE_P(true, false, true, true); break;
-    case 14: LBM_ADE_P(false, true, true, true); break;
-    default: LBM_ADE_P(true, true, true, true); break;
-#undef LBM_ADE_P
-  }
+  with_flags([&](auto NL, auto NS, auto M, auto F) {
+    LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL(), NS(), M(), F()>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g,
+                bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, sw);
+  }, nt & 1, nt & 2, mom, sw.fixed);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
@@ -213,16 +200,12 @@ static int ade_collide(const char* fn, double* fp, double* gp, const double* f, 
                        const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, double* rho,
                        double* u, double* conc, hipStream_t st, bool slab = false) {
   int rc = ade_validate(fn, lg, bc, fluid, scalar, slab);
+  if (!rc) rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false);
   if (rc) return rc;
-  LBM_REQUIRE(fp && gp && f && h, "%s: NULL lattice", fn);
-  LBM_REQUIRE((rho == nullptr) == (u == nullptr) && (rho == nullptr) == (conc == nullptr),
-              "%s: rho, u and conc must all be given or all be NULL", fn);
   const Geom g = make_geom(*lg);
-  if (ade_fast(scalar))
-    return ade_collide_launch(fp, gp, f, h, g, BgkFastModel(fluid->omega), AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c),
-                              rho, u, conc, st);
-  return ade_collide_launch(fp, gp, f, h, g, BgkModelT<0, 0>{fluid->omega}, AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c},
-                            rho, u, conc, st);
+  return with_ade_models(fluid, scalar, [&](const auto& fm, const auto& sm) {
+    return ade_collide_launch(fp, gp, f, h, g, fm, sm, rho, u, conc, st);
+  });
 }
 
 static int ade_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
@@ -232,36 +215,24 @@ static int ade_stream_collide(const char* fn, double* fn_, double* gn, const dou
   AdeWalls sw;  // the scalar's walls first: a FIXED edge names the edge mode it cannot sit on
   int rc = ade_scalar_bc_check(fn, sbc, lbc, &sw);
   if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar);
+  if (!rc) rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true);
   if (rc) return rc;
-  LBM_REQUIRE(fn_ && gn && fo && go, "%s: NULL lattice", fn);
-  LBM_REQUIRE(fn_ != fo && fn_ != go && gn != fo && gn != go && fn_ != gn && fo != go, "%s: aliased lattices", fn);
-  LBM_REQUIRE(aligned16(fn_) && aligned16(gn) && aligned16(fo) && aligned16(go), "%s: lattices must be 16-byte aligned", fn);
-  LBM_REQUIRE((rho == nullptr) == (u == nullptr) && (rho == nullptr) == (conc == nullptr),
-              "%s: rho, u and conc must all be given or all be NULL", fn);
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R, "%s: row range [%d, %d) outside [0, %d)", fn,
               row_begin, row_end, lg->R);
   if (row_begin == row_end) return LBM_OK;
   const Geom g = make_geom(*lg);
   const Bc bc = make_bc(lbc);
-  if (ade_fast(scalar))
-    return ade_step_launch(fn_, gn, fo, go, g, bc, BgkFastModel(fluid->omega),
-                           AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c), sw, row_begin, row_end, rho, u, conc,
-                           st, launches);
-  return ade_step_launch(fn_, gn, fo, go, g, bc, BgkModelT<0, 0>{fluid->omega},
-                         AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, sw, row_begin, row_end, rho, u, conc, st,
-                         launches);
+  return with_ade_models(fluid, scalar, [&](const auto& fm, const auto& sm) {
+    return ade_step_launch(fn_, gn, fo, go, g, bc, fm, sm, sw, row_begin, row_end, rho, u, conc, st, launches);
+  });
 }
 
 int ade_part_check(const char* name, const double* fn, const double* gn, const double* fo, const double* go,
                    const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                    int part, int edge_rows, const double* rho, const double* u, const double* conc) {
   int rc = ade_validate(name, lg, lbc, fluid, scalar, true);
+  if (!rc) rc = ade_lattice_args(name, fn, gn, fo, go, rho, u, conc, true);
   if (rc) return rc;
-  LBM_REQUIRE(fn && gn && fo && go, "%s: NULL lattice", name);
-  LBM_REQUIRE(fn != fo && fn != go && gn != fo && gn != go && fn != gn && fo != go, "%s: aliased lattices", name);
-  LBM_REQUIRE(aligned16(fn) && aligned16(gn) && aligned16(fo) && aligned16(go), "%s: lattices must be 16-byte aligned", name);
-  LBM_REQUIRE((rho == nullptr) == (u == nullptr) && (rho == nullptr) == (conc == nullptr),
-              "%s: rho, u and conc must all be given or all be NULL", name);
   LBM_REQUIRE(part == LBM_ADE_PART_FRAME || part == LBM_ADE_PART_INNER,
               "%s: part=%d (LBM_ADE_PART_FRAME or LBM_ADE_PART_INNER)", name, part);
   LBM_REQUIRE(edge_rows >= 1 && 2 * edge_rows < lg->R, "%s: edge_rows=%d: need 1 <= edge_rows and 2 x edge_rows < R=%d",
@@ -290,13 +261,9 @@ static int ade_part(const char* name, double* fn, double* gn, const double* fo, 
   const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;
   const int n0 = part == LBM_ADE_PART_FRAME ? edge_rows : R - 2 * edge_rows;
   const int band1 = R - edge_rows, nrows = part == LBM_ADE_PART_FRAME ? 2 * edge_rows : n0;
-  if (ade_fast(scalar))
-    return ade_part_launch(fn, gn, fo, go, g, bc, BgkFastModel(fluid->omega),
-                           AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c), sw, band0, n0, band1, nrows, rho, u,
-                           conc, st);
-  return ade_part_launch(fn, gn, fo, go, g, bc, BgkModelT<0, 0>{fluid->omega},
-                         AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, sw, band0, n0, band1, nrows, rho, u, conc,
-                         st);
+  return with_ade_models(fluid, scalar, [&](const auto& fm, const auto& sm) {
+    return ade_part_launch(fn, gn, fo, go, g, bc, fm, sm, sw, band0, n0, band1, nrows, rho, u, conc, st);
+  });
 }
 
 int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,

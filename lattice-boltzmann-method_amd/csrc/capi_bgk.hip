@@ -50,8 +50,7 @@ __global__ __launch_bounds__(256) void k_stream_only(double* __restrict__ f,
 static int launch_pressure_rows(bool from_post, double* pn, const double* in, const Geom& g,
                                 const Bc& bc, const BgkModel& m, hipStream_t st) {
   const int n = 2 * g.C;
-  if (from_post) LBM_KLAUNCH(k_bgk_pressure_rows<true>, dim3((n + 255) / 256), dim3(256), 0, st, pn, in, g, bc, m);
-  else LBM_KLAUNCH(k_bgk_pressure_rows<false>, dim3((n + 255) / 256), dim3(256), 0, st, pn, in, g, bc, m);
+  with_flags([&](auto POST) { LBM_KLAUNCH(k_bgk_pressure_rows<POST()>, dim3((n + 255) / 256), dim3(256), 0, st, pn, in, g, bc, m); }, from_post);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
@@ -72,6 +71,18 @@ static bool use_fast_bgk(const lbm_bgk_params* prm, const lbm_bc* bc) {
   return wanted && !prm->force_mode && !prm->incompressible && !(bc && bc->pressure_rows);
 }
 
+// the run-time-mode model: every parameter a field
+static BgkModel bgk_model(const lbm_bgk_params* prm) {
+  return BgkModel{prm->omega, prm->incompressible, prm->delta_form, prm->force_mode, prm->force_r, prm->force_c, prm->guo_a, prm->guo_b};
+}
+
+// f(model) with the model the one- and two-step entry points run: reassociated where use_fast_bgk allows it, else run-time-mode
+template <class F>
+static int with_bgk_model(const lbm_bgk_params* prm, const lbm_bc* bc, F f) {
+  if (use_fast_bgk(prm, bc)) return f(BgkFastModel(prm->omega));
+  return f(bgk_model(prm));
+}
+
 static int check_bgk(const char* fn, const lbm_bgk_params* prm) {
   LBM_REQUIRE(prm, "%s: NULL params", fn);
   LBM_REQUIRE(prm->omega > 0.0 && prm->omega < 2.0, "%s: omega=%g outside (0, 2)", fn, prm->omega);
@@ -90,15 +101,12 @@ int lbm_bgk_collide(double* p, const double* f, const lbm_geom* g, const lbm_bc*
                     const lbm_bgk_params* prm, double* rho, double* u, lbm_stream_t s) {
   int rc = check_bgk("lbm_bgk_collide", prm);
   if (rc) return rc;
-  if (use_fast_bgk(prm, bc))
-    return launch_collide_only("lbm_bgk_collide", p, f, g, bc, BgkFastModel(prm->omega), rho, u, as_stream(s));
-  const BgkModel m{prm->omega, prm->incompressible, prm->delta_form, prm->force_mode, prm->force_r, prm->force_c, prm->guo_a, prm->guo_b};
-  rc = launch_collide_only("lbm_bgk_collide", p, f, g, bc, m, rho, u, as_stream(s));
+  rc = with_bgk_model(prm, bc, [&](const auto& m) { return launch_collide_only("lbm_bgk_collide", p, f, g, bc, m, rho, u, as_stream(s)); });
   if (rc) return rc;
-  if (bc && bc->pressure_rows) {
+  if (bc && bc->pressure_rows) {  // (never with the reassociated model: use_fast_bgk)
     LBM_REQUIRE(p != f, "lbm_bgk_collide: pressure rows need distinct in/out lattices");
     LBM_REQUIRE(g->ghost == 0, "lbm_bgk_collide: pressure rows are single-block only");
-    return launch_pressure_rows(false, p, f, make_geom(*g), make_bc(bc), m, as_stream(s));
+    return launch_pressure_rows(false, p, f, make_geom(*g), make_bc(bc), bgk_model(prm), as_stream(s));
   }
   return LBM_OK;
 }
@@ -108,17 +116,14 @@ int lbm_bgk_stream_collide(double* p_new, const double* p_old, const lbm_geom* g
                            int row_end, double* rho, double* u, lbm_stream_t s) {
   int rc = check_bgk("lbm_bgk_stream_collide", prm);
   if (rc) return rc;
-  if (use_fast_bgk(prm, bc))
-    return launch_stream_collide("lbm_bgk_stream_collide", p_new, p_old, g, bc, BgkFastModel(prm->omega),
-                                 row_begin, row_end, rho, u, as_stream(s));
-  const BgkModel m{prm->omega, prm->incompressible, prm->delta_form, prm->force_mode, prm->force_r, prm->force_c, prm->guo_a, prm->guo_b};
-  rc = launch_stream_collide("lbm_bgk_stream_collide", p_new, p_old, g, bc, m, row_begin, row_end,
-                             rho, u, as_stream(s));
+  rc = with_bgk_model(prm, bc, [&](const auto& m) {
+    return launch_stream_collide("lbm_bgk_stream_collide", p_new, p_old, g, bc, m, row_begin, row_end, rho, u, as_stream(s));
+  });
   if (rc) return rc;
   if (bc && bc->pressure_rows) {
     LBM_REQUIRE(g->ghost == 0 && row_begin == 0 && row_end == g->R,
                 "lbm_bgk_stream_collide: pressure rows need the whole single block");
-    return launch_pressure_rows(true, p_new, p_old, make_geom(*g), make_bc(bc), m, as_stream(s));
+    return launch_pressure_rows(true, p_new, p_old, make_geom(*g), make_bc(bc), bgk_model(prm), as_stream(s));
   }
   return LBM_OK;
 }
@@ -128,12 +133,9 @@ int lbm_bgk_stream_collide_x2(double* p_new, const double* p_old, const lbm_geom
                               int row_end, lbm_stream_t s) {
   int rc = check_bgk("lbm_bgk_stream_collide_x2", prm);
   if (rc) return rc;
-  if (use_fast_bgk(prm, bc))
-    return launch_stream_collide_x2("lbm_bgk_stream_collide_x2", p_new, p_old, g, bc, BgkFastModel(prm->omega),
-                                    row_begin, row_end, as_stream(s));
-  const BgkModel m{prm->omega, prm->incompressible, prm->delta_form, prm->force_mode, prm->force_r, prm->force_c, prm->guo_a, prm->guo_b};
-  return launch_stream_collide_x2("lbm_bgk_stream_collide_x2", p_new, p_old, g, bc, m, row_begin,
-                                  row_end, as_stream(s));
+  return with_bgk_model(prm, bc, [&](const auto& m) {
+    return launch_stream_collide_x2("lbm_bgk_stream_collide_x2", p_new, p_old, g, bc, m, row_begin, row_end, as_stream(s));
+  });
 }
 
 static int bgk_xn(const char* fn, double* p_new, const double* p_old, const lbm_geom* g, const lbm_bc* bc,
@@ -142,19 +144,14 @@ static int bgk_xn(const char* fn, double* p_new, const double* p_old, const lbm_
   int rc = check_bgk(fn, prm);
   if (rc) return rc;
   if (!prm->force_mode) {  // compile-time model: no mode branches inside the unrolled window
-    const int key = (prm->incompressible ? 2 : 0) | (prm->delta_form ? 1 : 0);
     if (allow_fast && use_fast_bgk(prm, bc))  // leaner collision: best at one 2-wave block per SIMD pair (146.6 k vs 137 k MLUPS)
       return launch_stream_collide_sw(fn, p_new, p_old, g, bc, BgkFastModel(prm->omega), n_steps, row_begin, row_end, as_stream(s), 2, second_begin);
-    switch (key) {
-      case 0: return launch_stream_collide_sw(fn, p_new, p_old, g, bc, BgkModelT<0, 0>{prm->omega}, n_steps, row_begin, row_end, as_stream(s), 4, second_begin);
-      case 1: return launch_stream_collide_sw(fn, p_new, p_old, g, bc, BgkModelT<0, 1>{prm->omega}, n_steps, row_begin, row_end, as_stream(s), 4, second_begin);
-      case 2: return launch_stream_collide_sw(fn, p_new, p_old, g, bc, BgkModelT<1, 0>{prm->omega}, n_steps, row_begin, row_end, as_stream(s), 4, second_begin);
-      default: return launch_stream_collide_sw(fn, p_new, p_old, g, bc, BgkModelT<1, 1>{prm->omega}, n_steps, row_begin, row_end, as_stream(s), 4, second_begin);
-    }
+    return with_flags([&](auto INCOMP, auto DELTA) {
+      return launch_stream_collide_sw(fn, p_new, p_old, g, bc, BgkModelT<INCOMP(), DELTA()>{prm->omega}, n_steps, row_begin, row_end, as_stream(s), 4, second_begin);
+    }, prm->incompressible, prm->delta_form);
   }
-  const BgkModel m{prm->omega, prm->incompressible, prm->delta_form, prm->force_mode, prm->force_r, prm->force_c, prm->guo_a, prm->guo_b};
   // runtime-mode model (body force): uncapped 2-wave blocks (the 4-wave variants spill 280-410 VGPRs)
-  return launch_stream_collide_sw(fn, p_new, p_old, g, bc, m, n_steps, row_begin, row_end, as_stream(s), 2, second_begin);
+  return launch_stream_collide_sw(fn, p_new, p_old, g, bc, bgk_model(prm), n_steps, row_begin, row_end, as_stream(s), 2, second_begin);
 }
 
 int lbm_bgk_stream_collide_xn(double* p_new, const double* p_old, const lbm_geom* g,
@@ -201,8 +198,7 @@ int lbm::bgk_stream_collide_xn_ref(double* p_new, const double* p_old, const lbm
 int lbm::bgk_collide_ref(double* p, const double* f, const lbm_geom* g, const lbm_bgk_params* prm, hipStream_t st) {
   int rc = check_bgk("bgk_collide_ref", prm);
   if (rc) return rc;
-  const BgkModel m{prm->omega, prm->incompressible, prm->delta_form, prm->force_mode, prm->force_r, prm->force_c, prm->guo_a, prm->guo_b};
-  return launch_collide_only("bgk_collide_ref", p, f, g, nullptr, m, nullptr, nullptr, st);
+  return launch_collide_only("bgk_collide_ref", p, f, g, nullptr, bgk_model(prm), nullptr, nullptr, st);
 }
 
 bool lbm::bgk_uses_fast_model(const lbm_bgk_params* prm, const lbm_bc* bc) { return prm && use_fast_bgk(prm, bc); }

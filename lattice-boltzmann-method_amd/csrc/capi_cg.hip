@@ -65,14 +65,9 @@ static int launch_cg_collide(bool from_post, double* pn_r, double* pn_b, const d
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= g.R, "lbm_cg: row range [%d, %d) outside [0, %d)", row_begin, row_end, g.R);
   if (row_begin == row_end) return LBM_OK;
   const int tiles = ((row_end - row_begin + CG_TR - 1) / CG_TR) * ((g.C + CG_TC - 1) / CG_TC);
-  const bool fields = psi != nullptr;
-  if (from_post) {
-    if (fields) LBM_KLAUNCH((k_cg_collide<true, true>), dim3(tiles), dim3(256), 0, st, pn_r, pn_b, in_r, in_b, rho_r, rho_b, u, g, bc, cc, psi, snu, mi, row_begin, row_end);
-    else LBM_KLAUNCH((k_cg_collide<true, false>), dim3(tiles), dim3(256), 0, st, pn_r, pn_b, in_r, in_b, rho_r, rho_b, u, g, bc, cc, psi, snu, mi, row_begin, row_end);
-  } else {
-    if (fields) LBM_KLAUNCH((k_cg_collide<false, true>), dim3(tiles), dim3(256), 0, st, pn_r, pn_b, in_r, in_b, rho_r, rho_b, u, g, bc, cc, psi, snu, mi, row_begin, row_end);
-    else LBM_KLAUNCH((k_cg_collide<false, false>), dim3(tiles), dim3(256), 0, st, pn_r, pn_b, in_r, in_b, rho_r, rho_b, u, g, bc, cc, psi, snu, mi, row_begin, row_end);
-  }
+  with_flags([&](auto POST, auto FIELDS) {
+    LBM_KLAUNCH((k_cg_collide<POST(), FIELDS()>), dim3(tiles), dim3(256), 0, st, pn_r, pn_b, in_r, in_b, rho_r, rho_b, u, g, bc, cc, psi, snu, mi, row_begin, row_end);
+  }, from_post, psi != nullptr);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
@@ -84,6 +79,7 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
                              const Geom& g, const Bc& bc, const CgFast& cf, double* rho_r,
                              double* rho_b, double* u, double* psi, double* snu, const MacroIdx& mi,
                              int row_begin, int row_end, hipStream_t st, int part = 0, int edge_rows = 0) {
+  const bool fields = psi != nullptr;  // the launches write psi, s_nu and the moments
   // part 0: the whole row range (frame beside the inner launch on a helper stream); 1 / 2: ONLY the frame -- widened to
   // every node of the first and last `edge_rows` rows of the range -- / ONLY the inner rectangle, on `st`: a slab runs the
   // two on two streams and sends its edge rows while the inner launch is still busy (lbm_cg_step_fused_part)
@@ -144,16 +140,14 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
   }
   if (!split) {
     if (part == 2) return LBM_OK;  // no inner rectangle: the frame part runs every tile
-    if (psi) LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, true>), dim3(tiles), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs);
-    else LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, false>), dim3(tiles), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs);
+    with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, PSI()>), dim3(tiles), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs); }, fields);
     LBM_CHECK_LAUNCH();
     return LBM_OK;
   }
   const int inner = (rc.ir1 - rc.ir0) * (rc.ic1 - rc.ic0), frame = tiles - inner;
 #ifdef LBM_EXPERIMENTS
   if (!part && frame > 0 && !tuning("cg_strip2", 0) && tuning("cg_merge", 0)) {  // frame + inner tiles in one dispatch (opt-in: measured level with the two-launch form, 15.24 k either way)
-    if (psi) LBM_KLAUNCH((k_cg_fused_merged<TR, TC, WAVES, true>), dim3(frame + inner), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs, rc, frame);
-    else LBM_KLAUNCH((k_cg_fused_merged<TR, TC, WAVES, false>), dim3(frame + inner), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs, rc, frame);
+    with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_fused_merged<TR, TC, WAVES, PSI()>), dim3(frame + inner), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs, rc, frame); }, fields);
     LBM_CHECK_LAUNCH();
     return LBM_OK;
   }
@@ -164,8 +158,7 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
   hipStream_t fs = st;
   if (sd && hipEventRecord(sd->fork, st) == hipSuccess && hipStreamWaitEvent(sd->st, sd->fork, 0) == hipSuccess) fs = sd->st;
   if (frame > 0 && part != 2) {
-    if (psi) LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, true, 2>), dim3(frame), dim3(TR * TC), 0, fs, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, 0, rc);
-    else LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, false, 2>), dim3(frame), dim3(TR * TC), 0, fs, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, 0, rc);
+    with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, PSI(), 2>), dim3(frame), dim3(TR * TC), 0, fs, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, 0, rc); }, fields);
     LBM_CHECK_LAUNCH();
   }
   if (part == 1) return LBM_OK;
@@ -184,14 +177,12 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
       if (rpc < 16) rpc = 16;
       const int rows_total = n_btr * 16, chunks = (rows_total + rpc - 1) / rpc;
       const int wx = tuning("cg_walk_tile_xcd", 2);
-      if (psi) LBM_KLAUNCH((k_cg_walk_tile<true>), dim3(chunks * n_btc), dim3(512), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, ca, n_btc, rows_total, rpc, wx);
-      else LBM_KLAUNCH((k_cg_walk_tile<false>), dim3(chunks * n_btc), dim3(512), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, ca, n_btc, rows_total, rpc, wx);
+      with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_walk_tile<PSI()>), dim3(chunks * n_btc), dim3(512), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, ca, n_btc, rows_total, rpc, wx); }, fields);
     } else
 #endif
     {
 #define LBM_CG_BIG(BR, BC, BT, BM, BP)                                                                               \
-    if (psi) LBM_KLAUNCH((k_cg_tile_mn<BR, BC, BT, BM, BP, true>), dim3(nt), dim3(BT), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, ca, n_btc, bx); \
-    else LBM_KLAUNCH((k_cg_tile_mn<BR, BC, BT, BM, BP, false>), dim3(nt), dim3(BT), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, ca, n_btc, bx);
+    with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_tile_mn<BR, BC, BT, BM, BP, PSI()>), dim3(nt), dim3(BT), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, ca, n_btc, bx); }, fields);
     switch (shape) {
 #ifdef LBM_EXPERIMENTS  // the shapes of the round-4 sweep that lost to 16 x 64 (profiles/r04_cg_big_sweep.txt)
       case 1: LBM_CG_BIG(32, 32, 512, 4, true) break;    // 2 nodes per thread, the second parked in LDS: 2 workgroups per CU
@@ -224,12 +215,10 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
     const int xo = tuning("cg_walk_xcd", 1);
     g_last_inner_form = sw4;
     if (sw4 == 41 && tuning("cg_walk_pf", 1) == 0) {  // the 4 x 1 block without prefetch, 4 waves per SIMD
-      if (psi) LBM_KLAUNCH((k_cg_walk<4, 1, true, false>), dim3(grid), dim3(256), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, nb, xo);
-      else LBM_KLAUNCH((k_cg_walk<4, 1, false, false>), dim3(grid), dim3(256), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, nb, xo);
+      with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_walk<4, 1, PSI(), false>), dim3(grid), dim3(256), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, nb, xo); }, fields);
     } else
 #define LBM_CG_WALK(WTR, WWC)                                                                                          \
-    if (psi) LBM_KLAUNCH((k_cg_walk<WTR, WWC, true>), dim3(grid), dim3(WTR * WWC * 64), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, nb, xo); \
-    else LBM_KLAUNCH((k_cg_walk<WTR, WWC, false>), dim3(grid), dim3(WTR * WWC * 64), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, nb, xo);
+    with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_walk<WTR, WWC, PSI()>), dim3(grid), dim3(WTR * WWC * 64), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, nb, xo); }, fields);
     switch (sw4) {
       case 41: LBM_CG_WALK(4, 1) break;
       case 42: LBM_CG_WALK(6, 1) break;
@@ -258,8 +247,7 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
     const int chunks = (rb - ra + rpc - 1) / rpc, sync = tuning("cg_sync", 8);
     g_last_inner_form = sw4;
 #define LBM_CG_S5(WV)                                                                                              \
-    if (psi) LBM_KLAUNCH((k_cg_strip5<WV, true>), dim3(groups * chunks), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, groups, sync); \
-    else LBM_KLAUNCH((k_cg_strip5<WV, false>), dim3(groups * chunks), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, groups, sync);
+    with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_strip5<WV, PSI()>), dim3(groups * chunks), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, groups, sync); }, fields);
     if (sw4 == 31) { LBM_CG_S5(2) } else { LBM_CG_S5(4) }
 #undef LBM_CG_S5
   } else
@@ -280,8 +268,7 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
     const int chunks = (rb - ra + rpc - 1) / rpc;
     g_last_inner_form = sw4;
 #define LBM_CG_S4(WV)                                                                                              \
-    if (psi) LBM_KLAUNCH((k_cg_strip4<WV, true>), dim3(bstrips * chunks), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, bstrips, win0); \
-    else LBM_KLAUNCH((k_cg_strip4<WV, false>), dim3(bstrips * chunks), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, bstrips, win0);
+    with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_strip4<WV, PSI()>), dim3(bstrips * chunks), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, bstrips, win0); }, fields);
     if (sw4 == 21) { LBM_CG_S4(4) } else { LBM_CG_S4(8) }
 #undef LBM_CG_S4
   } else
@@ -307,14 +294,12 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
     const int chunks = (rb - ra + rpc - 1) / rpc, n_waves = strips * chunks;
     g_last_inner_form = sw;
 #define LBM_CG_S2(KERNEL, WV)                                                                                      \
-    if (psi) LBM_KLAUNCH((KERNEL<WV, true>), dim3((n_waves + WV - 1) / WV), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, n_waves); \
-    else LBM_KLAUNCH((KERNEL<WV, false>), dim3((n_waves + WV - 1) / WV), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, n_waves);
+    with_flags([&](auto PSI) { LBM_KLAUNCH((KERNEL<WV, PSI()>), dim3((n_waves + WV - 1) / WV), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, n_waves); }, fields);
     const int xo = tuning("cg_strip_xcd", 0);  // strip3: XCD k takes the k-th contiguous eighth of the strip sequence (measured: no effect)
 #define LBM_CG_S3(WV)                                                                                              \
     {                                                                                                              \
       const int nblk = (n_waves + WV - 1) / WV, grid3 = xo ? ((nblk + 7) / 8) * 8 : nblk;                          \
-      if (psi) LBM_KLAUNCH((k_cg_strip3<WV, true>), dim3(grid3), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, n_waves, xo); \
-      else LBM_KLAUNCH((k_cg_strip3<WV, false>), dim3(grid3), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, n_waves, xo); \
+      with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_strip3<WV, PSI()>), dim3(grid3), dim3(64 * WV), 0, st, pn_r, pn_b, in_r, in_b, g, cf, rho_r, rho_b, u, psi, snu, mi, ra, rb, ca, cb, rpc, strips, n_waves, xo); }, fields); \
     }
     if (sw == 2) { LBM_CG_S2(k_cg_strip2, 2) } else if (sw == 1) { LBM_CG_S2(k_cg_strip2, 1) }
     else if (sw == 11) LBM_CG_S3(1) else if (sw == 12) LBM_CG_S3(2)
@@ -323,8 +308,7 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
 #undef LBM_CG_S3
   } else
 #endif  // LBM_EXPERIMENTS (strip kernels)
-  if (psi) LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, true, 1>), dim3(inner), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs, rc);
-  else LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, false, 1>), dim3(inner), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs, rc);
+  with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, PSI(), 1>), dim3(inner), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs, rc); }, fields);
   LBM_CHECK_LAUNCH();
   if (fs != st) {
     LBM_CHECK_HIP(hipEventRecord(sd->join, fs));
@@ -339,14 +323,14 @@ static int launch_cg_strip_t(double* pn_r, double* pn_b, const double* in_r, con
                              const Geom& g, const Bc& bc, const CgFast& cf, double* rho_r,
                              double* rho_b, double* u, double* psi, double* snu, const MacroIdx& mi,
                              int row_begin, int row_end, hipStream_t st) {
+  const bool fields = psi != nullptr;
   int rpc = tuning("cg_rows", 16);
   const int nrows = row_end - row_begin;
   if (rpc > nrows) rpc = nrows;
   const int strips = (g.C + CG_SW - 1) / CG_SW, chunks = (nrows + rpc - 1) / rpc;
   const int n_waves = strips * chunks;
   const dim3 grid((n_waves + WAVES - 1) / WAVES);
-  if (psi) LBM_KLAUNCH((k_cg_strip<WAVES, true>), grid, dim3(64 * WAVES), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, rpc, strips, n_waves);
-  else LBM_KLAUNCH((k_cg_strip<WAVES, false>), grid, dim3(64 * WAVES), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, rpc, strips, n_waves);
+  with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_strip<WAVES, PSI()>), grid, dim3(64 * WAVES), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, rpc, strips, n_waves); }, fields);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }

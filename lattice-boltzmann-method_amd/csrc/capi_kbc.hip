@@ -105,8 +105,7 @@ static int launch_kbc_pressure_rows(int mode, double* pn, const double* in, cons
   const Geom g = make_geom(*lg);
   const Bc bc = make_bc(lbc);
   const int n = 2 * g.C;
-  if (mode) LBM_KLAUNCH(k_kbc_pressure_rows<1>, dim3((n + 255) / 256), dim3(256), 0, st, pn, in, g, bc, m, m0, m1);
-  else LBM_KLAUNCH(k_kbc_pressure_rows<0>, dim3((n + 255) / 256), dim3(256), 0, st, pn, in, g, bc, m, m0, m1);
+  with_flags([&](auto POST) { LBM_KLAUNCH(k_kbc_pressure_rows<POST() ? 1 : 0>, dim3((n + 255) / 256), dim3(256), 0, st, pn, in, g, bc, m, m0, m1); }, mode);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
@@ -116,56 +115,31 @@ static int launch_kbc_pressure_rows(int mode, double* pn, const double* in, cons
 static int launch_stream_collide_sw_kbc(const char* fn, double* pn, const double* po,
                                         const lbm_geom* lg, const lbm_bc* lbc, const KbcFastModel& m,
                                         int depth, int row_begin, int row_end, hipStream_t st) {
-  int rc = validate_geom_bc(fn, lg, lbc);
-  if (rc) return rc;
-  LBM_REQUIRE(pn && po && pn != po, "%s: NULL or aliased lattices", fn);
-  LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R,
-              "%s: row range [%d, %d) outside [0, %d)", fn, row_begin, row_end, lg->R);
-  const Bc bc = make_bc(lbc);
-  auto carried = [](int m) { return m == LBM_EDGE_PERIODIC || m == LBM_EDGE_HALO || bc_is_wall(m); };
-  LBM_REQUIRE(carried(bc.row_lo) && carried(bc.row_hi) && carried(bc.col_lo) && carried(bc.col_hi) && !bc.pressure_rows,
-              "%s: multi-step launches carry periodic / halo / bounce-back / specular / velocity edges only", fn);
-  LBM_REQUIRE(!bc_mixed_axis(bc), "%s: multi-step launches need both edges of an axis walled or neither", fn);
-  const bool walls = bc_needs_edge_pass(bc);
-  LBM_REQUIRE(!walls || (lg->ghost == 0 && depth <= 3), "%s: wall-carrying launches are single-block only, 2..3 steps", fn);
-  LBM_REQUIRE(lg->ghost == 0 || lg->ghost >= depth, "%s: ghost=%d rows, need 0 or >= %d", fn, lg->ghost, depth);
-  LBM_REQUIRE(lg->R >= 4 * depth + 8 && lg->C >= 64, "%s: lattice %dx%d too small for %d-step launches", fn, lg->R, lg->C, depth);
-  if (row_begin == row_end) return LBM_OK;
-  const Geom g = make_geom(*lg);
-  const int nrows = row_end - row_begin;
-  const int W = sw_strip_width(depth, sw_full_strips<KbcFastModel>::value);
-  const int strips = (g.C + W - 1) / W;
-  LBM_REQUIRE((long)strips * ((nrows + 31) / 32) < (1L << 30), "%s: lattice too large for one launch", fn);
-  // rows per wave: "sw_rows" if set, else fitted to the resident wave slots of the instance (launch.hpp)
-#define LBM_KBC_SW(...)                                                                               \
-  {                                                                                                   \
-    int rpc = tuning("sw_rows", -1);                                                                  \
-    if (rpc <= 0) {                                                                                   \
-      const long slots = sw_wave_slots((const void*)k_stream_collide_sw<__VA_ARGS__>, 128);           \
-      rpc = slots > 0 ? sw_pick_rows(nrows, strips, depth, slots) : 64;                               \
-    }                                                                                                 \
-    if (rpc > nrows) rpc = nrows;                                                                     \
-    const int n_waves = strips * ((nrows + rpc - 1) / rpc);                                           \
-    LBM_KLAUNCH((k_stream_collide_sw<__VA_ARGS__>), dim3((n_waves + 1) / 2), dim3(128), 0, st, pn, po, g, m, row_begin, row_end, rpc, strips, n_waves, LBM_KBC_SW_TAIL); \
-  }
-  if (walls) {  // plain instantiation on the wall-free interior, wall-carrying one on the frame (launch.hpp)
-    rc = depth == 2 ? sw_launch_walls<KbcFastModel, 2>(pn, po, g, m, bc, row_begin, row_end, st)
-                    : sw_launch_walls<KbcFastModel, 3>(pn, po, g, m, bc, row_begin, row_end, st);
+  SwArgs a;
+  int rc = sw_check_args(fn, pn, po, lg, lbc, depth, row_begin, row_end, sw_full_strips<KbcFastModel>::value, kSwKbc, &a);
+  if (rc || !a.nrows) return rc;
+  if (a.walls) {  // plain instantiation on the wall-free interior, wall-carrying one on the frame (launch.hpp)
+    rc = depth == 2 ? sw_launch_walls<KbcFastModel, 2>(pn, po, a.g, m, a.bc, row_begin, row_end, st)
+                    : sw_launch_walls<KbcFastModel, 3>(pn, po, a.g, m, a.bc, row_begin, row_end, st);
     if (rc) return rc;
     LBM_CHECK_LAUNCH();
     return LBM_OK;
   }
-#define LBM_KBC_SW_TAIL tuning("sw_xcd", 0)
-  // "sw_ldsring" (default 1): the ring of the 2- / 3-step window in wave-private LDS instead of registers (d2q9.hpp LDSR)
-  const bool ldsr = tuning("sw_ldsring", 1) != 0;
-  if (depth == 2 && ldsr) LBM_KBC_SW(KbcFastModel, 2, 2, true, false, false, true)
-  else if (depth == 3 && ldsr) LBM_KBC_SW(KbcFastModel, 3, 2, true, false, false, true)
-  else if (depth == 4 && ldsr) LBM_KBC_SW(KbcFastModel, 4, 2, true, false, false, true)
-  else if (depth == 2) LBM_KBC_SW(KbcFastModel, 2, 2, true)
-  else if (depth == 3) LBM_KBC_SW(KbcFastModel, 3, 2, true)
-  else LBM_KBC_SW(KbcFastModel, 4, 2, true)
-#undef LBM_KBC_SW_TAIL
-#undef LBM_KBC_SW
+  // rows per wave: "sw_rows" if set, else fitted to the resident wave slots of the instance (launch.hpp sw_plan)
+  auto launch = [&](auto D, auto LDSR) {
+    constexpr int DV = decltype(D)::value;
+    const SwPlan p = sw_plan(k_stream_collide_sw<KbcFastModel, DV, 2, true, false, false, LDSR()>, 128, a.nrows, a.strips, depth);
+    LBM_KLAUNCH((k_stream_collide_sw<KbcFastModel, DV, 2, true, false, false, LDSR()>), dim3((p.n_waves + 1) / 2), dim3(128), 0, st, pn, po, a.g, m,
+                row_begin, row_end, p.rpc, a.strips, p.n_waves, tuning("sw_xcd", 0));
+  };
+  // "sw_ldsring" (default 1): the ring of the 2- / 3- / 4-step window in wave-private LDS instead of registers (d2q9.hpp LDSR)
+  with_flags([&](auto LDSR) {
+    switch (depth) {
+      case 2: launch(std::integral_constant<int, 2>{}, LDSR); break;
+      case 3: launch(std::integral_constant<int, 3>{}, LDSR); break;
+      default: launch(std::integral_constant<int, 4>{}, LDSR); break;
+    }
+  }, tuning("sw_ldsring", 1) != 0);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
@@ -215,6 +189,14 @@ bool kbc_uses_fast_model(const lbm_kbc_params* prm) {
   return prm->form == LBM_FORM_DEFAULT ? tuning("kbc_fast", 1) != 0 : prm->form == LBM_FORM_REASSOCIATED;
 }
 
+// f(model) with the model the single-step entry points run: the reassociated collision (kbc.hpp) unless the caller asks
+// for the reference operation order or the pressure rows -- which re-collide their source rows in that order -- are in use
+template <class F>
+static int with_kbc_model(const lbm_kbc_params* prm, const lbm_bc* bc, F f) {
+  if (kbc_uses_fast_model(prm) && !(bc && bc->pressure_rows)) return f(KbcFastModel(prm->s2));
+  return f(KbcModel{prm->s2});
+}
+
 }  // namespace lbm
 
 using namespace lbm;
@@ -249,9 +231,7 @@ int lbm_kbc_collide(double* p, const double* f, const lbm_geom* g, const lbm_bc*
   int rc = check_kbc("lbm_kbc_collide", prm);
   if (rc) return rc;
   LBM_REQUIRE(!(bc && bc->pressure_rows), "lbm_kbc_collide: pressure rows need the moments of the source rows: use lbm_kbc_collide_first");
-  if (kbc_uses_fast_model(prm))
-    return launch_collide_only("lbm_kbc_collide", p, f, g, bc, KbcFastModel(prm->s2), rho, u, as_stream(s));
-  return launch_collide_only("lbm_kbc_collide", p, f, g, bc, KbcModel{prm->s2}, rho, u, as_stream(s));
+  return with_kbc_model(prm, bc, [&](const auto& m) { return launch_collide_only("lbm_kbc_collide", p, f, g, bc, m, rho, u, as_stream(s)); });
 }
 
 int lbm_kbc_collide_first(double* p, const double* f, const double* m0, const double* m1,
@@ -277,14 +257,9 @@ int lbm_kbc_stream_collide(double* p_new, const double* p_old, const lbm_geom* g
                            int row_end, double* rho, double* u, lbm_stream_t s) {
   int rc = check_kbc("lbm_kbc_stream_collide", prm);
   if (rc) return rc;
-  // the reassociated collision (kbc.hpp) unless the caller asks for the reference operation order
-  // (tuning "kbc_fast" = 0) or the pressure rows -- which re-collide their source rows in that order
-  // -- are in use
-  if (kbc_uses_fast_model(prm) && !(bc && bc->pressure_rows))
-    return launch_stream_collide("lbm_kbc_stream_collide", p_new, p_old, g, bc, KbcFastModel(prm->s2),
-                                 row_begin, row_end, rho, u, as_stream(s));
-  rc = launch_stream_collide("lbm_kbc_stream_collide", p_new, p_old, g, bc, KbcModel{prm->s2},
-                             row_begin, row_end, rho, u, as_stream(s));
+  rc = with_kbc_model(prm, bc, [&](const auto& m) {
+    return launch_stream_collide("lbm_kbc_stream_collide", p_new, p_old, g, bc, m, row_begin, row_end, rho, u, as_stream(s));
+  });
   if (rc) return rc;
   if (bc && bc->pressure_rows) {
     LBM_REQUIRE(row_begin == 0 && row_end == g->R, "lbm_kbc_stream_collide: pressure rows need the whole block");

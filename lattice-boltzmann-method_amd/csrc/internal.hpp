@@ -6,6 +6,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/lbm_hip.h"
 
@@ -88,6 +89,19 @@ int write_npy(const char* path, const double* data, const std::vector<long>& sha
     (void)hipGetLastError();           \
     hipLaunchKernelGGL(__VA_ARGS__);   \
   } while (0)
+
+// Run-time flags as template arguments: with_flags(f, a, b, ...) calls f(A, B, ...) with std::true_type / std::false_type
+// objects, so that a launch site names its kernel ONCE -- K<..., A(), B()> inside a generic lambda -- and all 2^N
+// instantiations exist.  A combination that must not be compiled is pruned with `if constexpr` inside the lambda.
+template <class F>
+auto with_flags(F&& f) {
+  return f();
+}
+template <class F, class... Rest>
+auto with_flags(F&& f, bool flag, Rest... rest) {
+  if (flag) return with_flags([&](auto... t) { return f(std::true_type{}, t...); }, rest...);
+  return with_flags([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
 
 inline hipStream_t as_stream(lbm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 

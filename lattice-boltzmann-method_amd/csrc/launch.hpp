@@ -68,8 +68,7 @@ int launch_stream_collide(const char* fn, double* pn, const double* po, const lb
   if (!fast) {  // generic path: boundary gather on every node
     const long n = (long)nrows * g.C;
     const int grid = capped_grid((n + 255) / 256);
-    if (mom) LBM_KLAUNCH((k_generic_collide<Model, true, true>), dim3(grid), dim3(256), 0, st, pn, po, g, bc, m, row_begin, row_end, rho, u);
-    else LBM_KLAUNCH((k_generic_collide<Model, true, false>), dim3(grid), dim3(256), 0, st, pn, po, g, bc, m, row_begin, row_end, rho, u);
+    with_flags([&](auto M) { LBM_KLAUNCH((k_generic_collide<Model, true, M()>), dim3(grid), dim3(256), 0, st, pn, po, g, bc, m, row_begin, row_end, rho, u); }, mom);
     LBM_CHECK_LAUNCH();
     return LBM_OK;
   }
@@ -81,13 +80,10 @@ int launch_stream_collide(const char* fn, double* pn, const double* po, const lb
     const int tiles = (g.C + 256 * NODES_PER_THREAD - 1) / (256 * NODES_PER_THREAD);            \
     const long items = (long)nrows * tiles;                                                     \
     const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30)); \
-    switch ((nt & 3) | (mom ? 4 : 0)) {                                                         \
-      case 0: LBM_KLAUNCH((KERNEL<Model, false, false, false>), dim3(grid), dim3(256), 0, st, pn, po, g, m, row_begin, row_end, tiles, rho, u); break; \
-      case 1: LBM_KLAUNCH((KERNEL<Model, true, false, false>), dim3(grid), dim3(256), 0, st, pn, po, g, m, row_begin, row_end, tiles, rho, u); break;  \
-      case 2: LBM_KLAUNCH((KERNEL<Model, false, true, false>), dim3(grid), dim3(256), 0, st, pn, po, g, m, row_begin, row_end, tiles, rho, u); break;  \
-      case 3: LBM_KLAUNCH((KERNEL<Model, true, true, false>), dim3(grid), dim3(256), 0, st, pn, po, g, m, row_begin, row_end, tiles, rho, u); break;   \
-      default: LBM_KLAUNCH((KERNEL<Model, false, false, true>), dim3(grid), dim3(256), 0, st, pn, po, g, m, row_begin, row_end, tiles, rho, u); break; \
-    }                                                                                           \
+    with_flags([&](auto NL, auto NS, auto M) { /* with moments: the temporal instantiation only */ \
+      if constexpr (!M() || (!NL() && !NS()))                                                   \
+        LBM_KLAUNCH((KERNEL<Model, NL(), NS(), M()>), dim3(grid), dim3(256), 0, st, pn, po, g, m, row_begin, row_end, tiles, rho, u); \
+    }, !mom && (nt & 1), !mom && (nt & 2), mom);                                                \
   } while (0)
   if (variant == 3 && !mom) {
     const int block = tuning("block", 256), rows = tuning("rows", 1);
@@ -99,12 +95,10 @@ int launch_stream_collide(const char* fn, double* pn, const double* po, const lb
     LBM_REQUIRE(items_l < (1L << 30), "%s: lattice too large for one launch", fn);                 \
     const int n_items = (int)items_l;                                                              \
     const dim3 grid(swz ? ((n_items + 7) / 8) * 8 : n_items);                                      \
-    switch (nt & 3) {                                                                              \
-      case 0: LBM_KLAUNCH((k_stream_collide_v3<Model, B, RW, false, false>), grid, dim3(B), 0, st, pn, po, g, m, row_begin, row_end, tiles_x, n_items, swz); break; \
-      case 1: LBM_KLAUNCH((k_stream_collide_v3<Model, B, RW, true, false>), grid, dim3(B), 0, st, pn, po, g, m, row_begin, row_end, tiles_x, n_items, swz); break;  \
-      case 2: LBM_KLAUNCH((k_stream_collide_v3<Model, B, RW, false, true>), grid, dim3(B), 0, st, pn, po, g, m, row_begin, row_end, tiles_x, n_items, swz); break;  \
-      default: LBM_KLAUNCH((k_stream_collide_v3<Model, B, RW, true, true>), grid, dim3(B), 0, st, pn, po, g, m, row_begin, row_end, tiles_x, n_items, swz); break;  \
-    }                                                                                              \
+    with_flags([&](auto NL, auto NS) {                                                             \
+      LBM_KLAUNCH((k_stream_collide_v3<Model, B, RW, NL(), NS()>), grid, dim3(B), 0, st, pn, po, g, m, row_begin, row_end, \
+                  tiles_x, n_items, swz);                                                          \
+    }, nt & 1, nt & 2);                                                                            \
   } else
     LBM_V3(128, 1) LBM_V3(256, 1) LBM_V3(512, 1) LBM_V3(1024, 1) LBM_V3(128, 2) LBM_V3(256, 2)
     LBM_V3(512, 2) LBM_V3(256, 4) LBM_V3(128, 4) {
@@ -119,8 +113,10 @@ int launch_stream_collide(const char* fn, double* pn, const double* po, const lb
 
   if (bc_needs_edge_pass(bc)) {
     const int n_edge = 2 * g.C + 2 * (row_end - row_begin);
-    if (mom) LBM_KLAUNCH((k_edge_stream_collide<Model, true>), dim3((n_edge + 255) / 256), dim3(256), 0, st, pn, po, g, bc, m, row_begin, row_end, rho, u);
-    else LBM_KLAUNCH((k_edge_stream_collide<Model, false>), dim3((n_edge + 255) / 256), dim3(256), 0, st, pn, po, g, bc, m, row_begin, row_end, rho, u);
+    with_flags([&](auto M) {
+      LBM_KLAUNCH((k_edge_stream_collide<Model, M()>), dim3((n_edge + 255) / 256), dim3(256), 0, st, pn, po, g, bc, m,
+                  row_begin, row_end, rho, u);
+    }, mom);
     LBM_CHECK_LAUNCH();
   }
   return LBM_OK;
@@ -151,8 +147,10 @@ int launch_stream_collide_x2(const char* fn, double* pn, const double* po, const
     const int tiles_y = (nrows + TRV - 1) / TRV;                                                  \
     const long nblk = (long)tiles_x * tiles_y;                                                    \
     LBM_REQUIRE(nblk < (1L << 30), "%s: lattice too large for one launch", fn);                   \
-    if (nt) LBM_KLAUNCH((k_stream_collide_tb2<Model, TRV, BV, true>), dim3((unsigned)nblk), dim3(BV), 0, st, pn, po, g, m, row_begin, row_end, tiles_x, tiles_y, order); \
-    else LBM_KLAUNCH((k_stream_collide_tb2<Model, TRV, BV, false>), dim3((unsigned)nblk), dim3(BV), 0, st, pn, po, g, m, row_begin, row_end, tiles_x, tiles_y, order);   \
+    with_flags([&](auto NS) {                                                                     \
+      LBM_KLAUNCH((k_stream_collide_tb2<Model, TRV, BV, NS()>), dim3((unsigned)nblk), dim3(BV), 0, st, pn, po, g, m, \
+                  row_begin, row_end, tiles_x, tiles_y, order);                                   \
+    }, nt);                                                                                       \
   } else
   LBM_TB2(4, 256) LBM_TB2(6, 256) LBM_TB2(8, 256) LBM_TB2(8, 512) LBM_TB2(12, 256) LBM_TB2(12, 512)
   LBM_TB2(14, 512) LBM_TB2(16, 512) LBM_TB2(16, 1024) LBM_TB2(30, 1024) {
@@ -210,22 +208,31 @@ inline long sw_wave_slots(const void* kernel, int block_threads) {
   return slots;
 }
 
+// The chunk plan of a sliding-window launch over nrows x strips: rows per wave -- rows_fixed, else "sw_rows", else fitted
+// to the resident wave slots of THIS kernel instance (64 where the occupancy query fails) -- and the number of waves.
+struct SwPlan {
+  int rpc, n_waves;
+};
+template <class Kernel>
+SwPlan sw_plan(Kernel* kernel, int block_threads, int nrows, int strips, int depth, int rows_fixed = 0) {
+  int rpc = rows_fixed > 0 ? rows_fixed : tuning("sw_rows", -1);
+  if (rpc <= 0) {
+    const long slots = sw_wave_slots((const void*)kernel, block_threads);
+    rpc = slots > 0 ? sw_pick_rows(nrows, strips, depth, slots) : 64;
+  }
+  if (rpc > nrows) rpc = nrows;
+  return {rpc, strips * ((nrows + rpc - 1) / rpc)};
+}
+
 // one rectangle (rows [r0, r1) x strips [s0, s0 + ns)) of a sliding-window launch through the 2-wave
 // instantiation with or without the wall fix-ups
 template <class Model, int DV, bool HAS_BC>
 void sw_launch_part(double* pn, const double* po, const Geom& g, const Model& m, const Bc& bc, int r0,
                     int r1, int s0, int ns, int rows_fixed, hipStream_t st) {
   if (r0 >= r1 || ns <= 0) return;
-  const int nrows = r1 - r0;
-  int rpc = rows_fixed > 0 ? rows_fixed : tuning("sw_rows", -1);
-  if (rpc <= 0) {
-    const long slots = sw_wave_slots((const void*)k_stream_collide_sw<Model, DV, 2, true, HAS_BC>, 128);
-    rpc = slots > 0 ? sw_pick_rows(nrows, ns, DV, slots) : 64;
-  }
-  if (rpc > nrows) rpc = nrows;
-  const int n_waves = ns * ((nrows + rpc - 1) / rpc);
-  LBM_KLAUNCH((k_stream_collide_sw<Model, DV, 2, true, HAS_BC>), dim3((n_waves + 1) / 2), dim3(128), 0, st, pn, po, g, m,
-              r0, r1, rpc, ns, n_waves, 0, bc, s0);
+  const SwPlan p = sw_plan(k_stream_collide_sw<Model, DV, 2, true, HAS_BC>, 128, r1 - r0, ns, DV, rows_fixed);
+  LBM_KLAUNCH((k_stream_collide_sw<Model, DV, 2, true, HAS_BC>), dim3((p.n_waves + 1) / 2), dim3(128), 0, st, pn, po, g, m,
+              r0, r1, p.rpc, ns, p.n_waves, 0, bc, s0);
 }
 
 // Helper stream of the calling host thread on the current device: the few waves of a wall frame run
@@ -301,12 +308,7 @@ int sw_launch_walls(double* pn, const double* po, const Geom& g, const Model& m,
     part(2, row_begin, ra, s0, s1 - s0, fr, w0);
     part(3, rb, row_end, s0, s1 - s0, fr, w0);
     pp.n_frame_waves = w0;
-    int rpc = tuning("sw_rows", -1);
-    if (rpc <= 0) {
-      const long slots = sw_wave_slots((const void*)k_stream_collide_sw_walls<Model, DV, true>, 128);
-      rpc = slots > 0 ? sw_pick_rows(rb - ra, s1 - s0, DV, slots) : 64;
-    }
-    part(4, ra, rb, s0, s1 - s0, rpc, w0);
+    part(4, ra, rb, s0, s1 - s0, sw_plan(k_stream_collide_sw_walls<Model, DV, true>, 128, rb - ra, s1 - s0, DV).rpc, w0);
     pp.n_waves = w0;
     LBM_KLAUNCH((k_stream_collide_sw_walls<Model, DV, true>), dim3((pp.n_waves + 1) / 2), dim3(128), 0, st, pn, po, g, m, bc, pp);
     return LBM_OK;
@@ -328,6 +330,54 @@ int sw_launch_walls(double* pn, const double* po, const Geom& g, const Model& m,
   return LBM_OK;
 }
 
+// what a model's window accepts: steps per launch without / with walls, the hint its mixed-axis message ends with,
+// wall-carrying launches single-block only
+struct SwLimits {
+  int max_depth, max_depth_walls;
+  const char* mixed_axis_hint;
+  bool walls_single_block;
+};
+constexpr SwLimits kSwBgk{6, 5, " (wall + PERIODIC on one axis: use single steps)", false};
+constexpr SwLimits kSwKbc{4, 3, "", true};
+struct SwArgs {
+  Geom g;
+  Bc bc;
+  bool walls;
+  int nrows, strips;  // nrows = 0: an empty row range, nothing to launch
+};
+// The argument checks of a multi-step window launch (the first failing one decides the message).  KBC never reaches the
+// "steps per launch" message: lbm_kbc_stream_collide_xn checks 2..4 itself and the single-block check catches walls at 4.
+inline int sw_check_args(const char* fn, const double* pn, const double* po, const lbm_geom* lg, const lbm_bc* lbc, int depth,
+                         int row_begin, int row_end, bool full_strips, const SwLimits& lim, SwArgs* a) {
+  int rc = validate_geom_bc(fn, lg, lbc);
+  if (rc) return rc;
+  LBM_REQUIRE(pn && po && pn != po, "%s: NULL or aliased lattices", fn);
+  LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R,
+              "%s: row range [%d, %d) outside [0, %d)", fn, row_begin, row_end, lg->R);
+  a->bc = make_bc(lbc);
+  const Bc& bc = a->bc;
+  auto carried = [](int m) { return m == LBM_EDGE_PERIODIC || m == LBM_EDGE_HALO || bc_is_wall(m); };
+  LBM_REQUIRE(carried(bc.row_lo) && carried(bc.row_hi) && carried(bc.col_lo) && carried(bc.col_hi) && !bc.pressure_rows,
+              "%s: multi-step launches carry periodic / halo / bounce-back / specular / velocity edges only", fn);
+  LBM_REQUIRE(!bc_mixed_axis(bc), "%s: multi-step launches need both edges of an axis walled or neither%s", fn, lim.mixed_axis_hint);
+  a->walls = bc_needs_edge_pass(bc);
+  if (lim.walls_single_block)
+    LBM_REQUIRE(!a->walls || (lg->ghost == 0 && depth <= lim.max_depth_walls),
+                "%s: wall-carrying launches are single-block only, 2..%d steps", fn, lim.max_depth_walls);
+  // (over slabs the ghost rows must then be COMPLETE: exchange with LBM_HALO_FULL(depth))
+  const int max_depth = a->walls ? lim.max_depth_walls : lim.max_depth;
+  LBM_REQUIRE(depth >= 2 && depth <= max_depth, "%s: %d steps per launch (supported: 2..%d)", fn, depth, max_depth);
+  LBM_REQUIRE(lg->ghost == 0 || lg->ghost >= depth, "%s: ghost=%d rows, need 0 or >= %d", fn, lg->ghost, depth);
+  LBM_REQUIRE(lg->R >= 4 * depth + 8 && lg->C >= 64, "%s: lattice %dx%d too small for %d-step launches", fn, lg->R, lg->C, depth);
+  a->nrows = row_end - row_begin;
+  if (!a->nrows) return LBM_OK;
+  a->g = make_geom(*lg);
+  const int W = sw_strip_width(depth, full_strips);
+  a->strips = (a->g.C + W - 1) / W;
+  LBM_REQUIRE((long)a->strips * ((a->nrows + 31) / 32) < (1L << 30), "%s: lattice too large for one launch", fn);
+  return LBM_OK;
+}
+
 // p_new = D steps from p_old with the register sliding-window kernel; rows [row_begin, row_end)
 template <class Model>
 int launch_stream_collide_sw(const char* fn, double* pn, const double* po, const lbm_geom* lg,
@@ -345,43 +395,20 @@ int launch_stream_collide_sw(const char* fn, double* pn, const double* po, const
       return launch_stream_collide_sw(fn, pn, po, lg, lbc, m, depth, second_begin, second_begin + (row_end - row_begin), st, default_waves);
     }
   }
-  int rc = validate_geom_bc(fn, lg, lbc);
-  if (rc) return rc;
-  LBM_REQUIRE(pn && po && pn != po, "%s: NULL or aliased lattices", fn);
-  LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R,
-              "%s: row range [%d, %d) outside [0, %d)", fn, row_begin, row_end, lg->R);
-  const Bc bc = make_bc(lbc);
-  auto carried = [](int m) { return m == LBM_EDGE_PERIODIC || m == LBM_EDGE_HALO || bc_is_wall(m); };
-  LBM_REQUIRE(carried(bc.row_lo) && carried(bc.row_hi) && carried(bc.col_lo) && carried(bc.col_hi) && !bc.pressure_rows,
-              "%s: multi-step launches carry periodic / halo / bounce-back / specular / velocity edges only", fn);
-  LBM_REQUIRE(!bc_mixed_axis(bc), "%s: multi-step launches need both edges of an axis walled or neither (wall + PERIODIC on one axis: use single steps)", fn);
-  const bool walls = bc_needs_edge_pass(bc);
-  // (over slabs the ghost rows must then be COMPLETE: exchange with LBM_HALO_FULL(depth))
-  LBM_REQUIRE(depth >= 2 && depth <= (walls ? 5 : 6), "%s: %d steps per launch (supported: 2..%d)", fn, depth, walls ? 5 : 6);
-  LBM_REQUIRE(lg->ghost == 0 || lg->ghost >= depth, "%s: ghost=%d rows, need 0 or >= %d", fn, lg->ghost, depth);
-  LBM_REQUIRE(lg->R >= 4 * depth + 8 && lg->C >= 64, "%s: lattice %dx%d too small for %d-step launches", fn, lg->R, lg->C, depth);
-  if (row_begin == row_end) return LBM_OK;
-  const Geom g = make_geom(*lg);
-  const int nrows = row_end - row_begin;
-  const int W = sw_strip_width(depth, sw_full_strips<Model>::value);
-  const int strips = (g.C + W - 1) / W;
-  LBM_REQUIRE((long)strips * ((nrows + 31) / 32) < (1L << 30), "%s: lattice too large for one launch", fn);
+  SwArgs a;
+  int rc = sw_check_args(fn, pn, po, lg, lbc, depth, row_begin, row_end, sw_full_strips<Model>::value, kSwBgk, &a);
+  if (rc || !a.nrows) return rc;
+  const Geom& g = a.g;
+  const Bc& bc = a.bc;
+  const int nrows = a.nrows, strips = a.strips;
   const int nt = tuning("nt", 3) & 2, waves = tuning("sw_waves", default_waves);
-  int rpc = 0, n_waves = 0;
-  // sw_rows > 0: fixed chunk height; unset: chosen per kernel instance from its resident wave slots
-  auto plan = [&](const void* kernel, int block_threads) {
-    rpc = tuning("sw_rows", -1);
-    if (rpc <= 0) {
-      const long slots = sw_wave_slots(kernel, block_threads);
-      rpc = slots > 0 ? sw_pick_rows(nrows, strips, depth, slots) : 64;
-    }
-    if (rpc > nrows) rpc = nrows;
-    n_waves = strips * ((nrows + rpc - 1) / rpc);
-    if (second_begin >= 0) rpc = nrows, n_waves = 2 * strips;  // one chunk per range
+  // the chunk plan of a kernel instance (sw_plan); two row ranges: one chunk per range
+  auto plan = [&](auto* kernel, int block_threads, int n_strips, int plan_depth) {
+    return second_begin >= 0 ? SwPlan{nrows, 2 * n_strips} : sw_plan(kernel, block_threads, nrows, n_strips, plan_depth);
   };
   const int chunk_stride = second_begin >= 0 ? second_begin - row_begin : 0;
   const int row_end_k = second_begin >= 0 ? second_begin + nrows : row_end;  // the kernel clips chunks at this row
-  if (walls) {  // wall-carrying variant: 2-wave blocks only (no register cap: 4-wave blocks, capped at
+  if (a.walls) {  // wall-carrying variant: 2-wave blocks only (no register cap: 4-wave blocks, capped at
                 // 168 / 256 VGPRs, spill up to 1300 registers with the fix-ups in)
 #define LBM_SWBC(DV)                                                                              \
   if (depth == DV) {                                                                              \
@@ -403,17 +430,13 @@ int launch_stream_collide_sw(const char* fn, double* pn, const double* po, const
     const int pw = tuning("sw_pair", 0);
     if ((pw == 2 || pw == 4) && depth == 5 && nt && g.C >= 256) {
       const int GW = swp_group_width(5, pw), groups = (g.C + GW - 1) / GW;
-      int rows = tuning("sw_rows", -1);
-      if (second_begin >= 0) rows = nrows;
-      else if (rows <= 0) {
-        const long slots = pw == 2 ? sw_wave_slots((const void*)k_stream_collide_swp<Model, 5, 2, true>, 128)
-                                   : sw_wave_slots((const void*)k_stream_collide_swp<Model, 5, 4, true>, 256);
-        rows = slots > 0 ? sw_pick_rows(nrows, groups * pw, 7, slots) : 64;  // 12 pipeline rows per chunk ~ depth 7
-      }
-      if (rows > nrows) rows = nrows;
-      const int chunks = second_begin >= 0 ? 2 : (nrows + rows - 1) / rows, total = groups * chunks;
-      if (pw == 2) LBM_KLAUNCH((k_stream_collide_swp<Model, 5, 2, true>), dim3(total), dim3(128), 0, st, pn, po, g, m, row_begin, row_end_k, rows, groups, total, chunk_stride);
-      else LBM_KLAUNCH((k_stream_collide_swp<Model, 5, 4, true>), dim3(total), dim3(256), 0, st, pn, po, g, m, row_begin, row_end_k, rows, groups, total, chunk_stride);
+      auto launch = [&](auto pw_c) {
+        constexpr int PW = decltype(pw_c)::value;
+        const SwPlan p = plan(k_stream_collide_swp<Model, 5, PW, true>, 64 * PW, groups * PW, 7);  // 12 pipeline rows per chunk ~ depth 7
+        const int total = p.n_waves / PW;
+        LBM_KLAUNCH((k_stream_collide_swp<Model, 5, PW, true>), dim3(total), dim3(64 * PW), 0, st, pn, po, g, m, row_begin, row_end_k, p.rpc, groups, total, chunk_stride);
+      };
+      if (pw == 4) launch(std::integral_constant<int, 4>{}); else launch(std::integral_constant<int, 2>{});
       launched = true;
     }
   }
@@ -422,25 +445,20 @@ int launch_stream_collide_sw(const char* fn, double* pn, const double* po, const
     if (!launched && tuning("sw_cols2", 0) && (depth == 5 || depth == 6) && nt && g.C % 2 == 0 && g.P % 2 == 0 && g.plane % 2 == 0 &&
         ((uintptr_t)pn % 16) == 0 && ((uintptr_t)po % 16) == 0) {
       const int W2 = sw2_strip_width(depth), strips2 = (g.C + W2 - 1) / W2;
-      int rows = tuning("sw_rows", -1);
-      const void* kp = depth == 5 ? (const void*)k_stream_collide_sw2<Model, 5, true> : (const void*)k_stream_collide_sw2<Model, 6, true>;
-      if (second_begin >= 0) rows = nrows;
-      else if (rows <= 0) {
-        const long slots = sw_wave_slots(kp, 128);
-        rows = slots > 0 ? sw_pick_rows(nrows, strips2, depth, slots) : 64;
-      }
-      if (rows > nrows) rows = nrows;
-      const int nw = second_begin >= 0 ? 2 * strips2 : strips2 * ((nrows + rows - 1) / rows);
-      if (depth == 5) LBM_KLAUNCH((k_stream_collide_sw2<Model, 5, true>), dim3((nw + 1) / 2), dim3(128), 0, st, pn, po, g, m, row_begin, row_end_k, rows, strips2, nw, chunk_stride);
-      else LBM_KLAUNCH((k_stream_collide_sw2<Model, 6, true>), dim3((nw + 1) / 2), dim3(128), 0, st, pn, po, g, m, row_begin, row_end_k, rows, strips2, nw, chunk_stride);
+      auto launch = [&](auto depth_c) {
+        constexpr int DV = decltype(depth_c)::value;
+        const SwPlan p = plan(k_stream_collide_sw2<Model, DV, true>, 128, strips2, depth);
+        LBM_KLAUNCH((k_stream_collide_sw2<Model, DV, true>), dim3((p.n_waves + 1) / 2), dim3(128), 0, st, pn, po, g, m, row_begin, row_end_k, p.rpc, strips2, p.n_waves, chunk_stride);
+      };
+      if (depth == 6) launch(std::integral_constant<int, 6>{}); else launch(std::integral_constant<int, 5>{});
       launched = true;
     }
   }
   if constexpr (std::is_same<Model, BgkFastModel>::value) {
     if (!launched && tuning("sw_pf2", 0) && depth == 5 && waves == 2 && nt) {  // level-1 rows prefetched two iterations ahead
-      plan((const void*)k_stream_collide_sw<Model, 5, 2, true, false, true>, 128);
-      LBM_KLAUNCH((k_stream_collide_sw<Model, 5, 2, true, false, true>), dim3((n_waves + 1) / 2), dim3(128), 0, st, pn, po, g, m,
-                  row_begin, row_end_k, rpc, strips, n_waves, tuning("sw_xcd", 0), Bc{}, 0, chunk_stride);
+      const SwPlan p = plan(k_stream_collide_sw<Model, 5, 2, true, false, true>, 128, strips, depth);
+      LBM_KLAUNCH((k_stream_collide_sw<Model, 5, 2, true, false, true>), dim3((p.n_waves + 1) / 2), dim3(128), 0, st, pn, po, g, m,
+                  row_begin, row_end_k, p.rpc, strips, p.n_waves, tuning("sw_xcd", 0), Bc{}, 0, chunk_stride);
       launched = true;
     }
   }
@@ -455,10 +473,11 @@ int launch_stream_collide_sw(const char* fn, double* pn, const double* po, const
   if (!launched) {
 #define LBM_SW(DV, WV)                                                                            \
   if (depth == DV && waves == WV) {                                                               \
-    plan((const void*)k_stream_collide_sw<Model, DV, WV, true>, 64 * WV);                         \
-    const dim3 grid((n_waves + WV - 1) / WV);                                                     \
-    if (nt) LBM_KLAUNCH((k_stream_collide_sw<Model, DV, WV, true>), grid, dim3(64 * WV), 0, st, pn, po, g, m, row_begin, row_end_k, rpc, strips, n_waves, tuning("sw_xcd", 0), Bc{}, 0, chunk_stride); \
-    else LBM_KLAUNCH((k_stream_collide_sw<Model, DV, WV, false>), grid, dim3(64 * WV), 0, st, pn, po, g, m, row_begin, row_end_k, rpc, strips, n_waves, tuning("sw_xcd", 0), Bc{}, 0, chunk_stride);   \
+    const SwPlan p = plan(k_stream_collide_sw<Model, DV, WV, true>, 64 * WV, strips, depth);      \
+    with_flags([&](auto NS) {                                                                     \
+      LBM_KLAUNCH((k_stream_collide_sw<Model, DV, WV, NS()>), dim3((p.n_waves + WV - 1) / WV), dim3(64 * WV), 0, st, pn, po, \
+                  g, m, row_begin, row_end_k, p.rpc, strips, p.n_waves, tuning("sw_xcd", 0), Bc{}, 0, chunk_stride); \
+    }, nt);                                                                                       \
   } else
   LBM_SW(2, 4) LBM_SW(3, 4) LBM_SW(4, 4) LBM_SW(5, 4) LBM_SW(6, 4)
   LBM_SW(2, 1) LBM_SW(3, 1) LBM_SW(4, 1) LBM_SW(2, 2) LBM_SW(3, 2) LBM_SW(4, 2) LBM_SW(5, 2) LBM_SW(6, 2) {
@@ -483,8 +502,7 @@ int launch_collide_only(const char* fn, double* p, const double* f, const lbm_ge
   const Bc bc = make_bc(lbc);
   const long n = (long)g.R * g.C;
   const int grid = capped_grid((n + 255) / 256);
-  if (rho) LBM_KLAUNCH((k_generic_collide<Model, false, true>), dim3(grid), dim3(256), 0, st, p, f, g, bc, m, 0, g.R, rho, u);
-  else LBM_KLAUNCH((k_generic_collide<Model, false, false>), dim3(grid), dim3(256), 0, st, p, f, g, bc, m, 0, g.R, rho, u);
+  with_flags([&](auto M) { LBM_KLAUNCH((k_generic_collide<Model, false, M()>), dim3(grid), dim3(256), 0, st, p, f, g, bc, m, 0, g.R, rho, u); }, rho != nullptr);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
