@@ -154,12 +154,16 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
 #endif
   // the frame (3-4 % of the tiles, latency-bound: 63 us on its own) goes FIRST and on the helper stream, so
   // that it runs beside the inner launch instead of behind it (fork / join through two events, launch.hpp)
-  SwSideStream* sd = !part && frame > 0 && tuning("cg_frame_beside", 1) ? sw_side_stream() : nullptr;
-  hipStream_t fs = st;
-  if (sd && hipEventRecord(sd->fork, st) == hipSuccess && hipStreamWaitEvent(sd->st, sd->fork, 0) == hipSuccess) fs = sd->st;
+  SideStream* sd = !part && frame > 0 && tuning("cg_frame_beside", 1) ? sw_side_stream() : nullptr;
+  if (sd && !sd->try_fork(st)) sd = nullptr;
+  hipStream_t fs = sd ? sd->st : st;
+  auto launched = [&]() -> int {  // the last launch's status; main waits for the helper stream whatever it is
+    LBM_CHECK_LAUNCH();
+    return LBM_OK;
+  };
   if (frame > 0 && part != 2) {
     with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, PSI(), 2>), dim3(frame), dim3(TR * TC), 0, fs, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, 0, rc); }, fields);
-    LBM_CHECK_LAUNCH();
+    if (const int e = launched()) return sd ? sd->join(st, e) : e;
   }
   if (part == 1) return LBM_OK;
   const int sw4 = (n_btr || (g.P != g.C && tuning("cg_strip2", 0) < 41)) ? 0 : tuning("cg_strip2", 0);  // (the strip forms of the experiments build know dense rows only)
@@ -309,12 +313,8 @@ static int launch_cg_fused_t(double* pn_r, double* pn_b, const double* in_r, con
   } else
 #endif  // LBM_EXPERIMENTS (strip kernels)
   with_flags([&](auto PSI) { LBM_KLAUNCH((k_cg_fused<TR, TC, WAVES, PSI(), 1>), dim3(inner), dim3(TR * TC), 0, st, pn_r, pn_b, in_r, in_b, g, bc, cf, rho_r, rho_b, u, psi, snu, mi, row_begin, row_end, xs, rc); }, fields);
-  LBM_CHECK_LAUNCH();
-  if (fs != st) {
-    LBM_CHECK_HIP(hipEventRecord(sd->join, fs));
-    LBM_CHECK_HIP(hipStreamWaitEvent(st, sd->join, 0));
-  }
-  return LBM_OK;
+  const int e = launched();
+  return sd ? sd->join(st, e) : e;
 }
 
 #ifdef LBM_EXPERIMENTS
@@ -481,8 +481,7 @@ struct lbm_cg_solver {
   double* rband[2][2];  // [buffer][colour]
   double* cband[2][2];
   lbm_geom rbg, cbg;
-  hipStream_t band_st;
-  hipEvent_t ev_band_fork, ev_band_join;
+  SideStream band_side;
   long pair_launches;
 };
 #ifdef LBM_EXPERIMENTS
@@ -509,8 +508,6 @@ int lbm_cg_solver_create(lbm_cg_solver** out, const lbm_geom* g, const lbm_bc* b
   sv->post = false;
   sv->steps = 0;
   sv->pair_launches = 0;
-  sv->band_st = nullptr;
-  sv->ev_band_fork = sv->ev_band_join = nullptr;
   for (int b = 0; b < 2; ++b)
     for (int k = 0; k < 2; ++k) sv->rband[b][k] = sv->cband[b][k] = nullptr;
   const size_t n = (size_t)g->R * g->C;
@@ -540,16 +537,11 @@ int lbm_cg_solver_create(lbm_cg_solver** out, const lbm_geom* g, const lbm_bc* b
 
 int lbm_cg_solver_destroy(lbm_cg_solver* sv) {
   if (!sv) return LBM_OK;
+  sv->band_side.destroy();
   for (double* p : {sv->lat[0][0], sv->lat[0][1], sv->lat[1][0], sv->lat[1][1], sv->rho_r, sv->rho_b,
                     sv->u, sv->psi, sv->snu, sv->stage, sv->rband[0][0], sv->rband[0][1], sv->rband[1][0], sv->rband[1][1],
                     sv->cband[0][0], sv->cband[0][1], sv->cband[1][0], sv->cband[1][1]})
     if (p) (void)hipFree(p);
-  if (sv->band_st) {
-    (void)hipStreamSynchronize(sv->band_st);
-    (void)hipStreamDestroy(sv->band_st);
-  }
-  if (sv->ev_band_fork) (void)hipEventDestroy(sv->ev_band_fork);
-  if (sv->ev_band_join) (void)hipEventDestroy(sv->ev_band_join);
   delete sv;
   return LBM_OK;
 }
@@ -594,7 +586,7 @@ static bool cg_two_step_applies(const lbm_cg_solver* sv) {
 }
 
 static int cg_two_step_prepare(lbm_cg_solver* sv) {
-  if (sv->band_st) return LBM_OK;
+  if (sv->band_side) return LBM_OK;
   const int R = sv->g.R, C = sv->g.C;
   sv->rbg = lbm_geom{2 * kCgX2HB, C, 0, (long long)2 * kCgX2HB * C + 1088};
   sv->cbg = lbm_geom{R, 2 * kCgX2WB, 0, (long long)R * 2 * kCgX2WB + 1088};
@@ -603,10 +595,7 @@ static int cg_two_step_prepare(lbm_cg_solver* sv) {
       LBM_CHECK_HIP(hipMalloc(&sv->rband[b][k], (size_t)sv->rbg.plane_stride * 9 * sizeof(double)));
       LBM_CHECK_HIP(hipMalloc(&sv->cband[b][k], (size_t)sv->cbg.plane_stride * 9 * sizeof(double)));
     }
-  LBM_CHECK_HIP(hipEventCreateWithFlags(&sv->ev_band_fork, hipEventDisableTiming));
-  LBM_CHECK_HIP(hipEventCreateWithFlags(&sv->ev_band_join, hipEventDisableTiming));
-  LBM_CHECK_HIP(hipStreamCreateWithFlags(&sv->band_st, hipStreamNonBlocking));
-  return LBM_OK;
+  return sv->band_side.create();
 }
 
 static int cg_solver_step2(lbm_cg_solver* sv) {
@@ -615,9 +604,9 @@ static int cg_solver_step2(lbm_cg_solver* sv) {
   const int R = sv->g.R, C = sv->g.C, HB = kCgX2HB, WB = kCgX2WB;
   double** src = sv->lat[sv->cur];
   double** dst = sv->lat[sv->cur ^ 1];
-  hipStream_t st = sv->st, bs = sv->band_st;
-  LBM_CHECK_HIP(hipEventRecord(sv->ev_band_fork, st));
-  LBM_CHECK_HIP(hipStreamWaitEvent(bs, sv->ev_band_fork, 0));
+  hipStream_t st = sv->st, bs = sv->band_side.st;
+  rc = sv->band_side.fork(st);
+  if (rc) return rc;
   // ---- the frame: copy in, two single steps, on the helper stream ----
   for (int k = 0; k < 2 && !rc; ++k) {
     rc = box_copy(sv->rband[0][k], sv->rbg, 0, 0, src[k], sv->g, 0, 0, HB, C, bs);
@@ -631,7 +620,7 @@ static int cg_solver_step2(lbm_cg_solver* sv) {
     if (!rc) rc = lbm_cg_step_fused(sv->cband[t ^ 1][0], sv->cband[t ^ 1][1], sv->cband[t][0], sv->cband[t][1], &sv->cbg, &sv->bc, &sv->prm,
                                     0, R, nullptr, nullptr, nullptr, nullptr, nullptr, bs);
   }
-  if (rc) return rc;
+  if (rc) return sv->band_side.join(st, rc);
   // ---- the inner rectangle: two steps in one pass, on the caller's stream ----
   {
     constexpr int Wv = 4, S = 64 * Wv - 2 * CG_X2_EDGE;
@@ -653,11 +642,14 @@ static int cg_solver_step2(lbm_cg_solver* sv) {
 #define LBM_CG_X2(M) LBM_KLAUNCH((k_cg_two_step<Wv, M>), dim3(bstrips * chunks), dim3(64 * Wv), 0, st, dst[0], dst[1], src[0], src[1], g, cf, ra, rb, ca, cb, rpc, bstrips, win0)
     if (mode == 0) LBM_CG_X2(0); else if (mode == 1) LBM_CG_X2(1); else if (mode == 2) LBM_CG_X2(2); else LBM_CG_X2(3);
 #undef LBM_CG_X2
-    LBM_CHECK_LAUNCH();
+    rc = [&]() -> int {
+      LBM_CHECK_LAUNCH();
+      return LBM_OK;
+    }();
   }
   // ---- the frame's valid part into the new lattice (behind the big launch: the regions are disjoint, but one stream writes) ----
-  LBM_CHECK_HIP(hipEventRecord(sv->ev_band_join, bs));
-  LBM_CHECK_HIP(hipStreamWaitEvent(st, sv->ev_band_join, 0));
+  rc = sv->band_side.join(st, rc);
+  if (rc) return rc;
   for (int k = 0; k < 2 && !rc; ++k) {
     rc = box_copy(dst[k], sv->g, 0, 0, sv->rband[0][k], sv->rbg, 0, 0, kCgX2RowBand, C, st);
     if (!rc) rc = box_copy(dst[k], sv->g, R - kCgX2RowBand, 0, sv->rband[0][k], sv->rbg, 2 * HB - kCgX2RowBand, 0, kCgX2RowBand, C, st);

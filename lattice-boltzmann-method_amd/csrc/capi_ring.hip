@@ -19,7 +19,7 @@
 #include "d2q9.hpp"
 #include "internal.hpp"
 #include "ring_ipc.hpp"
-#include "slab_ibm.hpp"
+#include "slab.hpp"
 
 namespace {
 
@@ -100,9 +100,8 @@ struct lbm_ring {
   int skipped;                   // launches without an exchange since the last one (their ghost rows are used up)
   int rank, nranks, next, prev;  // neighbours, -1 = none (chain end)
   lbm_geom g;                    // slab geometry (ghost = halo depth)
-  hipStream_t edge;              // edge rows, pack, send/recv, unpack
-  hipStream_t aux;               // immersed-boundary rows + forcing chain (created on first use)
-  hipEvent_t main_done, edge_done, aux_done;
+  lbm::SideStream edge;              // edge rows, pack, send/recv, unpack: forked off / joined into the caller's stream
+  lbm::SideStream aux;              // immersed-boundary rows + forcing chain (created on first use)
   double *send_next, *send_prev, *recv_prev, *recv_next;
   // lbm_ring_profile(1): timed events around the three phases of the last launch-step
   int closed;                    // periodic ring (every rank has both neighbours), not a chain with two ends
@@ -126,36 +125,22 @@ static int default_transport() {
 static int ring_transfer(lbm_ring* rg, const double* send_prev, size_t n_send_prev, double* recv_prev, size_t n_recv_prev,
                          const double* send_next, size_t n_send_next, double* recv_next, size_t n_recv_next) {
   if (rg->transport == LBM_RING_IPC)
-    return ipc_sendrecv(rg->ipc, send_prev, n_send_prev, recv_prev, n_recv_prev, send_next, n_send_next, recv_next, n_recv_next, rg->edge);
+    return ipc_sendrecv(rg->ipc, send_prev, n_send_prev, recv_prev, n_recv_prev, send_next, n_send_next, recv_next, n_recv_next, rg->edge.st);
   LBM_CHECK_NCCL(g_rccl.GroupStart());
   // sends (to next, to prev), receives (from prev, from next): with two ranks both neighbours
   // are the same peer and messages match in issue order
-  if (rg->next >= 0 && n_send_next) LBM_CHECK_NCCL(g_rccl.Send(send_next, n_send_next, kNcclFloat64, rg->next, rg->comm, rg->edge));
-  if (rg->prev >= 0 && n_send_prev) LBM_CHECK_NCCL(g_rccl.Send(send_prev, n_send_prev, kNcclFloat64, rg->prev, rg->comm, rg->edge));
-  if (rg->prev >= 0 && n_recv_prev) LBM_CHECK_NCCL(g_rccl.Recv(recv_prev, n_recv_prev, kNcclFloat64, rg->prev, rg->comm, rg->edge));
-  if (rg->next >= 0 && n_recv_next) LBM_CHECK_NCCL(g_rccl.Recv(recv_next, n_recv_next, kNcclFloat64, rg->next, rg->comm, rg->edge));
+  if (rg->next >= 0 && n_send_next) LBM_CHECK_NCCL(g_rccl.Send(send_next, n_send_next, kNcclFloat64, rg->next, rg->comm, rg->edge.st));
+  if (rg->prev >= 0 && n_send_prev) LBM_CHECK_NCCL(g_rccl.Send(send_prev, n_send_prev, kNcclFloat64, rg->prev, rg->comm, rg->edge.st));
+  if (rg->prev >= 0 && n_recv_prev) LBM_CHECK_NCCL(g_rccl.Recv(recv_prev, n_recv_prev, kNcclFloat64, rg->prev, rg->comm, rg->edge.st));
+  if (rg->next >= 0 && n_recv_next) LBM_CHECK_NCCL(g_rccl.Recv(recv_next, n_recv_next, kNcclFloat64, rg->next, rg->comm, rg->edge.st));
   LBM_CHECK_NCCL(g_rccl.GroupEnd());
   return LBM_OK;
 }
 
 // the ring's stream starts after everything enqueued on `main` so far
-static int ring_fork(lbm_ring* rg, hipStream_t main) {
-  LBM_CHECK_HIP(hipEventRecord(rg->main_done, main));
-  LBM_CHECK_HIP(hipStreamWaitEvent(rg->edge, rg->main_done, 0));
-  return LBM_OK;
-}
-
-// make `main` wait for the ring's stream.  rc != 0: the caller failed after its fork; the join is enqueued all the same
-// (nothing left on the ring's stream runs unordered against main's next use of the buffers) and rc is what returns
-static int ring_join(lbm_ring* rg, hipStream_t main, int rc = LBM_OK) {
-  if (rc) {
-    if (hipEventRecord(rg->edge_done, rg->edge) == hipSuccess) (void)hipStreamWaitEvent(main, rg->edge_done, 0);
-    return rc;
-  }
-  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
-  LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
-  return LBM_OK;
-}
+static int ring_fork(lbm_ring* rg, hipStream_t main) { return rg->edge.fork(main); }
+// make `main` wait for the ring's stream; rc != 0 (the caller failed after its fork): joined all the same, rc returns
+static int ring_join(lbm_ring* rg, hipStream_t main, int rc = LBM_OK) { return rg->edge.join(main, rc); }
 
 // Bring the ghost rows of one or two lattices up to date with halo depth code G (lbm_halo_rows: 1..15,
 // LBM_HALO_FULL(d), LBM_HALO_TWO_PHASE): pack, one send + one recv per neighbour carrying every lattice back to back,
@@ -165,7 +150,7 @@ static int ring_exchange_depth(lbm_ring* rg, double* lattice, double* lattice2, 
   LBM_REQUIRE(msg * (lattice2 ? 2 : 1) <= rg->bufsz, "lbm_ring: message of %zu doubles, buffers of %zu", msg * (lattice2 ? 2 : 1), rg->bufsz);
   rg->valid = G == LBM_HALO_TWO_PHASE ? 3 : (G >= 100 ? G - 100 : G);  // these ghost rows are current again
   rg->skipped = 0;
-  if (as_stream(after) != rg->edge) {
+  if (as_stream(after) != rg->edge.st) {
     int rc = ring_fork(rg, as_stream(after));
     if (rc) return rc;
   }
@@ -174,11 +159,11 @@ static int ring_exchange_depth(lbm_ring* rg, double* lattice, double* lattice2, 
   const size_t count = msg * nl;
   for (int k = 0; k < nl; ++k) {
     if (rg->next >= 0) {
-      int rc = lbm_halo_pack(rg->send_next + k * msg, lats[k], &rg->g, G, 1, rg->edge);
+      int rc = lbm_halo_pack(rg->send_next + k * msg, lats[k], &rg->g, G, 1, rg->edge.st);
       if (rc) return rc;
     }
     if (rg->prev >= 0) {
-      int rc = lbm_halo_pack(rg->send_prev + k * msg, lats[k], &rg->g, G, 0, rg->edge);
+      int rc = lbm_halo_pack(rg->send_prev + k * msg, lats[k], &rg->g, G, 0, rg->edge.st);
       if (rc) return rc;
     }
   }
@@ -189,11 +174,11 @@ static int ring_exchange_depth(lbm_ring* rg, double* lattice, double* lattice2, 
   }
   for (int k = 0; k < nl; ++k) {
     if (rg->prev >= 0) {
-      int rc = lbm_halo_unpack(lats[k], rg->recv_prev + k * msg, &rg->g, G, 0, rg->edge);
+      int rc = lbm_halo_unpack(lats[k], rg->recv_prev + k * msg, &rg->g, G, 0, rg->edge.st);
       if (rc) return rc;
     }
     if (rg->next >= 0) {
-      int rc = lbm_halo_unpack(lats[k], rg->recv_next + k * msg, &rg->g, G, 1, rg->edge);
+      int rc = lbm_halo_unpack(lats[k], rg->recv_next + k * msg, &rg->g, G, 1, rg->edge.st);
       if (rc) return rc;
     }
   }
@@ -245,19 +230,19 @@ static int ring_step(lbm_ring* rg, hipStream_t main, Edges&& edges, Interior&& i
   if (int rc = ring_fork(rg, main)) return rc;
   auto overlapped = [&]() -> int {
     const bool prof = rg->profile != 0;
-    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_edge0, rg->edge));
-    int rc = edges(rg->edge);
+    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_edge0, rg->edge.st));
+    int rc = edges(rg->edge.st);
     if (rc) return rc;
     if (prof) {
-      LBM_CHECK_HIP(hipEventRecord(rg->t_edge1, rg->edge));
+      LBM_CHECK_HIP(hipEventRecord(rg->t_edge1, rg->edge.st));
       LBM_CHECK_HIP(hipEventRecord(rg->t_main0, main));
     }
     rc = interior(main);  // overlaps the exchange
     if (rc) return rc;
     if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_main1, main));
-    rc = ring_exchange_depth(rg, dst, dst2, G, rg->edge);
+    rc = ring_exchange_depth(rg, dst, dst2, G, rg->edge.st);
     if (rc) return rc;
-    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_xchg1, rg->edge));
+    if (prof) LBM_CHECK_HIP(hipEventRecord(rg->t_xchg1, rg->edge.st));
     return LBM_OK;
   };
   return ring_join(rg, main, overlapped());
@@ -446,7 +431,7 @@ static int ring_pressure_start(lbm_ring* rg, lbm_slab_pressure* sl, double* post
   }
   // the start-up buffers are freed below: nothing enqueued on them may still be running -- on the error paths too
   hipError_t es = hipStreamSynchronize(main);
-  if (es == hipSuccess && rg->edge) es = hipStreamSynchronize(rg->edge);
+  if (es == hipSuccess && rg->edge.st) es = hipStreamSynchronize(rg->edge.st);
   if (!rc && es != hipSuccess) {
     set_error("lbm_ring_pressure_start: stream synchronisation failed");
     rc = LBM_ERR_HIP;
@@ -492,7 +477,6 @@ int lbm_ring_create_ex(lbm_ring** out, const unsigned char* id128, int rank, int
   }
   lbm_ring* rg = new (std::nothrow) lbm_ring();
   LBM_REQUIRE(rg, "lbm_ring_create: out of host memory");
-  std::memset(rg, 0, sizeof *rg);
   rg->transport = transport;
   rg->rank = rank;
   rg->nranks = nranks;
@@ -522,13 +506,12 @@ int lbm_ring_create_ex(lbm_ring** out, const unsigned char* id128, int rank, int
   }
   int lo = 0, hi = 0;
   hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-  if (e == hipSuccess) e = hipStreamCreateWithPriority(&rg->edge, hipStreamNonBlocking, hi);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&rg->main_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&rg->edge_done, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipStreamCreateWithPriority(&rg->edge.st, hipStreamNonBlocking, hi);
+  const int rc_ev = e == hipSuccess ? rg->edge.create_events() : LBM_OK;
   for (double** p : {&rg->send_next, &rg->send_prev, &rg->recv_prev, &rg->recv_next})
     if (e == hipSuccess) e = hipMalloc(p, bufsz * sizeof(double));
-  if (e != hipSuccess) {
-    set_error("lbm_ring_create: %s", hipGetErrorString(e));
+  if (e != hipSuccess) set_error("lbm_ring_create: %s", hipGetErrorString(e));
+  if (e != hipSuccess || rc_ev) {
     lbm_ring_destroy(rg);
     return LBM_ERR_HIP;
   }
@@ -576,19 +559,13 @@ int lbm_ring_window_cached(const lbm_ring* rg) { return rg && rg->ipc ? ipc_wind
 
 int lbm_ring_destroy(lbm_ring* rg) {
   if (!rg) return LBM_OK;
-  if (rg->edge) (void)hipStreamSynchronize(rg->edge);
+  if (rg->edge.st) (void)hipStreamSynchronize(rg->edge.st);
   for (double* p : {rg->send_next, rg->send_prev, rg->recv_prev, rg->recv_next})
     if (p) (void)hipFree(p);
-  if (rg->main_done) (void)hipEventDestroy(rg->main_done);
-  if (rg->edge_done) (void)hipEventDestroy(rg->edge_done);
-  if (rg->aux_done) (void)hipEventDestroy(rg->aux_done);
   for (hipEvent_t ev : {rg->t_edge0, rg->t_edge1, rg->t_xchg1, rg->t_main0, rg->t_main1})
     if (ev) (void)hipEventDestroy(ev);
-  if (rg->aux) {
-    (void)hipStreamSynchronize(rg->aux);
-    (void)hipStreamDestroy(rg->aux);
-  }
-  if (rg->edge) (void)hipStreamDestroy(rg->edge);
+  rg->aux.destroy();
+  rg->edge.destroy();
   // a communicator with an asynchronous error is aborted: ncclCommDestroy would wait for its outstanding operations
   if (rg->comm && rg->rccl_failed && g_rccl.CommAbort) (void)g_rccl.CommAbort(rg->comm);
   else if (rg->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(rg->comm);
@@ -748,8 +725,12 @@ int lbm_ring_bgk_step_ibm(lbm_ring* rg, double* dst, const double* src, const lb
     if (!rg->aux) {
       int lo = 0, hi = 0;
       LBM_CHECK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      LBM_CHECK_HIP(hipStreamCreateWithPriority(&rg->aux, hipStreamNonBlocking, hi));
-      LBM_CHECK_HIP(hipEventCreateWithFlags(&rg->aux_done, hipEventDisableTiming));
+      LBM_CHECK_HIP(hipStreamCreateWithPriority(&rg->aux.st, hipStreamNonBlocking, hi));
+      rc = rg->aux.create_events();
+      if (rc) {
+        rg->aux.destroy();
+        return rc;
+      }
     }
   }
   auto rows = [&](int r0, int r1, bool mom, hipStream_t st) -> int {
@@ -765,23 +746,18 @@ int lbm_ring_bgk_step_ibm(lbm_ring* rg, double* dst, const double* src, const lb
   };
   rc = ring_fork(rg, main);
   if (rc) return rc;
-  rc = rows_outside_roi(0, edge_rows, rg->edge);
-  if (!rc) rc = rows_outside_roi(R - edge_rows, R, rg->edge);
-  if (!rc) rc = ring_exchange(rg, dst, nullptr, rg->edge);
-  if (rc) return ring_join(rg, main, rc);
-  LBM_CHECK_HIP(hipEventRecord(rg->edge_done, rg->edge));
   if (ib) {
-    LBM_CHECK_HIP(hipStreamWaitEvent(rg->aux, rg->main_done, 0));
-    rc = rows(q0, q1, true, rg->aux);
-    if (!rc) rc = lbm_ibm_step(ib, dst, &rg->g, u, rho, prm->omega, guo_a, guo_b, rg->aux);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipEventRecord(rg->aux_done, rg->aux));
+    rc = rg->aux.fork(main);
+    if (rc) return ring_join(rg, main, rc);
   }
-  rc = rows_outside_roi(edge_rows, R - edge_rows, main);
-  if (rc) return rc;
-  LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->edge_done, 0));
-  if (ib) LBM_CHECK_HIP(hipStreamWaitEvent(main, rg->aux_done, 0));
-  return LBM_OK;
+  rc = rows_outside_roi(0, edge_rows, rg->edge.st);
+  if (!rc) rc = rows_outside_roi(R - edge_rows, R, rg->edge.st);
+  if (!rc) rc = ring_exchange(rg, dst, nullptr, rg->edge.st);
+  if (!rc && ib) rc = rows(q0, q1, true, rg->aux.st);
+  if (!rc && ib) rc = lbm_ibm_step(ib, dst, &rg->g, u, rho, prm->omega, guo_a, guo_b, rg->aux.st);
+  if (!rc) rc = rows_outside_roi(edge_rows, R - edge_rows, main);
+  if (ib) rc = rg->aux.join(main, rc);
+  return ring_join(rg, main, rc);
 }
 
 // Phase timing of launch-steps (diagnosis of a scaling run): on = 1 makes every overlapped launch-step (ring_step:

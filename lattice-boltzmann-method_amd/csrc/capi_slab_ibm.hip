@@ -21,19 +21,11 @@
 #include <cstring>
 #include <new>
 
+#include "blocks.hpp"
 #include "d2q9.hpp"
-#include "internal.hpp"
-#include "slab_ibm.hpp"
+#include "slab.hpp"
 
 using namespace lbm;
-
-namespace {
-inline long long plane_of(const lbm_geom& g) {
-  return g.plane_stride > 0 ? g.plane_stride : (long long)(g.R + 2 * g.ghost) * g.C;
-}
-// a message buffer of n rows viewed as a dense lattice [9][n][C]
-inline lbm_geom msg_geom(int n, int C) { return lbm_geom{n, C, 0, (long long)n * C}; }
-}  // namespace
 
 extern "C" {
 
@@ -56,16 +48,8 @@ int lbm_rows_copy(double* dst, const lbm_geom* dg, int dst_row, const double* sr
 
 int lbm_slab_ibm_destroy(lbm_slab_ibm* sl) {
   if (!sl) return LBM_OK;
-  if (sl->aux) {
-    (void)hipStreamSynchronize(sl->aux);
-    (void)hipStreamDestroy(sl->aux);
-  }
-  if (sl->bgst) {
-    (void)hipStreamSynchronize(sl->bgst);
-    (void)hipStreamDestroy(sl->bgst);
-  }
-  if (sl->ev_fork) (void)hipEventDestroy(sl->ev_fork);
-  if (sl->ev_join) (void)hipEventDestroy(sl->ev_join);
+  sl->aux.destroy();
+  sl->bg_side.destroy();
   if (sl->ib) (void)lbm_ibm_destroy(sl->ib);
   for (double* p : {sl->blat[0], sl->blat[1], sl->brho, sl->bu, sl->stash, sl->box[0], sl->box[1], sl->xrho, sl->xu})
     if (p) (void)hipFree(p);
@@ -93,7 +77,6 @@ int lbm_slab_ibm_create(lbm_slab_ibm** out, const lbm_geom* slab, int slab_row0,
   }
   lbm_slab_ibm* sl = new (std::nothrow) lbm_slab_ibm();
   LBM_REQUIRE(sl, "lbm_slab_ibm_create: out of host memory");
-  std::memset(sl, 0, sizeof *sl);
   sl->g = *slab;
   sl->row0 = slab_row0;
   sl->rows_global = rows_global;
@@ -145,12 +128,10 @@ int lbm_slab_ibm_create(lbm_slab_ibm** out, const lbm_geom* slab, int slab_row0,
   if (e == hipSuccess) e = hipMalloc(&sl->bu, 2 * n * sizeof(double));
   if (e == hipSuccess) e = hipMalloc(&sl->stash, (size_t)9 * D * C * sizeof(double));
   if (e == hipSuccess) e = hipMemset(sl->stash, 0, (size_t)9 * D * C * sizeof(double));
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&sl->aux, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&sl->ev_fork, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&sl->ev_join, hipEventDisableTiming);
+  if (e == hipSuccess) rc = sl->aux.create();
   // the forced box (lbm_slab_ibm_block_compute): only if it keeps clear of the wall columns
   int q0r, q1r, c0, c1;
-  if (e == hipSuccess && lbm_ibm_roi(sl->ib, &q0r, &q1r, &c0, &c1) == LBM_OK && c0 - 2 * D >= 8 && (c1 + 2 * D + 7) / 8 * 8 <= C - 1) {
+  if (e == hipSuccess && !rc && lbm_ibm_roi(sl->ib, &q0r, &q1r, &c0, &c1) == LBM_OK && c0 - 2 * D >= 8 && (c1 + 2 * D + 7) / 8 * 8 <= C - 1) {
     sl->bc0 = (c0 - 2 * D) / 8 * 8;
     sl->bc1 = (c1 + 2 * D + 7) / 8 * 8;
     const int Cb = sl->bc1 - sl->bc0;
@@ -162,11 +143,11 @@ int lbm_slab_ibm_create(lbm_slab_ibm** out, const lbm_geom* slab, int slab_row0,
     if (e == hipSuccess) e = hipMalloc(&sl->xu, 2 * xn * sizeof(double));
     // (ordinary priority: with the lowest one a co-owner's block took 1.15 instead of 0.70 ms in a running chain --
     // profiles/r02_cylinder_emulated_8_slabs_events.txt; one block on lbm_solver_step does not care, 75 / 96 / 119 k either way)
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&sl->bgst, hipStreamNonBlocking);
-    sl->boxed = e == hipSuccess;
+    if (e == hipSuccess) rc = sl->bg_side.create();
+    sl->boxed = e == hipSuccess && !rc;
   }
-  if (e != hipSuccess) {
-    set_error("lbm_slab_ibm_create: %s", hipGetErrorString(e));
+  if (e != hipSuccess) set_error("lbm_slab_ibm_create: %s", hipGetErrorString(e));
+  if (e != hipSuccess || rc) {
     lbm_slab_ibm_destroy(sl);
     return LBM_ERR_HIP;
   }
@@ -368,165 +349,100 @@ int lbm_slab_ibm_start_finish(lbm_slab_ibm* sl, double* post, double* pre, const
   return rc;
 }
 
+// the D outermost band rows of each side at time t into the band lattice: far rows of this slab (owned or ghost), or the
+// co-owner's from the stash
+static int slab_ibm_load_outer_rows(lbm_slab_ibm* sl, const double* src, lbm_stream_t s) {
+  const int D = sl->D, hi = sl->b1 - D;  // hi: global
+  const lbm_geom sg = msg_geom(D, sl->g.C);
+  double* bl = sl->blat[sl->bcur];
+  int rc = sl->straddle_prev ? lbm_rows_copy(bl, &sl->bg, 0, sl->stash, &sg, 0, D, s)
+                             : lbm_rows_copy(bl, &sl->bg, 0, src, &sl->g, sl->b0 - sl->row0, D, s);
+  if (rc) return rc;
+  return sl->straddle_next ? lbm_rows_copy(bl, &sl->bg, hi - sl->b0, sl->stash, &sg, 0, D, s)
+                           : lbm_rows_copy(bl, &sl->bg, hi - sl->b0, src, &sl->g, hi - sl->row0, D, s);
+}
+
 // One block, phase A: dst = D steps from src on the owned rows (band chain on the helper stream beside
 // the far rows), then both outgoing messages packed.  Ghost rows of src: complete and current.
 int lbm_slab_ibm_block_compute(lbm_slab_ibm* sl, double* dst, const double* src, double* send_prev,
                                double* send_next, lbm_stream_t s) {
   LBM_REQUIRE(sl && dst && src && dst != src, "lbm_slab_ibm_block_compute: bad argument");
   LBM_REQUIRE((!sl->has_prev || send_prev) && (!sl->has_next || send_next), "lbm_slab_ibm_block_compute: NULL send buffer");
-  const int R = sl->g.R, C = sl->g.C, D = sl->D, full = LBM_HALO_FULL(D);
+  const int R = sl->g.R, D = sl->D, Rb = sl->bg.R;
   hipStream_t st = as_stream(s);
+  const bool boxed = sl->owner && sl->boxed && tuning("ibm_box", 1);
+  const bool sole = boxed && !sl->straddle_prev && !sl->straddle_next && tuning("ibm_box_sole", 1);
   int rc = LBM_OK;
-  int o0 = R, o1 = R;  // owned rows [o0, o1) come from the band; everything else is far
-  if (sl->owner && sl->boxed && !sl->straddle_prev && !sl->straddle_next && tuning("ibm_box", 1) && tuning("ibm_box_sole", 1)) {
+  int o0 = R, o1 = R;  // owned rows [o0, o1) come from the band lattice; everything else is far
+  if (sl->owner && !sole) {
+    if (sl->blat_stale) {  // the band lattice fell behind while the slab lattice was worked on directly: all its rows are here
+      rc = lbm_rows_copy(sl->blat[sl->bcur], &sl->bg, 0, src, &sl->g, sl->b0 - sl->row0, Rb, s);
+      if (rc) return rc;
+      sl->blat_stale = false;
+    }
+    const int v0 = sl->b0 + D - sl->row0, v1 = sl->b1 - D - sl->row0;
+    o0 = v0 < 0 ? 0 : v0;
+    o1 = v1 > R ? R : v1;
+  }
+  // far rows: plain D-step window from the time-t lattice
+  auto far_rows = [&](hipStream_t on) -> int {
+    int rc = o0 > 0 ? lbm_bgk_stream_collide_xn(dst, src, &sl->g, &sl->bc, &sl->prm, D, 0, o0 < R ? o0 : R, on) : LBM_OK;
+    if (!rc && o1 < R) rc = lbm_bgk_stream_collide_xn(dst, src, &sl->g, &sl->bc, &sl->prm, D, o1, R, on);
+    return rc;
+  };
+  // my part of the valid band rows into the slab lattice
+  auto take_my_rows = [&](lbm_stream_t on) { return lbm_rows_copy(dst, &sl->g, o0, sl->blat[sl->bcur], &sl->bg, o0 + sl->row0 - sl->b0, o1 - o0, on); };
+  if (sole) {
     // SOLE owner (the whole valid band inside this slab's rows; its outer D rows at most in the ghost rows): the band
     // lattice would only mirror rows this slab holds anyway.  So, as lbm_solver_step does on one block: the box straight
     // out of the slab lattice, the D-step window over ALL owned rows beside the chain, the box ROI +- D straight back --
     // no band window launch, no copy of 300-odd full-width rows per block (31 us), one far launch instead of three.
-    const int Rb = sl->bg.R, Cb = sl->xg.C, br0 = sl->b0 - sl->row0;  // box row 0 in slab rows (>= -ghost)
-    const lbm_bc pb{LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, 0, 1.0, 1.0, 0.0, 0.0};
-    LBM_CHECK_HIP(hipEventRecord(sl->ev_fork, st));
-    rc = box_copy(sl->box[0], sl->xg, 0, 0, src, sl->g, br0, sl->bc0, Rb, Cb, st);
-    if (rc) return rc;
-    int cur = 0;
-    rc = tuning("ibm_chain_kernel", 0) ? ibm_box_chain(sl->ib, 0, sl->bc0, sl->box, &cur, &sl->xg, &sl->prm, bgk_uses_fast_model(&sl->prm, &pb), D,
-                                                       sl->xrho, sl->xu, sl->ga, sl->gb, st)
-                                       : 1;
-    if (rc < 0) return rc;
-    const bool one_launch = rc == 0;
-    LBM_CHECK_HIP(hipStreamWaitEvent(sl->bgst, sl->ev_fork, 0));
-    rc = one_launch ? ibm_gate(sl->ib, sl->bgst) : LBM_OK;
-    if (!rc) rc = lbm_bgk_stream_collide_xn(dst, src, &sl->g, &sl->bc, &sl->prm, D, 0, R, sl->bgst);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipEventRecord(sl->ev_join, sl->bgst));
-    for (int k = 1; k <= D && !one_launch && !rc; ++k) {  // cylinder_test.cpp:103-127 on the shrinking trapezoid
-      rc = lbm_bgk_stream_collide(sl->box[cur ^ 1], sl->box[cur], &sl->xg, &pb, &sl->prm, k, Rb - k, sl->xrho, sl->xu, s);
-      if (!rc) rc = ibm_step_window(sl->ib, 0, sl->bc0, sl->box[cur ^ 1], &sl->xg, sl->xu, sl->xrho, sl->prm.omega, sl->ga, sl->gb, st);
-      cur ^= 1;
-    }
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipStreamWaitEvent(st, sl->ev_join, 0));
-    rc = box_copy(dst, sl->g, br0 + D, sl->bc0 + D, sl->box[cur], sl->xg, D, D, Rb - 2 * D, Cb - 2 * D, st);
+    auto window = [&](hipStream_t on) { return lbm_bgk_stream_collide_xn(dst, src, &sl->g, &sl->bc, &sl->prm, D, 0, R, on); };
+    rc = ibm_forced_box_block(src, dst, sl->g, sl->b0 - sl->row0 /* >= -ghost */, sl->bc0, sl->box, sl->xg, sl->xrho, sl->xu, sl->ib, 0, sl->bc0,
+                              sl->prm, sl->ga, sl->gb, D, &sl->bg_side, window, st);
     if (rc) return rc;
     sl->blat_stale = true;
-    o0 = 0, o1 = R;  // (nothing left for the far launches below)
-  } else if (sl->owner && sl->boxed && tuning("ibm_box", 1)) {
-    if (sl->blat_stale) {  // the band lattice fell behind while the slab lattice was worked on directly: all its rows are here
-      rc = lbm_rows_copy(sl->blat[sl->bcur], &sl->bg, 0, src, &sl->g, sl->b0 - sl->row0, sl->bg.R, s);
-      if (rc) return rc;
-      sl->blat_stale = false;
-    }
-    // The forcing reaches a node only through the ROI, so the D forced single steps are cut to a BOX -- band rows x
-    // columns ROI +- 2 D -- held as a small periodic lattice pair of its own (what its wrap spoils is the frame that is
-    // dropped anyway), while the band as a whole takes the D-step window like any far row (unforced: right everywhere
-    // outside the box ROI +- D, which is then overwritten with the forced result).  The band lattice stays the whole
-    // band at time t / t + D on both co-owners, so nothing changes in what travels between them.  The chain of small
-    // launches stays on the caller's stream; both window launches go to a stream of their own beside it.
-    const int v0 = sl->b0 + D - sl->row0, v1 = sl->b1 - D - sl->row0;
-    o0 = v0 < 0 ? 0 : v0;
-    o1 = v1 > R ? R : v1;
+  } else if (boxed) {
+    // Co-owner (or "ibm_box_sole" = 0): the box out of the BAND lattice, while the band as a whole takes the D-step window
+    // like any far row (unforced: right everywhere outside the box ROI +- D, which is then overwritten with the forced
+    // result).  The band lattice stays the whole band at time t / t + D on both co-owners, so nothing changes in what
+    // travels between them.  The chain of small launches stays on the caller's stream; the band's window and the far rows'
+    // go to a stream of their own beside it.
+    rc = slab_ibm_load_outer_rows(sl, src, s);
+    if (rc) return rc;
     double* bl = sl->blat[sl->bcur];
     double* bn = sl->blat[sl->bcur ^ 1];
-    const lbm_geom sg = msg_geom(D, C);
-    const int Rb = sl->bg.R, Cb = sl->xg.C, hi = sl->b1 - D;  // hi: global
-    if (sl->straddle_prev) rc = lbm_rows_copy(bl, &sl->bg, 0, sl->stash, &sg, 0, D, s);
-    else rc = lbm_rows_copy(bl, &sl->bg, 0, src, &sl->g, sl->b0 - sl->row0, D, s);
-    if (rc) return rc;
-    if (sl->straddle_next) rc = lbm_rows_copy(bl, &sl->bg, hi - sl->b0, sl->stash, &sg, 0, D, s);
-    else rc = lbm_rows_copy(bl, &sl->bg, hi - sl->b0, src, &sl->g, hi - sl->row0, D, s);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipEventRecord(sl->ev_fork, st));
-    const lbm_bc pb{LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, 0, 1.0, 1.0, 0.0, 0.0};
-    rc = box_copy(sl->box[0], sl->xg, 0, 0, bl, sl->bg, 0, sl->bc0, Rb, Cb, st);
-    if (rc) return rc;
-    int cur = 0;
-    // "ibm_chain_kernel" = 1 (opt-in, level with the default): the chain as ONE launch on compute units of its own
-    // (lbm::ibm_box_chain), the window launches held back until its workgroups are resident
-    rc = tuning("ibm_chain_kernel", 0) ? ibm_box_chain(sl->ib, 0, sl->bc0, sl->box, &cur, &sl->xg, &sl->prm, bgk_uses_fast_model(&sl->prm, &pb), D,
-                                                       sl->xrho, sl->xu, sl->ga, sl->gb, st)
-                                       : 1;
-    if (rc < 0) return rc;
-    const bool one_launch = rc == 0;
-    LBM_CHECK_HIP(hipStreamWaitEvent(sl->bgst, sl->ev_fork, 0));
-    rc = one_launch ? ibm_gate(sl->ib, sl->bgst) : LBM_OK;
-    if (!rc) rc = lbm_bgk_stream_collide_xn(bn, bl, &sl->bg, &sl->bbc, &sl->prm, D, D, Rb - D, sl->bgst);
-    if (!rc && o0 > 0) rc = lbm_bgk_stream_collide_xn(dst, src, &sl->g, &sl->bc, &sl->prm, D, 0, o0 < R ? o0 : R, sl->bgst);
-    if (!rc && o1 < R) rc = lbm_bgk_stream_collide_xn(dst, src, &sl->g, &sl->bc, &sl->prm, D, o1, R, sl->bgst);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipEventRecord(sl->ev_join, sl->bgst));
-    for (int k = 1; k <= D && !one_launch && !rc; ++k) {  // cylinder_test.cpp:103-127 on the shrinking trapezoid
-      rc = lbm_bgk_stream_collide(sl->box[cur ^ 1], sl->box[cur], &sl->xg, &pb, &sl->prm, k, Rb - k, sl->xrho, sl->xu, s);
-      if (!rc) rc = ibm_step_window(sl->ib, 0, sl->bc0, sl->box[cur ^ 1], &sl->xg, sl->xu, sl->xrho, sl->prm.omega, sl->ga, sl->gb, st);
-      cur ^= 1;
-    }
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipStreamWaitEvent(st, sl->ev_join, 0));
-    rc = box_copy(bn, sl->bg, D, sl->bc0 + D, sl->box[cur], sl->xg, D, D, Rb - 2 * D, Cb - 2 * D, st);
-    sl->bcur ^= 1;
-    // my part of the valid rows into the slab lattice
-    if (!rc) rc = lbm_rows_copy(dst, &sl->g, o0, bn, &sl->bg, o0 + sl->row0 - sl->b0, o1 - o0, s);
+    auto windows = [&](hipStream_t on) {
+      const int rc = lbm_bgk_stream_collide_xn(bn, bl, &sl->bg, &sl->bbc, &sl->prm, D, D, Rb - D, on);
+      return rc ? rc : far_rows(on);
+    };
+    rc = ibm_forced_box_block(bl, bn, sl->bg, 0, sl->bc0, sl->box, sl->xg, sl->xrho, sl->xu, sl->ib, 0, sl->bc0, sl->prm, sl->ga, sl->gb, D,
+                              &sl->bg_side, windows, st);
+    if (!rc) sl->bcur ^= 1;
+    if (!rc) rc = take_my_rows(s);
     if (rc) return rc;
   } else if (sl->owner) {
-    if (sl->blat_stale) {
-      rc = lbm_rows_copy(sl->blat[sl->bcur], &sl->bg, 0, src, &sl->g, sl->b0 - sl->row0, sl->bg.R, s);
-      if (rc) return rc;
-      sl->blat_stale = false;
-    }
-    const int v0 = sl->b0 + D - sl->row0, v1 = sl->b1 - D - sl->row0;
-    o0 = v0 < 0 ? 0 : v0;
-    o1 = v1 > R ? R : v1;
-    LBM_CHECK_HIP(hipEventRecord(sl->ev_fork, st));
-    LBM_CHECK_HIP(hipStreamWaitEvent(sl->aux, sl->ev_fork, 0));
-    double* bl = sl->blat[sl->bcur];
-    const lbm_geom sg = msg_geom(D, C);
-    // the D outermost band rows of each side at time t: far rows of this slab (owned or ghost), or the co-owner's
-    if (sl->straddle_prev) rc = lbm_rows_copy(bl, &sl->bg, 0, sl->stash, &sg, 0, D, sl->aux);
-    else rc = lbm_rows_copy(bl, &sl->bg, 0, src, &sl->g, sl->b0 - sl->row0, D, sl->aux);
+    // "ibm_box" = 0, or a box that would touch a wall column: the full-width band chain on the helper stream, beside the
+    // far rows on the caller's
+    rc = sl->aux.fork(st);
     if (rc) return rc;
-    const int hi = sl->b1 - D;  // global
-    if (sl->straddle_next) rc = lbm_rows_copy(bl, &sl->bg, hi - sl->b0, sl->stash, &sg, 0, D, sl->aux);
-    else rc = lbm_rows_copy(bl, &sl->bg, hi - sl->b0, src, &sl->g, hi - sl->row0, D, sl->aux);
+    rc = slab_ibm_load_outer_rows(sl, src, sl->aux.st);
+    const int odd = D & 1;  // the chain ends in the other lattice of the pair when D is odd
+    if (!rc)
+      rc = ibm_forced_band_chain(sl->ib, sl->blat[sl->bcur], sl->blat[sl->bcur ^ odd], sl->blat[sl->bcur ^ odd ^ 1], sl->bg, sl->bbc, sl->prm, 0,
+                                 Rb, sl->brho, sl->bu, sl->ga, sl->gb, D, sl->aux.st);
+    if (!rc) sl->bcur ^= odd;
+    if (!rc) rc = take_my_rows(sl->aux.st);
+    if (!rc) rc = far_rows(st);
+    rc = sl->aux.join(st, rc);
     if (rc) return rc;
-    const int Rb = sl->bg.R;
-    for (int k = 1; k <= D; ++k) {  // cylinder_test.cpp:103-127 on the shrinking trapezoid
-      double* in = sl->blat[sl->bcur];
-      double* outl = sl->blat[sl->bcur ^ 1];
-      rc = lbm_bgk_stream_collide(outl, in, &sl->bg, &sl->bbc, &sl->prm, k, Rb - k, sl->brho, sl->bu, sl->aux);
-      if (!rc) rc = lbm_ibm_step(sl->ib, outl, &sl->bg, sl->bu, sl->brho, sl->prm.omega, sl->ga, sl->gb, sl->aux);
-      if (rc) return rc;
-      sl->bcur ^= 1;
-    }
-    // my part of the valid rows into the slab lattice
-    rc = lbm_rows_copy(dst, &sl->g, o0, sl->blat[sl->bcur], &sl->bg, o0 + sl->row0 - sl->b0, o1 - o0, sl->aux);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipEventRecord(sl->ev_join, sl->aux));
-  }
-  const bool boxed = sl->owner && sl->boxed && tuning("ibm_box", 1);  // (both boxed forms have launched their far rows)
-  if (!boxed) {
-    // far rows: plain D-step window from the time-t lattice
-    if (o0 > 0) rc = lbm_bgk_stream_collide_xn(dst, src, &sl->g, &sl->bc, &sl->prm, D, 0, o0 < R ? o0 : R, st);
-    if (!rc && o1 < R) rc = lbm_bgk_stream_collide_xn(dst, src, &sl->g, &sl->bc, &sl->prm, D, o1, R, st);
-    if (rc) return rc;
-    if (sl->owner) LBM_CHECK_HIP(hipStreamWaitEvent(st, sl->ev_join, 0));
-  }
-  // messages
-  if (sl->has_prev) {
-    if (sl->straddle_prev) {  // the co-owner above needs the band's lower outer rows: mine, far, now at t + D
-      const lbm_geom sg = msg_geom(D, C);
-      rc = lbm_rows_copy(send_prev, &sg, 0, dst, &sl->g, sl->b1 - D - sl->row0, D, s);
-    } else {
-      rc = lbm_halo_pack(send_prev, dst, &sl->g, full, 0, s);
-    }
+  } else {
+    rc = far_rows(st);
     if (rc) return rc;
   }
-  if (sl->has_next) {
-    if (sl->straddle_next) {  // the co-owner below needs the band's upper outer rows
-      const lbm_geom sg = msg_geom(D, C);
-      rc = lbm_rows_copy(send_next, &sg, 0, dst, &sl->g, sl->b0 - sl->row0, D, s);
-    } else {
-      rc = lbm_halo_pack(send_next, dst, &sl->g, full, 1, s);
-    }
-  }
+  // messages: across a straddled seam the co-owner needs the band's outer rows on ITS far side -- mine, far, now at t + D
+  if (sl->has_prev) rc = slab_pack_side(send_prev, dst, sl->g, D, 0, sl->straddle_prev, sl->b1 - D - sl->row0, s);
+  if (!rc && sl->has_next) rc = slab_pack_side(send_next, dst, sl->g, D, 1, sl->straddle_next, sl->b0 - sl->row0, s);
   return rc;
 }
 
@@ -535,17 +451,9 @@ int lbm_slab_ibm_block_compute(lbm_slab_ibm* sl, double* dst, const double* src,
 int lbm_slab_ibm_block_finish(lbm_slab_ibm* sl, double* dst, const double* recv_prev, const double* recv_next, lbm_stream_t s) {
   LBM_REQUIRE(sl && dst, "lbm_slab_ibm_block_finish: NULL argument");
   LBM_REQUIRE((!sl->has_prev || recv_prev) && (!sl->has_next || recv_next), "lbm_slab_ibm_block_finish: NULL receive buffer");
-  const int full = LBM_HALO_FULL(sl->D);
-  const size_t msg = (size_t)9 * sl->D * sl->g.C * sizeof(double);
   int rc = LBM_OK;
-  if (sl->has_prev) {
-    if (sl->straddle_prev) LBM_CHECK_HIP(hipMemcpyAsync(sl->stash, recv_prev, msg, hipMemcpyDeviceToDevice, as_stream(s)));
-    else rc = lbm_halo_unpack(dst, recv_prev, &sl->g, full, 0, s);
-  }
-  if (!rc && sl->has_next) {
-    if (sl->straddle_next) LBM_CHECK_HIP(hipMemcpyAsync(sl->stash, recv_next, msg, hipMemcpyDeviceToDevice, as_stream(s)));
-    else rc = lbm_halo_unpack(dst, recv_next, &sl->g, full, 1, s);
-  }
+  if (sl->has_prev) rc = slab_finish_side(dst, sl->stash, recv_prev, sl->g, sl->D, 0, sl->straddle_prev, s);
+  if (!rc && sl->has_next) rc = slab_finish_side(dst, sl->stash, recv_next, sl->g, sl->D, 1, sl->straddle_next, s);
   return rc;
 }
 
@@ -553,8 +461,8 @@ int lbm_slab_ibm_block_finish(lbm_slab_ibm* sl, double* dst, const double* recv_
 int lbm_slab_ibm_surface_force(lbm_slab_ibm* sl, double* out2, lbm_stream_t s) {
   LBM_REQUIRE(sl && out2, "lbm_slab_ibm_surface_force: NULL argument");
   LBM_REQUIRE(sl->owner && sl->ib, "lbm_slab_ibm_surface_force: this slab does not own the boundary");
-  LBM_CHECK_HIP(hipStreamSynchronize(sl->aux));
-  if (sl->bgst) LBM_CHECK_HIP(hipStreamSynchronize(sl->bgst));
+  LBM_CHECK_HIP(hipStreamSynchronize(sl->aux.st));
+  if (sl->bg_side) LBM_CHECK_HIP(hipStreamSynchronize(sl->bg_side.st));
   return lbm_ibm_surface_force(sl->ib, out2, s);
 }
 

@@ -13,10 +13,27 @@
 #include <cstring>
 #include <new>
 
+#include "blocks.hpp"
 #include "d2q9.hpp"
-#include "internal.hpp"
+#include "slab.hpp"
 
 using namespace lbm;
+
+// An END slab's place at the pressure seam, in rows (first slab: owns the virtual row 0 / last slab: row Rg - 1).  The small
+// lattice holds rows [0, 2D) of the domain, then rows [Rg - 2D, Rg): its own wrap is the seam.
+struct SeamEnd {
+  int side;             // the message side that crosses the pressure seam: 0 (previous) / 1 (next); -1: a middle slab
+  int own, own_s;       // my 2 D rows next to the seam: slab row 0 / R - 2D, small-lattice row 0 / 2D
+  int partner_s;        // the partner's 2 D rows in the small lattice: row 2D / 0
+  int near, near_s;     // my D rows next to the seam (valid after a block): slab row 0 / R - D, small-lattice row 0 / 3D
+  int far, far_s;       // my rows at distance [D, 2D) from the seam: slab row D / R - 2D, small-lattice row D / 2D
+  int partner_far_s;    // the partner's rows at that distance (they travel, and wait in the stash): small-lattice row 2D / D
+};
+static SeamEnd seam_end(bool first, bool last, int R, int D) {
+  if (first) return SeamEnd{0, 0, 0, 2 * D, 0, 0, D, D, 2 * D};
+  if (last) return SeamEnd{1, R - 2 * D, 2 * D, 0, R - D, 3 * D, R - 2 * D, 2 * D, D};
+  return SeamEnd{-1, 0, 0, 0, 0, 0, 0, 0, 0};
+}
 
 struct lbm_slab_pressure {
   int model;               // LBM_MODEL_BGK / LBM_MODEL_KBC
@@ -27,18 +44,13 @@ struct lbm_slab_pressure {
   lbm_bc bc_seam, bc_far;  // the small lattice's edges (= the domain's, pressure rows on); this slab's far rows (HALO rows, no pressure rows)
   lbm_bgk_params prm;
   bool first, last;        // owns the virtual row 0 / Rg - 1
+  SeamEnd se;
   lbm_geom sg;             // small lattice: rows [0, 2D) of the domain, then rows [Rg - 2D, Rg)
   double* slat[2];
   int scur;
   double* stash;           // [9][D][C]: the partner's rows at distance [D, 2D) from the seam
-  hipStream_t aux;
-  hipEvent_t ev_fork, ev_join;
+  SideStream aux;          // the small lattice's chain, beside the far rows on the caller's stream
 };
-
-namespace {
-inline lbm_geom msg_geom(int n, int C) { return lbm_geom{n, C, 0, (long long)n * C}; }
-inline long long plane_of(const lbm_geom& g) { return g.plane_stride > 0 ? g.plane_stride : (long long)(g.R + 2 * g.ghost) * g.C; }
-}  // namespace
 
 extern "C" {
 
@@ -53,12 +65,7 @@ int lbm_slab_pressure_info(const lbm_slab_pressure* sl, int* R, int* C, int* gho
 
 int lbm_slab_pressure_destroy(lbm_slab_pressure* sl) {
   if (!sl) return LBM_OK;
-  if (sl->aux) {
-    (void)hipStreamSynchronize(sl->aux);
-    (void)hipStreamDestroy(sl->aux);
-  }
-  if (sl->ev_fork) (void)hipEventDestroy(sl->ev_fork);
-  if (sl->ev_join) (void)hipEventDestroy(sl->ev_join);
+  sl->aux.destroy();
   for (double* p : {sl->slat[0], sl->slat[1], sl->stash, sl->sm0, sl->sm1})
     if (p) (void)hipFree(p);
   delete sl;
@@ -98,7 +105,6 @@ static int slab_pressure_create(lbm_slab_pressure** out, const lbm_geom* slab, i
               "lbm_slab_pressure_create: needs pressure rows on periodic row edges and periodic / wall columns");
   lbm_slab_pressure* sl = new (std::nothrow) lbm_slab_pressure();
   LBM_REQUIRE(sl, "lbm_slab_pressure_create: out of host memory");
-  std::memset(sl, 0, sizeof *sl);
   sl->g = *slab;
   sl->row0 = slab_row0;
   sl->rows_global = rows_global;
@@ -115,6 +121,7 @@ static int slab_pressure_create(lbm_slab_pressure** out, const lbm_geom* slab, i
   sl->bc_far.row_lo = sl->bc_far.row_hi = LBM_EDGE_HALO;  // every seam of the ring, the periodic one included
   sl->first = slab_row0 == 0;
   sl->last = slab_row0 + R == rows_global;
+  sl->se = seam_end(sl->first, sl->last, R, D);
   if (!sl->first && !sl->last) {
     *out = sl;
     return LBM_OK;
@@ -132,11 +139,9 @@ static int slab_pressure_create(lbm_slab_pressure** out, const lbm_geom* slab, i
     if (e == hipSuccess) e = hipMalloc(&sl->sm0, (size_t)4 * D * C * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&sl->sm1, (size_t)8 * D * C * sizeof(double));
   }
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&sl->aux, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&sl->ev_fork, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&sl->ev_join, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    set_error("lbm_slab_pressure_create: %s", hipGetErrorString(e));
+  const int rc = e == hipSuccess ? sl->aux.create() : LBM_OK;
+  if (e != hipSuccess) set_error("lbm_slab_pressure_create: %s", hipGetErrorString(e));
+  if (e != hipSuccess || rc) {
     lbm_slab_pressure_destroy(sl);
     return LBM_ERR_HIP;
   }
@@ -154,16 +159,37 @@ long long lbm_slab_pressure_msg_doubles(const lbm_slab_pressure* sl, int side, i
   return (long long)planes * (start && seam ? 2 * sl->D : sl->D) * sl->g.C;
 }
 
+// the start-up message of one side from the PRE-collision state: the complete D-row halo across an ordinary seam, my 2 D rows
+// next to it across the pressure seam
+static int start_pack_side(lbm_slab_pressure* sl, const double* pre, double* send, int side, lbm_stream_t s) {
+  if (side != sl->se.side) return lbm_halo_pack(send, pre, &sl->g, LBM_HALO_FULL(sl->D), side, s);
+  const lbm_geom mg = msg_geom(2 * sl->D, sl->g.C);
+  return lbm_rows_copy(send, &mg, 0, pre, &sl->g, sl->se.own, 2 * sl->D, s);
+}
+// the small lattice at start-up, pre-collision: my 2 D rows from the slab, the partner's from its message
+static int start_fill_small(lbm_slab_pressure* sl, const double* pre, const double* recv, lbm_stream_t s) {
+  const int D = sl->D;
+  const lbm_geom mg = msg_geom(2 * D, sl->g.C);
+  double* sp = sl->slat[sl->scur];
+  const int rc = lbm_rows_copy(sp, &sl->sg, sl->se.own_s, pre, &sl->g, sl->se.own, 2 * D, s);
+  return rc ? rc : lbm_rows_copy(sp, &sl->sg, sl->se.partner_s, recv, &mg, 0, 2 * D, s);
+}
+// ... and once it is collided: my 2 D rows into `post`, the partner's rows at distance [D, 2D) from the seam into the stash
+static int start_take_small(lbm_slab_pressure* sl, double* post, lbm_stream_t s) {
+  const int D = sl->D;
+  const double* so = sl->slat[sl->scur];
+  const lbm_geom dg = msg_geom(D, sl->g.C);
+  const int rc = lbm_rows_copy(post, &sl->g, sl->se.own, so, &sl->sg, sl->se.own_s, 2 * D, s);
+  return rc ? rc : lbm_rows_copy(sl->stash, &dg, 0, so, &sl->sg, sl->se.partner_far_s, D, s);
+}
+
 // start-up, on the driver's PRE-collision state: complete D-row halos across ordinary seams, the 2 D rows next to
 // the pressure seam across that one
 int lbm_slab_pressure_start_pack(lbm_slab_pressure* sl, const double* pre, double* send_prev, double* send_next, lbm_stream_t s) {
   LBM_REQUIRE(sl && pre && send_prev && send_next, "lbm_slab_pressure_start_pack: NULL argument");
   LBM_REQUIRE(sl->model == LBM_MODEL_BGK, "lbm_slab_pressure_start_pack: a KBC slab starts with lbm_slab_pressure_start_pack_kbc (held moments)");
-  const int R = sl->g.R, C = sl->g.C, D = sl->D, full = LBM_HALO_FULL(D);
-  const lbm_geom mg = msg_geom(2 * D, C);
-  int rc = sl->first ? lbm_rows_copy(send_prev, &mg, 0, pre, &sl->g, 0, 2 * D, s) : lbm_halo_pack(send_prev, pre, &sl->g, full, 0, s);
-  if (!rc) rc = sl->last ? lbm_rows_copy(send_next, &mg, 0, pre, &sl->g, R - 2 * D, 2 * D, s) : lbm_halo_pack(send_next, pre, &sl->g, full, 1, s);
-  return rc;
+  const int rc = start_pack_side(sl, pre, send_prev, 0, s);
+  return rc ? rc : start_pack_side(sl, pre, send_next, 1, s);
 }
 
 // ... then the driver's first iteration (collision of every row; the virtual rows and their neighbours from the
@@ -173,38 +199,19 @@ int lbm_slab_pressure_start_finish(lbm_slab_pressure* sl, double* post, double* 
                                    const double* recv_next, lbm_stream_t s) {
   LBM_REQUIRE(sl && post && pre && post != pre && recv_prev && recv_next, "lbm_slab_pressure_start_finish: bad argument");
   LBM_REQUIRE(sl->model == LBM_MODEL_BGK, "lbm_slab_pressure_start_finish: a KBC slab starts with lbm_slab_pressure_start_finish_kbc");
-  const int R = sl->g.R, C = sl->g.C, D = sl->D, G = sl->g.ghost, full = LBM_HALO_FULL(D);
-  hipStream_t st = as_stream(s);
+  const int R = sl->g.R, C = sl->g.C, G = sl->g.ghost, full = LBM_HALO_FULL(sl->D);
   int rc = LBM_OK;
   if (!sl->first) rc = lbm_halo_unpack(pre, recv_prev, &sl->g, full, 0, s);
   if (!rc && !sl->last) rc = lbm_halo_unpack(pre, recv_next, &sl->g, full, 1, s);
   if (rc) return rc;
   const lbm_geom tall{R + 2 * G, C, 0, plane_of(sl->g)};  // all rows, ghost rows included: collision is node-local
-  rc = bgk_collide_ref(post, pre, &tall, &sl->prm, st);
-  if (rc || (!sl->first && !sl->last)) return rc;
-  // small lattice, pre-collision: rows [0, 2D) of the domain, then rows [Rg - 2D, Rg)
-  const lbm_geom mg = msg_geom(2 * D, C);
-  double* sp = sl->slat[sl->scur];
-  if (sl->first) {
-    rc = lbm_rows_copy(sp, &sl->sg, 0, pre, &sl->g, 0, 2 * D, s);
-    if (!rc) rc = lbm_rows_copy(sp, &sl->sg, 2 * D, recv_prev, &mg, 0, 2 * D, s);
-  } else {
-    rc = lbm_rows_copy(sp, &sl->sg, 2 * D, pre, &sl->g, R - 2 * D, 2 * D, s);
-    if (!rc) rc = lbm_rows_copy(sp, &sl->sg, 0, recv_next, &mg, 0, 2 * D, s);
-  }
-  double* so = sl->slat[sl->scur ^ 1];
-  if (!rc) rc = lbm_bgk_collide(so, sp, &sl->sg, &sl->bc_seam, &sl->prm, nullptr, nullptr, s);  // incl. the pressure rows
+  rc = bgk_collide_ref(post, pre, &tall, &sl->prm, as_stream(s));
+  if (rc || sl->se.side < 0) return rc;
+  rc = start_fill_small(sl, pre, sl->se.side ? recv_next : recv_prev, s);
+  if (!rc) rc = lbm_bgk_collide(sl->slat[sl->scur ^ 1], sl->slat[sl->scur], &sl->sg, &sl->bc_seam, &sl->prm, nullptr, nullptr, s);  // incl. the pressure rows
   if (rc) return rc;
   sl->scur ^= 1;
-  const lbm_geom dg = msg_geom(D, C);
-  if (sl->first) {
-    rc = lbm_rows_copy(post, &sl->g, 0, so, &sl->sg, 0, 2 * D, s);
-    if (!rc) rc = lbm_rows_copy(sl->stash, &dg, 0, so, &sl->sg, 2 * D, D, s);  // the partner's rows [Rg - 2D, Rg - D)
-  } else {
-    rc = lbm_rows_copy(post, &sl->g, R - 2 * D, so, &sl->sg, 2 * D, 2 * D, s);
-    if (!rc) rc = lbm_rows_copy(sl->stash, &dg, 0, so, &sl->sg, D, D, s);      // the partner's rows [D, 2D)
-  }
-  return rc;
+  return start_take_small(sl, post, s);
 }
 
 // ---- KBC start-up (ulbm_poiseuille.cpp:85-139 on the initial state: adve_f as given, HELD moments m0 [R][C], m1 [2][R][C]
@@ -222,30 +229,17 @@ int lbm_slab_pressure_start_pack_kbc(lbm_slab_pressure* sl, const double* pre, c
                                      double* send_prev, double* send_next, lbm_stream_t s) {
   LBM_REQUIRE(sl && pre && m0 && m1 && send_prev && send_next, "lbm_slab_pressure_start_pack_kbc: NULL argument");
   LBM_REQUIRE(sl->model == LBM_MODEL_KBC, "lbm_slab_pressure_start_pack_kbc: not a KBC slab");
-  const int R = sl->g.R, C = sl->g.C, D = sl->D, full = LBM_HALO_FULL(D);
-  hipStream_t st = as_stream(s);
-  const lbm_geom mg = msg_geom(2 * D, C);
-  const size_t n = (size_t)R * C, rows = (size_t)2 * D * C;
-  int rc = LBM_OK;
-  if (sl->first) {
-    rc = lbm_rows_copy(send_prev, &mg, 0, pre, &sl->g, 0, 2 * D, s);
-    if (!rc) rc = rows_copy_plane(send_prev + 9 * rows, m0, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(send_prev + 10 * rows, m1, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(send_prev + 11 * rows, m1 + n, 2 * D, C, st);
-  } else {
-    rc = lbm_halo_pack(send_prev, pre, &sl->g, full, 0, s);
+  const int R = sl->g.R, C = sl->g.C, D = sl->D;
+  const size_t n = (size_t)R * C, rows = (size_t)2 * D * C, o = (size_t)sl->se.own * C;
+  double* const send[2] = {send_prev, send_next};
+  const double* const mom[3] = {m0, m1, m1 + n};  // m0, then the two planes of m1: message planes 9, 10, 11
+  for (int side = 0; side < 2; ++side) {
+    int rc = start_pack_side(sl, pre, send[side], side, s);
+    for (int k = 0; k < 3 && !rc && side == sl->se.side; ++k)
+      rc = rows_copy_plane(send[side] + (9 + k) * rows, mom[k] + o, 2 * D, C, as_stream(s));
+    if (rc) return rc;
   }
-  if (rc) return rc;
-  if (sl->last) {
-    const size_t o = (size_t)(R - 2 * D) * C;
-    rc = lbm_rows_copy(send_next, &mg, 0, pre, &sl->g, R - 2 * D, 2 * D, s);
-    if (!rc) rc = rows_copy_plane(send_next + 9 * rows, m0 + o, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(send_next + 10 * rows, m1 + o, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(send_next + 11 * rows, m1 + n + o, 2 * D, C, st);
-  } else {
-    rc = lbm_halo_pack(send_next, pre, &sl->g, full, 1, s);
-  }
-  return rc;
+  return LBM_OK;
 }
 
 int lbm_slab_pressure_start_finish_kbc(lbm_slab_pressure* sl, double* post, double* pre, const double* m0, const double* m1,
@@ -253,109 +247,61 @@ int lbm_slab_pressure_start_finish_kbc(lbm_slab_pressure* sl, double* post, doub
   LBM_REQUIRE(sl && post && pre && post != pre && m0 && m1 && recv_prev && recv_next, "lbm_slab_pressure_start_finish_kbc: bad argument");
   LBM_REQUIRE(sl->model == LBM_MODEL_KBC, "lbm_slab_pressure_start_finish_kbc: not a KBC slab");
   const int R = sl->g.R, C = sl->g.C, D = sl->D, G = sl->g.ghost;
-  hipStream_t st = as_stream(s);
+  const SeamEnd& se = sl->se;
   // the owned rows on their held moments (kbc::collide with the driver's m0, m1, ulbm.cpp:91-126)
   const lbm_geom own{R, C, 0, plane_of(sl->g)};
   int rc = lbm_kbc_collide_first(post + (size_t)G * C, pre + (size_t)G * C, m0, m1, &own, nullptr, &sl->kprm, s);
-  if (rc || (!sl->first && !sl->last)) return rc;
-  // small lattice, pre-collision: rows [0, 2D) of the domain, then rows [Rg - 2D, Rg); its held moments likewise
-  const lbm_geom mg = msg_geom(2 * D, C);
+  if (rc || se.side < 0) return rc;
+  // small lattice, pre-collision, and its held moments likewise: mine from the slab, the partner's from its message
+  const double* recv = se.side ? recv_next : recv_prev;
   const size_t n = (size_t)R * C, rows = (size_t)2 * D * C, sn = (size_t)4 * D * C;
-  double* sp = sl->slat[sl->scur];
-  if (sl->first) {
-    rc = lbm_rows_copy(sp, &sl->sg, 0, pre, &sl->g, 0, 2 * D, s);
-    if (!rc) rc = lbm_rows_copy(sp, &sl->sg, 2 * D, recv_prev, &mg, 0, 2 * D, s);
-    if (!rc) rc = rows_copy_plane(sl->sm0, m0, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm1, m1, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm1 + sn, m1 + n, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm0 + rows, recv_prev + 9 * rows, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm1 + rows, recv_prev + 10 * rows, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm1 + sn + rows, recv_prev + 11 * rows, 2 * D, C, st);
-  } else {
-    const size_t o = (size_t)(R - 2 * D) * C;
-    rc = lbm_rows_copy(sp, &sl->sg, 2 * D, pre, &sl->g, R - 2 * D, 2 * D, s);
-    if (!rc) rc = lbm_rows_copy(sp, &sl->sg, 0, recv_next, &mg, 0, 2 * D, s);
-    if (!rc) rc = rows_copy_plane(sl->sm0 + rows, m0 + o, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm1 + rows, m1 + o, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm1 + sn + rows, m1 + n + o, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm0, recv_next + 9 * rows, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm1, recv_next + 10 * rows, 2 * D, C, st);
-    if (!rc) rc = rows_copy_plane(sl->sm1 + sn, recv_next + 11 * rows, 2 * D, C, st);
-  }
-  double* so = sl->slat[sl->scur ^ 1];
-  if (!rc) rc = lbm_kbc_collide_first(so, sp, sl->sm0, sl->sm1, &sl->sg, &sl->bc_seam, &sl->kprm, s);  // incl. the pressure rows (:36-58)
+  rc = start_fill_small(sl, pre, recv, s);
+  double* const small[3] = {sl->sm0, sl->sm1, sl->sm1 + sn};
+  const double* const mom[3] = {m0, m1, m1 + n};
+  for (int k = 0; k < 3 && !rc; ++k) rc = rows_copy_plane(small[k] + (size_t)se.own_s * C, mom[k] + (size_t)se.own * C, 2 * D, C, as_stream(s));
+  for (int k = 0; k < 3 && !rc; ++k) rc = rows_copy_plane(small[k] + (size_t)se.partner_s * C, recv + (9 + k) * rows, 2 * D, C, as_stream(s));
+  if (!rc) rc = lbm_kbc_collide_first(sl->slat[sl->scur ^ 1], sl->slat[sl->scur], sl->sm0, sl->sm1, &sl->sg, &sl->bc_seam, &sl->kprm, s);  // incl. the pressure rows (:36-58)
   if (rc) return rc;
   sl->scur ^= 1;
-  const lbm_geom dg = msg_geom(D, C);
-  if (sl->first) {
-    rc = lbm_rows_copy(post, &sl->g, 0, so, &sl->sg, 0, 2 * D, s);
-    if (!rc) rc = lbm_rows_copy(sl->stash, &dg, 0, so, &sl->sg, 2 * D, D, s);
-  } else {
-    rc = lbm_rows_copy(post, &sl->g, R - 2 * D, so, &sl->sg, 2 * D, 2 * D, s);
-    if (!rc) rc = lbm_rows_copy(sl->stash, &dg, 0, so, &sl->sg, D, D, s);
-  }
-  return rc;
+  return start_take_small(sl, post, s);
 }
 
 // one block of D steps, phase A: dst from src on the owned rows, both outgoing messages packed
 int lbm_slab_pressure_block_compute(lbm_slab_pressure* sl, double* dst, const double* src, double* send_prev,
                                     double* send_next, lbm_stream_t s) {
   LBM_REQUIRE(sl && dst && src && dst != src && send_prev && send_next, "lbm_slab_pressure_block_compute: bad argument");
-  const int R = sl->g.R, C = sl->g.C, D = sl->D, full = LBM_HALO_FULL(D);
-  hipStream_t st = as_stream(s);
-  const bool end = sl->first || sl->last;
-  int rc = LBM_OK;
+  const int R = sl->g.R, C = sl->g.C, D = sl->D;
+  const SeamEnd& se = sl->se;
+  hipStream_t st = as_stream(s), aux = sl->aux.st;
+  const bool end = se.side >= 0;
+  int rc = end ? sl->aux.fork(st) : LBM_OK;
+  if (rc) return rc;
   if (end) {
-    LBM_CHECK_HIP(hipEventRecord(sl->ev_fork, st));
-    LBM_CHECK_HIP(hipStreamWaitEvent(sl->aux, sl->ev_fork, 0));
     double* sp = sl->slat[sl->scur];
     const lbm_geom dg = msg_geom(D, C);
     // the rows at distance [D, 2D) from the seam at time t: mine from the slab, the partner's from the stash
-    if (sl->first) {
-      rc = lbm_rows_copy(sp, &sl->sg, D, src, &sl->g, D, D, sl->aux);
-      if (!rc) rc = lbm_rows_copy(sp, &sl->sg, 2 * D, sl->stash, &dg, 0, D, sl->aux);
-    } else {
-      rc = lbm_rows_copy(sp, &sl->sg, 2 * D, src, &sl->g, R - 2 * D, D, sl->aux);
-      if (!rc) rc = lbm_rows_copy(sp, &sl->sg, D, sl->stash, &dg, 0, D, sl->aux);
-    }
-    for (int k = 0; k < D && !rc; ++k) {
-      rc = sl->model == LBM_MODEL_KBC
-               ? lbm_kbc_stream_collide(sl->slat[sl->scur ^ 1], sl->slat[sl->scur], &sl->sg, &sl->bc_seam, &sl->kprm, 0, 4 * D, nullptr, nullptr, sl->aux)
-               : lbm_bgk_stream_collide(sl->slat[sl->scur ^ 1], sl->slat[sl->scur], &sl->sg, &sl->bc_seam, &sl->prm, 0, 4 * D, nullptr,
-                                        nullptr, sl->aux);
-      sl->scur ^= 1;
-    }
-    if (rc) return rc;
+    rc = lbm_rows_copy(sp, &sl->sg, se.far_s, src, &sl->g, se.far, D, aux);
+    if (!rc) rc = lbm_rows_copy(sp, &sl->sg, se.partner_far_s, sl->stash, &dg, 0, D, aux);
+    if (!rc) rc = seam_chain(sl->slat, &sl->scur, sl->sg, sl->bc_seam, sl->model, sl->prm, sl->kprm, D, aux);
     // my D rows next to the seam (rows [0, D) and [3D, 4D) of the small lattice are valid)
-    rc = sl->first ? lbm_rows_copy(dst, &sl->g, 0, sl->slat[sl->scur], &sl->sg, 0, D, sl->aux)
-                   : lbm_rows_copy(dst, &sl->g, R - D, sl->slat[sl->scur], &sl->sg, 3 * D, D, sl->aux);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipEventRecord(sl->ev_join, sl->aux));
+    if (!rc) rc = lbm_rows_copy(dst, &sl->g, se.near, sl->slat[sl->scur], &sl->sg, se.near_s, D, aux);
   }
   // far rows: the D-step window in the reference operation order (lattices with pressure rows keep it on every path)
   const int r0 = sl->first ? D : 0, r1 = sl->last ? R - D : R;
-  rc = sl->model == LBM_MODEL_KBC ? kbc_stream_collide_x2_ref(dst, src, &sl->g, &sl->bc_far, &sl->kprm, r0, r1, st)
-                                  : bgk_stream_collide_xn_ref(dst, src, &sl->g, &sl->bc_far, &sl->prm, D, r0, r1, st);
-  if (rc) return rc;
-  if (end) LBM_CHECK_HIP(hipStreamWaitEvent(st, sl->ev_join, 0));
-  const lbm_geom dg = msg_geom(D, C);
-  rc = sl->first ? lbm_rows_copy(send_prev, &dg, 0, dst, &sl->g, D, D, s) : lbm_halo_pack(send_prev, dst, &sl->g, full, 0, s);
-  if (!rc) rc = sl->last ? lbm_rows_copy(send_next, &dg, 0, dst, &sl->g, R - 2 * D, D, s) : lbm_halo_pack(send_next, dst, &sl->g, full, 1, s);
+  if (!rc)
+    rc = sl->model == LBM_MODEL_KBC ? kbc_stream_collide_x2_ref(dst, src, &sl->g, &sl->bc_far, &sl->kprm, r0, r1, st)
+                                    : bgk_stream_collide_xn_ref(dst, src, &sl->g, &sl->bc_far, &sl->prm, D, r0, r1, st);
+  if (end) rc = sl->aux.join(st, rc);
+  if (!rc) rc = slab_pack_side(send_prev, dst, sl->g, D, 0, se.side == 0, se.far, s);
+  if (!rc) rc = slab_pack_side(send_next, dst, sl->g, D, 1, se.side == 1, se.far, s);
   return rc;
 }
 
 // phase B: ordinary halos into the ghost rows of dst, the partner's rows into the stash
 int lbm_slab_pressure_block_finish(lbm_slab_pressure* sl, double* dst, const double* recv_prev, const double* recv_next, lbm_stream_t s) {
   LBM_REQUIRE(sl && dst && recv_prev && recv_next, "lbm_slab_pressure_block_finish: NULL argument");
-  const int full = LBM_HALO_FULL(sl->D);
-  const size_t msg = (size_t)9 * sl->D * sl->g.C * sizeof(double);
-  int rc = LBM_OK;
-  if (sl->first) LBM_CHECK_HIP(hipMemcpyAsync(sl->stash, recv_prev, msg, hipMemcpyDeviceToDevice, as_stream(s)));
-  else rc = lbm_halo_unpack(dst, recv_prev, &sl->g, full, 0, s);
-  if (rc) return rc;
-  if (sl->last) LBM_CHECK_HIP(hipMemcpyAsync(sl->stash, recv_next, msg, hipMemcpyDeviceToDevice, as_stream(s)));
-  else rc = lbm_halo_unpack(dst, recv_next, &sl->g, full, 1, s);
-  return rc;
+  const int rc = slab_finish_side(dst, sl->stash, recv_prev, sl->g, sl->D, 0, sl->se.side == 0, s);
+  return rc ? rc : slab_finish_side(dst, sl->stash, recv_next, sl->g, sl->D, 1, sl->se.side == 1, s);
 }
 
 }  // extern "C"

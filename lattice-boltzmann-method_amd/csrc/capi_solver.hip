@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "blocks.hpp"
 #include "kbc.hpp"
 #include "launch.hpp"
 
@@ -29,22 +30,19 @@ struct lbm_solver {
   lbm_ibm* ibm;  // optional immersed boundary (not owned)
   double guo_a, guo_b;
   bool given_moments = false;  // first iteration collides on sv->rho / sv->u as set by the caller
-  hipStream_t side = nullptr;  // forcing chain of the immersed boundary, beside the lattice update
-  hipEvent_t ev_roi = nullptr, ev_ibm = nullptr;
+  lbm::SideStream side;        // forcing chain of the immersed boundary, beside the lattice update
   double* band = nullptr;      // third lattice: odd / even steps of the forced band (solver_ibm_block)
   // the forced BOX (solver_ibm_block): ROI +- 2 D rows and columns as a small lattice pair of its own
   double* box[2] = {nullptr, nullptr};
   double *box_rho = nullptr, *box_u = nullptr;
   long long box_plane = 0;
   int box_rows_max = 0, box_cols_max = 0;
-  hipStream_t far_st = nullptr;  // the D-step window over the whole lattice, beside the box chain
-  hipEvent_t ev_far_fork = nullptr, ev_far_join = nullptr;
+  lbm::SideStream far;           // the D-step window over the whole lattice, beside the box chain
   // pressure-periodic rows at multi-step speed (solver_pressure_block): two small lattices of 4 D rows
   // holding the rows on both sides of the virtual rows, advanced in single steps on a helper stream
   double* seam[2] = {nullptr, nullptr};
   long long seam_plane = 0;
-  hipStream_t seam_st = nullptr;
-  hipEvent_t ev_seam_fork = nullptr, ev_seam_join = nullptr;
+  lbm::SideStream seam_side;
 };
 static constexpr int kSeamMaxDepth = 5;
 
@@ -72,19 +70,13 @@ static int solver_fused(lbm_solver* sv, double* rho, double* u, bool with_ibm_ov
     int q0, q1, c0, c1;
     int rc = lbm_ibm_roi(sv->ibm, &q0, &q1, &c0, &c1);
     if (!rc) rc = lbm_bgk_stream_collide(dst, src, &sv->g, &sv->bc, &sv->bgk, q0, q1, rho, u, sv->st);
+    if (!rc) rc = sv->side.fork(sv->st);
     if (rc) return rc;
-    LBM_CHECK_HIP(hipEventRecord(sv->ev_roi, sv->st));
-    LBM_CHECK_HIP(hipStreamWaitEvent(sv->side, sv->ev_roi, 0));
-    rc = lbm_ibm_step(sv->ibm, dst, &sv->g, u, rho, sv->bgk.omega, sv->guo_a, sv->guo_b, sv->side);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipEventRecord(sv->ev_ibm, sv->side));
-    rc = ibm_gate(sv->ibm, sv->st);  // the lattice launches below must not take the forcing workgroup's CU first
-    if (rc) return rc;
-    rc = lbm_bgk_stream_collide(dst, src, &sv->g, &sv->bc, &sv->bgk, q1, sv->g.R, nullptr, nullptr, sv->st);
+    rc = lbm_ibm_step(sv->ibm, dst, &sv->g, u, rho, sv->bgk.omega, sv->guo_a, sv->guo_b, sv->side.st);
+    if (!rc) rc = ibm_gate(sv->ibm, sv->st);  // the lattice launches below must not take the forcing workgroup's CU first
+    if (!rc) rc = lbm_bgk_stream_collide(dst, src, &sv->g, &sv->bc, &sv->bgk, q1, sv->g.R, nullptr, nullptr, sv->st);
     if (!rc) rc = lbm_bgk_stream_collide(dst, src, &sv->g, &sv->bc, &sv->bgk, 0, q0, nullptr, nullptr, sv->st);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipStreamWaitEvent(sv->st, sv->ev_ibm, 0));
-    return LBM_OK;
+    return sv->side.join(sv->st, rc);
   }
   if (sv->model == LBM_MODEL_BGK)
     return lbm_bgk_stream_collide(dst, src, &sv->g, &sv->bc, &sv->bgk, 0, sv->g.R, rho, u, sv->st);
@@ -140,12 +132,10 @@ int lbm_solver_create(lbm_solver** out, int model, const lbm_geom* g, const lbm_
       e = hipMalloc(&sv->seam[k], (size_t)sv->seam_plane * 9 * sizeof(double));
       if (e == hipSuccess) e = hipMemsetAsync(sv->seam[k], 0, (size_t)sv->seam_plane * 9 * sizeof(double), sv->st);
     }
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&sv->seam_st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sv->ev_seam_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&sv->ev_seam_join, hipEventDisableTiming);
+    if (e == hipSuccess) rc = sv->seam_side.create();
   }
-  if (e != hipSuccess) {
-    set_error("lbm_solver_create: hipMalloc failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) set_error("lbm_solver_create: hipMalloc failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess || rc) {
     lbm_solver_destroy(sv);
     return LBM_ERR_HIP;
   }
@@ -155,27 +145,10 @@ int lbm_solver_create(lbm_solver** out, int model, const lbm_geom* g, const lbm_
 
 int lbm_solver_destroy(lbm_solver* sv) {
   if (!sv) return LBM_OK;
-  if (sv->seam_st) {
-    (void)hipStreamSynchronize(sv->seam_st);
-    (void)hipStreamDestroy(sv->seam_st);
-  }
-  if (sv->ev_seam_fork) (void)hipEventDestroy(sv->ev_seam_fork);
-  if (sv->ev_seam_join) (void)hipEventDestroy(sv->ev_seam_join);
+  for (SideStream* s : {&sv->seam_side, &sv->far, &sv->side}) s->destroy();  // (waits for their work: before the buffers go)
   for (double* p : {sv->lat[0], sv->lat[1], sv->stage, sv->rho, sv->u, sv->band, sv->seam[0], sv->seam[1], sv->box[0], sv->box[1],
                     sv->box_rho, sv->box_u})
     if (p) (void)hipFree(p);
-  if (sv->far_st) {
-    (void)hipStreamSynchronize(sv->far_st);
-    (void)hipStreamDestroy(sv->far_st);
-  }
-  if (sv->ev_far_fork) (void)hipEventDestroy(sv->ev_far_fork);
-  if (sv->ev_far_join) (void)hipEventDestroy(sv->ev_far_join);
-  if (sv->side) {
-    (void)hipStreamSynchronize(sv->side);
-    (void)hipStreamDestroy(sv->side);
-  }
-  if (sv->ev_roi) (void)hipEventDestroy(sv->ev_roi);
-  if (sv->ev_ibm) (void)hipEventDestroy(sv->ev_ibm);
   delete sv;
   return LBM_OK;
 }
@@ -290,68 +263,23 @@ static int solver_ibm_block(lbm_solver* sv, int D) {
   if (!sv->band) return 1;  // allocated by lbm_solver_attach_ibm (no allocation inside a step call)
   const double* src = sv->lat[sv->cur];
   double* dst = sv->lat[sv->cur ^ 1];
-  // The forced BOX.  The forcing reaches a node only through the ROI: columns at least 2 D away from it need the single
-  // steps as little as rows that far away do.  So the trapezoid is cut in both directions -- rows and columns ROI +- 2 D
-  // (columns widened to multiples of 8) copied into a small periodic lattice pair, D forced single steps there (what its
-  // wrap spoils is the frame that is dropped anyway), the box ROI +- D copied back -- and the D-step window runs over
-  // ALL rows from the time-t lattice, on a stream of its own beside the chain of small launches on the caller's stream.
-  // ("ibm_box" = 0: the full-width band below; also taken when the box would touch a wall column.)
+  // The forced BOX (ibm_forced_box_block, blocks.hpp): columns at least 2 D away from the ROI need the single steps as little as
+  // rows that far away do, so the trapezoid is cut in both directions -- rows and columns ROI +- 2 D (columns widened to
+  // multiples of 8) -- and the D-step window runs over ALL rows from the time-t lattice, on a stream of its own beside the
+  // chain.  ("ibm_box" = 0: the full-width band below; also taken when the box would touch a wall column.)
   const int bc0 = (c0 - 2 * D) / 8 * 8, bc1 = (c1 + 2 * D + 7) / 8 * 8;
-  if (sv->box[0] && sv->far_st && tuning("ibm_box", 1) && c0 - 2 * D >= 8 && bc1 <= sv->g.C - 1 && bc1 - bc0 <= sv->box_cols_max &&
+  if (sv->box[0] && sv->far && tuning("ibm_box", 1) && c0 - 2 * D >= 8 && bc1 <= sv->g.C - 1 && bc1 - bc0 <= sv->box_cols_max &&
       q1 - q0 + 4 * D <= sv->box_rows_max) {
-    const int Rb = q1 - q0 + 4 * D, Cb = bc1 - bc0, br0 = q0 - 2 * D;
-    const lbm_geom bg{Rb, Cb, 0, sv->box_plane};
-    const lbm_bc pb{LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, LBM_EDGE_PERIODIC, 0, 1.0, 1.0, 0.0, 0.0};
-    const bool beside = tuning("ibm_box_overlap", 1) != 0;
-    hipStream_t far = beside ? sv->far_st : sv->st;
-    if (beside) LBM_CHECK_HIP(hipEventRecord(sv->ev_far_fork, sv->st));
-    rc = box_copy(sv->box[0], bg, 0, 0, src, sv->g, br0, bc0, Rb, Cb, sv->st);
-    if (rc) return rc;
-    int cur = 0;
-    // "ibm_chain_kernel" = 1 (opt-in): the chain as ONE launch of a few workgroups on compute units of their own, the
-    // window launch held back until they are resident.  Bit-identical; measured level with the 3 D small launches
-    // (73 / 87 / 118 k against 77 / 98 / 121 k MLUPS at 2048 / 4096 / 16384 rows): what it gains in isolation it loses to
-    // coherent (L2-bypassing) accesses and 3 D grid barriers -- DESIGN 5.3
-    rc = tuning("ibm_chain_kernel", 0) ? ibm_box_chain(sv->ibm, br0, bc0, sv->box, &cur, &bg, &sv->bgk, bgk_uses_fast_model(&sv->bgk, &pb), D,
-                                                       sv->box_rho, sv->box_u, sv->guo_a, sv->guo_b, sv->st)
-                                       : 1;
-    if (rc < 0) return rc;
-    const bool one_launch = rc == 0;
-    if (beside) {
-      LBM_CHECK_HIP(hipStreamWaitEvent(far, sv->ev_far_fork, 0));
-      if (one_launch) rc = ibm_gate(sv->ibm, far);
-      else rc = LBM_OK;
-      // (round 4, measured and not kept: the window as PERSISTENT waves that leave 32 .. 256 wave slots of the card free for
-      // the chain from its first cycle to its last -- 143 - 150 k MLUPS against 148.5 / 149.3 k with every slot taken, and
-      // 115 - 118 k against 124 - 128 k in the reference order: the chain is not waiting for slots.  profiles/r04_ibm_reserve.txt)
-      if (!rc) rc = lbm_bgk_stream_collide_xn(dst, src, &sv->g, &sv->bc, &sv->bgk, D, 0, R, far);
-      if (rc) return rc;
-      LBM_CHECK_HIP(hipEventRecord(sv->ev_far_join, far));
-    }
-    for (int k = 1; k <= D && !one_launch; ++k) {
-      rc = lbm_bgk_stream_collide(sv->box[cur ^ 1], sv->box[cur], &bg, &pb, &sv->bgk, k, Rb - k, sv->box_rho, sv->box_u, sv->st);
-      if (!rc) rc = ibm_step_window(sv->ibm, br0, bc0, sv->box[cur ^ 1], &bg, sv->box_u, sv->box_rho, sv->bgk.omega, sv->guo_a, sv->guo_b, sv->st);
-      if (rc) return rc;
-      cur ^= 1;
-    }
-    if (beside) LBM_CHECK_HIP(hipStreamWaitEvent(sv->st, sv->ev_far_join, 0));
-    else rc = lbm_bgk_stream_collide_xn(dst, src, &sv->g, &sv->bc, &sv->bgk, D, 0, R, sv->st);
-    if (!rc) rc = box_copy(dst, sv->g, q0 - D, bc0 + D, sv->box[cur], bg, D, D, Rb - 2 * D, Cb - 2 * D, sv->st);
-    return rc;
+    const int br0 = q0 - 2 * D;
+    const lbm_geom bg{q1 - q0 + 4 * D, bc1 - bc0, 0, sv->box_plane};
+    auto window = [&](hipStream_t far) { return lbm_bgk_stream_collide_xn(dst, src, &sv->g, &sv->bc, &sv->bgk, D, 0, R, far); };
+    return ibm_forced_box_block(src, dst, sv->g, br0, bc0, sv->box, bg, sv->box_rho, sv->box_u, sv->ibm, br0, bc0, sv->bgk, sv->guo_a,
+                                sv->guo_b, D, tuning("ibm_box_overlap", 1) ? &sv->far : nullptr, window, sv->st);
   }
-  const double* in = src;
-  for (int k = 1; k <= D; ++k) {
-    double* out = ((D - k) % 2 == 0) ? dst : sv->band;
-    const int lo = q0 - 2 * D + k, hi = q1 + 2 * D - k;
-    // the whole band in ONE launch (rho, u are written for its rows outside the ROI too: harmless, and
-    // four launches fewer per step), then the forcing on the same stream: beside its one workgroup
-    // there is nothing left to run, and a cross-stream dependency costs more than it could hide
-    rc = lbm_bgk_stream_collide(out, in, &sv->g, &sv->bc, &sv->bgk, lo, hi, sv->rho, sv->u, sv->st);
-    if (!rc) rc = lbm_ibm_step(sv->ibm, out, &sv->g, sv->u, sv->rho, sv->bgk.omega, sv->guo_a, sv->guo_b, sv->st);
-    if (rc) return rc;
-    in = out;
-  }
-  rc = lbm_bgk_stream_collide_xn(dst, src, &sv->g, &sv->bc, &sv->bgk, D, 0, q0 - D, sv->st);
+  // the full-width band, alternating between lat[other] and the third lattice and ending in lat[other]
+  rc = ibm_forced_band_chain(sv->ibm, src, dst, sv->band, sv->g, sv->bc, sv->bgk, q0 - 2 * D, q1 + 2 * D, sv->rho, sv->u, sv->guo_a,
+                             sv->guo_b, D, sv->st);
+  if (!rc) rc = lbm_bgk_stream_collide_xn(dst, src, &sv->g, &sv->bc, &sv->bgk, D, 0, q0 - D, sv->st);
   if (!rc) rc = lbm_bgk_stream_collide_xn(dst, src, &sv->g, &sv->bc, &sv->bgk, D, q1 + D, R, sv->st);
   return rc;
 }
@@ -371,55 +299,40 @@ static int solver_pressure_block(lbm_solver* sv, int D) {
   const lbm_bc& b = sv->bc;
   const int R = sv->g.R, C = sv->g.C;
   auto col_ok = [](int m) { return m == LBM_EDGE_PERIODIC || bc_is_wall(m); };
-  if (!sv->seam[0] || !sv->seam_st || D < 2 || D > kSeamMaxDepth) return 1;
+  if (!sv->seam[0] || !sv->seam_side || D < 2 || D > kSeamMaxDepth) return 1;
   if (b.row_lo != LBM_EDGE_PERIODIC || b.row_hi != LBM_EDGE_PERIODIC || !col_ok(b.col_lo) || !col_ok(b.col_hi)) return 1;
   if (bc_mixed_axis(make_bc(&b)) || C < 64 || R < 6 * D + 8) return 1;
   if (sv->model == LBM_MODEL_KBC && D > 2) return 1;
-  const double* src = sv->lat[sv->cur];
+  double* src = sv->lat[sv->cur];
   double* dst = sv->lat[sv->cur ^ 1];
-  const int Rb = 4 * D;
-  lbm_geom sg{Rb, C, 0, sv->seam_plane};
+  const lbm_geom sg{4 * D, C, 0, sv->seam_plane};
   const size_t spitch = (size_t)sv->g.plane_stride * sizeof(double), dpitch = (size_t)sv->seam_plane * sizeof(double);
-  const size_t half = (size_t)2 * D * C * sizeof(double);
-  hipStream_t ss = sv->seam_st;
-  LBM_CHECK_HIP(hipEventRecord(sv->ev_seam_fork, sv->st));
-  LBM_CHECK_HIP(hipStreamWaitEvent(ss, sv->ev_seam_fork, 0));
-  // rows [0, 2D) -> small rows [0, 2D); rows [R - 2D, R) -> small rows [2D, 4D)
-  if (sv->g.row_pitch) {  // padded rows: the node-addressed copy
-    int rcp = solver_copy_planes(sv, const_cast<double*>(src), false, sv->seam[0], sv->seam_plane, Rb, 0, 0, 2 * D, ss);
-    if (!rcp) rcp = solver_copy_planes(sv, const_cast<double*>(src), false, sv->seam[0], sv->seam_plane, Rb, 2 * D, R - 2 * D, 2 * D, ss);
-    if (rcp) return rcp;
-  } else {
-  LBM_CHECK_HIP(hipMemcpy2DAsync(sv->seam[0], dpitch, src, spitch, half, 9, hipMemcpyDeviceToDevice, ss));
-  LBM_CHECK_HIP(hipMemcpy2DAsync(sv->seam[0] + (size_t)2 * D * C, dpitch, src + (size_t)(R - 2 * D) * C, spitch, half, 9,
-                                 hipMemcpyDeviceToDevice, ss));
-  }
-  int cur = 0, rc = LBM_OK;
-  for (int k = 0; k < D && !rc; ++k, cur ^= 1)
-    rc = sv->model == LBM_MODEL_BGK
-             ? lbm_bgk_stream_collide(sv->seam[cur ^ 1], sv->seam[cur], &sg, &sv->bc, &sv->bgk, 0, Rb, nullptr, nullptr, ss)
-             : lbm_kbc_stream_collide(sv->seam[cur ^ 1], sv->seam[cur], &sg, &sv->bc, &sv->kbc, 0, Rb, nullptr, nullptr, ss);
+  hipStream_t ss = sv->seam_side.st;
+  // n rows between the lattice (from row `row`; `into` = the new one, else out of the current one) and the small lattice
+  // sm (from row `srow`): plain 2-D copies, or the node-addressed copy where the solver's rows are padded
+  auto rows = [&](bool into, int row, double* sm, int srow, int n) -> int {
+    if (sv->g.row_pitch) return solver_copy_planes(sv, into ? dst : src, into, sm, sv->seam_plane, sg.R, srow, row, n, ss);
+    const size_t bytes = (size_t)n * C * sizeof(double);
+    if (into) LBM_CHECK_HIP(hipMemcpy2DAsync(dst + (size_t)row * C, spitch, sm + (size_t)srow * C, dpitch, bytes, 9, hipMemcpyDeviceToDevice, ss));
+    else LBM_CHECK_HIP(hipMemcpy2DAsync(sm + (size_t)srow * C, dpitch, src + (size_t)row * C, spitch, bytes, 9, hipMemcpyDeviceToDevice, ss));
+    return LBM_OK;
+  };
+  int rc = sv->seam_side.fork(sv->st);
   if (rc) return rc;
-  const size_t part = (size_t)D * C * sizeof(double);
-  if (sv->g.row_pitch) {
-    int rcp = solver_copy_planes(sv, dst, true, sv->seam[cur], sv->seam_plane, Rb, 0, 0, D, ss);
-    if (!rcp) rcp = solver_copy_planes(sv, dst, true, sv->seam[cur], sv->seam_plane, Rb, 3 * D, R - D, D, ss);
-    if (rcp) return rcp;
-  } else {
-  LBM_CHECK_HIP(hipMemcpy2DAsync(dst, spitch, sv->seam[cur], dpitch, part, 9, hipMemcpyDeviceToDevice, ss));
-  LBM_CHECK_HIP(hipMemcpy2DAsync(dst + (size_t)(R - D) * C, spitch, sv->seam[cur] + (size_t)3 * D * C, dpitch, part, 9,
-                                 hipMemcpyDeviceToDevice, ss));
-  }
-  LBM_CHECK_HIP(hipEventRecord(sv->ev_seam_join, ss));
+  // rows [0, 2D) -> small rows [0, 2D); rows [R - 2D, R) -> small rows [2D, 4D)
+  rc = rows(false, 0, sv->seam[0], 0, 2 * D);
+  if (!rc) rc = rows(false, R - 2 * D, sv->seam[0], 2 * D, 2 * D);
+  int cur = 0;
+  if (!rc) rc = seam_chain(sv->seam, &cur, sg, sv->bc, sv->model, sv->bgk, sv->kbc, D, ss);
+  if (!rc) rc = rows(true, 0, sv->seam[cur], 0, D);
+  if (!rc) rc = rows(true, R - D, sv->seam[cur], 3 * D, D);
   // the far rows: plain multi-step window (walls on the columns included), no pressure rows
   lbm_bc far = sv->bc;
   far.pressure_rows = 0;
-  rc = sv->model == LBM_MODEL_BGK
-           ? bgk_stream_collide_xn_ref(dst, src, &sv->g, &far, &sv->bgk, D, D, R - D, sv->st)
-           : kbc_stream_collide_x2_ref(dst, src, &sv->g, &far, &sv->kbc, D, R - D, sv->st);
-  if (rc) return rc;
-  LBM_CHECK_HIP(hipStreamWaitEvent(sv->st, sv->ev_seam_join, 0));
-  return LBM_OK;
+  if (!rc)
+    rc = sv->model == LBM_MODEL_BGK ? bgk_stream_collide_xn_ref(dst, src, &sv->g, &far, &sv->bgk, D, D, R - D, sv->st)
+                                    : kbc_stream_collide_x2_ref(dst, src, &sv->g, &far, &sv->kbc, D, R - D, sv->st);
+  return sv->seam_side.join(sv->st, rc);
 }
 
 // periodic or wall-bounded block without per-step observers: steps can be fused several per launch
@@ -546,9 +459,8 @@ int lbm_solver_attach_ibm(lbm_solver* sv, lbm_ibm* ib, double guo_a, double guo_
   }
   sv->ibm = ib;
   if (ib && !sv->side) {
-    LBM_CHECK_HIP(hipStreamCreateWithFlags(&sv->side, hipStreamNonBlocking));
-    LBM_CHECK_HIP(hipEventCreateWithFlags(&sv->ev_roi, hipEventDisableTiming));
-    LBM_CHECK_HIP(hipEventCreateWithFlags(&sv->ev_ibm, hipEventDisableTiming));
+    int rc = sv->side.create();
+    if (rc) return rc;
   }
   if (ib && !sv->band && sv->model == LBM_MODEL_BGK) {  // third lattice of the 5-step blocks (solver_ibm_block)
     const size_t bytes = (size_t)sv->g.plane_stride * 9 * sizeof(double);
@@ -563,7 +475,7 @@ int lbm_solver_attach_ibm(lbm_solver* sv, lbm_ibm* ib, double guo_a, double guo_
     if (rows > sv->box_rows_max || cols > sv->box_cols_max) {
       if (sv->box[0]) {  // a larger boundary than the one attached before: nothing may still be running on the old box
         LBM_CHECK_HIP(hipStreamSynchronize(sv->st));
-        if (sv->far_st) LBM_CHECK_HIP(hipStreamSynchronize(sv->far_st));
+        if (sv->far) LBM_CHECK_HIP(hipStreamSynchronize(sv->far.st));
       }
       for (double** p : {&sv->box[0], &sv->box[1], &sv->box_rho, &sv->box_u}) {
         if (*p) (void)hipFree(*p);
@@ -580,11 +492,9 @@ int lbm_solver_attach_ibm(lbm_solver* sv, lbm_ibm* ib, double guo_a, double guo_
       LBM_CHECK_HIP(hipMalloc(&sv->box_rho, n * sizeof(double)));
       LBM_CHECK_HIP(hipMalloc(&sv->box_u, 2 * n * sizeof(double)));
     }
-    if (!sv->far_st) {
-      int rc = make_background_stream(&sv->far_st);
+    if (!sv->far) {
+      int rc = sv->far.create(/*background=*/true);
       if (rc) return rc;
-      LBM_CHECK_HIP(hipEventCreateWithFlags(&sv->ev_far_fork, hipEventDisableTiming));
-      LBM_CHECK_HIP(hipEventCreateWithFlags(&sv->ev_far_join, hipEventDisableTiming));
     }
   }
   sv->guo_a = guo_a;

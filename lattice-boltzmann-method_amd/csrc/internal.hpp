@@ -105,6 +105,73 @@ auto with_flags(F&& f, bool flag, Rest... rest) {
 
 inline hipStream_t as_stream(lbm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// A helper stream that runs work BESIDE a main stream, and the two events that order it: fork(main) -- the helper starts
+// after everything enqueued on main so far; join(main) -- main waits for everything enqueued on the helper so far.
+struct SideStream {
+  hipStream_t st = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+
+  explicit operator bool() const { return st != nullptr; }
+  // the two events (for an owner that has made `st` itself, e.g. with a priority)
+  int create_events() {
+    LBM_CHECK_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    LBM_CHECK_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    return LBM_OK;
+  }
+  // a non-blocking stream (background: make_background_stream) and the events; all of them or, after a failure, none
+  int create(bool background = false) {
+    int rc = LBM_OK;
+    if (background) rc = make_background_stream(&st);
+    else if (hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) {
+      set_error("hipStreamCreateWithFlags failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+      rc = LBM_ERR_HIP;
+    }
+    if (!rc) rc = create_events();
+    if (rc) destroy();
+    return rc;
+  }
+  // waits for the helper's work, then releases everything; safe on a partly created or never created one
+  void destroy() {
+    if (st) {
+      (void)hipStreamSynchronize(st);
+      (void)hipStreamDestroy(st);
+    }
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    st = nullptr;
+    ev_fork = ev_join = nullptr;
+  }
+  int fork(hipStream_t main) {
+    const int rc = mark(main);
+    return rc ? rc : start();
+  }
+  // fork without an error record, for a caller that falls back to its own stream when the helper cannot be used
+  bool try_fork(hipStream_t main) {
+    return hipEventRecord(ev_fork, main) == hipSuccess && hipStreamWaitEvent(st, ev_fork, 0) == hipSuccess;
+  }
+  // fork in two halves, for a caller whose next launches on main are latency-critical: mark(main) fixes the point the helper
+  // will start after, start() -- once those launches are enqueued -- makes the helper wait for it (not for them)
+  int mark(hipStream_t main) {
+    LBM_CHECK_HIP(hipEventRecord(ev_fork, main));
+    return LBM_OK;
+  }
+  int start() {
+    LBM_CHECK_HIP(hipStreamWaitEvent(st, ev_fork, 0));
+    return LBM_OK;
+  }
+  // rc != 0: the caller failed after its fork; the join is enqueued all the same, best-effort (nothing left on the helper
+  // runs unordered against main's next use of the buffers), and rc is what returns
+  int join(hipStream_t main, int rc = LBM_OK) {
+    if (rc) {
+      if (hipEventRecord(ev_join, st) == hipSuccess) (void)hipStreamWaitEvent(main, ev_join, 0);
+      return rc;
+    }
+    LBM_CHECK_HIP(hipEventRecord(ev_join, st));
+    LBM_CHECK_HIP(hipStreamWaitEvent(main, ev_join, 0));
+    return LBM_OK;
+  }
+};
+
 // Grid for a memory-bound grid-stride kernel: enough blocks to fill 256 CUs x 8, no more
 // (cdna_hip_programming.md Guideline 11).
 inline int capped_grid(long work_items, int cap = 2048) {

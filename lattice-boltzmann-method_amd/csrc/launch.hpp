@@ -238,20 +238,16 @@ void sw_launch_part(double* pn, const double* po, const Geom& g, const Model& m,
 // Helper stream of the calling host thread on the current device: the few waves of a wall frame run
 // there, beside the interior launch on the caller's stream (fork / join through two events).  Lives
 // until the process ends; one per (thread, device).
-struct SwSideStream {
-  hipStream_t st = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
+struct SwSideStream : SideStream {
   int dev = -1;
 };
-inline SwSideStream* sw_side_stream() {
+inline SideStream* sw_side_stream() {
   static thread_local SwSideStream side[16];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   SwSideStream& s = side[dev];
   if (s.dev != dev) {
-    if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&s.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s.join, hipEventDisableTiming) != hipSuccess) {
+    if (s.create()) {  // (no helper stream: the callers run the frame on their own stream)
       (void)hipGetLastError();
       return nullptr;
     }
@@ -313,9 +309,9 @@ int sw_launch_walls(double* pn, const double* po, const Geom& g, const Model& m,
     LBM_KLAUNCH((k_stream_collide_sw_walls<Model, DV, true>), dim3((pp.n_waves + 1) / 2), dim3(128), 0, st, pn, po, g, m, bc, pp);
     return LBM_OK;
   }
-  SwSideStream* sd = sw_side_stream();
-  hipStream_t fs = st;
-  if (sd && hipEventRecord(sd->fork, st) == hipSuccess && hipStreamWaitEvent(sd->st, sd->fork, 0) == hipSuccess) fs = sd->st;
+  SideStream* sd = sw_side_stream();
+  if (sd && !sd->try_fork(st)) sd = nullptr;
+  hipStream_t fs = sd ? sd->st : st;
   // frame waves are few and latency-bound: short chunks (8 rows after 2 (D - 1) warm-up rows) keep each
   // of these launches to one brief round -- on a short row range they would otherwise outlast the interior
   sw_launch_part<Model, DV, true>(pn, po, g, m, bc, row_begin, row_end, 0, s0, 8, fs);
@@ -323,11 +319,7 @@ int sw_launch_walls(double* pn, const double* po, const Geom& g, const Model& m,
   sw_launch_part<Model, DV, true>(pn, po, g, m, bc, row_begin, ra, s0, s1 - s0, 8, fs);
   sw_launch_part<Model, DV, true>(pn, po, g, m, bc, rb, row_end, s0, s1 - s0, 8, fs);
   sw_launch_part<Model, DV, false>(pn, po, g, m, bc, ra, rb, s0, s1 - s0, 0, st);
-  if (fs != st) {
-    LBM_CHECK_HIP(hipEventRecord(sd->join, fs));
-    LBM_CHECK_HIP(hipStreamWaitEvent(st, sd->join, 0));
-  }
-  return LBM_OK;
+  return sd ? sd->join(st) : LBM_OK;
 }
 
 // what a model's window accepts: steps per launch without / with walls, the hint its mixed-axis message ends with,

@@ -309,10 +309,13 @@ def test_cylinder_with_the_default_collision(lib, oracle):
 
 
 # ---- config 5 over slabs in blocks of D steps, the boundary anywhere -- also across a seam -------------
-def _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, n_blocks, start_from_pre=False):
+def _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, n_blocks, start_from_pre=False, block_tuning=None):
     """the run through lbm_slab_ibm_* on n_slabs emulated slabs (one GPU, messages moved by device copies)
     and the same run on ONE block through the solver context; returns (P_slabs, P_block, Fs_slabs, Fs_block,
-    slab objects' roles)"""
+    slab objects' roles).  block_tuning: one {tuning key: value} per block, set for that block of the slab run
+    alone (every key is back at -1, its default, afterwards)"""
+    block_tuning = block_tuning or [{}] * n_blocks
+    assert len(block_tuning) == n_blocks
     R = X // n_slabs
     omega, u_in = 1.0 / 0.55, 0.05
     x, y = circle(cx, Y / 2 + 0.21, radius)
@@ -383,10 +386,16 @@ def _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, n_blocks, start_f
         exchange(lambda s, sl, b: lib.slab_ibm_prime_pack(sl.h, _ptr(lat[s][cur]), _ptr(b["sp"]), _ptr(b["sn"]), None),
                  lambda s, sl, b: lib.slab_ibm_prime_finish(sl.h, _ptr(lat[s][cur]), _ptr(b["rp"]), _ptr(b["rn"]), None),
                  lambda sl: (sl.prime_counts(0), sl.prime_counts(1)))
-    for _ in range(n_blocks):
+    for tune in block_tuning:
         m = lambda sl: ((sl.msg_doubles,) * 2, (sl.msg_doubles,) * 2)
-        exchange(lambda s, sl, b: lib.slab_ibm_block_compute(sl.h, _ptr(lat[s][cur ^ 1]), _ptr(lat[s][cur]), _ptr(b["sp"]), _ptr(b["sn"]), None),
-                 lambda s, sl, b: lib.slab_ibm_block_finish(sl.h, _ptr(lat[s][cur ^ 1]), _ptr(b["rp"]), _ptr(b["rn"]), None), m)
+        try:
+            for k, v in tune.items():
+                lib.set_tuning(k.encode(), v)
+            exchange(lambda s, sl, b: lib.slab_ibm_block_compute(sl.h, _ptr(lat[s][cur ^ 1]), _ptr(lat[s][cur]), _ptr(b["sp"]), _ptr(b["sn"]), None),
+                     lambda s, sl, b: lib.slab_ibm_block_finish(sl.h, _ptr(lat[s][cur ^ 1]), _ptr(b["rp"]), _ptr(b["rn"]), None), m)
+        finally:
+            for k in tune:
+                lib.set_tuning(k.encode(), -1)
         cur ^= 1
     P = torch.cat([lat[s][cur][:, D:R + D] for s in range(n_slabs)], dim=1).contiguous()
     out = torch.empty_like(P)
@@ -427,6 +436,31 @@ def test_cylinder_blocks_over_slabs_equal_single_block(lib, oracle, case):
     assert bits_equal(got, want), (case, ulp_diff(got, want))
     for F in Fs:                      # every co-owner holds the same forcing, bit for bit
         assert np.array_equal(F, Fw), (case, F, Fw)
+
+
+_SLAB_CASES = {"on_the_seam": (128.3, [(1, 0, 1), (1, 1, 0)]), "inside_slab0": (60.4, [(1, 0, 0), (0, 0, 0)])}
+
+
+@pytest.mark.parametrize("case,tunes", [
+    ("inside_slab0", [{"ibm_box_sole": 0}] * 3),   # the boxed band form without a straddle: outer rows from src
+    ("inside_slab0", [{"ibm_box": 0}] * 3),        # the full-width band, alone ...
+    ("on_the_seam", [{"ibm_box": 0}] * 3),         # ... and on both co-owners, outer rows through the stash
+    # the band lattice handed over: the sole owner leaves it stale, the boxed band form must refresh it, then full width
+    ("inside_slab0", [{}, {"ibm_box_sole": 0}, {"ibm_box": 0}]),
+], ids=["box_sole_0", "box_0", "box_0_on_the_seam", "stale_band_hand_over"])
+def test_cylinder_slab_block_forms_equal_single_block(lib, oracle, case, tunes):
+    """The forms of lbm_slab_ibm_block_compute that the default run never takes, 256 x 96 over 2 slabs, three blocks of
+    D = 5: the boxed BAND form on a slab that holds the whole band ("ibm_box_sole" = 0), the full-width band ("ibm_box"
+    = 0) on one owner and on two co-owners, and the three forms one after the other on one slab object (the sole
+    owner's block leaves the band lattice stale).  Populations and surface force equal the single block after 1 + 15
+    steps bit for bit, as in test_cylinder_blocks_over_slabs_equal_single_block."""
+    cx, want_roles = _SLAB_CASES[case]
+    got, want, Fs, Fw, roles = _slab_block_run(lib, oracle, 256, 96, 2, cx, 10.0, 5, 3, start_from_pre=case == "on_the_seam",
+                                               block_tuning=tunes)
+    assert [tuple(int(v) for v in r) for r in roles] == want_roles, roles
+    assert bits_equal(got, want), (case, tunes, ulp_diff(got, want))
+    for F in Fs:
+        assert np.array_equal(F, Fw), (case, tunes, F, Fw)
 
 
 def test_ring_ibm_block_wrappers_on_a_self_ring(lib, oracle):
