@@ -20,5 +20,6 @@ san:
 	LBM_HIP_LIB=$(CURDIR)/$(PKG)/lib_san/liblbm_hip.so LBM_ORACLE_LIB=$(CURDIR)/oracle/_build_san/liblbm_oracle.so \
 	LBM_PARAMS_DUMP=$(CURDIR)/$(PKG)/drivers/bin_san/params_dump OMP_NUM_THREADS=4 \
 	python -m pytest tests/test_oracle_golden.py tests/test_oracle_crosscheck.py tests/test_host_cpp.py tests/test_slab_plan.py tests/test_abi.py \
+	  tests/test_ade_buoyancy_abi.py \
 	  -q -m "not gpu" -p no:cacheprovider 2>&1 | tee profiles/r04_san_cpu.log
 .PHONY: all san

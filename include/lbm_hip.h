@@ -458,7 +458,8 @@ int lbm_solver_lattices(lbm_solver* sv, double** cur, double** other, lbm_geom* 
 /* ---- fluid + transported scalar (advection-diffusion; test/rectangle_sedimentation_test.cpp:88-247) -------
  * A second D2Q9 distribution g carried with a compressible BGK fluid f: the scalar's equilibrium is
  * solver::equilibrium(g_equi, u + w, C) with C = calc_rho(g) and u the fluid's velocity (:125), it relaxes with its
- * own BGK rate (:132) and streams like f (:145-146).  Dye, temperature as a passive scalar, sediment.
+ * own BGK rate (:132) and streams like f (:145-146).  Dye, temperature, sediment: passive, or pushing on the fluid through
+ * lbm_ade_buoyancy below.
  * One fused pull step per node streams both post-collision lattices, forms rho, u from f and C from g, collides both
  * and writes both (288 B per node update).  Single block (ghost = 0; row slabs: lbm_ade_stream_collide_part and
  * lbm_ring_ade_* below), C even.  Edges: PERIODIC or BOUNCE_BACK rows,
@@ -466,7 +467,8 @@ int lbm_solver_lattices(lbm_solver* sv, double** cur, double** other, lbm_geom* 
  * populations -- a no-flux wall (the driver's bottom wall, :234-236 = :180-182) -- unless lbm_ade_scalar_bc below makes
  * the edge a fixed-concentration wall.  Everything else (HALO, ABB_VELOCITY,
  * WRAP_NOSHIFT, pressure rows, ghost rows) is refused on the host.  The fluid parameters must be the plain
- * compressible model: incompressible = delta_form = force_mode = 0.  Both halves run in the form of `scalar->form`
+ * compressible model: incompressible = delta_form = force_mode = 0 (a force that follows the scalar: lbm_ade_buoyancy).
+ * Both halves run in the form of `scalar->form`
  * (LBM_FORM_DEFAULT resolves through "bgk_fast" as for BGK): REFERENCE_ORDER = solver.cpp's operation order, the fluid
  * half bitwise equal to lbm_bgk_stream_collide; REASSOCIATED = BgkFastModel for f and its counterpart for g. */
 typedef struct lbm_ade_params {
@@ -556,6 +558,49 @@ int lbm_ade_stream_collide_part_ex(double* fn, double* gn, const double* fo, con
  * against the context's edges; the descriptor is copied, a profile array is not. */
 int lbm_ade_solver_set_scalar_bc(lbm_ade_solver* sv, const lbm_ade_scalar_bc* sbc);
 
+/* Buoyancy: the transported scalar drives the fluid (Boussinesq coupling; additive to all of the above).  Per node the
+ * force is F = (C - c_ref) (beta_r, beta_c) with the node's own C = calc_rho(g), and the fluid half becomes the body-force
+ * collision of test/gravity_test.cpp:141-160 (lbm_bgk_params.force_mode) with that F.  After streaming and the fluid's
+ * wall fix-ups, in this order:
+ *   1. rho = calc_rho(f), u0 = calc_u(f, rho);
+ *   2. the scalar's wall rule (lbm_ade_scalar_bc) with v = u0 + w -- it never sees the shifted velocity;
+ *   3. C = calc_rho(g);   4. F = ((C - c_ref) beta_r, (C - c_ref) beta_c);   5. u = u0 + u_shift F;
+ *   6. feq = equilibrium(u, rho), S_q = ((1 - 0.5 omega) ((guo_a + guo_b (c_q.u)) (c_q.F) - guo_a (u.F)) w_q),
+ *      f* = f + (-omega (f - feq)) + S_q;
+ *   7. g* = collision(g, equilibrium(u + w, C)) with the same shifted u.
+ * Per collision the force changes the momentum by (omega rho u_shift + (1 - omega / 2) guo_a / 3) F: (u_shift, guo_a,
+ * guo_b) = (0.5, 3, 9) is Guo's scheme up to rho ~ 1, (1, 1/3, 1/9) the reference's (gravity_test.cpp:81-82,146,154).
+ * A NULL descriptor, or beta_r == 0 && beta_c == 0, is the passive step: the same bits and the same launches.  The forced
+ * relaxation is written as a delta form, so it rounds differently from the passive (1 - omega) f + omega feq even as
+ * beta -> 0.  A buoyant step always runs the REFERENCE order in both halves, whatever `form` says (the rule for BGK
+ * lattices with a body force), costs no launch and no halo traffic of its own, and keeps 288 B per node update.  Every
+ * field must be finite; the fluid parameters stay the plain compressible model; everything the passive calls refuse is
+ * refused, on the host, before any device call.  The moment outputs of the raw entry points are the values above: u is
+ * the shifted u of item 5 (what gravity_test's u holds after :146).  lbm_ade_solver_get_state is unchanged: it returns
+ * u = calc_u(f, rho); the velocity that enters the equilibria of the next step is u + u_shift beta (C - c_ref). */
+typedef struct lbm_ade_buoyancy {
+  double beta_r, beta_c; /* force per unit of (C - c_ref), row / column component */
+  double c_ref;
+  double u_shift;        /* multiple of F added to u before both equilibria: 1.0 = gravity_test.cpp:146 */
+  double guo_a, guo_b;   /* as lbm_bgk_params: (1/3, 1/9) = gravity_test.cpp:81-82,154 */
+} lbm_ade_buoyancy;
+/* lbm_ade_collide / lbm_ade_stream_collide_ex / _part_ex with the buoyancy; sbc and buoy may each be NULL (the
+ * collide-only call checks sbc and applies no wall rule: its input is a pre-collision state) */
+int lbm_ade_collide_b(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                      const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                      const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s);
+int lbm_ade_stream_collide_b(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                             const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                             const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int row_begin, int row_end,
+                             double* rho, double* u, double* conc, lbm_stream_t s);
+int lbm_ade_stream_collide_part_b(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                  const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int part, int edge_rows,
+                                  double* rho, double* u, double* conc, lbm_stream_t s);
+/* the context's buoyancy from the next step on; NULL = the passive scalar.  The descriptor is copied; a captured graph
+ * keeps the descriptor of its capture. */
+int lbm_ade_solver_set_buoyancy(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy);
+
 /* ---- slab ring in C++: one process per GPU, packed halo messages between row slabs ------------------
  * Native counterpart of pylbm/slab.py (same kernels, same halo sets): edge rows + pack + ONE message
  * to and from each neighbour + unpack on the ring's own high-priority stream, interior rows on the
@@ -632,6 +677,14 @@ int lbm_ring_ade_step(lbm_ring* rg, double* fn, double* gn, const double* fo, co
 int lbm_ring_ade_step_ex(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                          const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                          int edge_rows, lbm_stream_t main);
+/* lbm_ring_ade_collide / lbm_ring_ade_step_ex with the buoyancy (lbm_ade_buoyancy; sbc and buoy may each be NULL): the
+ * force is local to a node, so the messages and the schedule are those of the passive step */
+int lbm_ring_ade_collide_b(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                           const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                           const lbm_ade_buoyancy* buoy, lbm_stream_t main);
+int lbm_ring_ade_step_b(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                        const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                        const lbm_ade_buoyancy* buoy, int edge_rows, lbm_stream_t main);
 /* refresh the single-step ghost rows of two lattices in one message per neighbour (e.g. after restoring a state);
  * asynchronous, ordered after the work enqueued on `after` (lbm_ring_join makes a stream wait for it) */
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after);

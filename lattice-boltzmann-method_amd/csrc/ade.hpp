@@ -63,6 +63,94 @@ __device__ __forceinline__ void ade_collide_node(double (&f)[Q], double (&h)[Q],
   sm.collide(h, ux, uy, conc);
 }
 
+// Buoyancy (lbm_ade_buoyancy, device copy): the scalar pushes on the fluid, per node F = (C - c_ref) (beta_r, beta_c)
+// with the node's own C -- Boussinesq coupling, local, no halo and no launch of its own.  The fluid half becomes the
+// body-force collision of test/gravity_test.cpp:141-160 (BgkModel's force_mode branch, expression for expression) with
+// that per-node F:
+//   rho = calc_rho(f), u0 = calc_u(f, rho);  the scalar's wall rule (ade_fixed_walls) with u0;  C = calc_rho(g);
+//   F = ((C - c_ref) beta_r, (C - c_ref) beta_c);  u = u0 + u_shift F;  feq = equilibrium(u, rho);
+//   S_q = ((1 - 0.5 omega) ((guo_a + guo_b (c_q.u)) (c_q.F) - guo_a (u.F)) w_q);  f* = f + (-omega (f - feq)) + S_q;
+//   g* = AdeModelRef::collide(g, u) -- the same shifted u, w added inside.
+// Per collision the force changes the momentum by (omega rho u_shift + (1 - omega / 2) guo_a / 3) F: with (u_shift,
+// guo_a, guo_b) = (0.5, 3, 9) Guo's scheme up to rho ~ 1, with (1, 1/3, 1/9) the reference's.  The forced relaxation is a
+// delta form, f + (-omega (f - feq)): it rounds differently from the passive (1 - omega) f + omega feq even as beta -> 0,
+// which is why beta = (0, 0) takes the passive kernels instead.  Reference order only, in both halves.
+struct AdeBuoyancy {
+  double beta_r, beta_c, c_ref, u_shift, ga, gb;
+};
+
+// The two-node kernels hold 36 populations per lane and their passive instantiations come out at 114-128 VGPRs by
+// themselves.  The buoyant ones collide and store the scalar FIRST (it needs the shifted u, not the fluid's collision),
+// so that the forced collision -- more independent chains than the plain one -- runs with f alone in registers; they
+// also tell the compiler the occupancy to keep: four waves per SIMD at 256 threads = 128 VGPRs.
+#define LBM_ADE_WAVES(BUOYANT) __attribute__((amdgpu_waves_per_eu((BUOYANT) ? 4 : 1)))
+
+// rho = calc_rho(f), u0 = calc_u(f, rho): BgkModel::moments and the two divisions
+__device__ __forceinline__ void ade_fluid_moments(const double (&f)[Q], double& rho, double& ux, double& uy) {
+  double jx, jy;
+  BgkModel::moments(f, rho, jx, jy);
+  ux = jx / rho;
+  uy = jy / rho;
+}
+
+// F of a node from its C
+__device__ __forceinline__ void ade_buoyant_force(double conc, const AdeBuoyancy& by, double& Fr, double& Fc) {
+  const double dc = conc - by.c_ref;
+  Fr = dc * by.beta_r;
+  Fc = dc * by.beta_c;
+}
+
+// C and the shifted velocity of a buoyant node.  In: (ux, uy) = u0, h after the scalar's wall rule; out: conc =
+// calc_rho(h), (ux, uy) = u0 + u_shift F -- the velocity of BOTH collisions.
+__device__ __forceinline__ void ade_buoyant_shift(const double (&h)[Q], const AdeBuoyancy& by, double& ux, double& uy,
+                                                  double& conc) {
+  double Fr, Fc;
+  conc = ((((((((h[0] + h[1]) + h[2]) + h[3]) + h[4]) + h[5]) + h[6]) + h[7]) + h[8]);  // calc_rho(g)
+  ade_buoyant_force(conc, by, Fr, Fc);
+  ux = ux + by.u_shift * Fr;
+  uy = uy + by.u_shift * Fc;
+}
+
+// the same value, but one the compiler cannot trace back: what is formed from it is formed again, not kept in registers
+__device__ __forceinline__ double ade_again(double x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// The fluid's collision of a buoyant node: BgkModel::collide's force_mode branch with the node's F; (ux, uy) shifted,
+// conc = calc_rho(h).  rho and F are formed a second time here, from the f still in registers and from conc -- the same
+// operations on the same values, so the same bits -- instead of being held across the scalar's collision: ten
+// additions and four multiplications for five doubles of register file per node.
+__device__ __forceinline__ void ade_buoyant_fluid(double (&f)[Q], double omega, const AdeBuoyancy& by, double& rho,
+                                                  double ux, double uy, double conc) {
+  double jx, jy, Fr, Fc, e[Q];
+  f[0] = ade_again(f[0]);
+  BgkModel::moments(f, rho, jx, jy);  // calc_rho(f); the first moments are dead code
+  (void)jx;
+  (void)jy;
+  ade_buoyant_force(ade_again(conc), by, Fr, Fc);
+  BgkModel::feq_comp(e, rho, ux, uy);
+  const double uF = ux * Fr + uy * Fc;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const double cu = ux * (double)icx(q) + uy * (double)icy(q);
+    const double cF = Fr * (double)icx(q) + Fc * (double)icy(q);
+    const double S = ((1 - 0.5 * omega) * ((by.ga + by.gb * cu) * cF - by.ga * uF) * wq(q));
+    f[q] = f[q] + (-omega * (f[q] - e[q])) + S;
+  }
+}
+
+// both collisions of one buoyant node; in: (rho, ux, uy) = ade_fluid_moments(f), h after the scalar's wall rule
+// (sm.collide forms the same C again from the same h)
+template <class SM>
+__device__ __forceinline__ void ade_buoyant_collide(double (&f)[Q], double (&h)[Q], double omega, const SM& sm,
+                                                    const AdeBuoyancy& by, double& rho, double& ux, double& uy,
+                                                    double& conc) {
+  ade_buoyant_shift(h, by, ux, uy, conc);
+  sm.collide(h, ux, uy, conc);
+  ade_buoyant_fluid(f, omega, by, rho, ux, uy, conc);
+}
+
 // The scalar's fixed-concentration walls (lbm_ade_scalar_bc, device copy).  Edge e: 0 row_lo, 1 row_hi, 2 col_lo,
 // 3 col_hi.  C_w of a node: profile[e][c] on a row edge, profile[e][r] on a column edge (rows of the lattice the launch
 // sees), conc[e] where the edge has no profile.  The host checks that every FIXED edge is a wall of the fluid.
@@ -142,11 +230,12 @@ __device__ __forceinline__ void pull_pair(double (&a)[Q], double (&b)[Q], const 
 // (36 loads of 8 bytes as 18 16-byte accesses, the same stores); rows wrap (single block).  Boundary fix-ups are
 // NOT applied here: k_ade_edge recomputes the wall nodes afterwards.  Requires C % 2 == 0, even row pitch and
 // plane stride, 16-byte aligned lattices.  Moments (optional, dense [R][C] / [2][R][C]) of the streamed state.
-template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS>
-__global__ __launch_bounds__(256) void k_ade_stream_collide(
+// BUOYANT: the collisions are the buoyant ones (by; the u written is the shifted one); without it by is not read.
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool BUOYANT = false>
+__global__ __launch_bounds__(256) LBM_ADE_WAVES(BUOYANT) void k_ade_stream_collide(
     double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
     Geom g, FM fm, SM sm, int row_begin, int row_end, int tiles_per_row, double* __restrict__ rho_out,
-    double* __restrict__ u_out, double* __restrict__ c_out) {
+    double* __restrict__ u_out, double* __restrict__ c_out, AdeBuoyancy by) {
   const long items = (long)(row_end - row_begin) * tiles_per_row;
   for (long it = blockIdx.x; it < items; it += gridDim.x) {
     const int r = row_begin + (int)(it / tiles_per_row);
@@ -159,12 +248,29 @@ __global__ __launch_bounds__(256) void k_ade_stream_collide(
     pull_pair<NT_LOAD>(fa, fb, fo, g, rm, r0, rp, c);
     pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
     double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
-    ade_collide_node(fa, ha, fm, sm, rho_a, ux_a, uy_a, c_a);
-    ade_collide_node(fb, hb, fm, sm, rho_b, ux_b, uy_b, c_b);
+    if (BUOYANT) {  // g is collided and stored first: the forced collision then has the registers to itself
+      ade_fluid_moments(fa, rho_a, ux_a, uy_a);
+      ade_fluid_moments(fb, rho_b, ux_b, uy_b);
+      ade_buoyant_shift(ha, by, ux_a, uy_a, c_a);
+      ade_buoyant_shift(hb, by, ux_b, uy_b, c_b);
+      sm.collide(ha, ux_a, uy_a, c_a);
+      sm.collide(hb, ux_b, uy_b, c_b);
 #pragma unroll
-    for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+      ade_buoyant_fluid(fa, fm.omega, by, rho_a, ux_a, uy_a, c_a);
+      ade_buoyant_fluid(fb, fm.omega, by, rho_b, ux_b, uy_b, c_b);
 #pragma unroll
-    for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+    } else {
+      ade_collide_node(fa, ha, fm, sm, rho_a, ux_a, uy_a, c_a);
+      ade_collide_node(fb, hb, fm, sm, rho_b, ux_b, uy_b, c_b);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+    }
+    if (!BUOYANT) {  // (stored above otherwise)
+#pragma unroll
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    }
     if (WITH_MOMENTS) {
       const long o = (long)r * g.C + c;  // moment fields are dense
       const long n = (long)g.R * g.C;
@@ -183,12 +289,13 @@ __global__ __launch_bounds__(256) void k_ade_stream_collide(
 // listed only if its mode is a wall (the host passes which).
 // FIXED: the scalar's FIXED edges (sw) anti-bounce back between the two collisions (ade_fixed_walls); without it the
 // kernel is the no-flux pass and sw is not read.
-template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false>
+// BUOYANT: the fluid's moments first, the FIXED edges with that unshifted u0, then ade_buoyant_collide.
+template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
 __global__ __launch_bounds__(256) void k_ade_edge(double* __restrict__ fn, double* __restrict__ gn,
                                                   const double* __restrict__ fo, const double* __restrict__ go, Geom g,
                                                   Bc bc, FM fm, SM sm, int row_begin, int row_end,
                                                   double* __restrict__ rho_out, double* __restrict__ u_out,
-                                                  double* __restrict__ c_out, AdeWalls sw) {
+                                                  double* __restrict__ c_out, AdeWalls sw, AdeBuoyancy by) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x, n = row_end - row_begin;
   int r, c;
   if (i < g.C) { r = 0; c = i; if (!bc_is_wall(bc.row_lo)) return; }
@@ -203,7 +310,12 @@ __global__ __launch_bounds__(256) void k_ade_edge(double* __restrict__ fn, doubl
   if (i >= 2 * g.C + n && g.C == 1 && bc_is_wall(bc.col_lo)) return;
   double f[Q], h[Q], rho, ux, uy, conc;
   gather_walls(f, fo, g, bc, r, c);
-  if (FIXED) {
+  if (BUOYANT) {
+    gather_walls(h, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, r, c);
+    ade_fluid_moments(f, rho, ux, uy);
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+  } else if (FIXED) {
     gather_walls(h, go, g, ade_scalar_gather_bc(bc, sw.fixed), r, c);
     fm.collide(f, rho, ux, uy);
     ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
@@ -271,11 +383,14 @@ __device__ __forceinline__ void wall_fixups_pair(double (&a)[Q], double (&b)[Q],
 // wrapped on a single block (a wall row's pulled row is replaced).  Writes owned nodes only.
 // FIXED: as k_ade_edge -- g gathers with ade_scalar_gather_bc and the wall lanes anti-bounce back at the FIXED edges
 // between the two collisions of each node.
-template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool FIXED = false>
-__global__ __launch_bounds__(256) void k_ade_stream_collide_part(
+// BUOYANT: as k_ade_edge -- moments of f, the FIXED edges with u0, then g collided and stored before f.  f cannot be
+// stored before the scalar's wall rule here (its collision needs the C that rule leaves): it stays live across the rule
+// on the wall lanes.
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
+__global__ __launch_bounds__(256) LBM_ADE_WAVES(BUOYANT) void k_ade_stream_collide_part(
     double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
     Geom g, Bc bc, FM fm, SM sm, int band0, int n0, int band1, int nrows, int tiles_per_row,
-    double* __restrict__ rho_out, double* __restrict__ u_out, double* __restrict__ c_out, AdeWalls sw) {
+    double* __restrict__ rho_out, double* __restrict__ u_out, double* __restrict__ c_out, AdeWalls sw, AdeBuoyancy by) {
   const long items = (long)nrows * tiles_per_row;
   for (long it = blockIdx.x; it < items; it += gridDim.x) {
     const int v = (int)(it / tiles_per_row);
@@ -292,7 +407,25 @@ __global__ __launch_bounds__(256) void k_ade_stream_collide_part(
     if (wall) wall_fixups_pair<NT_LOAD>(fa, fb, fo, g, bc, row_lo, row_hi, r0, c);
     pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
     double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
-    if (FIXED) {  // f is stored before the scalar's walls and collisions: its registers are free for them
+    if (BUOYANT) {
+      if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, row_lo, row_hi, r0, c);
+      ade_fluid_moments(fa, rho_a, ux_a, uy_a);
+      ade_fluid_moments(fb, rho_b, ux_b, uy_b);
+      if (FIXED && wall) {
+        ade_fixed_walls(ha, g, bc, sw, r, c, ux_a, uy_a, sm.wr, sm.wc);
+        ade_fixed_walls(hb, g, bc, sw, r, c + 1, ux_b, uy_b, sm.wr, sm.wc);
+      }
+      ade_buoyant_shift(ha, by, ux_a, uy_a, c_a);
+      ade_buoyant_shift(hb, by, ux_b, uy_b, c_b);
+      sm.collide(ha, ux_a, uy_a, c_a);
+      sm.collide(hb, ux_b, uy_b, c_b);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+      ade_buoyant_fluid(fa, fm.omega, by, rho_a, ux_a, uy_a, c_a);
+      ade_buoyant_fluid(fb, fm.omega, by, rho_b, ux_b, uy_b, c_b);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
+    } else if (FIXED) {  // f is stored before the scalar's walls and collisions: its registers are free for them
       if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, ade_scalar_gather_bc(bc, sw.fixed), row_lo, row_hi, r0, c);
       fm.collide(fa, rho_a, ux_a, uy_a);
       fm.collide(fb, rho_b, ux_b, uy_b);
@@ -311,8 +444,10 @@ __global__ __launch_bounds__(256) void k_ade_stream_collide_part(
 #pragma unroll
       for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, fa[q], fb[q]);
     }
+    if (!BUOYANT) {  // (stored above otherwise)
 #pragma unroll
-    for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+      for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    }
     if (WITH_MOMENTS) {
       const long o = (long)r * g.C + c;  // moment fields are dense
       const long n = (long)g.R * g.C;
@@ -346,11 +481,12 @@ __global__ __launch_bounds__(256) void k_ade_fixed_state(double* __restrict__ hs
 }
 
 // Collide only, no streaming: the driver's first iteration on the pre-collision state (one node per thread).
-template <class FM, class SM, bool WITH_MOMENTS>
+template <class FM, class SM, bool WITH_MOMENTS, bool BUOYANT = false>
 __global__ __launch_bounds__(256) void k_ade_collide(double* __restrict__ fp, double* __restrict__ gp,
                                                      const double* __restrict__ f_in, const double* __restrict__ g_in,
                                                      Geom g, FM fm, SM sm, double* __restrict__ rho_out,
-                                                     double* __restrict__ u_out, double* __restrict__ c_out) {
+                                                     double* __restrict__ u_out, double* __restrict__ c_out,
+                                                     AdeBuoyancy by) {
   const long n_nodes = (long)g.R * g.C;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_nodes; i += (long)gridDim.x * blockDim.x) {
     const int r = (int)(i / g.C), c = (int)(i % g.C);
@@ -361,7 +497,12 @@ __global__ __launch_bounds__(256) void k_ade_collide(double* __restrict__ fp, do
       f[q] = f_in[q * g.plane + o];
       h[q] = g_in[q * g.plane + o];
     }
-    ade_collide_node(f, h, fm, sm, rho, ux, uy, conc);
+    if (BUOYANT) {
+      ade_fluid_moments(f, rho, ux, uy);
+      ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+    } else {
+      ade_collide_node(f, h, fm, sm, rho, ux, uy, conc);
+    }
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       fp[q * g.plane + o] = f[q];

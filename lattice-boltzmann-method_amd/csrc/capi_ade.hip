@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdint>
 #include <new>
+#include <type_traits>
 
 #include "ade.hpp"
 #include "launch.hpp"
@@ -89,11 +90,32 @@ static bool ade_fast(const lbm_ade_params* scalar) {
   return scalar->form == LBM_FORM_DEFAULT ? tuning("bgk_fast", 1) != 0 : scalar->form == LBM_FORM_REASSOCIATED;
 }
 
-// f(fluid model, scalar model): the reassociated pair or the reference-order pair
+// The buoyancy (lbm_ade_buoyancy, NULL allowed) on the host: every field finite.  *by receives the device copy and
+// *buoyant whether the step is a buoyant one -- beta = (0, 0), like NULL, is the passive step.
+static int ade_buoyancy_check(const char* fn, const lbm_ade_buoyancy* b, AdeBuoyancy* by, bool* buoyant) {
+  *by = AdeBuoyancy{};
+  *buoyant = false;
+  if (!b) return LBM_OK;
+  LBM_REQUIRE(std::isfinite(b->beta_r) && std::isfinite(b->beta_c), "%s: buoyancy beta=(%g, %g) must be finite", fn,
+              b->beta_r, b->beta_c);
+  LBM_REQUIRE(std::isfinite(b->c_ref), "%s: buoyancy c_ref=%g must be finite", fn, b->c_ref);
+  LBM_REQUIRE(std::isfinite(b->u_shift), "%s: buoyancy u_shift=%g must be finite", fn, b->u_shift);
+  LBM_REQUIRE(std::isfinite(b->guo_a) && std::isfinite(b->guo_b), "%s: buoyancy guo=(%g, %g) must be finite", fn,
+              b->guo_a, b->guo_b);
+  *by = AdeBuoyancy{b->beta_r, b->beta_c, b->c_ref, b->u_shift, b->guo_a, b->guo_b};
+  *buoyant = b->beta_r != 0.0 || b->beta_c != 0.0;
+  return LBM_OK;
+}
+
+// f(fluid model, scalar model, BUOYANT): the reassociated pair or the reference-order pair; a buoyant step is the
+// reference-order pair whatever the form
 template <class F>
-static int with_ade_models(const lbm_bgk_params* fluid, const lbm_ade_params* scalar, F f) {
-  if (ade_fast(scalar)) return f(BgkFastModel(fluid->omega), AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c));
-  return f(BgkModelT<0, 0>{fluid->omega}, AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c});
+static int with_ade_models(const lbm_bgk_params* fluid, const lbm_ade_params* scalar, bool buoyant, F f) {
+  if (buoyant)
+    return f(BgkModelT<0, 0>{fluid->omega}, AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, std::true_type{});
+  if (ade_fast(scalar))
+    return f(BgkFastModel(fluid->omega), AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c), std::false_type{});
+  return f(BgkModelT<0, 0>{fluid->omega}, AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c}, std::false_type{});
 }
 
 // The lattice and field arguments of a launch: four lattices given (distinct: also pairwise different and 16-byte
@@ -137,21 +159,21 @@ static int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, con
   return LBM_OK;
 }
 
-template <class FM, class SM>
+template <bool B, class FM, class SM>
 static int ade_collide_launch(double* fp, double* gp, const double* f, const double* h, const Geom& g, const FM& fm,
-                              const SM& sm, double* rho, double* u, double* conc, hipStream_t st) {
+                              const SM& sm, const AdeBuoyancy& by, double* rho, double* u, double* conc, hipStream_t st) {
   const long n = (long)g.R * g.C;
   const int grid = capped_grid((n + 255) / 256);
-  with_flags([&](auto M) { LBM_KLAUNCH((k_ade_collide<FM, SM, M()>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, g, fm, sm, rho, u, conc); }, rho != nullptr);
+  with_flags([&](auto M) { LBM_KLAUNCH((k_ade_collide<FM, SM, M(), B>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, g, fm, sm, rho, u, conc, by); }, rho != nullptr);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
 
 // interior launch + (walls only) the edge pass; *launches += the kernels enqueued
-template <class FM, class SM>
+template <bool B, class FM, class SM>
 static int ade_step_launch(double* fn, double* gn, const double* fo, const double* go, const Geom& g, const Bc& bc,
-                           const FM& fm, const SM& sm, const AdeWalls& sw, int row_begin, int row_end, double* rho,
-                           double* u, double* conc, hipStream_t st, long long* launches) {
+                           const FM& fm, const SM& sm, const AdeWalls& sw, const AdeBuoyancy& by, int row_begin,
+                           int row_end, double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
   const bool mom = rho != nullptr;
   const int nt = tuning("nt", 3);  // bit 0: non-temporal loads, bit 1: non-temporal stores
   const int cap = tuning("grid_cap", 0);
@@ -159,8 +181,8 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
   const long items = (long)(row_end - row_begin) * tiles;
   const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
   with_flags([&](auto NL, auto NS, auto M) {
-    LBM_KLAUNCH((k_ade_stream_collide<FM, SM, NL(), NS(), M()>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, fm, sm,
-                row_begin, row_end, tiles, rho, u, conc);
+    LBM_KLAUNCH((k_ade_stream_collide<FM, SM, NL(), NS(), M(), B>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, fm,
+                sm, row_begin, row_end, tiles, rho, u, conc, by);
   }, nt & 1, nt & 2, mom);
   LBM_CHECK_LAUNCH();
   ++*launches;
@@ -168,8 +190,8 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
     const int n_edge = 2 * g.C + 2 * (row_end - row_begin);
     const dim3 grid_e((n_edge + 255) / 256);
     with_flags([&](auto M, auto F) {
-      LBM_KLAUNCH((k_ade_edge<FM, SM, M(), F()>), grid_e, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin,
-                  row_end, rho, u, conc, sw);
+      LBM_KLAUNCH((k_ade_edge<FM, SM, M(), F(), B>), grid_e, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin,
+                  row_end, rho, u, conc, sw, by);
     }, mom, sw.fixed);
     LBM_CHECK_LAUNCH();
     ++*launches;
@@ -178,10 +200,10 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
 }
 
 // one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline
-template <class FM, class SM>
+template <bool B, class FM, class SM>
 static int ade_part_launch(double* fn, double* gn, const double* fo, const double* go, const Geom& g, const Bc& bc,
-                           const FM& fm, const SM& sm, const AdeWalls& sw, int band0, int n0, int band1, int nrows,
-                           double* rho, double* u, double* conc, hipStream_t st) {
+                           const FM& fm, const SM& sm, const AdeWalls& sw, const AdeBuoyancy& by, int band0, int n0,
+                           int band1, int nrows, double* rho, double* u, double* conc, hipStream_t st) {
   const bool mom = rho != nullptr;
   const int nt = tuning("nt", 3);  // as the single-block step
   const int cap = tuning("grid_cap", 0);
@@ -189,32 +211,43 @@ static int ade_part_launch(double* fn, double* gn, const double* fo, const doubl
   const long items = (long)nrows * tiles;
   const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
   with_flags([&](auto NL, auto NS, auto M, auto F) {
-    LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL(), NS(), M(), F()>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g,
-                bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, sw);
+    LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL(), NS(), M(), F(), B>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go,
+                g, bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, sw, by);
   }, nt & 1, nt & 2, mom, sw.fixed);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
 
+// collide only: no streaming, so no wall rule -- the scalar's walls (sbc) are checked and nothing more
 static int ade_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* lg,
-                       const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, double* rho,
-                       double* u, double* conc, hipStream_t st, bool slab = false) {
-  int rc = ade_validate(fn, lg, bc, fluid, scalar, slab);
+                       const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                       const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc,
+                       hipStream_t st, bool slab = false) {
+  AdeWalls sw;
+  AdeBuoyancy by;
+  bool buoyant;
+  int rc = ade_scalar_bc_check(fn, sbc, bc, &sw);
+  if (!rc) rc = ade_validate(fn, lg, bc, fluid, scalar, slab);
+  if (!rc) rc = ade_buoyancy_check(fn, buoy, &by, &buoyant);
   if (!rc) rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false);
   if (rc) return rc;
   const Geom g = make_geom(*lg);
-  return with_ade_models(fluid, scalar, [&](const auto& fm, const auto& sm) {
-    return ade_collide_launch(fp, gp, f, h, g, fm, sm, rho, u, conc, st);
+  return with_ade_models(fluid, scalar, buoyant, [&](const auto& fm, const auto& sm, auto B) {
+    return ade_collide_launch<B()>(fp, gp, f, h, g, fm, sm, by, rho, u, conc, st);
   });
 }
 
 static int ade_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
                               const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
-                              const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, int row_begin, int row_end,
-                              double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
+                              const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
+                              int row_begin, int row_end, double* rho, double* u, double* conc, hipStream_t st,
+                              long long* launches) {
   AdeWalls sw;  // the scalar's walls first: a FIXED edge names the edge mode it cannot sit on
+  AdeBuoyancy by;
+  bool buoyant;
   int rc = ade_scalar_bc_check(fn, sbc, lbc, &sw);
   if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar);
+  if (!rc) rc = ade_buoyancy_check(fn, buoy, &by, &buoyant);
   if (!rc) rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true);
   if (rc) return rc;
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R, "%s: row range [%d, %d) outside [0, %d)", fn,
@@ -222,8 +255,8 @@ static int ade_stream_collide(const char* fn, double* fn_, double* gn, const dou
   if (row_begin == row_end) return LBM_OK;
   const Geom g = make_geom(*lg);
   const Bc bc = make_bc(lbc);
-  return with_ade_models(fluid, scalar, [&](const auto& fm, const auto& sm) {
-    return ade_step_launch(fn_, gn, fo, go, g, bc, fm, sm, sw, row_begin, row_end, rho, u, conc, st, launches);
+  return with_ade_models(fluid, scalar, buoyant, [&](const auto& fm, const auto& sm, auto B) {
+    return ade_step_launch<B()>(fn_, gn, fo, go, g, bc, fm, sm, sw, by, row_begin, row_end, rho, u, conc, st, launches);
   });
 }
 
@@ -245,13 +278,22 @@ int ade_scalar_bc_validate(const char* fn, const lbm_ade_scalar_bc* sbc, const l
   return ade_scalar_bc_check(fn, sbc, bc, &sw);
 }
 
-// lbm_ade_stream_collide_part(_ex) under the caller's name
+int ade_buoyancy_validate(const char* fn, const lbm_ade_buoyancy* buoy) {
+  AdeBuoyancy by;
+  bool buoyant;
+  return ade_buoyancy_check(fn, buoy, &by, &buoyant);
+}
+
+// lbm_ade_stream_collide_part(_ex, _b) under the caller's name
 static int ade_part(const char* name, double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                     const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                    const lbm_ade_scalar_bc* sbc, int part, int edge_rows, double* rho, double* u, double* conc,
-                    hipStream_t st) {
+                    const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int part, int edge_rows, double* rho,
+                    double* u, double* conc, hipStream_t st) {
   AdeWalls sw;  // the scalar's walls first, as ade_stream_collide
+  AdeBuoyancy by;
+  bool buoyant;
   int rc = ade_scalar_bc_check(name, sbc, lbc, &sw);
+  if (!rc) rc = ade_buoyancy_check(name, buoy, &by, &buoyant);
   if (!rc) rc = ade_part_check(name, fn, gn, fo, go, lg, lbc, fluid, scalar, part, edge_rows, rho, u, conc);
   if (rc) return rc;
   const int R = lg->R;
@@ -261,8 +303,8 @@ static int ade_part(const char* name, double* fn, double* gn, const double* fo, 
   const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;
   const int n0 = part == LBM_ADE_PART_FRAME ? edge_rows : R - 2 * edge_rows;
   const int band1 = R - edge_rows, nrows = part == LBM_ADE_PART_FRAME ? 2 * edge_rows : n0;
-  return with_ade_models(fluid, scalar, [&](const auto& fm, const auto& sm) {
-    return ade_part_launch(fn, gn, fo, go, g, bc, fm, sm, sw, band0, n0, band1, nrows, rho, u, conc, st);
+  return with_ade_models(fluid, scalar, buoyant, [&](const auto& fm, const auto& sm, auto B) {
+    return ade_part_launch<B()>(fn, gn, fo, go, g, bc, fm, sm, sw, by, band0, n0, band1, nrows, rho, u, conc, st);
   });
 }
 
@@ -272,8 +314,9 @@ int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const
 }
 
 int ade_collide_slab(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
-                     const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, hipStream_t st) {
-  return ade_collide(fn, fp, gp, f, h, g, bc, fluid, scalar, nullptr, nullptr, nullptr, st, true);
+                     const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                     const lbm_ade_buoyancy* buoy, hipStream_t st) {
+  return ade_collide(fn, fp, gp, f, h, g, bc, fluid, scalar, nullptr, buoy, nullptr, nullptr, nullptr, st, true);
 }
 
 }  // namespace lbm
@@ -287,6 +330,8 @@ struct lbm_ade_solver {
   lbm_ade_params scalar;
   lbm_ade_scalar_bc sbc;  // all NO_FLUX unless set
   bool fixed;             // some edge of sbc is FIXED
+  lbm_ade_buoyancy buoy;  // lbm_ade_solver_set_buoyancy
+  bool buoyant;           // buoy is set (beta = (0, 0) included: the launches decide)
   hipStream_t st;
   double* lat[2];
   double* dense;  // [9][R][C] SoA scratch of get_state
@@ -306,15 +351,22 @@ extern "C" {
 int lbm_ade_collide(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
                     const lbm_bgk_params* fluid, const lbm_ade_params* scalar, double* rho, double* u, double* conc,
                     lbm_stream_t s) {
-  return ade_collide("lbm_ade_collide", fp, gp, f, g_in, g, bc, fluid, scalar, rho, u, conc, as_stream(s));
+  return ade_collide("lbm_ade_collide", fp, gp, f, g_in, g, bc, fluid, scalar, nullptr, nullptr, rho, u, conc,
+                     as_stream(s));
+}
+
+int lbm_ade_collide_b(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                      const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                      const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s) {
+  return ade_collide("lbm_ade_collide_b", fp, gp, f, g_in, g, bc, fluid, scalar, sbc, buoy, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_stream_collide(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                            const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int row_begin,
                            int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
   long long launches = 0;
-  return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, nullptr, row_begin, row_end,
-                            rho, u, conc, as_stream(s), &launches);
+  return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, nullptr, nullptr, row_begin,
+                            row_end, rho, u, conc, as_stream(s), &launches);
 }
 
 int lbm_ade_stream_collide_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
@@ -322,23 +374,40 @@ int lbm_ade_stream_collide_ex(double* fn, double* gn, const double* fo, const do
                               const lbm_ade_scalar_bc* sbc, int row_begin, int row_end, double* rho, double* u,
                               double* conc, lbm_stream_t s) {
   long long launches = 0;
-  return ade_stream_collide("lbm_ade_stream_collide_ex", fn, gn, fo, go, g, bc, fluid, scalar, sbc, row_begin, row_end,
-                            rho, u, conc, as_stream(s), &launches);
+  return ade_stream_collide("lbm_ade_stream_collide_ex", fn, gn, fo, go, g, bc, fluid, scalar, sbc, nullptr, row_begin,
+                            row_end, rho, u, conc, as_stream(s), &launches);
+}
+
+int lbm_ade_stream_collide_b(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                             const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                             const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int row_begin, int row_end,
+                             double* rho, double* u, double* conc, lbm_stream_t s) {
+  long long launches = 0;
+  return ade_stream_collide("lbm_ade_stream_collide_b", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, row_begin,
+                            row_end, rho, u, conc, as_stream(s), &launches);
 }
 
 int lbm_ade_stream_collide_part(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                                 const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int part,
                                 int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, fluid, scalar, nullptr, part, edge_rows, rho,
-                  u, conc, as_stream(s));
+  return ade_part("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, fluid, scalar, nullptr, nullptr, part,
+                  edge_rows, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_stream_collide_part_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                                    const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                                    const lbm_ade_scalar_bc* sbc, int part, int edge_rows, double* rho, double* u,
                                    double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part_ex", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, part, edge_rows, rho, u,
-                  conc, as_stream(s));
+  return ade_part("lbm_ade_stream_collide_part_ex", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, nullptr, part,
+                  edge_rows, rho, u, conc, as_stream(s));
+}
+
+int lbm_ade_stream_collide_part_b(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
+                                  const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int part, int edge_rows,
+                                  double* rho, double* u, double* conc, lbm_stream_t s) {
+  return ade_part("lbm_ade_stream_collide_part_b", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, buoy, part, edge_rows,
+                  rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
@@ -356,6 +425,8 @@ int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc*
   sv->scalar = *scalar;
   sv->sbc = lbm_ade_scalar_bc{};
   sv->fixed = false;
+  sv->buoy = lbm_ade_buoyancy{};
+  sv->buoyant = false;
   sv->st = as_stream(s);
   sv->cur = 0;
   sv->post = false;
@@ -414,17 +485,18 @@ int lbm_ade_solver_set_state(lbm_ade_solver* sv, const double* f_host, const dou
 // (one launch, two with wall edges).  Enqueues only: no allocation, no host synchronisation.
 int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
   LBM_REQUIRE(sv && n >= 0, "lbm_ade_solver_step: bad argument (n=%d)", n);
+  const lbm_ade_buoyancy* buoy = sv->buoyant ? &sv->buoy : nullptr;
   for (int i = 0; i < n; ++i) {
     const int k = sv->cur, o = k ^ 1;
     int rc;
     if (!sv->post) {
       rc = ade_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid,
-                       &sv->scalar, nullptr, nullptr, nullptr, sv->st);
+                       &sv->scalar, nullptr, buoy, nullptr, nullptr, nullptr, sv->st);
       if (!rc) ++sv->launches;
     } else {
       rc = ade_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
-                              &sv->fluid, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, 0, sv->g.R, nullptr, nullptr,
-                              nullptr, sv->st, &sv->launches);
+                              &sv->fluid, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, buoy, 0, sv->g.R, nullptr,
+                              nullptr, nullptr, sv->st, &sv->launches);
     }
     if (rc) return rc;
     sv->cur = o;
@@ -436,7 +508,8 @@ int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
 
 // What the reference loop holds after the iterations run so far: f_adve, g_adve (AoS [R][C][9]),
 // rho = calc_rho(f_adve), u = calc_u(f_adve, rho) (AoS [R][C][2]), C = calc_rho(g_adve), through the parity
-// operators whatever the form.  The post-collision state is streamed lazily (lbm_stream: the fix-ups are the
+// operators whatever the form and with or without buoyancy (u is calc_u(f_adve, rho): the velocity that enters the
+// next step's equilibria is u + u_shift beta (C - c_ref)).  The post-collision state is streamed lazily (lbm_stream: the fix-ups are the
 // same for both distributions) into the dead time level.  Any output may be NULL; synchronises.
 int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, double* rho, double* u, double* conc) {
   LBM_REQUIRE(sv, "lbm_ade_solver_get_state: NULL solver");
@@ -533,6 +606,15 @@ int lbm_ade_solver_set_scalar_bc(lbm_ade_solver* sv, const lbm_ade_scalar_bc* sb
   if (rc) return rc;
   sv->sbc = sbc ? *sbc : lbm_ade_scalar_bc{};
   sv->fixed = sw.fixed != 0;
+  return LBM_OK;
+}
+
+int lbm_ade_solver_set_buoyancy(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy) {
+  LBM_REQUIRE(sv, "lbm_ade_solver_set_buoyancy: NULL solver");
+  int rc = ade_buoyancy_validate("lbm_ade_solver_set_buoyancy", buoy);
+  if (rc) return rc;
+  sv->buoy = buoy ? *buoy : lbm_ade_buoyancy{};
+  sv->buoyant = buoy != nullptr;
   return LBM_OK;
 }
 

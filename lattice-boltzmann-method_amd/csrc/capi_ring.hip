@@ -323,10 +323,13 @@ static int ring_ade_edges(const char* fn, lbm_ring* rg, const lbm_bc* bc, const 
 // them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches
 static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go,
                          const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                         const lbm_ade_scalar_bc* gsbc, int edge_rows, lbm_stream_t main_s) {
+                         const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, int edge_rows,
+                         lbm_stream_t main_s) {
+  int rc = ade_buoyancy_validate(fn, buoy);  // needs no ring
+  if (rc) return rc;
   LBM_REQUIRE(rg && fn_ && gn && fo && go && fluid && scalar, "%s: NULL argument", fn);
   lbm_bc b;
-  int rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
+  rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
   if (rc) return rc;
   // the scalar's walls: checked against the global edges; a FIXED row acts where the slab keeps that edge (a chain end)
   // and is dropped at a seam, as the fluid's row wall is
@@ -347,8 +350,8 @@ static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, 
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
   auto part = [&](int which, hipStream_t st) {
-    return lbm_ade_stream_collide_part_ex(fn_, gn, fo, go, &rg->g, &b, fluid, scalar, sbc, which, edge_rows, nullptr,
-                                          nullptr, nullptr, st);
+    return lbm_ade_stream_collide_part_b(fn_, gn, fo, go, &rg->g, &b, fluid, scalar, sbc, buoy, which, edge_rows, nullptr,
+                                         nullptr, nullptr, st);
   };
   if (rg->prev < 0 && rg->next < 0) {  // a chain of one slab: nothing travels
     rc = part(LBM_ADE_PART_FRAME, main);
@@ -629,28 +632,50 @@ int lbm_ring_cg_step(lbm_ring* rg, double* dst_r, double* dst_b, const double* s
   return ring_step(rg, main, edges, interior, dst_r, dst_b, LBM_HALO_TWO_PHASE);
 }
 
-int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
-                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, lbm_stream_t main_s) {
-  const char* fn = "lbm_ring_ade_collide";
+// lbm_ring_ade_collide(_b) under the caller's name; gsbc: the scalar's walls of the global domain, checked only (the
+// collide-only iteration applies no wall rule)
+static int ring_ade_collide(const char* fn, lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in,
+                            const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                            const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, lbm_stream_t main_s) {
+  int rc = ade_buoyancy_validate(fn, buoy);  // needs no ring
+  if (rc) return rc;
   LBM_REQUIRE(rg && fp && gp && f && g_in && fluid && scalar, "%s: NULL argument", fn);
   lbm_bc b;
-  int rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
+  rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
+  if (!rc) rc = ade_scalar_bc_validate(fn, gsbc, bc ? bc : &kPeriodicBc);
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
-  rc = ade_collide_slab(fn, fp, gp, f, g_in, &rg->g, &b, fluid, scalar, main);
+  rc = ade_collide_slab(fn, fp, gp, f, g_in, &rg->g, &b, fluid, scalar, buoy, main);
   if (rc || (rg->prev < 0 && rg->next < 0)) return rc;
   return ring_join(rg, main, ring_exchange_depth(rg, fp, gp, 1, main));
 }
 
+int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, lbm_stream_t main_s) {
+  return ring_ade_collide("lbm_ring_ade_collide", rg, fp, gp, f, g_in, bc, fluid, scalar, nullptr, nullptr, main_s);
+}
+
+int lbm_ring_ade_collide_b(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                           const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                           const lbm_ade_buoyancy* buoy, lbm_stream_t main_s) {
+  return ring_ade_collide("lbm_ring_ade_collide_b", rg, fp, gp, f, g_in, bc, fluid, scalar, sbc, buoy, main_s);
+}
+
 int lbm_ring_ade_step(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                       const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step", rg, fn_, gn, fo, go, bc, fluid, scalar, nullptr, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step", rg, fn_, gn, fo, go, bc, fluid, scalar, nullptr, nullptr, edge_rows, main_s);
 }
 
 int lbm_ring_ade_step_ex(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                          const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                          int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step_ex", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step_ex", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, nullptr, edge_rows, main_s);
+}
+
+int lbm_ring_ade_step_b(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                        const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                        const lbm_ade_buoyancy* buoy, int edge_rows, lbm_stream_t main_s) {
+  return ring_ade_step("lbm_ring_ade_step_b", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, edge_rows, main_s);
 }
 
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after) {

@@ -55,10 +55,13 @@ int ade_part_check(const char* fn, const double* f_new, const double* g_new, con
                    int part, int edge_rows, const double* rho, const double* u, const double* conc);
 // the scalar's walls (lbm_ade_scalar_bc, NULL allowed) against the edges bc, on the host
 int ade_scalar_bc_validate(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc);
+// the buoyancy (lbm_ade_buoyancy, NULL allowed), on the host: every field finite
+int ade_buoyancy_validate(const char* fn, const lbm_ade_buoyancy* buoy);
 int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
                       const lbm_ade_params* scalar);
 int ade_collide_slab(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
-                     const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, hipStream_t st);
+                     const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                     const lbm_ade_buoyancy* buoy /* may be NULL */, hipStream_t st);
 // NumPy .npy (v1.0, little-endian f64, C order) writer shared by the snapshot objects
 int write_npy(const char* path, const double* data, const std::vector<long>& shape);
 

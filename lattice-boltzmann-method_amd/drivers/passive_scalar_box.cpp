@@ -4,10 +4,12 @@
 // f = equilibrium(u, rho); a Gaussian blob C = C0 exp(-|x - x_c|^2 / (2 sigma^2)) at the centre, g = equilibrium(u, C)
 // (as the driver initialises g_adve, :95).
 //   usage: passive_scalar_box R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]
-//          [--fixed edge=C_w[,edge=C_w...]]
+//          [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]
 // --dump writes prefix-{f0,g0,f,g,rho,u,C}.f64 (raw f64, reference layout [R][C][Q]); --walls 1: bounce-back columns,
 // 2: bounce-back rows and columns.  --fixed: the named edges (row_lo, row_hi, col_lo, col_hi; walls of the fluid) hold
-// the scalar at the constant C_w (lbm_ade_scalar_bc FIXED), the others stay no-flux.
+// the scalar at the constant C_w (lbm_ade_scalar_bc FIXED), the others stay no-flux.  --buoyancy: the scalar pushes on the
+// fluid with F = beta (C - c_ref) per node (lbm_ade_buoyancy; u_shift, guo_a, guo_b default to 1, 1/3, 1/9); without it
+// the scalar is passive.
 #include <cmath>
 #include <iostream>
 #include <sstream>
@@ -19,7 +21,7 @@
 int main(int argc, char** argv) {
   if (argc < 8) {
     std::cerr << "usage: " << argv[0] << " R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]"
-                 " [--fixed edge=C_w[,edge=C_w...]]\n";
+                 " [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]\n";
     return 1;
   }
   try {
@@ -40,6 +42,8 @@ int main(int argc, char** argv) {
       sbc.mode[e] = LBM_ADE_SCALAR_FIXED;
       sbc.conc[e] = std::stod(item.substr(eq + 1));
     }
+    double bv[6];
+    const bool buoyant = parse_buoyancy(arg_value(argc, argv, "--buoyancy", ""), bv);
     if (lbm_device_count() < 1) {
       std::cerr << "no HIP device available\n";
       return 2;
@@ -67,6 +71,7 @@ int main(int argc, char** argv) {
     if (walls == 2) bc.row_lo = bc.row_hi = LBM_EDGE_BOUNCE_BACK;
     lbm::AdeSolver sv(R, C, omega, omega_g, w_r, w_c, bc, form);
     sv.set_scalar_bc(sbc);
+    if (buoyant) sv.set_buoyancy(lbm_ade_buoyancy{bv[0], bv[1], bv[2], bv[3], bv[4], bv[5]});
     sv.set_state(f0, g0);
     sv.step(steps);
     const lbm::AdeSolver::State s = sv.state();

@@ -17,6 +17,8 @@
 //          chain at C_w = 1e-3, column 0 at a profile, 1e-3 on the last quarter of the global rows and 0 elsewhere, read
 //          from a device array of which each slab passes its slice, column C-1 absorbing, C_w = 0, beside the specular
 //          fluid column; the last row stays no-flux)
+//          --buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b] (the scalar pushes on the fluid, lbm_ade_buoyancy: the
+//          _b entry points, reference order whatever --form; --check's one block runs the same buoyant step)
 //
 // Printed: one JSON line; ms per step of the slowest slab, and the one-block step of a slab-sized lattice beside it.
 //
@@ -32,6 +34,17 @@ struct Args : RingOpts {
   int walls = 0, scalar_fixed = 0;
   double omega = 1.2, omega_g = 1.7;
   bool fast = true;
+  bool buoyant = false;
+  lbm_ade_buoyancy buoy{};
+  const lbm_ade_buoyancy* buoyancy() const { return buoyant ? &buoy : nullptr; }
+  // the JSON line's field, empty without --buoyancy
+  std::string buoyancy_field() const {
+    if (!buoyant) return "";
+    char t[256];
+    std::snprintf(t, sizeof t, ", \"buoyancy\": [%.17g, %.17g, %.17g, %.17g, %.17g, %.17g]", buoy.beta_r, buoy.beta_c,
+                  buoy.c_ref, buoy.u_shift, buoy.guo_a, buoy.guo_b);
+    return t;
+  }
 };
 
 // shear wave + Taylor-Green vortices on the GLOBAL box, scalar: a Gaussian blob; f = feq(u, rho), g = feq(u + w, C) in
@@ -128,11 +141,12 @@ void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_pa
   double* prof = scalar_profile(a, Rg);
   const lbm_ade_scalar_bc sbc = scalar_bc(prof, 0, bc);
   upload_rows(f[0], h[0], g, 0, Rg);
-  check(lbm_ade_collide(f[1], h[1], f[0], h[0], &g, &bc, &fl, &sc, nullptr, nullptr, nullptr, nullptr), "lbm_ade_collide");
+  check(lbm_ade_collide_b(f[1], h[1], f[0], h[0], &g, &bc, &fl, &sc, nullptr, a.buoyancy(), nullptr, nullptr, nullptr,
+                          nullptr), "lbm_ade_collide_b");
   int cur = 1;
   for (int t = 0; t < a.warmup + a.steps; ++t, cur ^= 1)
-    check(lbm_ade_stream_collide_ex(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr, 0, Rg,
-                                    nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_ex");
+    check(lbm_ade_stream_collide_b(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr,
+                                   a.buoyancy(), 0, Rg, nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_b");
   if (prof) lbm_free(prof);
   f_out = owned_to_host(f[cur], g);
   g_out = owned_to_host(h[cur], g);
@@ -157,10 +171,10 @@ struct SlabSizedBlock {
     }
     upload_rows(f[0], h[0], g, 0, R);
   }
-  void step(const lbm_bgk_params& fl, const lbm_ade_params& sc, bool timed) {
+  void step(const lbm_bgk_params& fl, const lbm_ade_params& sc, const lbm_ade_buoyancy* by, bool timed) {
     check(lbm_event_record(ev[0], nullptr), "event");
-    check(lbm_ade_stream_collide(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, nullptr, &fl, &sc, 0, g.R, nullptr, nullptr,
-                                 nullptr, nullptr), "lbm_ade_stream_collide");
+    check(lbm_ade_stream_collide_b(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, nullptr, &fl, &sc, nullptr, by, 0, g.R,
+                                   nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_b");
     check(lbm_event_record(ev[1], nullptr), "event");
     float m = 0;
     check(lbm_event_elapsed_ms(&m, ev[0], ev[1]), "elapsed");
@@ -203,7 +217,8 @@ int run_emulated(const Args& a, int N) {
     const lbm_geom gg{Rg, C, 0, 0, 0};
     double *f0 = alloc_lattice(gg), *h0 = alloc_lattice(gg), *fp = alloc_lattice(gg), *hp = alloc_lattice(gg);
     upload_rows(f0, h0, gg, 0, Rg);
-    check(lbm_ade_collide(fp, hp, f0, h0, &gg, &gbc, &fl, &sc, nullptr, nullptr, nullptr, nullptr), "lbm_ade_collide");
+    check(lbm_ade_collide_b(fp, hp, f0, h0, &gg, &gbc, &fl, &sc, nullptr, a.buoyancy(), nullptr, nullptr, nullptr, nullptr),
+          "lbm_ade_collide_b");
     for (int k = 0; k < N; ++k) {
       Slab& s = S[k];
       s.bc = gbc;
@@ -231,9 +246,9 @@ int run_emulated(const Args& a, int N) {
   EdgeStream es;
   SlabSizedBlock block(R, C);
   auto part = [&](Slab& s, int cur, int which, lbm_stream_t st) {
-    check(lbm_ade_stream_collide_part_ex(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
-                                         prof ? &s.sbc : nullptr, which, E, nullptr, nullptr, nullptr, st),
-          "lbm_ade_stream_collide_part_ex");
+    check(lbm_ade_stream_collide_part_b(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
+                                        prof ? &s.sbc : nullptr, a.buoyancy(), which, E, nullptr, nullptr, nullptr, st),
+          "lbm_ade_stream_collide_part_b");
   };
   auto pack = [&](int k, double* f, double* h, lbm_stream_t st) {
     for (int side = 0; side < 2; ++side) {
@@ -269,7 +284,7 @@ int run_emulated(const Args& a, int N) {
       }
       links.add_elapsed(k, i >= a.warmup);
     }
-    block.step(fl, sc, i >= a.warmup);  // alternated with the chain's step
+    block.step(fl, sc, a.buoyancy(), i >= a.warmup);  // alternated with the chain's step
     cur ^= 1;
   }
   check(lbm_stream_sync(es.edge), "sync");
@@ -290,7 +305,7 @@ int run_emulated(const Args& a, int N) {
               closed ? "closed ring" : "chain", N, R, C, Rg, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, E,
               2 * lbm_halo_rows(1), slowest, blk, blk / slowest);
   for (int k = 0; k < N; ++k) std::printf("%s%.4f", k ? ", " : "", links.ms(k) / a.steps);
-  std::printf("]%s}\n", check_field(a.check, bad));
+  std::printf("]%s%s}\n", a.buoyancy_field().c_str(), check_field(a.check, bad));
   std::fflush(stdout);
   for (auto& s : S)
     for (int b = 0; b < 2; ++b) {
@@ -313,13 +328,14 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   check(lbm_ring_create(&ring, id, rank, world, &g, /*periodic=*/a.walls ? 0 : 1), "lbm_ring_create");
   double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
   upload_rows(f[1], h[1], g, rank * R, Rg);  // pre-collision, then the first driver iteration: collide + one exchange
-  check(lbm_ring_ade_collide(ring, f[0], h[0], f[1], h[1], &gbc, &fl, &sc, nullptr), "lbm_ring_ade_collide");
+  check(lbm_ring_ade_collide_b(ring, f[0], h[0], f[1], h[1], &gbc, &fl, &sc, nullptr, a.buoyancy(), nullptr),
+        "lbm_ring_ade_collide_b");
   double* prof = scalar_profile(a, Rg);
   const lbm_ade_scalar_bc sbc = scalar_bc(prof, rank * R, gbc);  // the global descriptor, this slab's profile rows
   int cur = 0;
   auto step = [&]() {
-    check(lbm_ring_ade_step_ex(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
-                               a.edge_rows, nullptr), "lbm_ring_ade_step_ex");
+    check(lbm_ring_ade_step_b(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
+                              a.buoyancy(), a.edge_rows, nullptr), "lbm_ring_ade_step_b");
     cur ^= 1;
   };
   double tmax = 0;
@@ -340,14 +356,14 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   if (rank == 0) {
     // the one-block step of a slab-sized lattice on this GPU, after the ring's run
     SlabSizedBlock block(R, C);
-    for (int i = 0; i < a.warmup + a.steps; ++i) block.step(fl, sc, i >= a.warmup);
+    for (int i = 0; i < a.warmup + a.steps; ++i) block.step(fl, sc, a.buoyancy(), i >= a.warmup);
     const double ms = 1e3 * tmax / a.steps, blk = block.ms / a.steps;
     std::printf("{\"driver\": \"slab_ring_ade\", \"n_gpus\": %d, \"rows_per_gpu\": %d, \"cols\": %d, \"walls\": %d, "
                 "\"scalar_fixed\": %d, \"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, \"message_rows_per_side\": %d, "
                 "\"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, "
-                "\"mlups\": %.1f%s}\n",
+                "\"mlups\": %.1f%s%s}\n",
                 world, R, C, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, a.edge_rows, 2 * lbm_halo_rows(1), ms, blk, blk / ms,
-                (double)Rg * C / (ms * 1e3), check_field(a.check, bad));
+                (double)Rg * C / (ms * 1e3), a.buoyancy_field().c_str(), check_field(a.check, bad));
     std::fflush(stdout);
   }
   lbm_ring_destroy(ring);
@@ -380,5 +396,13 @@ int main(int argc, char** argv) {
     return 2;
   }
   a.fast = form == "fast";
+  try {
+    double bv[6];
+    a.buoyant = parse_buoyancy(arg_value(argc, argv, "--buoyancy", ""), bv);
+    if (a.buoyant) a.buoy = lbm_ade_buoyancy{bv[0], bv[1], bv[2], bv[3], bv[4], bv[5]};
+  } catch (const std::exception& e) {
+    std::fprintf(stderr, "slab_ring_ade: %s\n", e.what());
+    return 2;
+  }
   return ring_main("slab_ring_ade", a, run_rank, run_emulated);
 }

@@ -160,7 +160,8 @@ class Solver {  // single-phase BGK / KBC block, wraps lbm_solver
 
 // Compressible BGK fluid + transported scalar on one block, wraps lbm_ade_solver: the sediment concentration of
 // test/rectangle_sedimentation_test.cpp:88-247 (equilibrium(g_equi, u + w, C), its own BGK rate, streamed like f;
-// no-flux walls, or fixed-concentration ones through set_scalar_bc).  Host arrays in the reference layout.
+// no-flux walls, or fixed-concentration ones through set_scalar_bc; passive, or driving the fluid through set_buoyancy).
+// Host arrays in the reference layout.
 class AdeSolver {
  public:
   AdeSolver(int R, int C, double omega, double omega_g, double w_r, double w_c, const lbm_bc& bc = BoundarySet(),
@@ -185,6 +186,9 @@ class AdeSolver {
   // the scalar's walls from the next stream on: NO_FLUX or FIXED per edge (lbm_ade_scalar_bc; a profile is a device
   // array the caller keeps alive and may rewrite between steps)
   void set_scalar_bc(const lbm_ade_scalar_bc& sbc) { check(lbm_ade_solver_set_scalar_bc(h_, &sbc)); }
+  // the scalar pushes on the fluid from the next step on: F = beta (C - c_ref) per node (lbm_ade_buoyancy; beta = (0, 0)
+  // is the passive scalar).  state().u stays calc_u(f, rho): the equilibria take u + u_shift F.
+  void set_buoyancy(const lbm_ade_buoyancy& b) { check(lbm_ade_solver_set_buoyancy(h_, &b)); }
   // what the reference loop holds after the iterations run so far
   struct State {
     std::vector<double> f, g;  // [R][C][9]

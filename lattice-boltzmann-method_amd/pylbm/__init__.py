@@ -111,6 +111,17 @@ class AdeScalarBC(ct.Structure):
                 self._keep.append(prof)
 
 
+class AdeBuoyancy(ct.Structure):
+    """lbm_ade_buoyancy: the scalar pushes on the fluid (Boussinesq), per node F = beta * (C - c_ref), rows / columns.
+    u_shift * F is added to u before both equilibria and guo = (a, b) are the source term's coefficients: the defaults
+    (1, (1/3, 1/9)) are the reference's gravity_test.cpp, (0.5, (3, 9)) is Guo's scheme.  beta = (0, 0) is the passive step."""
+    _fields_ = [("beta_r", ct.c_double), ("beta_c", ct.c_double), ("c_ref", ct.c_double), ("u_shift", ct.c_double),
+                ("guo_a", ct.c_double), ("guo_b", ct.c_double)]
+
+    def __init__(self, beta=(0.0, 0.0), c_ref=0.0, u_shift=1.0, guo=(1.0 / 3.0, 1.0 / 9.0)):
+        super().__init__(beta[0], beta[1], c_ref, u_shift, guo[0], guo[1])
+
+
 class LbmError(RuntimeError):
     pass
 
@@ -259,25 +270,32 @@ class AdeSolver:
     """Python face of lbm_ade_solver: a compressible BGK fluid f and a transported scalar g on one block
     (the sediment loop of test/rectangle_sedimentation_test.cpp), numpy AoS in/out, reference layout."""
 
-    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None, scalar_bc=None):
+    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None, scalar_bc=None, buoyancy=None):
         self.lib, self.R, self.C, self.fluid, self.scalar = lib, R, C, fluid, scalar
         self.g = Geom(R, C, 0)
         self.bc = bc if bc is not None else Bc.periodic()
         self.h = ct.c_void_p()
         lib.ade_solver_create(ct.byref(self.h), ct.byref(self.g), ct.byref(self.bc), ct.byref(fluid),
                               ct.byref(scalar), _stream(stream))
-        self.scalar_bc = None
-        if scalar_bc is not None:
-            try:
+        self.scalar_bc = self.buoyancy = None
+        try:
+            if scalar_bc is not None:
                 self.set_scalar_bc(scalar_bc)
-            except LbmError:
-                self.close()
-                raise
+            if buoyancy is not None:
+                self.set_buoyancy(buoyancy)
+        except LbmError:
+            self.close()
+            raise
 
     def set_scalar_bc(self, scalar_bc):
         """the scalar's walls from the next stream on (AdeScalarBC, or None: all NO_FLUX)"""
         self.lib.ade_solver_set_scalar_bc(self.h, ct.byref(scalar_bc) if scalar_bc is not None else None)
         self.scalar_bc = scalar_bc  # keeps its profile arrays alive
+
+    def set_buoyancy(self, buoyancy):
+        """the scalar's force on the fluid from the next step on (AdeBuoyancy, or None: the passive scalar)"""
+        self.lib.ade_solver_set_buoyancy(self.h, ct.byref(buoyancy) if buoyancy is not None else None)
+        self.buoyancy = buoyancy
 
     def close(self):
         if self.h:

@@ -8,9 +8,12 @@ and against the single-step BGK launch, on one periodic box, in one process, alt
   --fixed-walls adds two walled boxes (bounce-back rows and columns, two launches per step): walls_no_flux, the scalar's
   no-flux walls, and walls_fixed, all four edges FIXED (lbm_ade_scalar_bc; C_w = 1e-3 on row 0, a device profile on
   column 0, 0 on the others)
+  --buoyancy adds a second periodic box whose scalar pushes on the fluid (lbm_ade_buoyancy, beta = (0.5, -0.3),
+  c_ref = 5e-4, Guo's coefficients): buoyant, the same one launch and 288 B per node update in the reference order
+  whatever --form says, beside the passive step of the same run
 MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
 (18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
-usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls]"""
+usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls] [--buoyancy]"""
 import argparse
 import ctypes as ct
 import json
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--form", choices=["default", "ref", "fast"], default="default")
     ap.add_argument("--skip-composed", action="store_true")
     ap.add_argument("--fixed-walls", action="store_true")
+    ap.add_argument("--buoyancy", action="store_true")
     a = ap.parse_args()
     form = {"default": pylbm.FORM_DEFAULT, "ref": pylbm.FORM_REFERENCE_ORDER, "fast": pylbm.FORM_REASSOCIATED}[a.form]
     lib = pylbm.Lib()
@@ -118,6 +122,15 @@ def main():
             walled[key] = w
         lib.stream_sync(st)
 
+    buoyant = None
+    if a.buoyancy:
+        buoyant = pylbm.AdeSolver(lib, R, C, fluid, scalar, stream=st.value,
+                                  buoyancy=pylbm.AdeBuoyancy((0.5, -0.3), 5e-4, 0.5, (3.0, 9.0)))
+        bf, bgl, _, _, bgeo = buoyant.lattices()
+        lib.lattice_copy_rows(_ptr(bf), ct.byref(bgeo), 0, _ptr(f), ct.byref(dg), 0, R, st)
+        lib.lattice_copy_rows(_ptr(bgl), ct.byref(bgeo), 0, _ptr(g), ct.byref(dg), 0, R, st)
+        lib.stream_sync(st)
+
     # composed: the reference loop from the unfused operators (dense lattices f, g advance in place of the loop)
     if not a.skip_composed:
         fe, ge, fc, gc = (torch.empty_like(f) for _ in range(4))
@@ -140,6 +153,8 @@ def main():
     runs = {"fused": run_fused, "bgk": run_bgk}
     for key, w in walled.items():
         runs[key] = w.step
+    if buoyant is not None:
+        runs["buoyant"] = buoyant.step
     if not a.skip_composed:
         runs["composed"] = run_composed
     for fn in runs.values():
@@ -172,6 +187,12 @@ def main():
         out["walls_launches_total"] = {k: w.launches() for k, w in walled.items()}
         for w in walled.values():
             w.close()
+    if buoyant is not None:
+        out["buoyant_mlups"] = round(mlups["buoyant"], 1)
+        out["buoyant_over_fused"] = round(mlups["buoyant"] / mlups["fused"], 4)
+        out["buoyant_over_fused_per_repeat"] = [round(p / b, 4) for p, b in zip(times["fused"], times["buoyant"])]
+        out["buoyant_launches_total"] = buoyant.launches()
+        buoyant.close()
     sv.close()
     lib.event_destroy(e0)
     lib.event_destroy(e1)
