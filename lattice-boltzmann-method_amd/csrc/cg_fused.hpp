@@ -18,6 +18,7 @@
 // two kernels below -- tile and column-strip -- produce identical bits.
 #pragma once
 #include "cg.hpp"
+#include "cg_plan.hpp"
 
 namespace lbm {
 
@@ -284,14 +285,8 @@ __device__ __forceinline__ void cg_collide_store(
   }
 }
 
-// The tiles of a launch split into an INNER rectangle [ir0, ir1) x [ic0, ic1) (tile coordinates) --
-// every node of the tile, of its +-2 ring and of their +-1 gathers lies inside the block or its
-// ghost rows and carries no boundary fix-up: plain offsets, no clamps, no wraps -- and the FRAME
-// around it, which keeps the general boundary gather.  MODE 0: all tiles through the general path
-// (small lattices), 1: the inner tiles, 2: the frame.  Same arithmetic per node in every mode.
-struct CgTileRect {
-  int ir0, ir1, ic0, ic1;
-};
+// The tiles of a launch split into an INNER rectangle and the FRAME around it (CgTileRect, cg_plan.hpp).  MODE 0: all
+// tiles through the general path (small lattices), 1: the inner tiles, 2: the frame.  Same arithmetic per node in every mode.
 template <int TR, int TC, bool WITH_FIELDS, int MODE>
 __device__ __forceinline__ void cg_fused_body(
     double* __restrict__ pn_r, double* __restrict__ pn_b, const double* __restrict__ in_r,

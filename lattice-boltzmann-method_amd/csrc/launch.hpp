@@ -208,17 +208,19 @@ inline long sw_wave_slots(const void* kernel, int block_threads) {
   return slots;
 }
 
-// The chunk plan of a sliding-window launch over nrows x strips: rows per wave -- rows_fixed, else "sw_rows", else fitted
-// to the resident wave slots of THIS kernel instance (64 where the occupancy query fails) -- and the number of waves.
+// The chunk plan of a sliding-window launch over nrows x strips: rows per wave -- rows_fixed, else "sw_rows" (or the
+// tuning key the launch names), else fitted to the resident wave slots of THIS kernel instance (64, or what the launch
+// names, where the occupancy query fails) -- and the number of waves.
 struct SwPlan {
   int rpc, n_waves;
 };
 template <class Kernel>
-SwPlan sw_plan(Kernel* kernel, int block_threads, int nrows, int strips, int depth, int rows_fixed = 0) {
-  int rpc = rows_fixed > 0 ? rows_fixed : tuning("sw_rows", -1);
+SwPlan sw_plan(Kernel* kernel, int block_threads, int nrows, int strips, int depth, int rows_fixed = 0,
+               const char* rows_key = "sw_rows", int rows_unfitted = 64) {
+  int rpc = rows_fixed > 0 ? rows_fixed : tuning(rows_key, -1);
   if (rpc <= 0) {
     const long slots = sw_wave_slots((const void*)kernel, block_threads);
-    rpc = slots > 0 ? sw_pick_rows(nrows, strips, depth, slots) : 64;
+    rpc = slots > 0 ? sw_pick_rows(nrows, strips, depth, slots) : rows_unfitted;
   }
   if (rpc > nrows) rpc = nrows;
   return {rpc, strips * ((nrows + rpc - 1) / rpc)};

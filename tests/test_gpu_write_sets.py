@@ -21,6 +21,7 @@ torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
 from gpu_util import dev  # noqa: E402
 from pylbm import _ptr  # noqa: E402
+from test_cg_plan import DEFAULT_KNOBS, plans as cg_plans  # noqa: E402
 
 SENTINEL = 0x7FF8DEADBEEF5A5A       # a quiet NaN no kernel computes: "never written"
 PLANE_PAD = 40                      # doubles of padding behind every plane (even: keeps 16-byte alignment)
@@ -174,9 +175,10 @@ def _cg_parts(lib, R, C, layout, pitch):
     dst = [alloc(g), alloc(g)]
     full = rows_mask(g, (0, R))
     errs = []
-    for edge in (3, 16, 40):
-        if 2 * edge > R:
-            continue
+    edges = [e for e in (3, 16, 40) if 2 * e <= R]
+    # the rectangle the host-only planner (drivers/cg_plan_dump) names for the same case, the knobs at their defaults
+    planned = cg_plans([(R, C, g.ghost, halo, halo, 0, R, pylbm.CG_PART_INNER, e) + DEFAULT_KNOBS for e in edges])
+    for edge, plan in zip(edges, planned):
 
         def part(p):
             lib.cg_step_fused_part(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc), ct.byref(pg),
@@ -201,6 +203,10 @@ def _cg_parts(lib, R, C, layout, pitch):
                 # INNER is checked against what it may write, the FRAME against all the rest: the edge rows INNER took
                 # from it show up as MISSED below
                 inner = inner & allowed
+            want = (16 * plan["ir0"], 16 * plan["ir1"], 32 * plan["ic0"], 32 * plan["ic1"])
+            if not plan["split"] or (r0, r1, c0, c1) != want:
+                errs.append(f"{what}: INNER wrote rows [{r0}, {r1}) x columns [{c0}, {c1}), cg_plan_dump plans "
+                            f"{'rows [%d, %d) x columns [%d, %d)' % want if plan['split'] else 'no inner rectangle'}")
         if C == 1040:
             if not rows:
                 errs.append(f"{what}: INNER wrote nothing where the lattice holds an inner rectangle")
