@@ -601,6 +601,56 @@ int lbm_ade_stream_collide_part_b(double* fn, double* gn, const double* fo, cons
  * keeps the descriptor of its capture. */
 int lbm_ade_solver_set_buoyancy(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy);
 
+/* Interior walls: wall nodes anywhere inside the block (additive to all of the above) -- the obstacle of
+ * test/rectangle_sedimentation_test.cpp:184-196 (f) and :220-232 (g), a step, a baffle, a heated plate.  A wall node
+ * stays a fluid node, as in the reference: for each named slot s in 1..8 the streamed population s is replaced from the
+ * node's OWN post-collision populations, x[s] = x*[opp(s)] -- what a BOUNCE_BACK domain edge does to its three slots.  A
+ * slot mask has bit s-1 for slot s; the four axis-aligned facings (c_s of d2q9: rows first) are
+ *   LBM_ADE_FACE_ROW_POS  slots 1, 5, 8: fluid on the +row side      LBM_ADE_FACE_ROW_NEG  slots 3, 6, 7
+ *   LBM_ADE_FACE_COL_POS  slots 2, 5, 6: fluid on the +column side   LBM_ADE_FACE_COL_NEG  slots 4, 7, 8
+ * (the driver's first wall is COL_NEG, its ceiling ROW_NEG, its second wall COL_POS).  f and g take separate masks -- the
+ * reference's g first wall runs through the bottom row, its f first wall stops one row short -- and g_mode is the rule
+ * of the segment's g slots: LBM_ADE_SCALAR_NO_FLUX the replacement above, LBM_ADE_SCALAR_FIXED the anti-bounce-back of
+ * lbm_ade_scalar_bc with C_w = conc, g[s] = -g*[q] + 2 ((((1 + 3 c_q.v) + 4.5 (c_q.v)^2) - 1.5 v.v) E_q) conc, q = opp(s),
+ * v = u + w, u the velocity of the node's fully fixed-up f (the unshifted u0 of a buoyant step); conc = 0 is the driver's
+ * absorbing rectangle.
+ * lbm_ade_iwalls_add names the n >= 1 nodes (r0 + i dr, c0 + i dc), dr, dc in {-1, 0, 1} and not both 0; a negative r0 /
+ * c0 counts from the end (-1 = the last row / column).  Either mask may be 0, not both.  Segments may overlap: per node
+ * the masks are OR-ed, each g slot keeps one mode and the node one conc -- naming a g slot of a node with two modes, or a
+ * node with two FIXED conc values, is refused at add (nothing of the segment is added).  A node may stand on a domain
+ * wall: the domain's rule is applied first, the table wins every slot it names and the domain keeps the rest.
+ * Everything is checked on the host.  lbm_ade_iwalls_finalize uploads the merged table, sorted by (r, c) -- the one
+ * device call; an empty finalized table makes none and behaves like NULL (the same bits, the same launches).  The table
+ * is immutable after finalize; steps BORROW it, it is never copied (the rule of lbm_ade_scalar_bc.profile): it must
+ * outlive every solver and every captured graph that uses it.
+ * The step with a non-empty table costs one more launch: one lane per table node, after the interior launch and the
+ * edge pass, overwriting its nodes (rows of [row_begin, row_end) only).  The collide-only first iteration applies no
+ * wall rule.  Row slabs do not take a table yet: lbm_ade_stream_collide_part* and lbm_ring_ade_* are unchanged (how a
+ * table splits per part is the open question of that follow-up). */
+#define LBM_ADE_FACE_ROW_POS 0x91u
+#define LBM_ADE_FACE_ROW_NEG 0x64u
+#define LBM_ADE_FACE_COL_POS 0x32u
+#define LBM_ADE_FACE_COL_NEG 0xC8u
+typedef struct lbm_ade_iwalls lbm_ade_iwalls;
+int lbm_ade_iwalls_create(lbm_ade_iwalls** out, int R, int C);
+int lbm_ade_iwalls_add(lbm_ade_iwalls* t, int r0, int c0, int dr, int dc, int n, unsigned f_slots, unsigned g_slots,
+                       int g_mode /* LBM_ADE_SCALAR_* */, double conc);
+int lbm_ade_iwalls_count(const lbm_ade_iwalls* t); /* distinct nodes so far; host only; 0 for NULL */
+/* node i of the merged table, sorted by (r, c); any output may be NULL; host only */
+int lbm_ade_iwalls_node(const lbm_ade_iwalls* t, int i, int* r, int* c, unsigned* f_slots, unsigned* g_slots,
+                        unsigned* g_fixed_slots, double* conc);
+int lbm_ade_iwalls_finalize(lbm_ade_iwalls* t);
+int lbm_ade_iwalls_destroy(lbm_ade_iwalls* t);
+/* lbm_ade_stream_collide_b with the table (NULL or empty: lbm_ade_stream_collide_b itself); the table must be finalized
+ * and built for the R x C of g */
+int lbm_ade_stream_collide_w(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                             const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                             const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                             int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
+/* the context's interior walls from the next stream on (the lazy one of get_state included); NULL clears them.  The
+ * table is borrowed, not copied. */
+int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls);
+
 /* ---- slab ring in C++: one process per GPU, packed halo messages between row slabs ------------------
  * Native counterpart of pylbm/slab.py (same kernels, same halo sets): edge rows + pack + ONE message
  * to and from each neighbour + unpack on the ring's own high-priority stream, interior rows on the

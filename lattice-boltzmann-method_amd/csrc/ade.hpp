@@ -166,6 +166,16 @@ struct AdeWalls {
 // column gathers as BOUNCE_BACK, also beside a specular fluid column); u is the fluid velocity of the streamed f.  Slot
 // ownership is bc_fixups_own's: rows first, a wall column wins at the corners, and each slot takes the rule and C_w of
 // the edge that wins it (a NO_FLUX column keeps its corner slots bounce-back).
+// One anti-bounce-back population: in hb the bounce-back value h*[q] of slot opp(q), out the FIXED value of that slot;
+// (vr, vc) = u + w, vv = v.v, cw = C_w.  The one expression of the domain's FIXED edges (ade_fixed_walls) and of the
+// interior walls (ade_iwalls_scalar).
+__device__ __forceinline__ double ade_fixed_slot(double hb, int q, double vr, double vc, double vv, double cw) {
+  // c_q.v as matmul(v, c) forms it (products with 0, +-1 are exact)
+  const double cv = q == 1 ? vr : q == 2 ? vc : q == 3 ? -vr : q == 4 ? -vc : q == 5 ? vr + vc : q == 6 ? -vr + vc
+                  : q == 7 ? -vr - vc : vr - vc;
+  return -hb + 2.0 * (((((1.0 + 3.0 * cv) + 4.5 * (cv * cv)) - 1.5 * vv) * wq(q)) * cw);
+}
+
 __device__ __forceinline__ void ade_fixed_walls(double (&h)[Q], const Geom& g, const Bc& bc, const AdeWalls& sw, int r,
                                                 int c, double ux, double uy, double wr, double wc) {
   const bool rl = r == 0 && bc.row_lo == LBM_EDGE_BOUNCE_BACK, rh = r == g.R - 1 && bc.row_hi == LBM_EDGE_BOUNCE_BACK;
@@ -182,11 +192,7 @@ __device__ __forceinline__ void ade_fixed_walls(double (&h)[Q], const Geom& g, c
     const int e = (cl && icy(s) == 1) ? 2 : (ch && icy(s) == -1) ? 3 : (rl && icx(s) == 1) ? 0 : (rh && icx(s) == -1) ? 1 : -1;
     if (e < 0 || !((sw.fixed >> e) & 1)) continue;
     const double cw = e == 0 ? w_rl : e == 1 ? w_rh : e == 2 ? w_cl : w_ch;
-    const int q = opp(s);  // the outgoing direction
-    // c_q.v as matmul(v, c) forms it (products with 0, +-1 are exact)
-    const double cv = q == 1 ? vr : q == 2 ? vc : q == 3 ? -vr : q == 4 ? -vc : q == 5 ? vr + vc : q == 6 ? -vr + vc
-                    : q == 7 ? -vr - vc : vr - vc;
-    h[s] = -h[s] + 2.0 * (((((1.0 + 3.0 * cv) + 4.5 * (cv * cv)) - 1.5 * vv) * wq(q)) * cw);
+    h[s] = ade_fixed_slot(h[s], opp(s), vr, vc, vv, cw);  // opp(s): the outgoing direction
   }
 }
 
@@ -478,6 +484,113 @@ __global__ __launch_bounds__(256) void k_ade_fixed_state(double* __restrict__ hs
   ade_fixed_walls(h, g, bc, sw, r, c, u[d], u[n + d], wr, wc);
 #pragma unroll
   for (int q = 0; q < Q; ++q) hs[q * g.plane + o] = h[q];
+}
+
+// Interior walls (lbm_ade_iwalls, device copy): one entry per wall node, sorted by (r, c).  A wall node stays a fluid
+// node (test/rectangle_sedimentation_test.cpp:184-196, :220-232): the streamed population s of a named slot is replaced
+// from the node's own post-collision populations.  slots: bits 0-7 the f slots, 8-15 the g slots, 16-23 the g slots that
+// are FIXED (a subset of the g slots); bit s-1 of each byte is slot s.  conc: C_w of the node's FIXED slots.
+struct AdeIwallNode {
+  int r, c;
+  unsigned slots;
+  int pad;
+  double conc;
+};
+
+// the f slots of an interior wall node: f[s] = f*[opp s] of the node itself (on-site bounce-back)
+__device__ __forceinline__ void ade_iwalls_fluid(double (&f)[Q], const double* __restrict__ fo, const Geom& g, long o,
+                                                 unsigned slots) {
+#pragma unroll
+  for (int s = 1; s < Q; ++s)
+    if ((slots >> (s - 1)) & 1u) f[s] = fo[opp(s) * g.plane + o];
+}
+
+// the g slots: NO_FLUX h[s] = h*[opp s], FIXED the anti-bounce-back of ade_fixed_slot with the node's conc; (ux, uy) the
+// velocity of the fully fixed-up f.  The table wins every slot it names, whatever the domain's rule left there.
+__device__ __forceinline__ void ade_iwalls_scalar(double (&h)[Q], const double* __restrict__ go, const Geom& g, long o,
+                                                  unsigned slots, double cw, double ux, double uy, double wr, double wc) {
+  const double vr = ux + wr, vc = uy + wc;
+  const double vv = vr * vr + vc * vc;
+#pragma unroll
+  for (int s = 1; s < Q; ++s) {
+    if (!((slots >> (7 + s)) & 1u)) continue;
+    const double hb = go[opp(s) * g.plane + o];
+    h[s] = ((slots >> (15 + s)) & 1u) ? ade_fixed_slot(hb, opp(s), vr, vc, vv, cw) : hb;
+  }
+}
+
+// Interior-wall pass: the table's nodes of rows [row_begin, row_end) recomputed, one lane per node, overwriting what the
+// interior launch (and the edge pass, where the node sits on a domain wall) stored for them.  Per node: the domain's
+// gather (gather_walls: a node may stand on a domain wall, as the rectangle's feet do), the f slots, the same for g
+// (FIXED: the domain's FIXED edges as in k_ade_edge), the g slots, both collisions -- in k_ade_edge's order, the
+// scalar's rules between the fluid's moments and the scalar's collision.  FIXED: the DOMAIN has FIXED edges (sw);
+// the table's own FIXED slots are per node and need no instantiation.
+template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
+__global__ __launch_bounds__(256) void k_ade_iwalls(double* __restrict__ fn, double* __restrict__ gn,
+                                                    const double* __restrict__ fo, const double* __restrict__ go, Geom g,
+                                                    Bc bc, FM fm, SM sm, int row_begin, int row_end,
+                                                    double* __restrict__ rho_out, double* __restrict__ u_out,
+                                                    double* __restrict__ c_out, AdeWalls sw, AdeBuoyancy by,
+                                                    const AdeIwallNode* __restrict__ nodes, int n_nodes) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_nodes) return;
+  const AdeIwallNode nd = nodes[i];
+  const int r = nd.r, c = nd.c;
+  if (r < row_begin || r >= row_end) return;
+  const long o = g.at(r, c);
+  double f[Q], h[Q], rho, ux, uy, conc;
+  gather_walls(f, fo, g, bc, r, c);
+  ade_iwalls_fluid(f, fo, g, o, nd.slots);
+  gather_walls(h, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, r, c);
+  if (BUOYANT) {
+    ade_fluid_moments(f, rho, ux, uy);
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_iwalls_scalar(h, go, g, o, nd.slots, nd.conc, ux, uy, sm.wr, sm.wc);
+    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+  } else {
+    fm.collide(f, rho, ux, uy);
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_iwalls_scalar(h, go, g, o, nd.slots, nd.conc, ux, uy, sm.wr, sm.wc);
+    sm.collide(h, ux, uy, conc);
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    fn[q * g.plane + o] = f[q];
+    gn[q * g.plane + o] = h[q];
+  }
+  if (WITH_MOMENTS) {
+    const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
+    rho_out[oo] = rho;
+    u_out[oo] = ux;
+    u_out[nn + oo] = uy;
+    c_out[oo] = conc;
+  }
+}
+
+// The interior walls of the lazily streamed state (lbm_ade_solver_get_state), one lane per table node.  SCALAR = false:
+// xs = the streamed f, post = the post-collision f: the f slots.  SCALAR = true: xs = the streamed g after
+// k_ade_fixed_state, post = the post-collision g, u = [2][R][C] dense, the reference-order calc_u of the fixed-up f: the
+// g slots.
+template <bool SCALAR>
+__global__ __launch_bounds__(256) void k_ade_iwalls_state(double* __restrict__ xs, const double* __restrict__ post,
+                                                          Geom g, const AdeIwallNode* __restrict__ nodes, int n_nodes,
+                                                          const double* __restrict__ u, double wr, double wc) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_nodes) return;
+  const AdeIwallNode nd = nodes[i];
+  if (!((nd.slots >> (SCALAR ? 8 : 0)) & 0xFFu)) return;
+  const long o = g.at(nd.r, nd.c);
+  double x[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) x[q] = xs[q * g.plane + o];
+  if (SCALAR) {
+    const long n = (long)g.R * g.C, d = (long)nd.r * g.C + nd.c;
+    ade_iwalls_scalar(x, post, g, o, nd.slots, nd.conc, u[d], u[n + d], wr, wc);
+  } else {
+    ade_iwalls_fluid(x, post, g, o, nd.slots);
+  }
+#pragma unroll
+  for (int q = 1; q < Q; ++q) xs[q * g.plane + o] = x[q];
 }
 
 // Collide only, no streaming: the driver's first iteration on the pre-collision state (one node per thread).

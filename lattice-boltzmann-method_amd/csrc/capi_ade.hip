@@ -3,11 +3,30 @@
 // context that runs the driver loop on one block.
 #include <cmath>
 #include <cstdint>
+#include <iterator>
+#include <map>
 #include <new>
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "ade.hpp"
 #include "launch.hpp"
+
+// Interior walls of the fused step: a host table of wall nodes, merged per node and kept sorted by (r, c) while it is
+// built; lbm_ade_iwalls_finalize uploads it once (the only device call) and it is immutable from then on.
+struct lbm_ade_iwalls {
+  struct Entry {
+    unsigned f = 0, g = 0, g_fixed = 0;  // slot masks, bit s-1 = slot s; g_fixed: the g slots that are FIXED
+    double conc = 0.0;                   // C_w of the FIXED slots
+    bool has_conc = false;               // some FIXED segment has named the node
+  };
+  int R = 0, C = 0;
+  std::map<std::pair<int, int>, Entry> nodes;
+  bool finalized = false;
+  int n = 0;                              // nodes uploaded
+  lbm::AdeIwallNode* d_nodes = nullptr;   // device copy, sorted by (r, c)
+};
 
 namespace lbm {
 
@@ -159,6 +178,20 @@ static int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, con
   return LBM_OK;
 }
 
+// The interior walls (lbm_ade_iwalls, NULL allowed) against the geometry of the call, on the host: finalized, and built
+// for the same R x C.  *nodes / *n receive the device table; an empty table is NULL's (nullptr, 0).
+static int ade_iwalls_check(const char* fn, const lbm_ade_iwalls* t, const lbm_geom* g, const AdeIwallNode** nodes, int* n) {
+  *nodes = nullptr;
+  *n = 0;
+  if (!t) return LBM_OK;
+  LBM_REQUIRE(t->finalized, "%s: interior walls: the table is not finalized (lbm_ade_iwalls_finalize)", fn);
+  LBM_REQUIRE(g && t->R == g->R && t->C == g->C, "%s: interior walls: the table is for a %d x %d lattice, the call for %d x %d",
+              fn, t->R, t->C, g ? g->R : 0, g ? g->C : 0);
+  *nodes = t->d_nodes;
+  *n = t->n;
+  return LBM_OK;
+}
+
 template <bool B, class FM, class SM>
 static int ade_collide_launch(double* fp, double* gp, const double* f, const double* h, const Geom& g, const FM& fm,
                               const SM& sm, const AdeBuoyancy& by, double* rho, double* u, double* conc, hipStream_t st) {
@@ -169,11 +202,13 @@ static int ade_collide_launch(double* fp, double* gp, const double* f, const dou
   return LBM_OK;
 }
 
-// interior launch + (walls only) the edge pass; *launches += the kernels enqueued
+// interior launch + (walls only) the edge pass + (a non-empty table of interior walls only) the interior-wall pass;
+// *launches += the kernels enqueued
 template <bool B, class FM, class SM>
 static int ade_step_launch(double* fn, double* gn, const double* fo, const double* go, const Geom& g, const Bc& bc,
-                           const FM& fm, const SM& sm, const AdeWalls& sw, const AdeBuoyancy& by, int row_begin,
-                           int row_end, double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
+                           const FM& fm, const SM& sm, const AdeWalls& sw, const AdeBuoyancy& by,
+                           const AdeIwallNode* wall_nodes, int n_wall_nodes, int row_begin, int row_end, double* rho,
+                           double* u, double* conc, hipStream_t st, long long* launches) {
   const bool mom = rho != nullptr;
   const int nt = tuning("nt", 3);  // bit 0: non-temporal loads, bit 1: non-temporal stores
   const int cap = tuning("grid_cap", 0);
@@ -192,6 +227,15 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
     with_flags([&](auto M, auto F) {
       LBM_KLAUNCH((k_ade_edge<FM, SM, M(), F(), B>), grid_e, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin,
                   row_end, rho, u, conc, sw, by);
+    }, mom, sw.fixed);
+    LBM_CHECK_LAUNCH();
+    ++*launches;
+  }
+  if (n_wall_nodes > 0) {  // one lane per table node, after the passes whose nodes it overwrites
+    const dim3 grid_w((n_wall_nodes + 255) / 256);
+    with_flags([&](auto M, auto F) {
+      LBM_KLAUNCH((k_ade_iwalls<FM, SM, M(), F(), B>), grid_w, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin,
+                  row_end, rho, u, conc, sw, by, wall_nodes, n_wall_nodes);
     }, mom, sw.fixed);
     LBM_CHECK_LAUNCH();
     ++*launches;
@@ -218,17 +262,21 @@ static int ade_part_launch(double* fn, double* gn, const double* fo, const doubl
   return LBM_OK;
 }
 
-// collide only: no streaming, so no wall rule -- the scalar's walls (sbc) are checked and nothing more
+// collide only: no streaming, so no wall rule -- the scalar's walls (sbc) and the interior walls (iwalls) are checked
+// and nothing more
 static int ade_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* lg,
                        const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                        const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc,
-                       hipStream_t st, bool slab = false) {
+                       hipStream_t st, bool slab = false, const lbm_ade_iwalls* iwalls = nullptr) {
   AdeWalls sw;
   AdeBuoyancy by;
   bool buoyant;
+  const AdeIwallNode* wall_nodes;
+  int n_wall_nodes;
   int rc = ade_scalar_bc_check(fn, sbc, bc, &sw);
   if (!rc) rc = ade_validate(fn, lg, bc, fluid, scalar, slab);
   if (!rc) rc = ade_buoyancy_check(fn, buoy, &by, &buoyant);
+  if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &wall_nodes, &n_wall_nodes);
   if (!rc) rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false);
   if (rc) return rc;
   const Geom g = make_geom(*lg);
@@ -240,14 +288,17 @@ static int ade_collide(const char* fn, double* fp, double* gp, const double* f, 
 static int ade_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
                               const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
                               const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
-                              int row_begin, int row_end, double* rho, double* u, double* conc, hipStream_t st,
-                              long long* launches) {
+                              const lbm_ade_iwalls* iwalls, int row_begin, int row_end, double* rho, double* u,
+                              double* conc, hipStream_t st, long long* launches) {
   AdeWalls sw;  // the scalar's walls first: a FIXED edge names the edge mode it cannot sit on
   AdeBuoyancy by;
   bool buoyant;
+  const AdeIwallNode* wall_nodes;
+  int n_wall_nodes;
   int rc = ade_scalar_bc_check(fn, sbc, lbc, &sw);
   if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar);
   if (!rc) rc = ade_buoyancy_check(fn, buoy, &by, &buoyant);
+  if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &wall_nodes, &n_wall_nodes);
   if (!rc) rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true);
   if (rc) return rc;
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R, "%s: row range [%d, %d) outside [0, %d)", fn,
@@ -256,7 +307,8 @@ static int ade_stream_collide(const char* fn, double* fn_, double* gn, const dou
   const Geom g = make_geom(*lg);
   const Bc bc = make_bc(lbc);
   return with_ade_models(fluid, scalar, buoyant, [&](const auto& fm, const auto& sm, auto B) {
-    return ade_step_launch<B()>(fn_, gn, fo, go, g, bc, fm, sm, sw, by, row_begin, row_end, rho, u, conc, st, launches);
+    return ade_step_launch<B()>(fn_, gn, fo, go, g, bc, fm, sm, sw, by, wall_nodes, n_wall_nodes, row_begin, row_end, rho,
+                                u, conc, st, launches);
   });
 }
 
@@ -332,6 +384,7 @@ struct lbm_ade_solver {
   bool fixed;             // some edge of sbc is FIXED
   lbm_ade_buoyancy buoy;  // lbm_ade_solver_set_buoyancy
   bool buoyant;           // buoy is set (beta = (0, 0) included: the launches decide)
+  const lbm_ade_iwalls* walls;  // lbm_ade_solver_set_walls: borrowed, never copied
   hipStream_t st;
   double* lat[2];
   double* dense;  // [9][R][C] SoA scratch of get_state
@@ -365,8 +418,8 @@ int lbm_ade_stream_collide(double* fn, double* gn, const double* fo, const doubl
                            const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int row_begin,
                            int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
   long long launches = 0;
-  return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, nullptr, nullptr, row_begin,
-                            row_end, rho, u, conc, as_stream(s), &launches);
+  return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, nullptr, nullptr, nullptr,
+                            row_begin, row_end, rho, u, conc, as_stream(s), &launches);
 }
 
 int lbm_ade_stream_collide_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
@@ -374,8 +427,8 @@ int lbm_ade_stream_collide_ex(double* fn, double* gn, const double* fo, const do
                               const lbm_ade_scalar_bc* sbc, int row_begin, int row_end, double* rho, double* u,
                               double* conc, lbm_stream_t s) {
   long long launches = 0;
-  return ade_stream_collide("lbm_ade_stream_collide_ex", fn, gn, fo, go, g, bc, fluid, scalar, sbc, nullptr, row_begin,
-                            row_end, rho, u, conc, as_stream(s), &launches);
+  return ade_stream_collide("lbm_ade_stream_collide_ex", fn, gn, fo, go, g, bc, fluid, scalar, sbc, nullptr, nullptr,
+                            row_begin, row_end, rho, u, conc, as_stream(s), &launches);
 }
 
 int lbm_ade_stream_collide_b(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
@@ -383,8 +436,17 @@ int lbm_ade_stream_collide_b(double* fn, double* gn, const double* fo, const dou
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int row_begin, int row_end,
                              double* rho, double* u, double* conc, lbm_stream_t s) {
   long long launches = 0;
-  return ade_stream_collide("lbm_ade_stream_collide_b", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, row_begin,
-                            row_end, rho, u, conc, as_stream(s), &launches);
+  return ade_stream_collide("lbm_ade_stream_collide_b", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, nullptr,
+                            row_begin, row_end, rho, u, conc, as_stream(s), &launches);
+}
+
+int lbm_ade_stream_collide_w(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                             const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                             const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                             int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
+  long long launches = 0;
+  return ade_stream_collide("lbm_ade_stream_collide_w", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, iwalls,
+                            row_begin, row_end, rho, u, conc, as_stream(s), &launches);
 }
 
 int lbm_ade_stream_collide_part(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
@@ -427,6 +489,7 @@ int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc*
   sv->fixed = false;
   sv->buoy = lbm_ade_buoyancy{};
   sv->buoyant = false;
+  sv->walls = nullptr;
   sv->st = as_stream(s);
   sv->cur = 0;
   sv->post = false;
@@ -491,12 +554,12 @@ int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
     int rc;
     if (!sv->post) {
       rc = ade_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid,
-                       &sv->scalar, nullptr, buoy, nullptr, nullptr, nullptr, sv->st);
+                       &sv->scalar, nullptr, buoy, nullptr, nullptr, nullptr, sv->st, false, sv->walls);
       if (!rc) ++sv->launches;
     } else {
       rc = ade_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
-                              &sv->fluid, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, buoy, 0, sv->g.R, nullptr,
-                              nullptr, nullptr, sv->st, &sv->launches);
+                              &sv->fluid, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, buoy, sv->walls, 0, sv->g.R,
+                              nullptr, nullptr, nullptr, sv->st, &sv->launches);
     }
     if (rc) return rc;
     sv->cur = o;
@@ -519,9 +582,20 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
   int k = sv->cur;
   const lbm_geom dg{R, C, 0, 0, 0};
   const bool fixed = sv->post && sv->fixed;
+  bool have_u = false;  // sv->rho, sv->u hold the moments of the streamed f
   if (sv->post) {
-    int rc = lbm_stream(sv->f(k ^ 1), sv->f(k), &g, &sv->bc, sv->st);
+    const AdeIwallNode* wall_nodes;
+    int n_wall_nodes;
+    int rc = ade_iwalls_check("lbm_ade_solver_get_state", sv->walls, &g, &wall_nodes, &n_wall_nodes);
     if (rc) return rc;
+    const dim3 grid_w((n_wall_nodes + 255) / 256);
+    rc = lbm_stream(sv->f(k ^ 1), sv->f(k), &g, &sv->bc, sv->st);
+    if (rc) return rc;
+    if (n_wall_nodes > 0) {  // the f slots, before the moments that the scalar's rules read
+      LBM_KLAUNCH(k_ade_iwalls_state<false>, grid_w, dim3(256), 0, sv->st, sv->f(k ^ 1), sv->f(k), make_geom(g), wall_nodes,
+                  n_wall_nodes, nullptr, 0.0, 0.0);
+      LBM_CHECK_LAUNCH();
+    }
     AdeWalls sw;
     rc = ade_scalar_bc_check("lbm_ade_solver_get_state", fixed ? &sv->sbc : nullptr, &sv->bc, &sw);
     if (rc) return rc;
@@ -533,14 +607,22 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
     rc = lbm_stream(sv->h(k ^ 1), sv->h(k), &g, &gbc, sv->st);
     if (rc) return rc;
     k ^= 1;
-    if (fixed) {
+    if (fixed || n_wall_nodes > 0) {
       rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->f(k), &g, 0, R, sv->st);
       if (!rc) rc = lbm_calc_rho(sv->rho, sv->dense, R, C, sv->st);
       if (!rc) rc = lbm_calc_u(sv->u, sv->dense, sv->rho, R, C, sv->st);
       if (rc) return rc;
+      have_u = true;
+    }
+    if (fixed) {
       const int n_edge = 2 * C + 2 * R;
       LBM_KLAUNCH(k_ade_fixed_state, dim3((n_edge + 255) / 256), dim3(256), 0, sv->st, sv->h(k), make_geom(g),
                   make_bc(&sv->bc), sw, sv->u, sv->scalar.w_r, sv->scalar.w_c);
+      LBM_CHECK_LAUNCH();
+    }
+    if (n_wall_nodes > 0) {  // the g slots last: the table wins every slot it names (post-collision level: k ^ 1)
+      LBM_KLAUNCH(k_ade_iwalls_state<true>, grid_w, dim3(256), 0, sv->st, sv->h(k), sv->h(k ^ 1), make_geom(g), wall_nodes,
+                  n_wall_nodes, sv->u, sv->scalar.w_r, sv->scalar.w_c);
       LBM_CHECK_LAUNCH();
     }
   }
@@ -550,7 +632,7 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
       if (rc) return rc;
       LBM_CHECK_HIP(hipMemcpyAsync(f, sv->stage, n * 9 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
     }
-    if ((rho || u) && !fixed) {
+    if ((rho || u) && !have_u) {
       int rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->f(k), &g, 0, R, sv->st);
       if (!rc) rc = lbm_calc_rho(sv->rho, sv->dense, R, C, sv->st);
       if (!rc) rc = lbm_calc_u(sv->u, sv->dense, sv->rho, R, C, sv->st);
@@ -615,6 +697,124 @@ int lbm_ade_solver_set_buoyancy(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy
   if (rc) return rc;
   sv->buoy = buoy ? *buoy : lbm_ade_buoyancy{};
   sv->buoyant = buoy != nullptr;
+  return LBM_OK;
+}
+
+int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls) {
+  LBM_REQUIRE(sv, "lbm_ade_solver_set_walls: NULL solver");
+  const AdeIwallNode* nodes;
+  int n;
+  int rc = ade_iwalls_check("lbm_ade_solver_set_walls", iwalls, &sv->g, &nodes, &n);
+  if (rc) return rc;
+  sv->walls = iwalls;
+  return LBM_OK;
+}
+
+int lbm_ade_iwalls_create(lbm_ade_iwalls** out, int R, int C) {
+  LBM_REQUIRE(out, "lbm_ade_iwalls_create: NULL argument");
+  LBM_REQUIRE(R >= 1 && C >= 1, "lbm_ade_iwalls_create: R=%d C=%d must be positive", R, C);
+  lbm_ade_iwalls* t = new (std::nothrow) lbm_ade_iwalls();
+  LBM_REQUIRE(t, "lbm_ade_iwalls_create: out of host memory");
+  t->R = R;
+  t->C = C;
+  *out = t;
+  return LBM_OK;
+}
+
+int lbm_ade_iwalls_add(lbm_ade_iwalls* t, int r0, int c0, int dr, int dc, int n, unsigned f_slots, unsigned g_slots,
+                       int g_mode, double conc) {
+  const char* fn = "lbm_ade_iwalls_add";
+  LBM_REQUIRE(t, "%s: NULL table", fn);
+  LBM_REQUIRE(!t->finalized, "%s: the table is finalized (immutable after lbm_ade_iwalls_finalize)", fn);
+  LBM_REQUIRE(n >= 1, "%s: n=%d must be at least 1", fn, n);
+  LBM_REQUIRE(dr >= -1 && dr <= 1 && dc >= -1 && dc <= 1 && (dr != 0 || dc != 0),
+              "%s: step (dr, dc)=(%d, %d): each of -1, 0, 1 and not both 0", fn, dr, dc);
+  LBM_REQUIRE(f_slots <= 0xFFu && g_slots <= 0xFFu, "%s: slot mask f_slots=0x%x g_slots=0x%x above 0xFF (bit s-1 = slot s, s in 1..8)",
+              fn, f_slots, g_slots);
+  LBM_REQUIRE(f_slots != 0 || g_slots != 0, "%s: f_slots and g_slots are both 0: the segment names no slot", fn);
+  LBM_REQUIRE(g_mode == LBM_ADE_SCALAR_NO_FLUX || g_mode == LBM_ADE_SCALAR_FIXED,
+              "%s: g_mode=%d (LBM_ADE_SCALAR_NO_FLUX or LBM_ADE_SCALAR_FIXED)", fn, g_mode);
+  LBM_REQUIRE(std::isfinite(conc), "%s: conc=%g must be finite", fn, conc);
+  if (r0 < 0) r0 += t->R;  // from the end, as the reference's slices count
+  if (c0 < 0) c0 += t->C;
+  for (long long k : {0LL, (long long)n - 1}) {  // the segment is linear: its two ends decide
+    const long long r = r0 + k * dr, c = c0 + k * dc;
+    LBM_REQUIRE(r >= 0 && r < t->R && c >= 0 && c < t->C, "%s: node (%lld, %lld) outside the %d x %d lattice", fn, r, c,
+                t->R, t->C);
+  }
+  const bool fixed = g_mode == LBM_ADE_SCALAR_FIXED && g_slots != 0;
+  // conflicts first: nothing is added on a refusal
+  for (int k = 0; k < n; ++k) {
+    const int r = r0 + k * dr, c = c0 + k * dc;
+    const auto it = t->nodes.find({r, c});
+    if (it == t->nodes.end()) continue;
+    const lbm_ade_iwalls::Entry& e = it->second;
+    const unsigned clash = g_slots & (fixed ? e.g & ~e.g_fixed : e.g_fixed);
+    if (clash) {
+      int s = 1;
+      while (!((clash >> (s - 1)) & 1u)) ++s;
+      LBM_REQUIRE(false, "%s: node (%d, %d): g slot %d named with two modes (NO_FLUX and FIXED)", fn, r, c, s);
+    }
+    LBM_REQUIRE(!fixed || !e.has_conc || e.conc == conc, "%s: node (%d, %d): FIXED conc=%g differs from the conc=%g the node has",
+                fn, r, c, conc, e.conc);
+  }
+  for (int k = 0; k < n; ++k) {
+    lbm_ade_iwalls::Entry& e = t->nodes[{r0 + k * dr, c0 + k * dc}];
+    e.f |= f_slots;
+    e.g |= g_slots;
+    if (fixed) {
+      e.g_fixed |= g_slots;
+      e.conc = conc;
+      e.has_conc = true;
+    }
+  }
+  return LBM_OK;
+}
+
+int lbm_ade_iwalls_count(const lbm_ade_iwalls* t) { return t ? (int)t->nodes.size() : 0; }
+
+int lbm_ade_iwalls_node(const lbm_ade_iwalls* t, int i, int* r, int* c, unsigned* f_slots, unsigned* g_slots,
+                        unsigned* g_fixed_slots, double* conc) {
+  LBM_REQUIRE(t, "lbm_ade_iwalls_node: NULL table");
+  LBM_REQUIRE(i >= 0 && i < (int)t->nodes.size(), "lbm_ade_iwalls_node: node %d outside [0, %d)", i, (int)t->nodes.size());
+  auto it = t->nodes.begin();
+  std::advance(it, i);
+  if (r) *r = it->first.first;
+  if (c) *c = it->first.second;
+  if (f_slots) *f_slots = it->second.f;
+  if (g_slots) *g_slots = it->second.g;
+  if (g_fixed_slots) *g_fixed_slots = it->second.g_fixed;
+  if (conc) *conc = it->second.conc;
+  return LBM_OK;
+}
+
+int lbm_ade_iwalls_finalize(lbm_ade_iwalls* t) {
+  LBM_REQUIRE(t, "lbm_ade_iwalls_finalize: NULL table");
+  LBM_REQUIRE(!t->finalized, "lbm_ade_iwalls_finalize: the table is finalized already");
+  if (!t->nodes.empty()) {  // an empty table makes no device call: it is NULL's
+    std::vector<AdeIwallNode> host;
+    host.reserve(t->nodes.size());
+    for (const auto& kv : t->nodes)
+      host.push_back(AdeIwallNode{kv.first.first, kv.first.second, kv.second.f | (kv.second.g << 8) | (kv.second.g_fixed << 16),
+                                  0, kv.second.conc});
+    LBM_CHECK_HIP(hipMalloc(&t->d_nodes, host.size() * sizeof(AdeIwallNode)));
+    hipError_t e = hipMemcpy(t->d_nodes, host.data(), host.size() * sizeof(AdeIwallNode), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(t->d_nodes);
+      t->d_nodes = nullptr;
+      set_error("lbm_ade_iwalls_finalize: %s", hipGetErrorString(e));
+      return LBM_ERR_HIP;
+    }
+    t->n = (int)host.size();
+  }
+  t->finalized = true;
+  return LBM_OK;
+}
+
+int lbm_ade_iwalls_destroy(lbm_ade_iwalls* t) {
+  if (!t) return LBM_OK;
+  if (t->d_nodes) (void)hipFree(t->d_nodes);
+  delete t;
   return LBM_OK;
 }
 

@@ -5,11 +5,15 @@
 // (as the driver initialises g_adve, :95).
 //   usage: passive_scalar_box R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]
 //          [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]
+//          [--rectangle r_top,c_first,c_second[,conc]]
 // --dump writes prefix-{f0,g0,f,g,rho,u,C}.f64 (raw f64, reference layout [R][C][Q]); --walls 1: bounce-back columns,
 // 2: bounce-back rows and columns.  --fixed: the named edges (row_lo, row_hi, col_lo, col_hi; walls of the fluid) hold
 // the scalar at the constant C_w (lbm_ade_scalar_bc FIXED), the others stay no-flux.  --buoyancy: the scalar pushes on the
 // fluid with F = beta (C - c_ref) per node (lbm_ade_buoyancy; u_shift, guo_a, guo_b default to 1, 1/3, 1/9); without it
-// the scalar is passive.
+// the scalar is passive.  --rectangle: the sedimentation driver's rectangle (rectangle_sedimentation_test.cpp:184-196,
+// :220-232) standing on the last row as interior walls (lbm::AdeInteriorWalls): ceiling row r_top (negative: from the
+// end) over columns c_first..c_second, the two side walls below it down to the last row; the scalar is absorbed
+// (FIXED, C_w = 0) unless conc gives the C_w the body holds.
 #include <cmath>
 #include <iostream>
 #include <sstream>
@@ -21,7 +25,8 @@
 int main(int argc, char** argv) {
   if (argc < 8) {
     std::cerr << "usage: " << argv[0] << " R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]"
-                 " [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]\n";
+                 " [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]"
+                 " [--rectangle r_top,c_first,c_second[,conc]]\n";
     return 1;
   }
   try {
@@ -44,6 +49,14 @@ int main(int argc, char** argv) {
     }
     double bv[6];
     const bool buoyant = parse_buoyancy(arg_value(argc, argv, "--buoyancy", ""), bv);
+    double rect[4] = {0.0, 0.0, 0.0, 0.0};
+    int n_rect = 0;
+    std::stringstream rectangle(arg_value(argc, argv, "--rectangle", ""));
+    for (std::string item; std::getline(rectangle, item, ',');) {
+      if (n_rect == 4) throw std::runtime_error("--rectangle: r_top,c_first,c_second[,conc]");
+      rect[n_rect++] = std::stod(item);
+    }
+    if (n_rect != 0 && n_rect < 3) throw std::runtime_error("--rectangle: r_top,c_first,c_second[,conc]");
     if (lbm_device_count() < 1) {
       std::cerr << "no HIP device available\n";
       return 2;
@@ -72,6 +85,21 @@ int main(int argc, char** argv) {
     lbm::AdeSolver sv(R, C, omega, omega_g, w_r, w_c, bc, form);
     sv.set_scalar_bc(sbc);
     if (buoyant) sv.set_buoyancy(lbm_ade_buoyancy{bv[0], bv[1], bv[2], bv[3], bv[4], bv[5]});
+    // the rectangle as the driver adds it: first wall (f stops one row short of the last row, g runs through it with
+    // slot 7 of the foot left to the domain's wall), ceiling, second wall
+    lbm::AdeInteriorWalls body(R, C);
+    if (n_rect) {
+      const int r_top = (int)rect[0] < 0 ? (int)rect[0] + R : (int)rect[0], c1 = (int)rect[1], c2 = (int)rect[2];
+      const int n_side = R - 2 - r_top;  // rows r_top + 1 .. R - 2
+      if (r_top < 0 || n_side < 1 || c2 <= c1) throw std::runtime_error("--rectangle: need 0 <= r_top < R - 2 and c_first < c_second");
+      const int fx = LBM_ADE_SCALAR_FIXED;
+      body.add(r_top + 1, c1, 1, 0, n_side, LBM_ADE_FACE_COL_NEG, LBM_ADE_FACE_COL_NEG, fx, rect[3]);
+      body.add(-1, c1, 1, 0, 1, 0, LBM_ADE_FACE_COL_NEG & ~0x40u, fx, rect[3]);
+      body.add(r_top, c1, 0, 1, c2 - c1 + 1, LBM_ADE_FACE_ROW_NEG, LBM_ADE_FACE_ROW_NEG, fx, rect[3]);
+      body.add(r_top + 1, c2, 1, 0, n_side, LBM_ADE_FACE_COL_POS, LBM_ADE_FACE_COL_POS, fx, rect[3]);
+      body.finalize();
+      sv.set_walls(body);
+    }
     sv.set_state(f0, g0);
     sv.step(steps);
     const lbm::AdeSolver::State s = sv.state();

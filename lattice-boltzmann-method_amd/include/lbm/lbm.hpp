@@ -158,9 +158,35 @@ class Solver {  // single-phase BGK / KBC block, wraps lbm_solver
   int R_, C_;
 };
 
+// Interior walls of the fluid + scalar step, wraps lbm_ade_iwalls: wall nodes inside the block (the rectangle of
+// test/rectangle_sedimentation_test.cpp:184-196, :220-232).  add() segments, finalize() (the upload), then
+// AdeSolver::set_walls; the table is borrowed and must outlive every solver and captured graph that uses it.
+class AdeInteriorWalls {
+ public:
+  AdeInteriorWalls(int R, int C) { check(lbm_ade_iwalls_create(&h_, R, C)); }
+  AdeInteriorWalls(AdeInteriorWalls&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  AdeInteriorWalls(const AdeInteriorWalls&) = delete;
+  ~AdeInteriorWalls() {
+    if (h_) lbm_ade_iwalls_destroy(h_);
+  }
+  // the n nodes (r0 + i dr, c0 + i dc), negative r0 / c0 from the end; slot masks LBM_ADE_FACE_* (bit s-1 = slot s)
+  AdeInteriorWalls& add(int r0, int c0, int dr, int dc, int n, unsigned f_slots, unsigned g_slots,
+                        int g_mode = LBM_ADE_SCALAR_NO_FLUX, double conc = 0.0) {
+    check(lbm_ade_iwalls_add(h_, r0, c0, dr, dc, n, f_slots, g_slots, g_mode, conc));
+    return *this;
+  }
+  int count() const { return lbm_ade_iwalls_count(h_); }
+  void finalize() { check(lbm_ade_iwalls_finalize(h_)); }
+  const lbm_ade_iwalls* handle() const { return h_; }
+
+ private:
+  lbm_ade_iwalls* h_ = nullptr;
+};
+
 // Compressible BGK fluid + transported scalar on one block, wraps lbm_ade_solver: the sediment concentration of
 // test/rectangle_sedimentation_test.cpp:88-247 (equilibrium(g_equi, u + w, C), its own BGK rate, streamed like f;
-// no-flux walls, or fixed-concentration ones through set_scalar_bc; passive, or driving the fluid through set_buoyancy).
+// no-flux walls, or fixed-concentration ones through set_scalar_bc; passive, or driving the fluid through set_buoyancy;
+// obstacles inside the block through set_walls).
 // Host arrays in the reference layout.
 class AdeSolver {
  public:
@@ -189,6 +215,9 @@ class AdeSolver {
   // the scalar pushes on the fluid from the next step on: F = beta (C - c_ref) per node (lbm_ade_buoyancy; beta = (0, 0)
   // is the passive scalar).  state().u stays calc_u(f, rho): the equilibria take u + u_shift F.
   void set_buoyancy(const lbm_ade_buoyancy& b) { check(lbm_ade_solver_set_buoyancy(h_, &b)); }
+  // interior walls from the next stream on (a finalized table, borrowed: it must outlive the solver); clear_walls: none
+  void set_walls(const AdeInteriorWalls& w) { check(lbm_ade_solver_set_walls(h_, w.handle())); }
+  void clear_walls() { check(lbm_ade_solver_set_walls(h_, nullptr)); }
   // what the reference loop holds after the iterations run so far
   struct State {
     std::vector<double> f, g;  // [R][C][9]

@@ -24,6 +24,8 @@ RING_DEFAULT, RING_RCCL, RING_IPC = -1, 0, 1
 CG_PART_FRAME, CG_PART_INNER = 1, 2   # lbm_cg_step_fused_part (LBM_CG_PART_*)
 ADE_PART_FRAME, ADE_PART_INNER = 1, 2  # lbm_ade_stream_collide_part (LBM_ADE_PART_*)
 ADE_SCALAR_NO_FLUX, ADE_SCALAR_FIXED = 0, 1  # lbm_ade_scalar_bc.mode (LBM_ADE_SCALAR_*)
+# slot masks of the interior walls' axis-aligned facings (LBM_ADE_FACE_*): bit s-1 = slot s, fluid on the named side
+ADE_FACE_ROW_POS, ADE_FACE_ROW_NEG, ADE_FACE_COL_POS, ADE_FACE_COL_NEG = 0x91, 0x64, 0x32, 0xC8
 
 _dp = ct.POINTER(ct.c_double)
 
@@ -124,6 +126,58 @@ class AdeBuoyancy(ct.Structure):
 
 class LbmError(RuntimeError):
     pass
+
+
+class AdeInteriorWalls:
+    """Python face of lbm_ade_iwalls: wall nodes inside the block of the fluid + scalar step (the rectangle of
+    test/rectangle_sedimentation_test.cpp:184-196, :220-232).  Build with add / add_box, then finalize() -- the upload --
+    and hand it to AdeSolver(walls=...) / set_walls; it must outlive every solver and captured graph that uses it."""
+
+    def __init__(self, lib, R, C):
+        self.lib, self.R, self.C = lib, R, C
+        self.h = ct.c_void_p()
+        lib.ade_iwalls_create(ct.byref(self.h), int(R), int(C))
+
+    def add(self, r0, c0, dr, dc, n, f_slots, g_slots, g_mode=ADE_SCALAR_NO_FLUX, conc=0.0):
+        """the n nodes (r0 + i dr, c0 + i dc); negative r0 / c0 count from the end; slot masks: bit s-1 = slot s"""
+        self.lib.ade_iwalls_add(self.h, int(r0), int(c0), int(dr), int(dc), int(n), ct.c_uint(f_slots), ct.c_uint(g_slots),
+                                int(g_mode), ct.c_double(conc))
+        return self
+
+    def add_box(self, r0, r1, c0, c1, g_mode=ADE_SCALAR_NO_FLUX, conc=0.0):
+        """the closed box of rows r0..r1 and columns c0..c1 (inclusive, 0 <= r0 <= r1, 0 <= c0 <= c1) as four
+        outward-facing segments, f and g alike; a corner node carries the union of its two facings"""
+        for args in ((r0, c0, 0, 1, c1 - c0 + 1, ADE_FACE_ROW_NEG), (r1, c0, 0, 1, c1 - c0 + 1, ADE_FACE_ROW_POS),
+                     (r0, c0, 1, 0, r1 - r0 + 1, ADE_FACE_COL_NEG), (r0, c1, 1, 0, r1 - r0 + 1, ADE_FACE_COL_POS)):
+            self.add(*args, args[-1], g_mode, conc)
+        return self
+
+    def count(self):
+        return int(self.lib.raw.lbm_ade_iwalls_count(self.h))
+
+    def nodes(self):
+        """the merged table, sorted by (r, c): a list of dicts r, c, f_slots, g_slots, g_fixed_slots, conc"""
+        out = []
+        for i in range(self.count()):
+            r, c, f, g, gf, conc = ct.c_int(), ct.c_int(), ct.c_uint(), ct.c_uint(), ct.c_uint(), ct.c_double()
+            self.lib.ade_iwalls_node(self.h, i, *[ct.byref(x) for x in (r, c, f, g, gf, conc)])
+            out.append(dict(r=r.value, c=c.value, f_slots=f.value, g_slots=g.value, g_fixed_slots=gf.value, conc=conc.value))
+        return out
+
+    def finalize(self):
+        self.lib.ade_iwalls_finalize(self.h)
+        return self
+
+    def close(self):
+        if self.h:
+            self.lib.ade_iwalls_destroy(self.h)
+            self.h = ct.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def declared_symbols(header=HEADER):
@@ -270,15 +324,17 @@ class AdeSolver:
     """Python face of lbm_ade_solver: a compressible BGK fluid f and a transported scalar g on one block
     (the sediment loop of test/rectangle_sedimentation_test.cpp), numpy AoS in/out, reference layout."""
 
-    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None, scalar_bc=None, buoyancy=None):
+    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None, scalar_bc=None, buoyancy=None, walls=None):
         self.lib, self.R, self.C, self.fluid, self.scalar = lib, R, C, fluid, scalar
         self.g = Geom(R, C, 0)
         self.bc = bc if bc is not None else Bc.periodic()
         self.h = ct.c_void_p()
         lib.ade_solver_create(ct.byref(self.h), ct.byref(self.g), ct.byref(self.bc), ct.byref(fluid),
                               ct.byref(scalar), _stream(stream))
-        self.scalar_bc = self.buoyancy = None
+        self.scalar_bc = self.buoyancy = self.walls = None
         try:
+            if walls is not None:
+                self.set_walls(walls)
             if scalar_bc is not None:
                 self.set_scalar_bc(scalar_bc)
             if buoyancy is not None:
@@ -296,6 +352,11 @@ class AdeSolver:
         """the scalar's force on the fluid from the next step on (AdeBuoyancy, or None: the passive scalar)"""
         self.lib.ade_solver_set_buoyancy(self.h, ct.byref(buoyancy) if buoyancy is not None else None)
         self.buoyancy = buoyancy
+
+    def set_walls(self, walls):
+        """the interior walls from the next stream on (a finalized AdeInteriorWalls, or None: none); borrowed, not copied"""
+        self.lib.ade_solver_set_walls(self.h, walls.h if walls is not None else None)
+        self.walls = walls  # keeps the table alive
 
     def close(self):
         if self.h:

@@ -11,9 +11,13 @@ and against the single-step BGK launch, on one periodic box, in one process, alt
   --buoyancy adds a second periodic box whose scalar pushes on the fluid (lbm_ade_buoyancy, beta = (0.5, -0.3),
   c_ref = 5e-4, Guo's coefficients): buoyant, the same one launch and 288 B per node update in the reference order
   whatever --form says, beside the passive step of the same run
+  --interior-walls adds two boxes with bounce-back rows: iwalls_plain, and iwalls_rectangle with the sedimentation
+  driver's rectangle (rectangle_sedimentation_test.cpp:73-75 scaled to the box: ceiling R/3 above the last row, columns
+  2C/8 .. 5C/16; absorbing) as interior walls (lbm_ade_iwalls): one more launch per step, one lane per table node
 MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
 (18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
-usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls] [--buoyancy]"""
+usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls] [--buoyancy]
+       [--interior-walls]"""
 import argparse
 import ctypes as ct
 import json
@@ -44,6 +48,7 @@ def main():
     ap.add_argument("--skip-composed", action="store_true")
     ap.add_argument("--fixed-walls", action="store_true")
     ap.add_argument("--buoyancy", action="store_true")
+    ap.add_argument("--interior-walls", action="store_true")
     a = ap.parse_args()
     form = {"default": pylbm.FORM_DEFAULT, "ref": pylbm.FORM_REFERENCE_ORDER, "fast": pylbm.FORM_REASSOCIATED}[a.form]
     lib = pylbm.Lib()
@@ -131,6 +136,26 @@ def main():
         lib.lattice_copy_rows(_ptr(bgl), ct.byref(bgeo), 0, _ptr(g), ct.byref(dg), 0, R, st)
         lib.stream_sync(st)
 
+    bodies, table = {}, None
+    if a.interior_walls:
+        rbc = pylbm.Bc(row_lo=pylbm.EDGE_BOUNCE_BACK, row_hi=pylbm.EDGE_BOUNCE_BACK)
+        r_top, c1, c2 = -(R // 3), C * 2 // 8, C * 5 // 16
+        n_side = R // 3 - 2  # rows r_top + 1 .. R - 2
+        fx, neg, pos = pylbm.ADE_SCALAR_FIXED, pylbm.ADE_FACE_COL_NEG, pylbm.ADE_FACE_COL_POS
+        table = pylbm.AdeInteriorWalls(lib, R, C)
+        table.add(r_top + 1, c1, 1, 0, n_side, neg, neg, fx, 0.0)          # first wall; g runs through the last row,
+        table.add(-1, c1, 1, 0, 1, 0, neg & ~0x40, fx, 0.0)                # slot 7 of its foot left to the bottom wall
+        table.add(r_top, c1, 0, 1, c2 - c1 + 1, pylbm.ADE_FACE_ROW_NEG, pylbm.ADE_FACE_ROW_NEG, fx, 0.0)  # ceiling
+        table.add(r_top + 1, c2, 1, 0, n_side, pos, pos, fx, 0.0)          # second wall
+        table.finalize()
+        for key, t in (("iwalls_plain", None), ("iwalls_rectangle", table)):
+            w = pylbm.AdeSolver(lib, R, C, fluid, scalar, bc=rbc, stream=st.value, walls=t)
+            wf, wg, _, _, wgeo = w.lattices()
+            lib.lattice_copy_rows(_ptr(wf), ct.byref(wgeo), 0, _ptr(f), ct.byref(dg), 0, R, st)
+            lib.lattice_copy_rows(_ptr(wg), ct.byref(wgeo), 0, _ptr(g), ct.byref(dg), 0, R, st)
+            bodies[key] = w
+        lib.stream_sync(st)
+
     # composed: the reference loop from the unfused operators (dense lattices f, g advance in place of the loop)
     if not a.skip_composed:
         fe, ge, fc, gc = (torch.empty_like(f) for _ in range(4))
@@ -155,6 +180,8 @@ def main():
         runs[key] = w.step
     if buoyant is not None:
         runs["buoyant"] = buoyant.step
+    for key, w in bodies.items():
+        runs[key] = w.step
     if not a.skip_composed:
         runs["composed"] = run_composed
     for fn in runs.values():
@@ -193,6 +220,17 @@ def main():
         out["buoyant_over_fused_per_repeat"] = [round(p / b, 4) for p, b in zip(times["fused"], times["buoyant"])]
         out["buoyant_launches_total"] = buoyant.launches()
         buoyant.close()
+    if bodies:
+        out["iwalls_plain_mlups"] = round(mlups["iwalls_plain"], 1)
+        out["iwalls_rectangle_mlups"] = round(mlups["iwalls_rectangle"], 1)
+        out["iwalls_rectangle_over_plain"] = round(mlups["iwalls_rectangle"] / mlups["iwalls_plain"], 4)
+        out["iwalls_rectangle_over_plain_per_repeat"] = [round(p / b, 4) for p, b in
+                                                         zip(times["iwalls_plain"], times["iwalls_rectangle"])]
+        out["iwalls_table_nodes"] = table.count()
+        out["iwalls_launches_total"] = {k: w.launches() for k, w in bodies.items()}
+        for w in bodies.values():
+            w.close()
+        table.close()
     sv.close()
     lib.event_destroy(e0)
     lib.event_destroy(e1)
