@@ -110,8 +110,11 @@ static bool ade_fast(const lbm_ade_params* scalar) {
 }
 
 // The buoyancy (lbm_ade_buoyancy, NULL allowed) on the host: every field finite.  *by receives the device copy and
-// *buoyant whether the step is a buoyant one -- beta = (0, 0), like NULL, is the passive step.
-static int ade_buoyancy_check(const char* fn, const lbm_ade_buoyancy* b, AdeBuoyancy* by, bool* buoyant) {
+// *buoyant whether the step is a buoyant one -- beta = (0, 0), like NULL, is the passive step (both or neither given).
+int ade_buoyancy_check(const char* fn, const lbm_ade_buoyancy* b, AdeBuoyancy* by, bool* buoyant) {
+  AdeBuoyancy unused_by;
+  bool unused_flag;
+  if (!by) by = &unused_by, buoyant = &unused_flag;
   *by = AdeBuoyancy{};
   *buoyant = false;
   if (!b) return LBM_OK;
@@ -154,8 +157,10 @@ static int ade_lattice_args(const char* fn, const double* fn_, const double* gn,
 static const char* const kEdge[4] = {"row_lo", "row_hi", "col_lo", "col_hi"};
 
 // The scalar's walls (lbm_ade_scalar_bc) against the edges `bc` the launch runs with, on the host: a FIXED edge must be a
-// wall of the fluid there -- a BOUNCE_BACK row, a BOUNCE_BACK or SPECULAR column.  *sw receives the device copy.
-static int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc, AdeWalls* sw) {
+// wall of the fluid there -- a BOUNCE_BACK row, a BOUNCE_BACK or SPECULAR column.  *sw (if given) receives the device copy.
+int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc, AdeWalls* sw) {
+  AdeWalls unused;
+  if (!sw) sw = &unused;
   *sw = AdeWalls{};
   if (!sbc) return LBM_OK;
   const int modes[4] = {bc ? bc->row_lo : LBM_EDGE_PERIODIC, bc ? bc->row_hi : LBM_EDGE_PERIODIC,
@@ -192,51 +197,85 @@ static int ade_iwalls_check(const char* fn, const lbm_ade_iwalls* t, const lbm_g
   return LBM_OK;
 }
 
+// One call of the fused step after its host checks: the device copies that every launch of the call takes.  fluid and
+// scalar are borrowed for the call (with_ade_models picks the models per launch).
+struct AdeCall {
+  Geom g;
+  Bc bc;
+  AdeWalls sw;
+  AdeBuoyancy by;
+  bool buoyant;
+  const AdeIwallNode* wall_nodes;
+  int n_wall_nodes;
+  const lbm_bgk_params* fluid;
+  const lbm_ade_params* scalar;
+};
+static_assert(sizeof(AdeCall) <= sizeof(AdeCallBuf) && alignof(AdeCall) <= alignof(AdeCallBuf) &&
+              std::is_trivially_copyable<AdeCall>::value, "AdeCallBuf (internal.hpp) holds an AdeCall");
+
+// The host checks of a call, once, under the caller's name: the scalar's walls first (a FIXED edge names the edge mode it
+// cannot sit on), geometry and parameters, buoyancy, interior walls.  An entry checks its lattices and range or part after.
+int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
+                const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
+                const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call) {
+  int rc = ade_scalar_bc_check(fn, sbc, lbc, &call->sw);
+  if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar, slab);
+  if (!rc) rc = ade_buoyancy_check(fn, buoy, &call->by, &call->buoyant);
+  if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &call->wall_nodes, &call->n_wall_nodes);
+  if (rc) return rc;
+  call->g = make_geom(*lg);
+  call->bc = make_bc(lbc);
+  call->fluid = fluid;
+  call->scalar = scalar;
+  return LBM_OK;
+}
+
 template <bool B, class FM, class SM>
-static int ade_collide_launch(double* fp, double* gp, const double* f, const double* h, const Geom& g, const FM& fm,
-                              const SM& sm, const AdeBuoyancy& by, double* rho, double* u, double* conc, hipStream_t st) {
-  const long n = (long)g.R * g.C;
+static int ade_collide_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fp, double* gp, const double* f,
+                              const double* h, double* rho, double* u, double* conc, hipStream_t st) {
+  const long n = (long)k.g.R * k.g.C;
   const int grid = capped_grid((n + 255) / 256);
-  with_flags([&](auto M) { LBM_KLAUNCH((k_ade_collide<FM, SM, M(), B>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, g, fm, sm, rho, u, conc, by); }, rho != nullptr);
+  with_flags([&](auto M) { LBM_KLAUNCH((k_ade_collide<FM, SM, M(), B>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, k.g, fm, sm, rho, u, conc, k.by); }, rho != nullptr);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
 
 // interior launch + (walls only) the edge pass + (a non-empty table of interior walls only) the interior-wall pass;
-// *launches += the kernels enqueued
+// *launches (if given) += the kernels enqueued
 template <bool B, class FM, class SM>
-static int ade_step_launch(double* fn, double* gn, const double* fo, const double* go, const Geom& g, const Bc& bc,
-                           const FM& fm, const SM& sm, const AdeWalls& sw, const AdeBuoyancy& by,
-                           const AdeIwallNode* wall_nodes, int n_wall_nodes, int row_begin, int row_end, double* rho,
-                           double* u, double* conc, hipStream_t st, long long* launches) {
+static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
+                           const double* go, int row_begin, int row_end, double* rho, double* u, double* conc,
+                           hipStream_t st, long long* launches) {
+  long long uncounted = 0;
+  if (!launches) launches = &uncounted;
   const bool mom = rho != nullptr;
   const int nt = tuning("nt", 3);  // bit 0: non-temporal loads, bit 1: non-temporal stores
   const int cap = tuning("grid_cap", 0);
-  const int tiles = (g.C + 511) / 512;
+  const int tiles = (k.g.C + 511) / 512;
   const long items = (long)(row_end - row_begin) * tiles;
   const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
   with_flags([&](auto NL, auto NS, auto M) {
-    LBM_KLAUNCH((k_ade_stream_collide<FM, SM, NL(), NS(), M(), B>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, g, fm,
-                sm, row_begin, row_end, tiles, rho, u, conc, by);
+    LBM_KLAUNCH((k_ade_stream_collide<FM, SM, NL(), NS(), M(), B>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, k.g, fm,
+                sm, row_begin, row_end, tiles, rho, u, conc, k.by);
   }, nt & 1, nt & 2, mom);
   LBM_CHECK_LAUNCH();
   ++*launches;
-  if (bc_needs_edge_pass(bc)) {
-    const int n_edge = 2 * g.C + 2 * (row_end - row_begin);
+  if (bc_needs_edge_pass(k.bc)) {
+    const int n_edge = 2 * k.g.C + 2 * (row_end - row_begin);
     const dim3 grid_e((n_edge + 255) / 256);
     with_flags([&](auto M, auto F) {
-      LBM_KLAUNCH((k_ade_edge<FM, SM, M(), F(), B>), grid_e, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin,
-                  row_end, rho, u, conc, sw, by);
-    }, mom, sw.fixed);
+      LBM_KLAUNCH((k_ade_edge<FM, SM, M(), F(), B>), grid_e, dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc, fm, sm, row_begin,
+                  row_end, rho, u, conc, k.sw, k.by);
+    }, mom, k.sw.fixed);
     LBM_CHECK_LAUNCH();
     ++*launches;
   }
-  if (n_wall_nodes > 0) {  // one lane per table node, after the passes whose nodes it overwrites
-    const dim3 grid_w((n_wall_nodes + 255) / 256);
+  if (k.n_wall_nodes > 0) {  // one lane per table node, after the passes whose nodes it overwrites
+    const dim3 grid_w((k.n_wall_nodes + 255) / 256);
     with_flags([&](auto M, auto F) {
-      LBM_KLAUNCH((k_ade_iwalls<FM, SM, M(), F(), B>), grid_w, dim3(256), 0, st, fn, gn, fo, go, g, bc, fm, sm, row_begin,
-                  row_end, rho, u, conc, sw, by, wall_nodes, n_wall_nodes);
-    }, mom, sw.fixed);
+      LBM_KLAUNCH((k_ade_iwalls<FM, SM, M(), F(), B>), grid_w, dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc, fm, sm, row_begin,
+                  row_end, rho, u, conc, k.sw, k.by, k.wall_nodes, k.n_wall_nodes);
+    }, mom, k.sw.fixed);
     LBM_CHECK_LAUNCH();
     ++*launches;
   }
@@ -245,95 +284,81 @@ static int ade_step_launch(double* fn, double* gn, const double* fo, const doubl
 
 // one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline
 template <bool B, class FM, class SM>
-static int ade_part_launch(double* fn, double* gn, const double* fo, const double* go, const Geom& g, const Bc& bc,
-                           const FM& fm, const SM& sm, const AdeWalls& sw, const AdeBuoyancy& by, int band0, int n0,
-                           int band1, int nrows, double* rho, double* u, double* conc, hipStream_t st) {
+static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
+                           const double* go, int band0, int n0, int band1, int nrows, double* rho, double* u,
+                           double* conc, hipStream_t st) {
   const bool mom = rho != nullptr;
   const int nt = tuning("nt", 3);  // as the single-block step
   const int cap = tuning("grid_cap", 0);
-  const int tiles = (g.C + 511) / 512;
+  const int tiles = (k.g.C + 511) / 512;
   const long items = (long)nrows * tiles;
   const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
   with_flags([&](auto NL, auto NS, auto M, auto F) {
     LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL(), NS(), M(), F(), B>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go,
-                g, bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, sw, by);
-  }, nt & 1, nt & 2, mom, sw.fixed);
+                k.g, k.bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, k.sw, k.by);
+  }, nt & 1, nt & 2, mom, k.sw.fixed);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
 
-// collide only: no streaming, so no wall rule -- the scalar's walls (sbc) and the interior walls (iwalls) are checked
-// and nothing more
+// collide only: no streaming, so no wall rule -- the scalar's walls and the interior walls of the call are checked and
+// nothing more
+int ade_collide_from(const char* fn, const AdeCall& k, double* fp, double* gp, const double* f, const double* h,
+                     double* rho, double* u, double* conc, hipStream_t st) {
+  if (int rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false)) return rc;
+  return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
+    return ade_collide_launch<B()>(k, fm, sm, fp, gp, f, h, rho, u, conc, st);
+  });
+}
+
 static int ade_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* lg,
                        const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                       const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc,
-                       hipStream_t st, bool slab = false, const lbm_ade_iwalls* iwalls = nullptr) {
-  AdeWalls sw;
-  AdeBuoyancy by;
-  bool buoyant;
-  const AdeIwallNode* wall_nodes;
-  int n_wall_nodes;
-  int rc = ade_scalar_bc_check(fn, sbc, bc, &sw);
-  if (!rc) rc = ade_validate(fn, lg, bc, fluid, scalar, slab);
-  if (!rc) rc = ade_buoyancy_check(fn, buoy, &by, &buoyant);
-  if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &wall_nodes, &n_wall_nodes);
-  if (!rc) rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false);
-  if (rc) return rc;
-  const Geom g = make_geom(*lg);
-  return with_ade_models(fluid, scalar, buoyant, [&](const auto& fm, const auto& sm, auto B) {
-    return ade_collide_launch<B()>(fp, gp, f, h, g, fm, sm, by, rho, u, conc, st);
-  });
+                       const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                       double* rho, double* u, double* conc, hipStream_t st) {
+  AdeCall k;
+  if (int rc = ade_resolve(fn, lg, bc, fluid, scalar, sbc, buoy, iwalls, false, &k)) return rc;
+  return ade_collide_from(fn, k, fp, gp, f, h, rho, u, conc, st);
 }
 
 static int ade_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
                               const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
                               const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
                               const lbm_ade_iwalls* iwalls, int row_begin, int row_end, double* rho, double* u,
-                              double* conc, hipStream_t st, long long* launches) {
-  AdeWalls sw;  // the scalar's walls first: a FIXED edge names the edge mode it cannot sit on
-  AdeBuoyancy by;
-  bool buoyant;
-  const AdeIwallNode* wall_nodes;
-  int n_wall_nodes;
-  int rc = ade_scalar_bc_check(fn, sbc, lbc, &sw);
-  if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar);
-  if (!rc) rc = ade_buoyancy_check(fn, buoy, &by, &buoyant);
-  if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &wall_nodes, &n_wall_nodes);
+                              double* conc, hipStream_t st, long long* launches = nullptr) {
+  AdeCall k;
+  int rc = ade_resolve(fn, lg, lbc, fluid, scalar, sbc, buoy, iwalls, false, &k);
   if (!rc) rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true);
   if (rc) return rc;
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R, "%s: row range [%d, %d) outside [0, %d)", fn,
               row_begin, row_end, lg->R);
   if (row_begin == row_end) return LBM_OK;
-  const Geom g = make_geom(*lg);
-  const Bc bc = make_bc(lbc);
-  return with_ade_models(fluid, scalar, buoyant, [&](const auto& fm, const auto& sm, auto B) {
-    return ade_step_launch<B()>(fn_, gn, fo, go, g, bc, fm, sm, sw, by, wall_nodes, n_wall_nodes, row_begin, row_end, rho,
-                                u, conc, st, launches);
+  return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
+    return ade_step_launch<B()>(k, fm, sm, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
   });
 }
 
-int ade_part_check(const char* name, const double* fn, const double* gn, const double* fo, const double* go,
-                   const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                   int part, int edge_rows, const double* rho, const double* u, const double* conc) {
-  int rc = ade_validate(name, lg, lbc, fluid, scalar, true);
-  if (!rc) rc = ade_lattice_args(name, fn, gn, fo, go, rho, u, conc, true);
-  if (rc) return rc;
+// the lattices and the part of a part launch, on the host
+int ade_part_args(const char* fn, const AdeCall& k, const double* fn_, const double* gn, const double* fo,
+                  const double* go, int part, int edge_rows, const double* rho, const double* u, const double* conc) {
+  if (int rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true)) return rc;
   LBM_REQUIRE(part == LBM_ADE_PART_FRAME || part == LBM_ADE_PART_INNER,
-              "%s: part=%d (LBM_ADE_PART_FRAME or LBM_ADE_PART_INNER)", name, part);
-  LBM_REQUIRE(edge_rows >= 1 && 2 * edge_rows < lg->R, "%s: edge_rows=%d: need 1 <= edge_rows and 2 x edge_rows < R=%d",
-              name, edge_rows, lg->R);
+              "%s: part=%d (LBM_ADE_PART_FRAME or LBM_ADE_PART_INNER)", fn, part);
+  LBM_REQUIRE(edge_rows >= 1 && 2 * edge_rows < k.g.R, "%s: edge_rows=%d: need 1 <= edge_rows and 2 x edge_rows < R=%d",
+              fn, edge_rows, k.g.R);
   return LBM_OK;
 }
 
-int ade_scalar_bc_validate(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc) {
-  AdeWalls sw;
-  return ade_scalar_bc_check(fn, sbc, bc, &sw);
-}
-
-int ade_buoyancy_validate(const char* fn, const lbm_ade_buoyancy* buoy) {
-  AdeBuoyancy by;
-  bool buoyant;
-  return ade_buoyancy_check(fn, buoy, &by, &buoyant);
+// one part of a call, after ade_part_args
+int ade_part_from(const AdeCall& k, double* fn, double* gn, const double* fo, const double* go, int part, int edge_rows,
+                  double* rho, double* u, double* conc, hipStream_t st) {
+  const int R = k.g.R;
+  // FRAME: rows [0, E) then [R - E, R); INNER: rows [E, R - E)
+  const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;
+  const int n0 = part == LBM_ADE_PART_FRAME ? edge_rows : R - 2 * edge_rows;
+  const int band1 = R - edge_rows, nrows = part == LBM_ADE_PART_FRAME ? 2 * edge_rows : n0;
+  return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
+    return ade_part_launch<B()>(k, fm, sm, fn, gn, fo, go, band0, n0, band1, nrows, rho, u, conc, st);
+  });
 }
 
 // lbm_ade_stream_collide_part(_ex, _b) under the caller's name
@@ -341,34 +366,10 @@ static int ade_part(const char* name, double* fn, double* gn, const double* fo, 
                     const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                     const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int part, int edge_rows, double* rho,
                     double* u, double* conc, hipStream_t st) {
-  AdeWalls sw;  // the scalar's walls first, as ade_stream_collide
-  AdeBuoyancy by;
-  bool buoyant;
-  int rc = ade_scalar_bc_check(name, sbc, lbc, &sw);
-  if (!rc) rc = ade_buoyancy_check(name, buoy, &by, &buoyant);
-  if (!rc) rc = ade_part_check(name, fn, gn, fo, go, lg, lbc, fluid, scalar, part, edge_rows, rho, u, conc);
-  if (rc) return rc;
-  const int R = lg->R;
-  const Geom g = make_geom(*lg);
-  const Bc bc = make_bc(lbc);
-  // FRAME: rows [0, E) then [R - E, R); INNER: rows [E, R - E)
-  const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;
-  const int n0 = part == LBM_ADE_PART_FRAME ? edge_rows : R - 2 * edge_rows;
-  const int band1 = R - edge_rows, nrows = part == LBM_ADE_PART_FRAME ? 2 * edge_rows : n0;
-  return with_ade_models(fluid, scalar, buoyant, [&](const auto& fm, const auto& sm, auto B) {
-    return ade_part_launch<B()>(fn, gn, fo, go, g, bc, fm, sm, sw, by, band0, n0, band1, nrows, rho, u, conc, st);
-  });
-}
-
-int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
-                      const lbm_ade_params* scalar) {
-  return ade_validate(fn, g, bc, fluid, scalar, true);
-}
-
-int ade_collide_slab(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
-                     const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                     const lbm_ade_buoyancy* buoy, hipStream_t st) {
-  return ade_collide(fn, fp, gp, f, h, g, bc, fluid, scalar, nullptr, buoy, nullptr, nullptr, nullptr, st, true);
+  AdeCall k;
+  int rc = ade_resolve(name, lg, lbc, fluid, scalar, sbc, buoy, nullptr, true, &k);
+  if (!rc) rc = ade_part_args(name, k, fn, gn, fo, go, part, edge_rows, rho, u, conc);
+  return rc ? rc : ade_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
 }
 
 }  // namespace lbm
@@ -404,49 +405,46 @@ extern "C" {
 int lbm_ade_collide(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
                     const lbm_bgk_params* fluid, const lbm_ade_params* scalar, double* rho, double* u, double* conc,
                     lbm_stream_t s) {
-  return ade_collide("lbm_ade_collide", fp, gp, f, g_in, g, bc, fluid, scalar, nullptr, nullptr, rho, u, conc,
+  return ade_collide("lbm_ade_collide", fp, gp, f, g_in, g, bc, fluid, scalar, nullptr, nullptr, nullptr, rho, u, conc,
                      as_stream(s));
 }
 
 int lbm_ade_collide_b(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
                       const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                       const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_collide("lbm_ade_collide_b", fp, gp, f, g_in, g, bc, fluid, scalar, sbc, buoy, rho, u, conc, as_stream(s));
+  return ade_collide("lbm_ade_collide_b", fp, gp, f, g_in, g, bc, fluid, scalar, sbc, buoy, nullptr, rho, u, conc,
+                     as_stream(s));
 }
 
 int lbm_ade_stream_collide(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                            const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int row_begin,
                            int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
-  long long launches = 0;
   return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, nullptr, nullptr, nullptr,
-                            row_begin, row_end, rho, u, conc, as_stream(s), &launches);
+                            row_begin, row_end, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_stream_collide_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                               const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                               const lbm_ade_scalar_bc* sbc, int row_begin, int row_end, double* rho, double* u,
                               double* conc, lbm_stream_t s) {
-  long long launches = 0;
   return ade_stream_collide("lbm_ade_stream_collide_ex", fn, gn, fo, go, g, bc, fluid, scalar, sbc, nullptr, nullptr,
-                            row_begin, row_end, rho, u, conc, as_stream(s), &launches);
+                            row_begin, row_end, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_stream_collide_b(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                              const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int row_begin, int row_end,
                              double* rho, double* u, double* conc, lbm_stream_t s) {
-  long long launches = 0;
   return ade_stream_collide("lbm_ade_stream_collide_b", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, nullptr,
-                            row_begin, row_end, rho, u, conc, as_stream(s), &launches);
+                            row_begin, row_end, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_stream_collide_w(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                              const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                              int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
-  long long launches = 0;
   return ade_stream_collide("lbm_ade_stream_collide_w", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, iwalls,
-                            row_begin, row_end, rho, u, conc, as_stream(s), &launches);
+                            row_begin, row_end, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_stream_collide_part(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
@@ -554,7 +552,7 @@ int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
     int rc;
     if (!sv->post) {
       rc = ade_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid,
-                       &sv->scalar, nullptr, buoy, nullptr, nullptr, nullptr, sv->st, false, sv->walls);
+                       &sv->scalar, nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st);
       if (!rc) ++sv->launches;
     } else {
       rc = ade_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
@@ -583,6 +581,13 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
   const lbm_geom dg{R, C, 0, 0, 0};
   const bool fixed = sv->post && sv->fixed;
   bool have_u = false;  // sv->rho, sv->u hold the moments of the streamed f
+  auto moments_of_f = [&]() {  // sv->rho = calc_rho, sv->u = calc_u of sv->f(k), through the parity operators
+    int rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->f(k), &g, 0, R, sv->st);
+    if (!rc) rc = lbm_calc_rho(sv->rho, sv->dense, R, C, sv->st);
+    if (!rc) rc = lbm_calc_u(sv->u, sv->dense, sv->rho, R, C, sv->st);
+    have_u = true;
+    return rc;
+  };
   if (sv->post) {
     const AdeIwallNode* wall_nodes;
     int n_wall_nodes;
@@ -599,21 +604,16 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
     AdeWalls sw;
     rc = ade_scalar_bc_check("lbm_ade_solver_get_state", fixed ? &sv->sbc : nullptr, &sv->bc, &sw);
     if (rc) return rc;
-    // g gathers as BOUNCE_BACK at a FIXED column (ade_scalar_gather_bc); the FIXED edges then take their rule with
-    // u = the reference-order calc_u of the streamed f
+    // g gathers as BOUNCE_BACK at a FIXED column; the FIXED edges then take their rule with u = the reference-order
+    // calc_u of the streamed f
+    const Bc gather = ade_scalar_gather_bc(make_bc(&sv->bc), sw.fixed);
     lbm_bc gbc = sv->bc;
-    if (sw.fixed & 4) gbc.col_lo = LBM_EDGE_BOUNCE_BACK;
-    if (sw.fixed & 8) gbc.col_hi = LBM_EDGE_BOUNCE_BACK;
+    gbc.col_lo = gather.col_lo, gbc.col_hi = gather.col_hi;
     rc = lbm_stream(sv->h(k ^ 1), sv->h(k), &g, &gbc, sv->st);
     if (rc) return rc;
     k ^= 1;
-    if (fixed || n_wall_nodes > 0) {
-      rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->f(k), &g, 0, R, sv->st);
-      if (!rc) rc = lbm_calc_rho(sv->rho, sv->dense, R, C, sv->st);
-      if (!rc) rc = lbm_calc_u(sv->u, sv->dense, sv->rho, R, C, sv->st);
-      if (rc) return rc;
-      have_u = true;
-    }
+    if (fixed || n_wall_nodes > 0)
+      if ((rc = moments_of_f())) return rc;
     if (fixed) {
       const int n_edge = 2 * C + 2 * R;
       LBM_KLAUNCH(k_ade_fixed_state, dim3((n_edge + 255) / 256), dim3(256), 0, sv->st, sv->h(k), make_geom(g),
@@ -626,25 +626,19 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
       LBM_CHECK_LAUNCH();
     }
   }
-  if (f || rho || u) {
-    if (f) {
-      int rc = lbm_soa_to_aos_pitched(sv->stage, sv->f(k), R, C, 9, g.plane_stride, g.row_pitch, sv->st);
+  if (f) {
+    int rc = lbm_soa_to_aos_pitched(sv->stage, sv->f(k), R, C, 9, g.plane_stride, g.row_pitch, sv->st);
+    if (rc) return rc;
+    LBM_CHECK_HIP(hipMemcpyAsync(f, sv->stage, n * 9 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
+  }
+  if (rho || u) {
+    if (!have_u)
+      if (int rc = moments_of_f()) return rc;
+    if (rho) LBM_CHECK_HIP(hipMemcpyAsync(rho, sv->rho, n * sizeof(double), hipMemcpyDeviceToHost, sv->st));
+    if (u) {
+      int rc = lbm_soa_to_aos(sv->stage, sv->u, R, C, 2, sv->st);
       if (rc) return rc;
-      LBM_CHECK_HIP(hipMemcpyAsync(f, sv->stage, n * 9 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
-    }
-    if ((rho || u) && !have_u) {
-      int rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->f(k), &g, 0, R, sv->st);
-      if (!rc) rc = lbm_calc_rho(sv->rho, sv->dense, R, C, sv->st);
-      if (!rc) rc = lbm_calc_u(sv->u, sv->dense, sv->rho, R, C, sv->st);
-      if (rc) return rc;
-    }
-    if (rho || u) {
-      if (rho) LBM_CHECK_HIP(hipMemcpyAsync(rho, sv->rho, n * sizeof(double), hipMemcpyDeviceToHost, sv->st));
-      if (u) {
-        int rc = lbm_soa_to_aos(sv->stage, sv->u, R, C, 2, sv->st);
-        if (rc) return rc;
-        LBM_CHECK_HIP(hipMemcpyAsync(u, sv->stage, n * 2 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
-      }
+      LBM_CHECK_HIP(hipMemcpyAsync(u, sv->stage, n * 2 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
     }
   }
   if (g_out) {
@@ -693,7 +687,7 @@ int lbm_ade_solver_set_scalar_bc(lbm_ade_solver* sv, const lbm_ade_scalar_bc* sb
 
 int lbm_ade_solver_set_buoyancy(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy) {
   LBM_REQUIRE(sv, "lbm_ade_solver_set_buoyancy: NULL solver");
-  int rc = ade_buoyancy_validate("lbm_ade_solver_set_buoyancy", buoy);
+  int rc = ade_buoyancy_check("lbm_ade_solver_set_buoyancy", buoy);
   if (rc) return rc;
   sv->buoy = buoy ? *buoy : lbm_ade_buoyancy{};
   sv->buoyant = buoy != nullptr;

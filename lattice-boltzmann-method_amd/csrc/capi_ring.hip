@@ -309,49 +309,43 @@ static int ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm
 }
 
 // ---- the fluid + scalar pair (lbm_ade_*) over row slabs: one ghost row per side, both lattices in one message ----------
-// The slab's edges (ring_slab_bc, periodic by default), checked with everything else the part launches check, before any
-// device call.
-static int ring_ade_edges(const char* fn, lbm_ring* rg, const lbm_bc* bc, const lbm_bgk_params* fluid,
-                          const lbm_ade_params* scalar, lbm_bc* b) {
+// The call of a ring entry, resolved once, before any device call: the slab's edges (ring_slab_bc, periodic by default) and
+// the scalar's walls -- gsbc, of the global domain, checked against the global edges; a FIXED row acts where the slab keeps
+// that edge (a chain end) and is dropped at a seam, as the fluid's row wall is.
+static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, const lbm_bgk_params* fluid,
+                            const lbm_ade_params* scalar, const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy,
+                            AdeCall* call) {
   LBM_REQUIRE(rg->g.ghost == 1, "%s: ghost=%d: the fluid + scalar step over slabs exchanges one ghost row per side (ring "
               "slabs need ghost=1)", fn, rg->g.ghost);
-  *b = ring_slab_bc(rg, bc);
-  return ade_validate_slab(fn, &rg->g, b, fluid, scalar);
+  const lbm_bc b = ring_slab_bc(rg, bc);
+  lbm_ade_scalar_bc sb{};
+  if (gsbc) {
+    if (int rc = ade_scalar_bc_check(fn, gsbc, bc ? bc : &kPeriodicBc)) return rc;
+    sb = *gsbc;
+    if (b.row_lo == LBM_EDGE_HALO) sb.mode[0] = LBM_ADE_SCALAR_NO_FLUX;
+    if (b.row_hi == LBM_EDGE_HALO) sb.mode[1] = LBM_ADE_SCALAR_NO_FLUX;
+  }
+  return ade_resolve(fn, &rg->g, &b, fluid, scalar, gsbc ? &sb : nullptr, buoy, nullptr, true, call);
 }
 
 // FRAME (both edge bands, one dispatch) + pack + one message per neighbour on the ring's stream, INNER on `main` beside
-// them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches
+// them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches of one resolved call
 static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go,
                          const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                          const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, int edge_rows,
                          lbm_stream_t main_s) {
-  int rc = ade_buoyancy_validate(fn, buoy);  // needs no ring
+  int rc = ade_buoyancy_check(fn, buoy);  // needs no ring
   if (rc) return rc;
   LBM_REQUIRE(rg && fn_ && gn && fo && go && fluid && scalar, "%s: NULL argument", fn);
-  lbm_bc b;
-  rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
-  if (rc) return rc;
-  // the scalar's walls: checked against the global edges; a FIXED row acts where the slab keeps that edge (a chain end)
-  // and is dropped at a seam, as the fluid's row wall is
-  lbm_ade_scalar_bc sb{};
-  const lbm_ade_scalar_bc* sbc = nullptr;
-  if (gsbc) {
-    rc = ade_scalar_bc_validate(fn, gsbc, bc ? bc : &kPeriodicBc);
-    if (rc) return rc;
-    sb = *gsbc;
-    if (b.row_lo == LBM_EDGE_HALO) sb.mode[0] = LBM_ADE_SCALAR_NO_FLUX;
-    if (b.row_hi == LBM_EDGE_HALO) sb.mode[1] = LBM_ADE_SCALAR_NO_FLUX;
-    sbc = &sb;
-  }
+  AdeCallBuf buf;
+  const AdeCall& call = *buf.get();
   if (edge_rows < 1) edge_rows = 1;
-  rc = ade_part_check(fn, fn_, gn, fo, go, &rg->g, &b, fluid, scalar, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr,
-                      nullptr);
-  if (!rc) rc = ade_scalar_bc_validate(fn, sbc, &b);
+  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, buf.get());
+  if (!rc) rc = ade_part_args(fn, call, fn_, gn, fo, go, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr, nullptr);
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
   auto part = [&](int which, hipStream_t st) {
-    return lbm_ade_stream_collide_part_b(fn_, gn, fo, go, &rg->g, &b, fluid, scalar, sbc, buoy, which, edge_rows, nullptr,
-                                         nullptr, nullptr, st);
+    return ade_part_from(call, fn_, gn, fo, go, which, edge_rows, nullptr, nullptr, nullptr, st);
   };
   if (rg->prev < 0 && rg->next < 0) {  // a chain of one slab: nothing travels
     rc = part(LBM_ADE_PART_FRAME, main);
@@ -632,20 +626,18 @@ int lbm_ring_cg_step(lbm_ring* rg, double* dst_r, double* dst_b, const double* s
   return ring_step(rg, main, edges, interior, dst_r, dst_b, LBM_HALO_TWO_PHASE);
 }
 
-// lbm_ring_ade_collide(_b) under the caller's name; gsbc: the scalar's walls of the global domain, checked only (the
-// collide-only iteration applies no wall rule)
+// lbm_ring_ade_collide(_b) under the caller's name; the scalar's walls are checked only (collide-only applies no wall rule)
 static int ring_ade_collide(const char* fn, lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in,
                             const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                             const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, lbm_stream_t main_s) {
-  int rc = ade_buoyancy_validate(fn, buoy);  // needs no ring
+  int rc = ade_buoyancy_check(fn, buoy);  // needs no ring
   if (rc) return rc;
   LBM_REQUIRE(rg && fp && gp && f && g_in && fluid && scalar, "%s: NULL argument", fn);
-  lbm_bc b;
-  rc = ring_ade_edges(fn, rg, bc, fluid, scalar, &b);
-  if (!rc) rc = ade_scalar_bc_validate(fn, gsbc, bc ? bc : &kPeriodicBc);
+  AdeCallBuf buf;
+  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, buf.get());
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
-  rc = ade_collide_slab(fn, fp, gp, f, g_in, &rg->g, &b, fluid, scalar, buoy, main);
+  rc = ade_collide_from(fn, *buf.get(), fp, gp, f, g_in, nullptr, nullptr, nullptr, main);
   if (rc || (rg->prev < 0 && rg->next < 0)) return rc;
   return ring_join(rg, main, ring_exchange_depth(rg, fp, gp, 1, main));
 }

@@ -48,20 +48,31 @@ int box_copy(double* dst, const lbm_geom& dg, int dst_row, int dst_col, const do
 // (A stream that spares one compute unit for the chain -- hipExtStreamCreateWithCUMask -- was tried and is far slower:
 // profiles/r02_ibm_box_bench.log.)
 int make_background_stream(hipStream_t* out);
-// capi_ade.hip: the host checks of lbm_ade_stream_collide_part (slab geometries: ghost rows, HALO row edges; all of its
-// arguments / the geometry and parameters alone) and the collide-only launch on the owned rows of such a geometry (the first driver iteration of lbm_ring_ade_collide)
-int ade_part_check(const char* fn, const double* f_new, const double* g_new, const double* f_old, const double* g_old,
-                   const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                   int part, int edge_rows, const double* rho, const double* u, const double* conc);
-// the scalar's walls (lbm_ade_scalar_bc, NULL allowed) against the edges bc, on the host
-int ade_scalar_bc_validate(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc);
-// the buoyancy (lbm_ade_buoyancy, NULL allowed), on the host: every field finite
-int ade_buoyancy_validate(const char* fn, const lbm_ade_buoyancy* buoy);
-int ade_validate_slab(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
-                      const lbm_ade_params* scalar);
-int ade_collide_slab(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
-                     const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                     const lbm_ade_buoyancy* buoy /* may be NULL */, hipStream_t st);
+// capi_ade.hip: one call of the fused fluid + scalar step after its host checks -- the device copies of geometry, edges,
+// scalar walls, buoyancy and interior-wall table that every launch of the call takes.  Its members are ade.hpp's, and
+// ade.hpp defines kernels, so AdeCall is complete in capi_ade.hip alone: another unit keeps one in an AdeCallBuf.
+struct AdeCall;
+struct AdeWalls;
+struct AdeBuoyancy;
+struct AdeCallBuf {
+  alignas(8) unsigned char bytes[256];
+  AdeCall* get() { return reinterpret_cast<AdeCall*>(bytes); }
+};
+// the host checks, once, under the caller's name fn (slab: ghost rows and HALO row edges allowed; sbc, buoy, iwalls may be
+// NULL), and the two of them that need no geometry on their own (sw, by: the device copy, if wanted)
+int ade_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
+                const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
+                const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call);
+int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc, AdeWalls* sw = nullptr);
+int ade_buoyancy_check(const char* fn, const lbm_ade_buoyancy* buoy, AdeBuoyancy* by = nullptr, bool* buoyant = nullptr);
+// launches from a resolved call: one part (LBM_ADE_PART_*; its lattices and part pass ade_part_args first) and the
+// collide-only pass on the owned rows (the first driver iteration)
+int ade_part_args(const char* fn, const AdeCall& call, const double* f_new, const double* g_new, const double* f_old,
+                  const double* g_old, int part, int edge_rows, const double* rho, const double* u, const double* conc);
+int ade_part_from(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old, int part,
+                  int edge_rows, double* rho, double* u, double* conc, hipStream_t st);
+int ade_collide_from(const char* fn, const AdeCall& call, double* fp, double* gp, const double* f, const double* h,
+                     double* rho, double* u, double* conc, hipStream_t st);
 // NumPy .npy (v1.0, little-endian f64, C order) writer shared by the snapshot objects
 int write_npy(const char* path, const double* data, const std::vector<long>& shape);
 

@@ -2,10 +2,10 @@
 _part_b, lbm_ade_solver_set_buoyancy, lbm_ring_ade_*_b through the slab_ring_ade driver; pylbm.AdeBuoyancy; the drivers'
 --buoyancy).
 
-The yardstick of every bitwise test is `buoyant_loop` below: the reference's sediment loop composed from the oracle's
-solver:: primitives (calc_rho, calc_u, equilibrium, advect, collision for the scalar), with the force, the velocity shift
-and the fluid's forced collision (items 4-6 of the step in include/lbm_hip.h) written in numpy in exactly that order --
-numpy's element-wise f64 operations do not fuse -- and the wall rules of tests/test_gpu_ade_scalar_bc.py, which take
+The yardstick of every bitwise test is `oracle_loop` of tests/ade_util.py with a buoyancy: the reference's sediment loop
+composed from the oracle's solver:: primitives (calc_rho, calc_u, equilibrium, advect, collision for the scalar), with the
+force, the velocity shift and the fluid's forced collision (items 4-6 of the step in include/lbm_hip.h) written in numpy
+in exactly that order -- numpy's element-wise f64 operations do not fuse -- and the wall rules, which take
 u = calc_u(f_adve), the UNSHIFTED velocity.  The loop never calls the library under test."""
 import ctypes as ct
 import json
@@ -19,7 +19,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
-import test_gpu_ade_scalar_bc as walls  # noqa: E402  (initial state, wall rules and slab helpers of the passive suite)
+import ade_util as ade  # noqa: E402
+from ade_util import GUO, REFERENCE, buoyancy, buoyant_collide, from_lattice, stream, to_lattice  # noqa: E402
 from gpu_util import bits_equal, dev  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
@@ -29,9 +30,6 @@ REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 BB, SP, HALO, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR, pylbm.EDGE_HALO, pylbm.EDGE_PERIODIC
 FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
 W = (3e-3, -2e-3)
-E9, CX, CY = walls.E9, walls.CX, walls.CY
-REFERENCE = (1.0, (1.0 / 3.0, 1.0 / 9.0))  # (u_shift, guo): test/gravity_test.cpp
-GUO = (0.5, (3.0, 9.0))
 OMEGA, OMEGA_G = 1.2, 1.7
 
 
@@ -42,56 +40,8 @@ def lib():
     return lib
 
 
-def buoyancy(beta, c_ref, variant):
-    return pylbm.AdeBuoyancy(beta, c_ref, variant[0], variant[1])
-
-
-# ---- the yardstick ------------------------------------------------------------------------------------------------------
-def buoyant_collide(orc, f, g, omega, omega_g, w, by):
-    """one node-local half iteration on the pre-collision (f, g): items 1 and 3-7; returns the post-collision pair and the
-    moments the raw entry points write (u: the shifted one)"""
-    rho = orc.calc_rho(f)                                               # 1
-    u0 = orc.calc_u(f, rho)
-    conc = orc.calc_rho(g)                                              # 3
-    dc = conc - by.c_ref                                                # 4
-    Fr, Fc = dc * by.beta_r, dc * by.beta_c
-    u = np.empty_like(u0)                                               # 5
-    u[..., 0] = u0[..., 0] + by.u_shift * Fr
-    u[..., 1] = u0[..., 1] + by.u_shift * Fc
-    fe = orc.equilibrium(u, rho)                                        # 6
-    uF = u[..., 0] * Fr + u[..., 1] * Fc
-    fc = np.empty_like(f)
-    for q in range(9):
-        cu = u[..., 0] * float(CX[q]) + u[..., 1] * float(CY[q])
-        cF = Fr * float(CX[q]) + Fc * float(CY[q])
-        S = ((1 - 0.5 * omega) * ((by.guo_a + by.guo_b * cu) * cF - by.guo_a * uF) * E9[q])
-        fc[..., q] = f[..., q] + (-omega * (f[..., q] - fe[..., q])) + S
-    ge = orc.equilibrium(u + np.asarray(w), conc)                       # 7
-    gc = orc.collision(g, ge, omega_g)
-    return dict(fc=fc, gc=gc, rho=rho, u=u, C=conc)
-
-
-def stream(orc, bc, fixed, fc, gc, w):
-    """advect both and apply the wall rules (item 2: the scalar's rule sees calc_u of the streamed f)"""
-    f, g = orc.advect(fc), orc.advect(gc)
-    walls.fix_up(orc, bc, fixed, f, fc, g, gc, w)
-    return f, g
-
-
-def buoyant_loop(orc, f, g, omega, omega_g, w, by, n, bc=None, fixed=None):
-    bc = bc if bc is not None else pylbm.Bc()
-    fixed = fixed or {}
-    for _ in range(n):
-        c = buoyant_collide(orc, f, g, omega, omega_g, w, by)
-        f, g = stream(orc, bc, fixed, c["fc"], c["gc"], w)
-    rho = orc.calc_rho(f)
-    return dict(f=f, g=g, rho=rho, u=orc.calc_u(f, rho), C=orc.calc_rho(g))
-
-
 def initial_state(orc, R, C, seed):
-    """the passive suite's state with the scalar scaled to C in [0, 1]: forces of ~1e-3 with beta ~ 1e-3"""
-    f, g = walls.initial_state(orc, R, C, seed=seed, w=W)
-    return f, g * 1e3
+    return ade.buoyant_initial_state(orc, R, C, seed, W)
 
 
 def solver(lib, R, C, by, bc=None, sbc=None, form=REF, stream_=None, w=W, omega=OMEGA, omega_g=OMEGA_G):
@@ -115,15 +65,15 @@ def test_periodic_box_is_the_loop_bit_for_bit(lib, oracle, variant):
         sv.set_state(f0, g0)
     done, want = 0, dict(f=f0, g=g0)
     for n in (1, 2, 37):
-        want = buoyant_loop(oracle, want["f"], want["g"], OMEGA, OMEGA_G, W, by, n - done)
+        want = ade.oracle_loop(oracle, want["f"], want["g"], OMEGA, OMEGA_G, W, n - done, by=by)
         for sv in svs:
             sv.step(n - done)
-            walls.assert_state_bits(sv.get_state(), want, f"periodic {variant} after {n} steps")
+            ade.assert_state_bits(sv.get_state(), want, f"periodic {variant} after {n} steps")
         done = n
     for sv in svs:
         assert sv.launches() == 37  # one launch per step, as the passive periodic step
         sv.close()
-    passive = walls.oracle_loop(oracle, f0, g0, OMEGA, OMEGA_G, W, 37, pylbm.Bc(), {})
+    passive = ade.oracle_loop(oracle, f0, g0, OMEGA, OMEGA_G, W, 37, pylbm.Bc(), {})
     assert not bits_equal(passive["f"], want["f"])  # the scalar does push on the fluid
 
 
@@ -135,14 +85,14 @@ def test_walls_with_fixed_edges_are_the_loop_bit_for_bit(lib, oracle, variant):
     R, C = 80, 102
     bc = pylbm.Bc(row_lo=BB, row_hi=BB, col_lo=SP, col_hi=SP)
     prof = np.linspace(0.1, 0.9, R) ** 2
-    sbc, fixed = walls.build_sbc({"row_lo": 0.7, "col_hi": ("profile", prof)}, R, C)
+    sbc, fixed = ade.build_sbc({"row_lo": 0.7, "col_hi": ("profile", prof)}, R, C)
     by = buoyancy(BETA, C_REF, variant)
     f0, g0 = initial_state(oracle, R, C, seed=5)
     sv = solver(lib, R, C, by, bc=bc, sbc=sbc)
     sv.set_state(f0, g0)
     sv.step(23)
-    want = buoyant_loop(oracle, f0, g0, OMEGA, OMEGA_G, W, by, 23, bc, fixed)
-    walls.assert_state_bits(sv.get_state(), want, f"walls + FIXED {variant}")
+    want = ade.oracle_loop(oracle, f0, g0, OMEGA, OMEGA_G, W, 23, bc, fixed, by=by)
+    ade.assert_state_bits(sv.get_state(), want, f"walls + FIXED {variant}")
     assert sv.launches() == 1 + 22 * 2  # interior + edge pass, as the passive step with walls
     sv.close()
 
@@ -175,25 +125,15 @@ def test_fluid_half_is_the_existing_forced_bgk(lib, oracle):
 
 
 # ---- 4. the raw entry points and their moments --------------------------------------------------------------------------
-def to_lattice(a, g):
-    t = walls.alloc(g)
-    walls.owned(t, g)[:] = torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1))).to(dev())
-    return t
-
-
-def from_lattice(t, g):
-    return np.ascontiguousarray(walls.owned(t, g).cpu().numpy().transpose(1, 2, 0))
-
-
 @pytest.mark.parametrize("with_walls", [False, True], ids=["periodic", "walls_fixed"])
 def test_raw_entry_points_write_the_shifted_velocity(lib, oracle, with_walls):
     R, C = 48, 66
-    g = walls.geom(R, C, 0)
+    g = ade.geom(R, C, 0)
     by = buoyancy(BETA, C_REF, GUO)
     prm = pylbm.BgkParams(OMEGA, 0, form=FAST), pylbm.AdeParams(OMEGA_G, W, form=FAST)  # the form is overruled
     if with_walls:
         bc = pylbm.Bc(row_lo=BB, row_hi=BB, col_lo=SP, col_hi=BB)
-        sbc, fixed = walls.build_sbc({"row_lo": 0.7, "col_hi": ("profile", np.linspace(0.0, 1.0, R))}, R, C)
+        sbc, fixed = ade.build_sbc({"row_lo": 0.7, "col_hi": ("profile", np.linspace(0.0, 1.0, R))}, R, C)
     else:
         bc, sbc, fixed = pylbm.Bc(), None, {}
     f0, g0 = initial_state(oracle, R, C, seed=21)
@@ -213,19 +153,19 @@ def test_raw_entry_points_write_the_shifted_velocity(lib, oracle, with_walls):
         assert bits_equal(mom[2][0].cpu().numpy(), want["C"]), what + ": conc"
 
     pre = to_lattice(f0, g), to_lattice(g0, g)
-    post = walls.alloc(g), walls.alloc(g)
+    post = ade.alloc(g), ade.alloc(g)
     m = moments()
     lib.ade_collide_b(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
                       ct.byref(prm[1]), ct.byref(sbc) if sbc else None, ct.byref(by), _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), None)
     check("lbm_ade_collide_b", post, m, c0)
-    nxt = walls.alloc(g), walls.alloc(g)
+    nxt = ade.alloc(g), ade.alloc(g)
     m = moments()
     lib.ade_stream_collide_b(_ptr(nxt[0]), _ptr(nxt[1]), _ptr(post[0]), _ptr(post[1]), ct.byref(g), ct.byref(bc),
                              ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc) if sbc else None, ct.byref(by), 0, R,
                              _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), None)
     check("lbm_ade_stream_collide_b", nxt, m, c1)
     for which in (FRAME, INNER):  # the part launch writes the same moments at its nodes
-        part, m = (walls.alloc(g), walls.alloc(g)), moments()
+        part, m = (ade.alloc(g), ade.alloc(g)), moments()
         lib.ade_stream_collide_part_b(_ptr(part[0]), _ptr(part[1]), _ptr(post[0]), _ptr(post[1]), ct.byref(g), ct.byref(bc),
                                       ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc) if sbc else None, ct.byref(by),
                                       which, 5, _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), None)
@@ -255,7 +195,7 @@ def test_zero_beta_and_null_are_the_passive_solver(lib, oracle, form, with_walls
         runs[key] = (sv.get_state(), sv.launches())
         sv.close()
     for key in ("null", "zero"):
-        walls.assert_state_bits(runs[key][0], runs["plain"][0], key)
+        ade.assert_state_bits(runs[key][0], runs["plain"][0], key)
         assert runs[key][1] == runs["plain"][1]
     assert runs["buoyant"][1] == runs["plain"][1] == 1 + 10 * (2 if with_walls else 1)  # buoyancy adds no launch
     assert not bits_equal(runs["buoyant"][0]["f"], runs["plain"][0]["f"])
@@ -293,7 +233,7 @@ def test_graph_replay_keeps_the_buoyancy_of_its_capture(lib, oracle):
         sv.set_buoyancy(None)
         lib.graph_launch(graph, 1, st)
         lib.stream_sync(st)
-        walls.assert_state_bits(sv.get_state(), want, "three replays of ten steps")  # get_state does not read the buoyancy
+        ade.assert_state_bits(sv.get_state(), want, "three replays of ten steps")  # get_state does not read the buoyancy
         sv.close()
     finally:
         if graph:
@@ -305,48 +245,30 @@ def test_graph_replay_keeps_the_buoyancy_of_its_capture(lib, oracle):
 SLAB_BY = pylbm.AdeBuoyancy((2e-2, -1e-2), 1.0, 0.5, (3.0, 9.0))  # random_lattice: C ~ 1.0 .. 1.05
 
 
-def params(form=FAST):
-    return pylbm.BgkParams(OMEGA, 0, form=form), pylbm.AdeParams(OMEGA_G, W, form=form)
-
-
-def full_step(lib, g, bc, prm, sbc, by, fo, go):
-    fn, gn = walls.alloc(g), walls.alloc(g)
-    lib.ade_stream_collide_b(_ptr(fn), _ptr(gn), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                             ct.byref(prm[1]), ct.byref(sbc) if sbc is not None else None, ct.byref(by), 0, g.R, None, None,
-                             None, None)
-    return fn, gn
-
-
-def part(lib, g, bc, prm, sbc, by, dst, src, which, E):
-    lib.ade_stream_collide_part_b(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                  ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc) if sbc is not None else None,
-                                  ct.byref(by), which, E, None, None, None, None)
-
-
 @pytest.mark.parametrize("with_walls", [False, True], ids=["periodic", "walls_fixed"])
 @pytest.mark.parametrize("R,C,E", [(64, 96, 1), (130, 200, 3)])
 def test_frame_plus_inner_is_the_full_buoyant_step(lib, R, C, E, with_walls):
-    prm = params()
-    gg = walls.geom(R, C, 0)
+    prm = ade.params(FAST, W, OMEGA, OMEGA_G)
+    gg = ade.geom(R, C, 0)
     prof = torch.from_numpy(np.linspace(0.9, 1.1, R)).to(dev())
-    bc = walls.GBC if with_walls else pylbm.Bc()
+    bc = ade.GBC if with_walls else pylbm.Bc()
     sbc = pylbm.AdeScalarBC(row_lo=1.02, col_lo=(0.0, prof), col_hi=0.0) if with_walls else None
-    src = (walls.random_lattice(gg, R + C), walls.random_lattice(gg, R * C))
-    want = full_step(lib, gg, bc, prm, sbc, SLAB_BY, *src)
-    passive = full_step(lib, gg, bc, prm, sbc, pylbm.AdeBuoyancy(), *src)
-    dst = (walls.alloc(gg), walls.alloc(gg))
+    src = (ade.random_lattice(gg, R + C), ade.random_lattice(gg, R * C))
+    want = ade.full_step(lib, gg, bc, prm, *src, sbc=sbc, by=SLAB_BY)
+    passive = ade.full_step(lib, gg, bc, prm, *src, sbc=sbc, by=pylbm.AdeBuoyancy())
+    dst = (ade.alloc(gg), ade.alloc(gg))
     for d in dst:
-        walls.bits(d).fill_(walls.SENTINEL)
-    part(lib, gg, bc, prm, sbc, SLAB_BY, dst, src, FRAME, E)
-    part(lib, gg, bc, prm, sbc, SLAB_BY, dst, src, INNER, E)
+        ade.bits(d).fill_(ade.SENTINEL)
+    ade.part(lib, gg, bc, prm, dst, src, FRAME, E, sbc=sbc, by=SLAB_BY)
+    ade.part(lib, gg, bc, prm, dst, src, INNER, E, sbc=sbc, by=SLAB_BY)
     torch.cuda.synchronize()
     for k in range(2):
-        walls.assert_bits(walls.owned(dst[k], gg), walls.owned(want[k], gg), f"R={R} C={C} E={E} lattice {k}")
+        ade.assert_bits(ade.owned(dst[k], gg), ade.owned(want[k], gg), f"R={R} C={C} E={E} lattice {k}")
         # nothing outside the owned nodes was written
         mask = torch.zeros(9 * gg.plane_stride, dtype=torch.bool, device=dev())
-        walls.owned(mask, gg)[:] = True
-        assert bool(((walls.bits(dst[k]) != walls.SENTINEL) == mask).all())
-    assert bool((walls.bits(want[0]) != walls.bits(passive[0])).any())
+        ade.owned(mask, gg)[:] = True
+        assert bool(((ade.bits(dst[k]) != ade.SENTINEL) == mask).all())
+    assert bool((ade.bits(want[0]) != ade.bits(passive[0])).any())
 
 
 @pytest.mark.parametrize("closed", [False, True], ids=["open", "closed"])
@@ -355,14 +277,14 @@ def test_emulated_chain_equals_one_block(lib, oracle, heights, closed):
     """slabs with one ghost row stepped by lbm_ade_stream_collide_part_b, halos of both lattices by lbm_halo_pack /
     _unpack; open: a chain with walls on its ends and FIXED edges, closed: a periodic ring with wall columns; 9 steps"""
     C, steps = 200, 9
-    prm = params()
+    prm = ade.params(FAST, W, OMEGA, OMEGA_G)
     Rg = sum(heights)
-    gg = walls.geom(Rg, C, 0)
+    gg = ade.geom(Rg, C, 0)
     by = buoyancy(BETA, C_REF, GUO)
     f0, g0 = initial_state(oracle, Rg, C, seed=Rg)
     pre = [to_lattice(a, gg) for a in (f0, g0)]
     prof = torch.from_numpy(np.linspace(0.0, 1.0, Rg)).to(dev())
-    gbc = pylbm.Bc(col_lo=BB, col_hi=SP) if closed else walls.GBC
+    gbc = pylbm.Bc(col_lo=BB, col_hi=SP) if closed else ade.GBC
 
     def descriptor(r0, bc):
         kw = dict(col_lo=(0.0, prof.data_ptr() + 8 * r0), col_hi=0.0)
@@ -371,12 +293,12 @@ def test_emulated_chain_equals_one_block(lib, oracle, heights, closed):
         return pylbm.AdeScalarBC(**kw)
 
     gsbc = descriptor(0, gbc)
-    post = [walls.alloc(gg), walls.alloc(gg)]
+    post = [ade.alloc(gg), ade.alloc(gg)]
     lib.ade_collide_b(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(gg), ct.byref(gbc),
                       ct.byref(prm[0]), ct.byref(prm[1]), None, ct.byref(by), None, None, None, None)
     cur = [t.clone() for t in post]
     for _ in range(steps):
-        cur = list(full_step(lib, gg, gbc, prm, gsbc, by, *cur))
+        cur = list(ade.full_step(lib, gg, gbc, prm, *cur, sbc=gsbc, by=by))
     r0s = np.concatenate([[0], np.cumsum(heights)]).tolist()
     n = len(heights)
     slabs = []
@@ -384,24 +306,24 @@ def test_emulated_chain_equals_one_block(lib, oracle, heights, closed):
         a, b = r0s[k], r0s[k + 1]
         bc = pylbm.Bc(row_lo=HALO if (closed or k > 0) else BB, row_hi=HALO if (closed or k < n - 1) else BB,
                       col_lo=gbc.col_lo, col_hi=gbc.col_hi)
-        cut = [walls.cut_slab(p, gg, a, b, 0) for p in post]
+        cut = [ade.cut_slab(p, gg, a, b, 0) for p in post]
         sg = cut[0][0]
         if closed:  # the ghost rows of the ring's ends wrap
             for j in range(2):
-                rv, src = walls.rows_view(cut[j][1], sg), walls.owned(post[j], gg)
+                rv, src = ade.rows_view(cut[j][1], sg), ade.owned(post[j], gg)
                 if k == 0:
                     rv[:, 0] = src[:, Rg - 1]
                 if k == n - 1:
                     rv[:, sg.R + 1] = src[:, 0]
-        slabs.append(dict(g=sg, bc=bc, sbc=descriptor(a, bc), lat=[[cut[0][1], cut[1][1]], [walls.alloc(sg), walls.alloc(sg)]]))
+        slabs.append(dict(g=sg, bc=bc, sbc=descriptor(a, bc), lat=[[cut[0][1], cut[1][1]], [ade.alloc(sg), ade.alloc(sg)]]))
     msg = lib.raw.lbm_halo_rows(1) * C
     links = [(k, k + 1) for k in range(n - 1)] + ([(n - 1, 0)] if closed else [])
     c = 0
     for _ in range(steps):
         for s in slabs:
             e = min(16, (s["g"].R - 1) // 2)
-            part(lib, s["g"], s["bc"], prm, s["sbc"], by, s["lat"][c ^ 1], s["lat"][c], FRAME, e)
-            part(lib, s["g"], s["bc"], prm, s["sbc"], by, s["lat"][c ^ 1], s["lat"][c], INNER, e)
+            ade.part(lib, s["g"], s["bc"], prm, s["lat"][c ^ 1], s["lat"][c], FRAME, e, sbc=s["sbc"], by=by)
+            ade.part(lib, s["g"], s["bc"], prm, s["lat"][c ^ 1], s["lat"][c], INNER, e, sbc=s["sbc"], by=by)
         for ka, kb in links:  # slab ka's high edge meets slab kb's low edge
             a, b = slabs[ka], slabs[kb]
             for j in range(2):
@@ -414,8 +336,8 @@ def test_emulated_chain_equals_one_block(lib, oracle, heights, closed):
         c ^= 1
     torch.cuda.synchronize()
     for j in range(2):
-        got = torch.cat([walls.owned(s["lat"][c][j], s["g"]) for s in slabs], dim=1)
-        walls.assert_bits(got, walls.owned(cur[j], gg), f"chain {heights} closed={closed} lattice {j}")
+        got = torch.cat([ade.owned(s["lat"][c][j], s["g"]) for s in slabs], dim=1)
+        ade.assert_bits(got, ade.owned(cur[j], gg), f"chain {heights} closed={closed} lattice {j}")
 
 
 DRIVER_BUOYANCY = "0.8,-0.5,0.0004,0.5,3,9"  # the drivers' scalars are ~1e-3
@@ -455,7 +377,7 @@ def test_passive_scalar_box_driver_with_buoyancy_equals_pylbm(lib, tmp_path):
         sv.close()
     want = dict(f=load("f", (R, C, 9)), g=load("g", (R, C, 9)), rho=load("rho", (R, C)), u=load("u", (R, C, 2)),
                 C=load("C", (R, C)))
-    walls.assert_state_bits(out[0], want, "driver vs pylbm")
+    ade.assert_state_bits(out[0], want, "driver vs pylbm")
     assert not bits_equal(out[1]["f"], want["f"])
 
 

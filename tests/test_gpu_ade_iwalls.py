@@ -1,11 +1,11 @@
 """GPU suite, interior walls of the fluid + scalar solver (lbm_ade_iwalls: lbm_ade_stream_collide_w,
 lbm_ade_solver_set_walls; pylbm.AdeInteriorWalls; passive_scalar_box --rectangle).
 
-The yardstick of the bitwise tests is `driver_loop` below: the reference's sediment loop composed from the oracle's
-solver:: primitives (tests/test_gpu_ade.py), with the index assignments of test/rectangle_sedimentation_test.cpp in the
+The yardstick of the bitwise tests is `driver_loop` below, `oracle_loop` of tests/ade_util.py with a body: the reference's
+sediment loop composed from the oracle's solver:: primitives (tests/test_gpu_ade.py), with the index assignments of test/rectangle_sedimentation_test.cpp in the
 driver's order -- the fluid's walls (:179-182), the rectangle on f (:184-196), calc_rho / calc_u (:198-200), the scalar's
 fixed-concentration edges (:203-218), the rectangle on g (:220-232: `-g_coll` where it absorbs), the bottom wall on g
-last (:233-236) -- and, for a buoyant step, the node-local collision of tests/test_gpu_ade_buoyancy.py.  The loop never
+last (:233-236) -- and, for a buoyant step, the node-local buoyant collision.  The loop never
 calls the library under test.  Bitwise means equal bit patterns."""
 import ctypes as ct
 import os
@@ -19,8 +19,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
-import test_gpu_ade_buoyancy as buoy  # noqa: E402  (the buoyant collision of the yardstick)
-import test_gpu_ade_scalar_bc as walls  # noqa: E402  (initial state, the domain's wall rules, lattice helpers)
+import ade_util as ade  # noqa: E402
+from ade_util import SENTINEL, Body  # noqa: E402
 from gpu_util import bits_equal, dev  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
@@ -33,8 +33,6 @@ ROW_POS, ROW_NEG, COL_POS, COL_NEG = (pylbm.ADE_FACE_ROW_POS, pylbm.ADE_FACE_ROW
                                       pylbm.ADE_FACE_COL_NEG)
 W = (3e-3, 3e-3)
 OMEGA, OMEGA_G = 1.2, 1.7
-E9, CX, CY, OPP = walls.E9, walls.CX, walls.CY, walls.OPP
-SENTINEL = walls.SENTINEL
 BETA, C_REF = (2e-3, -1.5e-3), 0.4
 
 
@@ -45,19 +43,7 @@ def lib():
     return lib
 
 
-def slots_of(mask):
-    return [s for s in range(1, 9) if (mask >> (s - 1)) & 1]
-
-
 # ---- the yardstick ------------------------------------------------------------------------------------------------------
-class Body:
-    """index assignments in the order the driver makes them: f segments and g segments, each (rows, cols, slot mask)
-    with numpy indices; the g segments share one rule (absorbing = FIXED at 0, FIXED at conc, or NO_FLUX)"""
-
-    def __init__(self, f_segments, g_segments, g_mode=FIXED, conc=0.0):
-        self.f_segments, self.g_segments, self.g_mode, self.conc = f_segments, g_segments, g_mode, conc
-
-
 def rectangle_body(R, r_top, c1, c2, g_mode=FIXED, conc=0.0):
     """:186-196 and :222-232 verbatim: f's side walls are Slice(R23 + 1, -1), g's first wall Slice(R23 + 1, None)"""
     top = r_top + R
@@ -79,55 +65,8 @@ def rectangle_table(lib, R, C, r_top, c1, c2, g_mode=FIXED, conc=0.0):
     return t.finalize()
 
 
-def driver_fix_up(orc, bc, fixed, body, f, fc, g, gc, w):
-    """one iteration's index assignments after advect, in the driver's order (columns periodic)"""
-    walls.fix_up(orc, bc, {}, f, fc, g, gc, w)                        # the domain's walls, g no-flux (:179-182)
-    for idx, mask in body.f_segments:                                  # the rectangle on f (:184-196)
-        for s in slots_of(mask):
-            f[idx + (s,)] = fc[idx + (OPP[s],)]
-    rho = orc.calc_rho(f)                                              # :198-200
-    v = orc.calc_u(f, rho) + np.asarray(w)
-
-    def abb(idx, s, cw):
-        q = OPP[s]
-        vr, vc = v[idx + (0,)], v[idx + (1,)]
-        cv = vr * CX[q] + vc * CY[q]
-        vv = vr * vr + vc * vc
-        return -gc[idx + (q,)] + 2.0 * ((((1.0 + 3.0 * cv) + 4.5 * (cv * cv)) - 1.5 * vv) * E9[q] * cw)
-
-    R, C = f.shape[:2]
-    for name in ("row_lo", "row_hi"):                                  # the scalar's FIXED edges (:203-218)
-        if name in fixed:
-            idx = walls._edge_index(name, R, C)
-            for s in walls.ROW_SLOTS[name]:
-                g[idx + (s,)] = abb(idx, s, fixed[name])
-    for idx, mask in body.g_segments:                                  # the rectangle on g (:220-232)
-        for s in slots_of(mask):
-            if body.g_mode == NO_FLUX:
-                g[idx + (s,)] = gc[idx + (OPP[s],)]
-            elif body.conc == 0.0:
-                g[idx + (s,)] = -gc[idx + (OPP[s],)]                   # the driver's own expression
-            else:
-                g[idx + (s,)] = abb(idx, s, body.conc)
-    if bc.row_hi == BB and "row_hi" not in fixed:                      # the bottom wall on g, last (:233-236)
-        for s in walls.ROW_SLOTS["row_hi"]:
-            g[R - 1, :, s] = gc[R - 1, :, OPP[s]]
-
-
 def driver_loop(orc, f, g, n, bc, fixed, body, w=W, by=None):
-    for _ in range(n):
-        if by is None:
-            rho = orc.calc_rho(f)
-            u = orc.calc_u(f, rho)
-            fc = orc.collision(f, orc.equilibrium(u, rho), OMEGA)
-            gc = orc.collision(g, orc.equilibrium(u + np.asarray(w), orc.calc_rho(g)), OMEGA_G)
-        else:
-            c = buoy.buoyant_collide(orc, f, g, OMEGA, OMEGA_G, w, by)
-            fc, gc = c["fc"], c["gc"]
-        f, g = orc.advect(fc), orc.advect(gc)
-        driver_fix_up(orc, bc, fixed, body, f, fc, g, gc, w)
-    rho = orc.calc_rho(f)
-    return dict(f=f, g=g, rho=rho, u=orc.calc_u(f, rho), C=orc.calc_rho(g))
+    return ade.oracle_loop(orc, f, g, OMEGA, OMEGA_G, w, n, bc, fixed, body, by)
 
 
 def solver(lib, R, C, form=REF, bc=None, sbc=None, by=None, table=None, stream=None, w=W):
@@ -149,14 +88,14 @@ ROWS_BB = pylbm.Bc(row_lo=BB, row_hi=BB)
 
 
 # ---- 1. the reference loop, bit for bit ---------------------------------------------------------------------------------
-@pytest.mark.parametrize("buoyancy", [None, buoy.REFERENCE, buoy.GUO], ids=["passive", "buoyant_reference", "buoyant_guo"])
+@pytest.mark.parametrize("buoyancy", [None, ade.REFERENCE, ade.GUO], ids=["passive", "buoyant_reference", "buoyant_guo"])
 @pytest.mark.parametrize("fixed_row_lo", [False, True], ids=["no_flux_rows", "fixed_row_lo"])
 @pytest.mark.parametrize("rule", [(FIXED, 0.0), (FIXED, 1e-3), (NO_FLUX, 0.0)], ids=["absorbing", "fixed_1e-3", "no_flux"])
 def test_the_rectangle_is_the_drivers_loop_bit_for_bit(lib, oracle, rule, fixed_row_lo, buoyancy):
     R, C, r_top, c1, c2 = RECT
-    by = buoy.buoyancy(BETA, C_REF, buoyancy) if buoyancy else None
-    sbc, fixed = walls.build_sbc({"row_lo": 7e-4}, R, C) if fixed_row_lo else (None, {})
-    f0, g0 = buoy.initial_state(oracle, R, C, seed=9) if by else walls.initial_state(oracle, R, C, seed=9)
+    by = ade.buoyancy(BETA, C_REF, buoyancy) if buoyancy else None
+    sbc, fixed = ade.build_sbc({"row_lo": 7e-4}, R, C) if fixed_row_lo else (None, {})
+    f0, g0 = ade.buoyant_initial_state(oracle, R, C, seed=9) if by else ade.initial_state(oracle, R, C, seed=9)
     table = rectangle_table(lib, R, C, r_top, c1, c2, *rule)
     body = rectangle_body(R, r_top, c1, c2, *rule)
     sv = solver(lib, R, C, REF, ROWS_BB, sbc, by, table)
@@ -166,7 +105,7 @@ def test_the_rectangle_is_the_drivers_loop_bit_for_bit(lib, oracle, rule, fixed_
         sv.step(n - done)
         want = driver_loop(oracle, want["f"], want["g"], n - done, ROWS_BB, fixed, body, by=by)
         done = n
-        walls.assert_state_bits(sv.get_state(), want, f"rectangle {rule} after {n} iterations")
+        ade.assert_state_bits(sv.get_state(), want, f"rectangle {rule} after {n} iterations")
     assert sv.launches() == 1 + 4 * 3  # collide-only, then interior + edge pass + wall pass
     sv.close()
     # the body is felt: without it the loop holds other bits
@@ -181,8 +120,8 @@ def test_one_node_and_a_wall_row_through_columns_0_and_C_minus_1_of_a_periodic_b
     periodic seam) with a FIXED scalar and one more node beside it; reference order bitwise (a buoyant step runs the
     reference order whatever the form of the context)"""
     R, C = 30, 42
-    by = buoy.buoyancy(BETA, C_REF, buoy.REFERENCE) if form_of_context != REF else None
-    f0, g0 = buoy.initial_state(oracle, R, C, seed=2) if by else walls.initial_state(oracle, R, C, seed=2)
+    by = ade.buoyancy(BETA, C_REF, ade.REFERENCE) if form_of_context != REF else None
+    f0, g0 = ade.buoyant_initial_state(oracle, R, C, seed=2) if by else ade.initial_state(oracle, R, C, seed=2)
     one = pylbm.AdeInteriorWalls(lib, R, C).add(5, 7, 0, 1, 1, ROW_POS, ROW_POS).finalize()
     assert one.count() == 1
     row = pylbm.AdeInteriorWalls(lib, R, C).add(12, 0, 0, 1, C, ROW_NEG, ROW_NEG, FIXED, 2e-3)
@@ -192,7 +131,7 @@ def test_one_node_and_a_wall_row_through_columns_0_and_C_minus_1_of_a_periodic_b
     for table, body in bodies.items():
         got, launches = run(lib, f0, g0, 7, form=form_of_context, by=by, table=table)
         want = driver_loop(oracle, f0, g0, 7, pylbm.Bc(), {}, body, by=by)
-        walls.assert_state_bits(got, want, f"{table.count()} nodes")
+        ade.assert_state_bits(got, want, f"{table.count()} nodes")
         assert launches == 1 + 6 * 2
         table.close()
 
@@ -217,8 +156,8 @@ def test_interior_walls_on_the_rim_are_the_domains_walls(lib, oracle, R, C, axis
     (columns) and the matching lbm_ade_scalar_bc, bit for bit after 20 steps, in both forms; 8 x 260 / 260 x 8: 520 table
     nodes, three workgroups of the pass"""
     conc = 1.5e-3
-    by = buoy.buoyancy(BETA, C_REF, buoy.GUO) if case == "buoyant_fixed" else None
-    f0, g0 = buoy.initial_state(oracle, R, C, seed=R) if by else walls.initial_state(oracle, R, C, seed=R)
+    by = ade.buoyancy(BETA, C_REF, ade.GUO) if case == "buoyant_fixed" else None
+    f0, g0 = ade.buoyant_initial_state(oracle, R, C, seed=R) if by else ade.initial_state(oracle, R, C, seed=R)
     lo, hi = ("row_lo", "row_hi") if axis == "rows" else ("col_lo", "col_hi")
     bc = pylbm.Bc(**{lo: BB, hi: BB})
     sbc = pylbm.AdeScalarBC(**{lo: conc, hi: conc}) if case != "no_flux" else None
@@ -226,7 +165,7 @@ def test_interior_walls_on_the_rim_are_the_domains_walls(lib, oracle, R, C, axis
     assert table.count() == 2 * (C if axis == "rows" else R)
     want, base = run(lib, f0, g0, 20, form=form, bc=bc, sbc=sbc, by=by)
     got, launches = run(lib, f0, g0, 20, form=form, by=by, table=table)
-    walls.assert_state_bits(got, want, f"{R}x{C} {axis} {case}")
+    ade.assert_state_bits(got, want, f"{R}x{C} {axis} {case}")
     assert launches == base == 1 + 19 * 2  # the wall pass where the other solver has its edge pass
     periodic, _ = run(lib, f0, g0, 20, form=form, by=by)
     assert not bits_equal(periodic["g"], got["g"])
@@ -264,19 +203,19 @@ def test_null_and_empty_tables_are_todays_solver(lib, oracle, form):
     R, C = 24, 32
     bc = pylbm.Bc(row_lo=BB, row_hi=BB, col_lo=BB, col_hi=pylbm.EDGE_SPECULAR)
     sbc = pylbm.AdeScalarBC(row_lo=1e-3, col_hi=0.0)
-    f0, g0 = walls.initial_state(oracle, R, C, seed=4)
+    f0, g0 = ade.initial_state(oracle, R, C, seed=4)
     empty = pylbm.AdeInteriorWalls(lib, R, C).finalize()
     box = pylbm.AdeInteriorWalls(lib, R, C).add_box(8, 12, 10, 20, FIXED, 0.0).finalize()
     plain, base = run(lib, f0, g0, 21, form=form, bc=bc, sbc=sbc)
     assert base == 1 + 20 * 2
     got, launches = run(lib, f0, g0, 21, form=form, bc=bc, sbc=sbc, table=empty)
-    walls.assert_state_bits(got, plain, "empty table")
+    ade.assert_state_bits(got, plain, "empty table")
     assert launches == base
     sv = solver(lib, R, C, form, bc, sbc, table=box)
     sv.set_walls(None)  # NULL clears
     sv.set_state(f0, g0)
     sv.step(21)
-    walls.assert_state_bits(sv.get_state(), plain, "cleared table")
+    ade.assert_state_bits(sv.get_state(), plain, "cleared table")
     assert sv.launches() == base
     sv.set_walls(box)   # from the next stream on
     sv.step(4)
@@ -287,12 +226,12 @@ def test_null_and_empty_tables_are_todays_solver(lib, oracle, form):
     assert launches == base + 20  # one more launch per streamed step
     assert not bits_equal(got["f"], plain["f"]) and not bits_equal(got["g"], plain["g"])
     # the raw entry point with NULL and with the empty table is lbm_ade_stream_collide_b
-    g = walls.geom(R, C, 0, C + 6)
-    prm = walls.params(form)
-    src = (walls.random_lattice(g, 1), walls.random_lattice(g, 2))
+    g = ade.geom(R, C, 0, C + 6)
+    prm = ade.params(form)
+    src = (ade.random_lattice(g, 1), ade.random_lattice(g, 2))
     outs = []
     for t in ("b", None, empty):
-        fn, gn = walls.alloc(g), walls.alloc(g)
+        fn, gn = ade.alloc(g), ade.alloc(g)
         if t == "b":
             lib.ade_stream_collide_b(_ptr(fn), _ptr(gn), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
                                      ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), None, 0, R, None, None, None, None)
@@ -303,8 +242,8 @@ def test_null_and_empty_tables_are_todays_solver(lib, oracle, form):
         torch.cuda.synchronize()
         outs.append((fn, gn))
     for k in range(2):
-        walls.assert_bits(outs[1][k], outs[0][k], f"NULL table, lattice {k}")
-        walls.assert_bits(outs[2][k], outs[0][k], f"empty table, lattice {k}")
+        ade.assert_bits(outs[1][k], outs[0][k], f"NULL table, lattice {k}")
+        ade.assert_bits(outs[2][k], outs[0][k], f"empty table, lattice {k}")
     empty.close()
     box.close()
 
@@ -316,19 +255,19 @@ def test_the_walled_step_writes_exactly_the_rows_of_its_range(lib, form):
     those rows only -- the table's row 2 keeps the pattern, its row 5 is written -- never the padding, and what it writes
     is what the call on [0, R) writes there; the moment outputs likewise"""
     R, C, lo, hi = 8, 260, 3, 7
-    g = walls.geom(R, C, 0, C + 12)
+    g = ade.geom(R, C, 0, C + 12)
     bc = pylbm.Bc(col_lo=BB, col_hi=BB)
     sbc = pylbm.AdeScalarBC(col_lo=5e-4)
-    prm = walls.params(form)
+    prm = ade.params(form)
     table = pylbm.AdeInteriorWalls(lib, R, C).add(2, 0, 0, 1, C, ROW_NEG, ROW_NEG, FIXED, 1e-3)
     table.add(5, 0, 0, 1, C, ROW_POS, ROW_POS, FIXED, 1e-3).finalize()
     assert table.count() == 520
-    src = (walls.random_lattice(g, 5), walls.random_lattice(g, 6))
+    src = (ade.random_lattice(g, 5), ade.random_lattice(g, 6))
 
     def call(a, b):
-        out = [walls.alloc(g), walls.alloc(g)] + [torch.zeros(n * R * C, dtype=torch.float64, device=dev()) for n in (1, 2, 1)]
+        out = [ade.alloc(g), ade.alloc(g)] + [torch.zeros(n * R * C, dtype=torch.float64, device=dev()) for n in (1, 2, 1)]
         for t in out:
-            walls.bits(t).fill_(SENTINEL)
+            ade.bits(t).fill_(SENTINEL)
         torch.cuda.synchronize()
         lib.ade_stream_collide_w(_ptr(out[0]), _ptr(out[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
                                  ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), None, table.h, a, b, _ptr(out[2]),
@@ -338,25 +277,25 @@ def test_the_walled_step_writes_exactly_the_rows_of_its_range(lib, form):
 
     full, part = call(0, R), call(lo, hi)
     expect = torch.zeros(9 * g.plane_stride, dtype=torch.bool, device=dev())
-    walls.owned(expect, g)[:, lo:hi] = True
+    ade.owned(expect, g)[:, lo:hi] = True
     for k in range(2):
-        changed = walls.bits(part[k]) != SENTINEL
+        changed = ade.bits(part[k]) != SENTINEL
         assert torch.nonzero(changed != expect).numel() == 0, f"lattice {k}: the write set is not rows [{lo}, {hi})"
-        assert torch.nonzero(expect & (walls.bits(part[k]) != walls.bits(full[k]))).numel() == 0, f"lattice {k}: other bits"
+        assert torch.nonzero(expect & (ade.bits(part[k]) != ade.bits(full[k]))).numel() == 0, f"lattice {k}: other bits"
         everything = torch.zeros_like(expect)
-        walls.owned(everything, g)[:] = True
-        assert torch.nonzero((walls.bits(full[k]) != SENTINEL) != everything).numel() == 0, f"lattice {k}: padding written"
+        ade.owned(everything, g)[:] = True
+        assert torch.nonzero((ade.bits(full[k]) != SENTINEL) != everything).numel() == 0, f"lattice {k}: padding written"
     for k, comps in ((2, 1), (3, 2), (4, 1)):
-        m, mf = walls.bits(part[k]).view(comps, R, C), walls.bits(full[k]).view(comps, R, C)
+        m, mf = ade.bits(part[k]).view(comps, R, C), ade.bits(full[k]).view(comps, R, C)
         assert bool((m[:, lo:hi] == mf[:, lo:hi]).all()) and bool((mf != SENTINEL).all())
         assert bool((m[:, :lo] == SENTINEL).all()) and bool((m[:, hi:] == SENTINEL).all())
     # the wall rows are the table's, not the plain step's
-    plain = [walls.alloc(g), walls.alloc(g)]
+    plain = [ade.alloc(g), ade.alloc(g)]
     lib.ade_stream_collide_b(_ptr(plain[0]), _ptr(plain[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
                              ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), None, 0, R, None, None, None, None)
     torch.cuda.synchronize()
     for k in range(2):
-        differs = (walls.bits(walls.owned(full[k], g)) != walls.bits(walls.owned(plain[k], g))).any(dim=0).any(dim=1)
+        differs = (ade.bits(ade.owned(full[k], g)) != ade.bits(ade.owned(plain[k], g))).any(dim=0).any(dim=1)
         assert differs.tolist() == [r in (2, 5) for r in range(R)], (k, differs.tolist())
     table.close()
 
@@ -367,7 +306,7 @@ def test_reassociated_form_agrees_with_the_reference_order_on_the_rectangle(lib,
     test_reassociated_form_agrees_with_the_reference_order): 500 iterations, 1e-10 relative to each field's largest
     magnitude"""
     R, C, r_top, c1, c2 = RECT
-    f0, g0 = walls.initial_state(oracle, R, C, seed=11)
+    f0, g0 = ade.initial_state(oracle, R, C, seed=11)
     sbc = pylbm.AdeScalarBC(row_lo=7e-4)
     table = rectangle_table(lib, R, C, r_top, c1, c2, FIXED, 1e-3)
     out = {form: run(lib, f0, g0, 500, form=form, bc=ROWS_BB, sbc=sbc, table=table)[0] for form in (REF, FAST)}
@@ -381,7 +320,7 @@ def test_reassociated_form_agrees_with_the_reference_order_on_the_rectangle(lib,
 # ---- 7. capture ---------------------------------------------------------------------------------------------------------
 def test_a_captured_graph_with_a_table_replays_the_eager_run(lib, oracle):
     R, C, r_top, c1, c2 = RECT
-    f0, g0 = walls.initial_state(oracle, R, C, seed=17)
+    f0, g0 = ade.initial_state(oracle, R, C, seed=17)
     table = rectangle_table(lib, R, C, r_top, c1, c2)
     want1, _ = run(lib, f0, g0, 11, form=pylbm.FORM_DEFAULT, bc=ROWS_BB, table=table)
     want2, _ = run(lib, f0, g0, 21, form=pylbm.FORM_DEFAULT, bc=ROWS_BB, table=table)
@@ -398,7 +337,7 @@ def test_a_captured_graph_with_a_table_replays_the_eager_run(lib, oracle):
         for want in (want1, want2):
             lib.graph_launch(graph, 1, st)
             lib.stream_sync(st)
-            walls.assert_state_bits(sv.get_state(), want, "replay")
+            ade.assert_state_bits(sv.get_state(), want, "replay")
         sv.close()
     finally:
         if graph:
@@ -431,7 +370,7 @@ def test_passive_scalar_box_driver_with_the_rectangle_equals_pylbm(lib, tmp_path
     sv.close()
     want = dict(f=load("f", (R, C, 9)), g=load("g", (R, C, 9)), rho=load("rho", (R, C)), u=load("u", (R, C, 2)),
                 C=load("C", (R, C)))
-    walls.assert_state_bits(got, want, "driver vs pylbm")
+    ade.assert_state_bits(got, want, "driver vs pylbm")
     out = dict(ln.split("=", 1) for ln in r.stdout.splitlines() if "=" in ln)
     assert int(out["launches"]) == 1 + (steps - 1) * 3
     assert float(out["mass_C"]) != float(out["mass_C0"])  # the body exchanges scalar with the box
