@@ -625,8 +625,8 @@ int lbm_ade_solver_set_buoyancy(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy
  * outlive every solver and every captured graph that uses it.
  * The step with a non-empty table costs one more launch: one lane per table node, after the interior launch and the
  * edge pass, overwriting its nodes (rows of [row_begin, row_end) only).  The collide-only first iteration applies no
- * wall rule.  Row slabs do not take a table yet: lbm_ade_stream_collide_part* and lbm_ring_ade_* are unchanged (how a
- * table splits per part is the open question of that follow-up). */
+ * wall rule.  Row slabs take a slab-local table (lbm_ade_iwalls_slab, lbm_ade_stream_collide_part_w, lbm_ring_ade_step_w
+ * below). */
 #define LBM_ADE_FACE_ROW_POS 0x91u
 #define LBM_ADE_FACE_ROW_NEG 0x64u
 #define LBM_ADE_FACE_COL_POS 0x32u
@@ -641,12 +641,29 @@ int lbm_ade_iwalls_node(const lbm_ade_iwalls* t, int i, int* r, int* c, unsigned
                         unsigned* g_fixed_slots, double* conc);
 int lbm_ade_iwalls_finalize(lbm_ade_iwalls* t);
 int lbm_ade_iwalls_destroy(lbm_ade_iwalls* t);
+/* The slab view of a table: a new, ordinary, unfinalized table for an R x C lattice (C the parent's) holding the parent's
+ * merged nodes of rows [row0, row0 + R) with r - row0 -- order, slot masks, FIXED slots and conc unchanged.  The parent
+ * may be finalized or not and is not modified; the view owns its nodes, takes further lbm_ade_iwalls_add calls (the
+ * clash rules hold against the inherited nodes) and is finalized and destroyed like any table.  Host only, no device
+ * call.  The wall rule is on-site and its gather reads the slab's ghost rows, so a body that crosses a seam needs no halo
+ * data of its own: each slab fixes up the wall nodes it owns. */
+int lbm_ade_iwalls_slab(lbm_ade_iwalls** out, const lbm_ade_iwalls* table, int row0, int R);
 /* lbm_ade_stream_collide_b with the table (NULL or empty: lbm_ade_stream_collide_b itself); the table must be finalized
  * and built for the R x C of g */
 int lbm_ade_stream_collide_w(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                              const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                              int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
+/* lbm_ade_stream_collide_part_b with a slab-local table: built, or viewed with lbm_ade_iwalls_slab, for the R x C of g,
+ * and finalized (NULL or empty: lbm_ade_stream_collide_part_b itself, the same bits and the same launches).  Behind the
+ * part's dispatch, on the same stream, one more dispatch recomputes the table's nodes of the part's rows -- one lane per
+ * node, found through the row index lbm_ade_iwalls_finalize keeps on the host: no allocation, no host synchronisation,
+ * capturable in a graph; a part without a table node enqueues nothing.  FRAME writes the wall nodes of FRAME rows only,
+ * INNER those of INNER rows; both read the old lattices only.  The moment outputs of wall nodes are overwritten as well. */
+int lbm_ade_stream_collide_part_w(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                  const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                                  int part, int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s);
 /* the context's interior walls from the next stream on (the lazy one of get_state included); NULL clears them.  The
  * table is borrowed, not copied. */
 int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls);
@@ -735,6 +752,14 @@ int lbm_ring_ade_collide_b(lbm_ring* rg, double* fp, double* gp, const double* f
 int lbm_ring_ade_step_b(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_buoyancy* buoy, int edge_rows, lbm_stream_t main);
+/* lbm_ring_ade_step_b with this slab's interior walls (a finalized slab-local table -- lbm_ade_iwalls_slab of the global
+ * one; NULL or empty: lbm_ring_ade_step_b itself).  The wall pass of the FRAME rows runs on the ring's stream behind the
+ * FRAME dispatch and BEFORE the pack -- a neighbour's ghost rows are this slab's post-collision rows, wall nodes fixed up
+ * -- and the pass of the INNER rows on `main` behind INNER; a chain of one slab runs both on `main`.  There is no
+ * lbm_ring_ade_collide_w: collide-only applies no wall rule, lbm_ring_ade_collide_b serves. */
+int lbm_ring_ade_step_w(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                        const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                        const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main);
 /* refresh the single-step ghost rows of two lattices in one message per neighbour (e.g. after restoring a state);
  * asynchronous, ordered after the work enqueued on `after` (lbm_ring_join makes a stream wait for it) */
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after);

@@ -567,6 +567,57 @@ __global__ __launch_bounds__(256) void k_ade_iwalls(double* __restrict__ fn, dou
   }
 }
 
+// The interior-wall pass of a PART of a slab (lbm_ade_stream_collide_part_w): the per-node body of k_ade_iwalls -- the same
+// template flags, the same order of gather, f slots, domain FIXED edges, g slots and both collisions; on a slab the gather
+// reads the ghost rows -- over two index ranges of the table in ONE dispatch: lane i < n0 takes node first0 + i, the other
+// lanes node first1 + (i - n0), n lanes in all.  The table is sorted by (r, c), so the nodes of a band of rows are one
+// range (the host's row index, lbm_ade_iwalls_finalize): FRAME = the prefix [0, first[E]) and the suffix
+// [first[R - E], n_nodes), INNER = the range between them with n0 = n.  No lane is filtered by its row.  Reads the old
+// lattices only and writes wall nodes of the part's rows only.  (The body is repeated, not shared with k_ade_iwalls
+// through an inline function: shared, k_ade_iwalls compiles to the same operations with other registers, and the existing
+// kernels stay instruction for instruction what they were -- profiles/ade_iwalls_slabs.txt.)
+template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
+__global__ __launch_bounds__(256) void k_ade_iwalls_ranges(double* __restrict__ fn, double* __restrict__ gn,
+                                                           const double* __restrict__ fo, const double* __restrict__ go,
+                                                           Geom g, Bc bc, FM fm, SM sm, double* __restrict__ rho_out,
+                                                           double* __restrict__ u_out, double* __restrict__ c_out,
+                                                           AdeWalls sw, AdeBuoyancy by,
+                                                           const AdeIwallNode* __restrict__ nodes, int first0, int n0,
+                                                           int first1, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const AdeIwallNode nd = nodes[i < n0 ? first0 + i : first1 + (i - n0)];
+  const int r = nd.r, c = nd.c;
+  const long o = g.at(r, c);
+  double f[Q], h[Q], rho, ux, uy, conc;
+  gather_walls(f, fo, g, bc, r, c);
+  ade_iwalls_fluid(f, fo, g, o, nd.slots);
+  gather_walls(h, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, r, c);
+  if (BUOYANT) {
+    ade_fluid_moments(f, rho, ux, uy);
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_iwalls_scalar(h, go, g, o, nd.slots, nd.conc, ux, uy, sm.wr, sm.wc);
+    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+  } else {
+    fm.collide(f, rho, ux, uy);
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_iwalls_scalar(h, go, g, o, nd.slots, nd.conc, ux, uy, sm.wr, sm.wc);
+    sm.collide(h, ux, uy, conc);
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    fn[q * g.plane + o] = f[q];
+    gn[q * g.plane + o] = h[q];
+  }
+  if (WITH_MOMENTS) {
+    const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
+    rho_out[oo] = rho;
+    u_out[oo] = ux;
+    u_out[nn + oo] = uy;
+    c_out[oo] = conc;
+  }
+}
+
 // The interior walls of the lazily streamed state (lbm_ade_solver_get_state), one lane per table node.  SCALAR = false:
 // xs = the streamed f, post = the post-collision f: the f slots.  SCALAR = true: xs = the streamed g after
 // k_ade_fixed_state, post = the post-collision g, u = [2][R][C] dense, the reference-order calc_u of the fixed-up f: the

@@ -14,7 +14,9 @@
 #include "launch.hpp"
 
 // Interior walls of the fused step: a host table of wall nodes, merged per node and kept sorted by (r, c) while it is
-// built; lbm_ade_iwalls_finalize uploads it once (the only device call) and it is immutable from then on.
+// built; lbm_ade_iwalls_finalize uploads it once (the only device call) and it is immutable from then on.  first: the
+// index of the first node of each row (R + 1 entries, first[R] = n), kept on the host by finalize -- a part of a slab
+// finds the node ranges of its rows there, with no allocation and no host synchronisation in the step path.
 struct lbm_ade_iwalls {
   struct Entry {
     unsigned f = 0, g = 0, g_fixed = 0;  // slot masks, bit s-1 = slot s; g_fixed: the g slots that are FIXED
@@ -26,6 +28,7 @@ struct lbm_ade_iwalls {
   bool finalized = false;
   int n = 0;                              // nodes uploaded
   lbm::AdeIwallNode* d_nodes = nullptr;   // device copy, sorted by (r, c)
+  std::vector<int> first;                 // finalized: first[r] = index of the first node of rows >= r
 };
 
 namespace lbm {
@@ -184,16 +187,20 @@ int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_
 }
 
 // The interior walls (lbm_ade_iwalls, NULL allowed) against the geometry of the call, on the host: finalized, and built
-// for the same R x C.  *nodes / *n receive the device table; an empty table is NULL's (nullptr, 0).
-static int ade_iwalls_check(const char* fn, const lbm_ade_iwalls* t, const lbm_geom* g, const AdeIwallNode** nodes, int* n) {
+// for the same R x C.  *nodes / *n receive the device table and *first (if wanted) the host's row index; an empty table
+// is NULL's (nullptr, 0, nullptr).
+static int ade_iwalls_check(const char* fn, const lbm_ade_iwalls* t, const lbm_geom* g, const AdeIwallNode** nodes, int* n,
+                            const int** first = nullptr) {
   *nodes = nullptr;
   *n = 0;
+  if (first) *first = nullptr;
   if (!t) return LBM_OK;
   LBM_REQUIRE(t->finalized, "%s: interior walls: the table is not finalized (lbm_ade_iwalls_finalize)", fn);
   LBM_REQUIRE(g && t->R == g->R && t->C == g->C, "%s: interior walls: the table is for a %d x %d lattice, the call for %d x %d",
               fn, t->R, t->C, g ? g->R : 0, g ? g->C : 0);
   *nodes = t->d_nodes;
   *n = t->n;
+  if (first && t->n > 0) *first = t->first.data();
   return LBM_OK;
 }
 
@@ -207,6 +214,7 @@ struct AdeCall {
   bool buoyant;
   const AdeIwallNode* wall_nodes;
   int n_wall_nodes;
+  const int* wall_first;  // host: the table's row index (R + 1 entries), NULL without nodes
   const lbm_bgk_params* fluid;
   const lbm_ade_params* scalar;
 };
@@ -221,7 +229,7 @@ int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm
   int rc = ade_scalar_bc_check(fn, sbc, lbc, &call->sw);
   if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar, slab);
   if (!rc) rc = ade_buoyancy_check(fn, buoy, &call->by, &call->buoyant);
-  if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &call->wall_nodes, &call->n_wall_nodes);
+  if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &call->wall_nodes, &call->n_wall_nodes, &call->wall_first);
   if (rc) return rc;
   call->g = make_geom(*lg);
   call->bc = make_bc(lbc);
@@ -298,6 +306,18 @@ static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
                 k.g, k.bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, k.sw, k.by);
   }, nt & 1, nt & 2, mom, k.sw.fixed);
   LBM_CHECK_LAUNCH();
+  if (k.n_wall_nodes == 0) return LBM_OK;
+  // the table's nodes of the part's rows, behind the dispatch whose nodes they overwrite, on the same stream: the two
+  // bands are two index ranges of the sorted table (one when n0 == nrows); a part without a table node enqueues nothing
+  const int* first = k.wall_first;
+  const int first0 = first[band0], w0 = first[band0 + n0] - first0;
+  const int first1 = first[band1], w = w0 + (n0 < nrows ? first[band1 + nrows - n0] - first1 : 0);
+  if (w == 0) return LBM_OK;
+  with_flags([&](auto M, auto F) {
+    LBM_KLAUNCH((k_ade_iwalls_ranges<FM, SM, M(), F(), B>), dim3((w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc,
+                fm, sm, rho, u, conc, k.sw, k.by, k.wall_nodes, first0, w0, first1, w);
+  }, mom, k.sw.fixed);
+  LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
 
@@ -361,13 +381,13 @@ int ade_part_from(const AdeCall& k, double* fn, double* gn, const double* fo, co
   });
 }
 
-// lbm_ade_stream_collide_part(_ex, _b) under the caller's name
+// lbm_ade_stream_collide_part(_ex, _b, _w) under the caller's name
 static int ade_part(const char* name, double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                     const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                    const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int part, int edge_rows, double* rho,
-                    double* u, double* conc, hipStream_t st) {
+                    const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int part,
+                    int edge_rows, double* rho, double* u, double* conc, hipStream_t st) {
   AdeCall k;
-  int rc = ade_resolve(name, lg, lbc, fluid, scalar, sbc, buoy, nullptr, true, &k);
+  int rc = ade_resolve(name, lg, lbc, fluid, scalar, sbc, buoy, iwalls, true, &k);
   if (!rc) rc = ade_part_args(name, k, fn, gn, fo, go, part, edge_rows, rho, u, conc);
   return rc ? rc : ade_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
 }
@@ -450,15 +470,15 @@ int lbm_ade_stream_collide_w(double* fn, double* gn, const double* fo, const dou
 int lbm_ade_stream_collide_part(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                                 const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int part,
                                 int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, fluid, scalar, nullptr, nullptr, part,
-                  edge_rows, rho, u, conc, as_stream(s));
+  return ade_part("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, fluid, scalar, nullptr, nullptr, nullptr,
+                  part, edge_rows, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_stream_collide_part_ex(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                                    const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                                    const lbm_ade_scalar_bc* sbc, int part, int edge_rows, double* rho, double* u,
                                    double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part_ex", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, nullptr, part,
+  return ade_part("lbm_ade_stream_collide_part_ex", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, nullptr, nullptr, part,
                   edge_rows, rho, u, conc, as_stream(s));
 }
 
@@ -466,8 +486,16 @@ int lbm_ade_stream_collide_part_b(double* fn, double* gn, const double* fo, cons
                                   const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                                   const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int part, int edge_rows,
                                   double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part_b", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, buoy, part, edge_rows,
-                  rho, u, conc, as_stream(s));
+  return ade_part("lbm_ade_stream_collide_part_b", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, buoy, nullptr, part,
+                  edge_rows, rho, u, conc, as_stream(s));
+}
+
+int lbm_ade_stream_collide_part_w(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
+                                  const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                                  int part, int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
+  return ade_part("lbm_ade_stream_collide_part_w", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, buoy, iwalls, part,
+                  edge_rows, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
@@ -765,6 +793,24 @@ int lbm_ade_iwalls_add(lbm_ade_iwalls* t, int r0, int c0, int dr, int dc, int n,
   return LBM_OK;
 }
 
+int lbm_ade_iwalls_slab(lbm_ade_iwalls** out, const lbm_ade_iwalls* table, int row0, int R) {
+  const char* fn = "lbm_ade_iwalls_slab";
+  LBM_REQUIRE(out && table, "%s: NULL argument", fn);
+  LBM_REQUIRE(row0 >= 0, "%s: row0=%d must not be negative", fn, row0);
+  LBM_REQUIRE(R >= 1, "%s: R=%d must be at least 1", fn, R);
+  LBM_REQUIRE((long long)row0 + R <= table->R, "%s: rows [%d, %lld) beyond the %d rows of the table", fn, row0,
+              (long long)row0 + R, table->R);
+  lbm_ade_iwalls* t = new (std::nothrow) lbm_ade_iwalls();
+  LBM_REQUIRE(t, "%s: out of host memory", fn);
+  t->R = R;
+  t->C = table->C;
+  // the map is sorted by (r, c): the rows of the view are one range of it, and stay in order with r - row0
+  for (auto it = table->nodes.lower_bound({row0, 0}); it != table->nodes.end() && it->first.first < row0 + R; ++it)
+    t->nodes.emplace_hint(t->nodes.end(), std::make_pair(it->first.first - row0, it->first.second), it->second);
+  *out = t;
+  return LBM_OK;
+}
+
 int lbm_ade_iwalls_count(const lbm_ade_iwalls* t) { return t ? (int)t->nodes.size() : 0; }
 
 int lbm_ade_iwalls_node(const lbm_ade_iwalls* t, int i, int* r, int* c, unsigned* f_slots, unsigned* g_slots,
@@ -787,7 +833,10 @@ int lbm_ade_iwalls_finalize(lbm_ade_iwalls* t) {
   LBM_REQUIRE(!t->finalized, "lbm_ade_iwalls_finalize: the table is finalized already");
   if (!t->nodes.empty()) {  // an empty table makes no device call: it is NULL's
     std::vector<AdeIwallNode> host;
+    std::vector<int> first((size_t)t->R + 1, 0);  // node counts per row, then their running sum
     host.reserve(t->nodes.size());
+    for (const auto& kv : t->nodes) ++first[(size_t)kv.first.first + 1];
+    for (int r = 0; r < t->R; ++r) first[(size_t)r + 1] += first[r];
     for (const auto& kv : t->nodes)
       host.push_back(AdeIwallNode{kv.first.first, kv.first.second, kv.second.f | (kv.second.g << 8) | (kv.second.g_fixed << 16),
                                   0, kv.second.conc});
@@ -800,6 +849,7 @@ int lbm_ade_iwalls_finalize(lbm_ade_iwalls* t) {
       return LBM_ERR_HIP;
     }
     t->n = (int)host.size();
+    t->first = std::move(first);
   }
   t->finalized = true;
   return LBM_OK;

@@ -314,7 +314,7 @@ static int ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm
 // that edge (a chain end) and is dropped at a seam, as the fluid's row wall is.
 static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, const lbm_bgk_params* fluid,
                             const lbm_ade_params* scalar, const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy,
-                            AdeCall* call) {
+                            const lbm_ade_iwalls* iwalls, AdeCall* call) {
   LBM_REQUIRE(rg->g.ghost == 1, "%s: ghost=%d: the fluid + scalar step over slabs exchanges one ghost row per side (ring "
               "slabs need ghost=1)", fn, rg->g.ghost);
   const lbm_bc b = ring_slab_bc(rg, bc);
@@ -325,22 +325,24 @@ static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, cons
     if (b.row_lo == LBM_EDGE_HALO) sb.mode[0] = LBM_ADE_SCALAR_NO_FLUX;
     if (b.row_hi == LBM_EDGE_HALO) sb.mode[1] = LBM_ADE_SCALAR_NO_FLUX;
   }
-  return ade_resolve(fn, &rg->g, &b, fluid, scalar, gsbc ? &sb : nullptr, buoy, nullptr, true, call);
+  return ade_resolve(fn, &rg->g, &b, fluid, scalar, gsbc ? &sb : nullptr, buoy, iwalls, true, call);
 }
 
 // FRAME (both edge bands, one dispatch) + pack + one message per neighbour on the ring's stream, INNER on `main` beside
-// them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches of one resolved call
+// them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches of one resolved call.
+// iwalls (this slab's table, NULL allowed): each part enqueues the wall pass of its rows behind its own dispatch
+// (ade_part_from), so FRAME's runs inside `edges`, before the pack, and INNER's on `main`.
 static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go,
                          const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                         const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, int edge_rows,
-                         lbm_stream_t main_s) {
+                         const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                         int edge_rows, lbm_stream_t main_s) {
   int rc = ade_buoyancy_check(fn, buoy);  // needs no ring
   if (rc) return rc;
   LBM_REQUIRE(rg && fn_ && gn && fo && go && fluid && scalar, "%s: NULL argument", fn);
   AdeCallBuf buf;
   const AdeCall& call = *buf.get();
   if (edge_rows < 1) edge_rows = 1;
-  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, buf.get());
+  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, iwalls, buf.get());
   if (!rc) rc = ade_part_args(fn, call, fn_, gn, fo, go, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr, nullptr);
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
@@ -634,7 +636,7 @@ static int ring_ade_collide(const char* fn, lbm_ring* rg, double* fp, double* gp
   if (rc) return rc;
   LBM_REQUIRE(rg && fp && gp && f && g_in && fluid && scalar, "%s: NULL argument", fn);
   AdeCallBuf buf;
-  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, buf.get());
+  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, nullptr, buf.get());
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
   rc = ade_collide_from(fn, *buf.get(), fp, gp, f, g_in, nullptr, nullptr, nullptr, main);
@@ -655,19 +657,25 @@ int lbm_ring_ade_collide_b(lbm_ring* rg, double* fp, double* gp, const double* f
 
 int lbm_ring_ade_step(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                       const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step", rg, fn_, gn, fo, go, bc, fluid, scalar, nullptr, nullptr, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step", rg, fn_, gn, fo, go, bc, fluid, scalar, nullptr, nullptr, nullptr, edge_rows, main_s);
 }
 
 int lbm_ring_ade_step_ex(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                          const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                          int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step_ex", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, nullptr, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step_ex", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, nullptr, nullptr, edge_rows, main_s);
 }
 
 int lbm_ring_ade_step_b(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_buoyancy* buoy, int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step_b", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step_b", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, nullptr, edge_rows, main_s);
+}
+
+int lbm_ring_ade_step_w(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                        const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                        const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main_s) {
+  return ring_ade_step("lbm_ring_ade_step_w", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, iwalls, edge_rows, main_s);
 }
 
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after) {

@@ -65,8 +65,9 @@ int ade_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_b
                 const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call);
 int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc, AdeWalls* sw = nullptr);
 int ade_buoyancy_check(const char* fn, const lbm_ade_buoyancy* buoy, AdeBuoyancy* by = nullptr, bool* buoyant = nullptr);
-// launches from a resolved call: one part (LBM_ADE_PART_*; its lattices and part pass ade_part_args first) and the
-// collide-only pass on the owned rows (the first driver iteration)
+// launches from a resolved call: one part (LBM_ADE_PART_*; its lattices and part pass ade_part_args first; with a table of
+// interior walls the wall pass of the part's rows follows its dispatch on the same stream) and the collide-only pass on
+// the owned rows (the first driver iteration)
 int ade_part_args(const char* fn, const AdeCall& call, const double* f_new, const double* g_new, const double* f_old,
                   const double* g_old, int part, int edge_rows, const double* rho, const double* u, const double* conc);
 int ade_part_from(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old, int part,

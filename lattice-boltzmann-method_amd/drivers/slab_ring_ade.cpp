@@ -1,7 +1,7 @@
 // Fluid + transported scalar (lbm_ade_*, the sediment loop of test/rectangle_sedimentation_test.cpp:88-247 without its
 // driver-specific edges) slab-decomposed along r: one ghost row per side, ONE packed message per neighbour per step
 // carrying the single-step halo of both lattices (2 x 3 rows), FRAME + pack + exchange on the ring's stream beside the
-// INNER rows (lbm_ring_ade_step).  C++ host on lbm_ring_* + lbm_ade_stream_collide_part; one process per GPU.
+// INNER rows (lbm_ring_ade_step_w).  C++ host on lbm_ring_* + lbm_ade_stream_collide_part_w; one process per GPU.
 //
 //   slab_ring_ade --spawn N [...]          fork N ranks on this node (rank i -> GPU i; --one-gpu 1: all on GPU 0,
 //                                          with --transport ipc: N real ranks sharing one device)
@@ -19,6 +19,10 @@
 //          fluid column; the last row stays no-flux)
 //          --buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b] (the scalar pushes on the fluid, lbm_ade_buoyancy: the
 //          _b entry points, reference order whatever --form; --check's one block runs the same buoyant step)
+//          --rectangle 1 (with --walls 1: interior walls, lbm_ade_iwalls -- the sedimentation driver's rectangle scaled to
+//          the GLOBAL box, ceiling Rg/3 above the last row, columns 2C/8 .. 5C/16, absorbing (FIXED at 0).  One global
+//          table per process; each slab or rank takes its view, lbm_ade_iwalls_slab; --check's one block runs
+//          lbm_ade_stream_collide_w with the global table)
 //
 // Printed: one JSON line; ms per step of the slowest slab, and the one-block step of a slab-sized lattice beside it.
 //
@@ -31,7 +35,7 @@
 namespace {
 
 struct Args : RingOpts {
-  int walls = 0, scalar_fixed = 0;
+  int walls = 0, scalar_fixed = 0, rectangle = 0;
   double omega = 1.2, omega_g = 1.7;
   bool fast = true;
   bool buoyant = false;
@@ -106,6 +110,31 @@ lbm_ade_scalar_bc scalar_bc(const double* profile, int row0, const lbm_bc& bc) {
   return s;
 }
 
+// --rectangle: the table of the global box (test/rectangle_sedimentation_test.cpp:184-196, :220-232 scaled as
+// scripts/ade_bench.py --interior-walls scales it), not finalized; NULL without the flag
+lbm_ade_iwalls* rectangle_table(const Args& a, int Rg) {
+  if (!a.rectangle) return nullptr;
+  const int C = a.cols, r_top = Rg - Rg / 3, c1 = C * 2 / 8, c2 = C * 5 / 16, n_side = Rg / 3 - 2;  // rows r_top + 1 .. Rg - 2
+  if (n_side < 1) throw std::runtime_error("--rectangle 1 needs at least 9 global rows");
+  const unsigned neg = LBM_ADE_FACE_COL_NEG, pos = LBM_ADE_FACE_COL_POS, top = LBM_ADE_FACE_ROW_NEG;
+  const int fx = LBM_ADE_SCALAR_FIXED;
+  lbm_ade_iwalls* t = nullptr;
+  check(lbm_ade_iwalls_create(&t, Rg, C), "lbm_ade_iwalls_create");
+  check(lbm_ade_iwalls_add(t, r_top + 1, c1, 1, 0, n_side, neg, neg, fx, 0.0), "lbm_ade_iwalls_add");  // first wall; g runs
+  check(lbm_ade_iwalls_add(t, -1, c1, 1, 0, 1, 0, neg & ~0x40u, fx, 0.0), "lbm_ade_iwalls_add");  // through the last row, slot 7 of its foot left to the bottom wall
+  check(lbm_ade_iwalls_add(t, r_top, c1, 0, 1, c2 - c1 + 1, top, top, fx, 0.0), "lbm_ade_iwalls_add");  // ceiling
+  check(lbm_ade_iwalls_add(t, r_top + 1, c2, 1, 0, n_side, pos, pos, fx, 0.0), "lbm_ade_iwalls_add");   // second wall
+  return t;
+}
+// the finalized view of rows [row0, row0 + R) of the global table; NULL for NULL
+lbm_ade_iwalls* slab_view(const lbm_ade_iwalls* global, int row0, int R) {
+  if (!global) return nullptr;
+  lbm_ade_iwalls* v = nullptr;
+  check(lbm_ade_iwalls_slab(&v, global, row0, R), "lbm_ade_iwalls_slab");
+  check(lbm_ade_iwalls_finalize(v), "lbm_ade_iwalls_finalize");
+  return v;
+}
+
 // pre-collision f, g of global rows [row0, row0 + R) into lattices of geometry g (owned rows; the rest zero)
 void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
   const int R = g.R, C = g.C;
@@ -133,8 +162,9 @@ void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
 
 // One block of Rg x C (ghost 0, dense), collide-only + `steps` fused steps: the yardstick of --check.  Returns f, g of
 // the owned rows as dense [9][Rg][C] on the host.
-void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_params& sc, std::vector<double>& f_out,
-               std::vector<double>& g_out) {
+void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_params& sc, lbm_ade_iwalls* walls,
+               std::vector<double>& f_out, std::vector<double>& g_out) {
+  if (walls) check(lbm_ade_iwalls_finalize(walls), "lbm_ade_iwalls_finalize");  // the global table: this is its one use on the device
   const lbm_geom g{Rg, a.cols, 0, 0, 0};
   const lbm_bc bc = global_bc(a);
   double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
@@ -145,8 +175,8 @@ void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_pa
                           nullptr), "lbm_ade_collide_b");
   int cur = 1;
   for (int t = 0; t < a.warmup + a.steps; ++t, cur ^= 1)
-    check(lbm_ade_stream_collide_b(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr,
-                                   a.buoyancy(), 0, Rg, nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_b");
+    check(lbm_ade_stream_collide_w(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr,
+                                   a.buoyancy(), walls, 0, Rg, nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_w");
   if (prof) lbm_free(prof);
   f_out = owned_to_host(f[cur], g);
   g_out = owned_to_host(h[cur], g);
@@ -190,8 +220,9 @@ struct SlabSizedBlock {
   }
 };
 
-// --emulate N: every slab in turn on ONE GPU.  A slab's step is what lbm_ring_ade_step enqueues -- FRAME on the ring's
-// stream, INNER on the main stream beside it, the pack behind FRAME -- with the messages (both lattices, 2 x 3 rows per
+// --emulate N: every slab in turn on ONE GPU.  A slab's step is what lbm_ring_ade_step_w enqueues -- FRAME on the ring's
+// stream, INNER on the main stream beside it (each followed by the wall pass of its rows where the slab's view of the
+// table has nodes there), the pack behind FRAME -- with the messages (both lattices, 2 x 3 rows per
 // side) as device copies between the steps.  Slab k's edges: the global box's, seams HALO (both row edges of a closed
 // ring).  The initial state is the one block's post-collision state, scattered into the slabs with their ghost rows.
 int run_emulated(const Args& a, int N) {
@@ -205,9 +236,11 @@ int run_emulated(const Args& a, int N) {
   const lbm_geom g = padded_geom(R, C, 1);
   const size_t msg = (size_t)lbm_halo_rows(1) * C;  // per lattice
   double* prof = scalar_profile(a, Rg);
+  lbm_ade_iwalls* table = rectangle_table(a, Rg);
   struct Slab {
     lbm_bc bc;
     lbm_ade_scalar_bc sbc;
+    lbm_ade_iwalls* walls;
     double *f[2], *h[2];
   };
   std::vector<Slab> S(N);
@@ -225,6 +258,7 @@ int run_emulated(const Args& a, int N) {
       if (links.prev(k)) s.bc.row_lo = LBM_EDGE_HALO;
       if (links.next(k)) s.bc.row_hi = LBM_EDGE_HALO;
       s.sbc = scalar_bc(prof, k * R, s.bc);
+      s.walls = slab_view(table, k * R, R);
       for (int b = 0; b < 2; ++b) {
         s.f[b] = alloc_lattice(g);
         s.h[b] = alloc_lattice(g);
@@ -246,9 +280,9 @@ int run_emulated(const Args& a, int N) {
   EdgeStream es;
   SlabSizedBlock block(R, C);
   auto part = [&](Slab& s, int cur, int which, lbm_stream_t st) {
-    check(lbm_ade_stream_collide_part_b(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
-                                        prof ? &s.sbc : nullptr, a.buoyancy(), which, E, nullptr, nullptr, nullptr, st),
-          "lbm_ade_stream_collide_part_b");
+    check(lbm_ade_stream_collide_part_w(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
+                                        prof ? &s.sbc : nullptr, a.buoyancy(), s.walls, which, E, nullptr, nullptr, nullptr,
+                                        st), "lbm_ade_stream_collide_part_w");
   };
   auto pack = [&](int k, double* f, double* h, lbm_stream_t st) {
     for (int side = 0; side < 2; ++side) {
@@ -292,7 +326,7 @@ int run_emulated(const Args& a, int N) {
   int bad = 0;
   if (a.check) {
     std::vector<double> want[2];
-    one_block(a, Rg, fl, sc, want[0], want[1]);
+    one_block(a, Rg, fl, sc, table, want[0], want[1]);
     for (int k = 0; k < N; ++k)
       for (int lat = 0; lat < 2; ++lat)
         bad += mismatching_planes(want[lat], Rg, owned_to_host(lat ? S[k].h[cur] : S[k].f[cur], g), R, k * R, C);
@@ -305,13 +339,22 @@ int run_emulated(const Args& a, int N) {
               closed ? "closed ring" : "chain", N, R, C, Rg, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, E,
               2 * lbm_halo_rows(1), slowest, blk, blk / slowest);
   for (int k = 0; k < N; ++k) std::printf("%s%.4f", k ? ", " : "", links.ms(k) / a.steps);
-  std::printf("]%s%s}\n", a.buoyancy_field().c_str(), check_field(a.check, bad));
+  std::printf("]");
+  if (table) {
+    std::printf(", \"interior_wall_nodes\": %d, \"interior_wall_nodes_per_slab\": [", lbm_ade_iwalls_count(table));
+    for (int k = 0; k < N; ++k) std::printf("%s%d", k ? ", " : "", lbm_ade_iwalls_count(S[k].walls));
+    std::printf("]");
+  }
+  std::printf("%s%s}\n", a.buoyancy_field().c_str(), check_field(a.check, bad));
   std::fflush(stdout);
-  for (auto& s : S)
+  for (auto& s : S) {
     for (int b = 0; b < 2; ++b) {
       lbm_free(s.f[b]);
       lbm_free(s.h[b]);
     }
+    lbm_ade_iwalls_destroy(s.walls);
+  }
+  lbm_ade_iwalls_destroy(table);
   return bad ? 3 : 0;
 }
 
@@ -332,10 +375,12 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
         "lbm_ring_ade_collide_b");
   double* prof = scalar_profile(a, Rg);
   const lbm_ade_scalar_bc sbc = scalar_bc(prof, rank * R, gbc);  // the global descriptor, this slab's profile rows
+  lbm_ade_iwalls* table = rectangle_table(a, Rg);                 // the global table, this slab's view
+  lbm_ade_iwalls* walls = slab_view(table, rank * R, R);
   int cur = 0;
   auto step = [&]() {
-    check(lbm_ring_ade_step_b(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
-                              a.buoyancy(), a.edge_rows, nullptr), "lbm_ring_ade_step_b");
+    check(lbm_ring_ade_step_w(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
+                              a.buoyancy(), walls, a.edge_rows, nullptr), "lbm_ring_ade_step_w");
     cur ^= 1;
   };
   double tmax = 0;
@@ -347,7 +392,7 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
     publish_owned_rows(a, ".g", rank, h[cur], g);
     if (rank == 0) {
       std::vector<double> want[2];
-      one_block(a, Rg, fl, sc, want[0], want[1]);
+      one_block(a, Rg, fl, sc, table, want[0], want[1]);
       for (int r = 0; r < world; ++r)
         for (int lat = 0; lat < 2; ++lat)
           bad += mismatching_planes(want[lat], Rg, read_owned_rows(a, lat ? ".g" : ".f", r, R, C), R, r * R, C);
@@ -361,12 +406,16 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
     std::printf("{\"driver\": \"slab_ring_ade\", \"n_gpus\": %d, \"rows_per_gpu\": %d, \"cols\": %d, \"walls\": %d, "
                 "\"scalar_fixed\": %d, \"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, \"message_rows_per_side\": %d, "
                 "\"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, "
-                "\"mlups\": %.1f%s%s}\n",
+                "\"mlups\": %.1f%s%s%s}\n",
                 world, R, C, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, a.edge_rows, 2 * lbm_halo_rows(1), ms, blk, blk / ms,
-                (double)Rg * C / (ms * 1e3), a.buoyancy_field().c_str(), check_field(a.check, bad));
+                (double)Rg * C / (ms * 1e3),
+                table ? (", \"interior_wall_nodes\": " + std::to_string(lbm_ade_iwalls_count(table))).c_str() : "",
+                a.buoyancy_field().c_str(), check_field(a.check, bad));
     std::fflush(stdout);
   }
   lbm_ring_destroy(ring);
+  lbm_ade_iwalls_destroy(walls);
+  lbm_ade_iwalls_destroy(table);
   if (prof) lbm_free(prof);
   for (int k = 0; k < 2; ++k) {
     lbm_free(f[k]);
@@ -386,6 +435,11 @@ int main(int argc, char** argv) {
   a.scalar_fixed = int_arg(argc, argv, "--scalar-fixed", 0);
   if (a.scalar_fixed && !a.walls) {
     std::fprintf(stderr, "--scalar-fixed 1 needs --walls 1 (fixed-concentration walls sit on walls of the fluid)\n");
+    return 1;
+  }
+  a.rectangle = int_arg(argc, argv, "--rectangle", 0);
+  if (a.rectangle && !a.walls) {
+    std::fprintf(stderr, "--rectangle 1 needs --walls 1 (the rectangle stands on the bounce-back last row of the chain)\n");
     return 1;
   }
   a.omega = std::atof(arg_value(argc, argv, "--omega", "1.2").c_str());

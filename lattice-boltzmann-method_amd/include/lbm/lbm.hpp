@@ -177,9 +177,17 @@ class AdeInteriorWalls {
   }
   int count() const { return lbm_ade_iwalls_count(h_); }
   void finalize() { check(lbm_ade_iwalls_finalize(h_)); }
+  // the slab view (lbm_ade_iwalls_slab): a new, unfinalized table for an R x C lattice with this table's nodes of rows
+  // [row0, row0 + R) at r - row0 -- what a row slab hands to lbm_ade_stream_collide_part_w / lbm_ring_ade_step_w
+  AdeInteriorWalls slab(int row0, int R) const {
+    lbm_ade_iwalls* v = nullptr;
+    check(lbm_ade_iwalls_slab(&v, h_, row0, R));
+    return AdeInteriorWalls(v);
+  }
   const lbm_ade_iwalls* handle() const { return h_; }
 
  private:
+  explicit AdeInteriorWalls(lbm_ade_iwalls* h) : h_(h) {}
   lbm_ade_iwalls* h_ = nullptr;
 };
 

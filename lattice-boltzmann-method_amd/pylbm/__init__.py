@@ -168,6 +168,14 @@ class AdeInteriorWalls:
         self.lib.ade_iwalls_finalize(self.h)
         return self
 
+    def slab(self, row0, R):
+        """the slab view (lbm_ade_iwalls_slab): a new, unfinalized AdeInteriorWalls for an R x C lattice holding this
+        table's nodes of rows [row0, row0 + R) with r - row0; this table may be finalized or not and is not modified"""
+        view = AdeInteriorWalls.__new__(AdeInteriorWalls)
+        view.lib, view.R, view.C, view.h = self.lib, int(R), self.C, ct.c_void_p()
+        self.lib.ade_iwalls_slab(ct.byref(view.h), self.h, int(row0), int(R))
+        return view
+
     def close(self):
         if self.h:
             self.lib.ade_iwalls_destroy(self.h)
