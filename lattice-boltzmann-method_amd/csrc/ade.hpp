@@ -312,7 +312,7 @@ __global__ __launch_bounds__(256) void k_ade_edge(double* __restrict__ fn, doubl
   if (r < row_begin || r >= row_end) return;
   // a corner with a wall row belongs to the row lists
   if (i >= 2 * g.C && ((r == 0 && bc_is_wall(bc.row_lo)) || (r == g.R - 1 && bc_is_wall(bc.row_hi)))) return;
-  // the same corner node on both column lists (C == 1) is listed once
+  // the same node on both column lists (C == 1) is listed once -- unreachable from the C ABI, which refuses an odd C
   if (i >= 2 * g.C + n && g.C == 1 && bc_is_wall(bc.col_lo)) return;
   double f[Q], h[Q], rho, ux, uy, conc;
   gather_walls(f, fo, g, bc, r, c);

@@ -1,6 +1,6 @@
 """Helpers shared by the GPU suites of the fluid + scalar solver (tests/test_gpu_ade_*.py): flat lattices with ghost rows
-and padding, the raw step through the one entry point that takes every descriptor (lbm_ade_stream_collide_b / _part_b),
-and the yardstick of the bitwise tests -- the reference's sediment loop composed from the oracle's solver:: primitives,
+and padding, the raw step through the entry points that take every descriptor (lbm_ade_stream_collide_b / _part_b, with
+interior walls _w / _part_w), the write set of a launch into SENTINEL lattices, and the yardstick of the bitwise tests -- the reference's sediment loop composed from the oracle's solver:: primitives,
 with the wall rules, the interior walls and the buoyant collision restated in numpy in the driver's expression order.
 The yardstick never calls the library under test."""
 import ctypes as ct
@@ -101,17 +101,71 @@ def _ref(x):
     return ct.byref(x) if x is not None else None
 
 
-def full_step(lib, g, bc, prm, fo, go, sbc=None, by=None, stream=None):
+def poisoned(g):
+    """a flat lattice with every double of the allocation -- ghost rows and padding included -- set to SENTINEL"""
+    t = alloc(g)
+    bits(t).fill_(SENTINEL)
+    return t
+
+
+def moment_fields(g):
+    """dense rho [R C], u [2 R C], conc [R C] for the raw entry points, every double SENTINEL"""
+    m = [torch.zeros(n * g.R * g.C, dtype=torch.float64, device=dev()) for n in (1, 2, 1)]
+    for t in m:
+        bits(t).fill_(SENTINEL)
+    return m
+
+
+def _moment_ptrs(moments):
+    return [_ptr(t) for t in moments] if moments is not None else [None, None, None]
+
+
+def step_into(lib, g, bc, prm, dst, src, sbc=None, by=None, rows=None, moments=None, stream=None):
+    """lbm_ade_stream_collide_b over rows [rows[0], rows[1]) (default: all of them) into the lattices given"""
+    r0, r1 = rows if rows is not None else (0, g.R)
+    lib.ade_stream_collide_b(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
+                             ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), r0, r1, *_moment_ptrs(moments),
+                             pylbm._stream(stream))
+
+
+def full_step(lib, g, bc, prm, fo, go, sbc=None, by=None, stream=None, moments=None):
     fn, gn = alloc(g), alloc(g)
-    lib.ade_stream_collide_b(_ptr(fn), _ptr(gn), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                             ct.byref(prm[1]), _ref(sbc), _ref(by), 0, g.R, None, None, None, pylbm._stream(stream))
+    step_into(lib, g, bc, prm, (fn, gn), (fo, go), sbc, by, None, moments, stream)
     return fn, gn
 
 
-def part(lib, g, bc, prm, dst, src, which, E, sbc=None, by=None, stream=None):
+def part(lib, g, bc, prm, dst, src, which, E, sbc=None, by=None, stream=None, moments=None):
     lib.ade_stream_collide_part_b(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), which, E, None, None, None,
-                                  pylbm._stream(stream))
+                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), which, E,
+                                  *_moment_ptrs(moments), pylbm._stream(stream))
+
+
+def _handle(table):
+    return table.h if table is not None else None
+
+
+def full_step_w(lib, g, bc, prm, fo, go, sbc=None, by=None, table=None, moments=None):
+    """lbm_ade_stream_collide_w on one block: the step with a table of interior walls (pylbm.AdeInteriorWalls or None)"""
+    fn, gn = alloc(g), alloc(g)
+    lib.ade_stream_collide_w(_ptr(fn), _ptr(gn), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
+                             ct.byref(prm[1]), _ref(sbc), _ref(by), _handle(table), 0, g.R, *_moment_ptrs(moments), None)
+    return fn, gn
+
+
+def part_w(lib, g, bc, prm, dst, src, which, E, sbc=None, by=None, table=None, moments=None):
+    lib.ade_stream_collide_part_w(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
+                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), _handle(table), which, E,
+                                  *_moment_ptrs(moments), None)
+
+
+def assert_write_set(t, g, rows, what):
+    """of a lattice that was SENTINEL everywhere: exactly the owned nodes of `rows` are written, in all 9 planes -- no
+    ghost row, no row padding, no plane padding"""
+    expect = torch.zeros(9 * g.plane_stride, dtype=torch.bool, device=dev())
+    owned(expect, g)[:, rows] = True
+    wrong = torch.nonzero((bits(t) != SENTINEL) != expect)
+    assert wrong.numel() == 0, f"{what}: {wrong.shape[0]} doubles wrong, first flat index {int(wrong[0, 0])} " \
+                               f"({'missed' if bool(expect[int(wrong[0, 0])]) else 'over-written'})"
 
 
 # ---- the yardstick ------------------------------------------------------------------------------------------------------
@@ -286,6 +340,19 @@ def buoyant_collide(orc, f, g, omega, omega_g, w, by):
         fc[..., q] = f[..., q] + (-omega * (f[..., q] - fe[..., q])) + S
     ge = orc.equilibrium(u + np.asarray(w), conc)                       # 7
     gc = orc.collision(g, ge, omega_g)
+    return dict(fc=fc, gc=gc, rho=rho, u=u, C=conc)
+
+
+def collide(orc, f, g, omega, omega_g, w, by=None):
+    """the collision half of one driver iteration on the pre-collision (f, g): what the raw entry points store -- the
+    post-collision pair fc, gc -- and the moments they write (u: the shifted one where there is a buoyancy)"""
+    if by is not None:
+        return buoyant_collide(orc, f, g, omega, omega_g, w, by)
+    rho = orc.calc_rho(f)
+    u = orc.calc_u(f, rho)
+    conc = orc.calc_rho(g)
+    fc = orc.collision(f, orc.equilibrium(u, rho), omega)
+    gc = orc.collision(g, orc.equilibrium(u + np.asarray(w), conc), omega_g)
     return dict(fc=fc, gc=gc, rho=rho, u=u, C=conc)
 
 
