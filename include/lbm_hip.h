@@ -668,6 +668,90 @@ int lbm_ade_stream_collide_part_w(double* fn, double* gn, const double* fo, cons
  * table is borrowed, not copied. */
 int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls);
 
+/* Open boundaries of the fused step on a single block: the inlet, the outlet, the specular lid and the zero-gradient
+ * copies of test/rectangle_sedimentation_test.cpp (:134-177, :203-218), as a host table built like lbm_ade_iwalls --
+ * create / add / finalize / destroy, segments (r0 + i dr, c0 + i dc), i < n, negative r0 / c0 counting from the end.
+ * Three kinds of segment, applied to the listed nodes AFTER the domain's own gather (bc, lbm_ade_scalar_bc), in the
+ * order added; per node and slot the segment added last wins, for f and g separately, and a slot no segment names keeps
+ * what the domain's gather gives it:
+ *   lbm_ade_open_add_f      an f rule on the slots of the mask (bit s-1 = slot s), q = opp(s), f* the node's own
+ *                           post-collision populations:
+ *     LBM_ADE_OPEN_BOUNCE_BACK        f[s] = f*[q]
+ *     LBM_ADE_OPEN_SPECULAR_ROW       f[s] = f*[s with c_x, the row component, negated]  (the driver's top: 8<-7, 1<-3, 5<-6)
+ *     LBM_ADE_OPEN_SPECULAR_COL       f[s] = f*[s with c_y negated]
+ *     LBM_ADE_OPEN_ABB                f[s] = -f*[q] + ((2 + 9 (u_w.c_q)^2) - 3 u_w.u_w) E_q, u_w = (p0, p1)
+ *     LBM_ADE_OPEN_ABB_EXTRAPOLATED   the same with u_w = p0 u_prev(node) + p1 u_prev(node + (nr, nc)) per component
+ *                                     (the driver's outlet: 1.5, -0.5, (0, -1)); u_prev = calc_u of the streamed state
+ *                                     BEFORE this iteration, which the step carries (below); (nr, nc) is not (0, 0) and
+ *                                     the neighbour lies inside the lattice (no wrap).  p0, p1, nr, nc unused otherwise.
+ *   lbm_ade_open_add_g      a g rule on the slots of the mask: LBM_ADE_SCALAR_NO_FLUX g[s] = g*[q], LBM_ADE_SCALAR_FIXED
+ *                           the anti-bounce-back of lbm_ade_iwalls with C_w = conc; v = u + w with the u of the node's
+ *                           fully fixed-up f (the unshifted u0 of a buoyant step).
+ *   lbm_ade_open_add_g_copy the zero-gradient copy g*[node] = g*[node + (from_dr, from_dc)] before streaming, the source
+ *                           inside the lattice.  g* is formed again every step, so a copy is a redirection: every read of
+ *                           the post-collision g of a node -- the nine pulls that target it, the own-population reads of
+ *                           every wall rule at it -- reads the node its map entry names.  The map starts as the identity
+ *                           and every copy segment sets map[dst] = map[src] for all its nodes at once, in the order added
+ *                           (a second copy sees the first).  f has no copy.
+ * lbm_ade_open_add_channel adds the sedimentation channel of the driver for the table's R x C (R >= 4, C >= 4): f inlet
+ * ABB (0, u_in) on all eight slots of column 0, rows 1 .. R-2; f outlet ABB_EXTRAPOLATED (1.5, -0.5, (0, -1)) on column
+ * C-1, all rows; SPECULAR_ROW on slots 8, 1, 5 of row 0; BOUNCE_BACK on slots 7, 3, 6 of node (R-1, C-1) -- the bottom
+ * wall itself is the domain's (bc.row_hi = BOUNCE_BACK), this segment takes the corner back from the outlet; the copies
+ * row 0 <- row 1 and column C-1 <- column C-2 (rows 1 .. R-2); g FIXED on all eight slots of column 0, rows 1 .. R-2, at
+ * conc 0, then at conc_w on the rows of the last conc_rows rows that the inlet has (R - conc_rows .. R-2).
+ * The resolved table (lbm_ade_open_count / _node, host only, valid after every add) lists, sorted by (r, c), exactly:
+ * every node with a rule; for every node whose map entry is not itself the nine nodes that pull from it under periodic
+ * wrap in both axes, itself included; the inward neighbour of every node with an extrapolated slot.  Per node it holds
+ * the rule of each slot (f_rule[s-1]: LBM_ADE_OPEN_*, 0 = none; g_rule[s-1]: 0 = none, 1 + LBM_ADE_SCALAR_*) and the nine
+ * nodes its g is pulled from (g_src_r / g_src_c[q]: the map entry of the periodic pull source of q; q = 0: of the node).
+ * Everything is checked on the host; lbm_ade_open_finalize uploads the table (the one device call; an empty table makes
+ * none and behaves like NULL: the same bits, the same launches).  Immutable after finalize and BORROWED by steps, solvers
+ * and captured graphs.
+ * The carry: lbm_ade_open_carry_len(table) doubles, two per listed node (u_r, u_c in the table's order).  A streamed step
+ * reads carry_in -- the u of the listed nodes before the iteration -- and writes carry_out, the u of their fixed-up f;
+ * the two must not alias and may be NULL only with a NULL or empty table.  lbm_ade_collide_o (the first iteration: no
+ * rule is applied) writes carry_out from the pre-collision f.  The context owns two carries and swaps them with its
+ * lattices.
+ * The step with a non-empty table costs one more launch, one lane per listed node, after the interior launch and the edge
+ * pass and before the interior-wall pass (collide-only: one more small launch that writes the carry).  A node may not be
+ * in the call's interior-wall table as well, unless the open table gives it no rule and every g slot whose resolved
+ * source differs from the plain pull is one a domain wall replaces at that node (the rectangle's foot on the bottom row).
+ * Whole block only: a row range other than [0, R) is refused; the _part entry points and the ring take no open table. */
+#define LBM_ADE_OPEN_BOUNCE_BACK 1
+#define LBM_ADE_OPEN_SPECULAR_ROW 2
+#define LBM_ADE_OPEN_SPECULAR_COL 3
+#define LBM_ADE_OPEN_ABB 4
+#define LBM_ADE_OPEN_ABB_EXTRAPOLATED 5
+typedef struct lbm_ade_open lbm_ade_open;
+int lbm_ade_open_create(lbm_ade_open** out, int R, int C);
+int lbm_ade_open_add_f(lbm_ade_open* t, int r0, int c0, int dr, int dc, int n, unsigned slots, int rule /* LBM_ADE_OPEN_* */,
+                       double p0, double p1, int nr, int nc);
+int lbm_ade_open_add_g(lbm_ade_open* t, int r0, int c0, int dr, int dc, int n, unsigned slots,
+                       int g_mode /* LBM_ADE_SCALAR_* */, double conc);
+int lbm_ade_open_add_g_copy(lbm_ade_open* t, int r0, int c0, int dr, int dc, int n, int from_dr, int from_dc);
+int lbm_ade_open_add_channel(lbm_ade_open* t, double u_in, double conc_w, int conc_rows);
+int lbm_ade_open_count(const lbm_ade_open* t); /* listed nodes so far; host only; 0 for NULL */
+/* node i of the resolved table; f_rule, g_rule: 8 ints, g_src_r, g_src_c: 9 ints; any output may be NULL; host only */
+int lbm_ade_open_node(const lbm_ade_open* t, int i, int* r, int* c, int* f_rule, int* g_rule, int* g_src_r, int* g_src_c);
+long long lbm_ade_open_carry_len(const lbm_ade_open* t); /* 2 x count; 0 for NULL */
+int lbm_ade_open_finalize(lbm_ade_open* t);
+int lbm_ade_open_destroy(lbm_ade_open* t);
+/* lbm_ade_collide_b / lbm_ade_stream_collide_w with the open table (NULL or empty: those calls themselves) */
+int lbm_ade_collide_o(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                      const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                      const lbm_ade_buoyancy* buoy, const lbm_ade_open* open, double* carry_out, double* rho, double* u,
+                      double* conc, lbm_stream_t s);
+int lbm_ade_stream_collide_o(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                             const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                             const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                             const lbm_ade_open* open, const double* carry_in, double* carry_out, int row_begin,
+                             int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
+/* the context's open table from the next step on (the lazy stream of get_state included, which applies it without
+ * touching the carry); NULL clears it.  Borrowed, not copied.  A non-empty table is taken on a pre-collision state only
+ * (before the first step, or after lbm_ade_solver_set_state, which primes the carry): the u before the iteration of a
+ * post-collision state cannot be formed for nodes that were not carried. */
+int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open);
+
 /* ---- slab ring in C++: one process per GPU, packed halo messages between row slabs ------------------
  * Native counterpart of pylbm/slab.py (same kernels, same halo sets): edge rows + pack + ONE message
  * to and from each neighbour + unpack on the ring's own high-priority stream, interior rows on the

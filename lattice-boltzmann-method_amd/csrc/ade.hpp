@@ -681,4 +681,201 @@ __global__ __launch_bounds__(256) void k_ade_collide(double* __restrict__ fp, do
   }
 }
 
+// Open boundaries (lbm_ade_open, device copy): one entry per listed node, sorted by (r, c), and the table's segments.
+// The host resolves everything (lbm_ade_open_finalize): per slot s the segment that won it (fseg / gseg: byte s-1 of the
+// two words = segment index + 1, 0 = the domain's own gather stays), the nine nodes the node's g is pulled from through
+// the scalar's source map (gsrc[q], dense r C + c; gsrc[0] = the node its OWN post-collision g is read from), and per
+// extrapolating slot the index in this table of the inward neighbour (xn).  The kernels look nothing up.
+struct AdeOpenSeg {
+  int kind, pad;  // LBM_ADE_OPEN_* of an f segment; of a g segment LBM_ADE_SCALAR_*
+  double p0, p1;  // ABB: u_w = (p0, p1); ABB_EXTRAPOLATED: u_w = p0 u_prev(node) + p1 u_prev(neighbour); g FIXED: C_w = p0
+};
+struct AdeOpenNode {
+  int r, c;
+  unsigned fseg[2], gseg[2];
+  int gsrc[Q];
+  int xn[Q - 1];
+  int pad;
+};
+
+__device__ __forceinline__ int ade_open_seg_of(const unsigned (&w)[2], int s) {
+  return (int)((w[(s - 1) >> 2] >> (8 * ((s - 1) & 3))) & 0xFFu);
+}
+// slot s with c_x (the row component) / c_y negated
+__host__ __device__ __forceinline__ constexpr int ade_flip_row(int s) {
+  return s == 1 ? 3 : s == 3 ? 1 : s == 5 ? 6 : s == 6 ? 5 : s == 7 ? 8 : s == 8 ? 7 : s;
+}
+__host__ __device__ __forceinline__ constexpr int ade_flip_col(int s) {
+  return s == 2 ? 4 : s == 4 ? 2 : s == 5 ? 8 : s == 8 ? 5 : s == 6 ? 7 : s == 7 ? 6 : s;
+}
+__device__ __forceinline__ long ade_open_at(const Geom& g, int dense) { return g.at(dense / g.C, dense % g.C); }
+
+// the f slots of a listed node from its own post-collision populations; the anti-bounce-back is the driver's :150, :164
+// expression, f[s] = -f*[q] + ((2 + 9 (u_w.c_q)^2) - 3 u_w.u_w) E_q with q = opp(s); carry = the u of every listed node
+// before the iteration (two doubles per node, this table's order), i = this node's index
+__device__ __forceinline__ void ade_open_fluid(double (&f)[Q], const double (&own)[Q], const AdeOpenNode& nd,
+                                               const AdeOpenSeg* __restrict__ segs, const double* __restrict__ carry,
+                                               int i) {
+#pragma unroll
+  for (int s = 1; s < Q; ++s) {
+    const int j = ade_open_seg_of(nd.fseg, s);
+    if (!j) continue;
+    const AdeOpenSeg sg = segs[j - 1];
+    const int q = opp(s);
+    if (sg.kind == LBM_ADE_OPEN_BOUNCE_BACK) f[s] = own[q];
+    else if (sg.kind == LBM_ADE_OPEN_SPECULAR_ROW) f[s] = own[ade_flip_row(s)];
+    else if (sg.kind == LBM_ADE_OPEN_SPECULAR_COL) f[s] = own[ade_flip_col(s)];
+    else {
+      double wr = sg.p0, wc = sg.p1;
+      if (sg.kind == LBM_ADE_OPEN_ABB_EXTRAPOLATED) {
+        const int m = nd.xn[s - 1];
+        wr = sg.p0 * carry[2 * i] + sg.p1 * carry[2 * m];
+        wc = sg.p0 * carry[2 * i + 1] + sg.p1 * carry[2 * m + 1];
+      }
+      const double uu = wr * wr + wc * wc;
+      const double uc = wr * (double)icx(q) + wc * (double)icy(q);
+      f[s] = -own[q] + ((2.0 + 9.0 * (uc * uc)) - 3.0 * uu) * wq(q);
+    }
+  }
+}
+
+// the g slots: NO_FLUX h[s] = h*[opp s], FIXED ade_fixed_slot with the segment's C_w; own = the post-collision g of the
+// node the map names for this one; (ux, uy) the velocity of the fully fixed-up f
+__device__ __forceinline__ void ade_open_scalar(double (&h)[Q], const double (&own)[Q], const AdeOpenNode& nd,
+                                                const AdeOpenSeg* __restrict__ segs, double ux, double uy, double wr,
+                                                double wc) {
+  const double vr = ux + wr, vc = uy + wc;
+  const double vv = vr * vr + vc * vc;
+#pragma unroll
+  for (int s = 1; s < Q; ++s) {
+    const int j = ade_open_seg_of(nd.gseg, s);
+    if (!j) continue;
+    const AdeOpenSeg sg = segs[j - 1];
+    const double hb = own[opp(s)];
+    h[s] = sg.kind == LBM_ADE_SCALAR_FIXED ? ade_fixed_slot(hb, opp(s), vr, vc, vv, sg.p0) : hb;
+  }
+}
+
+// g of a listed node pulled through the map, with the domain's wall gather (bc: the scalar's gather modes) taken from the
+// mapped own node; own is left holding those own populations
+__device__ __forceinline__ void ade_open_gather_scalar(double (&h)[Q], double (&own)[Q], const double* __restrict__ go,
+                                                       const Geom& g, const Bc& bc, const AdeOpenNode& nd) {
+  const long om = ade_open_at(g, nd.gsrc[0]);
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    h[q] = go[q * g.plane + ade_open_at(g, nd.gsrc[q])];
+    own[q] = go[q * g.plane + om];
+  }
+  bc_fixups_own(h, own, g, bc, nd.r, nd.c);
+}
+
+// Open-boundary pass: the table's nodes recomputed, one lane per node, after the interior launch and the edge pass and
+// BEFORE the interior-wall pass (a node of both tables carries no rule here: the host checks).  Per node: the domain's
+// gather of f and the table's f slots; the moments; g pulled from the nine resolved sources with the domain's gather, the
+// domain's FIXED edges, the table's g slots; both collisions in k_ade_edge's order.  carry_out[2 i], [2 i + 1] = the u of
+// the fixed-up f (the unshifted u0 of a buoyant step): the next step's carry_in.  Whole block only.
+template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
+__global__ __launch_bounds__(256) void k_ade_open(double* __restrict__ fn, double* __restrict__ gn,
+                                                  const double* __restrict__ fo, const double* __restrict__ go, Geom g,
+                                                  Bc bc, FM fm, SM sm, double* __restrict__ rho_out,
+                                                  double* __restrict__ u_out, double* __restrict__ c_out, AdeWalls sw,
+                                                  AdeBuoyancy by, const AdeOpenNode* __restrict__ nodes,
+                                                  const AdeOpenSeg* __restrict__ segs, int n_nodes,
+                                                  const double* __restrict__ carry_in, double* __restrict__ carry_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_nodes) return;
+  const AdeOpenNode nd = nodes[i];
+  const int r = nd.r, c = nd.c;
+  const long o = g.at(r, c);
+  double f[Q], h[Q], own[Q], rho, ux, uy, conc, u0r, u0c;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    f[q] = fo[q * g.plane + g.at(wrap_row(g, r - icx(q)), wrap_col(g, c - icy(q)))];
+    own[q] = fo[q * g.plane + o];
+  }
+  bc_fixups_own(f, own, g, bc, r, c);
+  ade_open_fluid(f, own, nd, segs, carry_in, i);
+  ade_open_gather_scalar(h, own, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, nd);
+  if (BUOYANT) {
+    ade_fluid_moments(f, rho, ux, uy);
+    u0r = ux, u0c = uy;
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
+    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+  } else {
+    fm.collide(f, rho, ux, uy);
+    u0r = ux, u0c = uy;
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
+    sm.collide(h, ux, uy, conc);
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    fn[q * g.plane + o] = f[q];
+    gn[q * g.plane + o] = h[q];
+  }
+  carry_out[2 * i] = u0r;
+  carry_out[2 * i + 1] = u0c;
+  if (WITH_MOMENTS) {
+    const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
+    rho_out[oo] = rho;
+    u_out[oo] = ux;
+    u_out[nn + oo] = uy;
+    c_out[oo] = conc;
+  }
+}
+
+// The carry of a PRE-collision state (lbm_ade_collide_o, lbm_ade_solver_set_state): u = calc_u(f, calc_rho(f)) of every
+// listed node, in the reference order -- what the first streamed step reads as carry_in.
+__global__ __launch_bounds__(256) void k_ade_open_prime(const double* __restrict__ f_in, Geom g,
+                                                        const AdeOpenNode* __restrict__ nodes, int n_nodes,
+                                                        double* __restrict__ carry_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_nodes) return;
+  const long o = g.at(nodes[i].r, nodes[i].c);
+  double f[Q], rho, ux, uy;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) f[q] = f_in[q * g.plane + o];
+  ade_fluid_moments(f, rho, ux, uy);
+  carry_out[2 * i] = ux;
+  carry_out[2 * i + 1] = uy;
+}
+
+// The open boundaries of the lazily streamed state (lbm_ade_solver_get_state), one lane per listed node; xs = the
+// streamed level, post = the post-collision one.  MODE 0: the f slots (carry: the one the next step would read).  MODE 1:
+// g gathered again through the map, with the domain's wall gather (bc: the scalar's gather modes) -- before
+// k_ade_fixed_state.  MODE 2: the g slots, u = [2][R][C] dense, the reference-order calc_u of the fixed-up f.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_ade_open_state(double* __restrict__ xs, const double* __restrict__ post, Geom g,
+                                                        Bc bc, const AdeOpenNode* __restrict__ nodes,
+                                                        const AdeOpenSeg* __restrict__ segs, int n_nodes,
+                                                        const double* __restrict__ carry, const double* __restrict__ u,
+                                                        double wr, double wc) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_nodes) return;
+  const AdeOpenNode nd = nodes[i];
+  if (MODE == 0 && !(nd.fseg[0] | nd.fseg[1])) return;
+  if (MODE == 2 && !(nd.gseg[0] | nd.gseg[1])) return;
+  const long o = g.at(nd.r, nd.c);
+  double x[Q], own[Q];
+  if (MODE == 1) {
+    ade_open_gather_scalar(x, own, post, g, bc, nd);
+  } else {
+    const long om = MODE == 2 ? ade_open_at(g, nd.gsrc[0]) : o;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      x[q] = xs[q * g.plane + o];
+      own[q] = post[q * g.plane + om];
+    }
+    if (MODE == 0) {
+      ade_open_fluid(x, own, nd, segs, carry, i);
+    } else {
+      const long n = (long)g.R * g.C, d = (long)nd.r * g.C + nd.c;
+      ade_open_scalar(x, own, nd, segs, u[d], u[n + d], wr, wc);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) xs[q * g.plane + o] = x[q];
+}
+
 }  // namespace lbm

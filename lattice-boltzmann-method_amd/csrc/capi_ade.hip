@@ -1,6 +1,7 @@
 // C ABI, fluid + transported scalar: the compressible BGK fluid f and the advection-diffusion scalar g of
 // test/rectangle_sedimentation_test.cpp:88-247 in one fused pull step per node (ade.hpp), and the solver
 // context that runs the driver loop on one block.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <iterator>
@@ -29,6 +30,28 @@ struct lbm_ade_iwalls {
   int n = 0;                              // nodes uploaded
   lbm::AdeIwallNode* d_nodes = nullptr;   // device copy, sorted by (r, c)
   std::vector<int> first;                 // finalized: first[r] = index of the first node of rows >= r
+};
+
+// Open boundaries of the fused step: the segments in the order added, and the table resolved from them after every add
+// (resolve below) -- the listed nodes sorted by (r, c), each with the segment that won every slot, its nine g sources
+// and its extrapolation neighbours.  lbm_ade_open_finalize uploads nodes and segments once; immutable from then on.
+struct lbm_ade_open {
+  enum Kind { F_RULE, G_RULE, G_COPY };
+  struct Seg {
+    Kind kind;
+    int r0, c0, dr, dc, n;
+    unsigned slots;
+    int rule;       // F_RULE: LBM_ADE_OPEN_*; G_RULE: LBM_ADE_SCALAR_*
+    double p0, p1;  // AdeOpenSeg's
+    int nr, nc;     // ABB_EXTRAPOLATED: the inward neighbour; G_COPY: the source offset
+  };
+  int R = 0, C = 0;
+  std::vector<Seg> segs;
+  std::vector<lbm::AdeOpenNode> nodes;  // resolved
+  bool finalized = false;
+  int n = 0;  // nodes uploaded
+  lbm::AdeOpenNode* d_nodes = nullptr;
+  lbm::AdeOpenSeg* d_segs = nullptr;
 };
 
 namespace lbm {
@@ -204,6 +227,116 @@ static int ade_iwalls_check(const char* fn, const lbm_ade_iwalls* t, const lbm_g
   return LBM_OK;
 }
 
+// The table resolved from the segments added so far (lbm_ade_open.nodes), on the host: the scalar's source map from the
+// copy segments (each sets map[dst] = map[src] for all its nodes at once, in the order added), the segment that won every
+// slot, and the listed nodes -- exactly the union of (a) the nodes with a rule, (b) the nine nodes that pull from a node
+// whose map entry is not itself, under periodic wrap in both axes, (c) the inward neighbour of a node with an extrapolated
+// slot -- sorted by (r, c), each with its nine g sources and the table index of its extrapolation neighbours.
+static void ade_open_resolve(lbm_ade_open* t) {
+  const int R = t->R, C = t->C;
+  auto dense = [C](int r, int c) { return (long long)r * C + c; };
+  std::map<long long, long long> map;  // entries a copy has set; every other node maps to itself
+  auto look = [&map](long long n) {
+    const auto it = map.find(n);
+    return it == map.end() ? n : it->second;
+  };
+  struct Slots {
+    unsigned char f[8] = {}, g[8] = {};
+  };
+  std::map<long long, Slots> listed;  // dense order = (r, c) order
+  for (size_t j = 0; j < t->segs.size(); ++j) {
+    const lbm_ade_open::Seg& s = t->segs[j];
+    if (s.kind == lbm_ade_open::G_COPY) {
+      std::vector<long long> src((size_t)s.n);
+      for (int k = 0; k < s.n; ++k) src[k] = look(dense(s.r0 + k * s.dr + s.nr, s.c0 + k * s.dc + s.nc));
+      for (int k = 0; k < s.n; ++k) map[dense(s.r0 + k * s.dr, s.c0 + k * s.dc)] = src[k];
+      continue;
+    }
+    for (int k = 0; k < s.n; ++k) {
+      Slots& e = listed[dense(s.r0 + k * s.dr, s.c0 + k * s.dc)];
+      for (int q = 1; q < Q; ++q)
+        if ((s.slots >> (q - 1)) & 1u) (s.kind == lbm_ade_open::F_RULE ? e.f : e.g)[q - 1] = (unsigned char)(j + 1);
+    }
+  }
+  auto extrapolated = [t](const Slots& e, int q) {
+    return e.f[q - 1] && t->segs[e.f[q - 1] - 1].rule == LBM_ADE_OPEN_ABB_EXTRAPOLATED;
+  };
+  std::vector<long long> more;
+  for (const auto& kv : map) {
+    if (kv.second == kv.first) continue;
+    const int r = (int)(kv.first / C), c = (int)(kv.first % C);
+    for (int q = 0; q < Q; ++q) more.push_back(dense((r + icx(q) + R) % R, (c + icy(q) + C) % C));
+  }
+  for (const auto& kv : listed)
+    for (int q = 1; q < Q; ++q)
+      if (extrapolated(kv.second, q)) {
+        const lbm_ade_open::Seg& s = t->segs[kv.second.f[q - 1] - 1];
+        more.push_back(kv.first + dense(s.nr, s.nc));
+      }
+  for (long long n : more) listed[n];
+  std::map<long long, int> index;
+  for (const auto& kv : listed) index.emplace_hint(index.end(), kv.first, (int)index.size());
+  t->nodes.clear();
+  t->nodes.reserve(listed.size());
+  for (const auto& kv : listed) {
+    AdeOpenNode nd{};
+    nd.r = (int)(kv.first / C), nd.c = (int)(kv.first % C);
+    for (int q = 1; q < Q; ++q) {
+      nd.fseg[(q - 1) >> 2] |= (unsigned)kv.second.f[q - 1] << (8 * ((q - 1) & 3));
+      nd.gseg[(q - 1) >> 2] |= (unsigned)kv.second.g[q - 1] << (8 * ((q - 1) & 3));
+      if (extrapolated(kv.second, q)) {
+        const lbm_ade_open::Seg& s = t->segs[kv.second.f[q - 1] - 1];
+        nd.xn[q - 1] = index[kv.first + dense(s.nr, s.nc)];
+      }
+    }
+    for (int q = 0; q < Q; ++q) nd.gsrc[q] = (int)look(dense((nd.r - icx(q) + R) % R, (nd.c - icy(q) + C) % C));
+    t->nodes.push_back(nd);
+  }
+}
+
+// slot q of g at node (r, c) is one the domain's wall gather replaces (bc_fixups_own under the scalar's gather modes)
+static bool ade_wall_replaces(const Bc& gbc, int R, int C, int r, int c, int q) {
+  if (r == 0 && gbc.row_lo == LBM_EDGE_BOUNCE_BACK && icx(q) == 1) return true;
+  if (r == R - 1 && gbc.row_hi == LBM_EDGE_BOUNCE_BACK && icx(q) == -1) return true;
+  if (c == C - 1 && bc_is_wall(gbc.col_hi) && icy(q) == -1) return true;
+  return c == 0 && bc_is_wall(gbc.col_lo) && icy(q) == 1;
+}
+
+// The open table (NULL allowed) against the call, on the host: finalized, built for the same R x C, and sharing no node
+// with the interior walls of the call -- but for a node the open table gives no rule and whose redirected g slots are all
+// slots a domain wall replaces there (gbc: the scalar's gather modes), which the interior-wall pass recomputes to the
+// same populations on its own.  An empty table is NULL's.
+static int ade_open_check(const char* fn, const lbm_ade_open* t, const lbm_geom* g, const Bc& gbc,
+                          const lbm_ade_iwalls* iwalls, const AdeOpenNode** nodes, const AdeOpenSeg** segs, int* n) {
+  LBM_REQUIRE(t->finalized, "%s: open boundaries: the table is not finalized (lbm_ade_open_finalize)", fn);
+  LBM_REQUIRE(g && t->R == g->R && t->C == g->C, "%s: open boundaries: the table is for a %d x %d lattice, the call for %d x %d",
+              fn, t->R, t->C, g ? g->R : 0, g ? g->C : 0);
+  if (t->n == 0) return LBM_OK;
+  if (iwalls) {
+    const int R = t->R, C = t->C;
+    for (const auto& kv : iwalls->nodes) {
+      const int r = kv.first.first, c = kv.first.second;
+      const auto it = std::lower_bound(t->nodes.begin(), t->nodes.end(), kv.first, [](const AdeOpenNode& a, const std::pair<int, int>& b) {
+        return std::make_pair(a.r, a.c) < b;
+      });
+      if (it == t->nodes.end() || it->r != r || it->c != c) continue;
+      LBM_REQUIRE(!(it->fseg[0] | it->fseg[1] | it->gseg[0] | it->gseg[1]),
+                  "%s: open boundaries: node (%d, %d) carries an open-boundary rule and is in the interior-wall table as well",
+                  fn, r, c);
+      for (int q = 0; q < Q; ++q) {
+        const long long plain = (long long)((r - icx(q) + R) % R) * C + (c - icy(q) + C) % C;
+        LBM_REQUIRE(it->gsrc[q] == plain || ade_wall_replaces(gbc, R, C, r, c, q),
+                    "%s: open boundaries: node (%d, %d) is in the interior-wall table and its g slot %d is redirected by a "
+                    "copy with no domain wall replacing it there", fn, r, c, q);
+      }
+    }
+  }
+  *nodes = t->d_nodes;
+  *segs = t->d_segs;
+  *n = t->n;
+  return LBM_OK;
+}
+
 // One call of the fused step after its host checks: the device copies that every launch of the call takes.  fluid and
 // scalar are borrowed for the call (with_ade_models picks the models per launch).
 struct AdeCall {
@@ -217,6 +350,9 @@ struct AdeCall {
   const int* wall_first;  // host: the table's row index (R + 1 entries), NULL without nodes
   const lbm_bgk_params* fluid;
   const lbm_ade_params* scalar;
+  const AdeOpenNode* open_nodes;  // the open-boundary table (lbm_ade_open), NULL without nodes
+  const AdeOpenSeg* open_segs;
+  int n_open_nodes;
 };
 static_assert(sizeof(AdeCall) <= sizeof(AdeCallBuf) && alignof(AdeCall) <= alignof(AdeCallBuf) &&
               std::is_trivially_copyable<AdeCall>::value, "AdeCallBuf (internal.hpp) holds an AdeCall");
@@ -225,7 +361,7 @@ static_assert(sizeof(AdeCall) <= sizeof(AdeCallBuf) && alignof(AdeCall) <= align
 // cannot sit on), geometry and parameters, buoyancy, interior walls.  An entry checks its lattices and range or part after.
 int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
                 const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
-                const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call) {
+                const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call, const lbm_ade_open* open) {
   int rc = ade_scalar_bc_check(fn, sbc, lbc, &call->sw);
   if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar, slab);
   if (!rc) rc = ade_buoyancy_check(fn, buoy, &call->by, &call->buoyant);
@@ -235,7 +371,13 @@ int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm
   call->bc = make_bc(lbc);
   call->fluid = fluid;
   call->scalar = scalar;
-  return LBM_OK;
+  call->open_nodes = nullptr;
+  call->open_segs = nullptr;
+  call->n_open_nodes = 0;
+  if (!open) return LBM_OK;
+  LBM_REQUIRE(!slab, "%s: open boundaries: a slab takes no open table (single block only)", fn);
+  return ade_open_check(fn, open, lg, ade_scalar_gather_bc(call->bc, call->sw.fixed), call->n_wall_nodes > 0 ? iwalls : nullptr,
+                        &call->open_nodes, &call->open_segs, &call->n_open_nodes);
 }
 
 template <bool B, class FM, class SM>
@@ -248,12 +390,14 @@ static int ade_collide_launch(const AdeCall& k, const FM& fm, const SM& sm, doub
   return LBM_OK;
 }
 
-// interior launch + (walls only) the edge pass + (a non-empty table of interior walls only) the interior-wall pass;
+// interior launch + (walls only) the edge pass + (a non-empty open table only) the open-boundary pass + (a non-empty
+// table of interior walls only) the interior-wall pass;
 // *launches (if given) += the kernels enqueued
 template <bool B, class FM, class SM>
 static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
                            const double* go, int row_begin, int row_end, double* rho, double* u, double* conc,
-                           hipStream_t st, long long* launches) {
+                           hipStream_t st, long long* launches, const double* carry_in = nullptr,
+                           double* carry_out = nullptr) {
   long long uncounted = 0;
   if (!launches) launches = &uncounted;
   const bool mom = rho != nullptr;
@@ -274,6 +418,15 @@ static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
     with_flags([&](auto M, auto F) {
       LBM_KLAUNCH((k_ade_edge<FM, SM, M(), F(), B>), grid_e, dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc, fm, sm, row_begin,
                   row_end, rho, u, conc, k.sw, k.by);
+    }, mom, k.sw.fixed);
+    LBM_CHECK_LAUNCH();
+    ++*launches;
+  }
+  if (k.n_open_nodes > 0) {  // one lane per listed node, before the interior-wall pass (whole block: the entry checks)
+    const dim3 grid_o((k.n_open_nodes + 255) / 256);
+    with_flags([&](auto M, auto F) {
+      LBM_KLAUNCH((k_ade_open<FM, SM, M(), F(), B>), grid_o, dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc, fm, sm, rho, u, conc,
+                  k.sw, k.by, k.open_nodes, k.open_segs, k.n_open_nodes, carry_in, carry_out);
     }, mom, k.sw.fixed);
     LBM_CHECK_LAUNCH();
     ++*launches;
@@ -331,29 +484,54 @@ int ade_collide_from(const char* fn, const AdeCall& k, double* fp, double* gp, c
   });
 }
 
+// the carry pointers of a call against its open table: both given (carry_in: where the call reads one) and distinct
+static int ade_carry_args(const char* fn, const AdeCall& k, bool reads, const double* carry_in, const double* carry_out) {
+  if (k.n_open_nodes == 0) return LBM_OK;
+  LBM_REQUIRE((!reads || carry_in) && carry_out, "%s: open boundaries: NULL carry with a table of %d nodes (%d doubles each)",
+              fn, k.n_open_nodes, 2 * k.n_open_nodes);
+  LBM_REQUIRE(!reads || carry_in != carry_out, "%s: open boundaries: carry_in and carry_out alias", fn);
+  return LBM_OK;
+}
+
+// the collide-only iteration; with a non-empty open table one more small launch writes carry_out from the pre-collision f
 static int ade_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* lg,
                        const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                        const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
-                       double* rho, double* u, double* conc, hipStream_t st) {
+                       double* rho, double* u, double* conc, hipStream_t st, const lbm_ade_open* open = nullptr,
+                       double* carry_out = nullptr, long long* launches = nullptr) {
   AdeCall k;
-  if (int rc = ade_resolve(fn, lg, bc, fluid, scalar, sbc, buoy, iwalls, false, &k)) return rc;
-  return ade_collide_from(fn, k, fp, gp, f, h, rho, u, conc, st);
+  int rc = ade_resolve(fn, lg, bc, fluid, scalar, sbc, buoy, iwalls, false, &k, open);
+  if (!rc) rc = ade_carry_args(fn, k, false, nullptr, carry_out);
+  if (!rc) rc = ade_collide_from(fn, k, fp, gp, f, h, rho, u, conc, st);
+  if (rc) return rc;
+  if (launches) ++*launches;
+  if (k.n_open_nodes == 0) return LBM_OK;
+  LBM_KLAUNCH(k_ade_open_prime, dim3((k.n_open_nodes + 255) / 256), dim3(256), 0, st, f, k.g, k.open_nodes, k.n_open_nodes,
+              carry_out);
+  LBM_CHECK_LAUNCH();
+  if (launches) ++*launches;
+  return LBM_OK;
 }
 
 static int ade_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
                               const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
                               const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
                               const lbm_ade_iwalls* iwalls, int row_begin, int row_end, double* rho, double* u,
-                              double* conc, hipStream_t st, long long* launches = nullptr) {
+                              double* conc, hipStream_t st, long long* launches = nullptr,
+                              const lbm_ade_open* open = nullptr, const double* carry_in = nullptr,
+                              double* carry_out = nullptr) {
   AdeCall k;
-  int rc = ade_resolve(fn, lg, lbc, fluid, scalar, sbc, buoy, iwalls, false, &k);
+  int rc = ade_resolve(fn, lg, lbc, fluid, scalar, sbc, buoy, iwalls, false, &k, open);
   if (!rc) rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true);
+  if (!rc) rc = ade_carry_args(fn, k, true, carry_in, carry_out);
   if (rc) return rc;
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R, "%s: row range [%d, %d) outside [0, %d)", fn,
               row_begin, row_end, lg->R);
+  LBM_REQUIRE(k.n_open_nodes == 0 || (row_begin == 0 && row_end == lg->R),
+              "%s: open boundaries: row range [%d, %d): the whole block [0, %d) only", fn, row_begin, row_end, lg->R);
   if (row_begin == row_end) return LBM_OK;
   return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
-    return ade_step_launch<B()>(k, fm, sm, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
+    return ade_step_launch<B()>(k, fm, sm, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches, carry_in, carry_out);
   });
 }
 
@@ -406,6 +584,8 @@ struct lbm_ade_solver {
   lbm_ade_buoyancy buoy;  // lbm_ade_solver_set_buoyancy
   bool buoyant;           // buoy is set (beta = (0, 0) included: the launches decide)
   const lbm_ade_iwalls* walls;  // lbm_ade_solver_set_walls: borrowed, never copied
+  const lbm_ade_open* open;     // lbm_ade_solver_set_open: borrowed, never copied
+  double* carry[2];             // the open table's carried u, one per time level (carry[k] goes with lat[k]); NULL without
   hipStream_t st;
   double* lat[2];
   double* dense;  // [9][R][C] SoA scratch of get_state
@@ -516,6 +696,8 @@ int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc*
   sv->buoy = lbm_ade_buoyancy{};
   sv->buoyant = false;
   sv->walls = nullptr;
+  sv->open = nullptr;
+  sv->carry[0] = sv->carry[1] = nullptr;
   sv->st = as_stream(s);
   sv->cur = 0;
   sv->post = false;
@@ -549,7 +731,7 @@ int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc*
 int lbm_ade_solver_destroy(lbm_ade_solver* sv) {
   if (!sv) return LBM_OK;
   if (sv->lat[0] || sv->lat[1]) (void)hipStreamSynchronize(sv->st);
-  for (double* p : {sv->lat[0], sv->lat[1], sv->dense, sv->stage, sv->rho, sv->u, sv->conc})
+  for (double* p : {sv->lat[0], sv->lat[1], sv->dense, sv->stage, sv->rho, sv->u, sv->conc, sv->carry[0], sv->carry[1]})
     if (p) (void)hipFree(p);
   delete sv;
   return LBM_OK;
@@ -565,6 +747,11 @@ int lbm_ade_solver_set_state(lbm_ade_solver* sv, const double* f_host, const dou
   LBM_CHECK_HIP(hipMemcpyAsync(sv->dense, g_host, bytes, hipMemcpyHostToDevice, sv->st));
   rc = lbm_aos_to_soa_pitched(sv->h(sv->cur), sv->dense, g.R, g.C, 9, g.plane_stride, g.row_pitch, sv->st);
   if (rc) return rc;
+  if (sv->open && sv->open->n > 0) {  // the carry of the state given
+    LBM_KLAUNCH(k_ade_open_prime, dim3((sv->open->n + 255) / 256), dim3(256), 0, sv->st, sv->f(sv->cur), make_geom(g),
+                sv->open->d_nodes, sv->open->n, sv->carry[sv->cur]);
+    LBM_CHECK_LAUNCH();
+  }
   LBM_CHECK_HIP(hipStreamSynchronize(sv->st));  // the host arrays may be reused by the caller
   sv->post = false;
   return LBM_OK;
@@ -580,12 +767,12 @@ int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
     int rc;
     if (!sv->post) {
       rc = ade_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid,
-                       &sv->scalar, nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st);
-      if (!rc) ++sv->launches;
+                       &sv->scalar, nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st, sv->open, sv->carry[o],
+                       &sv->launches);
     } else {
       rc = ade_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
                               &sv->fluid, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, buoy, sv->walls, 0, sv->g.R,
-                              nullptr, nullptr, nullptr, sv->st, &sv->launches);
+                              nullptr, nullptr, nullptr, sv->st, &sv->launches, sv->open, sv->carry[k], sv->carry[o]);
     }
     if (rc) return rc;
     sv->cur = o;
@@ -622,8 +809,19 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
     int rc = ade_iwalls_check("lbm_ade_solver_get_state", sv->walls, &g, &wall_nodes, &n_wall_nodes);
     if (rc) return rc;
     const dim3 grid_w((n_wall_nodes + 255) / 256);
+    // the open table, in the reference's order and without touching the carry: its f slots with the carry the next step
+    // would read, moments, the domain's FIXED edges, its g slots through the map
+    const int n_open = sv->open ? sv->open->n : 0;
+    const dim3 grid_o((n_open + 255) / 256);
+    const AdeOpenNode* open_nodes = n_open ? sv->open->d_nodes : nullptr;
+    const AdeOpenSeg* open_segs = n_open ? sv->open->d_segs : nullptr;
     rc = lbm_stream(sv->f(k ^ 1), sv->f(k), &g, &sv->bc, sv->st);
     if (rc) return rc;
+    if (n_open > 0) {
+      LBM_KLAUNCH(k_ade_open_state<0>, grid_o, dim3(256), 0, sv->st, sv->f(k ^ 1), sv->f(k), make_geom(g), make_bc(&sv->bc),
+                  open_nodes, open_segs, n_open, sv->carry[k], nullptr, 0.0, 0.0);
+      LBM_CHECK_LAUNCH();
+    }
     if (n_wall_nodes > 0) {  // the f slots, before the moments that the scalar's rules read
       LBM_KLAUNCH(k_ade_iwalls_state<false>, grid_w, dim3(256), 0, sv->st, sv->f(k ^ 1), sv->f(k), make_geom(g), wall_nodes,
                   n_wall_nodes, nullptr, 0.0, 0.0);
@@ -639,8 +837,13 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
     gbc.col_lo = gather.col_lo, gbc.col_hi = gather.col_hi;
     rc = lbm_stream(sv->h(k ^ 1), sv->h(k), &g, &gbc, sv->st);
     if (rc) return rc;
+    if (n_open > 0) {  // g of the listed nodes pulled again, through the map
+      LBM_KLAUNCH(k_ade_open_state<1>, grid_o, dim3(256), 0, sv->st, sv->h(k ^ 1), sv->h(k), make_geom(g), gather, open_nodes,
+                  open_segs, n_open, nullptr, nullptr, 0.0, 0.0);
+      LBM_CHECK_LAUNCH();
+    }
     k ^= 1;
-    if (fixed || n_wall_nodes > 0)
+    if (fixed || n_wall_nodes > 0 || n_open > 0)
       if ((rc = moments_of_f())) return rc;
     if (fixed) {
       const int n_edge = 2 * C + 2 * R;
@@ -651,6 +854,11 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
     if (n_wall_nodes > 0) {  // the g slots last: the table wins every slot it names (post-collision level: k ^ 1)
       LBM_KLAUNCH(k_ade_iwalls_state<true>, grid_w, dim3(256), 0, sv->st, sv->h(k), sv->h(k ^ 1), make_geom(g), wall_nodes,
                   n_wall_nodes, sv->u, sv->scalar.w_r, sv->scalar.w_c);
+      LBM_CHECK_LAUNCH();
+    }
+    if (n_open > 0) {  // (no node carries a g slot of both tables: the step's host check)
+      LBM_KLAUNCH(k_ade_open_state<2>, grid_o, dim3(256), 0, sv->st, sv->h(k), sv->h(k ^ 1), make_geom(g), gather, open_nodes,
+                  open_segs, n_open, nullptr, sv->u, sv->scalar.w_r, sv->scalar.w_c);
       LBM_CHECK_LAUNCH();
     }
   }
@@ -859,6 +1067,223 @@ int lbm_ade_iwalls_destroy(lbm_ade_iwalls* t) {
   if (!t) return LBM_OK;
   if (t->d_nodes) (void)hipFree(t->d_nodes);
   delete t;
+  return LBM_OK;
+}
+
+// ---- open boundaries (lbm_ade_open) -------------------------------------------------------------------------------------
+int lbm_ade_open_create(lbm_ade_open** out, int R, int C) {
+  LBM_REQUIRE(out, "lbm_ade_open_create: NULL argument");
+  LBM_REQUIRE(R >= 1 && C >= 1, "lbm_ade_open_create: R=%d C=%d must be positive", R, C);
+  LBM_REQUIRE((long long)R * C < (1LL << 31), "lbm_ade_open_create: R=%d C=%d: more than 2^31 - 1 nodes", R, C);
+  lbm_ade_open* t = new (std::nothrow) lbm_ade_open();
+  LBM_REQUIRE(t, "lbm_ade_open_create: out of host memory");
+  t->R = R;
+  t->C = C;
+  *out = t;
+  return LBM_OK;
+}
+
+// the checks every kind of segment shares; r0 / c0 come back counted from the start
+static int ade_open_segment(const char* fn, lbm_ade_open* t, int* r0, int* c0, int dr, int dc, int n) {
+  LBM_REQUIRE(t, "%s: NULL table", fn);
+  LBM_REQUIRE(!t->finalized, "%s: the table is finalized (immutable after lbm_ade_open_finalize)", fn);
+  LBM_REQUIRE(t->segs.size() < 255, "%s: the table holds 255 segments already", fn);
+  LBM_REQUIRE(n >= 1, "%s: n=%d must be at least 1", fn, n);
+  LBM_REQUIRE(dr >= -1 && dr <= 1 && dc >= -1 && dc <= 1 && (dr != 0 || dc != 0),
+              "%s: step (dr, dc)=(%d, %d): each of -1, 0, 1 and not both 0", fn, dr, dc);
+  if (*r0 < 0) *r0 += t->R;  // from the end, as the reference's slices count
+  if (*c0 < 0) *c0 += t->C;
+  for (long long k : {0LL, (long long)n - 1}) {  // the segment is linear: its two ends decide
+    const long long r = *r0 + k * dr, c = *c0 + k * dc;
+    LBM_REQUIRE(r >= 0 && r < t->R && c >= 0 && c < t->C, "%s: node (%lld, %lld) outside the %d x %d lattice", fn, r, c,
+                t->R, t->C);
+  }
+  return LBM_OK;
+}
+
+// node + (or, oc) inside the lattice for both ends of the segment (no wrap)
+static int ade_open_offset(const char* fn, const lbm_ade_open* t, int r0, int c0, int dr, int dc, int n, int or_, int oc,
+                           const char* what) {
+  LBM_REQUIRE(or_ != 0 || oc != 0, "%s: %s offset (0, 0): the node itself", fn, what);
+  for (long long k : {0LL, (long long)n - 1}) {
+    const long long r = r0 + k * dr, c = c0 + k * dc;
+    LBM_REQUIRE(r + or_ >= 0 && r + or_ < t->R && c + oc >= 0 && c + oc < t->C,
+                "%s: node (%lld, %lld): %s (%lld, %lld) outside the %d x %d lattice", fn, r, c, what, r + or_, c + oc, t->R,
+                t->C);
+  }
+  return LBM_OK;
+}
+
+int lbm_ade_open_add_f(lbm_ade_open* t, int r0, int c0, int dr, int dc, int n, unsigned slots, int rule, double p0,
+                       double p1, int nr, int nc) {
+  const char* fn = "lbm_ade_open_add_f";
+  if (int rc = ade_open_segment(fn, t, &r0, &c0, dr, dc, n)) return rc;
+  LBM_REQUIRE(slots >= 1 && slots <= 0xFFu, "%s: slot mask slots=0x%x (bit s-1 = slot s, s in 1..8; at least one)", fn, slots);
+  LBM_REQUIRE(rule >= LBM_ADE_OPEN_BOUNCE_BACK && rule <= LBM_ADE_OPEN_ABB_EXTRAPOLATED, "%s: rule=%d (LBM_ADE_OPEN_*)", fn, rule);
+  const bool abb = rule == LBM_ADE_OPEN_ABB || rule == LBM_ADE_OPEN_ABB_EXTRAPOLATED;
+  LBM_REQUIRE(!abb || (std::isfinite(p0) && std::isfinite(p1)), "%s: (p0, p1)=(%g, %g) must be finite", fn, p0, p1);
+  if (rule == LBM_ADE_OPEN_ABB_EXTRAPOLATED) {
+    if (int rc = ade_open_offset(fn, t, r0, c0, dr, dc, n, nr, nc, "neighbour")) return rc;
+  } else {
+    nr = nc = 0;
+  }
+  t->segs.push_back(lbm_ade_open::Seg{lbm_ade_open::F_RULE, r0, c0, dr, dc, n, slots, rule, abb ? p0 : 0.0, abb ? p1 : 0.0, nr, nc});
+  ade_open_resolve(t);
+  return LBM_OK;
+}
+
+int lbm_ade_open_add_g(lbm_ade_open* t, int r0, int c0, int dr, int dc, int n, unsigned slots, int g_mode, double conc) {
+  const char* fn = "lbm_ade_open_add_g";
+  if (int rc = ade_open_segment(fn, t, &r0, &c0, dr, dc, n)) return rc;
+  LBM_REQUIRE(slots >= 1 && slots <= 0xFFu, "%s: slot mask slots=0x%x (bit s-1 = slot s, s in 1..8; at least one)", fn, slots);
+  LBM_REQUIRE(g_mode == LBM_ADE_SCALAR_NO_FLUX || g_mode == LBM_ADE_SCALAR_FIXED,
+              "%s: g_mode=%d (LBM_ADE_SCALAR_NO_FLUX or LBM_ADE_SCALAR_FIXED)", fn, g_mode);
+  LBM_REQUIRE(std::isfinite(conc), "%s: conc=%g must be finite", fn, conc);
+  t->segs.push_back(lbm_ade_open::Seg{lbm_ade_open::G_RULE, r0, c0, dr, dc, n, slots, g_mode, conc, 0.0, 0, 0});
+  ade_open_resolve(t);
+  return LBM_OK;
+}
+
+int lbm_ade_open_add_g_copy(lbm_ade_open* t, int r0, int c0, int dr, int dc, int n, int from_dr, int from_dc) {
+  const char* fn = "lbm_ade_open_add_g_copy";
+  if (int rc = ade_open_segment(fn, t, &r0, &c0, dr, dc, n)) return rc;
+  if (int rc = ade_open_offset(fn, t, r0, c0, dr, dc, n, from_dr, from_dc, "copy source")) return rc;
+  t->segs.push_back(lbm_ade_open::Seg{lbm_ade_open::G_COPY, r0, c0, dr, dc, n, 0u, 0, 0.0, 0.0, from_dr, from_dc});
+  ade_open_resolve(t);
+  return LBM_OK;
+}
+
+int lbm_ade_open_add_channel(lbm_ade_open* t, double u_in, double conc_w, int conc_rows) {
+  const char* fn = "lbm_ade_open_add_channel";
+  LBM_REQUIRE(t, "%s: NULL table", fn);
+  LBM_REQUIRE(!t->finalized, "%s: the table is finalized (immutable after lbm_ade_open_finalize)", fn);
+  const int R = t->R, C = t->C;
+  LBM_REQUIRE(R >= 3 && C >= 2, "%s: R=%d C=%d: the channel needs R >= 3 and C >= 2", fn, R, C);
+  LBM_REQUIRE(std::isfinite(u_in) && std::isfinite(conc_w), "%s: u_in=%g conc_w=%g must be finite", fn, u_in, conc_w);
+  LBM_REQUIRE(conc_rows >= 0, "%s: conc_rows=%d must not be negative", fn, conc_rows);
+  LBM_REQUIRE(t->segs.size() + 9 <= 255, "%s: the table holds too many segments already", fn);
+  const int first = R - conc_rows > 1 ? R - conc_rows : 1;  // the inlet's rows of the last conc_rows rows: first .. R-2
+  // f: inlet (:150-161), outlet over all rows (:163-172), the specular top (:175-177), and the bottom corner of the outlet
+  // column back to the no-slip row (:180-182; the row itself is the domain's)
+  int rc = lbm_ade_open_add_f(t, 1, 0, 1, 0, R - 2, 0xFFu, LBM_ADE_OPEN_ABB, 0.0, u_in, 0, 0);
+  if (!rc) rc = lbm_ade_open_add_f(t, 0, C - 1, 1, 0, R, 0xFFu, LBM_ADE_OPEN_ABB_EXTRAPOLATED, 1.5, -0.5, 0, -1);
+  if (!rc) rc = lbm_ade_open_add_f(t, 0, 0, 0, 1, C, 0x91u, LBM_ADE_OPEN_SPECULAR_ROW, 0.0, 0.0, 0, 0);
+  if (!rc) rc = lbm_ade_open_add_f(t, R - 1, C - 1, 0, 1, 1, 0x64u, LBM_ADE_OPEN_BOUNCE_BACK, 0.0, 0.0, 0, 0);
+  // g: the zero-gradient copies, top then outlet (:138-141); the concentration inlet (:203-218)
+  if (!rc) rc = lbm_ade_open_add_g_copy(t, 0, 0, 0, 1, C, 1, 0);
+  if (!rc && R > 2) rc = lbm_ade_open_add_g_copy(t, 1, C - 1, 1, 0, R - 2, 0, -1);
+  if (!rc) rc = lbm_ade_open_add_g(t, 1, 0, 1, 0, R - 2, 0xFFu, LBM_ADE_SCALAR_FIXED, 0.0);
+  if (!rc && first <= R - 2) rc = lbm_ade_open_add_g(t, first, 0, 1, 0, R - 1 - first, 0xFFu, LBM_ADE_SCALAR_FIXED, conc_w);
+  return rc;
+}
+
+int lbm_ade_open_count(const lbm_ade_open* t) { return t ? (int)t->nodes.size() : 0; }
+
+long long lbm_ade_open_carry_len(const lbm_ade_open* t) { return t ? 2LL * (long long)t->nodes.size() : 0; }
+
+int lbm_ade_open_node(const lbm_ade_open* t, int i, int* r, int* c, int* f_rule, int* g_rule, int* g_src_r, int* g_src_c) {
+  LBM_REQUIRE(t, "lbm_ade_open_node: NULL table");
+  LBM_REQUIRE(i >= 0 && i < (int)t->nodes.size(), "lbm_ade_open_node: node %d outside [0, %d)", i, (int)t->nodes.size());
+  const AdeOpenNode& nd = t->nodes[(size_t)i];
+  if (r) *r = nd.r;
+  if (c) *c = nd.c;
+  for (int s = 1; s < Q; ++s) {
+    const int jf = (int)((nd.fseg[(s - 1) >> 2] >> (8 * ((s - 1) & 3))) & 0xFFu);
+    const int jg = (int)((nd.gseg[(s - 1) >> 2] >> (8 * ((s - 1) & 3))) & 0xFFu);
+    if (f_rule) f_rule[s - 1] = jf ? t->segs[(size_t)jf - 1].rule : 0;
+    if (g_rule) g_rule[s - 1] = jg ? 1 + t->segs[(size_t)jg - 1].rule : 0;
+  }
+  for (int q = 0; q < Q; ++q) {
+    if (g_src_r) g_src_r[q] = nd.gsrc[q] / t->C;
+    if (g_src_c) g_src_c[q] = nd.gsrc[q] % t->C;
+  }
+  return LBM_OK;
+}
+
+int lbm_ade_open_finalize(lbm_ade_open* t) {
+  LBM_REQUIRE(t, "lbm_ade_open_finalize: NULL table");
+  LBM_REQUIRE(!t->finalized, "lbm_ade_open_finalize: the table is finalized already");
+  if (!t->nodes.empty()) {  // an empty table makes no device call: it is NULL's
+    std::vector<AdeOpenSeg> segs;
+    segs.reserve(t->segs.size());
+    for (const lbm_ade_open::Seg& s : t->segs) segs.push_back(AdeOpenSeg{s.rule, 0, s.p0, s.p1});
+    LBM_CHECK_HIP(hipMalloc(&t->d_nodes, t->nodes.size() * sizeof(AdeOpenNode)));
+    hipError_t e = hipMalloc(&t->d_segs, segs.size() * sizeof(AdeOpenSeg));
+    if (e == hipSuccess) e = hipMemcpy(t->d_nodes, t->nodes.data(), t->nodes.size() * sizeof(AdeOpenNode), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_segs, segs.data(), segs.size() * sizeof(AdeOpenSeg), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(t->d_nodes);
+      if (t->d_segs) (void)hipFree(t->d_segs);
+      t->d_nodes = nullptr;
+      t->d_segs = nullptr;
+      set_error("lbm_ade_open_finalize: %s", hipGetErrorString(e));
+      return LBM_ERR_HIP;
+    }
+    t->n = (int)t->nodes.size();
+  }
+  t->finalized = true;
+  return LBM_OK;
+}
+
+int lbm_ade_open_destroy(lbm_ade_open* t) {
+  if (!t) return LBM_OK;
+  if (t->d_nodes) (void)hipFree(t->d_nodes);
+  if (t->d_segs) (void)hipFree(t->d_segs);
+  delete t;
+  return LBM_OK;
+}
+
+int lbm_ade_collide_o(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                      const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                      const lbm_ade_buoyancy* buoy, const lbm_ade_open* open, double* carry_out, double* rho, double* u,
+                      double* conc, lbm_stream_t s) {
+  return ade_collide("lbm_ade_collide_o", fp, gp, f, g_in, g, bc, fluid, scalar, sbc, buoy, nullptr, rho, u, conc,
+                     as_stream(s), open, carry_out);
+}
+
+int lbm_ade_stream_collide_o(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                             const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                             const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                             const lbm_ade_open* open, const double* carry_in, double* carry_out, int row_begin,
+                             int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
+  return ade_stream_collide("lbm_ade_stream_collide_o", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, iwalls, row_begin,
+                            row_end, rho, u, conc, as_stream(s), nullptr, open, carry_in, carry_out);
+}
+
+int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open) {
+  const char* fn = "lbm_ade_solver_set_open";
+  LBM_REQUIRE(sv, "%s: NULL solver", fn);
+  if (open == sv->open) return LBM_OK;
+  if (open) {
+    LBM_REQUIRE(open->finalized, "%s: open boundaries: the table is not finalized (lbm_ade_open_finalize)", fn);
+    LBM_REQUIRE(open->R == sv->g.R && open->C == sv->g.C, "%s: open boundaries: the table is for a %d x %d lattice, the call for %d x %d",
+                fn, open->R, open->C, sv->g.R, sv->g.C);
+    LBM_REQUIRE(open->n == 0 || !sv->post, "%s: the state is post-collision: the carried velocity of a new table cannot be formed "
+                "(set it before the first step or before lbm_ade_solver_set_state)", fn);
+  }
+  LBM_CHECK_HIP(hipStreamSynchronize(sv->st));  // nothing in flight reads the old carries
+  for (double*& p : sv->carry) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
+  sv->open = nullptr;
+  if (open && open->n > 0) {
+    const size_t bytes = 2 * (size_t)open->n * sizeof(double);
+    hipError_t e = hipMalloc(&sv->carry[0], bytes);
+    if (e == hipSuccess) e = hipMalloc(&sv->carry[1], bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(sv->carry[0], 0, bytes, sv->st);
+    if (e == hipSuccess) e = hipMemsetAsync(sv->carry[1], 0, bytes, sv->st);
+    if (e != hipSuccess) {
+      set_error("%s: %s", fn, hipGetErrorString(e));
+      return LBM_ERR_HIP;
+    }
+    if (!sv->post) {  // a state set before the table: its carry
+      LBM_KLAUNCH(k_ade_open_prime, dim3((open->n + 255) / 256), dim3(256), 0, sv->st, sv->f(sv->cur), make_geom(sv->g),
+                  open->d_nodes, open->n, sv->carry[sv->cur]);
+      LBM_CHECK_LAUNCH();
+    }
+  }
+  sv->open = open;
   return LBM_OK;
 }
 

@@ -55,14 +55,14 @@ struct AdeCall;
 struct AdeWalls;
 struct AdeBuoyancy;
 struct AdeCallBuf {
-  alignas(8) unsigned char bytes[256];
+  alignas(8) unsigned char bytes[320];
   AdeCall* get() { return reinterpret_cast<AdeCall*>(bytes); }
 };
 // the host checks, once, under the caller's name fn (slab: ghost rows and HALO row edges allowed; sbc, buoy, iwalls may be
 // NULL), and the two of them that need no geometry on their own (sw, by: the device copy, if wanted)
 int ade_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
                 const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
-                const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call);
+                const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call, const lbm_ade_open* open = nullptr);
 int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc, AdeWalls* sw = nullptr);
 int ade_buoyancy_check(const char* fn, const lbm_ade_buoyancy* buoy, AdeBuoyancy* by = nullptr, bool* buoyant = nullptr);
 // launches from a resolved call: one part (LBM_ADE_PART_*; its lattices and part pass ade_part_args first; with a table of

@@ -3,7 +3,12 @@
 // to BOTH velocity components, :124) in a channel with anti-bounce-back inlet / outlet columns, a
 // specular top, a no-slip bottom and a three-sided rectangular obstacle at hard-coded coordinates
 // (:71-73: the lattice needs more than 151 rows and 250 columns).
-//   usage: rectangle_sedimentation_test params.toml [--steps N] [--dump prefix]
+//   usage: rectangle_sedimentation_test params.toml [--steps N] [--dump prefix] [--fused 1] [--time 1]
+//
+// --fused 1: the first iteration on the operator path below (the driver collides g with the held C = C_w in it, not with
+// calc_rho(g)), then f_adve, g_adve go to lbm::AdeSolver with bc = {row_hi: BOUNCE_BACK}, the rectangle as
+// AdeInteriorWalls and the channel's AdeOpenBoundary, and the remaining steps run fused -- interior launch, edge pass,
+// open-boundary pass, interior-wall pass per step.  --time 1 prints ms per step of the loop of either path.
 //
 // Engine mapping (operator level, like the reference's loop): per step one fused collide launch for
 // f (with rho, u), the unfused equilibrium / collision pair for g (its equilibrium takes u + w_s,
@@ -11,6 +16,7 @@
 // ~50 slice assignments of the boundary conditions: plain copies, sign-flipped copies, and
 // "-f_coll + wall term" with per-row terms that lbm_wall_terms refreshes from the step's u.
 // Dumps (raw f64): <prefix>-rho.f64 [X][Y], -u.f64 [X][Y][2], -C.f64 [X][Y], -f.f64 / -g.f64 [X][Y][9].
+#include <chrono>
 #include <iostream>
 
 #include "../include/lbm/lbm.hpp"
@@ -43,7 +49,7 @@ struct Table {
 
 int main(int argc, char* argv[]) {
   if (argc < 2) {
-    std::cerr << "usage: " << argv[0] << " params.toml [--steps N] [--dump prefix]\n";
+    std::cerr << "usage: " << argv[0] << " params.toml [--steps N] [--dump prefix] [--fused 1] [--time 1]\n";
     return 1;
   }
   lbm::toml::table tbl;
@@ -62,6 +68,8 @@ int main(int argc, char* argv[]) {
     std::cout << sp << "\n";
     const int steps = std::stoi(arg_value(argc, argv, "--steps", std::to_string(sp.total_steps)));
     const std::string dump = arg_value(argc, argv, "--dump", "");
+    const bool fused = std::stoi(arg_value(argc, argv, "--fused", "0")) != 0;
+    const bool timed = std::stoi(arg_value(argc, argv, "--time", "0")) != 0;
     const int X = lp.X, Y = lp.Y;
     const int R23 = -151, C28 = 200, C38 = 250;  // :71-73
     if (X <= 152 || Y <= 251) {
@@ -167,7 +175,10 @@ int main(int argc, char* argv[]) {
     double* gcw[1] = {g_coll.data()};
     const double* gc[1] = {g_coll.data()};
     std::cout << "main loop\n";
-    for (int t = 0; t < steps; ++t) {
+    const int op_steps = fused ? (steps < 1 ? steps : 1) : steps;  // --fused: the hand-over follows the first iteration
+    lbm::check(lbm_stream_sync(nullptr));
+    auto t0 = std::chrono::steady_clock::now();
+    for (int t = 0; t < op_steps; ++t) {
       // :123-131  f: equilibrium + collision from its own moments (= the held u, rho); g: equilibrium(u + w_s, C)
       lbm::check(lbm_bgk_collide(f_coll.data(), f_adve.data(), &geom, nullptr, &prm, rho.data(), u.data(), nullptr));
       lbm::check(lbm_axpb(u_s.data(), u.data(), 1.0, w_s, (long long)(2 * n), nullptr));
@@ -191,6 +202,45 @@ int main(int argc, char* argv[]) {
     if (steps > 0) {
       rho = rho_new;
       u = u_new;
+    }
+    int timed_steps = op_steps;
+    if (fused && steps > 1) {
+      lbm_bc bc = lbm::BoundarySet();
+      bc.row_hi = LBM_EDGE_BOUNCE_BACK;  // the no-slip bottom, f and g (:180-182, :234-236)
+      lbm::AdeSolver sv(X, Y, lp.omega, lp.omega / 1.0, w_s, w_s, bc);
+      // the rectangle (:184-196, :220-232); absorbing at C_w = -0.0: the driver's `-g_coll`, the sign of a zero included
+      lbm::AdeInteriorWalls walls(X, Y);
+      const int n_side = (X - 1) - (X + R23 + 1);
+      walls.add(R23 + 1, C28, 1, 0, n_side, LBM_ADE_FACE_COL_NEG, LBM_ADE_FACE_COL_NEG, LBM_ADE_SCALAR_FIXED, -0.0);
+      walls.add(-1, C28, 1, 0, 1, 0, LBM_ADE_FACE_COL_NEG & ~(1u << 6), LBM_ADE_SCALAR_FIXED, -0.0);  // slot 7: the bottom's
+      walls.add(R23, C28, 0, 1, C38 - C28 + 1, LBM_ADE_FACE_ROW_NEG, LBM_ADE_FACE_ROW_NEG, LBM_ADE_SCALAR_FIXED, -0.0);
+      walls.add(R23 + 1, C38, 1, 0, n_side, LBM_ADE_FACE_COL_POS, LBM_ADE_FACE_COL_POS, LBM_ADE_SCALAR_FIXED, -0.0);
+      walls.finalize();
+      lbm::AdeOpenBoundary open(X, Y);
+      open.channel(lp.u, scalar_C_w, 50).finalize();
+      sv.set_walls(walls);
+      sv.set_open(open);
+      sv.set_state(f_adve.to_host(), g_adve.to_host());
+      sv.sync();
+      t0 = std::chrono::steady_clock::now();
+      sv.step(steps - 1);
+      sv.sync();
+      timed_steps = steps - 1;
+      const auto t1 = std::chrono::steady_clock::now();
+      if (timed)
+        std::cout << "ms_per_step=" << std::chrono::duration<double, std::milli>(t1 - t0).count() / timed_steps
+                  << " (fused, " << timed_steps << " steps, " << sv.launches() << " launches)" << std::endl;
+      const lbm::AdeSolver::State st = sv.state();
+      f_adve.from_host(st.f);
+      g_adve.from_host(st.g);
+      rho.from_host(st.rho);
+      u.from_host(st.u);
+      C.from_host(st.C);
+    } else if (timed && timed_steps > 0) {
+      lbm::check(lbm_stream_sync(nullptr));
+      const auto t1 = std::chrono::steady_clock::now();
+      std::cout << "ms_per_step=" << std::chrono::duration<double, std::milli>(t1 - t0).count() / timed_steps
+                << " (operator level, " << timed_steps << " steps)" << std::endl;
     }
     const auto Chost = C.to_host();
     double mass_c = 0.0;

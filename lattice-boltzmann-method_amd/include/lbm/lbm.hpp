@@ -191,6 +191,49 @@ class AdeInteriorWalls {
   lbm_ade_iwalls* h_ = nullptr;
 };
 
+// Open boundaries of the fluid + scalar step, wraps lbm_ade_open: f rules (bounce-back, specular, anti-bounce-back with a
+// fixed or an extrapolated wall velocity), g rules (no-flux, fixed concentration) and zero-gradient copies of g on listed
+// nodes -- the inlet, outlet and lid of test/rectangle_sedimentation_test.cpp (channel()).  Add segments, finalize() (the
+// upload), then AdeSolver::set_open; the table is borrowed and must outlive every solver and captured graph that uses it.
+class AdeOpenBoundary {
+ public:
+  AdeOpenBoundary(int R, int C) { check(lbm_ade_open_create(&h_, R, C)); }
+  AdeOpenBoundary(AdeOpenBoundary&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  AdeOpenBoundary(const AdeOpenBoundary&) = delete;
+  ~AdeOpenBoundary() {
+    if (h_) lbm_ade_open_destroy(h_);
+  }
+  // the n nodes (r0 + i dr, c0 + i dc), negative r0 / c0 from the end; slots: bit s-1 = slot s; rule: LBM_ADE_OPEN_*
+  // ((p0, p1): u_w of ABB; the weights of ABB_EXTRAPOLATED with its inward neighbour (nr, nc))
+  AdeOpenBoundary& add_f(int r0, int c0, int dr, int dc, int n, unsigned slots, int rule, double p0 = 0.0, double p1 = 0.0,
+                         int nr = 0, int nc = 0) {
+    check(lbm_ade_open_add_f(h_, r0, c0, dr, dc, n, slots, rule, p0, p1, nr, nc));
+    return *this;
+  }
+  AdeOpenBoundary& add_g(int r0, int c0, int dr, int dc, int n, unsigned slots, int g_mode = LBM_ADE_SCALAR_NO_FLUX,
+                         double conc = 0.0) {
+    check(lbm_ade_open_add_g(h_, r0, c0, dr, dc, n, slots, g_mode, conc));
+    return *this;
+  }
+  // the nodes of the segment read their post-collision g from node + (from_dr, from_dc)
+  AdeOpenBoundary& add_g_copy(int r0, int c0, int dr, int dc, int n, int from_dr, int from_dc) {
+    check(lbm_ade_open_add_g_copy(h_, r0, c0, dr, dc, n, from_dr, from_dc));
+    return *this;
+  }
+  // the sedimentation channel of the reference driver for this R x C (lbm_ade_open_add_channel)
+  AdeOpenBoundary& channel(double u_in, double conc_w = 1e-3, int conc_rows = 50) {
+    check(lbm_ade_open_add_channel(h_, u_in, conc_w, conc_rows));
+    return *this;
+  }
+  int count() const { return lbm_ade_open_count(h_); }
+  long long carry_len() const { return lbm_ade_open_carry_len(h_); }
+  void finalize() { check(lbm_ade_open_finalize(h_)); }
+  const lbm_ade_open* handle() const { return h_; }
+
+ private:
+  lbm_ade_open* h_ = nullptr;
+};
+
 // Compressible BGK fluid + transported scalar on one block, wraps lbm_ade_solver: the sediment concentration of
 // test/rectangle_sedimentation_test.cpp:88-247 (equilibrium(g_equi, u + w, C), its own BGK rate, streamed like f;
 // no-flux walls, or fixed-concentration ones through set_scalar_bc; passive, or driving the fluid through set_buoyancy;
@@ -226,6 +269,9 @@ class AdeSolver {
   // interior walls from the next stream on (a finalized table, borrowed: it must outlive the solver); clear_walls: none
   void set_walls(const AdeInteriorWalls& w) { check(lbm_ade_solver_set_walls(h_, w.handle())); }
   void clear_walls() { check(lbm_ade_solver_set_walls(h_, nullptr)); }
+  // open boundaries from the next step on (a finalized table, borrowed); taken before the first step or before set_state
+  void set_open(const AdeOpenBoundary& o) { check(lbm_ade_solver_set_open(h_, o.handle())); }
+  void clear_open() { check(lbm_ade_solver_set_open(h_, nullptr)); }
   // what the reference loop holds after the iterations run so far
   struct State {
     std::vector<double> f, g;  // [R][C][9]

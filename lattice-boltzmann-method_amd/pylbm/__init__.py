@@ -27,6 +27,9 @@ ADE_SCALAR_NO_FLUX, ADE_SCALAR_FIXED = 0, 1  # lbm_ade_scalar_bc.mode (LBM_ADE_S
 # slot masks of the interior walls' axis-aligned facings (LBM_ADE_FACE_*): bit s-1 = slot s, fluid on the named side
 ADE_FACE_ROW_POS, ADE_FACE_ROW_NEG, ADE_FACE_COL_POS, ADE_FACE_COL_NEG = 0x91, 0x64, 0x32, 0xC8
 
+# f rules of the open boundaries (LBM_ADE_OPEN_*)
+ADE_OPEN_BOUNCE_BACK, ADE_OPEN_SPECULAR_ROW, ADE_OPEN_SPECULAR_COL, ADE_OPEN_ABB, ADE_OPEN_ABB_EXTRAPOLATED = 1, 2, 3, 4, 5
+
 _dp = ct.POINTER(ct.c_double)
 
 
@@ -188,6 +191,71 @@ class AdeInteriorWalls:
             pass
 
 
+class AdeOpenBoundary:
+    """Python face of lbm_ade_open: open boundaries of the fluid + scalar step on one block (inlet, outlet, specular lid and
+    zero-gradient copies of test/rectangle_sedimentation_test.cpp).  Build with add_f / add_g / add_g_copy (or channel),
+    then finalize() -- the upload -- and hand it to AdeSolver(open=...) / set_open; it must outlive every solver and
+    captured graph that uses it."""
+
+    def __init__(self, lib, R, C):
+        self.lib, self.R, self.C = lib, R, C
+        self.h = ct.c_void_p()
+        lib.ade_open_create(ct.byref(self.h), int(R), int(C))
+
+    def add_f(self, r0, c0, dr, dc, n, slots, rule, p=(0.0, 0.0), neighbour=(0, 0)):
+        """an f rule (ADE_OPEN_*) on the slots of the mask; p: u_w of ABB, (a, b) of ABB_EXTRAPOLATED with its inward
+        neighbour offset"""
+        self.lib.ade_open_add_f(self.h, int(r0), int(c0), int(dr), int(dc), int(n), ct.c_uint(slots), int(rule),
+                                ct.c_double(p[0]), ct.c_double(p[1]), int(neighbour[0]), int(neighbour[1]))
+        return self
+
+    def add_g(self, r0, c0, dr, dc, n, slots, g_mode=ADE_SCALAR_NO_FLUX, conc=0.0):
+        self.lib.ade_open_add_g(self.h, int(r0), int(c0), int(dr), int(dc), int(n), ct.c_uint(slots), int(g_mode),
+                                ct.c_double(conc))
+        return self
+
+    def add_g_copy(self, r0, c0, dr, dc, n, source):
+        """the nodes of the segment read their post-collision g from node + source"""
+        self.lib.ade_open_add_g_copy(self.h, int(r0), int(c0), int(dr), int(dc), int(n), int(source[0]), int(source[1]))
+        return self
+
+    def channel(self, u_in, conc_w=1e-3, conc_rows=50):
+        """the sedimentation channel of the reference driver for this R x C (lbm_ade_open_add_channel)"""
+        self.lib.ade_open_add_channel(self.h, ct.c_double(u_in), ct.c_double(conc_w), int(conc_rows))
+        return self
+
+    def count(self):
+        return int(self.lib.raw.lbm_ade_open_count(self.h))
+
+    def carry_len(self):
+        return int(self.lib.raw.lbm_ade_open_carry_len(self.h))
+
+    def node(self, i):
+        """node i of the resolved table: dict r, c, f_rule [8], g_rule [8] (0 none, 1 + ADE_SCALAR_*), g_src [9] of (r, c)"""
+        r, c = ct.c_int(), ct.c_int()
+        fr, gr, sr, sc = (ct.c_int * 8)(), (ct.c_int * 8)(), (ct.c_int * 9)(), (ct.c_int * 9)()
+        self.lib.ade_open_node(self.h, int(i), ct.byref(r), ct.byref(c), fr, gr, sr, sc)
+        return dict(r=r.value, c=c.value, f_rule=list(fr), g_rule=list(gr), g_src=list(zip(sr, sc)))
+
+    def nodes(self):
+        return [self.node(i) for i in range(self.count())]
+
+    def finalize(self):
+        self.lib.ade_open_finalize(self.h)
+        return self
+
+    def close(self):
+        if self.h:
+            self.lib.ade_open_destroy(self.h)
+            self.h = ct.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def declared_symbols(header=HEADER):
     """Every function the C header declares (used by the ABI-completeness test)."""
     txt = open(header).read()
@@ -208,6 +276,7 @@ def load_library(path=LIB_PATH):
     lib.lbm_cg_solver_pair_launches.restype = ct.c_longlong
     lib.lbm_slab_pressure_msg_doubles.restype = ct.c_longlong
     lib.lbm_ade_solver_launches.restype = ct.c_longlong
+    lib.lbm_ade_open_carry_len.restype = ct.c_longlong
     return lib
 
 
@@ -332,17 +401,20 @@ class AdeSolver:
     """Python face of lbm_ade_solver: a compressible BGK fluid f and a transported scalar g on one block
     (the sediment loop of test/rectangle_sedimentation_test.cpp), numpy AoS in/out, reference layout."""
 
-    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None, scalar_bc=None, buoyancy=None, walls=None):
+    def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None, scalar_bc=None, buoyancy=None, walls=None,
+                 open=None):
         self.lib, self.R, self.C, self.fluid, self.scalar = lib, R, C, fluid, scalar
         self.g = Geom(R, C, 0)
         self.bc = bc if bc is not None else Bc.periodic()
         self.h = ct.c_void_p()
         lib.ade_solver_create(ct.byref(self.h), ct.byref(self.g), ct.byref(self.bc), ct.byref(fluid),
                               ct.byref(scalar), _stream(stream))
-        self.scalar_bc = self.buoyancy = self.walls = None
+        self.scalar_bc = self.buoyancy = self.walls = self.open = None
         try:
             if walls is not None:
                 self.set_walls(walls)
+            if open is not None:
+                self.set_open(open)
             if scalar_bc is not None:
                 self.set_scalar_bc(scalar_bc)
             if buoyancy is not None:
@@ -365,6 +437,12 @@ class AdeSolver:
         """the interior walls from the next stream on (a finalized AdeInteriorWalls, or None: none); borrowed, not copied"""
         self.lib.ade_solver_set_walls(self.h, walls.h if walls is not None else None)
         self.walls = walls  # keeps the table alive
+
+    def set_open(self, table):
+        """the open boundaries from the next step on (a finalized AdeOpenBoundary, or None: none); borrowed, not copied.
+        A non-empty table is taken before the first step or before set_state only."""
+        self.lib.ade_solver_set_open(self.h, table.h if table is not None else None)
+        self.open = table  # keeps the table alive
 
     def close(self):
         if self.h:

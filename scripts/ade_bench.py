@@ -14,10 +14,13 @@ and against the single-step BGK launch, on one periodic box, in one process, alt
   --interior-walls adds two boxes with bounce-back rows: iwalls_plain, and iwalls_rectangle with the sedimentation
   driver's rectangle (rectangle_sedimentation_test.cpp:73-75 scaled to the box: ceiling R/3 above the last row, columns
   2C/8 .. 5C/16; absorbing) as interior walls (lbm_ade_iwalls): one more launch per step, one lane per table node
+  --open adds two boxes with a bounce-back bottom row: open_plain, and open_channel with the sedimentation channel's open
+  boundaries (lbm_ade_open_add_channel: inlet, extrapolated outlet, specular lid, zero-gradient copies, concentration
+  inlet): one more launch per step, one lane per listed node (3 R + 3 C - 9 of them)
 MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
 (18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
 usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls] [--buoyancy]
-       [--interior-walls]"""
+       [--interior-walls] [--open]"""
 import argparse
 import ctypes as ct
 import json
@@ -49,6 +52,7 @@ def main():
     ap.add_argument("--fixed-walls", action="store_true")
     ap.add_argument("--buoyancy", action="store_true")
     ap.add_argument("--interior-walls", action="store_true")
+    ap.add_argument("--open", action="store_true")
     a = ap.parse_args()
     form = {"default": pylbm.FORM_DEFAULT, "ref": pylbm.FORM_REFERENCE_ORDER, "fast": pylbm.FORM_REASSOCIATED}[a.form]
     lib = pylbm.Lib()
@@ -156,6 +160,18 @@ def main():
             bodies[key] = w
         lib.stream_sync(st)
 
+    channels, open_table = {}, None
+    if a.open:
+        obc = pylbm.Bc(row_hi=pylbm.EDGE_BOUNCE_BACK)
+        open_table = pylbm.AdeOpenBoundary(lib, R, C).channel(0.02, 1e-3, R // 4).finalize()
+        for key, t in (("open_plain", None), ("open_channel", open_table)):
+            w = pylbm.AdeSolver(lib, R, C, fluid, scalar, bc=obc, stream=st.value, open=t)
+            wf, wg, _, _, wgeo = w.lattices()
+            lib.lattice_copy_rows(_ptr(wf), ct.byref(wgeo), 0, _ptr(f), ct.byref(dg), 0, R, st)
+            lib.lattice_copy_rows(_ptr(wg), ct.byref(wgeo), 0, _ptr(g), ct.byref(dg), 0, R, st)
+            channels[key] = w
+        lib.stream_sync(st)
+
     # composed: the reference loop from the unfused operators (dense lattices f, g advance in place of the loop)
     if not a.skip_composed:
         fe, ge, fc, gc = (torch.empty_like(f) for _ in range(4))
@@ -181,6 +197,8 @@ def main():
     if buoyant is not None:
         runs["buoyant"] = buoyant.step
     for key, w in bodies.items():
+        runs[key] = w.step
+    for key, w in channels.items():
         runs[key] = w.step
     if not a.skip_composed:
         runs["composed"] = run_composed
@@ -231,6 +249,16 @@ def main():
         for w in bodies.values():
             w.close()
         table.close()
+    if channels:
+        out["open_plain_mlups"] = round(mlups["open_plain"], 1)
+        out["open_channel_mlups"] = round(mlups["open_channel"], 1)
+        out["open_channel_over_plain"] = round(mlups["open_channel"] / mlups["open_plain"], 4)
+        out["open_channel_over_plain_per_repeat"] = [round(p / b, 4) for p, b in zip(times["open_plain"], times["open_channel"])]
+        out["open_table_nodes"] = open_table.count()
+        out["open_launches_total"] = {k: w.launches() for k, w in channels.items()}
+        for w in channels.values():
+            w.close()
+        open_table.close()
     sv.close()
     lib.event_destroy(e0)
     lib.event_destroy(e1)

@@ -1,0 +1,300 @@
+"""CPU suite, open boundaries of the fluid + scalar solver (lbm_ade_open, lbm_ade_stream_collide_o, lbm_ade_collide_o,
+lbm_ade_solver_set_open; pylbm.AdeOpenBoundary): exported and declared, plain C99, every refusal of the table builder and
+of the calls that take a table made on the host with LBM_ERR_INVALID and a message that names the node, the resolved table
+of the sedimentation channel at 160 x 256, and a supported call past validation to the NULL-lattice refusal (no GPU
+needed: only a non-empty finalize touches the device)."""
+import ctypes as ct
+import math
+import os
+import re
+import subprocess
+
+import pytest
+
+import pylbm
+
+SYMBOLS = ["lbm_ade_open_create", "lbm_ade_open_add_f", "lbm_ade_open_add_g", "lbm_ade_open_add_g_copy",
+           "lbm_ade_open_add_channel", "lbm_ade_open_count", "lbm_ade_open_node", "lbm_ade_open_carry_len",
+           "lbm_ade_open_finalize", "lbm_ade_open_destroy", "lbm_ade_collide_o", "lbm_ade_stream_collide_o",
+           "lbm_ade_solver_set_open"]
+BB, SP, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR, pylbm.EDGE_PERIODIC
+NO_FLUX, FIXED = pylbm.ADE_SCALAR_NO_FLUX, pylbm.ADE_SCALAR_FIXED
+O_BB, O_SROW, O_SCOL, O_ABB, O_ABBX = (pylbm.ADE_OPEN_BOUNCE_BACK, pylbm.ADE_OPEN_SPECULAR_ROW, pylbm.ADE_OPEN_SPECULAR_COL,
+                                       pylbm.ADE_OPEN_ABB, pylbm.ADE_OPEN_ABB_EXTRAPOLATED)
+LBM_ERR_INVALID = -1
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CX = [0, 1, 0, -1, 0, 1, -1, -1, 1]
+CY = [0, 0, 1, 0, -1, 1, 1, -1, -1]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return pylbm.Lib()
+
+
+def mask(*slots):
+    return sum(1 << (s - 1) for s in slots)
+
+
+def _refused(lib, rc, name, msg):
+    err = lib.raw.lbm_last_error_string().decode()
+    assert rc == LBM_ERR_INVALID, (name, rc, err)
+    assert err.startswith(name + ":") and re.search(msg, err), (name, err)
+
+
+def add_f(lib, t, r0, c0, dr, dc, n, slots, rule, p0=0.0, p1=0.0, nr=0, nc=0):
+    h = t.h if isinstance(t, pylbm.AdeOpenBoundary) else t
+    return lib.raw.lbm_ade_open_add_f(h, r0, c0, dr, dc, n, ct.c_uint(slots), rule, ct.c_double(p0), ct.c_double(p1), nr, nc)
+
+
+def add_g(lib, t, r0, c0, dr, dc, n, slots, mode=NO_FLUX, conc=0.0):
+    h = t.h if isinstance(t, pylbm.AdeOpenBoundary) else t
+    return lib.raw.lbm_ade_open_add_g(h, r0, c0, dr, dc, n, ct.c_uint(slots), mode, ct.c_double(conc))
+
+
+def add_copy(lib, t, r0, c0, dr, dc, n, fr, fc):
+    h = t.h if isinstance(t, pylbm.AdeOpenBoundary) else t
+    return lib.raw.lbm_ade_open_add_g_copy(h, r0, c0, dr, dc, n, fr, fc)
+
+
+def test_symbols_are_declared_and_exported(lib):
+    declared = set(pylbm.declared_symbols())
+    for name in SYMBOLS:
+        assert name in declared, name
+        assert hasattr(lib.raw, name), name
+    assert lib.raw.lbm_abi_version() == 1
+    txt = open(os.path.join(ROOT, "include", "lbm_hip.h")).read()
+    for name, v in (("BOUNCE_BACK", O_BB), ("SPECULAR_ROW", O_SROW), ("SPECULAR_COL", O_SCOL), ("ABB", O_ABB),
+                    ("ABB_EXTRAPOLATED", O_ABBX)):
+        assert re.search(rf"#define LBM_ADE_OPEN_{name} {v}\b", txt), name
+
+
+def test_header_is_plain_c99(tmp_path):
+    src = tmp_path / "open_c99.c"
+    src.write_text('#include "lbm_hip.h"\n'
+                   'int main(void){ lbm_ade_open* t = 0; int r, c, fr[8], gr[8], sr[9], sc[9];\n'
+                   '  if (lbm_ade_solver_set_open(0, 0) != LBM_ERR_INVALID) return 2;\n'
+                   '  if (lbm_ade_open_create(&t, 160, 256) != LBM_OK) return 3;\n'
+                   '  if (lbm_ade_open_add_channel(t, 0.03, 1e-3, 50) != LBM_OK) return 4;\n'
+                   '  if (lbm_ade_open_count(t) != 1239 || lbm_ade_open_carry_len(t) != 2478) return 5;\n'
+                   '  if (lbm_ade_open_node(t, 255, &r, &c, fr, gr, sr, sc) != LBM_OK || r != 0 || c != 255) return 6;\n'
+                   '  if (fr[7] != LBM_ADE_OPEN_SPECULAR_ROW || fr[1] != LBM_ADE_OPEN_ABB_EXTRAPOLATED || gr[0] != 0) return 7;\n'
+                   '  if (sr[0] != 1 || sc[0] != 255) return 8;\n'
+                   '  if (lbm_ade_stream_collide_o(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, t, 0, 0, 0, 0, 0, 0, 0, 0) != LBM_ERR_INVALID) return 9;\n'
+                   '  if (lbm_ade_collide_o(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, t, 0, 0, 0, 0, 0) != LBM_ERR_INVALID) return 10;\n'
+                   '  if (lbm_ade_open_destroy(t) != LBM_OK) return 11;\n'
+                   '  return lbm_abi_version() == 1 ? 0 : 1; }\n')
+    libdir = os.path.join(ROOT, "lattice-boltzmann-method_amd", "lib")
+    exe = tmp_path / "open_c99"
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           str(src), "-L", libdir, "-llbm_hip", f"-Wl,-rpath,{libdir}", "-o", str(exe)])
+    assert subprocess.call([str(exe)]) == 0
+
+
+# ---- the table builder's refusals ---------------------------------------------------------------------------------------
+def test_create_refuses_a_null_out_and_a_non_positive_size(lib):
+    _refused(lib, lib.raw.lbm_ade_open_create(None, 8, 8), "lbm_ade_open_create", "NULL argument")
+    h = ct.c_void_p()
+    for R, C in ((0, 8), (8, 0), (-3, 8)):
+        _refused(lib, lib.raw.lbm_ade_open_create(ct.byref(h), R, C), "lbm_ade_open_create", f"R={R} C={C} must be positive")
+        assert not h
+    _refused(lib, lib.raw.lbm_ade_open_create(ct.byref(h), 65536, 32768), "lbm_ade_open_create", "more than 2\\^31 - 1 nodes")
+
+
+def test_a_null_table_is_refused_by_every_entry_that_needs_one(lib):
+    _refused(lib, add_f(lib, None, 0, 0, 0, 1, 1, 1, O_BB), "lbm_ade_open_add_f", "NULL table")
+    _refused(lib, add_g(lib, None, 0, 0, 0, 1, 1, 1), "lbm_ade_open_add_g", "NULL table")
+    _refused(lib, add_copy(lib, None, 0, 0, 0, 1, 1, 1, 0), "lbm_ade_open_add_g_copy", "NULL table")
+    _refused(lib, lib.raw.lbm_ade_open_add_channel(None, ct.c_double(0.03), ct.c_double(1e-3), 50), "lbm_ade_open_add_channel",
+             "NULL table")
+    _refused(lib, lib.raw.lbm_ade_open_finalize(None), "lbm_ade_open_finalize", "NULL table")
+    _refused(lib, lib.raw.lbm_ade_open_node(None, 0, None, None, None, None, None, None), "lbm_ade_open_node", "NULL table")
+    assert lib.raw.lbm_ade_open_count(None) == 0 and lib.raw.lbm_ade_open_carry_len(None) == 0
+    assert lib.raw.lbm_ade_open_destroy(None) == 0
+    _refused(lib, lib.raw.lbm_ade_solver_set_open(None, None), "lbm_ade_solver_set_open", "NULL solver")
+
+
+ALL = 0xFF
+REFUSALS = [
+    (add_f, (24, 0, 0, 1, 1, ALL, O_BB), "lbm_ade_open_add_f", r"node \(24, 0\) outside the 24 x 32 lattice"),
+    (add_f, (3, 30, 0, 1, 3, ALL, O_BB), "lbm_ade_open_add_f", r"node \(3, 32\) outside the 24 x 32 lattice"),
+    (add_f, (-25, 0, 0, 1, 1, ALL, O_BB), "lbm_ade_open_add_f", r"node \(-1, 0\) outside the 24 x 32 lattice"),
+    (add_f, (3, 3, 0, 1, 2, 0, O_BB), "lbm_ade_open_add_f", r"slot mask slots=0x0"),
+    (add_f, (3, 3, 0, 1, 2, 0x100, O_BB), "lbm_ade_open_add_f", r"slot mask slots=0x100"),
+    (add_f, (3, 3, 0, 1, 2, ALL, 0), "lbm_ade_open_add_f", r"rule=0 \(LBM_ADE_OPEN_\*\)"),
+    (add_f, (3, 3, 0, 1, 2, ALL, 6), "lbm_ade_open_add_f", r"rule=6"),
+    (add_f, (3, 3, 0, 1, 0, ALL, O_BB), "lbm_ade_open_add_f", r"n=0 must be at least 1"),
+    (add_f, (3, 3, 0, 0, 2, ALL, O_BB), "lbm_ade_open_add_f", r"step \(dr, dc\)=\(0, 0\)"),
+    (add_f, (3, 3, 0, 2, 2, ALL, O_BB), "lbm_ade_open_add_f", r"step \(dr, dc\)=\(0, 2\)"),
+    (add_f, (3, 3, 0, 1, 2, ALL, O_ABB, math.nan, 0.0), "lbm_ade_open_add_f", r"\(p0, p1\)=\(nan, 0\) must be finite"),
+    (add_f, (3, 3, 0, 1, 2, ALL, O_ABBX, 1.5, math.inf, 0, -1), "lbm_ade_open_add_f", r"\(p0, p1\)=\(1.5, inf\) must be finite"),
+    # the outlet's inward neighbour: in the lattice, no wrap; the far end of the segment decides as well
+    (add_f, (0, 31, 1, 0, 24, ALL, O_ABBX, 1.5, -0.5, 0, 1), "lbm_ade_open_add_f",
+     r"node \(0, 31\): neighbour \(0, 32\) outside the 24 x 32 lattice"),
+    (add_f, (0, 0, 1, 0, 24, ALL, O_ABBX, 1.5, -0.5, 0, -1), "lbm_ade_open_add_f",
+     r"node \(0, 0\): neighbour \(0, -1\) outside"),
+    (add_f, (20, 5, 1, 0, 4, ALL, O_ABBX, 1.5, -0.5, 1, 0), "lbm_ade_open_add_f",
+     r"node \(23, 5\): neighbour \(24, 5\) outside"),
+    (add_f, (3, 3, 0, 1, 2, ALL, O_ABBX, 1.5, -0.5, 0, 0), "lbm_ade_open_add_f", r"neighbour offset \(0, 0\)"),
+    (add_g, (24, 0, 0, 1, 1, ALL), "lbm_ade_open_add_g", r"node \(24, 0\) outside the 24 x 32 lattice"),
+    (add_g, (3, 3, 0, 1, 2, 0), "lbm_ade_open_add_g", r"slot mask slots=0x0"),
+    (add_g, (3, 3, 0, 1, 2, ALL, 2), "lbm_ade_open_add_g", r"g_mode=2 \(LBM_ADE_SCALAR_NO_FLUX or LBM_ADE_SCALAR_FIXED\)"),
+    (add_g, (3, 3, 0, 1, 2, ALL, FIXED, math.nan), "lbm_ade_open_add_g", r"conc=nan must be finite"),
+    (add_copy, (0, 0, 0, 1, 32, -1, 0), "lbm_ade_open_add_g_copy", r"node \(0, 0\): copy source \(-1, 0\) outside the 24 x 32 lattice"),
+    (add_copy, (1, 31, 1, 0, 22, 0, 1), "lbm_ade_open_add_g_copy", r"node \(1, 31\): copy source \(1, 32\) outside"),
+    (add_copy, (1, 5, 1, 0, 23, 1, 0), "lbm_ade_open_add_g_copy", r"node \(23, 5\): copy source \(24, 5\) outside"),
+    (add_copy, (1, 5, 1, 0, 3, 0, 0), "lbm_ade_open_add_g_copy", r"copy source offset \(0, 0\)"),
+    (add_copy, (1, 32, 1, 0, 3, 0, -1), "lbm_ade_open_add_g_copy", r"node \(1, 32\) outside the 24 x 32 lattice"),
+]
+
+
+@pytest.mark.parametrize("case", range(len(REFUSALS)))
+def test_add_refuses_on_the_host_names_the_node_and_adds_nothing(lib, case):
+    fn, args, name, msg = REFUSALS[case]
+    t = pylbm.AdeOpenBoundary(lib, 24, 32)
+    t.add_f(2, 2, 0, 1, 3, mask(1, 5), O_BB)
+    before = t.nodes()
+    _refused(lib, fn(lib, t, *args), name, msg)
+    assert t.nodes() == before and t.count() == 3
+    t.close()
+
+
+def test_the_channel_helper_refuses_what_it_cannot_build(lib):
+    t = pylbm.AdeOpenBoundary(lib, 2, 8)
+    rc = lib.raw.lbm_ade_open_add_channel(t.h, ct.c_double(0.03), ct.c_double(1e-3), 50)
+    _refused(lib, rc, "lbm_ade_open_add_channel", r"R=2 C=8: the channel needs R >= 3")
+    t.close()
+    t = pylbm.AdeOpenBoundary(lib, 24, 32)
+    for u_in, cw, rows, msg in ((math.nan, 1e-3, 5, "u_in=nan"), (0.03, math.inf, 5, "conc_w=inf"), (0.03, 1e-3, -1, "conc_rows=-1")):
+        rc = lib.raw.lbm_ade_open_add_channel(t.h, ct.c_double(u_in), ct.c_double(cw), rows)
+        _refused(lib, rc, "lbm_ade_open_add_channel", msg)
+        assert t.count() == 0
+    t.close()
+
+
+def _step(lib, geom, t=None, iwalls=None, bc=None, sbc=None, carry=(None, None), rows=None, lattices=None):
+    fl, sc = pylbm.BgkParams(1.2, 0), pylbm.AdeParams(1.7, (3e-3, 3e-3))
+    r0, r1 = rows if rows else (0, geom.R)
+    lat = lattices or (None, None, None, None)
+    return lib.raw.lbm_ade_stream_collide_o(*lat, ct.byref(geom), ct.byref(bc) if bc else None, ct.byref(fl), ct.byref(sc),
+                                            ct.byref(sbc) if sbc else None, None, iwalls.h if iwalls else None,
+                                            t.h if t is not None else None, carry[0], carry[1], r0, r1, None, None, None, None)
+
+
+def test_the_table_is_immutable_after_finalize_and_unusable_before(lib):
+    g = pylbm.Geom(24, 32, 0)
+    t = pylbm.AdeOpenBoundary(lib, 24, 32)
+    _refused(lib, _step(lib, g, t), "lbm_ade_stream_collide_o", "open boundaries: the table is not finalized")
+    t.finalize()  # empty: no device call
+    _refused(lib, add_f(lib, t, 3, 3, 0, 1, 2, ALL, O_BB), "lbm_ade_open_add_f", "the table is finalized")
+    _refused(lib, add_g(lib, t, 3, 3, 0, 1, 2, ALL), "lbm_ade_open_add_g", "the table is finalized")
+    _refused(lib, add_copy(lib, t, 3, 3, 0, 1, 2, 1, 0), "lbm_ade_open_add_g_copy", "the table is finalized")
+    _refused(lib, lib.raw.lbm_ade_open_add_channel(t.h, ct.c_double(0.03), ct.c_double(1e-3), 5), "lbm_ade_open_add_channel",
+             "the table is finalized")
+    _refused(lib, lib.raw.lbm_ade_open_finalize(t.h), "lbm_ade_open_finalize", "finalized already")
+    assert t.count() == 0 and t.carry_len() == 0
+    _refused(lib, lib.raw.lbm_ade_open_node(t.h, 0, None, None, None, None, None, None), "lbm_ade_open_node",
+             r"node 0 outside \[0, 0\)")
+    for geom in (pylbm.Geom(24, 34, 0), pylbm.Geom(26, 32, 0)):  # a table built for another lattice
+        _refused(lib, _step(lib, geom, t), "lbm_ade_stream_collide_o",
+                 rf"open boundaries: the table is for a 24 x 32 lattice, the call for {geom.R} x {geom.C}")
+    _refused(lib, _step(lib, pylbm.Geom(24, 31, 0), t), "lbm_ade_stream_collide_o", "C=31 must be even")
+    t.close()
+
+
+def test_a_supported_call_passes_validation_without_a_gpu(lib):
+    """NULL, and an empty finalized table, with and without walls, FIXED edges and an (empty) interior-wall table, in
+    every form, any row range: up to the existing NULL-lattice refusal, for the streamed and the collide-only call"""
+    g = pylbm.Geom(24, 32, 0)
+    empty = pylbm.AdeOpenBoundary(lib, 24, 32).finalize()
+    no_walls = pylbm.AdeInteriorWalls(lib, 24, 32).finalize()
+    wall_bc = pylbm.Bc(row_lo=BB, row_hi=BB, col_lo=SP, col_hi=BB)
+    for t in (None, empty):
+        for bc, sbc in ((None, None), (wall_bc, None), (wall_bc, pylbm.AdeScalarBC(row_lo=1e-3, col_hi=0.0))):
+            for iw in (None, no_walls):
+                for rows in (None, (3, 9)):
+                    _refused(lib, _step(lib, g, t, iw, bc, sbc, rows=rows), "lbm_ade_stream_collide_o", "NULL lattice")
+            for form in (pylbm.FORM_DEFAULT, pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED):
+                fl, sc = pylbm.BgkParams(1.2, 0, form=form), pylbm.AdeParams(1.7, (3e-3, 3e-3), form=form)
+                rc = lib.raw.lbm_ade_collide_o(None, None, None, None, ct.byref(g), ct.byref(bc) if bc else None, ct.byref(fl),
+                                               ct.byref(sc), ct.byref(sbc) if sbc else None, None, t.h if t else None, None,
+                                               None, None, None, None)
+                _refused(lib, rc, "lbm_ade_collide_o", "NULL lattice")
+    empty.close()
+    no_walls.close()
+
+
+# ---- the resolved table -------------------------------------------------------------------------------------------------
+def test_merging_later_wins_per_slot_and_the_listed_nodes_are_exactly_the_union(lib):
+    R, C = 12, 16
+    t = pylbm.AdeOpenBoundary(lib, R, C)
+    t.add_f(5, 5, 0, 1, 2, mask(1, 2, 3), O_BB).add_f(5, 6, 0, 1, 1, mask(2), O_SCOL)
+    t.add_g(5, 5, 0, 1, 1, mask(4), FIXED, 2e-3).add_g(5, 5, 0, 1, 1, mask(4, 6), NO_FLUX)
+    by = {(n["r"], n["c"]): n for n in t.nodes()}
+    assert sorted(by) == [(5, 5), (5, 6)]
+    assert by[(5, 6)]["f_rule"] == [O_BB, O_SCOL, O_BB, 0, 0, 0, 0, 0] and by[(5, 6)]["g_rule"] == [0] * 8
+    assert by[(5, 5)]["g_rule"] == [0, 0, 0, 1 + NO_FLUX, 0, 1 + NO_FLUX, 0, 0]
+    # sources of a node without a redirected neighbour: the periodic pull
+    assert by[(5, 5)]["g_src"] == [((5 - CX[q]) % R, (5 - CY[q]) % C) for q in range(9)]
+    # a copy lists the nine readers of its destination, wrapped; a chain of copies resolves to the last source
+    t.add_g_copy(0, 0, 0, 1, 1, (1, 0)).add_g_copy(11, 15, 0, 1, 1, (-11, -15))
+    by = {(n["r"], n["c"]): n for n in t.nodes()}
+    readers = {((0 + CX[q]) % R, (0 + CY[q]) % C) for q in range(9)} | {((11 + CX[q]) % R, (15 + CY[q]) % C) for q in range(9)}
+    assert set(by) == readers | {(5, 5), (5, 6)}
+    assert by[(0, 0)]["g_src"][0] == (1, 0) and by[(11, 15)]["g_src"][0] == (1, 0)   # (11, 15) <- (0, 0) <- (1, 0)
+    assert by[(1, 1)]["g_src"][5] == (1, 0) and by[(1, 1)]["g_src"][0] == (1, 1)
+    # the inward neighbour of an extrapolating node is listed, with no rule of its own
+    t.add_f(8, 9, 1, 0, 1, mask(4), O_ABBX, (1.5, -0.5), (0, -1))
+    by = {(n["r"], n["c"]): n for n in t.nodes()}
+    assert by[(8, 8)]["f_rule"] == [0] * 8 and by[(8, 9)]["f_rule"][3] == O_ABBX
+    assert t.carry_len() == 2 * t.count() == 2 * len(by)
+    t.close()
+
+
+def test_the_sedimentation_channel_at_160_x_256(lib):
+    R, C = 160, 256
+    t = pylbm.AdeOpenBoundary(lib, R, C).channel(0.03)
+    assert t.count() == 3 * C + 3 * R - 9 == 1239 and t.carry_len() == 2478
+    nodes = t.nodes()
+    rc = [(n["r"], n["c"]) for n in nodes]
+    assert rc == sorted(rc)
+    assert set(rc) == {(r, c) for r in range(R) for c in range(C) if r in (0, 1, R - 1) or c in (0, C - 2, C - 1)}
+    by = {(n["r"], n["c"]): n for n in nodes}
+    # the outlet runs over all rows; the specular top and the no-slip bottom take their three slots back at the corners
+    want = [O_ABBX] * 8
+    for s in (8, 1, 5):
+        want[s - 1] = O_SROW
+    assert by[(0, C - 1)]["f_rule"] == want
+    want = [O_ABBX] * 8
+    for s in (7, 3, 6):
+        want[s - 1] = O_BB
+    assert by[(R - 1, C - 1)]["f_rule"] == want
+    assert by[(R - 1, C - 1)]["g_rule"] == [0] * 8
+    assert by[(5, C - 1)]["f_rule"] == [O_ABBX] * 8 and by[(5, 0)]["f_rule"] == [O_ABB] * 8
+    assert by[(0, 0)]["f_rule"] == [O_SROW if s in (8, 1, 5) else 0 for s in range(1, 9)]   # the inlet starts at row 1
+    assert by[(R - 1, 0)]["f_rule"] == [0] * 8 and by[(R - 1, 0)]["g_rule"] == [0] * 8
+    assert by[(5, 0)]["g_rule"] == [1 + FIXED] * 8 and by[(0, 0)]["g_rule"] == [0] * 8
+    # second copy after first: row 0 reads row 1 as it was BEFORE the outlet column was redirected
+    for q in range(9):
+        for node, src in (((1, C - 1), (1, C - 2)), ((0, C - 1), (1, C - 1))):
+            reader = ((node[0] + CX[q]) % R, (node[1] + CY[q]) % C)
+            assert by[reader]["g_src"][q] == src, (node, q)
+    assert by[(0, 7)]["g_src"][0] == (1, 7) and by[(1, 7)]["g_src"][1] == (1, 7) and by[(R - 1, 7)]["g_src"][3] == (1, 7)
+    assert by[(R - 1, C - 1)]["g_src"][0] == (R - 1, C - 1)   # the copy covers rows 1 .. R-2
+    t.close()
+    # the rows that hold the inlet concentration are cut to the inlet's rows
+    small = pylbm.AdeOpenBoundary(lib, 6, 8).channel(0.03, 1e-3, 50)
+    assert small.count() == 6 * 8 - 3 * 5
+    small.close()
+
+
+def test_overlap_with_the_interior_walls_is_refused_but_for_the_foot_on_a_wall_row(lib):
+    """on the host: the overlap check precedes the lattice checks and needs non-empty tables, so it is exercised where a
+    device is present (tests/test_gpu_ade_open.py); here: an empty interior-wall table never clashes"""
+    R, C = 24, 32
+    g = pylbm.Geom(R, C, 0)
+    t = pylbm.AdeOpenBoundary(lib, R, C).finalize()
+    iw = pylbm.AdeInteriorWalls(lib, R, C).finalize()
+    _refused(lib, _step(lib, g, t, iw, pylbm.Bc(row_hi=BB)), "lbm_ade_stream_collide_o", "NULL lattice")
+    t.close()
+    iw.close()
