@@ -285,7 +285,9 @@ def test_ulbm_poiseuille_vs_unmodified_main_snapshots(lib):
 
 def test_kbc_sliding_window_carries_walls(lib, oracle):
     """KBC multi-step launches on wall-bounded single blocks (bounce-back columns; closed box):
-    D = 2, 3 steps in one launch == single-step launches (interior kernel + edge pass), bit for bit."""
+    D = 2, 3 steps in one launch == single-step launches (interior kernel + edge pass), bit for bit -- with every frame /
+    interior split (sw_split 0: one wall-carrying launch, 1: frame on the helper stream, 2: one dispatch) and chunk
+    heights above, below and fitted to the lattice, as the BGK counterpart in test_gpu_bgk.py."""
     rng = np.random.default_rng(8)
     R, C = 96, 150
     rho = 1 + 0.01 * rng.standard_normal((R, C))
@@ -295,19 +297,27 @@ def test_kbc_sliding_window_carries_walls(lib, oracle):
     prm = pylbm.KbcParams(S2)
     p0 = upload_soa(lib, f0)
     a, b = torch.empty_like(p0), torch.empty_like(p0)
-    for rows_too in (False, True):
-        bc = pylbm.Bc.periodic()
-        bc.col_lo = bc.col_hi = pylbm.EDGE_BOUNCE_BACK
-        if rows_too:
-            bc.row_lo = bc.row_hi = pylbm.EDGE_BOUNCE_BACK
-        for D in (2, 3):
-            src = p0.clone()
-            for _ in range(D):
-                lib.kbc_stream_collide(_ptr(a), _ptr(src), ct.byref(g), ct.byref(bc), ct.byref(prm), 0, R, None, None, None)
-                src, a = a, src
-            lib.kbc_stream_collide_xn(_ptr(b), _ptr(p0), ct.byref(g), ct.byref(bc), ct.byref(prm), D, 0, R, None)
-            torch.cuda.synchronize()
-            assert torch.equal(b, src), (rows_too, D, float((b - src).abs().max()))
+    try:
+        for rows_too in (False, True):
+            bc = pylbm.Bc.periodic()
+            bc.col_lo = bc.col_hi = pylbm.EDGE_BOUNCE_BACK
+            if rows_too:
+                bc.row_lo = bc.row_hi = pylbm.EDGE_BOUNCE_BACK
+            for D in (2, 3):
+                src = p0.clone()
+                for _ in range(D):
+                    lib.kbc_stream_collide(_ptr(a), _ptr(src), ct.byref(g), ct.byref(bc), ct.byref(prm), 0, R, None, None, None)
+                    src, a = a, src
+                for rows, split in ((-1, -1), (64, 1), (24, 1), (-1, 1), (64, 0), (64, 2), (24, 2), (-1, 2)):   # (-1, -1): the defaults
+                    lib.set_tuning(b"sw_rows", rows)
+                    lib.set_tuning(b"sw_split", split)
+                    b.zero_()
+                    lib.kbc_stream_collide_xn(_ptr(b), _ptr(p0), ct.byref(g), ct.byref(bc), ct.byref(prm), D, 0, R, None)
+                    torch.cuda.synchronize()
+                    assert torch.equal(b, src), (rows_too, D, rows, split, float((b - src).abs().max()))
+    finally:
+        lib.set_tuning(b"sw_rows", -1)
+        lib.set_tuning(b"sw_split", -1)
 
 
 def test_two_solvers_with_different_collision_forms_coexist(lib, oracle):
