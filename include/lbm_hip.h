@@ -716,7 +716,10 @@ int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls);
  * pass and before the interior-wall pass (collide-only: one more small launch that writes the carry).  A node may not be
  * in the call's interior-wall table as well, unless the open table gives it no rule and every g slot whose resolved
  * source differs from the plain pull is one a domain wall replaces at that node (the rectangle's foot on the bottom row).
- * Whole block only: a row range other than [0, R) is refused; the _part entry points and the ring take no open table. */
+ * lbm_ade_collide_o / lbm_ade_stream_collide_o run the whole block: a row range other than [0, R) is refused, and so is a
+ * slab view.  Row slabs and the ring take a VIEW of the table (lbm_ade_open_slab, lbm_ade_stream_collide_part_o,
+ * lbm_ring_ade_collide_o, lbm_ring_ade_step_o below) and refuse an ordinary table; each refusal names the function to
+ * use. */
 #define LBM_ADE_OPEN_BOUNCE_BACK 1
 #define LBM_ADE_OPEN_SPECULAR_ROW 2
 #define LBM_ADE_OPEN_SPECULAR_COL 3
@@ -746,6 +749,43 @@ int lbm_ade_stream_collide_o(double* fn, double* gn, const double* fo, const dou
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                              const lbm_ade_open* open, const double* carry_in, double* carry_out, int row_begin,
                              int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
+/* The slab view of an open table: a new, unfinalized table for an R x C lattice (C the parent's) that lists exactly the
+ * parent's resolved nodes of rows [row0, row0 + R), 0 <= row0, row0 + R <= the parent's rows, at r - row0 and in the
+ * parent's order, each with its winning segment per f and g slot and the segments' parameters.  The parent may be finalized
+ * or not and is not modified.  Host only; lbm_ade_open_finalize uploads the view and keeps a host index of the first node
+ * of each row.  A view takes no lbm_ade_open_add_* call.  Re-resolved per view:
+ *   the nine g sources  slab-local, the row in [-1, R]: -1 and R are the slab's ghost rows (lbm_ade_open_node reports
+ *                       them so).  The source's global row counts modulo the parent's rows: a view that ends at the
+ *                       parent's last row sees global row 0 in its row R.  A source more than one row outside the slab
+ *                       cannot be addressed: it is marked unreachable and points at the slot's plain pull source.
+ *   the neighbours      of extrapolating slots must lie in the view's rows, or lbm_ade_open_slab fails and names the node:
+ *                       the carry is slab-local and no carry travels between slabs (the channel's neighbour is in the
+ *                       same row).
+ *   the carry           lbm_ade_open_carry_len(view) doubles, two per node of the view in the view's order.
+ * What a slab may reach is decided per call, on the host, from the slab's bc: a g source is usable in an owned row, or in
+ * the ghost row of a side whose row edge is HALO (ghost = 0: the wrapped row of a PERIODIC side).  Every slot of a listed
+ * node needs a usable source or must be one the domain's wall gather replaces at that node; the node's own source must be
+ * usable; an unreachable source never is.  Anything else is refused, naming node and slot.  The overlap rule with an
+ * interior-wall table holds between the two slab-local tables. */
+int lbm_ade_open_slab(lbm_ade_open** out, const lbm_ade_open* table, int row0, int R);
+/* the unreachable mark of node i of a view: bit q = the source of g slot q (q = 0: the node's own) lies more than one row
+ * outside the slab; 0 for an ordinary table, NULL or a node outside the table; host only */
+int lbm_ade_open_unreachable(const lbm_ade_open* t, int i);
+/* lbm_ade_stream_collide_part_w with this slab's view and its carry (NULL or empty view: lbm_ade_stream_collide_part_w
+ * itself, the same bits and the same launches; the carry follows the rules above).  Behind the part's dispatch, on the same
+ * stream and before the interior-wall pass, one more dispatch recomputes the view's nodes of the part's rows -- one lane
+ * per node, found through the view's row index: no allocation, no host synchronisation, capturable; a part without a
+ * listed node enqueues nothing.  Each part writes the lattices, moments and carry_out entries of its own rows' nodes only
+ * and reads the old lattices and carry_in only. */
+int lbm_ade_stream_collide_part_o(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                  const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                                  const lbm_ade_open* view, const double* carry_in, double* carry_out, int part,
+                                  int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s);
+/* kernels enqueued so far by the part launches of this process (lbm_ade_stream_collide_part*, lbm_ring_ade_step*): a part's
+ * dispatch, its open pass and its interior-wall pass count one each.  There is no solver context for slabs; this is what
+ * "one more launch per part with a listed node, none without" is tested with. */
+long long lbm_ade_part_launches(void);
 /* the context's open table from the next step on (the lazy stream of get_state included, which applies it without
  * touching the carry); NULL clears it.  Borrowed, not copied.  A non-empty table is taken on a pre-collision state only
  * (before the first step, or after lbm_ade_solver_set_state, which primes the carry): the u before the iteration of a
@@ -844,6 +884,18 @@ int lbm_ring_ade_step_b(lbm_ring* rg, double* fn, double* gn, const double* fo, 
 int lbm_ring_ade_step_w(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main);
+/* lbm_ring_ade_collide_b / lbm_ring_ade_step_w with this slab's view of the open table (lbm_ade_open_slab of the global
+ * one, finalized; NULL or empty: those calls themselves) and its carry.  Collide-only: one more small launch writes
+ * carry_out from the pre-collision f.  A step: the open pass of the FRAME rows runs on the ring's stream behind the FRAME
+ * dispatch and BEFORE the pack -- a neighbour never receives an un-fixed open node -- and the pass of the INNER rows on
+ * `main`; a chain of one slab runs both on `main`.  The carry needs no synchronisation beyond the lattices'. */
+int lbm_ring_ade_collide_o(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                           const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                           const lbm_ade_buoyancy* buoy, const lbm_ade_open* view, double* carry_out, lbm_stream_t main);
+int lbm_ring_ade_step_o(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                        const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                        const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, const lbm_ade_open* view,
+                        const double* carry_in, double* carry_out, int edge_rows, lbm_stream_t main);
 /* refresh the single-step ghost rows of two lattices in one message per neighbour (e.g. after restoring a state);
  * asynchronous, ordered after the work enqueued on `after` (lbm_ring_join makes a stream wait for it) */
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after);

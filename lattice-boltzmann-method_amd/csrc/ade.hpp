@@ -773,7 +773,8 @@ __device__ __forceinline__ void ade_open_gather_scalar(double (&h)[Q], double (&
 // BEFORE the interior-wall pass (a node of both tables carries no rule here: the host checks).  Per node: the domain's
 // gather of f and the table's f slots; the moments; g pulled from the nine resolved sources with the domain's gather, the
 // domain's FIXED edges, the table's g slots; both collisions in k_ade_edge's order.  carry_out[2 i], [2 i + 1] = the u of
-// the fixed-up f (the unshifted u0 of a buoyant step): the next step's carry_in.  Whole block only.
+// the fixed-up f (the unshifted u0 of a buoyant step): the next step's carry_in.  Whole block only (a part of a slab:
+// k_ade_open_ranges).
 template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
 __global__ __launch_bounds__(256) void k_ade_open(double* __restrict__ fn, double* __restrict__ gn,
                                                   const double* __restrict__ fo, const double* __restrict__ go, Geom g,
@@ -816,6 +817,85 @@ __global__ __launch_bounds__(256) void k_ade_open(double* __restrict__ fn, doubl
   }
   carry_out[2 * i] = u0r;
   carry_out[2 * i + 1] = u0c;
+  if (WITH_MOMENTS) {
+    const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
+    rho_out[oo] = rho;
+    u_out[oo] = ux;
+    u_out[nn + oo] = uy;
+    c_out[oo] = conc;
+  }
+}
+
+// A g source of a slab VIEW of the table (lbm_ade_open_slab): (row + 1) C + column with the row in [-1, R] -- -1 and R are
+// the ghost rows of a slab, and wrap on a ghost = 0 geometry (wrap_row) exactly as the ordinary table's sources do
+__device__ __forceinline__ long ade_open_view_at(const Geom& g, int biased) {
+  return g.at(wrap_row(g, biased / g.C - 1), biased % g.C);
+}
+
+// ade_open_gather_scalar with a view's source decoding
+__device__ __forceinline__ void ade_open_view_gather_scalar(double (&h)[Q], double (&own)[Q], const double* __restrict__ go,
+                                                            const Geom& g, const Bc& bc, const AdeOpenNode& nd) {
+  const long om = ade_open_view_at(g, nd.gsrc[0]);
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    h[q] = go[q * g.plane + ade_open_view_at(g, nd.gsrc[q])];
+    own[q] = go[q * g.plane + om];
+  }
+  bc_fixups_own(h, own, g, bc, nd.r, nd.c);
+}
+
+// The open-boundary pass of a PART of a slab (lbm_ade_stream_collide_part_o): the per-node body of k_ade_open -- the same
+// template flags, the same order of gathers, rules and collisions; the f gather reads the ghost rows of a slab and the g
+// sources are the view's (ade_open_view_at) -- over two index ranges of the sorted view in ONE dispatch, the launch shape of
+// k_ade_iwalls_ranges: lane i < n0 takes node first0 + i, the other lanes node first1 + (i - n0), n lanes in all.  The carry
+// index is the node's index m in the view.  No lane is filtered by its row.  Reads the old lattices and carry_in only and
+// writes, of its own nodes only, fn, gn, the moments and carry_out.  (The body is repeated, not shared with k_ade_open: the
+// existing kernels stay instruction for instruction what they were -- profiles/ade_open_slabs.txt.)
+template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
+__global__ __launch_bounds__(256) void k_ade_open_ranges(double* __restrict__ fn, double* __restrict__ gn,
+                                                         const double* __restrict__ fo, const double* __restrict__ go,
+                                                         Geom g, Bc bc, FM fm, SM sm, double* __restrict__ rho_out,
+                                                         double* __restrict__ u_out, double* __restrict__ c_out,
+                                                         AdeWalls sw, AdeBuoyancy by,
+                                                         const AdeOpenNode* __restrict__ nodes,
+                                                         const AdeOpenSeg* __restrict__ segs, int first0, int n0,
+                                                         int first1, int n, const double* __restrict__ carry_in,
+                                                         double* __restrict__ carry_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int m = i < n0 ? first0 + i : first1 + (i - n0);
+  const AdeOpenNode nd = nodes[m];
+  const int r = nd.r, c = nd.c;
+  const long o = g.at(r, c);
+  double f[Q], h[Q], own[Q], rho, ux, uy, conc, u0r, u0c;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    f[q] = fo[q * g.plane + g.at(wrap_row(g, r - icx(q)), wrap_col(g, c - icy(q)))];
+    own[q] = fo[q * g.plane + o];
+  }
+  bc_fixups_own(f, own, g, bc, r, c);
+  ade_open_fluid(f, own, nd, segs, carry_in, m);
+  ade_open_view_gather_scalar(h, own, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, nd);
+  if (BUOYANT) {
+    ade_fluid_moments(f, rho, ux, uy);
+    u0r = ux, u0c = uy;
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
+    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+  } else {
+    fm.collide(f, rho, ux, uy);
+    u0r = ux, u0c = uy;
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
+    sm.collide(h, ux, uy, conc);
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    fn[q * g.plane + o] = f[q];
+    gn[q * g.plane + o] = h[q];
+  }
+  carry_out[2 * m] = u0r;
+  carry_out[2 * m + 1] = u0c;
   if (WITH_MOMENTS) {
     const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
     rho_out[oo] = rho;

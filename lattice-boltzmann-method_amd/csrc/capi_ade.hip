@@ -2,6 +2,7 @@
 // test/rectangle_sedimentation_test.cpp:88-247 in one fused pull step per node (ade.hpp), and the solver
 // context that runs the driver loop on one block.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <iterator>
@@ -52,6 +53,15 @@ struct lbm_ade_open {
   int n = 0;  // nodes uploaded
   lbm::AdeOpenNode* d_nodes = nullptr;
   lbm::AdeOpenSeg* d_segs = nullptr;
+  // A slab VIEW (lbm_ade_open_slab): the parent's nodes of rows [row0, row0 + R) at r - row0 and its segments; gsrc holds
+  // (row + 1) C + column with the row in [-1, R], pad the mask of the g sources the slab cannot reach (bit q), xn indices
+  // into the view.  first: the row index lbm_ade_open_finalize keeps (R + 1 entries), as lbm_ade_iwalls.first.
+  bool view = false;
+  int row0 = 0, R_parent = 0;
+  std::vector<int> first;
+  // the call configuration (edge modes, ghost rows, FIXED edges) the reach check has last passed with, + 1: a step loop
+  // checks the view's sources once, not once per call
+  mutable std::atomic<unsigned> reach_ok{0};
 };
 
 namespace lbm {
@@ -302,16 +312,52 @@ static bool ade_wall_replaces(const Bc& gbc, int R, int C, int r, int c, int q) 
   return c == 0 && bc_is_wall(gbc.col_lo) && icy(q) == 1;
 }
 
+// What a slab may reach, per call (only the call knows the slab's edges): the g source of slot q of a listed node of a
+// view is USABLE if it lies in an owned row, or in the ghost row of a side whose row edge is HALO (ghost = 0: in the
+// wrapped row of a PERIODIC side) -- and is not marked unreachable.  Every slot needs a usable source or must be one the
+// domain's wall gather replaces at the node (gbc: the scalar's gather modes); the node's own source gsrc[0] must be usable.
+static int ade_open_reach(const char* fn, const lbm_ade_open* t, const lbm_geom* g, const Bc& bc, const Bc& gbc, int fixed) {
+  const unsigned key = 1u + ((unsigned)bc.row_lo | (unsigned)bc.row_hi << 3 | (unsigned)bc.col_lo << 6 | (unsigned)bc.col_hi << 9 |
+                             (unsigned)(g->ghost > 0) << 12 | (unsigned)fixed << 13);
+  if (t->reach_ok.load(std::memory_order_relaxed) == key) return LBM_OK;
+  const int R = t->R, C = t->C;
+  const bool lo_ok = g->ghost > 0 ? bc.row_lo == LBM_EDGE_HALO : bc.row_lo == LBM_EDGE_PERIODIC;
+  const bool hi_ok = g->ghost > 0 ? bc.row_hi == LBM_EDGE_HALO : bc.row_hi == LBM_EDGE_PERIODIC;
+  for (const AdeOpenNode& nd : t->nodes)
+    for (int q = 0; q < Q; ++q) {
+      const int sr = nd.gsrc[q] / C - 1, sc = nd.gsrc[q] % C;
+      const bool unreachable = (nd.pad >> q) & 1;
+      if (!unreachable && ((sr >= 0 && sr < R) || (sr == -1 && lo_ok) || (sr == R && hi_ok))) continue;
+      if (q > 0 && ade_wall_replaces(gbc, R, C, nd.r, nd.c, q)) continue;
+      LBM_REQUIRE(!unreachable, "%s: open boundaries: node (%d, %d), g slot %d: its source lies more than one row outside "
+                  "the slab's rows (unreachable) and no domain wall replaces the slot there", fn, nd.r, nd.c, q);
+      LBM_REQUIRE(false, "%s: open boundaries: node (%d, %d), g slot %d: its source (%d, %d) lies in the ghost row of %s, "
+                  "whose edge mode is %s (%s holds the neighbour's rows) and no domain wall replaces the slot there", fn, nd.r,
+                  nd.c, q, sr, sc, sr < 0 ? "row_lo" : "row_hi", edge_name(sr < 0 ? bc.row_lo : bc.row_hi),
+                  g->ghost > 0 ? "only a HALO side" : "with ghost = 0 only a PERIODIC side");
+    }
+  t->reach_ok.store(key, std::memory_order_relaxed);
+  return LBM_OK;
+}
+
 // The open table (NULL allowed) against the call, on the host: finalized, built for the same R x C, and sharing no node
 // with the interior walls of the call -- but for a node the open table gives no rule and whose redirected g slots are all
 // slots a domain wall replaces there (gbc: the scalar's gather modes), which the interior-wall pass recomputes to the
 // same populations on its own.  An empty table is NULL's.
 static int ade_open_check(const char* fn, const lbm_ade_open* t, const lbm_geom* g, const Bc& gbc,
-                          const lbm_ade_iwalls* iwalls, const AdeOpenNode** nodes, const AdeOpenSeg** segs, int* n) {
+                          const lbm_ade_iwalls* iwalls, const AdeOpenNode** nodes, const AdeOpenSeg** segs, int* n,
+                          bool slab = false, const Bc* bc = nullptr, int fixed = 0) {
+  // the two kinds of table do not mix (before anything else: a wrong kind is named whatever state the table is in)
+  LBM_REQUIRE(slab || !t->view, "%s: open boundaries: the table is a slab view (lbm_ade_open_slab): "
+              "lbm_ade_stream_collide_part_o, lbm_ring_ade_collide_o and lbm_ring_ade_step_o take it", fn);
+  LBM_REQUIRE(!slab || t->view, "%s: open boundaries: the table is not a slab view: a slab takes lbm_ade_open_slab of the "
+              "global table (lbm_ade_collide_o and lbm_ade_stream_collide_o take an ordinary table)", fn);
   LBM_REQUIRE(t->finalized, "%s: open boundaries: the table is not finalized (lbm_ade_open_finalize)", fn);
   LBM_REQUIRE(g && t->R == g->R && t->C == g->C, "%s: open boundaries: the table is for a %d x %d lattice, the call for %d x %d",
               fn, t->R, t->C, g ? g->R : 0, g ? g->C : 0);
   if (t->n == 0) return LBM_OK;
+  if (t->view)
+    if (int rc = ade_open_reach(fn, t, g, *bc, gbc, fixed)) return rc;
   if (iwalls) {
     const int R = t->R, C = t->C;
     for (const auto& kv : iwalls->nodes) {
@@ -324,8 +370,9 @@ static int ade_open_check(const char* fn, const lbm_ade_open* t, const lbm_geom*
                   "%s: open boundaries: node (%d, %d) carries an open-boundary rule and is in the interior-wall table as well",
                   fn, r, c);
       for (int q = 0; q < Q; ++q) {
-        const long long plain = (long long)((r - icx(q) + R) % R) * C + (c - icy(q) + C) % C;
-        LBM_REQUIRE(it->gsrc[q] == plain || ade_wall_replaces(gbc, R, C, r, c, q),
+        // the plain pull source in the table's encoding (a view: the row unwrapped, in [-1, R], + 1)
+        const long long plain = (long long)(t->view ? r - icx(q) + 1 : (r - icx(q) + R) % R) * C + (c - icy(q) + C) % C;
+        LBM_REQUIRE((it->gsrc[q] == plain && !((it->pad >> q) & 1)) || ade_wall_replaces(gbc, R, C, r, c, q),
                     "%s: open boundaries: node (%d, %d) is in the interior-wall table and its g slot %d is redirected by a "
                     "copy with no domain wall replacing it there", fn, r, c, q);
       }
@@ -353,6 +400,9 @@ struct AdeCall {
   const AdeOpenNode* open_nodes;  // the open-boundary table (lbm_ade_open), NULL without nodes
   const AdeOpenSeg* open_segs;
   int n_open_nodes;
+  const int* open_first;   // host: a slab view's row index (R + 1 entries), NULL without nodes or on a single block
+  const double* carry_in;  // the carry of a slab's call (ade_carry_set); the single-block entries pass theirs by argument
+  double* carry_out;
 };
 static_assert(sizeof(AdeCall) <= sizeof(AdeCallBuf) && alignof(AdeCall) <= alignof(AdeCallBuf) &&
               std::is_trivially_copyable<AdeCall>::value, "AdeCallBuf (internal.hpp) holds an AdeCall");
@@ -374,10 +424,14 @@ int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm
   call->open_nodes = nullptr;
   call->open_segs = nullptr;
   call->n_open_nodes = 0;
+  call->open_first = nullptr;
+  call->carry_in = nullptr;
+  call->carry_out = nullptr;
   if (!open) return LBM_OK;
-  LBM_REQUIRE(!slab, "%s: open boundaries: a slab takes no open table (single block only)", fn);
-  return ade_open_check(fn, open, lg, ade_scalar_gather_bc(call->bc, call->sw.fixed), call->n_wall_nodes > 0 ? iwalls : nullptr,
-                        &call->open_nodes, &call->open_segs, &call->n_open_nodes);
+  rc = ade_open_check(fn, open, lg, ade_scalar_gather_bc(call->bc, call->sw.fixed), call->n_wall_nodes > 0 ? iwalls : nullptr,
+                      &call->open_nodes, &call->open_segs, &call->n_open_nodes, slab, &call->bc, call->sw.fixed);
+  if (!rc && slab && call->n_open_nodes > 0) call->open_first = open->first.data();
+  return rc;
 }
 
 template <bool B, class FM, class SM>
@@ -443,6 +497,10 @@ static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
   return LBM_OK;
 }
 
+// kernels the part launches of this process have enqueued (lbm_ade_part_launches): what "a NULL view adds no launch" is
+// tested with, there being no solver context for slabs to count them
+static std::atomic<long long> g_part_launches{0};
+
 // one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline
 template <bool B, class FM, class SM>
 static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
@@ -459,6 +517,22 @@ static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
                 k.g, k.bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, k.sw, k.by);
   }, nt & 1, nt & 2, mom, k.sw.fixed);
   LBM_CHECK_LAUNCH();
+  g_part_launches.fetch_add(1, std::memory_order_relaxed);
+  if (k.n_open_nodes > 0) {
+    // the view's nodes of the part's rows, behind the dispatch whose nodes they overwrite and before the interior-wall
+    // pass, on the same stream: two index ranges of the sorted view, as below; a part without a listed node enqueues nothing
+    const int* first = k.open_first;
+    const int first0 = first[band0], w0 = first[band0 + n0] - first0;
+    const int first1 = first[band1], w = w0 + (n0 < nrows ? first[band1 + nrows - n0] - first1 : 0);
+    if (w > 0) {
+      with_flags([&](auto M, auto F) {
+        LBM_KLAUNCH((k_ade_open_ranges<FM, SM, M(), F(), B>), dim3((w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc,
+                    fm, sm, rho, u, conc, k.sw, k.by, k.open_nodes, k.open_segs, first0, w0, first1, w, k.carry_in, k.carry_out);
+      }, mom, k.sw.fixed);
+      LBM_CHECK_LAUNCH();
+      g_part_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+  }
   if (k.n_wall_nodes == 0) return LBM_OK;
   // the table's nodes of the part's rows, behind the dispatch whose nodes they overwrite, on the same stream: the two
   // bands are two index ranges of the sorted table (one when n0 == nrows); a part without a table node enqueues nothing
@@ -471,6 +545,7 @@ static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
                 fm, sm, rho, u, conc, k.sw, k.by, k.wall_nodes, first0, w0, first1, w);
   }, mom, k.sw.fixed);
   LBM_CHECK_LAUNCH();
+  g_part_launches.fetch_add(1, std::memory_order_relaxed);
   return LBM_OK;
 }
 
@@ -490,6 +565,23 @@ static int ade_carry_args(const char* fn, const AdeCall& k, bool reads, const do
   LBM_REQUIRE((!reads || carry_in) && carry_out, "%s: open boundaries: NULL carry with a table of %d nodes (%d doubles each)",
               fn, k.n_open_nodes, 2 * k.n_open_nodes);
   LBM_REQUIRE(!reads || carry_in != carry_out, "%s: open boundaries: carry_in and carry_out alias", fn);
+  return LBM_OK;
+}
+
+// the carry of a slab's call, checked and kept in the call for its launches
+int ade_carry_set(const char* fn, AdeCall* k, bool reads, const double* carry_in, double* carry_out) {
+  if (int rc = ade_carry_args(fn, *k, reads, carry_in, carry_out)) return rc;
+  k->carry_in = carry_in;
+  k->carry_out = carry_out;
+  return LBM_OK;
+}
+
+// the carry of a pre-collision state on a slab: k_ade_open_prime over the call's view (it addresses through Geom::at)
+int ade_open_prime_from(const AdeCall& k, const double* f, hipStream_t st) {
+  if (k.n_open_nodes == 0) return LBM_OK;
+  LBM_KLAUNCH(k_ade_open_prime, dim3((k.n_open_nodes + 255) / 256), dim3(256), 0, st, f, k.g, k.open_nodes, k.n_open_nodes,
+              k.carry_out);
+  LBM_CHECK_LAUNCH();
   return LBM_OK;
 }
 
@@ -563,10 +655,12 @@ int ade_part_from(const AdeCall& k, double* fn, double* gn, const double* fo, co
 static int ade_part(const char* name, double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                     const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                     const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int part,
-                    int edge_rows, double* rho, double* u, double* conc, hipStream_t st) {
+                    int edge_rows, double* rho, double* u, double* conc, hipStream_t st,
+                    const lbm_ade_open* view = nullptr, const double* carry_in = nullptr, double* carry_out = nullptr) {
   AdeCall k;
-  int rc = ade_resolve(name, lg, lbc, fluid, scalar, sbc, buoy, iwalls, true, &k);
+  int rc = ade_resolve(name, lg, lbc, fluid, scalar, sbc, buoy, iwalls, true, &k, view);
   if (!rc) rc = ade_part_args(name, k, fn, gn, fo, go, part, edge_rows, rho, u, conc);
+  if (!rc) rc = ade_carry_set(name, &k, true, carry_in, carry_out);
   return rc ? rc : ade_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
 }
 
@@ -1086,6 +1180,8 @@ int lbm_ade_open_create(lbm_ade_open** out, int R, int C) {
 // the checks every kind of segment shares; r0 / c0 come back counted from the start
 static int ade_open_segment(const char* fn, lbm_ade_open* t, int* r0, int* c0, int dr, int dc, int n) {
   LBM_REQUIRE(t, "%s: NULL table", fn);
+  LBM_REQUIRE(!t->view, "%s: the table is a slab view (lbm_ade_open_slab): it takes no segments -- add them to the global "
+              "table and take the view after", fn);
   LBM_REQUIRE(!t->finalized, "%s: the table is finalized (immutable after lbm_ade_open_finalize)", fn);
   LBM_REQUIRE(t->segs.size() < 255, "%s: the table holds 255 segments already", fn);
   LBM_REQUIRE(n >= 1, "%s: n=%d must be at least 1", fn, n);
@@ -1156,6 +1252,8 @@ int lbm_ade_open_add_g_copy(lbm_ade_open* t, int r0, int c0, int dr, int dc, int
 int lbm_ade_open_add_channel(lbm_ade_open* t, double u_in, double conc_w, int conc_rows) {
   const char* fn = "lbm_ade_open_add_channel";
   LBM_REQUIRE(t, "%s: NULL table", fn);
+  LBM_REQUIRE(!t->view, "%s: the table is a slab view (lbm_ade_open_slab): it takes no segments -- add them to the global "
+              "table and take the view after", fn);
   LBM_REQUIRE(!t->finalized, "%s: the table is finalized (immutable after lbm_ade_open_finalize)", fn);
   const int R = t->R, C = t->C;
   LBM_REQUIRE(R >= 3 && C >= 2, "%s: R=%d C=%d: the channel needs R >= 3 and C >= 2", fn, R, C);
@@ -1194,10 +1292,15 @@ int lbm_ade_open_node(const lbm_ade_open* t, int i, int* r, int* c, int* f_rule,
     if (g_rule) g_rule[s - 1] = jg ? 1 + t->segs[(size_t)jg - 1].rule : 0;
   }
   for (int q = 0; q < Q; ++q) {
-    if (g_src_r) g_src_r[q] = nd.gsrc[q] / t->C;
+    if (g_src_r) g_src_r[q] = nd.gsrc[q] / t->C - (t->view ? 1 : 0);  // a view: in [-1, R]
     if (g_src_c) g_src_c[q] = nd.gsrc[q] % t->C;
   }
   return LBM_OK;
+}
+
+int lbm_ade_open_unreachable(const lbm_ade_open* t, int i) {
+  if (!t || i < 0 || i >= (int)t->nodes.size()) return 0;
+  return t->view ? t->nodes[(size_t)i].pad : 0;
 }
 
 int lbm_ade_open_finalize(lbm_ade_open* t) {
@@ -1220,8 +1323,72 @@ int lbm_ade_open_finalize(lbm_ade_open* t) {
       return LBM_ERR_HIP;
     }
     t->n = (int)t->nodes.size();
+    if (t->view) {  // the row index: node counts per row, then their running sum
+      t->first.assign((size_t)t->R + 1, 0);
+      for (const AdeOpenNode& nd : t->nodes) ++t->first[(size_t)nd.r + 1];
+      for (int r = 0; r < t->R; ++r) t->first[(size_t)r + 1] += t->first[r];
+    }
   }
   t->finalized = true;
+  return LBM_OK;
+}
+
+int lbm_ade_open_slab(lbm_ade_open** out, const lbm_ade_open* table, int row0, int R) {
+  const char* fn = "lbm_ade_open_slab";
+  LBM_REQUIRE(out && table, "%s: NULL argument", fn);
+  LBM_REQUIRE(!table->view, "%s: the table is itself a slab view: views are taken of the global table", fn);
+  LBM_REQUIRE(row0 >= 0, "%s: row0=%d must not be negative", fn, row0);
+  LBM_REQUIRE(R >= 1, "%s: R=%d must be at least 1", fn, R);
+  LBM_REQUIRE((long long)row0 + R <= table->R, "%s: rows [%d, %lld) beyond the %d rows of the table", fn, row0,
+              (long long)row0 + R, table->R);
+  const int C = table->C, Rg = table->R;
+  LBM_REQUIRE(((long long)R + 2) * C < (1LL << 31), "%s: R=%d C=%d: (R + 2) x C exceeds 2^31 - 1 (the view's source encoding)",
+              fn, R, C);
+  // the parent's nodes are sorted by (r, c): the rows of the view are one range [i0, i1) of them
+  auto row_begin = [table](int r) {
+    return (int)(std::lower_bound(table->nodes.begin(), table->nodes.end(), r,
+                                  [](const AdeOpenNode& a, int b) { return a.r < b; }) - table->nodes.begin());
+  };
+  const int i0 = row_begin(row0), i1 = row_begin(row0 + R);
+  std::vector<AdeOpenNode> nodes(table->nodes.begin() + i0, table->nodes.begin() + i1);
+  for (AdeOpenNode& nd : nodes) {
+    const int rg = nd.r;
+    nd.r -= row0;
+    nd.pad = 0;
+    for (int q = 0; q < Q; ++q) {
+      // the source's global row modulo the parent's rows, as the slab-local row in [-1, R] nearest to the plain pull
+      const int sr = nd.gsrc[q] / C, pull = nd.r - icx(q);
+      int sc = nd.gsrc[q] % C, best = 0;
+      bool found = false;
+      for (int cand : {sr - row0 - Rg, sr - row0, sr - row0 + Rg})
+        if (cand >= -1 && cand <= R && (!found || std::abs(cand - pull) < std::abs(best - pull))) best = cand, found = true;
+      if (!found) {  // more than one row outside the slab: the plain pull source, marked unreachable
+        nd.pad |= 1 << q;
+        best = pull;
+        sc = (nd.c - icy(q) + C) % C;
+      }
+      nd.gsrc[q] = (best + 1) * C + sc;
+    }
+    for (int s = 1; s < Q; ++s) {
+      const int j = (int)((nd.fseg[(s - 1) >> 2] >> (8 * ((s - 1) & 3))) & 0xFFu);
+      if (!j || table->segs[(size_t)j - 1].rule != LBM_ADE_OPEN_ABB_EXTRAPOLATED) continue;
+      const int m = nd.xn[s - 1];
+      LBM_REQUIRE(m >= i0 && m < i1, "%s: node (%d, %d), f slot %d: its extrapolation neighbour (%d, %d) lies outside rows "
+                  "[%d, %d) of the view (the carry is slab-local: no carry exchange between slabs)", fn, rg, nd.c, s,
+                  table->nodes[(size_t)m].r, table->nodes[(size_t)m].c, row0, row0 + R);
+      nd.xn[s - 1] = m - i0;
+    }
+  }
+  lbm_ade_open* t = new (std::nothrow) lbm_ade_open();
+  LBM_REQUIRE(t, "%s: out of host memory", fn);
+  t->R = R;
+  t->C = C;
+  t->segs = table->segs;
+  t->nodes = std::move(nodes);
+  t->view = true;
+  t->row0 = row0;
+  t->R_parent = Rg;
+  *out = t;
   return LBM_OK;
 }
 
@@ -1250,11 +1417,24 @@ int lbm_ade_stream_collide_o(double* fn, double* gn, const double* fo, const dou
                             row_end, rho, u, conc, as_stream(s), nullptr, open, carry_in, carry_out);
 }
 
+int lbm_ade_stream_collide_part_o(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
+                                  const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                                  const lbm_ade_open* view, const double* carry_in, double* carry_out, int part,
+                                  int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
+  return ade_part("lbm_ade_stream_collide_part_o", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, buoy, iwalls, part,
+                  edge_rows, rho, u, conc, as_stream(s), view, carry_in, carry_out);
+}
+
+long long lbm_ade_part_launches(void) { return g_part_launches.load(std::memory_order_relaxed); }
+
 int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open) {
   const char* fn = "lbm_ade_solver_set_open";
   LBM_REQUIRE(sv, "%s: NULL solver", fn);
   if (open == sv->open) return LBM_OK;
   if (open) {
+    LBM_REQUIRE(!open->view, "%s: open boundaries: the table is a slab view (lbm_ade_open_slab): the context runs a single "
+                "block and takes the global table", fn);
     LBM_REQUIRE(open->finalized, "%s: open boundaries: the table is not finalized (lbm_ade_open_finalize)", fn);
     LBM_REQUIRE(open->R == sv->g.R && open->C == sv->g.C, "%s: open boundaries: the table is for a %d x %d lattice, the call for %d x %d",
                 fn, open->R, open->C, sv->g.R, sv->g.C);

@@ -314,7 +314,7 @@ static int ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm
 // that edge (a chain end) and is dropped at a seam, as the fluid's row wall is.
 static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, const lbm_bgk_params* fluid,
                             const lbm_ade_params* scalar, const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy,
-                            const lbm_ade_iwalls* iwalls, AdeCall* call) {
+                            const lbm_ade_iwalls* iwalls, AdeCall* call, const lbm_ade_open* view = nullptr) {
   LBM_REQUIRE(rg->g.ghost == 1, "%s: ghost=%d: the fluid + scalar step over slabs exchanges one ghost row per side (ring "
               "slabs need ghost=1)", fn, rg->g.ghost);
   const lbm_bc b = ring_slab_bc(rg, bc);
@@ -325,25 +325,32 @@ static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, cons
     if (b.row_lo == LBM_EDGE_HALO) sb.mode[0] = LBM_ADE_SCALAR_NO_FLUX;
     if (b.row_hi == LBM_EDGE_HALO) sb.mode[1] = LBM_ADE_SCALAR_NO_FLUX;
   }
-  return ade_resolve(fn, &rg->g, &b, fluid, scalar, gsbc ? &sb : nullptr, buoy, iwalls, true, call);
+  return ade_resolve(fn, &rg->g, &b, fluid, scalar, gsbc ? &sb : nullptr, buoy, iwalls, true, call, view);
 }
 
 // FRAME (both edge bands, one dispatch) + pack + one message per neighbour on the ring's stream, INNER on `main` beside
 // them -- the schedule of lbm_ring_bgk_step at n_steps = 1, with LBM_ADE_PART_* as the two launches of one resolved call.
 // iwalls (this slab's table, NULL allowed): each part enqueues the wall pass of its rows behind its own dispatch
 // (ade_part_from), so FRAME's runs inside `edges`, before the pack, and INNER's on `main`.
+// view (this slab's view of the open table, NULL allowed) with its carry: the open pass of each part likewise, behind the
+// part's dispatch and before its interior-wall pass.  The carry has the dependencies of the lattices -- written by the pass
+// that writes the node, read one step later by a pass that reads that node's old populations -- and ring_step's fork (the
+// ring's stream starts after everything on `main`) and join (`main` waits for the ring's stream) order both: nothing more
+// is synchronised here.
 static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go,
                          const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                          const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
-                         int edge_rows, lbm_stream_t main_s) {
+                         int edge_rows, lbm_stream_t main_s, const lbm_ade_open* view = nullptr,
+                         const double* carry_in = nullptr, double* carry_out = nullptr) {
   int rc = ade_buoyancy_check(fn, buoy);  // needs no ring
   if (rc) return rc;
   LBM_REQUIRE(rg && fn_ && gn && fo && go && fluid && scalar, "%s: NULL argument", fn);
   AdeCallBuf buf;
   const AdeCall& call = *buf.get();
   if (edge_rows < 1) edge_rows = 1;
-  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, iwalls, buf.get());
+  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, iwalls, buf.get(), view);
   if (!rc) rc = ade_part_args(fn, call, fn_, gn, fo, go, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr, nullptr);
+  if (!rc) rc = ade_carry_set(fn, buf.get(), true, carry_in, carry_out);
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
   auto part = [&](int which, hipStream_t st) {
@@ -631,15 +638,18 @@ int lbm_ring_cg_step(lbm_ring* rg, double* dst_r, double* dst_b, const double* s
 // lbm_ring_ade_collide(_b) under the caller's name; the scalar's walls are checked only (collide-only applies no wall rule)
 static int ring_ade_collide(const char* fn, lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in,
                             const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
-                            const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, lbm_stream_t main_s) {
+                            const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, lbm_stream_t main_s,
+                            const lbm_ade_open* view = nullptr, double* carry_out = nullptr) {
   int rc = ade_buoyancy_check(fn, buoy);  // needs no ring
   if (rc) return rc;
   LBM_REQUIRE(rg && fp && gp && f && g_in && fluid && scalar, "%s: NULL argument", fn);
   AdeCallBuf buf;
-  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, nullptr, buf.get());
+  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, nullptr, buf.get(), view);
+  if (!rc) rc = ade_carry_set(fn, buf.get(), false, nullptr, carry_out);
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
   rc = ade_collide_from(fn, *buf.get(), fp, gp, f, g_in, nullptr, nullptr, nullptr, main);
+  if (!rc) rc = ade_open_prime_from(*buf.get(), f, main);  // the carry of the pre-collision state: what the first step reads
   if (rc || (rg->prev < 0 && rg->next < 0)) return rc;
   return ring_join(rg, main, ring_exchange_depth(rg, fp, gp, 1, main));
 }
@@ -676,6 +686,20 @@ int lbm_ring_ade_step_w(lbm_ring* rg, double* fn_, double* gn, const double* fo,
                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main_s) {
   return ring_ade_step("lbm_ring_ade_step_w", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, iwalls, edge_rows, main_s);
+}
+
+int lbm_ring_ade_collide_o(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                           const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                           const lbm_ade_buoyancy* buoy, const lbm_ade_open* view, double* carry_out, lbm_stream_t main_s) {
+  return ring_ade_collide("lbm_ring_ade_collide_o", rg, fp, gp, f, g_in, bc, fluid, scalar, sbc, buoy, main_s, view, carry_out);
+}
+
+int lbm_ring_ade_step_o(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                        const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                        const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, const lbm_ade_open* view,
+                        const double* carry_in, double* carry_out, int edge_rows, lbm_stream_t main_s) {
+  return ring_ade_step("lbm_ring_ade_step_o", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, iwalls, edge_rows, main_s,
+                       view, carry_in, carry_out);
 }
 
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after) {

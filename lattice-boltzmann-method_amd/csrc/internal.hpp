@@ -59,7 +59,8 @@ struct AdeCallBuf {
   AdeCall* get() { return reinterpret_cast<AdeCall*>(bytes); }
 };
 // the host checks, once, under the caller's name fn (slab: ghost rows and HALO row edges allowed; sbc, buoy, iwalls may be
-// NULL), and the two of them that need no geometry on their own (sw, by: the device copy, if wanted)
+// NULL; open: on a slab a view of the global table, lbm_ade_open_slab, on a single block an ordinary table), and the two of
+// them that need no geometry on their own (sw, by: the device copy, if wanted)
 int ade_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
                 const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
                 const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call, const lbm_ade_open* open = nullptr);
@@ -74,6 +75,12 @@ int ade_part_from(const AdeCall& call, double* f_new, double* g_new, const doubl
                   int edge_rows, double* rho, double* u, double* conc, hipStream_t st);
 int ade_collide_from(const char* fn, const AdeCall& call, double* fp, double* gp, const double* f, const double* h,
                      double* rho, double* u, double* conc, hipStream_t st);
+// a slab's open table (ade_resolve's `open`: a view, lbm_ade_open_slab): the carry of the call, checked (both given with a
+// non-empty view -- carry_in where the call reads one -- and distinct) and kept in the call for ade_part_from, which
+// enqueues the open pass of the part's rows behind its dispatch and before the interior-wall pass; and the carry of a
+// pre-collision state f, written to the call's carry_out (one small launch; none without a listed node)
+int ade_carry_set(const char* fn, AdeCall* call, bool reads, const double* carry_in, double* carry_out);
+int ade_open_prime_from(const AdeCall& call, const double* f, hipStream_t st);
 // NumPy .npy (v1.0, little-endian f64, C order) writer shared by the snapshot objects
 int write_npy(const char* path, const double* data, const std::vector<long>& shape);
 

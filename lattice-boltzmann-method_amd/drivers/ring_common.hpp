@@ -290,6 +290,23 @@ inline int mismatching_planes(const std::vector<double>& one_block, int Rg, cons
     if (std::memcmp(&slab[(size_t)q * R * C], &one_block[(size_t)q * Rg * C + (size_t)row0 * C], (size_t)R * C * 8) != 0) ++bad;
   return bad;
 }
+// a device array of n doubles, zeroed (NULL for n = 0), and its copy on the host: the carry of an open table, which --check
+// compares beside the lattices
+inline double* alloc_doubles(size_t n) {
+  if (n == 0) return nullptr;
+  double* d = nullptr;
+  check(lbm_malloc((void**)&d, n * 8), "lbm_malloc");
+  check(lbm_memset(d, 0, n * 8, nullptr), "lbm_memset");
+  return d;
+}
+inline std::vector<double> doubles_to_host(const double* d, size_t n) {
+  std::vector<double> h(n);
+  if (n) check(lbm_memcpy_d2h(h.data(), d, n * 8, nullptr), "lbm_memcpy_d2h");
+  check(lbm_stream_sync(nullptr), "sync");
+  return h;
+}
+// true if the two arrays differ in any bit
+inline bool mismatching_doubles(const double* a, const double* b, size_t n) { return n && std::memcmp(a, b, n * 8) != 0; }
 // the tail of a driver's JSON line
 inline const char* check_field(int check, int bad) {
   return !check ? "" : (bad ? ", \"check\": \"MISMATCH\"" : ", \"check\": \"bitwise equal to one block\"");

@@ -1,7 +1,7 @@
 // Fluid + transported scalar (lbm_ade_*, the sediment loop of test/rectangle_sedimentation_test.cpp:88-247 without its
 // driver-specific edges) slab-decomposed along r: one ghost row per side, ONE packed message per neighbour per step
 // carrying the single-step halo of both lattices (2 x 3 rows), FRAME + pack + exchange on the ring's stream beside the
-// INNER rows (lbm_ring_ade_step_w).  C++ host on lbm_ring_* + lbm_ade_stream_collide_part_w; one process per GPU.
+// INNER rows (lbm_ring_ade_step_w / _o).  C++ host on lbm_ring_* + lbm_ade_stream_collide_part_w / _o; one process per GPU.
 //
 //   slab_ring_ade --spawn N [...]          fork N ranks on this node (rank i -> GPU i; --one-gpu 1: all on GPU 0,
 //                                          with --transport ipc: N real ranks sharing one device)
@@ -23,6 +23,12 @@
 //          the GLOBAL box, ceiling Rg/3 above the last row, columns 2C/8 .. 5C/16, absorbing (FIXED at 0).  One global
 //          table per process; each slab or rank takes its view, lbm_ade_iwalls_slab; --check's one block runs
 //          lbm_ade_stream_collide_w with the global table)
+//          --channel 1 (with --walls 1: open boundaries, lbm_ade_open -- the sedimentation channel of
+//          lbm_ade_open_add_channel on the GLOBAL box, u_in = 0.03, C_w = 1e-3 on the last quarter of the inlet's rows; the
+//          columns become PERIODIC edges that the inlet and outlet replace, the rows stay the chain's walls.  One global
+//          table per process; each slab or rank takes its view, lbm_ade_open_slab, and owns its carry; the _o entry points.
+//          Combines with --rectangle 1 and --buoyancy; --check's one block runs lbm_ade_collide_o / lbm_ade_stream_collide_o
+//          with the global tables and compares the carry as well)
 //
 // Printed: one JSON line; ms per step of the slowest slab, and the one-block step of a slab-sized lattice beside it.
 //
@@ -35,7 +41,7 @@
 namespace {
 
 struct Args : RingOpts {
-  int walls = 0, scalar_fixed = 0, rectangle = 0;
+  int walls = 0, scalar_fixed = 0, rectangle = 0, channel = 0;
   double omega = 1.2, omega_g = 1.7;
   bool fast = true;
   bool buoyant = false;
@@ -80,8 +86,8 @@ lbm_bc global_bc(const Args& a) {
   lbm_bc b{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
   if (a.walls) {
     b.row_lo = b.row_hi = LBM_EDGE_BOUNCE_BACK;
-    b.col_lo = LBM_EDGE_BOUNCE_BACK;
-    b.col_hi = LBM_EDGE_SPECULAR;
+    b.col_lo = a.channel ? LBM_EDGE_PERIODIC : LBM_EDGE_BOUNCE_BACK;  // --channel: the inlet and the outlet are the table's
+    b.col_hi = a.channel ? LBM_EDGE_PERIODIC : LBM_EDGE_SPECULAR;
   }
   return b;
 }
@@ -135,6 +141,25 @@ lbm_ade_iwalls* slab_view(const lbm_ade_iwalls* global, int row0, int R) {
   return v;
 }
 
+// --channel: the open table of the global box, finalized (the one block of --check and the emulation's first iteration run
+// it); NULL without the flag
+lbm_ade_open* channel_table(const Args& a, int Rg) {
+  if (!a.channel) return nullptr;
+  lbm_ade_open* t = nullptr;
+  check(lbm_ade_open_create(&t, Rg, a.cols), "lbm_ade_open_create");
+  check(lbm_ade_open_add_channel(t, 0.03, 1e-3, Rg / 4), "lbm_ade_open_add_channel");
+  check(lbm_ade_open_finalize(t), "lbm_ade_open_finalize");
+  return t;
+}
+// the finalized view of rows [row0, row0 + R) of the global open table; NULL for NULL
+lbm_ade_open* open_view(const lbm_ade_open* global, int row0, int R) {
+  if (!global) return nullptr;
+  lbm_ade_open* v = nullptr;
+  check(lbm_ade_open_slab(&v, global, row0, R), "lbm_ade_open_slab");
+  check(lbm_ade_open_finalize(v), "lbm_ade_open_finalize");
+  return v;
+}
+
 // pre-collision f, g of global rows [row0, row0 + R) into lattices of geometry g (owned rows; the rest zero)
 void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
   const int R = g.R, C = g.C;
@@ -162,8 +187,10 @@ void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
 
 // One block of Rg x C (ghost 0, dense), collide-only + `steps` fused steps: the yardstick of --check.  Returns f, g of
 // the owned rows as dense [9][Rg][C] on the host.
+// With an open table (--channel) the _o entry points run it and its carry comes back as well (the table's order).
 void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_params& sc, lbm_ade_iwalls* walls,
-               std::vector<double>& f_out, std::vector<double>& g_out) {
+               std::vector<double>& f_out, std::vector<double>& g_out, const lbm_ade_open* open = nullptr,
+               std::vector<double>* carry_out = nullptr) {
   if (walls) check(lbm_ade_iwalls_finalize(walls), "lbm_ade_iwalls_finalize");  // the global table: this is its one use on the device
   const lbm_geom g{Rg, a.cols, 0, 0, 0};
   const lbm_bc bc = global_bc(a);
@@ -171,13 +198,25 @@ void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_pa
   double* prof = scalar_profile(a, Rg);
   const lbm_ade_scalar_bc sbc = scalar_bc(prof, 0, bc);
   upload_rows(f[0], h[0], g, 0, Rg);
-  check(lbm_ade_collide_b(f[1], h[1], f[0], h[0], &g, &bc, &fl, &sc, nullptr, a.buoyancy(), nullptr, nullptr, nullptr,
-                          nullptr), "lbm_ade_collide_b");
+  double* carry[2] = {alloc_doubles((size_t)lbm_ade_open_carry_len(open)), alloc_doubles((size_t)lbm_ade_open_carry_len(open))};
+  if (open)
+    check(lbm_ade_collide_o(f[1], h[1], f[0], h[0], &g, &bc, &fl, &sc, nullptr, a.buoyancy(), open, carry[1], nullptr, nullptr,
+                            nullptr, nullptr), "lbm_ade_collide_o");
+  else
+    check(lbm_ade_collide_b(f[1], h[1], f[0], h[0], &g, &bc, &fl, &sc, nullptr, a.buoyancy(), nullptr, nullptr, nullptr,
+                            nullptr), "lbm_ade_collide_b");
   int cur = 1;
   for (int t = 0; t < a.warmup + a.steps; ++t, cur ^= 1)
-    check(lbm_ade_stream_collide_w(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr,
-                                   a.buoyancy(), walls, 0, Rg, nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_w");
+    if (open)
+      check(lbm_ade_stream_collide_o(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr,
+                                     a.buoyancy(), walls, open, carry[cur], carry[cur ^ 1], 0, Rg, nullptr, nullptr, nullptr,
+                                     nullptr), "lbm_ade_stream_collide_o");
+    else
+      check(lbm_ade_stream_collide_w(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr,
+                                     a.buoyancy(), walls, 0, Rg, nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_w");
   if (prof) lbm_free(prof);
+  if (carry_out) *carry_out = doubles_to_host(carry[cur], (size_t)lbm_ade_open_carry_len(open));
+  for (double* c : carry) lbm_free(c);
   f_out = owned_to_host(f[cur], g);
   g_out = owned_to_host(h[cur], g);
   for (int k = 0; k < 2; ++k) {
@@ -237,10 +276,13 @@ int run_emulated(const Args& a, int N) {
   const size_t msg = (size_t)lbm_halo_rows(1) * C;  // per lattice
   double* prof = scalar_profile(a, Rg);
   lbm_ade_iwalls* table = rectangle_table(a, Rg);
+  lbm_ade_open* channel = channel_table(a, Rg);
   struct Slab {
     lbm_bc bc;
     lbm_ade_scalar_bc sbc;
     lbm_ade_iwalls* walls;
+    lbm_ade_open* open;  // the slab's view of the channel and its two carries (carry[k] goes with f[k], h[k])
+    double* carry[2];
     double *f[2], *h[2];
   };
   std::vector<Slab> S(N);
@@ -250,8 +292,14 @@ int run_emulated(const Args& a, int N) {
     const lbm_geom gg{Rg, C, 0, 0, 0};
     double *f0 = alloc_lattice(gg), *h0 = alloc_lattice(gg), *fp = alloc_lattice(gg), *hp = alloc_lattice(gg);
     upload_rows(f0, h0, gg, 0, Rg);
-    check(lbm_ade_collide_b(fp, hp, f0, h0, &gg, &gbc, &fl, &sc, nullptr, a.buoyancy(), nullptr, nullptr, nullptr, nullptr),
-          "lbm_ade_collide_b");
+    double* carry0 = alloc_doubles((size_t)lbm_ade_open_carry_len(channel));  // of the global table: a view's is a slice of it
+    if (channel)
+      check(lbm_ade_collide_o(fp, hp, f0, h0, &gg, &gbc, &fl, &sc, nullptr, a.buoyancy(), channel, carry0, nullptr, nullptr,
+                              nullptr, nullptr), "lbm_ade_collide_o");
+    else
+      check(lbm_ade_collide_b(fp, hp, f0, h0, &gg, &gbc, &fl, &sc, nullptr, a.buoyancy(), nullptr, nullptr, nullptr, nullptr),
+            "lbm_ade_collide_b");
+    size_t first = 0;  // the views partition the table in its order
     for (int k = 0; k < N; ++k) {
       Slab& s = S[k];
       s.bc = gbc;
@@ -259,6 +307,11 @@ int run_emulated(const Args& a, int N) {
       if (links.next(k)) s.bc.row_hi = LBM_EDGE_HALO;
       s.sbc = scalar_bc(prof, k * R, s.bc);
       s.walls = slab_view(table, k * R, R);
+      s.open = open_view(channel, k * R, R);
+      const size_t len = (size_t)lbm_ade_open_carry_len(s.open);
+      for (int b = 0; b < 2; ++b) s.carry[b] = alloc_doubles(len);
+      if (len) check(lbm_memcpy_d2d(s.carry[0], carry0 + first, len * 8, nullptr), "lbm_memcpy_d2d");
+      first += len;
       for (int b = 0; b < 2; ++b) {
         s.f[b] = alloc_lattice(g);
         s.h[b] = alloc_lattice(g);
@@ -275,11 +328,17 @@ int run_emulated(const Args& a, int N) {
       }
     }
     check(lbm_stream_sync(nullptr), "sync");
-    for (double* p : {f0, h0, fp, hp}) lbm_free(p);
+    for (double* p : {f0, h0, fp, hp, carry0}) lbm_free(p);
   }
   EdgeStream es;
   SlabSizedBlock block(R, C);
   auto part = [&](Slab& s, int cur, int which, lbm_stream_t st) {
+    if (s.open) {
+      check(lbm_ade_stream_collide_part_o(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
+                                          prof ? &s.sbc : nullptr, a.buoyancy(), s.walls, s.open, s.carry[cur], s.carry[cur ^ 1],
+                                          which, E, nullptr, nullptr, nullptr, st), "lbm_ade_stream_collide_part_o");
+      return;
+    }
     check(lbm_ade_stream_collide_part_w(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
                                         prof ? &s.sbc : nullptr, a.buoyancy(), s.walls, which, E, nullptr, nullptr, nullptr,
                                         st), "lbm_ade_stream_collide_part_w");
@@ -325,11 +384,16 @@ int run_emulated(const Args& a, int N) {
   if (prof) lbm_free(prof);
   int bad = 0;
   if (a.check) {
-    std::vector<double> want[2];
-    one_block(a, Rg, fl, sc, table, want[0], want[1]);
-    for (int k = 0; k < N; ++k)
+    std::vector<double> want[2], want_carry;
+    one_block(a, Rg, fl, sc, table, want[0], want[1], channel, &want_carry);
+    size_t first = 0;
+    for (int k = 0; k < N; ++k) {
       for (int lat = 0; lat < 2; ++lat)
         bad += mismatching_planes(want[lat], Rg, owned_to_host(lat ? S[k].h[cur] : S[k].f[cur], g), R, k * R, C);
+      const size_t len = (size_t)lbm_ade_open_carry_len(S[k].open);
+      bad += mismatching_doubles(want_carry.data() + first, doubles_to_host(S[k].carry[cur], len).data(), len) ? 1 : 0;
+      first += len;
+    }
   }
   const double slowest = links.slowest_ms() / a.steps, blk = block.ms / a.steps;
   std::printf("{\"driver\": \"slab_ring_ade\", \"mode\": \"emulated %s on one GPU\", \"slabs\": %d, \"rows_per_slab\": %d, "
@@ -345,16 +409,24 @@ int run_emulated(const Args& a, int N) {
     for (int k = 0; k < N; ++k) std::printf("%s%d", k ? ", " : "", lbm_ade_iwalls_count(S[k].walls));
     std::printf("]");
   }
+  if (channel) {
+    std::printf(", \"open_nodes\": %d, \"open_nodes_per_slab\": [", lbm_ade_open_count(channel));
+    for (int k = 0; k < N; ++k) std::printf("%s%d", k ? ", " : "", lbm_ade_open_count(S[k].open));
+    std::printf("]");
+  }
   std::printf("%s%s}\n", a.buoyancy_field().c_str(), check_field(a.check, bad));
   std::fflush(stdout);
   for (auto& s : S) {
     for (int b = 0; b < 2; ++b) {
       lbm_free(s.f[b]);
       lbm_free(s.h[b]);
+      lbm_free(s.carry[b]);
     }
     lbm_ade_iwalls_destroy(s.walls);
+    lbm_ade_open_destroy(s.open);
   }
   lbm_ade_iwalls_destroy(table);
+  lbm_ade_open_destroy(channel);
   return bad ? 3 : 0;
 }
 
@@ -371,16 +443,27 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   check(lbm_ring_create(&ring, id, rank, world, &g, /*periodic=*/a.walls ? 0 : 1), "lbm_ring_create");
   double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
   upload_rows(f[1], h[1], g, rank * R, Rg);  // pre-collision, then the first driver iteration: collide + one exchange
-  check(lbm_ring_ade_collide_b(ring, f[0], h[0], f[1], h[1], &gbc, &fl, &sc, nullptr, a.buoyancy(), nullptr),
-        "lbm_ring_ade_collide_b");
+  lbm_ade_open* channel = channel_table(a, Rg);  // the global table, this slab's view and its carries
+  lbm_ade_open* open = open_view(channel, rank * R, R);
+  double* carry[2] = {alloc_doubles((size_t)lbm_ade_open_carry_len(open)), alloc_doubles((size_t)lbm_ade_open_carry_len(open))};
+  if (open)
+    check(lbm_ring_ade_collide_o(ring, f[0], h[0], f[1], h[1], &gbc, &fl, &sc, nullptr, a.buoyancy(), open, carry[0], nullptr),
+          "lbm_ring_ade_collide_o");
+  else
+    check(lbm_ring_ade_collide_b(ring, f[0], h[0], f[1], h[1], &gbc, &fl, &sc, nullptr, a.buoyancy(), nullptr),
+          "lbm_ring_ade_collide_b");
   double* prof = scalar_profile(a, Rg);
   const lbm_ade_scalar_bc sbc = scalar_bc(prof, rank * R, gbc);  // the global descriptor, this slab's profile rows
   lbm_ade_iwalls* table = rectangle_table(a, Rg);                 // the global table, this slab's view
   lbm_ade_iwalls* walls = slab_view(table, rank * R, R);
   int cur = 0;
   auto step = [&]() {
-    check(lbm_ring_ade_step_w(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
-                              a.buoyancy(), walls, a.edge_rows, nullptr), "lbm_ring_ade_step_w");
+    if (open)
+      check(lbm_ring_ade_step_o(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
+                                a.buoyancy(), walls, open, carry[cur], carry[cur ^ 1], a.edge_rows, nullptr), "lbm_ring_ade_step_o");
+    else
+      check(lbm_ring_ade_step_w(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
+                                a.buoyancy(), walls, a.edge_rows, nullptr), "lbm_ring_ade_step_w");
     cur ^= 1;
   };
   double tmax = 0;
@@ -392,7 +475,7 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
     publish_owned_rows(a, ".g", rank, h[cur], g);
     if (rank == 0) {
       std::vector<double> want[2];
-      one_block(a, Rg, fl, sc, table, want[0], want[1]);
+      one_block(a, Rg, fl, sc, table, want[0], want[1], channel);
       for (int r = 0; r < world; ++r)
         for (int lat = 0; lat < 2; ++lat)
           bad += mismatching_planes(want[lat], Rg, read_owned_rows(a, lat ? ".g" : ".f", r, R, C), R, r * R, C);
@@ -406,20 +489,24 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
     std::printf("{\"driver\": \"slab_ring_ade\", \"n_gpus\": %d, \"rows_per_gpu\": %d, \"cols\": %d, \"walls\": %d, "
                 "\"scalar_fixed\": %d, \"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, \"message_rows_per_side\": %d, "
                 "\"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, "
-                "\"mlups\": %.1f%s%s%s}\n",
+                "\"mlups\": %.1f%s%s%s%s}\n",
                 world, R, C, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, a.edge_rows, 2 * lbm_halo_rows(1), ms, blk, blk / ms,
                 (double)Rg * C / (ms * 1e3),
                 table ? (", \"interior_wall_nodes\": " + std::to_string(lbm_ade_iwalls_count(table))).c_str() : "",
+                channel ? (", \"open_nodes\": " + std::to_string(lbm_ade_open_count(channel))).c_str() : "",
                 a.buoyancy_field().c_str(), check_field(a.check, bad));
     std::fflush(stdout);
   }
   lbm_ring_destroy(ring);
   lbm_ade_iwalls_destroy(walls);
   lbm_ade_iwalls_destroy(table);
+  lbm_ade_open_destroy(open);
+  lbm_ade_open_destroy(channel);
   if (prof) lbm_free(prof);
   for (int k = 0; k < 2; ++k) {
     lbm_free(f[k]);
     lbm_free(h[k]);
+    lbm_free(carry[k]);
   }
   return bad ? 3 : 0;
 }
@@ -431,6 +518,8 @@ int main(int argc, char** argv) {
   parse_ring_opts(a, argc, argv, /*rows=*/512, /*cols=*/1024, /*steps=*/50, /*warmup=*/5, /*edge_rows=*/16);
   a.steps = std::max(1, a.steps);
   a.warmup = std::max(0, a.warmup);
+  // the default edge band on a slab too low for it: the widest that leaves an INNER row (an --edge-rows given is taken as it is)
+  if (arg_value(argc, argv, "--edge-rows", "").empty()) a.edge_rows = std::max(1, std::min(a.edge_rows, (a.rows - 1) / 2));
   a.walls = int_arg(argc, argv, "--walls", 0);
   a.scalar_fixed = int_arg(argc, argv, "--scalar-fixed", 0);
   if (a.scalar_fixed && !a.walls) {
@@ -440,6 +529,12 @@ int main(int argc, char** argv) {
   a.rectangle = int_arg(argc, argv, "--rectangle", 0);
   if (a.rectangle && !a.walls) {
     std::fprintf(stderr, "--rectangle 1 needs --walls 1 (the rectangle stands on the bounce-back last row of the chain)\n");
+    return 1;
+  }
+  a.channel = int_arg(argc, argv, "--channel", 0);
+  if (a.channel && (!a.walls || a.scalar_fixed)) {
+    std::fprintf(stderr, "--channel 1 needs --walls 1 (the channel's floor is the bounce-back last row of the chain) and no "
+                         "--scalar-fixed (its column walls are the channel's inlet and outlet)\n");
     return 1;
   }
   a.omega = std::atof(arg_value(argc, argv, "--omega", "1.2").c_str());

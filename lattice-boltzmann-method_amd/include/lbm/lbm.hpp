@@ -228,9 +228,18 @@ class AdeOpenBoundary {
   int count() const { return lbm_ade_open_count(h_); }
   long long carry_len() const { return lbm_ade_open_carry_len(h_); }
   void finalize() { check(lbm_ade_open_finalize(h_)); }
+  // the slab view (lbm_ade_open_slab): a new, unfinalized table for an R x C lattice listing this table's nodes of rows
+  // [row0, row0 + R) at r - row0, its g sources slab-local (ghost rows -1 and R) and its carry its own -- what a row slab
+  // hands to lbm_ade_stream_collide_part_o / lbm_ring_ade_collide_o / lbm_ring_ade_step_o; it takes no add_* call
+  AdeOpenBoundary slab(int row0, int R) const {
+    lbm_ade_open* v = nullptr;
+    check(lbm_ade_open_slab(&v, h_, row0, R));
+    return AdeOpenBoundary(v);
+  }
   const lbm_ade_open* handle() const { return h_; }
 
  private:
+  explicit AdeOpenBoundary(lbm_ade_open* h) : h_(h) {}
   lbm_ade_open* h_ = nullptr;
 };
 

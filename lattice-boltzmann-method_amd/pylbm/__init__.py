@@ -235,7 +235,8 @@ class AdeOpenBoundary:
         r, c = ct.c_int(), ct.c_int()
         fr, gr, sr, sc = (ct.c_int * 8)(), (ct.c_int * 8)(), (ct.c_int * 9)(), (ct.c_int * 9)()
         self.lib.ade_open_node(self.h, int(i), ct.byref(r), ct.byref(c), fr, gr, sr, sc)
-        return dict(r=r.value, c=c.value, f_rule=list(fr), g_rule=list(gr), g_src=list(zip(sr, sc)))
+        return dict(r=r.value, c=c.value, f_rule=list(fr), g_rule=list(gr), g_src=list(zip(sr, sc)),
+                    unreachable=int(self.lib.raw.lbm_ade_open_unreachable(self.h, int(i))))
 
     def nodes(self):
         return [self.node(i) for i in range(self.count())]
@@ -243,6 +244,16 @@ class AdeOpenBoundary:
     def finalize(self):
         self.lib.ade_open_finalize(self.h)
         return self
+
+    def slab(self, row0, R):
+        """the slab view (lbm_ade_open_slab): a new, unfinalized AdeOpenBoundary for an R x C lattice listing this table's
+        nodes of rows [row0, row0 + R) at r - row0, its g sources slab-local with the row in [-1, R] (the ghost rows), its
+        carry its own; this table may be finalized or not and is not modified.  A view takes no add_* call and goes to
+        ade_stream_collide_part_o / ring_ade_collide_o / ring_ade_step_o only."""
+        view = AdeOpenBoundary.__new__(AdeOpenBoundary)
+        view.lib, view.R, view.C, view.h = self.lib, int(R), self.C, ct.c_void_p()
+        self.lib.ade_open_slab(ct.byref(view.h), self.h, int(row0), int(R))
+        return view
 
     def close(self):
         if self.h:
@@ -277,6 +288,7 @@ def load_library(path=LIB_PATH):
     lib.lbm_slab_pressure_msg_doubles.restype = ct.c_longlong
     lib.lbm_ade_solver_launches.restype = ct.c_longlong
     lib.lbm_ade_open_carry_len.restype = ct.c_longlong
+    lib.lbm_ade_part_launches.restype = ct.c_longlong
     return lib
 
 
