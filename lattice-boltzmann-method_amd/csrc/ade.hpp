@@ -519,63 +519,18 @@ __device__ __forceinline__ void ade_iwalls_scalar(double (&h)[Q], const double* 
   }
 }
 
-// Interior-wall pass: the table's nodes of rows [row_begin, row_end) recomputed, one lane per node, overwriting what the
-// interior launch (and the edge pass, where the node sits on a domain wall) stored for them.  Per node: the domain's
-// gather (gather_walls: a node may stand on a domain wall, as the rectangle's feet do), the f slots, the same for g
-// (FIXED: the domain's FIXED edges as in k_ade_edge), the g slots, both collisions -- in k_ade_edge's order, the
-// scalar's rules between the fluid's moments and the scalar's collision.  FIXED: the DOMAIN has FIXED edges (sw);
-// the table's own FIXED slots are per node and need no instantiation.
-template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
-__global__ __launch_bounds__(256) void k_ade_iwalls(double* __restrict__ fn, double* __restrict__ gn,
-                                                    const double* __restrict__ fo, const double* __restrict__ go, Geom g,
-                                                    Bc bc, FM fm, SM sm, int row_begin, int row_end,
-                                                    double* __restrict__ rho_out, double* __restrict__ u_out,
-                                                    double* __restrict__ c_out, AdeWalls sw, AdeBuoyancy by,
-                                                    const AdeIwallNode* __restrict__ nodes, int n_nodes) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_nodes) return;
-  const AdeIwallNode nd = nodes[i];
-  const int r = nd.r, c = nd.c;
-  if (r < row_begin || r >= row_end) return;
-  const long o = g.at(r, c);
-  double f[Q], h[Q], rho, ux, uy, conc;
-  gather_walls(f, fo, g, bc, r, c);
-  ade_iwalls_fluid(f, fo, g, o, nd.slots);
-  gather_walls(h, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, r, c);
-  if (BUOYANT) {
-    ade_fluid_moments(f, rho, ux, uy);
-    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
-    ade_iwalls_scalar(h, go, g, o, nd.slots, nd.conc, ux, uy, sm.wr, sm.wc);
-    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
-  } else {
-    fm.collide(f, rho, ux, uy);
-    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
-    ade_iwalls_scalar(h, go, g, o, nd.slots, nd.conc, ux, uy, sm.wr, sm.wc);
-    sm.collide(h, ux, uy, conc);
-  }
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    fn[q * g.plane + o] = f[q];
-    gn[q * g.plane + o] = h[q];
-  }
-  if (WITH_MOMENTS) {
-    const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
-    rho_out[oo] = rho;
-    u_out[oo] = ux;
-    u_out[nn + oo] = uy;
-    c_out[oo] = conc;
-  }
-}
-
-// The interior-wall pass of a PART of a slab (lbm_ade_stream_collide_part_w): the per-node body of k_ade_iwalls -- the same
-// template flags, the same order of gather, f slots, domain FIXED edges, g slots and both collisions; on a slab the gather
-// reads the ghost rows -- over two index ranges of the table in ONE dispatch: lane i < n0 takes node first0 + i, the other
-// lanes node first1 + (i - n0), n lanes in all.  The table is sorted by (r, c), so the nodes of a band of rows are one
-// range (the host's row index, lbm_ade_iwalls_finalize): FRAME = the prefix [0, first[E]) and the suffix
-// [first[R - E], n_nodes), INNER = the range between them with n0 = n.  No lane is filtered by its row.  Reads the old
-// lattices only and writes wall nodes of the part's rows only.  (The body is repeated, not shared with k_ade_iwalls
-// through an inline function: shared, k_ade_iwalls compiles to the same operations with other registers, and the existing
-// kernels stay instruction for instruction what they were -- profiles/ade_iwalls_slabs.txt.)
+// Interior-wall pass: the table's nodes of a set of rows recomputed, one lane per node, overwriting what the interior
+// launch (and the edge pass, where the node sits on a domain wall) stored for them.  Per node: the domain's gather
+// (gather_walls: a node may stand on a domain wall, as the rectangle's feet do; on a slab it reads the ghost rows), the
+// f slots, the same for g (FIXED: the domain's FIXED edges as in k_ade_edge), the g slots, both collisions -- in
+// k_ade_edge's order, the scalar's rules between the fluid's moments and the scalar's collision.  FIXED: the DOMAIN has
+// FIXED edges (sw); the table's own FIXED slots are per node and need no instantiation.
+// The rows are two index ranges of the table in ONE dispatch: lane i < n0 takes node first0 + i, the other lanes node
+// first1 + (i - n0), n lanes in all.  The table is sorted by (r, c), so the nodes of a band of rows are one range (the
+// host's row index, lbm_ade_iwalls_finalize): rows [row_begin, row_end) of a single block = one range with n0 = n (the
+// whole block: all nodes); of a slab, FRAME = the prefix [0, first[E]) and the suffix [first[R - E], n_nodes), INNER =
+// the range between them with n0 = n.  No lane is filtered by its row.  Reads the old lattices only and writes wall
+// nodes of those rows only.
 template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
 __global__ __launch_bounds__(256) void k_ade_iwalls_ranges(double* __restrict__ fn, double* __restrict__ gn,
                                                            const double* __restrict__ fo, const double* __restrict__ go,
@@ -684,8 +639,8 @@ __global__ __launch_bounds__(256) void k_ade_collide(double* __restrict__ fp, do
 // Open boundaries (lbm_ade_open, device copy): one entry per listed node, sorted by (r, c), and the table's segments.
 // The host resolves everything (lbm_ade_open_finalize): per slot s the segment that won it (fseg / gseg: byte s-1 of the
 // two words = segment index + 1, 0 = the domain's own gather stays), the nine nodes the node's g is pulled from through
-// the scalar's source map (gsrc[q], dense r C + c; gsrc[0] = the node its OWN post-collision g is read from), and per
-// extrapolating slot the index in this table of the inward neighbour (xn).  The kernels look nothing up.
+// the scalar's source map (gsrc[q], (r + 1) C + c: ade_open_at; gsrc[0] = the node its OWN post-collision g is read
+// from), and per extrapolating slot the index in this table of the inward neighbour (xn).  The kernels look nothing up.
 struct AdeOpenSeg {
   int kind, pad;  // LBM_ADE_OPEN_* of an f segment; of a g segment LBM_ADE_SCALAR_*
   double p0, p1;  // ABB: u_w = (p0, p1); ABB_EXTRAPOLATED: u_w = p0 u_prev(node) + p1 u_prev(neighbour); g FIXED: C_w = p0
@@ -708,7 +663,6 @@ __host__ __device__ __forceinline__ constexpr int ade_flip_row(int s) {
 __host__ __device__ __forceinline__ constexpr int ade_flip_col(int s) {
   return s == 2 ? 4 : s == 4 ? 2 : s == 5 ? 8 : s == 8 ? 5 : s == 6 ? 7 : s == 7 ? 6 : s;
 }
-__device__ __forceinline__ long ade_open_at(const Geom& g, int dense) { return g.at(dense / g.C, dense % g.C); }
 
 // the f slots of a listed node from its own post-collision populations; the anti-bounce-back is the driver's :150, :164
 // expression, f[s] = -f*[q] + ((2 + 9 (u_w.c_q)^2) - 3 u_w.u_w) E_q with q = opp(s); carry = the u of every listed node
@@ -756,6 +710,12 @@ __device__ __forceinline__ void ade_open_scalar(double (&h)[Q], const double (&o
   }
 }
 
+// A g source of a table: (row + 1) C + column with the row in [-1, R].  An ordinary table's rows lie in [0, R); -1 and R
+// are the ghost rows of a slab (a VIEW of the table, lbm_ade_open_slab), and wrap on a ghost = 0 geometry (wrap_row)
+__device__ __forceinline__ long ade_open_at(const Geom& g, int biased) {
+  return g.at(wrap_row(g, biased / g.C - 1), biased % g.C);
+}
+
 // g of a listed node pulled through the map, with the domain's wall gather (bc: the scalar's gather modes) taken from the
 // mapped own node; own is left holding those own populations
 __device__ __forceinline__ void ade_open_gather_scalar(double (&h)[Q], double (&own)[Q], const double* __restrict__ go,
@@ -769,88 +729,15 @@ __device__ __forceinline__ void ade_open_gather_scalar(double (&h)[Q], double (&
   bc_fixups_own(h, own, g, bc, nd.r, nd.c);
 }
 
-// Open-boundary pass: the table's nodes recomputed, one lane per node, after the interior launch and the edge pass and
-// BEFORE the interior-wall pass (a node of both tables carries no rule here: the host checks).  Per node: the domain's
-// gather of f and the table's f slots; the moments; g pulled from the nine resolved sources with the domain's gather, the
-// domain's FIXED edges, the table's g slots; both collisions in k_ade_edge's order.  carry_out[2 i], [2 i + 1] = the u of
-// the fixed-up f (the unshifted u0 of a buoyant step): the next step's carry_in.  Whole block only (a part of a slab:
-// k_ade_open_ranges).
-template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
-__global__ __launch_bounds__(256) void k_ade_open(double* __restrict__ fn, double* __restrict__ gn,
-                                                  const double* __restrict__ fo, const double* __restrict__ go, Geom g,
-                                                  Bc bc, FM fm, SM sm, double* __restrict__ rho_out,
-                                                  double* __restrict__ u_out, double* __restrict__ c_out, AdeWalls sw,
-                                                  AdeBuoyancy by, const AdeOpenNode* __restrict__ nodes,
-                                                  const AdeOpenSeg* __restrict__ segs, int n_nodes,
-                                                  const double* __restrict__ carry_in, double* __restrict__ carry_out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_nodes) return;
-  const AdeOpenNode nd = nodes[i];
-  const int r = nd.r, c = nd.c;
-  const long o = g.at(r, c);
-  double f[Q], h[Q], own[Q], rho, ux, uy, conc, u0r, u0c;
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    f[q] = fo[q * g.plane + g.at(wrap_row(g, r - icx(q)), wrap_col(g, c - icy(q)))];
-    own[q] = fo[q * g.plane + o];
-  }
-  bc_fixups_own(f, own, g, bc, r, c);
-  ade_open_fluid(f, own, nd, segs, carry_in, i);
-  ade_open_gather_scalar(h, own, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, nd);
-  if (BUOYANT) {
-    ade_fluid_moments(f, rho, ux, uy);
-    u0r = ux, u0c = uy;
-    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
-    ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
-    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
-  } else {
-    fm.collide(f, rho, ux, uy);
-    u0r = ux, u0c = uy;
-    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
-    ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
-    sm.collide(h, ux, uy, conc);
-  }
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    fn[q * g.plane + o] = f[q];
-    gn[q * g.plane + o] = h[q];
-  }
-  carry_out[2 * i] = u0r;
-  carry_out[2 * i + 1] = u0c;
-  if (WITH_MOMENTS) {
-    const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
-    rho_out[oo] = rho;
-    u_out[oo] = ux;
-    u_out[nn + oo] = uy;
-    c_out[oo] = conc;
-  }
-}
-
-// A g source of a slab VIEW of the table (lbm_ade_open_slab): (row + 1) C + column with the row in [-1, R] -- -1 and R are
-// the ghost rows of a slab, and wrap on a ghost = 0 geometry (wrap_row) exactly as the ordinary table's sources do
-__device__ __forceinline__ long ade_open_view_at(const Geom& g, int biased) {
-  return g.at(wrap_row(g, biased / g.C - 1), biased % g.C);
-}
-
-// ade_open_gather_scalar with a view's source decoding
-__device__ __forceinline__ void ade_open_view_gather_scalar(double (&h)[Q], double (&own)[Q], const double* __restrict__ go,
-                                                            const Geom& g, const Bc& bc, const AdeOpenNode& nd) {
-  const long om = ade_open_view_at(g, nd.gsrc[0]);
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    h[q] = go[q * g.plane + ade_open_view_at(g, nd.gsrc[q])];
-    own[q] = go[q * g.plane + om];
-  }
-  bc_fixups_own(h, own, g, bc, nd.r, nd.c);
-}
-
-// The open-boundary pass of a PART of a slab (lbm_ade_stream_collide_part_o): the per-node body of k_ade_open -- the same
-// template flags, the same order of gathers, rules and collisions; the f gather reads the ghost rows of a slab and the g
-// sources are the view's (ade_open_view_at) -- over two index ranges of the sorted view in ONE dispatch, the launch shape of
-// k_ade_iwalls_ranges: lane i < n0 takes node first0 + i, the other lanes node first1 + (i - n0), n lanes in all.  The carry
-// index is the node's index m in the view.  No lane is filtered by its row.  Reads the old lattices and carry_in only and
-// writes, of its own nodes only, fn, gn, the moments and carry_out.  (The body is repeated, not shared with k_ade_open: the
-// existing kernels stay instruction for instruction what they were -- profiles/ade_open_slabs.txt.)
+// Open-boundary pass: the table's nodes of a set of rows recomputed, one lane per node, after the interior launch and the
+// edge pass and BEFORE the interior-wall pass (a node of both tables carries no rule here: the host checks).  Per node:
+// the domain's gather of f (on a slab it reads the ghost rows) and the table's f slots; the moments; g pulled from the
+// nine resolved sources with the domain's gather, the domain's FIXED edges, the table's g slots; both collisions in
+// k_ade_edge's order.  The rows are two index ranges of the sorted table in ONE dispatch, the launch shape of
+// k_ade_iwalls_ranges: lane i < n0 takes node first0 + i, the other lanes node first1 + (i - n0), n lanes in all; the
+// whole block is first0 = 0, n0 = n = n_nodes.  No lane is filtered by its row.  carry_out[2 m], [2 m + 1] = the u of the
+// fixed-up f (the unshifted u0 of a buoyant step) of node m of the table: the next step's carry_in.  Reads the old
+// lattices and carry_in only and writes, of its own nodes only, fn, gn, the moments and carry_out.
 template <class FM, class SM, bool WITH_MOMENTS, bool FIXED = false, bool BUOYANT = false>
 __global__ __launch_bounds__(256) void k_ade_open_ranges(double* __restrict__ fn, double* __restrict__ gn,
                                                          const double* __restrict__ fo, const double* __restrict__ go,
@@ -875,7 +762,7 @@ __global__ __launch_bounds__(256) void k_ade_open_ranges(double* __restrict__ fn
   }
   bc_fixups_own(f, own, g, bc, r, c);
   ade_open_fluid(f, own, nd, segs, carry_in, m);
-  ade_open_view_gather_scalar(h, own, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, nd);
+  ade_open_gather_scalar(h, own, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, nd);
   if (BUOYANT) {
     ade_fluid_moments(f, rho, ux, uy);
     u0r = ux, u0c = uy;

@@ -35,7 +35,8 @@ struct lbm_ade_iwalls {
 
 // Open boundaries of the fused step: the segments in the order added, and the table resolved from them after every add
 // (resolve below) -- the listed nodes sorted by (r, c), each with the segment that won every slot, its nine g sources
-// and its extrapolation neighbours.  lbm_ade_open_finalize uploads nodes and segments once; immutable from then on.
+// (gsrc: (row + 1) C + column, lbm::ade_open_at) and its extrapolation neighbours.  lbm_ade_open_finalize uploads nodes
+// and segments once and keeps the row index first (R + 1 entries, as lbm_ade_iwalls.first); immutable from then on.
 struct lbm_ade_open {
   enum Kind { F_RULE, G_RULE, G_COPY };
   struct Seg {
@@ -53,12 +54,12 @@ struct lbm_ade_open {
   int n = 0;  // nodes uploaded
   lbm::AdeOpenNode* d_nodes = nullptr;
   lbm::AdeOpenSeg* d_segs = nullptr;
-  // A slab VIEW (lbm_ade_open_slab): the parent's nodes of rows [row0, row0 + R) at r - row0 and its segments; gsrc holds
-  // (row + 1) C + column with the row in [-1, R], pad the mask of the g sources the slab cannot reach (bit q), xn indices
-  // into the view.  first: the row index lbm_ade_open_finalize keeps (R + 1 entries), as lbm_ade_iwalls.first.
+  std::vector<int> first;
+  // A slab VIEW (lbm_ade_open_slab): the parent's nodes of rows [row0, row0 + R) at r - row0 and its segments; the rows of
+  // gsrc lie in [-1, R] (an ordinary table's in [0, R)), pad the mask of the g sources the slab cannot reach (bit q), xn
+  // indices into the view.
   bool view = false;
   int row0 = 0, R_parent = 0;
-  std::vector<int> first;
   // the call configuration (edge modes, ghost rows, FIXED edges) the reach check has last passed with, + 1: a step loop
   // checks the view's sources once, not once per call
   mutable std::atomic<unsigned> reach_ok{0};
@@ -299,7 +300,7 @@ static void ade_open_resolve(lbm_ade_open* t) {
         nd.xn[q - 1] = index[kv.first + dense(s.nr, s.nc)];
       }
     }
-    for (int q = 0; q < Q; ++q) nd.gsrc[q] = (int)look(dense((nd.r - icx(q) + R) % R, (nd.c - icy(q) + C) % C));
+    for (int q = 0; q < Q; ++q) nd.gsrc[q] = (int)(look(dense((nd.r - icx(q) + R) % R, (nd.c - icy(q) + C) % C)) + C);
     t->nodes.push_back(nd);
   }
 }
@@ -370,8 +371,9 @@ static int ade_open_check(const char* fn, const lbm_ade_open* t, const lbm_geom*
                   "%s: open boundaries: node (%d, %d) carries an open-boundary rule and is in the interior-wall table as well",
                   fn, r, c);
       for (int q = 0; q < Q; ++q) {
-        // the plain pull source in the table's encoding (a view: the row unwrapped, in [-1, R], + 1)
-        const long long plain = (long long)(t->view ? r - icx(q) + 1 : (r - icx(q) + R) % R) * C + (c - icy(q) + C) % C;
+        // the plain pull source in the table's encoding (a view holds the row unwrapped, in [-1, R])
+        const int pull = t->view ? r - icx(q) : (r - icx(q) + R) % R;
+        const long long plain = (long long)(pull + 1) * C + (c - icy(q) + C) % C;
         LBM_REQUIRE((it->gsrc[q] == plain && !((it->pad >> q) & 1)) || ade_wall_replaces(gbc, R, C, r, c, q),
                     "%s: open boundaries: node (%d, %d) is in the interior-wall table and its g slot %d is redirected by a "
                     "copy with no domain wall replacing it there", fn, r, c, q);
@@ -400,8 +402,8 @@ struct AdeCall {
   const AdeOpenNode* open_nodes;  // the open-boundary table (lbm_ade_open), NULL without nodes
   const AdeOpenSeg* open_segs;
   int n_open_nodes;
-  const int* open_first;   // host: a slab view's row index (R + 1 entries), NULL without nodes or on a single block
-  const double* carry_in;  // the carry of a slab's call (ade_carry_set); the single-block entries pass theirs by argument
+  const int* open_first;   // host: the table's row index (R + 1 entries), NULL without nodes
+  const double* carry_in;  // the carry of the call (ade_carry_set)
   double* carry_out;
 };
 static_assert(sizeof(AdeCall) <= sizeof(AdeCallBuf) && alignof(AdeCall) <= alignof(AdeCallBuf) &&
@@ -430,7 +432,7 @@ int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm
   if (!open) return LBM_OK;
   rc = ade_open_check(fn, open, lg, ade_scalar_gather_bc(call->bc, call->sw.fixed), call->n_wall_nodes > 0 ? iwalls : nullptr,
                       &call->open_nodes, &call->open_segs, &call->n_open_nodes, slab, &call->bc, call->sw.fixed);
-  if (!rc && slab && call->n_open_nodes > 0) call->open_first = open->first.data();
+  if (!rc && call->n_open_nodes > 0) call->open_first = open->first.data();
   return rc;
 }
 
@@ -444,14 +446,56 @@ static int ade_collide_launch(const AdeCall& k, const FM& fm, const SM& sm, doub
   return LBM_OK;
 }
 
-// interior launch + (walls only) the edge pass + (a non-empty open table only) the open-boundary pass + (a non-empty
-// table of interior walls only) the interior-wall pass;
+// The rows of a launch -- [band0, band0 + n0), then [band1, band1 + nrows - n0) where n0 < nrows -- as two index ranges of
+// a table sorted by (r, c), from its row index first[]: nodes [first0, first0 + w0), then from first1 on, w in all
+struct AdeRanges {
+  int first0, w0, first1, w;
+};
+static AdeRanges ade_row_ranges(const int* first, int band0, int n0, int band1, int nrows) {
+  const int first0 = first[band0], w0 = first[band0 + n0] - first0, first1 = first[band1];
+  return AdeRanges{first0, w0, first1, w0 + (n0 < nrows ? first[band1 + nrows - n0] - first1 : 0)};
+}
+
+// The two table passes of a launch over the rows of ade_row_ranges, behind the dispatch whose nodes they overwrite and on
+// the same stream: the open table's listed nodes of those rows, then the interior walls' -- one lane per node, one
+// dispatch per table; rows without a node of a table enqueue nothing for it.  *launches += the kernels enqueued
+template <bool B, class FM, class SM>
+static int ade_table_passes(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
+                            const double* go, int band0, int n0, int band1, int nrows, double* rho, double* u,
+                            double* conc, hipStream_t st, long long* launches) {
+  const bool mom = rho != nullptr;
+  if (k.n_open_nodes > 0) {
+    const AdeRanges a = ade_row_ranges(k.open_first, band0, n0, band1, nrows);
+    if (a.w > 0) {
+      with_flags([&](auto M, auto F) {
+        LBM_KLAUNCH((k_ade_open_ranges<FM, SM, M(), F(), B>), dim3((a.w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, k.g,
+                    k.bc, fm, sm, rho, u, conc, k.sw, k.by, k.open_nodes, k.open_segs, a.first0, a.w0, a.first1, a.w,
+                    k.carry_in, k.carry_out);
+      }, mom, k.sw.fixed);
+      LBM_CHECK_LAUNCH();
+      ++*launches;
+    }
+  }
+  if (k.n_wall_nodes > 0) {
+    const AdeRanges a = ade_row_ranges(k.wall_first, band0, n0, band1, nrows);
+    if (a.w > 0) {
+      with_flags([&](auto M, auto F) {
+        LBM_KLAUNCH((k_ade_iwalls_ranges<FM, SM, M(), F(), B>), dim3((a.w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go,
+                    k.g, k.bc, fm, sm, rho, u, conc, k.sw, k.by, k.wall_nodes, a.first0, a.w0, a.first1, a.w);
+      }, mom, k.sw.fixed);
+      LBM_CHECK_LAUNCH();
+      ++*launches;
+    }
+  }
+  return LBM_OK;
+}
+
+// interior launch + (walls only) the edge pass + the table passes of rows [row_begin, row_end) (one range of each table);
 // *launches (if given) += the kernels enqueued
 template <bool B, class FM, class SM>
 static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
                            const double* go, int row_begin, int row_end, double* rho, double* u, double* conc,
-                           hipStream_t st, long long* launches, const double* carry_in = nullptr,
-                           double* carry_out = nullptr) {
+                           hipStream_t st, long long* launches) {
   long long uncounted = 0;
   if (!launches) launches = &uncounted;
   const bool mom = rho != nullptr;
@@ -476,32 +520,16 @@ static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
     LBM_CHECK_LAUNCH();
     ++*launches;
   }
-  if (k.n_open_nodes > 0) {  // one lane per listed node, before the interior-wall pass (whole block: the entry checks)
-    const dim3 grid_o((k.n_open_nodes + 255) / 256);
-    with_flags([&](auto M, auto F) {
-      LBM_KLAUNCH((k_ade_open<FM, SM, M(), F(), B>), grid_o, dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc, fm, sm, rho, u, conc,
-                  k.sw, k.by, k.open_nodes, k.open_segs, k.n_open_nodes, carry_in, carry_out);
-    }, mom, k.sw.fixed);
-    LBM_CHECK_LAUNCH();
-    ++*launches;
-  }
-  if (k.n_wall_nodes > 0) {  // one lane per table node, after the passes whose nodes it overwrites
-    const dim3 grid_w((k.n_wall_nodes + 255) / 256);
-    with_flags([&](auto M, auto F) {
-      LBM_KLAUNCH((k_ade_iwalls<FM, SM, M(), F(), B>), grid_w, dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc, fm, sm, row_begin,
-                  row_end, rho, u, conc, k.sw, k.by, k.wall_nodes, k.n_wall_nodes);
-    }, mom, k.sw.fixed);
-    LBM_CHECK_LAUNCH();
-    ++*launches;
-  }
-  return LBM_OK;
+  const int nrows = row_end - row_begin;
+  return ade_table_passes<B>(k, fm, sm, fn, gn, fo, go, row_begin, nrows, row_begin, nrows, rho, u, conc, st, launches);
 }
 
 // kernels the part launches of this process have enqueued (lbm_ade_part_launches): what "a NULL view adds no launch" is
 // tested with, there being no solver context for slabs to count them
 static std::atomic<long long> g_part_launches{0};
 
-// one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline
+// one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline, + the table passes of
+// those rows
 template <bool B, class FM, class SM>
 static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
                            const double* go, int band0, int n0, int band1, int nrows, double* rho, double* u,
@@ -517,36 +545,10 @@ static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
                 k.g, k.bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, k.sw, k.by);
   }, nt & 1, nt & 2, mom, k.sw.fixed);
   LBM_CHECK_LAUNCH();
-  g_part_launches.fetch_add(1, std::memory_order_relaxed);
-  if (k.n_open_nodes > 0) {
-    // the view's nodes of the part's rows, behind the dispatch whose nodes they overwrite and before the interior-wall
-    // pass, on the same stream: two index ranges of the sorted view, as below; a part without a listed node enqueues nothing
-    const int* first = k.open_first;
-    const int first0 = first[band0], w0 = first[band0 + n0] - first0;
-    const int first1 = first[band1], w = w0 + (n0 < nrows ? first[band1 + nrows - n0] - first1 : 0);
-    if (w > 0) {
-      with_flags([&](auto M, auto F) {
-        LBM_KLAUNCH((k_ade_open_ranges<FM, SM, M(), F(), B>), dim3((w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc,
-                    fm, sm, rho, u, conc, k.sw, k.by, k.open_nodes, k.open_segs, first0, w0, first1, w, k.carry_in, k.carry_out);
-      }, mom, k.sw.fixed);
-      LBM_CHECK_LAUNCH();
-      g_part_launches.fetch_add(1, std::memory_order_relaxed);
-    }
-  }
-  if (k.n_wall_nodes == 0) return LBM_OK;
-  // the table's nodes of the part's rows, behind the dispatch whose nodes they overwrite, on the same stream: the two
-  // bands are two index ranges of the sorted table (one when n0 == nrows); a part without a table node enqueues nothing
-  const int* first = k.wall_first;
-  const int first0 = first[band0], w0 = first[band0 + n0] - first0;
-  const int first1 = first[band1], w = w0 + (n0 < nrows ? first[band1 + nrows - n0] - first1 : 0);
-  if (w == 0) return LBM_OK;
-  with_flags([&](auto M, auto F) {
-    LBM_KLAUNCH((k_ade_iwalls_ranges<FM, SM, M(), F(), B>), dim3((w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc,
-                fm, sm, rho, u, conc, k.sw, k.by, k.wall_nodes, first0, w0, first1, w);
-  }, mom, k.sw.fixed);
-  LBM_CHECK_LAUNCH();
-  g_part_launches.fetch_add(1, std::memory_order_relaxed);
-  return LBM_OK;
+  long long launches = 1;
+  const int rc = ade_table_passes<B>(k, fm, sm, fn, gn, fo, go, band0, n0, band1, nrows, rho, u, conc, st, &launches);
+  g_part_launches.fetch_add(launches, std::memory_order_relaxed);
+  return rc;
 }
 
 // collide only: no streaming, so no wall rule -- the scalar's walls and the interior walls of the call are checked and
@@ -576,13 +578,18 @@ int ade_carry_set(const char* fn, AdeCall* k, bool reads, const double* carry_in
   return LBM_OK;
 }
 
-// the carry of a pre-collision state on a slab: k_ade_open_prime over the call's view (it addresses through Geom::at)
-int ade_open_prime_from(const AdeCall& k, const double* f, hipStream_t st) {
-  if (k.n_open_nodes == 0) return LBM_OK;
-  LBM_KLAUNCH(k_ade_open_prime, dim3((k.n_open_nodes + 255) / 256), dim3(256), 0, st, f, k.g, k.open_nodes, k.n_open_nodes,
-              k.carry_out);
+// The carry of a pre-collision state f -- u of the n listed nodes, k_ade_open_prime (it addresses through Geom::at) -- the
+// one launch site of that kernel; an empty table enqueues nothing
+static int ade_open_prime(const Geom& g, const AdeOpenNode* nodes, int n, const double* f, double* carry, hipStream_t st) {
+  if (n == 0) return LBM_OK;
+  LBM_KLAUNCH(k_ade_open_prime, dim3((n + 255) / 256), dim3(256), 0, st, f, g, nodes, n, carry);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
+}
+
+// the carry of a pre-collision state on a slab, over the call's view
+int ade_open_prime_from(const AdeCall& k, const double* f, hipStream_t st) {
+  return ade_open_prime(k.g, k.open_nodes, k.n_open_nodes, f, k.carry_out, st);
 }
 
 // the collide-only iteration; with a non-empty open table one more small launch writes carry_out from the pre-collision f
@@ -598,11 +605,9 @@ static int ade_collide(const char* fn, double* fp, double* gp, const double* f, 
   if (rc) return rc;
   if (launches) ++*launches;
   if (k.n_open_nodes == 0) return LBM_OK;
-  LBM_KLAUNCH(k_ade_open_prime, dim3((k.n_open_nodes + 255) / 256), dim3(256), 0, st, f, k.g, k.open_nodes, k.n_open_nodes,
-              carry_out);
-  LBM_CHECK_LAUNCH();
-  if (launches) ++*launches;
-  return LBM_OK;
+  rc = ade_open_prime(k.g, k.open_nodes, k.n_open_nodes, f, carry_out, st);
+  if (!rc && launches) ++*launches;
+  return rc;
 }
 
 static int ade_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
@@ -615,7 +620,7 @@ static int ade_stream_collide(const char* fn, double* fn_, double* gn, const dou
   AdeCall k;
   int rc = ade_resolve(fn, lg, lbc, fluid, scalar, sbc, buoy, iwalls, false, &k, open);
   if (!rc) rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true);
-  if (!rc) rc = ade_carry_args(fn, k, true, carry_in, carry_out);
+  if (!rc) rc = ade_carry_set(fn, &k, true, carry_in, carry_out);
   if (rc) return rc;
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R, "%s: row range [%d, %d) outside [0, %d)", fn,
               row_begin, row_end, lg->R);
@@ -623,7 +628,7 @@ static int ade_stream_collide(const char* fn, double* fn_, double* gn, const dou
               "%s: open boundaries: row range [%d, %d): the whole block [0, %d) only", fn, row_begin, row_end, lg->R);
   if (row_begin == row_end) return LBM_OK;
   return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
-    return ade_step_launch<B()>(k, fm, sm, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches, carry_in, carry_out);
+    return ade_step_launch<B()>(k, fm, sm, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
   });
 }
 
@@ -841,10 +846,9 @@ int lbm_ade_solver_set_state(lbm_ade_solver* sv, const double* f_host, const dou
   LBM_CHECK_HIP(hipMemcpyAsync(sv->dense, g_host, bytes, hipMemcpyHostToDevice, sv->st));
   rc = lbm_aos_to_soa_pitched(sv->h(sv->cur), sv->dense, g.R, g.C, 9, g.plane_stride, g.row_pitch, sv->st);
   if (rc) return rc;
-  if (sv->open && sv->open->n > 0) {  // the carry of the state given
-    LBM_KLAUNCH(k_ade_open_prime, dim3((sv->open->n + 255) / 256), dim3(256), 0, sv->st, sv->f(sv->cur), make_geom(g),
-                sv->open->d_nodes, sv->open->n, sv->carry[sv->cur]);
-    LBM_CHECK_LAUNCH();
+  if (sv->open) {  // the carry of the state given
+    rc = ade_open_prime(make_geom(g), sv->open->d_nodes, sv->open->n, sv->f(sv->cur), sv->carry[sv->cur], sv->st);
+    if (rc) return rc;
   }
   LBM_CHECK_HIP(hipStreamSynchronize(sv->st));  // the host arrays may be reused by the caller
   sv->post = false;
@@ -1168,7 +1172,8 @@ int lbm_ade_iwalls_destroy(lbm_ade_iwalls* t) {
 int lbm_ade_open_create(lbm_ade_open** out, int R, int C) {
   LBM_REQUIRE(out, "lbm_ade_open_create: NULL argument");
   LBM_REQUIRE(R >= 1 && C >= 1, "lbm_ade_open_create: R=%d C=%d must be positive", R, C);
-  LBM_REQUIRE((long long)R * C < (1LL << 31), "lbm_ade_open_create: R=%d C=%d: more than 2^31 - 1 nodes", R, C);
+  LBM_REQUIRE(((long long)R + 2) * C < (1LL << 31), "lbm_ade_open_create: R=%d C=%d: (R + 2) x C is more than 2^31 - 1 nodes "
+              "(the table's source encoding)", R, C);
   lbm_ade_open* t = new (std::nothrow) lbm_ade_open();
   LBM_REQUIRE(t, "lbm_ade_open_create: out of host memory");
   t->R = R;
@@ -1292,7 +1297,7 @@ int lbm_ade_open_node(const lbm_ade_open* t, int i, int* r, int* c, int* f_rule,
     if (g_rule) g_rule[s - 1] = jg ? 1 + t->segs[(size_t)jg - 1].rule : 0;
   }
   for (int q = 0; q < Q; ++q) {
-    if (g_src_r) g_src_r[q] = nd.gsrc[q] / t->C - (t->view ? 1 : 0);  // a view: in [-1, R]
+    if (g_src_r) g_src_r[q] = nd.gsrc[q] / t->C - 1;  // an ordinary table: in [0, R); a view: in [-1, R]
     if (g_src_c) g_src_c[q] = nd.gsrc[q] % t->C;
   }
   return LBM_OK;
@@ -1300,7 +1305,7 @@ int lbm_ade_open_node(const lbm_ade_open* t, int i, int* r, int* c, int* f_rule,
 
 int lbm_ade_open_unreachable(const lbm_ade_open* t, int i) {
   if (!t || i < 0 || i >= (int)t->nodes.size()) return 0;
-  return t->view ? t->nodes[(size_t)i].pad : 0;
+  return t->nodes[(size_t)i].pad;  // 0 but in a view
 }
 
 int lbm_ade_open_finalize(lbm_ade_open* t) {
@@ -1323,11 +1328,9 @@ int lbm_ade_open_finalize(lbm_ade_open* t) {
       return LBM_ERR_HIP;
     }
     t->n = (int)t->nodes.size();
-    if (t->view) {  // the row index: node counts per row, then their running sum
-      t->first.assign((size_t)t->R + 1, 0);
-      for (const AdeOpenNode& nd : t->nodes) ++t->first[(size_t)nd.r + 1];
-      for (int r = 0; r < t->R; ++r) t->first[(size_t)r + 1] += t->first[r];
-    }
+    t->first.assign((size_t)t->R + 1, 0);  // the row index: node counts per row, then their running sum
+    for (const AdeOpenNode& nd : t->nodes) ++t->first[(size_t)nd.r + 1];
+    for (int r = 0; r < t->R; ++r) t->first[(size_t)r + 1] += t->first[r];
   }
   t->finalized = true;
   return LBM_OK;
@@ -1341,9 +1344,7 @@ int lbm_ade_open_slab(lbm_ade_open** out, const lbm_ade_open* table, int row0, i
   LBM_REQUIRE(R >= 1, "%s: R=%d must be at least 1", fn, R);
   LBM_REQUIRE((long long)row0 + R <= table->R, "%s: rows [%d, %lld) beyond the %d rows of the table", fn, row0,
               (long long)row0 + R, table->R);
-  const int C = table->C, Rg = table->R;
-  LBM_REQUIRE(((long long)R + 2) * C < (1LL << 31), "%s: R=%d C=%d: (R + 2) x C exceeds 2^31 - 1 (the view's source encoding)",
-              fn, R, C);
+  const int C = table->C, Rg = table->R;  // (R + 2) C <= (Rg + 2) C < 2^31: the source encoding holds (lbm_ade_open_create)
   // the parent's nodes are sorted by (r, c): the rows of the view are one range [i0, i1) of them
   auto row_begin = [table](int r) {
     return (int)(std::lower_bound(table->nodes.begin(), table->nodes.end(), r,
@@ -1357,7 +1358,7 @@ int lbm_ade_open_slab(lbm_ade_open** out, const lbm_ade_open* table, int row0, i
     nd.pad = 0;
     for (int q = 0; q < Q; ++q) {
       // the source's global row modulo the parent's rows, as the slab-local row in [-1, R] nearest to the plain pull
-      const int sr = nd.gsrc[q] / C, pull = nd.r - icx(q);
+      const int sr = nd.gsrc[q] / C - 1, pull = nd.r - icx(q);
       int sc = nd.gsrc[q] % C, best = 0;
       bool found = false;
       for (int cand : {sr - row0 - Rg, sr - row0, sr - row0 + Rg})
@@ -1457,11 +1458,8 @@ int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open) {
       set_error("%s: %s", fn, hipGetErrorString(e));
       return LBM_ERR_HIP;
     }
-    if (!sv->post) {  // a state set before the table: its carry
-      LBM_KLAUNCH(k_ade_open_prime, dim3((open->n + 255) / 256), dim3(256), 0, sv->st, sv->f(sv->cur), make_geom(sv->g),
-                  open->d_nodes, open->n, sv->carry[sv->cur]);
-      LBM_CHECK_LAUNCH();
-    }
+    if (!sv->post)  // a state set before the table: its carry
+      if (int rc = ade_open_prime(make_geom(sv->g), open->d_nodes, open->n, sv->f(sv->cur), sv->carry[sv->cur], sv->st)) return rc;
   }
   sv->open = open;
   return LBM_OK;

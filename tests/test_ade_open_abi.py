@@ -101,6 +101,20 @@ def test_create_refuses_a_null_out_and_a_non_positive_size(lib):
     _refused(lib, lib.raw.lbm_ade_open_create(ct.byref(h), 65536, 32768), "lbm_ade_open_create", "more than 2\\^31 - 1 nodes")
 
 
+def test_create_bounds_the_source_encoding_at_r_plus_2_rows(lib):
+    """a g source is (row + 1) C + column with the row in [-1, R]: (R + 2) C must stay below 2^31.  65535 x 32768 has fewer
+    than 2^31 nodes and (R + 2) C = 2^31 + 32768; 65533 x 32768 has (R + 2) C = 2^31 - 32768.  Create and destroy only:
+    nothing is allocated per node"""
+    h = ct.c_void_p()
+    assert 65535 * 32768 < 2 ** 31 <= (65535 + 2) * 32768
+    _refused(lib, lib.raw.lbm_ade_open_create(ct.byref(h), 65535, 32768), "lbm_ade_open_create", r"R=65535 C=32768: \(R \+ 2\)")
+    assert not h
+    assert (65533 + 2) * 32768 == 2 ** 31 - 32768
+    assert lib.raw.lbm_ade_open_create(ct.byref(h), 65533, 32768) == 0 and h
+    assert lib.raw.lbm_ade_open_count(h) == 0
+    assert lib.raw.lbm_ade_open_destroy(h) == 0
+
+
 def test_a_null_table_is_refused_by_every_entry_that_needs_one(lib):
     _refused(lib, add_f(lib, None, 0, 0, 0, 1, 1, 1, O_BB), "lbm_ade_open_add_f", "NULL table")
     _refused(lib, add_g(lib, None, 0, 0, 0, 1, 1, 1), "lbm_ade_open_add_g", "NULL table")

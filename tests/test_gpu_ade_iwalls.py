@@ -250,11 +250,15 @@ def test_null_and_empty_tables_are_todays_solver(lib, oracle, form):
 
 # ---- 5. write set -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", [REF, FAST], ids=["reference_order", "reassociated"])
-def test_the_walled_step_writes_exactly_the_rows_of_its_range(lib, form):
-    """8 x 260 at a padded row pitch, two full-width wall rows (520 nodes): lbm_ade_stream_collide_w on rows [3, 7) writes
-    those rows only -- the table's row 2 keeps the pattern, its row 5 is written -- never the padding, and what it writes
-    is what the call on [0, R) writes there; the moment outputs likewise"""
-    R, C, lo, hi = 8, 260, 3, 7
+@pytest.mark.parametrize("lo,hi", [(3, 7), (0, 8), (0, 2), (2, 3), (6, 8), (5, 6)],
+                         ids=["rows_3_7", "whole_block", "before_the_table", "table_row_2", "after_the_table", "table_row_5"])
+def test_the_walled_step_writes_exactly_the_rows_of_its_range(lib, form, lo, hi):
+    """8 x 260 at a padded row pitch, two full-width wall rows (520 nodes, rows 2 and 5: an index range of the table
+    crosses a 256-lane workgroup): lbm_ade_stream_collide_w on rows [lo, hi) -- the table's nodes of those rows taken from
+    its row index -- writes those rows only, the table's rows outside keep the pattern, never the padding, and what it
+    writes is what the call on [0, R) writes there; the moment outputs likewise.  A range without a table row writes
+    lbm_ade_stream_collide_b's bits: nothing of the table is applied"""
+    R, C = 8, 260
     g = ade.geom(R, C, 0, C + 12)
     bc = pylbm.Bc(col_lo=BB, col_hi=BB)
     sbc = pylbm.AdeScalarBC(col_lo=5e-4)
@@ -297,6 +301,9 @@ def test_the_walled_step_writes_exactly_the_rows_of_its_range(lib, form):
     for k in range(2):
         differs = (ade.bits(ade.owned(full[k], g)) != ade.bits(ade.owned(plain[k], g))).any(dim=0).any(dim=1)
         assert differs.tolist() == [r in (2, 5) for r in range(R)], (k, differs.tolist())
+        if not any(lo <= r < hi for r in (2, 5)):
+            same = ade.bits(ade.owned(part[k], g))[:, lo:hi] == ade.bits(ade.owned(plain[k], g))[:, lo:hi]
+            assert bool(same.all()), f"lattice {k}: rows [{lo}, {hi}) are not the plain step's"
     table.close()
 
 
