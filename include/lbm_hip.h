@@ -1087,6 +1087,73 @@ int lbm_cg_snapshot_write_npy(lbm_cg_snapshot* sn, const char* rho_r_path, const
 int lbm_solver_checkpoint_save(lbm_solver* sv, const char* path);
 int lbm_solver_checkpoint_load(lbm_solver* sv, const char* path);
 
+/* ---- device-side diagnostics: reproducible field sums and run-to-convergence (DESIGN.md "Diagnostics") --------
+ * Sums, extrema and a non-finite count over the dense macroscopic fields rho [R][C], u [2][R][C] (ur = u[0],
+ * uc = u[1]) and, optionally, conc [R][C], without a field ever leaving the device.  The value of a sum is defined by
+ * node indices alone:  fold64(x[0..n)) takes 64 accumulators p[j] = +0.0, adds x[j + 64 k] to p[j] for k = 0, 1, ...
+ * in ascending order (missing elements add nothing), then p[j] += p[j + s] (j < s) for s = 32, 16, 8, 4, 2, 1, and is
+ * p[0]; all additions are IEEE f64, not contracted.  The value of row r is fold64 over its columns of the per-node
+ * term, the value of a row range is fold64 over its row values; minima / maxima fold the same way with fmin / fmax
+ * (NaN operands skipped) from +inf / -inf.  So a table filled slab by slab, under any launch shape, folds to the
+ * bits of one block.  Where a field holds a non-finite value, only NONFINITE is specified for the rows holding it. */
+#define LBM_DIAG_NQ 17
+#define LBM_DIAG_SUM_RHO 0    /* rho */
+#define LBM_DIAG_SUM_UR 1     /* ur */
+#define LBM_DIAG_SUM_UC 2     /* uc */
+#define LBM_DIAG_SUM_MR 3     /* rho*ur */
+#define LBM_DIAG_SUM_MC 4     /* rho*uc */
+#define LBM_DIAG_SUM_KE 5     /* 0.5 * (rho * (ur*ur + uc*uc)) */
+#define LBM_DIAG_MAX_U2 6     /* max of ur*ur + uc*uc */
+#define LBM_DIAG_MIN_RHO 7
+#define LBM_DIAG_MAX_RHO 8
+#define LBM_DIAG_NONFINITE 9  /* nodes where rho, ur, uc (or conc, if given) is NaN or +-inf; exact, as a double */
+#define LBM_DIAG_SUM_C 10     /* conc; slots 10-15 are 0.0 without conc */
+#define LBM_DIAG_SUM_CUR 11   /* conc*ur */
+#define LBM_DIAG_SUM_CUC 12   /* conc*uc */
+#define LBM_DIAG_MIN_C 13
+#define LBM_DIAG_MAX_C 14
+#define LBM_DIAG_SUM_C2 15    /* conc*conc */
+#define LBM_DIAG_SUM_DEV2 16  /* (ur - profile[c]) * (ur - profile[c]); 0.0 without profile */
+/* row values of rows [row_begin, row_end) of the fields into table [LBM_DIAG_NQ][table_rows] (device): row r lands
+ * at table[q * table_rows + table_row0 + r], nothing else is written -- a slab fills its rows of a global table.
+ * conc, profile (device, [C]) may be NULL.  Enqueues one launch; capturable. */
+int lbm_diag_rows(double* table, int table_rows, int table_row0, const double* rho, const double* u,
+                  const double* conc, const double* profile, int R, int C, int row_begin, int row_end,
+                  lbm_stream_t s);
+/* rows [row_begin, row_end) of a table to out_dev [LBM_DIAG_NQ] (device).  Enqueues one launch; capturable. */
+int lbm_diag_fold(double* out_dev, const double* table, int table_rows, int row_begin, int row_end, lbm_stream_t s);
+/* the same fold of a table in host memory, in plain C++ without any device call: for ranks that gather their row
+ * tables over a transport of their own */
+int lbm_diag_fold_host(double* out, const double* table_host, int table_rows, int row_begin, int row_end);
+/* the moments recorded by the last lbm_solver_step(.., 1), reduced over rows [row_begin, row_end): out_host
+ * [LBM_DIAG_NQ], and the row table [LBM_DIAG_NQ][R] if table_host is given.  profile_dev may be NULL.  The context
+ * owns the device table and a pinned buffer (allocated on first use); copies LBM_DIAG_NQ doubles (or the table)
+ * and synchronises. */
+int lbm_solver_diag(lbm_solver* sv, const double* profile_dev, int row_begin, int row_end, double* out_host,
+                    double* table_host);
+/* the same over rho, u, C of the streamed state, formed on the device as lbm_ade_solver_get_state forms them:
+ * equal to the fold of what get_state returns */
+int lbm_ade_solver_diag(lbm_ade_solver* sv, const double* profile_dev, int row_begin, int row_end, double* out_host,
+                        double* table_host);
+/* The stopping rule of the reference drivers (horizontal_poiseuille_test.cpp:113-126) on the device.  t counts the
+ * iterations of the call from 0.  At every t > 0 with t % interval == offset the watched value -- the sum `quantity`
+ * over rows [row_begin, row_end) of the moments of iteration t - 1, divided by the node count of that range -- is
+ * formed; the run stops (converged = 1) when |value / old - 1| < tolerance, otherwise old = value.  It also ends
+ * at max_steps (converged = 0; no check at t == max_steps).  Between checks the steps go through lbm_solver_step /
+ * lbm_ade_solver_step (multi-step blocks fuse as ever); one host synchronisation of LBM_DIAG_NQ doubles per check.
+ * steps_done, converged, last_value (the last value formed; old_value if none was) may be NULL. */
+typedef struct lbm_converge {
+  int quantity;         /* a LBM_DIAG_SUM_* index */
+  int interval, offset; /* reference: 100, 1 */
+  double tolerance;     /* reference: 1e-12 */
+  double old_value;     /* the first "old" value; reference: 1.0 */
+  int row_begin, row_end;
+} lbm_converge;
+int lbm_solver_run_until(lbm_solver* sv, const lbm_converge* cv, int max_steps, int* steps_done, int* converged,
+                         double* last_value);
+int lbm_ade_solver_run_until(lbm_ade_solver* sv, const lbm_converge* cv, int max_steps, int* steps_done,
+                             int* converged, double* last_value);
+
 /* Tuning table.  Launch-shape keys (every setting produces identical results) and the three
  * implementation switches, which select between a model's two collision implementations:
  *   "bgk_fast", "kbc_fast", "cg_fused" (default 1): the reassociated collision / the one-launch

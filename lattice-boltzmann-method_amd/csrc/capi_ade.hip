@@ -693,6 +693,7 @@ struct lbm_ade_solver {
   int cur;    // lat[cur] holds the state
   bool post;  // the state is post-collision (P-form); false: pre-collision f_adve, g_adve
   long long steps, launches;
+  lbm::DiagBuf diag;  // row table and result buffers of lbm_ade_solver_diag (allocated by its first call)
   double* f(int k) const { return lat[k]; }
   double* h(int k) const { return lat[k] + 9 * g.plane_stride; }
 };
@@ -832,6 +833,7 @@ int lbm_ade_solver_destroy(lbm_ade_solver* sv) {
   if (sv->lat[0] || sv->lat[1]) (void)hipStreamSynchronize(sv->st);
   for (double* p : {sv->lat[0], sv->lat[1], sv->dense, sv->stage, sv->rho, sv->u, sv->conc, sv->carry[0], sv->carry[1]})
     if (p) (void)hipFree(p);
+  sv->diag.release();
   delete sv;
   return LBM_OK;
 }
@@ -880,16 +882,12 @@ int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
   return LBM_OK;
 }
 
-// What the reference loop holds after the iterations run so far: f_adve, g_adve (AoS [R][C][9]),
-// rho = calc_rho(f_adve), u = calc_u(f_adve, rho) (AoS [R][C][2]), C = calc_rho(g_adve), through the parity
-// operators whatever the form and with or without buoyancy (u is calc_u(f_adve, rho): the velocity that enters the
-// next step's equilibria is u + u_shift beta (C - c_ref)).  The post-collision state is streamed lazily (lbm_stream: the fix-ups are the
-// same for both distributions) into the dead time level.  Any output may be NULL; synchronises.
-int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, double* rho, double* u, double* conc) {
-  LBM_REQUIRE(sv, "lbm_ade_solver_get_state: NULL solver");
+// The device half of lbm_ade_solver_get_state, shared with lbm_ade_solver_diag: enqueues what leaves f_adve, g_adve in
+// time level *k_out (the state itself, or its streamed image with every table's and edge's rule applied, in the dead
+// level) and, if wanted, sv->rho / sv->u = the parity-operator moments of that f and sv->conc = calc_rho of that g.
+static int ade_solver_form_state(lbm_ade_solver* sv, const char* fn, bool want_moments, bool want_conc, int* k_out) {
   const lbm_geom& g = sv->g;
   const int R = g.R, C = g.C;
-  const size_t n = (size_t)R * C;
   int k = sv->cur;
   const lbm_geom dg{R, C, 0, 0, 0};
   const bool fixed = sv->post && sv->fixed;
@@ -904,7 +902,7 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
   if (sv->post) {
     const AdeIwallNode* wall_nodes;
     int n_wall_nodes;
-    int rc = ade_iwalls_check("lbm_ade_solver_get_state", sv->walls, &g, &wall_nodes, &n_wall_nodes);
+    int rc = ade_iwalls_check(fn, sv->walls, &g, &wall_nodes, &n_wall_nodes);
     if (rc) return rc;
     const dim3 grid_w((n_wall_nodes + 255) / 256);
     // the open table, in the reference's order and without touching the carry: its f slots with the carry the next step
@@ -926,7 +924,7 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
       LBM_CHECK_LAUNCH();
     }
     AdeWalls sw;
-    rc = ade_scalar_bc_check("lbm_ade_solver_get_state", fixed ? &sv->sbc : nullptr, &sv->bc, &sw);
+    rc = ade_scalar_bc_check(fn, fixed ? &sv->sbc : nullptr, &sv->bc, &sw);
     if (rc) return rc;
     // g gathers as BOUNCE_BACK at a FIXED column; the FIXED edges then take their rule with u = the reference-order
     // calc_u of the streamed f
@@ -960,34 +958,81 @@ int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, doubl
       LBM_CHECK_LAUNCH();
     }
   }
+  if (want_moments && !have_u)
+    if (int rc = moments_of_f()) return rc;
+  if (want_conc) {
+    int rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->h(k), &g, 0, R, sv->st);
+    if (!rc) rc = lbm_calc_rho(sv->conc, sv->dense, R, C, sv->st);
+    if (rc) return rc;
+  }
+  *k_out = k;
+  return LBM_OK;
+}
+
+// What the reference loop holds after the iterations run so far: f_adve, g_adve (AoS [R][C][9]),
+// rho = calc_rho(f_adve), u = calc_u(f_adve, rho) (AoS [R][C][2]), C = calc_rho(g_adve), through the parity
+// operators whatever the form and with or without buoyancy (u is calc_u(f_adve, rho): the velocity that enters the
+// next step's equilibria is u + u_shift beta (C - c_ref)).  The post-collision state is streamed lazily (lbm_stream: the fix-ups are the
+// same for both distributions) into the dead time level.  Any output may be NULL; synchronises.
+int lbm_ade_solver_get_state(lbm_ade_solver* sv, double* f, double* g_out, double* rho, double* u, double* conc) {
+  LBM_REQUIRE(sv, "lbm_ade_solver_get_state: NULL solver");
+  const lbm_geom& g = sv->g;
+  const int R = g.R, C = g.C;
+  const size_t n = (size_t)R * C;
+  int k;
+  int rc = ade_solver_form_state(sv, "lbm_ade_solver_get_state", rho || u, conc != nullptr, &k);
+  if (rc) return rc;
   if (f) {
-    int rc = lbm_soa_to_aos_pitched(sv->stage, sv->f(k), R, C, 9, g.plane_stride, g.row_pitch, sv->st);
+    rc = lbm_soa_to_aos_pitched(sv->stage, sv->f(k), R, C, 9, g.plane_stride, g.row_pitch, sv->st);
     if (rc) return rc;
     LBM_CHECK_HIP(hipMemcpyAsync(f, sv->stage, n * 9 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
   }
   if (rho || u) {
-    if (!have_u)
-      if (int rc = moments_of_f()) return rc;
     if (rho) LBM_CHECK_HIP(hipMemcpyAsync(rho, sv->rho, n * sizeof(double), hipMemcpyDeviceToHost, sv->st));
     if (u) {
-      int rc = lbm_soa_to_aos(sv->stage, sv->u, R, C, 2, sv->st);
+      rc = lbm_soa_to_aos(sv->stage, sv->u, R, C, 2, sv->st);
       if (rc) return rc;
       LBM_CHECK_HIP(hipMemcpyAsync(u, sv->stage, n * 2 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
     }
   }
   if (g_out) {
-    int rc = lbm_soa_to_aos_pitched(sv->stage, sv->h(k), R, C, 9, g.plane_stride, g.row_pitch, sv->st);
+    rc = lbm_soa_to_aos_pitched(sv->stage, sv->h(k), R, C, 9, g.plane_stride, g.row_pitch, sv->st);
     if (rc) return rc;
     LBM_CHECK_HIP(hipMemcpyAsync(g_out, sv->stage, n * 9 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
   }
-  if (conc) {
-    int rc = lbm_lattice_copy_rows(sv->dense, &dg, 0, sv->h(k), &g, 0, R, sv->st);
-    if (!rc) rc = lbm_calc_rho(sv->conc, sv->dense, R, C, sv->st);
-    if (rc) return rc;
-    LBM_CHECK_HIP(hipMemcpyAsync(conc, sv->conc, n * sizeof(double), hipMemcpyDeviceToHost, sv->st));
-  }
+  if (conc) LBM_CHECK_HIP(hipMemcpyAsync(conc, sv->conc, n * sizeof(double), hipMemcpyDeviceToHost, sv->st));
   LBM_CHECK_HIP(hipStreamSynchronize(sv->st));
   return LBM_OK;
+}
+
+int lbm_ade_solver_diag(lbm_ade_solver* sv, const double* profile_dev, int row_begin, int row_end, double* out_host,
+                        double* table_host) {
+  LBM_REQUIRE(sv && out_host, "lbm_ade_solver_diag: NULL argument (solver, out_host)");
+  int rc = diag_range_check("lbm_ade_solver_diag", sv->g.R, row_begin, row_end);
+  if (rc) return rc;
+  int k;
+  rc = ade_solver_form_state(sv, "lbm_ade_solver_diag", true, true, &k);
+  if (rc) return rc;
+  return diag_reduce("lbm_ade_solver_diag", sv->diag, sv->rho, sv->u, sv->conc, profile_dev, sv->g.R, sv->g.C, row_begin,
+                     row_end, out_host, table_host, sv->st);
+}
+
+int lbm_ade_solver_run_until(lbm_ade_solver* sv, const lbm_converge* cv, int max_steps, int* steps_done, int* converged,
+                             double* last_value) {
+  int rc = diag_converge_check("lbm_ade_solver_run_until", cv, max_steps);
+  if (rc) return rc;
+  LBM_REQUIRE(sv, "lbm_ade_solver_run_until: NULL solver");
+  rc = diag_range_check("lbm_ade_solver_run_until", sv->g.R, cv->row_begin, cv->row_end);
+  if (rc) return rc;
+  const double nodes = (double)(cv->row_end - cv->row_begin) * sv->g.C;
+  return diag_run_until(
+      cv, max_steps, steps_done, converged, last_value, [&](int n) { return lbm_ade_solver_step(sv, n); },
+      [&](double* v) {
+        double out[LBM_DIAG_NQ] = {0.0};
+        const int rc2 = lbm_ade_solver_diag(sv, nullptr, cv->row_begin, cv->row_end, out, nullptr);
+        *v = out[cv->quantity] / nodes;
+        return rc2;
+      });
 }
 
 int lbm_ade_solver_sync(lbm_ade_solver* sv) {

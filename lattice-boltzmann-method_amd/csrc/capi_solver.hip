@@ -43,6 +43,7 @@ struct lbm_solver {
   double* seam[2] = {nullptr, nullptr};
   long long seam_plane = 0;
   lbm::SideStream seam_side;
+  lbm::DiagBuf diag;  // row table and result buffers of lbm_solver_diag (allocated by its first call)
 };
 static constexpr int kSeamMaxDepth = 5;
 
@@ -81,6 +82,13 @@ static int solver_fused(lbm_solver* sv, double* rho, double* u, bool with_ibm_ov
   if (sv->model == LBM_MODEL_BGK)
     return lbm_bgk_stream_collide(dst, src, &sv->g, &sv->bc, &sv->bgk, 0, sv->g.R, rho, u, sv->st);
   return lbm_kbc_stream_collide(dst, src, &sv->g, &sv->bc, &sv->kbc, 0, sv->g.R, rho, u, sv->st);
+}
+
+// the message of every call that needs the moments of a step(.., record_moments = 1)
+static int solver_need_moments(const lbm_solver* sv, const char* fn) {
+  if (sv->have_moments) return LBM_OK;
+  set_error("%s: no step(.., record_moments=1) since the last set_f", fn);
+  return LBM_ERR_STATE;
 }
 
 extern "C" {
@@ -149,6 +157,7 @@ int lbm_solver_destroy(lbm_solver* sv) {
   for (double* p : {sv->lat[0], sv->lat[1], sv->stage, sv->rho, sv->u, sv->band, sv->seam[0], sv->seam[1], sv->box[0], sv->box[1],
                     sv->box_rho, sv->box_u})
     if (p) (void)hipFree(p);
+  sv->diag.release();
   delete sv;
   return LBM_OK;
 }
@@ -435,10 +444,7 @@ int lbm_solver_step(lbm_solver* sv, int n, int record_moments) {
 
 int lbm_solver_get_moments_aos(lbm_solver* sv, double* rho_host, double* u_host) {
   LBM_REQUIRE(sv && rho_host && u_host, "lbm_solver_get_moments_aos: NULL argument");
-  if (!sv->have_moments) {
-    set_error("lbm_solver_get_moments_aos: no step(.., record_moments=1) since the last set_f");
-    return LBM_ERR_STATE;
-  }
+  if (int rc = solver_need_moments(sv, "lbm_solver_get_moments_aos")) return rc;
   const size_t n = (size_t)sv->g.R * sv->g.C;
   LBM_CHECK_HIP(hipMemcpyAsync(rho_host, sv->rho, n * sizeof(double), hipMemcpyDeviceToHost, sv->st));
   int rc = lbm_soa_to_aos(sv->stage, sv->u, sv->g.R, sv->g.C, 2, sv->st);
@@ -446,6 +452,34 @@ int lbm_solver_get_moments_aos(lbm_solver* sv, double* rho_host, double* u_host)
   LBM_CHECK_HIP(hipMemcpyAsync(u_host, sv->stage, n * 2 * sizeof(double), hipMemcpyDeviceToHost, sv->st));
   LBM_CHECK_HIP(hipStreamSynchronize(sv->st));
   return LBM_OK;
+}
+
+int lbm_solver_diag(lbm_solver* sv, const double* profile_dev, int row_begin, int row_end, double* out_host,
+                    double* table_host) {
+  LBM_REQUIRE(sv && out_host, "lbm_solver_diag: NULL argument (solver, out_host)");
+  int rc = diag_range_check("lbm_solver_diag", sv->g.R, row_begin, row_end);
+  if (!rc) rc = solver_need_moments(sv, "lbm_solver_diag");
+  if (rc) return rc;
+  return diag_reduce("lbm_solver_diag", sv->diag, sv->rho, sv->u, nullptr, profile_dev, sv->g.R, sv->g.C, row_begin, row_end,
+                     out_host, table_host, sv->st);
+}
+
+int lbm_solver_run_until(lbm_solver* sv, const lbm_converge* cv, int max_steps, int* steps_done, int* converged,
+                         double* last_value) {
+  int rc = diag_converge_check("lbm_solver_run_until", cv, max_steps);
+  if (rc) return rc;
+  LBM_REQUIRE(sv, "lbm_solver_run_until: NULL solver");
+  rc = diag_range_check("lbm_solver_run_until", sv->g.R, cv->row_begin, cv->row_end);
+  if (rc) return rc;
+  const double nodes = (double)(cv->row_end - cv->row_begin) * sv->g.C;
+  return diag_run_until(
+      cv, max_steps, steps_done, converged, last_value, [&](int n) { return lbm_solver_step(sv, n, 1); },
+      [&](double* v) {
+        double out[LBM_DIAG_NQ] = {0.0};
+        const int rc2 = lbm_solver_diag(sv, nullptr, cv->row_begin, cv->row_end, out, nullptr);
+        *v = out[cv->quantity] / nodes;
+        return rc2;
+      });
 }
 
 int lbm_solver_attach_ibm(lbm_solver* sv, lbm_ibm* ib, double guo_a, double guo_b) {

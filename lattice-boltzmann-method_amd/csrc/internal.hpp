@@ -81,6 +81,50 @@ int ade_collide_from(const char* fn, const AdeCall& call, double* fp, double* gp
 // pre-collision state f, written to the call's carry_out (one small launch; none without a listed node)
 int ade_carry_set(const char* fn, AdeCall* call, bool reads, const double* carry_in, double* carry_out);
 int ade_open_prime_from(const AdeCall& call, const double* f, hipStream_t st);
+// capi_diag.hip: what a solver context keeps for its diagnostics -- the row table [LBM_DIAG_NQ][R], the folded values on the
+// device and a pinned host buffer for them, all allocated by the first diag_reduce and kept.
+struct DiagBuf {
+  double* table = nullptr;
+  double* out_dev = nullptr;
+  double* pinned = nullptr;
+  void release();
+};
+// rows [row_begin, row_end) of the dense fields (conc, profile may be NULL) reduced on `st`: out_host [LBM_DIAG_NQ], and
+// the row table [LBM_DIAG_NQ][R] if table_host is given (rows outside the range: 0.0).  Arguments are checked under the
+// caller's name fn before any device call; synchronises st.
+int diag_reduce(const char* fn, DiagBuf& buf, const double* rho, const double* u, const double* conc, const double* profile,
+                int R, int C, int row_begin, int row_end, double* out_host, double* table_host, hipStream_t st);
+int diag_range_check(const char* fn, int R, int row_begin, int row_end);
+// the rule's own fields, checked before the context is looked at (its rows: diag_range_check, once the context is known)
+int diag_converge_check(const char* fn, const lbm_converge* cv, int max_steps);
+// the loop of lbm_solver_run_until / lbm_ade_solver_run_until (lbm_hip.h) over a context's own step(n) -- n iterations, the
+// last one leaving moments to reduce -- and value(&v): the watched value of the iteration run last
+template <class Step, class Value>
+int diag_run_until(const lbm_converge* cv, int max_steps, int* steps_done, int* converged, double* last_value, Step step,
+                   Value value) {
+  int t = 0, done = 0;
+  double old = cv->old_value, last = cv->old_value;
+  while (t < max_steps) {
+    if (t > 0 && t % cv->interval == cv->offset) {
+      if (int rc = value(&last)) return rc;
+      const double rel = last / old - 1.0;
+      if ((rel < 0 ? -rel : rel) < cv->tolerance) {
+        done = 1;
+        break;
+      }
+      old = last;
+    }
+    long long next = (long long)t - t % cv->interval + cv->offset;  // the next check point after t
+    if (next <= t) next += cv->interval;
+    const int n = (int)(next < max_steps ? next : max_steps) - t;
+    if (int rc = step(n)) return rc;
+    t += n;
+  }
+  if (steps_done) *steps_done = t;
+  if (converged) *converged = done;
+  if (last_value) *last_value = last;
+  return LBM_OK;
+}
 // NumPy .npy (v1.0, little-endian f64, C order) writer shared by the snapshot objects
 int write_npy(const char* path, const double* data, const std::vector<long>& shape);
 

@@ -2,7 +2,9 @@
 // Same flow parameters (:50-67), same convergence rule (:113-126), same L2 check (:163-175);
 // the hand-written loop body (:130-152: calc_rho, calc_incomp_u, incomp_equilibrium, collision,
 // pressure-periodic rows, advect, halfway bounce-back columns) is ONE fused launch per step.
-//   usage: horizontal_poiseuille_test [--H 21] [--W 21] [--T 8301] [--dump prefix]
+//   usage: horizontal_poiseuille_test [--H 21] [--W 21] [--T 8301] [--dump prefix] [--device-check 1]
+// --device-check 1: the convergence rule runs through Solver::run_until and the L2 check comes from the per-row
+// LBM_DIAG_SUM_DEV2 of Solver::diag against the uploaded parabola -- no field leaves the device inside the loop.
 #include <cassert>
 #include <cmath>
 #include <iostream>
@@ -18,6 +20,7 @@ int main(int argc, char** argv) {
   const int H = std::stoi(arg_value(argc, argv, "--H", "21"));
   const int W = std::stoi(arg_value(argc, argv, "--W", "21"));
   const std::string dump = arg_value(argc, argv, "--dump", "");
+  const bool device_check = std::stoi(arg_value(argc, argv, "--device-check", "0")) != 0;
   cout << "T=" << T << "\nH=" << H << "; W=" << W << endl;
   const double tau = std::sqrt(3.0 / 16.0) + 0.5;
   const double omega = 1.0 / tau;
@@ -63,7 +66,12 @@ int main(int argc, char** argv) {
       t += n;
     };
     cout << "main loop starts" << endl;
-    while (t < T) {
+    if (device_check) {  // the same rule, same check points, formed on the device
+      const lbm::RunResult run = sv.run_until(lbm::converge_rule(LBM_DIAG_SUM_UR, t_interval, 1, tolerance, old_mean), T);
+      t = run.steps;
+      if (run.converged) cout << "last t=" << t << endl;
+    }
+    while (!device_check && t < T) {
       if (t % t_interval == 1) {  // :113-126, u = the moments of iteration t-1
         double mean = 0.0;
         for (size_t i = 0; i < (size_t)H * W; ++i) mean += uh[2 * i];
@@ -87,7 +95,18 @@ int main(int argc, char** argv) {
     }
     den = 1.0 / std::sqrt(den);
     double sum = 0.0;
-    for (int r = 1; r < H - 1; ++r) {
+    const bool device_l2 = device_check && t > 0;
+    if (device_l2) {  // e of every row = its LBM_DIAG_SUM_DEV2 against the parabola
+      lbm::Field profile(1, W, 1);
+      profile.from_host(ua);
+      std::vector<double> table;
+      sv.diag(profile.data(), 0, H, &table);
+      for (int r = 1; r < H - 1; ++r) sum += std::sqrt(table[(size_t)LBM_DIAG_SUM_DEV2 * H + r]) * den;
+      auto m = sv.moments();  // for --dump, after the loop
+      rhoh = std::move(m.first);
+      uh = std::move(m.second);
+    }
+    for (int r = 1; r < H - 1 && !device_l2; ++r) {
       double e = 0.0;
       for (int c = 0; c < W; ++c) {
         const double d = uh[2 * ((size_t)r * W + c)] - ua[c];

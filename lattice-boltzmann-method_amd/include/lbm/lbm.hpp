@@ -103,6 +103,19 @@ struct BoundarySet : lbm_bc {
   BoundarySet() : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0} {}
 };
 
+// What run_until returns: the iterations done, whether the rule fired, the last watched value formed.
+struct RunResult {
+  int steps;
+  bool converged;
+  double last_value;
+};
+// The reference drivers' stopping rule (horizontal_poiseuille_test.cpp:113-126) for run_until: the mean of `quantity`
+// over rows [row_begin, row_end) every `interval` iterations; row_end < 0: all rows of the solver.
+inline lbm_converge converge_rule(int quantity = LBM_DIAG_SUM_UR, int interval = 100, int offset = 1, double tolerance = 1e-12,
+                                  double old_value = 1.0, int row_begin = 0, int row_end = -1) {
+  return lbm_converge{quantity, interval, offset, tolerance, old_value, row_begin, row_end};
+}
+
 class Solver {  // single-phase BGK / KBC block, wraps lbm_solver
  public:
   static Solver bgk(int R, int C, double omega, bool incompressible, const lbm_bc& bc = BoundarySet(),
@@ -145,6 +158,24 @@ class Solver {  // single-phase BGK / KBC block, wraps lbm_solver
     check(lbm_solver_attach_ibm(h_, ib, a, b));
   }
   void sync() { check(lbm_solver_sync(h_)); }
+  // the LBM_DIAG_NQ diagnostics of the moments of the last step(.., true), reduced on the device over rows
+  // [row_begin, row_end) (row_end < 0: all); profile_dev: device array [C] for LBM_DIAG_SUM_DEV2; table: the row table
+  // [LBM_DIAG_NQ][R] as well
+  std::vector<double> diag(const double* profile_dev = nullptr, int row_begin = 0, int row_end = -1,
+                           std::vector<double>* table = nullptr) {
+    std::vector<double> out(LBM_DIAG_NQ);
+    if (table) table->resize((size_t)LBM_DIAG_NQ * R_);
+    check(lbm_solver_diag(h_, profile_dev, row_begin, row_end < 0 ? R_ : row_end, out.data(), table ? table->data() : nullptr));
+    return out;
+  }
+  // step until the rule fires or max_steps are done, the check running on the device (lbm_solver_run_until)
+  RunResult run_until(lbm_converge cv, int max_steps) {
+    if (cv.row_end < 0) cv.row_end = R_;
+    int steps = 0, conv = 0;
+    double last = 0.0;
+    check(lbm_solver_run_until(h_, &cv, max_steps, &steps, &conv, &last));
+    return {steps, conv != 0, last};
+  }
   lbm_solver* handle() { return h_; }
   int rows() const { return R_; }
   int cols() const { return C_; }
@@ -297,6 +328,21 @@ class AdeSolver {
   }
   long long launches() const { return lbm_ade_solver_launches(h_); }
   void sync() { check(lbm_ade_solver_sync(h_)); }
+  // the LBM_DIAG_NQ diagnostics of rho, u, C of the streamed state (what state() returns), reduced on the device
+  std::vector<double> diag(const double* profile_dev = nullptr, int row_begin = 0, int row_end = -1,
+                           std::vector<double>* table = nullptr) {
+    std::vector<double> out(LBM_DIAG_NQ);
+    if (table) table->resize((size_t)LBM_DIAG_NQ * R_);
+    check(lbm_ade_solver_diag(h_, profile_dev, row_begin, row_end < 0 ? R_ : row_end, out.data(), table ? table->data() : nullptr));
+    return out;
+  }
+  RunResult run_until(lbm_converge cv, int max_steps) {
+    if (cv.row_end < 0) cv.row_end = R_;
+    int steps = 0, conv = 0;
+    double last = 0.0;
+    check(lbm_ade_solver_run_until(h_, &cv, max_steps, &steps, &conv, &last));
+    return {steps, conv != 0, last};
+  }
   lbm_ade_solver* handle() { return h_; }
 
  private:

@@ -30,6 +30,13 @@ ADE_FACE_ROW_POS, ADE_FACE_ROW_NEG, ADE_FACE_COL_POS, ADE_FACE_COL_NEG = 0x91, 0
 # f rules of the open boundaries (LBM_ADE_OPEN_*)
 ADE_OPEN_BOUNCE_BACK, ADE_OPEN_SPECULAR_ROW, ADE_OPEN_SPECULAR_COL, ADE_OPEN_ABB, ADE_OPEN_ABB_EXTRAPOLATED = 1, 2, 3, 4, 5
 
+# value slots of the diagnostics (LBM_DIAG_*): lbm_diag_rows / lbm_diag_fold / Solver.diag / AdeSolver.diag
+DIAG_NQ = 17
+(DIAG_SUM_RHO, DIAG_SUM_UR, DIAG_SUM_UC, DIAG_SUM_MR, DIAG_SUM_MC, DIAG_SUM_KE, DIAG_MAX_U2, DIAG_MIN_RHO, DIAG_MAX_RHO,
+ DIAG_NONFINITE, DIAG_SUM_C, DIAG_SUM_CUR, DIAG_SUM_CUC, DIAG_MIN_C, DIAG_MAX_C, DIAG_SUM_C2, DIAG_SUM_DEV2) = range(DIAG_NQ)
+DIAG_NAMES = ("SUM_RHO", "SUM_UR", "SUM_UC", "SUM_MR", "SUM_MC", "SUM_KE", "MAX_U2", "MIN_RHO", "MAX_RHO", "NONFINITE",
+              "SUM_C", "SUM_CUR", "SUM_CUC", "MIN_C", "MAX_C", "SUM_C2", "SUM_DEV2")
+
 _dp = ct.POINTER(ct.c_double)
 
 
@@ -125,6 +132,18 @@ class AdeBuoyancy(ct.Structure):
 
     def __init__(self, beta=(0.0, 0.0), c_ref=0.0, u_shift=1.0, guo=(1.0 / 3.0, 1.0 / 9.0)):
         super().__init__(beta[0], beta[1], c_ref, u_shift, guo[0], guo[1])
+
+
+class Converge(ct.Structure):
+    """lbm_converge: the stopping rule of run_until.  The watched value is the sum `quantity` (a DIAG_SUM_* index) over rows
+    [row_begin, row_end) divided by their node count, formed at every iteration count t > 0 with t % interval == offset
+    from the moments of iteration t - 1; the run stops when |value / old - 1| < tolerance.  The defaults are the
+    reference drivers' (SUM_UR, 100, 1, 1e-12, 1.0); row_end=None: all rows of the solver."""
+    _fields_ = [("quantity", ct.c_int), ("interval", ct.c_int), ("offset", ct.c_int), ("tolerance", ct.c_double),
+                ("old_value", ct.c_double), ("row_begin", ct.c_int), ("row_end", ct.c_int)]
+
+    def __init__(self, quantity=DIAG_SUM_UR, interval=100, offset=1, tolerance=1e-12, old_value=1.0, row_begin=0, row_end=None):
+        super().__init__(quantity, interval, offset, tolerance, old_value, row_begin, -1 if row_end is None else row_end)
 
 
 class LbmError(RuntimeError):
@@ -315,6 +334,16 @@ class Lib:
     def default_plane_pad(self, R, C):
         return int(self.raw.lbm_default_plane_pad(R, C))
 
+    def diag_fold_host(self, table, row_begin=0, row_end=None):
+        """lbm_diag_fold_host: rows [row_begin, row_end) of a host row table [DIAG_NQ, rows] -> the DIAG_NQ values
+        (diag_rows / diag_fold, the device calls, go through __getattr__ like every other entry point)"""
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        assert table.ndim == 2 and table.shape[0] == DIAG_NQ, table.shape
+        out = np.empty(DIAG_NQ)
+        self.__getattr__("diag_fold_host")(_hptr(out), _hptr(table), table.shape[1], int(row_begin),
+                                           int(table.shape[1] if row_end is None else row_end))
+        return out
+
     def reset_tuning(self):
         for k in (b"variant", b"nt", b"grid_cap", b"block", b"rows", b"xcd_swizzle", b"tb_rows", b"tb_block", b"tb_order", b"sw_rows", b"sw_waves", b"solver_depth", b"cg_fused", b"cg_tile", b"cg_xcd", b"kbc_fast", b"kbc_depth", b"bgk_fast", b"cg_strip", b"cg_rows", b"cg_split", b"sw_split", b"solver_depth_walls", b"ibm_depth", b"ibm_gate", b"bgk_fast_delta", b"pressure_depth", b"halo_grid", b"cg_strip2", b"cg_rows2", b"sw_pair", b"sw_pf2", b"cg_strip_xcd", b"cg_merge", b"cg_frame_beside", b"ring_period", b"ibm_step_opt", b"ibm_step_split", b"ibm_step_chain", b"ibm_box", b"ibm_box_overlap", b"bg_priority", b"ibm_chain_kernel", b"ibm_chain_wgs", b"ibm_box_sole", b"sw_ldsring", b"ring_ipc_timeout_ms", b"cg_big", b"cg_big_xcd", b"ring_ipc_force_cached", b"ring_ipc_cached_ok", b"row_pad", b"cg_walk_rows", b"cg_walk_tile_xcd", b"sw_cols2"):
             self.set_tuning(k, -1)
@@ -338,6 +367,25 @@ def _hptr(a):
 
 def _stream(s):
     return ct.c_void_p(0 if s is None else int(s))
+
+
+def _diag(call, h, R, profile, row_begin, row_end, table):
+    """shared by Solver.diag / AdeSolver.diag: the DIAG_NQ values of rows [row_begin, row_end), with the row table
+    [DIAG_NQ, R] as a second result if table"""
+    out = np.empty(DIAG_NQ)
+    tab = np.empty((DIAG_NQ, R)) if table else None
+    call(h, _ptr(profile), int(row_begin), int(R if row_end is None else row_end), _hptr(out),
+         _hptr(tab) if table else None)
+    return (out, tab) if table else out
+
+
+def _run_until(call, h, R, converge, max_steps):
+    """shared by Solver.run_until / AdeSolver.run_until: (steps_done, converged, last_value)"""
+    cv = Converge(converge.quantity, converge.interval, converge.offset, converge.tolerance, converge.old_value,
+                  converge.row_begin, R if converge.row_end < 0 else converge.row_end)
+    steps, conv, last = ct.c_int(), ct.c_int(), ct.c_double()
+    call(h, ct.byref(cv), int(max_steps), ct.byref(steps), ct.byref(conv), ct.byref(last))
+    return steps.value, bool(conv.value), last.value
 
 
 class Solver:
@@ -391,6 +439,15 @@ class Solver:
 
     def sync(self):
         self.lib.solver_sync(self.h)
+
+    def diag(self, profile=None, row_begin=0, row_end=None, table=False):
+        """the DIAG_NQ diagnostics of the moments of the last step(.., record_moments=True), reduced on the device;
+        profile: a device array [C] (float64 torch tensor or address) for DIAG_SUM_DEV2; table=True: (values, row table)"""
+        return _diag(self.lib.solver_diag, self.h, self.R, profile, row_begin, row_end, table)
+
+    def run_until(self, converge, max_steps):
+        """step until the rule of `converge` (Converge) fires or max_steps are done: (steps_done, converged, last_value)"""
+        return _run_until(self.lib.solver_run_until, self.h, self.R, converge, max_steps)
 
     def checkpoint_save(self, path):
         self.lib.solver_checkpoint_save(self.h, str(path).encode())
@@ -487,6 +544,15 @@ class AdeSolver:
 
     def sync(self):
         self.lib.ade_solver_sync(self.h)
+
+    def diag(self, profile=None, row_begin=0, row_end=None, table=False):
+        """the DIAG_NQ diagnostics of rho, u, C of the streamed state (what get_state returns), reduced on the device;
+        profile: a device array [C] for DIAG_SUM_DEV2; table=True: (values, row table)"""
+        return _diag(self.lib.ade_solver_diag, self.h, self.R, profile, row_begin, row_end, table)
+
+    def run_until(self, converge, max_steps):
+        """step until the rule of `converge` (Converge) fires or max_steps are done: (steps_done, converged, last_value)"""
+        return _run_until(self.lib.ade_solver_run_until, self.h, self.R, converge, max_steps)
 
     def launches(self):
         return int(self.lib.raw.lbm_ade_solver_launches(self.h))
