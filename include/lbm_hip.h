@@ -1021,14 +1021,18 @@ int lbm_ring_pressure_start_kbc(lbm_ring* rg, lbm_slab_pressure* sl, double* pos
  *     dst[dst_lattice][q_dst][r0 + k dr][c0 + k dc] = src[src_lattice][q_src][sr0 + k sdr][sc0 + k sdc],
  * k = 0 .. count-1.  Slices are added in the order the driver executes them; where two write the
  * same destination element the later one wins (resolved on the host, the device pass is race-free).
- * dst / src of lbm_links_apply: one pointer per lattice (typically f_adve and f_coll of each block). */
+ * dst / src of lbm_links_apply: one pointer per lattice (typically f_adve and f_coll of each block).
+ * In place (dst[i] == src[j]) every link reads the value from before the call, which holds only while no
+ * link reads from lattice j an element that a link of the same table writes in lattice i.  A call with such
+ * a pair is refused before anything is enqueued: split the table in two and apply one after the other. */
 typedef struct lbm_links lbm_links;
 int lbm_links_create(lbm_links** out, int n_lattices /* <= 8 */, const lbm_geom* geoms);
 int lbm_links_add(lbm_links* t, int dst_lat, int q_dst, int r0, int c0, int dr, int dc, int src_lat,
                   int q_src, int sr0, int sc0, int sdr, int sdc, int count);
 /* affine links: dst = scale * src (+ addends[add0 + k add_stride]; add0 < 0: no addend).  scale = -1
  * with an addend is the anti-bounce-back "-f_coll + term" of rectangle_sedimentation_test.cpp:152-170;
- * the addend array is handed to lbm_links_apply_affine (it changes every step there). */
+ * the addend array is handed to lbm_links_apply_affine (it changes every step there).  With add0 >= 0
+ * every index add0 + k add_stride must be >= 0 (both ends are checked; nothing is added otherwise). */
 int lbm_links_add_affine(lbm_links* t, int dst_lat, int q_dst, int r0, int c0, int dr, int dc,
                          int src_lat, int q_src, int sr0, int sc0, int sdr, int sdc, int count,
                          double scale, long long add0, long long add_stride);

@@ -4,10 +4,12 @@
 // index_put_ launches.  A table is built once from slice descriptions in the order the driver
 // executes them; where two slices write the same destination element the later one wins, which is
 // resolved on the host, so the device pass is a race-free element-wise gather
-//     dst[dst_lattice][dst_index] = src[src_lattice][src_index].
+//     dst[dst_lattice][dst_index] = src[src_lattice][src_index]
+// (in place, dst[i] == src[j], only while no link reads what another writes there: apply refuses such a call).
 // Also: the uniform momentum source of decompose_domain_loop.cpp:152-160 on a row window.
 #include <new>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "d2q9.hpp"
@@ -133,6 +135,9 @@ struct lbm_links {
   std::vector<long> dst_off, src_off, add_idx;
   std::vector<double> scale;
   bool affine = false;  // any link with scale != 1 or an addend
+  // chain[i][j]: some link writes lattice i at an offset that some link reads from lattice j -- with dst[i] == src[j]
+  // the gather's result would depend on the order of its threads (finalize fills it, apply refuses such a call)
+  bool chain[lbm::kMaxLinkLattices][lbm::kMaxLinkLattices] = {};
   int n = 0;
   int* d_lat = nullptr;
   long *d_dst = nullptr, *d_src = nullptr, *d_add = nullptr;
@@ -167,7 +172,6 @@ int lbm_links_add_affine(lbm_links* t, int dst_lat, int q_dst, int r0, int c0, i
                          int src_lat, int q_src, int sr0, int sc0, int sdr, int sdc, int count,
                          double scale, long long add0, long long add_stride) {
   LBM_REQUIRE(t && !t->d_lat, "lbm_links_add: NULL or already finalized table");
-  if (scale != 1.0 || add0 >= 0) t->affine = true;
   const int nl = (int)t->geoms.size();
   LBM_REQUIRE(dst_lat >= 0 && dst_lat < nl && src_lat >= 0 && src_lat < nl, "lbm_links_add: lattice index");
   LBM_REQUIRE(q_dst >= 0 && q_dst < 9 && q_src >= 0 && q_src < 9 && count >= 0, "lbm_links_add: bad population / count");
@@ -177,7 +181,11 @@ int lbm_links_add_affine(lbm_links* t, int dst_lat, int q_dst, int r0, int c0, i
     const int r = r0 + k * dr, c = c0 + k * dc, sr = sr0 + k * sdr, sc = sc0 + k * sdc;
     LBM_REQUIRE(r >= 0 && r < gd.R && c >= 0 && c < gd.C && sr >= 0 && sr < gs.R && sc >= 0 && sc < gs.C,
                 "lbm_links_add: slice leaves the lattice (dst %d,%d of %dx%d; src %d,%d of %dx%d)", r, c, gd.R, gd.C, sr, sc, gs.R, gs.C);
+    // the addend index is linear too; a negative one would be stored as "no addend" and the term silently dropped
+    const long long ai = add0 + (long long)k * add_stride;
+    LBM_REQUIRE(add0 < 0 || ai >= 0, "lbm_links_add_affine: addend index %lld of link %d is negative (add0 %lld, add_stride %lld)", ai, k, add0, add_stride);
   }
+  if (scale != 1.0 || add0 >= 0) t->affine = true;
   for (int k = 0; k < count; ++k) {
     const int r = r0 + k * dr, c = c0 + k * dc, sr = sr0 + k * sdr, sc = sc0 + k * sdc;
     const long d = q_dst * gd.plane + gd.at(r, c), s = q_src * gs.plane + gs.at(sr, sc);
@@ -204,6 +212,13 @@ int lbm_links_add_affine(lbm_links* t, int dst_lat, int q_dst, int r0, int c0, i
 int lbm_links_finalize(lbm_links* t) {
   LBM_REQUIRE(t && !t->d_lat, "lbm_links_finalize: NULL or already finalized table");
   t->n = (int)t->lat.size();
+  {
+    std::unordered_set<long> read[kMaxLinkLattices];
+    for (int k = 0; k < t->n; ++k) read[(t->lat[k] >> 4) & 15].insert(t->src_off[k]);
+    for (int k = 0; k < t->n; ++k)
+      for (size_t j = 0; j < t->geoms.size(); ++j)
+        if (read[j].count(t->dst_off[k])) t->chain[t->lat[k] & 15][j] = true;
+  }
   const size_t n = t->n ? t->n : 1;
   LBM_CHECK_HIP(hipMalloc(&t->d_lat, n * sizeof(int)));
   LBM_CHECK_HIP(hipMalloc(&t->d_dst, n * sizeof(long)));
@@ -246,6 +261,11 @@ int lbm_links_apply_affine(lbm_links* t, double* const* dst, const double* const
     p.dst[i] = dst[i];
     p.src[i] = src[i];
   }
+  for (size_t i = 0; i < t->geoms.size(); ++i)
+    for (size_t j = 0; j < t->geoms.size(); ++j)
+      LBM_REQUIRE(!(t->chain[i][j] && dst[i] == src[j]),
+                  "lbm_links_apply: in-place chain: dst[%d] and src[%d] are one buffer, and a link reads from lattice %d an element that a link writes in lattice %d (split the table in two)",
+                  (int)i, (int)j, (int)j, (int)i);
   if (t->affine)
     LBM_KLAUNCH(k_links_apply_affine, dim3((t->n + 255) / 256), dim3(256), 0, as_stream(s), p, t->n, t->d_lat, t->d_dst, t->d_src, t->d_scale, t->d_add, addends);
   else

@@ -105,3 +105,36 @@ def test_newer_entry_points_validate_before_touching_the_gpu():
         lib.pressure_row(one, ct.byref(g), 16, one, one, one, ct.byref(g), 1, ct.c_double(1.0), 0, None)
     with pytest.raises(pylbm.LbmError, match="equal width"):
         lib.pressure_row(one, ct.byref(g), 0, one, one, one, ct.byref(pylbm.Geom(16, 32, 0)), 1, ct.c_double(1.0), 0, None)
+
+
+def test_links_refuse_a_negative_addend_index():
+    """lbm_links_add_affine: with add0 >= 0 the addend index add0 + k add_stride is checked at both ends of the slice like
+    the slice itself -- a negative one would be stored as "no addend" and the wall term silently dropped -- and a refused
+    call adds nothing.  (The in-place chain refusal needs a finalized table, which allocates on a device:
+    tests/test_gpu_links.py.)"""
+    lib = pylbm.Lib()
+    g = pylbm.Geom(16, 16, 0)
+    t = ct.c_void_p()
+    lib.links_create(ct.byref(t), 1, ct.byref(g))
+
+    def add(count, add0, stride, scale=-1.0):
+        lib.links_add_affine(t, 0, 1, 0, 0, 1, 0, 0, 3, 0, 0, 1, 0, count, ct.c_double(scale), ct.c_longlong(add0),
+                             ct.c_longlong(stride))
+
+    try:
+        with pytest.raises(pylbm.LbmError, match="addend index -1 of link 3 is negative"):
+            add(4, 2, -1)                                   # 2, 1, 0, -1
+        with pytest.raises(pylbm.LbmError, match="addend index -9 of link 1 is negative"):
+            add(2, 0, -9)
+        assert lib.raw.lbm_links_count(t) == 0              # nothing was added
+        add(3, 2, -1)                                       # 2, 1, 0: a negative stride that stays inside is fine
+        assert lib.raw.lbm_links_count(t) == 3
+        add(0, 0, -5)                                       # no link, no index
+        add(16, -1, -7)                                     # add0 < 0: no addend, the stride means nothing
+        add(1, 0, -7)
+        assert lib.raw.lbm_links_count(t) == 16
+        with pytest.raises(pylbm.LbmError, match="negative"):
+            add(16, 14, -1, scale=1.0)
+        assert lib.raw.lbm_links_count(t) == 16
+    finally:
+        lib.links_destroy(t)
