@@ -77,6 +77,22 @@ def channel(R, C, u_in, conc_w=1e-3, conc_rows=50):
     return s
 
 
+def build_open(lib, kind, R, C):
+    """the global open tables of the slab suite by name (tests/test_gpu_ade_open_slabs.py and, from cfg["table"], its rank
+    processes tests/ade_ring_rank.py): 'channel' -- lbm_ade_open_add_channel; 'columns' -- an ABB inlet with a FIXED scalar
+    on column 0 and an extrapolated outlet with its zero-gradient copy on column C-1, ALL rows: an open node on the first
+    and last row of every slab, whatever the seams"""
+    t = pylbm.AdeOpenBoundary(lib, R, C)
+    if kind == "channel":
+        return t.channel(0.03, 1e-3, max(2, R // 4))
+    assert kind == "columns", kind
+    t.add_f(0, 0, 1, 0, R, ALL, ABB, (2e-3, 0.03))
+    t.add_f(0, C - 1, 1, 0, R, ALL, ABB_X, (1.5, -0.5), (0, -1))
+    t.add_g(0, 0, 1, 0, R, ALL, FIXED, 1e-3)
+    t.add_g_copy(0, C - 1, 1, 0, R, (0, -1))
+    return t
+
+
 def _idx(it):
     k = np.arange(it[5])
     return it[1] + k * it[3], it[2] + k * it[4]

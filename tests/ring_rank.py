@@ -7,22 +7,17 @@
 share GPU 0 through the peer-mapped transport (LBM_RING_IPC) -- the C++ ring of capi_ring.hip across REAL
 process boundaries, which RCCL cannot do on one device.  Every compute call goes through the C ABI."""
 import ctypes as ct
-import json
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-for p in (HERE, os.path.join(ROOT, "lattice-boltzmann-method_amd")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from proc_util import rank_prologue
 
 
 def main():
-    case, rank, n, work = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4]
-    cfg = json.load(open(os.path.join(work, "cfg.json")))
+    case = sys.argv[1]
+    rank, n, work, cfg, ident = rank_prologue(sys.argv)
     import torch
     import pylbm
     from pylbm import _ptr
@@ -32,7 +27,6 @@ def main():
     for k, v in cfg.get("tuning", {}).items():
         lib.set_tuning(k.encode(), int(v))
     d = torch.device("cuda:0")
-    ident = (ct.c_ubyte * 128).from_buffer_copy(open(os.path.join(work, "id.bin"), "rb").read())
     transport = int(cfg.get("transport", 1))
 
     def load(name):

@@ -10,8 +10,6 @@ reference by tests/golden/solver_units.npz, tests/test_oracle_golden.py):
     f = advect(f_coll); g = advect(g_coll)          (+ the halfway wall fix-ups on both, see _walls)
 In the reference operation order the fused step is compared BITWISE with it."""
 import ctypes as ct
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,10 +20,9 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
 from gpu_util import bits_equal, dev, download_aos, upload_soa  # noqa: E402
+from proc_util import key_values, run_driver  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin")
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 W = (3e-3, 3e-3)
 
@@ -345,14 +342,9 @@ def test_launches_per_step_and_graph_replay(lib, oracle):
 def test_passive_scalar_box_driver_equals_pylbm(lib, tmp_path, walls):
     """the C++ facade (lbm::AdeSolver) in drivers/passive_scalar_box: its dumps == pylbm.AdeSolver on the driver's
     own initial state, bit for bit"""
-    exe = os.path.join(BIN, "passive_scalar_box")
-    assert os.path.exists(exe), f"{exe} missing: run __graft_entry__.build()"
     R, C, steps, om, om_g, wr, wc = 72, 90, 40, 1.1, 1.6, 2e-3, 3e-3
     pre = tmp_path / "psb"
-    r = subprocess.run([exe, *map(str, (R, C, steps, om, om_g, wr, wc)), "--dump", str(pre), "--walls", walls],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    out = dict(ln.split("=", 1) for ln in r.stdout.splitlines() if "=" in ln)
+    out = key_values(run_driver("passive_scalar_box", R, C, steps, om, om_g, wr, wc, "--dump", pre, "--walls", walls, timeout=300))
     assert int(out["steps"]) == steps
     assert abs(float(out["mass_C"]) - float(out["mass_C0"])) <= 1e-12 * float(out["mass_C0"])
 

@@ -8,8 +8,6 @@ fixed-concentration edges (:203-218), the rectangle on g (:220-232: `-g_coll` wh
 last (:233-236) -- and, for a buoyant step, the node-local buoyant collision.  The loop never
 calls the library under test.  Bitwise means equal bit patterns."""
 import ctypes as ct
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,10 +20,9 @@ import pylbm  # noqa: E402
 import ade_util as ade  # noqa: E402
 from ade_util import SENTINEL, Body  # noqa: E402
 from gpu_util import bits_equal, dev  # noqa: E402
+from proc_util import key_values, run_driver  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin")
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 BB, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_PERIODIC
 NO_FLUX, FIXED = pylbm.ADE_SCALAR_NO_FLUX, pylbm.ADE_SCALAR_FIXED
@@ -356,14 +353,12 @@ def test_a_captured_graph_with_a_table_replays_the_eager_run(lib, oracle):
 # ---- 8. the driver ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("conc", [None, 1e-3], ids=["absorbing", "held_at_1e-3"])
 def test_passive_scalar_box_driver_with_the_rectangle_equals_pylbm(lib, tmp_path, conc):
-    exe = os.path.join(BIN, "passive_scalar_box")
     R, C, r_top, c1, c2 = RECT
     steps, om, om_g, wr, wc = 40, 1.1, 1.6, 2e-3, 3e-3
     pre = tmp_path / "psb"
     rect = f"{r_top},{c1},{c2}" + (f",{conc}" if conc is not None else "")
-    r = subprocess.run([exe, *map(str, (R, C, steps, om, om_g, wr, wc)), "--dump", str(pre), "--walls", "2",
-                        "--rectangle", rect], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = run_driver("passive_scalar_box", R, C, steps, om, om_g, wr, wc, "--dump", pre, "--walls", 2, "--rectangle", rect,
+                   timeout=300)
 
     def load(k, shape):
         return np.fromfile(f"{pre}-{k}.f64").reshape(shape)
@@ -378,7 +373,7 @@ def test_passive_scalar_box_driver_with_the_rectangle_equals_pylbm(lib, tmp_path
     want = dict(f=load("f", (R, C, 9)), g=load("g", (R, C, 9)), rho=load("rho", (R, C)), u=load("u", (R, C, 2)),
                 C=load("C", (R, C)))
     ade.assert_state_bits(got, want, "driver vs pylbm")
-    out = dict(ln.split("=", 1) for ln in r.stdout.splitlines() if "=" in ln)
+    out = key_values(r)
     assert int(out["launches"]) == 1 + (steps - 1) * 3
     assert float(out["mass_C"]) != float(out["mass_C0"])  # the body exchanges scalar with the box
     table.close()

@@ -11,11 +11,6 @@ rows 5 and 29, columns 20..30 (ROW_NEG): 68 nodes, 34 in each of the views [0, 2
 puts a node on the first and last row of every slab and into every FRAME and INNER band for any E; each test asserts that
 each band it exercises holds a table node (bands_hold_nodes), so that none passes by testing nothing."""
 import ctypes as ct
-import json
-import os
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
@@ -27,11 +22,9 @@ import pylbm  # noqa: E402
 from ade_util import (GBC, GUO, SENTINEL, W, alloc, assert_bits, bits, buoyancy, cut_slab, geom, owned, params,  # noqa: E402
                       random_lattice, to_lattice)
 from gpu_util import dev  # noqa: E402
+from proc_util import last_json, run_driver, run_ranks  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BIN = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin")
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
 BB, SP, HALO, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR, pylbm.EDGE_HALO, pylbm.EDGE_PERIODIC
@@ -347,44 +340,7 @@ def test_emulated_chain_with_the_body_equals_one_block(lib, oracle, form, closed
     table.close()
 
 
-# ---- 5. real rank processes ----------------------------------------------------------------------------------------------
-def run_ranks(lib, tmp_path, n, cfg, arrays, timeout=240):
-    """n processes of tests/ade_iwalls_ring_rank.py on this GPU over the peer-mapped transport; a failing rank ends the
-    rest, and the whole run has a time limit (run_ranks of tests/test_gpu_ade_slabs.py, for the rank script of this suite)"""
-    work = str(tmp_path)
-    json.dump(cfg, open(os.path.join(work, "cfg.json"), "w"))
-    ident = (ct.c_ubyte * 128)()
-    lib.ring_unique_id_ex(ident, pylbm.RING_IPC)
-    open(os.path.join(work, "id.bin"), "wb").write(bytes(ident))
-    for k, a in arrays.items():
-        np.save(os.path.join(work, k + ".npy"), a)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = []
-    for r in range(n):
-        log = open(os.path.join(work, f"rank{r}.log"), "w")
-        procs.append((subprocess.Popen([sys.executable, os.path.join(HERE, "ade_iwalls_ring_rank.py"), str(r), str(n), work],
-                                       stdout=log, stderr=subprocess.STDOUT, env=env), log))
-    t0, failed = time.time(), None
-    while any(p.poll() is None for p, _ in procs):
-        bad = [r for r, (p, _) in enumerate(procs) if p.poll() not in (None, 0)]
-        if bad or time.time() - t0 > timeout:
-            failed = f"rank(s) {bad} failed" if bad else f"timed out after {timeout} s"
-            for p, _ in procs:
-                if p.poll() is None:
-                    p.kill()
-            break
-        time.sleep(0.05)
-    for p, log in procs:
-        p.wait()
-        log.close()
-    bad = [r for r, (p, _) in enumerate(procs) if p.returncode != 0]
-    if failed or bad:
-        logs = "\n".join(f"--- rank {r} (rc {procs[r][0].returncode}) ---\n" + open(os.path.join(work, f"rank{r}.log")).read()[-3000:]
-                         for r in range(n))
-        raise AssertionError(f"{failed or bad}\n{logs}")
-    return [np.load(os.path.join(work, f"out_{r}.npz")) for r in range(n)]
-
-
+# ---- 5. real rank processes (tests/ade_ring_rank.py, entry "walls") ------------------------------------------------------
 @pytest.mark.parametrize("closed", [True, False], ids=["closed_ring", "walled_chain"])
 def test_ring_of_rank_processes_with_the_body_equals_one_block(lib, oracle, tmp_path, closed):
     """two ranks, lbm_ring_ade_step_w: the wall pass of the FRAME rows runs before the pack -- enqueued behind it, the
@@ -402,8 +358,9 @@ def test_ring_of_rank_processes_with_the_body_equals_one_block(lib, oracle, tmp_
     _, plain = one_block(lib, gg, pre, gbc, prm, steps, None)
     assert not torch.equal(bits(want[1]), bits(plain[1]))
     cfg = dict(R=R, C=C, steps=steps, edge_rows=E, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
-               segments=body_segments(R * n), g_mode=rule[0], conc=rule[1])
-    outs = run_ranks(lib, tmp_path, n, cfg, dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()))
+               entry="walls", segments=body_segments(R * n), g_mode=rule[0], conc=rule[1])
+    outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", n, cfg,
+                     dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()), timeout=240)
     for j, key in enumerate(("f", "g")):
         got = np.concatenate([o[key] for o in outs], axis=1)
         ref = owned(want[j], gg).cpu().numpy()
@@ -491,12 +448,8 @@ def test_a_sealed_wall_on_a_seam_seals(lib, oracle, form):
 # ---- 8. the driver -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", ["fast", "ref"])
 def test_slab_ring_ade_driver_emulated_chain_of_four_with_the_rectangle(form):
-    exe = os.path.join(BIN, "slab_ring_ade")
-    r = subprocess.run([exe, "--emulate", "4", "--rows", "48", "--cols", "200", "--steps", "9", "--warmup", "2",
-                        "--edge-rows", "8", "--walls", "1", "--rectangle", "1", "--form", form, "--check", "1"],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_ade", "--emulate", 4, "--rows", 48, "--cols", 200, "--steps", 9, "--warmup", 2,
+                                "--edge-rows", 8, "--walls", 1, "--rectangle", 1, "--form", form, "--check", 1, timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["slabs"] == 4
     assert line["interior_wall_nodes"] > 0
     per_slab = line["interior_wall_nodes_per_slab"]
@@ -506,18 +459,13 @@ def test_slab_ring_ade_driver_emulated_chain_of_four_with_the_rectangle(form):
 
 def test_slab_ring_ade_driver_self_ring_with_the_rectangle(tmp_path):
     """one forked rank with walls: a chain of one slab through lbm_ring_ade_step_w == one block bit for bit"""
-    exe = os.path.join(BIN, "slab_ring_ade")
-    r = subprocess.run([exe, "--spawn", "1", "--rows", "96", "--cols", "256", "--steps", "5", "--warmup", "1",
-                        "--edge-rows", "16", "--walls", "1", "--rectangle", "1", "--check", "1", "--id-file", str(tmp_path / "id")],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_ade", "--spawn", 1, "--rows", 96, "--cols", 256, "--steps", 5, "--warmup", 1,
+                                "--edge-rows", 16, "--walls", 1, "--rectangle", 1, "--check", 1, "--id-file", tmp_path / "id",
+                                timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["n_gpus"] == 1 and line["interior_wall_nodes"] > 0
 
 
 def test_slab_ring_ade_driver_refuses_the_rectangle_without_walls():
-    exe = os.path.join(BIN, "slab_ring_ade")
-    r = subprocess.run([exe, "--emulate", "2", "--rows", "48", "--cols", "64", "--rectangle", "1"], capture_output=True,
-                       text=True, timeout=60)
+    r = run_driver("slab_ring_ade", "--emulate", 2, "--rows", 48, "--cols", 64, "--rectangle", 1, timeout=60, check=False)
     assert r.returncode != 0
     assert "--rectangle 1 needs --walls 1" in r.stderr

@@ -7,11 +7,6 @@ global table (pinned to the oracle in tests/test_gpu_ade_open.py).  Every compar
 tolerances.  Each test asserts that every band it exercises holds a listed node (bands_hold_nodes): an inlet or outlet
 column puts one into every row."""
 import ctypes as ct
-import json
-import os
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
@@ -20,15 +15,13 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
-from ade_open_ring_rank import build_open  # noqa: E402
+from ade_open_util import build_open  # noqa: E402
 from ade_util import (GUO, REFERENCE, SENTINEL, W, alloc, assert_bits, bits, buoyancy, cut_slab, geom, owned, params,  # noqa: E402
                       random_lattice, to_lattice)
 from gpu_util import dev  # noqa: E402
+from proc_util import last_json, run_driver, run_ranks  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BIN = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin")
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 FORMS = pytest.mark.parametrize("form", [REF, FAST], ids=["reference_order", "reassociated"])
 FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
@@ -89,7 +82,7 @@ def specular(lib, R, C):
 
 
 def channel(lib, R, C):
-    return build_open(lib, pylbm, "channel", R, C)
+    return build_open(lib, "channel", R, C)
 
 
 def rectangle(lib, R, C, r_top, c1, c2):
@@ -505,44 +498,7 @@ def test_refusals_at_call_time_name_what_is_wrong(lib):
         t.close()
 
 
-# ---- 7. real rank processes ----------------------------------------------------------------------------------------------
-def run_ranks(lib, tmp_path, n, cfg, arrays, timeout=240):
-    """n processes of tests/ade_open_ring_rank.py on this GPU over the peer-mapped transport; a failing rank ends the rest,
-    and the whole run has a time limit (run_ranks of tests/test_gpu_ade_iwalls_slabs.py, for the rank script of this suite)"""
-    work = str(tmp_path)
-    json.dump(cfg, open(os.path.join(work, "cfg.json"), "w"))
-    ident = (ct.c_ubyte * 128)()
-    lib.ring_unique_id_ex(ident, pylbm.RING_IPC)
-    open(os.path.join(work, "id.bin"), "wb").write(bytes(ident))
-    for k, a in arrays.items():
-        np.save(os.path.join(work, k + ".npy"), a)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = []
-    for r in range(n):
-        log = open(os.path.join(work, f"rank{r}.log"), "w")
-        procs.append((subprocess.Popen([sys.executable, os.path.join(HERE, "ade_open_ring_rank.py"), str(r), str(n), work],
-                                       stdout=log, stderr=subprocess.STDOUT, env=env), log))
-    t0, failed = time.time(), None
-    while any(p.poll() is None for p, _ in procs):
-        bad = [r for r, (p, _) in enumerate(procs) if p.poll() not in (None, 0)]
-        if bad or time.time() - t0 > timeout:
-            failed = f"rank(s) {bad} failed" if bad else f"timed out after {timeout} s"
-            for p, _ in procs:
-                if p.poll() is None:
-                    p.kill()
-            break
-        time.sleep(0.05)
-    for p, log in procs:
-        p.wait()
-        log.close()
-    bad = [r for r, (p, _) in enumerate(procs) if p.returncode != 0]
-    if failed or bad:
-        logs = "\n".join(f"--- rank {r} (rc {procs[r][0].returncode}) ---\n" + open(os.path.join(work, f"rank{r}.log")).read()[-3000:]
-                         for r in range(n))
-        raise AssertionError(f"{failed or bad}\n{logs}")
-    return [np.load(os.path.join(work, f"out_{r}.npz")) for r in range(n)]
-
-
+# ---- 7. real rank processes (tests/ade_ring_rank.py, entry "open") -------------------------------------------------------
 @pytest.mark.parametrize("closed,kind", [(True, "columns"), (False, "channel")], ids=["closed_ring_columns", "walled_chain_channel"])
 def test_ring_of_two_rank_processes_equals_one_block(lib, oracle, tmp_path, closed, kind):
     """lbm_ring_ade_collide_o + lbm_ring_ade_step_o, an open node on every seam row: the open pass of the FRAME rows runs
@@ -551,7 +507,7 @@ def test_ring_of_two_rank_processes_equals_one_block(lib, oracle, tmp_path, clos
     n, R, C, steps, E, form = 2, 24, CG, 11, 4, FAST
     prm, gbc = params(form), (pylbm.Bc.periodic() if closed else WALLS)
     gg, pre = global_state(oracle, R * n, C, seed=2)
-    table = build_open(lib, pylbm, kind, R * n, C).finalize()
+    table = build_open(lib, kind, R * n, C).finalize()
     counts = []
     for k in range(n):
         view = table.slab(k * R, R)
@@ -562,8 +518,10 @@ def test_ring_of_two_rank_processes_equals_one_block(lib, oracle, tmp_path, clos
     _, _, plain = one_block(lib, gg, pre, gbc, prm, (steps,), None)
     (wlat, wcarry), (plat, _) = want[steps], plain[steps]
     assert not torch.equal(bits(wlat[1]), bits(plat[1]))
-    cfg = dict(R=R, C=C, steps=steps, edge_rows=E, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W), table=kind)
-    outs = run_ranks(lib, tmp_path, n, cfg, dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()))
+    cfg = dict(R=R, C=C, steps=steps, edge_rows=E, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
+               entry="open", table=kind)
+    outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", n, cfg,
+                     dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()), timeout=240)
     for j, key in enumerate(("f", "g")):
         got = np.concatenate([o[key] for o in outs], axis=1)
         ref = owned(wlat[j], gg).cpu().numpy()
@@ -686,11 +644,8 @@ def test_a_captured_graph_of_an_even_number_of_part_steps_replays_the_eager_run(
 # ---- 11. the driver ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("extra", [[], ["--buoyancy", "2e-2,-1e-2,5e-4"]], ids=["passive", "buoyant"])
 def test_slab_ring_ade_driver_emulated_chain_of_three_with_the_channel_and_the_rectangle(extra):
-    exe = os.path.join(BIN, "slab_ring_ade")
-    r = subprocess.run([exe, "--emulate", "3", "--rows", "16", "--cols", "64", "--walls", "1", "--channel", "1", "--rectangle", "1",
-                        "--check", "1"] + extra, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_ade", "--emulate", 3, "--rows", 16, "--cols", 64, "--walls", 1, "--channel", 1,
+                                "--rectangle", 1, "--check", 1, *extra, timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["slabs"] == 3
     per_slab = line["open_nodes_per_slab"]
     assert len(per_slab) == 3 and sum(per_slab) == line["open_nodes"] and all(n > 0 for n in per_slab)

@@ -9,9 +9,6 @@ driver's expression order:
 at every population a FIXED edge wins (rows first, columns win at the corners).  In the reference operation order the
 step is compared BITWISE with it."""
 import ctypes as ct
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -24,10 +21,9 @@ import pylbm  # noqa: E402
 from ade_util import (GBC, SENTINEL, W, alloc, assert_bits, assert_state_bits, bits, build_sbc, cut_slab,  # noqa: E402
                       geom, initial_state, oracle_loop, owned, params, random_lattice)
 from gpu_util import bits_equal, dev  # noqa: E402
+from proc_util import ipc_env, key_values, last_json, run_driver  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin")
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 BB, SP, HALO, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR, pylbm.EDGE_HALO, pylbm.EDGE_PERIODIC
 FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
@@ -413,36 +409,25 @@ def test_emulated_chain_with_fixed_walls_equals_one_block(lib, oracle, form, hei
 # ---- 8. drivers and real rank processes ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", ["fast", "ref"])
 def test_slab_ring_ade_driver_emulated_chain_with_fixed_walls(form):
-    exe = os.path.join(BIN, "slab_ring_ade")
-    r = subprocess.run([exe, "--emulate", "4", "--rows", "50", "--cols", "200", "--steps", "9", "--warmup", "2",
-                        "--edge-rows", "8", "--walls", "1", "--scalar-fixed", "1", "--form", form, "--check", "1"],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_ade", "--emulate", 4, "--rows", 50, "--cols", 200, "--steps", 9, "--warmup", 2,
+                                "--edge-rows", 8, "--walls", 1, "--scalar-fixed", 1, "--form", form, "--check", 1, timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["slabs"] == 4 and line["scalar_fixed"] == 1
 
 
 def test_slab_ring_ade_driver_rank_processes_with_fixed_walls(tmp_path):
     """two forked rank processes sharing this GPU over the peer-mapped transport (lbm_ring_ade_step_ex): a chain whose
     ends carry the FIXED row / NO_FLUX row, == one block bit for bit"""
-    exe = os.path.join(BIN, "slab_ring_ade")
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([exe, "--spawn", "2", "--one-gpu", "1", "--transport", "ipc", "--rows", "50", "--cols", "200",
-                        "--steps", "7", "--warmup", "1", "--edge-rows", "8", "--walls", "1", "--scalar-fixed", "1",
-                        "--check", "1", "--id-file", str(tmp_path / "id")],
-                       capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_ade", "--spawn", 2, "--one-gpu", 1, "--transport", "ipc", "--rows", 50, "--cols", 200,
+                                "--steps", 7, "--warmup", 1, "--edge-rows", 8, "--walls", 1, "--scalar-fixed", 1,
+                                "--check", 1, "--id-file", tmp_path / "id", timeout=300, env=ipc_env()))
     assert line["check"] == "bitwise equal to one block" and line["n_gpus"] == 2 and line["scalar_fixed"] == 1
 
 
 def test_passive_scalar_box_driver_with_fixed_edges_equals_pylbm(lib, tmp_path):
-    exe = os.path.join(BIN, "passive_scalar_box")
     R, C, steps, om, om_g, wr, wc = 72, 90, 40, 1.1, 1.6, 2e-3, 3e-3
     pre = tmp_path / "psb"
-    r = subprocess.run([exe, *map(str, (R, C, steps, om, om_g, wr, wc)), "--dump", str(pre), "--walls", "2",
-                        "--fixed", "row_lo=0.001,col_hi=0"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = run_driver("passive_scalar_box", R, C, steps, om, om_g, wr, wc, "--dump", pre, "--walls", 2,
+                   "--fixed", "row_lo=0.001,col_hi=0", timeout=300)
 
     def load(k, shape):
         return np.fromfile(f"{pre}-{k}.f64").reshape(shape)
@@ -457,5 +442,5 @@ def test_passive_scalar_box_driver_with_fixed_edges_equals_pylbm(lib, tmp_path):
     want = dict(f=load("f", (R, C, 9)), g=load("g", (R, C, 9)), rho=load("rho", (R, C)), u=load("u", (R, C, 2)),
                 C=load("C", (R, C)))
     assert_state_bits(got, want, "driver vs pylbm")
-    out = dict(ln.split("=", 1) for ln in r.stdout.splitlines() if "=" in ln)
+    out = key_values(r)
     assert float(out["mass_C"]) != float(out["mass_C0"])  # the FIXED walls exchange scalar with the box

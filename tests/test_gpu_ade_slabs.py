@@ -10,10 +10,6 @@ tests/test_gpu_ade.py).  Post-collision f and g are compared BITWISE on every ow
   * the driver's own --check; and the scalar's mass and transport across the seams."""
 import ctypes as ct
 import json
-import os
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
@@ -26,11 +22,9 @@ from ade_util import (GBC, SENTINEL, W, alloc, assert_bits, bits, cut_slab, geom
                       random_lattice, to_lattice)
 from ade_util import full_step as full_step_b  # noqa: E402  (lbm_ade_stream_collide_b: every descriptor)
 from gpu_util import dev  # noqa: E402
+from proc_util import last_json, run_driver, run_ranks  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-BIN = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin")
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
 BB, SP, HALO, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR, pylbm.EDGE_HALO, pylbm.EDGE_PERIODIC
@@ -243,43 +237,7 @@ def test_emulated_chain_equals_one_block(lib, oracle, form, closed, heights, C):
         assert_bits(ch.gather(j), owned(want[j], gg), f"{len(heights)} slabs {heights} closed={closed} lattice {j}")
 
 
-# ---- 4. real rank processes ----------------------------------------------------------------------------------------------
-def run_ranks(lib, tmp_path, n, cfg, arrays, timeout=240):
-    """n processes of tests/ade_ring_rank.py on this GPU over the peer-mapped transport; a failing rank ends the rest"""
-    work = str(tmp_path)
-    json.dump(cfg, open(os.path.join(work, "cfg.json"), "w"))
-    ident = (ct.c_ubyte * 128)()
-    lib.ring_unique_id_ex(ident, pylbm.RING_IPC)
-    open(os.path.join(work, "id.bin"), "wb").write(bytes(ident))
-    for k, a in arrays.items():
-        np.save(os.path.join(work, k + ".npy"), a)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = []
-    for r in range(n):
-        log = open(os.path.join(work, f"rank{r}.log"), "w")
-        procs.append((subprocess.Popen([sys.executable, os.path.join(HERE, "ade_ring_rank.py"), str(r), str(n), work],
-                                       stdout=log, stderr=subprocess.STDOUT, env=env), log))
-    t0, failed = time.time(), None
-    while any(p.poll() is None for p, _ in procs):
-        bad = [r for r, (p, _) in enumerate(procs) if p.poll() not in (None, 0)]
-        if bad or time.time() - t0 > timeout:
-            failed = f"rank(s) {bad} failed" if bad else f"timed out after {timeout} s"
-            for p, _ in procs:
-                if p.poll() is None:
-                    p.kill()
-            break
-        time.sleep(0.05)
-    for p, log in procs:
-        p.wait()
-        log.close()
-    bad = [r for r, (p, _) in enumerate(procs) if p.returncode != 0]
-    if failed or bad:
-        logs = "\n".join(f"--- rank {r} (rc {procs[r][0].returncode}) ---\n" + open(os.path.join(work, f"rank{r}.log")).read()[-3000:]
-                         for r in range(n))
-        raise AssertionError(f"{failed or bad}\n{logs}")
-    return [np.load(os.path.join(work, f"out_{r}.npz")) for r in range(n)]
-
-
+# ---- 4. real rank processes (tests/ade_ring_rank.py, entry "plain") ------------------------------------------------------
 @pytest.mark.parametrize("n", [2, 3])
 @pytest.mark.parametrize("closed", [True, False])
 def test_ring_of_rank_processes_equals_one_block(lib, oracle, tmp_path, n, closed):
@@ -287,8 +245,10 @@ def test_ring_of_rank_processes_equals_one_block(lib, oracle, tmp_path, n, close
     prm, gbc = params(form), (pylbm.Bc.periodic() if closed else wall_bc(True))
     gg, pre = global_state(lib, oracle, R * n, C, seed=n)
     _, want = one_block(lib, gg, pre, gbc, prm, steps)
-    cfg = dict(R=R, C=C, steps=steps, edge_rows=16, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W))
-    outs = run_ranks(lib, tmp_path, n, cfg, dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()))
+    cfg = dict(R=R, C=C, steps=steps, edge_rows=16, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
+               entry="plain")
+    outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", n, cfg,
+                     dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()), timeout=240)
     for j, key in enumerate(("f", "g")):
         got = np.concatenate([o[key] for o in outs], axis=1)
         ref = owned(want[j], gg).cpu().numpy()
@@ -299,8 +259,8 @@ def test_ring_of_rank_processes_equals_one_block(lib, oracle, tmp_path, n, close
 
 def test_ring_entry_points_refuse_a_ring_without_one_ghost_row(lib, tmp_path):
     """ghost != 1 on the ring: every ring entry point of the pair refuses it on the host (one rank, its own process)"""
-    cfg = dict(case="refusals", R=32, C=64)
-    outs = run_ranks(lib, tmp_path, 1, cfg, {})
+    cfg = dict(case="refusals", entry="plain", R=32, C=64)
+    outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", 1, cfg, {}, timeout=240)
     msgs = json.loads(str(outs[0]["msgs"]))
     assert len(msgs) == 3
     for m in msgs:
@@ -342,12 +302,8 @@ def test_ring_step_with_walls_fixed_edges_and_buoyancy_is_the_one_block_step(lib
 @pytest.mark.parametrize("walls", [0, 1])
 @pytest.mark.parametrize("form", ["fast", "ref"])
 def test_slab_ring_ade_driver_emulated_chain_of_four(walls, form):
-    exe = os.path.join(BIN, "slab_ring_ade")
-    r = subprocess.run([exe, "--emulate", "4", "--rows", "48", "--cols", "200", "--steps", "9", "--warmup", "2",
-                        "--edge-rows", "8", "--walls", str(walls), "--form", form, "--check", "1"],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_ade", "--emulate", 4, "--rows", 48, "--cols", 200, "--steps", 9, "--warmup", 2,
+                                "--edge-rows", 8, "--walls", walls, "--form", form, "--check", 1, timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["slabs"] == 4 and line["message_rows_per_side"] == 6
     assert line["slowest_slab_ms_per_step"] > 0 and line["one_block_slab_sized_ms_per_step"] > 0
 
@@ -356,12 +312,8 @@ def test_slab_ring_ade_driver_emulated_chain_of_four(walls, form):
 def test_slab_ring_ade_driver_self_ring(tmp_path, walls):
     """one forked rank: closed, its neighbours are itself (every step exchanges through the ring); with walls a chain
     of one slab (nothing travels) -- both == one block bit for bit"""
-    exe = os.path.join(BIN, "slab_ring_ade")
-    r = subprocess.run([exe, "--spawn", "1", "--rows", "96", "--cols", "256", "--steps", "5", "--warmup", "1",
-                        "--edge-rows", "16", "--walls", str(walls), "--check", "1", "--id-file", str(tmp_path / "id")],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_ade", "--spawn", 1, "--rows", 96, "--cols", 256, "--steps", 5, "--warmup", 1,
+                                "--edge-rows", 16, "--walls", walls, "--check", 1, "--id-file", tmp_path / "id", timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["n_gpus"] == 1
 
 

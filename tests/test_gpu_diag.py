@@ -2,8 +2,6 @@
 solver contexts' diag and run_until, and the Poiseuille driver's --device-check path -- pinned BITWISE to the
 independent numpy restatement of the summation order in tests/diag_reference.py (nothing there calls the library)."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,12 +11,11 @@ import ade_util as ade
 import diag_reference as ref
 import pylbm
 from gpu_util import dev
+from proc_util import key_values, run_driver
 from pylbm import _ptr
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin")
 SENTINEL = 0x7FF8DEADBEEF5A5A  # a quiet NaN no kernel computes: "never written"
 ROWS = (1, 2, 63, 65, 200)      # fewer rows than a workgroup takes, one short of / one past the accumulator count, many
 COLS = (1, 2, 63, 64, 65, 130)  # straddle the lane count, ragged last slice, more than one slice
@@ -333,9 +330,8 @@ def host_loop(sv, max_steps):
 
 
 def driver(*args):
-    r = subprocess.run([os.path.join(BIN, "horizontal_poiseuille_test"), *map(str, args)], capture_output=True, text=True, timeout=300)
-    out = dict(ln.split("=", 1) for ln in r.stdout.splitlines() if "=" in ln and " " not in ln.split("=")[0])
-    return r, out
+    """the key=value lines of horizontal_poiseuille_test; it ran to exit 0"""
+    return key_values(run_driver("horizontal_poiseuille_test", *args, timeout=300))
 
 
 @pytest.fixture(scope="module")
@@ -371,12 +367,11 @@ def test_run_until_stops_where_the_existing_driver_stops(poiseuille_runs):
     """the driver's own loop sums row-major on the host; run_until sums in the diagnostics' order.  Both numbers are
     printed; they must agree -- with the driver's default T as with a T beyond the stopping step."""
     device = poiseuille_runs[0]
-    r, out = driver("--T", 40000)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = driver("--T", 40000)
     print(f"driver --T 40000: steps={out['steps']}; run_until(max_steps=40000): steps_done={device[0]}")
     assert int(out["steps"]) == device[0]
-    r, out = driver()
-    assert r.returncode == 0 and int(out["steps"]) == min(T_DRIVER, device[0])
+    out = driver()
+    assert int(out["steps"]) == min(T_DRIVER, device[0])
 
 
 def test_run_until_ends_at_max_steps_below_the_stopping_step(lib, poiseuille_runs):
@@ -434,9 +429,8 @@ def test_ade_run_until_applies_the_same_rule(lib, oracle):
 
 
 def test_driver_with_device_check_prints_the_reference_assertion():
-    r, out = driver("--device-check", 1)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]      # the driver's own L2 <= 1e-11 check passed
-    r0, out0 = driver()
+    out = driver("--device-check", 1)                                  # exit 0: the driver's own L2 <= 1e-11 check passed
+    out0 = driver()
     print(f"--device-check 1: steps={out['steps']} L2={out['L2']}; default: steps={out0['steps']} L2={out0['L2']}")
     assert float(out["L2"]) <= 1e-11                                   # horizontal_poiseuille_test.cpp:172
     assert out["steps"] == out0["steps"]

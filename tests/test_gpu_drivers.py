@@ -1,25 +1,18 @@
 """GPU suite: the C++ drivers (reference mains restated on the facade + C ABI) end to end."""
+import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 from conftest import golden, relerr
+from proc_util import PKG, key_values, last_json, run_driver
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "lattice-boltzmann-method_amd")
-BIN = os.path.join(PKG, "drivers", "bin")
 
-
-def run(name, *args, cwd=None, tune=None):
-    exe = os.path.join(BIN, name)
-    assert os.path.exists(exe), f"{exe} missing: run __graft_entry__.build()"
-    env = dict(os.environ, LBM_TUNE=tune) if tune else None    # process-wide tuning of the library, through the environment
-    r = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, cwd=cwd, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    return dict(ln.split("=", 1) for ln in r.stdout.splitlines() if "=" in ln and " " not in ln.split("=")[0])
+def run(name, *args, **kw):
+    """a driver that prints key=value lines, run to exit 0 -> the dict of them"""
+    return key_values(run_driver(name, *args, timeout=600, **kw))
 
 
 def test_poiseuille_driver_reproduces_reference_assertion(tmp_path):
@@ -145,16 +138,10 @@ def test_slab_ring_box_driver_self_ring(tmp_path):
     """C++ host of the multi-GPU path (drivers/slab_ring_box.cpp on lbm_ring_*): one forked rank whose
     ring neighbours are itself, so every launch-step runs the packed ncclSend/ncclRecv exchange on the
     edge stream; --check compares with the same box advanced as one ghost-free block, bit for bit."""
-    import json
-    exe = os.path.join(BIN, "slab_ring_box")
-    assert os.path.exists(exe)
     for depth, edge, model, period in ((5, 16, "bgk", 2), (5, 16, "bgk", 1), (3, 16, "bgk", 3), (1, 8, "bgk", 2), (3, 16, "kbc", 2)):
-        r = subprocess.run([exe, "--spawn", "1", "--rows", "160", "--cols", "256", "--steps", "3", "--model", model,
-                            "--warmup", "1", "--depth", str(depth), "--edge-rows", str(edge), "--check", "1",
-                            "--period", str(period), "--id-file", str(tmp_path / f"id{depth}{model}{period}")],
-                           capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        line = json.loads(r.stdout.strip().splitlines()[-1])
+        line = last_json(run_driver("slab_ring_box", "--spawn", 1, "--rows", 160, "--cols", 256, "--steps", 3, "--model", model,
+                                    "--warmup", 1, "--depth", depth, "--edge-rows", edge, "--check", 1, "--period", period,
+                                    "--id-file", tmp_path / f"id{depth}{model}{period}", timeout=300))
         assert line["check"] == "bitwise equal to one block" and line["depth"] == depth
         # window launches: ghost = period x depth rows, one exchange per `period` launches
         assert line["ghost_rows"] == (depth * period if depth > 1 else depth)
@@ -165,13 +152,8 @@ def test_slab_ring_rt_driver(tmp_path):
     chain has no neighbour, so this checks the slab-geometry path (3 ghost rows, walls on the slab)
     against the ghost-free single block bit for bit; the exchange itself is covered by
     test_cg_fused_two_slabs_equal_single_block and the BGK self-ring tests."""
-    import json
-    exe = os.path.join(BIN, "slab_ring_rt")
-    assert os.path.exists(exe)
-    r = subprocess.run([exe, "--spawn", "1", "--rows", "128", "--cols", "64", "--steps", "8", "--warmup", "2",
-                        "--check", "1", "--id-file", str(tmp_path / "id")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_rt", "--spawn", 1, "--rows", 128, "--cols", 64, "--steps", 8, "--warmup", 2,
+                                "--check", 1, "--id-file", tmp_path / "id", timeout=300))
     assert line["check"] == "bitwise equal to one block"
 
 
@@ -179,12 +161,8 @@ def test_slab_ring_rt_emulated_chain_of_four_slabs(tmp_path):
     """BASELINE config 4's decomposition in small (mrtcg_rayleigh_taylor.cpp:413-478 with its walls :495-533 on the
     outer slabs): 4 slabs in turn on one GPU, the two-colour 21-row messages by device copies, edge rows before
     interior rows; == the single block bit for bit"""
-    import json
-    exe = os.path.join(BIN, "slab_ring_rt")
-    r = subprocess.run([exe, "--emulate", "4", "--rows", "64", "--cols", "96", "--steps", "9", "--warmup", "2", "--edge-rows", "8",
-                        "--check", "1"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_rt", "--emulate", 4, "--rows", 64, "--cols", 96, "--steps", 9, "--warmup", 2,
+                                "--edge-rows", 8, "--check", 1, timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["slabs"] == 4 and line["message_rows_per_colour_and_side"] == 21
 
 
@@ -192,12 +170,8 @@ def test_slab_ring_rt_emulated_chain_of_four_slabs(tmp_path):
 def test_slab_ring_rt_emulated_chain_with_partial_tiles(tmp_path, rows, edge):
     """slab heights 16 does not divide, with edge rows that reach into the last, partial tile row (50 % 16 = 2 < 16,
     130 % 16 = 2 < 3): the frame part must still compute every edge row the messages carry; == the single block bit for bit"""
-    import json
-    exe = os.path.join(BIN, "slab_ring_rt")
-    r = subprocess.run([exe, "--emulate", "3", "--rows", str(rows), "--cols", "200", "--steps", "7", "--warmup", "2",
-                        "--edge-rows", str(edge), "--check", "1"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_rt", "--emulate", 3, "--rows", rows, "--cols", 200, "--steps", 7, "--warmup", 2,
+                                "--edge-rows", edge, "--check", 1, timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["slabs"] == 3
 
 
@@ -205,17 +179,12 @@ def test_slab_ring_rt_with_row_padded_slabs(tmp_path):
     """1024 columns: slab_geom pads the rows of the slabs' lattices (lbm_default_row_pitch) -- init through
     lbm_lattice_copy_rows, ring pack / unpack, the two-part step and the check all on padded lattices; the emulated chain
     and two real rank processes, both bitwise against the dense single block"""
-    import json
-    exe = os.path.join(BIN, "slab_ring_rt")
-    r = subprocess.run([exe, "--emulate", "3", "--rows", "48", "--cols", "1024", "--steps", "7", "--warmup", "2", "--edge-rows", "16",
-                        "--check", "1"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert json.loads(r.stdout.strip().splitlines()[-1])["check"] == "bitwise equal to one block"
-    r = subprocess.run([exe, "--spawn", "2", "--transport", "ipc", "--one-gpu", "1", "--check", "1", "--id-file", str(tmp_path / "id"),
-                        "--rows", "48", "--cols", "1024", "--steps", "6", "--warmup", "2", "--edge-rows", "16"],
-                       capture_output=True, text=True, timeout=400)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert json.loads(r.stdout.strip().splitlines()[-1])["check"] == "bitwise equal to one block"
+    r = run_driver("slab_ring_rt", "--emulate", 3, "--rows", 48, "--cols", 1024, "--steps", 7, "--warmup", 2, "--edge-rows", 16,
+                   "--check", 1, timeout=300)
+    assert last_json(r)["check"] == "bitwise equal to one block"
+    r = run_driver("slab_ring_rt", "--spawn", 2, "--transport", "ipc", "--one-gpu", 1, "--check", 1, "--id-file", tmp_path / "id",
+                   "--rows", 48, "--cols", 1024, "--steps", 6, "--warmup", 2, "--edge-rows", 16, timeout=400)
+    assert last_json(r)["check"] == "bitwise equal to one block"
 
 
 @pytest.mark.parametrize("driver,args", [
@@ -228,12 +197,8 @@ def test_ring_drivers_with_three_real_ranks_on_one_gpu(tmp_path, driver, args):
     """the C++ hosts of the multi-GPU path as they run on a node -- `--spawn 3`: three forked rank processes --, here all on
     GPU 0 through the peer-mapped transport (--transport ipc --one-gpu 1); --check 1: rank 0 recomputes the domain as one
     block and compares every rank's rows bit for bit"""
-    import json
-    exe = os.path.join(BIN, driver)
-    r = subprocess.run([exe, "--spawn", "3", "--transport", "ipc", "--one-gpu", "1", "--check", "1", "--id-file", str(tmp_path / "id")] + args,
-                       capture_output=True, text=True, timeout=400)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver(driver, "--spawn", 3, "--transport", "ipc", "--one-gpu", 1, "--check", 1, "--id-file", tmp_path / "id",
+                                *args, timeout=400))
     assert line["check"] == "bitwise equal to one block" and line["n_gpus"] == 3
 
 
@@ -241,12 +206,9 @@ def test_ring_driver_reports_a_neighbour_that_left(tmp_path):
     """the C++ ring hosts read lbm_ring_status after their timed launches.  `--desert 1`: rank 1 joins the ring and
     leaves; rank 0's bounded waits give up (1.5 s here), its lattices and timings are void -- it says so as JSON and the
     driver returns 4 instead of a rate"""
-    import json
-    exe = os.path.join(BIN, "slab_ring_box")
-    env = dict(os.environ, LBM_TUNE="ring_ipc_timeout_ms=1500")
-    r = subprocess.run([exe, "--spawn", "2", "--transport", "ipc", "--one-gpu", "1", "--desert", "1", "--rows", "96", "--cols", "160",
-                        "--steps", "3", "--warmup", "1", "--depth", "5", "--period", "2", "--edge-rows", "16", "--id-file", str(tmp_path / "id")],
-                       capture_output=True, text=True, timeout=300, env=env)
+    r = run_driver("slab_ring_box", "--spawn", 2, "--transport", "ipc", "--one-gpu", 1, "--desert", 1, "--rows", 96, "--cols", 160,
+                   "--steps", 3, "--warmup", 1, "--depth", 5, "--period", 2, "--edge-rows", 16, "--id-file", tmp_path / "id",
+                   timeout=300, tune="ring_ipc_timeout_ms=1500", check=False)
     assert r.returncode == 4, (r.returncode, r.stdout[-1000:], r.stderr[-1000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["rank"] == 0 and "never delivered" in line["error"] and "mlups" not in line
@@ -258,14 +220,8 @@ def test_slab_ring_cylinder_driver(tmp_path):
     rows.  --check: populations and surface force equal the single-block solver-context run bit for bit.
     (One rank: the chain has no neighbour; the exchange is covered by the self-ring tests and by the
     emulated chain below.)"""
-    import json
-    exe = os.path.join(BIN, "slab_ring_cylinder")
-    assert os.path.exists(exe)
-    r = subprocess.run([exe, "--spawn", "1", "--rows", "192", "--cols", "160", "--diameter", "30", "--steps", "12",
-                        "--warmup", "3", "--edge-rows", "8", "--check", "1", "--id-file", str(tmp_path / "id")],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_cylinder", "--spawn", 1, "--rows", 192, "--cols", 160, "--diameter", 30, "--steps", 12,
+                                "--warmup", 3, "--edge-rows", 8, "--check", 1, "--id-file", tmp_path / "id", timeout=300))
     assert line["check"] == "bitwise equal to one block"
     assert line["markers"] == 94 and abs(line["Fs"][0]) > 0
     assert line["this_rank"]["owner"] == 1 and line["steps_per_block"] == 5
@@ -275,12 +231,8 @@ def test_slab_ring_cylinder_emulated_chain_with_the_cylinder_on_a_seam(tmp_path)
     """the BASELINE layout in small: 4 slabs, the cylinder centred at rows / 4 = exactly the seam between
     slabs 0 and 1 -- both co-own the band; every slab in turn on one GPU, messages by device copies;
     == the single block bit for bit (populations of every slab, surface force of both co-owners)"""
-    import json
-    exe = os.path.join(BIN, "slab_ring_cylinder")
-    r = subprocess.run([exe, "--emulate", "4", "--uniform", "1", "--rows", "96", "--cols", "160", "--diameter", "30", "--steps", "15",
-                        "--warmup", "5", "--check", "1"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_cylinder", "--emulate", 4, "--uniform", 1, "--rows", 96, "--cols", 160, "--diameter", 30,
+                                "--steps", 15, "--warmup", 5, "--check", 1, timeout=300))
     assert line["check"] == "bitwise equal to one block"
     roles = [(s["owner"], s["straddle_prev"], s["straddle_next"]) for s in line["per_slab"]]
     assert roles == [(1, 0, 1), (1, 1, 0), (0, 0, 0), (0, 0, 0)], roles
@@ -289,26 +241,18 @@ def test_slab_ring_cylinder_emulated_chain_with_the_cylinder_on_a_seam(tmp_path)
 def test_slab_ring_cylinder_emulated_chain_with_the_reassociated_collision(tmp_path):
     """--form reassociated (lbm_bgk_params.form on every slab and on the single block): the cylinder on the seam, both
     co-owners; slabs == the single block bit for bit in this operation order too"""
-    import json
-    exe = os.path.join(BIN, "slab_ring_cylinder")
-    r = subprocess.run([exe, "--emulate", "4", "--uniform", "1", "--rows", "96", "--cols", "160", "--diameter", "30", "--steps", "15",
-                        "--warmup", "5", "--check", "1", "--form", "reassociated"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_cylinder", "--emulate", 4, "--uniform", 1, "--rows", 96, "--cols", 160, "--diameter", 30,
+                                "--steps", 15, "--warmup", 5, "--check", 1, "--form", "reassociated", timeout=300))
     assert line["check"] == "bitwise equal to one block"
-    r = subprocess.run([exe, "--emulate", "2", "--form", "fast"], capture_output=True, text=True, timeout=60)
+    r = run_driver("slab_ring_cylinder", "--emulate", 2, "--form", "fast", timeout=60, check=False)
     assert r.returncode == 2 and "--form" in r.stderr
 
 
 def test_slab_ring_cylinder_emulated_chain_with_planned_slab_heights(tmp_path):
     """the default: the LIBRARY cuts the domain (lbm_slab_ibm_plan_rows) -- the forced band lands inside ONE short slab,
     nobody straddles; == the single block bit for bit"""
-    import json
-    exe = os.path.join(BIN, "slab_ring_cylinder")
-    r = subprocess.run([exe, "--emulate", "4", "--rows", "96", "--cols", "160", "--diameter", "30", "--steps", "15",
-                        "--warmup", "5", "--check", "1"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(r.stdout.strip().splitlines()[-1])
+    line = last_json(run_driver("slab_ring_cylinder", "--emulate", 4, "--rows", 96, "--cols", 160, "--diameter", 30, "--steps", 15,
+                                "--warmup", 5, "--check", 1, timeout=300))
     assert line["check"] == "bitwise equal to one block" and line["slab_heights"].startswith("planned")
     heights = [s["rows"] for s in line["per_slab"]]
     assert sum(heights) == 384 and min(heights) >= 28
@@ -322,14 +266,10 @@ def test_slab_ring_cylinder_emulated_chain_with_unequal_slab_heights(tmp_path):
     """--slab-rows: each slab brings its own height (a chain runs at its slowest slab's pace, so the slabs that carry
     the forced band get fewer rows).  The band inside one short slab, and straddling two short ones; == the single
     block bit for bit."""
-    import json
-    exe = os.path.join(BIN, "slab_ring_cylinder")
     for heights, centre, roles_want in (("112,72,104,96", 148, [(0, 0, 0), (1, 0, 0), (0, 0, 0), (0, 0, 0)]),
                                         ("104,80,88,112", 184, [(0, 0, 0), (1, 0, 1), (1, 1, 0), (0, 0, 0)])):
-        r = subprocess.run([exe, "--emulate", "4", "--slab-rows", heights, "--cols", "160", "--diameter", "22", "--centre-row", str(centre),
-                            "--steps", "15", "--warmup", "5", "--check", "1"], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        line = json.loads(r.stdout.strip().splitlines()[-1])
+        line = last_json(run_driver("slab_ring_cylinder", "--emulate", 4, "--slab-rows", heights, "--cols", 160, "--diameter", 22,
+                                    "--centre-row", centre, "--steps", 15, "--warmup", 5, "--check", 1, timeout=300))
         assert line["check"] == "bitwise equal to one block" and line["global_rows"] == 384
         assert [s["rows"] for s in line["per_slab"]] == [int(h) for h in heights.split(",")]
         roles = [(s["owner"], s["straddle_prev"], s["straddle_next"]) for s in line["per_slab"]]
@@ -381,15 +321,10 @@ def test_decompose_domain_loop_driver_vs_oracle(tmp_path, oracle, fast):
     drivers/decompose_domain_loop.cpp on lbm_links_* (one gather launch for the ~70 slice assignments
     of a step).  L = 128, 300 steps: bitwise vs the oracle in the reference operation order; 1e-12
     with the default reassociated collision (blocks B, C, D; A's delta form always runs in order)."""
-    env = dict(os.environ)
-    exe = os.path.join(BIN, "decompose_domain_loop")
-    assert os.path.exists(exe)
-    # the tuning switch is process-wide state of the library: hand it over through the environment
-    env["LBM_TUNE"] = f"bgk_fast={fast}"
+    # the tuning switch is process-wide state of the library: handed over through the environment
     # fast = 1 also replays the step as a captured HIP graph (lbm_graph_*): same bits as plain launches
-    r = subprocess.run([exe, "--L", "128", "--T", "300", "--graph", str(fast), "--dump", str(tmp_path / "ddl")],
-                       capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    run_driver("decompose_domain_loop", "--L", 128, "--T", 300, "--graph", fast, "--dump", tmp_path / "ddl", timeout=300,
+               tune=f"bgk_fast={fast}")
     want = oracle.ddl_run(128, 300)
     shapes = [(128, 32), (32, 64), (128, 32), (32, 64)]
     for k, name in enumerate("ABCD"):
@@ -440,20 +375,16 @@ def test_rectangle_sedimentation_driver_vs_oracle(tmp_path, oracle, fast):
     drivers/rectangle_sedimentation_test.cpp on lbm_links_* (affine links) vs the oracle (PARITY
     UNPINNED: the reference driver needs toml++).  540 x 420 lattice, 60 steps: bitwise in the
     reference operation order, 1e-12 with the default reassociated collision."""
-    import json
     toml = open(os.path.join(PKG, "examples", "parameters.toml")).read()
     toml = toml.replace("characteristic_velocity = 0.5", "characteristic_velocity = 0.03")
     toml = toml.replace("lattice_spacing = 2.0E-5", "lattice_spacing = 1.0E-4")
     (tmp_path / "sed.toml").write_text(toml)
-    r = subprocess.run([os.path.join(BIN, "params_dump"), str(tmp_path / "sed.toml")], capture_output=True, text=True)
-    lp = json.loads(r.stdout)["lattice"]
+    lp = json.loads(run_driver("params_dump", tmp_path / "sed.toml", timeout=60).stdout)["lattice"]
     X, Y = lp["X"], lp["Y"]
     assert (X, Y) == (540, 420) and lp["u"] < 0.06
-    env = dict(os.environ, LBM_TUNE=f"bgk_fast={fast}")
     steps = 60
-    r = subprocess.run([os.path.join(BIN, "rectangle_sedimentation_test"), str(tmp_path / "sed.toml"), "--steps", str(steps),
-                        "--dump", str(tmp_path / "sed")], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    run_driver("rectangle_sedimentation_test", tmp_path / "sed.toml", "--steps", steps, "--dump", tmp_path / "sed", timeout=300,
+               tune=f"bgk_fast={fast}")
     want = oracle.sed_steps(X, Y, lp["omega"], lp["u"], steps)
     got = dict(f=np.fromfile(tmp_path / "sed-f.f64").reshape(X, Y, 9), g=np.fromfile(tmp_path / "sed-g.f64").reshape(X, Y, 9),
                rho=np.fromfile(tmp_path / "sed-rho.f64").reshape(X, Y), u=np.fromfile(tmp_path / "sed-u.f64").reshape(X, Y, 2),

@@ -8,11 +8,7 @@ cylinder on the seam, lbm_ring_pressure_start / lbm_ring_bgk_block_pressure.
 Reference contract: the block binding of test/decompose_domain.cpp:181-187 and the cross-block pressure rows
 of :50-73 (two blocks there; n slabs with D ghost rows here)."""
 import ctypes as ct
-import json
 import os
-import subprocess
-import sys
-import time
 
 import numpy as np
 import pytest
@@ -22,10 +18,10 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
 from gpu_util import bits_equal, dev, download_aos, ulp_diff, upload_soa  # noqa: E402
+from proc_util import run_ranks as start_ranks  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 from pyoracle import hpt_params  # noqa: E402
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 IPC = 1
 W9 = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
 
@@ -41,41 +37,9 @@ def hexof(s):
     return bytes(s).hex()
 
 
-def run_ranks(lib, tmp_path, case, n, cfg, arrays, timeout=300):
-    """start n rank processes on `case`, wait, return their outputs (a failing rank ends the others)"""
-    work = str(tmp_path)
-    cfg = dict(cfg, transport=IPC)
-    json.dump(cfg, open(os.path.join(work, "cfg.json"), "w"))
-    ident = (ct.c_ubyte * 128)()
-    lib.ring_unique_id_ex(ident, IPC)
-    open(os.path.join(work, "id.bin"), "wb").write(bytes(ident))
-    for k, a in arrays.items():
-        np.save(os.path.join(work, k + ".npy"), a)
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = []
-    for r in range(n):
-        log = open(os.path.join(work, f"rank{r}.log"), "w")
-        procs.append((subprocess.Popen([sys.executable, os.path.join(HERE, "ring_rank.py"), case, str(r), str(n), work],
-                                       stdout=log, stderr=subprocess.STDOUT, env=env), log))
-    t0, failed = time.time(), None
-    while any(p.poll() is None for p, _ in procs):
-        bad = [r for r, (p, _) in enumerate(procs) if p.poll() not in (None, 0)]
-        if bad or time.time() - t0 > timeout:
-            failed = f"rank(s) {bad} failed" if bad else f"timed out after {timeout} s"
-            for p, _ in procs:
-                if p.poll() is None:
-                    p.kill()
-            break
-        time.sleep(0.05)
-    for p, log in procs:
-        p.wait()
-        log.close()
-    bad = [r for r, (p, _) in enumerate(procs) if p.returncode != 0]
-    if failed or bad:
-        logs = "\n".join(f"--- rank {r} (rc {procs[r][0].returncode}) ---\n" + open(os.path.join(work, f"rank{r}.log")).read()[-3000:]
-                         for r in range(n))
-        raise AssertionError(f"{case}: {failed or bad}\n{logs}")
-    return [np.load(os.path.join(work, f"out_{r}.npz")) for r in range(n)]
+def run_ranks(lib, tmp_path, case, n, cfg, arrays):
+    """start n rank processes of tests/ring_rank.py on `case`, wait, return their outputs (a failing rank ends the others)"""
+    return start_ranks(lib, tmp_path, "ring_rank.py", n, dict(cfg, transport=IPC), arrays, args=(case,), timeout=300, what=case)
 
 
 def perturbed_rest(H, W, seed):
