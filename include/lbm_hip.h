@@ -1158,6 +1158,61 @@ int lbm_solver_run_until(lbm_solver* sv, const lbm_converge* cv, int max_steps, 
 int lbm_ade_solver_run_until(lbm_ade_solver* sv, const lbm_converge* cv, int max_steps, int* steps_done,
                              int* converged, double* last_value);
 
+/* ---- wall exchange: what the interior walls (lbm_ade_iwalls) take from the lattices in one stream ----------------
+ * A table node of the wall pass first gets the domain's own rules (the wall gather of f and of g, and the anti-bounce-
+ * back of the domain's FIXED edges), then the table's.  For every slot s the table names at the node, x_in[s] is the
+ * streamed population immediately before the table's rule for that distribution, x_out[s] the one after it, and
+ * d[s] = x_in[s] - x_out[s] is what the wall removes from the lattice at that slot in this stream.  Per node, each term
+ * is accumulated from +0.0 over s = 1..8 ascending, named slots only, in IEEE f64 without contraction:
+ *   FORCE_R       f slots: + d[s] where c_s has row component +1, - d[s] where -1 -- the momentum given to the walls, i.e.
+ *                 the force on them, row component
+ *   FORCE_C       the same with the column component
+ *   MASS          f slots: d[s], the fluid mass taken
+ *   SCALAR        all named g slots: d[s], the scalar taken (deposition)
+ *   SCALAR_FIXED  the FIXED g slots only
+ *   NODES         1.0 per counted node; exact
+ * This is the conservation form, the model's own: a wall node stays a fluid node whose outgoing populations stream on to
+ * the node behind it, so the sums are exactly what leaves the lattices (Ladd's link form would count momentum the
+ * lattice never loses).  The velocity the FIXED g slots see is the pass's own: the collision's u in the form of the
+ * call, the unshifted u0 in a buoyant step -- in the reference order x_out is, bit for bit, the population the pass
+ * holds before it collides.  An open-boundary table plays no part (the wall pass ignores the source map as well: the
+ * host refuses the overlaps where that would matter).
+ * region4 = {r0, r1, c0, c1} selects the nodes of [r0, r1) x [c0, c1) in the row and column indices of the lattice of
+ * the call (clipped to it; NULL: every node); a node outside contributes nothing.  Summation is the diagnostics' (fold64
+ * above): the value of lattice row r is fold64 over the row's table nodes in column order (the k-th node of the row is
+ * element k; a node outside the region adds nothing), the value of a row range fold64 over the row values; a row without
+ * a counted node has the value +0.0.  So a table filled slab by slab, under any launch shape, folds to the bits of one
+ * block. */
+#define LBM_WALLX_NQ 6
+#define LBM_WALLX_FORCE_R 0
+#define LBM_WALLX_FORCE_C 1
+#define LBM_WALLX_MASS 2
+#define LBM_WALLX_SCALAR 3
+#define LBM_WALLX_SCALAR_FIXED 4
+#define LBM_WALLX_NODES 5
+/* row values of rows [row_begin, row_end) of the stream FROM the post-collision lattices fo, go into table
+ * [LBM_WALLX_NQ][table_rows] (device): row r lands at table[q * table_rows + table_row0 + r], nothing else is written
+ * and the lattices are only read.  The arguments are those of lbm_ade_stream_collide_w for the same stream; on a slab g
+ * carries the ghost rows (row edges HALO or BOUNCE_BACK) and iwalls is the slab's view (lbm_ade_iwalls_slab).  A NULL or
+ * empty table writes +0.0 row values.  Enqueues one launch: no atomics, no allocation, no host synchronisation;
+ * capturable. */
+int lbm_ade_wallx_rows(double* table, int table_rows, int table_row0, const double* fo, const double* go,
+                       const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                       const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                       const int* region4, int row_begin, int row_end, lbm_stream_t s);
+/* rows [row_begin, row_end) of a table to out_dev [LBM_WALLX_NQ] (device).  Enqueues one launch; capturable. */
+int lbm_ade_wallx_fold(double* out_dev, const double* table, int table_rows, int row_begin, int row_end, lbm_stream_t s);
+/* the same fold of a table in host memory, in plain C++ without any device call */
+int lbm_ade_wallx_fold_host(double* out, const double* table_host, int table_rows, int row_begin, int row_end);
+/* The exchange of the stream lbm_ade_solver_get_state shows -- from the post-collision level the context holds, with its
+ * own edges, parameters, scalar walls, buoyancy and table (after the collide-only first step too, whose stream takes the
+ * same rules) -- over rows [row_begin, row_end): out_host [LBM_WALLX_NQ], and the row table [LBM_WALLX_NQ][R] if
+ * table_host is given (rows outside the range: 0.0).  The context owns the device table and a pinned buffer (allocated
+ * on first use); copies LBM_WALLX_NQ doubles (or the table) and synchronises once.  LBM_ERR_STATE while the state is
+ * pre-collision (before the first step): nothing has streamed. */
+int lbm_ade_solver_wall_exchange(lbm_ade_solver* sv, const int* region4, int row_begin, int row_end, double* out_host,
+                                 double* table_host);
+
 /* Tuning table.  Launch-shape keys (every setting produces identical results) and the three
  * implementation switches, which select between a model's two collision implementations:
  *   "bgk_fast", "kbc_fast", "cg_fused" (default 1): the reassociated collision / the one-launch

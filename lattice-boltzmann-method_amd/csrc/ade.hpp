@@ -599,6 +599,116 @@ __global__ __launch_bounds__(256) void k_ade_iwalls_state(double* __restrict__ x
   for (int q = 1; q < Q; ++q) xs[q * g.plane + o] = x[q];
 }
 
+// the six halvings of fold64 across a wave (diag.hpp: diag_wave_fold<DIAG_ADD>, the same additions): lane j < s takes
+// p[j] + p[j + s]; the other lanes hold values nobody reads
+__device__ __forceinline__ double ade_wave_sum(double p) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) p = p + __shfl_down(p, s, 64);
+  return p;
+}
+
+// Wall exchange (lbm_hip.h "wall exchange"): what the table's rules take from the lattices in the stream FROM fo, go, as
+// LBM_WALLX_NQ row values per lattice row.  One wave per row, four rows per workgroup, grid-strided over rows [row_begin,
+// row_end); lane j takes the row's nodes first[r] + j + 64 k, k ascending, and IS accumulator j of fold64 -- the halvings
+// are wave shuffles, as in k_diag_rows.  Per node the lane runs k_ade_iwalls_ranges' body up to the collisions -- the
+// domain's gather of f, the f slots, the moments, the domain's gather and FIXED edges of g, the g slots -- noting each
+// named slot before and after the table's rule; the only part of fm.collide that is used is its u (what the wall pass
+// feeds the FIXED slots; a buoyant call passes the reference-order model, whose u is ade_fluid_moments' u0), so the
+// relaxation is dead code.  A node outside rows [reg_r0, reg_r1) or columns [reg_c0, reg_c1) adds nothing.  first =
+// NULL: no table, every row value +0.0.  Lane 0 writes table[q * table_rows + table_row0 + r]; nothing else is written.
+// No atomics, no LDS, no scratch.  211 VGPRs (228 with FIXED) where the wall pass has 70-93: with no collision and no store
+// between them the compiler issues the 72 loads of a node (two gathers, each with the node's own populations) together.
+// That is what a launch of a few thousand nodes wants -- its time is load latency, not occupancy
+// (profiles/ade_wall_exchange.txt).
+template <class FM, bool FIXED>
+__global__ __launch_bounds__(256) void k_ade_wall_exchange(double* __restrict__ table, int table_rows, int table_row0,
+                                                           const double* __restrict__ fo, const double* __restrict__ go,
+                                                           Geom g, Bc bc, FM fm, double wr, double wc, AdeWalls sw,
+                                                           const AdeIwallNode* __restrict__ nodes,
+                                                           const int* __restrict__ first, int reg_r0, int reg_r1,
+                                                           int reg_c0, int reg_c1, int row_begin, int row_end) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  for (long long rr = row_begin + (long long)blockIdx.x * 4 + wave; rr < row_end; rr += (long long)gridDim.x * 4) {
+    const int r = (int)rr;
+    double acc[LBM_WALLX_NQ];
+#pragma unroll
+    for (int q = 0; q < LBM_WALLX_NQ; ++q) acc[q] = 0.0;
+    const bool counted = first != nullptr && r >= reg_r0 && r < reg_r1;  // wave-uniform
+    const int i1 = counted ? first[r + 1] : 0;
+    for (int i = (counted ? first[r] : 0) + lane; i < i1; i += 64) {
+      const AdeIwallNode nd = nodes[i];
+      const int c = nd.c;
+      if (c < reg_c0 || c >= reg_c1) continue;
+      const long o = g.at(r, c);
+      double f[Q], h[Q], x[Q], rho, ux, uy;
+      gather_walls(f, fo, g, bc, r, c);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) x[q] = f[q];
+      ade_iwalls_fluid(f, fo, g, o, nd.slots);
+      double t_r = 0.0, t_c = 0.0, t_m = 0.0, t_s = 0.0, t_f = 0.0;
+#pragma unroll
+      for (int s = 1; s < Q; ++s) {
+        if (!((nd.slots >> (s - 1)) & 1u)) continue;
+        const double d = x[s] - f[s];
+        if (icx(s) == 1) t_r = t_r + d;
+        if (icx(s) == -1) t_r = t_r - d;
+        if (icy(s) == 1) t_c = t_c + d;
+        if (icy(s) == -1) t_c = t_c - d;
+        t_m = t_m + d;
+      }
+#pragma unroll
+      for (int q = 0; q < Q; ++q) x[q] = f[q];
+      fm.collide(x, rho, ux, uy);
+      gather_walls(h, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, r, c);
+      if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, wr, wc);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) x[q] = h[q];
+      ade_iwalls_scalar(h, go, g, o, nd.slots, nd.conc, ux, uy, wr, wc);
+#pragma unroll
+      for (int s = 1; s < Q; ++s) {
+        if (!((nd.slots >> (7 + s)) & 1u)) continue;
+        const double d = x[s] - h[s];
+        t_s = t_s + d;
+        if ((nd.slots >> (15 + s)) & 1u) t_f = t_f + d;
+      }
+      acc[LBM_WALLX_FORCE_R] = acc[LBM_WALLX_FORCE_R] + t_r;
+      acc[LBM_WALLX_FORCE_C] = acc[LBM_WALLX_FORCE_C] + t_c;
+      acc[LBM_WALLX_MASS] = acc[LBM_WALLX_MASS] + t_m;
+      acc[LBM_WALLX_SCALAR] = acc[LBM_WALLX_SCALAR] + t_s;
+      acc[LBM_WALLX_SCALAR_FIXED] = acc[LBM_WALLX_SCALAR_FIXED] + t_f;
+      acc[LBM_WALLX_NODES] = acc[LBM_WALLX_NODES] + 1.0;
+    }
+#pragma unroll
+    for (int q = 0; q < LBM_WALLX_NQ; ++q) acc[q] = ade_wave_sum(acc[q]);
+    if (lane == 0) {
+      double* __restrict__ t = table + table_row0 + r;
+#pragma unroll
+      for (int q = 0; q < LBM_WALLX_NQ; ++q) t[(size_t)q * table_rows] = acc[q];
+    }
+  }
+}
+
+// Rows [row_begin, row_end) of a wall-exchange table to LBM_WALLX_NQ values: ONE workgroup of LBM_WALLX_NQ waves, wave q
+// folds quantity q with lane j as accumulator j -- k_diag_fold's fold for sums alone: the slices are loaded four at a time
+// (the loads in flight together) and added in ascending order.
+__global__ __launch_bounds__(64 * LBM_WALLX_NQ) void k_ade_wallx_fold(double* __restrict__ out,
+                                                                     const double* __restrict__ table, int table_rows,
+                                                                     int row_begin, int row_end) {
+  const int lane = threadIdx.x & 63;
+  const int q = threadIdx.x >> 6;
+  const double* __restrict__ x = table + (size_t)q * table_rows;
+  double p = 0.0;
+  int r = row_begin + lane;
+  for (; r - lane + 256 <= row_end; r += 256) {  // four full slices (r - lane is wave-uniform)
+    const double a = x[r], b = x[r + 64], c = x[r + 128], d = x[r + 192];
+    p = (((p + a) + b) + c) + d;
+  }
+  for (; r < row_end; r += 64) p = p + x[r];
+  p = ade_wave_sum(p);
+  if (lane == 0) out[q] = p;
+}
+
 // Collide only, no streaming: the driver's first iteration on the pre-collision state (one node per thread).
 template <class FM, class SM, bool WITH_MOMENTS, bool BUOYANT = false>
 __global__ __launch_bounds__(256) void k_ade_collide(double* __restrict__ fp, double* __restrict__ gp,

@@ -18,7 +18,8 @@
 // Interior walls of the fused step: a host table of wall nodes, merged per node and kept sorted by (r, c) while it is
 // built; lbm_ade_iwalls_finalize uploads it once (the only device call) and it is immutable from then on.  first: the
 // index of the first node of each row (R + 1 entries, first[R] = n), kept on the host by finalize -- a part of a slab
-// finds the node ranges of its rows there, with no allocation and no host synchronisation in the step path.
+// finds the node ranges of its rows there, with no allocation and no host synchronisation in the step path -- and uploaded
+// beside the nodes (d_first) for the wall exchange, whose waves find their rows on the device.
 struct lbm_ade_iwalls {
   struct Entry {
     unsigned f = 0, g = 0, g_fixed = 0;  // slot masks, bit s-1 = slot s; g_fixed: the g slots that are FIXED
@@ -30,6 +31,7 @@ struct lbm_ade_iwalls {
   bool finalized = false;
   int n = 0;                              // nodes uploaded
   lbm::AdeIwallNode* d_nodes = nullptr;   // device copy, sorted by (r, c)
+  int* d_first = nullptr;                 // device copy of first
   std::vector<int> first;                 // finalized: first[r] = index of the first node of rows >= r
 };
 
@@ -669,6 +671,45 @@ static int ade_part(const char* name, double* fn, double* gn, const double* fo, 
   return rc ? rc : ade_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
 }
 
+// The wall exchange of rows [row_begin, row_end) of the stream from fo, go, under the caller's name: the host checks of the
+// stream itself (ade_resolve; a single block or a slab, as the geometry says), the table's rows, one launch.  The region
+// is clipped to the lattice here.  A buoyant call takes the reference-order model, as its step does.
+static int ade_wallx_rows(const char* fn, double* table, int table_rows, int table_row0, const double* fo, const double* go,
+                          const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                          const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                          const int* region4, int row_begin, int row_end, hipStream_t st) {
+  AdeCall k;
+  int rc = ade_resolve(fn, lg, lbc, fluid, scalar, sbc, buoy, iwalls, true, &k);
+  if (rc) return rc;
+  LBM_REQUIRE(table && fo && go, "%s: NULL argument (table, fo, go)", fn);
+  rc = diag_range_check(fn, lg->R, row_begin, row_end);
+  if (rc) return rc;
+  LBM_REQUIRE(table_row0 >= 0 && table_rows > 0 && (long long)table_row0 + row_end <= table_rows,
+              "%s: table_row0=%d + rows [%d, %d) do not fit table_rows=%d", fn, table_row0, row_begin, row_end, table_rows);
+  auto clip = [](int v, int n) { return v < 0 ? 0 : v > n ? n : v; };
+  const int r0 = region4 ? clip(region4[0], lg->R) : 0, r1 = region4 ? clip(region4[1], lg->R) : lg->R;
+  const int c0 = region4 ? clip(region4[2], lg->C) : 0, c1 = region4 ? clip(region4[3], lg->C) : lg->C;
+  const int* first = k.n_wall_nodes > 0 ? iwalls->d_first : nullptr;
+  const int cap = tuning("grid_cap", 0);
+  const int grid = capped_grid((row_end - row_begin + 3) / 4, cap > 0 ? cap : 8192);
+  return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto) {
+    using FM = std::decay_t<decltype(fm)>;
+    with_flags([&](auto F) {
+      LBM_KLAUNCH((k_ade_wall_exchange<FM, F()>), dim3(grid), dim3(256), 0, st, table, table_rows, table_row0, fo, go, k.g,
+                  k.bc, fm, sm.wr, sm.wc, k.sw, k.wall_nodes, first, r0, r1, c0, c1, row_begin, row_end);
+    }, k.sw.fixed);
+    LBM_CHECK_LAUNCH();
+    return (int)LBM_OK;
+  });
+}
+
+static int ade_wallx_fold_launch(double* out_dev, const double* table, int table_rows, int row_begin, int row_end,
+                                 hipStream_t st) {
+  LBM_KLAUNCH(k_ade_wallx_fold, dim3(1), dim3(64 * LBM_WALLX_NQ), 0, st, out_dev, table, table_rows, row_begin, row_end);
+  LBM_CHECK_LAUNCH();
+  return LBM_OK;
+}
+
 }  // namespace lbm
 
 // the driver loop on one block: two time levels, each one allocation holding the 9 planes of f followed by the
@@ -694,6 +735,7 @@ struct lbm_ade_solver {
   bool post;  // the state is post-collision (P-form); false: pre-collision f_adve, g_adve
   long long steps, launches;
   lbm::DiagBuf diag;  // row table and result buffers of lbm_ade_solver_diag (allocated by its first call)
+  lbm::DiagBuf wallx;  // the same of lbm_ade_solver_wall_exchange: [LBM_WALLX_NQ][R], LBM_WALLX_NQ values
   double* f(int k) const { return lat[k]; }
   double* h(int k) const { return lat[k] + 9 * g.plane_stride; }
 };
@@ -834,6 +876,7 @@ int lbm_ade_solver_destroy(lbm_ade_solver* sv) {
   for (double* p : {sv->lat[0], sv->lat[1], sv->dense, sv->stage, sv->rho, sv->u, sv->conc, sv->carry[0], sv->carry[1]})
     if (p) (void)hipFree(p);
   sv->diag.release();
+  sv->wallx.release();
   delete sv;
   return LBM_OK;
 }
@@ -1017,6 +1060,52 @@ int lbm_ade_solver_diag(lbm_ade_solver* sv, const double* profile_dev, int row_b
                      row_end, out_host, table_host, sv->st);
 }
 
+int lbm_ade_wallx_rows(double* table, int table_rows, int table_row0, const double* fo, const double* go, const lbm_geom* g,
+                       const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                       const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                       const int* region4, int row_begin, int row_end, lbm_stream_t s) {
+  return ade_wallx_rows("lbm_ade_wallx_rows", table, table_rows, table_row0, fo, go, g, bc, fluid, scalar, sbc, buoy, iwalls,
+                        region4, row_begin, row_end, as_stream(s));
+}
+
+int lbm_ade_wallx_fold(double* out_dev, const double* table, int table_rows, int row_begin, int row_end, lbm_stream_t s) {
+  int rc = diag_fold_check("lbm_ade_wallx_fold", out_dev, table, table_rows, row_begin, row_end);
+  if (rc) return rc;
+  return ade_wallx_fold_launch(out_dev, table, table_rows, row_begin, row_end, as_stream(s));
+}
+
+int lbm_ade_solver_wall_exchange(lbm_ade_solver* sv, const int* region4, int row_begin, int row_end, double* out_host,
+                                 double* table_host) {
+  const char* fn = "lbm_ade_solver_wall_exchange";
+  LBM_REQUIRE(sv && out_host, "%s: NULL argument (solver, out_host)", fn);
+  const int R = sv->g.R;
+  int rc = diag_range_check(fn, R, row_begin, row_end);
+  if (rc) return rc;
+  if (!sv->post) {
+    set_error("%s: the state is pre-collision (no step yet): nothing has streamed", fn);
+    return LBM_ERR_STATE;
+  }
+  DiagBuf& buf = sv->wallx;
+  const size_t table_bytes = (size_t)LBM_WALLX_NQ * R * sizeof(double);
+  if (!buf.table) {
+    LBM_CHECK_HIP(hipMalloc(&buf.table, table_bytes));
+    LBM_CHECK_HIP(hipMalloc(&buf.out_dev, LBM_WALLX_NQ * sizeof(double)));
+    LBM_CHECK_HIP(hipHostMalloc(&buf.pinned, LBM_WALLX_NQ * sizeof(double)));
+  }
+  if (table_host && (row_begin > 0 || row_end < R)) LBM_CHECK_HIP(hipMemsetAsync(buf.table, 0, table_bytes, sv->st));
+  const int k = sv->cur;
+  rc = ade_wallx_rows(fn, buf.table, R, 0, sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid, &sv->scalar,
+                      sv->fixed ? &sv->sbc : nullptr, sv->buoyant ? &sv->buoy : nullptr, sv->walls, region4, row_begin,
+                      row_end, sv->st);
+  if (!rc) rc = ade_wallx_fold_launch(buf.out_dev, buf.table, R, row_begin, row_end, sv->st);
+  if (rc) return rc;
+  LBM_CHECK_HIP(hipMemcpyAsync(buf.pinned, buf.out_dev, LBM_WALLX_NQ * sizeof(double), hipMemcpyDeviceToHost, sv->st));
+  if (table_host) LBM_CHECK_HIP(hipMemcpyAsync(table_host, buf.table, table_bytes, hipMemcpyDeviceToHost, sv->st));
+  LBM_CHECK_HIP(hipStreamSynchronize(sv->st));
+  for (int q = 0; q < LBM_WALLX_NQ; ++q) out_host[q] = buf.pinned[q];
+  return LBM_OK;
+}
+
 int lbm_ade_solver_run_until(lbm_ade_solver* sv, const lbm_converge* cv, int max_steps, int* steps_done, int* converged,
                              double* last_value) {
   int rc = diag_converge_check("lbm_ade_solver_run_until", cv, max_steps);
@@ -1192,10 +1281,14 @@ int lbm_ade_iwalls_finalize(lbm_ade_iwalls* t) {
       host.push_back(AdeIwallNode{kv.first.first, kv.first.second, kv.second.f | (kv.second.g << 8) | (kv.second.g_fixed << 16),
                                   0, kv.second.conc});
     LBM_CHECK_HIP(hipMalloc(&t->d_nodes, host.size() * sizeof(AdeIwallNode)));
-    hipError_t e = hipMemcpy(t->d_nodes, host.data(), host.size() * sizeof(AdeIwallNode), hipMemcpyHostToDevice);
+    hipError_t e = hipMalloc(&t->d_first, first.size() * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(t->d_nodes, host.data(), host.size() * sizeof(AdeIwallNode), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_first, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
       (void)hipFree(t->d_nodes);
+      if (t->d_first) (void)hipFree(t->d_first);
       t->d_nodes = nullptr;
+      t->d_first = nullptr;
       set_error("lbm_ade_iwalls_finalize: %s", hipGetErrorString(e));
       return LBM_ERR_HIP;
     }
@@ -1209,6 +1302,7 @@ int lbm_ade_iwalls_finalize(lbm_ade_iwalls* t) {
 int lbm_ade_iwalls_destroy(lbm_ade_iwalls* t) {
   if (!t) return LBM_OK;
   if (t->d_nodes) (void)hipFree(t->d_nodes);
+  if (t->d_first) (void)hipFree(t->d_first);
   delete t;
   return LBM_OK;
 }

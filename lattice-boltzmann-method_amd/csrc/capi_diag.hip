@@ -47,7 +47,7 @@ static int diag_rows_launch(double* table, int table_rows, int table_row0, const
   return LBM_OK;
 }
 
-static int diag_fold_check(const char* fn, const double* out, const double* table, int table_rows, int row_begin, int row_end) {
+int diag_fold_check(const char* fn, const double* out, const double* table, int table_rows, int row_begin, int row_end) {
   LBM_REQUIRE(out && table, "%s: NULL argument (out, table)", fn);
   LBM_REQUIRE(table_rows > 0, "%s: table_rows=%d must be positive", fn, table_rows);
   return diag_range_check(fn, table_rows, row_begin, row_end);
@@ -109,6 +109,15 @@ int lbm_diag_fold_host(double* out, const double* table_host, int table_rows, in
   if (rc) return rc;
   for (int q = 0; q < LBM_DIAG_NQ; ++q)
     out[q] = diag_fold_one(table_host + (size_t)q * table_rows + row_begin, row_end - row_begin, diag_op(q));
+  return LBM_OK;
+}
+
+// the wall exchange's table (lbm_hip.h "wall exchange"): LBM_WALLX_NQ sums, the same host fold
+int lbm_ade_wallx_fold_host(double* out, const double* table_host, int table_rows, int row_begin, int row_end) {
+  int rc = diag_fold_check("lbm_ade_wallx_fold_host", out, table_host, table_rows, row_begin, row_end);
+  if (rc) return rc;
+  for (int q = 0; q < LBM_WALLX_NQ; ++q)
+    out[q] = diag_fold_one(table_host + (size_t)q * table_rows + row_begin, row_end - row_begin, DIAG_ADD);
   return LBM_OK;
 }
 

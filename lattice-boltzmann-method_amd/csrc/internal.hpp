@@ -95,6 +95,9 @@ struct DiagBuf {
 int diag_reduce(const char* fn, DiagBuf& buf, const double* rho, const double* u, const double* conc, const double* profile,
                 int R, int C, int row_begin, int row_end, double* out_host, double* table_host, hipStream_t st);
 int diag_range_check(const char* fn, int R, int row_begin, int row_end);
+// the arguments of a fold of a row table (out, table given; table_rows positive; the range inside it), shared with the wall
+// exchange's folds (capi_ade.hip)
+int diag_fold_check(const char* fn, const double* out, const double* table, int table_rows, int row_begin, int row_end);
 // the rule's own fields, checked before the context is looked at (its rows: diag_range_check, once the context is known)
 int diag_converge_check(const char* fn, const lbm_converge* cv, int max_steps);
 // the loop of lbm_solver_run_until / lbm_ade_solver_run_until (lbm_hip.h) over a context's own step(n) -- n iterations, the

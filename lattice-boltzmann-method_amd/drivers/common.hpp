@@ -36,6 +36,12 @@ inline bool parse_buoyancy(const std::string& s, double (&v)[6]) {
   if (n != 3 && n != 6) throw std::runtime_error("--buoyancy: beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b] ('" + s + "')");
   return true;
 }
+// the six values of a wall exchange (LBM_WALLX_* order) as key=value lines, 17 significant digits
+inline void print_wall_exchange(const std::vector<double>& x) {
+  static const char* const keys[6] = {"force_r", "force_c", "mass", "uptake", "uptake_fixed", "wall_nodes"};
+  for (size_t q = 0; q < 6 && q < x.size(); ++q) std::printf("%s=%.17g\n", keys[q], x[q]);
+  std::fflush(stdout);
+}
 inline std::string arg_value(int argc, char** argv, const std::string& key, const std::string& dflt) {
   for (int i = 1; i + 1 < argc; ++i)
     if (key == argv[i]) return argv[i + 1];

@@ -5,7 +5,7 @@
 // (as the driver initialises g_adve, :95).
 //   usage: passive_scalar_box R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]
 //          [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]
-//          [--rectangle r_top,c_first,c_second[,conc]]
+//          [--rectangle r_top,c_first,c_second[,conc]] [--exchange 0|1]
 // --dump writes prefix-{f0,g0,f,g,rho,u,C}.f64 (raw f64, reference layout [R][C][Q]); --walls 1: bounce-back columns,
 // 2: bounce-back rows and columns.  --fixed: the named edges (row_lo, row_hi, col_lo, col_hi; walls of the fluid) hold
 // the scalar at the constant C_w (lbm_ade_scalar_bc FIXED), the others stay no-flux.  --buoyancy: the scalar pushes on the
@@ -13,7 +13,8 @@
 // the scalar is passive.  --rectangle: the sedimentation driver's rectangle (rectangle_sedimentation_test.cpp:184-196,
 // :220-232) standing on the last row as interior walls (lbm::AdeInteriorWalls): ceiling row r_top (negative: from the
 // end) over columns c_first..c_second, the two side walls below it down to the last row; the scalar is absorbed
-// (FIXED, C_w = 0) unless conc gives the C_w the body holds.
+// (FIXED, C_w = 0) unless conc gives the C_w the body holds.  --exchange 1: what the body takes from the lattices in the
+// stream of the final state (lbm::AdeSolver::wall_exchange) as force_r, force_c, mass, uptake, uptake_fixed, wall_nodes.
 #include <cmath>
 #include <iostream>
 #include <sstream>
@@ -26,7 +27,7 @@ int main(int argc, char** argv) {
   if (argc < 8) {
     std::cerr << "usage: " << argv[0] << " R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]"
                  " [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]"
-                 " [--rectangle r_top,c_first,c_second[,conc]]\n";
+                 " [--rectangle r_top,c_first,c_second[,conc]] [--exchange 0|1]\n";
     return 1;
   }
   try {
@@ -36,6 +37,7 @@ int main(int argc, char** argv) {
     const std::string dump = arg_value(argc, argv, "--dump", "");
     const int form = std::stoi(arg_value(argc, argv, "--form", "0"));
     const int walls = std::stoi(arg_value(argc, argv, "--walls", "0"));
+    const bool exchange = std::stoi(arg_value(argc, argv, "--exchange", "0")) != 0;
     lbm_ade_scalar_bc sbc{};
     std::stringstream fixed(arg_value(argc, argv, "--fixed", ""));
     for (std::string item; std::getline(fixed, item, ',');) {
@@ -113,6 +115,7 @@ int main(int argc, char** argv) {
     std::cout.precision(17);
     std::cout << "steps=" << steps << "\nlaunches=" << sv.launches() << "\nmass_C0=" << mass0 << "\nmass_C=" << mass
               << std::endl;
+    if (exchange) print_wall_exchange(sv.wall_exchange());
     if (!dump.empty()) {
       dump_f64(dump + "-f0.f64", f0);
       dump_f64(dump + "-g0.f64", g0);

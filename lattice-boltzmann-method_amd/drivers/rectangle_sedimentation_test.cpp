@@ -3,12 +3,15 @@
 // to BOTH velocity components, :124) in a channel with anti-bounce-back inlet / outlet columns, a
 // specular top, a no-slip bottom and a three-sided rectangular obstacle at hard-coded coordinates
 // (:71-73: the lattice needs more than 151 rows and 250 columns).
-//   usage: rectangle_sedimentation_test params.toml [--steps N] [--dump prefix] [--fused 1] [--time 1]
+//   usage: rectangle_sedimentation_test params.toml [--steps N] [--dump prefix] [--fused 1] [--time 1] [--exchange 1]
 //
 // --fused 1: the first iteration on the operator path below (the driver collides g with the held C = C_w in it, not with
 // calc_rho(g)), then f_adve, g_adve go to lbm::AdeSolver with bc = {row_hi: BOUNCE_BACK}, the rectangle as
 // AdeInteriorWalls and the channel's AdeOpenBoundary, and the remaining steps run fused -- interior launch, edge pass,
 // open-boundary pass, interior-wall pass per step.  --time 1 prints ms per step of the loop of either path.
+// --exchange 1 (with --fused 1): the deposition history -- at every snapshot interval of the parameters (and at the end)
+// `step=N` and what the rectangle took in the stream of that state, lbm::AdeSolver::wall_exchange, as force_r, force_c,
+// mass, uptake, uptake_fixed, wall_nodes.
 //
 // Engine mapping (operator level, like the reference's loop): per step one fused collide launch for
 // f (with rho, u), the unfused equilibrium / collision pair for g (its equilibrium takes u + w_s,
@@ -49,7 +52,7 @@ struct Table {
 
 int main(int argc, char* argv[]) {
   if (argc < 2) {
-    std::cerr << "usage: " << argv[0] << " params.toml [--steps N] [--dump prefix] [--fused 1] [--time 1]\n";
+    std::cerr << "usage: " << argv[0] << " params.toml [--steps N] [--dump prefix] [--fused 1] [--time 1] [--exchange 1]\n";
     return 1;
   }
   lbm::toml::table tbl;
@@ -70,6 +73,7 @@ int main(int argc, char* argv[]) {
     const std::string dump = arg_value(argc, argv, "--dump", "");
     const bool fused = std::stoi(arg_value(argc, argv, "--fused", "0")) != 0;
     const bool timed = std::stoi(arg_value(argc, argv, "--time", "0")) != 0;
+    const bool exchange = std::stoi(arg_value(argc, argv, "--exchange", "0")) != 0;
     const int X = lp.X, Y = lp.Y;
     const int R23 = -151, C28 = 200, C38 = 250;  // :71-73
     if (X <= 152 || Y <= 251) {
@@ -223,7 +227,18 @@ int main(int argc, char* argv[]) {
       sv.set_state(f_adve.to_host(), g_adve.to_host());
       sv.sync();
       t0 = std::chrono::steady_clock::now();
-      sv.step(steps - 1);
+      if (exchange) {  // iteration `done` of the driver = fused step done - 1
+        const int every = sp.snapshot_steps > 0 ? sp.snapshot_steps : steps;
+        for (int done = 1; done < steps;) {
+          const int next = std::min(steps, (done / every + 1) * every);
+          sv.step(next - done);
+          done = next;
+          std::cout << "step=" << done << std::endl;
+          print_wall_exchange(sv.wall_exchange());
+        }
+      } else {
+        sv.step(steps - 1);
+      }
       sv.sync();
       timed_steps = steps - 1;
       const auto t1 = std::chrono::steady_clock::now();

@@ -29,6 +29,9 @@
 //          table per process; each slab or rank takes its view, lbm_ade_open_slab, and owns its carry; the _o entry points.
 //          Combines with --rectangle 1 and --buoyancy; --check's one block runs lbm_ade_collide_o / lbm_ade_stream_collide_o
 //          with the global tables and compares the carry as well)
+//          --exchange 1 (with --emulate and --rectangle 1: the wall exchange of the final state -- every slab fills its rows
+//          of ONE global row table, lbm_ade_wallx_rows with its view; printed before the JSON line: `wallx_slabs=` the
+//          fold of that table, `wallx_one_block=` the fold of the one block's, six values each in LBM_WALLX_* order)
 //
 // Printed: one JSON line; ms per step of the slowest slab, and the one-block step of a slab-sized lattice beside it.
 //
@@ -41,7 +44,7 @@
 namespace {
 
 struct Args : RingOpts {
-  int walls = 0, scalar_fixed = 0, rectangle = 0, channel = 0;
+  int walls = 0, scalar_fixed = 0, rectangle = 0, channel = 0, exchange = 0;
   double omega = 1.2, omega_g = 1.7;
   bool fast = true;
   bool buoyant = false;
@@ -188,9 +191,10 @@ void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
 // One block of Rg x C (ghost 0, dense), collide-only + `steps` fused steps: the yardstick of --check.  Returns f, g of
 // the owned rows as dense [9][Rg][C] on the host.
 // With an open table (--channel) the _o entry points run it and its carry comes back as well (the table's order).
+// wallx_out (--exchange): the wall exchange of the stream from that state, lbm_ade_wallx_rows + lbm_ade_wallx_fold.
 void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_params& sc, lbm_ade_iwalls* walls,
                std::vector<double>& f_out, std::vector<double>& g_out, const lbm_ade_open* open = nullptr,
-               std::vector<double>* carry_out = nullptr) {
+               std::vector<double>* carry_out = nullptr, std::vector<double>* wallx_out = nullptr) {
   if (walls) check(lbm_ade_iwalls_finalize(walls), "lbm_ade_iwalls_finalize");  // the global table: this is its one use on the device
   const lbm_geom g{Rg, a.cols, 0, 0, 0};
   const lbm_bc bc = global_bc(a);
@@ -214,6 +218,14 @@ void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_pa
     else
       check(lbm_ade_stream_collide_w(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr,
                                      a.buoyancy(), walls, 0, Rg, nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_w");
+  if (wallx_out) {
+    double* t = alloc_doubles((size_t)LBM_WALLX_NQ * (Rg + 1));  // the row table, then the folded values
+    check(lbm_ade_wallx_rows(t, Rg, 0, f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr, a.buoyancy(), walls, nullptr,
+                             0, Rg, nullptr), "lbm_ade_wallx_rows");
+    check(lbm_ade_wallx_fold(t + (size_t)LBM_WALLX_NQ * Rg, t, Rg, 0, Rg, nullptr), "lbm_ade_wallx_fold");
+    *wallx_out = doubles_to_host(t + (size_t)LBM_WALLX_NQ * Rg, LBM_WALLX_NQ);
+    lbm_free(t);
+  }
   if (prof) lbm_free(prof);
   if (carry_out) *carry_out = doubles_to_host(carry[cur], (size_t)lbm_ade_open_carry_len(open));
   for (double* c : carry) lbm_free(c);
@@ -381,11 +393,31 @@ int run_emulated(const Args& a, int N) {
     cur ^= 1;
   }
   check(lbm_stream_sync(es.edge), "sync");
+  // --exchange: every slab fills its rows of ONE global table from its own lattices (ghost rows as the last exchange left
+  // them) and its view of the walls; the fold of that table against the one block's
+  std::vector<double> wallx, wallx_block;
+  if (a.exchange) {
+    double* t = alloc_doubles((size_t)LBM_WALLX_NQ * (Rg + 1));  // the row table, then the folded values
+    for (int k = 0; k < N; ++k)
+      check(lbm_ade_wallx_rows(t, Rg, k * R, S[k].f[cur], S[k].h[cur], &g, &S[k].bc, &fl, &sc, prof ? &S[k].sbc : nullptr,
+                               a.buoyancy(), S[k].walls, nullptr, 0, R, nullptr), "lbm_ade_wallx_rows");
+    check(lbm_ade_wallx_fold(t + (size_t)LBM_WALLX_NQ * Rg, t, Rg, 0, Rg, nullptr), "lbm_ade_wallx_fold");
+    wallx = doubles_to_host(t + (size_t)LBM_WALLX_NQ * Rg, LBM_WALLX_NQ);
+    lbm_free(t);
+  }
   if (prof) lbm_free(prof);
   int bad = 0;
+  std::vector<double> want[2], want_carry;
+  if (a.check || a.exchange)
+    one_block(a, Rg, fl, sc, table, want[0], want[1], channel, &want_carry, a.exchange ? &wallx_block : nullptr);
+  if (a.exchange) {
+    for (const auto* v : {&wallx, &wallx_block}) {
+      std::printf(v == &wallx ? "wallx_slabs=" : "wallx_one_block=");
+      for (int q = 0; q < LBM_WALLX_NQ; ++q) std::printf("%s%.17g", q ? "," : "", (*v)[q]);
+      std::printf("\n");
+    }
+  }
   if (a.check) {
-    std::vector<double> want[2], want_carry;
-    one_block(a, Rg, fl, sc, table, want[0], want[1], channel, &want_carry);
     size_t first = 0;
     for (int k = 0; k < N; ++k) {
       for (int lat = 0; lat < 2; ++lat)
@@ -527,6 +559,12 @@ int main(int argc, char** argv) {
     return 1;
   }
   a.rectangle = int_arg(argc, argv, "--rectangle", 0);
+  a.exchange = int_arg(argc, argv, "--exchange", 0);
+  if (a.exchange && (!a.rectangle || arg_value(argc, argv, "--emulate", "").empty())) {
+    std::fprintf(stderr, "--exchange 1 needs --emulate N and --rectangle 1 (ranks fold their row tables over a transport of "
+                         "their own: lbm_ade_wallx_fold_host)\n");
+    return 1;
+  }
   if (a.rectangle && !a.walls) {
     std::fprintf(stderr, "--rectangle 1 needs --walls 1 (the rectangle stands on the bounce-back last row of the chain)\n");
     return 1;

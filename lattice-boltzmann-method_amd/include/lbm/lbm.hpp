@@ -343,6 +343,16 @@ class AdeSolver {
     check(lbm_ade_solver_run_until(h_, &cv, max_steps, &steps, &conv, &last));
     return {steps, conv != 0, last};
   }
+  // the LBM_WALLX_NQ values of what the interior walls take in the stream state() shows -- the force on them, the fluid
+  // mass, the scalar uptake -- over rows [row_begin, row_end); region4 = {r0, r1, c0, c1}: the nodes of that box only
+  std::vector<double> wall_exchange(const int* region4 = nullptr, int row_begin = 0, int row_end = -1,
+                                    std::vector<double>* table = nullptr) {
+    std::vector<double> out(LBM_WALLX_NQ);
+    if (table) table->resize((size_t)LBM_WALLX_NQ * R_);
+    check(lbm_ade_solver_wall_exchange(h_, region4, row_begin, row_end < 0 ? R_ : row_end, out.data(),
+                                       table ? table->data() : nullptr));
+    return out;
+  }
   lbm_ade_solver* handle() { return h_; }
 
  private:

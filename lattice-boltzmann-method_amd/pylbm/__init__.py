@@ -37,6 +37,11 @@ DIAG_NQ = 17
 DIAG_NAMES = ("SUM_RHO", "SUM_UR", "SUM_UC", "SUM_MR", "SUM_MC", "SUM_KE", "MAX_U2", "MIN_RHO", "MAX_RHO", "NONFINITE",
               "SUM_C", "SUM_CUR", "SUM_CUC", "MIN_C", "MAX_C", "SUM_C2", "SUM_DEV2")
 
+# value slots of the wall exchange (LBM_WALLX_*): lbm_ade_wallx_rows / lbm_ade_wallx_fold / AdeSolver.wall_exchange
+WALLX_NQ = 6
+WALLX_FORCE_R, WALLX_FORCE_C, WALLX_MASS, WALLX_SCALAR, WALLX_SCALAR_FIXED, WALLX_NODES = range(WALLX_NQ)
+WALLX_NAMES = ("FORCE_R", "FORCE_C", "MASS", "SCALAR", "SCALAR_FIXED", "NODES")
+
 _dp = ct.POINTER(ct.c_double)
 
 
@@ -344,6 +349,15 @@ class Lib:
                                            int(table.shape[1] if row_end is None else row_end))
         return out
 
+    def wallx_fold_host(self, table, row_begin=0, row_end=None):
+        """lbm_ade_wallx_fold_host: rows [row_begin, row_end) of a host row table [WALLX_NQ, rows] -> the WALLX_NQ values"""
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        assert table.ndim == 2 and table.shape[0] == WALLX_NQ, table.shape
+        out = np.empty(WALLX_NQ)
+        self.__getattr__("ade_wallx_fold_host")(_hptr(out), _hptr(table), table.shape[1], int(row_begin),
+                                                int(table.shape[1] if row_end is None else row_end))
+        return out
+
     def reset_tuning(self):
         for k in (b"variant", b"nt", b"grid_cap", b"block", b"rows", b"xcd_swizzle", b"tb_rows", b"tb_block", b"tb_order", b"sw_rows", b"sw_waves", b"solver_depth", b"cg_fused", b"cg_tile", b"cg_xcd", b"kbc_fast", b"kbc_depth", b"bgk_fast", b"cg_strip", b"cg_rows", b"cg_split", b"sw_split", b"solver_depth_walls", b"ibm_depth", b"ibm_gate", b"bgk_fast_delta", b"pressure_depth", b"halo_grid", b"cg_strip2", b"cg_rows2", b"sw_pair", b"sw_pf2", b"cg_strip_xcd", b"cg_merge", b"cg_frame_beside", b"ring_period", b"ibm_step_opt", b"ibm_step_split", b"ibm_step_chain", b"ibm_box", b"ibm_box_overlap", b"bg_priority", b"ibm_chain_kernel", b"ibm_chain_wgs", b"ibm_box_sole", b"sw_ldsring", b"ring_ipc_timeout_ms", b"cg_big", b"cg_big_xcd", b"ring_ipc_force_cached", b"ring_ipc_cached_ok", b"row_pad", b"cg_walk_rows", b"cg_walk_tile_xcd", b"sw_cols2"):
             self.set_tuning(k, -1)
@@ -553,6 +567,17 @@ class AdeSolver:
     def run_until(self, converge, max_steps):
         """step until the rule of `converge` (Converge) fires or max_steps are done: (steps_done, converged, last_value)"""
         return _run_until(self.lib.ade_solver_run_until, self.h, self.R, converge, max_steps)
+
+    def wall_exchange(self, region=None, row_begin=0, row_end=None, table=False):
+        """the WALLX_NQ values of what the interior walls take in the stream get_state shows (force on them, fluid mass,
+        scalar uptake), over rows [row_begin, row_end); region = (r0, r1, c0, c1): the nodes of that box only (clipped to
+        the lattice); table=True: (values, row table [WALLX_NQ, R])"""
+        out = np.empty(WALLX_NQ)
+        tab = np.empty((WALLX_NQ, self.R)) if table else None
+        box = (ct.c_int * 4)(*[int(v) for v in region]) if region is not None else None
+        self.lib.ade_solver_wall_exchange(self.h, box, int(row_begin), int(self.R if row_end is None else row_end),
+                                          _hptr(out), _hptr(tab) if table else None)
+        return (out, tab) if table else out
 
     def launches(self):
         return int(self.lib.raw.lbm_ade_solver_launches(self.h))

@@ -17,10 +17,15 @@ and against the single-step BGK launch, on one periodic box, in one process, alt
   --open adds two boxes with a bounce-back bottom row: open_plain, and open_channel with the sedimentation channel's open
   boundaries (lbm_ade_open_add_channel: inlet, extrapolated outlet, specular lid, zero-gradient copies, concentration
   inlet): one more launch per step, one lane per listed node (3 R + 3 C - 9 of them)
+  --wall-exchange is a mode of its own (nothing else is measured): on the iwalls_rectangle box after `warmup` steps, one
+  AdeSolver.wall_exchange call (row kernel + fold + 48-byte copy + synchronise; 20 calls per repeat) alternated with the
+  only other route to the same figures, both lattices of lbm_ade_solver_get_state copied into preallocated, touched host
+  arrays (the host arithmetic on top is not counted); host clock around each call, after one forced call of either
+  route, medians
 MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
 (18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
 usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls] [--buoyancy]
-       [--interior-walls] [--open]"""
+       [--interior-walls] [--open] [--wall-exchange]"""
 import argparse
 import ctypes as ct
 import json
@@ -28,6 +33,7 @@ import math
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "lattice-boltzmann-method_amd"))
@@ -39,6 +45,62 @@ from pylbm import _ptr  # noqa: E402
 
 HBM_TBS = 8.0
 W = (3e-3, 3e-3)
+
+
+def rectangle_table(lib, R, C):
+    """the sedimentation driver's rectangle (rectangle_sedimentation_test.cpp:73-75) scaled to the box, absorbing"""
+    r_top, c1, c2 = -(R // 3), C * 2 // 8, C * 5 // 16
+    n_side = R // 3 - 2  # rows r_top + 1 .. R - 2
+    fx, neg, pos = pylbm.ADE_SCALAR_FIXED, pylbm.ADE_FACE_COL_NEG, pylbm.ADE_FACE_COL_POS
+    table = pylbm.AdeInteriorWalls(lib, R, C)
+    table.add(r_top + 1, c1, 1, 0, n_side, neg, neg, fx, 0.0)          # first wall; g runs through the last row,
+    table.add(-1, c1, 1, 0, 1, 0, neg & ~0x40, fx, 0.0)                # slot 7 of its foot left to the bottom wall
+    table.add(r_top, c1, 0, 1, c2 - c1 + 1, pylbm.ADE_FACE_ROW_NEG, pylbm.ADE_FACE_ROW_NEG, fx, 0.0)  # ceiling
+    table.add(r_top + 1, c2, 1, 0, n_side, pos, pos, fx, 0.0)          # second wall
+    return table.finalize()
+
+
+def wall_exchange_bench(lib, a, fluid, scalar, f, g, st):
+    """--wall-exchange: the JSON fields of that mode; f, g: the dense pre-collision state on the device"""
+    import numpy as np
+    R = C = a.size
+    rbc = pylbm.Bc(row_lo=pylbm.EDGE_BOUNCE_BACK, row_hi=pylbm.EDGE_BOUNCE_BACK)
+    table = rectangle_table(lib, R, C)
+    w = pylbm.AdeSolver(lib, R, C, fluid, scalar, bc=rbc, stream=st.value, walls=table)
+    wf, wg, _, _, wgeo = w.lattices()
+    dg = pylbm.Geom(R, C, 0)
+    lib.lattice_copy_rows(_ptr(wf), ct.byref(wgeo), 0, _ptr(f), ct.byref(dg), 0, R, st)
+    lib.lattice_copy_rows(_ptr(wg), ct.byref(wgeo), 0, _ptr(g), ct.byref(dg), 0, R, st)
+    w.step(max(a.warmup, 2))
+    w.sync()
+    hf, hg = np.zeros((R, C, 9)), np.zeros((R, C, 9))  # preallocated and touched
+
+    def state():
+        lib.ade_solver_get_state(w.h, pylbm._hptr(hf), pylbm._hptr(hg), None, None, None)
+
+    def clock(fn):
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    values = w.wall_exchange()  # the forced warm-up of either route: first-use allocations
+    state()
+    t_x, t_s = [], []
+    for _ in range(a.repeats):
+        t_x += [clock(w.wall_exchange) for _ in range(20)]
+        t_s.append(clock(state))
+
+    def summary(v):
+        return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4), "calls": len(v)}
+
+    out = {"metric": "wall exchange of the iwalls_rectangle box against get_state of both lattices to the host",
+           "size": [R, C], "form": a.form, "steps_before": max(a.warmup, 2), "iwalls_table_nodes": table.count(),
+           "wall_exchange": summary(t_x), "get_state_f_g": summary(t_s),
+           "get_state_over_wall_exchange": round(statistics.median(t_s) / statistics.median(t_x), 1),
+           "values": dict(zip(pylbm.WALLX_NAMES, values.tolist()))}
+    w.close()
+    table.close()
+    return out
 
 
 def main():
@@ -53,6 +115,7 @@ def main():
     ap.add_argument("--buoyancy", action="store_true")
     ap.add_argument("--interior-walls", action="store_true")
     ap.add_argument("--open", action="store_true")
+    ap.add_argument("--wall-exchange", action="store_true")
     a = ap.parse_args()
     form = {"default": pylbm.FORM_DEFAULT, "ref": pylbm.FORM_REFERENCE_ORDER, "fast": pylbm.FORM_REASSOCIATED}[a.form]
     lib = pylbm.Lib()
@@ -89,8 +152,16 @@ def main():
     lib.equilibrium(_ptr(g), _ptr(u), _ptr(conc), R, C, None)
     torch.cuda.synchronize()
 
-    # fused: the solver context; its lattices are filled from the dense arrays (pre-collision state)
     fluid, scalar = pylbm.BgkParams(1.2, 0, form=form), pylbm.AdeParams(1.7, W, form=form)
+    if a.wall_exchange:
+        out = wall_exchange_bench(lib, a, fluid, scalar, f, g, st)
+        lib.event_destroy(e0)
+        lib.event_destroy(e1)
+        lib.stream_destroy(st)
+        print(json.dumps(out))
+        return
+
+    # fused: the solver context; its lattices are filled from the dense arrays (pre-collision state)
     sv = pylbm.AdeSolver(lib, R, C, fluid, scalar, stream=st.value)
     f_cur, g_cur, _, _, sg = sv.lattices()   # device addresses as Python ints: through _ptr, never bare (a bare int is a C int)
     dg = pylbm.Geom(R, C, 0)
@@ -143,15 +214,7 @@ def main():
     bodies, table = {}, None
     if a.interior_walls:
         rbc = pylbm.Bc(row_lo=pylbm.EDGE_BOUNCE_BACK, row_hi=pylbm.EDGE_BOUNCE_BACK)
-        r_top, c1, c2 = -(R // 3), C * 2 // 8, C * 5 // 16
-        n_side = R // 3 - 2  # rows r_top + 1 .. R - 2
-        fx, neg, pos = pylbm.ADE_SCALAR_FIXED, pylbm.ADE_FACE_COL_NEG, pylbm.ADE_FACE_COL_POS
-        table = pylbm.AdeInteriorWalls(lib, R, C)
-        table.add(r_top + 1, c1, 1, 0, n_side, neg, neg, fx, 0.0)          # first wall; g runs through the last row,
-        table.add(-1, c1, 1, 0, 1, 0, neg & ~0x40, fx, 0.0)                # slot 7 of its foot left to the bottom wall
-        table.add(r_top, c1, 0, 1, c2 - c1 + 1, pylbm.ADE_FACE_ROW_NEG, pylbm.ADE_FACE_ROW_NEG, fx, 0.0)  # ceiling
-        table.add(r_top + 1, c2, 1, 0, n_side, pos, pos, fx, 0.0)          # second wall
-        table.finalize()
+        table = rectangle_table(lib, R, C)
         for key, t in (("iwalls_plain", None), ("iwalls_rectangle", table)):
             w = pylbm.AdeSolver(lib, R, C, fluid, scalar, bc=rbc, stream=st.value, walls=t)
             wf, wg, _, _, wgeo = w.lattices()
