@@ -12,15 +12,16 @@ all:
 # golden vectors exercise), the C ABI's host side through ctypes (validation of every entry point's arguments, the
 # slab-height planner, link tables, tuning table), the TOML reader and the params:: mirror (params_dump), the tile planner
 # of the two-phase step over the sweep of tests/test_cg_plan.py (cg_plan_dump, run directly), the diagnostics' host fold and
-# argument checks and the wall exchange's (diag_host_check, wallx_host_check: programs of their own linked against the
-# sanitizer build of the library, run directly).
+# argument checks, the wall exchange's and the host checks of the fluid + scalar step with a KBC fluid (diag_host_check,
+# wallx_host_check, ade_kbc_host_check: programs of their own linked against the sanitizer build of the library, run directly).
 san:
 	$(MAKE) -C $(PKG)/csrc SAN=1 -j8
 	$(MAKE) -C oracle SAN=1
-	$(MAKE) -C $(PKG)/drivers bin_san/params_dump bin_san/cg_plan_dump bin_san/diag_host_check bin_san/wallx_host_check
+	$(MAKE) -C $(PKG)/drivers bin_san/params_dump bin_san/cg_plan_dump bin_san/diag_host_check bin_san/wallx_host_check bin_san/ade_kbc_host_check
 	mkdir -p profiles
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(PKG)/drivers/bin_san/diag_host_check
 	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(PKG)/drivers/bin_san/wallx_host_check
+	ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(PKG)/drivers/bin_san/ade_kbc_host_check
 	bash -o pipefail -c 'python tests/test_cg_plan.py | UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $(PKG)/drivers/bin_san/cg_plan_dump | wc -l'
 	LD_PRELOAD=$(SAN_RT) ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
 	LBM_HIP_LIB=$(CURDIR)/$(PKG)/lib_san/liblbm_hip.so LBM_ORACLE_LIB=$(CURDIR)/oracle/_build_san/liblbm_oracle.so \

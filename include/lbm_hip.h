@@ -668,6 +668,40 @@ int lbm_ade_stream_collide_part_w(double* fn, double* gn, const double* fo, cons
  * table is borrowed, not copied. */
 int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls);
 
+/* The fluid of the step by model: the compressible BGK fluid of everything above, or the entropic KBC collision
+ * (lbm_kbc_params; src/ulbm.cpp kbc::collide on the populations' own moments, as lbm_kbc_stream_collide runs it) for the
+ * regimes BGK does not survive -- a scalar in an under-resolved shear layer, a viscosity with omega next to 2.  The
+ * scalar half is unchanged: its equilibrium takes the u the fluid's collision forms.
+ * model = LBM_MODEL_BGK: the `_m` calls ARE lbm_ade_collide_b / lbm_ade_stream_collide_w / lbm_ade_solver_create with
+ * `bgk` (buoyancy NULL) -- the same checks under those names, the same launches, the same bits.
+ * model = LBM_MODEL_KBC: kbc.s2 in (0, 2]; kbc.form LBM_FORM_DEFAULT or equal to scalar->form, which sets both halves
+ * (LBM_FORM_DEFAULT resolves through "kbc_fast"): REFERENCE_ORDER = KbcModel with the reference-order scalar, the fluid
+ * half bitwise equal to lbm_kbc_stream_collide in that form; REASSOCIATED = KbcFastModel with the reassociated scalar.
+ * Supported, single block, ghost = 0, C even: the edge modes of lbm_ade_stream_collide, lbm_ade_scalar_bc (NO_FLUX and
+ * FIXED, constant or profile), the interior-wall table, the optional moments, the collide-only first iteration, row
+ * ranges, graph capture of the context's step.  Launches as for BGK: one per step on a periodic box (the interior pair
+ * kernel written for this fluid, ade_kbc.hpp), one more with wall edges, one more per non-empty table.
+ * Refused on the host (LBM_ERR_INVALID, the message names the feature and the model): bc->pressure_rows; on a context
+ * lbm_ade_solver_set_buoyancy with beta != (0, 0) (the forced collision is the BGK driver's: the reference has no forced
+ * KBC), lbm_ade_solver_set_open with a non-empty table, lbm_ade_solver_wall_exchange.  There is no slab or ring entry
+ * for a KBC fluid: lbm_ade_stream_collide_part* and lbm_ring_ade_* take lbm_bgk_params. */
+typedef struct lbm_ade_fluid {
+  int model;          /* LBM_MODEL_BGK or LBM_MODEL_KBC */
+  lbm_bgk_params bgk; /* read when model == LBM_MODEL_BGK */
+  lbm_kbc_params kbc; /* read when model == LBM_MODEL_KBC */
+} lbm_ade_fluid;
+int lbm_ade_collide_m(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                      const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, double* rho,
+                      double* u, double* conc, lbm_stream_t s);
+int lbm_ade_stream_collide_m(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                             const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                             const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int row_begin, int row_end,
+                             double* rho, double* u, double* conc, lbm_stream_t s);
+/* the context with either fluid; with a KBC fluid it supports set_state, step, get_state, sync, lattices, launches,
+ * set_scalar_bc, set_walls, lbm_ade_solver_diag and lbm_ade_solver_run_until */
+int lbm_ade_solver_create_m(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc /* NULL = periodic */,
+                            const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, lbm_stream_t s);
+
 /* Open boundaries of the fused step on a single block: the inlet, the outlet, the specular lid and the zero-gradient
  * copies of test/rectangle_sedimentation_test.cpp (:134-177, :203-218), as a host table built like lbm_ade_iwalls --
  * create / add / finalize / destroy, segments (r0 + i dr, c0 + i dc), i < n, negative r0 / c0 counting from the end.

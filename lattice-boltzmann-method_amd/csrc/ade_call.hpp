@@ -1,0 +1,49 @@
+// The resolved call of the fused fluid + scalar step and what its launch sites share: for the translation units that
+// launch ade.hpp's kernels (capi_ade.hip: the BGK fluid; capi_ade_kbc.hip: the KBC fluid).  Every other unit keeps a call
+// in an AdeCallBuf (internal.hpp) and never sees its members.
+#pragma once
+#include <type_traits>
+
+#include "ade.hpp"
+#include "launch.hpp"
+
+namespace lbm {
+
+// One call of the fused step after its host checks: the device copies that every launch of the call takes.  fluid and
+// scalar are borrowed for the call (with_ade_models picks the models per launch).
+struct AdeCall {
+  Geom g;
+  Bc bc;
+  AdeWalls sw;
+  AdeBuoyancy by;
+  bool buoyant;
+  const AdeIwallNode* wall_nodes;
+  int n_wall_nodes;
+  const int* wall_first;  // host: the table's row index (R + 1 entries), NULL without nodes
+  const lbm_bgk_params* fluid;
+  const lbm_ade_params* scalar;
+  const AdeOpenNode* open_nodes;  // the open-boundary table (lbm_ade_open), NULL without nodes
+  const AdeOpenSeg* open_segs;
+  int n_open_nodes;
+  const int* open_first;   // host: the table's row index (R + 1 entries), NULL without nodes
+  const double* carry_in;  // the carry of the call (ade_carry_set)
+  double* carry_out;
+};
+static_assert(sizeof(AdeCall) <= sizeof(AdeCallBuf) && alignof(AdeCall) <= alignof(AdeCallBuf) &&
+              std::is_trivially_copyable<AdeCall>::value, "AdeCallBuf (internal.hpp) holds an AdeCall");
+
+// The rows of a launch -- [band0, band0 + n0), then [band1, band1 + nrows - n0) where n0 < nrows -- as two index ranges of
+// a table sorted by (r, c), from its row index first[]: nodes [first0, first0 + w0), then from first1 on, w in all
+struct AdeRanges {
+  int first0, w0, first1, w;
+};
+inline AdeRanges ade_row_ranges(const int* first, int band0, int n0, int band1, int nrows) {
+  const int first0 = first[band0], w0 = first[band0 + n0] - first0, first1 = first[band1];
+  return AdeRanges{first0, w0, first1, w0 + (n0 < nrows ? first[band1 + nrows - n0] - first1 : 0)};
+}
+
+// the lattice and field arguments of a launch (capi_ade.hip)
+int ade_lattice_args(const char* fn, const double* fn_, const double* gn, const double* fo, const double* go,
+                     const double* rho, const double* u, const double* conc, bool distinct);
+
+}  // namespace lbm

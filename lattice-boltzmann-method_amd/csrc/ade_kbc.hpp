@@ -1,0 +1,76 @@
+// Fluid + transported scalar with the entropic KBC collision as the fluid: the interior pair kernel of that step.  The
+// edge pass, the interior-wall pass and the collide-only launch are ade.hpp's kernels with a KBC model as FM (one node
+// per lane, latency-bound); only the kernel that holds two nodes of both lattices per lane is written for this fluid.
+#pragma once
+#include "ade.hpp"
+#include "kbc.hpp"
+
+namespace lbm {
+
+// nothing moves across this point in the instruction schedule: the phases of k_ade_kbc_stream_collide stay phases
+__device__ __forceinline__ void ade_kbc_phase() { __builtin_amdgcn_sched_barrier(0); }
+
+// k_ade_stream_collide for a KBC fluid: the same pair of column-adjacent nodes per lane, the same 16-byte gather
+// (pull_pair), stores, grid stride and optional moments -- in another ORDER.  The KBC collision keeps ~100 doubles of
+// its own live (nine central moments, two 9-vectors and the equilibrium of each node), so with all 36 populations of
+// the pair in registers beside it the kernel comes out at 222-252 VGPRs: two waves per SIMD.  Here the lane holds one
+// lattice at a time:
+//   f pair in -> collide node a, node b -> f pair out; (rho, ux, uy) of both nodes stay (6 doubles)
+//   g pair in -> the scalar's collision of both nodes with those u -> g pair out -> moments out
+// G_EARLY: the 18 loads of g are issued BEFORE the fluid's collisions (their latency hides behind ~400 f64 operations,
+// at 36 more registers during the collisions, which then run one after the other behind a fence: 186 VGPRs, interleaved
+// 222); without it after the f stores (152 VGPRs reassociated, 172 reference order).  The phases are fenced
+// (ade_kbc_phase): the scheduler would otherwise hoist the g loads -- independent, __restrict__ -- to the top of the
+// iteration, which is the naive kernel again.  Measured at 8192^2 (profiles/ade_kbc.txt): reassociated early 3.46 ms, late
+// 3.51 ms per step in every repeat -- two waves per SIMD with the loads in flight beat three that wait for them -- so the
+// reassociated pair runs early; the reference-order pair (234 VGPRs early) runs late.  128 VGPRs were not to be had
+// without scratch: amdgpu_waves_per_eu(4) spills 124-260 B, (3) on the reference order 20 B.  The attribute asks for two
+// waves: with it the reference-order pair comes out at 172 VGPRs, without it at 218.
+// The arithmetic is fm.collide's and sm.collide's, expression for expression: only the order of independent loads and
+// stores differs from k_ade_stream_collide<FM, SM>, so the populations stored are the same bits.
+// Requirements as k_ade_stream_collide: C % 2 == 0, even pitch and plane stride, 16-byte aligned lattices; no wall
+// fix-ups (k_ade_edge recomputes the wall nodes afterwards).
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool G_EARLY>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_ade_kbc_stream_collide(
+    double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
+    Geom g, FM fm, SM sm, int row_begin, int row_end, int tiles_per_row, double* __restrict__ rho_out,
+    double* __restrict__ u_out, double* __restrict__ c_out) {
+  const long items = (long)(row_end - row_begin) * tiles_per_row;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const int r = row_begin + (int)(it / tiles_per_row);
+    const int c = ((int)(it % tiles_per_row) * 256 + threadIdx.x) * 2;
+    if (c >= g.C) continue;
+    const long rm = g.at(wrap_row(g, r - 1), 0);  // source row of cx = +1 populations
+    const long r0 = g.at(r, 0);
+    const long rp = g.at(wrap_row(g, r + 1), 0);  // source row of cx = -1 populations
+    double xa[Q], xb[Q], ha[Q], hb[Q];            // the lattice in flight of node (r, c) and node (r, c + 1)
+    double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
+    pull_pair<NT_LOAD>(xa, xb, fo, g, rm, r0, rp, c);
+    if (G_EARLY) pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+    ade_kbc_phase();
+    fm.collide(xa, rho_a, ux_a, uy_a);
+    if (G_EARLY) ade_kbc_phase();  // with g in registers too: one collision at a time (interleaved: 222 VGPRs, fenced: 186)
+    fm.collide(xb, rho_b, ux_b, uy_b);
+    ade_kbc_phase();
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, xa[q], xb[q]);
+    if (!G_EARLY) {
+      ade_kbc_phase();
+      pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+    }
+    sm.collide(ha, ux_a, uy_a, c_a);
+    sm.collide(hb, ux_b, uy_b, c_b);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    if (WITH_MOMENTS) {
+      const long o = (long)r * g.C + c;  // moment fields are dense
+      const long n = (long)g.R * g.C;
+      store2<false>(rho_out + o, rho_a, rho_b);
+      store2<false>(u_out + o, ux_a, ux_b);
+      store2<false>(u_out + n + o, uy_a, uy_b);
+      store2<false>(c_out + o, c_a, c_b);
+    }
+  }
+}
+
+}  // namespace lbm

@@ -12,8 +12,8 @@
 #include <utility>
 #include <vector>
 
-#include "ade.hpp"
-#include "launch.hpp"
+#include "ade_call.hpp"
+#include "ade_plain.hpp"
 
 // Interior walls of the fused step: a host table of wall nodes, merged per node and kept sorted by (r, c) while it is
 // built; lbm_ade_iwalls_finalize uploads it once (the only device call) and it is immutable from then on.  first: the
@@ -181,7 +181,7 @@ static int with_ade_models(const lbm_bgk_params* fluid, const lbm_ade_params* sc
 
 // The lattice and field arguments of a launch: four lattices given (distinct: also pairwise different and 16-byte
 // aligned -- the collide-only launch reads and writes node by node and asks for neither); rho, u, conc all or none.
-static int ade_lattice_args(const char* fn, const double* fn_, const double* gn, const double* fo, const double* go,
+int ade_lattice_args(const char* fn, const double* fn_, const double* gn, const double* fo, const double* go,
                             const double* rho, const double* u, const double* conc, bool distinct) {
   LBM_REQUIRE(fn_ && gn && fo && go, "%s: NULL lattice", fn);
   if (distinct) {
@@ -388,29 +388,6 @@ static int ade_open_check(const char* fn, const lbm_ade_open* t, const lbm_geom*
   return LBM_OK;
 }
 
-// One call of the fused step after its host checks: the device copies that every launch of the call takes.  fluid and
-// scalar are borrowed for the call (with_ade_models picks the models per launch).
-struct AdeCall {
-  Geom g;
-  Bc bc;
-  AdeWalls sw;
-  AdeBuoyancy by;
-  bool buoyant;
-  const AdeIwallNode* wall_nodes;
-  int n_wall_nodes;
-  const int* wall_first;  // host: the table's row index (R + 1 entries), NULL without nodes
-  const lbm_bgk_params* fluid;
-  const lbm_ade_params* scalar;
-  const AdeOpenNode* open_nodes;  // the open-boundary table (lbm_ade_open), NULL without nodes
-  const AdeOpenSeg* open_segs;
-  int n_open_nodes;
-  const int* open_first;   // host: the table's row index (R + 1 entries), NULL without nodes
-  const double* carry_in;  // the carry of the call (ade_carry_set)
-  double* carry_out;
-};
-static_assert(sizeof(AdeCall) <= sizeof(AdeCallBuf) && alignof(AdeCall) <= alignof(AdeCallBuf) &&
-              std::is_trivially_copyable<AdeCall>::value, "AdeCallBuf (internal.hpp) holds an AdeCall");
-
 // The host checks of a call, once, under the caller's name: the scalar's walls first (a FIXED edge names the edge mode it
 // cannot sit on), geometry and parameters, buoyancy, interior walls.  An entry checks its lattices and range or part after.
 int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
@@ -446,16 +423,6 @@ static int ade_collide_launch(const AdeCall& k, const FM& fm, const SM& sm, doub
   with_flags([&](auto M) { LBM_KLAUNCH((k_ade_collide<FM, SM, M(), B>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, k.g, fm, sm, rho, u, conc, k.by); }, rho != nullptr);
   LBM_CHECK_LAUNCH();
   return LBM_OK;
-}
-
-// The rows of a launch -- [band0, band0 + n0), then [band1, band1 + nrows - n0) where n0 < nrows -- as two index ranges of
-// a table sorted by (r, c), from its row index first[]: nodes [first0, first0 + w0), then from first1 on, w in all
-struct AdeRanges {
-  int first0, w0, first1, w;
-};
-static AdeRanges ade_row_ranges(const int* first, int band0, int n0, int band1, int nrows) {
-  const int first0 = first[band0], w0 = first[band0 + n0] - first0, first1 = first[band1];
-  return AdeRanges{first0, w0, first1, w0 + (n0 < nrows ? first[band1 + nrows - n0] - first1 : 0)};
 }
 
 // The two table passes of a launch over the rows of ade_row_ranges, behind the dispatch whose nodes they overwrite and on
@@ -717,7 +684,9 @@ static int ade_wallx_fold_launch(double* out_dev, const double* table, int table
 struct lbm_ade_solver {
   lbm_geom g;  // padded geometry of either lattice
   lbm_bc bc;
+  int model;             // LBM_MODEL_BGK: fluid; LBM_MODEL_KBC: kbc (lbm_ade_solver_create_m)
   lbm_bgk_params fluid;
+  lbm_kbc_params kbc;
   lbm_ade_params scalar;
   lbm_ade_scalar_bc sbc;  // all NO_FLUX unless set
   bool fixed;             // some edge of sbc is FIXED
@@ -820,18 +789,22 @@ int lbm_ade_stream_collide_part_w(double* fn, double* gn, const double* fo, cons
                   edge_rows, rho, u, conc, as_stream(s));
 }
 
-int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
-                          const lbm_ade_params* scalar, lbm_stream_t s) {
-  LBM_REQUIRE(out, "lbm_ade_solver_create: NULL argument");
-  int rc = ade_validate("lbm_ade_solver_create", g, bc, fluid, scalar);
+// the context of either fluid (exactly one of fluid, kbc given), under the caller's name
+static int ade_solver_create(const char* fn, lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc,
+                             const lbm_bgk_params* fluid, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
+                             lbm_stream_t s) {
+  LBM_REQUIRE(out, "%s: NULL argument", fn);
+  int rc = kbc ? ade_kbc_validate(fn, g, bc, kbc, scalar) : ade_validate(fn, g, bc, fluid, scalar);
   if (rc) return rc;
   LBM_REQUIRE(g->row_pitch == 0 && g->plane_stride == 0,
-              "lbm_ade_solver_create: the context pads its own lattices (row_pitch and plane_stride must be 0)");
+              "%s: the context pads its own lattices (row_pitch and plane_stride must be 0)", fn);
   lbm_ade_solver* sv = new (std::nothrow) lbm_ade_solver();
-  LBM_REQUIRE(sv, "lbm_ade_solver_create: out of host memory");
+  LBM_REQUIRE(sv, "%s: out of host memory", fn);
   sv->g = *g;
   sv->bc = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
-  sv->fluid = *fluid;
+  sv->model = kbc ? LBM_MODEL_KBC : LBM_MODEL_BGK;
+  sv->fluid = fluid ? *fluid : lbm_bgk_params{};
+  sv->kbc = kbc ? *kbc : lbm_kbc_params{};
   sv->scalar = *scalar;
   sv->sbc = lbm_ade_scalar_bc{};
   sv->fixed = false;
@@ -862,12 +835,27 @@ int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc*
   if (e == hipSuccess) e = hipMemsetAsync(sv->lat[0], 0, lat_doubles * sizeof(double), sv->st);
   if (e == hipSuccess) e = hipMemsetAsync(sv->lat[1], 0, lat_doubles * sizeof(double), sv->st);
   if (e != hipSuccess) {
-    set_error("lbm_ade_solver_create: %s", hipGetErrorString(e));
+    set_error("%s: %s", fn, hipGetErrorString(e));
     lbm_ade_solver_destroy(sv);
     return LBM_ERR_HIP;
   }
   *out = sv;
   return LBM_OK;
+}
+
+int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
+                          const lbm_ade_params* scalar, lbm_stream_t s) {
+  return ade_solver_create("lbm_ade_solver_create", out, g, bc, fluid, nullptr, scalar, s);
+}
+
+int lbm_ade_solver_create_m(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_ade_fluid* fluid,
+                            const lbm_ade_params* scalar, lbm_stream_t s) {
+  const char* fn = "lbm_ade_solver_create_m";
+  LBM_REQUIRE(fluid, "%s: NULL fluid (lbm_ade_fluid)", fn);
+  LBM_REQUIRE(fluid->model == LBM_MODEL_BGK || fluid->model == LBM_MODEL_KBC,
+              "%s: fluid model=%d (LBM_MODEL_BGK or LBM_MODEL_KBC)", fn, fluid->model);
+  if (fluid->model == LBM_MODEL_BGK) return lbm_ade_solver_create(out, g, bc, &fluid->bgk, scalar, s);
+  return ade_solver_create(fn, out, g, bc, nullptr, &fluid->kbc, scalar, s);
 }
 
 int lbm_ade_solver_destroy(lbm_ade_solver* sv) {
@@ -908,7 +896,13 @@ int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
   for (int i = 0; i < n; ++i) {
     const int k = sv->cur, o = k ^ 1;
     int rc;
-    if (!sv->post) {
+    if (sv->model == LBM_MODEL_KBC) {  // (no buoyancy and no open table on such a context: their setters refuse)
+      rc = !sv->post ? ade_kbc_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->kbc,
+                                       &sv->scalar, nullptr, sv->walls, nullptr, nullptr, nullptr, sv->st, &sv->launches)
+                     : ade_kbc_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
+                                              &sv->kbc, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, sv->walls, 0, sv->g.R,
+                                              nullptr, nullptr, nullptr, sv->st, &sv->launches);
+    } else if (!sv->post) {
       rc = ade_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid,
                        &sv->scalar, nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st, sv->open, sv->carry[o],
                        &sv->launches);
@@ -1078,6 +1072,7 @@ int lbm_ade_solver_wall_exchange(lbm_ade_solver* sv, const int* region4, int row
                                  double* table_host) {
   const char* fn = "lbm_ade_solver_wall_exchange";
   LBM_REQUIRE(sv && out_host, "%s: NULL argument (solver, out_host)", fn);
+  LBM_REQUIRE(sv->model != LBM_MODEL_KBC, "%s: the wall exchange is not supported with a KBC fluid", fn);
   const int R = sv->g.R;
   int rc = diag_range_check(fn, R, row_begin, row_end);
   if (rc) return rc;
@@ -1157,6 +1152,9 @@ int lbm_ade_solver_set_buoyancy(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy
   LBM_REQUIRE(sv, "lbm_ade_solver_set_buoyancy: NULL solver");
   int rc = ade_buoyancy_check("lbm_ade_solver_set_buoyancy", buoy);
   if (rc) return rc;
+  LBM_REQUIRE(sv->model != LBM_MODEL_KBC || !buoy || (buoy->beta_r == 0.0 && buoy->beta_c == 0.0),
+              "lbm_ade_solver_set_buoyancy: buoyancy with beta=(%g, %g) is not supported with a KBC fluid (the forced "
+              "collision is the BGK fluid's)", buoy->beta_r, buoy->beta_c);
   sv->buoy = buoy ? *buoy : lbm_ade_buoyancy{};
   sv->buoyant = buoy != nullptr;
   return LBM_OK;
@@ -1572,6 +1570,9 @@ int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open) {
   const char* fn = "lbm_ade_solver_set_open";
   LBM_REQUIRE(sv, "%s: NULL solver", fn);
   if (open == sv->open) return LBM_OK;
+  LBM_REQUIRE(sv->model != LBM_MODEL_KBC || !open || open->nodes.empty(),
+              "%s: open boundaries (a table of %d nodes) are not supported with a KBC fluid", fn,
+              open ? (int)open->nodes.size() : 0);
   if (open) {
     LBM_REQUIRE(!open->view, "%s: open boundaries: the table is a slab view (lbm_ade_open_slab): the context runs a single "
                 "block and takes the global table", fn);

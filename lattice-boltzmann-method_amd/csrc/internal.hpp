@@ -50,7 +50,8 @@ int box_copy(double* dst, const lbm_geom& dg, int dst_row, int dst_col, const do
 int make_background_stream(hipStream_t* out);
 // capi_ade.hip: one call of the fused fluid + scalar step after its host checks -- the device copies of geometry, edges,
 // scalar walls, buoyancy and interior-wall table that every launch of the call takes.  Its members are ade.hpp's, and
-// ade.hpp defines kernels, so AdeCall is complete in capi_ade.hip alone: another unit keeps one in an AdeCallBuf.
+// ade.hpp defines kernels, so AdeCall is complete (ade_call.hpp) in the units that launch them alone -- capi_ade.hip and
+// capi_ade_kbc.hip: another unit keeps one in an AdeCallBuf.
 struct AdeCall;
 struct AdeWalls;
 struct AdeBuoyancy;
@@ -81,6 +82,19 @@ int ade_collide_from(const char* fn, const AdeCall& call, double* fp, double* gp
 // pre-collision state f, written to the call's carry_out (one small launch; none without a listed node)
 int ade_carry_set(const char* fn, AdeCall* call, bool reads, const double* carry_in, double* carry_out);
 int ade_open_prime_from(const AdeCall& call, const double* f, hipStream_t st);
+// capi_ade_kbc.hip: the fused step with a KBC fluid (lbm_ade_fluid, model = LBM_MODEL_KBC), under the caller's name fn --
+// the host checks alone (what lbm_ade_solver_create_m asks before it allocates), the collide-only iteration and the step
+// on rows [row_begin, row_end); *launches (if given) += the kernels enqueued
+int ade_kbc_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
+                     const lbm_ade_params* scalar);
+int ade_kbc_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
+                    const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
+                    const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, double* rho, double* u, double* conc,
+                    hipStream_t st, long long* launches);
+int ade_kbc_stream_collide(const char* fn, double* f_new, double* g_new, const double* f_old, const double* g_old,
+                           const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
+                           const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int row_begin, int row_end,
+                           double* rho, double* u, double* conc, hipStream_t st, long long* launches);
 // capi_diag.hip: what a solver context keeps for its diagnostics -- the row table [LBM_DIAG_NQ][R], the folded values on the
 // device and a pinned host buffer for them, all allocated by the first diag_reduce and kept.
 struct DiagBuf {

@@ -1,0 +1,111 @@
+// The CPU-reachable half of the fluid + scalar step with a KBC fluid as a stand-alone program: every host-side check of
+// lbm_ade_collide_m, lbm_ade_stream_collide_m and lbm_ade_solver_create_m -- the fluid by model, the KBC parameters, what
+// the step refuses with this fluid, the checks it shares with the BGK fluid, and model = BGK answering with the message of
+// the call it forwards to.  Needs no device: every call is refused before a device call (the interior-wall table it
+// builds is empty, whose finalize makes none).  `make san` at the root builds it against the sanitizer build of the
+// library (ASan + UBSan) and runs it; the ordinary build runs it from tests/test_ade_kbc_abi.py.  Exit status 0 = all
+// checks passed.
+#include <cstdio>
+#include <string>
+
+#include "../../include/lbm_hip.h"
+
+static int failures = 0, checks = 0;
+
+// refused with LBM_ERR_INVALID and a message that names `word`
+static void refused(int rc, const char* word, const char* what) {
+  const std::string msg = lbm_last_error_string();
+  ++checks;
+  if (rc == LBM_ERR_INVALID && msg.find(word) != std::string::npos) return;
+  ++failures;
+  std::printf("FAIL: %s -> %d: %s\n", what, rc, msg.c_str());
+}
+
+int main() {
+  double buf[8] = {0.0}, other[8] = {0.0};
+  const lbm_geom g{8, 8, 0, 0, 0};
+  const lbm_ade_params sc{1.7, 3e-3, 3e-3, LBM_FORM_DEFAULT};
+  lbm_ade_fluid kbc{};
+  kbc.model = LBM_MODEL_KBC;
+  kbc.kbc = lbm_kbc_params{1.9, LBM_FORM_DEFAULT};
+  // the three entry points on one fluid / geometry / edges / scalar: each refuses before it looks at a lattice
+  auto all = [&](const lbm_ade_fluid* fl, const lbm_geom* lg, const lbm_bc* bc, const lbm_ade_params* s, const char* word,
+                 const char* what) {
+    refused(lbm_ade_stream_collide_m(nullptr, nullptr, nullptr, nullptr, lg, bc, fl, s, nullptr, nullptr, 0, 8, nullptr, nullptr,
+                                     nullptr, nullptr), word, what);
+    refused(lbm_ade_collide_m(nullptr, nullptr, nullptr, nullptr, lg, bc, fl, s, nullptr, nullptr, nullptr, nullptr, nullptr), word, what);
+    lbm_ade_solver* sv = nullptr;
+    refused(lbm_ade_solver_create_m(&sv, lg, bc, fl, s, nullptr), word, what);
+    if (sv) {
+      ++failures;
+      std::printf("FAIL: %s left a context\n", what);
+    }
+  };
+  all(nullptr, &g, nullptr, &sc, "NULL fluid", "NULL fluid");
+  {
+    lbm_ade_fluid f = kbc;
+    f.model = 7;
+    all(&f, &g, nullptr, &sc, "fluid model=7", "unknown model");
+    f = kbc;
+    f.kbc.s2 = 0.0;
+    all(&f, &g, nullptr, &sc, "s2=0 outside (0, 2]", "s2 = 0");
+    f.kbc.s2 = 2.5;
+    all(&f, &g, nullptr, &sc, "s2=2.5 outside (0, 2]", "s2 = 2.5");
+    f = kbc;
+    f.kbc.form = 9;
+    all(&f, &g, nullptr, &sc, "KBC fluid: form=9", "unknown KBC form");
+    f.kbc.form = LBM_FORM_REFERENCE_ORDER;
+    const lbm_ade_params fast{1.7, 0.0, 0.0, LBM_FORM_REASSOCIATED};
+    all(&f, &g, nullptr, &fast, "KBC fluid form=1 differs from the scalar form=2", "forms differ");
+  }
+  {
+    const lbm_bc pressure{0, 0, 0, 0, 1, 1.0, 1.0, 0.0, 0.0};
+    all(&kbc, &g, &pressure, &sc, "pressure rows", "pressure rows with a KBC fluid");
+    all(&kbc, &g, &pressure, &sc, "KBC fluid", "pressure rows name the model");
+    const lbm_geom odd{8, 7, 0, 0, 0}, ghost{8, 8, 2, 0, 0};
+    all(&kbc, &odd, nullptr, &sc, "C=7 must be even", "odd C");
+    all(&kbc, &ghost, nullptr, &sc, "ghost=2", "ghost rows");
+    all(&kbc, nullptr, nullptr, &sc, "NULL geometry", "NULL geometry");
+    all(&kbc, &g, nullptr, nullptr, "NULL scalar params", "NULL scalar");
+    const lbm_bc halo{LBM_EDGE_HALO, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
+    all(&kbc, &g, &halo, &sc, "row edge mode HALO", "HALO rows on a single block");
+  }
+  // past the fluid: the lattices, the moments, the range, the scalar's walls, the interior walls
+  refused(lbm_ade_stream_collide_m(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &kbc, &sc, nullptr, nullptr, 0, 8, nullptr, nullptr,
+                                   nullptr, nullptr), "NULL lattice", "NULL lattices with a good KBC fluid");
+  refused(lbm_ade_stream_collide_m(buf, buf, other, other, &g, nullptr, &kbc, &sc, nullptr, nullptr, 0, 8, nullptr, nullptr, nullptr,
+                                   nullptr), "aliased lattices", "aliased lattices");
+  refused(lbm_ade_collide_m(buf, buf, buf, buf, &g, nullptr, &kbc, &sc, nullptr, buf, nullptr, nullptr, nullptr), "rho, u and conc",
+          "rho without u and conc");
+  {
+    lbm_ade_scalar_bc sbc{};
+    sbc.mode[0] = LBM_ADE_SCALAR_FIXED;  // FIXED on a periodic row
+    refused(lbm_ade_stream_collide_m(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &kbc, &sc, &sbc, nullptr, 0, 8, nullptr, nullptr,
+                                     nullptr, nullptr), "FIXED on a PERIODIC", "FIXED scalar edge on a periodic row");
+    lbm_ade_iwalls* table = nullptr;  // empty: finalize makes no device call
+    if (lbm_ade_iwalls_create(&table, 6, 8) != LBM_OK || lbm_ade_iwalls_finalize(table) != LBM_OK) {
+      ++failures;
+      std::printf("FAIL: building an empty table\n");
+    }
+    refused(lbm_ade_stream_collide_m(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &kbc, &sc, nullptr, table, 0, 8, nullptr, nullptr,
+                                     nullptr, nullptr), "6 x 8", "table built for another R x C");
+    lbm_ade_iwalls_destroy(table);
+  }
+  {  // model = BGK: the message of the call it forwards to; the kbc member is not read
+    lbm_ade_fluid bgk{};
+    bgk.model = LBM_MODEL_BGK;
+    bgk.bgk = lbm_bgk_params{2.0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, LBM_FORM_DEFAULT};
+    bgk.kbc = lbm_kbc_params{-3.0, 9};
+    refused(lbm_ade_stream_collide_m(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &bgk, &sc, nullptr, nullptr, 0, 8, nullptr, nullptr,
+                                     nullptr, nullptr), "lbm_ade_stream_collide_w: omega=2", "BGK through stream_collide_m");
+    refused(lbm_ade_collide_m(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &bgk, &sc, nullptr, nullptr, nullptr, nullptr, nullptr),
+            "lbm_ade_collide_b: omega=2", "BGK through collide_m");
+    lbm_ade_solver* sv = nullptr;
+    refused(lbm_ade_solver_create_m(&sv, &g, nullptr, &bgk, &sc, nullptr), "lbm_ade_solver_create: omega=2", "BGK through create_m");
+    bgk.bgk.omega = 1.2;
+    refused(lbm_ade_stream_collide_m(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &bgk, &sc, nullptr, nullptr, 0, 8, nullptr, nullptr,
+                                     nullptr, nullptr), "lbm_ade_stream_collide_w: NULL lattice", "good BGK through stream_collide_m");
+  }
+  std::printf("ade_kbc_host_check: %d refusals checked, %d failures\n", checks, failures);
+  return failures ? 1 : 0;
+}

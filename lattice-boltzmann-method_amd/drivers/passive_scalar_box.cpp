@@ -5,7 +5,7 @@
 // (as the driver initialises g_adve, :95).
 //   usage: passive_scalar_box R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]
 //          [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]
-//          [--rectangle r_top,c_first,c_second[,conc]] [--exchange 0|1]
+//          [--rectangle r_top,c_first,c_second[,conc]] [--exchange 0|1] [--fluid bgk|kbc] [--s2 X]
 // --dump writes prefix-{f0,g0,f,g,rho,u,C}.f64 (raw f64, reference layout [R][C][Q]); --walls 1: bounce-back columns,
 // 2: bounce-back rows and columns.  --fixed: the named edges (row_lo, row_hi, col_lo, col_hi; walls of the fluid) hold
 // the scalar at the constant C_w (lbm_ade_scalar_bc FIXED), the others stay no-flux.  --buoyancy: the scalar pushes on the
@@ -15,6 +15,10 @@
 // end) over columns c_first..c_second, the two side walls below it down to the last row; the scalar is absorbed
 // (FIXED, C_w = 0) unless conc gives the C_w the body holds.  --exchange 1: what the body takes from the lattices in the
 // stream of the final state (lbm::AdeSolver::wall_exchange) as force_r, force_c, mass, uptake, uptake_fixed, wall_nodes.
+// --fluid kbc: the entropic KBC collision as the fluid (lbm::AdeSolver::kbc) with the rate --s2 (default: omega); omega is
+// then not used.  KBC's stabiliser is 0/0 on a lattice exactly at equilibrium, in the reference too, so this fluid starts
+// as the reference's KBC driver starts (ulbm_double_shear_flow.cpp:96, eval_equilibrium with the u^2 terms left out) and
+// drifts with u_r = U0 / 2, which leaves no node at rest.  --buoyancy and --exchange fail with the library's message.
 #include <cmath>
 #include <iostream>
 #include <sstream>
@@ -27,7 +31,7 @@ int main(int argc, char** argv) {
   if (argc < 8) {
     std::cerr << "usage: " << argv[0] << " R C steps omega omega_g w_r w_c [--dump prefix] [--form 0|1|2] [--walls 0|1|2]"
                  " [--fixed edge=C_w[,edge=C_w...]] [--buoyancy beta_r,beta_c,c_ref[,u_shift,guo_a,guo_b]]"
-                 " [--rectangle r_top,c_first,c_second[,conc]] [--exchange 0|1]\n";
+                 " [--rectangle r_top,c_first,c_second[,conc]] [--exchange 0|1] [--fluid bgk|kbc] [--s2 X]\n";
     return 1;
   }
   try {
@@ -38,6 +42,10 @@ int main(int argc, char** argv) {
     const int form = std::stoi(arg_value(argc, argv, "--form", "0"));
     const int walls = std::stoi(arg_value(argc, argv, "--walls", "0"));
     const bool exchange = std::stoi(arg_value(argc, argv, "--exchange", "0")) != 0;
+    const std::string fluid = arg_value(argc, argv, "--fluid", "bgk");
+    if (fluid != "bgk" && fluid != "kbc") throw std::runtime_error("--fluid: '" + fluid + "' is not bgk or kbc");
+    const bool kbc = fluid == "kbc";
+    const double s2 = std::stod(arg_value(argc, argv, "--s2", argv[4]));
     lbm_ade_scalar_bc sbc{};
     std::stringstream fixed(arg_value(argc, argv, "--fixed", ""));
     for (std::string item; std::getline(fixed, item, ',');) {
@@ -68,7 +76,7 @@ int main(int argc, char** argv) {
     for (int r = 0; r < R; ++r)
       for (int c = 0; c < C; ++c) {
         const size_t i = (size_t)r * C + c;
-        uh[2 * i] = 0.0;
+        uh[2 * i] = kbc ? 0.5 * U0 : 0.0;
         uh[2 * i + 1] = U0 * std::sin(2.0 * pi * r / R);
         const double dr = r - 0.5 * R, dc = c - 0.5 * C;
         ch[i] = C0 * std::exp(-(dr * dr + dc * dc) / (2.0 * sigma * sigma));
@@ -77,14 +85,16 @@ int main(int argc, char** argv) {
     u.from_host(uh);
     rho.fill(1.0);
     conc.from_host(ch);
-    solver::equilibrium(f_adve, u, rho);
+    if (kbc) lbm::check(lbm_kbc_equilibrium(f_adve.data(), rho.data(), u.data(), R, C, 1, nullptr));
+    else solver::equilibrium(f_adve, u, rho);
     solver::equilibrium(g_adve, u, conc);
     const std::vector<double> f0 = f_adve.to_host(), g0 = g_adve.to_host();
 
     lbm::BoundarySet bc;
     if (walls) bc.col_lo = bc.col_hi = LBM_EDGE_BOUNCE_BACK;
     if (walls == 2) bc.row_lo = bc.row_hi = LBM_EDGE_BOUNCE_BACK;
-    lbm::AdeSolver sv(R, C, omega, omega_g, w_r, w_c, bc, form);
+    lbm::AdeSolver sv = kbc ? lbm::AdeSolver::kbc(R, C, s2, omega_g, w_r, w_c, bc, form)
+                            : lbm::AdeSolver(R, C, omega, omega_g, w_r, w_c, bc, form);
     sv.set_scalar_bc(sbc);
     if (buoyant) sv.set_buoyancy(lbm_ade_buoyancy{bv[0], bv[1], bv[2], bv[3], bv[4], bv[5]});
     // the rectangle as the driver adds it: first wall (f stops one row short of the last row, g runs through it with

@@ -289,6 +289,19 @@ class AdeSolver {
     const lbm_ade_params scalar{omega_g, w_r, w_c, form};
     check(lbm_ade_solver_create(&h_, &g, &bc, &fluid, &scalar, nullptr));
   }
+  // the same loop with the entropic KBC collision as the fluid (lbm_ade_fluid, model = LBM_MODEL_KBC): s2 in (0, 2] in
+  // place of omega.  set_buoyancy with a non-zero beta, set_open with a non-empty table and wall_exchange throw on it.
+  static AdeSolver kbc(int R, int C, double s2, double omega_g, double w_r, double w_c, const lbm_bc& bc = BoundarySet(),
+                       int form = LBM_FORM_DEFAULT) {
+    AdeSolver sv(R, C);
+    lbm_geom g{R, C, 0, 0, 0};
+    lbm_ade_fluid fluid{};
+    fluid.model = LBM_MODEL_KBC;
+    fluid.kbc = lbm_kbc_params{s2, form};
+    const lbm_ade_params scalar{omega_g, w_r, w_c, form};
+    check(lbm_ade_solver_create_m(&sv.h_, &g, &bc, &fluid, &scalar, nullptr));
+    return sv;
+  }
   AdeSolver(AdeSolver&& o) noexcept : h_(o.h_), R_(o.R_), C_(o.C_) { o.h_ = nullptr; }
   AdeSolver(const AdeSolver&) = delete;
   ~AdeSolver() {
@@ -356,6 +369,7 @@ class AdeSolver {
   lbm_ade_solver* handle() { return h_; }
 
  private:
+  AdeSolver(int R, int C) : R_(R), C_(C) {}  // no context yet: kbc() creates it
   lbm_ade_solver* h_ = nullptr;
   int R_, C_;
 };

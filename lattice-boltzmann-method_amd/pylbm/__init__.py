@@ -107,6 +107,22 @@ class AdeParams(ct.Structure):
         super().__init__(omega_g, w[0], w[1], form)
 
 
+class AdeFluid(ct.Structure):
+    """lbm_ade_fluid: the fluid of the fluid + scalar step by model -- AdeFluid(BgkParams(...)) or AdeFluid(KbcParams(...));
+    what lbm_ade_collide_m, lbm_ade_stream_collide_m and lbm_ade_solver_create_m take"""
+    _fields_ = [("model", ct.c_int), ("bgk", BgkParams), ("kbc", KbcParams)]
+
+    def __init__(self, params=None, model=None):
+        """model: MODEL_* to override what the type of params says (the ABI tests pass an unknown one)"""
+        super().__init__()
+        if isinstance(params, KbcParams):
+            self.model, self.kbc = MODEL_KBC, params
+        elif params is not None:
+            self.model, self.bgk = MODEL_BGK, params
+        if model is not None:
+            self.model = model
+
+
 class AdeScalarBC(ct.Structure):
     """lbm_ade_scalar_bc: the scalar's wall per edge (row_lo, row_hi, col_lo, col_hi), NO_FLUX or FIXED.  A FIXED edge
     takes fixed=(conc, profile) with profile None (the constant conc) or a device array of C_w along the edge (a float64
@@ -481,8 +497,9 @@ class Solver:
 
 
 class AdeSolver:
-    """Python face of lbm_ade_solver: a compressible BGK fluid f and a transported scalar g on one block
-    (the sediment loop of test/rectangle_sedimentation_test.cpp), numpy AoS in/out, reference layout."""
+    """Python face of lbm_ade_solver: a fluid f and a transported scalar g on one block (the sediment loop of
+    test/rectangle_sedimentation_test.cpp), numpy AoS in/out, reference layout.  fluid: BgkParams (the compressible BGK
+    fluid, lbm_ade_solver_create), or KbcParams / AdeFluid (the entropic KBC fluid, lbm_ade_solver_create_m)."""
 
     def __init__(self, lib, R, C, fluid, scalar, bc=None, stream=None, scalar_bc=None, buoyancy=None, walls=None,
                  open=None):
@@ -490,8 +507,13 @@ class AdeSolver:
         self.g = Geom(R, C, 0)
         self.bc = bc if bc is not None else Bc.periodic()
         self.h = ct.c_void_p()
-        lib.ade_solver_create(ct.byref(self.h), ct.byref(self.g), ct.byref(self.bc), ct.byref(fluid),
-                              ct.byref(scalar), _stream(stream))
+        if isinstance(fluid, (KbcParams, AdeFluid)):
+            self.fluid_m = fluid if isinstance(fluid, AdeFluid) else AdeFluid(fluid)
+            lib.ade_solver_create_m(ct.byref(self.h), ct.byref(self.g), ct.byref(self.bc), ct.byref(self.fluid_m),
+                                    ct.byref(scalar), _stream(stream))
+        else:
+            lib.ade_solver_create(ct.byref(self.h), ct.byref(self.g), ct.byref(self.bc), ct.byref(fluid),
+                                  ct.byref(scalar), _stream(stream))
         self.scalar_bc = self.buoyancy = self.walls = self.open = None
         try:
             if walls is not None:

@@ -22,10 +22,15 @@ and against the single-step BGK launch, on one periodic box, in one process, alt
   only other route to the same figures, both lattices of lbm_ade_solver_get_state copied into preallocated, touched host
   arrays (the host arithmetic on top is not counted); host clock around each call, after one forced call of either
   route, medians
+  --kbc is a mode of its own (nothing else is measured): the pair step with a KBC fluid (lbm_ade_solver_create_m,
+  ade_kbc.hpp) in both forms against what a user could assemble without it -- (a) the BGK pair step plus (c) one single-step lbm_kbc_stream_collide launch of
+  the form, 432 B per node where the fused step moves 288 B.  All start from the reference KBC driver's state
+  (lbm_kbc_equilibrium without the u^2 terms) on a drifting shear wave: a lattice exactly at equilibrium makes KBC's
+  gamma 0/0.  ms per step of every repeat, the condition (b) < (a) + (c) per repeat, (b) / (a), the algorithmic TB/s of (b)
 MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
 (18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
 usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls] [--buoyancy]
-       [--interior-walls] [--open] [--wall-exchange]"""
+       [--interior-walls] [--open] [--wall-exchange] [--kbc]"""
 import argparse
 import ctypes as ct
 import json
@@ -103,6 +108,71 @@ def wall_exchange_bench(lib, a, fluid, scalar, f, g, st):
     return out
 
 
+def kbc_bench(lib, a, rho, conc, u, st, timed):
+    """--kbc: the JSON fields of that mode; rho, conc, u: the dense initial moments on the device (u overwritten)"""
+    R = C = a.size
+    n = R * C
+    dev = rho.device
+    s2 = 1.0 / (0.5 + 3.0 * 1.7e-4)
+    u[0] = 0.01  # no node at rest
+    f, g = (torch.empty((9, R, C), dtype=torch.float64, device=dev) for _ in range(2))
+    lib.kbc_equilibrium(_ptr(f), _ptr(rho), _ptr(u), R, C, 1, None)
+    lib.equilibrium(_ptr(g), _ptr(u), _ptr(conc), R, C, None)
+    torch.cuda.synchronize()
+    dg = pylbm.Geom(R, C, 0)
+    forms = {"fast": pylbm.FORM_REASSOCIATED, "ref": pylbm.FORM_REFERENCE_ORDER}
+    solvers = {"bgk_pair": pylbm.AdeSolver(lib, R, C, pylbm.BgkParams(1.2, 0), pylbm.AdeParams(1.7, W), stream=st.value)}
+    for name, form in forms.items():
+        solvers["kbc_pair_" + name] = pylbm.AdeSolver(lib, R, C, pylbm.KbcParams(s2, form), pylbm.AdeParams(1.7, W, form=form),
+                                                      stream=st.value)
+    for sv in solvers.values():
+        fc, gc, _, _, sg = sv.lattices()
+        lib.lattice_copy_rows(_ptr(fc), ct.byref(sg), 0, _ptr(f), ct.byref(dg), 0, R, st)
+        lib.lattice_copy_rows(_ptr(gc), ct.byref(sg), 0, _ptr(g), ct.byref(dg), 0, R, st)
+    # (c): the single-step KBC launch on two padded lattices, per form
+    plane = n + lib.default_plane_pad(R, C)
+    lat = [torch.empty(9 * plane, dtype=torch.float64, device=dev) for _ in range(2)]
+    pg, pbc = pylbm.Geom(R, C, 0, plane, 0), pylbm.Bc.periodic()
+    lib.lattice_copy_rows(_ptr(lat[0]), ct.byref(pg), 0, _ptr(f), ct.byref(dg), 0, R, st)
+    lib.kbc_collide(_ptr(lat[1]), _ptr(lat[0]), ct.byref(pg), ct.byref(pbc), ct.byref(pylbm.KbcParams(s2, forms["fast"])), None, None, st)
+    lib.stream_sync(st)
+    del f, g
+    cur = [1]
+
+    def single(form):
+        prm = pylbm.KbcParams(s2, form)
+
+        def run(k):
+            for _ in range(k):
+                lib.kbc_stream_collide(_ptr(lat[cur[0] ^ 1]), _ptr(lat[cur[0]]), ct.byref(pg), ct.byref(pbc), ct.byref(prm), 0, R,
+                                       None, None, st)
+                cur[0] ^= 1
+        return run
+
+    runs = {k: sv.step for k, sv in solvers.items()}
+    for name, form in forms.items():
+        runs["kbc_single_" + name] = single(form)
+    for fn in runs.values():
+        timed(fn, a.warmup)
+    times = {k: [] for k in runs}
+    for _ in range(a.repeats):
+        for k, fn in runs.items():
+            times[k].append(timed(fn, a.steps))
+    ms = {k: [round(t / a.steps * 1e3, 4) for t in v] for k, v in times.items()}
+    nonfinite = {k: float(sv.diag()[pylbm.DIAG_NONFINITE]) for k, sv in solvers.items()}
+    out = {"metric": "fluid + scalar pair step with a KBC fluid, D2Q9 f64, periodic box", "size": [R, C], "steps": a.steps,
+           "repeats": a.repeats, "s2": s2, "ms_per_step": ms, "nonfinite_after": nonfinite}
+    for name in forms:
+        b, c = ms["kbc_pair_" + name], ms["kbc_single_" + name]
+        out[name] = {"b_lt_a_plus_c_per_repeat": [x < y + z for x, y, z in zip(b, ms["bgk_pair"], c)],
+                     "a_plus_c_ms": [round(y + z, 4) for y, z in zip(ms["bgk_pair"], c)],
+                     "b_over_a": [round(x / y, 3) for x, y in zip(b, ms["bgk_pair"])],
+                     "b_algorithmic_tbs": round(288.0 * n / (statistics.median(b) * 1e-3) / 1e12, 3)}
+    for sv in solvers.values():
+        sv.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=8192)
@@ -116,6 +186,7 @@ def main():
     ap.add_argument("--interior-walls", action="store_true")
     ap.add_argument("--open", action="store_true")
     ap.add_argument("--wall-exchange", action="store_true")
+    ap.add_argument("--kbc", action="store_true")
     a = ap.parse_args()
     form = {"default": pylbm.FORM_DEFAULT, "ref": pylbm.FORM_REFERENCE_ORDER, "fast": pylbm.FORM_REASSOCIATED}[a.form]
     lib = pylbm.Lib()
@@ -146,6 +217,13 @@ def main():
     u = torch.zeros((2, R, C), dtype=torch.float64, device=dev)
     u[1] = 0.02 * torch.sin(2 * math.pi * r / R)
     del r, c
+    if a.kbc:
+        out = kbc_bench(lib, a, rho, conc, u, st, timed)
+        lib.event_destroy(e0)
+        lib.event_destroy(e1)
+        lib.stream_destroy(st)
+        print(json.dumps(out))
+        return
     f = torch.empty((9, R, C), dtype=torch.float64, device=dev)
     g = torch.empty_like(f)
     lib.equilibrium(_ptr(f), _ptr(u), _ptr(rho), R, C, None)
