@@ -683,8 +683,8 @@ int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls);
  * kernel written for this fluid, ade_kbc.hpp), one more with wall edges, one more per non-empty table.
  * Refused on the host (LBM_ERR_INVALID, the message names the feature and the model): bc->pressure_rows; on a context
  * lbm_ade_solver_set_buoyancy with beta != (0, 0) (the forced collision is the BGK driver's: the reference has no forced
- * KBC), lbm_ade_solver_set_open with a non-empty table, lbm_ade_solver_wall_exchange.  There is no slab or ring entry
- * for a KBC fluid: lbm_ade_stream_collide_part* and lbm_ring_ade_* take lbm_bgk_params. */
+ * KBC), lbm_ade_solver_set_open with a non-empty table, lbm_ade_solver_wall_exchange.  Row slabs and the ring:
+ * lbm_ade_stream_collide_part_m below, lbm_ring_ade_collide_m / lbm_ring_ade_step_m with the ring. */
 typedef struct lbm_ade_fluid {
   int model;          /* LBM_MODEL_BGK or LBM_MODEL_KBC */
   lbm_bgk_params bgk; /* read when model == LBM_MODEL_BGK */
@@ -697,6 +697,22 @@ int lbm_ade_stream_collide_m(double* fn, double* gn, const double* fo, const dou
                              const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int row_begin, int row_end,
                              double* rho, double* u, double* conc, lbm_stream_t s);
+/* One part of a slab's step with either fluid: lbm_ade_stream_collide_part_w's arguments with the fluid by model.
+ * model = LBM_MODEL_BGK: IS lbm_ade_stream_collide_part_w with `bgk` and a NULL buoyancy -- the same checks under that
+ * name, the same launches, the same bits.
+ * model = LBM_MODEL_KBC: the geometries and edges of lbm_ade_stream_collide_part (ghost = 0 with PERIODIC or BOUNCE_BACK
+ * rows; ghost >= 1 with HALO or BOUNCE_BACK rows), lbm_ade_scalar_bc, a slab-local interior-wall table
+ * (lbm_ade_iwalls_slab) and the optional moments.  ONE dispatch per part -- the part kernel written for this fluid
+ * (ade_kbc.hpp: both row bands, wall fix-ups inline, one lattice in registers at a time; there is no edge pass) -- and one
+ * more, the interior-wall pass, where the part's rows hold table nodes; both count in lbm_ade_part_launches.  The stored
+ * bits are those of lbm_ade_stream_collide_m on one block.  The call only enqueues: no allocation, no host
+ * synchronisation, capturable in a graph.  Refused on the host before any device call, the message naming the feature
+ * and the model: bc->pressure_rows; a kbc.form that differs from scalar->form.  There is no parameter for buoyancy or
+ * for an open view, and the wall exchange stays refused for this fluid. */
+int lbm_ade_stream_collide_part_m(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                  const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int part, int edge_rows,
+                                  double* rho, double* u, double* conc, lbm_stream_t s);
 /* the context with either fluid; with a KBC fluid it supports set_state, step, get_state, sync, lattices, launches,
  * set_scalar_bc, set_walls, lbm_ade_solver_diag and lbm_ade_solver_run_until */
 int lbm_ade_solver_create_m(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc /* NULL = periodic */,
@@ -930,6 +946,19 @@ int lbm_ring_ade_step_o(lbm_ring* rg, double* fn, double* gn, const double* fo, 
                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, const lbm_ade_open* view,
                         const double* carry_in, double* carry_out, int edge_rows, lbm_stream_t main);
+/* The ring's collide-only iteration and overlapped step with the fluid by model (lbm_ade_fluid).
+ * model = LBM_MODEL_BGK: ARE lbm_ring_ade_collide_b / lbm_ring_ade_step_w with `bgk` and a NULL buoyancy -- the same
+ * checks under those names, the same launches, the same bits.
+ * model = LBM_MODEL_KBC: the same schedule with lbm_ade_stream_collide_part_m's launches -- ghost = 1; bc and sbc of the
+ * GLOBAL domain, seams HALO, a FIXED row dropped at a seam; FRAME and its wall pass on the ring's stream before the pack,
+ * INNER and its wall pass on `main`; a chain of one slab runs both parts on `main`; one message per neighbour carrying
+ * both lattices.  No synchronisation beyond lbm_ring_ade_step_w's.  Refusals as lbm_ade_stream_collide_part_m. */
+int lbm_ring_ade_collide_m(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                           const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                           lbm_stream_t main);
+int lbm_ring_ade_step_m(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                        const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                        const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main);
 /* refresh the single-step ghost rows of two lattices in one message per neighbour (e.g. after restoring a state);
  * asynchronous, ordered after the work enqueued on `after` (lbm_ring_join makes a stream wait for it) */
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after);

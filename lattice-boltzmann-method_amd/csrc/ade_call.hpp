@@ -21,6 +21,7 @@ struct AdeCall {
   int n_wall_nodes;
   const int* wall_first;  // host: the table's row index (R + 1 entries), NULL without nodes
   const lbm_bgk_params* fluid;
+  const lbm_kbc_params* kbc;  // a KBC fluid (ade_kbc_resolve): the launches are capi_ade_kbc(_part).hip's; NULL for a BGK fluid
   const lbm_ade_params* scalar;
   const AdeOpenNode* open_nodes;  // the open-boundary table (lbm_ade_open), NULL without nodes
   const AdeOpenSeg* open_segs;

@@ -1,6 +1,7 @@
-// Fluid + transported scalar with the entropic KBC collision as the fluid: the interior pair kernel of that step.  The
-// edge pass, the interior-wall pass and the collide-only launch are ade.hpp's kernels with a KBC model as FM (one node
-// per lane, latency-bound); only the kernel that holds two nodes of both lattices per lane is written for this fluid.
+// Fluid + transported scalar with the entropic KBC collision as the fluid: the interior pair kernel of that step and its
+// part form for row slabs.  The edge pass, the interior-wall pass and the collide-only launch are ade.hpp's kernels with a
+// KBC model as FM (one node per lane, latency-bound); only the kernels that hold two nodes of both lattices per lane are
+// written for this fluid.
 #pragma once
 #include "ade.hpp"
 #include "kbc.hpp"
@@ -57,6 +58,77 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     if (!G_EARLY) {
       ade_kbc_phase();
       pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+    }
+    sm.collide(ha, ux_a, uy_a, c_a);
+    sm.collide(hb, ux_b, uy_b, c_b);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    if (WITH_MOMENTS) {
+      const long o = (long)r * g.C + c;  // moment fields are dense
+      const long n = (long)g.R * g.C;
+      store2<false>(rho_out + o, rho_a, rho_b);
+      store2<false>(u_out + o, ux_a, ux_b);
+      store2<false>(u_out + n + o, uy_a, uy_b);
+      store2<false>(c_out + o, c_a, c_b);
+    }
+  }
+}
+
+// k_ade_stream_collide_part for a KBC fluid: the fused step on a PART of a slab in ONE dispatch with the wall fix-ups
+// inline -- rows [band0, band0 + n0) followed by rows [band1, band1 + nrows - n0), rows through wrap_row (ghost rows once
+// g.ghost > 0), owned nodes written only -- in the ORDER of k_ade_kbc_stream_collide, one lattice per lane at a time:
+//   f pair in, its wall fix-ups -> collide node a, node b -> f pair out; (rho, ux, uy) of both nodes stay
+//   g pair in, its wall fix-ups (FIXED: gathered with ade_scalar_gather_bc) -> FIXED: the wall lanes anti-bounce back at
+//   the FIXED edges with the kept u -> the scalar's collisions -> g pair out -> moments out
+// G_EARLY: the g pull and its fix-ups in front of the fluid's collisions, as in the interior kernel.  Measured on 4 slabs
+// of 2048 x 8192 (profiles/ade_kbc_slabs.txt), the answer is NOT the interior kernel's: the reference-order pair runs early
+// (206-210 VGPRs; faster than late, 174-177, in every repeat, with and without walls), the reassociated pair late (154-156
+// VGPRs, three waves; early, 186-189, wins on the walled chain and loses on the ring).  No instantiation has scratch.
+// Instantiating k_ade_stream_collide_part with a KBC model instead holds all 36 populations beside the collision: the
+// naive kernel.  Launched from a translation unit of its own (capi_ade_kbc_part.hip).
+// Each population is the value of the one load gather_walls / pull_pair take for it, and the arithmetic is fm.collide's,
+// ade_fixed_walls' and sm.collide's in k_ade_edge's FIXED order, expression for expression: the stored bits are those of
+// k_ade_kbc_stream_collide + k_ade_edge<KbcModel ...> on one block.  There is no BUOYANT form: a KBC fluid has no forced
+// collision.  Requirements as k_ade_stream_collide_part.
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool FIXED, bool G_EARLY>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_ade_kbc_stream_collide_part(
+    double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
+    Geom g, Bc bc, FM fm, SM sm, int band0, int n0, int band1, int nrows, int tiles_per_row,
+    double* __restrict__ rho_out, double* __restrict__ u_out, double* __restrict__ c_out, AdeWalls sw) {
+  const long items = (long)nrows * tiles_per_row;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const int v = (int)(it / tiles_per_row);
+    const int r = v < n0 ? band0 + v : band1 + (v - n0);
+    const int c = ((int)(it % tiles_per_row) * 256 + threadIdx.x) * 2;
+    if (c >= g.C) continue;
+    const long rm = g.at(wrap_row(g, r - 1), 0);  // source row of cx = +1 populations
+    const long r0 = g.at(r, 0);
+    const long rp = g.at(wrap_row(g, r + 1), 0);  // source row of cx = -1 populations
+    const bool row_lo = r == 0 && bc.row_lo == LBM_EDGE_BOUNCE_BACK, row_hi = r == g.R - 1 && bc.row_hi == LBM_EDGE_BOUNCE_BACK;
+    const bool wall = row_lo || row_hi || (c == 0 && bc_is_wall(bc.col_lo)) || (c + 2 == g.C && bc_is_wall(bc.col_hi));
+    double xa[Q], xb[Q], ha[Q], hb[Q];            // the lattice in flight of node (r, c) and node (r, c + 1)
+    double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
+    pull_pair<NT_LOAD>(xa, xb, fo, g, rm, r0, rp, c);
+    if (wall) wall_fixups_pair<NT_LOAD>(xa, xb, fo, g, bc, row_lo, row_hi, r0, c);
+    if (G_EARLY) {
+      pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+      if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, row_lo, row_hi, r0, c);
+    }
+    ade_kbc_phase();
+    fm.collide(xa, rho_a, ux_a, uy_a);
+    if (G_EARLY) ade_kbc_phase();  // with g in registers too: one collision at a time
+    fm.collide(xb, rho_b, ux_b, uy_b);
+    ade_kbc_phase();
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, xa[q], xb[q]);
+    if (!G_EARLY) {
+      ade_kbc_phase();
+      pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+      if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, row_lo, row_hi, r0, c);
+    }
+    if (FIXED && wall) {
+      ade_fixed_walls(ha, g, bc, sw, r, c, ux_a, uy_a, sm.wr, sm.wc);
+      ade_fixed_walls(hb, g, bc, sw, r, c + 1, ux_b, uy_b, sm.wr, sm.wc);
     }
     sm.collide(ha, ux_a, uy_a, c_a);
     sm.collide(hb, ux_b, uy_b, c_b);

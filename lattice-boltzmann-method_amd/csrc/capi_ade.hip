@@ -401,6 +401,7 @@ int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm
   call->g = make_geom(*lg);
   call->bc = make_bc(lbc);
   call->fluid = fluid;
+  call->kbc = nullptr;
   call->scalar = scalar;
   call->open_nodes = nullptr;
   call->open_segs = nullptr;
@@ -496,6 +497,7 @@ static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
 // kernels the part launches of this process have enqueued (lbm_ade_part_launches): what "a NULL view adds no launch" is
 // tested with, there being no solver context for slabs to count them
 static std::atomic<long long> g_part_launches{0};
+void ade_part_launches_add(long long n) { g_part_launches.fetch_add(n, std::memory_order_relaxed); }
 
 // one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline, + the table passes of
 // those rows
@@ -524,6 +526,7 @@ static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
 // nothing more
 int ade_collide_from(const char* fn, const AdeCall& k, double* fp, double* gp, const double* f, const double* h,
                      double* rho, double* u, double* conc, hipStream_t st) {
+  if (k.kbc) return ade_kbc_collide_from(fn, k, fp, gp, f, h, rho, u, conc, st);
   if (int rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false)) return rc;
   return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
     return ade_collide_launch<B()>(k, fm, sm, fp, gp, f, h, rho, u, conc, st);
@@ -615,6 +618,7 @@ int ade_part_args(const char* fn, const AdeCall& k, const double* fn_, const dou
 // one part of a call, after ade_part_args
 int ade_part_from(const AdeCall& k, double* fn, double* gn, const double* fo, const double* go, int part, int edge_rows,
                   double* rho, double* u, double* conc, hipStream_t st) {
+  if (k.kbc) return ade_kbc_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
   const int R = k.g.R;
   // FRAME: rows [0, E) then [R - E, R); INNER: rows [E, R - E)
   const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;

@@ -1,19 +1,21 @@
 // C ABI, fluid + transported scalar with the entropic KBC collision as the fluid (lbm_ade_fluid, lbm_hip.h): the `_m`
 // entry points.  A BGK fluid forwards to the existing calls of capi_ade.hip; a KBC fluid is checked and launched here --
 // the interior pair kernel of ade_kbc.hpp, and ade.hpp's edge, interior-wall and collide-only kernels with a KBC model
-// as the fluid.  No buoyancy, no open boundaries, no slabs.
+// as the fluid.  On a slab the part kernel of ade_kbc.hpp is launched from capi_ade_kbc_part.hip -- a unit of its own, so
+// that the device code of this one stays what it was -- and the interior-wall pass of the part's rows from here
+// (ade_kbc_iwalls_pass).  No buoyancy, no open boundaries, no wall exchange.
 #include <cmath>
 
-#include "ade_call.hpp"
-#include "ade_kbc.hpp"
+#include "ade_kbc_call.hpp"
 
 namespace lbm {
 
 // the KBC parameters as lbm_kbc_* checks them, what the step cannot do with this fluid, then every check of the step
-// that does not depend on the fluid (ade_resolve with a stand-in BGK fluid that passes)
-static int ade_kbc_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
-                           const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls,
-                           AdeCall* call) {
+// that does not depend on the fluid (ade_resolve with a stand-in BGK fluid that passes; slab: its flag of that name).  The
+// resolved call keeps kbc (borrowed, like scalar): ade_part_from and ade_collide_from launch from it with this fluid.
+int ade_kbc_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
+                    const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, bool slab,
+                    AdeCall* call) {
   LBM_REQUIRE(kbc, "%s: NULL fluid params", fn);
   LBM_REQUIRE(kbc->s2 > 0.0 && kbc->s2 <= 2.0, "%s: KBC fluid: s2=%g outside (0, 2]", fn, kbc->s2);
   LBM_REQUIRE(kbc->form >= LBM_FORM_DEFAULT && kbc->form <= LBM_FORM_REASSOCIATED, "%s: KBC fluid: form=%d (LBM_FORM_*)", fn,
@@ -21,21 +23,39 @@ static int ade_kbc_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, 
   LBM_REQUIRE(!(bc && bc->pressure_rows), "%s: pressure rows (pressure_rows=%d) are not supported by the fluid + scalar "
               "step with a KBC fluid", fn, bc ? bc->pressure_rows : 0);
   const lbm_bgk_params stand_in{1.0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, LBM_FORM_DEFAULT};
-  if (int rc = ade_resolve(fn, g, bc, &stand_in, scalar, sbc, nullptr, iwalls, false, call)) return rc;
+  if (int rc = ade_resolve(fn, g, bc, &stand_in, scalar, sbc, nullptr, iwalls, slab, call)) return rc;
   call->fluid = nullptr;  // (the stand-in's lifetime ends here; the KBC launches never read it)
+  call->kbc = kbc;
   LBM_REQUIRE(kbc->form == LBM_FORM_DEFAULT || kbc->form == scalar->form,
               "%s: KBC fluid form=%d differs from the scalar form=%d (lbm_ade_params.form sets both halves)", fn, kbc->form,
               scalar->form);
   return LBM_OK;
 }
 
-// f(fluid model, scalar model): one form for both halves, lbm_ade_params.form; LBM_FORM_DEFAULT resolves through
-// "kbc_fast", as for lbm_kbc_*
-template <class F>
-static int with_ade_kbc_models(const lbm_kbc_params* kbc, const lbm_ade_params* scalar, F f) {
-  const bool fast = scalar->form == LBM_FORM_DEFAULT ? tuning("kbc_fast", 1) != 0 : scalar->form == LBM_FORM_REASSOCIATED;
-  if (fast) return f(KbcFastModel(kbc->s2), AdeFastModel(scalar->omega_g, scalar->w_r, scalar->w_c));
-  return f(KbcModel{kbc->s2}, AdeModelRef{scalar->omega_g, scalar->w_r, scalar->w_c});
+// The interior-wall pass of rows [band0, band0 + n0) and [band1, band1 + nrows - n0) (ade_row_ranges), behind the dispatch
+// whose nodes it overwrites and on the same stream: the one launch site of k_ade_iwalls_ranges with a KBC model.  Rows
+// without a table node enqueue nothing.  *launches += the kernels enqueued
+template <class FM, class SM>
+static int ade_kbc_iwalls_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
+                                 const double* go, int band0, int n0, int band1, int nrows, double* rho, double* u,
+                                 double* conc, hipStream_t st, long long* launches) {
+  if (k.n_wall_nodes == 0) return LBM_OK;
+  const AdeRanges a = ade_row_ranges(k.wall_first, band0, n0, band1, nrows);
+  if (a.w == 0) return LBM_OK;
+  with_flags([&](auto M, auto F) {
+    LBM_KLAUNCH((k_ade_iwalls_ranges<FM, SM, M(), F(), false>), dim3((a.w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go,
+                k.g, k.bc, fm, sm, rho, u, conc, k.sw, k.by, k.wall_nodes, a.first0, a.w0, a.first1, a.w);
+  }, rho != nullptr, k.sw.fixed);
+  LBM_CHECK_LAUNCH();
+  ++*launches;
+  return LBM_OK;
+}
+
+int ade_kbc_iwalls_pass(const AdeCall& k, double* fn, double* gn, const double* fo, const double* go, int band0, int n0,
+                        int band1, int nrows, double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
+  return with_ade_kbc_models(k.kbc, k.scalar, [&](const auto& fm, const auto& sm) {
+    return ade_kbc_iwalls_launch(k, fm, sm, fn, gn, fo, go, band0, n0, band1, nrows, rho, u, conc, st, launches);
+  });
 }
 
 // interior launch + (walls only) the edge pass + the interior-wall pass of rows [row_begin, row_end): ade_step_launch's
@@ -68,25 +88,14 @@ static int ade_kbc_step_launch(const AdeCall& k, const FM& fm, const SM& sm, dou
     LBM_CHECK_LAUNCH();
     ++*launches;
   }
-  if (k.n_wall_nodes > 0) {
-    const int nrows = row_end - row_begin;
-    const AdeRanges a = ade_row_ranges(k.wall_first, row_begin, nrows, row_begin, nrows);
-    if (a.w > 0) {
-      with_flags([&](auto M, auto F) {
-        LBM_KLAUNCH((k_ade_iwalls_ranges<FM, SM, M(), F(), false>), dim3((a.w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go,
-                    k.g, k.bc, fm, sm, rho, u, conc, k.sw, k.by, k.wall_nodes, a.first0, a.w0, a.first1, a.w);
-      }, mom, k.sw.fixed);
-      LBM_CHECK_LAUNCH();
-      ++*launches;
-    }
-  }
-  return LBM_OK;
+  const int nrows = row_end - row_begin;
+  return ade_kbc_iwalls_launch(k, fm, sm, fn, gn, fo, go, row_begin, nrows, row_begin, nrows, rho, u, conc, st, launches);
 }
 
 int ade_kbc_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
                      const lbm_ade_params* scalar) {
   AdeCall k;
-  return ade_kbc_resolve(fn, g, bc, kbc, scalar, nullptr, nullptr, &k);
+  return ade_kbc_resolve(fn, g, bc, kbc, scalar, nullptr, nullptr, false, &k);
 }
 
 // collide only: no streaming, so no wall rule -- the scalar's walls and the interior walls are checked and nothing more
@@ -95,12 +104,19 @@ int ade_kbc_collide(const char* fn, double* fp, double* gp, const double* f, con
                     const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, double* rho, double* u, double* conc,
                     hipStream_t st, long long* launches) {
   AdeCall k;
-  int rc = ade_kbc_resolve(fn, lg, bc, kbc, scalar, sbc, iwalls, &k);
-  if (!rc) rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false);
-  if (rc) return rc;
+  int rc = ade_kbc_resolve(fn, lg, bc, kbc, scalar, sbc, iwalls, false, &k);
+  if (!rc) rc = ade_kbc_collide_from(fn, k, fp, gp, f, h, rho, u, conc, st);
+  if (!rc && launches) ++*launches;
+  return rc;
+}
+
+// the collide-only launch of a resolved call (a single block or a slab: the owned rows)
+int ade_kbc_collide_from(const char* fn, const AdeCall& k, double* fp, double* gp, const double* f, const double* h,
+                         double* rho, double* u, double* conc, hipStream_t st) {
+  if (int rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false)) return rc;
   const long n = (long)k.g.R * k.g.C;
   const int grid = capped_grid((n + 255) / 256);
-  rc = with_ade_kbc_models(kbc, scalar, [&](const auto& fm, const auto& sm) {
+  return with_ade_kbc_models(k.kbc, k.scalar, [&](const auto& fm, const auto& sm) {
     using FM = std::decay_t<decltype(fm)>;
     using SM = std::decay_t<decltype(sm)>;
     with_flags([&](auto M) {
@@ -109,8 +125,6 @@ int ade_kbc_collide(const char* fn, double* fp, double* gp, const double* f, con
     LBM_CHECK_LAUNCH();
     return (int)LBM_OK;
   });
-  if (!rc && launches) ++*launches;
-  return rc;
 }
 
 int ade_kbc_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
@@ -118,7 +132,7 @@ int ade_kbc_stream_collide(const char* fn, double* fn_, double* gn, const double
                            const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int row_begin, int row_end,
                            double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
   AdeCall k;
-  int rc = ade_kbc_resolve(fn, lg, bc, kbc, scalar, sbc, iwalls, &k);
+  int rc = ade_kbc_resolve(fn, lg, bc, kbc, scalar, sbc, iwalls, false, &k);
   if (!rc) rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true);
   if (rc) return rc;
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R, "%s: row range [%d, %d) outside [0, %d)", fn,
@@ -131,7 +145,7 @@ int ade_kbc_stream_collide(const char* fn, double* fn_, double* gn, const double
   });
 }
 
-static int ade_fluid_model(const char* fn, const lbm_ade_fluid* fluid) {
+int ade_fluid_model(const char* fn, const lbm_ade_fluid* fluid) {
   LBM_REQUIRE(fluid, "%s: NULL fluid (lbm_ade_fluid)", fn);
   LBM_REQUIRE(fluid->model == LBM_MODEL_BGK || fluid->model == LBM_MODEL_KBC,
               "%s: fluid model=%d (LBM_MODEL_BGK or LBM_MODEL_KBC)", fn, fluid->model);
@@ -164,6 +178,21 @@ int lbm_ade_stream_collide_m(double* fn, double* gn, const double* fo, const dou
                                     rho, u, conc, s);
   return ade_kbc_stream_collide("lbm_ade_stream_collide_m", fn, gn, fo, go, g, bc, &fluid->kbc, scalar, sbc, iwalls,
                                 row_begin, row_end, rho, u, conc, as_stream(s), nullptr);
+}
+
+int lbm_ade_stream_collide_part_m(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                  const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int part, int edge_rows,
+                                  double* rho, double* u, double* conc, lbm_stream_t s) {
+  const char* name = "lbm_ade_stream_collide_part_m";
+  if (int rc = ade_fluid_model(name, fluid)) return rc;
+  if (fluid->model == LBM_MODEL_BGK)
+    return lbm_ade_stream_collide_part_w(fn, gn, fo, go, g, bc, &fluid->bgk, scalar, sbc, nullptr, iwalls, part, edge_rows,
+                                         rho, u, conc, s);
+  AdeCall k;
+  int rc = ade_kbc_resolve(name, g, bc, &fluid->kbc, scalar, sbc, iwalls, true, &k);
+  if (!rc) rc = ade_part_args(name, k, fn, gn, fo, go, part, edge_rows, rho, u, conc);
+  return rc ? rc : ade_kbc_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, as_stream(s));
 }
 
 }  // extern "C"

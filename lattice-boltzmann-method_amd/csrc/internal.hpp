@@ -95,6 +95,19 @@ int ade_kbc_stream_collide(const char* fn, double* f_new, double* g_new, const d
                            const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
                            const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int row_begin, int row_end,
                            double* rho, double* u, double* conc, hipStream_t st, long long* launches);
+// the same with a resolved call: ade_kbc_resolve is ade_resolve for this fluid (slab: as there), and a call it resolved is
+// what ade_part_from and ade_collide_from hand to ade_kbc_part_from / ade_kbc_collide_from -- one dispatch of the part
+// kernel of ade_kbc.hpp (capi_ade_kbc_part.hip) + the interior-wall pass of the part's rows, counted by
+// ade_part_launches_add (capi_ade.hip: what lbm_ade_part_launches reports).  ade_fluid_model: fluid given, model BGK or KBC.
+int ade_fluid_model(const char* fn, const lbm_ade_fluid* fluid);
+int ade_kbc_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
+                    const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, bool slab,
+                    AdeCall* call);
+int ade_kbc_collide_from(const char* fn, const AdeCall& call, double* fp, double* gp, const double* f, const double* h,
+                         double* rho, double* u, double* conc, hipStream_t st);
+int ade_kbc_part_from(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old, int part,
+                      int edge_rows, double* rho, double* u, double* conc, hipStream_t st);
+void ade_part_launches_add(long long n);
 // capi_diag.hip: what a solver context keeps for its diagnostics -- the row table [LBM_DIAG_NQ][R], the folded values on the
 // device and a pinned host buffer for them, all allocated by the first diag_reduce and kept.
 struct DiagBuf {

@@ -106,6 +106,77 @@ int main() {
     refused(lbm_ade_stream_collide_m(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &bgk, &sc, nullptr, nullptr, 0, 8, nullptr, nullptr,
                                      nullptr, nullptr), "lbm_ade_stream_collide_w: NULL lattice", "good BGK through stream_collide_m");
   }
+  {  // a part of a slab, lbm_ade_stream_collide_part_m: the fluid, the geometry of a slab, the part, the table
+    auto part = [&](const lbm_ade_fluid* fl, const lbm_geom* lg, const lbm_bc* bc, const lbm_ade_params* s, double* fn, double* gn,
+                    double* fo, double* go, const lbm_ade_iwalls* t, int which, int edge_rows, const char* word, const char* what) {
+      refused(lbm_ade_stream_collide_part_m(fn, gn, fo, go, lg, bc, fl, s, nullptr, t, which, edge_rows, nullptr, nullptr, nullptr,
+                                            nullptr), word, what);
+    };
+    alignas(16) double l0[2], l1[2], l2[2], l3[2];  // four distinct, aligned "lattices": the part is refused before any is read
+    const int F = LBM_ADE_PART_FRAME;
+    part(nullptr, &g, nullptr, &sc, l0, l1, l2, l3, nullptr, F, 1, "lbm_ade_stream_collide_part_m: NULL fluid", "part: NULL fluid");
+    lbm_ade_fluid f = kbc;
+    f.model = 7;
+    part(&f, &g, nullptr, &sc, l0, l1, l2, l3, nullptr, F, 1, "fluid model=7", "part: unknown model");
+    f = kbc;
+    f.kbc.s2 = 0.0;
+    part(&f, &g, nullptr, &sc, l0, l1, l2, l3, nullptr, F, 1, "s2=0 outside (0, 2]", "part: s2 = 0");
+    f.kbc.s2 = 2.5;
+    part(&f, &g, nullptr, &sc, l0, l1, l2, l3, nullptr, F, 1, "s2=2.5 outside (0, 2]", "part: s2 = 2.5");
+    f = kbc;
+    f.kbc.form = LBM_FORM_REFERENCE_ORDER;
+    const lbm_ade_params fast{1.7, 0.0, 0.0, LBM_FORM_REASSOCIATED};
+    part(&f, &g, nullptr, &fast, l0, l1, l2, l3, nullptr, F, 1, "KBC fluid form=1 differs from the scalar form=2", "part: forms differ");
+    const lbm_bc pressure{0, 0, 0, 0, 1, 1.0, 1.0, 0.0, 0.0};
+    part(&kbc, &g, &pressure, &sc, l0, l1, l2, l3, nullptr, F, 1, "pressure rows", "part: pressure rows");
+    part(&kbc, &g, &pressure, &sc, l0, l1, l2, l3, nullptr, F, 1, "KBC fluid", "part: pressure rows name the model");
+    part(&kbc, &g, nullptr, &sc, l0, l1, l2, l3, nullptr, 5, 1, "part=5", "part: neither FRAME nor INNER");
+    part(&kbc, &g, nullptr, &sc, l0, l1, l2, l3, nullptr, F, 0, "edge_rows=0", "part: edge_rows = 0");
+    part(&kbc, &g, nullptr, &sc, l0, l1, l2, l3, nullptr, F, 4, "2 x edge_rows < R=8", "part: 2 x edge_rows = R");
+    part(&kbc, &g, nullptr, &sc, nullptr, l1, l2, l3, nullptr, F, 1, "NULL lattice", "part: NULL lattice");
+    part(&kbc, &g, nullptr, &sc, l0, l0, l2, l3, nullptr, F, 1, "aliased lattices", "part: aliased lattices");
+    const lbm_bc halo{LBM_EDGE_HALO, LBM_EDGE_HALO, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
+    part(&kbc, &g, &halo, &sc, l0, l1, l2, l3, nullptr, F, 1, "HALO needs ghost rows", "part: HALO rows with ghost = 0");
+    const lbm_geom slab{8, 8, 1, 0, 0};
+    part(&kbc, &slab, nullptr, &sc, l0, l1, l2, l3, nullptr, F, 1, "row edge mode PERIODIC given", "part: PERIODIC rows with ghost = 1 (NULL bc)");
+    const lbm_bc periodic{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
+    part(&kbc, &slab, &periodic, &sc, l0, l1, l2, l3, nullptr, F, 1, "row edge mode PERIODIC given", "part: PERIODIC rows with ghost = 1");
+    // a good slab geometry passes the fluid's and the geometry's checks and is stopped at the part
+    part(&kbc, &slab, &halo, &sc, l0, l1, l2, l3, nullptr, 5, 1, "part=5", "part: ghost = 1 with HALO rows is a geometry of the call");
+    lbm_ade_iwalls* table = nullptr;
+    if (lbm_ade_iwalls_create(&table, 8, 8) != LBM_OK) {
+      ++failures;
+      std::printf("FAIL: creating a table\n");
+    }
+    part(&kbc, &slab, &halo, &sc, l0, l1, l2, l3, table, F, 1, "finalize", "part: unfinalized table");
+    lbm_ade_iwalls_destroy(table);
+    table = nullptr;
+    if (lbm_ade_iwalls_create(&table, 6, 8) != LBM_OK || lbm_ade_iwalls_finalize(table) != LBM_OK) {
+      ++failures;
+      std::printf("FAIL: building an empty table\n");
+    }
+    part(&kbc, &slab, &halo, &sc, l0, l1, l2, l3, table, F, 1, "6 x 8", "part: table built for another R x C");
+    lbm_ade_iwalls_destroy(table);
+    // model = BGK: lbm_ade_stream_collide_part_w's message
+    lbm_ade_fluid bgk{};
+    bgk.model = LBM_MODEL_BGK;
+    bgk.bgk = lbm_bgk_params{2.0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, LBM_FORM_DEFAULT};
+    bgk.kbc = lbm_kbc_params{-3.0, 9};
+    part(&bgk, &slab, &halo, &sc, l0, l1, l2, l3, nullptr, F, 1, "lbm_ade_stream_collide_part_w: omega=2", "BGK through part_m");
+    bgk.bgk.omega = 1.2;
+    part(&bgk, &slab, &halo, &sc, l0, l1, l2, l3, nullptr, F, 4, "lbm_ade_stream_collide_part_w: edge_rows=4", "good BGK through part_m");
+    // the ring's entries look at the fluid before they look at the ring
+    refused(lbm_ring_ade_collide_m(nullptr, l0, l1, l2, l3, nullptr, nullptr, &sc, nullptr, nullptr), "lbm_ring_ade_collide_m: NULL fluid",
+            "ring collide: NULL fluid");
+    f = kbc;
+    f.model = 7;
+    refused(lbm_ring_ade_step_m(nullptr, l0, l1, l2, l3, nullptr, &f, &sc, nullptr, nullptr, 1, nullptr), "fluid model=7",
+            "ring step: unknown model");
+    refused(lbm_ring_ade_step_m(nullptr, l0, l1, l2, l3, nullptr, &kbc, &sc, nullptr, nullptr, 1, nullptr), "lbm_ring_ade_step_m: NULL argument",
+            "ring step: NULL ring");
+    refused(lbm_ring_ade_collide_m(nullptr, l0, l1, l2, l3, nullptr, &kbc, &sc, nullptr, nullptr), "lbm_ring_ade_collide_m: NULL argument",
+            "ring collide: NULL ring");
+  }
   std::printf("ade_kbc_host_check: %d refusals checked, %d failures\n", checks, failures);
   return failures ? 1 : 0;
 }

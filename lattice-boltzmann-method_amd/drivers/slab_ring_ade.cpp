@@ -1,7 +1,8 @@
 // Fluid + transported scalar (lbm_ade_*, the sediment loop of test/rectangle_sedimentation_test.cpp:88-247 without its
 // driver-specific edges) slab-decomposed along r: one ghost row per side, ONE packed message per neighbour per step
 // carrying the single-step halo of both lattices (2 x 3 rows), FRAME + pack + exchange on the ring's stream beside the
-// INNER rows (lbm_ring_ade_step_w / _o).  C++ host on lbm_ring_* + lbm_ade_stream_collide_part_w / _o; one process per GPU.
+// INNER rows (lbm_ring_ade_step_w / _o / _m).  C++ host on lbm_ring_* + lbm_ade_stream_collide_part_w / _o / _m; one
+// process per GPU.
 //
 //   slab_ring_ade --spawn N [...]          fork N ranks on this node (rank i -> GPU i; --one-gpu 1: all on GPU 0,
 //                                          with --transport ipc: N real ranks sharing one device)
@@ -12,7 +13,8 @@
 //
 // Options: --rows R (per slab, weak scaling) --cols C --steps K --warmup W --edge-rows E --omega w --omega-g wg
 //          --walls 1 (bounce-back rows on the chain ends, bounce-back column 0, specular column C-1: a chain; default a
-//          closed, periodic ring)  --form ref|fast (both halves)  --check 1 (bitwise against one block: small sizes)
+//          closed, periodic ring)  --form ref|fast (both halves)  --check 1 (bitwise against one block: small sizes; a one
+//          block that is not finite fails the check, and the line reports how many values as "one_block_nonfinite")
 //          --scalar-fixed 1 (with --walls 1: fixed-concentration walls of the scalar, lbm_ade_scalar_bc -- row 0 of the
 //          chain at C_w = 1e-3, column 0 at a profile, 1e-3 on the last quarter of the global rows and 0 elsewhere, read
 //          from a device array of which each slab passes its slice, column C-1 absorbing, C_w = 0, beside the specular
@@ -33,6 +35,13 @@
 //          of ONE global row table, lbm_ade_wallx_rows with its view; printed before the JSON line: `wallx_slabs=` the
 //          fold of that table, `wallx_one_block=` the fold of the one block's, six values each in LBM_WALLX_* order)
 //
+//          --fluid bgk|kbc (default bgk) --s2 X (default --omega): kbc = the entropic KBC collision as the fluid
+//          (lbm_ade_fluid) through the _m entry points -- lbm_ring_ade_collide_m / lbm_ring_ade_step_m,
+//          lbm_ade_stream_collide_part_m; --check's one block runs lbm_ade_collide_m / lbm_ade_stream_collide_m.  KBC's
+//          stabiliser is 0/0 on a lattice exactly at equilibrium, so this fluid starts as passive_scalar_box --fluid kbc
+//          does: lbm_kbc_equilibrium without the u^2 terms on a shear wave that drifts along r.  Combines with --walls 1,
+//          --scalar-fixed 1, --rectangle 1 and --form; --buoyancy, --channel 1 and --exchange 1 are refused with it.
+//
 // Printed: one JSON line; ms per step of the slowest slab, and the one-block step of a slab-sized lattice beside it.
 //
 // run_rank / run_emulated hold the model and its lbm_ring_* calls; options, main(), the timed run, --check's comparison
@@ -47,6 +56,8 @@ struct Args : RingOpts {
   int walls = 0, scalar_fixed = 0, rectangle = 0, channel = 0, exchange = 0;
   double omega = 1.2, omega_g = 1.7;
   bool fast = true;
+  bool kbc = false;  // --fluid kbc
+  double s2 = 1.2;   // --s2
   bool buoyant = false;
   lbm_ade_buoyancy buoy{};
   const lbm_ade_buoyancy* buoyancy() const { return buoyant ? &buoy : nullptr; }
@@ -63,11 +74,15 @@ struct Args : RingOpts {
 // shear wave + Taylor-Green vortices on the GLOBAL box, scalar: a Gaussian blob; f = feq(u, rho), g = feq(u + w, C) in
 // the reference's operation order (solver.cpp:51-62) -- the same bits for every decomposition
 const double kW[2] = {3e-3, 3e-3};
-void init_node(double* f9, double* g9, int gr, int c, int Rg, int C) {
+// kbc: rho = 1 on the shear wave u = (U0 / 2, U0 sin(2 pi r / Rg)), U0 = 0.02, of passive_scalar_box --fluid kbc; f9 is then
+// a placeholder (upload_rows forms f on the device, lbm_kbc_equilibrium) and (rho_u[0], rho_u[1], rho_u[2]) = (rho, u)
+void init_node(double* f9, double* g9, int gr, int c, int Rg, int C, bool kbc = false, double* rho_u = nullptr) {
   const double pi = 3.14159265358979323846;
   const double x = 2 * pi * gr / Rg, y = 2 * pi * c / C;
-  const double u0 = 0.03 * std::sin(x) * std::cos(y), u1 = 0.03 * std::sin(x) - 0.02 * std::cos(x) * std::sin(y);
-  const double rho = 1.0 + 0.01 * std::cos(2 * x);
+  const double u0 = kbc ? 0.01 : 0.03 * std::sin(x) * std::cos(y);
+  const double u1 = kbc ? 0.02 * std::sin(x) : 0.03 * std::sin(x) - 0.02 * std::cos(x) * std::sin(y);
+  const double rho = kbc ? 1.0 : 1.0 + 0.01 * std::cos(2 * x);
+  if (rho_u) rho_u[0] = rho, rho_u[1] = u0, rho_u[2] = u1;
   const double dr = gr - 0.45 * Rg, dc = c - 0.55 * C, s = 0.12 * std::min(Rg, C);
   const double conc = 1e-3 * std::exp(-(dr * dr + dc * dc) / (2 * s * s));
   d2q9_equilibrium(f9, rho, u0, u1);
@@ -80,6 +95,14 @@ lbm_bgk_params fluid_params(const Args& a) {
   p.omega = a.omega;
   p.form = a.fast ? LBM_FORM_REASSOCIATED : LBM_FORM_REFERENCE_ORDER;
   return p;
+}
+// the fluid by model (the _m entry points): --fluid kbc with the rate --s2, in the form of --form
+lbm_ade_fluid fluid_model(const Args& a) {
+  lbm_ade_fluid m{};
+  m.model = a.kbc ? LBM_MODEL_KBC : LBM_MODEL_BGK;
+  m.bgk = fluid_params(a);
+  m.kbc = lbm_kbc_params{a.s2, a.fast ? LBM_FORM_REASSOCIATED : LBM_FORM_REFERENCE_ORDER};
+  return m;
 }
 lbm_ade_params scalar_params(const Args& a) {
   return lbm_ade_params{a.omega_g, kW[0], kW[1], a.fast ? LBM_FORM_REASSOCIATED : LBM_FORM_REFERENCE_ORDER};
@@ -163,25 +186,50 @@ lbm_ade_open* open_view(const lbm_ade_open* global, int row0, int R) {
   return v;
 }
 
-// pre-collision f, g of global rows [row0, row0 + R) into lattices of geometry g (owned rows; the rest zero)
-void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg) {
+// --check: the values of the one block's lattices that are not finite.  The comparison is on bit patterns, and equal NaNs
+// are equal bits: a yardstick that is not finite is a failed check, and the JSON line says how many values ("one_block_nonfinite")
+size_t count_nonfinite(const std::vector<double>& a) {
+  size_t n = 0;
+  for (double x : a) n += std::isfinite(x) ? 0 : 1;
+  return n;
+}
+std::string nonfinite_field(int check, size_t n) {
+  return check ? ", \"one_block_nonfinite\": " + std::to_string(n) : "";
+}
+
+// pre-collision f, g of global rows [row0, row0 + R) into lattices of geometry g (owned rows; the rest zero).  kbc: f =
+// lbm_kbc_equilibrium(rho, u) without the u^2 terms, formed on the device node by node -- the same bits for every
+// decomposition
+void upload_rows(double* f, double* h, const lbm_geom& g, int row0, int Rg, bool kbc) {
   const int R = g.R, C = g.C;
   const lbm_geom d{R, C, 0, 0, 0};
-  std::vector<double> hf((size_t)9 * R * C), hg((size_t)9 * R * C);
-  double f9[9], g9[9];
+  const size_t n = (size_t)R * C;
+  std::vector<double> hf(9 * n), hg(9 * n), hm(kbc ? 3 * n : 0);  // hm: rho [R][C], then u [2][R][C]
+  double f9[9], g9[9], m[3];
   for (int r = 0; r < R; ++r)
     for (int c = 0; c < C; ++c) {
-      init_node(f9, g9, row0 + r, c, Rg, C);
+      init_node(f9, g9, row0 + r, c, Rg, C, kbc, m);
+      const size_t i = (size_t)r * C + c;
       for (int q = 0; q < 9; ++q) {
-        hf[(size_t)q * R * C + (size_t)r * C + c] = f9[q];
-        hg[(size_t)q * R * C + (size_t)r * C + c] = g9[q];
+        hf[(size_t)q * n + i] = f9[q];
+        hg[(size_t)q * n + i] = g9[q];
       }
+      if (kbc)
+        for (int k = 0; k < 3; ++k) hm[k * n + i] = m[k];
     }
   double* stage = nullptr;
   check(lbm_malloc((void**)&stage, hf.size() * 8), "lbm_malloc");
   for (auto [dst, src] : {std::pair<double*, std::vector<double>*>{f, &hf}, {h, &hg}}) {
     check(lbm_memset(dst, 0, plane_doubles(g) * 9 * 8, nullptr), "memset");
-    check(lbm_memcpy_h2d(stage, src->data(), src->size() * 8, nullptr), "h2d");
+    if (kbc && dst == f) {
+      double* mom = alloc_doubles(3 * n);
+      check(lbm_memcpy_h2d(mom, hm.data(), hm.size() * 8, nullptr), "h2d");
+      check(lbm_kbc_equilibrium(stage, mom, mom + n, R, C, /*zero_u2=*/1, nullptr), "lbm_kbc_equilibrium");
+      check(lbm_stream_sync(nullptr), "sync");
+      lbm_free(mom);
+    } else {
+      check(lbm_memcpy_h2d(stage, src->data(), src->size() * 8, nullptr), "h2d");
+    }
     check(lbm_lattice_copy_rows(dst, &g, 0, stage, &d, 0, R, nullptr), "lbm_lattice_copy_rows");
   }
   check(lbm_stream_sync(nullptr), "sync");
@@ -201,9 +249,13 @@ void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_pa
   double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
   double* prof = scalar_profile(a, Rg);
   const lbm_ade_scalar_bc sbc = scalar_bc(prof, 0, bc);
-  upload_rows(f[0], h[0], g, 0, Rg);
+  upload_rows(f[0], h[0], g, 0, Rg, a.kbc);
+  const lbm_ade_fluid fm = fluid_model(a);
   double* carry[2] = {alloc_doubles((size_t)lbm_ade_open_carry_len(open)), alloc_doubles((size_t)lbm_ade_open_carry_len(open))};
-  if (open)
+  if (a.kbc)
+    check(lbm_ade_collide_m(f[1], h[1], f[0], h[0], &g, &bc, &fm, &sc, nullptr, nullptr, nullptr, nullptr, nullptr),
+          "lbm_ade_collide_m");
+  else if (open)
     check(lbm_ade_collide_o(f[1], h[1], f[0], h[0], &g, &bc, &fl, &sc, nullptr, a.buoyancy(), open, carry[1], nullptr, nullptr,
                             nullptr, nullptr), "lbm_ade_collide_o");
   else
@@ -211,7 +263,10 @@ void one_block(const Args& a, int Rg, const lbm_bgk_params& fl, const lbm_ade_pa
                             nullptr), "lbm_ade_collide_b");
   int cur = 1;
   for (int t = 0; t < a.warmup + a.steps; ++t, cur ^= 1)
-    if (open)
+    if (a.kbc)
+      check(lbm_ade_stream_collide_m(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fm, &sc, prof ? &sbc : nullptr, walls, 0,
+                                     Rg, nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_m");
+    else if (open)
       check(lbm_ade_stream_collide_o(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, &bc, &fl, &sc, prof ? &sbc : nullptr,
                                      a.buoyancy(), walls, open, carry[cur], carry[cur ^ 1], 0, Rg, nullptr, nullptr, nullptr,
                                      nullptr), "lbm_ade_stream_collide_o");
@@ -244,18 +299,24 @@ struct SlabSizedBlock {
   int cur = 0;
   void* ev[2];
   double ms = 0;
-  SlabSizedBlock(int R, int C) : g(padded_geom(R, C, 0)) {
+  SlabSizedBlock(int R, int C, bool kbc) : g(padded_geom(R, C, 0)) {
     for (int k = 0; k < 2; ++k) {
       f[k] = alloc_lattice(g);
       h[k] = alloc_lattice(g);
       check(lbm_event_create(&ev[k]), "lbm_event_create");
     }
-    upload_rows(f[0], h[0], g, 0, R);
+    upload_rows(f[0], h[0], g, 0, R, kbc);
   }
-  void step(const lbm_bgk_params& fl, const lbm_ade_params& sc, const lbm_ade_buoyancy* by, bool timed) {
+  // fm: the fluid by model where it is a KBC fluid (NULL: the BGK fluid fl)
+  void step(const lbm_bgk_params& fl, const lbm_ade_params& sc, const lbm_ade_buoyancy* by, bool timed,
+            const lbm_ade_fluid* fm = nullptr) {
     check(lbm_event_record(ev[0], nullptr), "event");
-    check(lbm_ade_stream_collide_b(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, nullptr, &fl, &sc, nullptr, by, 0, g.R,
-                                   nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_b");
+    if (fm)
+      check(lbm_ade_stream_collide_m(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, nullptr, fm, &sc, nullptr, nullptr, 0, g.R,
+                                     nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_m");
+    else
+      check(lbm_ade_stream_collide_b(f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &g, nullptr, &fl, &sc, nullptr, by, 0, g.R,
+                                     nullptr, nullptr, nullptr, nullptr), "lbm_ade_stream_collide_b");
     check(lbm_event_record(ev[1], nullptr), "event");
     float m = 0;
     check(lbm_event_elapsed_ms(&m, ev[0], ev[1]), "elapsed");
@@ -282,6 +343,7 @@ int run_emulated(const Args& a, int N) {
   if (E < 1 || 2 * E >= R) throw std::runtime_error("--edge-rows must satisfy 1 <= E and 2 E < rows");
   const lbm_bgk_params fl = fluid_params(a);
   const lbm_ade_params sc = scalar_params(a);
+  const lbm_ade_fluid fm = fluid_model(a);
   const lbm_bc gbc = global_bc(a);
   const bool closed = !a.walls;
   const lbm_geom g = padded_geom(R, C, 1);
@@ -303,9 +365,11 @@ int run_emulated(const Args& a, int N) {
     // the one block's post-collision state (lbm_ade_collide on the global lattice), scattered into the slabs
     const lbm_geom gg{Rg, C, 0, 0, 0};
     double *f0 = alloc_lattice(gg), *h0 = alloc_lattice(gg), *fp = alloc_lattice(gg), *hp = alloc_lattice(gg);
-    upload_rows(f0, h0, gg, 0, Rg);
+    upload_rows(f0, h0, gg, 0, Rg, a.kbc);
     double* carry0 = alloc_doubles((size_t)lbm_ade_open_carry_len(channel));  // of the global table: a view's is a slice of it
-    if (channel)
+    if (a.kbc)
+      check(lbm_ade_collide_m(fp, hp, f0, h0, &gg, &gbc, &fm, &sc, nullptr, nullptr, nullptr, nullptr, nullptr), "lbm_ade_collide_m");
+    else if (channel)
       check(lbm_ade_collide_o(fp, hp, f0, h0, &gg, &gbc, &fl, &sc, nullptr, a.buoyancy(), channel, carry0, nullptr, nullptr,
                               nullptr, nullptr), "lbm_ade_collide_o");
     else
@@ -343,8 +407,14 @@ int run_emulated(const Args& a, int N) {
     for (double* p : {f0, h0, fp, hp, carry0}) lbm_free(p);
   }
   EdgeStream es;
-  SlabSizedBlock block(R, C);
+  SlabSizedBlock block(R, C, a.kbc);
   auto part = [&](Slab& s, int cur, int which, lbm_stream_t st) {
+    if (a.kbc) {
+      check(lbm_ade_stream_collide_part_m(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fm, &sc,
+                                          prof ? &s.sbc : nullptr, s.walls, which, E, nullptr, nullptr, nullptr, st),
+            "lbm_ade_stream_collide_part_m");
+      return;
+    }
     if (s.open) {
       check(lbm_ade_stream_collide_part_o(s.f[cur ^ 1], s.h[cur ^ 1], s.f[cur], s.h[cur], &g, &s.bc, &fl, &sc,
                                           prof ? &s.sbc : nullptr, a.buoyancy(), s.walls, s.open, s.carry[cur], s.carry[cur ^ 1],
@@ -389,7 +459,7 @@ int run_emulated(const Args& a, int N) {
       }
       links.add_elapsed(k, i >= a.warmup);
     }
-    block.step(fl, sc, a.buoyancy(), i >= a.warmup);  // alternated with the chain's step
+    block.step(fl, sc, a.buoyancy(), i >= a.warmup, a.kbc ? &fm : nullptr);  // alternated with the chain's step
     cur ^= 1;
   }
   check(lbm_stream_sync(es.edge), "sync");
@@ -417,7 +487,10 @@ int run_emulated(const Args& a, int N) {
       std::printf("\n");
     }
   }
+  size_t nonfinite = 0;
   if (a.check) {
+    nonfinite = count_nonfinite(want[0]) + count_nonfinite(want[1]);
+    bad += nonfinite ? 1 : 0;
     size_t first = 0;
     for (int k = 0; k < N; ++k) {
       for (int lat = 0; lat < 2; ++lat)
@@ -429,10 +502,11 @@ int run_emulated(const Args& a, int N) {
   }
   const double slowest = links.slowest_ms() / a.steps, blk = block.ms / a.steps;
   std::printf("{\"driver\": \"slab_ring_ade\", \"mode\": \"emulated %s on one GPU\", \"slabs\": %d, \"rows_per_slab\": %d, "
-              "\"cols\": %d, \"global_rows\": %d, \"walls\": %d, \"scalar_fixed\": %d, \"form\": \"%s\", \"steps\": %d, "
+              "\"cols\": %d, \"global_rows\": %d, \"walls\": %d, \"scalar_fixed\": %d, \"form\": \"%s\", \"fluid\": \"%s\", \"s2\": %.17g, \"steps\": %d, "
               "\"edge_rows\": %d, \"message_rows_per_side\": %d, \"slowest_slab_ms_per_step\": %.4f, "
               "\"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, \"per_slab_ms\": [",
-              closed ? "closed ring" : "chain", N, R, C, Rg, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, E,
+              closed ? "closed ring" : "chain", N, R, C, Rg, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref",
+              a.kbc ? "kbc" : "bgk", a.s2, a.steps, E,
               2 * lbm_halo_rows(1), slowest, blk, blk / slowest);
   for (int k = 0; k < N; ++k) std::printf("%s%.4f", k ? ", " : "", links.ms(k) / a.steps);
   std::printf("]");
@@ -446,7 +520,7 @@ int run_emulated(const Args& a, int N) {
     for (int k = 0; k < N; ++k) std::printf("%s%d", k ? ", " : "", lbm_ade_open_count(S[k].open));
     std::printf("]");
   }
-  std::printf("%s%s}\n", a.buoyancy_field().c_str(), check_field(a.check, bad));
+  std::printf("%s%s%s}\n", a.buoyancy_field().c_str(), nonfinite_field(a.check, nonfinite).c_str(), check_field(a.check, bad));
   std::fflush(stdout);
   for (auto& s : S) {
     for (int b = 0; b < 2; ++b) {
@@ -467,6 +541,7 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   const int R = a.rows, C = a.cols, Rg = R * world;
   const lbm_bgk_params fl = fluid_params(a);
   const lbm_ade_params sc = scalar_params(a);
+  const lbm_ade_fluid fm = fluid_model(a);
   const lbm_bc gbc = global_bc(a);
   const lbm_geom g = padded_geom(R, C, 1);
   unsigned char id[128];
@@ -474,11 +549,13 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   lbm_ring* ring = nullptr;
   check(lbm_ring_create(&ring, id, rank, world, &g, /*periodic=*/a.walls ? 0 : 1), "lbm_ring_create");
   double *f[2] = {alloc_lattice(g), alloc_lattice(g)}, *h[2] = {alloc_lattice(g), alloc_lattice(g)};
-  upload_rows(f[1], h[1], g, rank * R, Rg);  // pre-collision, then the first driver iteration: collide + one exchange
+  upload_rows(f[1], h[1], g, rank * R, Rg, a.kbc);  // pre-collision, then the first driver iteration: collide + one exchange
   lbm_ade_open* channel = channel_table(a, Rg);  // the global table, this slab's view and its carries
   lbm_ade_open* open = open_view(channel, rank * R, R);
   double* carry[2] = {alloc_doubles((size_t)lbm_ade_open_carry_len(open)), alloc_doubles((size_t)lbm_ade_open_carry_len(open))};
-  if (open)
+  if (a.kbc)
+    check(lbm_ring_ade_collide_m(ring, f[0], h[0], f[1], h[1], &gbc, &fm, &sc, nullptr, nullptr), "lbm_ring_ade_collide_m");
+  else if (open)
     check(lbm_ring_ade_collide_o(ring, f[0], h[0], f[1], h[1], &gbc, &fl, &sc, nullptr, a.buoyancy(), open, carry[0], nullptr),
           "lbm_ring_ade_collide_o");
   else
@@ -490,7 +567,10 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   lbm_ade_iwalls* walls = slab_view(table, rank * R, R);
   int cur = 0;
   auto step = [&]() {
-    if (open)
+    if (a.kbc)
+      check(lbm_ring_ade_step_m(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fm, &sc, prof ? &sbc : nullptr, walls,
+                                a.edge_rows, nullptr), "lbm_ring_ade_step_m");
+    else if (open)
       check(lbm_ring_ade_step_o(ring, f[cur ^ 1], h[cur ^ 1], f[cur], h[cur], &gbc, &fl, &sc, prof ? &sbc : nullptr,
                                 a.buoyancy(), walls, open, carry[cur], carry[cur ^ 1], a.edge_rows, nullptr), "lbm_ring_ade_step_o");
     else
@@ -502,12 +582,15 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   if (const int failed = timed_ring_run(ring, "slab_ring_ade", a, rank, world, a.warmup, a.steps, step, &tmax)) return failed;
 
   int bad = 0;
+  size_t nonfinite = 0;
   if (a.check) {
     publish_owned_rows(a, ".f", rank, f[cur], g);
     publish_owned_rows(a, ".g", rank, h[cur], g);
     if (rank == 0) {
       std::vector<double> want[2];
       one_block(a, Rg, fl, sc, table, want[0], want[1], channel);
+      nonfinite = count_nonfinite(want[0]) + count_nonfinite(want[1]);
+      bad += nonfinite ? 1 : 0;
       for (int r = 0; r < world; ++r)
         for (int lat = 0; lat < 2; ++lat)
           bad += mismatching_planes(want[lat], Rg, read_owned_rows(a, lat ? ".g" : ".f", r, R, C), R, r * R, C);
@@ -515,18 +598,20 @@ int run_rank(const Args& a, int rank, int world, int local_rank) {
   }
   if (rank == 0) {
     // the one-block step of a slab-sized lattice on this GPU, after the ring's run
-    SlabSizedBlock block(R, C);
-    for (int i = 0; i < a.warmup + a.steps; ++i) block.step(fl, sc, a.buoyancy(), i >= a.warmup);
+    SlabSizedBlock block(R, C, a.kbc);
+    for (int i = 0; i < a.warmup + a.steps; ++i) block.step(fl, sc, a.buoyancy(), i >= a.warmup, a.kbc ? &fm : nullptr);
     const double ms = 1e3 * tmax / a.steps, blk = block.ms / a.steps;
     std::printf("{\"driver\": \"slab_ring_ade\", \"n_gpus\": %d, \"rows_per_gpu\": %d, \"cols\": %d, \"walls\": %d, "
-                "\"scalar_fixed\": %d, \"form\": \"%s\", \"steps\": %d, \"edge_rows\": %d, \"message_rows_per_side\": %d, "
+                "\"scalar_fixed\": %d, \"form\": \"%s\", \"fluid\": \"%s\", \"s2\": %.17g, \"steps\": %d, \"edge_rows\": %d, "
+                "\"message_rows_per_side\": %d, "
                 "\"slowest_slab_ms_per_step\": %.4f, \"one_block_slab_sized_ms_per_step\": %.4f, \"slab_rate_over_one_block\": %.3f, "
-                "\"mlups\": %.1f%s%s%s%s}\n",
-                world, R, C, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.steps, a.edge_rows, 2 * lbm_halo_rows(1), ms, blk, blk / ms,
+                "\"mlups\": %.1f%s%s%s%s%s}\n",
+                world, R, C, a.walls, a.scalar_fixed, a.fast ? "fast" : "ref", a.kbc ? "kbc" : "bgk", a.s2, a.steps, a.edge_rows,
+                2 * lbm_halo_rows(1), ms, blk, blk / ms,
                 (double)Rg * C / (ms * 1e3),
                 table ? (", \"interior_wall_nodes\": " + std::to_string(lbm_ade_iwalls_count(table))).c_str() : "",
                 channel ? (", \"open_nodes\": " + std::to_string(lbm_ade_open_count(channel))).c_str() : "",
-                a.buoyancy_field().c_str(), check_field(a.check, bad));
+                a.buoyancy_field().c_str(), nonfinite_field(a.check, nonfinite).c_str(), check_field(a.check, bad));
     std::fflush(stdout);
   }
   lbm_ring_destroy(ring);
@@ -583,6 +668,22 @@ int main(int argc, char** argv) {
     return 2;
   }
   a.fast = form == "fast";
+  const std::string fluid = arg_value(argc, argv, "--fluid", "bgk");
+  if (fluid != "bgk" && fluid != "kbc") {
+    std::fprintf(stderr, "slab_ring_ade: --fluid bgk|kbc\n");
+    return 2;
+  }
+  a.kbc = fluid == "kbc";
+  a.s2 = std::atof(arg_value(argc, argv, "--s2", arg_value(argc, argv, "--omega", "1.2")).c_str());
+  if (a.kbc) {  // what the step cannot do with this fluid: named here, never silently ignored
+    const char* flag = !arg_value(argc, argv, "--buoyancy", "").empty() ? "--buoyancy" : a.channel ? "--channel 1"
+                     : a.exchange ? "--exchange 1" : nullptr;
+    if (flag) {
+      std::fprintf(stderr, "slab_ring_ade: %s is not supported with --fluid kbc (the fluid + scalar step with a KBC fluid has no "
+                           "buoyancy, no open boundaries and no wall exchange)\n", flag);
+      return 1;
+    }
+  }
   try {
     double bv[6];
     a.buoyant = parse_buoyancy(arg_value(argc, argv, "--buoyancy", ""), bv);

@@ -329,6 +329,13 @@ def load_library(path=LIB_PATH):
     lib.lbm_ade_solver_launches.restype = ct.c_longlong
     lib.lbm_ade_open_carry_len.restype = ct.c_longlong
     lib.lbm_ade_part_launches.restype = ct.c_longlong
+    # the slab and ring entries of the fluid by model (AdeFluid): lattices, descriptors by reference, handles, streams
+    p, i = ct.c_void_p, ct.c_int
+    lib.lbm_ade_stream_collide_part_m.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, p, p, p, p]
+    lib.lbm_ring_ade_collide_m.argtypes = [p, p, p, p, p, p, p, p, p, p]
+    lib.lbm_ring_ade_step_m.argtypes = [p, p, p, p, p, p, p, p, p, p, i, p]
+    for fn in (lib.lbm_ade_stream_collide_part_m, lib.lbm_ring_ade_collide_m, lib.lbm_ring_ade_step_m):
+        fn.restype = ct.c_int
     return lib
 
 

@@ -1,0 +1,204 @@
+"""CPU suite, the fluid + scalar step with a KBC fluid over row slabs and the ring (lbm_ade_stream_collide_part_m,
+lbm_ring_ade_collide_m, lbm_ring_ade_step_m): the entry points are declared, exported and bound with their argument
+types, the header compiles as C99, and every host refusal of the part call comes with its message before any device call
+-- the fluid, the geometry of a slab, the part, the interior-wall table; model = BGK answers with the message of
+lbm_ade_stream_collide_part_w.  The ring's entries need a ring, and a ring needs a device: what they refuse before they
+look at the ring is here, the rest in tests/test_gpu_ade_kbc_slabs.py."""
+import ctypes as ct
+import os
+import re
+import subprocess
+
+import pytest
+
+import pylbm
+
+SYMBOLS = ["lbm_ade_stream_collide_part_m", "lbm_ring_ade_collide_m", "lbm_ring_ade_step_m"]
+REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
+FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
+HALO, BB = pylbm.EDGE_HALO, pylbm.EDGE_BOUNCE_BACK
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+G0 = pylbm.Geom(16, 16, 0)
+G1 = pylbm.Geom(16, 16, 1)
+SEAMS = pylbm.Bc(row_lo=HALO, row_hi=HALO)
+SCALAR = pylbm.AdeParams(1.7, (3e-3, 3e-3))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return pylbm.Lib()
+
+
+@pytest.fixture(scope="module")
+def lattices():
+    """four distinct 16-byte aligned host buffers: every call here is refused before a lattice is read"""
+    bufs = [(ct.c_double * 8)() for _ in range(4)]
+    ptrs = [(ct.addressof(b) + 15) & ~15 for b in bufs]
+    return bufs, ptrs
+
+
+def kbc(s2=1.6, form=pylbm.FORM_DEFAULT):
+    return pylbm.AdeFluid(pylbm.KbcParams(s2, form))
+
+
+def _ref(x):
+    return ct.byref(x) if x is not None else None
+
+
+def part_m(lib, lat, g, bc, fluid, scalar, part=FRAME, E=1, sbc=None, table=None, rho=None):
+    lib.ade_stream_collide_part_m(*lat, _ref(g), _ref(bc), _ref(fluid), _ref(scalar), _ref(sbc),
+                                  table.h if table is not None else None, part, E, rho, None, None, None)
+
+
+def refused(lib, lattices, msg, g=G1, bc=SEAMS, fluid=None, scalar=SCALAR, **kw):
+    with pytest.raises(pylbm.LbmError, match=msg):
+        part_m(lib, lattices[1], g, bc, fluid, scalar, **kw)
+
+
+def test_symbols_are_declared_exported_and_bound(lib):
+    declared = set(pylbm.declared_symbols())
+    for name in SYMBOLS:
+        assert name in declared, name
+        assert hasattr(lib.raw, name), name
+        fn = getattr(lib.raw, name)
+        assert fn.argtypes is not None and fn.restype is ct.c_int, name
+    assert len(lib.raw.lbm_ade_stream_collide_part_m.argtypes) == 16
+    assert len(lib.raw.lbm_ring_ade_collide_m.argtypes) == 10
+    assert len(lib.raw.lbm_ring_ade_step_m.argtypes) == 12
+    assert lib.raw.lbm_ade_stream_collide_part_m.argtypes[10:12] == [ct.c_int, ct.c_int]  # part, edge_rows
+    assert lib.raw.lbm_ring_ade_step_m.argtypes[10] is ct.c_int                              # edge_rows
+
+
+def test_null_fluid_and_unknown_model(lib, lattices):
+    refused(lib, lattices, "lbm_ade_stream_collide_part_m: NULL fluid", fluid=None)
+    refused(lib, lattices, "lbm_ade_stream_collide_part_m: fluid model=7", fluid=pylbm.AdeFluid(pylbm.KbcParams(1.6), model=7))
+    refused(lib, lattices, "fluid model=-1", fluid=pylbm.AdeFluid(pylbm.BgkParams(1.2, 0), model=-1))
+
+
+@pytest.mark.parametrize("s2", [0.0, 2.5, -1.0])
+def test_s2_outside_its_range(lib, lattices, s2):
+    refused(lib, lattices, r"lbm_ade_stream_collide_part_m: KBC fluid: s2=\S+ outside \(0, 2\]", fluid=kbc(s2))
+
+
+def test_a_fluid_form_that_differs_from_the_scalars(lib, lattices):
+    refused(lib, lattices, "KBC fluid form=1 differs from the scalar form=2", fluid=kbc(form=REF),
+            scalar=pylbm.AdeParams(1.7, (0.0, 0.0), form=FAST))
+    refused(lib, lattices, "KBC fluid form=2 differs from the scalar form=0", fluid=kbc(form=FAST),
+            scalar=pylbm.AdeParams(1.7, (0.0, 0.0)))
+    refused(lib, lattices, "KBC fluid: form=7", fluid=kbc(form=7))
+
+
+def test_pressure_rows_are_refused_by_name(lib, lattices):
+    refused(lib, lattices, "lbm_ade_stream_collide_part_m: pressure rows .* with a KBC fluid",
+            bc=pylbm.Bc(row_lo=HALO, row_hi=HALO, pressure_rows=1), fluid=kbc())
+
+
+def test_a_wrong_part_and_the_edge_rows(lib, lattices):
+    refused(lib, lattices, r"part=5 \(LBM_ADE_PART_FRAME or LBM_ADE_PART_INNER\)", fluid=kbc(), part=5)
+    refused(lib, lattices, "edge_rows=0: need 1 <= edge_rows", fluid=kbc(), E=0)
+    refused(lib, lattices, "edge_rows=8: need 1 <= edge_rows and 2 x edge_rows < R=16", fluid=kbc(), E=8)
+    refused(lib, lattices, "edge_rows=8", fluid=kbc(), E=8, part=INNER)
+
+
+def test_the_geometry_of_a_slab(lib, lattices):
+    """ghost >= 1 with HALO or BOUNCE_BACK rows and ghost = 0 with PERIODIC or BOUNCE_BACK rows pass the geometry's checks
+    (they are stopped at the part); HALO without ghost rows and PERIODIC with ghost rows stay refused"""
+    refused(lib, lattices, "row edge mode HALO needs ghost rows", g=G0, bc=SEAMS, fluid=kbc())
+    refused(lib, lattices, "row edge mode PERIODIC given", g=G1, bc=pylbm.Bc.periodic(), fluid=kbc())
+    refused(lib, lattices, "row edge mode PERIODIC given", g=G1, bc=None, fluid=kbc())
+    refused(lib, lattices, "row edge mode PERIODIC given", g=G1, bc=pylbm.Bc(row_lo=HALO), fluid=kbc())
+    for g, bc in ((G1, SEAMS), (G1, pylbm.Bc(row_lo=BB, row_hi=HALO)), (pylbm.Geom(16, 16, 2), SEAMS),
+                  (G0, pylbm.Bc.periodic()), (G0, pylbm.Bc(row_lo=BB, row_hi=BB))):
+        refused(lib, lattices, "part=5", g=g, bc=bc, fluid=kbc(), part=5)
+    refused(lib, lattices, "_part_m: C=15 must be even", g=pylbm.Geom(16, 15, 1), fluid=kbc())
+    refused(lib, lattices, "_part_m: ghost=16 must be 0..15", g=pylbm.Geom(16, 16, 16), fluid=kbc())
+    refused(lib, lattices, "NULL scalar params", fluid=kbc(), scalar=None)
+    refused(lib, lattices, "_part_m: scalar edge row_lo: FIXED on a HALO", fluid=kbc(), sbc=pylbm.AdeScalarBC(row_lo=1e-3))
+
+
+def test_lattice_and_moment_arguments(lib, lattices):
+    p = lattices[1]
+    with pytest.raises(pylbm.LbmError, match="_part_m: NULL lattice"):
+        part_m(lib, [None, p[1], p[2], p[3]], G1, SEAMS, kbc(), SCALAR)
+    with pytest.raises(pylbm.LbmError, match="_part_m: aliased lattices"):
+        part_m(lib, [p[0], p[0], p[2], p[3]], G1, SEAMS, kbc(), SCALAR)
+    with pytest.raises(pylbm.LbmError, match="_part_m: lattices must be 16-byte aligned"):
+        part_m(lib, [p[0] + 8, p[1], p[2], p[3]], G1, SEAMS, kbc(), SCALAR)
+    with pytest.raises(pylbm.LbmError, match="rho, u and conc"):
+        part_m(lib, p, G1, SEAMS, kbc(), SCALAR, rho=p[0])
+
+
+def test_an_unfinalized_table_and_a_table_of_the_wrong_shape(lib, lattices):
+    t = pylbm.AdeInteriorWalls(lib, 16, 16)  # empty: no device call at finalize
+    refused(lib, lattices, "_part_m: interior walls: the table is not finalized", fluid=kbc(), table=t)
+    t.close()
+    t = pylbm.AdeInteriorWalls(lib, 12, 16).finalize()
+    refused(lib, lattices, "_part_m: interior walls: the table is for a 12 x 16 lattice, the call for 16 x 16", fluid=kbc(), table=t)
+    t.close()
+    view = pylbm.AdeInteriorWalls(lib, 48, 16).slab(16, 16)  # a view is unfinalized until its own finalize
+    refused(lib, lattices, "the table is not finalized", fluid=kbc(), table=view)
+    view.close()
+
+
+def test_model_bgk_is_part_w(lib, lattices):
+    """bad BGK parameters, a bad part and a bad geometry through `_m` give lbm_ade_stream_collide_part_w's message; the kbc
+    member is not read"""
+    for bad, msg in ((pylbm.BgkParams(2.0, 0), "omega=2 outside"), (pylbm.BgkParams(1.2, 1), "incompressible=1")):
+        refused(lib, lattices, "lbm_ade_stream_collide_part_w: " + msg, fluid=pylbm.AdeFluid(bad))
+    fl = pylbm.AdeFluid(pylbm.BgkParams(1.2, 0))
+    fl.kbc = pylbm.KbcParams(-3.0, 9)
+    refused(lib, lattices, "lbm_ade_stream_collide_part_w: part=5", fluid=fl, part=5)
+    refused(lib, lattices, "lbm_ade_stream_collide_part_w: edge_rows=8", fluid=fl, E=8)
+    refused(lib, lattices, "lbm_ade_stream_collide_part_w: row edge mode HALO needs ghost rows", g=G0, fluid=fl)
+
+
+def test_the_ring_entries_look_at_the_fluid_first(lib, lattices):
+    p = lattices[1]
+    sc = ct.byref(SCALAR)
+    with pytest.raises(pylbm.LbmError, match="lbm_ring_ade_collide_m: NULL fluid"):
+        lib.ring_ade_collide_m(None, *p, None, None, sc, None, None)
+    with pytest.raises(pylbm.LbmError, match="lbm_ring_ade_step_m: NULL fluid"):
+        lib.ring_ade_step_m(None, *p, None, None, sc, None, None, 1, None)
+    bad = pylbm.AdeFluid(pylbm.KbcParams(1.6), model=7)
+    with pytest.raises(pylbm.LbmError, match="lbm_ring_ade_step_m: fluid model=7"):
+        lib.ring_ade_step_m(None, *p, None, ct.byref(bad), sc, None, None, 1, None)
+    with pytest.raises(pylbm.LbmError, match="lbm_ring_ade_collide_m: NULL argument"):
+        lib.ring_ade_collide_m(None, *p, None, ct.byref(kbc()), sc, None, None)
+    with pytest.raises(pylbm.LbmError, match="lbm_ring_ade_step_m: NULL argument"):
+        lib.ring_ade_step_m(None, *p, None, ct.byref(kbc()), sc, None, None, 1, None)
+    fl = pylbm.AdeFluid(pylbm.BgkParams(1.2, 0))  # model = BGK: the entries it forwards to answer
+    with pytest.raises(pylbm.LbmError, match="lbm_ring_ade_collide_b: NULL argument"):
+        lib.ring_ade_collide_m(None, *p, None, ct.byref(fl), sc, None, None)
+    with pytest.raises(pylbm.LbmError, match="lbm_ring_ade_step_w: NULL argument"):
+        lib.ring_ade_step_m(None, *p, None, ct.byref(fl), sc, None, None, 1, None)
+
+
+def test_header_with_the_new_prototypes_is_plain_c99(tmp_path):
+    src = tmp_path / "ade_kbc_slab_c99.c"
+    src.write_text('#include "lbm_hip.h"\n'
+                   'int main(void){ lbm_ade_fluid fl; lbm_ade_params p = {1.0, 0.0, 0.0, LBM_FORM_DEFAULT};\n'
+                   '  lbm_geom g = {16, 16, 1, 0, 0}; double a[2] = {0}, b[2] = {0}, c[2] = {0}, d[2] = {0};\n'
+                   '  fl.model = LBM_MODEL_KBC; fl.kbc.s2 = 0.0; fl.kbc.form = LBM_FORM_DEFAULT;\n'
+                   '  if (lbm_ade_stream_collide_part_m(a, b, c, d, &g, 0, &fl, &p, 0, 0, LBM_ADE_PART_FRAME, 1, 0, 0, 0, 0)\n'
+                   '      != LBM_ERR_INVALID) return 1;\n'
+                   '  if (lbm_ring_ade_collide_m(0, a, b, c, d, 0, 0, &p, 0, 0) != LBM_ERR_INVALID) return 2;\n'
+                   '  return lbm_ring_ade_step_m(0, a, b, c, d, 0, 0, &p, 0, 0, 1, 0) == LBM_ERR_INVALID ? 0 : 3; }\n')
+    libdir = os.path.join(ROOT, "lattice-boltzmann-method_amd", "lib")
+    exe = tmp_path / "ade_kbc_slab_c99"
+    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           str(src), "-L", libdir, "-llbm_hip", f"-Wl,-rpath,{libdir}", "-o", str(exe)])
+    assert subprocess.call([str(exe)]) == 0
+
+
+def test_the_extended_host_check_program_passes():
+    """the ORDINARY build of drivers/ade_kbc_host_check: the refusals of the part call and of the ring entries from C++, 72
+    in all, 40 of them from before the slab entries.  The sanitizer build of the same source is `make san`'s and is not
+    run here; this test only holds the recipe to naming it"""
+    exe = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin", "ade_kbc_host_check")
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    m = re.search(r"(\d+) refusals checked, 0 failures", r.stdout)
+    assert m and int(m.group(1)) >= 72, r.stdout
+    root_make = open(os.path.join(ROOT, "Makefile")).read()
+    assert "bin_san/ade_kbc_host_check" in root_make  # `make san` builds and runs it
