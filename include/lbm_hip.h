@@ -683,8 +683,8 @@ int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls);
  * kernel written for this fluid, ade_kbc.hpp), one more with wall edges, one more per non-empty table.
  * Refused on the host (LBM_ERR_INVALID, the message names the feature and the model): bc->pressure_rows; on a context
  * lbm_ade_solver_set_buoyancy with beta != (0, 0) (the forced collision is the BGK driver's: the reference has no forced
- * KBC), lbm_ade_solver_set_open with a non-empty table, lbm_ade_solver_wall_exchange.  Row slabs and the ring:
- * lbm_ade_stream_collide_part_m below, lbm_ring_ade_collide_m / lbm_ring_ade_step_m with the ring. */
+ * KBC; the forced KBC collision is lbm_ade_solver_set_buoyancy_m's, below), lbm_ade_solver_set_open with a non-empty
+ * table, lbm_ade_solver_wall_exchange.  Row slabs and the ring: lbm_ade_stream_collide_part_m below, lbm_ring_ade_collide_m / lbm_ring_ade_step_m with the ring. */
 typedef struct lbm_ade_fluid {
   int model;          /* LBM_MODEL_BGK or LBM_MODEL_KBC */
   lbm_bgk_params bgk; /* read when model == LBM_MODEL_BGK */
@@ -717,6 +717,42 @@ int lbm_ade_stream_collide_part_m(double* fn, double* gn, const double* fo, cons
  * set_scalar_bc, set_walls, lbm_ade_solver_diag and lbm_ade_solver_run_until */
 int lbm_ade_solver_create_m(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc /* NULL = periodic */,
                             const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, lbm_stream_t s);
+
+/* Buoyancy with the fluid by model, single block: lbm_ade_collide_m / lbm_ade_stream_collide_m with the descriptor of
+ * lbm_ade_buoyancy after sbc, and the context's setter for either fluid.
+ * model = LBM_MODEL_BGK: the calls ARE lbm_ade_collide_b / lbm_ade_stream_collide_w / lbm_ade_solver_set_buoyancy with
+ * `bgk` -- the same checks under those names, the same launches, the same bits.
+ * model = LBM_MODEL_KBC: the forced KBC collision.  The reference has no forced KBC and needs none: kbc::collide()
+ * collides on the moments the driver HOLDS (src/ulbm.cpp:91-126), and the conserved central moments relax with rate 1
+ * (ulbm.cpp:46-49), so colliding on m1 = u0 + u_shift F instead of the populations' own u0 leaves the post-collision
+ * momentum at rho (u0 + u_shift F) -- a velocity-shift forcing.  Per node, after streaming and the fluid's wall fix-ups,
+ * the list of lbm_ade_buoyancy with item 6 replaced:
+ *   1. rho = calc_rho(f), u0 = calc_u(f, rho);
+ *   2. the scalar's wall rule (lbm_ade_scalar_bc, the FIXED slots of an interior-wall table) with v = u0 + w;
+ *   3. C = calc_rho(g);   4. F = ((C - c_ref) beta_r, (C - c_ref) beta_c);   5. u = u0 + u_shift F;
+ *   6. f* = kbc::collide() on the held moments m0 = rho, m1 = u;
+ *   7. g* = collision(g, equilibrium(u + w, C)) with the same shifted u.
+ * Per collision the momentum changes by exactly rho u_shift F and the mass not at all; the physical velocity is
+ * u0 + u_shift F / 2, and u_shift = 1 gives F per step at rho ~ 1.  guo_a and guo_b are NOT read for this fluid (there is
+ * no source term); they must still be finite, like every field.  A NULL descriptor or beta = (0, 0) is the passive step of
+ * the `_m` calls in either form: the same bits and the same launches.  A buoyant step runs the REFERENCE order in both
+ * halves whatever `form` says (KbcModel and the reference-order scalar).  The moment outputs of the raw calls hold the
+ * shifted u of item 5; lbm_ade_solver_get_state keeps returning u = calc_u(f, rho).  288 B per node update, no launch of
+ * its own (one per step on a periodic box, one more with wall edges, one more per non-empty table), no halo traffic.
+ * Refused on the host before any device call, under the `_mb` name: a non-finite field of the descriptor and everything the
+ * `_m` calls refuse.  The calls only enqueue; a captured graph keeps the descriptor of its capture.
+ * Not extended: row slabs and the ring (lbm_ade_stream_collide_part_m, lbm_ring_ade_*_m have no parameter for buoyancy),
+ * open boundaries and the wall exchange with a KBC fluid stay refused, and lbm_ade_solver_set_buoyancy itself still
+ * refuses beta != (0, 0) on a KBC context. */
+int lbm_ade_collide_mb(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                       const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                       const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s);
+int lbm_ade_stream_collide_mb(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                              const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                              int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
+/* the context's buoyancy for either fluid, from the next step on; NULL = the passive scalar.  The descriptor is copied */
+int lbm_ade_solver_set_buoyancy_m(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy);
 
 /* Open boundaries of the fused step on a single block: the inlet, the outlet, the specular lid and the zero-gradient
  * copies of test/rectangle_sedimentation_test.cpp (:134-177, :203-218), as a host table built like lbm_ade_iwalls --

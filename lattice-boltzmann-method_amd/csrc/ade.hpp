@@ -140,15 +140,25 @@ __device__ __forceinline__ void ade_buoyant_fluid(double (&f)[Q], double omega, 
   }
 }
 
+// The forced collision of a buoyant node by fluid model -- the hook of the one-node kernels below.  In: rho =
+// calc_rho(f), (ux, uy) the shifted u, conc = calc_rho(h).  Any model with an `omega` (the BGK models) takes the force
+// branch above; another fluid overloads this on its model type (KbcModel: ade_kbc.hpp), found by argument-dependent lookup
+// where a kernel is instantiated with it.
+template <class FM>
+__device__ __forceinline__ void ade_forced_fluid(double (&f)[Q], const FM& fm, const AdeBuoyancy& by, double& rho,
+                                                 double ux, double uy, double conc) {
+  ade_buoyant_fluid(f, fm.omega, by, rho, ux, uy, conc);
+}
+
 // both collisions of one buoyant node; in: (rho, ux, uy) = ade_fluid_moments(f), h after the scalar's wall rule
 // (sm.collide forms the same C again from the same h)
-template <class SM>
-__device__ __forceinline__ void ade_buoyant_collide(double (&f)[Q], double (&h)[Q], double omega, const SM& sm,
+template <class FM, class SM>
+__device__ __forceinline__ void ade_buoyant_collide(double (&f)[Q], double (&h)[Q], const FM& fm, const SM& sm,
                                                     const AdeBuoyancy& by, double& rho, double& ux, double& uy,
                                                     double& conc) {
   ade_buoyant_shift(h, by, ux, uy, conc);
   sm.collide(h, ux, uy, conc);
-  ade_buoyant_fluid(f, omega, by, rho, ux, uy, conc);
+  ade_forced_fluid(f, fm, by, rho, ux, uy, conc);
 }
 
 // The scalar's fixed-concentration walls (lbm_ade_scalar_bc, device copy).  Edge e: 0 row_lo, 1 row_hi, 2 col_lo,
@@ -316,11 +326,11 @@ __global__ __launch_bounds__(256) void k_ade_edge(double* __restrict__ fn, doubl
   if (i >= 2 * g.C + n && g.C == 1 && bc_is_wall(bc.col_lo)) return;
   double f[Q], h[Q], rho, ux, uy, conc;
   gather_walls(f, fo, g, bc, r, c);
-  if constexpr (BUOYANT) {  // (constexpr: fm.omega is named for a BGK fluid alone)
+  if constexpr (BUOYANT) {  // (constexpr: the forced collision exists for the fluids with an ade_forced_fluid alone)
     gather_walls(h, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, r, c);
     ade_fluid_moments(f, rho, ux, uy);
     if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
-    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+    ade_buoyant_collide(f, h, fm, sm, by, rho, ux, uy, conc);
   } else if (FIXED) {
     gather_walls(h, go, g, ade_scalar_gather_bc(bc, sw.fixed), r, c);
     fm.collide(f, rho, ux, uy);
@@ -531,7 +541,7 @@ __global__ __launch_bounds__(256) void k_ade_iwalls_ranges(double* __restrict__ 
     ade_fluid_moments(f, rho, ux, uy);
     if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
     ade_iwalls_scalar(h, go, g, o, nd.slots, nd.conc, ux, uy, sm.wr, sm.wc);
-    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+    ade_buoyant_collide(f, h, fm, sm, by, rho, ux, uy, conc);
   } else {
     fm.collide(f, rho, ux, uy);
     if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
@@ -687,7 +697,7 @@ __global__ __launch_bounds__(256) void k_ade_collide(double* __restrict__ fp, do
     }
     if constexpr (BUOYANT) {
       ade_fluid_moments(f, rho, ux, uy);
-      ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+      ade_buoyant_collide(f, h, fm, sm, by, rho, ux, uy, conc);
     } else {
       ade_collide_node(f, h, fm, sm, rho, ux, uy, conc);
     }
@@ -837,7 +847,7 @@ __global__ __launch_bounds__(256) void k_ade_open_ranges(double* __restrict__ fn
     u0r = ux, u0c = uy;
     if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
     ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
-    ade_buoyant_collide(f, h, fm.omega, sm, by, rho, ux, uy, conc);
+    ade_buoyant_collide(f, h, fm, sm, by, rho, ux, uy, conc);
   } else {
     fm.collide(f, rho, ux, uy);
     u0r = ux, u0c = uy;

@@ -74,6 +74,74 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   }
 }
 
+// The forced collision of a KBC fluid (ade.hpp ade_forced_fluid, the hook of the one-node kernels): kbc::collide() on the
+// moments the driver HOLDS (src/ulbm.cpp:91-126) -- m0 = rho = calc_rho(f) and m1 = the shifted u = u0 + u_shift F.  The
+// conserved central moments relax with rate 1 (S = {1, 1, 1, s2, ...}, ulbm.cpp:46-49), so the post-collision momentum is
+// rho (u0 + u_shift F): a velocity-shift forcing with a momentum input of exactly rho u_shift F per collision and no
+// source term -- by.ga, by.gb and conc are not read.  KbcFastModel drops the conserved central moments and has no such
+// collision: a buoyant step runs the reference order.
+__device__ __forceinline__ void ade_forced_fluid(double (&f)[Q], const KbcModel& fm, const AdeBuoyancy&, double& rho,
+                                                 double ux, double uy, double) {
+  fm.collide_with(f, rho, ux, uy);
+}
+
+// k_ade_kbc_stream_collide, BUOYANT: the scalar pushes on the fluid (AdeBuoyancy; lbm_hip.h "buoyancy with a KBC fluid").
+// The fluid's collision needs C now, so the passive order (f in, collide, f out, then g) cannot stay; the order is the one
+// that made the BGK buoyant kernels fit -- the scalar is collided and STORED before the fluid's collisions, which then run
+// with f alone in registers:
+//   f pair in -> rho, u0 of both nodes (ade_fluid_moments, as KbcModel::collide forms them)
+//   g pair in -> C, the shifted u (ade_buoyant_shift) -> the scalar's collisions with that u -> g pair out
+//   collide_with node a | collide_with node b, fenced one after the other -> f pair out -> moments out (the shifted u)
+// There is no fence between the fluid's moments and the g pull: the scheduler issues the 18 loads of g with those of f
+// (36 populations in registers while nothing else is live).  A candidate with that fence -- the g loads wait for the
+// moments -- has the same registers and measured 0.2 - 0.3 % slower at 8192^2 in every repeat (profiles/
+// ade_kbc_buoyancy.txt); it is not built.  172 VGPRs (178 with the moments), no scratch: the passive reference-order pair's.
+// The arithmetic is ade_fluid_moments', ade_buoyant_shift's, sm.collide's and fm.collide_with's, expression for
+// expression: the stored bits are those of k_ade_collide<KbcModel, SM, ., true> on the streamed populations.
+// Requirements as k_ade_kbc_stream_collide; no wall fix-ups (k_ade_edge recomputes the wall nodes afterwards).
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_ade_kbc_stream_collide_buoyant(
+    double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
+    Geom g, FM fm, SM sm, int row_begin, int row_end, int tiles_per_row, double* __restrict__ rho_out,
+    double* __restrict__ u_out, double* __restrict__ c_out, AdeBuoyancy by) {
+  const long items = (long)(row_end - row_begin) * tiles_per_row;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const int r = row_begin + (int)(it / tiles_per_row);
+    const int c = ((int)(it % tiles_per_row) * 256 + threadIdx.x) * 2;
+    if (c >= g.C) continue;
+    const long rm = g.at(wrap_row(g, r - 1), 0);  // source row of cx = +1 populations
+    const long r0 = g.at(r, 0);
+    const long rp = g.at(wrap_row(g, r + 1), 0);  // source row of cx = -1 populations
+    double xa[Q], xb[Q], ha[Q], hb[Q];            // f and g of node (r, c) and node (r, c + 1)
+    double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
+    pull_pair<NT_LOAD>(xa, xb, fo, g, rm, r0, rp, c);
+    ade_fluid_moments(xa, rho_a, ux_a, uy_a);
+    ade_fluid_moments(xb, rho_b, ux_b, uy_b);
+    pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+    ade_buoyant_shift(ha, by, ux_a, uy_a, c_a);
+    ade_buoyant_shift(hb, by, ux_b, uy_b, c_b);
+    sm.collide(ha, ux_a, uy_a, c_a);
+    sm.collide(hb, ux_b, uy_b, c_b);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    ade_kbc_phase();
+    fm.collide_with(xa, rho_a, ux_a, uy_a);
+    ade_kbc_phase();  // one collision at a time
+    fm.collide_with(xb, rho_b, ux_b, uy_b);
+    ade_kbc_phase();
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, xa[q], xb[q]);
+    if (WITH_MOMENTS) {
+      const long o = (long)r * g.C + c;  // moment fields are dense
+      const long n = (long)g.R * g.C;
+      store2<false>(rho_out + o, rho_a, rho_b);
+      store2<false>(u_out + o, ux_a, ux_b);
+      store2<false>(u_out + n + o, uy_a, uy_b);
+      store2<false>(c_out + o, c_a, c_b);
+    }
+  }
+}
+
 // k_ade_stream_collide_part for a KBC fluid: the fused step on a PART of a slab in ONE dispatch with the wall fix-ups
 // inline -- rows [band0, band0 + n0) followed by rows [band1, band1 + nrows - n0), rows through wrap_row (ghost rows once
 // g.ghost > 0), owned nodes written only -- in the ORDER of k_ade_kbc_stream_collide, one lattice per lane at a time:
@@ -88,8 +156,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // naive kernel.  Launched from a translation unit of its own (capi_ade_kbc_part.hip).
 // Each population is the value of the one load gather_walls / pull_pair take for it, and the arithmetic is fm.collide's,
 // ade_fixed_walls' and sm.collide's in k_ade_edge's FIXED order, expression for expression: the stored bits are those of
-// k_ade_kbc_stream_collide + k_ade_edge<KbcModel ...> on one block.  There is no BUOYANT form: a KBC fluid has no forced
-// collision.  Requirements as k_ade_stream_collide_part.
+// k_ade_kbc_stream_collide + k_ade_edge<KbcModel ...> on one block.  There is no BUOYANT form of the part kernel: the forced
+// collision runs on a single block.  Requirements as k_ade_stream_collide_part.
 template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool FIXED, bool G_EARLY>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_ade_kbc_stream_collide_part(
     double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,

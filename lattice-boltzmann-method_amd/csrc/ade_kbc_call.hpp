@@ -21,4 +21,13 @@ int ade_kbc_iwalls_pass(const AdeCall& call, double* f_new, double* g_new, const
                         int band0, int n0, int band1, int nrows, double* rho, double* u, double* conc, hipStream_t st,
                         long long* launches);
 
+// capi_ade_kbc_buoyant.hip: the launches of a resolved call with call.buoyant on a single block -- the collide-only
+// iteration, and the step on rows [row_begin, row_end) (interior pair kernel, edge pass with wall edges, interior-wall pass
+// with table nodes in those rows; *launches += the kernels enqueued).  The reference order in both halves.
+int ade_kbc_buoyant_collide_from(const AdeCall& call, double* fp, double* gp, const double* f, const double* h, double* rho,
+                                 double* u, double* conc, hipStream_t st);
+int ade_kbc_buoyant_step(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old,
+                         int row_begin, int row_end, double* rho, double* u, double* conc, hipStream_t st,
+                         long long* launches);
+
 }  // namespace lbm

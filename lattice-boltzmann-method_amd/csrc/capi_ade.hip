@@ -900,12 +900,12 @@ int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
   for (int i = 0; i < n; ++i) {
     const int k = sv->cur, o = k ^ 1;
     int rc;
-    if (sv->model == LBM_MODEL_KBC) {  // (no buoyancy and no open table on such a context: their setters refuse)
+    if (sv->model == LBM_MODEL_KBC) {  // (no open table on such a context: its setter refuses)
       rc = !sv->post ? ade_kbc_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->kbc,
-                                       &sv->scalar, nullptr, sv->walls, nullptr, nullptr, nullptr, sv->st, &sv->launches)
+                                       &sv->scalar, nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st, &sv->launches)
                      : ade_kbc_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
-                                              &sv->kbc, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, sv->walls, 0, sv->g.R,
-                                              nullptr, nullptr, nullptr, sv->st, &sv->launches);
+                                              &sv->kbc, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, buoy, sv->walls, 0,
+                                              sv->g.R, nullptr, nullptr, nullptr, sv->st, &sv->launches);
     } else if (!sv->post) {
       rc = ade_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid,
                        &sv->scalar, nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st, sv->open, sv->carry[o],
@@ -1159,6 +1159,17 @@ int lbm_ade_solver_set_buoyancy(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy
   LBM_REQUIRE(sv->model != LBM_MODEL_KBC || !buoy || (buoy->beta_r == 0.0 && buoy->beta_c == 0.0),
               "lbm_ade_solver_set_buoyancy: buoyancy with beta=(%g, %g) is not supported with a KBC fluid (the forced "
               "collision is the BGK fluid's)", buoy->beta_r, buoy->beta_c);
+  sv->buoy = buoy ? *buoy : lbm_ade_buoyancy{};
+  sv->buoyant = buoy != nullptr;
+  return LBM_OK;
+}
+
+int lbm_ade_solver_set_buoyancy_m(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy) {
+  LBM_REQUIRE(sv, "lbm_ade_solver_set_buoyancy_m: NULL solver");
+  if (sv->model == LBM_MODEL_BGK) return lbm_ade_solver_set_buoyancy(sv, buoy);
+  int rc = ade_buoyancy_check("lbm_ade_solver_set_buoyancy_m", buoy);
+  if (rc) return rc;
+  // (a KBC context holds no open table and runs no wall exchange: lbm_ade_solver_set_open and _wall_exchange refuse)
   sv->buoy = buoy ? *buoy : lbm_ade_buoyancy{};
   sv->buoyant = buoy != nullptr;
   return LBM_OK;

@@ -3,7 +3,8 @@
 // the interior pair kernel of ade_kbc.hpp, and ade.hpp's edge, interior-wall and collide-only kernels with a KBC model
 // as the fluid.  On a slab the part kernel of ade_kbc.hpp is launched from capi_ade_kbc_part.hip -- a unit of its own, so
 // that the device code of this one stays what it was -- and the interior-wall pass of the part's rows from here
-// (ade_kbc_iwalls_pass).  No buoyancy, no open boundaries, no wall exchange.
+// (ade_kbc_iwalls_pass).  Buoyancy on a single block (the `_mb` entry points): the forced collision is launched from
+// capi_ade_kbc_buoyant.hip, a unit of its own for the same reason.  No open boundaries, no wall exchange.
 #include <cmath>
 
 #include "ade_kbc_call.hpp"
@@ -11,11 +12,12 @@
 namespace lbm {
 
 // the KBC parameters as lbm_kbc_* checks them, what the step cannot do with this fluid, then every check of the step
-// that does not depend on the fluid (ade_resolve with a stand-in BGK fluid that passes; slab: its flag of that name).  The
+// that does not depend on the fluid (ade_resolve with a stand-in BGK fluid that passes; slab: its flag of that name; buoy:
+// the buoyancy of a single block, NULL allowed -- call->buoyant then picks the forced collision at the launch sites).  The
 // resolved call keeps kbc (borrowed, like scalar): ade_part_from and ade_collide_from launch from it with this fluid.
 int ade_kbc_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
                     const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, bool slab,
-                    AdeCall* call) {
+                    AdeCall* call, const lbm_ade_buoyancy* buoy) {
   LBM_REQUIRE(kbc, "%s: NULL fluid params", fn);
   LBM_REQUIRE(kbc->s2 > 0.0 && kbc->s2 <= 2.0, "%s: KBC fluid: s2=%g outside (0, 2]", fn, kbc->s2);
   LBM_REQUIRE(kbc->form >= LBM_FORM_DEFAULT && kbc->form <= LBM_FORM_REASSOCIATED, "%s: KBC fluid: form=%d (LBM_FORM_*)", fn,
@@ -23,7 +25,7 @@ int ade_kbc_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const l
   LBM_REQUIRE(!(bc && bc->pressure_rows), "%s: pressure rows (pressure_rows=%d) are not supported by the fluid + scalar "
               "step with a KBC fluid", fn, bc ? bc->pressure_rows : 0);
   const lbm_bgk_params stand_in{1.0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, LBM_FORM_DEFAULT};
-  if (int rc = ade_resolve(fn, g, bc, &stand_in, scalar, sbc, nullptr, iwalls, slab, call)) return rc;
+  if (int rc = ade_resolve(fn, g, bc, &stand_in, scalar, sbc, buoy, iwalls, slab, call)) return rc;
   call->fluid = nullptr;  // (the stand-in's lifetime ends here; the KBC launches never read it)
   call->kbc = kbc;
   LBM_REQUIRE(kbc->form == LBM_FORM_DEFAULT || kbc->form == scalar->form,
@@ -101,10 +103,10 @@ int ade_kbc_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, const 
 // collide only: no streaming, so no wall rule -- the scalar's walls and the interior walls are checked and nothing more
 int ade_kbc_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* lg,
                     const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
-                    const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, double* rho, double* u, double* conc,
-                    hipStream_t st, long long* launches) {
+                    const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, double* rho,
+                    double* u, double* conc, hipStream_t st, long long* launches) {
   AdeCall k;
-  int rc = ade_kbc_resolve(fn, lg, bc, kbc, scalar, sbc, iwalls, false, &k);
+  int rc = ade_kbc_resolve(fn, lg, bc, kbc, scalar, sbc, iwalls, false, &k, buoy);
   if (!rc) rc = ade_kbc_collide_from(fn, k, fp, gp, f, h, rho, u, conc, st);
   if (!rc && launches) ++*launches;
   return rc;
@@ -114,6 +116,7 @@ int ade_kbc_collide(const char* fn, double* fp, double* gp, const double* f, con
 int ade_kbc_collide_from(const char* fn, const AdeCall& k, double* fp, double* gp, const double* f, const double* h,
                          double* rho, double* u, double* conc, hipStream_t st) {
   if (int rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false)) return rc;
+  if (k.buoyant) return ade_kbc_buoyant_collide_from(k, fp, gp, f, h, rho, u, conc, st);
   const long n = (long)k.g.R * k.g.C;
   const int grid = capped_grid((n + 255) / 256);
   return with_ade_kbc_models(k.kbc, k.scalar, [&](const auto& fm, const auto& sm) {
@@ -129,10 +132,11 @@ int ade_kbc_collide_from(const char* fn, const AdeCall& k, double* fp, double* g
 
 int ade_kbc_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
                            const lbm_geom* lg, const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
-                           const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int row_begin, int row_end,
-                           double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
+                           const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                           int row_begin, int row_end, double* rho, double* u, double* conc, hipStream_t st,
+                           long long* launches) {
   AdeCall k;
-  int rc = ade_kbc_resolve(fn, lg, bc, kbc, scalar, sbc, iwalls, false, &k);
+  int rc = ade_kbc_resolve(fn, lg, bc, kbc, scalar, sbc, iwalls, false, &k, buoy);
   if (!rc) rc = ade_lattice_args(fn, fn_, gn, fo, go, rho, u, conc, true);
   if (rc) return rc;
   LBM_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= lg->R, "%s: row range [%d, %d) outside [0, %d)", fn,
@@ -140,6 +144,7 @@ int ade_kbc_stream_collide(const char* fn, double* fn_, double* gn, const double
   if (row_begin == row_end) return LBM_OK;
   long long uncounted = 0;
   if (!launches) launches = &uncounted;
+  if (k.buoyant) return ade_kbc_buoyant_step(k, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
   return with_ade_kbc_models(kbc, scalar, [&](const auto& fm, const auto& sm) {
     return ade_kbc_step_launch(k, fm, sm, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
   });
@@ -164,7 +169,17 @@ int lbm_ade_collide_m(double* fp, double* gp, const double* f, const double* g_i
   if (int rc = ade_fluid_model("lbm_ade_collide_m", fluid)) return rc;
   if (fluid->model == LBM_MODEL_BGK)
     return lbm_ade_collide_b(fp, gp, f, g_in, g, bc, &fluid->bgk, scalar, sbc, nullptr, rho, u, conc, s);
-  return ade_kbc_collide("lbm_ade_collide_m", fp, gp, f, g_in, g, bc, &fluid->kbc, scalar, sbc, nullptr, rho, u, conc,
+  return ade_kbc_collide("lbm_ade_collide_m", fp, gp, f, g_in, g, bc, &fluid->kbc, scalar, sbc, nullptr, nullptr, rho, u,
+                         conc, as_stream(s), nullptr);
+}
+
+int lbm_ade_collide_mb(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                       const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                       const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s) {
+  if (int rc = ade_fluid_model("lbm_ade_collide_mb", fluid)) return rc;
+  if (fluid->model == LBM_MODEL_BGK)
+    return lbm_ade_collide_b(fp, gp, f, g_in, g, bc, &fluid->bgk, scalar, sbc, buoy, rho, u, conc, s);
+  return ade_kbc_collide("lbm_ade_collide_mb", fp, gp, f, g_in, g, bc, &fluid->kbc, scalar, sbc, buoy, nullptr, rho, u, conc,
                          as_stream(s), nullptr);
 }
 
@@ -176,7 +191,19 @@ int lbm_ade_stream_collide_m(double* fn, double* gn, const double* fo, const dou
   if (fluid->model == LBM_MODEL_BGK)
     return lbm_ade_stream_collide_w(fn, gn, fo, go, g, bc, &fluid->bgk, scalar, sbc, nullptr, iwalls, row_begin, row_end,
                                     rho, u, conc, s);
-  return ade_kbc_stream_collide("lbm_ade_stream_collide_m", fn, gn, fo, go, g, bc, &fluid->kbc, scalar, sbc, iwalls,
+  return ade_kbc_stream_collide("lbm_ade_stream_collide_m", fn, gn, fo, go, g, bc, &fluid->kbc, scalar, sbc, nullptr, iwalls,
+                                row_begin, row_end, rho, u, conc, as_stream(s), nullptr);
+}
+
+int lbm_ade_stream_collide_mb(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                              const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                              int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
+  if (int rc = ade_fluid_model("lbm_ade_stream_collide_mb", fluid)) return rc;
+  if (fluid->model == LBM_MODEL_BGK)
+    return lbm_ade_stream_collide_w(fn, gn, fo, go, g, bc, &fluid->bgk, scalar, sbc, buoy, iwalls, row_begin, row_end, rho, u,
+                                    conc, s);
+  return ade_kbc_stream_collide("lbm_ade_stream_collide_mb", fn, gn, fo, go, g, bc, &fluid->kbc, scalar, sbc, buoy, iwalls,
                                 row_begin, row_end, rho, u, conc, as_stream(s), nullptr);
 }
 

@@ -84,17 +84,19 @@ int ade_carry_set(const char* fn, AdeCall* call, bool reads, const double* carry
 int ade_open_prime_from(const AdeCall& call, const double* f, hipStream_t st);
 // capi_ade_kbc.hip: the fused step with a KBC fluid (lbm_ade_fluid, model = LBM_MODEL_KBC), under the caller's name fn --
 // the host checks alone (what lbm_ade_solver_create_m asks before it allocates), the collide-only iteration and the step
-// on rows [row_begin, row_end); *launches (if given) += the kernels enqueued
+// on rows [row_begin, row_end); *launches (if given) += the kernels enqueued.  buoy (NULL allowed): the buoyancy of a single
+// block -- beta != (0, 0) takes the forced collision (capi_ade_kbc_buoyant.hip), NULL or beta = (0, 0) the passive launches
 int ade_kbc_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
                      const lbm_ade_params* scalar);
 int ade_kbc_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
                     const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
-                    const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, double* rho, double* u, double* conc,
-                    hipStream_t st, long long* launches);
+                    const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, double* rho,
+                    double* u, double* conc, hipStream_t st, long long* launches);
 int ade_kbc_stream_collide(const char* fn, double* f_new, double* g_new, const double* f_old, const double* g_old,
                            const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
-                           const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int row_begin, int row_end,
-                           double* rho, double* u, double* conc, hipStream_t st, long long* launches);
+                           const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                           int row_begin, int row_end, double* rho, double* u, double* conc, hipStream_t st,
+                           long long* launches);
 // the same with a resolved call: ade_kbc_resolve is ade_resolve for this fluid (slab: as there), and a call it resolved is
 // what ade_part_from and ade_collide_from hand to ade_kbc_part_from / ade_kbc_collide_from -- one dispatch of the part
 // kernel of ade_kbc.hpp (capi_ade_kbc_part.hip) + the interior-wall pass of the part's rows, counted by
@@ -102,7 +104,7 @@ int ade_kbc_stream_collide(const char* fn, double* f_new, double* g_new, const d
 int ade_fluid_model(const char* fn, const lbm_ade_fluid* fluid);
 int ade_kbc_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
                     const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, bool slab,
-                    AdeCall* call);
+                    AdeCall* call, const lbm_ade_buoyancy* buoy = nullptr);
 int ade_kbc_collide_from(const char* fn, const AdeCall& call, double* fp, double* gp, const double* f, const double* h,
                          double* rho, double* u, double* conc, hipStream_t st);
 int ade_kbc_part_from(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old, int part,

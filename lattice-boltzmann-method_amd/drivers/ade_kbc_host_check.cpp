@@ -1,10 +1,12 @@
 // The CPU-reachable half of the fluid + scalar step with a KBC fluid as a stand-alone program: every host-side check of
-// lbm_ade_collide_m, lbm_ade_stream_collide_m and lbm_ade_solver_create_m -- the fluid by model, the KBC parameters, what
+// lbm_ade_collide_m, lbm_ade_stream_collide_m and lbm_ade_solver_create_m, and of their buoyant forms lbm_ade_collide_mb,
+// lbm_ade_stream_collide_mb and lbm_ade_solver_set_buoyancy_m -- the fluid by model, the KBC parameters, what
 // the step refuses with this fluid, the checks it shares with the BGK fluid, and model = BGK answering with the message of
 // the call it forwards to.  Needs no device: every call is refused before a device call (the interior-wall table it
 // builds is empty, whose finalize makes none).  `make san` at the root builds it against the sanitizer build of the
 // library (ASan + UBSan) and runs it; the ordinary build runs it from tests/test_ade_kbc_abi.py.  Exit status 0 = all
 // checks passed.
+#include <cmath>
 #include <cstdio>
 #include <string>
 
@@ -176,6 +178,51 @@ int main() {
             "ring step: NULL ring");
     refused(lbm_ring_ade_collide_m(nullptr, l0, l1, l2, l3, nullptr, &kbc, &sc, nullptr, nullptr), "lbm_ring_ade_collide_m: NULL argument",
             "ring collide: NULL ring");
+  }
+  {  // buoyancy by model, lbm_ade_collide_mb / lbm_ade_stream_collide_mb / lbm_ade_solver_set_buoyancy_m: the descriptor, the fluid
+    const double nan = std::nan(""), inf = HUGE_VAL;
+    auto both = [&](const lbm_ade_fluid* fl, const lbm_bc* bc, const lbm_ade_params* s, const lbm_ade_buoyancy* by, const char* word,
+                    const char* what) {
+      refused(lbm_ade_stream_collide_mb(nullptr, nullptr, nullptr, nullptr, &g, bc, fl, s, nullptr, by, nullptr, 0, 8, nullptr, nullptr,
+                                        nullptr, nullptr), word, what);
+      refused(lbm_ade_collide_mb(nullptr, nullptr, nullptr, nullptr, &g, bc, fl, s, nullptr, by, nullptr, nullptr, nullptr, nullptr), word,
+              what);
+    };
+    const lbm_ade_buoyancy good{1e-2, -5e-3, 0.4, 1.0, 1.0 / 3.0, 1.0 / 9.0};
+    lbm_ade_buoyancy b = good;
+    b.beta_r = nan;
+    both(&kbc, nullptr, &sc, &b, "_mb: buoyancy beta=(nan, -0.005) must be finite", "mb: beta_r = NaN");
+    b = good;
+    b.beta_c = inf;
+    both(&kbc, nullptr, &sc, &b, "_mb: buoyancy beta=(0.01, inf) must be finite", "mb: beta_c = inf");
+    b = good;
+    b.c_ref = nan;
+    both(&kbc, nullptr, &sc, &b, "_mb: buoyancy c_ref=nan must be finite", "mb: c_ref = NaN");
+    b = good;
+    b.u_shift = -inf;
+    both(&kbc, nullptr, &sc, &b, "_mb: buoyancy u_shift=-inf must be finite", "mb: u_shift = -inf");
+    b = good;
+    b.guo_b = nan;
+    both(&kbc, nullptr, &sc, &b, "_mb: buoyancy guo=", "mb: guo_b = NaN (not read for this fluid, still checked)");
+    both(nullptr, nullptr, &sc, &good, "_mb: NULL fluid", "mb: NULL fluid");
+    const lbm_bc pressure{0, 0, 0, 0, 1, 1.0, 1.0, 0.0, 0.0};
+    both(&kbc, &pressure, &sc, &good, "pressure rows", "mb: pressure rows with a KBC fluid");
+    lbm_ade_fluid f = kbc;
+    f.kbc.form = LBM_FORM_REFERENCE_ORDER;
+    const lbm_ade_params fast{1.7, 0.0, 0.0, LBM_FORM_REASSOCIATED};
+    both(&f, nullptr, &fast, &good, "KBC fluid form=1 differs from the scalar form=2", "mb: forms differ");
+    both(&kbc, nullptr, &sc, &good, "_mb: NULL lattice", "mb: a good descriptor is stopped at the lattices");
+    both(&kbc, nullptr, &sc, nullptr, "_mb: NULL lattice", "mb: a NULL descriptor is stopped at the lattices");
+    lbm_ade_fluid bgk{};  // model = BGK: the messages of lbm_ade_stream_collide_w / lbm_ade_collide_b
+    bgk.model = LBM_MODEL_BGK;
+    bgk.bgk = lbm_bgk_params{1.2, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, LBM_FORM_DEFAULT};
+    b = good;
+    b.c_ref = inf;
+    refused(lbm_ade_stream_collide_mb(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &bgk, &sc, nullptr, &b, nullptr, 0, 8, nullptr,
+                                      nullptr, nullptr, nullptr), "lbm_ade_stream_collide_w: buoyancy c_ref=inf", "BGK through stream_collide_mb");
+    refused(lbm_ade_collide_mb(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &bgk, &sc, nullptr, &b, nullptr, nullptr, nullptr, nullptr),
+            "lbm_ade_collide_b: buoyancy c_ref=inf", "BGK through collide_mb");
+    refused(lbm_ade_solver_set_buoyancy_m(nullptr, &good), "lbm_ade_solver_set_buoyancy_m: NULL solver", "set_buoyancy_m: NULL solver");
   }
   std::printf("ade_kbc_host_check: %d refusals checked, %d failures\n", checks, failures);
   return failures ? 1 : 0;

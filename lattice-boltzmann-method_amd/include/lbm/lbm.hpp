@@ -281,25 +281,28 @@ class AdeOpenBoundary {
 // Host arrays in the reference layout.
 class AdeSolver {
  public:
+  // stream: a created stream (lbm_stream_create) for a context whose step() is to be captured in a graph; NULL: the
+  // default stream
   AdeSolver(int R, int C, double omega, double omega_g, double w_r, double w_c, const lbm_bc& bc = BoundarySet(),
-            int form = LBM_FORM_DEFAULT)
+            int form = LBM_FORM_DEFAULT, lbm_stream_t stream = nullptr)
       : R_(R), C_(C) {
     lbm_geom g{R, C, 0, 0, 0};
     const lbm_bgk_params fluid{omega, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, form};
     const lbm_ade_params scalar{omega_g, w_r, w_c, form};
-    check(lbm_ade_solver_create(&h_, &g, &bc, &fluid, &scalar, nullptr));
+    check(lbm_ade_solver_create(&h_, &g, &bc, &fluid, &scalar, stream));
   }
   // the same loop with the entropic KBC collision as the fluid (lbm_ade_fluid, model = LBM_MODEL_KBC): s2 in (0, 2] in
-  // place of omega.  set_buoyancy with a non-zero beta, set_open with a non-empty table and wall_exchange throw on it.
+  // place of omega.  set_buoyancy with a non-zero beta (set_buoyancy_m takes it), set_open with a non-empty table and
+  // wall_exchange throw on it.
   static AdeSolver kbc(int R, int C, double s2, double omega_g, double w_r, double w_c, const lbm_bc& bc = BoundarySet(),
-                       int form = LBM_FORM_DEFAULT) {
+                       int form = LBM_FORM_DEFAULT, lbm_stream_t stream = nullptr) {
     AdeSolver sv(R, C);
     lbm_geom g{R, C, 0, 0, 0};
     lbm_ade_fluid fluid{};
     fluid.model = LBM_MODEL_KBC;
     fluid.kbc = lbm_kbc_params{s2, form};
     const lbm_ade_params scalar{omega_g, w_r, w_c, form};
-    check(lbm_ade_solver_create_m(&sv.h_, &g, &bc, &fluid, &scalar, nullptr));
+    check(lbm_ade_solver_create_m(&sv.h_, &g, &bc, &fluid, &scalar, stream));
     return sv;
   }
   AdeSolver(AdeSolver&& o) noexcept : h_(o.h_), R_(o.R_), C_(o.C_) { o.h_ = nullptr; }
@@ -319,6 +322,9 @@ class AdeSolver {
   // the scalar pushes on the fluid from the next step on: F = beta (C - c_ref) per node (lbm_ade_buoyancy; beta = (0, 0)
   // is the passive scalar).  state().u stays calc_u(f, rho): the equilibria take u + u_shift F.
   void set_buoyancy(const lbm_ade_buoyancy& b) { check(lbm_ade_solver_set_buoyancy(h_, &b)); }
+  // the same for either fluid (lbm_ade_solver_set_buoyancy_m): on a context made by kbc() the forced KBC collision --
+  // kbc::collide on the held moments (rho, u0 + u_shift F); guo_a, guo_b are not read; on a BGK context set_buoyancy itself
+  void set_buoyancy_m(const lbm_ade_buoyancy& b) { check(lbm_ade_solver_set_buoyancy_m(h_, &b)); }
   // interior walls from the next stream on (a finalized table, borrowed: it must outlive the solver); clear_walls: none
   void set_walls(const AdeInteriorWalls& w) { check(lbm_ade_solver_set_walls(h_, w.handle())); }
   void clear_walls() { check(lbm_ade_solver_set_walls(h_, nullptr)); }

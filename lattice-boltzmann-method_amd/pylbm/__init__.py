@@ -109,7 +109,8 @@ class AdeParams(ct.Structure):
 
 class AdeFluid(ct.Structure):
     """lbm_ade_fluid: the fluid of the fluid + scalar step by model -- AdeFluid(BgkParams(...)) or AdeFluid(KbcParams(...));
-    what lbm_ade_collide_m, lbm_ade_stream_collide_m and lbm_ade_solver_create_m take"""
+    what lbm_ade_collide_m, lbm_ade_stream_collide_m, their buoyant forms lbm_ade_collide_mb / lbm_ade_stream_collide_mb and
+    lbm_ade_solver_create_m take"""
     _fields_ = [("model", ct.c_int), ("bgk", BgkParams), ("kbc", KbcParams)]
 
     def __init__(self, params=None, model=None):
@@ -529,8 +530,8 @@ class AdeSolver:
                 self.set_open(open)
             if scalar_bc is not None:
                 self.set_scalar_bc(scalar_bc)
-            if buoyancy is not None:
-                self.set_buoyancy(buoyancy)
+            if buoyancy is not None:  # by model: a KBC fluid takes the forced collision of set_buoyancy_m
+                (self.set_buoyancy_m if isinstance(fluid, (KbcParams, AdeFluid)) else self.set_buoyancy)(buoyancy)
         except LbmError:
             self.close()
             raise
@@ -543,6 +544,12 @@ class AdeSolver:
     def set_buoyancy(self, buoyancy):
         """the scalar's force on the fluid from the next step on (AdeBuoyancy, or None: the passive scalar)"""
         self.lib.ade_solver_set_buoyancy(self.h, ct.byref(buoyancy) if buoyancy is not None else None)
+        self.buoyancy = buoyancy
+
+    def set_buoyancy_m(self, buoyancy):
+        """set_buoyancy for either fluid (lbm_ade_solver_set_buoyancy_m): with a KBC fluid the forced KBC collision --
+        kbc::collide on the held moments (rho, u0 + u_shift F), guo not read; with a BGK fluid set_buoyancy itself"""
+        self.lib.ade_solver_set_buoyancy_m(self.h, ct.byref(buoyancy) if buoyancy is not None else None)
         self.buoyancy = buoyancy
 
     def set_walls(self, walls):

@@ -27,6 +27,10 @@ and against the single-step BGK launch, on one periodic box, in one process, alt
   the form, 432 B per node where the fused step moves 288 B.  All start from the reference KBC driver's state
   (lbm_kbc_equilibrium without the u^2 terms) on a drifting shear wave: a lattice exactly at equilibrium makes KBC's
   gamma 0/0.  ms per step of every repeat, the condition (b) < (a) + (c) per repeat, (b) / (a), the algorithmic TB/s of (b)
+  --kbc --buoyancy adds to that mode, in the same process and alternated with the rest: kbc_pair_buoyant, the pair step with
+  the forced KBC collision (lbm_ade_solver_set_buoyancy_m, beta = (0.5, -0.3), c_ref = 5e-4, u_shift = 1; the reference order),
+  and bgk_pair_buoyant, the BGK buoyant pair step (Guo's coefficients); under "buoyant": the condition kbc_pair_buoyant < bgk_pair + kbc_single_ref
+  per repeat, and kbc_pair_buoyant over the passive reference-order kbc_pair_ref and over bgk_pair_buoyant
 MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
 (18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
 usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls] [--buoyancy]
@@ -125,6 +129,12 @@ def kbc_bench(lib, a, rho, conc, u, st, timed):
     for name, form in forms.items():
         solvers["kbc_pair_" + name] = pylbm.AdeSolver(lib, R, C, pylbm.KbcParams(s2, form), pylbm.AdeParams(1.7, W, form=form),
                                                       stream=st.value)
+    if a.buoyancy:
+        ref = forms["ref"]
+        solvers["kbc_pair_buoyant"] = pylbm.AdeSolver(lib, R, C, pylbm.KbcParams(s2, ref), pylbm.AdeParams(1.7, W, form=ref),
+                                                      stream=st.value, buoyancy=pylbm.AdeBuoyancy((0.5, -0.3), 5e-4, 1.0))
+        solvers["bgk_pair_buoyant"] = pylbm.AdeSolver(lib, R, C, pylbm.BgkParams(1.2, 0), pylbm.AdeParams(1.7, W), stream=st.value,
+                                                      buoyancy=pylbm.AdeBuoyancy((0.5, -0.3), 5e-4, 0.5, (3.0, 9.0)))
     for sv in solvers.values():
         fc, gc, _, _, sg = sv.lattices()
         lib.lattice_copy_rows(_ptr(fc), ct.byref(sg), 0, _ptr(f), ct.byref(dg), 0, R, st)
@@ -168,6 +178,13 @@ def kbc_bench(lib, a, rho, conc, u, st, timed):
                      "a_plus_c_ms": [round(y + z, 4) for y, z in zip(ms["bgk_pair"], c)],
                      "b_over_a": [round(x / y, 3) for x, y in zip(b, ms["bgk_pair"])],
                      "b_algorithmic_tbs": round(288.0 * n / (statistics.median(b) * 1e-3) / 1e12, 3)}
+    if a.buoyancy:
+        x, p, bb, sgl = ms["kbc_pair_buoyant"], ms["kbc_pair_ref"], ms["bgk_pair_buoyant"], ms["kbc_single_ref"]
+        out["buoyant"] = {"a_lt_bgk_pair_plus_kbc_single_ref_per_repeat": [v < y + z for v, y, z in zip(x, ms["bgk_pair"], sgl)],
+                          "bgk_pair_plus_kbc_single_ref_ms": [round(y + z, 4) for y, z in zip(ms["bgk_pair"], sgl)],
+                          "a_over_passive_ref": [round(v / y, 3) for v, y in zip(x, p)],
+                          "a_over_bgk_buoyant": [round(v / y, 3) for v, y in zip(x, bb)],
+                          "a_algorithmic_tbs": round(288.0 * n / (statistics.median(x) * 1e-3) / 1e12, 3)}
     for sv in solvers.values():
         sv.close()
     return out
