@@ -40,18 +40,20 @@ struct AdeFastModel {
     const double us = vx + vy, ud = vx - vy;
     const double base = 1.0 - 1.5 * (vx * vx + vy * vy);
     const double r1 = ow1 * conc, r5 = ow5 * conc;
-    const double E1 = r1 * (base + 4.5 * vx * vx), E2 = r1 * (base + 4.5 * vy * vy);
-    const double E5 = r5 * (base + 4.5 * us * us), E6 = r5 * (base + 4.5 * ud * ud);
-    const double O1 = 3.0 * r1 * vx, O2 = 3.0 * r1 * vy, O5 = 3.0 * r5 * us, O8 = 3.0 * r5 * ud;
+    // even part shared by a pair, the odd part joined before the scaling: BgkFastModel's order (d2q9.hpp) and its reason
+    const double S1 = base + 4.5 * vx * vx, S2 = base + 4.5 * vy * vy;
+    const double S5 = base + 4.5 * us * us, S6 = base + 4.5 * ud * ud;
+    const double A1 = S1 + 3.0 * vx, A3 = S1 - 3.0 * vx, A2 = S2 + 3.0 * vy, A4 = S2 - 3.0 * vy;
+    const double A5 = S5 + 3.0 * us, A7 = S5 - 3.0 * us, A8 = S6 + 3.0 * ud, A6 = S6 - 3.0 * ud;
     g[0] = keep * g[0] + (ow0 * conc) * base;
-    g[1] = keep * g[1] + (E1 + O1);
-    g[3] = keep * g[3] + (E1 - O1);
-    g[2] = keep * g[2] + (E2 + O2);
-    g[4] = keep * g[4] + (E2 - O2);
-    g[5] = keep * g[5] + (E5 + O5);
-    g[7] = keep * g[7] + (E5 - O5);
-    g[8] = keep * g[8] + (E6 + O8);
-    g[6] = keep * g[6] + (E6 - O8);
+    g[1] = keep * g[1] + r1 * A1;
+    g[3] = keep * g[3] + r1 * A3;
+    g[2] = keep * g[2] + r1 * A2;
+    g[4] = keep * g[4] + r1 * A4;
+    g[5] = keep * g[5] + r5 * A5;
+    g[7] = keep * g[7] + r5 * A7;
+    g[8] = keep * g[8] + r5 * A8;
+    g[6] = keep * g[6] + r5 * A6;
   }
 };
 

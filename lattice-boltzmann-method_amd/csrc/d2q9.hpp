@@ -301,9 +301,19 @@ struct BgkModelT {
   }
 };
 
+// 1 / x to rounding for the reassociated collisions.  v_rcp_f64 delivers a single-precision seed r0 (error e = 1 - x r0
+// of about 2^-24); one Newton step would only square that (2^-48: 32 units in the last place of 1 / rho, several units
+// of u = j / rho at Mach 0.25).  1 / x = r0 (1 + e + e^2 + ...) cut after e^2 leaves e^3 < 2^-72: three FMAs, and the
+// result is within one rounding of 1 / x.
+__device__ __forceinline__ double rcp_f64(double x) {
+  const double r0 = __builtin_amdgcn_rcp(x);
+  const double e = __builtin_fma(-x, r0, 1.0);
+  return __builtin_fma(r0, __builtin_fma(e, e, e), r0);
+}
+
 // The compressible BGK collision reassociated (opt-in, tuning "bgk_fast" = 1; the models above
 // follow solver.cpp operation by operation and are bit-identical to the oracle): pairwise moment
-// sums, u = j * (1/rho) with v_rcp_f64 + one Newton step instead of two IEEE divisions, the
+// sums, u = j * (1/rho) with rcp_f64 (v_rcp_f64 + three FMAs) instead of two IEEE divisions, the
 // equilibrium split into its parts even / odd under c -> -c, relaxation as f + omega (feq - f),
 // FMA contraction per expression (identical in every kernel it is inlined into).  ~75 f64
 // operations per node instead of ~130; agreement with the reference order to rounding.
@@ -317,27 +327,31 @@ struct BgkFastModel {
     const double e57 = f[5] - f[7], e68 = f[6] - f[8];
     rho = (f[0] + a) + (b + (d57 + d68));
     const double jx = (f[1] - f[3]) + (e57 - e68), jy = (f[2] - f[4]) + (e57 + e68);
-    double ir = __builtin_amdgcn_rcp(rho);
-    ir = __builtin_fma(ir, __builtin_fma(-rho, ir, 1.0), ir);
+    const double ir = rcp_f64(rho);
     ux = jx * ir;
     uy = jy * ir;
     const double us = ux + uy, ud = ux - uy;
     const double base = 1.0 - 1.5 * (ux * ux + uy * uy);
-    // relaxation as (1 - omega) f + omega feq with omega folded into the weights: one add + one FMA
-    // per population instead of two adds + one FMA for f + omega (feq - f)
+    // relaxation as (1 - omega) f + omega feq with omega folded into the weights: one FMA per population
+    // instead of two adds + one FMA for f + omega (feq - f).  The part of the equilibrium even under c -> -c,
+    // S = base + 4.5 (c.u)^2, is shared by a pair; the odd part joins it BEFORE the scaling by omega w rho,
+    // A+- = S +- 3 c.u in one FMA each, so the cancellation of an upwind population at Mach 0.25 (S = 1.45,
+    // 3 c.u = -1.05) rounds once at the size of its result (scaling the parts first, E = r S, O = 3 r c.u,
+    // E +- O, would round five times at the size of E, 3.6 x the result's, and cost two more multiplications).
     const double r1 = ow1 * rho, r5 = ow5 * rho;
-    const double E1 = r1 * (base + 4.5 * ux * ux), E2 = r1 * (base + 4.5 * uy * uy);
-    const double E5 = r5 * (base + 4.5 * us * us), E6 = r5 * (base + 4.5 * ud * ud);
-    const double O1 = 3.0 * r1 * ux, O2 = 3.0 * r1 * uy, O5 = 3.0 * r5 * us, O8 = 3.0 * r5 * ud;
+    const double S1 = base + 4.5 * ux * ux, S2 = base + 4.5 * uy * uy;
+    const double S5 = base + 4.5 * us * us, S6 = base + 4.5 * ud * ud;
+    const double A1 = S1 + 3.0 * ux, A3 = S1 - 3.0 * ux, A2 = S2 + 3.0 * uy, A4 = S2 - 3.0 * uy;
+    const double A5 = S5 + 3.0 * us, A7 = S5 - 3.0 * us, A8 = S6 + 3.0 * ud, A6 = S6 - 3.0 * ud;
     f[0] = keep * f[0] + (ow0 * rho) * base;
-    f[1] = keep * f[1] + (E1 + O1);
-    f[3] = keep * f[3] + (E1 - O1);
-    f[2] = keep * f[2] + (E2 + O2);
-    f[4] = keep * f[4] + (E2 - O2);
-    f[5] = keep * f[5] + (E5 + O5);
-    f[7] = keep * f[7] + (E5 - O5);
-    f[8] = keep * f[8] + (E6 + O8);
-    f[6] = keep * f[6] + (E6 - O8);
+    f[1] = keep * f[1] + r1 * A1;
+    f[3] = keep * f[3] + r1 * A3;
+    f[2] = keep * f[2] + r1 * A2;
+    f[4] = keep * f[4] + r1 * A4;
+    f[5] = keep * f[5] + r5 * A5;
+    f[7] = keep * f[7] + r5 * A7;
+    f[8] = keep * f[8] + r5 * A8;
+    f[6] = keep * f[6] + r5 * A6;
   }
 };
 

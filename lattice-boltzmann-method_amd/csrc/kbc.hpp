@@ -148,7 +148,9 @@ struct KbcModel {
 //    1 / D: X_i ~ w_i x the other two D of its axis, no reciprocal -- 2 reciprocals per node instead of 8.
 // Round 4: 189 f64 operations + 2 v_rcp_f64 per collision (235 + 3 before): the k22 central moment is folded into H~_0, the
 // weights of gamma's sums need no reciprocal, the final update forms S~ + gamma H~ first.
-// Agreement with the reference-order model to rounding (tests/test_gpu_kbc.py states the tolerance).
+// Both reciprocals (1 / rho, 1 / den) are carried to rounding (rcp_f64, d2q9.hpp: one FMA each more than a single Newton step).
+// Agreement with the reference-order model to rounding: per population within 1.5 x the reference order's own error against
+// 80-bit arithmetic (tests/test_gpu_collision_accuracy.py); tests/test_gpu_kbc.py states the field-norm tolerances.
 struct KbcFastModel {
   double s2, is2, hs2, qs2;  // is2 = 1 / s2 (one IEEE division on the host instead of one per node); s2 / 2, s2 / 4
   __host__ __device__ explicit KbcFastModel(double s) : s2(s), is2(1.0 / s), hs2(0.5 * s), qs2(0.25 * s) {}
@@ -158,10 +160,7 @@ struct KbcFastModel {
   // 31 ps per node (2 steps: 0.53 ms, 3 steps: 0.59 ms = 85 k instead of 77.5 k MLUPS; profiles/r04_kbc_strip_width.txt)
   static constexpr bool kFullStrips = false;  // d2q9.hpp sw_strip_width
 
-  __device__ __forceinline__ static double rcp(double x) {
-    const double r = __builtin_amdgcn_rcp(x);
-    return __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
-  }
+  __device__ __forceinline__ static double rcp(double x) { return rcp_f64(x); }  // d2q9.hpp: to rounding
 
   __device__ __forceinline__ void collide(double (&f)[Q], double& rho, double& ux, double& uy) const {
     // contract(on): products feeding a sum IN THE SAME EXPRESSION become FMAs, decided by the front

@@ -192,7 +192,9 @@ def test_the_fluid_is_the_existing_bgk_fluid(lib, oracle, form, walls):
 
 def test_reassociated_form_agrees_with_the_reference_order(lib, oracle):
     """500 iterations, stated tolerance 1e-10 relative (to the field's largest magnitude), fixed before measuring.
-    Measured on MI355X: f 6.1e-14, g 1.3e-13, rho 6.0e-14, u 7.3e-13, C 1.3e-13."""
+    Measured on MI355X: f 6.1e-14, g 1.3e-13, rho 6.0e-14, u 7.3e-13, C 1.3e-13.  This guards the trajectory; the accuracy
+    of one collision of either half is bounded per population in units in the last place by
+    tests/test_gpu_collision_accuracy.py."""
     R, C = 128, 192
     bc = pylbm.Bc(row_lo=pylbm.EDGE_BOUNCE_BACK, row_hi=pylbm.EDGE_BOUNCE_BACK)
     f0, g0 = initial_state(oracle, R, C, seed=11)

@@ -33,7 +33,10 @@ def lib():
 #   fast             (the default) d2q9.hpp BgkFastModel -- reciprocal instead of two divisions,
 #                    equilibrium split into even / odd parts, FMA per expression: stated tolerance
 #                    1e-12 relative (L2 over the field) against the oracle for the <= 100 steps
-#                    these tests run (north star: rho, u within 1e-6 for BGK).
+#                    these tests run (north star: rho, u within 1e-6 for BGK).  That field norm guards the
+#                    trajectories; the accuracy of one collision is stated per population in units in the last
+#                    place, against 80-bit arithmetic and the reference order's own error:
+#                    tests/test_gpu_collision_accuracy.py.
 # Incompressible / delta-form / forced models and lattices with pressure rows always run in the
 # reference order, so their comparisons stay bitwise in both modes.
 _MODE = {"fast": False}

@@ -30,7 +30,9 @@ def mode(request, lib):
     """reference_order: kbc.hpp KbcModel, -ffp-contract=off: BITWISE vs the oracle.
     fast (the default): KbcFastModel, same mathematics reassociated (raw-moment butterfly, one
     back-transform per part, product-form equilibrium, reciprocals, FMA): stated tolerance 1e-12
-    relative (L2 over the field) for <= 20 steps, 1e-10 for <= 500 steps."""
+    relative (L2 over the field) for <= 20 steps, 1e-10 for <= 500 steps.  Those field norms guard the trajectories;
+    the accuracy of one collision is stated per population in units in the last place, against 80-bit arithmetic and
+    the reference order's own error: tests/test_gpu_collision_accuracy.py."""
     lib.set_tuning(b"kbc_fast", 1 if request.param == "fast" else 0)
     yield request.param
     lib.set_tuning(b"kbc_fast", -1)
