@@ -1,6 +1,7 @@
-// The resolved call of the fused fluid + scalar step and what its launch sites share: for the translation units that
-// launch ade.hpp's kernels (capi_ade.hip: the BGK fluid; capi_ade_kbc.hip: the KBC fluid).  Every other unit keeps a call
-// in an AdeCallBuf (internal.hpp) and never sees its members.
+// The resolved call of the fused fluid + scalar step: for the four translation units that launch ade.hpp's kernels
+// (capi_ade.hip: the BGK fluid and every host check; capi_ade_kbc.hip, capi_ade_kbc_part.hip, capi_ade_kbc_buoyant.hip: the
+// KBC fluid), which share their launch path in ade_launch.hpp.  Every other unit keeps a call in an AdeCallBuf
+// (internal.hpp) and never sees its members.
 #pragma once
 #include <type_traits>
 
@@ -9,8 +10,9 @@
 
 namespace lbm {
 
-// One call of the fused step after its host checks: the device copies that every launch of the call takes.  fluid and
-// scalar are borrowed for the call (with_ade_models picks the models per launch).
+// One call of the fused step after its host checks (ade_resolve): the device copies that every launch of the call takes.
+// The fluid -- exactly one of fluid, kbc -- and scalar are borrowed for the call (with_ade_models / with_ade_kbc_models
+// pick the models per launch).
 struct AdeCall {
   Geom g;
   Bc bc;
@@ -20,8 +22,8 @@ struct AdeCall {
   const AdeIwallNode* wall_nodes;
   int n_wall_nodes;
   const int* wall_first;  // host: the table's row index (R + 1 entries), NULL without nodes
-  const lbm_bgk_params* fluid;
-  const lbm_kbc_params* kbc;  // a KBC fluid (ade_kbc_resolve): the launches are capi_ade_kbc(_part).hip's; NULL for a BGK fluid
+  const lbm_bgk_params* fluid;  // a BGK fluid: the launches are capi_ade.hip's; NULL for a KBC fluid
+  const lbm_kbc_params* kbc;    // a KBC fluid: the launches are capi_ade_kbc(_part, _buoyant).hip's; NULL for a BGK fluid
   const lbm_ade_params* scalar;
   const AdeOpenNode* open_nodes;  // the open-boundary table (lbm_ade_open), NULL without nodes
   const AdeOpenSeg* open_segs;
@@ -42,9 +44,5 @@ inline AdeRanges ade_row_ranges(const int* first, int band0, int n0, int band1, 
   const int first0 = first[band0], w0 = first[band0 + n0] - first0, first1 = first[band1];
   return AdeRanges{first0, w0, first1, w0 + (n0 < nrows ? first[band1 + nrows - n0] - first1 : 0)};
 }
-
-// the lattice and field arguments of a launch (capi_ade.hip)
-int ade_lattice_args(const char* fn, const double* fn_, const double* gn, const double* fo, const double* go,
-                     const double* rho, const double* u, const double* conc, bool distinct);
 
 }  // namespace lbm

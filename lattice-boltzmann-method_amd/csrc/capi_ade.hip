@@ -1,6 +1,9 @@
 // C ABI, fluid + transported scalar: the compressible BGK fluid f and the advection-diffusion scalar g of
 // test/rectangle_sedimentation_test.cpp:88-247 in one fused pull step per node (ade.hpp), and the solver
-// context that runs the driver loop on one block.
+// context that runs the driver loop on one block.  Every host check of the step is here, for either fluid (ade_resolve:
+// the fluid is an AdeFluid, a BGK parameter block or a KBC one), and every entry point, the `_m` / `_mb` ones included; a
+// resolved call is launched by its fluid (ade_step_from, ade_part_from, ade_collide_from) -- the BGK fluid's kernels from
+// here, the KBC fluid's from the three capi_ade_kbc*.hip units, all through the one launch path of ade_launch.hpp.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -12,7 +15,7 @@
 #include <utility>
 #include <vector>
 
-#include "ade_call.hpp"
+#include "ade_launch.hpp"
 #include "ade_plain.hpp"
 
 // Interior walls of the fused step: a host table of wall nodes, merged per node and kept sorted by (r, c) while it is
@@ -83,12 +86,38 @@ static const char* edge_name(int m) {
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-// Everything the fused step accepts, checked on the host before any device call.  Single block (slab = false): ghost
+// The BGK fluid's own parameters: where ade_validate asks, between the edges and the scalar's parameters
+static int ade_bgk_fluid_check(const char* fn, const lbm_bgk_params* fluid) {
+  LBM_REQUIRE(fluid, "%s: NULL fluid params", fn);
+  LBM_REQUIRE(fluid->omega > 0.0 && fluid->omega < 2.0, "%s: omega=%g outside (0, 2)", fn, fluid->omega);
+  LBM_REQUIRE(fluid->incompressible == 0, "%s: incompressible=%d: the fluid is the compressible BGK model", fn,
+              fluid->incompressible);
+  LBM_REQUIRE(fluid->force_mode == 0, "%s: force_mode=%d: no body force in the fluid + scalar step", fn,
+              fluid->force_mode);
+  LBM_REQUIRE(fluid->delta_form == 0, "%s: delta_form=%d not supported by the fluid + scalar step", fn, fluid->delta_form);
+  LBM_REQUIRE(fluid->form >= LBM_FORM_DEFAULT && fluid->form <= LBM_FORM_REASSOCIATED, "%s: fluid form=%d (LBM_FORM_*)",
+              fn, fluid->form);
+  return LBM_OK;
+}
+
+// The KBC fluid's own parameters, as lbm_kbc_* checks them, and what the step cannot do with this fluid: the first checks
+// of a call with a KBC fluid, before ade_resolve looks at anything else
+static int ade_kbc_fluid_check(const char* fn, const lbm_kbc_params* kbc, const lbm_bc* bc) {
+  LBM_REQUIRE(kbc->s2 > 0.0 && kbc->s2 <= 2.0, "%s: KBC fluid: s2=%g outside (0, 2]", fn, kbc->s2);
+  LBM_REQUIRE(kbc->form >= LBM_FORM_DEFAULT && kbc->form <= LBM_FORM_REASSOCIATED, "%s: KBC fluid: form=%d (LBM_FORM_*)", fn,
+              kbc->form);
+  LBM_REQUIRE(!(bc && bc->pressure_rows), "%s: pressure rows (pressure_rows=%d) are not supported by the fluid + scalar "
+              "step with a KBC fluid", fn, bc ? bc->pressure_rows : 0);
+  return LBM_OK;
+}
+
+// Everything the fused step accepts but the KBC fluid's own parameters (ade_kbc_fluid_check, before this), checked on the
+// host before any device call.  Single block (slab = false): ghost
 // 0, rows PERIODIC or BOUNCE_BACK.  Slab (the part launches and the ring): ghost 0 with PERIODIC or BOUNCE_BACK rows, or
 // ghost >= 1 with HALO or BOUNCE_BACK rows -- ghost rows are read where a row edge is HALO and nothing wraps.  Columns:
 // PERIODIC, BOUNCE_BACK or SPECULAR.  The scalar takes the fluid's fix-up at every wall.
-static int ade_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
-                        const lbm_ade_params* scalar, bool slab = false) {
+static int ade_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, const AdeFluid& fluid,
+                        const lbm_ade_params* scalar, bool slab) {
   LBM_REQUIRE(g, "%s: NULL geometry", fn);
   LBM_REQUIRE(g->R >= 1 && g->C >= 1, "%s: R=%d C=%d must be positive", fn, g->R, g->C);
   if (slab) LBM_REQUIRE(g->ghost >= 0 && g->ghost <= 15, "%s: ghost=%d must be 0..15", fn, g->ghost);
@@ -124,21 +153,14 @@ static int ade_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, con
     LBM_REQUIRE(col_ok(bc->col_hi), "%s: column edge mode %s (%d) not supported (PERIODIC, BOUNCE_BACK or SPECULAR)",
                 fn, edge_name(bc->col_hi), bc->col_hi);
   }
-  LBM_REQUIRE(fluid, "%s: NULL fluid params", fn);
-  LBM_REQUIRE(fluid->omega > 0.0 && fluid->omega < 2.0, "%s: omega=%g outside (0, 2)", fn, fluid->omega);
-  LBM_REQUIRE(fluid->incompressible == 0, "%s: incompressible=%d: the fluid is the compressible BGK model", fn,
-              fluid->incompressible);
-  LBM_REQUIRE(fluid->force_mode == 0, "%s: force_mode=%d: no body force in the fluid + scalar step", fn,
-              fluid->force_mode);
-  LBM_REQUIRE(fluid->delta_form == 0, "%s: delta_form=%d not supported by the fluid + scalar step", fn, fluid->delta_form);
-  LBM_REQUIRE(fluid->form >= LBM_FORM_DEFAULT && fluid->form <= LBM_FORM_REASSOCIATED, "%s: fluid form=%d (LBM_FORM_*)",
-              fn, fluid->form);
+  if (!fluid.kbc)
+    if (int rc = ade_bgk_fluid_check(fn, fluid.bgk)) return rc;
   LBM_REQUIRE(scalar, "%s: NULL scalar params", fn);
   LBM_REQUIRE(scalar->omega_g > 0.0 && scalar->omega_g < 2.0, "%s: omega_g=%g outside (0, 2)", fn, scalar->omega_g);
   LBM_REQUIRE(scalar->form >= LBM_FORM_DEFAULT && scalar->form <= LBM_FORM_REASSOCIATED,
               "%s: scalar form=%d (LBM_FORM_*)", fn, scalar->form);
-  LBM_REQUIRE(fluid->form == LBM_FORM_DEFAULT || fluid->form == scalar->form,
-              "%s: fluid form=%d differs from the scalar form=%d (lbm_ade_params.form sets both halves)", fn, fluid->form,
+  LBM_REQUIRE(fluid.kbc || fluid.bgk->form == LBM_FORM_DEFAULT || fluid.bgk->form == scalar->form,
+              "%s: fluid form=%d differs from the scalar form=%d (lbm_ade_params.form sets both halves)", fn, fluid.bgk->form,
               scalar->form);
   return LBM_OK;
 }
@@ -181,7 +203,7 @@ static int with_ade_models(const lbm_bgk_params* fluid, const lbm_ade_params* sc
 
 // The lattice and field arguments of a launch: four lattices given (distinct: also pairwise different and 16-byte
 // aligned -- the collide-only launch reads and writes node by node and asks for neither); rho, u, conc all or none.
-int ade_lattice_args(const char* fn, const double* fn_, const double* gn, const double* fo, const double* go,
+static int ade_lattice_args(const char* fn, const double* fn_, const double* gn, const double* fo, const double* go,
                             const double* rho, const double* u, const double* conc, bool distinct) {
   LBM_REQUIRE(fn_ && gn && fo && go, "%s: NULL lattice", fn);
   if (distinct) {
@@ -388,20 +410,41 @@ static int ade_open_check(const char* fn, const lbm_ade_open* t, const lbm_geom*
   return LBM_OK;
 }
 
-// The host checks of a call, once, under the caller's name: the scalar's walls first (a FIXED edge names the edge mode it
-// cannot sit on), geometry and parameters, buoyancy, interior walls.  An entry checks its lattices and range or part after.
-int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
-                const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
-                const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call, const lbm_ade_open* open) {
-  int rc = ade_scalar_bc_check(fn, sbc, lbc, &call->sw);
+// the fluid of an `_m` entry: given, its model BGK or KBC; *out: the parameter block of that model
+int ade_fluid_model(const char* fn, const lbm_ade_fluid* fluid, AdeFluid* out) {
+  LBM_REQUIRE(fluid, "%s: NULL fluid (lbm_ade_fluid)", fn);
+  LBM_REQUIRE(fluid->model == LBM_MODEL_BGK || fluid->model == LBM_MODEL_KBC,
+              "%s: fluid model=%d (LBM_MODEL_BGK or LBM_MODEL_KBC)", fn, fluid->model);
+  *out = fluid->model == LBM_MODEL_KBC ? AdeFluid{nullptr, &fluid->kbc} : AdeFluid{&fluid->bgk, nullptr};
+  return LBM_OK;
+}
+
+// The host checks of a call with either fluid, once, under the caller's name: a KBC fluid's own parameters; the scalar's
+// walls (a FIXED edge names the edge mode it cannot sit on), geometry and parameters -- a BGK fluid's among them --
+// buoyancy, interior walls; a KBC fluid's form against the scalar's; the open table.  An entry checks its lattices and range
+// or part after.  The order is observable (a call with two faults reports the first) and differs per fluid.
+int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const AdeFluid& fluid, const lbm_ade_params* scalar,
+                const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, bool slab,
+                AdeCall* call, const lbm_ade_open* open) {
+  const lbm_kbc_params* kbc = fluid.kbc;
+  int rc = kbc ? ade_kbc_fluid_check(fn, kbc, lbc) : LBM_OK;
+  if (!rc) rc = ade_scalar_bc_check(fn, sbc, lbc, &call->sw);
   if (!rc) rc = ade_validate(fn, lg, lbc, fluid, scalar, slab);
   if (!rc) rc = ade_buoyancy_check(fn, buoy, &call->by, &call->buoyant);
   if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &call->wall_nodes, &call->n_wall_nodes, &call->wall_first);
   if (rc) return rc;
+  if (kbc) {
+    // (no public call reaches this line: the ring's `_m` entries and the `_m` part entry have no parameter for buoyancy)
+    LBM_REQUIRE(!(slab && call->buoyant), "%s: buoyancy on a slab is not supported with a KBC fluid (the forced KBC collision "
+                "runs on a single block)", fn);
+    LBM_REQUIRE(kbc->form == LBM_FORM_DEFAULT || kbc->form == scalar->form,
+                "%s: KBC fluid form=%d differs from the scalar form=%d (lbm_ade_params.form sets both halves)", fn, kbc->form,
+                scalar->form);
+  }
   call->g = make_geom(*lg);
   call->bc = make_bc(lbc);
-  call->fluid = fluid;
-  call->kbc = nullptr;
+  call->fluid = fluid.bgk;
+  call->kbc = kbc;
   call->scalar = scalar;
   call->open_nodes = nullptr;
   call->open_segs = nullptr;
@@ -412,86 +455,41 @@ int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const lbm
   if (!open) return LBM_OK;
   rc = ade_open_check(fn, open, lg, ade_scalar_gather_bc(call->bc, call->sw.fixed), call->n_wall_nodes > 0 ? iwalls : nullptr,
                       &call->open_nodes, &call->open_segs, &call->n_open_nodes, slab, &call->bc, call->sw.fixed);
-  if (!rc && call->n_open_nodes > 0) call->open_first = open->first.data();
-  return rc;
-}
-
-template <bool B, class FM, class SM>
-static int ade_collide_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fp, double* gp, const double* f,
-                              const double* h, double* rho, double* u, double* conc, hipStream_t st) {
-  const long n = (long)k.g.R * k.g.C;
-  const int grid = capped_grid((n + 255) / 256);
-  with_flags([&](auto M) { LBM_KLAUNCH((k_ade_collide<FM, SM, M(), B>), dim3(grid), dim3(256), 0, st, fp, gp, f, h, k.g, fm, sm, rho, u, conc, k.by); }, rho != nullptr);
-  LBM_CHECK_LAUNCH();
+  if (rc) return rc;
+  // (nor this one: no `_m` entry has a parameter for a table, and lbm_ade_solver_set_open refuses a KBC context)
+  LBM_REQUIRE(!(kbc && call->n_open_nodes > 0), "%s: open boundaries (a table of %d nodes) are not supported with a KBC fluid",
+              fn, call->n_open_nodes);
+  if (call->n_open_nodes > 0) call->open_first = open->first.data();
   return LBM_OK;
 }
 
-// The two table passes of a launch over the rows of ade_row_ranges, behind the dispatch whose nodes they overwrite and on
-// the same stream: the open table's listed nodes of those rows, then the interior walls' -- one lane per node, one
-// dispatch per table; rows without a node of a table enqueue nothing for it.  *launches += the kernels enqueued
+// The open-table pass of the rows `r` (ade_row_ranges), behind the dispatch whose nodes it overwrites and on the same
+// stream: one lane per listed node; rows without one enqueue nothing.  The one launch site of k_ade_open_ranges, which
+// exists with the BGK fluid alone.  *launches += the kernels enqueued
 template <bool B, class FM, class SM>
-static int ade_table_passes(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
-                            const double* go, int band0, int n0, int band1, int nrows, double* rho, double* u,
-                            double* conc, hipStream_t st, long long* launches) {
-  const bool mom = rho != nullptr;
-  if (k.n_open_nodes > 0) {
-    const AdeRanges a = ade_row_ranges(k.open_first, band0, n0, band1, nrows);
-    if (a.w > 0) {
-      with_flags([&](auto M, auto F) {
-        LBM_KLAUNCH((k_ade_open_ranges<FM, SM, M(), F(), B>), dim3((a.w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, k.g,
-                    k.bc, fm, sm, rho, u, conc, k.sw, k.by, k.open_nodes, k.open_segs, a.first0, a.w0, a.first1, a.w,
-                    k.carry_in, k.carry_out);
-      }, mom, k.sw.fixed);
-      LBM_CHECK_LAUNCH();
-      ++*launches;
-    }
-  }
-  if (k.n_wall_nodes > 0) {
-    const AdeRanges a = ade_row_ranges(k.wall_first, band0, n0, band1, nrows);
-    if (a.w > 0) {
-      with_flags([&](auto M, auto F) {
-        LBM_KLAUNCH((k_ade_iwalls_ranges<FM, SM, M(), F(), B>), dim3((a.w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go,
-                    k.g, k.bc, fm, sm, rho, u, conc, k.sw, k.by, k.wall_nodes, a.first0, a.w0, a.first1, a.w);
-      }, mom, k.sw.fixed);
-      LBM_CHECK_LAUNCH();
-      ++*launches;
-    }
-  }
-  return LBM_OK;
-}
-
-// interior launch + (walls only) the edge pass + the table passes of rows [row_begin, row_end) (one range of each table);
-// *launches (if given) += the kernels enqueued
-template <bool B, class FM, class SM>
-static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
-                           const double* go, int row_begin, int row_end, double* rho, double* u, double* conc,
-                           hipStream_t st, long long* launches) {
-  long long uncounted = 0;
-  if (!launches) launches = &uncounted;
-  const bool mom = rho != nullptr;
-  const int nt = tuning("nt", 3);  // bit 0: non-temporal loads, bit 1: non-temporal stores
-  const int cap = tuning("grid_cap", 0);
-  const int tiles = (k.g.C + 511) / 512;
-  const long items = (long)(row_end - row_begin) * tiles;
-  const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
-  with_flags([&](auto NL, auto NS, auto M) {
-    LBM_KLAUNCH((k_ade_stream_collide<FM, SM, NL(), NS(), M(), B>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go, k.g, fm,
-                sm, row_begin, row_end, tiles, rho, u, conc, k.by);
-  }, nt & 1, nt & 2, mom);
+static int ade_open_pass(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
+                         const double* go, const AdeRows& r, double* rho, double* u, double* conc, hipStream_t st,
+                         long long* launches) {
+  if (k.n_open_nodes == 0) return LBM_OK;
+  const AdeRanges a = ade_row_ranges(k.open_first, r.band0, r.n0, r.band1, r.nrows);
+  if (a.w == 0) return LBM_OK;
+  with_flags([&](auto M, auto F) {
+    LBM_KLAUNCH((k_ade_open_ranges<FM, SM, M(), F(), B>), dim3((a.w + 255) / 256), dim3(256), 0, st, fn, gn, fo, go, k.g,
+                k.bc, fm, sm, rho, u, conc, k.sw, k.by, k.open_nodes, k.open_segs, a.first0, a.w0, a.first1, a.w,
+                k.carry_in, k.carry_out);
+  }, rho != nullptr, k.sw.fixed);
   LBM_CHECK_LAUNCH();
   ++*launches;
-  if (bc_needs_edge_pass(k.bc)) {
-    const int n_edge = 2 * k.g.C + 2 * (row_end - row_begin);
-    const dim3 grid_e((n_edge + 255) / 256);
-    with_flags([&](auto M, auto F) {
-      LBM_KLAUNCH((k_ade_edge<FM, SM, M(), F(), B>), grid_e, dim3(256), 0, st, fn, gn, fo, go, k.g, k.bc, fm, sm, row_begin,
-                  row_end, rho, u, conc, k.sw, k.by);
-    }, mom, k.sw.fixed);
-    LBM_CHECK_LAUNCH();
-    ++*launches;
-  }
-  const int nrows = row_end - row_begin;
-  return ade_table_passes<B>(k, fm, sm, fn, gn, fo, go, row_begin, nrows, row_begin, nrows, rho, u, conc, st, launches);
+  return LBM_OK;
+}
+
+// the two table passes of a launch with the BGK fluid: the open table's listed nodes of the rows, then the interior walls'
+template <bool B, class FM, class SM>
+static int ade_table_passes(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
+                            const double* go, const AdeRows& r, double* rho, double* u, double* conc, hipStream_t st,
+                            long long* launches) {
+  if (int rc = ade_open_pass<B>(k, fm, sm, fn, gn, fo, go, r, rho, u, conc, st, launches)) return rc;
+  return ade_iwalls_pass<B>(k, fm, sm, fn, gn, fo, go, r, rho, u, conc, st, launches);
 }
 
 // kernels the part launches of this process have enqueued (lbm_ade_part_launches): what "a NULL view adds no launch" is
@@ -499,37 +497,58 @@ static int ade_step_launch(const AdeCall& k, const FM& fm, const SM& sm, double*
 static std::atomic<long long> g_part_launches{0};
 void ade_part_launches_add(long long n) { g_part_launches.fetch_add(n, std::memory_order_relaxed); }
 
-// one dispatch over rows [band0, band0 + n0) and [band1, band1 + nrows - n0), wall fix-ups inline, + the table passes of
-// those rows
-template <bool B, class FM, class SM>
-static int ade_part_launch(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
-                           const double* go, int band0, int n0, int band1, int nrows, double* rho, double* u,
-                           double* conc, hipStream_t st) {
-  const bool mom = rho != nullptr;
-  const int nt = tuning("nt", 3);  // as the single-block step
-  const int cap = tuning("grid_cap", 0);
-  const int tiles = (k.g.C + 511) / 512;
-  const long items = (long)nrows * tiles;
-  const int grid = cap > 0 ? capped_grid(items, cap) : (int)(items < (1L << 30) ? items : (1L << 30));
-  with_flags([&](auto NL, auto NS, auto M, auto F) {
-    LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL(), NS(), M(), F(), B>), dim3(grid), dim3(256), 0, st, fn, gn, fo, go,
-                k.g, k.bc, fm, sm, band0, n0, band1, nrows, tiles, rho, u, conc, k.sw, k.by);
-  }, nt & 1, nt & 2, mom, k.sw.fixed);
-  LBM_CHECK_LAUNCH();
-  long long launches = 1;
-  const int rc = ade_table_passes<B>(k, fm, sm, fn, gn, fo, go, band0, n0, band1, nrows, rho, u, conc, st, &launches);
-  g_part_launches.fetch_add(launches, std::memory_order_relaxed);
-  return rc;
-}
-
+// The launches of a resolved call, by its fluid: BGK here, KBC in capi_ade_kbc.hip (a part: capi_ade_kbc_part.hip), KBC with
+// call.buoyant in capi_ade_kbc_buoyant.hip.
 // collide only: no streaming, so no wall rule -- the scalar's walls and the interior walls of the call are checked and
 // nothing more
 int ade_collide_from(const char* fn, const AdeCall& k, double* fp, double* gp, const double* f, const double* h,
                      double* rho, double* u, double* conc, hipStream_t st) {
-  if (k.kbc) return ade_kbc_collide_from(fn, k, fp, gp, f, h, rho, u, conc, st);
   if (int rc = ade_lattice_args(fn, fp, gp, f, h, rho, u, conc, false)) return rc;
+  if (k.kbc && k.buoyant) return ade_kbc_buoyant_collide_from(k, fp, gp, f, h, rho, u, conc, st);
+  if (k.kbc) return ade_kbc_collide_from(k, fp, gp, f, h, rho, u, conc, st);
   return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
     return ade_collide_launch<B()>(k, fm, sm, fp, gp, f, h, rho, u, conc, st);
+  });
+}
+
+// the step on rows [row_begin, row_end) of a single block; *launches (if given) += the kernels enqueued
+static int ade_step_from(const AdeCall& k, double* fn, double* gn, const double* fo, const double* go, int row_begin,
+                         int row_end, double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
+  long long uncounted = 0;
+  if (!launches) launches = &uncounted;
+  if (k.kbc && k.buoyant) return ade_kbc_buoyant_step(k, fn, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
+  if (k.kbc) return ade_kbc_step(k, fn, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
+  return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
+    using FM = std::decay_t<decltype(fm)>;
+    using SM = std::decay_t<decltype(sm)>;
+    constexpr bool kB = decltype(B)::value;
+    return ade_step_sequence<kB>(k, fm, sm, fn, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches,
+        [&](const AdeDispatch& d) {
+          with_flags([&](auto NL, auto NS, auto M) {
+            LBM_KLAUNCH((k_ade_stream_collide<FM, SM, NL(), NS(), M(), kB>), dim3(d.grid), dim3(256), 0, st, fn, gn, fo, go,
+                        k.g, fm, sm, row_begin, row_end, d.tiles, rho, u, conc, k.by);
+          }, d.nt & 1, d.nt & 2, rho != nullptr);
+        },
+        [&](const AdeRows& r, long long* n) { return ade_table_passes<kB>(k, fm, sm, fn, gn, fo, go, r, rho, u, conc, st, n); });
+  });
+}
+
+// one part of a call, after ade_part_args
+int ade_part_from(const AdeCall& k, double* fn, double* gn, const double* fo, const double* go, int part, int edge_rows,
+                  double* rho, double* u, double* conc, hipStream_t st) {
+  if (k.kbc) return ade_kbc_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
+  return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
+    using FM = std::decay_t<decltype(fm)>;
+    using SM = std::decay_t<decltype(sm)>;
+    constexpr bool kB = decltype(B)::value;
+    return ade_part_sequence(k, part, edge_rows,
+        [&](const AdeDispatch& d, const AdeRows& r) {
+          with_flags([&](auto NL, auto NS, auto M, auto F) {
+            LBM_KLAUNCH((k_ade_stream_collide_part<FM, SM, NL(), NS(), M(), F(), kB>), dim3(d.grid), dim3(256), 0, st, fn, gn,
+                        fo, go, k.g, k.bc, fm, sm, r.band0, r.n0, r.band1, r.nrows, d.tiles, rho, u, conc, k.sw, k.by);
+          }, d.nt & 1, d.nt & 2, rho != nullptr, k.sw.fixed);
+        },
+        [&](const AdeRows& r, long long* n) { return ade_table_passes<kB>(k, fm, sm, fn, gn, fo, go, r, rho, u, conc, st, n); });
   });
 }
 
@@ -566,7 +585,7 @@ int ade_open_prime_from(const AdeCall& k, const double* f, hipStream_t st) {
 
 // the collide-only iteration; with a non-empty open table one more small launch writes carry_out from the pre-collision f
 static int ade_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* lg,
-                       const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                       const lbm_bc* bc, const AdeFluid& fluid, const lbm_ade_params* scalar,
                        const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                        double* rho, double* u, double* conc, hipStream_t st, const lbm_ade_open* open = nullptr,
                        double* carry_out = nullptr, long long* launches = nullptr) {
@@ -583,7 +602,7 @@ static int ade_collide(const char* fn, double* fp, double* gp, const double* f, 
 }
 
 static int ade_stream_collide(const char* fn, double* fn_, double* gn, const double* fo, const double* go,
-                              const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid,
+                              const lbm_geom* lg, const lbm_bc* lbc, const AdeFluid& fluid,
                               const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
                               const lbm_ade_iwalls* iwalls, int row_begin, int row_end, double* rho, double* u,
                               double* conc, hipStream_t st, long long* launches = nullptr,
@@ -599,9 +618,7 @@ static int ade_stream_collide(const char* fn, double* fn_, double* gn, const dou
   LBM_REQUIRE(k.n_open_nodes == 0 || (row_begin == 0 && row_end == lg->R),
               "%s: open boundaries: row range [%d, %d): the whole block [0, %d) only", fn, row_begin, row_end, lg->R);
   if (row_begin == row_end) return LBM_OK;
-  return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
-    return ade_step_launch<B()>(k, fm, sm, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
-  });
+  return ade_step_from(k, fn_, gn, fo, go, row_begin, row_end, rho, u, conc, st, launches);
 }
 
 // the lattices and the part of a part launch, on the host
@@ -615,23 +632,9 @@ int ade_part_args(const char* fn, const AdeCall& k, const double* fn_, const dou
   return LBM_OK;
 }
 
-// one part of a call, after ade_part_args
-int ade_part_from(const AdeCall& k, double* fn, double* gn, const double* fo, const double* go, int part, int edge_rows,
-                  double* rho, double* u, double* conc, hipStream_t st) {
-  if (k.kbc) return ade_kbc_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
-  const int R = k.g.R;
-  // FRAME: rows [0, E) then [R - E, R); INNER: rows [E, R - E)
-  const int band0 = part == LBM_ADE_PART_FRAME ? 0 : edge_rows;
-  const int n0 = part == LBM_ADE_PART_FRAME ? edge_rows : R - 2 * edge_rows;
-  const int band1 = R - edge_rows, nrows = part == LBM_ADE_PART_FRAME ? 2 * edge_rows : n0;
-  return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
-    return ade_part_launch<B()>(k, fm, sm, fn, gn, fo, go, band0, n0, band1, nrows, rho, u, conc, st);
-  });
-}
-
-// lbm_ade_stream_collide_part(_ex, _b, _w) under the caller's name
+// lbm_ade_stream_collide_part(_ex, _b, _w, _o, _m) under the caller's name
 static int ade_part(const char* name, double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
-                    const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                    const lbm_bc* lbc, const AdeFluid& fluid, const lbm_ade_params* scalar,
                     const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int part,
                     int edge_rows, double* rho, double* u, double* conc, hipStream_t st,
                     const lbm_ade_open* view = nullptr, const double* carry_in = nullptr, double* carry_out = nullptr) {
@@ -650,7 +653,7 @@ static int ade_wallx_rows(const char* fn, double* table, int table_rows, int tab
                           const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                           const int* region4, int row_begin, int row_end, hipStream_t st) {
   AdeCall k;
-  int rc = ade_resolve(fn, lg, lbc, fluid, scalar, sbc, buoy, iwalls, true, &k);
+  int rc = ade_resolve(fn, lg, lbc, AdeFluid{fluid, nullptr}, scalar, sbc, buoy, iwalls, true, &k);
   if (rc) return rc;
   LBM_REQUIRE(table && fo && go, "%s: NULL argument (table, fo, go)", fn);
   rc = diag_range_check(fn, lg->R, row_begin, row_end);
@@ -720,21 +723,21 @@ extern "C" {
 int lbm_ade_collide(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
                     const lbm_bgk_params* fluid, const lbm_ade_params* scalar, double* rho, double* u, double* conc,
                     lbm_stream_t s) {
-  return ade_collide("lbm_ade_collide", fp, gp, f, g_in, g, bc, fluid, scalar, nullptr, nullptr, nullptr, rho, u, conc,
+  return ade_collide("lbm_ade_collide", fp, gp, f, g_in, g, bc, {fluid, nullptr}, scalar, nullptr, nullptr, nullptr, rho, u, conc,
                      as_stream(s));
 }
 
 int lbm_ade_collide_b(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
                       const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                       const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_collide("lbm_ade_collide_b", fp, gp, f, g_in, g, bc, fluid, scalar, sbc, buoy, nullptr, rho, u, conc,
+  return ade_collide("lbm_ade_collide_b", fp, gp, f, g_in, g, bc, {fluid, nullptr}, scalar, sbc, buoy, nullptr, rho, u, conc,
                      as_stream(s));
 }
 
 int lbm_ade_stream_collide(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                            const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int row_begin,
                            int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, fluid, scalar, nullptr, nullptr, nullptr,
+  return ade_stream_collide("lbm_ade_stream_collide", fn, gn, fo, go, g, bc, {fluid, nullptr}, scalar, nullptr, nullptr, nullptr,
                             row_begin, row_end, rho, u, conc, as_stream(s));
 }
 
@@ -742,7 +745,7 @@ int lbm_ade_stream_collide_ex(double* fn, double* gn, const double* fo, const do
                               const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                               const lbm_ade_scalar_bc* sbc, int row_begin, int row_end, double* rho, double* u,
                               double* conc, lbm_stream_t s) {
-  return ade_stream_collide("lbm_ade_stream_collide_ex", fn, gn, fo, go, g, bc, fluid, scalar, sbc, nullptr, nullptr,
+  return ade_stream_collide("lbm_ade_stream_collide_ex", fn, gn, fo, go, g, bc, {fluid, nullptr}, scalar, sbc, nullptr, nullptr,
                             row_begin, row_end, rho, u, conc, as_stream(s));
 }
 
@@ -750,7 +753,7 @@ int lbm_ade_stream_collide_b(double* fn, double* gn, const double* fo, const dou
                              const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int row_begin, int row_end,
                              double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_stream_collide("lbm_ade_stream_collide_b", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, nullptr,
+  return ade_stream_collide("lbm_ade_stream_collide_b", fn, gn, fo, go, g, bc, {fluid, nullptr}, scalar, sbc, buoy, nullptr,
                             row_begin, row_end, rho, u, conc, as_stream(s));
 }
 
@@ -758,14 +761,14 @@ int lbm_ade_stream_collide_w(double* fn, double* gn, const double* fo, const dou
                              const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                              int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_stream_collide("lbm_ade_stream_collide_w", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, iwalls,
+  return ade_stream_collide("lbm_ade_stream_collide_w", fn, gn, fo, go, g, bc, {fluid, nullptr}, scalar, sbc, buoy, iwalls,
                             row_begin, row_end, rho, u, conc, as_stream(s));
 }
 
 int lbm_ade_stream_collide_part(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* lg,
                                 const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int part,
                                 int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, fluid, scalar, nullptr, nullptr, nullptr,
+  return ade_part("lbm_ade_stream_collide_part", fn, gn, fo, go, lg, lbc, {fluid, nullptr}, scalar, nullptr, nullptr, nullptr,
                   part, edge_rows, rho, u, conc, as_stream(s));
 }
 
@@ -773,7 +776,7 @@ int lbm_ade_stream_collide_part_ex(double* fn, double* gn, const double* fo, con
                                    const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                                    const lbm_ade_scalar_bc* sbc, int part, int edge_rows, double* rho, double* u,
                                    double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part_ex", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, nullptr, nullptr, part,
+  return ade_part("lbm_ade_stream_collide_part_ex", fn, gn, fo, go, lg, lbc, {fluid, nullptr}, scalar, sbc, nullptr, nullptr, part,
                   edge_rows, rho, u, conc, as_stream(s));
 }
 
@@ -781,7 +784,7 @@ int lbm_ade_stream_collide_part_b(double* fn, double* gn, const double* fo, cons
                                   const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                                   const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, int part, int edge_rows,
                                   double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part_b", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, buoy, nullptr, part,
+  return ade_part("lbm_ade_stream_collide_part_b", fn, gn, fo, go, lg, lbc, {fluid, nullptr}, scalar, sbc, buoy, nullptr, part,
                   edge_rows, rho, u, conc, as_stream(s));
 }
 
@@ -789,26 +792,25 @@ int lbm_ade_stream_collide_part_w(double* fn, double* gn, const double* fo, cons
                                   const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                                   const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                                   int part, int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part_w", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, buoy, iwalls, part,
+  return ade_part("lbm_ade_stream_collide_part_w", fn, gn, fo, go, lg, lbc, {fluid, nullptr}, scalar, sbc, buoy, iwalls, part,
                   edge_rows, rho, u, conc, as_stream(s));
 }
 
-// the context of either fluid (exactly one of fluid, kbc given), under the caller's name
-static int ade_solver_create(const char* fn, lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc,
-                             const lbm_bgk_params* fluid, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
-                             lbm_stream_t s) {
+// the context of either fluid, under the caller's name
+static int ade_solver_create(const char* fn, lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const AdeFluid& fluid,
+                             const lbm_ade_params* scalar, lbm_stream_t s) {
   LBM_REQUIRE(out, "%s: NULL argument", fn);
-  int rc = kbc ? ade_kbc_validate(fn, g, bc, kbc, scalar) : ade_validate(fn, g, bc, fluid, scalar);
-  if (rc) return rc;
+  AdeCall unused;
+  if (int rc = ade_resolve(fn, g, bc, fluid, scalar, nullptr, nullptr, nullptr, false, &unused)) return rc;
   LBM_REQUIRE(g->row_pitch == 0 && g->plane_stride == 0,
               "%s: the context pads its own lattices (row_pitch and plane_stride must be 0)", fn);
   lbm_ade_solver* sv = new (std::nothrow) lbm_ade_solver();
   LBM_REQUIRE(sv, "%s: out of host memory", fn);
   sv->g = *g;
   sv->bc = bc ? *bc : lbm_bc{0, 0, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
-  sv->model = kbc ? LBM_MODEL_KBC : LBM_MODEL_BGK;
-  sv->fluid = fluid ? *fluid : lbm_bgk_params{};
-  sv->kbc = kbc ? *kbc : lbm_kbc_params{};
+  sv->model = fluid.kbc ? LBM_MODEL_KBC : LBM_MODEL_BGK;
+  sv->fluid = fluid.bgk ? *fluid.bgk : lbm_bgk_params{};
+  sv->kbc = fluid.kbc ? *fluid.kbc : lbm_kbc_params{};
   sv->scalar = *scalar;
   sv->sbc = lbm_ade_scalar_bc{};
   sv->fixed = false;
@@ -849,17 +851,14 @@ static int ade_solver_create(const char* fn, lbm_ade_solver** out, const lbm_geo
 
 int lbm_ade_solver_create(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
                           const lbm_ade_params* scalar, lbm_stream_t s) {
-  return ade_solver_create("lbm_ade_solver_create", out, g, bc, fluid, nullptr, scalar, s);
+  return ade_solver_create("lbm_ade_solver_create", out, g, bc, {fluid, nullptr}, scalar, s);
 }
 
 int lbm_ade_solver_create_m(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc, const lbm_ade_fluid* fluid,
                             const lbm_ade_params* scalar, lbm_stream_t s) {
-  const char* fn = "lbm_ade_solver_create_m";
-  LBM_REQUIRE(fluid, "%s: NULL fluid (lbm_ade_fluid)", fn);
-  LBM_REQUIRE(fluid->model == LBM_MODEL_BGK || fluid->model == LBM_MODEL_KBC,
-              "%s: fluid model=%d (LBM_MODEL_BGK or LBM_MODEL_KBC)", fn, fluid->model);
-  if (fluid->model == LBM_MODEL_BGK) return lbm_ade_solver_create(out, g, bc, &fluid->bgk, scalar, s);
-  return ade_solver_create(fn, out, g, bc, nullptr, &fluid->kbc, scalar, s);
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_solver_create_m", fluid, &fl)) return rc;
+  return ade_solver_create(fl.kbc ? "lbm_ade_solver_create_m" : "lbm_ade_solver_create", out, g, bc, fl, scalar, s);
 }
 
 int lbm_ade_solver_destroy(lbm_ade_solver* sv) {
@@ -897,23 +896,18 @@ int lbm_ade_solver_set_state(lbm_ade_solver* sv, const double* f_host, const dou
 int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
   LBM_REQUIRE(sv && n >= 0, "lbm_ade_solver_step: bad argument (n=%d)", n);
   const lbm_ade_buoyancy* buoy = sv->buoyant ? &sv->buoy : nullptr;
+  // (a KBC context holds no open table with nodes: its setter refuses)
+  const AdeFluid fluid = sv->model == LBM_MODEL_KBC ? AdeFluid{nullptr, &sv->kbc} : AdeFluid{&sv->fluid, nullptr};
   for (int i = 0; i < n; ++i) {
     const int k = sv->cur, o = k ^ 1;
     int rc;
-    if (sv->model == LBM_MODEL_KBC) {  // (no open table on such a context: its setter refuses)
-      rc = !sv->post ? ade_kbc_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->kbc,
-                                       &sv->scalar, nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st, &sv->launches)
-                     : ade_kbc_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
-                                              &sv->kbc, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, buoy, sv->walls, 0,
-                                              sv->g.R, nullptr, nullptr, nullptr, sv->st, &sv->launches);
-    } else if (!sv->post) {
-      rc = ade_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid,
-                       &sv->scalar, nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st, sv->open, sv->carry[o],
-                       &sv->launches);
+    if (!sv->post) {
+      rc = ade_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, fluid, &sv->scalar,
+                       nullptr, buoy, sv->walls, nullptr, nullptr, nullptr, sv->st, sv->open, sv->carry[o], &sv->launches);
     } else {
-      rc = ade_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc,
-                              &sv->fluid, &sv->scalar, sv->fixed ? &sv->sbc : nullptr, buoy, sv->walls, 0, sv->g.R,
-                              nullptr, nullptr, nullptr, sv->st, &sv->launches, sv->open, sv->carry[k], sv->carry[o]);
+      rc = ade_stream_collide("lbm_ade_solver_step", sv->f(o), sv->h(o), sv->f(k), sv->h(k), &sv->g, &sv->bc, fluid,
+                              &sv->scalar, sv->fixed ? &sv->sbc : nullptr, buoy, sv->walls, 0, sv->g.R, nullptr, nullptr,
+                              nullptr, sv->st, &sv->launches, sv->open, sv->carry[k], sv->carry[o]);
     }
     if (rc) return rc;
     sv->cur = o;
@@ -1557,7 +1551,7 @@ int lbm_ade_collide_o(double* fp, double* gp, const double* f, const double* g_i
                       const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                       const lbm_ade_buoyancy* buoy, const lbm_ade_open* open, double* carry_out, double* rho, double* u,
                       double* conc, lbm_stream_t s) {
-  return ade_collide("lbm_ade_collide_o", fp, gp, f, g_in, g, bc, fluid, scalar, sbc, buoy, nullptr, rho, u, conc,
+  return ade_collide("lbm_ade_collide_o", fp, gp, f, g_in, g, bc, {fluid, nullptr}, scalar, sbc, buoy, nullptr, rho, u, conc,
                      as_stream(s), open, carry_out);
 }
 
@@ -1566,7 +1560,7 @@ int lbm_ade_stream_collide_o(double* fn, double* gn, const double* fo, const dou
                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                              const lbm_ade_open* open, const double* carry_in, double* carry_out, int row_begin,
                              int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_stream_collide("lbm_ade_stream_collide_o", fn, gn, fo, go, g, bc, fluid, scalar, sbc, buoy, iwalls, row_begin,
+  return ade_stream_collide("lbm_ade_stream_collide_o", fn, gn, fo, go, g, bc, {fluid, nullptr}, scalar, sbc, buoy, iwalls, row_begin,
                             row_end, rho, u, conc, as_stream(s), nullptr, open, carry_in, carry_out);
 }
 
@@ -1575,8 +1569,59 @@ int lbm_ade_stream_collide_part_o(double* fn, double* gn, const double* fo, cons
                                   const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                                   const lbm_ade_open* view, const double* carry_in, double* carry_out, int part,
                                   int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
-  return ade_part("lbm_ade_stream_collide_part_o", fn, gn, fo, go, lg, lbc, fluid, scalar, sbc, buoy, iwalls, part,
+  return ade_part("lbm_ade_stream_collide_part_o", fn, gn, fo, go, lg, lbc, {fluid, nullptr}, scalar, sbc, buoy, iwalls, part,
                   edge_rows, rho, u, conc, as_stream(s), view, carry_in, carry_out);
+}
+
+// The fluid by model (lbm_ade_fluid): the `_m` entries and their buoyant forms `_mb`.  model = BGK: the checks and launches
+// of the call they name in lbm_hip.h -- lbm_ade_collide_b, lbm_ade_stream_collide_w, lbm_ade_stream_collide_part_w --
+// under that call's name; model = KBC: the same entry with the KBC fluid, under their own.
+int lbm_ade_collide_m(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                      const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, double* rho,
+                      double* u, double* conc, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_collide_m", fluid, &fl)) return rc;
+  return ade_collide(fl.kbc ? "lbm_ade_collide_m" : "lbm_ade_collide_b", fp, gp, f, g_in, g, bc, fl, scalar, sbc, nullptr,
+                     nullptr, rho, u, conc, as_stream(s));
+}
+
+int lbm_ade_collide_mb(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                       const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                       const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_collide_mb", fluid, &fl)) return rc;
+  return ade_collide(fl.kbc ? "lbm_ade_collide_mb" : "lbm_ade_collide_b", fp, gp, f, g_in, g, bc, fl, scalar, sbc, buoy,
+                     nullptr, rho, u, conc, as_stream(s));
+}
+
+int lbm_ade_stream_collide_m(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                             const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                             const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int row_begin, int row_end,
+                             double* rho, double* u, double* conc, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_stream_collide_m", fluid, &fl)) return rc;
+  return ade_stream_collide(fl.kbc ? "lbm_ade_stream_collide_m" : "lbm_ade_stream_collide_w", fn, gn, fo, go, g, bc, fl, scalar,
+                            sbc, nullptr, iwalls, row_begin, row_end, rho, u, conc, as_stream(s));
+}
+
+int lbm_ade_stream_collide_mb(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                              const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                              const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                              int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_stream_collide_mb", fluid, &fl)) return rc;
+  return ade_stream_collide(fl.kbc ? "lbm_ade_stream_collide_mb" : "lbm_ade_stream_collide_w", fn, gn, fo, go, g, bc, fl, scalar,
+                            sbc, buoy, iwalls, row_begin, row_end, rho, u, conc, as_stream(s));
+}
+
+int lbm_ade_stream_collide_part_m(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                  const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int part, int edge_rows,
+                                  double* rho, double* u, double* conc, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_stream_collide_part_m", fluid, &fl)) return rc;
+  return ade_part(fl.kbc ? "lbm_ade_stream_collide_part_m" : "lbm_ade_stream_collide_part_w", fn, gn, fo, go, g, bc, fl, scalar,
+                  sbc, nullptr, iwalls, part, edge_rows, rho, u, conc, as_stream(s));
 }
 
 long long lbm_ade_part_launches(void) { return g_part_launches.load(std::memory_order_relaxed); }

@@ -312,11 +312,10 @@ static int ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm
 // The call of a ring entry, resolved once, before any device call: the slab's edges (ring_slab_bc, periodic by default) and
 // the scalar's walls -- gsbc, of the global domain, checked against the global edges; a FIXED row acts where the slab keeps
 // that edge (a chain end) and is dropped at a seam, as the fluid's row wall is.
-// kbc: a KBC fluid (the `_m` entries; fluid, buoy and view are then NULL) -- ade_kbc_resolve in ade_resolve's place
-static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, const lbm_bgk_params* fluid,
+// fluid: either fluid (the `_m` entries have no parameter for buoy or view, which ade_resolve refuses with a KBC fluid)
+static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, const AdeFluid& fluid,
                             const lbm_ade_params* scalar, const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy,
-                            const lbm_ade_iwalls* iwalls, AdeCall* call, const lbm_ade_open* view = nullptr,
-                            const lbm_kbc_params* kbc = nullptr) {
+                            const lbm_ade_iwalls* iwalls, AdeCall* call, const lbm_ade_open* view = nullptr) {
   LBM_REQUIRE(rg->g.ghost == 1, "%s: ghost=%d: the fluid + scalar step over slabs exchanges one ghost row per side (ring "
               "slabs need ghost=1)", fn, rg->g.ghost);
   const lbm_bc b = ring_slab_bc(rg, bc);
@@ -327,7 +326,6 @@ static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, cons
     if (b.row_lo == LBM_EDGE_HALO) sb.mode[0] = LBM_ADE_SCALAR_NO_FLUX;
     if (b.row_hi == LBM_EDGE_HALO) sb.mode[1] = LBM_ADE_SCALAR_NO_FLUX;
   }
-  if (kbc) return ade_kbc_resolve(fn, &rg->g, &b, kbc, scalar, gsbc ? &sb : nullptr, iwalls, true, call);
   return ade_resolve(fn, &rg->g, &b, fluid, scalar, gsbc ? &sb : nullptr, buoy, iwalls, true, call, view);
 }
 
@@ -341,18 +339,17 @@ static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, cons
 // ring's stream starts after everything on `main`) and join (`main` waits for the ring's stream) order both: nothing more
 // is synchronised here.
 static int ring_ade_step(const char* fn, lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go,
-                         const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                         const lbm_bc* bc, const AdeFluid& fluid, const lbm_ade_params* scalar,
                          const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                          int edge_rows, lbm_stream_t main_s, const lbm_ade_open* view = nullptr,
-                         const double* carry_in = nullptr, double* carry_out = nullptr,
-                         const lbm_kbc_params* kbc = nullptr) {
+                         const double* carry_in = nullptr, double* carry_out = nullptr) {
   int rc = ade_buoyancy_check(fn, buoy);  // needs no ring
   if (rc) return rc;
-  LBM_REQUIRE(rg && fn_ && gn && fo && go && (fluid || kbc) && scalar, "%s: NULL argument", fn);
+  LBM_REQUIRE(rg && fn_ && gn && fo && go && (fluid.bgk || fluid.kbc) && scalar, "%s: NULL argument", fn);
   AdeCallBuf buf;
   const AdeCall& call = *buf.get();
   if (edge_rows < 1) edge_rows = 1;
-  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, iwalls, buf.get(), view, kbc);
+  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, iwalls, buf.get(), view);
   if (!rc) rc = ade_part_args(fn, call, fn_, gn, fo, go, LBM_ADE_PART_FRAME, edge_rows, nullptr, nullptr, nullptr);
   if (!rc) rc = ade_carry_set(fn, buf.get(), true, carry_in, carry_out);
   if (rc) return rc;
@@ -641,15 +638,14 @@ int lbm_ring_cg_step(lbm_ring* rg, double* dst_r, double* dst_b, const double* s
 
 // lbm_ring_ade_collide(_b) under the caller's name; the scalar's walls are checked only (collide-only applies no wall rule)
 static int ring_ade_collide(const char* fn, lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in,
-                            const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                            const lbm_bc* bc, const AdeFluid& fluid, const lbm_ade_params* scalar,
                             const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy, lbm_stream_t main_s,
-                            const lbm_ade_open* view = nullptr, double* carry_out = nullptr,
-                            const lbm_kbc_params* kbc = nullptr) {
+                            const lbm_ade_open* view = nullptr, double* carry_out = nullptr) {
   int rc = ade_buoyancy_check(fn, buoy);  // needs no ring
   if (rc) return rc;
-  LBM_REQUIRE(rg && fp && gp && f && g_in && (fluid || kbc) && scalar, "%s: NULL argument", fn);
+  LBM_REQUIRE(rg && fp && gp && f && g_in && (fluid.bgk || fluid.kbc) && scalar, "%s: NULL argument", fn);
   AdeCallBuf buf;
-  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, nullptr, buf.get(), view, kbc);
+  rc = ring_ade_resolve(fn, rg, bc, fluid, scalar, gsbc, buoy, nullptr, buf.get(), view);
   if (!rc) rc = ade_carry_set(fn, buf.get(), false, nullptr, carry_out);
   if (rc) return rc;
   hipStream_t main = as_stream(main_s);
@@ -661,70 +657,69 @@ static int ring_ade_collide(const char* fn, lbm_ring* rg, double* fp, double* gp
 
 int lbm_ring_ade_collide(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
                          const lbm_bgk_params* fluid, const lbm_ade_params* scalar, lbm_stream_t main_s) {
-  return ring_ade_collide("lbm_ring_ade_collide", rg, fp, gp, f, g_in, bc, fluid, scalar, nullptr, nullptr, main_s);
+  return ring_ade_collide("lbm_ring_ade_collide", rg, fp, gp, f, g_in, bc, {fluid, nullptr}, scalar, nullptr, nullptr, main_s);
 }
 
 int lbm_ring_ade_collide_b(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
                            const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                            const lbm_ade_buoyancy* buoy, lbm_stream_t main_s) {
-  return ring_ade_collide("lbm_ring_ade_collide_b", rg, fp, gp, f, g_in, bc, fluid, scalar, sbc, buoy, main_s);
+  return ring_ade_collide("lbm_ring_ade_collide_b", rg, fp, gp, f, g_in, bc, {fluid, nullptr}, scalar, sbc, buoy, main_s);
 }
 
 int lbm_ring_ade_step(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                       const lbm_bgk_params* fluid, const lbm_ade_params* scalar, int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step", rg, fn_, gn, fo, go, bc, fluid, scalar, nullptr, nullptr, nullptr, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step", rg, fn_, gn, fo, go, bc, {fluid, nullptr}, scalar, nullptr, nullptr, nullptr, edge_rows, main_s);
 }
 
 int lbm_ring_ade_step_ex(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                          const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                          int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step_ex", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, nullptr, nullptr, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step_ex", rg, fn_, gn, fo, go, bc, {fluid, nullptr}, scalar, sbc, nullptr, nullptr, edge_rows, main_s);
 }
 
 int lbm_ring_ade_step_b(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_buoyancy* buoy, int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step_b", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, nullptr, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step_b", rg, fn_, gn, fo, go, bc, {fluid, nullptr}, scalar, sbc, buoy, nullptr, edge_rows, main_s);
 }
 
 int lbm_ring_ade_step_w(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step_w", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, iwalls, edge_rows, main_s);
+  return ring_ade_step("lbm_ring_ade_step_w", rg, fn_, gn, fo, go, bc, {fluid, nullptr}, scalar, sbc, buoy, iwalls, edge_rows, main_s);
 }
 
-// the fluid by model: BGK forwards to the _b / _w entries under their names; KBC takes the same schedule with its own
-// resolve and launches (ade_kbc_resolve; ade_collide_from / ade_part_from hand a call with a KBC fluid to capi_ade_kbc.hip)
+// the fluid by model: BGK is the _b / _w entry under its name; KBC takes the same schedule under its own (ade_collide_from
+// and ade_part_from launch a resolved call by its fluid)
 int lbm_ring_ade_collide_m(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
                            const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                            lbm_stream_t main_s) {
-  if (int rc = ade_fluid_model("lbm_ring_ade_collide_m", fluid)) return rc;
-  if (fluid->model == LBM_MODEL_BGK) return lbm_ring_ade_collide_b(rg, fp, gp, f, g_in, bc, &fluid->bgk, scalar, sbc, nullptr, main_s);
-  return ring_ade_collide("lbm_ring_ade_collide_m", rg, fp, gp, f, g_in, bc, nullptr, scalar, sbc, nullptr, main_s, nullptr,
-                          nullptr, &fluid->kbc);
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ring_ade_collide_m", fluid, &fl)) return rc;
+  return ring_ade_collide(fl.kbc ? "lbm_ring_ade_collide_m" : "lbm_ring_ade_collide_b", rg, fp, gp, f, g_in, bc, fl, scalar, sbc,
+                          nullptr, main_s);
 }
 
 int lbm_ring_ade_step_m(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                         const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main_s) {
-  if (int rc = ade_fluid_model("lbm_ring_ade_step_m", fluid)) return rc;
-  if (fluid->model == LBM_MODEL_BGK)
-    return lbm_ring_ade_step_w(rg, fn_, gn, fo, go, bc, &fluid->bgk, scalar, sbc, nullptr, iwalls, edge_rows, main_s);
-  return ring_ade_step("lbm_ring_ade_step_m", rg, fn_, gn, fo, go, bc, nullptr, scalar, sbc, nullptr, iwalls, edge_rows,
-                       main_s, nullptr, nullptr, nullptr, &fluid->kbc);
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ring_ade_step_m", fluid, &fl)) return rc;
+  return ring_ade_step(fl.kbc ? "lbm_ring_ade_step_m" : "lbm_ring_ade_step_w", rg, fn_, gn, fo, go, bc, fl, scalar, sbc, nullptr,
+                       iwalls, edge_rows, main_s);
 }
 
 int lbm_ring_ade_collide_o(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
                            const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                            const lbm_ade_buoyancy* buoy, const lbm_ade_open* view, double* carry_out, lbm_stream_t main_s) {
-  return ring_ade_collide("lbm_ring_ade_collide_o", rg, fp, gp, f, g_in, bc, fluid, scalar, sbc, buoy, main_s, view, carry_out);
+  return ring_ade_collide("lbm_ring_ade_collide_o", rg, fp, gp, f, g_in, bc, {fluid, nullptr}, scalar, sbc, buoy, main_s, view, carry_out);
 }
 
 int lbm_ring_ade_step_o(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                         const lbm_bgk_params* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, const lbm_ade_open* view,
                         const double* carry_in, double* carry_out, int edge_rows, lbm_stream_t main_s) {
-  return ring_ade_step("lbm_ring_ade_step_o", rg, fn_, gn, fo, go, bc, fluid, scalar, sbc, buoy, iwalls, edge_rows, main_s,
+  return ring_ade_step("lbm_ring_ade_step_o", rg, fn_, gn, fo, go, bc, {fluid, nullptr}, scalar, sbc, buoy, iwalls, edge_rows, main_s,
                        view, carry_in, carry_out);
 }
 

@@ -49,9 +49,9 @@ int box_copy(double* dst, const lbm_geom& dg, int dst_row, int dst_col, const do
 // profiles/r02_ibm_box_bench.log.)
 int make_background_stream(hipStream_t* out);
 // capi_ade.hip: one call of the fused fluid + scalar step after its host checks -- the device copies of geometry, edges,
-// scalar walls, buoyancy and interior-wall table that every launch of the call takes.  Its members are ade.hpp's, and
-// ade.hpp defines kernels, so AdeCall is complete (ade_call.hpp) in the units that launch them alone -- capi_ade.hip and
-// capi_ade_kbc.hip: another unit keeps one in an AdeCallBuf.
+// scalar walls, buoyancy and the tables that every launch of the call takes.  Its members are ade.hpp's, and ade.hpp
+// defines kernels, so AdeCall is complete (ade_call.hpp) in the units that launch them alone -- capi_ade.hip and the three
+// capi_ade_kbc*.hip: another unit keeps one in an AdeCallBuf.
 struct AdeCall;
 struct AdeWalls;
 struct AdeBuoyancy;
@@ -59,17 +59,25 @@ struct AdeCallBuf {
   alignas(8) unsigned char bytes[320];
   AdeCall* get() { return reinterpret_cast<AdeCall*>(bytes); }
 };
+// the fluid of a call: a BGK parameter block or a KBC one, exactly one of them given (both NULL: a BGK call without its
+// fluid, refused where the BGK fluid is checked).  ade_fluid_model: the fluid of an `_m` entry -- given, model BGK or KBC
+struct AdeFluid {
+  const lbm_bgk_params* bgk;
+  const lbm_kbc_params* kbc;
+};
+int ade_fluid_model(const char* fn, const lbm_ade_fluid* fluid, AdeFluid* out);
 // the host checks, once, under the caller's name fn (slab: ghost rows and HALO row edges allowed; sbc, buoy, iwalls may be
-// NULL; open: on a slab a view of the global table, lbm_ade_open_slab, on a single block an ordinary table), and the two of
-// them that need no geometry on their own (sw, by: the device copy, if wanted)
-int ade_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_bgk_params* fluid,
-                const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy,
-                const lbm_ade_iwalls* iwalls, bool slab, AdeCall* call, const lbm_ade_open* open = nullptr);
+// NULL; open: on a slab a view of the global table, lbm_ade_open_slab, on a single block an ordinary table; a KBC fluid
+// takes no table with nodes and, on a slab, no buoyancy), and the two of them that need no geometry on their own (sw, by:
+// the device copy, if wanted)
+int ade_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const AdeFluid& fluid, const lbm_ade_params* scalar,
+                const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, bool slab,
+                AdeCall* call, const lbm_ade_open* open = nullptr);
 int ade_scalar_bc_check(const char* fn, const lbm_ade_scalar_bc* sbc, const lbm_bc* bc, AdeWalls* sw = nullptr);
 int ade_buoyancy_check(const char* fn, const lbm_ade_buoyancy* buoy, AdeBuoyancy* by = nullptr, bool* buoyant = nullptr);
-// launches from a resolved call: one part (LBM_ADE_PART_*; its lattices and part pass ade_part_args first; with a table of
-// interior walls the wall pass of the part's rows follows its dispatch on the same stream) and the collide-only pass on
-// the owned rows (the first driver iteration)
+// launches from a resolved call, whatever its fluid: one part (LBM_ADE_PART_*; its lattices and part pass ade_part_args
+// first; the table passes of the part's rows follow its dispatch on the same stream) and the collide-only pass on the owned
+// rows (the first driver iteration)
 int ade_part_args(const char* fn, const AdeCall& call, const double* f_new, const double* g_new, const double* f_old,
                   const double* g_old, int part, int edge_rows, const double* rho, const double* u, const double* conc);
 int ade_part_from(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old, int part,
@@ -82,34 +90,6 @@ int ade_collide_from(const char* fn, const AdeCall& call, double* fp, double* gp
 // pre-collision state f, written to the call's carry_out (one small launch; none without a listed node)
 int ade_carry_set(const char* fn, AdeCall* call, bool reads, const double* carry_in, double* carry_out);
 int ade_open_prime_from(const AdeCall& call, const double* f, hipStream_t st);
-// capi_ade_kbc.hip: the fused step with a KBC fluid (lbm_ade_fluid, model = LBM_MODEL_KBC), under the caller's name fn --
-// the host checks alone (what lbm_ade_solver_create_m asks before it allocates), the collide-only iteration and the step
-// on rows [row_begin, row_end); *launches (if given) += the kernels enqueued.  buoy (NULL allowed): the buoyancy of a single
-// block -- beta != (0, 0) takes the forced collision (capi_ade_kbc_buoyant.hip), NULL or beta = (0, 0) the passive launches
-int ade_kbc_validate(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
-                     const lbm_ade_params* scalar);
-int ade_kbc_collide(const char* fn, double* fp, double* gp, const double* f, const double* h, const lbm_geom* g,
-                    const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
-                    const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, double* rho,
-                    double* u, double* conc, hipStream_t st, long long* launches);
-int ade_kbc_stream_collide(const char* fn, double* f_new, double* g_new, const double* f_old, const double* g_old,
-                           const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc, const lbm_ade_params* scalar,
-                           const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
-                           int row_begin, int row_end, double* rho, double* u, double* conc, hipStream_t st,
-                           long long* launches);
-// the same with a resolved call: ade_kbc_resolve is ade_resolve for this fluid (slab: as there), and a call it resolved is
-// what ade_part_from and ade_collide_from hand to ade_kbc_part_from / ade_kbc_collide_from -- one dispatch of the part
-// kernel of ade_kbc.hpp (capi_ade_kbc_part.hip) + the interior-wall pass of the part's rows, counted by
-// ade_part_launches_add (capi_ade.hip: what lbm_ade_part_launches reports).  ade_fluid_model: fluid given, model BGK or KBC.
-int ade_fluid_model(const char* fn, const lbm_ade_fluid* fluid);
-int ade_kbc_resolve(const char* fn, const lbm_geom* g, const lbm_bc* bc, const lbm_kbc_params* kbc,
-                    const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, bool slab,
-                    AdeCall* call, const lbm_ade_buoyancy* buoy = nullptr);
-int ade_kbc_collide_from(const char* fn, const AdeCall& call, double* fp, double* gp, const double* f, const double* h,
-                         double* rho, double* u, double* conc, hipStream_t st);
-int ade_kbc_part_from(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old, int part,
-                      int edge_rows, double* rho, double* u, double* conc, hipStream_t st);
-void ade_part_launches_add(long long n);
 // capi_diag.hip: what a solver context keeps for its diagnostics -- the row table [LBM_DIAG_NQ][R], the folded values on the
 // device and a pinned host buffer for them, all allocated by the first diag_reduce and kept.
 struct DiagBuf {

@@ -2,7 +2,8 @@
 // lbm_ade_collide_m, lbm_ade_stream_collide_m and lbm_ade_solver_create_m, and of their buoyant forms lbm_ade_collide_mb,
 // lbm_ade_stream_collide_mb and lbm_ade_solver_set_buoyancy_m -- the fluid by model, the KBC parameters, what
 // the step refuses with this fluid, the checks it shares with the BGK fluid, and model = BGK answering with the message of
-// the call it forwards to.  Needs no device: every call is refused before a device call (the interior-wall table it
+// the call it names -- and, for both fluids, WHICH fault a call with two faults reports (the order of the host checks is
+// observable and differs per fluid; the last section).  Needs no device: every call is refused before a device call (the interior-wall table it
 // builds is empty, whose finalize makes none).  `make san` at the root builds it against the sanitizer build of the
 // library (ASan + UBSan) and runs it; the ordinary build runs it from tests/test_ade_kbc_abi.py.  Exit status 0 = all
 // checks passed.
@@ -223,6 +224,183 @@ int main() {
     refused(lbm_ade_collide_mb(nullptr, nullptr, nullptr, nullptr, &g, nullptr, &bgk, &sc, nullptr, &b, nullptr, nullptr, nullptr, nullptr),
             "lbm_ade_collide_b: buoyancy c_ref=inf", "BGK through collide_mb");
     refused(lbm_ade_solver_set_buoyancy_m(nullptr, &good), "lbm_ade_solver_set_buoyancy_m: NULL solver", "set_buoyancy_m: NULL solver");
+  }
+  {  // two faults in one call: the one reported is the one the call checks FIRST -- the order per fluid, every entry kind
+    // (BGK entries, the `_m` / `_mb` entries with both models, the part entries).  Each pair: the earlier fault, then the later
+    struct Call {
+      lbm_ade_fluid fl;
+      lbm_geom g;
+      const lbm_bc* bc;
+      lbm_ade_params sc;
+      const lbm_ade_scalar_bc* sbc;
+      const lbm_ade_buoyancy* buoy;
+      const lbm_ade_iwalls* walls;
+      bool lattices;  // four distinct aligned lattices given (false: all NULL)
+      int row_begin, row_end, part, edge_rows;
+    };
+    alignas(16) double l0[2], l1[2], l2[2], l3[2];
+    auto lat = [&](const Call& c, double* l) { return c.lattices ? l : nullptr; };
+    // the BGK entries take c.fl.bgk, the `_m` / `_mb` entries c.fl by model; an entry without a parameter drops it
+    auto stream_w = [&](const Call& c) {
+      return lbm_ade_stream_collide_w(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl.bgk, &c.sc, c.sbc, c.buoy,
+                                      c.walls, c.row_begin, c.row_end, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto collide_b = [&](const Call& c) {
+      return lbm_ade_collide_b(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl.bgk, &c.sc, c.sbc, c.buoy, nullptr,
+                               nullptr, nullptr, nullptr);
+    };
+    auto part_w = [&](const Call& c) {
+      return lbm_ade_stream_collide_part_w(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl.bgk, &c.sc, c.sbc,
+                                           c.buoy, c.walls, c.part, c.edge_rows, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto stream_m = [&](const Call& c) {
+      return lbm_ade_stream_collide_m(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, c.walls,
+                                      c.row_begin, c.row_end, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto stream_mb = [&](const Call& c) {
+      return lbm_ade_stream_collide_mb(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, c.buoy,
+                                       c.walls, c.row_begin, c.row_end, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto collide_m = [&](const Call& c) {
+      return lbm_ade_collide_m(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, nullptr, nullptr,
+                               nullptr, nullptr);
+    };
+    auto collide_mb = [&](const Call& c) {
+      return lbm_ade_collide_mb(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, c.buoy, nullptr,
+                                nullptr, nullptr, nullptr);
+    };
+    auto part_m = [&](const Call& c) {
+      return lbm_ade_stream_collide_part_m(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, c.walls,
+                                           c.part, c.edge_rows, nullptr, nullptr, nullptr, nullptr);
+    };
+    lbm_ade_scalar_bc fixed{};
+    fixed.mode[0] = LBM_ADE_SCALAR_FIXED;  // on a PERIODIC row (NULL bc)
+    lbm_ade_buoyancy bad_buoy{1e-2, -5e-3, HUGE_VAL, 1.0, 1.0 / 3.0, 1.0 / 9.0};  // c_ref = inf
+    lbm_ade_iwalls* open_table = nullptr;  // never finalized
+    if (lbm_ade_iwalls_create(&open_table, 8, 8) != LBM_OK) {
+      ++failures;
+      std::printf("FAIL: creating a table\n");
+    }
+    const lbm_bc pressure{0, 0, 0, 0, 1, 1.0, 1.0, 0.0, 0.0};
+    Call good_bgk{};
+    good_bgk.fl.model = LBM_MODEL_BGK;
+    good_bgk.fl.bgk = lbm_bgk_params{1.2, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, LBM_FORM_DEFAULT};
+    good_bgk.fl.kbc = lbm_kbc_params{-3.0, 9};  // not read with model = BGK
+    good_bgk.g = g;
+    good_bgk.sc = sc;
+    good_bgk.lattices = true;
+    good_bgk.row_begin = 0, good_bgk.row_end = 8, good_bgk.part = LBM_ADE_PART_FRAME, good_bgk.edge_rows = 1;
+    Call good_kbc = good_bgk;
+    good_kbc.fl = kbc;
+    Call c;
+
+    // ---- the BGK fluid: scalar walls, geometry, edges, fluid, scalar, form mismatch, buoyancy, interior walls, lattices, range
+    c = good_bgk;  // FIXED on a PERIODIC edge + odd C
+    c.sbc = &fixed, c.g.C = 7;
+    refused(stream_w(c), "lbm_ade_stream_collide_w: scalar edge row_lo: FIXED on a PERIODIC", "2 faults: FIXED on PERIODIC + odd C, stream_w");
+    refused(collide_b(c), "lbm_ade_collide_b: scalar edge row_lo: FIXED on a PERIODIC", "2 faults: FIXED on PERIODIC + odd C, collide_b");
+    refused(part_w(c), "lbm_ade_stream_collide_part_w: scalar edge row_lo: FIXED on a PERIODIC", "2 faults: FIXED on PERIODIC + odd C, part_w");
+    refused(stream_m(c), "lbm_ade_stream_collide_w: scalar edge row_lo: FIXED on a PERIODIC", "2 faults: FIXED on PERIODIC + odd C, stream_m (BGK)");
+    refused(collide_mb(c), "lbm_ade_collide_b: scalar edge row_lo: FIXED on a PERIODIC", "2 faults: FIXED on PERIODIC + odd C, collide_mb (BGK)");
+    refused(part_m(c), "lbm_ade_stream_collide_part_w: scalar edge row_lo: FIXED on a PERIODIC", "2 faults: FIXED on PERIODIC + odd C, part_m (BGK)");
+    c = good_bgk;  // odd C + omega outside range
+    c.g.C = 7, c.fl.bgk.omega = 2.0;
+    refused(stream_w(c), "lbm_ade_stream_collide_w: C=7 must be even", "2 faults: odd C + omega, stream_w");
+    refused(collide_b(c), "lbm_ade_collide_b: C=7 must be even", "2 faults: odd C + omega, collide_b");
+    refused(part_w(c), "lbm_ade_stream_collide_part_w: C=7 must be even", "2 faults: odd C + omega, part_w");
+    refused(stream_mb(c), "lbm_ade_stream_collide_w: C=7 must be even", "2 faults: odd C + omega, stream_mb (BGK)");
+    refused(collide_m(c), "lbm_ade_collide_b: C=7 must be even", "2 faults: odd C + omega, collide_m (BGK)");
+    refused(part_m(c), "lbm_ade_stream_collide_part_w: C=7 must be even", "2 faults: odd C + omega, part_m (BGK)");
+    c = good_bgk;  // omega + omega_g outside range
+    c.fl.bgk.omega = 2.0, c.sc.omega_g = 2.5;
+    refused(stream_w(c), "lbm_ade_stream_collide_w: omega=2 outside (0, 2)", "2 faults: omega + omega_g, stream_w");
+    refused(collide_b(c), "lbm_ade_collide_b: omega=2 outside (0, 2)", "2 faults: omega + omega_g, collide_b");
+    refused(part_w(c), "lbm_ade_stream_collide_part_w: omega=2 outside (0, 2)", "2 faults: omega + omega_g, part_w");
+    refused(stream_m(c), "lbm_ade_stream_collide_w: omega=2 outside (0, 2)", "2 faults: omega + omega_g, stream_m (BGK)");
+    refused(collide_mb(c), "lbm_ade_collide_b: omega=2 outside (0, 2)", "2 faults: omega + omega_g, collide_mb (BGK)");
+    refused(part_m(c), "lbm_ade_stream_collide_part_w: omega=2 outside (0, 2)", "2 faults: omega + omega_g, part_m (BGK)");
+    c = good_bgk;  // omega_g outside range + non-finite buoyancy
+    c.sc.omega_g = 2.5, c.buoy = &bad_buoy;
+    refused(stream_w(c), "lbm_ade_stream_collide_w: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + buoyancy, stream_w");
+    refused(collide_b(c), "lbm_ade_collide_b: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + buoyancy, collide_b");
+    refused(part_w(c), "lbm_ade_stream_collide_part_w: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + buoyancy, part_w");
+    refused(stream_mb(c), "lbm_ade_stream_collide_w: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + buoyancy, stream_mb (BGK)");
+    refused(collide_mb(c), "lbm_ade_collide_b: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + buoyancy, collide_mb (BGK)");
+    c = good_bgk;  // fluid / scalar form mismatch + non-finite buoyancy
+    c.fl.bgk.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED, c.buoy = &bad_buoy;
+    refused(stream_w(c), "lbm_ade_stream_collide_w: fluid form=1 differs from the scalar form=2", "2 faults: BGK form mismatch + buoyancy, stream_w");
+    refused(collide_mb(c), "lbm_ade_collide_b: fluid form=1 differs from the scalar form=2", "2 faults: BGK form mismatch + buoyancy, collide_mb (BGK)");
+    c = good_bgk;  // non-finite buoyancy + unfinalized interior-wall table
+    c.buoy = &bad_buoy, c.walls = open_table;
+    refused(stream_w(c), "lbm_ade_stream_collide_w: buoyancy c_ref=inf", "2 faults: buoyancy + unfinalized table, stream_w");
+    refused(part_w(c), "lbm_ade_stream_collide_part_w: buoyancy c_ref=inf", "2 faults: buoyancy + unfinalized table, part_w");
+    refused(stream_mb(c), "lbm_ade_stream_collide_w: buoyancy c_ref=inf", "2 faults: buoyancy + unfinalized table, stream_mb (BGK)");
+    c = good_bgk;  // unfinalized table + NULL lattice
+    c.walls = open_table, c.lattices = false;
+    refused(stream_w(c), "lbm_ade_stream_collide_w: interior walls: the table is not finalized", "2 faults: unfinalized table + NULL lattice, stream_w");
+    refused(part_w(c), "lbm_ade_stream_collide_part_w: interior walls: the table is not finalized", "2 faults: unfinalized table + NULL lattice, part_w");
+    refused(stream_m(c), "lbm_ade_stream_collide_w: interior walls: the table is not finalized", "2 faults: unfinalized table + NULL lattice, stream_m (BGK)");
+    refused(stream_mb(c), "lbm_ade_stream_collide_w: interior walls: the table is not finalized", "2 faults: unfinalized table + NULL lattice, stream_mb (BGK)");
+    refused(part_m(c), "lbm_ade_stream_collide_part_w: interior walls: the table is not finalized", "2 faults: unfinalized table + NULL lattice, part_m (BGK)");
+    c = good_bgk;  // NULL lattice + bad row range / bad part
+    c.lattices = false, c.row_begin = 5, c.row_end = 3, c.part = 5;
+    refused(stream_w(c), "lbm_ade_stream_collide_w: NULL lattice", "2 faults: NULL lattice + bad row range, stream_w");
+    refused(stream_mb(c), "lbm_ade_stream_collide_w: NULL lattice", "2 faults: NULL lattice + bad row range, stream_mb (BGK)");
+    refused(part_w(c), "lbm_ade_stream_collide_part_w: NULL lattice", "2 faults: NULL lattice + part=5, part_w");
+    refused(part_m(c), "lbm_ade_stream_collide_part_w: NULL lattice", "2 faults: NULL lattice + part=5, part_m (BGK)");
+    c = good_bgk;  // part=5 + bad edge_rows
+    c.part = 5, c.edge_rows = 0;
+    refused(part_w(c), "lbm_ade_stream_collide_part_w: part=5", "2 faults: part=5 + edge_rows=0, part_w");
+    refused(part_m(c), "lbm_ade_stream_collide_part_w: part=5", "2 faults: part=5 + edge_rows=0, part_m (BGK)");
+
+    // ---- the KBC fluid: s2, KBC form, pressure rows; scalar walls, geometry, edges, scalar, buoyancy, interior walls; the KBC
+    // form mismatch; lattices, range or part
+    c = good_kbc;  // s2 outside range + FIXED on a PERIODIC edge
+    c.fl.kbc.s2 = 2.5, c.sbc = &fixed;
+    refused(stream_m(c), "lbm_ade_stream_collide_m: KBC fluid: s2=2.5 outside (0, 2]", "2 faults: s2 + FIXED on PERIODIC, stream_m");
+    refused(collide_m(c), "lbm_ade_collide_m: KBC fluid: s2=2.5 outside (0, 2]", "2 faults: s2 + FIXED on PERIODIC, collide_m");
+    refused(stream_mb(c), "lbm_ade_stream_collide_mb: KBC fluid: s2=2.5 outside (0, 2]", "2 faults: s2 + FIXED on PERIODIC, stream_mb");
+    refused(collide_mb(c), "lbm_ade_collide_mb: KBC fluid: s2=2.5 outside (0, 2]", "2 faults: s2 + FIXED on PERIODIC, collide_mb");
+    refused(part_m(c), "lbm_ade_stream_collide_part_m: KBC fluid: s2=2.5 outside (0, 2]", "2 faults: s2 + FIXED on PERIODIC, part_m");
+    c = good_kbc;  // pressure rows + odd C
+    c.bc = &pressure, c.g.C = 7;
+    refused(stream_m(c), "lbm_ade_stream_collide_m: pressure rows (pressure_rows=1) are not supported by the fluid + scalar step with a KBC fluid",
+            "2 faults: pressure rows + odd C, stream_m");
+    refused(collide_mb(c), "lbm_ade_collide_mb: pressure rows (pressure_rows=1)", "2 faults: pressure rows + odd C, collide_mb");
+    refused(part_m(c), "lbm_ade_stream_collide_part_m: pressure rows (pressure_rows=1)", "2 faults: pressure rows + odd C, part_m");
+    c = good_kbc;  // omega_g outside range + KBC / scalar form mismatch
+    c.sc.omega_g = 2.5, c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED;
+    refused(stream_m(c), "lbm_ade_stream_collide_m: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + KBC form mismatch, stream_m");
+    refused(collide_m(c), "lbm_ade_collide_m: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + KBC form mismatch, collide_m");
+    refused(stream_mb(c), "lbm_ade_stream_collide_mb: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + KBC form mismatch, stream_mb");
+    refused(part_m(c), "lbm_ade_stream_collide_part_m: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + KBC form mismatch, part_m");
+    c = good_kbc;  // non-finite buoyancy + KBC / scalar form mismatch
+    c.buoy = &bad_buoy, c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED;
+    refused(stream_mb(c), "lbm_ade_stream_collide_mb: buoyancy c_ref=inf", "2 faults: buoyancy + KBC form mismatch, stream_mb");
+    refused(collide_mb(c), "lbm_ade_collide_mb: buoyancy c_ref=inf", "2 faults: buoyancy + KBC form mismatch, collide_mb");
+    c = good_kbc;  // unfinalized table + KBC / scalar form mismatch
+    c.walls = open_table, c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED;
+    refused(stream_m(c), "lbm_ade_stream_collide_m: interior walls: the table is not finalized", "2 faults: unfinalized table + KBC form mismatch, stream_m");
+    refused(stream_mb(c), "lbm_ade_stream_collide_mb: interior walls: the table is not finalized", "2 faults: unfinalized table + KBC form mismatch, stream_mb");
+    refused(part_m(c), "lbm_ade_stream_collide_part_m: interior walls: the table is not finalized", "2 faults: unfinalized table + KBC form mismatch, part_m");
+    c = good_kbc;  // KBC / scalar form mismatch + NULL lattice
+    c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED, c.lattices = false;
+    refused(stream_m(c), "lbm_ade_stream_collide_m: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + NULL lattice, stream_m");
+    refused(collide_m(c), "lbm_ade_collide_m: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + NULL lattice, collide_m");
+    refused(stream_mb(c), "lbm_ade_stream_collide_mb: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + NULL lattice, stream_mb");
+    refused(collide_mb(c), "lbm_ade_collide_mb: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + NULL lattice, collide_mb");
+    refused(part_m(c), "lbm_ade_stream_collide_part_m: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + NULL lattice, part_m");
+    c = good_kbc;  // KBC / scalar form mismatch + part=5
+    c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED, c.part = 5;
+    refused(part_m(c), "lbm_ade_stream_collide_part_m: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + part=5, part_m");
+    c = good_kbc;  // NULL lattice + bad row range
+    c.lattices = false, c.row_begin = 5, c.row_end = 3;
+    refused(stream_m(c), "lbm_ade_stream_collide_m: NULL lattice", "2 faults: NULL lattice + bad row range, stream_m");
+    refused(stream_mb(c), "lbm_ade_stream_collide_mb: NULL lattice", "2 faults: NULL lattice + bad row range, stream_mb");
+    c = good_kbc;  // part=5 + bad edge_rows
+    c.part = 5, c.edge_rows = 0;
+    refused(part_m(c), "lbm_ade_stream_collide_part_m: part=5", "2 faults: part=5 + edge_rows=0, part_m");
+    lbm_ade_iwalls_destroy(open_table);
   }
   std::printf("ade_kbc_host_check: %d refusals checked, %d failures\n", checks, failures);
   return failures ? 1 : 0;

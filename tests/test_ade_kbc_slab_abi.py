@@ -192,13 +192,13 @@ def test_header_with_the_new_prototypes_is_plain_c99(tmp_path):
 
 
 def test_the_extended_host_check_program_passes():
-    """the ORDINARY build of drivers/ade_kbc_host_check: the refusals of the part call and of the ring entries from C++, 72
-    in all, 40 of them from before the slab entries.  The sanitizer build of the same source is `make san`'s and is not
-    run here; this test only holds the recipe to naming it"""
+    """the ORDINARY build of drivers/ade_kbc_host_check: the refusals of the part call and of the ring entries from C++, 160
+    in all -- 40 of them from before the slab entries, 65 of them calls with two faults that pin which one is reported.  The
+    sanitizer build of the same source is `make san`'s and is not run here; this test only holds the recipe to naming it"""
     exe = os.path.join(ROOT, "lattice-boltzmann-method_amd", "drivers", "bin", "ade_kbc_host_check")
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     m = re.search(r"(\d+) refusals checked, 0 failures", r.stdout)
-    assert m and int(m.group(1)) >= 72, r.stdout
+    assert m and int(m.group(1)) >= 160, r.stdout
     root_make = open(os.path.join(ROOT, "Makefile")).read()
     assert "bin_san/ade_kbc_host_check" in root_make  # `make san` builds and runs it
