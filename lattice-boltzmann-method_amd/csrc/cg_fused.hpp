@@ -23,7 +23,7 @@
 namespace lbm {
 
 struct CgFast {
-  double inv_rho0[2], qc[2], beta[2];
+  double rho0[2], inv_rho0[2], qc[2], beta[2];
   double phi0[2], phi1[2], phi5[2];  // phi by |c|^2 class (colour.cpp:49-64)
   double eta1[2], eta5[2];
   double sigma, Gr, Gc;
@@ -34,6 +34,7 @@ struct CgFast {
 inline CgFast make_cg_fast(const CgConsts& c) {
   CgFast f;
   for (int k = 0; k < 2; ++k) {
+    f.rho0[k] = c.k[k].rho_0;
     f.inv_rho0[k] = 1.0 / c.k[k].rho_0;
     f.qc[k] = c.k[k].qcoef;
     f.beta[k] = c.k[k].beta;
@@ -159,13 +160,12 @@ __device__ __forceinline__ double cg_ddcol(const double (*s)[LDC], int tr, int t
 // the four stencil results; writes both colours (and the observable fields on request)
 // cg_collide_values: the post-collision populations of both colours as values (the two-step kernel keeps level 1's in LDS);
 // cg_collide_store: the same, stored.
-__device__ __forceinline__ void cg_collide_values(
+__device__ __forceinline__ void cg_collide_core(
     const double (&ft)[Q], const CgNode& me, double gx, double gy, double dxqx, double dyqy,
-    const CgFast& cf, double (&out_r)[Q], double (&out_b)[Q], double& s_nu_out) {
+    const CgFast& cf, double s_nu, double (&out_r)[Q], double (&out_b)[Q]) {
 #pragma clang fp contract(on)
   const double rr = me.rr, rb = me.rb, ux = me.ux, uy = me.uy, irt = me.irt;
   const double rt = rr + rb;
-  const double s_nu = cg_snu_fast(cf, me.psi);
   constexpr double W0 = 4.0 / 9.0, W1 = 1.0 / 9.0, W5 = 1.0 / 36.0;
   constexpr double B0 = -4.0 / 27.0, B1 = 2.0 / 27.0, B5 = 5.0 / 108.0;  // :158-163
 
@@ -255,17 +255,98 @@ __device__ __forceinline__ void cg_collide_values(
     out_r[q] = (xr * tot[q] + cf.beta[0] * kap[q]) + src[q];
     out_b[q] = (xb * tot[q] + cf.beta[1] * kap[q]) + src[q];
   }
-  s_nu_out = s_nu;
+}
+__device__ __forceinline__ void cg_collide_values(
+    const double (&ft)[Q], const CgNode& me, double gx, double gy, double dxqx, double dyqy,
+    const CgFast& cf, double (&out_r)[Q], double (&out_b)[Q], double& s_nu_out) {
+  s_nu_out = cg_snu_fast(cf, me.psi);
+  cg_collide_core(ft, me, gx, gy, dxqx, dyqy, cf, s_nu_out, out_r, out_b);
 }
 
+// The relaxation rate of node (r, c) for the collision, and psi as the node reports it.  Outside the blend band the rate
+// is one of the two colours' constants.  Inside it, |psi| <= delta, s_nu(psi) has a slope of up to 2 |s_1 - omega_k| / delta
+// (30 at density ratio 100): the one or two units of rounding error that rho_r and rho_b carry become up to 130 units of
+// s_nu, in the reference order too (profiles/cg_accuracy.txt).  There -- about one node per interface column, so almost
+// every wave skips the branch -- the node's 18 populations are gathered once more (L2 hits), summed together with their
+// rounding errors (cascaded TwoSum) and rho_r rho_0b -+ rho_b rho_0r formed with the products' (fma): psi to a tenth of a
+// unit, s_nu to about 2 units.  me.psi becomes that value; the stencils keep the psi every node reduction computes, so
+// nothing depends on which tile a node is reduced in.  Every kernel comes through cg_snu_node or cg_psi_node (the two-step
+// kernel's second level, whose populations are in LDS, through cg_psi_compensated on the same 18 values in the same order).
+__device__ __forceinline__ void cg_two_sum(double& s, double& e, double x) {
+  const double t = s + x, z = t - s;
+  e += (s - (t - z)) + (x - z);
+  s = t;
+}
+// psi from the two colours' sums with their rounding errors (sr + er, sb + eb): the band's value
+__device__ __forceinline__ double cg_psi_compensated(double sr, double er, double sb, double eb, const CgFast& cf) {
+#pragma clang fp contract(on)
+  const double pr = sr * cf.rho0[1], pb = sb * cf.rho0[0];
+  const double lr = __builtin_fma(sr, cf.rho0[1], -pr) + er * cf.rho0[1];
+  const double lb = __builtin_fma(sb, cf.rho0[0], -pb) + eb * cf.rho0[0];
+  return ((pr - pb) + (lr - lb)) / ((pr + pb) + (lr + lb));
+}
+// the band's psi of node (r, c), its populations gathered again
+template <bool INTERIOR>
+__device__ __forceinline__ double cg_psi_band(const double* __restrict__ in_r, const double* __restrict__ in_b, const Geom& g,
+                                              const Bc& bc, const CgFast& cf, int r, int c) {
+  double sr = 0.0, er = 0.0, sb = 0.0, eb = 0.0;
+  if (INTERIOR) {
+    // rolled, one population of each colour at a time: unrolled, the 18 loads and their addresses are all in flight at
+    // once and take the registers of the collision behind the branch (scratch in the 16 x 64 tile kernel)
+    const long o = g.at(r, c);
+#pragma unroll 1
+    for (int q = 0; q < Q; ++q) {
+      const long a = q * g.plane + (o - icx(q) * g.P - icy(q));
+      cg_two_sum(sr, er, in_r[a]);
+      cg_two_sum(sb, eb, in_b[a]);
+    }
+  } else {
+    double fr[Q], fb[Q];
+    gather_bc(fr, in_r, g, bc, r, c);
+    gather_bc(fb, in_b, g, bc, r, c);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      cg_two_sum(sr, er, fr[q]);
+      cg_two_sum(sb, eb, fb[q]);
+    }
+  }
+  return cg_psi_compensated(sr, er, sb, eb, cf);
+}
+// The rate of the node and, in me.psi, the psi it reports.  For every finite psi this is cg_snu_fast of the psi that
+// cg_psi_node returns -- outside the band cg_snu_fast is one of the two constants too --, without the two polynomials and
+// four selects on the way of the nodes outside the band.  A psi that is not finite (rho_r = rho_b = 0: everything of
+// such a node is NaN) gives b_omega here and 0 from cg_snu_fast; nothing finite depends on it.
+template <bool INTERIOR>
+__device__ __forceinline__ double cg_snu_node(CgNode& me, const double* __restrict__ in_r, const double* __restrict__ in_b,
+                                              const Geom& g, const Bc& bc, const CgFast& cf, int r, int c) {
+#pragma clang fp contract(on)
+  double s_nu = me.psi > 0.0 ? cf.r_omega : cf.b_omega;
+  if (fabs(me.psi) <= cf.delta) {
+    const double psi = cg_psi_band<INTERIOR>(in_r, in_b, g, bc, cf, r, c);
+    me.psi = psi;
+    s_nu = cg_snu_fast(cf, psi);
+  }
+  return s_nu;
+}
+// The same psi for the kernels that keep the rate inside their collision (cg_collide_store / cg_collide_values: the kernels of
+// the EXPERIMENTS build): me.psi = cg_psi_node(me.psi, ...) before the call gives the bits of cg_snu_node.
+template <bool INTERIOR>
+__device__ __forceinline__ double cg_psi_node(double psi, const double* __restrict__ in_r, const double* __restrict__ in_b,
+                                              const Geom& g, const Bc& bc, const CgFast& cf, int r, int c) {
+  if (fabs(psi) <= cf.delta) psi = cg_psi_band<INTERIOR>(in_r, in_b, g, bc, cf, r, c);
+  return psi;
+}
+
+// cg_collide_store_s: with the rate given (cg_snu_node); cg_collide_store: with cg_snu_fast of me.psi, which the caller
+// has passed through cg_psi_node
 template <bool WITH_FIELDS>
-__device__ __forceinline__ void cg_collide_store(
+__device__ __forceinline__ void cg_collide_store_s(
     const double (&ft)[Q], const CgNode& me, double gx, double gy, double dxqx, double dyqy,
-    const CgFast& cf, const Geom& g, const MacroIdx& mi, int r, int c, double* __restrict__ pn_r,
+    const CgFast& cf, double s_nu, const Geom& g, const MacroIdx& mi, int r, int c, double* __restrict__ pn_r,
     double* __restrict__ pn_b, double* __restrict__ rho_r_out, double* __restrict__ rho_b_out,
     double* __restrict__ u_out, double* __restrict__ psi_out, double* __restrict__ snu_out) {
-  double out_r[Q], out_b[Q], s_nu;
-  cg_collide_values(ft, me, gx, gy, dxqx, dyqy, cf, out_r, out_b, s_nu);
+  double out_r[Q], out_b[Q];
+  cg_collide_core(ft, me, gx, gy, dxqx, dyqy, cf, s_nu, out_r, out_b);
   const long lo = g.at(r, c);
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
@@ -283,6 +364,15 @@ __device__ __forceinline__ void cg_collide_store(
     psi_out[oo] = me.psi;
     snu_out[oo] = s_nu;
   }
+}
+template <bool WITH_FIELDS>
+__device__ __forceinline__ void cg_collide_store(
+    const double (&ft)[Q], const CgNode& me, double gx, double gy, double dxqx, double dyqy,
+    const CgFast& cf, const Geom& g, const MacroIdx& mi, int r, int c, double* __restrict__ pn_r,
+    double* __restrict__ pn_b, double* __restrict__ rho_r_out, double* __restrict__ rho_b_out,
+    double* __restrict__ u_out, double* __restrict__ psi_out, double* __restrict__ snu_out) {
+  cg_collide_store_s<WITH_FIELDS>(ft, me, gx, gy, dxqx, dyqy, cf, cg_snu_fast(cf, me.psi), g, mi, r, c, pn_r, pn_b,
+                                  rho_r_out, rho_b_out, u_out, psi_out, snu_out);
 }
 
 // The tiles of a launch split into an INNER rectangle and the FRAME around it (CgTileRect, cg_plan.hpp).  MODE 0: all
@@ -385,11 +475,13 @@ __device__ __forceinline__ void cg_fused_body(
   __syncthreads();
   if (!INNER && (r >= row_end || c >= g.C)) return;
 
+  // the rate first: here only the node's own sums are live, so the band's branch finds free registers
+  const double s_nu = cg_snu_node<INNER>(me, in_r, in_b, g, bc, cf, r, c);
   const double gx = cg_ddrow<LDC>(s_psi, tr, tc), gy = cg_ddcol<LDC>(s_psi, tr, tc);
   const double dxqx = cg_ddrow<LDC>(s_qx, tr, tc), dyqy = cg_ddcol<LDC>(s_qy, tr, tc);
 
-  cg_collide_store<WITH_FIELDS>(ft, me, gx, gy, dxqx, dyqy, cf, g, mi, r, c, pn_r, pn_b, rho_r_out,
-                                rho_b_out, u_out, psi_out, snu_out);
+  cg_collide_store_s<WITH_FIELDS>(ft, me, gx, gy, dxqx, dyqy, cf, s_nu, g, mi, r, c, pn_r, pn_b, rho_r_out,
+                                  rho_b_out, u_out, psi_out, snu_out);
 }
 
 template <int TR, int TC, int WAVES, bool WITH_FIELDS, int MODE = 0>
@@ -539,23 +631,26 @@ __global__ __launch_bounds__(NT, MINB) void k_cg_tile_mn(
     // recomputed per node instead of waiting in ten register pairs
     CgFast cfk = cf;
     asm volatile("" : "+s"(cfk.Gr), "+s"(cfk.Gc));
-    double fk[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) fk[q] = (PARK && j > 0) ? s_park[j > 0 ? j - 1 : 0][q][threadIdx.x] : ft[PARK ? 0 : j][q];
     CgNode me;  // == cg_node's expressions on the held sums
     me.rr = rr[j];
     me.rb = rb[j];
+    me.psi = s_psi[tr + 2][tc + 2];
+    // the rate first: nothing else of this node is live yet, so the band's branch finds free registers (placed behind the
+    // node's velocity it cost 0.5 % of the step, here 0.2 %: profiles/cg_accuracy.txt)
+    const double s_nu = cg_snu_node<true>(me, in_r, in_b, g, Bc{}, cfk, r_base + tr, c_base + tc);
+    double fk[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) fk[q] = (PARK && j > 0) ? s_park[j > 0 ? j - 1 : 0][q][threadIdx.x] : ft[PARK ? 0 : j][q];
     const double jx = ((fk[1] - fk[3]) + (fk[5] - fk[6])) + (fk[8] - fk[7]);
     const double jy = ((fk[2] - fk[4]) + (fk[5] - fk[8])) + (fk[6] - fk[7]);
     me.irt = 1.0 / (me.rr + me.rb);
     me.ux = (jx + 0.5 * cfk.Gr) * me.irt;
     me.uy = (jy + 0.5 * cfk.Gc) * me.irt;
-    me.psi = s_psi[tr + 2][tc + 2];
     me.qx = me.qy = 0.0;  // not used by the collision
     const double gx = cg_ddrow<LDC>(s_psi, tr, tc), gy = cg_ddcol<LDC>(s_psi, tr, tc);
     const double dxqx = cg_ddrow<LDC>(s_qx, tr, tc), dyqy = cg_ddcol<LDC>(s_qy, tr, tc);
-    cg_collide_store<WITH_FIELDS>(fk, me, gx, gy, dxqx, dyqy, cfk, g, mi, r_base + tr, c_base + tc, pn_r, pn_b,
-                                  rho_r_out, rho_b_out, u_out, psi_out, snu_out);
+    cg_collide_store_s<WITH_FIELDS>(fk, me, gx, gy, dxqx, dyqy, cfk, s_nu, g, mi, r_base + tr, c_base + tc, pn_r, pn_b,
+                                    rho_r_out, rho_b_out, u_out, psi_out, snu_out);
     if (j + 1 < NPT) __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -740,9 +835,16 @@ __global__ __launch_bounds__(TR* WC * 64, PF ? 3 : 4) void k_cg_walk(
     __syncthreads();  // the fields of rows Rk - 2 .. Rk + TR + 1 are in the ring
     // (no second barrier: the next step's rows take the slots of rows Rk - TR - 2 .. Rk - 3, which nobody reads any more,
     // and no wave gets two steps ahead -- it would have to pass the next barrier first)
-    if (PF && k + 1 < n_steps) issue(k + 1);
     const int m = parks ? tr - (TR - 2) : tr + 2;  // this thread collides row Rk + m
-    if (k >= 0 && lane_out && Rk + m < R1) {
+    const bool collides = k >= 0 && lane_out && Rk + m < R1;
+    // the rate BEFORE the prefetch: the band's loads are waited for, and vmcnt counts in order -- behind issue(k + 1) that
+    // wait would cover the whole prefetch
+    CgNode me;
+    me.psi = n6[5];
+    double s_nu = 0.0;
+    if (collides) s_nu = cg_snu_node<true>(me, in_r, in_b, g, Bc{}, cfl, Rk + m, c_base - 2 + l);
+    if (PF && k + 1 < n_steps) issue(k + 1);
+    if (collides) {
       int rs[5];
 #pragma unroll
       for (int i = 0; i < 5; ++i) {
@@ -773,12 +875,10 @@ __global__ __launch_bounds__(TR* WC * 64, PF ? 3 : 4) void k_cg_walk(
         dyqy += c1 * (s_qy[sl][l0 + 3] - s_qy[sl][l0 + 1]);
         sl = sl + 1 >= NR ? 0 : sl + 1;
       }
-      CgNode me;
-      me.rr = n6[0]; me.rb = n6[1]; me.ux = n6[2]; me.uy = n6[3]; me.irt = n6[4]; me.psi = n6[5];
+      me.rr = n6[0]; me.rb = n6[1]; me.ux = n6[2]; me.uy = n6[3]; me.irt = n6[4];
       me.qx = 0.0;
       me.qy = 0.0;
-      double s_nu;
-      cg_collide_values(ft, me, gx, gy, dxqx, dyqy, cfl, out_r, out_b, s_nu);
+      cg_collide_core(ft, me, gx, gy, dxqx, dyqy, cfl, s_nu, out_r, out_b);
       if (WITH_FIELDS) {
         of[0] = me.rr; of[1] = me.rb; of[2] = me.ux; of[3] = me.uy; of[4] = me.psi; of[5] = s_nu;
       }

@@ -100,6 +100,7 @@ __global__ __launch_bounds__(64 * W, 2) void k_cg_strip5(
       CgNode me;
       me.rr = rn[2][0]; me.rb = rn[2][1]; me.ux = rn[2][2]; me.uy = rn[2][3]; me.irt = rn[2][4]; me.psi = rn[2][5];
       me.qx = 0.0; me.qy = 0.0;
+      me.psi = cg_psi_node<true>(me.psi, in_r, in_b, g, Bc{}, cf, r, c);
       cg_collide_store<WITH_FIELDS>(fc, me, gx, gy, dxqx, dyqy, cf, g, mi, r, c, pn_r, pn_b, rho_r_out, rho_b_out,
                                     u_out, psi_out, snu_out);
     }

@@ -148,6 +148,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_cg_strip(
         dyqy += a0[ii] * (s_qy[sl][lane + 4] - s_qy[sl][lane]);
         dyqy += a1[ii] * (s_qy[sl][lane + 3] - s_qy[sl][lane + 1]);
       }
+      me.psi = cg_psi_node<false>(me.psi, in_r, in_b, g, bc, cf, r, c);  // (gather_bc of a plain node is the plain gather)
       cg_collide_store<WITH_FIELDS>(ft, me, gx, gy, dxqx, dyqy, cf, g, mi, r, c, pn_r, pn_b, rho_r_out,
                                     rho_b_out, u_out, psi_out, snu_out);
     }
@@ -251,6 +252,7 @@ __device__ __forceinline__ void cg_strip2_iter(
   CgNode me;
   me.rr = rn[KC][0]; me.rb = rn[KC][1]; me.ux = rn[KC][2]; me.uy = rn[KC][3]; me.irt = rn[KC][4]; me.psi = rn[KC][5];
   me.qx = 0.0; me.qy = 0.0;
+  me.psi = cg_psi_node<true>(me.psi, in_r, in_b, g, Bc{}, cf, r, c);
   cg_collide_store<WITH_FIELDS>(fc, me, gx, gy, dxqx, dyqy, cf, g, mi, r, c, pn_r, pn_b, rho_r_out, rho_b_out,
                                 u_out, psi_out, snu_out);
 }
@@ -389,6 +391,7 @@ __device__ __forceinline__ void cg_strip3_iter(
   CgNode me;
   me.rr = rn[KC][0]; me.rb = rn[KC][1]; me.ux = rn[KC][2]; me.uy = rn[KC][3]; me.irt = rn[KC][4]; me.psi = rn[KC][5];
   me.qx = 0.0; me.qy = 0.0;
+  me.psi = cg_psi_node<true>(me.psi, in_r, in_b, g, Bc{}, cf, r, c);
   cg_collide_store<WITH_FIELDS>(fc, me, gx, gy, dxqx, dyqy, cf, g, mi, r, c, pn_r, pn_b, rho_r_out, rho_b_out,
                                 u_out, psi_out, snu_out);
 }
@@ -532,6 +535,7 @@ __device__ __forceinline__ void cg_strip4_iter(
     CgNode me;
     me.rr = rn[KC][0]; me.rb = rn[KC][1]; me.ux = rn[KC][2]; me.uy = rn[KC][3]; me.irt = rn[KC][4]; me.psi = rn[KC][5];
     me.qx = 0.0; me.qy = 0.0;
+    me.psi = cg_psi_node<true>(me.psi, in_r, in_b, g, Bc{}, cf, r, c);
     cg_collide_store<WITH_FIELDS>(fc, me, gx, gy, dxqx, dyqy, cf, g, mi, r, c, pn_r, pn_b, rho_r_out, rho_b_out,
                                   u_out, psi_out, snu_out);
   }

@@ -114,6 +114,7 @@ __device__ __forceinline__ void cg_two_step_iter(CgX2Lds<W>& L, double (&raw_r)[
     CgNode me;
     me.rr = n1[2][0]; me.rb = n1[2][1]; me.ux = n1[2][2]; me.uy = n1[2][3]; me.irt = n1[2][4]; me.psi = n1[2][5];
     me.qx = 0.0; me.qy = 0.0;
+    me.psi = cg_psi_node<true>(me.psi, in_r, in_b, g, Bc{}, cf, R0 - 10 + i, cl);  // row m1 - 2: the band's psi, as a single step takes it
     cg_collide_values(s1[2], me, gx, gy, dxqx, dyqy, cf, o_r, o_b, snu1);
   }
   if (STEADY) {
@@ -150,11 +151,11 @@ __device__ __forceinline__ void cg_two_step_iter(CgX2Lds<W>& L, double (&raw_r)[
 #pragma unroll
   for (int q = 0; q < 6; ++q) n2[2][q] = n2[1][q], n2[1][q] = n2[0][q];
   if (STEADY || i >= 6) {
-    const int sb = 1 + ((i - 1) & 1), sc = 3 + (i - 2) % 3;
+    const int sb_ = 1 + ((i - 1) & 1), sc_ = 3 + (i - 2) % 3;
     double fr[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-      const int slot = icx(q) == -1 ? 0 : (icx(q) == 0 ? sb : sc);
+      const int slot = icx(q) == -1 ? 0 : (icx(q) == 0 ? sb_ : sc_);
       int lsrc = gl - icy(q);
       lsrc = lsrc < 0 ? 0 : (lsrc > LN - 1 ? LN - 1 : lsrc);
       fr[q] = L.p1[0][slot][sw_grp_pos(q)][lsrc];
@@ -166,6 +167,21 @@ __device__ __forceinline__ void cg_two_step_iter(CgX2Lds<W>& L, double (&raw_r)[
     L.ring2[0][slot][gl] = psi;
     L.ring2[1][slot][gl] = qx;
     L.ring2[2][slot][gl] = qy;
+    // the band's psi of this level-2 node (cg_psi_node of a single step): its 18 streamed populations are the level-1 results
+    // in LDS, not in the lattice -- the same values in the same order through the same sums.  The ring keeps the plain psi
+    // (the stencils'), the node's own copy waits for its collision three iterations on.
+    if (fabs(psi) <= cf.delta) {
+      double sr = 0.0, er = 0.0, sb = 0.0, eb = 0.0;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const int pslot = icx(q) == -1 ? 0 : (icx(q) == 0 ? sb_ : sc_);
+        int lsrc = gl - icy(q);
+        lsrc = lsrc < 0 ? 0 : (lsrc > LN - 1 ? LN - 1 : lsrc);
+        cg_two_sum(sr, er, L.p1[0][pslot][sw_grp_pos(q)][lsrc]);
+        cg_two_sum(sb, eb, L.p1[1][pslot][sw_grp_pos(q)][lsrc]);
+      }
+      n2[0][5] = cg_psi_compensated(sr, er, sb, eb, cf);
+    }
   }
 }
 

@@ -112,6 +112,7 @@ __global__ __launch_bounds__(512, 4) void k_cg_walk_tile(
     me.qx = me.qy = 0.0;
     const double gx = cg_ddrow_ring<LDC>(s_psi, rs, tc), gy = cg_ddcol_ring<LDC>(s_psi, rs, tc);
     const double dxqx = cg_ddrow_ring<LDC>(s_qx, rs, tc), dyqy = cg_ddcol_ring<LDC>(s_qy, rs, tc);
+    me.psi = cg_psi_node<true>(me.psi, in_r, in_b, g, Bc{}, cfk, R0 + rho, c_base + tc);
     cg_collide_store<WITH_FIELDS>(fk, me, gx, gy, dxqx, dyqy, cfk, g, mi, R0 + rho, c_base + tc, pn_r, pn_b, rho_r_out,
                                   rho_b_out, u_out, psi_out, snu_out);
   };

@@ -1060,25 +1060,36 @@ void orc_cg_init_droplet(const orc_cg_params* p, double* f_r, double* f_b, doubl
     }
 }
 
-void orc_cg_steps(const orc_cg_params* p, double* f_r, double* f_b, double* rho_r, double* rho_b,
-                  double* u, int nsteps, double* psi_out, double* snu_out, double* col_r_out,
-                  double* col_b_out) {
-  const int R = p->R, C = p->C;
-  const size_t N = (size_t)R * C;
-  small_grid_guard sg(N);
-  const colour_consts kr(p->red), kb(p->blue);
-  const relax_fn relax(kr, kb, p->delta);
-  const double g_r = p->g_r, g_c = p->g_c, sigma = p->sigma;
-  std::vector<double> rho(N), psi(N, 0.0), snu(N, 0.0), Qx(N), Qy(N), DxQx_r(N), DyQy_r(N),
-      DxQx_b(N), DyQy_b(N), gx(N), gy(N), col_r(N * 9), col_b(N * 9);
-  for (size_t i = 0; i < N; ++i) rho[i] = rho_r[i] + rho_b[i];  // :407 / :474
+namespace {
+// the loop body of main() (:431-477) in its two halves; orc_cg_steps runs collide then stream (the driver's order),
+// orc_cg_step_from_post stream then collide (the order of a GPU step, whose state is the post-collision populations)
+struct cg_loop {
+  const orc_cg_params* p;
+  const int R, C;
+  const size_t N;
+  small_grid_guard sg;
+  const colour_consts kr, kb;
+  const relax_fn relax;
+  const double g_r, g_c, sigma;
+  std::vector<double> rho, psi, snu, Qx, Qy, DxQx_r, DyQy_r, DxQx_b, DyQy_b, gx, gy, col_r, col_b;
   double unitx[9], unity[9];  // :176-178
-  for (int q = 0; q < 9; ++q) {
-    const double d = (q < 5) ? 1.0 : std::sqrt(2);
-    unitx[q] = CX[q] / d;
-    unity[q] = CY[q] / d;
+  explicit cg_loop(const orc_cg_params* p_)
+      : p(p_), R(p_->R), C(p_->C), N((size_t)p_->R * p_->C), sg(N), kr(p_->red), kb(p_->blue),
+        relax(kr, kb, p_->delta), g_r(p_->g_r), g_c(p_->g_c), sigma(p_->sigma), rho(N), psi(N, 0.0),
+        snu(N, 0.0), Qx(N), Qy(N), DxQx_r(N), DyQy_r(N), DxQx_b(N), DyQy_b(N), gx(N), gy(N),
+        col_r(N * 9), col_b(N * 9) {
+    for (int q = 0; q < 9; ++q) {
+      const double d = (q < 5) ? 1.0 : std::sqrt(2);
+      unitx[q] = CX[q] / d;
+      unity[q] = CY[q] / d;
+    }
   }
-  for (int t = 0; t < nsteps; ++t) {
+  void total_rho(const double* rho_r, const double* rho_b) {  // :407 / :474
+    for (size_t i = 0; i < N; ++i) rho[i] = rho_r[i] + rho_b[i];
+  }
+  // :431-464: col_r, col_b, psi, snu from the streamed populations and their fields (rho = rho_r + rho_b)
+  void collide(const double* f_r, const double* f_b, const double* rho_r, const double* rho_b,
+               const double* u) {
     // :434-435 phase field and relaxation blend
 #pragma omp parallel for schedule(static)
     for (long i = 0; i < (long)N; ++i) {
@@ -1148,6 +1159,9 @@ void orc_cg_steps(const orc_cg_params* p, double* f_r, double* f_b, double* rho_
         cb[q] = p->add_source ? o3b + Fq : o3b;  // :464 / :514
       }
     }
+  }
+  // :466-477: stream + boundaries into f_r, f_b, then their moments
+  void stream(double* f_r, double* f_b, double* rho_r, double* rho_b, double* u) {
     advect(f_r, col_r.data(), R, C);  // :466-467
     advect(f_b, col_b.data(), R, C);
     cg_boundary(f_r, col_r.data(), R, C);  // :469-470
@@ -1167,10 +1181,36 @@ void orc_cg_steps(const orc_cg_params* p, double* f_r, double* f_b, double* rho_
       u[2 * i + 1] = jy / rho[i] + 0.5 * g_c / rho[i];
     }
   }
-  if (psi_out) std::memcpy(psi_out, psi.data(), N * sizeof(double));
-  if (snu_out) std::memcpy(snu_out, snu.data(), N * sizeof(double));
-  if (col_r_out) std::memcpy(col_r_out, col_r.data(), N * 9 * sizeof(double));
-  if (col_b_out) std::memcpy(col_b_out, col_b.data(), N * 9 * sizeof(double));
+  void copy_out(double* psi_out, double* snu_out, double* col_r_out, double* col_b_out) const {
+    if (psi_out) std::memcpy(psi_out, psi.data(), N * sizeof(double));
+    if (snu_out) std::memcpy(snu_out, snu.data(), N * sizeof(double));
+    if (col_r_out) std::memcpy(col_r_out, col_r.data(), N * 9 * sizeof(double));
+    if (col_b_out) std::memcpy(col_b_out, col_b.data(), N * 9 * sizeof(double));
+  }
+};
+}  // namespace
+
+void orc_cg_steps(const orc_cg_params* p, double* f_r, double* f_b, double* rho_r, double* rho_b,
+                  double* u, int nsteps, double* psi_out, double* snu_out, double* col_r_out,
+                  double* col_b_out) {
+  cg_loop lp(p);
+  lp.total_rho(rho_r, rho_b);
+  for (int t = 0; t < nsteps; ++t) {
+    lp.collide(f_r, f_b, rho_r, rho_b, u);
+    lp.stream(f_r, f_b, rho_r, rho_b, u);
+  }
+  lp.copy_out(psi_out, snu_out, col_r_out, col_b_out);
+}
+
+void orc_cg_step_from_post(const orc_cg_params* p, const double* p_r, const double* p_b, double* f_r,
+                           double* f_b, double* rho_r, double* rho_b, double* u, double* psi_out,
+                           double* snu_out, double* col_r_out, double* col_b_out) {
+  cg_loop lp(p);
+  std::memcpy(lp.col_r.data(), p_r, lp.N * 9 * sizeof(double));
+  std::memcpy(lp.col_b.data(), p_b, lp.N * 9 * sizeof(double));
+  lp.stream(f_r, f_b, rho_r, rho_b, u);
+  lp.collide(f_r, f_b, rho_r, rho_b, u);
+  lp.copy_out(psi_out, snu_out, col_r_out, col_b_out);
 }
 
 // ---------------------------------------------------------------------------------

@@ -123,6 +123,13 @@ void orc_cg_init_droplet(const orc_cg_params* p, double* f_r, double* f_b,
 void orc_cg_steps(const orc_cg_params* p, double* f_r, double* f_b, double* rho_r,
                   double* rho_b, double* u, int nsteps, double* psi_out, double* snu_out,
                   double* col_r_out, double* col_b_out);
+/* The same loop body rotated to the order of a GPU step: from the post-collision populations p_r, p_b
+ * (read only) stream + boundaries -> f_r, f_b, their moments -> rho_r, rho_b, u, then one collision ->
+ * psi, s_nu, col_r / col_b (each output may be NULL except f, rho, u).  Both entries call the same two
+ * functions: fed the col of orc_cg_steps(n), it returns the col, psi and s_nu of orc_cg_steps(n + 1). */
+void orc_cg_step_from_post(const orc_cg_params* p, const double* p_r, const double* p_b, double* f_r,
+                           double* f_b, double* rho_r, double* rho_b, double* u, double* psi_out,
+                           double* snu_out, double* col_r_out, double* col_b_out);
 
 /* ---- immersed boundary (src/ibm.cpp) + cylinder driver (test/cylinder_test.cpp) ---- */
 typedef struct {

@@ -269,6 +269,20 @@ class Oracle:
             s.update(col_r=col_r, col_b=col_b)
         return s
 
+    def cg_step_from_post(self, p, p_r, p_b):
+        """orc_cg_step_from_post: one step in the order of a GPU step, from the post-collision populations [R, C, 9]:
+        f_r, f_b (streamed), rho_r, rho_b, u, psi, s_nu and the new post-collision populations col_r, col_b"""
+        R, C = p.R, p.C
+        p_r, p_b = _c(p_r), _c(p_b)
+        assert p_r.shape == p_b.shape == (R, C, 9)
+        s = dict(f_r=np.empty((R, C, 9)), f_b=np.empty((R, C, 9)), rho_r=np.empty((R, C)), rho_b=np.empty((R, C)),
+                 u=np.empty((R, C, 2)), psi=np.empty((R, C)), s_nu=np.empty((R, C)), col_r=np.empty((R, C, 9)),
+                 col_b=np.empty((R, C, 9)))
+        self.lib.orc_cg_step_from_post(ct.byref(p), _p(p_r), _p(p_b), _p(s["f_r"]), _p(s["f_b"]), _p(s["rho_r"]),
+                                       _p(s["rho_b"]), _p(s["u"]), _p(s["psi"]), _p(s["s_nu"]), _p(s["col_r"]),
+                                       _p(s["col_b"]))
+        return s
+
     # -- IBM ------------------------------------------------------------------
     @staticmethod
     def _markers(x, y, m_max=5):

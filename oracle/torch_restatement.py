@@ -126,22 +126,55 @@ def cg_run(R, C, red, blue, sigma, gravity, steps, delta=0.1, droplet=False):
                 else:
                     ans = (1.0 if rr < s else 0.0) if invert else (1.0 if rr >= s else 0.0)
                 k.rho[rr, c, 0] = k.rho_0 * ans
-    relax = relaxation_function(r, b, delta)
     u = torch.zeros(R, C, 2)
-    s_nu = torch.zeros(R, C)
-    S = torch.diagflat(torch.tensor([0.0, 1.25, 1.14, 0.0, 1.6, 0.0, 1.6, 0.0, 0.0])).repeat(R, C, 1, 1)
     Fg = torch.tensor([[0.0], [gravity]]) if droplet else torch.tensor([[gravity], [0.0]])
-    rho = r.rho + b.rho
     if droplet:
-        u = u + 0.5 * Fg.t() / rho  # mrtcg_static_droplet.cpp:457
+        u = u + 0.5 * Fg.t() / (r.rho + b.rho)  # mrtcg_static_droplet.cpp:457
     r.adv_f = eval_equilibrium(r.rho, r.phi, r.eta, u)
     b.adv_f = eval_equilibrium(b.rho, b.phi, b.eta, u)
-    phase = torch.zeros(R, C, 1)
+    loop = CgLoop(r, b, sigma, Fg, delta, add_source=not droplet)
+    loop.u = u
     for _ in range(steps):
+        loop.collide()
+        loop.stream()
+    return loop.result()
+
+
+def cg_step_from_post(p_r, p_b, red, blue, sigma, Fg, delta=0.1, add_source=True):
+    """the same loop body in the order of a GPU step, from post-collision populations p_r, p_b [R, C, 9] (numpy): stream +
+    boundaries and moments (:466-477), then one collision (:431-464).  Fg = (row, column) components.  Returns f_r, f_b
+    (streamed), rho_r, rho_b, u, psi, s_nu and the new post-collision col_r, col_b."""
+    R, C = p_r.shape[:2]
+    r, b = Colour(*red, R, C), Colour(*blue, R, C)
+    loop = CgLoop(r, b, sigma, torch.tensor([[float(Fg[0])], [float(Fg[1])]]), delta, add_source)
+    loop.r_col, loop.b_col = torch.from_numpy(p_r.copy()), torch.from_numpy(p_b.copy())
+    loop.stream()
+    out = loop.result()
+    loop.collide()
+    out.update(psi=loop.phase.squeeze(-1).numpy(), s_nu=loop.s_nu.numpy(), col_r=loop.r_col.numpy(), col_b=loop.b_col.numpy())
+    return out
+
+
+class CgLoop:
+    """the loop body of main() (:431-477) as its two halves, on the two Colour objects and u"""
+
+    def __init__(self, r, b, sigma, Fg, delta, add_source):
+        R, C = r.rho.shape[:2]
+        self.r, self.b, self.sigma, self.Fg, self.add_source = r, b, sigma, Fg, add_source
+        self.relax = relaxation_function(r, b, delta)
+        self.u = torch.zeros(R, C, 2)
+        self.s_nu = torch.zeros(R, C)
+        self.S = torch.diagflat(torch.tensor([0.0, 1.25, 1.14, 0.0, 1.6, 0.0, 1.6, 0.0, 0.0])).repeat(R, C, 1, 1)
+        self.phase = torch.zeros(R, C, 1)
+        self.r_col = self.b_col = None
+
+    def collide(self):
+        r, b, u, S, Fg, sigma = self.r, self.b, self.u, self.S, self.Fg, self.sigma
+        rho = r.rho + b.rho
         r_equ = eval_equilibrium(r.rho, r.phi, r.eta, u)
         b_equ = eval_equilibrium(b.rho, b.phi, b.eta, u)
         phase = (r.rho / r.rho_0 - b.rho / b.rho_0) / (r.rho / r.rho_0 + b.rho / b.rho_0)  # :212-225
-        s_nu = relax(s_nu, phase)
+        s_nu = self.relax(self.s_nu, phase)
         for k in (r, b):  # update_C :320-336
             DxQx = D.x((1.8 * k.alpha - 0.8) * k.rho.squeeze(-1) * u[..., 0])
             DyQy = D.y((1.8 * k.alpha - 0.8) * k.rho.squeeze(-1) * u[..., 1])
@@ -162,17 +195,25 @@ def cg_run(R, C, red, blue, sigma, gravity, steps, delta=0.1, droplet=False):
         om3_r = r.rho * total_f / rho + r.beta * kappa
         om3_b = b.rho * total_f / rho + b.beta * kappa
         force = (1 - 0.5 * s_nu.unsqueeze(-1)) * ((3.0 + 9.0 * u.matmul(E)) * Fg.t().matmul(E) - 3.0 * u.matmul(Fg)) * W
-        r_col, b_col = (om3_r, om3_b) if droplet else (om3_r + force, om3_b + force)
-        r.adv_f, b.adv_f = advect(r_col), advect(b_col)
-        apply_boundary_conditions(r.adv_f, r_col)
-        apply_boundary_conditions(b.adv_f, b_col)
+        self.r_col, self.b_col = (om3_r + force, om3_b + force) if self.add_source else (om3_r, om3_b)
+        self.phase, self.s_nu = phase, s_nu
+
+    def stream(self):
+        r, b = self.r, self.b
+        r.adv_f, b.adv_f = advect(self.r_col), advect(self.b_col)
+        apply_boundary_conditions(r.adv_f, self.r_col)
+        apply_boundary_conditions(b.adv_f, self.b_col)
         r.rho = r.adv_f.sum(-1).unsqueeze(-1)
         b.rho = b.adv_f.sum(-1).unsqueeze(-1)
         rho = r.rho + b.rho
         u = (r.adv_f + b.adv_f).matmul(E.t()) / rho  # solver::calc_u
-        u = u + 0.5 * Fg.t() / rho
-    return dict(f_r=r.adv_f.numpy(), f_b=b.adv_f.numpy(), rho_r=r.rho.squeeze(-1).numpy(),
-                rho_b=b.rho.squeeze(-1).numpy(), u=u.numpy(), psi=phase.squeeze(-1).numpy(), s_nu=s_nu.numpy())
+        self.u = u + 0.5 * self.Fg.t() / rho
+
+    def result(self):
+        r, b = self.r, self.b
+        return dict(f_r=r.adv_f.numpy(), f_b=b.adv_f.numpy(), rho_r=r.rho.squeeze(-1).numpy(),
+                    rho_b=b.rho.squeeze(-1).numpy(), u=self.u.numpy(), psi=self.phase.squeeze(-1).numpy(),
+                    s_nu=self.s_nu.numpy())
 
 
 # ---------------------------------------------------------------------------------------------
