@@ -1,14 +1,12 @@
 """Helpers of the suites of the fluid + scalar step with a KBC fluid (tests/test_ade_kbc_abi.py, tests/test_gpu_ade_kbc.py):
-the raw `_m` calls and the yardstick -- one driver iteration composed on the CPU from the oracle's kbc::collide
-(Oracle.kbc_collide on the populations' own moments, as ulbm_double_shear_flow.cpp:141-142 forms them) and the scalar half
-and wall rules of tests/ade_util.py.  The yardstick never calls the library under test."""
-import ctypes as ct
-
+the parameters of the `_m` calls (made through tests/ade_calls.py) and the yardstick -- one driver iteration composed on
+the CPU from the oracle's kbc::collide (Oracle.kbc_collide on the populations' own moments, as
+ulbm_double_shear_flow.cpp:141-142 forms them) and the scalar half and wall rules of tests/ade_util.py.  The yardstick
+never calls the library under test."""
 import numpy as np
 
 import pylbm
-from ade_util import W, _moment_ptrs, _ref, alloc, stream
-from pylbm import _ptr
+from ade_util import W, stream
 
 S2 = 1.0 / (0.5 + 3 * 0.02)  # nu = 0.02: gamma far from its limits on the random states of ade_util.initial_state
 OMEGA_G = 1.7
@@ -17,24 +15,6 @@ OMEGA_G = 1.7
 def params(form, s2=S2, w=W, omega_g=OMEGA_G):
     """(lbm_ade_fluid with a KBC fluid, lbm_ade_params), both halves in `form`"""
     return pylbm.AdeFluid(pylbm.KbcParams(s2, form)), pylbm.AdeParams(omega_g, w, form=form)
-
-
-def _handle(table):
-    return table.h if table is not None else None
-
-
-def step_into(lib, g, bc, prm, dst, src, sbc=None, table=None, rows=None, moments=None, stream=None):
-    """lbm_ade_stream_collide_m over rows [rows[0], rows[1]) (default: all of them) into the lattices given"""
-    r0, r1 = rows if rows is not None else (0, g.R)
-    lib.ade_stream_collide_m(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                             ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _handle(table), r0, r1, *_moment_ptrs(moments),
-                             pylbm._stream(stream))
-
-
-def full_step(lib, g, bc, prm, fo, go, sbc=None, table=None, moments=None):
-    fn, gn = alloc(g), alloc(g)
-    step_into(lib, g, bc, prm, (fn, gn), (fo, go), sbc, table, None, moments)
-    return fn, gn
 
 
 def collide(orc, f, g, s2, omega_g, w):

@@ -1,16 +1,13 @@
 """Helpers shared by the GPU suites of the fluid + scalar solver (tests/test_gpu_ade_*.py): flat lattices with ghost rows
-and padding, the raw step through the entry points that take every descriptor (lbm_ade_stream_collide_b / _part_b, with
-interior walls _w / _part_w), the write set of a launch into SENTINEL lattices, and the yardstick of the bitwise tests -- the reference's sediment loop composed from the oracle's solver:: primitives,
-with the wall rules, the interior walls and the buoyant collision restated in numpy in the driver's expression order.
-The yardstick never calls the library under test."""
-import ctypes as ct
-
+and padding, the write set of a launch into SENTINEL lattices, the start states, and the yardstick of the bitwise tests --
+the reference's sediment loop composed from the oracle's solver:: primitives, with the wall rules, the interior walls and
+the buoyant collision restated in numpy in the driver's expression order.  The yardstick never calls the library under
+test.  The raw calls of the entry points are in tests/ade_calls.py, the chain of slabs in tests/ade_slab_util.py."""
 import numpy as np
 import torch
 
 import pylbm
 from gpu_util import bits_equal, dev
-from pylbm import _ptr
 
 BB, SP = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR
 NO_FLUX = pylbm.ADE_SCALAR_NO_FLUX
@@ -92,13 +89,9 @@ def cut_slab(glob, gg, r0, r1, pitch, closed=False):
     return sg, t
 
 
-# ---- the raw step -------------------------------------------------------------------------------------------------------
+# ---- parameters, poisoned targets and the write set ---------------------------------------------------------------------
 def params(form, w=W, omega=1.2, omega_g=1.7):
     return pylbm.BgkParams(omega, 0, form=form), pylbm.AdeParams(omega_g, w, form=form)
-
-
-def _ref(x):
-    return ct.byref(x) if x is not None else None
 
 
 def poisoned(g):
@@ -116,48 +109,6 @@ def moment_fields(g):
     return m
 
 
-def _moment_ptrs(moments):
-    return [_ptr(t) for t in moments] if moments is not None else [None, None, None]
-
-
-def step_into(lib, g, bc, prm, dst, src, sbc=None, by=None, rows=None, moments=None, stream=None):
-    """lbm_ade_stream_collide_b over rows [rows[0], rows[1]) (default: all of them) into the lattices given"""
-    r0, r1 = rows if rows is not None else (0, g.R)
-    lib.ade_stream_collide_b(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                             ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), r0, r1, *_moment_ptrs(moments),
-                             pylbm._stream(stream))
-
-
-def full_step(lib, g, bc, prm, fo, go, sbc=None, by=None, stream=None, moments=None):
-    fn, gn = alloc(g), alloc(g)
-    step_into(lib, g, bc, prm, (fn, gn), (fo, go), sbc, by, None, moments, stream)
-    return fn, gn
-
-
-def part(lib, g, bc, prm, dst, src, which, E, sbc=None, by=None, stream=None, moments=None):
-    lib.ade_stream_collide_part_b(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), which, E,
-                                  *_moment_ptrs(moments), pylbm._stream(stream))
-
-
-def _handle(table):
-    return table.h if table is not None else None
-
-
-def full_step_w(lib, g, bc, prm, fo, go, sbc=None, by=None, table=None, moments=None):
-    """lbm_ade_stream_collide_w on one block: the step with a table of interior walls (pylbm.AdeInteriorWalls or None)"""
-    fn, gn = alloc(g), alloc(g)
-    lib.ade_stream_collide_w(_ptr(fn), _ptr(gn), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                             ct.byref(prm[1]), _ref(sbc), _ref(by), _handle(table), 0, g.R, *_moment_ptrs(moments), None)
-    return fn, gn
-
-
-def part_w(lib, g, bc, prm, dst, src, which, E, sbc=None, by=None, table=None, moments=None):
-    lib.ade_stream_collide_part_w(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), _handle(table), which, E,
-                                  *_moment_ptrs(moments), None)
-
-
 def assert_write_set(t, g, rows, what):
     """of a lattice that was SENTINEL everywhere: exactly the owned nodes of `rows` are written, in all 9 planes -- no
     ghost row, no row padding, no plane padding"""
@@ -169,8 +120,9 @@ def assert_write_set(t, g, rows, what):
 
 
 # ---- the yardstick ------------------------------------------------------------------------------------------------------
-def initial_state(orc, R, C, seed=0, w=W):
-    """f: shear wave plus noise; g: equilibrium(u + w, C) of a Gaussian, C in [0, 1e-3]"""
+def initial_state(orc, R, C, seed=0, w=W, conc_rows=None, scale=1.0):
+    """f: shear wave plus noise; g: equilibrium(u + w, C) of a Gaussian, C in [0, scale * 1e-3] -- or, with conc_rows = (a, b),
+    of a blob confined to rows [a, b): exactly zero elsewhere"""
     rng = np.random.default_rng(seed)
     r, c = np.meshgrid(np.arange(R, dtype=float), np.arange(C, dtype=float), indexing="ij")
     u = np.zeros((R, C, 2))
@@ -179,7 +131,11 @@ def initial_state(orc, R, C, seed=0, w=W):
     rho = 1 + 0.01 * rng.standard_normal((R, C))
     f = orc.equilibrium(u, rho) * (1 + 0.005 * rng.standard_normal((R, C, 9)))
     s = 0.15 * min(R, C)
-    conc = 1e-3 * np.exp(-((r - 0.4 * R) ** 2 + (c - 0.55 * C) ** 2) / (2 * s * s))
+    if conc_rows is None:
+        conc = scale * 1e-3 * np.exp(-((r - 0.4 * R) ** 2 + (c - 0.55 * C) ** 2) / (2 * s * s))
+    else:
+        a, b = conc_rows
+        conc = np.where((r >= a) & (r < b), scale * 1e-3 * np.exp(-((r - (a + b) / 2) ** 2 + (c - C / 2) ** 2) / (2 * s * s)), 0.0)
     return f, orc.equilibrium(u + np.asarray(w), conc)
 
 

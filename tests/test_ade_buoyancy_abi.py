@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 import pylbm
+from ade_calls import ref as _ref
 
 SYMBOLS = ["lbm_ade_collide_b", "lbm_ade_stream_collide_b", "lbm_ade_stream_collide_part_b",
            "lbm_ade_solver_set_buoyancy", "lbm_ring_ade_collide_b", "lbm_ring_ade_step_b"]
@@ -72,10 +73,6 @@ def test_buoyancy_header_is_plain_c99(tmp_path):
 
 
 # ---- the three raw entry points, called with NULL lattices: everything is decided on the host ---------------------------
-def _ref(x):
-    return ct.byref(x) if x is not None else None
-
-
 def _prm(**fluid):
     return pylbm.BgkParams(1.2, 0, **fluid), pylbm.AdeParams(1.7, (3e-3, 3e-3))
 

@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 import pylbm
+from ade_calls import ref as _ref
 
 SYMBOLS = ["lbm_ade_collide_mb", "lbm_ade_stream_collide_mb", "lbm_ade_solver_set_buoyancy_m"]
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
@@ -26,10 +27,6 @@ def lib():
 
 def kbc(s2=1.6, form=pylbm.FORM_DEFAULT):
     return pylbm.AdeFluid(pylbm.KbcParams(s2, form))
-
-
-def _ref(x):
-    return ct.byref(x) if x is not None else None
 
 
 def both_raw(lib, msg, g=G, bc=None, fluid=None, scalar=SCALAR, sbc=None, by=BY, names=None):

@@ -12,6 +12,7 @@ import subprocess
 import pytest
 
 import pylbm
+from ade_calls import ref as _ref
 
 SYMBOLS = ["lbm_ade_stream_collide_part_m", "lbm_ring_ade_collide_m", "lbm_ring_ade_step_m"]
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
@@ -40,10 +41,6 @@ def lattices():
 
 def kbc(s2=1.6, form=pylbm.FORM_DEFAULT):
     return pylbm.AdeFluid(pylbm.KbcParams(s2, form))
-
-
-def _ref(x):
-    return ct.byref(x) if x is not None else None
 
 
 def part_m(lib, lat, g, bc, fluid, scalar, part=FRAME, E=1, sbc=None, table=None, rho=None):

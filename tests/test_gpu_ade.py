@@ -19,12 +19,13 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
+from ade_calls import collide, step_into  # noqa: E402
+from ade_util import W, assert_state_bits, initial_state  # noqa: E402
 from gpu_util import bits_equal, dev, download_aos, upload_soa  # noqa: E402
 from proc_util import key_values, run_driver  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
-W = (3e-3, 3e-3)
 
 
 @pytest.fixture(scope="module")
@@ -32,21 +33,6 @@ def lib():
     lib = pylbm.Lib()
     assert lib.device_count() >= 1, "no HIP device visible"
     return lib
-
-
-def initial_state(orc, R, C, seed=0, w=W):
-    """f: shear wave u_c = U0 sin(2 pi r / R) plus noise; g: equilibrium(u + w, C) of a Gaussian, C in [0, 1e-3]"""
-    rng = np.random.default_rng(seed)
-    r, c = np.meshgrid(np.arange(R, dtype=float), np.arange(C, dtype=float), indexing="ij")
-    u = np.zeros((R, C, 2))
-    u[..., 1] = 0.03 * np.sin(2 * np.pi * r / R)
-    u += 0.005 * rng.standard_normal((R, C, 2))
-    rho = 1 + 0.01 * rng.standard_normal((R, C))
-    f = orc.equilibrium(u, rho) * (1 + 0.005 * rng.standard_normal((R, C, 9)))
-    s = 0.15 * min(R, C)
-    conc = 1e-3 * np.exp(-((r - 0.4 * R) ** 2 + (c - 0.55 * C) ** 2) / (2 * s * s))
-    g = orc.equilibrium(u + np.asarray(w), conc)
-    return f, g
 
 
 def _walls(bc):
@@ -89,11 +75,6 @@ def oracle_loop(orc, f, g, omega, omega_g, w, n, bc=None):
 def ade(lib, R, C, omega, omega_g, w, form, bc=None, stream=None):
     return pylbm.AdeSolver(lib, R, C, pylbm.BgkParams(omega, 0, form=form), pylbm.AdeParams(omega_g, w, form=form),
                            bc=bc, stream=stream)
-
-
-def assert_state_bits(got, want, what):
-    for k in ("f", "g", "rho", "u", "C"):
-        assert bits_equal(got[k], want[k]), f"{what}: {k} differs, max |d| = {np.max(np.abs(got[k] - want[k]))}"
 
 
 @pytest.mark.parametrize("R,C", [(96, 70), (1024, 1024)])
@@ -143,14 +124,12 @@ def test_raw_entry_points_with_moments(lib, oracle):
     rho = torch.empty((R, C), dtype=torch.float64, device=dev())
     u = torch.empty((2, R, C), dtype=torch.float64, device=dev())
     conc = torch.empty((R, C), dtype=torch.float64, device=dev())
-    lib.ade_collide(_ptr(fb), _ptr(gb), _ptr(fa), _ptr(ga), ct.byref(geo), ct.byref(bc), ct.byref(fl), ct.byref(sc),
-                    _ptr(rho), _ptr(u), _ptr(conc), None)
+    collide(lib, "", geo, bc, (fl, sc), (fb, gb), (fa, ga), moments=(rho, u, conc))
     torch.cuda.synchronize()
     want0 = oracle_loop(oracle, f0, g0, 1.3, 0.9, (2e-3, -1e-3), 0)
     assert bits_equal(rho.cpu().numpy(), want0["rho"]) and bits_equal(conc.cpu().numpy(), want0["C"])
     for _ in range(6):
-        lib.ade_stream_collide(_ptr(fa), _ptr(ga), _ptr(fb), _ptr(gb), ct.byref(geo), ct.byref(bc), ct.byref(fl),
-                               ct.byref(sc), 0, R, _ptr(rho), _ptr(u), _ptr(conc), None)
+        step_into(lib, "", geo, bc, (fl, sc), (fa, ga), (fb, gb), moments=(rho, u, conc))
         fa, fb, ga, gb = fb, fa, gb, ga
     torch.cuda.synchronize()
     want = oracle_loop(oracle, f0, g0, 1.3, 0.9, (2e-3, -1e-3), 6, bc=bc)

@@ -6,7 +6,8 @@ The yardstick of every bitwise test is `oracle_loop` of tests/ade_util.py with a
 composed from the oracle's solver:: primitives (calc_rho, calc_u, equilibrium, advect, collision for the scalar), with the
 force, the velocity shift and the fluid's forced collision (items 4-6 of the step in include/lbm_hip.h) written in numpy
 in exactly that order -- numpy's element-wise f64 operations do not fuse -- and the wall rules, which take
-u = calc_u(f_adve), the UNSHIFTED velocity.  The loop never calls the library under test."""
+u = calc_u(f_adve), the UNSHIFTED velocity.  The loop never calls the library under test.  The slab tests run the chain of
+tests/ade_slab_util.py through the _b entries (tests/ade_calls.py)."""
 import ctypes as ct
 
 import numpy as np
@@ -16,11 +17,12 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
+import ade_calls  # noqa: E402
 import ade_util as ade  # noqa: E402
+from ade_slab_util import Chain  # noqa: E402
 from ade_util import GUO, REFERENCE, buoyancy, buoyant_collide, from_lattice, stream, to_lattice  # noqa: E402
 from gpu_util import bits_equal, dev  # noqa: E402
 from proc_util import last_json, run_driver  # noqa: E402
-from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 BB, SP, HALO, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR, pylbm.EDGE_HALO, pylbm.EDGE_PERIODIC
@@ -151,20 +153,15 @@ def test_raw_entry_points_write_the_shifted_velocity(lib, oracle, with_walls):
     pre = to_lattice(f0, g), to_lattice(g0, g)
     post = ade.alloc(g), ade.alloc(g)
     m = moments()
-    lib.ade_collide_b(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                      ct.byref(prm[1]), ct.byref(sbc) if sbc else None, ct.byref(by), _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), None)
+    ade_calls.collide(lib, "_b", g, bc, prm, post, pre, sbc=sbc, buoy=by, moments=m)
     check("lbm_ade_collide_b", post, m, c0)
     nxt = ade.alloc(g), ade.alloc(g)
     m = moments()
-    lib.ade_stream_collide_b(_ptr(nxt[0]), _ptr(nxt[1]), _ptr(post[0]), _ptr(post[1]), ct.byref(g), ct.byref(bc),
-                             ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc) if sbc else None, ct.byref(by), 0, R,
-                             _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), None)
+    ade_calls.step_into(lib, "_b", g, bc, prm, nxt, post, sbc=sbc, buoy=by, moments=m)
     check("lbm_ade_stream_collide_b", nxt, m, c1)
     for which in (FRAME, INNER):  # the part launch writes the same moments at its nodes
         part, m = (ade.alloc(g), ade.alloc(g)), moments()
-        lib.ade_stream_collide_part_b(_ptr(part[0]), _ptr(part[1]), _ptr(post[0]), _ptr(post[1]), ct.byref(g), ct.byref(bc),
-                                      ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc) if sbc else None, ct.byref(by),
-                                      which, 5, _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), None)
+        ade_calls.part(lib, "_b", g, bc, prm, part, post, which, 5, sbc=sbc, buoy=by, moments=m)
         torch.cuda.synchronize()
         rows = np.r_[0:5, R - 5:R] if which == FRAME else np.r_[5:R - 5]
         assert bits_equal(m[1].cpu().numpy().transpose(1, 2, 0)[rows], c1["u"][rows]), f"part {which}: u"
@@ -250,13 +247,12 @@ def test_frame_plus_inner_is_the_full_buoyant_step(lib, R, C, E, with_walls):
     bc = ade.GBC if with_walls else pylbm.Bc()
     sbc = pylbm.AdeScalarBC(row_lo=1.02, col_lo=(0.0, prof), col_hi=0.0) if with_walls else None
     src = (ade.random_lattice(gg, R + C), ade.random_lattice(gg, R * C))
-    want = ade.full_step(lib, gg, bc, prm, *src, sbc=sbc, by=SLAB_BY)
-    passive = ade.full_step(lib, gg, bc, prm, *src, sbc=sbc, by=pylbm.AdeBuoyancy())
+    want = ade_calls.full_step(lib, "_b", gg, bc, prm, *src, sbc=sbc, buoy=SLAB_BY)
+    passive = ade_calls.full_step(lib, "_b", gg, bc, prm, *src, sbc=sbc, buoy=pylbm.AdeBuoyancy())
     dst = (ade.alloc(gg), ade.alloc(gg))
     for d in dst:
         ade.bits(d).fill_(ade.SENTINEL)
-    ade.part(lib, gg, bc, prm, dst, src, FRAME, E, sbc=sbc, by=SLAB_BY)
-    ade.part(lib, gg, bc, prm, dst, src, INNER, E, sbc=sbc, by=SLAB_BY)
+    ade_calls.both_parts(lib, "_b", gg, bc, prm, dst, src, E, sbc=sbc, buoy=SLAB_BY)
     torch.cuda.synchronize()
     for k in range(2):
         ade.assert_bits(ade.owned(dst[k], gg), ade.owned(want[k], gg), f"R={R} C={C} E={E} lattice {k}")
@@ -270,8 +266,8 @@ def test_frame_plus_inner_is_the_full_buoyant_step(lib, R, C, E, with_walls):
 @pytest.mark.parametrize("closed", [False, True], ids=["open", "closed"])
 @pytest.mark.parametrize("heights", [(48, 48, 48), (50, 130)])
 def test_emulated_chain_equals_one_block(lib, oracle, heights, closed):
-    """slabs with one ghost row stepped by lbm_ade_stream_collide_part_b, halos of both lattices by lbm_halo_pack /
-    _unpack; open: a chain with walls on its ends and FIXED edges, closed: a periodic ring with wall columns; 9 steps"""
+    """slabs with one ghost row stepped by lbm_ade_stream_collide_part_b (ade_slab_util.Chain, which moves the halos of both
+    lattices); open: a chain with walls on its ends and FIXED edges, closed: a periodic ring with wall columns; 9 steps"""
     C, steps = 200, 9
     prm = ade.params(FAST, W, OMEGA, OMEGA_G)
     Rg = sum(heights)
@@ -290,50 +286,18 @@ def test_emulated_chain_equals_one_block(lib, oracle, heights, closed):
 
     gsbc = descriptor(0, gbc)
     post = [ade.alloc(gg), ade.alloc(gg)]
-    lib.ade_collide_b(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(gg), ct.byref(gbc),
-                      ct.byref(prm[0]), ct.byref(prm[1]), None, ct.byref(by), None, None, None, None)
+    ade_calls.collide(lib, "_b", gg, gbc, prm, post, pre, buoy=by)
     cur = [t.clone() for t in post]
     for _ in range(steps):
-        cur = list(ade.full_step(lib, gg, gbc, prm, *cur, sbc=gsbc, by=by))
-    r0s = np.concatenate([[0], np.cumsum(heights)]).tolist()
-    n = len(heights)
-    slabs = []
-    for k in range(n):
-        a, b = r0s[k], r0s[k + 1]
-        bc = pylbm.Bc(row_lo=HALO if (closed or k > 0) else BB, row_hi=HALO if (closed or k < n - 1) else BB,
-                      col_lo=gbc.col_lo, col_hi=gbc.col_hi)
-        cut = [ade.cut_slab(p, gg, a, b, 0) for p in post]
-        sg = cut[0][0]
-        if closed:  # the ghost rows of the ring's ends wrap
-            for j in range(2):
-                rv, src = ade.rows_view(cut[j][1], sg), ade.owned(post[j], gg)
-                if k == 0:
-                    rv[:, 0] = src[:, Rg - 1]
-                if k == n - 1:
-                    rv[:, sg.R + 1] = src[:, 0]
-        slabs.append(dict(g=sg, bc=bc, sbc=descriptor(a, bc), lat=[[cut[0][1], cut[1][1]], [ade.alloc(sg), ade.alloc(sg)]]))
-    msg = lib.raw.lbm_halo_rows(1) * C
-    links = [(k, k + 1) for k in range(n - 1)] + ([(n - 1, 0)] if closed else [])
-    c = 0
+        cur = list(ade_calls.full_step(lib, "_b", gg, gbc, prm, *cur, sbc=gsbc, buoy=by))
+    ch = Chain(lib, gg, post, heights, closed, gbc,
+               lambda s, dst, src, e: ade_calls.both_parts(lib, "_b", s["g"], s["bc"], prm, dst, src, e, sbc=s["sbc"], buoy=by),
+               per_slab=lambda k, a, b, bc: dict(sbc=descriptor(a, bc)))
     for _ in range(steps):
-        for s in slabs:
-            e = min(16, (s["g"].R - 1) // 2)
-            ade.part(lib, s["g"], s["bc"], prm, s["lat"][c ^ 1], s["lat"][c], FRAME, e, sbc=s["sbc"], by=by)
-            ade.part(lib, s["g"], s["bc"], prm, s["lat"][c ^ 1], s["lat"][c], INNER, e, sbc=s["sbc"], by=by)
-        for ka, kb in links:  # slab ka's high edge meets slab kb's low edge
-            a, b = slabs[ka], slabs[kb]
-            for j in range(2):
-                down = torch.empty(msg, dtype=torch.float64, device=dev())
-                up = torch.empty(msg, dtype=torch.float64, device=dev())
-                lib.halo_pack(_ptr(down), _ptr(a["lat"][c ^ 1][j]), ct.byref(a["g"]), 1, 1, None)
-                lib.halo_pack(_ptr(up), _ptr(b["lat"][c ^ 1][j]), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(b["lat"][c ^ 1][j]), _ptr(down), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(a["lat"][c ^ 1][j]), _ptr(up), ct.byref(a["g"]), 1, 1, None)
-        c ^= 1
+        ch.step(16)
     torch.cuda.synchronize()
     for j in range(2):
-        got = torch.cat([ade.owned(s["lat"][c][j], s["g"]) for s in slabs], dim=1)
-        ade.assert_bits(got, ade.owned(cur[j], gg), f"chain {heights} closed={closed} lattice {j}")
+        ade.assert_bits(ch.gather(j), ade.owned(cur[j], gg), f"chain {heights} closed={closed} lattice {j}")
 
 
 DRIVER_BUOYANCY = "0.8,-0.5,0.0004,0.5,3,9"  # the drivers' scalars are ~1e-3

@@ -17,11 +17,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
+import ade_calls  # noqa: E402
 import ade_util as ade  # noqa: E402
 from ade_util import SENTINEL, Body  # noqa: E402
 from gpu_util import bits_equal, dev  # noqa: E402
 from proc_util import key_values, run_driver  # noqa: E402
-from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 BB, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_PERIODIC
@@ -228,16 +228,11 @@ def test_null_and_empty_tables_are_todays_solver(lib, oracle, form):
     src = (ade.random_lattice(g, 1), ade.random_lattice(g, 2))
     outs = []
     for t in ("b", None, empty):
-        fn, gn = ade.alloc(g), ade.alloc(g)
         if t == "b":
-            lib.ade_stream_collide_b(_ptr(fn), _ptr(gn), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                     ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), None, 0, R, None, None, None, None)
+            outs.append(ade_calls.full_step(lib, "_b", g, bc, prm, *src, sbc=sbc))
         else:
-            lib.ade_stream_collide_w(_ptr(fn), _ptr(gn), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                     ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), None, t.h if t else None, 0, R,
-                                     None, None, None, None)
+            outs.append(ade_calls.full_step(lib, "_w", g, bc, prm, *src, sbc=sbc, iwalls=t))
         torch.cuda.synchronize()
-        outs.append((fn, gn))
     for k in range(2):
         ade.assert_bits(outs[1][k], outs[0][k], f"NULL table, lattice {k}")
         ade.assert_bits(outs[2][k], outs[0][k], f"empty table, lattice {k}")
@@ -270,9 +265,7 @@ def test_the_walled_step_writes_exactly_the_rows_of_its_range(lib, form, lo, hi)
         for t in out:
             ade.bits(t).fill_(SENTINEL)
         torch.cuda.synchronize()
-        lib.ade_stream_collide_w(_ptr(out[0]), _ptr(out[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                 ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), None, table.h, a, b, _ptr(out[2]),
-                                 _ptr(out[3]), _ptr(out[4]), None)
+        ade_calls.step_into(lib, "_w", g, bc, prm, out[:2], src, (a, b), sbc=sbc, iwalls=table, moments=out[2:])
         torch.cuda.synchronize()
         return out
 
@@ -291,9 +284,7 @@ def test_the_walled_step_writes_exactly_the_rows_of_its_range(lib, form, lo, hi)
         assert bool((m[:, lo:hi] == mf[:, lo:hi]).all()) and bool((mf != SENTINEL).all())
         assert bool((m[:, :lo] == SENTINEL).all()) and bool((m[:, hi:] == SENTINEL).all())
     # the wall rows are the table's, not the plain step's
-    plain = [ade.alloc(g), ade.alloc(g)]
-    lib.ade_stream_collide_b(_ptr(plain[0]), _ptr(plain[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                             ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), None, 0, R, None, None, None, None)
+    plain = ade_calls.full_step(lib, "_b", g, bc, prm, *src, sbc=sbc)
     torch.cuda.synchronize()
     for k in range(2):
         differs = (ade.bits(ade.owned(full[k], g)) != ade.bits(ade.owned(plain[k], g))).any(dim=0).any(dim=1)

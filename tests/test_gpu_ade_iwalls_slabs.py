@@ -9,9 +9,8 @@ tolerances -- except the scalar mass of the sealed seam, whose bound is that of 
 The body, on a global 48 x 64 lattice: a column wall at column 20 through ALL rows (COL_NEG for f and g) and row walls at
 rows 5 and 29, columns 20..30 (ROW_NEG): 68 nodes, 34 in each of the views [0, 24), [24, 48), [12, 36).  The column wall
 puts a node on the first and last row of every slab and into every FRAME and INNER band for any E; each test asserts that
-each band it exercises holds a table node (bands_hold_nodes), so that none passes by testing nothing."""
-import ctypes as ct
-
+each band it exercises holds a table node (bands_hold_nodes), so that none passes by testing nothing.  The body, the chain of
+slabs and the write-set check of a part are tests/ade_slab_util.py's; every raw call goes through tests/ade_calls.py."""
 import numpy as np
 import pytest
 
@@ -19,11 +18,13 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
-from ade_util import (GBC, GUO, SENTINEL, W, alloc, assert_bits, bits, buoyancy, cut_slab, geom, owned, params,  # noqa: E402
-                      random_lattice, to_lattice)
+import ade_calls  # noqa: E402
+from ade_slab_util import (Chain, OneSlabRing, assert_part_write_sets, bands_hold_nodes, body_segments, body_table,  # noqa: E402
+                           global_state, slab_bc)
+from ade_util import (GBC, GUO, W, alloc, assert_bits, bits, buoyancy, cut_slab, geom, moment_fields, owned, params,  # noqa: E402
+                      poisoned, random_lattice, to_lattice)
 from gpu_util import dev  # noqa: E402
 from proc_util import last_json, run_driver, run_ranks  # noqa: E402
-from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
@@ -40,58 +41,12 @@ def lib():
     return lib
 
 
-def _ref(x):
-    return ct.byref(x) if x is not None else None
-
-
-def _h(t):
-    return t.h if t is not None else None
-
-
-# ---- the body and the calls under test -----------------------------------------------------------------------------------
-def body_segments(R):
-    """the test body on a lattice of R rows: (r0, c0, dr, dc, n, slots) -- the row walls that fit into R rows"""
-    return [(0, 20, 1, 0, R, COL_NEG)] + [(r, 20, 0, 1, 11, ROW_NEG) for r in (5, 29) if r < R]
-
-
-def body_table(lib, R, C, rule=(NO_FLUX, 0.0), finalize=True):
-    t = pylbm.AdeInteriorWalls(lib, R, C)
-    for r0, c0, dr, dc, n, slots in body_segments(R):
-        t.add(r0, c0, dr, dc, n, slots, slots, *rule)
-    return t.finalize() if finalize else t
-
-
-def bands_hold_nodes(table, E):
-    """every band of a part launch with E edge rows holds a node of the (slab-local) table"""
-    rows = {n["r"] for n in table.nodes()}
-    R = table.R
-    return all(any(a <= r < b for r in rows) for a, b in ((0, E), (E, R - E), (R - E, R)))
-
-
-def full_w(lib, g, bc, prm, fo, go, sbc=None, by=None, table=None, moments=None):
-    """the yardstick: lbm_ade_stream_collide_w on one block"""
-    fn, gn = alloc(g), alloc(g)
-    m = [_ptr(t) for t in moments] if moments else [None, None, None]
-    lib.ade_stream_collide_w(_ptr(fn), _ptr(gn), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                             ct.byref(prm[1]), _ref(sbc), _ref(by), _h(table), 0, g.R, *m, None)
-    return fn, gn
-
-
-def part_w(lib, g, bc, prm, dst, src, which, E, sbc=None, by=None, table=None, moments=None, stream=None):
-    m = [_ptr(t) for t in moments] if moments else [None, None, None]
-    lib.ade_stream_collide_part_w(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), _h(table), which, E, *m,
-                                  pylbm._stream(stream))
-
-
-def part_b(lib, g, bc, prm, dst, src, which, E, sbc=None, by=None):
-    lib.ade_stream_collide_part_b(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), which, E, None, None, None, None)
-
-
-def slab_bc(gbc, r0, r1, Rg, closed=False):
-    return pylbm.Bc(row_lo=HALO if (closed or r0 > 0) else gbc.row_lo, row_hi=HALO if (closed or r1 < Rg) else gbc.row_hi,
-                    col_lo=gbc.col_lo, col_hi=gbc.col_hi)
+# the yardstick is lbm_ade_stream_collide_w on one block; the calls under test are lbm_ade_stream_collide_part_w's
+def chain(lib, gg, post, heights, closed, gbc, prm, table):
+    """ade_slab_util.Chain through lbm_ade_stream_collide_part_w, every slab with its view of the global table"""
+    return Chain(lib, gg, post, heights, closed, gbc,
+                 lambda s, dst, src, e: ade_calls.both_parts(lib, "_w", s["g"], s["bc"], prm, dst, src, e, iwalls=s["view"]),
+                 per_slab=lambda k, a, b, bc: dict(view=table.slab(a, b - a).finalize() if table is not None else None))
 
 
 # ---- 1. FRAME + INNER with a view == the one-block step on the global lattice --------------------------------------------
@@ -111,8 +66,8 @@ def test_frame_plus_inner_with_a_view_is_the_one_block_step(lib, form, case, C, 
     table = body_table(lib, RG, C, rule)
     assert table.count() == 68
     twin = body_table(lib, RG, C, rule, finalize=False)
-    want = full_w(lib, gg, GBC, prm, *src, sbc=gsbc, by=by, table=table)
-    plain = full_w(lib, gg, GBC, prm, *src, sbc=gsbc, by=by)
+    want = ade_calls.full_step(lib, "_w", gg, GBC, prm, *src, sbc=gsbc, buoy=by, iwalls=table)
+    plain = ade_calls.full_step(lib, "_w", gg, GBC, prm, *src, sbc=gsbc, buoy=by)
     assert not torch.equal(bits(want[1]), bits(plain[1]))  # the body is felt
     for r0, r1 in ((0, 24), (24, 48), (12, 36)):
         view = table.slab(r0, r1 - r0)
@@ -127,8 +82,7 @@ def test_frame_plus_inner_with_a_view_is_the_one_block_step(lib, form, case, C, 
         for E in (1, 3, 8):
             assert bands_hold_nodes(view, E)
             dst = (alloc(sg), alloc(sg))
-            part_w(lib, sg, bc, prm, dst, (slab[0][1], slab[1][1]), FRAME, E, sbc, by, view)
-            part_w(lib, sg, bc, prm, dst, (slab[0][1], slab[1][1]), INNER, E, sbc, by, view)
+            ade_calls.both_parts(lib, "_w", sg, bc, prm, dst, (slab[0][1], slab[1][1]), E, sbc=sbc, buoy=by, iwalls=view)
             torch.cuda.synchronize()
             for k in range(2):
                 assert_bits(owned(dst[k], sg), owned(want[k], gg)[:, r0:r1], f"{case} C={C} slab [{r0}, {r1}) E={E} lattice {k}")
@@ -146,18 +100,11 @@ def test_the_moment_outputs_of_wall_nodes_are_the_one_block_steps(lib, form):
     assert bands_hold_nodes(table, E)
     src = (random_lattice(g, 3), random_lattice(g, 4))
 
-    def moments():
-        m = [torch.zeros(n * R * C, dtype=torch.float64, device=dev()) for n in (1, 2, 1)]
-        for t in m:
-            bits(t).fill_(SENTINEL)
-        return m
-
-    mw, mp, mplain = moments(), moments(), moments()
-    want = full_w(lib, g, bc, prm, *src, table=table, moments=mw)
-    full_w(lib, g, bc, prm, *src, moments=mplain)
+    mw, mp, mplain = moment_fields(g), moment_fields(g), moment_fields(g)
+    want = ade_calls.full_step(lib, "_w", g, bc, prm, *src, iwalls=table, moments=mw)
+    ade_calls.full_step(lib, "_w", g, bc, prm, *src, moments=mplain)
     dst = (alloc(g), alloc(g))
-    for which in (FRAME, INNER):
-        part_w(lib, g, bc, prm, dst, src, which, E, table=table, moments=mp)
+    ade_calls.both_parts(lib, "_w", g, bc, prm, dst, src, E, iwalls=table, moments=mp)
     torch.cuda.synchronize()
     for k in range(2):
         assert_bits(owned(dst[k], g), owned(want[k], g), f"lattice {k}")
@@ -182,14 +129,11 @@ def test_null_and_empty_tables_are_part_b(lib, form):
     for drive in (None, by):
         outs = []
         for t in ("b", None, empty, view):
-            dst = (alloc(g), alloc(g))
-            for d in dst:
-                bits(d).fill_(SENTINEL)
-            for which in (FRAME, INNER):
-                if t == "b":
-                    part_b(lib, g, bc, prm, dst, src, which, E, sbc, drive)
-                else:
-                    part_w(lib, g, bc, prm, dst, src, which, E, sbc, drive, t)
+            dst = (poisoned(g), poisoned(g))
+            if t == "b":
+                ade_calls.both_parts(lib, "_b", g, bc, prm, dst, src, E, sbc=sbc, buoy=drive)
+            else:
+                ade_calls.both_parts(lib, "_w", g, bc, prm, dst, src, E, sbc=sbc, buoy=drive, iwalls=t)
             torch.cuda.synchronize()
             outs.append(dst)
         for i, what in ((1, "NULL"), (2, "empty"), (3, "empty view")):
@@ -214,107 +158,28 @@ def test_each_part_alone_with_the_table_writes_exactly_its_rows(lib, R, C, E, wa
     src = (random_lattice(g, R), random_lattice(g, C))
     want, plain = [alloc(g), alloc(g)], [alloc(g), alloc(g)]
     for which in (FRAME, INNER):
-        part_w(lib, g, bc, prm, want, src, which, E, table=table)
-        part_b(lib, g, bc, prm, plain, src, which, E)
+        ade_calls.part(lib, "_w", g, bc, prm, want, src, which, E, iwalls=table)
+        ade_calls.part(lib, "_b", g, bc, prm, plain, src, which, E)
     torch.cuda.synchronize()
     wall_rows = sorted({n["r"] for n in table.nodes()})
     for k in range(2):
         differs = (bits(owned(want[k], g)) != bits(owned(plain[k], g))).any(dim=0).any(dim=1)
         assert differs.tolist() == [r in wall_rows for r in range(R)], (k, differs.tolist())
-    for which, rows in ((FRAME, list(range(E)) + list(range(R - E, R))), (INNER, list(range(E, R - E)))):
-        dst = (alloc(g), alloc(g))
-        for d in dst:
-            bits(d).fill_(SENTINEL)
-        torch.cuda.synchronize()
-        part_w(lib, g, bc, prm, dst, src, which, E, table=table)
-        torch.cuda.synchronize()
-        expect = torch.zeros(9 * g.plane_stride, dtype=torch.bool, device=dev())
-        owned(expect, g)[:, rows] = True
-        for k in range(2):
-            changed = bits(dst[k]) != SENTINEL
-            wrong = torch.nonzero(changed != expect)
-            what = f"{'FRAME' if which == FRAME else 'INNER'} R={R} C={C} E={E} walls={walls} lattice {k}"
-            assert wrong.numel() == 0, f"{what}: {wrong.shape[0]} doubles wrong, first flat index {int(wrong[0, 0])} " \
-                                       f"({'missed' if bool(expect[int(wrong[0, 0])]) else 'over-written'})"
-            diff = torch.nonzero(expect & (bits(dst[k]) != bits(want[k])))
-            assert diff.numel() == 0, f"{what}: {diff.shape[0]} written doubles differ from the full call"
+    assert_part_write_sets(lambda dst, which: ade_calls.part(lib, "_w", g, bc, prm, dst, src, which, E, iwalls=table), g, want, E,
+                           f"R={R} C={C} E={E} walls={walls}")
     table.close()
 
 
 # ---- 4. chains and rings of slabs in one process -------------------------------------------------------------------------
-def global_state(oracle, Rg, C, seed=0, w=W):
-    """pre-collision f, g of the global box (dense SoA, ghost 0): a shear wave with noise, the scalar a Gaussian blob"""
-    rng = np.random.default_rng(seed)
-    r, c = np.meshgrid(np.arange(Rg, dtype=float), np.arange(C, dtype=float), indexing="ij")
-    u = np.zeros((Rg, C, 2))
-    u[..., 1] = 0.03 * np.sin(2 * np.pi * r / Rg)
-    u += 0.005 * rng.standard_normal((Rg, C, 2))
-    rho = 1 + 0.01 * rng.standard_normal((Rg, C))
-    f = oracle.equilibrium(u, rho) * (1 + 0.005 * rng.standard_normal((Rg, C, 9)))
-    s = 0.15 * min(Rg, C)
-    conc = 1e-3 * np.exp(-((r - 0.4 * Rg) ** 2 + (c - 0.55 * C) ** 2) / (2 * s * s))
-    gg = geom(Rg, C, 0)
-    return gg, [to_lattice(a, gg) for a in (f, oracle.equilibrium(u + np.asarray(w), conc))]
-
-
 def one_block(lib, gg, pre, gbc, prm, steps, table):
     """lbm_ade_collide + `steps` x lbm_ade_stream_collide_w on the global lattice: (post-collision state, after steps)"""
     post = [alloc(gg), alloc(gg)]
-    lib.ade_collide(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(gg), ct.byref(gbc),
-                    ct.byref(prm[0]), ct.byref(prm[1]), None, None, None, None)
+    ade_calls.collide(lib, "", gg, gbc, prm, post, pre)
     cur = [t.clone() for t in post]
     for _ in range(steps):
-        cur = list(full_w(lib, gg, gbc, prm, *cur, table=table))
+        cur = list(ade_calls.full_step(lib, "_w", gg, gbc, prm, *cur, iwalls=table))
     torch.cuda.synchronize()
     return post, cur
-
-
-class Chain:
-    """slabs of the given heights of one global box, every slab in turn on this GPU: FRAME + INNER through
-    lbm_ade_stream_collide_part_w with the slab's view of the global table, then the single-step halo of BOTH lattices by
-    lbm_halo_pack -> lbm_halo_unpack (tests/test_gpu_ade_slabs.py's Chain with a table)"""
-
-    def __init__(self, lib, gg, post, heights, closed, gbc, prm, table):
-        self.lib, self.prm, self.closed, self.n = lib, prm, closed, len(heights)
-        self.r0 = np.concatenate([[0], np.cumsum(heights)]).tolist()
-        self.slabs = []
-        for k in range(self.n):
-            a, b = self.r0[k], self.r0[k + 1]
-            cut = [cut_slab(p, gg, a, b, 0, closed) for p in post]
-            g = cut[0][0]
-            view = table.slab(a, b - a).finalize() if table is not None else None
-            self.slabs.append(dict(g=g, bc=slab_bc(gbc, a, b, gg.R, closed), view=view,
-                                   lat=[[cut[0][1], cut[1][1]], [alloc(g), alloc(g)]]))
-        self.msg = lib.raw.lbm_halo_rows(1) * gg.C
-        self.cur = 0
-
-    def step(self, E):
-        lib, cur = self.lib, self.cur
-        for s in self.slabs:
-            e = min(E, (s["g"].R - 1) // 2)
-            for which in (FRAME, INNER):
-                part_w(lib, s["g"], s["bc"], self.prm, s["lat"][cur ^ 1], s["lat"][cur], which, e, table=s["view"])
-        n = self.n
-        for k in range(n):
-            if not self.closed and k == n - 1:
-                continue
-            a, b = self.slabs[k], self.slabs[(k + 1) % n]
-            for j in range(2):
-                down = torch.empty(self.msg, dtype=torch.float64, device=dev())
-                up = torch.empty(self.msg, dtype=torch.float64, device=dev())
-                lib.halo_pack(_ptr(down), _ptr(a["lat"][cur ^ 1][j]), ct.byref(a["g"]), 1, 1, None)
-                lib.halo_pack(_ptr(up), _ptr(b["lat"][cur ^ 1][j]), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(b["lat"][cur ^ 1][j]), _ptr(down), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(a["lat"][cur ^ 1][j]), _ptr(up), ct.byref(a["g"]), 1, 1, None)
-        self.cur ^= 1
-
-    def gather(self, j):
-        return torch.cat([owned(s["lat"][self.cur][j], s["g"]) for s in self.slabs], dim=1)
-
-    def close(self):
-        for s in self.slabs:
-            if s["view"] is not None:
-                s["view"].close()
 
 
 @pytest.mark.parametrize("form", [REF, FAST], ids=["reference_order", "reassociated"])
@@ -329,7 +194,7 @@ def test_emulated_chain_with_the_body_equals_one_block(lib, oracle, form, closed
     post, want = one_block(lib, gg, pre, gbc, prm, steps, table)
     _, plain = one_block(lib, gg, pre, gbc, prm, steps, None)
     assert not torch.equal(bits(want[0]), bits(plain[0])) and not torch.equal(bits(want[1]), bits(plain[1]))
-    ch = Chain(lib, gg, post, heights, closed, gbc, prm, table)
+    ch = chain(lib, gg, post, heights, closed, gbc, prm, table)
     assert all(bands_hold_nodes(s["view"], min(E, (s["g"].R - 1) // 2)) for s in ch.slabs)
     for _ in range(steps):
         ch.step(E)
@@ -357,12 +222,12 @@ def test_ring_of_rank_processes_with_the_body_equals_one_block(lib, oracle, tmp_
     _, want = one_block(lib, gg, pre, gbc, prm, steps, table)
     _, plain = one_block(lib, gg, pre, gbc, prm, steps, None)
     assert not torch.equal(bits(want[1]), bits(plain[1]))
-    cfg = dict(R=R, C=C, steps=steps, edge_rows=E, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
+    cfg = dict(R=R, C=C, steps=[steps], edge_rows=E, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
                entry="walls", segments=body_segments(R * n), g_mode=rule[0], conc=rule[1])
     outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", n, cfg,
                      dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()), timeout=240)
     for j, key in enumerate(("f", "g")):
-        got = np.concatenate([o[key] for o in outs], axis=1)
+        got = np.concatenate([o[f"{key}_{steps}"] for o in outs], axis=1)
         ref = owned(want[j], gg).cpu().numpy()
         assert np.array_equal(got.view(np.uint64), ref.view(np.uint64)), f"{n} ranks closed={closed}: {key} differs"
     assert [int(o["nodes"]) for o in outs] == [34, 34]
@@ -388,19 +253,13 @@ def test_ring_step_w_on_a_chain_of_one_slab_is_the_one_block_step(lib):
     sg = cut[0][0]
     lat = [[cut[0][1], cut[1][1]], [alloc(sg), alloc(sg)]]
     for _ in range(steps):
-        want = full_w(lib, gg, GBC, prm, *want, sbc=sbc, by=by, table=table)
-        plain = full_w(lib, gg, GBC, prm, *plain, sbc=sbc, by=by)
-    ring, ident = ct.c_void_p(), (ct.c_ubyte * 128)()
-    lib.ring_unique_id(ident)
-    lib.ring_create(ct.byref(ring), ident, 0, 1, ct.byref(sg), 0)
-    try:
+        want = ade_calls.full_step(lib, "_w", gg, GBC, prm, *want, sbc=sbc, buoy=by, iwalls=table)
+        plain = ade_calls.full_step(lib, "_w", gg, GBC, prm, *plain, sbc=sbc, buoy=by)
+    with OneSlabRing(lib, sg) as ring:
         for k in range(steps):
-            src, dst = lat[k & 1], lat[(k & 1) ^ 1]
-            lib.ring_ade_step_w(ring, _ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(GBC),
-                                ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), ct.byref(by), table.h, E, None)
+            ade_calls.call(lib, "lbm_ring_ade_step_w", rg=ring, dst=lat[(k & 1) ^ 1], src=lat[k & 1], bc=GBC, prm=prm, sbc=sbc,
+                           buoy=by, iwalls=table, edge_rows=E)
         torch.cuda.synchronize()
-    finally:
-        lib.ring_destroy(ring)
     for j in range(2):
         assert_bits(owned(lat[steps & 1][j], sg), owned(want[j], gg), f"lattice {j}")
         assert not torch.equal(bits(owned(want[j], gg)), bits(owned(plain[j], gg)))
@@ -428,7 +287,7 @@ def test_a_sealed_wall_on_a_seam_seals(lib, oracle, form):
     table.finalize()
     out = {}
     for name, t in (("sealed", table), ("open", None)):
-        ch = Chain(lib, gg, post, heights, False, gbc, prm, t)
+        ch = chain(lib, gg, post, heights, False, gbc, prm, t)
         if t is not None:  # E = 2: the pair lies in the FRAME bands of both slabs
             assert [s["view"].count() for s in ch.slabs] == [C, C]
             assert {n["r"] for n in ch.slabs[0]["view"].nodes()} == {11} and {n["r"] for n in ch.slabs[1]["view"].nodes()} == {0}

@@ -18,12 +18,13 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+import ade_calls  # noqa: E402
 import ade_kbc_util as kbc  # noqa: E402
 import diag_reference as ref  # noqa: E402
 import pylbm  # noqa: E402
+from ade_slab_util import body_table  # noqa: E402
 from ade_util import (GBC, W, Body, alloc, assert_bits, assert_state_bits, assert_write_set, bits, build_sbc,  # noqa: E402
                       geom, initial_state, moment_fields, owned, poisoned, random_lattice, to_lattice)
-from ade_util import full_step_w as bgk_full_step_w  # noqa: E402
 from ade_util import params as bgk_params  # noqa: E402
 from gpu_util import bits_equal, dev  # noqa: E402
 from proc_util import run_driver  # noqa: E402
@@ -107,7 +108,7 @@ def post_collision(oracle, state, g):
 def raw_steps(lib, g, bc, prm, src, steps, sbc=None, table=None, with_moments=True):
     cur, m = src, (moment_fields(g) if with_moments else None)
     for _ in range(steps):
-        cur = kbc.full_step(lib, g, bc, prm, *cur, sbc=sbc, table=table, moments=m)
+        cur = ade_calls.full_step(lib, "_m", g, bc, prm, *cur, sbc=sbc, iwalls=table, moments=m)
     torch.cuda.synchronize()
     return cur, m
 
@@ -141,7 +142,7 @@ def test_reference_order_is_the_yardstick(lib, oracle, shape, edges):
         sv.set_state(yard[0]["f"], yard[0]["g"])
         for n in ITERATIONS:
             for _ in range(n - done):
-                cur = kbc.full_step(lib, g, bc, prm, *cur, moments=m)
+                cur = ade_calls.full_step(lib, "_m", g, bc, prm, *cur, moments=m)
             sv.step(n - done)
             done = n
             torch.cuda.synchronize()
@@ -161,7 +162,7 @@ def test_the_fluid_half_is_lbm_kbc_stream_collide(lib, shape, edges, form):
     g, bc = geom(R, C, 0, pitch), EDGES[edges]
     fo, go = random_lattice(g, 21), random_lattice(g, 22)
     m = moment_fields(g)
-    fn, _ = kbc.full_step(lib, g, bc, kbc.params(FORMS[form]), fo, go, moments=m)
+    fn, _ = ade_calls.full_step(lib, "_m", g, bc, kbc.params(FORMS[form]), fo, go, moments=m)
     want, rho, u = alloc(g), torch.zeros(R * C, dtype=torch.float64, device=dev()), torch.zeros(2 * R * C, dtype=torch.float64, device=dev())
     prm = pylbm.KbcParams(S2, FORMS[form])
     lib.kbc_stream_collide(_ptr(want), _ptr(fo), ct.byref(g), ct.byref(bc), ct.byref(prm), 0, R, _ptr(rho), _ptr(u), None)
@@ -201,15 +202,13 @@ def test_model_bgk_is_the_existing_call(lib, oracle, form):
     table = body_table(lib, R, C, (FIXED, 2e-3))
     fo, go = random_lattice(g, 31), random_lattice(g, 32)
     want_m, got_m = moment_fields(g), moment_fields(g)
-    want = bgk_full_step_w(lib, g, GBC, prm, fo, go, sbc=sbc, table=table, moments=want_m)
-    got = kbc.full_step(lib, g, GBC, (fluid, prm[1]), fo, go, sbc=sbc, table=table, moments=got_m)
+    want = ade_calls.full_step(lib, "_w", g, GBC, prm, fo, go, sbc=sbc, iwalls=table, moments=want_m)
+    got = ade_calls.full_step(lib, "_m", g, GBC, (fluid, prm[1]), fo, go, sbc=sbc, iwalls=table, moments=got_m)
     torch.cuda.synchronize()
     assert_same_run((got, got_m), (want, want_m), f"{form}: lbm_ade_stream_collide_m against _w")
     cw, cg, cm_w, cm_g = (alloc(g), alloc(g)), (alloc(g), alloc(g)), moment_fields(g), moment_fields(g)
-    lib.ade_collide_b(_ptr(cw[0]), _ptr(cw[1]), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(GBC), ct.byref(prm[0]), ct.byref(prm[1]),
-                      ct.byref(sbc), None, *[_ptr(t) for t in cm_w], None)
-    lib.ade_collide_m(_ptr(cg[0]), _ptr(cg[1]), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(GBC), ct.byref(fluid), ct.byref(prm[1]),
-                      ct.byref(sbc), *[_ptr(t) for t in cm_g], None)
+    ade_calls.collide(lib, "_b", g, GBC, prm, cw, (fo, go), sbc=sbc, moments=cm_w)
+    ade_calls.collide(lib, "_m", g, GBC, (fluid, prm[1]), cg, (fo, go), sbc=sbc, moments=cm_g)
     torch.cuda.synchronize()
     assert_same_run((cg, cm_g), (cw, cm_w), f"{form}: lbm_ade_collide_m against _b")
     table.close()
@@ -316,15 +315,6 @@ BODY_R, BODY_C = 48, 64
 BODY_BC = pylbm.Bc(row_lo=BB)
 
 
-def body_table(lib, R, C, rule):
-    """the 68-node body of the interior-wall suites on R >= 48 rows: a column wall at column 20 through ALL rows (COL_NEG)
-    and row walls at rows 5 and 29, columns 20..30 (ROW_NEG), f and g slots alike"""
-    t = pylbm.AdeInteriorWalls(lib, R, C)
-    for r0, c0, dr, dc, n, slots in [(0, 20, 1, 0, R, COL_NEG), (5, 20, 0, 1, 11, ROW_NEG), (29, 20, 0, 1, 11, ROW_NEG)]:
-        t.add(r0, c0, dr, dc, n, slots, slots, *rule)
-    return t.finalize()
-
-
 def body_numpy(rule):
     seg = [((slice(None), 20), COL_NEG), ((5, slice(20, 31)), ROW_NEG), ((29, slice(20, 31)), ROW_NEG)]
     return Body(seg, seg, *rule)
@@ -366,10 +356,10 @@ def test_a_row_range_writes_exactly_its_rows(lib, shape, rows, form):
     table = body_table(lib, R, C, (FIXED, 2e-3)) if R >= 48 else None
     src = random_lattice(g, 41), random_lattice(g, 42)
     want_m = moment_fields(g)
-    want = kbc.full_step(lib, g, GBC, prm, *src, table=table, moments=want_m)
+    want = ade_calls.full_step(lib, "_m", g, GBC, prm, *src, iwalls=table, moments=want_m)
     lib.set_tuning(b"grid_cap", 7)
     dst, m = (poisoned(g), poisoned(g)), moment_fields(g)
-    kbc.step_into(lib, g, GBC, prm, dst, src, table=table, rows=rows, moments=m)
+    ade_calls.step_into(lib, "_m", g, GBC, prm, dst, src, rows, iwalls=table, moments=m)
     torch.cuda.synchronize()
     span = list(range(*rows))
     for k, name in enumerate("fg"):

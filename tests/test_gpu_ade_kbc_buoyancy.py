@@ -17,15 +17,16 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+import ade_calls  # noqa: E402
 import ade_kbc_buoyancy_util as yb  # noqa: E402
 import ade_kbc_util as kbc  # noqa: E402
 import diag_reference as ref  # noqa: E402
 import pylbm  # noqa: E402
-from ade_util import (GBC, Body, _moment_ptrs, _ref, alloc, assert_bits, assert_state_bits, assert_write_set, bits,  # noqa: E402
+from ade_slab_util import body_table  # noqa: E402
+from ade_util import (GBC, Body, alloc, assert_bits, assert_state_bits, assert_write_set, bits,  # noqa: E402
                       buoyant_initial_state, from_lattice, geom, moment_fields, owned, poisoned, to_lattice)
 from gpu_util import bits_equal, dev  # noqa: E402
 from proc_util import last_json, run_driver  # noqa: E402
-from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 BB, SP = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR
@@ -142,15 +143,6 @@ def _oracle():
 BODY_R, BODY_C, BODY_BC = 48, 64, pylbm.Bc(row_lo=BB)
 
 
-def body_table(lib, R, C, rule):
-    """the 68-node body of the interior-wall suites: a column wall at column 20 through ALL rows (COL_NEG) and row walls at
-    rows 5 and 29, columns 20..30 (ROW_NEG), f and g slots alike"""
-    t = pylbm.AdeInteriorWalls(lib, R, C)
-    for r0, c0, dr, dc, n, slots in [(0, 20, 1, 0, R, COL_NEG), (5, 20, 0, 1, 11, ROW_NEG), (29, 20, 0, 1, 11, ROW_NEG)]:
-        t.add(r0, c0, dr, dc, n, slots, slots, *rule)
-    return t.finalize()
-
-
 def body_numpy(rule):
     seg = [((slice(None), 20), COL_NEG), ((5, slice(20, 31)), ROW_NEG), ((29, slice(20, 31)), ROW_NEG)]
     return Body(seg, seg, *rule)
@@ -203,18 +195,14 @@ def test_every_launch_variant(lib, edges):
 
 
 # ---- 2. the raw calls ------------------------------------------------------------------------------------------------------
-def raw_collide(lib, g, bc, prm, src, sbc=None, by=BY, moments=None):
+def raw_collide(lib, g, bc, prm, src, **kw):
     dst = alloc(g), alloc(g)
-    lib.ade_collide_mb(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                       ct.byref(prm[1]), _ref(sbc), _ref(by), *_moment_ptrs(moments), None)
+    ade_calls.collide(lib, "_mb", g, bc, prm, dst, src, buoy=BY, **kw)
     return dst
 
 
-def raw_step_into(lib, g, bc, prm, dst, src, sbc=None, by=BY, table=None, rows=None, moments=None):
-    r0, r1 = rows if rows is not None else (0, g.R)
-    lib.ade_stream_collide_mb(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                              ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), table.h if table is not None else None,
-                              r0, r1, *_moment_ptrs(moments), None)
+def raw_step_into(lib, g, bc, prm, dst, src, **kw):
+    ade_calls.step_into(lib, "_mb", g, bc, prm, dst, src, buoy=BY, **kw)
 
 
 def assert_raw(what, g, lat, m, want):
@@ -242,10 +230,10 @@ def test_raw_calls_write_the_shifted_velocity(lib, oracle, R, C, pitch, edges):
     c1 = yb.collide(oracle, f1, g1, S2, OMEGA_G, W, BY)
     assert not bits_equal(c0["u"], oracle.calc_u(f0, c0["rho"]))  # the shift is there
     m = moment_fields(g)
-    post = raw_collide(lib, g, bc, prm, (to_lattice(f0, g), to_lattice(g0, g)), sbc, moments=m)
+    post = raw_collide(lib, g, bc, prm, (to_lattice(f0, g), to_lattice(g0, g)), sbc=sbc, moments=m)
     assert_raw("lbm_ade_collide_mb", g, post, m, c0)
     nxt, m = (alloc(g), alloc(g)), moment_fields(g)
-    raw_step_into(lib, g, bc, prm, nxt, post, sbc, moments=m)
+    raw_step_into(lib, g, bc, prm, nxt, post, sbc=sbc, moments=m)
     assert_raw("lbm_ade_stream_collide_mb", g, nxt, m, c1)
 
 
@@ -261,10 +249,10 @@ def test_a_row_range_writes_exactly_its_rows(lib, oracle, shape, pitch, rows):
     f0, g0 = buoyant_initial_state(oracle, R, C, seed=41, w=W)
     src = to_lattice(f0, g), to_lattice(g0, g)
     want, want_m = (alloc(g), alloc(g)), moment_fields(g)
-    raw_step_into(lib, g, GBC, prm, want, src, sbc, table=table, moments=want_m)
+    raw_step_into(lib, g, GBC, prm, want, src, sbc=sbc, iwalls=table, moments=want_m)
     lib.set_tuning(b"grid_cap", 7)
     dst, m = (poisoned(g), poisoned(g)), moment_fields(g)
-    raw_step_into(lib, g, GBC, prm, dst, src, sbc, table=table, rows=rows, moments=m)
+    raw_step_into(lib, g, GBC, prm, dst, src, sbc=sbc, iwalls=table, rows=rows, moments=m)
     torch.cuda.synchronize()
     span = list(range(*rows))
     for k, name in enumerate("fg"):

@@ -7,7 +7,8 @@ the CPU composition of the oracle's kbc::collide bit for bit in tests/test_gpu_a
 unchanged and asserted finite wherever it is used -- equal NaNs must not pass.  One chain is also tied to
 ade_kbc_util.oracle_loop, which never calls the library.  Every comparison is on bit patterns, in both forms, so there
 are no tolerances.  Start states: ade_util.initial_state (off equilibrium: KBC's gamma is 0/0 on a lattice at equilibrium)
-with ade_kbc_util.S2."""
+with ade_kbc_util.S2.  The body, the chain of slabs and the write-set check of a part are tests/ade_slab_util.py's; every raw
+call goes through tests/ade_calls.py, the rank processes run tests/ade_ring_rank.py with entry "model"."""
 import ctypes as ct
 import functools
 import json
@@ -18,14 +19,16 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+import ade_calls  # noqa: E402
 import ade_kbc_util as kbc  # noqa: E402
 import pylbm  # noqa: E402
-from ade_util import (GBC, SENTINEL, W, alloc, assert_bits, assert_write_set, bits, cut_slab, geom, initial_state,  # noqa: E402
-                      moment_fields, owned, poisoned, to_lattice)
+from ade_slab_util import (Chain, OneSlabRing, assert_finite, assert_part_write_sets, bands_hold_nodes, body_segments,  # noqa: E402
+                           body_table, slab_bc)
+from ade_util import (GBC, SENTINEL, W, alloc, assert_bits, bits, cut_slab, geom, initial_state, moment_fields, owned,  # noqa: E402
+                      poisoned, to_lattice)
 from ade_util import params as bgk_params  # noqa: E402
 from gpu_util import dev  # noqa: E402
 from proc_util import ipc_env, last_json, run_driver, run_ranks  # noqa: E402
-from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 FORMS = pytest.mark.parametrize("form", [REF, FAST], ids=["reference_order", "reassociated"])
@@ -35,6 +38,7 @@ FIXED = pylbm.ADE_SCALAR_FIXED
 ROW_NEG, COL_NEG = pylbm.ADE_FACE_ROW_NEG, pylbm.ADE_FACE_COL_NEG
 S2, OMEGA_G = kbc.S2, kbc.OMEGA_G
 RG = 48
+RULE = (FIXED, 1e-3)  # of the body's g slots
 
 
 @pytest.fixture(scope="module")
@@ -50,38 +54,10 @@ def _default_knobs_afterwards(lib):
     lib.reset_tuning()
 
 
-def _ref(x):
-    return ct.byref(x) if x is not None else None
-
-
-def _h(t):
-    return t.h if t is not None else None
-
-
-def _m(moments):
-    return [_ptr(t) for t in moments] if moments else [None, None, None]
-
-
 # ---- the calls under test and the one block ------------------------------------------------------------------------------
-def part_m(lib, g, bc, prm, dst, src, which, E, sbc=None, table=None, moments=None, stream=None):
-    lib.ade_stream_collide_part_m(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _h(table), which, E, *_m(moments),
-                                  pylbm._stream(stream))
-
-
-def both_parts(lib, g, bc, prm, dst, src, E, **kw):
-    for which in (FRAME, INNER):
-        part_m(lib, g, bc, prm, dst, src, which, E, **kw)
-
-
-def full_m(lib, g, bc, prm, fo, go, sbc=None, table=None, moments=None):
-    """the yardstick: lbm_ade_stream_collide_m on one block"""
-    return kbc.full_step(lib, g, bc, prm, fo, go, sbc=sbc, table=table, moments=moments)
-
-
-def assert_finite(lats, g, what):
-    for k, t in enumerate(lats):
-        assert bool(torch.isfinite(owned(t, g)).all()), f"{what}: the yardstick's lattice {k} is not finite"
+def chain(lib, gg, post, heights, closed, gbc, prm):
+    return Chain(lib, gg, post, heights, closed, gbc,
+                 lambda s, dst, src, e: ade_calls.both_parts(lib, "_m", s["g"], s["bc"], prm, dst, src, e))
 
 
 @functools.lru_cache(maxsize=None)
@@ -98,35 +74,10 @@ def post_collision(lib, gg, gbc, prm, seed=None):
     f, g = _start(gg.R, gg.C, gg.R * gg.C if seed is None else seed)
     pre = [to_lattice(f, gg), to_lattice(g, gg)]
     post = [alloc(gg), alloc(gg)]
-    lib.ade_collide_m(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(gg), ct.byref(gbc), ct.byref(prm[0]),
-                      ct.byref(prm[1]), None, None, None, None, None)
+    ade_calls.collide(lib, "_m", gg, gbc, prm, post, pre)
     torch.cuda.synchronize()
     assert_finite(post, gg, "post-collision state")
     return pre, post
-
-
-def slab_bc(gbc, r0, r1, Rg, closed=False):
-    return pylbm.Bc(row_lo=HALO if (closed or r0 > 0) else gbc.row_lo, row_hi=HALO if (closed or r1 < Rg) else gbc.row_hi,
-                    col_lo=gbc.col_lo, col_hi=gbc.col_hi)
-
-
-def body_segments(R):
-    """a column wall at column 20 through ALL rows (a wall node on every seam row and in every band) and row walls at rows 5
-    and 29, columns 20..30: (r0, c0, dr, dc, n, slots)"""
-    return [(0, 20, 1, 0, R, COL_NEG)] + [(r, 20, 0, 1, 11, ROW_NEG) for r in (5, 29) if r < R]
-
-
-def body_table(lib, R, C, rule=(FIXED, 1e-3)):
-    t = pylbm.AdeInteriorWalls(lib, R, C)
-    for r0, c0, dr, dc, n, slots in body_segments(R):
-        t.add(r0, c0, dr, dc, n, slots, slots, *rule)
-    return t.finalize()
-
-
-def bands_hold_nodes(table, E):
-    rows = {n["r"] for n in table.nodes()}
-    R = table.R
-    return all(any(a <= r < b for r in rows) for a, b in ((0, E), (E, R - E), (R - E, R)))
 
 
 # ---- 1. FRAME + INNER == lbm_ade_stream_collide_m on one block (ghost = 0) ---------------------------------------------------
@@ -143,14 +94,14 @@ def test_frame_plus_inner_is_the_one_block_step(lib, form, edges, shape):
     g, bc, prm = geom(R, C, 0, pitch), EDGES[edges], kbc.params(form)
     _, src = post_collision(lib, g, bc, prm)
     mw = moment_fields(g)
-    want = full_m(lib, g, bc, prm, *src, moments=mw)
+    want = ade_calls.full_step(lib, "_m", g, bc, prm, *src, moments=mw)
     torch.cuda.synchronize()
     assert_finite(want, g, shape)
     assert all(bool(torch.isfinite(t).all()) for t in mw)
     for E in Es:
         for with_moments in (True, False):
             dst, mp = (alloc(g), alloc(g)), (moment_fields(g) if with_moments else None)
-            both_parts(lib, g, bc, prm, dst, src, E, moments=mp)
+            ade_calls.both_parts(lib, "_m", g, bc, prm, dst, src, E, moments=mp)
             torch.cuda.synchronize()
             for k in range(2):
                 assert_bits(owned(dst[k], g), owned(want[k], g), f"{shape} {edges} E={E} moments={with_moments} lattice {k}")
@@ -173,21 +124,11 @@ def test_each_part_alone_writes_exactly_its_rows(lib, form, walls, R, C, pitch, 
     cut = [cut_slab(p, gg, 1, R + 1, pitch) for p in post]
     g, src = cut[0][0], (cut[0][1], cut[1][1])
     want = (alloc(g), alloc(g))
-    both_parts(lib, g, bc, prm, want, src, E)
+    ade_calls.both_parts(lib, "_m", g, bc, prm, want, src, E)
     torch.cuda.synchronize()
     assert_finite(want, g, "FRAME + INNER")
-    for which, rows in ((FRAME, list(range(E)) + list(range(R - E, R))), (INNER, list(range(E, R - E)))):
-        dst = (poisoned(g), poisoned(g))
-        torch.cuda.synchronize()
-        part_m(lib, g, bc, prm, dst, src, which, E)
-        torch.cuda.synchronize()
-        expect = torch.zeros(9 * g.plane_stride, dtype=torch.bool, device=dev())
-        owned(expect, g)[:, rows] = True
-        for k in range(2):
-            what = f"{'FRAME' if which == FRAME else 'INNER'} {R}x{C} E={E} walls={walls} lattice {k}"
-            assert_write_set(dst[k], g, rows, what)
-            diff = torch.nonzero(expect & (bits(dst[k]) != bits(want[k])))
-            assert diff.numel() == 0, f"{what}: {diff.shape[0]} written doubles differ from FRAME + INNER"
+    assert_part_write_sets(lambda dst, which: ade_calls.part(lib, "_m", g, bc, prm, dst, src, which, E), g, want, E,
+                           f"{R}x{C} E={E} walls={walls}")
 
 
 # ---- 3. slabs cut from a global 48 x C lattice -----------------------------------------------------------------------------
@@ -210,9 +151,9 @@ def test_slabs_cut_from_the_global_lattice_give_the_one_blocks_rows(lib, form, c
     _, src = post_collision(lib, gg, GBC, prm)
     prof = torch.from_numpy(np.linspace(1.5e-3, 3e-4, RG)).to(dev())
     gsbc = fixed_edges(0, RG, prof) if case == "fixed" else None
-    table = body_table(lib, RG, C) if case == "body" else None
-    want = full_m(lib, gg, GBC, prm, *src, sbc=gsbc, table=table)
-    plain = full_m(lib, gg, GBC, prm, *src)
+    table = body_table(lib, RG, C, RULE) if case == "body" else None
+    want = ade_calls.full_step(lib, "_m", gg, GBC, prm, *src, sbc=gsbc, iwalls=table)
+    plain = ade_calls.full_step(lib, "_m", gg, GBC, prm, *src)
     torch.cuda.synchronize()
     assert_finite(want, gg, case)
     if case != "box":
@@ -226,7 +167,7 @@ def test_slabs_cut_from_the_global_lattice_give_the_one_blocks_rows(lib, form, c
         for E in (1, 3, 8):
             assert view is None or bands_hold_nodes(view, E)
             dst = (alloc(sg), alloc(sg))
-            both_parts(lib, sg, bc, prm, dst, (cut[0][1], cut[1][1]), E, sbc=sbc, table=view)
+            ade_calls.both_parts(lib, "_m", sg, bc, prm, dst, (cut[0][1], cut[1][1]), E, sbc=sbc, iwalls=view)
             torch.cuda.synchronize()
             for k in range(2):
                 assert_bits(owned(dst[k], sg), owned(want[k], gg)[:, r0:r1], f"{case} C={C} slab [{r0}, {r1}) E={E} lattice {k}")
@@ -237,44 +178,6 @@ def test_slabs_cut_from_the_global_lattice_give_the_one_blocks_rows(lib, form, c
 
 
 # ---- 4. emulated chains and closed rings -----------------------------------------------------------------------------------
-class Chain:
-    """slabs of the given heights of one global box, every slab in turn on this GPU: FRAME + INNER through
-    lbm_ade_stream_collide_part_m, then the single-step halo of BOTH lattices by lbm_halo_pack -> lbm_halo_unpack"""
-
-    def __init__(self, lib, gg, post, heights, closed, gbc, prm):
-        self.lib, self.prm, self.closed, self.n = lib, prm, closed, len(heights)
-        r0 = np.concatenate([[0], np.cumsum(heights)]).tolist()
-        self.slabs = []
-        for k in range(self.n):
-            a, b = r0[k], r0[k + 1]
-            cut = [cut_slab(p, gg, a, b, 0, closed) for p in post]
-            g = cut[0][0]
-            self.slabs.append(dict(g=g, bc=slab_bc(gbc, a, b, gg.R, closed), lat=[[cut[0][1], cut[1][1]], [alloc(g), alloc(g)]]))
-        self.msg = lib.raw.lbm_halo_rows(1) * gg.C
-        self.cur = 0
-
-    def step(self, E):
-        lib, cur = self.lib, self.cur
-        for s in self.slabs:
-            both_parts(lib, s["g"], s["bc"], self.prm, s["lat"][cur ^ 1], s["lat"][cur], min(E, (s["g"].R - 1) // 2))
-        n = self.n
-        for k in range(n):
-            if not self.closed and k == n - 1:
-                continue
-            a, b = self.slabs[k], self.slabs[(k + 1) % n]
-            for j in range(2):
-                down = torch.empty(self.msg, dtype=torch.float64, device=dev())
-                up = torch.empty(self.msg, dtype=torch.float64, device=dev())
-                lib.halo_pack(_ptr(down), _ptr(a["lat"][cur ^ 1][j]), ct.byref(a["g"]), 1, 1, None)
-                lib.halo_pack(_ptr(up), _ptr(b["lat"][cur ^ 1][j]), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(b["lat"][cur ^ 1][j]), _ptr(down), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(a["lat"][cur ^ 1][j]), _ptr(up), ct.byref(a["g"]), 1, 1, None)
-        self.cur ^= 1
-
-    def gather(self, j):
-        return torch.cat([owned(s["lat"][self.cur][j], s["g"]) for s in self.slabs], dim=1)
-
-
 @FORMS
 @pytest.mark.parametrize("closed", [True, False], ids=["closed_ring", "walled_chain"])
 @pytest.mark.parametrize("heights,C", [((24, 24), 64), ((16, 20, 12), 64), ((3, 3, 3, 3), 8)], ids=["2x24x64", "16_20_12x64", "4x3x8"])
@@ -283,11 +186,11 @@ def test_emulated_chain_equals_one_block(lib, form, closed, heights, C):
     prm, gbc = kbc.params(form), (pylbm.Bc.periodic() if closed else GBC)
     gg = geom(sum(heights), C, 0)
     _, post = post_collision(lib, gg, gbc, prm)
-    ch = Chain(lib, gg, post, heights, closed, gbc, prm)
+    ch = chain(lib, gg, post, heights, closed, gbc, prm)
     want, done = [t.clone() for t in post], 0
     for n in (1, 2, 20):
         for _ in range(n - done):
-            want = list(full_m(lib, gg, gbc, prm, *want))
+            want = list(ade_calls.full_step(lib, "_m", gg, gbc, prm, *want))
             ch.step(4)
         done = n
         torch.cuda.synchronize()
@@ -310,7 +213,7 @@ def test_emulated_chain_in_the_reference_order_equals_the_oracle_loop(lib, oracl
     assert kbc.finite(st)
     c = kbc.collide(oracle, st["f"], st["g"], S2, OMEGA_G, W)
     assert np.all(np.isfinite(c["fc"])) and np.all(np.isfinite(c["gc"]))
-    ch = Chain(lib, gg, post, heights, closed, gbc, prm)
+    ch = chain(lib, gg, post, heights, closed, gbc, prm)
     for _ in range(steps):
         ch.step(4)
     torch.cuda.synchronize()
@@ -319,13 +222,13 @@ def test_emulated_chain_in_the_reference_order_equals_the_oracle_loop(lib, oracl
         assert_bits(ch.gather(j), want, f"closed={closed} lattice {j} against the oracle loop")
 
 
-# ---- 5. rank processes (tests/ade_kbc_ring_rank.py) ------------------------------------------------------------------------
+# ---- 5. rank processes (tests/ade_ring_rank.py, entry "model") -------------------------------------------------------------
 def one_block_after(lib, gg, gbc, prm, post, counts, table=None):
     """{n: the lattices after n steps of lbm_ade_stream_collide_m from the post-collision pair}"""
     out, cur, done = {}, [t.clone() for t in post], 0
     for n in counts:
         for _ in range(n - done):
-            cur = list(full_m(lib, gg, gbc, prm, *cur, table=table))
+            cur = list(ade_calls.full_step(lib, "_m", gg, gbc, prm, *cur, iwalls=table))
         done = n
         torch.cuda.synchronize()
         assert_finite(cur, gg, f"one block after {n} steps")
@@ -352,8 +255,8 @@ def test_ring_of_rank_processes_equals_one_block(lib, tmp_path, form, n, closed)
     plain = one_block_after(lib, gg, gbc, prm, post, counts)
     assert not torch.equal(bits(want[20][1]), bits(plain[20][1]))
     cfg = dict(R=R, C=C, steps=list(counts), edge_rows=E, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W), s2=S2,
-               omega_g=OMEGA_G, segments=body_segments(R * n), g_mode=rule[0], conc=rule[1])
-    outs = run_ranks(lib, tmp_path, "ade_kbc_ring_rank.py", n, cfg,
+               omega_g=OMEGA_G, entry="model", segments=body_segments(R * n), g_mode=rule[0], conc=rule[1])
+    outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", n, cfg,
                      dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()), timeout=240)
     for steps in counts:
         for j, key in enumerate(("f", "g")):
@@ -366,27 +269,12 @@ def test_ring_of_rank_processes_equals_one_block(lib, tmp_path, form, n, closed)
 
 def test_ring_entry_points_refuse_a_ring_without_one_ghost_row(lib, tmp_path):
     """ghost = 2 on the ring: both `_m` ring entries refuse it on the host with the existing message"""
-    cfg = dict(case="refusals", R=32, C=64, s2=S2, omega_g=OMEGA_G, form=FAST, w=list(W))
-    outs = run_ranks(lib, tmp_path, "ade_kbc_ring_rank.py", 1, cfg, {}, timeout=240)
+    cfg = dict(case="refusals", entry="model", R=32, C=64, s2=S2, omega_g=OMEGA_G, form=FAST, w=list(W))
+    outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", 1, cfg, {}, timeout=240)
     msgs = json.loads(str(outs[0]["msgs"]))
     assert len(msgs) == 2
     for name, m in zip(("lbm_ring_ade_collide_m", "lbm_ring_ade_step_m"), msgs):
         assert f"{name}: ghost=2: the fluid + scalar step over slabs exchanges one ghost row per side" in m, m
-
-
-class OneSlabRing:
-    """a ring of one rank in this process, not closed: a chain of one slab -- nothing travels, both parts run on `main`"""
-
-    def __init__(self, lib, sg):
-        self.lib, self.ring, ident = lib, ct.c_void_p(), (ct.c_ubyte * 128)()
-        lib.ring_unique_id(ident)
-        lib.ring_create(ct.byref(self.ring), ident, 0, 1, ct.byref(sg), 0)
-
-    def __enter__(self):
-        return self.ring
-
-    def __exit__(self, *exc):
-        self.lib.ring_destroy(self.ring)
 
 
 @FORMS
@@ -396,7 +284,7 @@ def test_ring_step_m_on_a_chain_of_one_slab_is_the_one_block_step(lib, form):
     prm = kbc.params(form)
     prof = torch.from_numpy(np.linspace(1.5e-3, 3e-4, R)).to(dev())
     sbc = pylbm.AdeScalarBC(row_lo=7e-4, col_lo=(0.0, prof), col_hi=0.0)
-    table = body_table(lib, R, C)
+    table = body_table(lib, R, C, RULE)
     assert bands_hold_nodes(table, E)
     gg = geom(R, C, 0)
     _, want = post_collision(lib, gg, GBC, prm)
@@ -405,15 +293,14 @@ def test_ring_step_m_on_a_chain_of_one_slab_is_the_one_block_step(lib, form):
     sg = cut[0][0]
     lat = [[cut[0][1], cut[1][1]], [alloc(sg), alloc(sg)]]
     for _ in range(steps):
-        want = full_m(lib, gg, GBC, prm, *want, sbc=sbc, table=table)
-        plain = full_m(lib, gg, GBC, prm, *plain)
+        want = ade_calls.full_step(lib, "_m", gg, GBC, prm, *want, sbc=sbc, iwalls=table)
+        plain = ade_calls.full_step(lib, "_m", gg, GBC, prm, *plain)
     torch.cuda.synchronize()
     assert_finite(want, gg, "one block")
     with OneSlabRing(lib, sg) as ring:
         for k in range(steps):
             src, dst = lat[k & 1], lat[(k & 1) ^ 1]
-            lib.ring_ade_step_m(ring, _ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(GBC), ct.byref(prm[0]),
-                                ct.byref(prm[1]), ct.byref(sbc), table.h, E, None)
+            ade_calls.call(lib, "lbm_ring_ade_step_m", rg=ring, dst=dst, src=src, bc=GBC, prm=prm, sbc=sbc, iwalls=table, edge_rows=E)
         torch.cuda.synchronize()
     for j in range(2):
         assert_bits(owned(lat[steps & 1][j], sg), owned(want[j], gg), f"lattice {j}")
@@ -435,7 +322,7 @@ def test_model_bgk_through_the_m_calls_is_part_w_and_step_w(lib, form):
     _, post = post_collision(lib, gg, pylbm.Bc(row_lo=BB, col_lo=BB, col_hi=SP), kbc.params(form))
     cut = [cut_slab(p, gg, 0, R, C + 6) for p in post]
     g, src = cut[0][0], (cut[0][1], cut[1][1])
-    table = body_table(lib, R, C)
+    table = body_table(lib, R, C, RULE)
     count = lib.raw.lbm_ade_part_launches
     outs, launches = [], []
     for which_call in ("w", "m"):
@@ -443,11 +330,9 @@ def test_model_bgk_through_the_m_calls_is_part_w_and_step_w(lib, form):
         before = count()
         for which in (FRAME, INNER):
             if which_call == "w":
-                lib.ade_stream_collide_part_w(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                              ct.byref(bprm[0]), ct.byref(bprm[1]), ct.byref(sbc), None, table.h, which, E,
-                                              None, None, None, None)
+                ade_calls.part(lib, "_w", g, bc, bprm, dst, src, which, E, sbc=sbc, iwalls=table)
             else:
-                part_m(lib, g, bc, mprm, dst, src, which, E, sbc=sbc, table=table)
+                ade_calls.part(lib, "_m", g, bc, mprm, dst, src, which, E, sbc=sbc, iwalls=table)
         torch.cuda.synchronize()
         outs.append(dst)
         launches.append(count() - before)
@@ -466,11 +351,8 @@ def test_model_bgk_through_the_m_calls_is_part_w_and_step_w(lib, form):
         for which_call in ("w", "m"):
             dst = (poisoned(sg), poisoned(sg))
             before = count()
-            args = (ring, _ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(gbc))
-            if which_call == "w":
-                lib.ring_ade_step_w(*args, ct.byref(bprm[0]), ct.byref(bprm[1]), ct.byref(sbc), None, table.h, E, None)
-            else:
-                lib.ring_ade_step_m(*args, ct.byref(mprm[0]), ct.byref(mprm[1]), ct.byref(sbc), table.h, E, None)
+            ade_calls.call(lib, "lbm_ring_ade_step_" + which_call, rg=ring, dst=dst, src=src, bc=gbc,
+                           prm=bprm if which_call == "w" else mprm, sbc=sbc, iwalls=table, edge_rows=E)
             torch.cuda.synchronize()
             outs.append(dst)
             launches.append(count() - before)
@@ -496,7 +378,7 @@ def test_a_part_is_one_launch_and_two_where_its_rows_hold_wall_nodes(lib, form):
     empty = pylbm.AdeInteriorWalls(lib, R, C).finalize()
     none_here = pylbm.AdeInteriorWalls(lib, 48, C).add(40, 3, 0, 1, 5, ROW_NEG, ROW_NEG).slab(0, R).finalize()
     inner_only = pylbm.AdeInteriorWalls(lib, R, C).add(10, 20, 0, 1, 11, ROW_NEG, ROW_NEG).finalize()
-    everywhere = body_table(lib, R, C)
+    everywhere = body_table(lib, R, C, RULE)
     assert empty.count() == none_here.count() == 0 and bands_hold_nodes(everywhere, E)
     count = lib.raw.lbm_ade_part_launches
     got, outs = {}, {}
@@ -505,7 +387,7 @@ def test_a_part_is_one_launch_and_two_where_its_rows_hold_wall_nodes(lib, form):
         per_part = []
         for which in (FRAME, INNER):
             before = count()
-            part_m(lib, g, bc, prm, dst, src, which, E, sbc=sbc, table=t)
+            ade_calls.part(lib, "_m", g, bc, prm, dst, src, which, E, sbc=sbc, iwalls=t)
             per_part.append(count() - before)
         torch.cuda.synchronize()
         got[name], outs[name] = per_part, dst
@@ -531,16 +413,16 @@ def test_a_captured_graph_of_frame_then_inner_replays_to_the_same_bits(lib, form
     _, post = post_collision(lib, gg, pylbm.Bc(row_lo=BB, col_lo=BB, col_hi=SP), prm)
     cut = [cut_slab(p, gg, 0, R, C + 6) for p in post]
     g, src = cut[0][0], (cut[0][1], cut[1][1])
-    table = body_table(lib, R, C)
+    table = body_table(lib, R, C, RULE)
     want, dst = (poisoned(g), poisoned(g)), (poisoned(g), poisoned(g))
-    both_parts(lib, g, bc, prm, want, src, E, sbc=sbc, table=table)
+    ade_calls.both_parts(lib, "_m", g, bc, prm, want, src, E, sbc=sbc, iwalls=table)
     torch.cuda.synchronize()
     assert_finite(want, g, "the eager run")
     st, graph = ct.c_void_p(), ct.c_void_p()
     lib.stream_create(ct.byref(st))
     try:
         lib.graph_begin_capture(st)
-        both_parts(lib, g, bc, prm, dst, src, E, sbc=sbc, table=table, stream=st.value)
+        ade_calls.both_parts(lib, "_m", g, bc, prm, dst, src, E, sbc=sbc, iwalls=table, s=st.value)
         lib.graph_end_capture(st, ct.byref(graph))
         for replay in range(2):
             for d in dst:

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
+import ade_calls  # noqa: E402
 import ade_open_util as aou  # noqa: E402
 import ade_util as ade  # noqa: E402
 from ade_open_util import ABB, ABB_X, ALL, BB_RULE, SPEC_COL, SPEC_ROW, Segments, mask  # noqa: E402
@@ -89,19 +90,12 @@ def carry_buffer(table, extra=0):
     return t
 
 
-def raw_collide(lib, g, bc, prm, dst, src, table, carry_out, sbc=None, by=None, moments=None):
-    lib.ade_collide_o(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                      ct.byref(prm[1]), ade._ref(sbc), ade._ref(by), ade._handle(table), _ptr(carry_out),
-                      *ade._moment_ptrs(moments), None)
+def raw_collide(lib, g, bc, prm, dst, src, table, carry_out, **kw):
+    ade_calls.collide(lib, "_o", g, bc, prm, dst, src, open=table, carry_out=carry_out, **kw)
 
 
-def raw_step(lib, g, bc, prm, dst, src, table, carry_in, carry_out, sbc=None, by=None, walls=None, moments=None, rows=None,
-             stream=None):
-    r0, r1 = rows if rows is not None else (0, g.R)
-    lib.ade_stream_collide_o(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                             ct.byref(prm[0]), ct.byref(prm[1]), ade._ref(sbc), ade._ref(by), ade._handle(walls),
-                             ade._handle(table), _ptr(carry_in), _ptr(carry_out), r0, r1, *ade._moment_ptrs(moments),
-                             pylbm._stream(stream))
+def raw_step(lib, g, bc, prm, dst, src, table, carry_in, carry_out, **kw):
+    ade_calls.step_into(lib, "_o", g, bc, prm, dst, src, open=table, carry_in=carry_in, carry_out=carry_out, **kw)
 
 
 def raw_run(lib, g, bc, prm, f0, g0, n, table, sbc=None, by=None, walls=None):
@@ -110,10 +104,10 @@ def raw_run(lib, g, bc, prm, f0, g0, n, table, sbc=None, by=None, walls=None):
     src = (ade.to_lattice(f0, g), ade.to_lattice(g0, g))
     cin, moments = carry_buffer(table), None
     dst = (ade.poisoned(g), ade.poisoned(g))
-    raw_collide(lib, g, bc, prm, dst, src, table, cin, sbc, by)
+    raw_collide(lib, g, bc, prm, dst, src, table, cin, sbc=sbc, buoy=by)
     for _ in range(n):
         src, dst, cout, moments = dst, (ade.poisoned(g), ade.poisoned(g)), carry_buffer(table), ade.moment_fields(g)
-        raw_step(lib, g, bc, prm, dst, src, table, cin, cout, sbc, by, walls, moments)
+        raw_step(lib, g, bc, prm, dst, src, table, cin, cout, sbc=sbc, buoy=by, iwalls=walls, moments=moments)
         cin = cout
     torch.cuda.synchronize()
     return dst, cin, moments
@@ -293,10 +287,10 @@ def test_null_and_the_empty_table_are_the_walled_step_and_a_table_costs_one_laun
     fo, go = ade.to_lattice(f0, g), ade.to_lattice(g0, g)
     walls = rectangle_table(lib, R, C, -7, 10, 16)
     empty = pylbm.AdeOpenBoundary(lib, R, C).finalize()
-    want = ade.full_step_w(lib, g, BOTTOM, prm, fo, go, table=walls)
+    want = ade_calls.full_step(lib, "_w", g, BOTTOM, prm, fo, go, iwalls=walls)
     for table in (None, empty):
         dst = (ade.alloc(g), ade.alloc(g))
-        raw_step(lib, g, BOTTOM, prm, dst, (fo, go), table, None, None, walls=walls)  # no carry asked for
+        raw_step(lib, g, BOTTOM, prm, dst, (fo, go), table, None, None, iwalls=walls)  # no carry asked for
         ade.assert_bits(dst[0], want[0], "f")
         ade.assert_bits(dst[1], want[1], "g")
     launches = {}
@@ -368,18 +362,18 @@ def test_carry_row_range_and_overlap_refusals_name_what_is_wrong(lib, oracle):
              "the table is for a 12 x 16 lattice, the call for 12 x 18")
     # a node of both tables with an open rule
     walls = pylbm.AdeInteriorWalls(lib, R, C).add(5, C - 1, 1, 0, 2, COL_NEG, 0).finalize()
-    _refused(lib, lambda: raw_step(lib, g, BOTTOM, prm, dst, src, table, a, b, walls=walls), step,
+    _refused(lib, lambda: raw_step(lib, g, BOTTOM, prm, dst, src, table, a, b, iwalls=walls), step,
              r"node \(5, 15\) carries an open-boundary rule and is in the interior-wall table")
     walls.close()
     # a node of both tables without a rule, reading a redirected node where no wall replaces the slot
     walls = pylbm.AdeInteriorWalls(lib, R, C).add(1, 5, 0, 1, 1, ROW_NEG, 0).finalize()
-    _refused(lib, lambda: raw_step(lib, g, BOTTOM, prm, dst, src, table, a, b, walls=walls), step,
+    _refused(lib, lambda: raw_step(lib, g, BOTTOM, prm, dst, src, table, a, b, iwalls=walls), step,
              r"node \(1, 5\) is in the interior-wall table and its g slot \d is redirected")
     walls.close()
     # the foot on the bottom wall is allowed -- but only while that row is a wall
     walls = pylbm.AdeInteriorWalls(lib, R, C).add(-1, 5, 0, 1, 1, 0, mask(4, 8), FIXED, 0.0).finalize()
-    raw_step(lib, g, BOTTOM, prm, dst, src, table, a, b, walls=walls)
-    _refused(lib, lambda: raw_step(lib, g, pylbm.Bc(), prm, dst, src, table, a, b, walls=walls), step,
+    raw_step(lib, g, BOTTOM, prm, dst, src, table, a, b, iwalls=walls)
+    _refused(lib, lambda: raw_step(lib, g, pylbm.Bc(), prm, dst, src, table, a, b, iwalls=walls), step,
              r"node \(11, 5\) is in the interior-wall table and its g slot 3 is redirected")
     torch.cuda.synchronize()
     walls.close()

@@ -5,7 +5,8 @@ lbm_ring_ade_step_o and slab_ring_ade --channel.
 The yardstick is one block in the SAME form: lbm_ade_collide_o / lbm_ade_stream_collide_o on the global lattice with the
 global table (pinned to the oracle in tests/test_gpu_ade_open.py).  Every comparison is of bit patterns, so there are no
 tolerances.  Each test asserts that every band it exercises holds a listed node (bands_hold_nodes): an inlet or outlet
-column puts one into every row."""
+column puts one into every row.  The chain of slabs, the carry helpers and the write-set check of a part are
+tests/ade_slab_util.py's; every raw call goes through tests/ade_calls.py."""
 import ctypes as ct
 
 import numpy as np
@@ -16,11 +17,13 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
 from ade_open_util import build_open  # noqa: E402
-from ade_util import (GUO, REFERENCE, SENTINEL, W, alloc, assert_bits, bits, buoyancy, cut_slab, geom, owned, params,  # noqa: E402
-                      random_lattice, to_lattice)
+import ade_calls  # noqa: E402
+from ade_slab_util import (Chain, OneSlabRing, assert_part_write_sets, bands_hold_nodes, carry_like, first_index,  # noqa: E402
+                           global_state, slab_bc)
+from ade_util import (GUO, REFERENCE, SENTINEL, W, alloc, assert_bits, bits, buoyancy, cut_slab, geom, moment_fields,  # noqa: E402
+                      owned, params, poisoned, random_lattice)
 from gpu_util import dev  # noqa: E402
 from proc_util import last_json, run_driver, run_ranks  # noqa: E402
-from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 FORMS = pytest.mark.parametrize("form", [REF, FAST], ids=["reference_order", "reassociated"])
@@ -41,14 +44,6 @@ def lib():
     lib = pylbm.Lib()
     assert lib.device_count() >= 1, "no HIP device visible"
     return lib
-
-
-def _ref(x):
-    return ct.byref(x) if x is not None else None
-
-
-def _h(t):
-    return t.h if t is not None else None
 
 
 # ---- tables and calls ----------------------------------------------------------------------------------------------------
@@ -97,66 +92,15 @@ def rectangle(lib, R, C, r_top, c1, c2):
     return t
 
 
-def bands_hold_nodes(view, E):
-    rows = {n["r"] for n in view.nodes()}
-    R = view.R
-    return all(any(a <= r < b for r in rows) for a, b in ((0, E), (E, R - E), (R - E, R)))
-
-
-def first_index(table, row0):
-    """the index in the parent of the first node of a view that starts at row0"""
-    return sum(1 for n in table.nodes() if n["r"] < row0)
-
-
-def moment_fields(g):
-    m = [torch.zeros(n * g.R * g.C, dtype=torch.float64, device=dev()) for n in (1, 2, 1)]
-    for t in m:
-        bits(t).fill_(SENTINEL)
-    return m
-
-
-def carry_like(table, seed=None):
-    """a carry of the table: SENTINEL, or (seed) velocities of a few per cent"""
-    if table is None:
-        return None
-    n = table.carry_len()
-    if seed is None:
-        t = torch.zeros(n, dtype=torch.float64, device=dev())
-        bits(t).fill_(SENTINEL)
-        return t
-    return torch.from_numpy(0.03 * np.random.default_rng(seed).standard_normal(n)).to(dev())
-
-
-def block_o(lib, g, bc, prm, src, table, cin, sbc=None, by=None, walls=None, moments=None):
+def block_o(lib, g, bc, prm, src, table, cin, **kw):
     """the yardstick: lbm_ade_stream_collide_o on one block -> (fn, gn, carry_out)"""
-    fn, gn, cout = alloc(g), alloc(g), carry_like(table)
-    m = [_ptr(t) for t in moments] if moments else [None, None, None]
-    lib.ade_stream_collide_o(_ptr(fn), _ptr(gn), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                             ct.byref(prm[1]), _ref(sbc), _ref(by), _h(walls), _h(table), _ptr(cin), _ptr(cout), 0, g.R, *m, None)
+    cout = carry_like(table)
+    fn, gn = ade_calls.full_step(lib, "_o", g, bc, prm, *src, open=table, carry_in=cin, carry_out=cout, **kw)
     return fn, gn, cout
 
 
-def part_o_rc(lib, g, bc, prm, dst, src, which, E, view, cin, cout, sbc=None, by=None, walls=None, moments=None, stream=None):
-    m = [_ptr(t) for t in moments] if moments else [None, None, None]
-    return lib.raw.lbm_ade_stream_collide_part_o(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g),
-                                                 ct.byref(bc), ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), _h(walls),
-                                                 _h(view), _ptr(cin), _ptr(cout), which, E, *m, pylbm._stream(stream))
-
-
-def part_o(lib, *a, **kw):
-    rc = part_o_rc(lib, *a, **kw)
-    assert rc == 0, lib.raw.lbm_last_error_string().decode()
-
-
-def part_w(lib, g, bc, prm, dst, src, which, E, sbc=None, by=None, walls=None):
-    lib.ade_stream_collide_part_w(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                  ct.byref(prm[0]), ct.byref(prm[1]), _ref(sbc), _ref(by), _h(walls), which, E, None, None, None,
-                                  None)
-
-
-def slab_bc(gbc, r0, r1, Rg, closed=False):
-    return pylbm.Bc(row_lo=HALO if (closed or r0 > 0) else gbc.row_lo, row_hi=HALO if (closed or r1 < Rg) else gbc.row_hi,
-                    col_lo=gbc.col_lo, col_hi=gbc.col_hi)
+def part_o(lib, g, bc, prm, dst, src, which, E, view, cin, cout, **kw):
+    ade_calls.part(lib, "_o", g, bc, prm, dst, src, which, E, view=view, carry_in=cin, carry_out=cout, **kw)
 
 
 # ---- 1. FRAME + INNER with a view == the one-block step on the global lattice --------------------------------------------
@@ -188,8 +132,8 @@ def test_frame_plus_inner_with_a_view_is_the_one_block_step(lib, form, case, C, 
     walls = rectangle(lib, RG, C, 30, C // 2 - 3, C // 2 + 3).finalize() if spec.get("walls") else None
     cin = carry_like(table, seed=5)
     mw = moment_fields(gg)
-    want = block_o(lib, gg, WALLS, prm, src, table, cin, gsbc, by, walls, mw)
-    plain = block_o(lib, gg, WALLS, prm, src, None, None, gsbc, by, walls)
+    want = block_o(lib, gg, WALLS, prm, src, table, cin, sbc=gsbc, buoy=by, iwalls=walls, moments=mw)
+    plain = block_o(lib, gg, WALLS, prm, src, None, None, sbc=gsbc, buoy=by, iwalls=walls)
     assert not torch.equal(bits(want[0]), bits(plain[0])) or not torch.equal(bits(want[1]), bits(plain[1]))  # the table is felt
     for r0, r1 in VIEWS:
         R = r1 - r0
@@ -210,7 +154,8 @@ def test_frame_plus_inner_with_a_view_is_the_one_block_step(lib, form, case, C, 
             assert bands_hold_nodes(view, E)
             dst, cout, mp = (alloc(sg), alloc(sg)), carry_like(view), moment_fields(sg)
             for which in (FRAME, INNER):
-                part_o(lib, sg, bc, prm, dst, (slab[0][1], slab[1][1]), which, E, view, vin, cout, sbc, by, wview, mp)
+                part_o(lib, sg, bc, prm, dst, (slab[0][1], slab[1][1]), which, E, view, vin, cout, sbc=sbc, buoy=by, iwalls=wview,
+                       moments=mp)
             torch.cuda.synchronize()
             what = f"{case} C={C} slab [{r0}, {r1}) E={E}"
             for k in range(2):
@@ -228,29 +173,14 @@ def test_frame_plus_inner_with_a_view_is_the_one_block_step(lib, form, case, C, 
 
 
 # ---- emulated chains and rings in one process ----------------------------------------------------------------------------
-def global_state(oracle, Rg, C, seed=0, w=W, scale=1.0):
-    rng = np.random.default_rng(seed)
-    r, c = np.meshgrid(np.arange(Rg, dtype=float), np.arange(C, dtype=float), indexing="ij")
-    u = np.zeros((Rg, C, 2))
-    u[..., 1] = 0.03 * np.sin(2 * np.pi * r / Rg)
-    u += 0.005 * rng.standard_normal((Rg, C, 2))
-    rho = 1 + 0.01 * rng.standard_normal((Rg, C))
-    f = oracle.equilibrium(u, rho) * (1 + 0.005 * rng.standard_normal((Rg, C, 9)))
-    s = 0.15 * min(Rg, C)
-    conc = scale * 1e-3 * np.exp(-((r - 0.4 * Rg) ** 2 + (c - 0.55 * C) ** 2) / (2 * s * s))
-    gg = geom(Rg, C, 0)
-    return gg, [to_lattice(a, gg) for a in (f, oracle.equilibrium(u + np.asarray(w), conc))]
-
-
 def one_block(lib, gg, pre, gbc, prm, steps, table, walls=None, by=None):
     """lbm_ade_collide_o + steps x lbm_ade_stream_collide_o on the global lattice: the post-collision state and its carry,
     and the (lattices, carry) after each number of steps in `steps`"""
     post, c0 = [alloc(gg), alloc(gg)], carry_like(table)
-    lib.ade_collide_o(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(gg), ct.byref(gbc), ct.byref(prm[0]),
-                      ct.byref(prm[1]), None, _ref(by), _h(table), _ptr(c0), None, None, None, None)
+    ade_calls.collide(lib, "_o", gg, gbc, prm, post, pre, buoy=by, open=table, carry_out=c0)
     cur, carry, out = post, c0, {}
     for k in range(1, max(steps) + 1):
-        fn, gn, carry = block_o(lib, gg, gbc, prm, cur, table, carry, None, by, walls)
+        fn, gn, carry = block_o(lib, gg, gbc, prm, cur, table, carry, buoy=by, iwalls=walls)
         cur = [fn, gn]
         if k in steps:
             out[k] = (cur, carry)
@@ -258,67 +188,32 @@ def one_block(lib, gg, pre, gbc, prm, steps, table, walls=None, by=None):
     return post, c0, out
 
 
-class Chain:
-    """slabs of the given heights of one global box, every slab in turn on this GPU: FRAME + INNER through
-    lbm_ade_stream_collide_part_o with the slab's views, then the single-step halo of BOTH lattices by lbm_halo_pack ->
-    lbm_halo_unpack.  The carry never travels."""
+def chain(lib, gg, post, carry0, heights, closed, gbc, prm, table, walls=None, by=None):
+    """ade_slab_util.Chain through lbm_ade_stream_collide_part_o, every slab with its views and its two carries (the part
+    of carry0 of its nodes, and a poisoned one).  The carry never travels."""
+    def per_slab(k, a, b, bc):
+        view, i0 = table.slab(a, b - a).finalize(), first_index(table, a)
+        return dict(view=view, walls=walls.slab(a, b - a).finalize() if walls is not None else None,
+                    carry=[carry0[2 * i0:2 * (i0 + view.count())].clone(), carry_like(view)])
 
-    def __init__(self, lib, gg, post, carry0, heights, closed, gbc, prm, table, walls=None, by=None):
-        self.lib, self.prm, self.closed, self.n, self.by = lib, prm, closed, len(heights), by
-        self.r0 = np.concatenate([[0], np.cumsum(heights)]).tolist()
-        self.slabs = []
-        for k in range(self.n):
-            a, b = self.r0[k], self.r0[k + 1]
-            cut = [cut_slab(p, gg, a, b, 0, closed) for p in post]
-            g = cut[0][0]
-            view = table.slab(a, b - a).finalize()
-            i0 = first_index(table, a)
-            wview = walls.slab(a, b - a).finalize() if walls is not None else None
-            self.slabs.append(dict(g=g, bc=slab_bc(gbc, a, b, gg.R, closed), view=view, walls=wview,
-                                   lat=[[cut[0][1], cut[1][1]], [alloc(g), alloc(g)]],
-                                   carry=[carry0[2 * i0:2 * (i0 + view.count())].clone(), carry_like(view)]))
-        self.msg = lib.raw.lbm_halo_rows(1) * gg.C
-        self.cur = 0
+    def advance(s, dst, src, e):
+        for which in (FRAME, INNER):
+            part_o(lib, s["g"], s["bc"], prm, dst, src, which, e, s["view"], s["carry"][s["cur"]], s["carry"][s["cur"] ^ 1],
+                   buoy=by, iwalls=s["walls"])
 
-    def step(self, E):
-        lib, cur = self.lib, self.cur
-        for s in self.slabs:
-            e = min(E, (s["g"].R - 1) // 2)
-            for which in (FRAME, INNER):
-                part_o(lib, s["g"], s["bc"], self.prm, s["lat"][cur ^ 1], s["lat"][cur], which, e, s["view"], s["carry"][cur],
-                       s["carry"][cur ^ 1], None, self.by, s["walls"])
-        n = self.n
-        for k in range(n):
-            if (not self.closed and k == n - 1) or n == 1:
-                continue
-            a, b = self.slabs[k], self.slabs[(k + 1) % n]
-            for j in range(2):
-                down = torch.empty(self.msg, dtype=torch.float64, device=dev())
-                up = torch.empty(self.msg, dtype=torch.float64, device=dev())
-                lib.halo_pack(_ptr(down), _ptr(a["lat"][cur ^ 1][j]), ct.byref(a["g"]), 1, 1, None)
-                lib.halo_pack(_ptr(up), _ptr(b["lat"][cur ^ 1][j]), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(b["lat"][cur ^ 1][j]), _ptr(down), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(a["lat"][cur ^ 1][j]), _ptr(up), ct.byref(a["g"]), 1, 1, None)
-        self.cur ^= 1
+    return Chain(lib, gg, post, heights, closed, gbc, advance, per_slab=per_slab)
 
-    def gather(self, j):
-        return torch.cat([owned(s["lat"][self.cur][j], s["g"]) for s in self.slabs], dim=1)
 
-    def carry(self):
-        return torch.cat([s["carry"][self.cur] for s in self.slabs])
+def chain_carry(ch):
+    return torch.cat([s["carry"][ch.cur] for s in ch.slabs])
 
-    def check(self, gg, want, what):
-        torch.cuda.synchronize()
-        (lat, carry) = want
-        for j in range(2):
-            assert_bits(self.gather(j), owned(lat[j], gg), f"{what} lattice {j}")
-        assert_bits(self.carry(), carry, f"{what} carry")
 
-    def close(self):
-        for s in self.slabs:
-            s["view"].close()
-            if s["walls"] is not None:
-                s["walls"].close()
+def check_chain(ch, gg, want, what):
+    torch.cuda.synchronize()
+    (lat, carry) = want
+    for j in range(2):
+        assert_bits(ch.gather(j), owned(lat[j], gg), f"{what} lattice {j}")
+    assert_bits(chain_carry(ch), carry, f"{what} carry")
 
 
 CHAINS = {
@@ -343,14 +238,14 @@ def test_emulated_chains_and_rings_equal_one_block_after_1_2_and_20_steps(lib, o
     post, c0, want = one_block(lib, gg, pre, gbc, prm, (1, 2, 20), table, walls)
     _, _, plain = one_block(lib, gg, pre, gbc, prm, (20,), None, walls)
     assert not torch.equal(bits(want[20][0][0]), bits(plain[20][0][0]))
-    ch = Chain(lib, gg, post, c0, heights, spec["closed"], gbc, prm, table, walls)
+    ch = chain(lib, gg, post, c0, heights, spec["closed"], gbc, prm, table, walls)
     assert all(bands_hold_nodes(s["view"], min(E, (s["g"].R - 1) // 2)) for s in ch.slabs)
     if walls is not None:
         assert all(s["walls"].count() > 0 for s in ch.slabs[1:])
     for k in range(1, 21):
         ch.step(E)
         if k in want:
-            ch.check(gg, want[k], f"{case} {heights} after {k} steps")
+            check_chain(ch, gg, want[k], f"{case} {heights} after {k} steps")
     ch.close()
     for t in (table, walls):
         if t is not None:
@@ -371,12 +266,12 @@ def test_the_smallest_shapes(lib, oracle, form, shape):
     gg, pre = global_state(oracle, Rg, C, seed=4)
     table = make(lib, Rg, C).finalize()
     post, c0, want = one_block(lib, gg, pre, gbc, prm, (1, 2, 7), table)
-    ch = Chain(lib, gg, post, c0, heights, closed, gbc, prm, table)
+    ch = chain(lib, gg, post, c0, heights, closed, gbc, prm, table)
     assert all(bands_hold_nodes(s["view"], 1) for s in ch.slabs)
     for k in range(1, 8):
         ch.step(1)
         if k in want:
-            ch.check(gg, want[k], f"{shape} after {k} steps")
+            check_chain(ch, gg, want[k], f"{shape} after {k} steps")
     ch.close()
     table.close()
 
@@ -398,18 +293,16 @@ def test_null_and_empty_views_are_part_w_and_a_view_costs_one_launch_a_part(lib,
     for drive in (None, by):
         outs, launches = [], []
         for t in ("w", None, empty, none_here, real):
-            dst = (alloc(g), alloc(g))
-            for d in dst:
-                bits(d).fill_(SENTINEL)
+            dst = (poisoned(g), poisoned(g))
             cout = carry_like(real)
             before = count()
             for which in (FRAME, INNER):
                 if t == "w":
-                    part_w(lib, g, bc, prm, dst, src, which, E, sbc, drive)
+                    ade_calls.part(lib, "_w", g, bc, prm, dst, src, which, E, sbc=sbc, buoy=drive)
                 elif t is real:
-                    part_o(lib, g, bc, prm, dst, src, which, E, t, carry_like(real, 3), cout, sbc, drive)
+                    part_o(lib, g, bc, prm, dst, src, which, E, t, carry_like(real, 3), cout, sbc=sbc, buoy=drive)
                 else:
-                    part_o(lib, g, bc, prm, dst, src, which, E, t, None, None, sbc, drive)  # no carry needed
+                    part_o(lib, g, bc, prm, dst, src, which, E, t, None, None, sbc=sbc, buoy=drive)  # no carry needed
             torch.cuda.synchronize()
             outs.append(dst)
             launches.append(count() - before)
@@ -437,28 +330,23 @@ def test_each_part_alone_writes_its_rows_nodes_and_their_carry(lib, R, C, E):
     want, wcarry, plain = [alloc(g), alloc(g)], carry_like(view), [alloc(g), alloc(g)]
     for which in (FRAME, INNER):
         part_o(lib, g, bc, prm, want, src, which, E, view, cin, wcarry)
-        part_w(lib, g, bc, prm, plain, src, which, E)
+        ade_calls.part(lib, "_w", g, bc, prm, plain, src, which, E)
     torch.cuda.synchronize()
     assert not (bits(wcarry) == SENTINEL).any()
     assert not torch.equal(bits(want[1]), bits(plain[1]))
     node_rows = torch.tensor([n["r"] for n in view.nodes()], device=dev()).repeat_interleave(2)
-    for which, rows in ((FRAME, list(range(E)) + list(range(R - E, R))), (INNER, list(range(E, R - E)))):
-        dst, cout = (alloc(g), alloc(g)), carry_like(view)
-        for d in dst:
-            bits(d).fill_(SENTINEL)
-        torch.cuda.synchronize()
-        part_o(lib, g, bc, prm, dst, src, which, E, view, cin, cout)
-        torch.cuda.synchronize()
-        what = f"{'FRAME' if which == FRAME else 'INNER'} R={R} C={C} E={E}"
-        expect = torch.zeros(9 * g.plane_stride, dtype=torch.bool, device=dev())
-        owned(expect, g)[:, rows] = True
-        for k in range(2):
-            wrong = torch.nonzero((bits(dst[k]) != SENTINEL) != expect)
-            assert wrong.numel() == 0, f"{what} lattice {k}: {wrong.shape[0]} doubles wrong"
-            assert torch.nonzero(expect & (bits(dst[k]) != bits(want[k]))).numel() == 0, f"{what} lattice {k}: differs from the full call"
-        mine = torch.isin(node_rows, torch.tensor(rows, device=dev()))
+    couts = {}
+
+    def launch(dst, which):
+        couts[which] = carry_like(view)
+        part_o(lib, g, bc, prm, dst, src, which, E, view, cin, couts[which])
+
+    def carry_of_the_part(which, rows, what):
+        cout, mine = couts[which], torch.isin(node_rows, torch.tensor(rows, device=dev()))
         assert torch.equal(bits(cout) != SENTINEL, mine), f"{what}: carry entries written outside its rows' nodes, or missed"
         assert torch.equal(bits(cout)[mine], bits(wcarry)[mine]), f"{what}: carry differs from the full call"
+
+    assert_part_write_sets(launch, g, want, E, f"R={R} C={C} E={E}", also=carry_of_the_part)
     view.close()
 
 
@@ -472,7 +360,8 @@ def test_refusals_at_call_time_name_what_is_wrong(lib):
     def refused(view, bc, msg, cin="in", cout="out", walls=None):
         a = carry_like(view, 1) if cin == "in" else cin
         b = carry_like(view) if cout == "out" else (a if cout == "alias" else cout)
-        rc = part_o_rc(lib, g, bc, prm, dst, src, FRAME, E, view, a, b, walls=walls)
+        rc = ade_calls.call_rc(lib, name, dst=dst, src=src, g=g, bc=bc, prm=prm, iwalls=walls, view=view, carry_in=a, carry_out=b,
+                               part=FRAME, edge_rows=E)
         err = lib.raw.lbm_last_error_string().decode()
         assert rc == LBM_ERR_INVALID and err.startswith(name + ":") and msg in err, (rc, err)
 
@@ -518,12 +407,12 @@ def test_ring_of_two_rank_processes_equals_one_block(lib, oracle, tmp_path, clos
     _, _, plain = one_block(lib, gg, pre, gbc, prm, (steps,), None)
     (wlat, wcarry), (plat, _) = want[steps], plain[steps]
     assert not torch.equal(bits(wlat[1]), bits(plat[1]))
-    cfg = dict(R=R, C=C, steps=steps, edge_rows=E, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
+    cfg = dict(R=R, C=C, steps=[steps], edge_rows=E, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
                entry="open", table=kind)
     outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", n, cfg,
                      dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()), timeout=240)
     for j, key in enumerate(("f", "g")):
-        got = np.concatenate([o[key] for o in outs], axis=1)
+        got = np.concatenate([o[f"{key}_{steps}"] for o in outs], axis=1)
         ref = owned(wlat[j], gg).cpu().numpy()
         assert np.array_equal(got.view(np.uint64), ref.view(np.uint64)), f"{n} ranks closed={closed}: {key} differs"
     carry = np.concatenate([o["carry"] for o in outs])
@@ -550,24 +439,18 @@ def test_the_ring_entry_points_on_a_chain_of_one_slab_are_the_one_block(lib, ora
     sg = cut[0][0]
     lat = [[alloc(sg), alloc(sg)], [alloc(sg), alloc(sg)]]
     carry = [carry_like(view), carry_like(view)]
-    ring, ident = ct.c_void_p(), (ct.c_ubyte * 128)()
-    lib.ring_unique_id(ident)
-    lib.ring_create(ct.byref(ring), ident, 0, 1, ct.byref(sg), 0)
-    try:
-        lib.ring_ade_collide_o(ring, _ptr(lat[0][0]), _ptr(lat[0][1]), _ptr(cut[0][1]), _ptr(cut[1][1]), ct.byref(WALLS),
-                               ct.byref(prm[0]), ct.byref(prm[1]), None, ct.byref(by), view.h, _ptr(carry[0]), None)
+    with OneSlabRing(lib, sg) as ring:
+        ade_calls.call(lib, "lbm_ring_ade_collide_o", rg=ring, dst=lat[0], src=(cut[0][1], cut[1][1]), bc=WALLS, prm=prm, buoy=by,
+                       view=view, carry_out=carry[0])
         torch.cuda.synchronize()
         for j in range(2):
             assert_bits(owned(lat[0][j], sg), owned(post[j], gg), f"collide-only lattice {j}")
         assert_bits(carry[0], c0, "primed carry")
         for k in range(steps):
             a, b = k & 1, (k & 1) ^ 1
-            lib.ring_ade_step_o(ring, _ptr(lat[b][0]), _ptr(lat[b][1]), _ptr(lat[a][0]), _ptr(lat[a][1]), ct.byref(WALLS),
-                                ct.byref(prm[0]), ct.byref(prm[1]), None, ct.byref(by), None, view.h, _ptr(carry[a]),
-                                _ptr(carry[b]), E, None)
+            ade_calls.call(lib, "lbm_ring_ade_step_o", rg=ring, dst=lat[b], src=lat[a], bc=WALLS, prm=prm, buoy=by, view=view,
+                           carry_in=carry[a], carry_out=carry[b], edge_rows=E)
         torch.cuda.synchronize()
-    finally:
-        lib.ring_destroy(ring)
     (wlat, wcarry) = want[steps]
     for j in range(2):
         assert_bits(owned(lat[steps & 1][j], sg), owned(wlat[j], gg), f"lattice {j}")
@@ -589,13 +472,13 @@ def test_the_chain_channel_is_the_single_block_channel_but_for_the_lids_own_scal
     table = channel(lib, RG, CG).finalize()
     _, _, single = one_block(lib, gg, pre, pylbm.Bc(row_lo=PER, row_hi=BB), prm, (steps,), table)
     post, c0, _ = one_block(lib, gg, pre, WALLS, prm, (1,), table)
-    ch = Chain(lib, gg, post, c0, heights, False, WALLS, prm, table)
+    ch = chain(lib, gg, post, c0, heights, False, WALLS, prm, table)
     for _ in range(steps):
         ch.step(4)
     torch.cuda.synchronize()
     (wlat, wcarry) = single[steps]
     assert_bits(ch.gather(0), owned(wlat[0], gg), "f")
-    assert_bits(ch.carry(), wcarry, "carry")
+    assert_bits(chain_carry(ch), wcarry, "carry")
     got, ref = ch.gather(1), owned(wlat[1], gg)
     assert_bits(got[:, 1:], ref[:, 1:], "g below the lid")
     assert not torch.equal(bits(got[:, 0]), bits(ref[:, 0]))
@@ -624,7 +507,7 @@ def test_a_captured_graph_of_an_even_number_of_part_steps_replays_the_eager_run(
         for k in range(10):  # even: lattices and carries are back where the capture found them
             a, b = k & 1, (k & 1) ^ 1
             for which in (FRAME, INNER):
-                part_o(lib, sg, bc, prm, lat[b], lat[a], which, E, view, carry[a], carry[b], stream=st.value)
+                part_o(lib, sg, bc, prm, lat[b], lat[a], which, E, view, carry[a], carry[b], s=st.value)
         lib.graph_end_capture(st, ct.byref(graph))
         for n in (10, 20):
             lib.graph_launch(graph, 1, st)

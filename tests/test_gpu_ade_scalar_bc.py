@@ -7,7 +7,8 @@ driver's expression order:
     g_adve[qbar] = -g_coll[q] + 2.0 * ((((1.0 + 3.0 cv) + 4.5 cv^2) - 1.5 vv) * E_q * C_w),  v = u + w,
     u = calc_u(f_adve) after the fluid's wall fix-ups, cv = c_q.v, vv = v.v
 at every population a FIXED edge wins (rows first, columns win at the corners).  In the reference operation order the
-step is compared BITWISE with it."""
+step is compared BITWISE with it.  The slab tests run the chain and the write-set check of tests/ade_slab_util.py through the
+_ex entries (tests/ade_calls.py)."""
 import ctypes as ct
 
 import numpy as np
@@ -18,11 +19,12 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
-from ade_util import (GBC, SENTINEL, W, alloc, assert_bits, assert_state_bits, bits, build_sbc, cut_slab,  # noqa: E402
-                      geom, initial_state, oracle_loop, owned, params, random_lattice)
+import ade_calls  # noqa: E402
+from ade_slab_util import Chain, assert_part_write_sets, global_state  # noqa: E402
+from ade_util import (GBC, W, alloc, assert_bits, assert_state_bits, build_sbc, cut_slab, geom, initial_state,  # noqa: E402
+                      oracle_loop, owned, params, random_lattice)
 from gpu_util import bits_equal, dev  # noqa: E402
 from proc_util import ipc_env, key_values, last_json, run_driver  # noqa: E402
-from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 BB, SP, HALO, PER = pylbm.EDGE_BOUNCE_BACK, pylbm.EDGE_SPECULAR, pylbm.EDGE_HALO, pylbm.EDGE_PERIODIC
@@ -264,19 +266,7 @@ def test_graph_replay_reads_the_profile_array_at_every_replay(lib, oracle):
 
 
 # ---- 7. slabs -----------------------------------------------------------------------------------------------------------
-# the yardstick and the parts through the entry points this suite is about (the _ex ones)
-def full_step(lib, g, bc, prm, sbc, fo, go):
-    fn, gn = alloc(g), alloc(g)
-    lib.ade_stream_collide_ex(_ptr(fn), _ptr(gn), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                              ct.byref(prm[1]), ct.byref(sbc), 0, g.R, None, None, None, None)
-    return fn, gn
-
-
-def part(lib, g, bc, prm, sbc, dst, src, which, E):
-    lib.ade_stream_collide_part_ex(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                   ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), which, E, None, None, None, None)
-
-
+# every slab call of this suite goes through the entry points it is about (the _ex ones)
 def slab_descriptor(prof, r0, bc):
     """FIXED row 0 (a chain end only), row R-1 NO_FLUX, column 0 a profile slice, column C-1 absorbing"""
     kw = dict(col_lo=(0.0, prof.data_ptr() + 8 * r0), col_hi=0.0)
@@ -296,13 +286,13 @@ def test_frame_plus_inner_is_the_one_block_step_with_fixed_walls(lib, form):
         prof = torch.from_numpy(reference_profile(R)).to(dev())
         gsbc = slab_descriptor(prof, 0, GBC)
         src = (random_lattice(gg, R + C), random_lattice(gg, R * C))
-        want = full_step(lib, gg, GBC, prm, gsbc, *src)
+        want = ade_calls.full_step(lib, "_ex", gg, GBC, prm, *src, sbc=gsbc)
         for E in (1, 3, 16, 40):
             if 2 * E >= R:
                 continue
             dst = (alloc(gg), alloc(gg))
-            part(lib, gg, GBC, prm, gsbc, dst, src, FRAME, E)
-            part(lib, gg, GBC, prm, gsbc, dst, src, INNER, E)
+            ade_calls.part(lib, "_ex", gg, GBC, prm, dst, src, FRAME, E, sbc=gsbc)
+            ade_calls.part(lib, "_ex", gg, GBC, prm, dst, src, INNER, E, sbc=gsbc)
             torch.cuda.synchronize()
             for k in range(2):
                 assert_bits(owned(dst[k], gg), owned(want[k], gg), f"one block R={R} C={C} E={E} lattice {k}")
@@ -316,8 +306,8 @@ def test_frame_plus_inner_is_the_one_block_step_with_fixed_walls(lib, form):
                 if 2 * E >= sg.R:
                     continue
                 dst = (alloc(sg), alloc(sg))
-                part(lib, sg, bc, prm, sbc, dst, (slab[0][1], slab[1][1]), FRAME, E)
-                part(lib, sg, bc, prm, sbc, dst, (slab[0][1], slab[1][1]), INNER, E)
+                ade_calls.part(lib, "_ex", sg, bc, prm, dst, (slab[0][1], slab[1][1]), FRAME, E, sbc=sbc)
+                ade_calls.part(lib, "_ex", sg, bc, prm, dst, (slab[0][1], slab[1][1]), INNER, E, sbc=sbc)
                 torch.cuda.synchronize()
                 for k in range(2):
                     assert_bits(owned(dst[k], sg), owned(want[k], gg)[:, r0:r1],
@@ -333,77 +323,35 @@ def test_each_fixed_part_alone_writes_exactly_its_rows(lib, R, C, E):
     sbc = slab_descriptor(prof, 0, bc)
     src = (random_lattice(g, R), random_lattice(g, C))
     want = [alloc(g), alloc(g)]
-    part(lib, g, bc, prm, sbc, want, src, FRAME, E)
-    part(lib, g, bc, prm, sbc, want, src, INNER, E)
-    for which, rows in ((FRAME, list(range(E)) + list(range(R - E, R))), (INNER, list(range(E, R - E)))):
-        dst = (alloc(g), alloc(g))
-        for d in dst:
-            bits(d).fill_(SENTINEL)
-        torch.cuda.synchronize()
-        part(lib, g, bc, prm, sbc, dst, src, which, E)
-        torch.cuda.synchronize()
-        expect = torch.zeros(9 * g.plane_stride, dtype=torch.bool, device=dev())
-        owned(expect, g)[:, rows] = True
-        for k in range(2):
-            changed = bits(dst[k]) != SENTINEL
-            wrong = torch.nonzero(changed != expect)
-            assert wrong.numel() == 0, f"part {which} R={R} C={C} E={E} lattice {k}: {wrong.shape[0]} doubles wrong"
-            diff = torch.nonzero(expect & (bits(dst[k]) != bits(want[k])))
-            assert diff.numel() == 0, f"part {which} R={R} C={C} E={E} lattice {k}: written doubles differ"
+    ade_calls.part(lib, "_ex", g, bc, prm, want, src, FRAME, E, sbc=sbc)
+    ade_calls.part(lib, "_ex", g, bc, prm, want, src, INNER, E, sbc=sbc)
+    assert_part_write_sets(lambda dst, which: ade_calls.part(lib, "_ex", g, bc, prm, dst, src, which, E, sbc=sbc), g, want, E,
+                           f"R={R} C={C} E={E}")
 
 
 @pytest.mark.parametrize("form", [REF, FAST])
 @pytest.mark.parametrize("heights,C", [((50, 130), 200), ((40, 40, 40, 40), 96)])
 def test_emulated_chain_with_fixed_walls_equals_one_block(lib, oracle, form, heights, C):
-    """a chain (walls on its ends) stepped slab by slab, halos of both lattices by lbm_halo_pack / _unpack, FIXED row
+    """a chain (walls on its ends) stepped slab by slab (ade_slab_util.Chain, which moves the halos of both lattices), FIXED row
     0 on the first slab only, column profile sliced per slab: == one block, 41 steps"""
     prm = params(form)
     Rg, steps = sum(heights), 41
-    gg = geom(Rg, C, 0)
-    f0, g0 = initial_state(oracle, Rg, C, seed=Rg)
-    pre = []
-    for a in (f0, g0):
-        t = alloc(gg)
-        owned(t, gg)[:] = torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1))).to(dev())
-        pre.append(t)
+    gg, pre = global_state(oracle, Rg, C, seed=Rg)
     prof = torch.from_numpy(reference_profile(Rg)).to(dev())
     gsbc = slab_descriptor(prof, 0, GBC)
     post = [alloc(gg), alloc(gg)]
-    lib.ade_collide(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(gg), ct.byref(GBC),
-                    ct.byref(prm[0]), ct.byref(prm[1]), None, None, None, None)
+    ade_calls.collide(lib, "", gg, GBC, prm, post, pre)
     cur = [t.clone() for t in post]
     for _ in range(steps):
-        cur = list(full_step(lib, gg, GBC, prm, gsbc, *cur))
-    r0s = np.concatenate([[0], np.cumsum(heights)]).tolist()
-    n = len(heights)
-    slabs = []
-    for k in range(n):
-        a, b = r0s[k], r0s[k + 1]
-        bc = pylbm.Bc(row_lo=BB if k == 0 else HALO, row_hi=BB if k == n - 1 else HALO, col_lo=BB, col_hi=SP)
-        cut = [cut_slab(p, gg, a, b, 0) for p in post]
-        slabs.append(dict(g=cut[0][0], bc=bc, sbc=slab_descriptor(prof, a, bc),
-                          lat=[[cut[0][1], cut[1][1]], [alloc(cut[0][0]), alloc(cut[0][0])]]))
-    msg = lib.raw.lbm_halo_rows(1) * C
-    c = 0
+        cur = list(ade_calls.full_step(lib, "_ex", gg, GBC, prm, *cur, sbc=gsbc))
+    ch = Chain(lib, gg, post, heights, False, GBC,
+               lambda s, dst, src, e: ade_calls.both_parts(lib, "_ex", s["g"], s["bc"], prm, dst, src, e, sbc=s["sbc"]),
+               per_slab=lambda k, a, b, bc: dict(sbc=slab_descriptor(prof, a, bc)))
     for _ in range(steps):
-        for s in slabs:
-            e = min(16, (s["g"].R - 1) // 2)
-            part(lib, s["g"], s["bc"], prm, s["sbc"], s["lat"][c ^ 1], s["lat"][c], FRAME, e)
-            part(lib, s["g"], s["bc"], prm, s["sbc"], s["lat"][c ^ 1], s["lat"][c], INNER, e)
-        for k in range(n - 1):
-            a, b = slabs[k], slabs[k + 1]
-            for j in range(2):
-                down = torch.empty(msg, dtype=torch.float64, device=dev())
-                up = torch.empty(msg, dtype=torch.float64, device=dev())
-                lib.halo_pack(_ptr(down), _ptr(a["lat"][c ^ 1][j]), ct.byref(a["g"]), 1, 1, None)
-                lib.halo_pack(_ptr(up), _ptr(b["lat"][c ^ 1][j]), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(b["lat"][c ^ 1][j]), _ptr(down), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(a["lat"][c ^ 1][j]), _ptr(up), ct.byref(a["g"]), 1, 1, None)
-        c ^= 1
+        ch.step(16)
     torch.cuda.synchronize()
     for j in range(2):
-        got = torch.cat([owned(s["lat"][c][j], s["g"]) for s in slabs], dim=1)
-        assert_bits(got, owned(cur[j], gg), f"chain {heights} lattice {j}")
+        assert_bits(ch.gather(j), owned(cur[j], gg), f"chain {heights} lattice {j}")
 
 
 # ---- 8. drivers and real rank processes ---------------------------------------------------------------------------------

@@ -5,10 +5,11 @@ The yardstick is one block: lbm_ade_stream_collide on the global lattice (pinned
 tests/test_gpu_ade.py).  Post-collision f and g are compared BITWISE on every owned node:
   * FRAME + INNER == the full step, on single blocks and on ghost-1 slabs cut from the global lattice;
   * each part alone writes exactly its rows, nothing of the ghost rows or the padding (NaN-poisoned destinations);
-  * chains / rings of 2..4 slabs, halos moved by lbm_halo_pack / _unpack on both lattices, == one block;
+  * chains / rings of 2..4 slabs, the one-row halos of both lattices moved by ade_slab_util.Chain, == one block;
   * real rank processes over the peer-mapped transport (tests/ade_ring_rank.py) == one block;
-  * the driver's own --check; and the scalar's mass and transport across the seams."""
-import ctypes as ct
+  * the driver's own --check; and the scalar's mass and transport across the seams.
+The chain of slabs, the edges of a slab and the write-set check of a part are tests/ade_slab_util.py's; every raw call goes
+through tests/ade_calls.py with the suffix-less entries."""
 import json
 
 import numpy as np
@@ -18,12 +19,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
-from ade_util import (GBC, SENTINEL, W, alloc, assert_bits, bits, cut_slab, geom, owned, params,  # noqa: E402
-                      random_lattice, to_lattice)
-from ade_util import full_step as full_step_b  # noqa: E402  (lbm_ade_stream_collide_b: every descriptor)
+import ade_calls  # noqa: E402
+from ade_slab_util import Chain, OneSlabRing, assert_part_write_sets, global_state, slab_bc  # noqa: E402
+from ade_util import GBC, W, alloc, assert_bits, cut_slab, geom, owned, params, random_lattice  # noqa: E402
 from gpu_util import dev  # noqa: E402
 from proc_util import last_json, run_driver, run_ranks  # noqa: E402
-from pylbm import _ptr  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
 FRAME, INNER = pylbm.ADE_PART_FRAME, pylbm.ADE_PART_INNER
@@ -45,18 +45,10 @@ def pitch_of(C):
     return C + 16 if C >= 1024 else 0  # 1040 columns: a padded row pitch
 
 
-# the yardstick and the parts through the entry points this suite is about (the suffix-less ones)
-def full_step(lib, g, bc, prm, fo, go):
-    fn, gn = alloc(g), alloc(g)
-    lib.ade_stream_collide(_ptr(fn), _ptr(gn), _ptr(fo), _ptr(go), ct.byref(g), ct.byref(bc), ct.byref(prm[0]),
-                           ct.byref(prm[1]), 0, g.R, None, None, None, None)
-    return fn, gn
-
-
-def part(lib, g, bc, prm, dst, src, which, E, stream=None):
-    lib.ade_stream_collide_part(_ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(g), ct.byref(bc),
-                                ct.byref(prm[0]), ct.byref(prm[1]), which, E, None, None, None, None,
-                                pylbm._stream(stream))
+# every call of this suite goes through the suffix-less entry points
+def chain(lib, gg, post, heights, closed, gbc, prm):
+    return Chain(lib, gg, post, heights, closed, gbc,
+                 lambda s, dst, src, e: ade_calls.both_parts(lib, "", s["g"], s["bc"], prm, dst, src, e))
 
 
 # ---- 1. FRAME + INNER == the full step -----------------------------------------------------------------------------------
@@ -68,13 +60,13 @@ def test_frame_plus_inner_is_the_full_step_on_one_block(lib, form, walls):
         for C in (96, 200, 1040):
             g = geom(R, C, 0, pitch_of(C))
             src = (random_lattice(g, R + C), random_lattice(g, R * C))
-            want = full_step(lib, g, bc, prm, *src)
+            want = ade_calls.full_step(lib, "", g, bc, prm, *src)
             for E in (1, 3, 16, 40):
                 if 2 * E >= R:
                     continue
                 dst = (alloc(g), alloc(g))
-                part(lib, g, bc, prm, dst, src, FRAME, E)
-                part(lib, g, bc, prm, dst, src, INNER, E)
+                ade_calls.part(lib, "", g, bc, prm, dst, src, FRAME, E)
+                ade_calls.part(lib, "", g, bc, prm, dst, src, INNER, E)
                 torch.cuda.synchronize()
                 for k in range(2):
                     assert_bits(owned(dst[k], g), owned(want[k], g), f"R={R} C={C} E={E} walls={walls} lattice {k}")
@@ -89,19 +81,18 @@ def test_frame_plus_inner_on_slabs_cut_from_the_global_lattice(lib, form, walls)
         for C in (96, 200, 1040):
             gg = geom(R, C, 0, pitch_of(C))
             src = (random_lattice(gg, R + 7 * C), random_lattice(gg, 3 * R + C))
-            want = full_step(lib, gg, gbc, prm, *src)
+            want = ade_calls.full_step(lib, "", gg, gbc, prm, *src)
             h = R // 2
             for r0, r1 in ((0, h), (h, R), (R // 4, R // 4 + h)):
-                bc = pylbm.Bc(row_lo=gbc.row_lo if (r0 == 0 and walls) else HALO,
-                              row_hi=gbc.row_hi if (r1 == R and walls) else HALO, col_lo=gbc.col_lo, col_hi=gbc.col_hi)
+                bc = slab_bc(gbc, r0, r1, R, not walls)
                 slab = [cut_slab(s, gg, r0, r1, pitch_of(C), not walls) for s in src]
                 sg = slab[0][0]
                 for E in (1, 3, 16, 40):
                     if 2 * E >= sg.R:
                         continue
                     dst = (alloc(sg), alloc(sg))
-                    part(lib, sg, bc, prm, dst, (slab[0][1], slab[1][1]), FRAME, E)
-                    part(lib, sg, bc, prm, dst, (slab[0][1], slab[1][1]), INNER, E)
+                    ade_calls.part(lib, "", sg, bc, prm, dst, (slab[0][1], slab[1][1]), FRAME, E)
+                    ade_calls.part(lib, "", sg, bc, prm, dst, (slab[0][1], slab[1][1]), INNER, E)
                     torch.cuda.synchronize()
                     for k in range(2):
                         assert_bits(owned(dst[k], sg), owned(want[k], gg)[:, r0:r1],
@@ -122,100 +113,20 @@ def test_each_part_alone_writes_exactly_its_rows(lib, R, C, E, walls):
     g = geom(R, C, 1, pitch_of(C))
     src = (random_lattice(g, R), random_lattice(g, C))
     want = [alloc(g), alloc(g)]
-    part(lib, g, bc, prm, want, src, FRAME, E)
-    part(lib, g, bc, prm, want, src, INNER, E)
-    for which, rows in ((FRAME, list(range(E)) + list(range(R - E, R))), (INNER, list(range(E, R - E)))):
-        dst = (alloc(g), alloc(g))
-        for d in dst:
-            bits(d).fill_(SENTINEL)
-        torch.cuda.synchronize()
-        part(lib, g, bc, prm, dst, src, which, E)
-        torch.cuda.synchronize()
-        expect = torch.zeros(9 * g.plane_stride, dtype=torch.bool, device=dev())
-        owned(expect, g)[:, rows] = True
-        for k in range(2):
-            changed = bits(dst[k]) != SENTINEL
-            wrong = torch.nonzero(changed != expect)
-            what = f"{'FRAME' if which == FRAME else 'INNER'} R={R} C={C} E={E} walls={walls} lattice {k}"
-            assert wrong.numel() == 0, f"{what}: {wrong.shape[0]} doubles wrong, first flat index {int(wrong[0, 0])} " \
-                                       f"({'missed' if bool(expect[int(wrong[0, 0])]) else 'over-written'})"
-            diff = torch.nonzero(expect & (bits(dst[k]) != bits(want[k])))
-            assert diff.numel() == 0, f"{what}: {diff.shape[0]} written doubles differ from the full call"
+    ade_calls.part(lib, "", g, bc, prm, want, src, FRAME, E)
+    ade_calls.part(lib, "", g, bc, prm, want, src, INNER, E)
+    assert_part_write_sets(lambda dst, which: ade_calls.part(lib, "", g, bc, prm, dst, src, which, E), g, want, E,
+                           f"R={R} C={C} E={E} walls={walls}")
 
 
 # ---- 3. chains and rings of slabs in one process -------------------------------------------------------------------------
-def global_state(lib, oracle, Rg, C, seed=0, w=W, conc_rows=None):
-    """pre-collision f, g of the global box (dense SoA, ghost 0): a shear wave with noise, the scalar a Gaussian blob
-    (or, with conc_rows = (a, b), a blob confined to rows [a, b): exactly zero elsewhere)"""
-    rng = np.random.default_rng(seed)
-    r, c = np.meshgrid(np.arange(Rg, dtype=float), np.arange(C, dtype=float), indexing="ij")
-    u = np.zeros((Rg, C, 2))
-    u[..., 1] = 0.03 * np.sin(2 * np.pi * r / Rg)
-    u += 0.005 * rng.standard_normal((Rg, C, 2))
-    rho = 1 + 0.01 * rng.standard_normal((Rg, C))
-    f = oracle.equilibrium(u, rho) * (1 + 0.005 * rng.standard_normal((Rg, C, 9)))
-    s = 0.15 * min(Rg, C)
-    if conc_rows is None:
-        conc = 1e-3 * np.exp(-((r - 0.4 * Rg) ** 2 + (c - 0.55 * C) ** 2) / (2 * s * s))
-    else:
-        a, b = conc_rows
-        conc = np.where((r >= a) & (r < b), 1e-3 * np.exp(-((r - (a + b) / 2) ** 2 + (c - C / 2) ** 2) / (2 * s * s)), 0.0)
-    g = oracle.equilibrium(u + np.asarray(w), conc)
-    gg = geom(Rg, C, 0)
-    return gg, [to_lattice(a, gg) for a in (f, g)]
-
-
-class Chain:
-    """slabs of the given heights of one global box, every slab in turn on this GPU: FRAME + INNER, then the single-step
-    halo of BOTH lattices by lbm_halo_pack -> device copy -> lbm_halo_unpack"""
-
-    def __init__(self, lib, gg, post, heights, closed, gbc, prm, C_pitch=0):
-        self.lib, self.prm, self.closed, self.n = lib, prm, closed, len(heights)
-        self.r0 = np.concatenate([[0], np.cumsum(heights)]).tolist()
-        self.slabs = []
-        for k in range(self.n):
-            a, b = self.r0[k], self.r0[k + 1]
-            bc = pylbm.Bc(row_lo=HALO if (closed or k > 0) else gbc.row_lo,
-                          row_hi=HALO if (closed or k < self.n - 1) else gbc.row_hi, col_lo=gbc.col_lo, col_hi=gbc.col_hi)
-            cut = [cut_slab(p, gg, a, b, C_pitch, closed) for p in post]
-            g = cut[0][0]
-            self.slabs.append(dict(g=g, bc=bc, lat=[[cut[0][1], cut[1][1]], [alloc(g), alloc(g)]]))
-        self.msg = lib.raw.lbm_halo_rows(1) * gg.C
-        self.cur = 0
-
-    def step(self, E):
-        lib, cur = self.lib, self.cur
-        for s in self.slabs:
-            e = min(E, (s["g"].R - 1) // 2)
-            part(lib, s["g"], s["bc"], self.prm, s["lat"][cur ^ 1], s["lat"][cur], FRAME, e)
-            part(lib, s["g"], s["bc"], self.prm, s["lat"][cur ^ 1], s["lat"][cur], INNER, e)
-        n = self.n
-        for k in range(n):
-            nx = (k + 1) % n
-            if not self.closed and k == n - 1:
-                continue
-            a, b = self.slabs[k], self.slabs[nx]
-            for j in range(2):
-                down = torch.empty(self.msg, dtype=torch.float64, device=dev())
-                up = torch.empty(self.msg, dtype=torch.float64, device=dev())
-                lib.halo_pack(_ptr(down), _ptr(a["lat"][cur ^ 1][j]), ct.byref(a["g"]), 1, 1, None)
-                lib.halo_pack(_ptr(up), _ptr(b["lat"][cur ^ 1][j]), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(b["lat"][cur ^ 1][j]), _ptr(down), ct.byref(b["g"]), 1, 0, None)
-                lib.halo_unpack(_ptr(a["lat"][cur ^ 1][j]), _ptr(up), ct.byref(a["g"]), 1, 1, None)
-        self.cur ^= 1
-
-    def gather(self, j):
-        return torch.cat([owned(s["lat"][self.cur][j], s["g"]) for s in self.slabs], dim=1)
-
-
 def one_block(lib, gg, pre, gbc, prm, steps):
     """lbm_ade_collide + `steps` x lbm_ade_stream_collide on the global lattice: (post-collision state, after steps)"""
     post = [alloc(gg), alloc(gg)]
-    lib.ade_collide(_ptr(post[0]), _ptr(post[1]), _ptr(pre[0]), _ptr(pre[1]), ct.byref(gg), ct.byref(gbc),
-                    ct.byref(prm[0]), ct.byref(prm[1]), None, None, None, None)
+    ade_calls.collide(lib, "", gg, gbc, prm, post, pre)
     cur = [t.clone() for t in post]
     for _ in range(steps):
-        cur = list(full_step(lib, gg, gbc, prm, *cur))
+        cur = list(ade_calls.full_step(lib, "", gg, gbc, prm, *cur))
     torch.cuda.synchronize()
     return post, cur
 
@@ -227,9 +138,9 @@ def one_block(lib, gg, pre, gbc, prm, steps):
 def test_emulated_chain_equals_one_block(lib, oracle, form, closed, heights, C):
     prm, gbc = params(form), (pylbm.Bc.periodic() if closed else wall_bc(True))
     Rg, steps = sum(heights), 53
-    gg, pre = global_state(lib, oracle, Rg, C)
+    gg, pre = global_state(oracle, Rg, C)
     post, want = one_block(lib, gg, pre, gbc, prm, steps)
-    ch = Chain(lib, gg, post, heights, closed, gbc, prm)
+    ch = chain(lib, gg, post, heights, closed, gbc, prm)
     for _ in range(steps):
         ch.step(16)
     torch.cuda.synchronize()
@@ -243,14 +154,14 @@ def test_emulated_chain_equals_one_block(lib, oracle, form, closed, heights, C):
 def test_ring_of_rank_processes_equals_one_block(lib, oracle, tmp_path, n, closed):
     R, C, steps, form = 48, 200, 31, FAST
     prm, gbc = params(form), (pylbm.Bc.periodic() if closed else wall_bc(True))
-    gg, pre = global_state(lib, oracle, R * n, C, seed=n)
+    gg, pre = global_state(oracle, R * n, C, seed=n)
     _, want = one_block(lib, gg, pre, gbc, prm, steps)
-    cfg = dict(R=R, C=C, steps=steps, edge_rows=16, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
+    cfg = dict(R=R, C=C, steps=[steps], edge_rows=16, closed=int(closed), form=form, bc=bytes(gbc).hex(), w=list(W),
                entry="plain")
     outs = run_ranks(lib, tmp_path, "ade_ring_rank.py", n, cfg,
                      dict(f0=owned(pre[0], gg).cpu().numpy(), g0=owned(pre[1], gg).cpu().numpy()), timeout=240)
     for j, key in enumerate(("f", "g")):
-        got = np.concatenate([o[key] for o in outs], axis=1)
+        got = np.concatenate([o[f"{key}_{steps}"] for o in outs], axis=1)
         ref = owned(want[j], gg).cpu().numpy()
         assert np.array_equal(got.view(np.uint64), ref.view(np.uint64)), f"{n} ranks closed={closed}: {key} differs"
     # refresh after a restore (lbm_ring_exchange_pair) is checked by the ranks themselves: ghost rows == neighbours' rows
@@ -282,18 +193,12 @@ def test_ring_step_with_walls_fixed_edges_and_buoyancy_is_the_one_block_step(lib
     sg = cut[0][0]
     lat = [[cut[0][1], cut[1][1]], [alloc(sg), alloc(sg)]]
     for _ in range(steps):
-        want = full_step_b(lib, gg, GBC, prm, *want, sbc=sbc, by=by)
-    ring, ident = ct.c_void_p(), (ct.c_ubyte * 128)()
-    lib.ring_unique_id(ident)
-    lib.ring_create(ct.byref(ring), ident, 0, 1, ct.byref(sg), 0)
-    try:
+        want = ade_calls.full_step(lib, "_b", gg, GBC, prm, *want, sbc=sbc, buoy=by)
+    with OneSlabRing(lib, sg) as ring:
         for k in range(steps):
-            src, dst = lat[k & 1], lat[(k & 1) ^ 1]
-            lib.ring_ade_step_b(ring, _ptr(dst[0]), _ptr(dst[1]), _ptr(src[0]), _ptr(src[1]), ct.byref(GBC),
-                                ct.byref(prm[0]), ct.byref(prm[1]), ct.byref(sbc), ct.byref(by), E, None)
+            ade_calls.call(lib, "lbm_ring_ade_step_b", rg=ring, dst=lat[(k & 1) ^ 1], src=lat[k & 1], bc=GBC, prm=prm, sbc=sbc,
+                           buoy=by, edge_rows=E)
         torch.cuda.synchronize()
-    finally:
-        lib.ring_destroy(ring)
     for j in range(2):
         assert_bits(owned(lat[steps & 1][j], sg), owned(want[j], gg), f"lattice {j}")
 
@@ -324,10 +229,10 @@ def test_scalar_mass_and_transport_across_the_seams_of_a_walled_chain(lib, oracl
     heights, C = (40, 40, 40), 64
     w = (0.05, 0.0)
     prm, gbc = params(FAST, w=w), wall_bc(True)
-    gg, pre = global_state(lib, oracle, sum(heights), C, seed=5, w=w, conc_rows=(4, 36))
+    gg, pre = global_state(oracle, sum(heights), C, seed=5, w=w, conc_rows=(4, 36))
     assert float(owned(pre[1], gg)[:, 40:].abs().sum()) == 0.0
     post, _ = one_block(lib, gg, pre, gbc, prm, 0)
-    ch = Chain(lib, gg, post, heights, False, gbc, prm)
+    ch = chain(lib, gg, post, heights, False, gbc, prm)
     m0 = float(ch.gather(1).sum())
     for _ in range(500):
         ch.step(8)

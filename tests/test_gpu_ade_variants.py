@@ -23,10 +23,11 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
+from ade_calls import full_step, part, step_into  # noqa: E402
+from ade_slab_util import slab_bc  # noqa: E402
 from ade_util import (GBC, GUO, W, alloc, assert_bits, assert_state_bits, assert_write_set, bits, build_sbc,  # noqa: E402
-                      buoyancy, buoyant_initial_state, collide, cut_slab, from_lattice, full_step, full_step_w, geom,
-                      initial_state, moment_fields, oracle_loop, owned, params, part, part_w, poisoned, random_lattice,
-                      step_into, to_lattice)
+                      buoyancy, buoyant_initial_state, collide, cut_slab, from_lattice, geom, initial_state, moment_fields,
+                      oracle_loop, owned, params, poisoned, random_lattice, to_lattice)
 from gpu_util import bits_equal, dev  # noqa: E402
 
 REF, FAST = pylbm.FORM_REFERENCE_ORDER, pylbm.FORM_REASSOCIATED
@@ -74,7 +75,7 @@ def run_steps(lib, g, bc, prm, src, steps, sbc, by, with_moments):
     """`steps` ping-pong steps of lbm_ade_stream_collide_b: (the last pair of lattices, the moments of the last step)"""
     cur, m = src, (moment_fields(g) if with_moments else None)
     for _ in range(steps):
-        cur = full_step(lib, g, bc, prm, *cur, sbc=sbc, by=by, moments=m)
+        cur = full_step(lib, "_b", g, bc, prm, *cur, sbc=sbc, buoy=by, moments=m)
     torch.cuda.synchronize()
     return cur, m
 
@@ -110,7 +111,7 @@ def test_every_variant_of_the_one_block_step(lib, oracle, edges, descriptor):
     if fixed and edges == "periodic":
         for form in FORMS.values():
             with pytest.raises(pylbm.LbmError, match="FIXED on a PERIODIC"):
-                full_step(lib, g, bc, params(form, w=w), *src, sbc=sbc)
+                full_step(lib, "_b", g, bc, params(form, w=w), *src, sbc=sbc)
         return
     st = oracle_loop(oracle, f0, g0, OMEGA, OMEGA_G, w, steps, bc, fixed, by=by)
     yard = collide(oracle, st["f"], st["g"], OMEGA, OMEGA_G, w, by)
@@ -144,7 +145,7 @@ def test_every_variant_of_the_one_block_step(lib, oracle, edges, descriptor):
             knobs(lib, nt, 7)
             dst, m = (alloc(g), alloc(g)), moment_fields(g)
             for rows in ((0, 2), (2, R)):
-                step_into(lib, g, bc, prm, dst, src, sbc, by, rows, m)
+                step_into(lib, "_b", g, bc, prm, dst, src, rows, sbc=sbc, buoy=by, moments=m)
             torch.cuda.synchronize()
             assert_same_run((dst, m), first, f"{fname} rows [0, 2) + [2, {R}) nt={nt} grid_cap=7")
 
@@ -165,9 +166,7 @@ def cut(gg, gbc, src, r0, r1):
     if (r0, r1) == (0, gg.R):
         return gg, gbc, src
     slab = [cut_slab(s, gg, r0, r1, gg.row_pitch) for s in src]
-    bc = pylbm.Bc(row_lo=HALO if r0 > 0 else gbc.row_lo, row_hi=HALO if r1 < gg.R else gbc.row_hi, col_lo=gbc.col_lo,
-                  col_hi=gbc.col_hi)
-    return slab[0][0], bc, (slab[0][1], slab[1][1])
+    return slab[0][0], slab_bc(gbc, r0, r1, gg.R), (slab[0][1], slab[1][1])
 
 
 def scalar_walls(prof, r0, r1, Rg):
@@ -228,12 +227,12 @@ def test_every_variant_of_the_part_launches(lib, layout, form, descriptor):
     src_g = random_lattice(gg, 1), random_lattice(gg, 2)
     default_knobs(lib)
     want_m = moment_fields(gg)
-    want = full_step(lib, gg, GBC, prm, *src_g, sbc=gsbc, by=by, moments=want_m)
+    want = full_step(lib, "_b", gg, GBC, prm, *src_g, sbc=gsbc, buoy=by, moments=want_m)
     g, bc, src = cut(gg, GBC, src_g, r0, r1)
     assert g.R == R0
 
     def launch(dst, which, E, m):
-        part(lib, g, bc, prm, dst, src, which, E, sbc=sbc, by=by, moments=m)
+        part(lib, "_b", g, bc, prm, dst, src, which, E, sbc=sbc, buoy=by, moments=m)
 
     for E in (1, 2):
         check_parts(lib, launch, g, E, gg, want, want_m, r0, r1, f"{layout} {form} {descriptor}")
@@ -266,13 +265,13 @@ def test_every_variant_of_the_part_launches_with_interior_walls(lib, layout, for
     assert rows == set(range(R0))  # every band of E = 1 and E = 2 holds a node
     default_knobs(lib)
     want_m = moment_fields(gg)
-    want = full_step_w(lib, gg, GBC, prm, *src_g, sbc=gsbc, by=by, table=table, moments=want_m)
-    plain = full_step(lib, gg, GBC, prm, *src_g, sbc=gsbc, by=by)
+    want = full_step(lib, "_w", gg, GBC, prm, *src_g, sbc=gsbc, buoy=by, iwalls=table, moments=want_m)
+    plain = full_step(lib, "_b", gg, GBC, prm, *src_g, sbc=gsbc, buoy=by)
     assert not torch.equal(bits(want[1]), bits(plain[1]))  # the body is felt
     g, bc, src = cut(gg, GBC, src_g, r0, r1)
 
     def launch(dst, which, E, m):
-        part_w(lib, g, bc, prm, dst, src, which, E, sbc=sbc, by=by, table=view, moments=m)
+        part(lib, "_w", g, bc, prm, dst, src, which, E, sbc=sbc, buoy=by, iwalls=view, moments=m)
 
     for E in (1, 2):
         check_parts(lib, launch, g, E, gg, want, want_m, r0, r1, f"{layout} {form} {descriptor} with the body")
@@ -361,14 +360,14 @@ def test_the_smallest_slab(lib, C, layout, form, descriptor):
     wants = []
     for t, v in ((None, None), (table, view)):
         what = f"R=3 C={C} {layout} {form} {descriptor} table={t is not None}"
-        want = full_step_w(lib, gg, GBC, prm, *src_g, sbc=gsbc, by=by, table=t)
+        want = full_step(lib, "_w", gg, GBC, prm, *src_g, sbc=gsbc, buoy=by, iwalls=t)
         wants.append(want)
         dst = poisoned(g), poisoned(g)
         for which, rows in ((FRAME, [0, 2]), (INNER, [0, 1, 2])):
             if t is None:
-                part(lib, g, bc, prm, dst, src, which, E, sbc=sbc, by=by)
+                part(lib, "_b", g, bc, prm, dst, src, which, E, sbc=sbc, buoy=by)
             else:
-                part_w(lib, g, bc, prm, dst, src, which, E, sbc=sbc, by=by, table=v)
+                part(lib, "_w", g, bc, prm, dst, src, which, E, sbc=sbc, buoy=by, iwalls=v)
             torch.cuda.synchronize()
             for k, name in enumerate("fg"):
                 assert_write_set(dst[k], g, rows, f"{what}: after part {which}, {name}")
