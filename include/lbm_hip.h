@@ -718,7 +718,7 @@ int lbm_ade_stream_collide_part_m(double* fn, double* gn, const double* fo, cons
 int lbm_ade_solver_create_m(lbm_ade_solver** out, const lbm_geom* g, const lbm_bc* bc /* NULL = periodic */,
                             const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, lbm_stream_t s);
 
-/* Buoyancy with the fluid by model, single block: lbm_ade_collide_m / lbm_ade_stream_collide_m with the descriptor of
+/* Buoyancy with the fluid by model: lbm_ade_collide_m / lbm_ade_stream_collide_m with the descriptor of
  * lbm_ade_buoyancy after sbc, and the context's setter for either fluid.
  * model = LBM_MODEL_BGK: the calls ARE lbm_ade_collide_b / lbm_ade_stream_collide_w / lbm_ade_solver_set_buoyancy with
  * `bgk` -- the same checks under those names, the same launches, the same bits.
@@ -741,9 +741,9 @@ int lbm_ade_solver_create_m(lbm_ade_solver** out, const lbm_geom* g, const lbm_b
  * its own (one per step on a periodic box, one more with wall edges, one more per non-empty table), no halo traffic.
  * Refused on the host before any device call, under the `_mb` name: a non-finite field of the descriptor and everything the
  * `_m` calls refuse.  The calls only enqueue; a captured graph keeps the descriptor of its capture.
- * Not extended: row slabs and the ring (lbm_ade_stream_collide_part_m, lbm_ring_ade_*_m have no parameter for buoyancy),
- * open boundaries and the wall exchange with a KBC fluid stay refused, and lbm_ade_solver_set_buoyancy itself still
- * refuses beta != (0, 0) on a KBC context. */
+ * Row slabs and the ring: lbm_ade_slab_stream_collide_mb below, lbm_ring_ade_slab_collide_mb / lbm_ring_ade_slab_step_mb
+ * with the ring.  Open boundaries and the wall exchange with a KBC fluid stay refused, there is no solver context for
+ * slabs, and lbm_ade_solver_set_buoyancy itself still refuses beta != (0, 0) on a KBC context. */
 int lbm_ade_collide_mb(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
                        const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                        const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s);
@@ -753,6 +753,28 @@ int lbm_ade_stream_collide_mb(double* fn, double* gn, const double* fo, const do
                               int row_begin, int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
 /* the context's buoyancy for either fluid, from the next step on; NULL = the passive scalar.  The descriptor is copied */
 int lbm_ade_solver_set_buoyancy_m(lbm_ade_solver* sv, const lbm_ade_buoyancy* buoy);
+/* One part of a slab's step with the fluid by model AND buoyancy: lbm_ade_stream_collide_part_m's arguments with the
+ * descriptor of lbm_ade_buoyancy after sbc.  (Its name, like those of the two ring entries lbm_ring_ade_slab_collide_mb /
+ * lbm_ring_ade_slab_step_mb, does not continue the lbm_ade_stream_collide_part* family: the set of those names is closed.)
+ * model = LBM_MODEL_KBC, beta != (0, 0): the forced collision of the seven-step list above on the part's rows -- the
+ * geometries, edges, lbm_ade_scalar_bc, slab-local interior-wall table and optional moments (the shifted u) of
+ * lbm_ade_stream_collide_part_m.  ONE dispatch per part, the buoyant part kernel (ade_kbc.hpp: both row bands, wall fix-ups
+ * inline, the scalar collided and stored before the fluid's two collisions; there is no edge pass), and one more, the
+ * interior-wall pass, where the part's rows hold table nodes; both count in lbm_ade_part_launches.  The reference order in
+ * both halves whatever `form` says.  FRAME + INNER store the bits of lbm_ade_stream_collide_mb on one block.  The call only
+ * enqueues: no allocation, no host synchronisation, capturable in a graph, which keeps the descriptor of its capture.
+ * model = LBM_MODEL_KBC, NULL descriptor or beta = (0, 0): the passive lbm_ade_stream_collide_part_m step of either form --
+ * the same bits, the same launches.
+ * model = LBM_MODEL_BGK: IS lbm_ade_stream_collide_part_w with `bgk` and the same `buoy` -- the same checks under that
+ * name, the same launches, the same bits.
+ * Refused on the host before any device call, under this name: NULL arguments, a non-finite field of the descriptor and
+ * everything lbm_ade_stream_collide_part_m refuses (pressure rows, a kbc.form that differs from scalar->form, s2 outside
+ * (0, 2], a bad part or edge_rows).  There is no parameter for an open view, and the wall exchange stays refused for this
+ * fluid. */
+int lbm_ade_slab_stream_collide_mb(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                   const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                                   const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                                   int part, int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s);
 
 /* Open boundaries of the fused step on a single block: the inlet, the outlet, the specular lid and the zero-gradient
  * copies of test/rectangle_sedimentation_test.cpp (:134-177, :203-218), as a host table built like lbm_ade_iwalls --
@@ -995,6 +1017,19 @@ int lbm_ring_ade_collide_m(lbm_ring* rg, double* fp, double* gp, const double* f
 int lbm_ring_ade_step_m(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
                         const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                         const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main);
+/* The two `_m` ring entries with the descriptor of lbm_ade_buoyancy after sbc (lbm_ade_slab_stream_collide_mb's fluids and
+ * refusals, under these names).  model = LBM_MODEL_KBC with beta != (0, 0): the collide-only iteration and the step run the
+ * forced KBC collision on lbm_ring_ade_step_m's schedule, unchanged -- ghost = 1, seams HALO, a FIXED row dropped at a seam,
+ * FRAME and its wall pass on the ring's stream before the pack, INNER on `main`, one message per neighbour with both
+ * lattices.  The force is local to a node: no synchronisation is added.  NULL or beta = (0, 0): lbm_ring_ade_collide_m /
+ * lbm_ring_ade_step_m.  model = LBM_MODEL_BGK: ARE lbm_ring_ade_collide_b / lbm_ring_ade_step_w with `bgk` and the same
+ * `buoy`.  Bitwise equal to lbm_ade_collide_mb / lbm_ade_stream_collide_mb on one block. */
+int lbm_ring_ade_slab_collide_mb(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                                 const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                                 const lbm_ade_buoyancy* buoy, lbm_stream_t main);
+int lbm_ring_ade_slab_step_mb(lbm_ring* rg, double* fn, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                              const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                              const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main);
 /* refresh the single-step ghost rows of two lattices in one message per neighbour (e.g. after restoring a state);
  * asynchronous, ordered after the work enqueued on `after` (lbm_ring_join makes a stream wait for it) */
 int lbm_ring_exchange_pair(lbm_ring* rg, double* lattice_a, double* lattice_b, lbm_stream_t after);

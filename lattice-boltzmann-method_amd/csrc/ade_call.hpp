@@ -1,6 +1,6 @@
-// The resolved call of the fused fluid + scalar step: for the four translation units that launch ade.hpp's kernels
-// (capi_ade.hip: the BGK fluid and every host check; capi_ade_kbc.hip, capi_ade_kbc_part.hip, capi_ade_kbc_buoyant.hip: the
-// KBC fluid), which share their launch path in ade_launch.hpp.  Every other unit keeps a call in an AdeCallBuf
+// The resolved call of the fused fluid + scalar step: for the translation units that launch ade.hpp's kernels
+// (capi_ade.hip: the BGK fluid and every host check; capi_ade_kbc.hip, capi_ade_kbc_part.hip, capi_ade_kbc_buoyant.hip,
+// capi_ade_kbc_buoyant_part.hip: the KBC fluid), which share their launch path in ade_launch.hpp.  Every other unit keeps a call in an AdeCallBuf
 // (internal.hpp) and never sees its members.
 #pragma once
 #include <type_traits>

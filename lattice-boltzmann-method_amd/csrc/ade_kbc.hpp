@@ -156,8 +156,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // naive kernel.  Launched from a translation unit of its own (capi_ade_kbc_part.hip).
 // Each population is the value of the one load gather_walls / pull_pair take for it, and the arithmetic is fm.collide's,
 // ade_fixed_walls' and sm.collide's in k_ade_edge's FIXED order, expression for expression: the stored bits are those of
-// k_ade_kbc_stream_collide + k_ade_edge<KbcModel ...> on one block.  There is no BUOYANT form of the part kernel: the forced
-// collision runs on a single block.  Requirements as k_ade_stream_collide_part.
+// k_ade_kbc_stream_collide + k_ade_edge<KbcModel ...> on one block.  The BUOYANT form is a kernel of its own,
+// k_ade_kbc_stream_collide_part_buoyant below.  Requirements as k_ade_stream_collide_part.
 template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool FIXED, bool G_EARLY>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_ade_kbc_stream_collide_part(
     double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
@@ -202,6 +202,76 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     sm.collide(hb, ux_b, uy_b, c_b);
 #pragma unroll
     for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    if (WITH_MOMENTS) {
+      const long o = (long)r * g.C + c;  // moment fields are dense
+      const long n = (long)g.R * g.C;
+      store2<false>(rho_out + o, rho_a, rho_b);
+      store2<false>(u_out + o, ux_a, ux_b);
+      store2<false>(u_out + n + o, uy_a, uy_b);
+      store2<false>(c_out + o, c_a, c_b);
+    }
+  }
+}
+
+// k_ade_kbc_stream_collide_part, BUOYANT: the forced KBC collision on a PART of a slab.  The launch shape is the part
+// kernel's -- both row bands in one dispatch, a column pair per lane, rows through wrap_row, owned nodes written only, wall
+// fix-ups inline -- and the order is k_ade_kbc_stream_collide_buoyant's, the scalar collided and STORED before the fluid:
+//   f pair in, its wall fix-ups -> rho, u0 of both nodes (ade_fluid_moments)
+//   g pair in, its wall fix-ups (FIXED: gathered with ade_scalar_gather_bc) -> FIXED: the wall lanes anti-bounce back at
+//   the FIXED edges with the UNSHIFTED u0 (k_ade_edge's BUOYANT order) -> C, the shifted u (ade_buoyant_shift) -> the
+//   scalar's collisions with that u -> g pair out
+//   collide_with node a | collide_with node b, fenced one after the other with f alone in registers -> f pair out ->
+//   moments out (the shifted u)
+// f cannot be stored before the scalar's wall rule (its collision needs the C that rule leaves): on the wall lanes it stays
+// live across the rule, as in k_ade_stream_collide_part<..., BUOYANT>.
+// G_FENCED: a fence between the fluid's moments and the g pull -- the g loads wait for the moments instead of being issued
+// with those of f.  The candidate of the order; built with LBM_EXPERIMENTS alone.
+// Each population is the value of the one load gather_walls / pull_pair take for it, and the arithmetic is
+// ade_fluid_moments', ade_fixed_walls', ade_buoyant_shift's, sm.collide's and fm.collide_with's, expression for expression:
+// FRAME + INNER store the bits of k_ade_kbc_stream_collide_buoyant + k_ade_edge<KbcModel, ., ., ., BUOYANT> on one block.
+// Launched from a translation unit of its own (capi_ade_kbc_buoyant_part.hip).  Requirements as k_ade_stream_collide_part.
+template <class FM, class SM, bool NT_LOAD, bool NT_STORE, bool WITH_MOMENTS, bool FIXED, bool G_FENCED = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_ade_kbc_stream_collide_part_buoyant(
+    double* __restrict__ fn, double* __restrict__ gn, const double* __restrict__ fo, const double* __restrict__ go,
+    Geom g, Bc bc, FM fm, SM sm, int band0, int n0, int band1, int nrows, int tiles_per_row,
+    double* __restrict__ rho_out, double* __restrict__ u_out, double* __restrict__ c_out, AdeWalls sw, AdeBuoyancy by) {
+  const long items = (long)nrows * tiles_per_row;
+  for (long it = blockIdx.x; it < items; it += gridDim.x) {
+    const int v = (int)(it / tiles_per_row);
+    const int r = v < n0 ? band0 + v : band1 + (v - n0);
+    const int c = ((int)(it % tiles_per_row) * 256 + threadIdx.x) * 2;
+    if (c >= g.C) continue;
+    const long rm = g.at(wrap_row(g, r - 1), 0);  // source row of cx = +1 populations
+    const long r0 = g.at(r, 0);
+    const long rp = g.at(wrap_row(g, r + 1), 0);  // source row of cx = -1 populations
+    const bool row_lo = r == 0 && bc.row_lo == LBM_EDGE_BOUNCE_BACK, row_hi = r == g.R - 1 && bc.row_hi == LBM_EDGE_BOUNCE_BACK;
+    const bool wall = row_lo || row_hi || (c == 0 && bc_is_wall(bc.col_lo)) || (c + 2 == g.C && bc_is_wall(bc.col_hi));
+    double xa[Q], xb[Q], ha[Q], hb[Q];            // f and g of node (r, c) and node (r, c + 1)
+    double rho_a, ux_a, uy_a, c_a, rho_b, ux_b, uy_b, c_b;
+    pull_pair<NT_LOAD>(xa, xb, fo, g, rm, r0, rp, c);
+    if (wall) wall_fixups_pair<NT_LOAD>(xa, xb, fo, g, bc, row_lo, row_hi, r0, c);
+    ade_fluid_moments(xa, rho_a, ux_a, uy_a);
+    ade_fluid_moments(xb, rho_b, ux_b, uy_b);
+    if (G_FENCED) ade_kbc_phase();
+    pull_pair<NT_LOAD>(ha, hb, go, g, rm, r0, rp, c);
+    if (wall) wall_fixups_pair<NT_LOAD>(ha, hb, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, row_lo, row_hi, r0, c);
+    if (FIXED && wall) {  // with the unshifted u0
+      ade_fixed_walls(ha, g, bc, sw, r, c, ux_a, uy_a, sm.wr, sm.wc);
+      ade_fixed_walls(hb, g, bc, sw, r, c + 1, ux_b, uy_b, sm.wr, sm.wc);
+    }
+    ade_buoyant_shift(ha, by, ux_a, uy_a, c_a);
+    ade_buoyant_shift(hb, by, ux_b, uy_b, c_b);
+    sm.collide(ha, ux_a, uy_a, c_a);
+    sm.collide(hb, ux_b, uy_b, c_b);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(gn + q * g.plane + r0 + c, ha[q], hb[q]);
+    ade_kbc_phase();
+    fm.collide_with(xa, rho_a, ux_a, uy_a);
+    ade_kbc_phase();  // one collision at a time
+    fm.collide_with(xb, rho_b, ux_b, uy_b);
+    ade_kbc_phase();
+#pragma unroll
+    for (int q = 0; q < Q; ++q) store2<NT_STORE>(fn + q * g.plane + r0 + c, xa[q], xb[q]);
     if (WITH_MOMENTS) {
       const long o = (long)r * g.C + c;  // moment fields are dense
       const long n = (long)g.R * g.C;

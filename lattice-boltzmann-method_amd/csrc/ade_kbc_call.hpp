@@ -1,6 +1,7 @@
-// What the three translation units of the fluid + scalar step with a KBC fluid share on the host (capi_ade_kbc.hip: every
+// What the four translation units of the fluid + scalar step with a KBC fluid share on the host (capi_ade_kbc.hip: every
 // launch without buoyancy but one; capi_ade_kbc_part.hip: the part kernel of a slab; capi_ade_kbc_buoyant.hip: the forced
-// collision): the kernels of ade_kbc.hpp, the launch path and the choice of the model pair.
+// collision; capi_ade_kbc_buoyant_part.hip: its part kernel): the kernels of ade_kbc.hpp, the launch path and the choice of
+// the model pair.
 #pragma once
 #include "ade_kbc.hpp"
 #include "ade_launch.hpp"

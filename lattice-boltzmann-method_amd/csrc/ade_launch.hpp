@@ -1,6 +1,6 @@
 // The launch path of the fused fluid + scalar step, once, for the four translation units that launch k_ade_* kernels
-// (capi_ade.hip: the BGK fluid; capi_ade_kbc.hip, capi_ade_kbc_part.hip, capi_ade_kbc_buoyant.hip: the KBC fluid -- four
-// units because the device code of each is pinned).  Everything here is a template on the models and
+// (capi_ade.hip: the BGK fluid; capi_ade_kbc.hip, capi_ade_kbc_part.hip, capi_ade_kbc_buoyant.hip,
+// capi_ade_kbc_buoyant_part.hip: the KBC fluid -- units of their own because the device code of each is pinned).  Everything here is a template on the models and
 // BUOYANT, so a unit instantiates exactly the kernels it asks for: the sequences take the unit's interior launch and its
 // table passes as callables and name no interior kernel, no open-table kernel and no model themselves.  Nothing here
 // allocates or synchronises: the slab calls are captured into graphs.
@@ -114,8 +114,9 @@ int ade_part_sequence(const AdeCall& k, int part, int edge_rows, Interior interi
 
 // What capi_ade.hip's dispatch on the fluid of a resolved call (ade_step_from, ade_part_from, ade_collide_from) hands a KBC
 // fluid to -- capi_ade_kbc.hip: the step, the collide-only pass and, for the part unit, the interior-wall pass of a part's
-// rows; capi_ade_kbc_part.hip: one part; capi_ade_kbc_buoyant.hip: the step and the collide-only pass of a call with
-// call.buoyant (the forced collision, the reference order in both halves)
+// rows; capi_ade_kbc_part.hip: one part; capi_ade_kbc_buoyant.hip: the step, the collide-only pass and the interior-wall pass
+// of a part's rows of a call with call.buoyant (the forced collision, the reference order in both halves);
+// capi_ade_kbc_buoyant_part.hip: one part of such a call
 int ade_kbc_step(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old, int row_begin,
                  int row_end, double* rho, double* u, double* conc, hipStream_t st, long long* launches);
 int ade_kbc_collide_from(const AdeCall& call, double* fp, double* gp, const double* f, const double* h, double* rho, double* u,
@@ -128,5 +129,9 @@ int ade_kbc_buoyant_step(const AdeCall& call, double* f_new, double* g_new, cons
                          int row_begin, int row_end, double* rho, double* u, double* conc, hipStream_t st, long long* launches);
 int ade_kbc_buoyant_collide_from(const AdeCall& call, double* fp, double* gp, const double* f, const double* h, double* rho,
                                  double* u, double* conc, hipStream_t st);
+int ade_kbc_buoyant_iwalls_pass(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old,
+                                const AdeRows& rows, double* rho, double* u, double* conc, hipStream_t st, long long* launches);
+int ade_kbc_buoyant_part_from(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old,
+                              int part, int edge_rows, double* rho, double* u, double* conc, hipStream_t st);
 
 }  // namespace lbm

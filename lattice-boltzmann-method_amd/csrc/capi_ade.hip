@@ -434,9 +434,6 @@ int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const Ade
   if (!rc) rc = ade_iwalls_check(fn, iwalls, lg, &call->wall_nodes, &call->n_wall_nodes, &call->wall_first);
   if (rc) return rc;
   if (kbc) {
-    // (no public call reaches this line: the ring's `_m` entries and the `_m` part entry have no parameter for buoyancy)
-    LBM_REQUIRE(!(slab && call->buoyant), "%s: buoyancy on a slab is not supported with a KBC fluid (the forced KBC collision "
-                "runs on a single block)", fn);
     LBM_REQUIRE(kbc->form == LBM_FORM_DEFAULT || kbc->form == scalar->form,
                 "%s: KBC fluid form=%d differs from the scalar form=%d (lbm_ade_params.form sets both halves)", fn, kbc->form,
                 scalar->form);
@@ -498,7 +495,7 @@ static std::atomic<long long> g_part_launches{0};
 void ade_part_launches_add(long long n) { g_part_launches.fetch_add(n, std::memory_order_relaxed); }
 
 // The launches of a resolved call, by its fluid: BGK here, KBC in capi_ade_kbc.hip (a part: capi_ade_kbc_part.hip), KBC with
-// call.buoyant in capi_ade_kbc_buoyant.hip.
+// call.buoyant in capi_ade_kbc_buoyant.hip (a part: capi_ade_kbc_buoyant_part.hip).
 // collide only: no streaming, so no wall rule -- the scalar's walls and the interior walls of the call are checked and
 // nothing more
 int ade_collide_from(const char* fn, const AdeCall& k, double* fp, double* gp, const double* f, const double* h,
@@ -536,6 +533,7 @@ static int ade_step_from(const AdeCall& k, double* fn, double* gn, const double*
 // one part of a call, after ade_part_args
 int ade_part_from(const AdeCall& k, double* fn, double* gn, const double* fo, const double* go, int part, int edge_rows,
                   double* rho, double* u, double* conc, hipStream_t st) {
+  if (k.kbc && k.buoyant) return ade_kbc_buoyant_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
   if (k.kbc) return ade_kbc_part_from(k, fn, gn, fo, go, part, edge_rows, rho, u, conc, st);
   return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto B) {
     using FM = std::decay_t<decltype(fm)>;
@@ -1622,6 +1620,17 @@ int lbm_ade_stream_collide_part_m(double* fn, double* gn, const double* fo, cons
   if (int rc = ade_fluid_model("lbm_ade_stream_collide_part_m", fluid, &fl)) return rc;
   return ade_part(fl.kbc ? "lbm_ade_stream_collide_part_m" : "lbm_ade_stream_collide_part_w", fn, gn, fo, go, g, bc, fl, scalar,
                   sbc, nullptr, iwalls, part, edge_rows, rho, u, conc, as_stream(s));
+}
+
+// lbm_ade_stream_collide_part_m with the descriptor of lbm_ade_buoyancy after sbc (the name: lbm_hip.h)
+int lbm_ade_slab_stream_collide_mb(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                   const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                                   const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                                   int part, int edge_rows, double* rho, double* u, double* conc, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_slab_stream_collide_mb", fluid, &fl)) return rc;
+  return ade_part(fl.kbc ? "lbm_ade_slab_stream_collide_mb" : "lbm_ade_stream_collide_part_w", fn, gn, fo, go, g, bc, fl, scalar,
+                  sbc, buoy, iwalls, part, edge_rows, rho, u, conc, as_stream(s));
 }
 
 long long lbm_ade_part_launches(void) { return g_part_launches.load(std::memory_order_relaxed); }

@@ -1,7 +1,8 @@
-// The fluid + scalar step with a KBC fluid and BUOYANCY (lbm_ade_buoyancy with beta != (0, 0)) on a single block: the
-// launch sites of every kernel with the forced KBC collision -- the buoyant interior pair kernel of ade_kbc.hpp and the
-// BUOYANT instantiations of ade.hpp's collide-only, edge and interior-wall kernels with KbcModel as the fluid
-// (ade_forced_fluid: collide_with on the shifted u).  A translation unit of its own, so that the device code of
+// The fluid + scalar step with a KBC fluid and BUOYANCY (lbm_ade_buoyancy with beta != (0, 0)): the launch sites of every
+// kernel with the forced KBC collision but the part kernel of a slab (capi_ade_kbc_buoyant_part.hip) -- the buoyant interior
+// pair kernel of ade_kbc.hpp and the BUOYANT instantiations of ade.hpp's collide-only, edge and interior-wall kernels with
+// KbcModel as the fluid (ade_forced_fluid: collide_with on the shifted u); the interior-wall pass serves a single block's
+// rows and a part's (ade_kbc_buoyant_iwalls_pass).  A translation unit of its own, so that the device code of
 // capi_ade_kbc.hip and capi_ade_kbc_part.hip stays what it was.  A buoyant step runs the reference order in both halves
 // whatever `form` says: KbcModel + AdeModelRef.  Called from capi_ade.hip (ade_step_from, ade_collide_from) with a call
 // ade_resolve resolved; the sequences are ade_launch.hpp's.
@@ -9,7 +10,15 @@
 
 namespace lbm {
 
-// the collide-only launch (the first driver iteration)
+// the interior-wall pass of a part's rows: the buoyant part unit must not instantiate k_ade_iwalls_ranges
+int ade_kbc_buoyant_iwalls_pass(const AdeCall& k, double* fn, double* gn, const double* fo, const double* go,
+                                const AdeRows& rows, double* rho, double* u, double* conc, hipStream_t st, long long* launches) {
+  const KbcModel fm{k.kbc->s2};
+  const AdeModelRef sm{k.scalar->omega_g, k.scalar->w_r, k.scalar->w_c};
+  return ade_iwalls_pass<true>(k, fm, sm, fn, gn, fo, go, rows, rho, u, conc, st, launches);
+}
+
+// the collide-only launch (the first driver iteration; a single block or a slab: the owned rows)
 int ade_kbc_buoyant_collide_from(const AdeCall& k, double* fp, double* gp, const double* f, const double* h, double* rho,
                                  double* u, double* conc, hipStream_t st) {
   const KbcModel fm{k.kbc->s2};

@@ -312,7 +312,7 @@ static int ring_bgk_step(lbm_ring* rg, double* dst, const double* src, const lbm
 // The call of a ring entry, resolved once, before any device call: the slab's edges (ring_slab_bc, periodic by default) and
 // the scalar's walls -- gsbc, of the global domain, checked against the global edges; a FIXED row acts where the slab keeps
 // that edge (a chain end) and is dropped at a seam, as the fluid's row wall is.
-// fluid: either fluid (the `_m` entries have no parameter for buoy or view, which ade_resolve refuses with a KBC fluid)
+// fluid: either fluid (the `_m` and `_mb` entries have no parameter for a view, which ade_resolve refuses with a KBC fluid)
 static int ring_ade_resolve(const char* fn, lbm_ring* rg, const lbm_bc* bc, const AdeFluid& fluid,
                             const lbm_ade_params* scalar, const lbm_ade_scalar_bc* gsbc, const lbm_ade_buoyancy* buoy,
                             const lbm_ade_iwalls* iwalls, AdeCall* call, const lbm_ade_open* view = nullptr) {
@@ -706,6 +706,27 @@ int lbm_ring_ade_step_m(lbm_ring* rg, double* fn_, double* gn, const double* fo,
   AdeFluid fl;
   if (int rc = ade_fluid_model("lbm_ring_ade_step_m", fluid, &fl)) return rc;
   return ring_ade_step(fl.kbc ? "lbm_ring_ade_step_m" : "lbm_ring_ade_step_w", rg, fn_, gn, fo, go, bc, fl, scalar, sbc, nullptr,
+                       iwalls, edge_rows, main_s);
+}
+
+// the `_m` entries with the descriptor of lbm_ade_buoyancy after sbc (the names: lbm_hip.h): the same schedule -- the force
+// is local to a node, so nothing more is synchronised; a KBC fluid with beta != (0, 0) launches the forced collision
+// (ade_collide_from, ade_part_from)
+int lbm_ring_ade_slab_collide_mb(lbm_ring* rg, double* fp, double* gp, const double* f, const double* g_in, const lbm_bc* bc,
+                                 const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                                 const lbm_ade_buoyancy* buoy, lbm_stream_t main_s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ring_ade_slab_collide_mb", fluid, &fl)) return rc;
+  return ring_ade_collide(fl.kbc ? "lbm_ring_ade_slab_collide_mb" : "lbm_ring_ade_collide_b", rg, fp, gp, f, g_in, bc, fl, scalar,
+                          sbc, buoy, main_s);
+}
+
+int lbm_ring_ade_slab_step_mb(lbm_ring* rg, double* fn_, double* gn, const double* fo, const double* go, const lbm_bc* bc,
+                              const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                              const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls, int edge_rows, lbm_stream_t main_s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ring_ade_slab_step_mb", fluid, &fl)) return rc;
+  return ring_ade_step(fl.kbc ? "lbm_ring_ade_slab_step_mb" : "lbm_ring_ade_step_w", rg, fn_, gn, fo, go, bc, fl, scalar, sbc, buoy,
                        iwalls, edge_rows, main_s);
 }
 

@@ -1,6 +1,7 @@
 // The CPU-reachable half of the fluid + scalar step with a KBC fluid as a stand-alone program: every host-side check of
 // lbm_ade_collide_m, lbm_ade_stream_collide_m and lbm_ade_solver_create_m, and of their buoyant forms lbm_ade_collide_mb,
-// lbm_ade_stream_collide_mb and lbm_ade_solver_set_buoyancy_m -- the fluid by model, the KBC parameters, what
+// lbm_ade_stream_collide_mb and lbm_ade_solver_set_buoyancy_m, and of the buoyant slab and ring entries
+// lbm_ade_slab_stream_collide_mb, lbm_ring_ade_slab_collide_mb and lbm_ring_ade_slab_step_mb -- the fluid by model, the KBC parameters, what
 // the step refuses with this fluid, the checks it shares with the BGK fluid, and model = BGK answering with the message of
 // the call it names -- and, for both fluids, WHICH fault a call with two faults reports (the order of the host checks is
 // observable and differs per fluid; the last section).  Needs no device: every call is refused before a device call (the interior-wall table it
@@ -400,6 +401,145 @@ int main() {
     c = good_kbc;  // part=5 + bad edge_rows
     c.part = 5, c.edge_rows = 0;
     refused(part_m(c), "lbm_ade_stream_collide_part_m: part=5", "2 faults: part=5 + edge_rows=0, part_m");
+
+    // ---- buoyancy over row slabs and the ring: lbm_ade_slab_stream_collide_mb, lbm_ring_ade_slab_collide_mb,
+    // lbm_ring_ade_slab_step_mb.  The ring's entries are given a NULL ring: what they refuse before they look at it
+    auto slab_mb = [&](const Call& c) {
+      return lbm_ade_slab_stream_collide_mb(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, c.buoy,
+                                            c.walls, c.part, c.edge_rows, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto ring_collide_mb = [&](const Call& c, const lbm_ade_fluid* fl) {
+      return lbm_ring_ade_slab_collide_mb(nullptr, lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), c.bc, fl, &c.sc, c.sbc, c.buoy, nullptr);
+    };
+    auto ring_step_mb = [&](const Call& c, const lbm_ade_fluid* fl) {
+      return lbm_ring_ade_slab_step_mb(nullptr, lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), c.bc, fl, &c.sc, c.sbc, c.buoy, c.walls,
+                                       c.edge_rows, nullptr);
+    };
+    lbm_ade_buoyancy good_buoy{1e-2, -5e-3, 0.4, 1.0, 1.0 / 3.0, 1.0 / 9.0};
+    lbm_ade_buoyancy nan_beta = good_buoy;
+    nan_beta.beta_r = std::nan("");
+    const lbm_geom slab{8, 8, 1, 0, 0};
+    const lbm_bc seams{LBM_EDGE_HALO, LBM_EDGE_HALO, 0, 0, 0, 1.0, 1.0, 0.0, 0.0};
+    Call good_slab = good_kbc;
+    good_slab.g = slab, good_slab.bc = &seams, good_slab.buoy = &good_buoy;
+    refused(lbm_ade_slab_stream_collide_mb(l0, l1, l2, l3, &slab, &seams, nullptr, &sc, nullptr, &good_buoy, nullptr, LBM_ADE_PART_FRAME, 1,
+                                           nullptr, nullptr, nullptr, nullptr), "lbm_ade_slab_stream_collide_mb: NULL fluid", "slab_mb: NULL fluid");
+    c = good_slab;
+    c.fl.model = 7;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: fluid model=7", "slab_mb: unknown model");
+    for (int field = 0; field < 6; ++field) {  // every field of the descriptor, non-finite
+      lbm_ade_buoyancy b = good_buoy;
+      if (field == 0) b.beta_r = HUGE_VAL;
+      if (field == 1) b.beta_c = std::nan("");
+      if (field == 2) b.c_ref = -HUGE_VAL;
+      if (field == 3) b.u_shift = std::nan("");
+      if (field == 4) b.guo_a = HUGE_VAL;
+      if (field == 5) b.guo_b = std::nan("");
+      static const char* const kWord[6] = {"buoyancy beta=", "buoyancy beta=", "buoyancy c_ref=", "buoyancy u_shift=", "buoyancy guo=",
+                                           "buoyancy guo="};
+      c = good_slab;
+      c.buoy = &b;
+      refused(slab_mb(c), kWord[field], "slab_mb: a non-finite field of the descriptor");
+      refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: buoyancy", "slab_mb: a non-finite field under the new name");
+      refused(ring_collide_mb(c, &c.fl), "lbm_ring_ade_slab_collide_mb: buoyancy", "ring_collide_mb: a non-finite field");
+      refused(ring_step_mb(c, &c.fl), "lbm_ring_ade_slab_step_mb: buoyancy", "ring_step_mb: a non-finite field");
+    }
+    c = good_slab;  // beta = (0, 0) is the passive step, but the descriptor is still checked
+    lbm_ade_buoyancy zero_inf{0.0, 0.0, HUGE_VAL, 1.0, 0.0, 0.0};
+    c.buoy = &zero_inf;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: buoyancy c_ref=inf", "slab_mb: zero beta, c_ref = inf");
+    c = good_slab;
+    c.fl.kbc.s2 = 2.5;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: KBC fluid: s2=2.5 outside (0, 2]", "slab_mb: s2 = 2.5");
+    c.fl.kbc.s2 = 0.0;
+    refused(slab_mb(c), "s2=0 outside (0, 2]", "slab_mb: s2 = 0");
+    c = good_slab;
+    c.bc = &pressure;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: pressure rows", "slab_mb: pressure rows");
+    c = good_slab;
+    c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: KBC fluid form=1 differs from the scalar form=2", "slab_mb: forms differ");
+    c = good_slab;
+    c.part = 5;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: part=5", "slab_mb: part = 5");
+    c = good_slab;
+    c.edge_rows = 0;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: edge_rows=0", "slab_mb: edge_rows = 0");
+    c.edge_rows = 4;
+    refused(slab_mb(c), "edge_rows=4: need 1 <= edge_rows and 2 x edge_rows < R=8", "slab_mb: edge_rows = R / 2");
+    c = good_slab;
+    c.lattices = false;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: NULL lattice", "slab_mb: NULL lattices, buoyant");
+    c.buoy = nullptr;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: NULL lattice", "slab_mb: NULL lattices, NULL descriptor");
+    c = good_slab;
+    c.g.ghost = 0;  // HALO rows without ghost rows
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: row edge mode HALO needs ghost rows", "slab_mb: HALO without ghost rows");
+    c = good_slab;
+    c.walls = open_table;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: interior walls: the table is not finalized", "slab_mb: unfinalized table");
+    // the ring's entries before the ring: the fluid, then the descriptor, then their arguments
+    c = good_slab;
+    refused(ring_collide_mb(c, nullptr), "lbm_ring_ade_slab_collide_mb: NULL fluid", "ring_collide_mb: NULL fluid");
+    refused(ring_step_mb(c, nullptr), "lbm_ring_ade_slab_step_mb: NULL fluid", "ring_step_mb: NULL fluid");
+    refused(ring_collide_mb(c, &c.fl), "lbm_ring_ade_slab_collide_mb: NULL argument", "ring_collide_mb: NULL ring");
+    refused(ring_step_mb(c, &c.fl), "lbm_ring_ade_slab_step_mb: NULL argument", "ring_step_mb: NULL ring");
+    c.fl.model = 7;
+    refused(ring_collide_mb(c, &c.fl), "lbm_ring_ade_slab_collide_mb: fluid model=7", "ring_collide_mb: unknown model");
+    refused(ring_step_mb(c, &c.fl), "lbm_ring_ade_slab_step_mb: fluid model=7", "ring_step_mb: unknown model");
+    // model = BGK: the entries they forward to answer, with the same descriptor
+    c = good_slab;
+    c.fl = good_bgk.fl;
+    c.part = 5;
+    refused(slab_mb(c), "lbm_ade_stream_collide_part_w: part=5", "slab_mb (BGK): part = 5");
+    c.buoy = &nan_beta;
+    refused(slab_mb(c), "lbm_ade_stream_collide_part_w: buoyancy beta=", "slab_mb (BGK): non-finite beta");
+    refused(ring_collide_mb(c, &c.fl), "lbm_ring_ade_collide_b: buoyancy beta=", "ring_collide_mb (BGK): non-finite beta");
+    refused(ring_step_mb(c, &c.fl), "lbm_ring_ade_step_w: buoyancy beta=", "ring_step_mb (BGK): non-finite beta");
+    c.buoy = &good_buoy;
+    refused(ring_collide_mb(c, &c.fl), "lbm_ring_ade_collide_b: NULL argument", "ring_collide_mb (BGK): NULL ring");
+    refused(ring_step_mb(c, &c.fl), "lbm_ring_ade_step_w: NULL argument", "ring_step_mb (BGK): NULL ring");
+    c.fl.bgk.omega = 2.0;
+    refused(slab_mb(c), "lbm_ade_stream_collide_part_w: omega=2 outside (0, 2)", "slab_mb (BGK): omega = 2");
+    // two faults: which one is reported
+    c = good_slab;  // s2 outside range + non-finite buoyancy
+    c.fl.kbc.s2 = 2.5, c.buoy = &bad_buoy;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: KBC fluid: s2=2.5", "2 faults: s2 + buoyancy, slab_mb");
+    c = good_slab;  // pressure rows + non-finite buoyancy
+    c.bc = &pressure, c.buoy = &bad_buoy;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: pressure rows (pressure_rows=1)", "2 faults: pressure rows + buoyancy, slab_mb");
+    c = good_slab;  // odd C + non-finite buoyancy
+    c.g.C = 7, c.buoy = &bad_buoy;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: C=7 must be even", "2 faults: odd C + buoyancy, slab_mb");
+    c = good_slab;  // omega_g outside range + non-finite buoyancy
+    c.sc.omega_g = 2.5, c.buoy = &bad_buoy;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + buoyancy, slab_mb");
+    c = good_slab;  // non-finite buoyancy + unfinalized table
+    c.buoy = &bad_buoy, c.walls = open_table;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: buoyancy c_ref=inf", "2 faults: buoyancy + unfinalized table, slab_mb");
+    c = good_slab;  // non-finite buoyancy + KBC / scalar form mismatch
+    c.buoy = &bad_buoy, c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: buoyancy c_ref=inf", "2 faults: buoyancy + KBC form mismatch, slab_mb");
+    c = good_slab;  // unfinalized table + KBC / scalar form mismatch
+    c.walls = open_table, c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: interior walls: the table is not finalized", "2 faults: unfinalized table + KBC form mismatch, slab_mb");
+    c = good_slab;  // KBC / scalar form mismatch + NULL lattice
+    c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED, c.lattices = false;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + NULL lattice, slab_mb");
+    c = good_slab;  // NULL lattice + part=5
+    c.lattices = false, c.part = 5;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: NULL lattice", "2 faults: NULL lattice + part=5, slab_mb");
+    c = good_slab;  // part=5 + bad edge_rows
+    c.part = 5, c.edge_rows = 0;
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: part=5", "2 faults: part=5 + edge_rows=0, slab_mb");
+    c = good_slab;  // the ring's entries: non-finite buoyancy + NULL ring
+    c.buoy = &bad_buoy;
+    refused(ring_collide_mb(c, &c.fl), "lbm_ring_ade_slab_collide_mb: buoyancy c_ref=inf", "2 faults: buoyancy + NULL ring, ring_collide_mb");
+    refused(ring_step_mb(c, &c.fl), "lbm_ring_ade_slab_step_mb: buoyancy c_ref=inf", "2 faults: buoyancy + NULL ring, ring_step_mb");
+    c.fl.model = 7;  // unknown model + non-finite buoyancy
+    refused(ring_collide_mb(c, &c.fl), "lbm_ring_ade_slab_collide_mb: fluid model=7", "2 faults: model + buoyancy, ring_collide_mb");
+    refused(ring_step_mb(c, &c.fl), "lbm_ring_ade_slab_step_mb: fluid model=7", "2 faults: model + buoyancy, ring_step_mb");
+    refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: fluid model=7", "2 faults: model + buoyancy, slab_mb");
     lbm_ade_iwalls_destroy(open_table);
   }
   std::printf("ade_kbc_host_check: %d refusals checked, %d failures\n", checks, failures);

@@ -335,7 +335,12 @@ def load_library(path=LIB_PATH):
     lib.lbm_ade_stream_collide_part_m.argtypes = [p, p, p, p, p, p, p, p, p, p, i, i, p, p, p, p]
     lib.lbm_ring_ade_collide_m.argtypes = [p, p, p, p, p, p, p, p, p, p]
     lib.lbm_ring_ade_step_m.argtypes = [p, p, p, p, p, p, p, p, p, p, i, p]
-    for fn in (lib.lbm_ade_stream_collide_part_m, lib.lbm_ring_ade_collide_m, lib.lbm_ring_ade_step_m):
+    # and their buoyant forms: the descriptor of lbm_ade_buoyancy after sbc
+    lib.lbm_ade_slab_stream_collide_mb.argtypes = [p, p, p, p, p, p, p, p, p, p, p, i, i, p, p, p, p]
+    lib.lbm_ring_ade_slab_collide_mb.argtypes = [p, p, p, p, p, p, p, p, p, p, p]
+    lib.lbm_ring_ade_slab_step_mb.argtypes = [p, p, p, p, p, p, p, p, p, p, p, i, p]
+    for fn in (lib.lbm_ade_stream_collide_part_m, lib.lbm_ring_ade_collide_m, lib.lbm_ring_ade_step_m,
+               lib.lbm_ade_slab_stream_collide_mb, lib.lbm_ring_ade_slab_collide_mb, lib.lbm_ring_ade_slab_step_mb):
         fn.restype = ct.c_int
     return lib
 
