@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 import pylbm  # noqa: E402
 from gpu_util import bits_equal, dev, download_aos, ulp_diff, upload_soa  # noqa: E402
+from ibm_util import circle, cylinder_solver, expected_blocks, roi_of  # noqa: E402
 from pylbm import _ptr  # noqa: E402
 
 
@@ -22,12 +23,6 @@ def lib():
     lib = pylbm.Lib()
     assert lib.device_count() >= 1
     return lib
-
-
-def circle(cx, cy, radius, spacing=1.0):
-    n = int(round(2 * np.pi * radius / spacing))
-    t = 2 * np.pi * np.arange(n) / n
-    return cx + radius * np.cos(t), cy + radius * np.sin(t)
 
 
 def test_eulerian_force_density_vs_oracle(lib, oracle):
@@ -50,19 +45,6 @@ def test_eulerian_force_density_vs_oracle(lib, oracle):
     fs = ib.surface_force()
     assert np.allclose(fs, want.reshape(-1, 2).sum(0), rtol=1e-12, atol=1e-15)
     ib.close()
-
-
-def cylinder_solver(lib, X, Y, omega, u_in, x, y, form=pylbm.FORM_REFERENCE_ORDER):
-    """the cylinder preset; the parity tests hold it to the oracle BITWISE, i.e. in the reference's operation order
-    (the library's default is the reassociated collision: test_cylinder_with_the_default_collision)"""
-    bc = pylbm.Bc.periodic()
-    bc.row_lo = bc.row_hi = pylbm.EDGE_ABB_VELOCITY      # cylinder_test.cpp:135-154
-    bc.col_lo = bc.col_hi = pylbm.EDGE_SPECULAR          # :157-163
-    bc.uw_r, bc.uw_c = u_in, 0.0
-    sv = pylbm.Solver(lib, pylbm.MODEL_BGK, X, Y, pylbm.BgkParams(omega, 0, 1, form=form), bc=bc)
-    ib = pylbm.Ibm(lib, x, y, X, Y)
-    sv.attach_ibm(ib)
-    return sv, ib
 
 
 @pytest.mark.parametrize("X,Y,radius", [(120, 90, 10.0), (96, 51, 6.5)])
@@ -218,12 +200,9 @@ def test_moving_boundary_extension(lib, oracle):
     assert Fs_counter[0] < 1.5 * Fs_ref[0]                 # counter-moving: larger resistance (more negative)
 
 
-@pytest.mark.parametrize("cx_frac", [0.5, 0.12])
-def test_forced_band_blocks_equal_single_steps(lib, oracle, cx_frac):
-    """lbm_solver_step with an immersed boundary advances D steps per block (forced band around the ROI
-    on a shrinking trapezoid + D-step window for the rows farther away; tuning ibm_depth = 5 default, 3)
-    or one step per launch (ibm_depth = 1): same bits after 13 steps (two blocks + singles), and equal
-    to the oracle.  cx_frac = 0.12 puts the ROI too close to the inlet for a block: silent fallback."""
+def _band_runs(lib, oracle, cx_frac, form):
+    """13 steps of the 160 x 128 cylinder under "ibm_depth" = 1, 5 and 3 in the given form:
+    {depth: (f, surface force, blocks launched)} and the inputs (x, y, f0, omega, u_in)"""
     X, Y, omega, u_in, radius = 160, 128, 1.0 / 0.55, 0.05, 8.0
     x, y = circle(X * cx_frac + 0.3, Y / 2.0 - 0.4, radius)
     u0 = np.zeros((X, Y, 2)); u0[..., 0] = u_in
@@ -232,20 +211,31 @@ def test_forced_band_blocks_equal_single_steps(lib, oracle, cx_frac):
     try:
         for depth in (1, 5, 3):
             lib.set_tuning(b"ibm_depth", depth)
-            sv, ib = cylinder_solver(lib, X, Y, omega, u_in, x, y)
+            sv, ib = cylinder_solver(lib, X, Y, omega, u_in, x, y, form=form)
             sv.set_f(f0)
             sv.step(13, record_moments=False)
-            res[depth] = (sv.get_f(), ib.surface_force())
+            res[depth] = (sv.get_f(), ib.surface_force(), int(lib.raw.lbm_solver_block_launches(sv.h)))
             sv.close(); ib.close()
     finally:
         lib.set_tuning(b"ibm_depth", -1)
+    return res, (x, y, f0, omega, u_in)
+
+
+@pytest.mark.parametrize("cx_frac", [0.5, 0.12])
+def test_forced_band_blocks_equal_single_steps(lib, oracle, cx_frac):
+    """lbm_solver_step with an immersed boundary advances D steps per block (forced band around the ROI
+    on a shrinking trapezoid + D-step window for the rows farther away; tuning ibm_depth = 5 default, 3)
+    or one step per launch (ibm_depth = 1): same bits after 13 steps (two blocks + singles), and equal
+    to the oracle.  cx_frac = 0.12 puts the ROI too close to the inlet for a block: silent fallback."""
+    res, (x, y, f0, omega, u_in) = _band_runs(lib, oracle, cx_frac, pylbm.FORM_REFERENCE_ORDER)
     fo, uo, rhoo, Fso = oracle.cylinder_steps(x, y, f0, omega, u_in, 13)
-    for depth, (f, Fs) in res.items():
+    for depth, (f, Fs, blocks) in res.items():
+        assert blocks == expected_blocks(160, 128, roi_of(x, y), 13, max_depth=depth), (depth, blocks)
         assert bits_equal(f, fo), (depth, ulp_diff(f, fo))
         assert np.allclose(Fs, Fso, rtol=1e-11, atol=1e-16)
 
 
-@pytest.mark.parametrize("tune,cy_frac", [
+BOX_VARIANTS = [
     ({"ibm_box": 0}, 0.55),                          # full-width band (round 2, first half)
     ({"ibm_box": 1, "ibm_box_overlap": 0}, 0.55),    # forced box, window launch behind the chain on one stream
     ({"ibm_box": 1, "ibm_step_chain": 1}, 0.55),     # box; forcing as the 10-launch chain
@@ -256,22 +246,22 @@ def test_forced_band_blocks_equal_single_steps(lib, oracle, cx_frac):
     ({"ibm_box": 1, "ibm_chain_kernel": 1, "ibm_chain_wgs": 40, "ibm_box_overlap": 0}, 0.55),
     ({"ibm_box": 1}, 0.12),                          # box would touch the wall columns: the band takes over
     ({"ibm_box": 1}, 0.87),
-])
-def test_forced_box_variants_equal_the_oracle(lib, oracle, tune, cy_frac):
-    """The forced BOX of an immersed-boundary block (rows and columns ROI +- 2 D on a small lattice of its own,
-    D-step window over all rows beside it) and every switch around it: same bits as the oracle after 16 steps
-    (1 + three 5-step blocks), same surface force; the blocks really ran (lbm_solver_block_launches)."""
+]
+
+
+def _box_variant_run(lib, oracle, tune, cy_frac, form):
+    """16 steps of the 176 x 200 cylinder under the tuning `tune` in the given form: (f, surface force, blocks launched)
+    and the inputs (x, y, f0, omega, u_in)"""
     if tune.get("ibm_chain_kernel") and not lib.raw.lbm_build_has_experiments():
         pytest.skip("the one-launch forcing chain is an experiment: make -C lattice-boltzmann-method_amd/csrc EXPERIMENTS=1")
     X, Y, omega, u_in, radius = 176, 200, 1.0 / 0.55, 0.05, 9.0
     x, y = circle(X * 0.45 + 0.3, Y * cy_frac - 0.4, radius)
     u0 = np.zeros((X, Y, 2)); u0[..., 0] = u_in
     f0 = oracle.incomp_equilibrium(u0, np.ones((X, Y)))
-    fo, uo, rhoo, Fso = oracle.cylinder_steps(x, y, f0, omega, u_in, 16)
     try:
         for k, v in tune.items():
             lib.set_tuning(k.encode(), v)
-        sv, ib = cylinder_solver(lib, X, Y, omega, u_in, x, y)
+        sv, ib = cylinder_solver(lib, X, Y, omega, u_in, x, y, form=form)
         sv.set_f(f0)
         sv.step(16, record_moments=False)
         f, Fs = sv.get_f(), ib.surface_force()
@@ -280,6 +270,16 @@ def test_forced_box_variants_equal_the_oracle(lib, oracle, tune, cy_frac):
     finally:
         for k in tune:
             lib.set_tuning(k.encode(), -1)
+    return (f, Fs, blocks), (x, y, f0, omega, u_in)
+
+
+@pytest.mark.parametrize("tune,cy_frac", BOX_VARIANTS)
+def test_forced_box_variants_equal_the_oracle(lib, oracle, tune, cy_frac):
+    """The forced BOX of an immersed-boundary block (rows and columns ROI +- 2 D on a small lattice of its own,
+    D-step window over all rows beside it) and every switch around it: same bits as the oracle after 16 steps
+    (1 + three 5-step blocks), same surface force; the blocks really ran (lbm_solver_block_launches)."""
+    (f, Fs, blocks), (x, y, f0, omega, u_in) = _box_variant_run(lib, oracle, tune, cy_frac, pylbm.FORM_REFERENCE_ORDER)
+    fo, uo, rhoo, Fso = oracle.cylinder_steps(x, y, f0, omega, u_in, 16)
     assert blocks == 3, blocks
     assert bits_equal(f, fo), ulp_diff(f, fo)
     assert np.allclose(Fs, Fso, rtol=1e-11, atol=1e-16)
@@ -309,11 +309,13 @@ def test_cylinder_with_the_default_collision(lib, oracle):
 
 
 # ---- config 5 over slabs in blocks of D steps, the boundary anywhere -- also across a seam -------------
-def _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, n_blocks, start_from_pre=False, block_tuning=None):
+def _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, n_blocks, start_from_pre=False, block_tuning=None,
+                    form=pylbm.FORM_REFERENCE_ORDER, yardstick_depth=None):
     """the run through lbm_slab_ibm_* on n_slabs emulated slabs (one GPU, messages moved by device copies)
     and the same run on ONE block through the solver context; returns (P_slabs, P_block, Fs_slabs, Fs_block,
     slab objects' roles).  block_tuning: one {tuning key: value} per block, set for that block of the slab run
-    alone (every key is back at -1, its default, afterwards)"""
+    alone (every key is back at -1, its default, afterwards).  form: the collision of both runs; yardstick_depth: the
+    "ibm_depth" of the one-block run alone (1: single steps)"""
     block_tuning = block_tuning or [{}] * n_blocks
     assert len(block_tuning) == n_blocks
     R = X // n_slabs
@@ -321,7 +323,7 @@ def _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, n_blocks, start_f
     x, y = circle(cx, Y / 2 + 0.21, radius)
     u0 = np.zeros((X, Y, 2)); u0[..., 0] = u_in
     f0 = oracle.incomp_equilibrium(u0, np.ones((X, Y)))
-    prm = pylbm.BgkParams(omega, 0, 1, form=pylbm.FORM_REFERENCE_ORDER)
+    prm = pylbm.BgkParams(omega, 0, 1, form=form)
     bc = pylbm.Bc(row_lo=pylbm.EDGE_ABB_VELOCITY, row_hi=pylbm.EDGE_ABB_VELOCITY, col_lo=pylbm.EDGE_SPECULAR,
                   col_hi=pylbm.EDGE_SPECULAR, uw_r=u_in)
     n = 1 + D * n_blocks
@@ -330,8 +332,13 @@ def _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, n_blocks, start_f
     ibw = pylbm.Ibm(lib, x, y, X, Y)
     sv.attach_ibm(ibw)
     sv.set_f(f0)
-    sv.step(n)
-    want, Fw = sv.get_f(), ibw.surface_force()
+    try:
+        if yardstick_depth is not None:
+            lib.set_tuning(b"ibm_depth", yardstick_depth)
+        sv.step(n)
+        want, Fw = sv.get_f(), ibw.surface_force()
+    finally:
+        lib.set_tuning(b"ibm_depth", -1)
     sv.close(); ibw.close()
     # first iteration on the whole block: collide, forcing, source (cylinder_test.cpp:103-127)
     d = dev()
@@ -409,14 +416,21 @@ def _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, n_blocks, start_f
     return got, want, Fs, Fw, roles
 
 
-@pytest.mark.parametrize("case", ["on_the_seam", "inside_slab0", "band_into_ghost_rows", "three_slabs_seam_1_2",
-                                  "off_centre_on_seam", "depth3_on_seam"])
+SLAB_LAYOUTS = ["on_the_seam", "inside_slab0", "band_into_ghost_rows", "three_slabs_seam_1_2", "off_centre_on_seam", "depth3_on_seam"]
+
+
+@pytest.mark.parametrize("case", SLAB_LAYOUTS)
 def test_cylinder_blocks_over_slabs_equal_single_block(lib, oracle, case):
     """the cylinder centred ON a seam (the BASELINE geometry: centre at rows/4 of 8 slabs),
     in blocks of D = 5 steps: both co-owners run the band chain, swap the band's outer rows, nothing else
     changes -- populations and surface force equal the single block bit for bit.  Also the boundary wholly
     inside one slab, the band reaching into (but its valid rows not across) the ghost rows, three slabs
     with a non-owner, an off-centre straddle and D = 3."""
+    _slab_layout_check(lib, oracle, case, pylbm.FORM_REFERENCE_ORDER)
+
+
+def _slab_layout_check(lib, oracle, case, form, yardstick_depth=None):
+    """one layout of test_cylinder_blocks_over_slabs_equal_single_block in the given form (yardstick_depth: _slab_block_run)"""
     X, Y, n_slabs, radius, D, nb = 256, 96, 2, 10.0, 5, 3
     if case == "on_the_seam":
         cx, want_roles = 128.3, [(1, 0, 1), (1, 1, 0)]
@@ -431,7 +445,8 @@ def test_cylinder_blocks_over_slabs_equal_single_block(lib, oracle, case):
     else:
         cx, D, nb, want_roles = 128.3, 3, 4, [(1, 0, 1), (1, 1, 0)]
     got, want, Fs, Fw, roles = _slab_block_run(lib, oracle, X, Y, n_slabs, cx, radius, D, nb,
-                                               start_from_pre=case in ("on_the_seam", "three_slabs_seam_1_2", "band_into_ghost_rows"))
+                                               start_from_pre=case in ("on_the_seam", "three_slabs_seam_1_2", "band_into_ghost_rows"),
+                                               form=form, yardstick_depth=yardstick_depth)
     assert [tuple(int(v) for v in r) for r in roles] == want_roles, roles
     assert bits_equal(got, want), (case, ulp_diff(got, want))
     for F in Fs:                      # every co-owner holds the same forcing, bit for bit
@@ -441,22 +456,31 @@ def test_cylinder_blocks_over_slabs_equal_single_block(lib, oracle, case):
 _SLAB_CASES = {"on_the_seam": (128.3, [(1, 0, 1), (1, 1, 0)]), "inside_slab0": (60.4, [(1, 0, 0), (0, 0, 0)])}
 
 
-@pytest.mark.parametrize("case,tunes", [
+SLAB_FORMS = [
     ("inside_slab0", [{"ibm_box_sole": 0}] * 3),   # the boxed band form without a straddle: outer rows from src
     ("inside_slab0", [{"ibm_box": 0}] * 3),        # the full-width band, alone ...
     ("on_the_seam", [{"ibm_box": 0}] * 3),         # ... and on both co-owners, outer rows through the stash
     # the band lattice handed over: the sole owner leaves it stale, the boxed band form must refresh it, then full width
     ("inside_slab0", [{}, {"ibm_box_sole": 0}, {"ibm_box": 0}]),
-], ids=["box_sole_0", "box_0", "box_0_on_the_seam", "stale_band_hand_over"])
+]
+SLAB_FORM_IDS = ["box_sole_0", "box_0", "box_0_on_the_seam", "stale_band_hand_over"]
+
+
+@pytest.mark.parametrize("case,tunes", SLAB_FORMS, ids=SLAB_FORM_IDS)
 def test_cylinder_slab_block_forms_equal_single_block(lib, oracle, case, tunes):
     """The forms of lbm_slab_ibm_block_compute that the default run never takes, 256 x 96 over 2 slabs, three blocks of
     D = 5: the boxed BAND form on a slab that holds the whole band ("ibm_box_sole" = 0), the full-width band ("ibm_box"
     = 0) on one owner and on two co-owners, and the three forms one after the other on one slab object (the sole
     owner's block leaves the band lattice stale).  Populations and surface force equal the single block after 1 + 15
     steps bit for bit, as in test_cylinder_blocks_over_slabs_equal_single_block."""
+    _slab_form_check(lib, oracle, case, tunes, pylbm.FORM_REFERENCE_ORDER)
+
+
+def _slab_form_check(lib, oracle, case, tunes, form, yardstick_depth=None):
+    """one case of test_cylinder_slab_block_forms_equal_single_block in the given form"""
     cx, want_roles = _SLAB_CASES[case]
     got, want, Fs, Fw, roles = _slab_block_run(lib, oracle, 256, 96, 2, cx, 10.0, 5, 3, start_from_pre=case == "on_the_seam",
-                                               block_tuning=tunes)
+                                               block_tuning=tunes, form=form, yardstick_depth=yardstick_depth)
     assert [tuple(int(v) for v in r) for r in roles] == want_roles, roles
     assert bits_equal(got, want), (case, tunes, ulp_diff(got, want))
     for F in Fs:
@@ -464,6 +488,11 @@ def test_cylinder_slab_block_forms_equal_single_block(lib, oracle, case, tunes):
 
 
 def test_ring_ibm_block_wrappers_on_a_self_ring(lib, oracle):
+    """_self_ring_run in the reference order"""
+    _self_ring_run(lib, oracle, pylbm.FORM_REFERENCE_ORDER)
+
+
+def _self_ring_run(lib, oracle, form):
     """lbm_ring_ibm_start / lbm_ring_bgk_block_ibm (RCCL transport of the slab blocks) on hardware: one rank whose
     two neighbours are itself (periodic self ring), playing the MIDDLE slab of a 3-slab domain that owns the
     cylinder.  The messages it receives are its own -- physically meaningless, but the same bytes a plain device
@@ -472,7 +501,7 @@ def test_ring_ibm_block_wrappers_on_a_self_ring(lib, oracle):
     X, Y, R, D = 384, 96, 128, 5
     omega, u_in = 1.0 / 0.55, 0.05
     x, y = circle(R + 64.3, Y / 2 + 0.21, 10.0)
-    prm = pylbm.BgkParams(omega, 0, 1, form=pylbm.FORM_REFERENCE_ORDER)
+    prm = pylbm.BgkParams(omega, 0, 1, form=form)
     bc = pylbm.Bc(row_lo=pylbm.EDGE_ABB_VELOCITY, row_hi=pylbm.EDGE_ABB_VELOCITY, col_lo=pylbm.EDGE_SPECULAR,
                   col_hi=pylbm.EDGE_SPECULAR, uw_r=u_in)
     u0 = np.zeros((R, Y, 2)); u0[..., 0] = u_in

@@ -16,6 +16,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
+import ibm_util  # noqa: E402
 import pylbm  # noqa: E402
 from gpu_util import bits_equal, dev, download_aos, ulp_diff, upload_soa  # noqa: E402
 from proc_util import run_ranks as start_ranks  # noqa: E402
@@ -151,9 +152,7 @@ def cg_ring_vs_one_block(lib, oracle, tmp_path, n, R, C, edge):
 
 # ---- immersed boundary over a chain, the cylinder on a seam -----------------------------------------------------------
 def circle(cx, cy, radius):
-    k = int(np.ceil(2 * np.pi * radius))
-    t = 2 * np.pi * np.arange(k) / k
-    return cx + radius * np.cos(t), cy + radius * np.sin(t)
+    return ibm_util.circle(cx, cy, radius, n=int(np.ceil(2 * np.pi * radius)))
 
 
 @pytest.mark.parametrize("n,cx,want_roles,cols", [

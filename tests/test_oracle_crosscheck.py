@@ -8,6 +8,7 @@ from conftest import relerr
 
 import pyoracle
 import torch_restatement as tr
+from ibm_util import circle
 
 
 @pytest.mark.parametrize("R,C,steps", [(24, 16, 1), (24, 16, 12), (31, 20, 5)])
@@ -18,12 +19,6 @@ def test_colour_gradient_restatements_agree(oracle, R, C, steps):
     b = tr.cg_run(R, C, red, blue, 0.1, 6.25e-6, steps)
     for k in ("f_r", "f_b", "rho_r", "rho_b", "u", "psi", "s_nu"):
         assert relerr(a[k], b[k]) < 1e-12, (k, relerr(a[k], b[k]))
-
-
-def circle(cx, cy, radius):
-    n = int(round(2 * np.pi * radius))
-    t = 2 * np.pi * np.arange(n) / n
-    return cx + radius * np.cos(t), cy + radius * np.sin(t)
 
 
 def test_ibm_force_restatements_agree(oracle):
