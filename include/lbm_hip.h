@@ -684,7 +684,9 @@ int lbm_ade_solver_set_walls(lbm_ade_solver* sv, const lbm_ade_iwalls* iwalls);
  * Refused on the host (LBM_ERR_INVALID, the message names the feature and the model): bc->pressure_rows; on a context
  * lbm_ade_solver_set_buoyancy with beta != (0, 0) (the forced collision is the BGK driver's: the reference has no forced
  * KBC; the forced KBC collision is lbm_ade_solver_set_buoyancy_m's, below), lbm_ade_solver_set_open with a non-empty
- * table, lbm_ade_solver_wall_exchange.  Row slabs and the ring: lbm_ade_stream_collide_part_m below, lbm_ring_ade_collide_m / lbm_ring_ade_step_m with the ring. */
+ * table, lbm_ade_solver_wall_exchange -- those two keep refusing a KBC context; open boundaries and the wall exchange with
+ * this fluid are lbm_ade_open_collide_m / lbm_ade_open_stream_collide_m / lbm_ade_solver_set_open_m and
+ * lbm_ade_wallx_rows_m / lbm_ade_solver_wall_exchange_m, below.  Row slabs and the ring: lbm_ade_stream_collide_part_m below, lbm_ring_ade_collide_m / lbm_ring_ade_step_m with the ring. */
 typedef struct lbm_ade_fluid {
   int model;          /* LBM_MODEL_BGK or LBM_MODEL_KBC */
   lbm_bgk_params bgk; /* read when model == LBM_MODEL_BGK */
@@ -708,7 +710,7 @@ int lbm_ade_stream_collide_m(double* fn, double* gn, const double* fo, const dou
  * bits are those of lbm_ade_stream_collide_m on one block.  The call only enqueues: no allocation, no host
  * synchronisation, capturable in a graph.  Refused on the host before any device call, the message naming the feature
  * and the model: bc->pressure_rows; a kbc.form that differs from scalar->form.  There is no parameter for buoyancy or
- * for an open view, and the wall exchange stays refused for this fluid. */
+ * for an open view; the wall exchange of a slab's rows with this fluid is lbm_ade_wallx_rows_m. */
 int lbm_ade_stream_collide_part_m(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                                   const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
                                   const lbm_ade_scalar_bc* sbc, const lbm_ade_iwalls* iwalls, int part, int edge_rows,
@@ -742,8 +744,10 @@ int lbm_ade_solver_create_m(lbm_ade_solver** out, const lbm_geom* g, const lbm_b
  * Refused on the host before any device call, under the `_mb` name: a non-finite field of the descriptor and everything the
  * `_m` calls refuse.  The calls only enqueue; a captured graph keeps the descriptor of its capture.
  * Row slabs and the ring: lbm_ade_slab_stream_collide_mb below, lbm_ring_ade_slab_collide_mb / lbm_ring_ade_slab_step_mb
- * with the ring.  Open boundaries and the wall exchange with a KBC fluid stay refused, there is no solver context for
- * slabs, and lbm_ade_solver_set_buoyancy itself still refuses beta != (0, 0) on a KBC context. */
+ * with the ring.  Open boundaries on one block and the wall exchange with a KBC fluid, buoyant or not, are
+ * lbm_ade_open_stream_collide_m and lbm_ade_wallx_rows_m below; open boundaries over slabs and the ring stay refused with
+ * this fluid, there is no solver context for slabs, and lbm_ade_solver_set_buoyancy itself still refuses beta != (0, 0) on
+ * a KBC context. */
 int lbm_ade_collide_mb(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
                        const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
                        const lbm_ade_buoyancy* buoy, double* rho, double* u, double* conc, lbm_stream_t s);
@@ -769,8 +773,8 @@ int lbm_ade_solver_set_buoyancy_m(lbm_ade_solver* sv, const lbm_ade_buoyancy* bu
  * name, the same launches, the same bits.
  * Refused on the host before any device call, under this name: NULL arguments, a non-finite field of the descriptor and
  * everything lbm_ade_stream_collide_part_m refuses (pressure rows, a kbc.form that differs from scalar->form, s2 outside
- * (0, 2], a bad part or edge_rows).  There is no parameter for an open view, and the wall exchange stays refused for this
- * fluid. */
+ * (0, 2], a bad part or edge_rows).  There is no parameter for an open view; the wall exchange of a slab's rows with this
+ * fluid is lbm_ade_wallx_rows_m. */
 int lbm_ade_slab_stream_collide_mb(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
                                    const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
                                    const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
@@ -899,6 +903,43 @@ long long lbm_ade_part_launches(void);
  * (before the first step, or after lbm_ade_solver_set_state, which primes the carry): the u before the iteration of a
  * post-collision state cannot be formed for nodes that were not carried. */
 int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open);
+/* Open boundaries with the fluid by model, on a single block: lbm_ade_collide_o / lbm_ade_stream_collide_o /
+ * lbm_ade_solver_set_open with a lbm_ade_fluid where those take lbm_bgk_params (the context's setter: for either fluid).
+ * model = LBM_MODEL_BGK: the calls ARE lbm_ade_collide_o / lbm_ade_stream_collide_o with `bgk` -- the same checks under
+ * those names, the same launches, the same bits; on a BGK context lbm_ade_solver_set_open_m IS lbm_ade_solver_set_open.
+ * model = LBM_MODEL_KBC, NULL or empty table: the calls ARE lbm_ade_collide_mb / lbm_ade_stream_collide_mb -- the same
+ * bits, the same launches, no carry needed.
+ * model = LBM_MODEL_KBC, a table with nodes: the step of lbm_ade_stream_collide_o with the fluid's collision replaced.
+ * One more launch follows the interior launch and the edge pass, before the interior-wall pass, one lane per listed node.
+ * Per node: the domain's gather of f, then the table's f slots (bounce-back, specular row / column, ABB and
+ * ABB_EXTRAPOLATED with the carried u: expressions on populations, independent of the collision); g pulled through the
+ * source map with the domain's gather, the domain's FIXED edges, the table's g slots with v = u + w, u the velocity of the
+ * fully fixed-up f; both collisions in the edge pass's order.  carry_out holds the unshifted u0 of the fixed-up f.  Passive,
+ * the fluid's collision is kbc::collide in the form of the call; with beta != (0, 0) it is the forced KBC collision of
+ * lbm_ade_collide_mb (collide_with on u0 + u_shift F), the table's g slots and the FIXED edges see the UNSHIFTED u0, the
+ * moment outputs hold the shifted u, and the step runs the reference order in both halves whatever `form` says.  The
+ * collide-only call writes carry_out from the pre-collision f in one more launch.  The calls only enqueue: no atomics, no
+ * allocation, no host synchronisation; a captured graph keeps the table and the descriptor of its capture.
+ * lbm_ade_solver_set_open_m on a KBC context follows the rule of lbm_ade_solver_set_open: a non-empty table is taken on a
+ * pre-collision state only, the table is borrowed, NULL clears it; lbm_ade_solver_step then carries the table and the two
+ * carries through, lbm_ade_solver_set_state primes the carry, and get_state, diag and run_until apply the table to the lazy
+ * stream.  lbm_ade_solver_set_open itself keeps refusing a non-empty table on that context.
+ * Refused on the host before any device call, under the new entry's name, the message naming feature and model -- the
+ * fluid's own checks first: pressure rows, s2 outside (0, 2], a kbc.form that differs from scalar->form, a non-finite
+ * field of the buoyancy descriptor (everything the `_m` / `_mb` calls refuse); an unfinalized table, a table for another
+ * lattice, a slab view, a NULL or aliasing carry, a row range other than the whole block, the overlap rule with the
+ * interior walls (everything the `_o` calls refuse).  Open boundaries over row slabs and the ring stay refused with this
+ * fluid: no entry takes a view with a lbm_ade_fluid. */
+int lbm_ade_open_collide_m(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                           const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                           const lbm_ade_buoyancy* buoy, const lbm_ade_open* open, double* carry_out, double* rho, double* u,
+                           double* conc, lbm_stream_t s);
+int lbm_ade_open_stream_collide_m(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                  const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                                  const lbm_ade_open* open, const double* carry_in, double* carry_out, int row_begin,
+                                  int row_end, double* rho, double* u, double* conc, lbm_stream_t s);
+int lbm_ade_solver_set_open_m(lbm_ade_solver* sv, const lbm_ade_open* open);
 
 /* ---- slab ring in C++: one process per GPU, packed halo messages between row slabs ------------------
  * Native counterpart of pylbm/slab.py (same kernels, same halo sets): edge rows + pack + ONE message
@@ -1346,6 +1387,21 @@ int lbm_ade_wallx_fold_host(double* out, const double* table_host, int table_row
  * pre-collision (before the first step): nothing has streamed. */
 int lbm_ade_solver_wall_exchange(lbm_ade_solver* sv, const int* region4, int row_begin, int row_end, double* out_host,
                                  double* table_host);
+/* The wall exchange with the fluid by model, defined exactly as above: lbm_ade_wallx_rows with a lbm_ade_fluid, and the
+ * context's call for either fluid.  model = LBM_MODEL_BGK (a BGK context): the calls ARE lbm_ade_wallx_rows /
+ * lbm_ade_solver_wall_exchange -- the same checks under those names, the same launch, the same bits.  model =
+ * LBM_MODEL_KBC: the velocity the FIXED g slots see is the KBC collision's u in the form of the call; in a buoyant call the
+ * unshifted u0 with the reference-order model.  The raw call serves a single block or a slab as the geometry says (on a
+ * slab iwalls is the slab's lbm_ade_iwalls_slab view); lbm_ade_wallx_fold and lbm_ade_wallx_fold_host fold its table.  An
+ * open table set on the context plays no part.  Refused on the host before any device call, under these names: what
+ * lbm_ade_stream_collide_mb refuses and what lbm_ade_wallx_rows refuses; lbm_ade_solver_wall_exchange itself keeps
+ * refusing a KBC context. */
+int lbm_ade_wallx_rows_m(double* table, int table_rows, int table_row0, const double* fo, const double* go,
+                         const lbm_geom* g, const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                         const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                         const int* region4, int row_begin, int row_end, lbm_stream_t s);
+int lbm_ade_solver_wall_exchange_m(lbm_ade_solver* sv, const int* region4, int row_begin, int row_end, double* out_host,
+                                   double* table_host);
 
 /* Tuning table.  Launch-shape keys (every setting produces identical results) and the three
  * implementation switches, which select between a model's two collision implementations:

@@ -1,6 +1,6 @@
 // The resolved call of the fused fluid + scalar step: for the translation units that launch ade.hpp's kernels
 // (capi_ade.hip: the BGK fluid and every host check; capi_ade_kbc.hip, capi_ade_kbc_part.hip, capi_ade_kbc_buoyant.hip,
-// capi_ade_kbc_buoyant_part.hip: the KBC fluid), which share their launch path in ade_launch.hpp.  Every other unit keeps a call in an AdeCallBuf
+// capi_ade_kbc_buoyant_part.hip, capi_ade_kbc_open.hip: the KBC fluid), which share their launch path in ade_launch.hpp.  Every other unit keeps a call in an AdeCallBuf
 // (internal.hpp) and never sees its members.
 #pragma once
 #include <type_traits>
@@ -23,7 +23,7 @@ struct AdeCall {
   int n_wall_nodes;
   const int* wall_first;  // host: the table's row index (R + 1 entries), NULL without nodes
   const lbm_bgk_params* fluid;  // a BGK fluid: the launches are capi_ade.hip's; NULL for a KBC fluid
-  const lbm_kbc_params* kbc;    // a KBC fluid: the launches are capi_ade_kbc(_part, _buoyant).hip's; NULL for a BGK fluid
+  const lbm_kbc_params* kbc;    // a KBC fluid: the launches are capi_ade_kbc(_part, _buoyant, _open).hip's; NULL for a BGK fluid
   const lbm_ade_params* scalar;
   const AdeOpenNode* open_nodes;  // the open-boundary table (lbm_ade_open), NULL without nodes
   const AdeOpenSeg* open_segs;

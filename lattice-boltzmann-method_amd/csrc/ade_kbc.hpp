@@ -283,4 +283,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   }
 }
 
+// k_ade_open_ranges for a KBC fluid: the open-boundary pass of a set of rows, one lane per listed node -- the same launch
+// shape (two index ranges of the sorted table in one dispatch), the same loads, rules, stores and carry, expression for
+// expression, so what it stores are the bits of k_ade_open_ranges<FM, SM, ...> were that instantiated.  A kernel of its
+// own for one reason: the shared template chooses its BUOYANT branch with a plain `if`, so it also compiles the forced
+// collision for the passive models, and KbcFastModel has none (it drops the conserved central moments: ade_forced_fluid
+// above).  Here the branch is `if constexpr`.  BUOYANT: the forced collision (collide_with on u0 + u_shift F) through
+// ade_buoyant_collide; the domain's FIXED edges, the table's g slots and carry_out see the UNSHIFTED u0, the moments
+// written hold the shifted u.  One node per lane: f, h, own and the collision are what is live.
+template <class FM, class SM, bool WITH_MOMENTS, bool FIXED, bool BUOYANT>
+__global__ __launch_bounds__(256) void k_ade_kbc_open_ranges(double* __restrict__ fn, double* __restrict__ gn,
+                                                             const double* __restrict__ fo, const double* __restrict__ go,
+                                                             Geom g, Bc bc, FM fm, SM sm, double* __restrict__ rho_out,
+                                                             double* __restrict__ u_out, double* __restrict__ c_out,
+                                                             AdeWalls sw, AdeBuoyancy by,
+                                                             const AdeOpenNode* __restrict__ nodes,
+                                                             const AdeOpenSeg* __restrict__ segs, int first0, int n0,
+                                                             int first1, int n, const double* __restrict__ carry_in,
+                                                             double* __restrict__ carry_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int m = i < n0 ? first0 + i : first1 + (i - n0);
+  const AdeOpenNode nd = nodes[m];
+  const int r = nd.r, c = nd.c;
+  const long o = g.at(r, c);
+  double f[Q], h[Q], own[Q], rho, ux, uy, conc, u0r, u0c;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    f[q] = fo[q * g.plane + g.at(wrap_row(g, r - icx(q)), wrap_col(g, c - icy(q)))];
+    own[q] = fo[q * g.plane + o];
+  }
+  bc_fixups_own(f, own, g, bc, r, c);
+  ade_open_fluid(f, own, nd, segs, carry_in, m);
+  ade_open_gather_scalar(h, own, go, g, FIXED ? ade_scalar_gather_bc(bc, sw.fixed) : bc, nd);
+  if constexpr (BUOYANT) {
+    ade_fluid_moments(f, rho, ux, uy);
+    u0r = ux, u0c = uy;
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
+    ade_buoyant_collide(f, h, fm, sm, by, rho, ux, uy, conc);
+  } else {
+    fm.collide(f, rho, ux, uy);
+    u0r = ux, u0c = uy;
+    if (FIXED) ade_fixed_walls(h, g, bc, sw, r, c, ux, uy, sm.wr, sm.wc);
+    ade_open_scalar(h, own, nd, segs, ux, uy, sm.wr, sm.wc);
+    sm.collide(h, ux, uy, conc);
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    fn[q * g.plane + o] = f[q];
+    gn[q * g.plane + o] = h[q];
+  }
+  carry_out[2 * m] = u0r;
+  carry_out[2 * m + 1] = u0c;
+  if (WITH_MOMENTS) {
+    const long nn = (long)g.R * g.C, oo = (long)r * g.C + c;
+    rho_out[oo] = rho;
+    u_out[oo] = ux;
+    u_out[nn + oo] = uy;
+    c_out[oo] = conc;
+  }
+}
+
 }  // namespace lbm

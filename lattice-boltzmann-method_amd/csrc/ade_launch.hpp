@@ -1,6 +1,6 @@
-// The launch path of the fused fluid + scalar step, once, for the four translation units that launch k_ade_* kernels
+// The launch path of the fused fluid + scalar step, once, for the translation units that launch k_ade_* kernels
 // (capi_ade.hip: the BGK fluid; capi_ade_kbc.hip, capi_ade_kbc_part.hip, capi_ade_kbc_buoyant.hip,
-// capi_ade_kbc_buoyant_part.hip: the KBC fluid -- units of their own because the device code of each is pinned).  Everything here is a template on the models and
+// capi_ade_kbc_buoyant_part.hip, capi_ade_kbc_open.hip: the KBC fluid -- units of their own because the device code of each is pinned).  Everything here is a template on the models and
 // BUOYANT, so a unit instantiates exactly the kernels it asks for: the sequences take the unit's interior launch and its
 // table passes as callables and name no interior kernel, no open-table kernel and no model themselves.  Nothing here
 // allocates or synchronises: the slab calls are captured into graphs.
@@ -133,5 +133,13 @@ int ade_kbc_buoyant_iwalls_pass(const AdeCall& call, double* f_new, double* g_ne
                                 const AdeRows& rows, double* rho, double* u, double* conc, hipStream_t st, long long* launches);
 int ade_kbc_buoyant_part_from(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old,
                               int part, int edge_rows, double* rho, double* u, double* conc, hipStream_t st);
+// capi_ade_kbc_open.hip: the open-table pass of the rows of a call with either KBC collision (call.buoyant decides; no
+// launch without listed nodes in those rows) -- what the two step units run before their interior-wall pass -- and the one
+// launch of the wall exchange (region4: the region clipped to the lattice, first: the table's row index on the device)
+int ade_kbc_open_pass(const AdeCall& call, double* f_new, double* g_new, const double* f_old, const double* g_old,
+                      const AdeRows& rows, double* rho, double* u, double* conc, hipStream_t st, long long* launches);
+int ade_kbc_wallx_launch(const AdeCall& call, double* table, int table_rows, int table_row0, const double* f_old,
+                         const double* g_old, const int* first, const int* region4, int row_begin, int row_end, int grid,
+                         hipStream_t st);
 
 }  // namespace lbm

@@ -3,7 +3,8 @@
 // context that runs the driver loop on one block.  Every host check of the step is here, for either fluid (ade_resolve:
 // the fluid is an AdeFluid, a BGK parameter block or a KBC one), and every entry point, the `_m` / `_mb` ones included; a
 // resolved call is launched by its fluid (ade_step_from, ade_part_from, ade_collide_from) -- the BGK fluid's kernels from
-// here, the KBC fluid's from the three capi_ade_kbc*.hip units, all through the one launch path of ade_launch.hpp.
+// here, the KBC fluid's from the capi_ade_kbc*.hip units (its open pass and wall exchange: capi_ade_kbc_open.hip), all through
+// the one launch path of ade_launch.hpp.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -453,16 +454,18 @@ int ade_resolve(const char* fn, const lbm_geom* lg, const lbm_bc* lbc, const Ade
   rc = ade_open_check(fn, open, lg, ade_scalar_gather_bc(call->bc, call->sw.fixed), call->n_wall_nodes > 0 ? iwalls : nullptr,
                       &call->open_nodes, &call->open_segs, &call->n_open_nodes, slab, &call->bc, call->sw.fixed);
   if (rc) return rc;
-  // (nor this one: no `_m` entry has a parameter for a table, and lbm_ade_solver_set_open refuses a KBC context)
-  LBM_REQUIRE(!(kbc && call->n_open_nodes > 0), "%s: open boundaries (a table of %d nodes) are not supported with a KBC fluid",
-              fn, call->n_open_nodes);
+  // a slab's view with a KBC fluid has no launch (the open pass of this fluid runs on one block: capi_ade_kbc_open.hip).  No
+  // public call reaches this: the `_m` / `_mb` part and ring entries have no parameter for a view, and the `_o` part and
+  // ring entries take BGK parameters only
+  LBM_REQUIRE(!(kbc && slab && call->n_open_nodes > 0), "%s: open boundaries over row slabs (a view of %d nodes) are not "
+              "supported with a KBC fluid", fn, call->n_open_nodes);
   if (call->n_open_nodes > 0) call->open_first = open->first.data();
   return LBM_OK;
 }
 
 // The open-table pass of the rows `r` (ade_row_ranges), behind the dispatch whose nodes it overwrites and on the same
 // stream: one lane per listed node; rows without one enqueue nothing.  The one launch site of k_ade_open_ranges, which
-// exists with the BGK fluid alone.  *launches += the kernels enqueued
+// exists with the BGK fluid alone (a KBC fluid's: k_ade_kbc_open_ranges, capi_ade_kbc_open.hip).  *launches += the kernels enqueued
 template <bool B, class FM, class SM>
 static int ade_open_pass(const AdeCall& k, const FM& fm, const SM& sm, double* fn, double* gn, const double* fo,
                          const double* go, const AdeRows& r, double* rho, double* u, double* conc, hipStream_t st,
@@ -645,13 +648,14 @@ static int ade_part(const char* name, double* fn, double* gn, const double* fo, 
 
 // The wall exchange of rows [row_begin, row_end) of the stream from fo, go, under the caller's name: the host checks of the
 // stream itself (ade_resolve; a single block or a slab, as the geometry says), the table's rows, one launch.  The region
-// is clipped to the lattice here.  A buoyant call takes the reference-order model, as its step does.
+// is clipped to the lattice here.  A buoyant call takes the reference-order model, as its step does.  Either fluid: a KBC
+// fluid's launch is capi_ade_kbc_open.hip's.
 static int ade_wallx_rows(const char* fn, double* table, int table_rows, int table_row0, const double* fo, const double* go,
-                          const lbm_geom* lg, const lbm_bc* lbc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
+                          const lbm_geom* lg, const lbm_bc* lbc, const AdeFluid& fluid, const lbm_ade_params* scalar,
                           const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                           const int* region4, int row_begin, int row_end, hipStream_t st) {
   AdeCall k;
-  int rc = ade_resolve(fn, lg, lbc, AdeFluid{fluid, nullptr}, scalar, sbc, buoy, iwalls, true, &k);
+  int rc = ade_resolve(fn, lg, lbc, fluid, scalar, sbc, buoy, iwalls, true, &k);
   if (rc) return rc;
   LBM_REQUIRE(table && fo && go, "%s: NULL argument (table, fo, go)", fn);
   rc = diag_range_check(fn, lg->R, row_begin, row_end);
@@ -664,6 +668,10 @@ static int ade_wallx_rows(const char* fn, double* table, int table_rows, int tab
   const int* first = k.n_wall_nodes > 0 ? iwalls->d_first : nullptr;
   const int cap = tuning("grid_cap", 0);
   const int grid = capped_grid((row_end - row_begin + 3) / 4, cap > 0 ? cap : 8192);
+  if (k.kbc) {  // capi_ade_kbc_open.hip
+    const int region[4] = {r0, r1, c0, c1};
+    return ade_kbc_wallx_launch(k, table, table_rows, table_row0, fo, go, first, region, row_begin, row_end, grid, st);
+  }
   return with_ade_models(k.fluid, k.scalar, k.buoyant, [&](const auto& fm, const auto& sm, auto) {
     using FM = std::decay_t<decltype(fm)>;
     with_flags([&](auto F) {
@@ -894,7 +902,6 @@ int lbm_ade_solver_set_state(lbm_ade_solver* sv, const double* f_host, const dou
 int lbm_ade_solver_step(lbm_ade_solver* sv, int n) {
   LBM_REQUIRE(sv && n >= 0, "lbm_ade_solver_step: bad argument (n=%d)", n);
   const lbm_ade_buoyancy* buoy = sv->buoyant ? &sv->buoy : nullptr;
-  // (a KBC context holds no open table with nodes: its setter refuses)
   const AdeFluid fluid = sv->model == LBM_MODEL_KBC ? AdeFluid{nullptr, &sv->kbc} : AdeFluid{&sv->fluid, nullptr};
   for (int i = 0; i < n; ++i) {
     const int k = sv->cur, o = k ^ 1;
@@ -1054,8 +1061,18 @@ int lbm_ade_wallx_rows(double* table, int table_rows, int table_row0, const doub
                        const lbm_bc* bc, const lbm_bgk_params* fluid, const lbm_ade_params* scalar,
                        const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
                        const int* region4, int row_begin, int row_end, lbm_stream_t s) {
-  return ade_wallx_rows("lbm_ade_wallx_rows", table, table_rows, table_row0, fo, go, g, bc, fluid, scalar, sbc, buoy, iwalls,
-                        region4, row_begin, row_end, as_stream(s));
+  return ade_wallx_rows("lbm_ade_wallx_rows", table, table_rows, table_row0, fo, go, g, bc, {fluid, nullptr}, scalar, sbc, buoy,
+                        iwalls, region4, row_begin, row_end, as_stream(s));
+}
+
+int lbm_ade_wallx_rows_m(double* table, int table_rows, int table_row0, const double* fo, const double* go, const lbm_geom* g,
+                         const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                         const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                         const int* region4, int row_begin, int row_end, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_wallx_rows_m", fluid, &fl)) return rc;
+  return ade_wallx_rows(fl.kbc ? "lbm_ade_wallx_rows_m" : "lbm_ade_wallx_rows", table, table_rows, table_row0, fo, go, g, bc, fl,
+                        scalar, sbc, buoy, iwalls, region4, row_begin, row_end, as_stream(s));
 }
 
 int lbm_ade_wallx_fold(double* out_dev, const double* table, int table_rows, int row_begin, int row_end, lbm_stream_t s) {
@@ -1064,11 +1081,11 @@ int lbm_ade_wallx_fold(double* out_dev, const double* table, int table_rows, int
   return ade_wallx_fold_launch(out_dev, table, table_rows, row_begin, row_end, as_stream(s));
 }
 
-int lbm_ade_solver_wall_exchange(lbm_ade_solver* sv, const int* region4, int row_begin, int row_end, double* out_host,
-                                 double* table_host) {
-  const char* fn = "lbm_ade_solver_wall_exchange";
+// the wall exchange of a context under the caller's name; kbc_ok: the entry serves a KBC context (the `_m` one)
+static int ade_solver_wall_exchange(const char* fn, bool kbc_ok, lbm_ade_solver* sv, const int* region4, int row_begin,
+                                    int row_end, double* out_host, double* table_host) {
   LBM_REQUIRE(sv && out_host, "%s: NULL argument (solver, out_host)", fn);
-  LBM_REQUIRE(sv->model != LBM_MODEL_KBC, "%s: the wall exchange is not supported with a KBC fluid", fn);
+  LBM_REQUIRE(kbc_ok || sv->model != LBM_MODEL_KBC, "%s: the wall exchange is not supported with a KBC fluid", fn);
   const int R = sv->g.R;
   int rc = diag_range_check(fn, R, row_begin, row_end);
   if (rc) return rc;
@@ -1085,7 +1102,8 @@ int lbm_ade_solver_wall_exchange(lbm_ade_solver* sv, const int* region4, int row
   }
   if (table_host && (row_begin > 0 || row_end < R)) LBM_CHECK_HIP(hipMemsetAsync(buf.table, 0, table_bytes, sv->st));
   const int k = sv->cur;
-  rc = ade_wallx_rows(fn, buf.table, R, 0, sv->f(k), sv->h(k), &sv->g, &sv->bc, &sv->fluid, &sv->scalar,
+  const AdeFluid fluid = sv->model == LBM_MODEL_KBC ? AdeFluid{nullptr, &sv->kbc} : AdeFluid{&sv->fluid, nullptr};
+  rc = ade_wallx_rows(fn, buf.table, R, 0, sv->f(k), sv->h(k), &sv->g, &sv->bc, fluid, &sv->scalar,
                       sv->fixed ? &sv->sbc : nullptr, sv->buoyant ? &sv->buoy : nullptr, sv->walls, region4, row_begin,
                       row_end, sv->st);
   if (!rc) rc = ade_wallx_fold_launch(buf.out_dev, buf.table, R, row_begin, row_end, sv->st);
@@ -1095,6 +1113,19 @@ int lbm_ade_solver_wall_exchange(lbm_ade_solver* sv, const int* region4, int row
   LBM_CHECK_HIP(hipStreamSynchronize(sv->st));
   for (int q = 0; q < LBM_WALLX_NQ; ++q) out_host[q] = buf.pinned[q];
   return LBM_OK;
+}
+
+int lbm_ade_solver_wall_exchange(lbm_ade_solver* sv, const int* region4, int row_begin, int row_end, double* out_host,
+                                 double* table_host) {
+  return ade_solver_wall_exchange("lbm_ade_solver_wall_exchange", false, sv, region4, row_begin, row_end, out_host, table_host);
+}
+
+// a BGK context: the call above, under its name
+int lbm_ade_solver_wall_exchange_m(lbm_ade_solver* sv, const int* region4, int row_begin, int row_end, double* out_host,
+                                   double* table_host) {
+  const bool kbc = sv && sv->model == LBM_MODEL_KBC;
+  return ade_solver_wall_exchange(kbc ? "lbm_ade_solver_wall_exchange_m" : "lbm_ade_solver_wall_exchange", true, sv, region4,
+                                  row_begin, row_end, out_host, table_host);
 }
 
 int lbm_ade_solver_run_until(lbm_ade_solver* sv, const lbm_converge* cv, int max_steps, int* steps_done, int* converged,
@@ -1161,7 +1192,6 @@ int lbm_ade_solver_set_buoyancy_m(lbm_ade_solver* sv, const lbm_ade_buoyancy* bu
   if (sv->model == LBM_MODEL_BGK) return lbm_ade_solver_set_buoyancy(sv, buoy);
   int rc = ade_buoyancy_check("lbm_ade_solver_set_buoyancy_m", buoy);
   if (rc) return rc;
-  // (a KBC context holds no open table and runs no wall exchange: lbm_ade_solver_set_open and _wall_exchange refuse)
   sv->buoy = buoy ? *buoy : lbm_ade_buoyancy{};
   sv->buoyant = buoy != nullptr;
   return LBM_OK;
@@ -1635,13 +1665,14 @@ int lbm_ade_slab_stream_collide_mb(double* fn, double* gn, const double* fo, con
 
 long long lbm_ade_part_launches(void) { return g_part_launches.load(std::memory_order_relaxed); }
 
-int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open) {
-  const char* fn = "lbm_ade_solver_set_open";
+// the open table of a context under the caller's name; kbc_ok: the entry serves a KBC context (the `_m` one).  The refusal
+// of a KBC context comes before everything else, the table the context already holds included
+static int ade_solver_set_open(const char* fn, bool kbc_ok, lbm_ade_solver* sv, const lbm_ade_open* open) {
   LBM_REQUIRE(sv, "%s: NULL solver", fn);
-  if (open == sv->open) return LBM_OK;
-  LBM_REQUIRE(sv->model != LBM_MODEL_KBC || !open || open->nodes.empty(),
+  LBM_REQUIRE(kbc_ok || sv->model != LBM_MODEL_KBC || !open || open->nodes.empty(),
               "%s: open boundaries (a table of %d nodes) are not supported with a KBC fluid", fn,
               open ? (int)open->nodes.size() : 0);
+  if (open == sv->open) return LBM_OK;
   if (open) {
     LBM_REQUIRE(!open->view, "%s: open boundaries: the table is a slab view (lbm_ade_open_slab): the context runs a single "
                 "block and takes the global table", fn);
@@ -1672,6 +1703,39 @@ int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open) {
   }
   sv->open = open;
   return LBM_OK;
+}
+
+int lbm_ade_solver_set_open(lbm_ade_solver* sv, const lbm_ade_open* open) {
+  return ade_solver_set_open("lbm_ade_solver_set_open", false, sv, open);
+}
+
+// a BGK context: the call above, under its name
+int lbm_ade_solver_set_open_m(lbm_ade_solver* sv, const lbm_ade_open* open) {
+  const bool kbc = sv && sv->model == LBM_MODEL_KBC;
+  return ade_solver_set_open(kbc ? "lbm_ade_solver_set_open_m" : "lbm_ade_solver_set_open", true, sv, open);
+}
+
+// lbm_ade_collide_o / lbm_ade_stream_collide_o with the fluid by model; model = BGK: those calls under their names
+int lbm_ade_open_collide_m(double* fp, double* gp, const double* f, const double* g_in, const lbm_geom* g, const lbm_bc* bc,
+                           const lbm_ade_fluid* fluid, const lbm_ade_params* scalar, const lbm_ade_scalar_bc* sbc,
+                           const lbm_ade_buoyancy* buoy, const lbm_ade_open* open, double* carry_out, double* rho, double* u,
+                           double* conc, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_open_collide_m", fluid, &fl)) return rc;
+  return ade_collide(fl.kbc ? "lbm_ade_open_collide_m" : "lbm_ade_collide_o", fp, gp, f, g_in, g, bc, fl, scalar, sbc, buoy,
+                     nullptr, rho, u, conc, as_stream(s), open, carry_out);
+}
+
+int lbm_ade_open_stream_collide_m(double* fn, double* gn, const double* fo, const double* go, const lbm_geom* g,
+                                  const lbm_bc* bc, const lbm_ade_fluid* fluid, const lbm_ade_params* scalar,
+                                  const lbm_ade_scalar_bc* sbc, const lbm_ade_buoyancy* buoy, const lbm_ade_iwalls* iwalls,
+                                  const lbm_ade_open* open, const double* carry_in, double* carry_out, int row_begin,
+                                  int row_end, double* rho, double* u, double* conc, lbm_stream_t s) {
+  AdeFluid fl;
+  if (int rc = ade_fluid_model("lbm_ade_open_stream_collide_m", fluid, &fl)) return rc;
+  return ade_stream_collide(fl.kbc ? "lbm_ade_open_stream_collide_m" : "lbm_ade_stream_collide_o", fn, gn, fo, go, g, bc, fl,
+                            scalar, sbc, buoy, iwalls, row_begin, row_end, rho, u, conc, as_stream(s), nullptr, open, carry_in,
+                            carry_out);
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 // of a resolved call are capi_ade.hip's (ade_resolve, ade_step_from, ade_collide_from); the sequences are ade_launch.hpp's.
 // On a slab the part kernel is launched from capi_ade_kbc_part.hip and the forced collision from
 // capi_ade_kbc_buoyant.hip -- units of their own, so that the device code of this one stays what it was; the
-// interior-wall pass of a part's rows is launched from here (ade_kbc_iwalls_pass).  No open boundaries, no wall exchange.
+// interior-wall pass of a part's rows is launched from here (ade_kbc_iwalls_pass).  The open-boundary pass and the wall
+// exchange are capi_ade_kbc_open.hip's; the step runs the open pass before the interior walls (ade_kbc_open_pass).
 #include "ade_kbc_call.hpp"
 
 namespace lbm {
@@ -33,7 +34,10 @@ int ade_kbc_step(const AdeCall& k, double* fn, double* gn, const double* fo, con
                         go, k.g, fm, sm, row_begin, row_end, d.tiles, rho, u, conc);
           }, d.nt & 1, d.nt & 2, rho != nullptr);
         },
-        [&](const AdeRows& r, long long* n) { return ade_iwalls_pass<false>(k, fm, sm, fn, gn, fo, go, r, rho, u, conc, st, n); });
+        [&](const AdeRows& r, long long* n) {  // the open table's listed nodes (capi_ade_kbc_open.hip), then the interior walls'
+          if (int rc = ade_kbc_open_pass(k, fn, gn, fo, go, r, rho, u, conc, st, n)) return rc;
+          return ade_iwalls_pass<false>(k, fm, sm, fn, gn, fo, go, r, rho, u, conc, st, n);
+        });
   });
 }
 

@@ -38,7 +38,10 @@ int ade_kbc_buoyant_step(const AdeCall& k, double* fn, double* gn, const double*
                       fn, gn, fo, go, k.g, fm, sm, row_begin, row_end, d.tiles, rho, u, conc, k.by);
         }, d.nt & 1, d.nt & 2, rho != nullptr);
       },
-      [&](const AdeRows& r, long long* n) { return ade_iwalls_pass<true>(k, fm, sm, fn, gn, fo, go, r, rho, u, conc, st, n); });
+      [&](const AdeRows& r, long long* n) {  // the open table's listed nodes (capi_ade_kbc_open.hip), then the interior walls'
+        if (int rc = ade_kbc_open_pass(k, fn, gn, fo, go, r, rho, u, conc, st, n)) return rc;
+        return ade_iwalls_pass<true>(k, fm, sm, fn, gn, fo, go, r, rho, u, conc, st, n);
+      });
 }
 
 }  // namespace lbm

@@ -1,7 +1,9 @@
 // The CPU-reachable half of the fluid + scalar step with a KBC fluid as a stand-alone program: every host-side check of
 // lbm_ade_collide_m, lbm_ade_stream_collide_m and lbm_ade_solver_create_m, and of their buoyant forms lbm_ade_collide_mb,
 // lbm_ade_stream_collide_mb and lbm_ade_solver_set_buoyancy_m, and of the buoyant slab and ring entries
-// lbm_ade_slab_stream_collide_mb, lbm_ring_ade_slab_collide_mb and lbm_ring_ade_slab_step_mb -- the fluid by model, the KBC parameters, what
+// lbm_ade_slab_stream_collide_mb, lbm_ring_ade_slab_collide_mb and lbm_ring_ade_slab_step_mb, and of open boundaries and the wall
+// exchange with the fluid by model, lbm_ade_open_collide_m, lbm_ade_open_stream_collide_m, lbm_ade_solver_set_open_m,
+// lbm_ade_wallx_rows_m and lbm_ade_solver_wall_exchange_m -- the fluid by model, the KBC parameters, what
 // the step refuses with this fluid, the checks it shares with the BGK fluid, and model = BGK answering with the message of
 // the call it names -- and, for both fluids, WHICH fault a call with two faults reports (the order of the host checks is
 // observable and differs per fluid; the last section).  Needs no device: every call is refused before a device call (the interior-wall table it
@@ -541,6 +543,234 @@ int main() {
     refused(ring_step_mb(c, &c.fl), "lbm_ring_ade_slab_step_mb: fluid model=7", "2 faults: model + buoyancy, ring_step_mb");
     refused(slab_mb(c), "lbm_ade_slab_stream_collide_mb: fluid model=7", "2 faults: model + buoyancy, slab_mb");
     lbm_ade_iwalls_destroy(open_table);
+  }
+  {  // open boundaries and the wall exchange with the fluid by model: lbm_ade_open_collide_m, lbm_ade_open_stream_collide_m,
+    // lbm_ade_solver_set_open_m, lbm_ade_wallx_rows_m, lbm_ade_solver_wall_exchange_m.  Without a device only an EMPTY open
+    // table can be finalized, so what needs listed nodes (the carry, the row range, the overlap rule) is the GPU suite's
+    struct Call {
+      lbm_ade_fluid fl;
+      lbm_geom g;
+      const lbm_bc* bc;
+      lbm_ade_params sc;
+      const lbm_ade_scalar_bc* sbc;
+      const lbm_ade_buoyancy* buoy;
+      const lbm_ade_iwalls* walls;
+      const lbm_ade_open* open;
+      bool lattices;  // four distinct aligned lattices / the exchange's table, fo, go given (false: all NULL)
+      int row_begin, row_end;
+    };
+    alignas(16) double l0[2], l1[2], l2[2], l3[2];
+    auto lat = [&](const Call& c, double* l) { return c.lattices ? l : nullptr; };
+    auto collide_o = [&](const Call& c) {
+      return lbm_ade_collide_o(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl.bgk, &c.sc, c.sbc, c.buoy, c.open, nullptr, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto stream_o = [&](const Call& c) {
+      return lbm_ade_stream_collide_o(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl.bgk, &c.sc, c.sbc, c.buoy, c.walls, c.open, nullptr, nullptr, c.row_begin, c.row_end, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto wallx = [&](const Call& c) {
+      return lbm_ade_wallx_rows(lat(c, l0), 8, 0, lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl.bgk, &c.sc, c.sbc, c.buoy, c.walls, nullptr, c.row_begin, c.row_end, nullptr);
+    };
+    auto open_collide_m = [&](const Call& c) {
+      return lbm_ade_open_collide_m(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, c.buoy, c.open, nullptr, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto open_stream_m = [&](const Call& c) {
+      return lbm_ade_open_stream_collide_m(lat(c, l0), lat(c, l1), lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, c.buoy, c.walls, c.open, nullptr, nullptr, c.row_begin, c.row_end, nullptr, nullptr, nullptr, nullptr);
+    };
+    auto wallx_m = [&](const Call& c) {
+      return lbm_ade_wallx_rows_m(lat(c, l0), 8, 0, lat(c, l2), lat(c, l3), &c.g, c.bc, &c.fl, &c.sc, c.sbc, c.buoy, c.walls, nullptr, c.row_begin, c.row_end, nullptr);
+    };
+    lbm_ade_scalar_bc fixed{};
+    fixed.mode[0] = LBM_ADE_SCALAR_FIXED;  // on a PERIODIC row (NULL bc)
+    lbm_ade_buoyancy bad_buoy{1e-2, -5e-3, HUGE_VAL, 1.0, 1.0 / 3.0, 1.0 / 9.0};  // c_ref = inf
+    const lbm_bc pressure{0, 0, 0, 0, 1, 1.0, 1.0, 0.0, 0.0};
+    lbm_ade_iwalls* raw_walls = nullptr;                                   // never finalized
+    lbm_ade_open *raw_open = nullptr, *small = nullptr, *view = nullptr;  // a column of rules, never finalized; an empty 6 x 8
+    bool built = lbm_ade_iwalls_create(&raw_walls, 8, 8) == LBM_OK && lbm_ade_open_create(&raw_open, 8, 8) == LBM_OK;
+    built = built && lbm_ade_open_add_f(raw_open, 0, 0, 1, 0, 8, 0xFFu, LBM_ADE_OPEN_BOUNCE_BACK, 0.0, 0.0, 0, 0) == LBM_OK;
+    built = built && lbm_ade_open_create(&small, 6, 8) == LBM_OK && lbm_ade_open_finalize(small) == LBM_OK;
+    built = built && lbm_ade_open_slab(&view, raw_open, 0, 8) == LBM_OK;  // a slab view of all rows, never finalized
+    if (!built) {
+      ++failures;
+      std::printf("FAIL: building the tables of the open-boundary section\n");
+    }
+    Call good_bgk{};
+    good_bgk.fl.model = LBM_MODEL_BGK;
+    good_bgk.fl.bgk = lbm_bgk_params{1.2, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, LBM_FORM_DEFAULT};
+    good_bgk.fl.kbc = lbm_kbc_params{-3.0, 9};  // not read with model = BGK
+    good_bgk.g = g;
+    good_bgk.sc = sc;
+    good_bgk.lattices = true;
+    good_bgk.row_begin = 0, good_bgk.row_end = 8;
+    Call good_kbc = good_bgk;
+    good_kbc.fl = kbc;
+    Call c;
+
+    // ---- the fluid of the new entries, and everything the `_m` / `_mb` calls refuse, under the new names
+    refused(lbm_ade_open_collide_m(l0, l1, l2, l3, &g, nullptr, nullptr, &sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "lbm_ade_open_collide_m: NULL fluid", "open_collide_m: NULL fluid");
+    refused(lbm_ade_open_stream_collide_m(l0, l1, l2, l3, &g, nullptr, nullptr, &sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 8, nullptr, nullptr, nullptr, nullptr), "lbm_ade_open_stream_collide_m: NULL fluid", "open_stream_m: NULL fluid");
+    refused(lbm_ade_wallx_rows_m(l0, 8, 0, l2, l3, &g, nullptr, nullptr, &sc, nullptr, nullptr, nullptr, nullptr, 0, 8, nullptr), "lbm_ade_wallx_rows_m: NULL fluid", "wallx_m: NULL fluid");
+    c = good_kbc;
+    c.fl.model = 7;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: fluid model=7", "open_collide_m: unknown model");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: fluid model=7", "open_stream_m: unknown model");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: fluid model=7", "wallx_m: unknown model");
+    c = good_kbc;
+    c.fl.kbc.s2 = 2.5;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: KBC fluid: s2=2.5 outside (0, 2]", "open_collide_m: s2 = 2.5");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: KBC fluid: s2=2.5 outside (0, 2]", "open_stream_m: s2 = 2.5");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: KBC fluid: s2=2.5 outside (0, 2]", "wallx_m: s2 = 2.5");
+    c.fl.kbc.s2 = 0.0;
+    refused(open_stream_m(c), "s2=0 outside (0, 2]", "open_stream_m: s2 = 0");
+    c = good_kbc;
+    c.bc = &pressure;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: pressure rows (pressure_rows=1) are not supported by the fluid + scalar step with a KBC fluid", "open_collide_m: pressure rows");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: pressure rows (pressure_rows=1)", "open_stream_m: pressure rows");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: pressure rows (pressure_rows=1)", "wallx_m: pressure rows");
+    c = good_kbc;
+    c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: KBC fluid form=1 differs from the scalar form=2", "open_collide_m: forms differ");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: KBC fluid form=1 differs from the scalar form=2", "open_stream_m: forms differ");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: KBC fluid form=1 differs from the scalar form=2", "wallx_m: forms differ");
+    c = good_kbc;
+    c.buoy = &bad_buoy;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: buoyancy c_ref=inf must be finite", "open_collide_m: non-finite buoyancy");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: buoyancy c_ref=inf must be finite", "open_stream_m: non-finite buoyancy");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: buoyancy c_ref=inf must be finite", "wallx_m: non-finite buoyancy");
+    c = good_kbc;
+    c.g.C = 7;
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: C=7 must be even", "open_stream_m: odd C");
+    c = good_kbc;
+    c.sbc = &fixed;
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: scalar edge row_lo: FIXED on a PERIODIC", "open_stream_m: FIXED on a periodic row");
+    c = good_kbc;
+    c.walls = raw_walls;
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: interior walls: the table is not finalized", "open_stream_m: unfinalized interior walls");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: interior walls: the table is not finalized", "wallx_m: unfinalized interior walls");
+
+    // ---- everything the `_o` calls refuse that needs no listed node, under the new names
+    c = good_kbc;
+    c.open = raw_open;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: open boundaries: the table is not finalized", "open_collide_m: unfinalized table");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: open boundaries: the table is not finalized", "open_stream_m: unfinalized table");
+    c.open = small;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: open boundaries: the table is for a 6 x 8 lattice, the call for 8 x 8", "open_collide_m: table of another size");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: open boundaries: the table is for a 6 x 8 lattice, the call for 8 x 8", "open_stream_m: table of another size");
+    c.open = view;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: open boundaries: the table is a slab view", "open_collide_m: slab view");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: open boundaries: the table is a slab view", "open_stream_m: slab view");
+    c = good_kbc;  // a NULL table is the `_mb` call, stopped at its lattices and its range under the new name
+    c.lattices = false;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: NULL lattice", "open_collide_m: NULL lattices");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: NULL lattice", "open_stream_m: NULL lattices");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: NULL argument (table, fo, go)", "wallx_m: NULL table, fo, go");
+    c = good_kbc;
+    c.row_begin = 5, c.row_end = 3;
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: row range [5, 3) outside [0, 8)", "open_stream_m: bad row range");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: ", "wallx_m: bad row range");
+    c = good_kbc;
+    c.row_end = 9;
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: ", "wallx_m: rows beyond the lattice");
+    refused(lbm_ade_wallx_rows_m(l0, 4, 0, l2, l3, &g, nullptr, &kbc, &sc, nullptr, nullptr, nullptr, nullptr, 0, 8, nullptr), "lbm_ade_wallx_rows_m: table_row0=0 + rows [0, 8) do not fit table_rows=4", "wallx_m: table too short");
+    // the context's entries without a context
+    refused(lbm_ade_solver_set_open_m(nullptr, nullptr), "NULL solver", "set_open_m: NULL solver");
+    double out6[LBM_WALLX_NQ];
+    refused(lbm_ade_solver_wall_exchange_m(nullptr, nullptr, 0, 8, out6, nullptr), "NULL argument (solver, out_host)", "wall_exchange_m: NULL solver");
+
+    // ---- model = BGK: the siblings answer, under their names
+    c = good_bgk;
+    c.fl.bgk.omega = 2.0;
+    refused(open_collide_m(c), "lbm_ade_collide_o: omega=2 outside (0, 2)", "BGK through open_collide_m");
+    refused(open_stream_m(c), "lbm_ade_stream_collide_o: omega=2 outside (0, 2)", "BGK through open_stream_m");
+    refused(wallx_m(c), "lbm_ade_wallx_rows: omega=2 outside (0, 2)", "BGK through wallx_m");
+    c = good_bgk;
+    c.open = raw_open;
+    refused(open_collide_m(c), "lbm_ade_collide_o: open boundaries: the table is not finalized", "BGK through open_collide_m: unfinalized table");
+    refused(open_stream_m(c), "lbm_ade_stream_collide_o: open boundaries: the table is not finalized", "BGK through open_stream_m: unfinalized table");
+    c = good_bgk;
+    c.lattices = false;
+    refused(wallx_m(c), "lbm_ade_wallx_rows: NULL argument (table, fo, go)", "BGK through wallx_m: NULL table, fo, go");
+
+    // ---- two faults in one call.  model = BGK: the new entry reports what its sibling reports, word for word
+    c = good_bgk;  // omega_g outside range + unfinalized open table
+    c.sc.omega_g = 2.5, c.open = raw_open;
+    refused(collide_o(c), "lbm_ade_collide_o: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + unfinalized open table, collide_o");
+    refused(stream_o(c), "lbm_ade_stream_collide_o: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + unfinalized open table, stream_o");
+    refused(open_collide_m(c), "lbm_ade_collide_o: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + unfinalized open table, open_collide_m (BGK)");
+    refused(open_stream_m(c), "lbm_ade_stream_collide_o: omega_g=2.5 outside (0, 2)", "2 faults: omega_g + unfinalized open table, open_stream_m (BGK)");
+    c = good_bgk;  // unfinalized interior walls + unfinalized open table
+    c.walls = raw_walls, c.open = raw_open;
+    refused(stream_o(c), "lbm_ade_stream_collide_o: interior walls: the table is not finalized", "2 faults: unfinalized walls + unfinalized open table, stream_o");
+    refused(open_stream_m(c), "lbm_ade_stream_collide_o: interior walls: the table is not finalized", "2 faults: unfinalized walls + unfinalized open table, open_stream_m (BGK)");
+    c = good_bgk;  // unfinalized open table + NULL lattice
+    c.open = raw_open, c.lattices = false;
+    refused(collide_o(c), "lbm_ade_collide_o: open boundaries: the table is not finalized", "2 faults: unfinalized open table + NULL lattice, collide_o");
+    refused(stream_o(c), "lbm_ade_stream_collide_o: open boundaries: the table is not finalized", "2 faults: unfinalized open table + NULL lattice, stream_o");
+    refused(open_collide_m(c), "lbm_ade_collide_o: open boundaries: the table is not finalized", "2 faults: unfinalized open table + NULL lattice, open_collide_m (BGK)");
+    refused(open_stream_m(c), "lbm_ade_stream_collide_o: open boundaries: the table is not finalized", "2 faults: unfinalized open table + NULL lattice, open_stream_m (BGK)");
+    c = good_bgk;  // a slab view that is not finalized either: the kind is named first
+    c.open = view;
+    refused(stream_o(c), "lbm_ade_stream_collide_o: open boundaries: the table is a slab view", "2 faults: slab view + unfinalized, stream_o");
+    refused(open_stream_m(c), "lbm_ade_stream_collide_o: open boundaries: the table is a slab view", "2 faults: slab view + unfinalized, open_stream_m (BGK)");
+    c = good_bgk;  // table of another size + bad row range
+    c.open = small, c.row_begin = 5, c.row_end = 3;
+    refused(stream_o(c), "lbm_ade_stream_collide_o: open boundaries: the table is for a 6 x 8 lattice", "2 faults: table size + bad row range, stream_o");
+    refused(open_stream_m(c), "lbm_ade_stream_collide_o: open boundaries: the table is for a 6 x 8 lattice", "2 faults: table size + bad row range, open_stream_m (BGK)");
+    c = good_bgk;  // NULL lattice + bad row range
+    c.lattices = false, c.row_begin = 5, c.row_end = 3;
+    refused(stream_o(c), "lbm_ade_stream_collide_o: NULL lattice", "2 faults: NULL lattice + bad row range, stream_o");
+    refused(open_stream_m(c), "lbm_ade_stream_collide_o: NULL lattice", "2 faults: NULL lattice + bad row range, open_stream_m (BGK)");
+    c = good_bgk;  // the exchange: non-finite buoyancy + NULL table, fo, go
+    c.buoy = &bad_buoy, c.lattices = false;
+    refused(wallx(c), "lbm_ade_wallx_rows: buoyancy c_ref=inf", "2 faults: buoyancy + NULL argument, wallx_rows");
+    refused(wallx_m(c), "lbm_ade_wallx_rows: buoyancy c_ref=inf", "2 faults: buoyancy + NULL argument, wallx_m (BGK)");
+    c = good_bgk;  // the exchange: unfinalized interior walls + NULL table, fo, go
+    c.walls = raw_walls, c.lattices = false;
+    refused(wallx(c), "lbm_ade_wallx_rows: interior walls: the table is not finalized", "2 faults: unfinalized walls + NULL argument, wallx_rows");
+    refused(wallx_m(c), "lbm_ade_wallx_rows: interior walls: the table is not finalized", "2 faults: unfinalized walls + NULL argument, wallx_m (BGK)");
+    c = good_bgk;  // the exchange: NULL table, fo, go + bad row range
+    c.lattices = false, c.row_begin = 5, c.row_end = 3;
+    refused(wallx(c), "lbm_ade_wallx_rows: NULL argument (table, fo, go)", "2 faults: NULL argument + bad row range, wallx_rows");
+    refused(wallx_m(c), "lbm_ade_wallx_rows: NULL argument (table, fo, go)", "2 faults: NULL argument + bad row range, wallx_m (BGK)");
+
+    // ---- two faults, model = KBC: the fluid's own checks first, the KBC form mismatch after the interior walls, the open
+    // table last of what the call resolves, the lattices and the range after
+    c = good_kbc;  // s2 outside range + unfinalized open table
+    c.fl.kbc.s2 = 2.5, c.open = raw_open;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: KBC fluid: s2=2.5 outside (0, 2]", "2 faults: s2 + unfinalized open table, open_collide_m");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: KBC fluid: s2=2.5 outside (0, 2]", "2 faults: s2 + unfinalized open table, open_stream_m");
+    c = good_kbc;  // pressure rows + slab view
+    c.bc = &pressure, c.open = view;
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: pressure rows (pressure_rows=1)", "2 faults: pressure rows + slab view, open_stream_m");
+    c = good_kbc;  // non-finite buoyancy + unfinalized open table
+    c.buoy = &bad_buoy, c.open = raw_open;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: buoyancy c_ref=inf", "2 faults: buoyancy + unfinalized open table, open_collide_m");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: buoyancy c_ref=inf", "2 faults: buoyancy + unfinalized open table, open_stream_m");
+    c = good_kbc;  // KBC / scalar form mismatch + unfinalized open table
+    c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED, c.open = raw_open;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + unfinalized open table, open_collide_m");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + unfinalized open table, open_stream_m");
+    c = good_kbc;  // unfinalized interior walls + KBC / scalar form mismatch
+    c.walls = raw_walls, c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED;
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: interior walls: the table is not finalized", "2 faults: unfinalized walls + KBC form mismatch, open_stream_m");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: interior walls: the table is not finalized", "2 faults: unfinalized walls + KBC form mismatch, wallx_m");
+    c = good_kbc;  // unfinalized open table + NULL lattice
+    c.open = raw_open, c.lattices = false;
+    refused(open_collide_m(c), "lbm_ade_open_collide_m: open boundaries: the table is not finalized", "2 faults: unfinalized open table + NULL lattice, open_collide_m");
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: open boundaries: the table is not finalized", "2 faults: unfinalized open table + NULL lattice, open_stream_m");
+    c = good_kbc;  // a slab view that is not finalized either
+    c.open = view;
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: open boundaries: the table is a slab view", "2 faults: slab view + unfinalized, open_stream_m");
+    c = good_kbc;  // NULL lattice + bad row range
+    c.lattices = false, c.row_begin = 5, c.row_end = 3;
+    refused(open_stream_m(c), "lbm_ade_open_stream_collide_m: NULL lattice", "2 faults: NULL lattice + bad row range, open_stream_m");
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: NULL argument (table, fo, go)", "2 faults: NULL argument + bad row range, wallx_m");
+    c = good_kbc;  // the exchange: KBC / scalar form mismatch + NULL table, fo, go
+    c.fl.kbc.form = LBM_FORM_REFERENCE_ORDER, c.sc.form = LBM_FORM_REASSOCIATED, c.lattices = false;
+    refused(wallx_m(c), "lbm_ade_wallx_rows_m: KBC fluid form=1 differs from the scalar form=2", "2 faults: KBC form mismatch + NULL argument, wallx_m");
+    lbm_ade_open_destroy(view);
+    lbm_ade_open_destroy(small);
+    lbm_ade_open_destroy(raw_open);
+    lbm_ade_iwalls_destroy(raw_walls);
   }
   std::printf("ade_kbc_host_check: %d refusals checked, %d failures\n", checks, failures);
   return failures ? 1 : 0;

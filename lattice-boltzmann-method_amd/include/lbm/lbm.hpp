@@ -292,8 +292,8 @@ class AdeSolver {
     check(lbm_ade_solver_create(&h_, &g, &bc, &fluid, &scalar, stream));
   }
   // the same loop with the entropic KBC collision as the fluid (lbm_ade_fluid, model = LBM_MODEL_KBC): s2 in (0, 2] in
-  // place of omega.  set_buoyancy with a non-zero beta (set_buoyancy_m takes it), set_open with a non-empty table and
-  // wall_exchange throw on it.
+  // place of omega.  set_buoyancy with a non-zero beta, set_open with a non-empty table and wall_exchange throw on it:
+  // set_buoyancy_m, set_open_m and wall_exchange_m take them.
   static AdeSolver kbc(int R, int C, double s2, double omega_g, double w_r, double w_c, const lbm_bc& bc = BoundarySet(),
                        int form = LBM_FORM_DEFAULT, lbm_stream_t stream = nullptr) {
     AdeSolver sv(R, C);
@@ -331,6 +331,10 @@ class AdeSolver {
   // open boundaries from the next step on (a finalized table, borrowed); taken before the first step or before set_state
   void set_open(const AdeOpenBoundary& o) { check(lbm_ade_solver_set_open(h_, o.handle())); }
   void clear_open() { check(lbm_ade_solver_set_open(h_, nullptr)); }
+  // the same for either fluid (lbm_ade_solver_set_open_m): on a context made by kbc() the open pass with the KBC collision,
+  // the forced one under set_buoyancy_m; on a BGK context set_open itself
+  void set_open_m(const AdeOpenBoundary& o) { check(lbm_ade_solver_set_open_m(h_, o.handle())); }
+  void clear_open_m() { check(lbm_ade_solver_set_open_m(h_, nullptr)); }
   // what the reference loop holds after the iterations run so far
   struct State {
     std::vector<double> f, g;  // [R][C][9]
@@ -370,6 +374,16 @@ class AdeSolver {
     if (table) table->resize((size_t)LBM_WALLX_NQ * R_);
     check(lbm_ade_solver_wall_exchange(h_, region4, row_begin, row_end < 0 ? R_ : row_end, out.data(),
                                        table ? table->data() : nullptr));
+    return out;
+  }
+  // the same for either fluid (lbm_ade_solver_wall_exchange_m): on a context made by kbc() the FIXED slots see the KBC
+  // collision's u (the unshifted u0 under buoyancy); on a BGK context wall_exchange itself
+  std::vector<double> wall_exchange_m(const int* region4 = nullptr, int row_begin = 0, int row_end = -1,
+                                      std::vector<double>* table = nullptr) {
+    std::vector<double> out(LBM_WALLX_NQ);
+    if (table) table->resize((size_t)LBM_WALLX_NQ * R_);
+    check(lbm_ade_solver_wall_exchange_m(h_, region4, row_begin, row_end < 0 ? R_ : row_end, out.data(),
+                                         table ? table->data() : nullptr));
     return out;
   }
   lbm_ade_solver* handle() { return h_; }

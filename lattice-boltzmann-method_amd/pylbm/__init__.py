@@ -339,8 +339,17 @@ def load_library(path=LIB_PATH):
     lib.lbm_ade_slab_stream_collide_mb.argtypes = [p, p, p, p, p, p, p, p, p, p, p, i, i, p, p, p, p]
     lib.lbm_ring_ade_slab_collide_mb.argtypes = [p, p, p, p, p, p, p, p, p, p, p]
     lib.lbm_ring_ade_slab_step_mb.argtypes = [p, p, p, p, p, p, p, p, p, p, p, i, p]
+    # open boundaries and the wall exchange with the fluid by model: lbm_ade_collide_o / lbm_ade_stream_collide_o /
+    # lbm_ade_solver_set_open / lbm_ade_wallx_rows / lbm_ade_solver_wall_exchange with an AdeFluid
+    lib.lbm_ade_open_collide_m.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p]
+    lib.lbm_ade_open_stream_collide_m.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, p, p, p, p]
+    lib.lbm_ade_solver_set_open_m.argtypes = [p, p]
+    lib.lbm_ade_wallx_rows_m.argtypes = [p, i, i, p, p, p, p, p, p, p, p, p, p, i, i, p]
+    lib.lbm_ade_solver_wall_exchange_m.argtypes = [p, p, i, i, p, p]
     for fn in (lib.lbm_ade_stream_collide_part_m, lib.lbm_ring_ade_collide_m, lib.lbm_ring_ade_step_m,
-               lib.lbm_ade_slab_stream_collide_mb, lib.lbm_ring_ade_slab_collide_mb, lib.lbm_ring_ade_slab_step_mb):
+               lib.lbm_ade_slab_stream_collide_mb, lib.lbm_ring_ade_slab_collide_mb, lib.lbm_ring_ade_slab_step_mb,
+               lib.lbm_ade_open_collide_m, lib.lbm_ade_open_stream_collide_m, lib.lbm_ade_solver_set_open_m,
+               lib.lbm_ade_wallx_rows_m, lib.lbm_ade_solver_wall_exchange_m):
         fn.restype = ct.c_int
     return lib
 
@@ -531,8 +540,8 @@ class AdeSolver:
         try:
             if walls is not None:
                 self.set_walls(walls)
-            if open is not None:
-                self.set_open(open)
+            if open is not None:  # by model: a KBC fluid takes the table through set_open_m
+                (self.set_open_m if isinstance(fluid, (KbcParams, AdeFluid)) else self.set_open)(open)
             if scalar_bc is not None:
                 self.set_scalar_bc(scalar_bc)
             if buoyancy is not None:  # by model: a KBC fluid takes the forced collision of set_buoyancy_m
@@ -566,6 +575,12 @@ class AdeSolver:
         """the open boundaries from the next step on (a finalized AdeOpenBoundary, or None: none); borrowed, not copied.
         A non-empty table is taken before the first step or before set_state only."""
         self.lib.ade_solver_set_open(self.h, table.h if table is not None else None)
+        self.open = table  # keeps the table alive
+
+    def set_open_m(self, table):
+        """set_open for either fluid (lbm_ade_solver_set_open_m): with a KBC fluid the open pass with that fluid's
+        collision, the forced one under set_buoyancy_m; with a BGK fluid set_open itself"""
+        self.lib.ade_solver_set_open_m(self.h, table.h if table is not None else None)
         self.open = table  # keeps the table alive
 
     def close(self):
@@ -618,6 +633,16 @@ class AdeSolver:
         box = (ct.c_int * 4)(*[int(v) for v in region]) if region is not None else None
         self.lib.ade_solver_wall_exchange(self.h, box, int(row_begin), int(self.R if row_end is None else row_end),
                                           _hptr(out), _hptr(tab) if table else None)
+        return (out, tab) if table else out
+
+    def wall_exchange_m(self, region=None, row_begin=0, row_end=None, table=False):
+        """wall_exchange for either fluid (lbm_ade_solver_wall_exchange_m): with a KBC fluid the FIXED slots see that
+        collision's u (the unshifted u0 under buoyancy); with a BGK fluid wall_exchange itself"""
+        out = np.empty(WALLX_NQ)
+        tab = np.empty((WALLX_NQ, self.R)) if table else None
+        box = (ct.c_int * 4)(*[int(v) for v in region]) if region is not None else None
+        self.lib.ade_solver_wall_exchange_m(self.h, box, int(row_begin), int(self.R if row_end is None else row_end),
+                                            _hptr(out), _hptr(tab) if table else None)
         return (out, tab) if table else out
 
     def launches(self):

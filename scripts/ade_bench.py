@@ -31,10 +31,17 @@ and against the single-step BGK launch, on one periodic box, in one process, alt
   the forced KBC collision (lbm_ade_solver_set_buoyancy_m, beta = (0.5, -0.3), c_ref = 5e-4, u_shift = 1; the reference order),
   and bgk_pair_buoyant, the BGK buoyant pair step (Guo's coefficients); under "buoyant": the condition kbc_pair_buoyant < bgk_pair + kbc_single_ref
   per repeat, and kbc_pair_buoyant over the passive reference-order kbc_pair_ref and over bgk_pair_buoyant
+  --kbc --open is a mode of its own: the sedimentation channel with a KBC fluid (lbm_ade_solver_set_open_m, the open pass of
+  capi_ade_kbc_open.hip) -- a bounce-back bottom row, the channel's open table (lbm_ade_open_add_channel, u_in = 0.02, s2 = 1.6) and the
+  scaled rectangle as interior walls -- in one process, alternated: kbc_channel (default form: interior, edge pass, open
+  pass, interior-wall pass), kbc_plain (the same box without tables: interior + edge pass), bgk_channel (the BGK fluid with
+  the same tables, the lbm_ade_stream_collide_o path) and, with --buoyancy, kbc_channel_buoyant (the forced collision).  ms
+  per step of every repeat, kbc_channel over kbc_plain and over bgk_channel per repeat, the table sizes, the launches per
+  step, and the host time of one wall_exchange_m call on the KBC channel (20 calls, median)
 MLUPS count node updates (of the pair for fused / composed).  Algorithmic bytes of the fused step: 288 B per node update
 (18 loads + 18 stores of 8 bytes), of the BGK step 144 B.  Time: device events around `steps` steps after `warmup`.
 usage: ade_bench.py [--size 8192] [--steps 50] [--warmup 5] [--repeats 3] [--form default|ref|fast] [--fixed-walls] [--buoyancy]
-       [--interior-walls] [--open] [--wall-exchange] [--kbc]"""
+       [--interior-walls] [--open] [--wall-exchange] [--kbc] [--kbc --open [--buoyancy]]"""
 import argparse
 import ctypes as ct
 import json
@@ -190,6 +197,72 @@ def kbc_bench(lib, a, rho, conc, u, st, timed):
     return out
 
 
+def kbc_open_bench(lib, a, rho, conc, u, st, timed):
+    """--kbc --open: the JSON fields of that mode; rho, conc, u: the dense initial moments on the device (u overwritten)"""
+    R = C = a.size
+    dev = rho.device
+    # s2 = 1.6: next to 2 the channel does not stay finite with this collision (nor does the CPU yardstick's: DESIGN.md
+    # section 11); the time of a step does not depend on the rate
+    s2 = 1.6
+    u[0] = 0.01   # no node at rest: the reference KBC driver's state on a shear wave ...
+    u[1] += 0.02  # ... drifting towards the outlet with the inlet's velocity
+    f, g = (torch.empty((9, R, C), dtype=torch.float64, device=dev) for _ in range(2))
+    lib.kbc_equilibrium(_ptr(f), _ptr(rho), _ptr(u), R, C, 1, None)
+    lib.equilibrium(_ptr(g), _ptr(u), _ptr(conc), R, C, None)
+    torch.cuda.synchronize()
+    dg = pylbm.Geom(R, C, 0)
+    obc = pylbm.Bc(row_hi=pylbm.EDGE_BOUNCE_BACK)
+    channel = pylbm.AdeOpenBoundary(lib, R, C).channel(0.02, 1e-3, R // 4).finalize()
+    body = rectangle_table(lib, R, C)
+    scalar = pylbm.AdeParams(1.7, W)
+    kw = dict(bc=obc, stream=st.value)
+    solvers = {"kbc_channel": pylbm.AdeSolver(lib, R, C, pylbm.KbcParams(s2), scalar, walls=body, open=channel, **kw),
+               "kbc_plain": pylbm.AdeSolver(lib, R, C, pylbm.KbcParams(s2), scalar, **kw),
+               "bgk_channel": pylbm.AdeSolver(lib, R, C, pylbm.BgkParams(1.2, 0), scalar, walls=body, open=channel, **kw)}
+    if a.buoyancy:
+        solvers["kbc_channel_buoyant"] = pylbm.AdeSolver(lib, R, C, pylbm.KbcParams(s2), scalar, walls=body, open=channel,
+                                                         buoyancy=pylbm.AdeBuoyancy((0.5, -0.3), 5e-4, 1.0), **kw)
+    for sv in solvers.values():  # the state through the context, which primes the carry of its table
+        fc, gc, _, _, sg = sv.lattices()
+        lib.lattice_copy_rows(_ptr(fc), ct.byref(sg), 0, _ptr(f), ct.byref(dg), 0, R, st)
+        lib.lattice_copy_rows(_ptr(gc), ct.byref(sg), 0, _ptr(g), ct.byref(dg), 0, R, st)
+        lib.stream_sync(st)
+        if sv.open is not None:  # the carry of the state just copied in: the table again, on the pre-collision state
+            sv.set_open_m(None)
+            sv.set_open_m(channel)
+    del f, g
+    runs = {k: sv.step for k, sv in solvers.items()}
+    for fn in runs.values():
+        timed(fn, a.warmup)
+    before = {k: sv.launches() for k, sv in solvers.items()}
+    times = {k: [] for k in runs}
+    for _ in range(a.repeats):
+        for k, fn in runs.items():
+            times[k].append(timed(fn, a.steps))
+    ms = {k: [round(t / a.steps * 1e3, 4) for t in v] for k, v in times.items()}
+    per_step = {k: (sv.launches() - before[k]) / (a.steps * a.repeats) for k, sv in solvers.items()}
+    nonfinite = {k: float(sv.diag()[pylbm.DIAG_NONFINITE]) for k, sv in solvers.items()}
+    x = solvers["kbc_channel"]
+    values = x.wall_exchange_m()  # the forced first call: its allocations
+    calls = []
+    for _ in range(20):
+        t0 = time.perf_counter()
+        x.wall_exchange_m()
+        calls.append((time.perf_counter() - t0) * 1e3)
+    out = {"metric": "sedimentation channel (open table + rectangle) with a KBC fluid, D2Q9 f64", "size": [R, C], "steps": a.steps,
+           "repeats": a.repeats, "s2": s2, "open_table_nodes": channel.count(), "iwalls_table_nodes": body.count(),
+           "ms_per_step": ms, "launches_per_step": per_step, "nonfinite_after": nonfinite,
+           "kbc_channel_over_kbc_plain": [round(p / q, 4) for p, q in zip(ms["kbc_channel"], ms["kbc_plain"])],
+           "kbc_channel_over_bgk_channel": [round(p / q, 4) for p, q in zip(ms["kbc_channel"], ms["bgk_channel"])],
+           "wall_exchange_m_ms": {"median": round(statistics.median(calls), 4), "min": round(min(calls), 4), "calls": len(calls)},
+           "wall_exchange_values": dict(zip(pylbm.WALLX_NAMES, values.tolist()))}
+    for sv in solvers.values():
+        sv.close()
+    channel.close()
+    body.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=8192)
@@ -235,7 +308,7 @@ def main():
     u[1] = 0.02 * torch.sin(2 * math.pi * r / R)
     del r, c
     if a.kbc:
-        out = kbc_bench(lib, a, rho, conc, u, st, timed)
+        out = (kbc_open_bench if a.open else kbc_bench)(lib, a, rho, conc, u, st, timed)
         lib.event_destroy(e0)
         lib.event_destroy(e1)
         lib.stream_destroy(st)
